@@ -1,15 +1,28 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path: GP.Observe + GP.Gradient evaluations per second.
 
-    python bench.py --gpus N --steps K --warmup W [--config C]
+    python bench.py --gpus N --steps K --warmup W [--config C] [--full] [--dump-outputs DIR]
+
+A plain run sets up, runs W warm-up steps, times K steps and prints the line: `metric`, `value`,
+`unit`, `higher_is_better`, `dtype`, `ms_per_step` (wall time of one timed step), `lml` and the
+`roofline` / `hbm_bound_kernels` figures that the timed steps' own HIP events give.  Everything that
+takes runs of its own -- the CPU baseline and oracle parity, the calibrated MFMA peak, Produce, the
+L-BFGS loop, the PCIe-inclusive, single-candidate, concurrent-candidate, hipGraph-replay, mixed-precision
+and 1 x 1 sharded figures, and on N > 1 the transport pre-flight and the extra sharded evaluation of the
+replica configurations -- runs only with --full.
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step returned to its
+caller as float64 arrays: DIR/lml.npy (candidates_per_step,) and DIR/grad.npy (candidates_per_step x P).
+The inputs and the thetas of every step depend only on the arguments, so two builds can be compared
+output for output.
 
 N > 1 runs one rank per GPU.  Started WITHOUT a launcher (no WORLD_SIZE in the environment) this
 process starts `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1
 ... bench.py <same arguments>` as a CHILD -- before it has touched the GPU itself -- and relays the one
 JSON line and the exit code.  Started by a launcher it checks WORLD_SIZE == N and refuses (exit 2) on a
-mismatch: a run never silently degrades to one rank.  Every N > 1 run begins with a pre-flight of the
-transport (process group, communicator, one grouped send/recv ring, one all-reduce), each phase under a
-30 s watchdog that names rank and phase and exits non-zero.
+mismatch: a run never silently degrades to one rank.  The pre-flight of the transport (process group,
+communicator, one grouped send/recv ring, one all-reduce) runs each phase under a 30 s watchdog that
+names rank and phase and exits non-zero (configs 1-3: the process group always, the rest with --full).
 
 One "step" = one hyperparameters-only Observe(log theta) (Gram build + blocked
 Cholesky + forward solve + LML) followed by Gradient() (triangular inverse,
@@ -23,7 +36,7 @@ N=16384, D=8, fp64, one MI355X).
 N > 1:
   * configs 1-3 (one evaluation fits and is quoted on ONE GPU): every GPU evaluates its
     own hyperparameter candidate on the full data -- weak scaling, no data-path
-    collective; `value` is the replica throughput.  AFTER that measurement the transport
+    collective; `value` is the replica throughput.  With --full, AFTER that measurement the transport
     of the sharded evaluation is pre-flighted (communicator, send/recv ring, all-reduce,
     a first sharded evaluation at N = 64: `preflight`, `rccl_ranks`) and ONE evaluation
     sharded over all ranks is timed and reported as `sharded_evaluation`; a phase of these
@@ -31,12 +44,13 @@ N > 1:
     measurement does not depend on the library's communicator;
   * configs 4-5 (BASELINE quotes them as ONE evaluation over all GPUs): `value` is the
     throughput of the 2-D block-cyclic sharded evaluation (strong scaling); the pre-flight
-    runs first, each phase under a watchdog that ends the run non-zero with rank and phase.
+    runs first, each phase under a watchdog that ends the run non-zero with rank and phase
+    (with --full, the L-BFGS loop over the shards and the agreement with one GPU follow).
 
 Prints ONE JSON line on rank 0 (contract in the task description), including
   "roofline":     the dominant kernel (fp64 MFMA GEMM/SYRK tile kernel), HIP-event
                   timed on the streams it is launched on during the timed region;
-  "cpu_baseline": the CPU oracle's numpy/scipy twin ("port") timed on the host cores, at
+  "cpu_baseline": (--full) the CPU oracle's numpy/scipy twin ("port") timed on the host cores, at
                   the FULL size of the workload when N <= 16384 (so that the LML /
                   gradient / mu / sigma errors are measured on the metric's own
                   configuration), on a bounded sample otherwise.
@@ -228,6 +242,13 @@ def pmc_traffic(config, build_id):
     return e, None
 
 
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, float64 (what the timed path returned in its last step)."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def launch_ranks(ngpus, argv):
     """`--gpus N` without a launcher: one rank per GPU through torch.distributed.run, started as a child
     process BEFORE this process makes any GPU call (a process that has initialised the GPU must not
@@ -333,7 +354,8 @@ def stub_rank_body(args, rank, world, json_out):
         seen = int(t.item())
     if rank == 0:
         print(json.dumps({"stub": True, "n_gpus": world, "ranks_seen": seen, "gpus_arg": args.gpus,
-                          "config": args.config, "steps": args.steps, "nobs": args.nobs}),
+                          "config": args.config, "steps": args.steps, "nobs": args.nobs, "full": args.full,
+                          "dump_outputs": args.dump_outputs}),
               file=json_out, flush=True)
     if world > 1:
         dist.barrier()
@@ -352,13 +374,18 @@ def main():
     ap.add_argument("--config", type=int, default=3, choices=[1, 2, 3, 4, 5])
     ap.add_argument("--nobs", type=int, default=None)
     ap.add_argument("--ndim", type=int, default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beside the headline figure (CPU baseline and oracle parity, "
+                         "calibrated peak, Produce, L-BFGS loop, PCIe, candidate and sharded variants)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's LML and gradient as DIR/lml.npy, DIR/grad.npy (float64)")
     ap.add_argument("--cpu-sample-n", type=int, default=8192,
-                    help="CPU baseline sample when the full workload is too large for the oracle")
+                    help="--full: CPU baseline sample when the full workload is too large for the oracle")
     ap.add_argument("--no-produce", action="store_true",
-                    help="skip the secondary Produce measurement (profiling runs)")
+                    help="--full: skip the secondary Produce measurement (profiling runs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--candidates", type=int, default=4,
-                    help="N <= 8192: also time this many candidates evaluated concurrently")
+                    help="--full, N <= 8192: also time this many candidates evaluated concurrently")
     ap.add_argument("--candidates-per-step", type=int, default=None,
                     help="candidate thetas evaluated per step in ONE launch sequence "
                          "(gogp_observe_gradient_candidates); default 8 for configs 1 and 2 (N <= 4096: one "
@@ -367,8 +394,8 @@ def main():
                     help="gogp_set_option on the benchmarked handle (A/B runs), e.g. superpanel=3")
     ap.add_argument("--no-sharded", action="store_true")
     ap.add_argument("--sharded", action="store_true",
-                    help="--gpus 1: also time the SHARDED code path (dist2d.hip) on a 1x1 grid over the RCCL transport "
-                         "and report it beside the fused sweep as `sharded_1x1` (default for configs 4 and 5)")
+                    help="--full --gpus 1: also time the SHARDED code path (dist2d.hip) on a 1x1 grid over the RCCL "
+                         "transport and report it beside the fused sweep as `sharded_1x1` (default for configs 4 and 5)")
     ap.add_argument("--sharded-timeout", type=int, default=300)
     ap.add_argument("--preflight-timeout", type=int, default=30,
                     help="seconds per pre-flight phase of an N > 1 run before the watchdog ends it")
@@ -376,6 +403,8 @@ def main():
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if (args.steps is not None and args.steps < 1) or (args.warmup is not None and args.warmup < 0):
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # no launcher around us: start the N ranks ourselves, as a child, before any GPU call
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -499,11 +528,13 @@ def main():
         dy = torch.from_numpy(y).to("cuda")
         torch.cuda.synchronize()
         g.set_data_device(dX.data_ptr(), dy.data_ptr(), N)
+        last = {}  # cps > 1: every candidate's LML and gradient of the latest step (--dump-outputs)
 
         def step(k):
             if cps > 1:  # cps candidate thetas in one launch sequence
                 xs = np.array([wl.log_theta(k * cps + i, rank) for i in range(cps)])
                 lmls, grads, _ = g.observe_gradient_candidates(xs)
+                last["lml"], last["grad"] = lmls, grads
                 return float(lmls[-1]), grads[-1]
             lml = g.Observe(wl.log_theta(k, rank))
             grad = g.Gradient()
@@ -518,6 +549,8 @@ def main():
             lml, grad = step(warmup + k)
         sync()
         dt = time.perf_counter() - t0
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, dict(last) if cps > 1 else {"lml": [lml], "grad": grad[None, :]})
         gemm_ms, gemm_launches, gemm_flops, gemm_busy_ms = g.profile_read()
         gram_ms, gram_n = g.profile_read_aux(0)
         grad_ms, grad_n = g.profile_read_aux(1)
@@ -549,6 +582,8 @@ def main():
             lml, grad = step(warmup + k)
         sync()
         dt = time.perf_counter() - t0
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, {"lml": [lml], "grad": grad[None, :]})
         gemm_ms, gemm_launches, gemm_flops, gemm_busy_ms = sg.profile_read()
         gram_ms = gram_n = grad_ms = grad_n = 0
         sg.profile_enable(False)
@@ -557,7 +592,7 @@ def main():
         par_text = "ONE evaluation sharded 2-D block-cyclically over a %s grid of GPUs (%s)" % (
             sg.grid_text(), sg.transport_text())
         scaling = "strong"
-        if not args.no_produce:
+        if args.full and not args.no_produce:
             # configs[4]: "LML+grad inside L-BFGS hyperparameter loop" -- the optimiser over the SHARDED
             # handle: every rank runs the same (deterministic) iteration on the same all-reduced LML and
             # gradient, so the ranks stay in step without any extra exchange
@@ -596,9 +631,11 @@ def main():
         # 0's and the algorithmic work per rank is N^3 / world.
         per_rank = algo_flops_step / (world if sharded_value else 1)
         achieved = (per_rank * steps / (gemm_busy_ms * 1e-3) / 1e12 if gemm_busy_ms > 0 else 0.0)
+        peak_cal = peak_cal32 = None  # a microbenchmark of its own: --full only
         try:
-            peak_cal = G.mfma_f64_peak(20000, local_rank) if prec == 64 else None
-            peak_cal32 = G.mfma_f32_peak(20000, local_rank) if prec == 32 else None
+            if args.full:
+                peak_cal = G.mfma_f64_peak(20000, local_rank) if prec == 64 else None
+                peak_cal32 = G.mfma_f32_peak(20000, local_rank) if prec == 32 else None
         except Exception:
             peak_cal = peak_cal32 = None
         out = {
@@ -625,10 +662,11 @@ def main():
             "lml": lml,
             # N > 1: did the transport of the sharded evaluation come up (communicator, send/recv ring, all-reduce,
             # a first sharded evaluation)?  One boolean a driver can read without parsing `preflight`; rccl_ranks is
-            # ncclCommCount, 0 (never null) when RCCL did not carry the run.  N = 1: no transport, both absent.
+            # ncclCommCount, 0 (never null) when RCCL did not carry the run.  N = 1, or a replica configuration
+            # without --full (no pre-flight): both absent.
             **({"transport_ok": bool(preflight and "error" not in preflight),
                 "rccl_ranks": int(preflight["comm_ranks"]) if preflight and preflight.get("rccl") else 0}
-               if world > 1 else {}),
+               if world > 1 and (sharded_value or args.full) else {}),
             "preflight": preflight,
             "roofline": {
                 "bound": "mfma",
@@ -655,7 +693,7 @@ def main():
                         "avg_launch_ms x launches_per_step); frac_wall = the same flop / wall time per "
                         "step (a lower bound that needs no event arithmetic); peak = 78.6 TFLOP/s fp64 spec "
                         "(157.3 fp32 matrix); peak_calibrated = sustained v_mfma_f64 (fp32 path: v_mfma_f32_32x32x2) "
-                        "issue-rate microbenchmark on this device",
+                        "issue-rate microbenchmark on this device (--full only)",
             },
         }
         version = G._lib.lib().gogp_version().decode()
@@ -684,7 +722,7 @@ def main():
                 "note": "8 B (fp64 path; 4 B with precision = 32) per lower-triangle element written (Gram; the part built on the main "
                         "stream) / read (K^-1 in the fused gradient reduction); HIP events on the "
                         "kernel's stream"}
-        if cps > 1 and N <= 1024:
+        if args.full and cps > 1 and N <= 1024:
             # up to N = 1024 the candidates' launch sequence is replayed from a captured hipGraph --
             # except while the tile kernel's launches carry profiling events, as in the timed region
             # above: the same steps again without instrumentation
@@ -699,7 +737,7 @@ def main():
                 "evals_per_s": steps * cps / tg, "ms_per_step": tg / steps * 1e3,
                 "note": "the timed steps repeated with profiling events off: the launch sequence of a step "
                         "is one captured hipGraph (linear; N <= 1024)"}
-        if cps > 1 and 1024 < N <= 8192:
+        if args.full and cps > 1 and 1024 < N <= 8192:
             # the same steps replayed from an EXPLICITLY built hipGraph (option graph = 2: one node per launch / copy,
             # the sweep's cross-stream dependencies as edges, no stream capture -- graphrec.h).  Reported, not used for
             # `value`: this runtime executes the graph's parallel branches no faster than their serialisation.
@@ -720,7 +758,7 @@ def main():
                 "bit_identical_to_stream_path": bool(ref_l == got_l and np.array_equal(ref_g, got_g)),
                 "note": "explicitly built hipGraph of one step (hipGraphAddKernelNode / MemcpyNode / MemsetNode with "
                         "explicit dependencies); `value` above is the stream path, which is faster on this runtime"}
-        if cps > 1:
+        if args.full and cps > 1:
             # the same workload one candidate at a time (the latency-bound chain `value` amortises)
             g.Observe(wl.log_theta(0)); g.Gradient()
             torch.cuda.synchronize()
@@ -736,7 +774,7 @@ def main():
                 "note": "Observe + Gradient one theta at a time on the same handle (what a strictly "
                         "sequential optimiser sees); `value` evaluates candidates_per_step thetas per "
                         "launch sequence"}
-        if world == 1 and N <= 8192 and args.candidates > 1:
+        if args.full and world == 1 and N <= 8192 and args.candidates > 1:
             # below N ~ 8192 one evaluation is a chain of small dependent launches: k candidates
             # evaluated at once (gogp_observe_gradient_batch; the reference's optimiser can do the
             # same, optimize.Settings.Concurrent, tutorial/tutorial.go:141) overlap their chains
@@ -761,7 +799,7 @@ def main():
                         "one-launch-sequence form"}
             for gg in gps[1:]:
                 gg.close()
-        if world == 1 and prec == 64 and cps == 1 and N >= 4096 and g is not None and not args.no_produce:
+        if args.full and world == 1 and prec == 64 and cps == 1 and N >= 4096 and g is not None and not args.no_produce:
             # beyond the native-fp64 roof with LML / mu / sigma untouched -- "compute only the
             # gradient's K^-1 in fp32 MFMA".  Option gradient_precision = 32: fp64 factorisation, LML, alpha, Produce;
             # Y = L^-T and K^-1 = Y Y^T on the fp32 tile kernel.  Reported beside `value`, never as it.
@@ -784,7 +822,7 @@ def main():
                         "Produce, the triangular inverse and K^-1 = Y Y^T in fp32 from a float copy of the fp64 factor, "
                         "trace and output-scale components of the gradient from closed forms; the reference checks "
                         "its gradient to 1e-4 (gp_test.go:170,248)"}
-        if world == 1 and not args.no_produce and g is not None:
+        if args.full and world == 1 and not args.no_produce and g is not None:
             # configs[4] words the workload as "LML+grad inside L-BFGS hyperparameter loop": a few major
             # iterations of the optimiser on this handle (gogp_amd/optimize.py) -- the same
             # evaluations, now chosen by the line search
@@ -803,7 +841,7 @@ def main():
                             "when accepted) on the resident data"}
             except Exception as e:  # noqa: BLE001
                 out["lbfgs_loop"] = {"error": repr(e)[:200]}
-        if world == 1 and not args.no_produce and g is not None and N <= 40000:
+        if args.full and world == 1 and not args.no_produce and g is not None and N <= 40000:
             # the boundary's host-buffer form (gogp_set_data: X, y from host memory): the same
             # evaluation with the inputs re-sent over PCIe every step -- never `value`
             reps = 3 if N > 6000 else 10
@@ -821,7 +859,7 @@ def main():
                         "(gogp_set_data drains the streams and copies synchronously), one candidate at a time"}
             g.set_data_device(dX.data_ptr(), dy.data_ptr(), N)
             g.Observe(wl.log_theta(0))  # new data invalidate the factorisation: Produce below needs one
-        if world == 1 and g is not None and (args.sharded or (wl.sharded and not args.no_sharded)) and cps == 1:
+        if args.full and world == 1 and g is not None and (args.sharded or (wl.sharded and not args.no_sharded)) and cps == 1:
             # the code path configs[3] / configs[4] run on 8 GPUs, on the one GPU there is: a 1x1 grid of the 2-D
             # block-cyclic sweep over the RCCL transport (one rank: communicator, all-reduces, every launch and filter of
             # dist2d.hip) beside the fused single-GPU sweep -- its per-rank efficiency
@@ -848,7 +886,7 @@ def main():
                 s11.close()
             except Exception as e:  # noqa: BLE001
                 out["sharded_1x1"] = {"error": repr(e)[:300]}
-        if world == 1 and not args.no_produce and g is not None:
+        if args.full and world == 1 and not args.no_produce and g is not None:
             # secondary metric: Produce throughput at the same N, M = 1024 fresh
             # test points per call, host Z in / host mu, sigma out -- outside the timed region
             M = 1024 if N >= 1024 else 16
@@ -919,7 +957,7 @@ def main():
 
     # ---- N > 1, replica configs: the transport's pre-flight, then ONE evaluation sharded over all ranks --
     sharded = None
-    if world > 1 and not sharded_value:
+    if world > 1 and not sharded_value and args.full:
         pw.soft = True
         try:
             preflight = run_preflight()
@@ -929,7 +967,7 @@ def main():
             out["preflight"] = preflight
             out["transport_ok"] = "error" not in preflight
             out["rccl_ranks"] = int(preflight["comm_ranks"]) if preflight.get("rccl") else 0
-    if world > 1 and not sharded_value and not args.no_sharded and "error" not in preflight:
+    if world > 1 and not sharded_value and args.full and not args.no_sharded and "error" not in preflight:
         try:
             from gogp_amd.sharded import ShardedGP
             sg = ShardedGP(D, simil, noise, X=X, Y=y, device=local_rank)
@@ -959,7 +997,7 @@ def main():
         # agreement of the sharded evaluation with ONE GPU running the same evaluation alone
         try:
             kk = warmup + steps - 1
-            if rank == 0:
+            if rank == 0 and args.full:
                 g1 = G.GP(D, simil, noise, X=X, Y=y, device=local_rank, precision=prec)
                 lml_1 = g1.Observe(wl.log_theta(kk))
                 grad_1 = g1.Gradient()
@@ -982,7 +1020,7 @@ def main():
             out["sharded_evaluation"] = sharded
             if "error" in sharded and world > 1:
                 out["transport_ok"] = False  # the transport came up but the sharded evaluation over it failed
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             def gpu_fn(Xs, ys, x, Z):
                 if len(ys) == N and g is not None:
                     g2 = g  # the full workload is already resident

@@ -49,6 +49,20 @@ def test_one_gpu_runs_in_process():
     assert d["n_gpus"] == 1 and d["ranks_seen"] == 1 and d["config"] == 1
 
 
+def test_full_and_dump_outputs_reach_every_rank(tmp_path):
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--config", "2", "--steps", "3", "--full",
+                        "--dump-outputs", str(tmp_path)],
+                       env=_env(GOGP_BENCH_STUB="1"), capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = _one_line(r.stdout)
+    assert d["ranks_seen"] == 2 and d["full"] is True and d["dump_outputs"] == str(tmp_path) and d["steps"] == 3
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "1"], env=_env(GOGP_BENCH_STUB="1"),
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = _one_line(r.stdout)
+    assert d["full"] is False and d["dump_outputs"] is None  # a plain run is the default
+
+
 def test_a_failing_rank_fails_the_run():
     r = subprocess.run([sys.executable, BENCH, "--gpus", "2"],
                        env=_env(GOGP_BENCH_STUB="1", GOGP_BENCH_STUB_EXIT="7", GOGP_BENCH_STUB_EXIT_RANK="1"),
@@ -88,7 +102,7 @@ def test_bench_two_ranks_as_the_driver_runs_it():
     replica evaluations and ONE evaluation sharded over both ranks.  The two ranks share the box's one
     GPU, hence the gloo process group and the host-callback transport."""
     r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--config", "2", "--nobs", "512", "--steps", "2",
-                        "--no-cpu-baseline"],
+                        "--no-cpu-baseline", "--full"],
                        env=_env(GOGP_DIST_BACKEND="gloo"), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _one_line(r.stdout)
@@ -107,7 +121,7 @@ def test_bench_sharded_config_runs_the_optimiser_over_the_shards():
     """configs[4] ("LML+grad inside L-BFGS hyperparameter loop") at a rehearsal size on two gloo ranks:
     `value` is the sharded evaluation and the line carries the optimiser loop over the sharded handle."""
     r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--config", "5", "--nobs", "1024", "--ndim", "8",
-                        "--steps", "2", "--warmup", "1"],
+                        "--steps", "2", "--warmup", "1", "--full"],
                        env=_env(GOGP_DIST_BACKEND="gloo"), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _one_line(r.stdout)
@@ -116,6 +130,60 @@ def test_bench_sharded_config_runs_the_optimiser_over_the_shards():
     assert "error" not in lb, lb
     assert lb["evaluations"] >= 2 and lb["lml_end"] >= lb["lml_start"]
     assert d["sharded_evaluation"]["lml_rel_diff_vs_single_gpu"] < 1e-4
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_the_last_timed_step(tmp_path):
+    """A plain one-GPU run carries the contract fields and none of the measurements that take runs of their own
+    (those need --full); --dump-outputs holds every candidate's LML and gradient of the LAST timed step, which the CPU
+    oracle reproduces from the same inputs and thetas."""
+    import numpy as np
+    steps, warmup = 3, 1
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--config", "2", "--nobs", "512", "--steps", str(steps),
+                        "--warmup", str(warmup), "--dump-outputs", str(tmp_path / "out")],
+                       env=_env(), capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = _one_line(r.stdout)
+    assert d["unit"] == "evals/s" and d["higher_is_better"] is True and d["dtype"] == "f64" and "N=512" in d["metric"]
+    assert d["steps"] == steps and d["warmup"] == warmup
+    cps = d["config"]["candidates_per_step"]
+    assert cps == 8 and abs(d["value"] - cps * 1e3 / d["ms_per_step"]) < 1e-9 * d["value"]
+    for k in ("cpu_baseline", "parity_vs_oracle", "produce", "lbfgs_loop", "pcie_inclusive", "single_candidate",
+              "concurrent_candidates", "hipgraph_replay", "sharded_1x1"):
+        assert k not in d, k
+    assert d["roofline"]["peak_calibrated_mfma_f64"] is None
+    lml = np.load(str(tmp_path / "out" / "lml.npy"))
+    grad = np.load(str(tmp_path / "out" / "grad.npy"))
+    assert lml.dtype == grad.dtype == np.float64 and lml.shape == (cps,) and grad.shape == (cps, 3)
+    assert lml[-1] == d["lml"]
+    from gogp_amd import configs
+    from oracle.oracle import FastOracle
+    wl = configs.workload(2, 512)
+    X, y = wl.inputs()
+    o = FastOracle(wl.D, wl.simil, wl.noise)
+    o.set_data(X, y)
+    k = warmup + steps - 1  # bench.py's step index of the last timed step
+    for c in range(cps):
+        lo = o.Observe(wl.log_theta(k * cps + c))
+        go = o.Gradient()
+        assert abs(lml[c] - lo) <= 1e-9 * abs(lo), (c, lml[c], lo)
+        assert np.abs(grad[c] - go).max() <= 1e-7 * max(1.0, np.abs(go).max()), (c, grad[c], go)
+
+
+@pytest.mark.gpu
+def test_full_run_keeps_the_secondary_measurements():
+    """--full: the measurements beside the headline figure are still there (CPU baseline and oracle parity, Produce,
+    the optimiser loop, the one-candidate and hipGraph-replay figures)."""
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--config", "2", "--nobs", "512", "--steps", "2",
+                        "--warmup", "1", "--full"],
+                       env=_env(), capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = _one_line(r.stdout)
+    for k in ("cpu_baseline", "produce", "lbfgs_loop", "pcie_inclusive", "single_candidate", "concurrent_candidates",
+              "hipgraph_replay"):
+        assert k in d and "error" not in d[k], (k, d.get(k))
+    assert d["lml_rel_err_vs_oracle"] < 1e-9 and d["grad_rel_err_vs_oracle"] < 1e-7
+    assert d["roofline"]["peak_calibrated_mfma_f64"] is not None
 
 
 def test_phase_watchdog_names_rank_and_phase_and_exits_nonzero(tmp_path):

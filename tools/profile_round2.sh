@@ -6,9 +6,9 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/prof_r2
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 FAST="--no-cpu-baseline --no-produce --candidates 1"
-python3 $R/bench.py > $O/bench_c3.json 2> $O/bench_c3.err
+python3 $R/bench.py --full > $O/bench_c3.json 2> $O/bench_c3.err
 echo "bench c3 done"
-for c in 1 2 4 5; do python3 $R/bench.py --config $c > $O/bench_c$c.json 2> $O/bench_c$c.err; echo "bench c$c done"; done
+for c in 1 2 4 5; do python3 $R/bench.py --full --config $c > $O/bench_c$c.json 2> $O/bench_c$c.err; echo "bench c$c done"; done
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_c3 -- python3 $R/bench.py --steps 5 --warmup 1 $FAST > $O/stats_c3.log 2>&1
 echo "stats c3 done"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_c2 -- python3 $R/bench.py --config 2 --candidates-per-step 1 --steps 20 --warmup 2 $FAST > $O/stats_c2.log 2>&1

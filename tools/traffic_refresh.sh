@@ -22,7 +22,7 @@ json.dump(d, open("$O/pmc_traffic.json", "w"), indent=1)
 json.dump(d, open("$R/profiles/r04_pmc_traffic.json", "w"), indent=1)
 print(v)
 PY
-python3 bench.py > $O/bench_c3_final.json 2> $O/bench_c3_final.err
+python3 bench.py --full > $O/bench_c3_final.json 2> $O/bench_c3_final.err
 find $O -name "*counter_collection.csv" -size +6M -delete
 find $O -name "*kernel_trace.csv" -size +6M -delete
 find $O -name "*.db" -delete
