@@ -608,3 +608,30 @@ void gogp_oracle_grad_reduce_omp(const gogp_desc *d, const double *theta_s, cons
     for (int p = 0; p <= ns; p++) out[p] += (p < ns ? 0.5 : 1.0) * acc[p];
   }
 }
+
+/* gx (n x ndim) : gx[i][d] = sum_{j != i} W_ij dk(x_i, x_j)/dx_{i,d},  W = alpha alpha^T - Kinv
+ * (Kinv read from its lower triangle): the input part of the full-form gradient in the same
+ * W-matrix form.  gp/gp.go:118-129 adds dk/dx_i and dk/dx_j of every pair to the dense dK of
+ * coordinate (i, d), whose only non-zero row and column are i; 1/2 tr(W dK) is the sum above.
+ * The noise kernels do not depend on x.  OpenMP over rows, each row summed in column order. */
+void gogp_oracle_xgrad_omp(const gogp_desc *d, const double *theta_s, const double *X,
+                           const double *alpha, const double *Kinv, int64_t n, double *gx) {
+  int D = d->ndim, ns = d->ntheta_simil;
+#pragma omp parallel
+  {
+    double g[GOGP_MAX_TERMS * (GOGP_MAX_NDIM + 2) + 2 * GOGP_MAX_NDIM];
+    double acc[GOGP_MAX_NDIM];
+#pragma omp for schedule(dynamic, 16)
+    for (int64_t i = 0; i < n; i++) {
+      for (int q = 0; q < D; q++) acc[q] = 0.0;
+      for (int64_t j = 0; j < n; j++) {
+        if (j == i) continue;
+        double kij = j < i ? Kinv[i * n + j] : Kinv[j * n + i];
+        double w = alpha[i] * alpha[j] - kij;
+        gogp_oracle_simil(d, theta_s, X + i * D, X + j * D, g);
+        for (int q = 0; q < D; q++) acc[q] += w * g[ns + q];
+      }
+      for (int q = 0; q < D; q++) gx[i * D + q] = acc[q];
+    }
+  }
+}

@@ -87,6 +87,8 @@ def lib():
         L.gogp_oracle_cross_omp.argtypes = [descp, dp, dp, i64, dp, i64, dp]
         L.gogp_oracle_grad_reduce_omp.restype = None
         L.gogp_oracle_grad_reduce_omp.argtypes = [descp, dp, dp, dp, dp, i64, dp]
+        L.gogp_oracle_xgrad_omp.restype = None
+        L.gogp_oracle_xgrad_omp.argtypes = [descp, dp, dp, dp, dp, i64, dp]
         _lib = L
     return _lib
 
@@ -308,6 +310,57 @@ def gram_np(desc: CDesc, theta_s: np.ndarray, A: np.ndarray, B: np.ndarray,
     return (K, dK) if want_grad else K
 
 
+def xgrad_np(desc: CDesc, theta_s: np.ndarray, A: np.ndarray, B: np.ndarray, W: np.ndarray) -> np.ndarray:
+    """sum_j W_ij dk(A_i, B_j)/dA_{i,d} (nA x D): the input part of the full-form gradient for the rows A
+    against the inputs B, closed forms per primitive composed as in gram_np.  Differences are formed per
+    dimension; a pair with A_i == B_j (the diagonal, or a duplicate input) adds exact zeros (every
+    derivative carries the factor a_d - b_d or sign(a_d - b_d)), so W's diagonal needs no masking."""
+    D = desc.ndim
+    W = np.asarray(W, dtype=np.float64)
+    out = np.zeros((len(A), D))
+
+    def diff(j):
+        return A[:, j, None] - B[None, :, j]
+
+    for T in _terms(desc):
+        c = theta_s[T.scale_idx] if T.scale_idx >= 0 else 1.0
+        ls = np.array([theta_s[T.len_idx + (j if T.ard else 0)] for j in range(D)])
+        if T.kind == K_PERIODIC:
+            # k = c exp(-2 sum_d sin^2(phi_d) / l_d^2), phi_d = pi |a_d - b_d| / p
+            p = T.period_mult * theta_s[T.period_idx]
+            s2 = np.zeros(W.shape)
+            for j in range(D):
+                dd = np.sin((np.pi / p) * np.abs(diff(j))) / ls[j]
+                s2 += dd * dd
+            G = W * (c * np.exp(-2 * s2) * (-4.0 * np.pi / p))
+            for j in range(D):
+                u = diff(j)
+                phi = (np.pi / p) * np.abs(u)
+                out[:, j] += (G * (np.sin(phi) * np.cos(phi) * np.sign(u))).sum(1) / (ls[j] * ls[j])
+            continue
+        r2 = np.zeros(W.shape)
+        for j in range(D):
+            u = diff(j) / ls[j]
+            r2 += u * u
+        if T.kind == K_NORMAL:
+            dfdr2 = -0.5 * np.exp(-0.5 * r2)
+        else:
+            r = np.sqrt(r2)
+            if T.kind == K_MATERN32:
+                dfdr2 = -1.5 * np.exp(-SQRT3 * r)
+            elif T.kind == K_MATERN52:
+                dfdr2 = -0.5 * (3 + SQRT5 * r) * np.exp(-SQRT5 * r)
+            elif T.kind == K_MATERN52_TEXTBOOK:
+                dfdr2 = -(5.0 / 6.0) * (1 + SQRT5 * r) * np.exp(-SQRT5 * r)
+            else:
+                raise ValueError("kind")
+        # dk/da_d = c f'(r^2) 2 (a_d - b_d) / l_d^2
+        G = W * (2.0 * c * dfdr2)
+        for j in range(D):
+            out[:, j] += (G * diff(j)).sum(1) / (ls[j] * ls[j])
+    return out
+
+
 def potrf_blocked(K, nb=1024):
     """Lower Cholesky factor of the C-ordered matrix K, in place (the strict upper triangle is left as it
     was): right-looking blocked factorisation whose O(N^3) work is numpy matmul (threaded dgemm) on
@@ -365,7 +418,7 @@ def potri_blocked(L, nb=1024):
 
 
 class FastOracle:
-    """Restatement in the W-matrix form (hyperparameters-only Observe/Gradient,
+    """Restatement in the W-matrix form (Observe/Gradient in both forms of gp/gp.go:366-369,
     Absorb, Produce): LAPACK potrf/potri/potrs (scipy, OpenBLAS threads) for the
     O(N^3) parts; the O(N^2) pair loops either in C/OpenMP (``use_c=True``, the
     default: gogp_oracle_gram_omp / gogp_oracle_grad_reduce_omp) or in numpy
@@ -386,6 +439,8 @@ class FastOracle:
         self.Y = np.zeros((0,))
         self.Lc = None
         self.Alpha = None
+        #: the last Observe carried the inputs and outputs in x (gp.withObs, gp/gp.go:386)
+        self.with_obs = False
         #: seconds spent per phase since the last reset (bench.py's cpu_baseline reports them)
         self.timings = {}
 
@@ -442,6 +497,7 @@ class FastOracle:
 
     def Absorb(self, X, y, theta_simil, theta_noise=()):
         self.set_data(X, y)
+        self.with_obs = False
         self._factor(theta_simil, theta_noise)
 
     def LML(self) -> float:
@@ -452,17 +508,29 @@ class FastOracle:
                 - 0.5 * float(self.Y @ self.Alpha))
 
     def Observe(self, x) -> float:
-        x = _arr(x)
-        assert x.size == self.ns + self.nn, "FastOracle: hyperparameters-only form"
-        th = np.exp(x)
+        """x = log theta [| X.ravel() | y] as in gp/gp.go:366-373.  The full form takes X and y from x
+        (gp/gp.go:391-396) and makes Gradient() return the inputs' and outputs' parts as well."""
+        x = _arr(x).reshape(-1)
+        P = self.ns + self.nn
+        rest = x.size - P
+        n = rest // (self.ndim + 1) if rest > 0 else 0
+        if rest < 0 or n * (self.ndim + 1) != rest:
+            raise ValueError("len(x)")
+        self.with_obs = rest > 0
+        if self.with_obs:
+            self.set_data(x[P:P + n * self.ndim], x[P + n * self.ndim:])
+        th = np.exp(x[:P])
         self._factor(th[:self.ns], th[self.ns:])
         return self.LML()
 
     def Gradient(self) -> np.ndarray:
+        """Hyperparameter part, then with the full form (gp/gp.go:488-493) the inputs' part
+        gx[i, d] = sum_{j != i} W_ij dk(x_i, x_j)/dx_{i,d} (row-major) and the outputs' part -alpha."""
         import scipy.linalg as sla
         n = len(self.X)
         P = self.ns + self.nn
-        g = np.zeros(P)
+        full = self.with_obs
+        g = np.zeros(P + (n * (self.ndim + 1) if full else 0))
         if n == 0:
             return g
         # K^-1 from the factor (dpotri).  LAPACK is column-major: handed the C-ordered factor as its
@@ -488,6 +556,13 @@ class FastOracle:
             self._t("grad_reduce", t0)
             g[:self.ns] = out[:self.ns]
             trW = out[self.ns]
+            if full:
+                gx = np.zeros((n, self.ndim))
+                t0 = time.perf_counter()
+                lib().gogp_oracle_xgrad_omp(ctypes.byref(self.desc), _dp(self.ts), _dp(self.X), _dp(a),
+                                            _dp(Kinv), n, _dp(gx))
+                self._t("xgrad", t0)
+                g[P:P + n * self.ndim] = gx.reshape(-1)
         else:
             Kinv = np.tril(Kinv) + np.tril(Kinv, -1).T
             b = self.block
@@ -496,9 +571,14 @@ class FastOracle:
                 _, dK = gram_np(self.desc, self.ts, self.X[i0:i0 + b], self.X, want_grad=True)
                 for p in range(self.ns):
                     g[p] += 0.5 * float((W * dK[p]).sum())
+                if full:
+                    g[P + i0 * self.ndim:P + (i0 + len(W)) * self.ndim] = \
+                        xgrad_np(self.desc, self.ts, self.X[i0:i0 + b], self.X, W).reshape(-1)
             trW = float(a @ a) - float(np.trace(Kinv))
         if self.nn and self.desc.noise_kind == NOISE_UNIFORM:
             g[self.ns] = 0.5 * trW * 2.0 * self.desc.noise_scale * self.tn[0] ** 2
+        if full:
+            g[P + n * self.ndim:] = -self.Alpha
         return g  # NOISE_CONSTANT_PARAM: K does not depend on the parameter, component 0
 
     def Produce(self, Z):

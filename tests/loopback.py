@@ -34,12 +34,17 @@ class Loopback:
 
     def allreduce(self, rank, arr):
         self.log[rank].append(("allreduce", arr.nbytes))
+        # the parts are added in rank order, not in the threads' arrival order: the same inputs give the same
+        # sum bit for bit from one run to the next, as RCCL's fixed reduction order does
         with self.lock:
             if self.acc is None:
-                self.acc = np.zeros_like(arr)
-            self.acc += arr
+                self.acc = [None] * self.world
+            self.acc[rank] = arr.copy()
         self.barrier.wait(timeout=120)
-        arr[:] = self.acc
+        total = np.zeros_like(arr)
+        for part in self.acc:
+            total += part
+        arr[:] = total
         self.barrier.wait(timeout=120)
         if rank == 0:
             self.acc = None

@@ -1,0 +1,380 @@
+"""The full Observe form on the GPU (gp/gp.go:366-369): x = [log theta | X.ravel() | y], whose gradient is the
+hyperparameter part, dLML/dX (gp/gp.go:118-129: grad.hip, mirror_lower_kernel + xgrad_kernel<DMAX> over
+W = alpha alpha^T - K^-1) and dLML/dy = -alpha (gp/gp.go:488-493), against oracle.FastOracle's full form
+(pinned to the faithful oracle in tests/test_oracle_full_form.py).
+
+Every check compares the WHOLE gradient vector, part by part:
+  * LML                         1e-9 relative,
+  * hyperparameter part and gx  1e-7 * max(1, |part_ref|_inf)  (the ARD tests' bound against FastOracle),
+  * -alpha                      1e-7 * max(1, |alpha_ref|_inf).
+The shapes are chosen to leave the one-launch path (n > 128, or option tiny = 0), to end on a 64-column step
+that holds real rows (n = 1000, npad = 1024), and to run every xgrad_kernel instance (DMAX = 4, 8, 16, and 32 in
+one or two passes)."""
+import numpy as np
+import pytest
+
+from gogp_amd import kernel
+from cases import ANYNOISE, CASES
+
+pytestmark = pytest.mark.gpu
+
+FAMILIES = CASES + [ANYNOISE]
+#: a periodic kernel over several dimensions, one length scale each (sign and sincos per dimension)
+PERIODIC_ARD = ("periodic_ard3", 3, kernel.Scaled(kernel.ARD(kernel.Periodic, 3)), kernel.UniformNoise,
+                [1.0, 0.7, 0.8, 0.9, 0.45], [0.2])
+TOL = 1e-7
+#: default_noise: the reference's default noise variance of 1e-10 leaves cond(K) = 6.5e8 at n = 1000, and the LML
+#: follows K's rounding: the GPU measured 1.04e-9 from FastOracle there, two CPU restatements (LAPACK vs blocked
+#: potrf / potri) are 7.2e-10 apart.  Every other family stays below 3e-11.
+LML_TOL = {"default_noise": 1e-8}
+
+
+@pytest.fixture(scope="module")
+def gpmod():
+    from gogp_amd import gp
+    return gp
+
+
+def _data(rng, n, D):
+    X = rng.uniform(0, 1, (n, D))
+    y = np.sin(2 * np.pi * X).sum(1) / np.sqrt(D) + 0.1 * rng.normal(size=n)
+    return X, (y - y.mean()) / y.std()
+
+
+def _full_x(theta, X, y):
+    return np.concatenate([np.log(np.asarray(theta, dtype=float)), X.reshape(-1), y])
+
+
+def _reference(D, simil, noise, x):
+    from oracle.oracle import FastOracle
+    o = FastOracle(D, simil, noise)
+    lml = o.Observe(x)
+    return lml, o.Gradient()
+
+
+def _rel(a, b):
+    return float(np.abs(a - b).max() / max(1.0, np.abs(b).max())) if b.size else 0.0
+
+
+def _check(tag, P, D, lml, grad, lml_o, grad_o, tol=TOL, lml_tol=1e-9):
+    """The whole full-form gradient against the reference; returns the worst relative errors (printed: pytest -s
+    shows them)."""
+    n = (grad_o.size - P) // (D + 1)
+    assert grad.shape == grad_o.shape == (P + n * (D + 1),), (tag, grad.shape, grad_o.shape)
+    assert np.all(np.isfinite(grad)), tag
+    e = {"lml": abs(lml - lml_o) / abs(lml_o),
+         "theta": _rel(grad[:P], grad_o[:P]),
+         "gx": _rel(grad[P:P + n * D], grad_o[P:P + n * D]),
+         "alpha": _rel(grad[P + n * D:], grad_o[P + n * D:])}
+    print("ERR %s %s" % (tag, " ".join("%s=%.2e" % kv for kv in e.items())))
+    assert e["lml"] <= lml_tol, (tag, e)
+    assert e["theta"] <= tol, (tag, e)
+    assert e["gx"] <= tol, (tag, e, np.abs(grad - grad_o)[P:P + n * D].argmax())
+    assert e["alpha"] <= tol, (tag, e)
+    return e
+
+
+def _observe_check(gpmod, tag, D, simil, noise, theta, X, y, opts=(), ref=None, lml_tol=1e-9):
+    x = _full_x(theta, X, y)
+    lml_o, grad_o = ref if ref is not None else _reference(D, simil, noise, x)
+    g = gpmod.GP(D, simil, noise)
+    for k, v in dict(opts).items():
+        g.set_option(k, v)
+    lml = g.Observe(x)
+    grad = g.Gradient()
+    _check(tag, len(theta), D, lml, grad, lml_o, grad_o, lml_tol=lml_tol)
+    return g, x, grad
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# families x sizes
+# ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("n", [129, 300, 1000])
+@pytest.mark.parametrize("name,D,simil,noise,ts,tn", FAMILIES + [PERIODIC_ARD],
+                         ids=[c[0] for c in FAMILIES + [PERIODIC_ARD]])
+def test_full_form_families_general_path(gpmod, name, D, simil, noise, ts, tn, n):
+    """n = 129: the first size off the one-launch path; n = 300: several 64-row blocks, the last 64-column step
+    all padding (npad = 512); n = 1000: ragged, its last 64-column step holds real rows (npad = 1024)."""
+    X, y = _data(np.random.default_rng(n + 7 * D), n, D)
+    g, _, _ = _observe_check(gpmod, ("families", name, n), D, simil, noise, list(ts) + list(tn), X, y,
+                             lml_tol=LML_TOL.get(name, 1e-9))
+    g.close()
+
+
+@pytest.mark.parametrize("name,D,simil,noise,ts,tn", FAMILIES + [PERIODIC_ARD],
+                         ids=[c[0] for c in FAMILIES + [PERIODIC_ARD]])
+def test_full_form_families_tiny_off(gpmod, name, D, simil, noise, ts, tn):
+    """n = 100 with option tiny = 0: a size the one-launch path would take, through the general sweep."""
+    X, y = _data(np.random.default_rng(100 + D), 100, D)
+    g, _, _ = _observe_check(gpmod, ("tiny_off", name, 100), D, simil, noise, list(ts) + list(tn), X, y,
+                             opts={"tiny": 0}, lml_tol=LML_TOL.get(name, 1e-9))
+    g.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# every xgrad_kernel instance
+# ---------------------------------------------------------------------------------------------------------------
+def _ard(kind, D):
+    ell = list(np.sqrt(D / 6.0) * (1 + np.arange(D) / (2.0 * D)))
+    if kind == "ard_rbf":
+        return kernel.Scaled(kernel.ARD(kernel.Normal, D)), [1.1] + ell + [0.2]
+    if kind == "ard_matern52":
+        return kernel.Scaled(kernel.ARD(kernel.Matern52, D)), [1.1] + ell + [0.2]
+    # test_ard_gradient_many_dimensions_two_terms' kernel
+    simil = kernel.Sum([kernel.Scaled(kernel.ARD(kernel.Normal, D)), kernel.Scaled(kernel.Matern32)])
+    return simil, [1.1] + ell + [0.3, 1.5] + [0.2]
+
+
+@pytest.mark.parametrize("kind", ["ard_rbf", "ard_matern52", "ard_rbf+matern32"])
+@pytest.mark.parametrize("D", [4, 5, 8, 9, 16, 17, 32, 33, 64])
+def test_full_form_every_xgrad_instance(gpmod, D, kind):
+    """launch_xgrad: DMAX = 4 (D <= 4), 8 (5..8), 16 (9..16), 32 in one pass (17..32) and in two (33..64); each
+    instance at its first and last D, n = 700 (11 row blocks, the last one ragged)."""
+    simil, theta = _ard(kind, D)
+    assert simil.NTheta() + 1 == len(theta)
+    X, y = _data(np.random.default_rng(700 + D), 700, D)
+    g, _, _ = _observe_check(gpmod, ("instances", kind, D, 700), D, simil, kernel.UniformNoise, theta, X, y)
+    g.close()
+
+
+def test_full_form_max_ndim_many_row_blocks(gpmod):
+    """D = 64 at n = 4200: 99 KB of dynamic LDS (above the default 64 KB, raised explicitly), 66 row blocks, two
+    passes of 32 dimensions."""
+    D, n = 64, 4200
+    simil, theta = _ard("ard_rbf", D)
+    X, y = _data(np.random.default_rng(4264), n, D)
+    g, _, _ = _observe_check(gpmod, ("instances", "ard_rbf", D, n), D, simil, kernel.UniformNoise, theta, X, y)
+    g.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# how K^-1 reaches bufA
+# ---------------------------------------------------------------------------------------------------------------
+ROUTE_N, ROUTE_D = 2300, 5
+ROUTE_SIMIL = kernel.Scaled(kernel.ARD(kernel.Matern52, ROUTE_D))
+ROUTE_THETA = [1.1, 0.5, 0.6, 0.7, 0.8, 0.9, 0.2]
+
+
+@pytest.fixture(scope="module")
+def route_case():
+    X, y = _data(np.random.default_rng(2300), ROUTE_N, ROUTE_D)
+    x = _full_x(ROUTE_THETA, X, y)
+    return X, y, _reference(ROUTE_D, ROUTE_SIMIL, kernel.UniformNoise, x)
+
+
+@pytest.mark.parametrize("opts", [
+    {}, {"kinv_fused": 0}, {"kinv_fused": 1}, {"kinv_split": 50}, {"eager": 0}, {"lookahead": 0},
+    {"chain_split": 0}, {"chain_split": 1}, {"chain_split": 2}, {"superpanel": 1}, {"superpanel": 3},
+    {"krag": 0}, {"krag": 1},
+], ids=lambda o: ",".join("%s=%d" % kv for kv in o.items()) or "default")
+def test_full_form_kinv_routes(gpmod, route_case, opts):
+    """n = 2300 under every schedule option that changes how K^-1 is formed (fused rank-k updates, LAUUM, the
+    split inverse, the lazy / eager inverse, the diagonal-block chain, super-panels, the K^-1 tile order).
+    Gradient() twice after one Observe: the second call mirrors bufA's lower triangle again
+    (mirror_lower_kernel), which must change nothing -- bit-identical results."""
+    X, y, ref = route_case
+    g, x, grad = _observe_check(gpmod, ("routes", opts), ROUTE_D, ROUTE_SIMIL, kernel.UniformNoise, ROUTE_THETA,
+                                X, y, opts=opts, ref=ref)
+    np.testing.assert_array_equal(g.Gradient(), grad)
+    g.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the hyperparameter part is the hyperparameters-only form's gradient
+# ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("n", [100, 700])
+@pytest.mark.parametrize("name,D,simil,noise,ts,tn", FAMILIES + [PERIODIC_ARD],
+                         ids=[c[0] for c in FAMILIES + [PERIODIC_ARD]])
+def test_full_form_hyperparameter_part_is_the_hyperparameters_only_gradient(gpmod, name, D, simil, noise, ts,
+                                                                              tn, n):
+    """Same data and theta: the full form's first P components equal Gradient() of the hyperparameters-only form
+    bit for bit (the same factorisation and the same reduction over the same K^-1 -- the input part runs after it
+    and only writes bufA's upper triangle), on the one-launch path (n = 100) and the general one (n = 700)."""
+    X, y = _data(np.random.default_rng(n + D), n, D)
+    theta = list(ts) + list(tn)
+    P = len(theta)
+    a = gpmod.GP(D, simil, noise)
+    lml_a = a.Observe(_full_x(theta, X, y))
+    full = a.Gradient()
+    b = gpmod.GP(D, simil, noise, X=X, Y=y)
+    assert b.Observe(np.log(theta)) == lml_a
+    np.testing.assert_array_equal(b.Gradient(), full[:P])
+    # ... and on the full form's own handle, which keeps the data it took from x
+    assert a.Observe(np.log(theta)) == lml_a
+    np.testing.assert_array_equal(a.Gradient(), full[:P])
+    a.close()
+    b.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# state on one handle
+# ---------------------------------------------------------------------------------------------------------------
+def test_full_form_state_on_one_handle(gpmod):
+    """Full form at n1, then n2 < n1 and n3 > n1 (npad shrinks, then grows), the hyperparameters-only form (the
+    gradient's length drops back to P), the full form again; each step against the reference.  Then Absorb and
+    restore: Gradient() is a state error after each (gp/gp.go:85-86: no dK after Absorb)."""
+    from gogp_amd import _lib
+    from oracle.oracle import FastOracle
+    name, D, simil, noise, ts, tn = [c for c in CASES if c[0] == "matern52_ref"][0]
+    theta = list(ts) + list(tn)
+    P = len(theta)
+    rng = np.random.default_rng(31)
+    g = gpmod.GP(D, simil, noise)
+    for n in (700, 300, 1500):
+        X, y = _data(rng, n, D)
+        x = _full_x(theta, X, y)
+        lml_o, grad_o = _reference(D, simil, noise, x)
+        _check(("handle", name, n), P, D, g.Observe(x), g.Gradient(), lml_o, grad_o)
+    # hyperparameters only, on the data the last full-form call carried
+    o = FastOracle(D, simil, noise)
+    o.set_data(X, y)
+    lml_o = o.Observe(np.log(theta))
+    grad_o = o.Gradient()
+    lml = g.Observe(np.log(theta))
+    grad = g.Gradient()
+    assert grad.shape == (P,)
+    assert abs(lml - lml_o) <= 1e-9 * abs(lml_o)
+    assert _rel(grad, grad_o) <= TOL
+    X, y = _data(rng, 700, D)
+    x = _full_x(theta, X, y)
+    lml_o, grad_o = _reference(D, simil, noise, x)
+    _check(("handle", name, "again"), P, D, g.Observe(x), g.Gradient(), lml_o, grad_o)
+    # Absorb: no gradient
+    g.ThetaSimil, g.ThetaNoise = list(ts), list(tn)
+    g.Absorb(X, y)
+    assert abs(g.LML() - lml_o) <= 1e-9 * abs(lml_o)
+    with pytest.raises(gpmod.GogpError) as ei:
+        g.Gradient()
+    assert ei.value.code == _lib.GOGP_ESTATE
+    # full form again, then restore from the exported factor: no gradient either
+    _check(("handle", name, "after absorb"), P, D, g.Observe(x), g.Gradient(), lml_o, grad_o)
+    L, alpha = g.L, g.Alpha
+    g.restore(L, alpha)
+    with pytest.raises(gpmod.GogpError) as ei:
+        g.Gradient()
+    assert ei.value.code == _lib.GOGP_ESTATE
+    g.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# refusals
+# ---------------------------------------------------------------------------------------------------------------
+def test_full_form_refused_with_gradient_precision_32(gpmod):
+    """gradient_precision = 32 (K^-1 in fp32) does not offer the input gradient: Gradient() after a full-form
+    Observe fails through GogpError; the handle then still evaluates the hyperparameters-only form correctly
+    (within the mixed gradient's 1e-6 of test_mixed_precision_gradient_option), and the full form again once the
+    option is back at 64."""
+    from gogp_amd import _lib
+    from oracle.oracle import FastOracle
+    D, n = 3, 700
+    simil, noise = kernel.Scaled(kernel.Normal), kernel.UniformNoise
+    theta = [1.0, 0.7, 0.1]
+    X, y = _data(np.random.default_rng(32), n, D)
+    x = _full_x(theta, X, y)
+    lml_o, grad_o = _reference(D, simil, noise, x)
+    g = gpmod.GP(D, simil, noise)
+    g.set_option("gradient_precision", 32)
+    g.Observe(x)
+    with pytest.raises(gpmod.GogpError) as ei:
+        g.Gradient()
+    assert ei.value.code == _lib.GOGP_EARG
+    o = FastOracle(D, simil, noise)
+    o.set_data(X, y)
+    lml_h, grad_h = o.Observe(np.log(theta)), o.Gradient()
+    assert abs(g.Observe(np.log(theta)) - lml_h) <= 1e-9 * abs(lml_h)
+    assert np.abs(g.Gradient() - grad_h).max() <= 1e-6 * np.abs(grad_h).max()
+    g.set_option("gradient_precision", 64)
+    _check(("refusal", "gradient_precision back to 64"), 3, D, g.Observe(x), g.Gradient(), lml_o, grad_o)
+    g.close()
+
+
+def test_full_form_refused_on_a_sharded_handle(gpmod):
+    """A sharded evaluation (2 loopback ranks, as in tests/test_sharded.py) does not offer the input gradient:
+    every rank's Gradient() after a full-form Observe fails through GogpError, before any exchange; the ranks
+    then evaluate the hyperparameters-only form on the same data correctly."""
+    import loopback
+    from gogp_amd.sharded import ShardedGP
+    from oracle.oracle import FastOracle
+    D, n = 3, 700
+    simil, noise = kernel.Scaled(kernel.Matern52), kernel.UniformNoise
+    theta = [1.1, 0.5, 0.2]
+    X, y = _data(np.random.default_rng(62), n, D)
+    x = _full_x(theta, X, y)
+    o = FastOracle(D, simil, noise)
+    o.set_data(X, y)
+    lml_o, grad_o = o.Observe(np.log(theta)), o.Gradient()
+    grid = (1, 2)
+
+    def rank_fn(r, lb):
+        sh = ShardedGP(D, simil, noise, device=0, grid=grid, rank=r, world=2, exchange=lb.exchange,
+                       allreduce=lb.allreduce)
+        lml_full = sh.Observe(x)
+        with pytest.raises(gpmod.GogpError):
+            sh.Gradient()
+        lml = sh.Observe(np.log(theta))
+        grad = sh.Gradient()
+        sh.close()
+        return lml_full, lml, grad
+
+    outs, _ = loopback.run_ranks(2, rank_fn)
+    for lml_full, lml, grad in outs:
+        assert abs(lml_full - lml_o) <= 1e-9 * abs(lml_o)
+        assert abs(lml - lml_o) <= 1e-9 * abs(lml_o)
+        assert _rel(grad, grad_o) <= TOL
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# one large size: BASELINE config 3 (N = 16384, D = 8, RBF + uniform noise) in the full form
+# ---------------------------------------------------------------------------------------------------------------
+def test_full_form_config3_size(gpmod):
+    """The whole gx of 8 sampled rows i against the host: L downloaded once (2 GB), the rows of K^-1 by two
+    triangular solves, W_i = alpha_i alpha - K^-1_i and sum_j W_ij dk(x_i, x_j)/dx_i by the reference's closed
+    forms (oracle.xgrad_np).  -alpha against the same solves applied to y.  And a five-point central difference
+    of the LML along one random unit direction in input space against grad . v."""
+    import scipy.linalg as sla
+
+    from gogp_amd import synth
+    from oracle.oracle import xgrad_np
+    from gogp_amd.kernel import build_desc
+    N, D = 16384, 8
+    X, y = synth.make_inputs(N, D, 20251116)
+    simil, noise = kernel.Scaled(kernel.Normal), kernel.UniformNoise
+    th = synth.theta0(D)
+    P = 3
+    x = _full_x(th, X, y)
+    g = gpmod.GP(D, simil, noise)
+    lml = g.Observe(x)
+    grad = g.Gradient()
+    assert grad.shape == x.shape and np.all(np.isfinite(grad))
+    gx = grad[P:P + N * D].reshape(N, D)
+    U = g.L.T  # Fortran-ordered view: the upper factor U = L^T, no copy
+    rng = np.random.default_rng(3)
+    rows = np.concatenate([[0, N - 1], rng.choice(np.arange(1, N - 1), 6, replace=False)])
+    E = np.zeros((N, rows.size))
+    E[rows, np.arange(rows.size)] = 1.0
+    # K^-1 e_i = U^-1 U^-T e_i; alpha = U^-1 U^-T y
+    R = sla.solve_triangular(U, np.column_stack([E, y]), lower=False, trans="T", check_finite=False)
+    R = sla.solve_triangular(U, R, lower=False, check_finite=False)
+    kinv_rows, alpha = R[:, :rows.size].T, R[:, rows.size]
+    del U, R
+    W = np.outer(alpha[rows], alpha) - kinv_rows
+    want = xgrad_np(build_desc(D, simil, noise), th[:2], X[rows], X, W)
+    e_gx = _rel(gx[rows], want)
+    e_a = _rel(grad[P + N * D:], -alpha)
+    print("ERR config3 gx=%.2e alpha=%.2e" % (e_gx, e_a))
+    assert e_gx <= TOL, (e_gx, rows)
+    assert e_a <= TOL
+    v = np.zeros_like(x)
+    v[P:P + N * D] = rng.normal(size=N * D)
+    v /= np.linalg.norm(v)
+    # |LML| ~ 1e4: at h = 1e-3 the LML's rounding already shows (2e-6 on the CPU reference), at 1e-2 the
+    # five-point quotient agrees to 1e-7 there
+    h = 1e-2
+
+    def at(t):
+        return g.Observe(x + t * v)
+    fd = (8.0 * (at(h) - at(-h)) - (at(2 * h) - at(-2 * h))) / (12.0 * h)
+    print("ERR config3 directional fd=%.12e grad.v=%.12e" % (fd, grad @ v))
+    assert abs(fd - grad @ v) <= 1e-6 * max(1.0, abs(fd)), (fd, grad @ v)
+    assert np.isfinite(lml)
+    g.close()
