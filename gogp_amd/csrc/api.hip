@@ -162,7 +162,6 @@ struct StreamSet {
   bool in_use = false;
   hipStream_t s = nullptr, s2 = nullptr, sp = nullptr, st = nullptr, sl = nullptr, sk = nullptr;
   hipStream_t sg = nullptr;  // capture / replay stream of the candidates' hipGraph, created on first use
-  hipStream_t s2_low = nullptr, st_low = nullptr;  // option "inv_prio": low-priority twins, created on first use
 };
 static std::mutex g_pool_mutex;
 static std::vector<StreamSet *> g_stream_pool;
@@ -216,25 +215,6 @@ static hipError_t acquire_streams(gogp_handle *h, int device) {
   h->st = ss->st;
   h->sl = ss->sl;
   h->sk = ss->sk;
-  return hipSuccess;
-}
-
-// option "inv_prio": the streams of the triangular inverse at low priority (twins of s2 / st in the
-// handle's pooled set, created on first use)
-static hipError_t apply_inv_prio(gogp_handle *h) {
-  StreamSet *ss = static_cast<StreamSet *>(h->stream_set);
-  int least = 0, greatest = 0;
-  (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
-  if (h->inv_prio >= 1 && !ss->s2_low) {
-    const hipError_t e = hipStreamCreateWithPriority(&ss->s2_low, hipStreamNonBlocking, least);
-    if (e != hipSuccess) return e;
-  }
-  if (h->inv_prio >= 2 && !ss->st_low) {
-    const hipError_t e = hipStreamCreateWithPriority(&ss->st_low, hipStreamNonBlocking, least);
-    if (e != hipSuccess) return e;
-  }
-  h->s2 = h->inv_prio >= 1 ? ss->s2_low : ss->s2;
-  h->st = h->inv_prio >= 2 ? ss->st_low : ss->st;
   return hipSuccess;
 }
 
@@ -797,50 +777,22 @@ static void mixed_superstep(gogp_handle *h, int P0, int nsub, int prevP0, int ne
   }
 }
 
-// ---- option "chain_split" (fp64): the diagonal block in two halves, the products between them on the tile kernel -----
-// Measured (tools/wg_stamps.py, N = 4096): the 256-block kernel takes 130 us, sixteen of them are 2.09 of the 3.26 ms the
-// Cholesky chain of one evaluation lasts; 40 % of it are four 128^3 products on one compute unit.  Here the chain per
-// 256-panel is diag128 (half 0) -> L[c1:, c0:c1] = A[c1:, c0:c1] X00^T -> A[c1:, c1:c2] -= L[c1:, c0:c1] L[c1:c2, c0:c1]^T
-// -> diag128 (half 1) -> L[c2:, c1:c2] = A[c2:, c1:c2] X11^T: five short launches instead of two, each GEMM with K = 128.
-// -1 (default): on where the evaluation is latency-bound (npad <= 8192); beside the bulk updates of a large N every
-// chain launch costs its dispatch (wg_stamps: 80 of 144 us for a K = 256 panel solve at N = 16384), so more launches lose.
-// Measured (tools/split_probe.py): Observe + Gradient N = 1024 0.89 -> 0.84 ms, 2048 1.65 -> 1.46, 4096 3.50 -> 3.25, 8192
-// 12.2 -> 12.2, 16384 72.2 -> 73.0; the Cholesky alone (eager = 0) 4096 3.28 -> 2.72, 8192 8.2 -> 7.3, 16384 33.3 -> 31.9:
-// so also on at any size when no inverse runs beside the factorisation (Absorb, eager = 0).  (Not for the mixed gradient
-// above that size: its LML is promised to be the native path's bit for bit.)
-// 2: the chain per 128 columns is ONE launch (panel128.hip: every workgroup factors the diagonal 128-block redundantly
-// and forward-substitutes its own 64 panel rows on the way: no block inverse and no solve launch on the chain); the
-// 256 x 256 block inverses are formed off the chain from the finished factor (dinv_blocks below).
-// Above that size, beside the inverse, the choice CAN be made super-panel by super-panel: form 2 once at most `chain_tail`
-// rows (option) remain below the super-panel's first column, where the bulk updates are small and a launch has few
-// workgroups to repeat the diagonal block in.  Measured (tools/tail_probe.py, N = 16384, alternating on one box): tail 0 /
-// 2048 / 4096 / 6144 / 8192 rows: 71.0 / 71.2 / 72.2 / 72.2 / 72.8 ms; N = 32768: 542.4 / - / 543.5 / - / 545.3 -- the
-// evaluation's tail is not waiting for the Cholesky chain (the inverse's chain runs beside it and fills what it leaves):
-// default 0, off.
-static inline int chain_split_of(const gogp_handle *h, bool eager, int64_t C0) {
+// ---- option "chain_split" (fp64): the form of the Cholesky chain per 256-panel ----------------------------------------
+// 0: the 256-block kernel factors and inverts the diagonal block on one compute unit, then a K = 256 panel solve on the
+// tile kernel.  2: the chain per 128 columns is ONE launch (panel128.hip: every workgroup factors the diagonal 128-block
+// redundantly and forward-substitutes its own 64 panel rows on the way: no block inverse and no solve launch on the
+// chain); the 256 x 256 block inverses are formed off the chain from the finished factor (dinv_blocks below).
+// -1 (default): 2 where the evaluation is latency-bound (npad <= 8192) and wherever no inverse runs beside the
+// factorisation (Absorb, eager = 0); 0 above that size beside the inverse, where the GPU is throughput-bound and the
+// redundant factorisations of form 2 cost more than its shorter chain saves.  Measured (tools/split_probe.py, DESIGN.md
+// "The chain step in one launch"): Observe + Gradient 0 -> 2 N = 1024 0.89 -> 0.66 ms, 4096 3.48 -> 3.07, 16384 70.4 ->
+// 73.1; Observe only 4096 3.25 -> 2.46, 16384 32.9 -> 30.0.  (Not for the mixed gradient above that size: its LML is
+// promised to be the native path's bit for bit.)
+static inline int chain_split_of(const gogp_handle *h, bool eager) {
   if (h->dist || h->prec != 64) return 0;
   if (h->chain_split >= 0) return h->chain_split;
-  return (h->npad <= 8192 || !eager || h->npad - C0 <= h->chain_tail) ? 2 : 0;
+  return (h->npad <= 8192 || !eager) ? 2 : 0;
 }
-static void split_panel(gogp_handle *h, hipStream_t sp, double *A, double *L, double *Dp, int64_t ld, int64_t c0,
-                        int64_t npad, GemmProfile *pf) {
-  const int64_t c1 = c0 + TILE, c2 = c0 + PANEL;
-  const int mt1 = (int)((npad - c1) / TILE), mt2 = (int)((npad - c2) / TILE);
-  GemmGrid gtri, gch;
-  gtri.ktri = h->ktri;
-  gtri.prio = gch.prio = chain_prio_of(h);
-  launch_diag128(sp, A + c0 * ld + c0, ld, L + c0 * ld + c0, ld, Dp, 0, c0, h->n, h->info);
-  // L10 and the first half of the panel below the block: rows c1.. of columns c0 .. c1
-  launch_gemm_nt(sp, GEMM_RECT, mt1, 1, TILE, 1.0, A + c1 * ld + c0, ld, Dp, PANEL, 0.0, L + c1 * ld + c0, ld, pf, &gtri);
-  // the second half of the panel's columns, from the diagonal block's A11 down
-  launch_gemm_nt(sp, GEMM_RECT, mt1, 1, TILE, -1.0, L + c1 * ld + c0, ld, L + c1 * ld + c0, ld, 1.0, A + c1 * ld + c1, ld,
-                 pf, &gch);
-  launch_diag128(sp, A + c0 * ld + c0, ld, L + c0 * ld + c0, ld, Dp, 1, c0, h->n, h->info);
-  if (mt2 > 0)
-    launch_gemm_nt(sp, GEMM_RECT, mt2, 1, TILE, 1.0, A + c2 * ld + c1, ld, Dp + (size_t)TILE * PANEL + TILE, PANEL, 0.0,
-                   L + c2 * ld + c1, ld, pf, &gtri);
-}
-static void split_panel(gogp_handle *, hipStream_t, float *, float *, float *, int64_t, int64_t, int64_t, GemmProfile *) {}
 // chain_split = 2: panel128 (half 0) -> A[c1:, c1:c2] -= L[c1:, c0:c1] L[c1:c2, c0:c1]^T (tile kernel) -> panel128 (half 1)
 static void fused_panel(gogp_handle *h, hipStream_t sp, double *A, double *L, int64_t ld, int64_t c0, int64_t npad,
                         GemmProfile *pf) {
@@ -858,39 +810,6 @@ static void dinv_blocks(hipStream_t s, const double *L, double *Dinv, int64_t ld
   launch_dinv256_blocks(s, L + (int64_t)P0 * PANEL * (ld + 1), ld, Dinv + (size_t)P0 * PANEL * PANEL, nsub);
 }
 static void dinv_blocks(hipStream_t, const float *, float *, int64_t, int, int) {}
-// X10 = -X11 (L10 X00) for the nsub diagonal blocks of a super-panel: two batched 128^3 products (solve.hip:
-// blockmm_kernel); M = L10 X00 goes through the block's A10 position in bufA, which is dead once split_panel has read it
-static void x10_blocks(gogp_handle *h, hipStream_t s, double *A, const double *L, double *Dinv, int64_t ld, int P0, int nsub) {
-  (void)h;
-  for (int b0 = 0; b0 < nsub; b0 += 6) {
-    const int nb = std::min(6, nsub - b0);
-    const double *A1[6], *B1[6], *A2[6], *B2[6];
-    double *C1[6], *C2[6];
-    int64_t lda1[6], ldb1[6], ldc1[6], lda2[6], ldb2[6], ldc2[6];
-    int K[6];
-    for (int b = 0; b < nb; ++b) {
-      const int p = P0 + b0 + b;
-      const int64_t c0 = (int64_t)p * PANEL, c1 = c0 + TILE;
-      double *Dp = Dinv + (size_t)p * PANEL * PANEL;
-      A1[b] = L + c1 * ld + c0;
-      lda1[b] = ld;
-      B1[b] = Dp;
-      ldb1[b] = PANEL;
-      C1[b] = A + c1 * ld + c0;
-      ldc1[b] = ld;
-      A2[b] = Dp + (size_t)TILE * PANEL + TILE;
-      lda2[b] = PANEL;
-      B2[b] = C1[b];
-      ldb2[b] = ld;
-      C2[b] = Dp + (size_t)TILE * PANEL;
-      ldc2[b] = PANEL;
-      K[b] = TILE;
-    }
-    launch_blockmm(s, nb, A1, lda1, B1, ldb1, C1, ldc1, K, 1.0, TILE);
-    launch_blockmm(s, nb, A2, lda2, B2, ldb2, C2, ldc2, K, -1.0, TILE);
-  }
-}
-static void x10_blocks(gogp_handle *, hipStream_t, float *, const float *, float *, int64_t, int, int) {}
 
 template <class T>
 static int factorize_t(gogp_handle *h, bool eager) {
@@ -991,29 +910,21 @@ static int factorize_t(gogp_handle *h, bool eager) {
   // super-panel) runs on the panel stream with 256-wide steps; the trailing
   // matrix gets ONE rank-(SW*256) update per super-panel on the main stream
   // (next super-panel's block columns first: look-ahead).
+  const int split = std::is_same<T, double>::value ? chain_split_of(h, eager) : 0;  // the form of the chain: 0 or 2
   int prevP0 = -1;
   for (int P0 = 0, nsub = 0; P0 < npanel; prevP0 = P0, P0 += nsub) {
     nsub = superpanel_width(h, npanel, P0);
     const int next_nsub = (P0 + nsub < npanel) ? superpanel_width(h, npanel, P0 + nsub) : 0;
     const int64_t C0 = (int64_t)P0 * PANEL, CE = C0 + (int64_t)nsub * PANEL;
-    const int split = std::is_same<T, double>::value ? chain_split_of(h, eager, C0) : 0;  // the form of this super-panel's chain
     for (int q = 0; q < nsub; ++q) {
       const int p = P0 + q;
       const int64_t c0 = (int64_t)p * PANEL, c2 = c0 + PANEL;
       T *Dp = Dinv + (size_t)p * PANEL * PANEL;
       const int mt2 = (int)((npad - c2) / TILE);
-      if (split == 2) {
+      if (split)
         fused_panel(h, sp, A, L, ld, c0, npad, pf);
-      } else if (split) {
-        // option "chain_split": the two 128 x 128 halves of the diagonal block are factored and inverted on their own
-        // (diag256.hip: diag128_kernel) and the three products between them -- which the 256-block kernel does on ONE
-        // compute unit -- go to the tile kernel for ALL rows of the panel at once: they are the panel solve and the
-        // update of the panel's second half.  X10 (the inverse's off-diagonal block) leaves the chain: x10_blocks below.
-        split_panel(h, sp, A, L, Dp, ld, c0, npad, pf);
-      } else {
-      // 256x256 diagonal block: factor + dense inverse, one workgroup
-      diag_block(h, sp, A + c0 * ld + c0, ld, L + c0 * ld + c0, ld, Dp, c0);
-      }
+      else  // 256x256 diagonal block: factor + dense inverse, one workgroup
+        diag_block(h, sp, A + c0 * ld + c0, ld, L + c0 * ld + c0, ld, Dp, c0);
       // L[c2:, c0:c2] = A[c2:, c0:c2] * inv(L_pp)^T   (one K=256 GEMM)
       if (mt2 > 0 && !split) {
         GemmGrid gtri;  // Dp is lower triangular: the first tile column only needs k < 128
@@ -1045,12 +956,9 @@ static int factorize_t(gogp_handle *h, bool eager) {
     if (sz != sp) (void)gogp::rec_stream_wait(sz, ev(h, EV_BASE + 4 * P0));
 
     if (split) {
-      // X10 = -X11 (L10 X00) of the super-panel's diagonal blocks (chain_split = 2: their whole inverses), off the chain:
-      // the substitution steps right below and the triangular inverse (st) are its first readers
-      if (split == 2)
-        dinv_blocks(sz, L, Dinv, ld, P0, nsub);
-      else
-        x10_blocks(h, sz, A, L, Dinv, ld, P0, nsub);
+      // the inverses of the super-panel's diagonal blocks, off the chain: the substitution steps right below and the
+      // triangular inverse (st) are their first readers
+      dinv_blocks(sz, L, Dinv, ld, P0, nsub);
       if (eager) {
         (void)gogp::rec_event_record(ev(h, EV_BASE + 5 * (size_t)npanel + 32 + (size_t)P0), sz);
         (void)gogp::rec_stream_wait(st, ev(h, EV_BASE + 5 * (size_t)npanel + 32 + (size_t)P0));
@@ -2594,26 +2502,13 @@ extern "C" int gogp_set_option(gogp_handle *h, const char *name, int64_t value) 
     h->chain_slabs = (int)value;
     return GOGP_OK;
   }
-  if (strcmp(name, "chain_tail") == 0) {  // chain_split = -1 above npad = 8192 beside the inverse: form 2 once this many rows remain
-    if (value < 0 || value > (1 << 20)) return fail(h, GOGP_EARG, "chain_tail must be 0..2^20");
-    h->chain_tail = value;
-    return GOGP_OK;
-  }
-  if (strcmp(name, "chain_split") == 0) {  // -1: by size, 0: 256-block kernel, 1: two 128-halves + products on the tile kernel
-    if (value < -1 || value > 2) return fail(h, GOGP_EARG, "chain_split must be -1..2");
+  if (strcmp(name, "chain_split") == 0) {  // -1: by size, 0: 256-block kernel, 2: panel128.hip (form 1 is gone, 2 keeps its number)
+    if (value < -1 || value > 2 || value == 1) return fail(h, GOGP_EARG, "chain_split must be -1, 0 or 2");
     h->chain_split = (int)value;
     return GOGP_OK;
   }
   if (strcmp(name, "ktri") == 0) {
     h->ktri = value != 0;
-    return GOGP_OK;
-  }
-  if (strcmp(name, "inv_prio") == 0) {
-    if (value < 0 || value > 2) return fail(h, GOGP_EARG, "inv_prio must be 0..2");
-    HIPCHK(h, hipSetDevice(h->device));
-    for (hipStream_t q : work_streams(h)) HIPCHK(h, hipStreamSynchronize(q));
-    h->inv_prio = (int)value;
-    HIPCHK(h, apply_inv_prio(h));
     return GOGP_OK;
   }
   if (strcmp(name, "graph") == 0) {  // candidates: hipGraph replay -- 1 a chain (N <= 1024), 2 the real DAG (N <= 8192), 0 streams

@@ -92,10 +92,9 @@ struct gogp_handle {
   int superpanel_head = -1;    // > 0: super-panel width while more than head_remaining panels are to come; -1: 3 (fp64) / 4 (fp32)
   int head_remaining = 16;     // (measured, N = 16384: 3 / 16 72.7 ms, 3 / 24 72.8, 4 / 32 74.2, off 73.0-73.4)
   int chain_prio = -1;         // tile-kernel launches on the two chains raise their waves' issue priority (-1: by size)
-  int64_t chain_tail = 0;      // chain_split = -1, large N beside the inverse: panel128 for the super-panels with at most this many rows left (0: none)
   int tiny = 1;                // N <= 128 observations: one launch for the whole factorisation (api.hip: tiny_factorize)
   int chain_slabs = 0;         // chain_split = 2: slabs of 64 panel rows per workgroup (panel128.hip); 0: by the launch's size
-  int chain_split = -1;        // 1: the diagonal block in two 128-halves, their products on the tile kernel; 2: panel128.hip (api.hip; -1: by size)
+  int chain_split = -1;        // 0: the 256-block kernel + a panel solve; 2: panel128.hip (api.hip: chain_split_of; -1: by size)
   int ktri = 1;                // panel solves skip the zero half of the block inverse (common.h: GemmGrid)
   // T^-1 (lower, row-major) of the diagonal block of every super-panel of the factor: rows C0.. of an npad x tinv_ld
   // matrix, assembled by the first Produce on a factor (api.hip: assemble_tinv, produce_solve_t).  Produce then solves
@@ -127,8 +126,6 @@ struct gogp_handle {
   int64_t kinv_c1 = 0;         // ... columns that launch covered in the current factorisation (0: none)
   int kinv_fused = -1;          // ... and accumulates K^-1 = sum_P Y_P Y_P^T behind it, one rank-k update
                                // per super-panel of Y (0: one LAUUM launch over the finished Y in Gradient; -1: by size)
-  int inv_prio = 0;            // 0: the inverse's streams at normal priority; 1: its bulk updates (s2) low;
-                               // 2: bulk and chain (s2, st) low
   bool kinv_pending = false;   // K^-1 is being accumulated on sk (wait for EV_KINV)
   bool trtri_done = false;     // Y = L^-T of the current factor is (being) computed
   bool trtri_pending = false;  // ... and still running on st/s2 (wait for EV_TRTRI)

@@ -5,11 +5,10 @@
 // mat.Cholesky.Factorize (gp/gp.go:228); "not positive definite" is reported through *info (first failing pivot + 1).
 //
 // Why: tools/wg_stamps.py (profiles/r05_wg_stamps_*): the chain per 256-panel was diag256 (130 us on ONE compute unit:
-// two 128-factorisations, two 128-inverses, four 128^3 products) + a K = 256 panel solve on the tile kernel; option
-// "chain_split" moved the products to the tile kernel but still pays a 128 x 128 inverse (22K cycles) and a launch for
-// each half's solve.  The inverse exists only to turn the solve into a GEMM.  Here the solve rides on the factorisation
-// instead: workgroup g takes the 64 panel rows c1 + 64 g .. and EVERY workgroup factors the diagonal block redundantly
-// (the same arithmetic in the same order, so all of them hold the same bits and nothing is exchanged).  The stacked
+// two 128-factorisations, two 128-inverses, four 128^3 products) + a K = 256 panel solve on the tile kernel.  The
+// inverses exist only to turn the solve into a GEMM.  Here the solve rides on the factorisation instead: workgroup g
+// takes the 64 panel rows c1 + 64 g .. and EVERY workgroup factors the diagonal block redundantly (the same arithmetic
+// in the same order, so all of them hold the same bits and nothing is exchanged).  The stacked
 // matrix M = [D; P] (128 + 64 rows x 128 columns) lives in LDS; per 16-column step the panel rows are rows of M like
 // the rows of D below the pivot block: forward-substituted in the lanes of the pivot waves (panel16m) and updated
 // by rank-16 MFMA products.  The launch lasts as long as ONE 128-factorisation (the pivot-column chain), whatever the

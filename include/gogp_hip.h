@@ -390,22 +390,18 @@ int gogp_profile_read_aux(gogp_handle *h, int cls, double *ms, int64_t *launches
  *                          summed in fp64 from the float panels (diagsyrk.hip) and the fp64 diagonal-block kernel
  *                          factors THAT image; 0: it widens the float matrix's block (rounds 2-4)    (default 1)
  *   "krag"         1 | 0   the triangular inverse's updates skip the zero triangle of a super-panel of Y (default 1)
- *   "chain_split"  -1 | 0 | 1 | 2   fp64, the factorisation's dependency chain per 256-panel: 0 one workgroup factors and
+ *   "chain_split"  -1 | 0 | 2   fp64, the factorisation's dependency chain per 256-panel: 0 one workgroup factors and
  *                          inverts the 256 x 256 diagonal block, the panel solve is a K = 256 product with that inverse;
- *                          1 two 128-halves (factor + inverse each) with the products between them on the tile kernel
- *                          and X10 of the block inverse formed off the chain; 2 per 128 columns ONE launch factors the
- *                          diagonal 128-block and forward-substitutes every panel row on the way (panel128.hip), the
- *                          block inverses are formed off the chain from the finished factor; -1: 2 where the
- *                          evaluation is latency-bound (N <= 8192) or no fp64 inverse runs beside the factorisation
- *                          (Absorb, eager = 0); above that, beside the inverse, 0 -- and 2 for the super-panels with at
- *                          most "chain_tail" rows left                                                (default -1)
+ *                          2 per 128 columns ONE launch factors the diagonal 128-block and forward-substitutes every
+ *                          panel row on the way (panel128.hip), the block inverses are formed off the chain from the
+ *                          finished factor; -1: 2 where the evaluation is latency-bound (N <= 8192) or no fp64 inverse
+ *                          runs beside the factorisation (Absorb, eager = 0), 0 above that beside the inverse (default -1)
  *   "tiny"         1 | 0   fp64, one GPU, N <= 128 observations (the reference's own case studies): Gram matrix, factor, block
  *                          inverse, z, alpha and K^-1 in ONE launch of one workgroup instead of the general sweep's ~15
  *                          dependent launches; 0: the general sweep                                   (default 1)
  *   "chain_slabs"  0..8    chain_split = 2: 64-row slabs of the panel per workgroup of the chain step; the result does
  *                          not depend on it; 0: one while the launch has at most a workgroup per compute unit, up to 4
  *                          beyond (measured at N = 16384: 1 / 2 / 4 slabs 30.1 / 32.0 / 35.4 ms Observe only) (default 0)
- *   "chain_tail"   0..2^20 rows (see chain_split; measured slower at N = 16384 and 32768)            (default 0)
  *   "produce_small_max" 0..64   gogp_produce with up to this many test points (fp32 path: up to 16 of them): ONE
  *                          persistent launch that reads the factor once (trsm_small.hip; float factors are widened in
  *                          registers, the sums are fp64) instead of the tile-kernel chain; 0: never  (default 64)

@@ -164,7 +164,7 @@ def route_case():
 
 @pytest.mark.parametrize("opts", [
     {}, {"kinv_fused": 0}, {"kinv_fused": 1}, {"kinv_split": 50}, {"eager": 0}, {"lookahead": 0},
-    {"chain_split": 0}, {"chain_split": 1}, {"chain_split": 2}, {"superpanel": 1}, {"superpanel": 3},
+    {"chain_split": 0}, {"chain_split": 2}, {"superpanel": 1}, {"superpanel": 3},
     {"krag": 0}, {"krag": 1},
 ], ids=lambda o: ",".join("%s=%d" % kv for kv in o.items()) or "default")
 def test_full_form_kinv_routes(gpmod, route_case, opts):

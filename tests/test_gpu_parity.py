@@ -545,30 +545,6 @@ def test_chain_step_kernel_against_numpy(rows_below):
         np.testing.assert_allclose(L[128:], ref, rtol=0, atol=1e-12 * np.abs(ref).max())
 
 
-@pytest.mark.parametrize("rows_below", [0, 64, 192, 1024])
-def test_chain_step_kernel_against_numpy(rows_below):
-    """panel128.hip alone (gp/gp.go:228, the diagonal-block factorisation and the panel solve of Factorize): the factor of
-    a 128 x 128 block and the rows under it solved against it, against numpy's Cholesky / triangular solve."""
-    import ctypes
-    from gogp_amd import _lib
-    H = _lib.hooks()
-    rng = np.random.default_rng(rows_below + 1)
-    n = 128 + rows_below
-    B = rng.normal(size=(n, 150))
-    K = B @ B.T / 150 + 0.3 * np.eye(n)
-    A = np.ascontiguousarray(K[:, :128])
-    L = np.zeros_like(A)
-    st = (ctypes.c_uint64 * 72)()
-    us = ctypes.c_double()
-    assert H.gogp_test_panel128(0, A.ctypes.data_as(_lib._dp), L.ctypes.data_as(_lib._dp), rows_below, 1, st,
-                                ctypes.byref(us)) == 0
-    Ld = np.linalg.cholesky(K[:128, :128])
-    np.testing.assert_allclose(L[:128], Ld, rtol=0, atol=1e-13 * np.abs(Ld).max())   # upper triangle: zeros
-    if rows_below:
-        ref = np.linalg.solve(Ld, K[128:, :128].T).T
-        np.testing.assert_allclose(L[128:], ref, rtol=0, atol=1e-12 * np.abs(ref).max())
-
-
 @pytest.mark.parametrize("rows_below", [64, 192, 1024])
 def test_chain_step_result_does_not_depend_on_slabs_per_workgroup(rows_below):
     """panel128.hip, multi-slab workgroups (launches with more workgroups than compute units: k candidates, tall panels): a
@@ -665,18 +641,18 @@ def _same_results(a, b):
 
 
 @pytest.mark.parametrize("n,D", [(1, 1), (129, 1), (700, 2), (1500, 3), (4096, 4)])
-def test_diagonal_block_in_two_halves_matches_the_256_block_kernel(gpmod, n, D):
-    """Option chain_split (gp/gp.go:228-230, the diagonal-block work of Factorize): the 256 x 256 diagonal block factored
-    and inverted as two 128 x 128 halves (diag256.hip: diag128_kernel) with the products between them on the tile kernel
-    and X10 of the block inverse formed off the chain -- against the one-workgroup 256-block kernel: the same factor
-    (rows of L), alpha, LML (1e-12 as VERDICT round 4 asks), gradient, mu / sigma; candidates; the failing pivot."""
+def test_one_launch_chain_step_matches_the_256_block_kernel(gpmod, n, D):
+    """Option chain_split (gp/gp.go:228-230, the diagonal-block work of Factorize): form 2, the chain per 128 columns in
+    one launch (panel128.hip) with the 256 x 256 block inverses formed off the chain, against form 0, the one-workgroup
+    256-block kernel: the same factor (rows of L), alpha, LML (1e-12 as VERDICT round 4 asks), gradient, mu / sigma;
+    candidates; the failing pivot.  The removed form 1 and options chain_tail / inv_prio are refused."""
     rng = np.random.default_rng(n + D)
     X, y = _data(rng, n, D)
     Z = rng.uniform(-0.1, 1.1, (9, D))
     simil, noise = kernel.Scaled(kernel.Matern32), kernel.UniformNoise
     x = np.log([1.2, 0.5, 0.2])
     out = {}
-    for split in (0, 1, 2):
+    for split in (0, 2):
         g = gpmod.GP(D, simil, noise, X=X, Y=y)
         g.set_option("chain_split", split)
         lml = g.Observe(x)
@@ -688,20 +664,24 @@ def test_diagonal_block_in_two_halves_matches_the_256_block_kernel(gpmod, n, D):
         mu_a, sg_a = g.Produce(Z)
         out[split] = (lml, grad, mu, sg, g.Alpha.copy(), g.L.copy(), cl, cg, list(cs), mu_a, sg_a)
         g.close()
-    for other in (1, 2):
-        _same_results(out[0], out[other])
+    _same_results(out[0], out[2])
     # the failing pivot is reported from whichever half meets it (gp/gp.go:228-230): inputs so far apart that K = I in
     # floating point, the last one duplicated -- the last pivot is exactly 1 - 1 = 0 on every path
     for m in (2, 130, 200, 300):
         Xd = 100.0 * np.arange(m, dtype=float)[:, None]
         Xd[-1] = Xd[-2]
-        for split in (0, 1, 2):
+        for split in (0, 2):
             g = gpmod.GP(1, kernel.Normal, kernel.ConstantNoise(0.0), ThetaSimil=[1.0])
             g.set_option("chain_split", split)
             with pytest.raises(gpmod.FactorizeError) as ei:
                 g.Absorb(Xd, np.ones(m))
             assert ei.value.pivot == m - 1
             g.close()
+    g = gpmod.GP(D, simil, noise, X=X, Y=y)
+    for name, value in (("chain_split", 1), ("chain_tail", 0), ("inv_prio", 0)):
+        with pytest.raises(gpmod.GogpError):
+            g.set_option(name, value)
+    g.close()
 
 
 def test_not_positive_definite(gpmod):

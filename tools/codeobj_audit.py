@@ -34,8 +34,6 @@ SGPR_SPILL_ALLOW = {
     # (the pivot pass broadcasts with DPP, pivot16.h: no v_readlane results to hoist); what is left are kernel arguments and
     # the products' loop state
     r"diag256_kernel<true, false, \d+>": 64,
-    # one 128-half of the block on its own (option chain_split = 1): the same potrf128_lds / inv16 code (round 5: 91 -> 7)
-    r"diag128_kernel": 48,
     # cold path: only gogp_set_factor (restore of stored results) inverts blocks of an existing factor (round 4: 248 -> 6)
     r"diag256_kernel<false, false, \d+>": 48,
     # multi-term / periodic kernels keep the per-pair loop: kind, scale, period and length tables of up to

@@ -1,4 +1,4 @@
-"""Option chain_split (the diagonal block in two 128-halves, products on the tile kernel) against the 256-block kernel:
+"""Option chain_split: the one-launch chain step (2, panel128.hip) against the 256-block kernel (0):
 one Observe + Gradient at a time, Observe only (eager = 0), 8 candidates per launch sequence.
 usage: python3 tools/split_probe.py [N,N,...]"""
 import os, sys, time
@@ -13,7 +13,7 @@ for N in Ns:
     x = np.log([1.0, np.sqrt(D / 6.0), 0.1])
     g = G.GP(D, kernel.Scaled(kernel.Normal), kernel.UniformNoise, X=X, Y=y)
     res = {}
-    for split in (0, 1, 2, 0, 1, 2):
+    for split in (0, 2, 0, 2):
         g.set_option("chain_split", split)
         g.set_option("eager", 1)
         lml = g.Observe(x); g.Gradient()
