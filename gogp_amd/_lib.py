@@ -36,6 +36,15 @@ class CXfer(ctypes.Structure):
 EXCHANGE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(CXfer), ctypes.c_int32)
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_double),
                                 ctypes.c_int64)
+class CGemmOpts(ctypes.Structure):
+    """gogp_test_gemm_opts (include/gogp_testhooks.h): the tile kernel's GemmGrid and the candidate batch."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("ktri", "krag0", "new_row0", "kbeg0", "small_below", "prio", "rule",
+                                              "tpb_shift", "rblk0", "cblk0", "pr", "Pr", "pc", "Pc", "beta0", "k")]
+    _fields_ += [("bstride", ctypes.c_int64)]
+    DEFAULTS = dict(ktri=0, krag0=-1, new_row0=-1, kbeg0=0, small_below=384, prio=0, rule=0, tpb_shift=0, rblk0=0,
+                    cblk0=0, pr=0, Pr=1, pc=0, Pc=1, beta0=-1, k=1, bstride=0)
+
+
 SYMBOLS = [
     ("gogp_desc_check", ctypes.c_int, [_descp]),
     ("gogp_desc_ntheta_noise", ctypes.c_int, [_descp]),
@@ -96,6 +105,13 @@ HOOK_SYMBOLS = [
     ("gogp_test_panel128", ctypes.c_int,
      [ctypes.c_int, _dp, _dp, _i64, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64), _dp]),
     ("gogp_test_panel128_slabs", ctypes.c_int, [ctypes.c_int, _dp, _dp, _i64, ctypes.c_int, ctypes.c_int, _dp]),
+    ("gogp_test_gemm_nt", ctypes.c_int,
+     [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _i64, ctypes.c_double, ctypes.c_double]
+     + [ctypes.c_void_p, _i64, _i64, _i64] * 3 + [ctypes.POINTER(CGemmOpts)]),
+    ("gogp_test_diag_syrk", ctypes.c_int,
+     [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, _i64, _i64, _i64, _i64, _i64, _dp, _i64, ctypes.c_int]),
+    ("gogp_test_diag256_product", ctypes.c_int,
+     [ctypes.c_int, ctypes.c_int, _dp, _i64, _dp, _i64, _dp, _i64, _i64, ctypes.POINTER(ctypes.c_longlong)]),
     # per-rank replay of the sharded sweep (tools/sharded_replay.py): a transport that reads recorded panels
     ("gogp_test_dist_init_replay", ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int] * 4),
 ]

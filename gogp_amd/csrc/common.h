@@ -84,8 +84,11 @@ struct GemmGrid {
   // priority (s_setprio 3), so that on a CU they share with bulk workgroups their MFMAs go first
   int prio = 0;
   // GEMM_RECT / GEMM_LOWER: the rows of A from tile row krag0 (128-tiles) on are upper triangular against the K
-  // range -- row block krag0 + i of A is zero for k < i * 128 (a super-panel of Y = L^-T with its triangular diagonal
-  // part: api.hip, trtri_superstep) -- so tile row ti >= krag0 only sums k >= (ti - krag0) * 128.  -1: none.
+  // range (a super-panel of Y = L^-T with its triangular diagonal part: api.hip, trtri_superstep), so a workgroup
+  // tile row starts at k = (its first row - krag0 * 128).  The launches on 64 x 64 tiles count that in 64-row
+  // steps: row krag0 * 128 + r of A must be zero for k < 64 * floor(r / 64) -- zero per 128-row block (k < 128 i
+  // in block krag0 + i) is NOT enough there (rows 64..127 of the block skip [128 i, 128 i + 64) too).  Y is zero
+  // left of its diagonal element by element, which covers both.  -1: none.
   int krag0 = -1;
   // launches with fewer 128-tiles than this use 64 x 64 tiles (default 384).  Alone on the GPU the 64-tile shape wins
   // up to ~3000 tiles (820 tiles at K = 768: 61 against 51 TFLOP/s); inside an evaluation, beside other streams'

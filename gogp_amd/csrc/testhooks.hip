@@ -221,6 +221,160 @@ extern "C" int gogp_test_dgemm_nt(int device, int64_t M, int64_t N, int64_t K, d
   return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
 }
 
+// ---- the product launchers of the tile kernel, the fp64 diagonal-block update and the diagonal-block kernel on host
+// buffers (tests/test_tile_kernels.py).  Every argument is checked BEFORE the device is touched: a test mistake comes back
+// as GOGP_EARG, never as an access outside the buffers.  Each array is copied to the device whole and (outputs) back whole,
+// so a test sees the elements a launch must leave alone as well as those it writes.
+namespace {
+// off + (k - 1) * stride + (rows - 1) * ld + cols <= len, all in elements
+bool covers(int64_t len, int64_t off, int64_t ld, int64_t rows, int64_t cols, int64_t k, int64_t stride) {
+  if (len <= 0 || off < 0 || ld < cols || rows <= 0 || cols <= 0 || k <= 0 || stride < 0) return false;
+  const int64_t hi = off + (k - 1) * stride + (rows - 1) * ld + cols;
+  return hi <= len;
+}
+bool device_ok(int device) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return false;
+  return device < 0 || hipSetDevice(device) == hipSuccess;
+}
+}  // namespace
+
+extern "C" int gogp_test_gemm_nt(int device, int precision, int mode, int mt, int nt, int64_t K, double alpha,
+                                 double beta, const void *A, int64_t a_len, int64_t a_off, int64_t lda, const void *B,
+                                 int64_t b_len, int64_t b_off, int64_t ldb, void *C, int64_t c_len, int64_t c_off,
+                                 int64_t ldc, const gogp_test_gemm_opts *opt) {
+  gogp_test_gemm_opts o = {0, -1, -1, 0, 384, 0, 0, 0, 0, 0, 0, 1, 0, 1, -1, 1, 0};
+  if (opt) o = *opt;
+  if (!A || !B || !C || (precision != 64 && precision != 32)) return GOGP_EARG;
+  if (mode < GEMM_RECT || mode > GEMM_TRAP || mt <= 0 || nt <= 0 || K <= 0) return GOGP_EARG;
+  const int64_t es = precision / 8, kstep = precision == 64 ? GEMM_BK : 32, al = 16 / es;  // al: elements per 16 B
+  if (K % kstep || K > (1 << 30)) return GOGP_EARG;
+  if ((mode == GEMM_LOWER || mode == GEMM_LAUUM) && mt != nt) return GOGP_EARG;
+  if (alpha == 0.0 || (precision == 32 && (float)alpha == 0.0f)) return GOGP_EARG;  // accumulators start at (beta/alpha) C
+  if (o.k < 1 || o.k > 64 || o.bstride < 0 || o.bstride % al || (o.k > 1 && o.bstride == 0)) return GOGP_EARG;
+  if (precision == 32 && (o.k > 1 || o.kbeg0 != 0)) return GOGP_EARG;  // the fp32 kernel has neither
+  if (o.kbeg0 < 0 || o.kbeg0 % kstep || o.kbeg0 > K || (o.kbeg0 && mode != GEMM_LAUUM)) return GOGP_EARG;
+  if (o.new_row0 < -1 || (o.new_row0 >= 0 && mode != GEMM_LOWER)) return GOGP_EARG;
+  if (o.ktri && mode != GEMM_RECT) return GOGP_EARG;
+  if (o.krag0 < -1 || (o.krag0 >= 0 && (o.ktri || (mode != GEMM_RECT && mode != GEMM_LOWER)))) return GOGP_EARG;
+  // the first k-step of tile row ti >= krag0 is loaded at k = (ti - krag0) * tile before the loop count is known
+  if (o.krag0 >= 0 && o.krag0 < mt && K < (int64_t)(mt - o.krag0) * TILE) return GOGP_EARG;
+  if (o.rule < 0 || o.rule > 2 || (o.rule && mode != GEMM_RECT)) return GOGP_EARG;
+  if (o.rule && (o.tpb_shift < 0 || o.tpb_shift > 8 || o.rblk0 < 0 || o.cblk0 < 0 || o.Pr < 1 || o.Pc < 1 ||
+                 o.pr < 0 || o.pr >= o.Pr || o.pc < 0 || o.pc >= o.Pc))
+    return GOGP_EARG;
+  if (lda % al || ldb % al || ldc % al || a_off % al || b_off % al || c_off % al) return GOGP_EARG;
+  const int64_t M = (int64_t)mt * TILE, N = (int64_t)nt * TILE;
+  if (!covers(a_len, a_off, lda, M, K, o.k, o.bstride) || !covers(b_len, b_off, ldb, N, K, o.k, o.bstride) ||
+      !covers(c_len, c_off, ldc, M, N, o.k, o.bstride))
+    return GOGP_EARG;
+  if (!device_ok(device)) return GOGP_EHIP;
+
+  char *dA = nullptr, *dB = nullptr, *dC = nullptr;
+  hipError_t e = hipMalloc(&dA, (size_t)(a_len * es));
+  if (e == hipSuccess) e = hipMalloc(&dB, (size_t)(b_len * es));
+  if (e == hipSuccess) e = hipMalloc(&dC, (size_t)(c_len * es));
+  if (e == hipSuccess) e = hipMemcpy(dA, A, (size_t)(a_len * es), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(dB, B, (size_t)(b_len * es), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(dC, C, (size_t)(c_len * es), hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    GemmGrid g;
+    g.ktri = o.ktri;
+    g.krag0 = o.krag0;
+    g.new_row0 = o.new_row0;
+    g.kbeg0 = o.kbeg0;
+    g.small_below = o.small_below;
+    g.prio = o.prio;
+    g.rule = o.rule;
+    g.tpb_shift = o.tpb_shift;
+    g.rblk0 = o.rblk0;
+    g.cblk0 = o.cblk0;
+    g.pr = o.pr;
+    g.Pr = o.Pr;
+    g.pc = o.pc;
+    g.Pc = o.Pc;
+    g.beta0 = o.beta0;
+    tl_batch.k = o.k;
+    tl_batch.stride = (long)(o.bstride * es);
+    if (precision == 64)
+      launch_gemm_nt(0, (GemmMode)mode, mt, nt, K, alpha, (const double *)dA + a_off, lda, (const double *)dB + b_off, ldb,
+                     beta, (double *)dC + c_off, ldc, nullptr, &g);
+    else
+      launch_gemm_nt(0, (GemmMode)mode, mt, nt, K, alpha, (const float *)dA + a_off, lda, (const float *)dB + b_off, ldb,
+                     beta, (float *)dC + c_off, ldc, nullptr, &g);
+    tl_batch.k = 1;
+    tl_batch.stride = 0;
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+  }
+  if (e == hipSuccess) e = hipMemcpy(C, dC, (size_t)(c_len * es), hipMemcpyDeviceToHost);
+  (void)hipFree(dA);
+  (void)hipFree(dB);
+  (void)hipFree(dC);
+  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+}
+
+extern "C" int gogp_test_diag_syrk(int device, int bs, const float *L, int64_t l_len, int64_t l_off, int64_t ld,
+                                   int64_t K, int64_t row_stride, double *D64, int64_t d_len, int nblocks) {
+  if (!L || !D64 || (bs != PANEL && bs != 2 * PANEL) || nblocks < 1 || nblocks > 4096) return GOGP_EARG;
+  if (K < 16 || K % 16 || ld % 4 || l_off % 4 || row_stride % 4) return GOGP_EARG;  // float4 loads, k-chunks of 16
+  if (bs == PANEL && row_stride != PANEL * ld) return GOGP_EARG;  // launch_diag_syrk_f64: blocks 256 rows apart
+  if (!covers(l_len, l_off, ld, bs, K, nblocks, row_stride) || d_len < (int64_t)nblocks * bs * bs) return GOGP_EARG;
+  if (!device_ok(device)) return GOGP_EHIP;
+  float *dL = nullptr;
+  double *dD = nullptr;
+  hipError_t e = hipMalloc(&dL, (size_t)l_len * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc(&dD, (size_t)d_len * sizeof(double));
+  if (e == hipSuccess) e = hipMemcpy(dL, L, (size_t)l_len * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(dD, D64, (size_t)d_len * sizeof(double), hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    if (bs == PANEL)
+      launch_diag_syrk_f64(0, dL + l_off, ld, K, dD, nblocks);
+    else
+      launch_diag_syrk_f64_tiles(0, dL + l_off, ld, K, dD, nblocks, row_stride, bs);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+  }
+  if (e == hipSuccess) e = hipMemcpy(D64, dD, (size_t)d_len * sizeof(double), hipMemcpyDeviceToHost);
+  (void)hipFree(dL);
+  (void)hipFree(dD);
+  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+}
+
+extern "C" int gogp_test_diag256_product(int device, int variant, const double *A, int64_t ld, double *L, int64_t ldl,
+                                         double *Dinv, int64_t row0, int64_t nvalid, long long *info) {
+  if (!A || !L || !Dinv || !info || variant < 0 || variant > 3) return GOGP_EARG;
+  if (ld < PANEL || ldl < PANEL || ld % 2 || ldl % 2 || row0 < 0 || nvalid < 0) return GOGP_EARG;  // 16-B loads
+  const int64_t ldd = (variant & 1) ? 2 * PANEL : PANEL;  // variants 1, 3: Dinv a block of a leading dimension 512
+  if (!device_ok(device)) return GOGP_EHIP;
+  double *dA = nullptr, *dL = nullptr, *dD = nullptr;
+  long long *dinfo = nullptr;
+  const size_t na = (size_t)PANEL * ld * 8, nl = (size_t)PANEL * ldl * 8, nd = (size_t)PANEL * ldd * 8;
+  hipError_t e = hipMalloc(&dA, na);
+  if (e == hipSuccess) e = hipMalloc(&dL, nl);
+  if (e == hipSuccess) e = hipMalloc(&dD, nd);
+  if (e == hipSuccess) e = hipMalloc(&dinfo, 8);
+  if (e == hipSuccess) e = hipMemcpy(dA, A, na, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(dL, L, nl, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(dD, Dinv, nd, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(dinfo, info, 8, hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    switch (variant) {
+      case 0: launch_diag256(0, dA, ld, dL, ldl, dD, row0, nvalid, dinfo); break;
+      case 1: launch_diag256_ld512(0, dA, ld, dL, ldl, dD, row0, nvalid, dinfo); break;
+      case 2: launch_diag256_inv_only(0, dA, ld, dD); break;
+      default: launch_diag256_inv_only_ld512(0, dA, ld, dD); break;
+    }
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+  }
+  if (e == hipSuccess) e = hipMemcpy(L, dL, nl, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(Dinv, dD, nd, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(info, dinfo, 8, hipMemcpyDeviceToHost);
+  (void)hipFree(dA); (void)hipFree(dL); (void)hipFree(dD); (void)hipFree(dinfo);
+  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+}
+
 // Diagnostic: factor+invert one 256x256 SPD block (host buffers) with the stamped
 // build of the diagonal kernel; returns the factor, the inverse and 24 s_memtime stamps.
 extern "C" int gogp_test_diag256(int device, const double *A, double *Lout, double *Dinv,

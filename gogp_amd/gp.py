@@ -445,3 +445,95 @@ def bench_gemm(mode: int, mt: int, nt: int, K: int, reps: int = 5, device: int =
     if rc != _lib.GOGP_OK:
         raise GogpError(rc, "bench_gemm")
     return ms.value, tf.value
+
+
+GEMM_MODES = {"RECT": 0, "LOWER": 1, "LAUUM": 2, "TRAP": 3}
+
+
+def _covers(n, off, ld, rows, cols, k, stride, what):
+    # the launch addresses off + c * stride + r * ld + [0, cols) for c < k, r < rows
+    if off < 0 or ld < cols or stride < 0 or off + (k - 1) * stride + (rows - 1) * ld + cols > n:
+        raise ValueError("%s: %d elements do not cover off %d, ld %d, %d x %d, %d slots %d apart"
+                         % (what, n, off, ld, rows, cols, k, stride))
+
+
+def gemm_nt_check(mode, mt: int, nt: int, K: int, A: np.ndarray, B: np.ndarray, C: np.ndarray, alpha=1.0, beta=0.0,
+                  lda=None, ldb=None, ldc=None, a_off=0, b_off=0, c_off=0, device: int = -1, **opts) -> np.ndarray:
+    """The product launcher of the tile kernel (test hook gogp_test_gemm_nt) on host arrays: returns a copy of the
+    whole of C after  C = beta C + alpha A B^T  over mt x nt tiles of 128 in `mode` (RECT, LOWER, LAUUM, TRAP or
+    0..3).  The dtype (float64 / float32, the same for all three) picks the kernel.  The arrays are taken flat; the
+    launch sees them at element offsets a_off, b_off, c_off with leading dimensions lda, ldb, ldc (default: the
+    arrays' row length).  opts: the GemmGrid fields of _lib.CGemmOpts, plus k candidates bstride elements apart.
+    Every array must cover what the launch addresses (ValueError otherwise, before the hook is called)."""
+    mode = GEMM_MODES.get(mode, mode)
+    arrs = []
+    for a in (A, B, C):
+        if not isinstance(a, np.ndarray) or a.dtype not in (np.float64, np.float32) or not a.flags.c_contiguous:
+            raise TypeError("operands: C-contiguous float64 / float32 arrays")
+        arrs.append(a)
+    if len({a.dtype for a in arrs}) != 1:
+        raise TypeError("A, B and C must share one dtype")
+    prec = 64 if A.dtype == np.float64 else 32
+    lda = A.shape[-1] if lda is None else lda
+    ldb = B.shape[-1] if ldb is None else ldb
+    ldc = C.shape[-1] if ldc is None else ldc
+    o = dict(_lib.CGemmOpts.DEFAULTS)
+    unknown = set(opts) - set(o)
+    if unknown:
+        raise TypeError("unknown options %s" % sorted(unknown))
+    o.update(opts)
+    k, bstride = o["k"], o["bstride"]
+    rows_b = mt if mode in (1, 2) else nt
+    _covers(A.size, a_off, lda, mt * 128, K, k, bstride, "A")
+    _covers(B.size, b_off, ldb, rows_b * 128, K, k, bstride, "B")
+    _covers(C.size, c_off, ldc, mt * 128, nt * 128, k, bstride, "C")
+    out = C.copy()
+    copt = _lib.CGemmOpts(**o)
+    rc = _lib.hooks().gogp_test_gemm_nt(device, prec, mode, mt, nt, K, alpha, beta,
+                                        A.ctypes.data, A.size, a_off, lda, B.ctypes.data, B.size, b_off, ldb,
+                                        out.ctypes.data, out.size, c_off, ldc, ctypes.byref(copt))
+    if rc != _lib.GOGP_OK:
+        raise GogpError(rc, "test_gemm_nt")
+    return out
+
+
+def diag_syrk_check(L: np.ndarray, D64: np.ndarray, K: int, nblocks: int, bs: int = 256, ld=None, l_off: int = 0,
+                    row_stride=None, device: int = -1) -> np.ndarray:
+    """The fp32 path's fp64 diagonal-block update (test hook gogp_test_diag_syrk): returns a copy of the whole of D64
+    after  D64 block b -= R_b R_b^T  (b < nblocks), R_b the bs x K floats of L at l_off + b * row_stride, leading
+    dimension ld.  bs = 256 is the single-GPU launcher (row_stride = 256 ld), 512 the sharded one."""
+    if L.dtype != np.float32 or D64.dtype != np.float64 or not (L.flags.c_contiguous and D64.flags.c_contiguous):
+        raise TypeError("L: float32, D64: float64, both C-contiguous")
+    ld = L.shape[-1] if ld is None else ld
+    row_stride = bs * ld if row_stride is None else row_stride
+    _covers(L.size, l_off, ld, bs, K, nblocks, row_stride, "L")
+    if D64.size < nblocks * bs * bs:
+        raise ValueError("D64 holds fewer than %d blocks" % nblocks)
+    out = D64.copy()
+    rc = _lib.hooks().gogp_test_diag_syrk(device, bs, L.ctypes.data, L.size, l_off, ld, K, row_stride, _dp(out),
+                                          out.size, nblocks)
+    if rc != _lib.GOGP_OK:
+        raise GogpError(rc, "test_diag_syrk")
+    return out
+
+
+def diag256_product(A: np.ndarray, variant: int = 0, row0: int = 0, nvalid: int = 256, L=None, Dinv=None,
+                    device: int = -1):
+    """The product build of the diagonal-block kernel (test hook gogp_test_diag256_product) on one 256 x 256 block:
+    variant 0 factor + inverse, 1 the same with Dinv of leading dimension 512, 2 inverse only (A holds the factor),
+    3 inverse only at 512.  A: 256 rows (its row length is the leading dimension).  L (256 x ldl) and Dinv
+    (256 x 256 | 512) are the outputs' initial contents (zeros by default).  Returns (L, Dinv, info)."""
+    A = _arr(A)
+    if A.ndim != 2 or A.shape[0] != 256 or A.shape[1] < 256:
+        raise ValueError("A: 256 rows of at least 256")
+    L = np.zeros((256, 256)) if L is None else _arr(L).copy()
+    ldd = 512 if variant in (1, 3) else 256
+    Dinv = np.zeros((256, ldd)) if Dinv is None else _arr(Dinv).copy()
+    if L.ndim != 2 or L.shape[0] != 256 or L.shape[1] < 256 or Dinv.shape != (256, ldd):
+        raise ValueError("L: 256 rows of at least 256, Dinv: 256 x %d" % ldd)
+    info = ctypes.c_longlong(0)
+    rc = _lib.hooks().gogp_test_diag256_product(device, variant, _dp(A), A.shape[1], _dp(L), L.shape[1], _dp(Dinv),
+                                                row0, nvalid, ctypes.byref(info))
+    if rc != _lib.GOGP_OK:
+        raise GogpError(rc, "test_diag256_product")
+    return L, Dinv, info.value

@@ -32,6 +32,40 @@ int gogp_mfma_f32_peak(int device, int iters, double *tflops, double *cyc_per_mf
 int gogp_test_dgemm_nt(int device, int64_t M, int64_t N, int64_t K, double alpha,
                        const double *A, const double *B, double beta, double *C);
 
+/* Every GemmGrid field of the tile kernel's launcher (gogp_amd/csrc/common.h) and the candidate batch: k launches
+ * side by side on gridDim.z, candidate c's A, B and C lying c * bstride ELEMENTS after candidate 0's. */
+typedef struct gogp_test_gemm_opts {
+  int32_t ktri, krag0, new_row0, kbeg0, small_below, prio;
+  int32_t rule, tpb_shift, rblk0, cblk0, pr, Pr, pc, Pc, beta0;
+  int32_t k;
+  int64_t bstride;
+} gogp_test_gemm_opts;
+
+/* The product launcher of the tile kernel on host buffers: C = beta C + alpha A B^T over mt x nt tiles of 128 in `mode`
+ * (0 RECT, 1 LOWER, 2 LAUUM, 3 TRAP), precision 64 (double) or 32 (float).  A, B, C hold a_len, b_len, c_len elements;
+ * the launch sees them at element offsets a_off, b_off, c_off with leading dimensions lda, ldb, ldc.  Each array is
+ * copied whole to the device and C whole back.  opt == NULL: the launcher's defaults.  Returns GOGP_EARG, before the
+ * device is touched, for K not a multiple of the K-step (16 / 32), leading dimensions or offsets that are not 16-byte
+ * aligned, arrays that do not cover the region the launch addresses, mt != nt for LOWER / LAUUM, alpha == 0, options
+ * the mode does not have, and fp32 with k > 1 or kbeg0 != 0 (the fp32 kernel has neither). */
+int gogp_test_gemm_nt(int device, int precision, int mode, int mt, int nt, int64_t K, double alpha, double beta,
+                      const void *A, int64_t a_len, int64_t a_off, int64_t lda, const void *B, int64_t b_len,
+                      int64_t b_off, int64_t ldb, void *C, int64_t c_len, int64_t c_off, int64_t ldc,
+                      const gogp_test_gemm_opts *opt);
+
+/* The fp32 path's fp64 update of the diagonal blocks (diagsyrk.hip): D64 block b (bs x bs, bs = 256 or 512) -= R_b R_b^T
+ * with R_b the bs x K floats at L + l_off + b * row_stride (leading dimension ld), for b < nblocks.  bs = 256 drives
+ * launch_diag_syrk_f64 (row_stride must be 256 ld), bs = 512 launch_diag_syrk_f64_tiles.  GOGP_EARG for K not a
+ * multiple of 16 or below 16 and for buffers that do not cover the launch. */
+int gogp_test_diag_syrk(int device, int bs, const float *L, int64_t l_len, int64_t l_off, int64_t ld, int64_t K,
+                        int64_t row_stride, double *D64, int64_t d_len, int nblocks);
+
+/* The product build of the diagonal-block kernel (diag256.hip) on one 256 x 256 block: variant 0 factor + inverse,
+ * 1 the same with Dinv of leading dimension 512, 2 inverse only (A holds the factor), 3 inverse only at 512.  A: 256 x ld,
+ * L: 256 x ldl (in / out; variants 0, 1 write the factor), Dinv: 256 x (256 | 512) (in / out), info: in / out. */
+int gogp_test_diag256_product(int device, int variant, const double *A, int64_t ld, double *L, int64_t ldl,
+                              double *Dinv, int64_t row0, int64_t nvalid, long long *info);
+
 /* Benchmark hook for the tile kernel: `reps` launches of one shape (mode 0 RECT
  * mt x nt tiles, 1 LOWER mt x mt, 2 LAUUM mt x mt with K = mt*128) on device
  * buffers; returns ms per launch and TFLOP/s on the flops launched. */
