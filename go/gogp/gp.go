@@ -33,6 +33,16 @@ type DeviceKernel interface {
 	Terms() []Term
 }
 
+// EventKernel is optionally implemented by a DeviceKernel whose similarity is
+// discounted across event boundaries (tutorial/events/kernel/kernel.go:14-44):
+// Events() returns [from, to, discount] triples, EventAxis() the input dimension
+// they lie on (0 for the reference's 1-D case).  The shim passes them to
+// gogp_set_events.
+type EventKernel interface {
+	Events() [][]float64
+	EventAxis() int
+}
+
 // DeviceNoise is implemented by noise kernels that can run on the GPU.
 type DeviceNoise interface {
 	Kernel
@@ -113,6 +123,19 @@ func (gp *GP) handle() *C.gogp_handle {
 		panic(fmt.Sprintf("gogp_create: %s", C.GoString(C.gogp_last_error(nil))))
 	}
 	runtime.SetFinalizer(gp, func(g *GP) { C.gogp_destroy(g.h) })
+	if ek, ok := gp.Simil.(EventKernel); ok && len(ek.Events()) > 0 {
+		evs := ek.Events()
+		flat := make([]float64, 0, 3*len(evs))
+		for _, e := range evs {
+			if len(e) != 3 {
+				panic("gogp: an event is [from, to, discount]")
+			}
+			flat = append(flat, e...)
+		}
+		if rc := C.gogp_set_events(gp.h, dptr(flat), C.int(len(evs)), C.int(ek.EventAxis())); rc != C.GOGP_OK {
+			panic(fmt.Sprintf("gogp_set_events: %s", C.GoString(C.gogp_last_error(gp.h))))
+		}
+	}
 	gp.dirty = true
 	return gp.h
 }

@@ -66,6 +66,15 @@ extern "C" int gogp_desc_check(const gogp_desc *d) {
   return GOGP_OK;
 }
 
+extern "C" int gogp_events_check(const double *events, int nevents, int axis, int ndim) {
+  if (nevents < 0 || nevents > GOGP_MAX_EVENTS) return GOGP_EARG;
+  if (ndim < 1 || ndim > GOGP_MAX_NDIM || axis < 0 || axis >= ndim) return GOGP_EARG;
+  if (nevents > 0 && !events) return GOGP_EARG;
+  for (int i = 0; i < 3 * nevents; ++i)
+    if (!isfinite(events[i])) return GOGP_EARG;
+  return GOGP_OK;
+}
+
 extern "C" const char *gogp_version(void) {
 #ifndef GOGP_BUILD_ID
 #define GOGP_BUILD_ID "unknown"
@@ -383,6 +392,34 @@ extern "C" int gogp_set_data_device(gogp_handle *h, const double *dX, const doub
   return set_data_impl(h, dX, dy, n, hipMemcpyDeviceToDevice);
 }
 
+// ---- event discounts (tutorial/events/kernel/kernel.go:14-44) --------------------------------
+// Host state only: fill_params copies the table into every DevParams, and h->ev() selects the kernels' *_ev_kernel
+// instances at every launch that evaluates the similarity.
+extern "C" int gogp_set_events(gogp_handle *h, const double *events, int nevents, int axis) {
+  if (!h) return GOGP_EARG;
+  if (nevents == 0 && !events) axis = 0;  // clearing: the axis does not matter
+  if (gogp_events_check(events, nevents, axis, h->D) != GOGP_OK)
+    return fail(h, GOGP_EARG, "set_events: need 0 <= nevents <= GOGP_MAX_EVENTS, 0 <= axis < ndim, finite values");
+  if (nevents > 0 && h->ard_dims > 0)
+    return fail(h, GOGP_EARG, "set_events: event discounts are not supported with an ARD term");
+  HIPCHK(h, hipSetDevice(h->device));
+  // nothing enqueued may still read the old kernel; stored results (factor, alpha, K^-1) no longer match it
+  for (hipStream_t q : work_streams(h)) HIPCHK(h, hipStreamSynchronize(q));
+  if (h->dist) {
+    const int rcs = gogp_dist_sync(h);
+    if (rcs != GOGP_OK) return rcs;
+  }
+  drop_cand_graph(h);  // a captured candidates sequence launched the other kernel instances
+  h->nevents = nevents;
+  h->ev_axis = axis;
+  for (int e = 0; e < nevents; ++e)
+    for (int f = 0; f < 3; ++f) h->events[e][f] = events[3 * e + f];
+  h->factored = h->have_alpha = h->have_kinv = h->observed = h->grad_valid = false;
+  h->trtri_done = h->trtri_pending = h->alpha_pending = h->kinv_pending = false;
+  h->tinv_valid = h->tinv_pending = false;
+  return GOGP_OK;
+}
+
 // ---- parameters ---------------------------------------------------------------------------
 // DevParams of the handle's current natural parameters (theta_s, theta_n)
 static void fill_params(const gogp_handle *h, DevParams &p) {
@@ -411,6 +448,13 @@ static void fill_params(const gogp_handle *h, DevParams &p) {
     const double sd = h->theta_n[0];
     p.noise_var = d.noise_scale * sd * sd;  // kernel/noise.go:47-49
     p.dnoise = 2.0 * p.noise_var;
+  }
+  p.nevents = h->nevents;
+  p.ev_axis = h->ev_axis;
+  for (int e = 0; e < h->nevents; ++e) {
+    p.ev_from[e] = h->events[e][0];
+    p.ev_to[e] = h->events[e][1];
+    p.ev_disc[e] = h->events[e][2];
   }
 }
 
@@ -868,7 +912,7 @@ static int factorize_t(gogp_handle *h, bool eager) {
   {
     AuxTimer tm(h, GOGP_PROF_GRAM, s);  // the main-stream part: all but the first block columns
     launch_gram_lower_split(sp, s, h->devP, h->D, h->dX, h->n, npad, reinterpret_cast<T *>(h->bufA), ld,
-                            (int64_t)superpanel_width(h, (int)(npad / PANEL), 0) * PANEL);
+                            (int64_t)superpanel_width(h, (int)(npad / PANEL), 0) * PANEL, h->ev());
   }
   // fp32 path, option "diag_fp64": the diagonal blocks leave the float matrix here -- widened once, every later
   // contribution summed in fp64 (diagsyrk.hip); the first super-panel's on the chain stream, the rest behind the build
@@ -1060,7 +1104,7 @@ static int factorize_t(gogp_handle *h, bool eager) {
     const size_t vb = (size_t)npad * sizeof(double);
     for (int it = 0; it < h->refine_steps; ++it) {
       launch_residual(sp, h->devP, h->D, h->dX, h->n, npad, h->alpha, h->dy, h->rpart, REFINE_SLABS, h->rw,
-                      h->radial1);
+                      h->radial1, h->ev());
       for (int b = 0; b < npanel; ++b) launch_trsv_fwd_step(sp, L, ld, Dinv, b, npanel, h->rw, h->rz);
       HIPCHK(h, hipMemcpyAsync(h->rw, h->rz, vb, hipMemcpyDeviceToDevice, sp));
       for (int b = npanel - 1; b >= 0; --b) launch_trsv_bwd_step(sp, L, ld, Dinv, b, npanel, h->rw, h->rd);
@@ -1155,7 +1199,7 @@ static int tiny_factorize(gogp_handle *h, bool eager) {
   }
   if (!h->batch_mode) h->tinv_valid = false;
   HIPCHK(h, cand_memset(h, h->info, sizeof(long long), s));
-  launch_tiny_eval(s, h->devP, h->dX, h->dy, h->n, h->bufA, h->bufL, h->Dinv, h->z, h->alpha, h->info, eager);
+  launch_tiny_eval(s, h->devP, h->dX, h->dy, h->n, h->bufA, h->bufL, h->Dinv, h->z, h->alpha, h->info, eager, h->ev());
   launch_lml_scalars(s, h->bufL, h->npad, h->z, nullptr, nullptr, h->n, h->scalars);
   (void)gogp::rec_event_record(ev(h, EV_ALPHA), s);
   HIPCHK(h, cand_d2h(h, h->hscal, h->scalars, 7 * sizeof(double), s));
@@ -1385,6 +1429,8 @@ static void assemble_gradient(const gogp_handle *h, const double *a, double dnoi
 //   trace slot     tr(W) = |alpha|^2 - |Y|_F^2                    (fp64 sums over Y = L^-T, launch_trace_from_y)
 //   scale slot     sum_ij W_ij c k_ij = tr(W (K - v I)) = (y^T alpha - n) - v tr(W)     (K alpha = y holds for the
 //                  refined alpha; v: the noise variance on the diagonal) -- one radial term with an output scale.
+//                  It holds with event discounts too: the discounted similarity c f d is still homogeneous of
+//                  degree 1 in c, so the scale slot c d f summed against W is still tr(W (K - v I)).
 // Measured on the stress case of round 3 (Matern-3/2, N = 1721, D = 2, gradient error 3.6e-3 of its largest
 // component, all of it in the scale slot): tests/test_gpu_parity.py::test_fp32_gradient_ill_conditioned_case.
 static void fp32_gradient_identities(const gogp_handle *h, double *a, double trace_w, double yta, double noise_var) {
@@ -1424,13 +1470,13 @@ extern "C" int gogp_gradient(gogp_handle *h, double *grad, int64_t len) {
       AuxTimer tm(h, GOGP_PROF_GRAD, s);
       if (h->prec == 32)
         launch_grad_reduce(s, h->devP, h->D, h->ard_dims, h->dX, h->alpha,
-                           reinterpret_cast<const float *>(h->bufA), h->npad, h->n, h->npad, h->gpart, h->gout, h->radial1, h->ard_mfma_min);
+                           reinterpret_cast<const float *>(h->bufA), h->npad, h->n, h->npad, h->gpart, h->gout, h->radial1, h->ard_mfma_min, h->ev());
       else if (mixed_gradient(h))
         launch_grad_reduce(s, h->devP, h->D, h->ard_dims, h->dX, h->alpha, (const float *)h->g32A, h->npad, h->n,
-                           h->npad, h->gpart, h->gout, h->radial1, h->ard_mfma_min);
+                           h->npad, h->gpart, h->gout, h->radial1, h->ard_mfma_min, h->ev());
       else
         launch_grad_reduce(s, h->devP, h->D, h->ard_dims, h->dX, h->alpha, h->bufA, h->npad, h->n,
-                           h->npad, h->gpart, h->gout, h->radial1, h->ard_mfma_min);
+                           h->npad, h->gpart, h->gout, h->radial1, h->ard_mfma_min, h->ev());
     }
     HIPCHK(h, cand_d2h(h, h->hscal + 16, h->gout, NACC * sizeof(double), s));
     h->hscal[9] = NAN;
@@ -1459,7 +1505,7 @@ extern "C" int gogp_gradient(gogp_handle *h, double *grad, int64_t len) {
     const int64_t n = h->n;
     double *gx = nullptr;
     HIPCHK(h, hipMalloc(&gx, (size_t)h->npad * h->D * sizeof(double)));
-    launch_xgrad(s, h->devP, h->D, h->dX, h->alpha, h->bufA, h->npad, n, h->npad, gx);
+    launch_xgrad(s, h->devP, h->D, h->dX, h->alpha, h->bufA, h->npad, n, h->npad, gx, h->ev());
     hipError_t e = hipMemcpyAsync(grad + h->P, gx, (size_t)n * h->D * sizeof(double),
                                   hipMemcpyDeviceToHost, s);
     if (e == hipSuccess)
@@ -1706,10 +1752,10 @@ extern "C" int gogp_observe_gradient_candidates(gogp_handle *h, int k, const dou
       AuxTimer tm(h, GOGP_PROF_GRAD, h->s);
       if (f32)
         launch_grad_reduce(h->s, h->devP, h->D, h->ard_dims, h->dX, h->alpha, reinterpret_cast<const float *>(h->bufA),
-                           h->npad, h->n, h->npad, h->gpart, h->gout, h->radial1, h->ard_mfma_min);
+                           h->npad, h->n, h->npad, h->gpart, h->gout, h->radial1, h->ard_mfma_min, h->ev());
       else
         launch_grad_reduce(h->s, h->devP, h->D, h->ard_dims, h->dX, h->alpha, h->bufA, h->npad, h->n, h->npad,
-                           h->gpart, h->gout, h->radial1, h->ard_mfma_min);
+                           h->gpart, h->gout, h->radial1, h->ard_mfma_min, h->ev());
     }
     HIPCHK(h, cand_d2h(h, h->hscal + 16, h->gout, NACC * sizeof(double), h->s));
     h->hscal[9] = NAN;
@@ -1948,7 +1994,7 @@ static void produce_solve_t(gogp_handle *h, hipStream_t s, int64_t m, int64_t mp
   const T *L = reinterpret_cast<const T *>(h->bufL), *Dinv = reinterpret_cast<const T *>(h->Dinv);
   {
     AuxTimer tm(h, GOGP_PROF_CROSS, s);
-    launch_cross(s, h->devP, h->D, h->dX, h->n, npad, h->dZ, m, mpad, R, ld);  // gp/gp.go:322-332
+    launch_cross(s, h->devP, h->D, h->dX, h->n, npad, h->dZ, m, mpad, R, ld, h->ev());  // gp/gp.go:322-332
   }
   // mean = Kstar^T alpha (gp/gp.go:335)
   launch_rownorm_dot(s, R, ld, h->alpha, npad, m, dmu, nullptr);
@@ -2054,9 +2100,9 @@ static int produce_small(gogp_handle *h, hipStream_t s, int64_t m, int64_t mpad,
   {
     AuxTimer tm(h, GOGP_PROF_CROSS, s);
     if (f32)
-      launch_cross(s, h->devP, h->D, h->dX, h->n, npad, h->dZ, m, mpad, reinterpret_cast<float *>(h->KsT), ld);
+      launch_cross(s, h->devP, h->D, h->dX, h->n, npad, h->dZ, m, mpad, reinterpret_cast<float *>(h->KsT), ld, h->ev());
     else
-      launch_cross(s, h->devP, h->D, h->dX, h->n, npad, h->dZ, m, mpad, h->KsT, ld);  // gp/gp.go:322-332
+      launch_cross(s, h->devP, h->D, h->dX, h->n, npad, h->dZ, m, mpad, h->KsT, ld, h->ev());  // gp/gp.go:322-332
   }
   // mean = Kstar^T alpha (gp/gp.go:335)
   if (f32)

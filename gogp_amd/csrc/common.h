@@ -28,6 +28,10 @@ struct DevParams {
   double inv_len[GOGP_MAX_TERMS][GOGP_MAX_NDIM];  // 1/l_d (all equal unless ard)
   double noise_var;  // value added on the diagonal
   double dnoise;     // d noise_var / d log(std)  (0 for ConstantNoise)
+  // event discounts (gogp_set_events; kern_eval.h: event_mask).  Appended: the fields above keep their offsets,
+  // and only the kernel instances compiled with events (template flag EV) read these.
+  int nevents, ev_axis;
+  double ev_from[GOGP_MAX_EVENTS], ev_to[GOGP_MAX_EVENTS], ev_disc[GOGP_MAX_EVENTS];
 };
 
 // Accumulator slots of the fused gradient reduction (see grad.hip):
@@ -158,9 +162,9 @@ void launch_gemm_nt(hipStream_t s, GemmMode mode, int mt, int nt, int64_t K, dou
                     GemmProfile *prof, const GemmGrid *grid = nullptr);  // sgemm.hip
 void launch_gram_lower_split(hipStream_t s_first, hipStream_t s_rest, const DevParams *p, int ndim,
                              const double *X, int64_t n, int64_t npad, float *K, int64_t ld,
-                             int64_t wcols);
+                             int64_t wcols, bool ev = false);
 void launch_cross(hipStream_t s, const DevParams *p, int ndim, const double *X, int64_t n,
-                  int64_t npad, const double *Z, int64_t m, int64_t mpad, float *KsT, int64_t ld);
+                  int64_t npad, const double *Z, int64_t m, int64_t mpad, float *KsT, int64_t ld, bool ev = false);
 void launch_trsv_fwd_step(hipStream_t s, const float *L, int64_t ld, const float *Dinv, int b, int nblk,
                           double *y, double *z);
 void launch_trsv_bwd_step(hipStream_t s, const float *L, int64_t ld, const float *Dinv, int b, int nblk,
@@ -182,31 +186,32 @@ void launch_convert_block(hipStream_t s, const double *src, int64_t lds_, float 
                           int cols);
 void launch_grad_reduce(hipStream_t s, const DevParams *p, int ndim, int ard_dims, const double *X,
                         const double *alpha, const float *Kinv, int64_t ld, int64_t n, int64_t npad,
-                        double *partials, double *out, bool radial1 = false, int mfma_min_dims = 1);
+                        double *partials, double *out, bool radial1 = false, int mfma_min_dims = 1, bool ev = false);
 
 void launch_gram_lower(hipStream_t s, const DevParams *p, int ndim, const double *X,
-                       int64_t n, int64_t npad, double *K, int64_t ld);
+                       int64_t n, int64_t npad, double *K, int64_t ld, bool ev = false);
 // Local tiles (mrows x ncols) of a 2-D block-cyclic Gram matrix: tiles of the global lower
 // triangle get kernel values (identity padding for rows >= n), distribution blocks strictly
 // above the diagonal are zero-filled (the work area R of the triangular inverse).
 void launch_gram_local(hipStream_t s, const DevParams *p, int ndim, const double *X, int64_t n,
-                       int64_t mrows, int64_t ncols, BlockMap map, double *K, int64_t ld);
+                       int64_t mrows, int64_t ncols, BlockMap map, double *K, int64_t ld, bool ev = false);
 void launch_gram_local(hipStream_t s, const DevParams *p, int ndim, const double *X, int64_t n,
-                       int64_t mrows, int64_t ncols, BlockMap map, float *K, int64_t ld);
+                       int64_t mrows, int64_t ncols, BlockMap map, float *K, int64_t ld, bool ev = false);
 void launch_gram_lower_split(hipStream_t s_first, hipStream_t s_rest, const DevParams *p, int ndim,
                              const double *X, int64_t n, int64_t npad, double *K, int64_t ld,
-                             int64_t wcols);
+                             int64_t wcols, bool ev = false);
 // KsT (mpad x npad): KsT[j][i] = k(x_i, z_j); zero for i >= n or j >= m.
 void launch_cross(hipStream_t s, const DevParams *p, int ndim, const double *X, int64_t n,
                   int64_t npad, const double *Z, int64_t m, int64_t mpad, double *KsT,
-                  int64_t ld);
+                  int64_t ld, bool ev = false);
 // r = y - K v with K recomputed in fp64 on the fly (iterative refinement of alpha on the fp32 path);
 // part: nslab * npad doubles of scratch
 void launch_residual(hipStream_t s, const DevParams *p, int ndim, const double *X, int64_t n, int64_t npad,
-                     const double *v, const double *y, double *part, int nslab, double *r, bool radial1 = false);
+                     const double *v, const double *y, double *part, int nslab, double *r, bool radial1 = false,
+                     bool ev = false);
 void launch_kmatvec_share(hipStream_t s, const DevParams *p, int ndim, const double *X, int64_t n, int64_t npad,
                           const double *v, int part_idx, int nparts, double *part, int nslab, double *out,
-                          bool radial1 = false);
+                          bool radial1 = false, bool ev = false);
 void launch_prior(hipStream_t s, const DevParams *p, const double *Z, int64_t m,
                   double *prior);
 
@@ -249,7 +254,7 @@ void launch_panel128_slabs(hipStream_t s, const double *A, int64_t ld, double *L
 // diag256.hip: a whole evaluation of n <= 128 observations in one launch (npad = 256): Gram matrix, factor, block inverse, z,
 // alpha and (want_kinv) K^-1, left where the general path leaves them (A: K^-1 lower, L, Dinv: leading dimension 256)
 void launch_tiny_eval(hipStream_t s, const DevParams *P, const double *X, const double *y, int64_t n, double *A, double *L,
-                      double *Dinv, double *z, double *alpha, long long *info, bool want_kinv);
+                      double *Dinv, double *z, double *alpha, long long *info, bool want_kinv, bool ev = false);
 // dense inverses of nblk consecutive 256 x 256 diagonal blocks of a finished factor (block b at L + b * 256 * (ld + 1))
 void launch_dinv256_blocks(hipStream_t s, const double *L, int64_t ld, double *Dinv, int nblk);
 void launch_diag256_inv_only_ld512(hipStream_t s, const double *L, int64_t ld, double *Dinv);  // Dinv: ld 512
@@ -264,18 +269,19 @@ int grad_reduce_blocks(int64_t npad);
 // fused gradient reduction over lower tiles of Kinv; out: NACC doubles
 void launch_grad_reduce(hipStream_t s, const DevParams *p, int ndim, int ard_dims,
                         const double *X, const double *alpha, const double *Kinv, int64_t ld, int64_t n,
-                        int64_t npad, double *partials, double *out, bool radial1 = false, int mfma_min_dims = 1);
+                        int64_t npad, double *partials, double *out, bool radial1 = false, int mfma_min_dims = 1,
+                        bool ev = false);
 // the same over the LOCAL tiles (mrows x ncols, leading dimension ld) of a 2-D block-cyclic
 // K^-1: tiles of the global lower triangle only; `partials` needs grad_reduce_blocks_local
 int grad_reduce_blocks_local(int64_t mrows, int64_t ncols);
 void launch_grad_reduce_local(hipStream_t s, const DevParams *p, int ndim, int ard_dims,
                               const double *X, const double *alpha, const double *Kinv, int64_t ld,
                               int64_t n, int64_t mrows, int64_t ncols, BlockMap map, double *partials,
-                              double *out, bool radial1 = false, int mfma_min_dims = 1);
+                              double *out, bool radial1 = false, int mfma_min_dims = 1, bool ev = false);
 void launch_grad_reduce_local(hipStream_t s, const DevParams *p, int ndim, int ard_dims,
                               const double *X, const double *alpha, const float *Kinv, int64_t ld,
                               int64_t n, int64_t mrows, int64_t ncols, BlockMap map, double *partials,
-                              double *out, bool radial1 = false, int mfma_min_dims = 1);
+                              double *out, bool radial1 = false, int mfma_min_dims = 1, bool ev = false);
 
 // grad_mfma.hip: the reduction pass for ONE radial term with ARD length scales, distances and per-dimension sums
 // on the matrix cores; ntc == 0: lower triangle of an unsharded K^-1 (nt x nt tiles of 64, candidate batching
@@ -294,7 +300,7 @@ void launch_grad_ard_mfma(hipStream_t s, const DevParams *p, int ndim, const dou
 // gx[i][d] = sum_j (alpha_i alpha_j - Kinv_ij) dk(x_i,x_j)/dx_{i,d}
 void launch_xgrad(hipStream_t s, const DevParams *p, int ndim, const double *X,
                   const double *alpha, double *Kinv, int64_t ld, int64_t n, int64_t npad,
-                  double *gx);
+                  double *gx, bool ev = false);
 
 // dot_j = sum_i V[j][i] vec_i ; sq_j = sum_i V[j][i]^2  (either output may be null)
 void launch_rownorm_dot(hipStream_t s, const double *V, int64_t ld, const double *vec,

@@ -37,6 +37,7 @@
 // LDS: S[128][130] doubles (padding 2 => the MFMA fragment reads of 16 rows x
 // 2 k hit 64 distinct banks), G = 2304 doubles: the eight 16x16 inverses during the factor /
 // inverse phases, the double-buffered B chunks during the products.
+#ifndef GOGP_EV  // first pass: the whole file, tiny_eval_kernel without event discounts
 #include "common.h"
 #include "kern_eval.h"
 #include "pivot16.h"
@@ -654,6 +655,10 @@ __global__ __launch_bounds__(NT) void dinv256_blocks_kernel(const double *__rest
                                   nullptr);
 }
 
+#define GOGP_EV 0
+#define GOGP_EVN(name) name
+#endif  // GOGP_EV
+
 // ---- tutorial-sized evaluations: N <= 128 observations in ONE workgroup, ONE launch ---------------------------------------
 // The reference's own case studies fit 20 ... 44 observations (tutorial/data/*.csv; BASELINE configs[0]: N = 64).  At that
 // size the general sweep is fifteen dependent launches of a few microseconds each (kernel trace at N = 64: 0.34 ms per
@@ -663,7 +668,9 @@ __global__ __launch_bounds__(NT) void dinv256_blocks_kernel(const double *__rest
 // and writes L, the 256 x 256 block inverse, z, alpha and K^-1 where the general path leaves them; workgroups 1..3 fill
 // the constant quadrants of the padded 256-blocks meanwhile.  The log-determinant, the gradient reduction, Produce etc.
 // are the general path's kernels on these buffers.  Candidate batching as everywhere (blockIdx.z).
-__global__ __launch_bounds__(NT) void tiny_eval_kernel(const DevParams *__restrict__ Pp, const double *__restrict__ X,
+// Compiled twice (the file includes itself once, below): tiny_eval_kernel as before, and with GOGP_EV = 1 as
+// tiny_eval_kernel_ev, whose Gram matrix carries the event discounts (kern_eval.h: event_mask).
+__global__ __launch_bounds__(NT) void GOGP_EVN(tiny_eval_kernel)(const DevParams *__restrict__ Pp, const double *__restrict__ X,
                                                         const double *__restrict__ y, long n, double *__restrict__ A,
                                                         double *__restrict__ Lout, double *__restrict__ Dinv,
                                                         double *__restrict__ z, double *__restrict__ alpha,
@@ -696,7 +703,12 @@ __global__ __launch_bounds__(NT) void tiny_eval_kernel(const DevParams *__restri
   __shared__ __attribute__((aligned(16))) double G[GSIZE];
   __shared__ double rinv_s[8 * 16];
   __shared__ double ys[128], zs[128];
+  __shared__ unsigned long long em[GOGP_EV ? 128 : 1];  // GOGP_EV: the rows' event masks
   const int D = P.ndim;
+  if (GOGP_EV) {
+    if (tid < 128) em[tid] = event_mask(P, tid < n ? X[(long)tid * D + P.ev_axis] : 0.0);
+    __syncthreads();
+  }
   // ---- the Gram matrix, lower triangle, into S (gp/gp.go:109-156; rows / columns >= n: identity) ------------------------
   for (int idx = tid; idx < 128 * 128; idx += NT) {
     const int i = idx >> 7, j = idx & 127;
@@ -705,6 +717,7 @@ __global__ __launch_bounds__(NT) void tiny_eval_kernel(const DevParams *__restri
       if (i < n) {
         const double *xi = X + (long)i * D, *xj = X + (long)j * D;
         k = simil_value(P, [&](int d) { return xi[d]; }, [&](int d) { return xj[d]; });
+        if (GOGP_EV) k *= event_discount(P, em[i], em[j]);
         if (i == j) k += P.noise_var;
       } else {
         k = (i == j) ? 1.0 : 0.0;
@@ -779,11 +792,26 @@ __global__ __launch_bounds__(NT) void tiny_eval_kernel(const DevParams *__restri
       }
 }
 
+#if !GOGP_EV  // second pass (the product library only): tiny_eval_kernel again, with event discounts, as tiny_eval_kernel_ev
+#ifndef GOGP_BUILD_TESTHOOKS
+#undef GOGP_EV
+#undef GOGP_EVN
+#define GOGP_EV 1
+#define GOGP_EVN(name) name##_ev
+#include "diag256.hip"
+#endif
+#undef GOGP_EV
+#undef GOGP_EVN
+
 #ifndef GOGP_BUILD_TESTHOOKS
 void launch_tiny_eval(hipStream_t s, const DevParams *P, const double *X, const double *y, int64_t n, double *A, double *L,
-                      double *Dinv, double *z, double *alpha, long long *info, bool want_kinv) {
-  GOGP_KLAUNCH(tiny_eval_kernel, dim3(4, 1, (unsigned)gogp::tl_batch.k), dim3(NT), 0, s, P, X, y, (long)n, A, L, Dinv, z, alpha,
-               info, want_kinv ? 1 : 0, gogp::tl_batch.stride);
+                      double *Dinv, double *z, double *alpha, long long *info, bool want_kinv, bool ev) {
+  if (ev)
+    GOGP_KLAUNCH(tiny_eval_kernel_ev, dim3(4, 1, (unsigned)gogp::tl_batch.k), dim3(NT), 0, s, P, X, y, (long)n, A, L, Dinv, z,
+                 alpha, info, want_kinv ? 1 : 0, gogp::tl_batch.stride);
+  else
+    GOGP_KLAUNCH(tiny_eval_kernel, dim3(4, 1, (unsigned)gogp::tl_batch.k), dim3(NT), 0, s, P, X, y, (long)n, A, L, Dinv, z, alpha,
+                 info, want_kinv ? 1 : 0, gogp::tl_batch.stride);
 }
 #endif
 
@@ -838,3 +866,4 @@ void launch_diag256_stamped(hipStream_t s, const double *A, double *Lout, double
 #endif
 
 }  // namespace GOGP_NS
+#endif  // !GOGP_EV

@@ -528,7 +528,7 @@ static int dist_factorize_t(gogp_handle *h, bool want_kinv) {
   // every rank builds its own tiles of K (X is replicated): no communication for the O(N^2) step;
   // the strictly upper blocks are zero-filled (R)
   launch_gram_local(s, h->devP, h->D, h->dX, h->n, (int64_t)mloc * nb, (int64_t)nloc * nb, d->map(), A,
-                    ldA);
+                    ldA, h->ev());
   // fp32 evaluation, option "diag_fp64": my tiles of the global diagonal leave the float matrix here (widened once; every
   // later contribution is summed in fp64 from the float panel tiles: diagsyrk.hip, api.hip does the same per 256-block)
   d->d64_on = sizeof(T) == 4 && h->diag_fp64 != 0 && d->dq_count > 0 && d->d64 != nullptr;
@@ -811,7 +811,7 @@ static int dist_factorize_t(gogp_handle *h, bool want_kinv) {
     // quadratic term of the LML is y^T alpha of the refined alpha.
     for (int it = 0; it < h->refine_steps; ++it) {
       launch_kmatvec_share(sc, h->devP, h->D, h->dX, h->n, npad, h->alpha, d->rank, d->nranks, h->rpart,
-                           REFINE_SLABS, h->rw, h->radial1);
+                           REFINE_SLABS, h->rw, h->radial1, h->ev());
       TRCHK(d->tr->allreduce(sc, h->rw, npad, &e_));
       launch_residual_from(sc, h->rw, h->dy, npad);  // rw := y - K alpha, then its local rows
       hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((lrows + 255) / 256)), dim3(256), 0, sc, h->rw,
@@ -870,10 +870,10 @@ int gogp_dist_gradient_sums(gogp_handle *h, double *hacc) {
   // the last rank-nb updates of K^-1 run on s2; alpha is final (host-synchronised)
   if (h->prec == 32)
     launch_grad_reduce_local(s2, h->devP, h->D, h->ard_dims, h->dX, h->alpha, d->mat<float>(d->A), d->ldA(), h->n,
-                             (int64_t)d->mloc * d->nb, (int64_t)d->nloc * d->nb, d->map(), d->gpart, h->gout, h->radial1, h->ard_mfma_min);
+                             (int64_t)d->mloc * d->nb, (int64_t)d->nloc * d->nb, d->map(), d->gpart, h->gout, h->radial1, h->ard_mfma_min, h->ev());
   else
     launch_grad_reduce_local(s2, h->devP, h->D, h->ard_dims, h->dX, h->alpha, d->A, d->ldA(), h->n,
-                             (int64_t)d->mloc * d->nb, (int64_t)d->nloc * d->nb, d->map(), d->gpart, h->gout, h->radial1, h->ard_mfma_min);
+                             (int64_t)d->mloc * d->nb, (int64_t)d->nloc * d->nb, d->map(), d->gpart, h->gout, h->radial1, h->ard_mfma_min, h->ev());
   // float tiles: tr(K^-1) = |Y|_F^2 and |alpha|^2 in fp64 ride along in two free slots (13, 14) of the all-reduce
   const bool tr64 = h->prec == 32 && h->trace_fp64 && d->rloc;
   if (tr64) {
@@ -1433,7 +1433,7 @@ static int dist_produce_t(gogp_handle *h, const double *Z, int64_t m, double *mu
     }
   }
   // cross-covariance of the test points with my tile rows: Ks[j][lrow] (gp/gp.go:322-332)
-  launch_cross(s, h->devP, h->D, Xloc, nvalid, lrows, dZ, m, mpad, Ks, lrows);
+  launch_cross(s, h->devP, h->D, Xloc, nvalid, lrows, dZ, m, mpad, Ks, lrows, h->ev());
   launch_rownorm_dot(s, Ks, lrows, aloc, lrows, m, red2, nullptr);  // partial mu = Kstar^T alpha (:335)
   if (Pc > 1)  // the Pc ranks of a process row hold the same tile rows
     hipLaunchKernelGGL(scale_kernel, dim3((unsigned)((mpad + 255) / 256)), dim3(256), 0, s, red2, 1.0 / Pc,

@@ -11,19 +11,27 @@
 // (no dK matrix is ever stored).  Off-diagonal elements count twice.
 //
 // Output: NACC slot sums (see common.h); the host maps slots to theta indices.
+#ifndef GOGP_EV  // first pass: the whole file, the kernels without event discounts
 #include "kern_eval.h"
 
+#define GOGP_EV 0
+#define GOGP_EVN(name) name
 namespace gogp {
 
 constexpr int GR_BLOCKS_MAX = 2048;
+#endif
 
 // LOCAL: the tiles are the local ones of a 2-D block-cyclic K^-1 (rectangular nt x ntc tile
 // grid, global row / column indices through `map`, tiles of the global upper triangle skipped).
 // KT: element type of K^-1 (float on the fp32 path; all sums are fp64 either way).
 // RADIAL1: the similarity kernel is ONE radial term (every BASELINE configuration; the host checks):
 // that instance carries only the restructured loops below, the other only the generic accumulation.
+// GOGP_EV = 1: the handle has event discounts (kern_eval.h: event_mask): the pair's weight is multiplied by its discount,
+// so every slot of the similarity (scale, length, period) is; the noise slot (trace of W) is not.  This kernel and
+// xgrad_kernel are compiled twice -- as before, and with GOGP_EV = 1 as grad_reduce_kernel_ev / xgrad_kernel_ev (the file
+// includes itself once, below); the events instances are launched without ARD only (gogp_set_events refuses it).
 template <int ARD_D, bool LOCAL, class KT, bool RADIAL1>
-__global__ __launch_bounds__(256) void grad_reduce_kernel(
+__global__ __launch_bounds__(256) void GOGP_EVN(grad_reduce_kernel)(
     const DevParams *__restrict__ Pp, const double *__restrict__ X,
     const double *__restrict__ alpha, const KT *__restrict__ Kinv, long ld, long n, int nt,
     int ntiles, double *__restrict__ partials, int ntc, BlockMap map, int ard0, long bstride) {
@@ -38,6 +46,7 @@ __global__ __launch_bounds__(256) void grad_reduce_kernel(
   double *ai = CjT + 64 * (D + (ARD_D > 0 ? ARD_D : 0));  // [64]
   double *aj = ai + 64;         // [64]
   double *red = aj + 64;        // [4][NACC]
+  unsigned long long *Mr = reinterpret_cast<unsigned long long *>(red + 4 * NACC), *Mc = Mr + 64;  // GOGP_EV: [64] each
   const int tid = threadIdx.x;
   const int tx = tid & 63, ty = tid >> 6;
 
@@ -84,6 +93,8 @@ __global__ __launch_bounds__(256) void grad_reduce_kernel(
     }
     if (tid < 64) ai[tid] = (r0 + tid < n) ? alpha[r0 + tid] : 0.0;
     else if (tid < 128) aj[tid - 64] = (c0 + tid - 64 < n) ? alpha[c0 + tid - 64] : 0.0;
+    else if (GOGP_EV && tid < 192) Mr[tid - 128] = event_mask(P, (r0 + tid - 128 < n) ? X[(r0 + tid - 128) * D + P.ev_axis] : 0.0);
+    else if (GOGP_EV) Mc[tid - 192] = event_mask(P, (c0 + tid - 192 < n) ? X[(c0 + tid - 192) * D + P.ev_axis] : 0.0);
     __syncthreads();
     const long gj = c0 + tx;
     const double *cj = CjT + tx;
@@ -120,7 +131,8 @@ __global__ __launch_bounds__(256) void grad_reduce_kernel(
         gg[rr] = 0.0;
         if (gi < n && gj <= gi) {
           const double w = ai[r] * ajv - (double)Kinv[(lr0 + r) * ld + lc0 + tx];
-          const double wgt = (gj < gi) ? 2.0 * w : w;
+          double wgt = (gj < gi) ? 2.0 * w : w;
+          if (GOGP_EV) wgt *= event_discount(P, Mr[r], Mc[tx]);
           double f, dfdr2;
           radial_eval(kind, s[rr], f, dfdr2);
           acc[0] += wgt * cc * f;
@@ -168,7 +180,8 @@ __global__ __launch_bounds__(256) void grad_reduce_kernel(
       const long gi = r0 + r;
       if (gi < n && gj <= gi) {
         const double w = ai[r] * ajv - (double)Kinv[(lr0 + r) * ld + lc0 + tx];
-        const double wgt = (gj < gi) ? 2.0 * w : w;
+        double wgt = (gj < gi) ? 2.0 * w : w;
+        if (GOGP_EV) wgt *= event_discount(P, Mr[r], Mc[tx]);
         const double *ri = Ri + r * D;
         simil_grad_accum<ARD_D>(
             P, [&](int d) { return ri[d]; }, [&](int d) { return cj[d * 64]; }, wgt, acc, ard, ard0);
@@ -208,7 +221,20 @@ __global__ __launch_bounds__(256) void grad_reduce_kernel(
   }
 }
 
+#if !GOGP_EV  // second pass: the kernels of this file again, with event discounts, as *_ev
+#undef GOGP_EV
+#undef GOGP_EVN
+#define GOGP_EV 1
+#define GOGP_EVN(name) name##_ev
+#include "grad.hip"
+#undef GOGP_EV
+#undef GOGP_EVN
+#define GOGP_EV 0
+#define GOGP_EVN(name) name
+#endif
+
 #ifndef GOGP_GRAD_KERNEL_ONLY  // (the hook library includes this file for the reduction kernel template alone)
+#if !GOGP_EV
 // out[q] = sum over blocks of partials[b][q]; one workgroup per slot q, fixed
 // summation tree (bitwise reproducible)
 __global__ __launch_bounds__(256) void grad_final_kernel(const double *__restrict__ partials,
@@ -229,23 +255,28 @@ __global__ __launch_bounds__(256) void grad_final_kernel(const double *__restric
 
 // dynamic LDS of one instance: Ri [64][D], CjT [D + AD][64], ai, aj, red [4][NACC] -- sized per instance (an isotropic
 // kernel at D = 8 asks for 11.8 KB, not for the 32-slot instance's 28 KB: the LDS occupancy ceiling of the hot path)
-static inline size_t gr_lds_bytes(int ndim, int ad) {
-  return (size_t)(128 * ndim + 64 * ad + 128 + 4 * NACC) * sizeof(double);
+static inline size_t gr_lds_bytes(int ndim, int ad, bool ev = false) {
+  return (size_t)(128 * ndim + 64 * ad + 128 + 4 * NACC + (ev ? 128 : 0)) * sizeof(double);  // (the masks: 8 bytes each)
 }
 // launch one instance; above 64 KB of dynamic LDS (ndim >= 45 with 32 slots) the limit is raised explicitly, as
 // launch_xgrad and grad_mfma.hip do, instead of relying on what the runtime tolerates
-template <int AD, bool LOCAL, class KT, bool R1, class... Args>
+template <int AD, bool LOCAL, class KT, bool R1, bool EV = false, class... Args>
 static void gr_launch(dim3 grid, hipStream_t s, int ndim, Args... args) {
-  const size_t lds = gr_lds_bytes(ndim, AD);
+  const size_t lds = gr_lds_bytes(ndim, AD, EV);
   if (lds > 64 * 1024) {
     static bool raised = false;  // per instance (template): the attribute sticks to the function
     if (!raised) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&grad_reduce_kernel<AD, LOCAL, KT, R1>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)gr_lds_bytes(GOGP_MAX_NDIM, AD));
+      const void *fn;
+      if constexpr (EV) fn = reinterpret_cast<const void *>(&grad_reduce_kernel_ev<AD, LOCAL, KT, R1>);
+      else fn = reinterpret_cast<const void *>(&grad_reduce_kernel<AD, LOCAL, KT, R1>);
+      (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gr_lds_bytes(GOGP_MAX_NDIM, AD, EV));
       raised = true;
     }
   }
-  GOGP_KLAUNCH((grad_reduce_kernel<AD, LOCAL, KT, R1>), grid, dim3(256), lds, s, args...);
+  if constexpr (EV)
+    GOGP_KLAUNCH((grad_reduce_kernel_ev<AD, LOCAL, KT, R1>), grid, dim3(256), lds, s, args...);
+  else
+    GOGP_KLAUNCH((grad_reduce_kernel<AD, LOCAL, KT, R1>), grid, dim3(256), lds, s, args...);
 }
 
 int grad_reduce_blocks(int64_t npad) {
@@ -257,7 +288,8 @@ int grad_reduce_blocks(int64_t npad) {
 template <class KT>
 static void grad_reduce_t(hipStream_t s, const DevParams *p, int ndim, int ard_dims,
                           const double *X, const double *alpha, const KT *Kinv, int64_t ld,
-                          int64_t n, int64_t npad, double *partials, double *out, bool radial1, int mfma_min) {
+                          int64_t n, int64_t npad, double *partials, double *out, bool radial1, int mfma_min,
+                          bool ev) {
   const int nt = (int)(npad / 64);
   const int ntiles = nt * (nt + 1) / 2;
   const int blocks = grad_reduce_blocks(npad);
@@ -275,7 +307,14 @@ static void grad_reduce_t(hipStream_t s, const DevParams *p, int ndim, int ard_d
       gr_launch<AD, false, KT, false>(dim3(blocks, 1, nz), s, ndim, p, X, alpha, Kinv, (long)ld, (long)n, nt, ntiles, \
                                       partials, 0, BlockMap(), (int)(A0), (long)tl_batch.stride);  \
   } while (0)
-  if (radial1 && ard_dims > 0 && ard_dims >= mfma_min)
+  if (ev) {  // event discounts (never with ARD: gogp_set_events)
+    if (radial1)
+      gr_launch<0, false, KT, true, true>(dim3(blocks, 1, nz), s, ndim, p, X, alpha, Kinv, (long)ld, (long)n, nt, ntiles,
+                                          partials, 0, BlockMap(), 0, (long)tl_batch.stride);
+    else
+      gr_launch<0, false, KT, false, true>(dim3(blocks, 1, nz), s, ndim, p, X, alpha, Kinv, (long)ld, (long)n, nt, ntiles,
+                                           partials, 0, BlockMap(), 0, (long)tl_batch.stride);
+  } else if (radial1 && ard_dims > 0 && ard_dims >= mfma_min)
     // one radial term, many ARD length scales: distances and per-dimension sums on the matrix cores
     launch_grad_ard_mfma(s, p, ndim, X, alpha, Kinv, ld, n, nt, 0, ntiles, blocks, BlockMap(), partials);
   else if (ard_dims <= 0) GOGP_LAUNCH_GR(0, 0);
@@ -303,13 +342,13 @@ static void grad_reduce_t(hipStream_t s, const DevParams *p, int ndim, int ard_d
 }
 void launch_grad_reduce(hipStream_t s, const DevParams *p, int ndim, int ard_dims,
                         const double *X, const double *alpha, const double *Kinv, int64_t ld,
-                        int64_t n, int64_t npad, double *partials, double *out, bool radial1, int mfma_min) {
-  grad_reduce_t(s, p, ndim, ard_dims, X, alpha, Kinv, ld, n, npad, partials, out, radial1, mfma_min);
+                        int64_t n, int64_t npad, double *partials, double *out, bool radial1, int mfma_min, bool ev) {
+  grad_reduce_t(s, p, ndim, ard_dims, X, alpha, Kinv, ld, n, npad, partials, out, radial1, mfma_min, ev);
 }
 void launch_grad_reduce(hipStream_t s, const DevParams *p, int ndim, int ard_dims,
                         const double *X, const double *alpha, const float *Kinv, int64_t ld,
-                        int64_t n, int64_t npad, double *partials, double *out, bool radial1, int mfma_min) {
-  grad_reduce_t(s, p, ndim, ard_dims, X, alpha, Kinv, ld, n, npad, partials, out, radial1, mfma_min);
+                        int64_t n, int64_t npad, double *partials, double *out, bool radial1, int mfma_min, bool ev) {
+  grad_reduce_t(s, p, ndim, ard_dims, X, alpha, Kinv, ld, n, npad, partials, out, radial1, mfma_min, ev);
 }
 
 int grad_reduce_blocks_local(int64_t mrows, int64_t ncols) {
@@ -321,7 +360,7 @@ template <class KT>
 static void grad_reduce_local_t(hipStream_t s, const DevParams *p, int ndim, int ard_dims,
                                 const double *X, const double *alpha, const KT *Kinv, int64_t ld,
                                 int64_t n, int64_t mrows, int64_t ncols, BlockMap map, double *partials,
-                                double *out, bool radial1, int mfma_min) {
+                                double *out, bool radial1, int mfma_min, bool ev) {
   const int nt = (int)(mrows / 64), ntc = (int)(ncols / 64);
   const int ntiles = nt * ntc;
   const int blocks = grad_reduce_blocks_local(mrows, ncols);
@@ -334,7 +373,14 @@ static void grad_reduce_local_t(hipStream_t s, const DevParams *p, int ndim, int
       gr_launch<AD, true, KT, false>(dim3(blocks), s, ndim, p, X, alpha, Kinv, (long)ld, (long)n, nt, ntiles, partials, \
                                      ntc, map, (int)(A0), 0L);                                     \
   } while (0)
-  if (radial1 && ard_dims > 0 && ard_dims >= mfma_min)
+  if (ev) {  // event discounts (never with ARD: gogp_set_events)
+    if (radial1)
+      gr_launch<0, true, KT, true, true>(dim3(blocks), s, ndim, p, X, alpha, Kinv, (long)ld, (long)n, nt, ntiles, partials,
+                                         ntc, map, 0, 0L);
+    else
+      gr_launch<0, true, KT, false, true>(dim3(blocks), s, ndim, p, X, alpha, Kinv, (long)ld, (long)n, nt, ntiles, partials,
+                                          ntc, map, 0, 0L);
+  } else if (radial1 && ard_dims > 0 && ard_dims >= mfma_min)
     launch_grad_ard_mfma(s, p, ndim, X, alpha, Kinv, ld, n, nt, ntc, ntiles, blocks, map, partials);
   else if (ard_dims <= 0) GOGP_LAUNCH_GRL(0, 0);
   else if (ard_dims <= 8) GOGP_LAUNCH_GRL(8, 0);
@@ -359,14 +405,16 @@ static void grad_reduce_local_t(hipStream_t s, const DevParams *p, int ndim, int
 void launch_grad_reduce_local(hipStream_t s, const DevParams *p, int ndim, int ard_dims,
                               const double *X, const double *alpha, const double *Kinv, int64_t ld,
                               int64_t n, int64_t mrows, int64_t ncols, BlockMap map, double *partials,
-                              double *out, bool radial1, int mfma_min) {
-  grad_reduce_local_t(s, p, ndim, ard_dims, X, alpha, Kinv, ld, n, mrows, ncols, map, partials, out, radial1, mfma_min);
+                              double *out, bool radial1, int mfma_min, bool ev) {
+  grad_reduce_local_t(s, p, ndim, ard_dims, X, alpha, Kinv, ld, n, mrows, ncols, map, partials, out, radial1, mfma_min,
+                      ev);
 }
 void launch_grad_reduce_local(hipStream_t s, const DevParams *p, int ndim, int ard_dims,
                               const double *X, const double *alpha, const float *Kinv, int64_t ld,
                               int64_t n, int64_t mrows, int64_t ncols, BlockMap map, double *partials,
-                              double *out, bool radial1, int mfma_min) {
-  grad_reduce_local_t(s, p, ndim, ard_dims, X, alpha, Kinv, ld, n, mrows, ncols, map, partials, out, radial1, mfma_min);
+                              double *out, bool radial1, int mfma_min, bool ev) {
+  grad_reduce_local_t(s, p, ndim, ard_dims, X, alpha, Kinv, ld, n, mrows, ncols, map, partials, out, radial1, mfma_min,
+                      ev);
 }
 
 // ---- gradient w.r.t. the inputs (full Observe form) ------------------------------
@@ -395,8 +443,11 @@ __global__ __launch_bounds__(256) void mirror_lower_kernel(double *__restrict__ 
   for (int r = 0; r < 32; r += 8) A[(long)(tj * 32 + ty + r) * ld + ti * 32 + tx] = tile[tx][ty + r];
 }
 
+#endif  // !GOGP_EV
+
+// GOGP_EV = 1 (xgrad_kernel_ev): event discounts (kern_eval.h: event_mask), W_ij is multiplied by the pair's discount
 template <int DMAX>
-__global__ __launch_bounds__(256) void xgrad_kernel(const DevParams *__restrict__ Pp,
+__global__ __launch_bounds__(256) void GOGP_EVN(xgrad_kernel)(const DevParams *__restrict__ Pp,
                                                     const double *__restrict__ X,
                                                     const double *__restrict__ alpha,
                                                     const double *__restrict__ Kinv, long ld,
@@ -408,6 +459,7 @@ __global__ __launch_bounds__(256) void xgrad_kernel(const DevParams *__restrict_
   double *Xj = Xi + 64 * D;      // [64][D]
   double *T = Xj + 64 * D;       // [64][65]  W tile
   double *aj = T + 64 * 65;      // [64]
+  unsigned long long *Mj = reinterpret_cast<unsigned long long *>(aj + 64);  // GOGP_EV: [64] column masks
   const int tid = threadIdx.x;
   const long r0 = (long)blockIdx.x * 64;
   const int r = tid >> 2, q = tid & 3;
@@ -416,6 +468,7 @@ __global__ __launch_bounds__(256) void xgrad_kernel(const DevParams *__restrict_
     Xi[idx] = (r0 + rr < n) ? X[(r0 + rr) * D + d] : 0.0;
   }
   const double ai = (r0 + r < n) ? alpha[r0 + r] : 0.0;
+  const unsigned long long mi = GOGP_EV ? event_mask(P, (r0 + r < n) ? X[(r0 + r) * D + P.ev_axis] : 0.0) : 0ull;
   double acc[DMAX];
 #pragma unroll
   for (int d = 0; d < DMAX; ++d) acc[d] = 0.0;
@@ -427,6 +480,7 @@ __global__ __launch_bounds__(256) void xgrad_kernel(const DevParams *__restrict_
       Xj[idx] = (c0 + rr < n) ? X[(c0 + rr) * D + d] : 0.0;
     }
     if (tid < 64) aj[tid] = (c0 + tid < n) ? alpha[c0 + tid] : 0.0;
+    else if (GOGP_EV && tid < 128) Mj[tid - 64] = event_mask(P, (c0 + tid - 64 < n) ? X[(c0 + tid - 64) * D + P.ev_axis] : 0.0);
     for (int idx = tid; idx < 64 * 64; idx += 256) {
       const int rr = idx >> 6, cc = idx & 63;
       T[rr * 65 + cc] = Kinv[(r0 + rr) * ld + c0 + cc];
@@ -436,7 +490,8 @@ __global__ __launch_bounds__(256) void xgrad_kernel(const DevParams *__restrict_
       for (int jj = 0; jj < 16; ++jj) {
         const int j = q * 16 + jj;
         if (c0 + j < n && c0 + j != r0 + r) {
-          const double W = ai * aj[j] - T[r * 65 + j];
+          double W = ai * aj[j] - T[r * 65 + j];
+          if (GOGP_EV) W *= event_discount(P, mi, Mj[j]);
           const double *xj = Xj + j * D;
           simil_xgrad_accum<DMAX>(
               P, [&](int d) { return xi[d]; }, [&](int d) { return xj[d]; }, W, acc, d0);
@@ -453,9 +508,10 @@ __global__ __launch_bounds__(256) void xgrad_kernel(const DevParams *__restrict_
   }
 }
 
+#if !GOGP_EV
 void launch_xgrad(hipStream_t s, const DevParams *p, int ndim, const double *X,
                   const double *alpha, double *Kinv, int64_t ld, int64_t n, int64_t npad,
-                  double *gx) {
+                  double *gx, bool ev) {
   const int nt32 = (int)(npad / 32);
   GOGP_KLAUNCH(mirror_lower_kernel, dim3(nt32 * (nt32 + 1) / 2), dim3(256), 0, s, Kinv,
                      (long)ld, nt32);
@@ -473,7 +529,24 @@ void launch_xgrad(hipStream_t s, const DevParams *p, int ndim, const double *X,
   // more than 32 dimensions: passes of 32 (a 64-accumulator instance needs 326 VGPRs, AGPRs included,
   // and 128 SGPR spills -- the register footprint that produced wrong sums in the parameter-gradient
   // reduction; see launch_grad_reduce)
-  if (ndim <= 4) GOGP_LAUNCH_XG(4, 0);
+  if (ev) {
+    // event discounts: instances of up to 16 accumulators, passes of 16 beyond (inside the SGPR spill limit without an
+    // allow-list entry)
+    const size_t ldse = lds + 64 * sizeof(unsigned long long);
+#define GOGP_LAUNCH_XGE(DM, D0)                                                                 \
+  do {                                                                                          \
+    if (ldse > 64 * 1024)                                                                       \
+      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&xgrad_kernel_ev<DM>),        \
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldse);         \
+    GOGP_KLAUNCH((xgrad_kernel_ev<DM>), grid, dim3(256), ldse, s, p, X, alpha, Kinv, (long)ld, \
+                 (long)n, (long)npad, gx, D0);                                                  \
+  } while (0)
+    if (ndim <= 4) GOGP_LAUNCH_XGE(4, 0);
+    else if (ndim <= 8) GOGP_LAUNCH_XGE(8, 0);
+    else
+      for (int d0 = 0; d0 < ndim; d0 += 16) GOGP_LAUNCH_XGE(16, d0);
+#undef GOGP_LAUNCH_XGE
+  } else if (ndim <= 4) GOGP_LAUNCH_XG(4, 0);
   else if (ndim <= 8) GOGP_LAUNCH_XG(8, 0);
   else if (ndim <= 16) GOGP_LAUNCH_XG(16, 0);
   else
@@ -481,6 +554,11 @@ void launch_xgrad(hipStream_t s, const DevParams *p, int ndim, const double *X,
 #undef GOGP_LAUNCH_XG
 }
 
+#endif  // !GOGP_EV
 #endif  // GOGP_GRAD_KERNEL_ONLY
 
+#if !GOGP_EV
 }  // namespace gogp
+#undef GOGP_EV
+#undef GOGP_EVN
+#endif

@@ -8,21 +8,31 @@
 //   gram_kernel<true>: cross-covariance for Produce, stored transposed,
 //       KsT[j][i] = Simil(x_i, z_j)                    gp/gp.go:322-332
 //   prior_kernel: k(z_j, z_j)                          gp/gp.go:269-278
+//     (never discounted by events: equal points lie on the same side of every boundary)
+//
+// Event discounts (kern_eval.h: event_mask): the kernels below are compiled twice -- the file includes itself once,
+// below, with GOGP_EV = 1.  gram_kernel, gram_local_kernel and kmatvec_kernel are compiled without them, exactly as
+// before; gram_kernel_ev, gram_local_kernel_ev and kmatvec_kernel_ev with them, staging the tile's row and column
+// masks in LDS behind the inputs.
 //
 // Layout: one workgroup = 64x64 tile, 256 threads.  The row inputs are staged
 // in LDS row-major (read as wave-uniform broadcasts), the column inputs
 // transposed [d][col] so that the 64 lanes of a wave read consecutive
 // addresses; each wave writes 512 contiguous bytes per output row.
+#ifndef GOGP_EV  // first pass: the whole file, the kernels without event discounts
 #include <algorithm>
 
 #include "kern_eval.h"
 
+#define GOGP_EV 0
+#define GOGP_EVN(name) name
 namespace gogp {
+#endif
 
 // T: element type of the output matrix (double, or float on the fp32 path: the kernel value
 // is computed in fp64 from the fp64 inputs and rounded once on store)
 template <bool CROSS, class T>
-__global__ __launch_bounds__(256) void gram_kernel(const DevParams *__restrict__ Pp,
+__global__ __launch_bounds__(256) void GOGP_EVN(gram_kernel)(const DevParams *__restrict__ Pp,
                                                    const double *__restrict__ Rsrc, long nrows,
                                                    const double *__restrict__ Csrc, long ncols,
                                                    T *__restrict__ Out, long ld, int ntc,
@@ -33,6 +43,7 @@ __global__ __launch_bounds__(256) void gram_kernel(const DevParams *__restrict__
   const int D = P.ndim;
   double *Ri = sm;            // [64][D]
   double *CjT = sm + 64 * D;  // [D][64]
+  unsigned long long *Mr = reinterpret_cast<unsigned long long *>(CjT + 64 * D), *Mc = Mr + 64;  // GOGP_EV: [64] each
   const int tid = threadIdx.x;
   int ti, tj;
   if (CROSS) {
@@ -66,6 +77,10 @@ __global__ __launch_bounds__(256) void gram_kernel(const DevParams *__restrict__
   for (int idx = tid; idx < 64 * D; idx += 256) {
     const int d = idx >> 6, r = idx & 63;
     CjT[idx] = (c0 + r < ncols) ? Csrc[(c0 + r) * D + d] : 0.0;
+  }
+  if (GOGP_EV) {
+    if (tid < 64) Mr[tid] = event_mask(P, (r0 + tid < nrows) ? Rsrc[(r0 + tid) * D + P.ev_axis] : 0.0);
+    else if (tid < 128) Mc[tid - 64] = event_mask(P, (c0 + tid - 64 < ncols) ? Csrc[(c0 + tid - 64) * D + P.ev_axis] : 0.0);
   }
   __syncthreads();
   const int tx = tid & 63, ty = tid >> 6;
@@ -101,6 +116,7 @@ __global__ __launch_bounds__(256) void gram_kernel(const DevParams *__restrict__
         double f, dfdr2;
         radial_eval(kind, s[rr], f, dfdr2);
         k = 0.0 + c0s * f;
+        if (GOGP_EV) k *= event_discount(P, Mr[rbase + rr], Mc[tx]);
         if (gi == gj) k += P.noise_var;
       } else {
         k = (gi == gj) ? 1.0 : 0.0;
@@ -118,6 +134,7 @@ __global__ __launch_bounds__(256) void gram_kernel(const DevParams *__restrict__
     if (gi < nrows && gj < ncols) {
       k = simil_value(
           P, [&](int d) { return ri[d]; }, [&](int d) { return cj[d * 64]; });
+      if (GOGP_EV) k *= event_discount(P, Mr[r], Mc[tx]);
       if (!CROSS && gi == gj) k += P.noise_var;
     } else {
       k = (!CROSS && gi == gj) ? 1.0 : 0.0;
@@ -129,7 +146,7 @@ __global__ __launch_bounds__(256) void gram_kernel(const DevParams *__restrict__
 // 2-D block-cyclic variant: rectangular grid over the LOCAL 64x64 tiles, global indices
 // through the block map (see common.h).
 template <class T>
-__global__ __launch_bounds__(256) void gram_local_kernel(const DevParams *__restrict__ Pp,
+__global__ __launch_bounds__(256) void GOGP_EVN(gram_local_kernel)(const DevParams *__restrict__ Pp,
                                                          const double *__restrict__ X, long n,
                                                          T *__restrict__ Out, long ld, int ntc,
                                                          BlockMap map) {
@@ -138,6 +155,7 @@ __global__ __launch_bounds__(256) void gram_local_kernel(const DevParams *__rest
   const int D = P.ndim;
   double *Ri = sm;
   double *CjT = sm + 64 * D;
+  unsigned long long *Mr = reinterpret_cast<unsigned long long *>(CjT + 64 * D), *Mc = Mr + 64;  // GOGP_EV: [64] each
   const int tid = threadIdx.x;
   const int ti = blockIdx.x / ntc, tj = blockIdx.x - ti * ntc;
   const long lr0 = (long)ti * 64, lc0 = (long)tj * 64;
@@ -156,6 +174,10 @@ __global__ __launch_bounds__(256) void gram_local_kernel(const DevParams *__rest
   for (int idx = tid; idx < 64 * D; idx += 256) {  // lanes along a row of CjT: conflict-free stores (gram_kernel)
     const int d = idx >> 6, r = idx & 63;
     CjT[idx] = (c0 + r < n) ? X[(c0 + r) * D + d] : 0.0;
+  }
+  if (GOGP_EV) {
+    if (tid < 64) Mr[tid] = event_mask(P, (r0 + tid < n) ? X[(r0 + tid) * D + P.ev_axis] : 0.0);
+    else if (tid < 128) Mc[tid - 64] = event_mask(P, (c0 + tid - 64 < n) ? X[(c0 + tid - 64) * D + P.ev_axis] : 0.0);
   }
   __syncthreads();
   const long gj = c0 + tx;
@@ -186,6 +208,7 @@ __global__ __launch_bounds__(256) void gram_local_kernel(const DevParams *__rest
         double f, dfdr2;
         radial_eval(kind, s[rr], f, dfdr2);
         k = 0.0 + c0s * f;
+        if (GOGP_EV) k *= event_discount(P, Mr[rbase + rr], Mc[tx]);
         if (gi == gj) k += P.noise_var;
       } else {
         k = (gi == gj) ? 1.0 : 0.0;
@@ -203,6 +226,7 @@ __global__ __launch_bounds__(256) void gram_local_kernel(const DevParams *__rest
     if (gi < n && gj < n) {
       k = simil_value(
           P, [&](int d) { return ri[d]; }, [&](int d) { return cj[d * 64]; });
+      if (GOGP_EV) k *= event_discount(P, Mr[r], Mc[tx]);
       if (gi == gj) k += P.noise_var;
     } else {
       k = (gi == gj) ? 1.0 : 0.0;
@@ -217,7 +241,7 @@ __global__ __launch_bounds__(256) void gram_local_kernel(const DevParams *__rest
 // fp32 copy.  One workgroup = 64 rows x one slab of column tiles; the slabs are summed (fixed
 // order) by kmatvec_finish_kernel, which also forms r = y - K v.
 template <bool RADIAL1>
-__global__ __launch_bounds__(256) void kmatvec_kernel(const DevParams *__restrict__ Pp,
+__global__ __launch_bounds__(256) void GOGP_EVN(kmatvec_kernel)(const DevParams *__restrict__ Pp,
                                                       const double *__restrict__ X, long n,
                                                       const double *__restrict__ v, long npad,
                                                       int tiles_per_slab, double *__restrict__ part,
@@ -230,6 +254,7 @@ __global__ __launch_bounds__(256) void kmatvec_kernel(const DevParams *__restric
   double *CjT = sm + 64 * D;    // [D][64] current column tile (read as broadcasts)
   double *vj = CjT + 64 * D;    // [64]
   double *red = vj + 64;        // [4][64]
+  unsigned long long *Mc = reinterpret_cast<unsigned long long *>(red + 256);  // GOGP_EV: [64] column masks
   const int tid = threadIdx.x;
   const int tx = tid & 63, ty = tid >> 6;
   const long r0 = (long)blockIdx.x * 64;
@@ -241,6 +266,7 @@ __global__ __launch_bounds__(256) void kmatvec_kernel(const DevParams *__restric
   // thread (tx, ty): row r0 + tx, columns ty*16 .. ty*16+15 of every tile
   double acc = 0.0;
   const long gi = r0 + tx;
+  const unsigned long long mrow = GOGP_EV ? event_mask(P, gi < n ? X[gi * D + P.ev_axis] : 0.0) : 0ull;
   // column tiles [tile_begin, tile_end): all of them, or one rank's share of a sharded evaluation
   for (int t = tile_begin + slab * tiles_per_slab; t < tile_begin + (slab + 1) * tiles_per_slab && t < tile_end;
        ++t) {
@@ -252,6 +278,7 @@ __global__ __launch_bounds__(256) void kmatvec_kernel(const DevParams *__restric
         CjT[idx] = (c0 + r < n) ? X[(c0 + r) * D + d] : 0.0;
       }
     if (tid < 64) vj[tid] = (c0 + tid < n) ? v[c0 + tid] : 0.0;
+    else if (GOGP_EV && tid < 128) Mc[tid - 64] = event_mask(P, (c0 + tid - 64 < n) ? X[(c0 + tid - 64) * D + P.ev_axis] : 0.0);
     __syncthreads();
     if (RADIAL1) {
       // one radial term: dimension loop outside, the thread's 16 columns inside; their coordinates
@@ -282,6 +309,7 @@ __global__ __launch_bounds__(256) void kmatvec_kernel(const DevParams *__restric
             double f, dfdr2;
             radial_eval(kind, s[cc], f, dfdr2);
             double k = 0.0 + cs * f;
+            if (GOGP_EV) k *= event_discount(P, mrow, Mc[c]);
             if (gi == gj) k += P.noise_var;
             acc += k * vj[c];
           }
@@ -296,6 +324,7 @@ __global__ __launch_bounds__(256) void kmatvec_kernel(const DevParams *__restric
           const double *cj = CjT + c;
           double k = simil_value(
               P, [&](int d) { return ri[d * 64]; }, [&](int d) { return cj[d * 64]; });
+          if (GOGP_EV) k *= event_discount(P, mrow, Mc[c]);
           if (gi == gj) k += P.noise_var;
           acc += k * vj[c];
         }
@@ -307,6 +336,16 @@ __global__ __launch_bounds__(256) void kmatvec_kernel(const DevParams *__restric
   if (ty == 0 && gi < npad)
     part[(long)slab * npad + gi] = red[tx] + red[64 + tx] + red[128 + tx] + red[192 + tx];
 }
+
+
+#if !GOGP_EV  // second pass: the kernels above again, with event discounts, as *_ev
+#undef GOGP_EV
+#undef GOGP_EVN
+#define GOGP_EV 1
+#define GOGP_EVN(name) name##_ev
+#include "gram.hip"
+#undef GOGP_EV
+#undef GOGP_EVN
 
 // r_i = y_i - sum_slab part[slab][i]  (i < n; 0 beyond); without y: the plain sum (K v over a range
 // of columns, to be all-reduced)
@@ -321,11 +360,17 @@ __global__ void kmatvec_finish_kernel(const double *__restrict__ part, int nslab
 
 void launch_residual(hipStream_t s, const DevParams *p, int ndim, const double *X, int64_t n,
                      int64_t npad, const double *v, const double *y, double *part, int nslab, double *r,
-                     bool radial1) {
+                     bool radial1, bool ev) {
   const int ntile = (int)(npad / 64);
   const int tps = (ntile + nslab - 1) / nslab;
   const size_t lds = (size_t)(128 * ndim + 64 + 256) * sizeof(double);
-  if (radial1)
+  if (ev && radial1)
+    GOGP_KLAUNCH((kmatvec_kernel_ev<true>), dim3((unsigned)ntile, (unsigned)nslab), dim3(256), lds + 64 * 8, s, p, X,
+                 (long)n, v, (long)npad, tps, part, 0, ntile);
+  else if (ev)
+    GOGP_KLAUNCH((kmatvec_kernel_ev<false>), dim3((unsigned)ntile, (unsigned)nslab), dim3(256), lds + 64 * 8, s, p, X,
+                 (long)n, v, (long)npad, tps, part, 0, ntile);
+  else if (radial1)
     GOGP_KLAUNCH(kmatvec_kernel<true>, dim3((unsigned)ntile, (unsigned)nslab), dim3(256), lds, s, p, X, (long)n,
                        v, (long)npad, tps, part, 0, ntile);
   else
@@ -340,13 +385,19 @@ void launch_residual(hipStream_t s, const DevParams *p, int ndim, const double *
 // all-reduced.
 void launch_kmatvec_share(hipStream_t s, const DevParams *p, int ndim, const double *X, int64_t n, int64_t npad,
                           const double *v, int part_idx, int nparts, double *part, int nslab, double *out,
-                          bool radial1) {
+                          bool radial1, bool ev) {
   const int ntile = (int)(npad / 64);
   const int per = (ntile + nparts - 1) / nparts;
   const int t0 = std::min(ntile, part_idx * per), t1 = std::min(ntile, (part_idx + 1) * per);
   const int tps = std::max(1, (t1 - t0 + nslab - 1) / nslab);
   const size_t lds = (size_t)(128 * ndim + 64 + 256) * sizeof(double);
-  if (radial1)
+  if (ev && radial1)
+    GOGP_KLAUNCH((kmatvec_kernel_ev<true>), dim3((unsigned)ntile, (unsigned)nslab), dim3(256), lds + 64 * 8, s, p, X,
+                 (long)n, v, (long)npad, tps, part, t0, t1);
+  else if (ev)
+    GOGP_KLAUNCH((kmatvec_kernel_ev<false>), dim3((unsigned)ntile, (unsigned)nslab), dim3(256), lds + 64 * 8, s, p, X,
+                 (long)n, v, (long)npad, tps, part, t0, t1);
+  else if (radial1)
     GOGP_KLAUNCH(kmatvec_kernel<true>, dim3((unsigned)ntile, (unsigned)nslab), dim3(256), lds, s, p, X, (long)n,
                        v, (long)npad, tps, part, t0, t1);
   else
@@ -368,16 +419,20 @@ __global__ void prior_kernel(const DevParams *__restrict__ Pp, const double *__r
 
 template <class T>
 static void gram_lower_t(hipStream_t s, const DevParams *p, int ndim, const double *X, int64_t n,
-                         int64_t npad, T *K, int64_t ld) {
+                         int64_t npad, T *K, int64_t ld, bool ev) {
   const int nt = (int)(npad / 64);
   const int ntiles = nt * (nt + 1) / 2;
   const size_t lds = (size_t)2 * 64 * ndim * sizeof(double);
-  GOGP_KLAUNCH((gram_kernel<false, T>), dim3(ntiles), dim3(256), lds, s, p, X, (long)n, X,
-                     (long)n, K, (long)ld, nt, 0, 0, 0L);
+  if (ev)
+    GOGP_KLAUNCH((gram_kernel_ev<false, T>), dim3(ntiles), dim3(256), lds + 128 * 8, s, p, X, (long)n, X, (long)n, K,
+                 (long)ld, nt, 0, 0, 0L);
+  else
+    GOGP_KLAUNCH((gram_kernel<false, T>), dim3(ntiles), dim3(256), lds, s, p, X, (long)n, X,
+                       (long)n, K, (long)ld, nt, 0, 0, 0L);
 }
 void launch_gram_lower(hipStream_t s, const DevParams *p, int ndim, const double *X, int64_t n,
-                       int64_t npad, double *K, int64_t ld) {
-  gram_lower_t(s, p, ndim, X, n, npad, K, ld);
+                       int64_t npad, double *K, int64_t ld, bool ev) {
+  gram_lower_t(s, p, ndim, X, n, npad, K, ld, ev);
 }
 
 // The same lower triangle in two launches: block columns [0, wcols) on `s_first` (the panel
@@ -386,63 +441,79 @@ void launch_gram_lower(hipStream_t s, const DevParams *p, int ndim, const double
 template <class T>
 static void gram_lower_split_t(hipStream_t s_first, hipStream_t s_rest, const DevParams *p, int ndim,
                                const double *X, int64_t n, int64_t npad, T *K, int64_t ld,
-                               int64_t wcols) {
+                               int64_t wcols, bool ev) {
   const int nt = (int)(npad / 64);
   int w = (int)(wcols / 64);
   if (w > nt) w = nt;
   const size_t lds = (size_t)2 * 64 * ndim * sizeof(double);
   const unsigned nz = (unsigned)tl_batch.k;
+  const int nr = nt - w;
+  if (ev) {
+    GOGP_KLAUNCH((gram_kernel_ev<false, T>), dim3(nt * w, 1, nz), dim3(256), lds + 128 * 8, s_first, p, X, (long)n, X,
+                 (long)n, K, (long)ld, nt, w, 0, tl_batch.stride);
+    if (nr > 0)
+      GOGP_KLAUNCH((gram_kernel_ev<false, T>), dim3(nr * (nr + 1) / 2, 1, nz), dim3(256), lds + 128 * 8, s_rest, p, X,
+                   (long)n, X, (long)n, K, (long)ld, nt, 0, w, tl_batch.stride);
+    return;
+  }
   GOGP_KLAUNCH((gram_kernel<false, T>), dim3(nt * w, 1, nz), dim3(256), lds, s_first, p, X, (long)n, X,
                      (long)n, K, (long)ld, nt, w, 0, tl_batch.stride);
-  const int nr = nt - w;
   if (nr > 0)
     GOGP_KLAUNCH((gram_kernel<false, T>), dim3(nr * (nr + 1) / 2, 1, nz), dim3(256), lds, s_rest, p, X,
                        (long)n, X, (long)n, K, (long)ld, nt, 0, w, tl_batch.stride);
 }
 void launch_gram_lower_split(hipStream_t s_first, hipStream_t s_rest, const DevParams *p, int ndim,
                              const double *X, int64_t n, int64_t npad, double *K, int64_t ld,
-                             int64_t wcols) {
-  gram_lower_split_t(s_first, s_rest, p, ndim, X, n, npad, K, ld, wcols);
+                             int64_t wcols, bool ev) {
+  gram_lower_split_t(s_first, s_rest, p, ndim, X, n, npad, K, ld, wcols, ev);
 }
 void launch_gram_lower_split(hipStream_t s_first, hipStream_t s_rest, const DevParams *p, int ndim,
                              const double *X, int64_t n, int64_t npad, float *K, int64_t ld,
-                             int64_t wcols) {
-  gram_lower_split_t(s_first, s_rest, p, ndim, X, n, npad, K, ld, wcols);
+                             int64_t wcols, bool ev) {
+  gram_lower_split_t(s_first, s_rest, p, ndim, X, n, npad, K, ld, wcols, ev);
 }
 
 template <class T>
 static void gram_local_t(hipStream_t s, const DevParams *p, int ndim, const double *X, int64_t n,
-                         int64_t mrows, int64_t ncols, BlockMap map, T *K, int64_t ld) {
+                         int64_t mrows, int64_t ncols, BlockMap map, T *K, int64_t ld, bool ev) {
   const int ntr = (int)(mrows / 64), ntc = (int)(ncols / 64);
   if (ntr <= 0 || ntc <= 0) return;
   const size_t lds = (size_t)2 * 64 * ndim * sizeof(double);
-  GOGP_KLAUNCH(gram_local_kernel<T>, dim3(ntr * ntc), dim3(256), lds, s, p, X, (long)n, K, (long)ld,
-                     ntc, map);
+  if (ev)
+    GOGP_KLAUNCH((gram_local_kernel_ev<T>), dim3(ntr * ntc), dim3(256), lds + 128 * 8, s, p, X, (long)n, K, (long)ld,
+                 ntc, map);
+  else
+    GOGP_KLAUNCH(gram_local_kernel<T>, dim3(ntr * ntc), dim3(256), lds, s, p, X, (long)n, K, (long)ld,
+                       ntc, map);
 }
 void launch_gram_local(hipStream_t s, const DevParams *p, int ndim, const double *X, int64_t n,
-                       int64_t mrows, int64_t ncols, BlockMap map, double *K, int64_t ld) {
-  gram_local_t(s, p, ndim, X, n, mrows, ncols, map, K, ld);
+                       int64_t mrows, int64_t ncols, BlockMap map, double *K, int64_t ld, bool ev) {
+  gram_local_t(s, p, ndim, X, n, mrows, ncols, map, K, ld, ev);
 }
 void launch_gram_local(hipStream_t s, const DevParams *p, int ndim, const double *X, int64_t n,
-                       int64_t mrows, int64_t ncols, BlockMap map, float *K, int64_t ld) {
-  gram_local_t(s, p, ndim, X, n, mrows, ncols, map, K, ld);
+                       int64_t mrows, int64_t ncols, BlockMap map, float *K, int64_t ld, bool ev) {
+  gram_local_t(s, p, ndim, X, n, mrows, ncols, map, K, ld, ev);
 }
 
 template <class T>
 static void cross_t(hipStream_t s, const DevParams *p, int ndim, const double *X, int64_t n,
-                    int64_t npad, const double *Z, int64_t m, int64_t mpad, T *KsT, int64_t ld) {
+                    int64_t npad, const double *Z, int64_t m, int64_t mpad, T *KsT, int64_t ld, bool ev) {
   const int ntr = (int)(mpad / 64), ntc = (int)(npad / 64);
   const size_t lds = (size_t)2 * 64 * ndim * sizeof(double);
-  GOGP_KLAUNCH((gram_kernel<true, T>), dim3(ntr * ntc), dim3(256), lds, s, p, Z, (long)m, X,
-                     (long)n, KsT, (long)ld, ntc, 0, 0, 0L);
+  if (ev)
+    GOGP_KLAUNCH((gram_kernel_ev<true, T>), dim3(ntr * ntc), dim3(256), lds + 128 * 8, s, p, Z, (long)m, X, (long)n, KsT,
+                 (long)ld, ntc, 0, 0, 0L);
+  else
+    GOGP_KLAUNCH((gram_kernel<true, T>), dim3(ntr * ntc), dim3(256), lds, s, p, Z, (long)m, X,
+                       (long)n, KsT, (long)ld, ntc, 0, 0, 0L);
 }
 void launch_cross(hipStream_t s, const DevParams *p, int ndim, const double *X, int64_t n,
-                  int64_t npad, const double *Z, int64_t m, int64_t mpad, double *KsT, int64_t ld) {
-  cross_t(s, p, ndim, X, n, npad, Z, m, mpad, KsT, ld);
+                  int64_t npad, const double *Z, int64_t m, int64_t mpad, double *KsT, int64_t ld, bool ev) {
+  cross_t(s, p, ndim, X, n, npad, Z, m, mpad, KsT, ld, ev);
 }
 void launch_cross(hipStream_t s, const DevParams *p, int ndim, const double *X, int64_t n,
-                  int64_t npad, const double *Z, int64_t m, int64_t mpad, float *KsT, int64_t ld) {
-  cross_t(s, p, ndim, X, n, npad, Z, m, mpad, KsT, ld);
+                  int64_t npad, const double *Z, int64_t m, int64_t mpad, float *KsT, int64_t ld, bool ev) {
+  cross_t(s, p, ndim, X, n, npad, Z, m, mpad, KsT, ld, ev);
 }
 
 void launch_prior(hipStream_t s, const DevParams *p, const double *Z, int64_t m,
@@ -453,3 +524,4 @@ void launch_prior(hipStream_t s, const DevParams *p, const double *Z, int64_t m,
 }
 
 }  // namespace gogp
+#endif  // !GOGP_EV

@@ -22,6 +22,11 @@ struct gogp_handle {
   int ns = 0, nn = 0, P = 0, D = 0;
   int ard_dims = 0;
   bool radial1 = false;  // the similarity kernel is one radial (non-periodic) term: restructured O(N^2) kernels
+  // event discounts (gogp_set_events): nevents x {from, to, discount} on input dimension ev_axis; > 0 selects the
+  // *_ev_kernel instances of every kernel that evaluates the similarity
+  int nevents = 0, ev_axis = 0;
+  double events[GOGP_MAX_EVENTS][3] = {};
+  bool ev() const { return nevents > 0; }
   int64_t n = 0, npad = 0;
   int nblk = 0;  // 128-blocks
   // device buffers

@@ -39,6 +39,28 @@ __device__ __forceinline__ void radial_eval(int kind, double r2, double &f, doub
   }
 }
 
+// ---- event discounts (tutorial/events/kernel/kernel.go:33-44) -------------------------------------------------------
+// The reference swaps the pair's coordinates so that xa <= xb and walks the events: the first with xa < from <= xb or
+// xa < to <= xb multiplies k by its discount, then it stops.  Per point x (coordinate ev_axis) bit 2e of the mask is
+// (from_e <= x) and bit 2e+1 is (to_e <= x); for xa <= xb, "xa < from_e <= xb" is exactly "bit 2e differs between the two
+// masks" (the same for to_e).  So a pair is discounted iff ma ^ mb != 0, by the event ctz(ma ^ mb) >> 1 -- the first in
+// list order, the reference's `break`.  Equal points never are.  Masks depend on X and the events only: the kernels
+// form them once per point and tile (2 * nevents compares, shared by the 64 partners of the tile), and a pair costs one
+// XOR and, when discounted, one table read.
+__device__ __forceinline__ unsigned long long event_mask(const DevParams &P, double x) {
+  unsigned long long m = 0;
+  for (int e = 0; e < P.nevents; ++e) {
+    m |= (unsigned long long)(P.ev_from[e] <= x) << (2 * e);
+    m |= (unsigned long long)(P.ev_to[e] <= x) << (2 * e + 1);
+  }
+  return m;
+}
+// the factor of the pair with masks ma, mb (1 when no event lies between them)
+__device__ __forceinline__ double event_discount(const DevParams &P, unsigned long long ma, unsigned long long mb) {
+  const unsigned long long m = ma ^ mb;
+  return m ? P.ev_disc[__builtin_ctzll(m) >> 1] : 1.0;
+}
+
 // value only.  xa(d), xb(d): accessors of the two inputs' coordinates.
 template <class FA, class FB>
 __device__ __forceinline__ double simil_value(const DevParams &P, FA xa, FB xb) {

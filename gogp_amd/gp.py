@@ -91,6 +91,10 @@ class GP:
         self.precision = int(precision)
         if self.precision != 64:
             self._check(L.gogp_set_option(self._h, b"precision", self.precision))
+        events = getattr(Simil, "events", None)
+        if events:  # kernel.Events: the discounts of tutorial/events/kernel/kernel.go:14-44 (gogp_set_events)
+            ev = np.ascontiguousarray(np.asarray(events, dtype=np.float64).reshape(-1, 3))
+            self._check(L.gogp_set_events(self._h, _dp(ev), len(ev), int(Simil.event_axis)))
         self._X = np.zeros((0, self.NDim))
         self._Y = np.zeros((0,))
         self._data_dirty = True

@@ -162,6 +162,13 @@ class GP {
   // an exception -- for sums of terms, whose scale components would come off the float K^-1 at 1.9e-4)
   void SetOption(const char *name, int64_t value) { check(gogp_set_option(h_, name, value)); }
 
+  // event discounts of tutorial/events/kernel/kernel.go:14-44 (gogp_set_events): events holds nevents
+  // {from, to, discount} triples on input dimension `axis`; an empty vector clears them
+  void SetEvents(const std::vector<double> &events, int axis = 0) {
+    if (events.size() % 3) throw Error(GOGP_EARG, "SetEvents: events must be {from, to, discount} triples");
+    check(gogp_set_events(h_, events.empty() ? nullptr : events.data(), (int)(events.size() / 3), axis));
+  }
+
   gogp_handle *handle() { return h_; }
 
  private:

@@ -18,6 +18,8 @@ Composition mirrors what the reference's tutorials do in Go source:
   * ``ScaledNoise(s)`` -> ``s * UniformNoise.Observe`` (tutorial/barebones/kernel/kernel.go:25-31)
   * ``ARD(k, ndim)``   -> one length scale per input dimension (build-defined,
                           SURVEY.md section 8d: the reference primitives are 1-D).
+  * ``Events(k, ev)``  -> similarity discounted across event boundaries
+                          (tutorial/events/kernel/kernel.go:14-44; gogp_set_events).
 """
 from __future__ import annotations
 
@@ -29,6 +31,7 @@ from typing import List, Optional, Sequence
 # ---- ctypes mirror of include/gogp_hip.h ------------------------------------
 GOGP_MAX_TERMS = 4
 GOGP_MAX_NDIM = 64
+GOGP_MAX_EVENTS = 32
 
 K_NORMAL, K_MATERN32, K_MATERN52, K_MATERN52_TEXTBOOK, K_PERIODIC = 0, 1, 2, 3, 4
 NOISE_CONSTANT, NOISE_UNIFORM, NOISE_CONSTANT_PARAM = 0, 1, 2
@@ -123,6 +126,9 @@ class SimilKernel:
         self.terms = terms
         self._ntheta = ntheta
         self.name = name
+        #: event discounts [(from, to, discount), ...] on input dimension ``event_axis`` (``Events``); none: []
+        self.events: List[tuple] = []
+        self.event_axis = 0
 
     # reference interface ---------------------------------------------------
     def NTheta(self) -> int:
@@ -136,10 +142,30 @@ class SimilKernel:
             raise ValueError("Observe: len(x)")
         D = rest // 2
         theta, xa, xb = x[:nt], x[nt:nt + D], x[nt + D:]
-        return sum(_term_value(t, theta, xa, xb) for t in self.terms)
+        k = sum(_term_value(t, theta, xa, xb) for t in self.terms)
+        if self.events:
+            k *= event_discount(self.events, xa[self.event_axis], xb[self.event_axis])
+        return k
 
     def __repr__(self):
         return "<%s NTheta=%d>" % (self.name, self._ntheta)
+
+
+def _no_events(*ks: SimilKernel, what: str) -> None:
+    """The event discount multiplies the WHOLE similarity (tutorial/events/kernel/kernel.go:33-44): a combinator that
+    rebuilds a kernel from its terms cannot keep it silently, so it refuses a kernel that carries events."""
+    for k in ks:
+        if getattr(k, "events", None):
+            raise ValueError("%s of a kernel with events is not supported: apply Events last, to the whole similarity"
+                             % what)
+
+
+def _carry_events(src: SimilKernel, dst: SimilKernel) -> SimilKernel:
+    dst.events = list(src.events)
+    dst.event_axis = src.event_axis
+    if src.events:
+        dst.name = "Events(%s,%d)" % (dst.name, len(src.events))
+    return dst
 
 
 def _single(kind: int, name: str) -> SimilKernel:
@@ -160,6 +186,7 @@ Periodic = SimilKernel([Term(K_PERIODIC, -1, 0, False, 1, 1.0)], 2, "Periodic")
 
 def ARD(k: SimilKernel, ndim: int) -> SimilKernel:
     """Single-term kernel with one length scale per input dimension."""
+    _no_events(k, what="ARD")
     if len(k.terms) != 1 or k.terms[0].scale_idx >= 0:
         raise ValueError("ARD wraps a primitive kernel")
     t = k.terms[0]
@@ -170,12 +197,13 @@ def ARD(k: SimilKernel, ndim: int) -> SimilKernel:
 
 def Scaled(k: SimilKernel) -> SimilKernel:
     """``x[0] * k.Observe(x[1:])`` -- tutorial/barebones/kernel/kernel.go:14-18.
-    theta = [c | theta of k]."""
+    theta = [c | theta of k].  Events of k are kept: c * (f * d) == (c * f) * d."""
     if len(k.terms) != 1 or k.terms[0].scale_idx >= 0:
         raise ValueError("Scaled wraps an unscaled single-term kernel")
     t = k.terms[0].shifted(1)
     t.scale_idx = 0
-    return SimilKernel([t], k.NTheta() + 1, "Scaled(%s)" % k.name)
+    base = k.name[len("Events("):k.name.rindex(",")] if k.events else k.name
+    return _carry_events(k, SimilKernel([t], k.NTheta() + 1, "Scaled(%s)" % base))
 
 
 def Sum(parts: Sequence[SimilKernel], order: Optional[Sequence[int]] = None) -> SimilKernel:
@@ -183,6 +211,7 @@ def Sum(parts: Sequence[SimilKernel], order: Optional[Sequence[int]] = None) -> 
     parameter vectors; ``order`` (a permutation: new index of each old index)
     reproduces hand-written layouts such as [c1, c2, l1, l2, p] of
     tutorial/hyperpriors/kernel/kernel.go:12-25."""
+    _no_events(*parts, what="Sum")
     terms: List[Term] = []
     off = 0
     for k in parts:
@@ -210,7 +239,8 @@ def PeriodScaled(k: SimilKernel, mult: float) -> SimilKernel:
     (the ``10*x[p]`` of tutorial/hyperpriors/kernel/kernel.go:24)."""
     terms = [Term(t.kind, t.scale_idx, t.len_idx, t.ard, t.period_idx, t.period_mult * mult)
              for t in k.terms]
-    return SimilKernel(terms, k.NTheta(), "PeriodScaled(%s,%g)" % (k.name, mult))
+    base = k.name[len("Events("):k.name.rindex(",")] if k.events else k.name
+    return _carry_events(k, SimilKernel(terms, k.NTheta(), "PeriodScaled(%s,%g)" % (base, mult)))
 
 
 class NoiseKernel:
@@ -257,6 +287,56 @@ UniformNoise = NoiseKernel(NOISE_UNIFORM, scale=1.0)
 def ScaledNoise(scale: float) -> NoiseKernel:
     """``scale * kernel.UniformNoise.Observe(x)`` -- tutorial/barebones/kernel/kernel.go:25-31."""
     return NoiseKernel(NOISE_UNIFORM, scale=scale)
+
+
+def event_discount(events: Sequence[Sequence[float]], xa: float, xb: float) -> float:
+    """The factor tutorial/events/kernel/kernel.go:33-44 applies to the pair (xa, xb): the discount of the first
+    event with xa < from <= xb or xa < to <= xb (after swapping so that xa <= xb), else 1."""
+    if xa > xb:
+        xa, xb = xb, xa
+    for frm, to, disc in events:
+        if xa < frm <= xb or xa < to <= xb:
+            return disc
+    return 1.0
+
+
+def Events(simil: SimilKernel, events: Sequence[Sequence[float]], axis: int = 0) -> SimilKernel:
+    """``simil`` multiplied by an event discount when the two points lie on different sides of an event boundary
+    (tutorial/events/kernel/kernel.go:14-44).  ``events``: [(from, to, discount), ...], constants, not parameters --
+    NTheta is that of ``simil``.  ``axis``: the input dimension the boundaries lie on (the reference is 1-D: 0)."""
+    if not isinstance(simil, SimilKernel):
+        raise TypeError("Events wraps a SimilKernel")
+    if simil.events:
+        raise ValueError("the kernel already carries events")
+    ev = [tuple(float(v) for v in e) for e in events]
+    if any(len(e) != 3 for e in ev):
+        raise ValueError("an event is (from, to, discount)")
+    if len(ev) > GOGP_MAX_EVENTS:
+        raise ValueError("at most %d events" % GOGP_MAX_EVENTS)
+    if not all(math.isfinite(v) for e in ev for v in e):
+        raise ValueError("event values must be finite")
+    if axis < 0:
+        raise ValueError("axis must be >= 0")
+    if any(t.ard for t in simil.terms):
+        raise ValueError("event discounts are not supported with an ARD term")
+    k = SimilKernel([Term(t.kind, t.scale_idx, t.len_idx, t.ard, t.period_idx, t.period_mult) for t in simil.terms],
+                    simil.NTheta(), "Events(%s,%d)" % (simil.name, len(ev)))
+    k.events = ev
+    k.event_axis = axis
+    return k
+
+
+def parse_events(spec: str) -> List[tuple]:
+    """The ``-events`` flag of tutorial/events/main.go:31-33: "from:to:discount,from:to:discount,..."."""
+    out = []
+    for part in spec.split(","):
+        if not part.strip():
+            continue
+        f = part.split(":")
+        if len(f) != 3:
+            raise ValueError("event %r is not from:to:discount" % part)
+        out.append(tuple(float(v) for v in f))
+    return out
 
 
 def build_desc(ndim: int, simil: SimilKernel, noise: Optional[NoiseKernel]) -> CDesc:

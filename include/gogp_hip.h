@@ -139,6 +139,26 @@ int gogp_set_data(gogp_handle *h, const double *X, const double *y, int64_t n);
 int gogp_set_data_device(gogp_handle *h, const double *dX, const double *dy,
                          int64_t n);
 
+/* ---- event discounts (tutorial/events/kernel/kernel.go:14-44) -------------------------
+ * The similarity of two points on different sides of an event boundary is multiplied by the
+ * event's discount: with xa <= xb the coordinates of the two points on input dimension `axis`,
+ * the FIRST event (in list order) with  xa < from <= xb  or  xa < to <= xb  applies its
+ * discount to the whole similarity (all terms; not the noise), and the walk stops.  Events are
+ * constants, not parameters: NTheta, the gradient slots and the noise are unchanged, and every
+ * derivative is the discount times the undiscounted one.  `axis` generalises the reference's
+ * 1-D x[a], x[b] to NDim > 1 (the reference case: axis = 0, ndim = 1).  Not combined with an
+ * ARD term (GOGP_EARG). */
+#define GOGP_MAX_EVENTS 32
+/* Pure host validation: 0 <= nevents <= GOGP_MAX_EVENTS, 0 <= axis < ndim,
+ * from / to / discount finite.  GOGP_OK or GOGP_EARG. */
+int gogp_events_check(const double *events /* nevents x 3: from, to, discount */,
+                      int nevents, int axis, int ndim);
+/* Event discounts of tutorial/events/kernel/kernel.go:14-44 on input dimension
+ * `axis`, multiplying the whole similarity (all terms); nevents == 0 clears.
+ * Stored results (factor, alpha) no longer match and are dropped, as by gogp_set_data.
+ * On a sharded handle every rank makes the same call. */
+int gogp_set_events(gogp_handle *h, const double *events, int nevents, int axis);
+
 /* ---- the hot path ----------------------------------------------------------*/
 
 /* gp.GP.Absorb (gp/gp.go:80-87) minus the data assignment (gogp_set_data):
