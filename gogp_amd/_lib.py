@@ -18,6 +18,7 @@ HOOKS_PATH = os.path.join(_HERE, "libgogp_testhooks.so")
 
 GOGP_OK, GOGP_EARG, GOGP_ENOTPD, GOGP_EHIP, GOGP_ESTATE, GOGP_ENOMEM, GOGP_ECOND = 0, 1, 2, 3, 4, 5, 6
 GOGP_MAX_CANDIDATES = 16
+GOGP_BATCH_MAX_N = 128
 
 #: every symbol include/gogp_hip.h declares: (name, restype, argtypes)
 _dp = ctypes.POINTER(ctypes.c_double)
@@ -66,6 +67,13 @@ SYMBOLS = [
      [ctypes.POINTER(_h), ctypes.c_int, _dp, _i64, _dp, _dp, ctypes.POINTER(ctypes.c_int)]),
     ("gogp_observe_gradient_candidates", ctypes.c_int,
      [_h, ctypes.c_int, _dp, _i64, _dp, _dp, ctypes.POINTER(ctypes.c_int)]),
+    ("gogp_batch_set_data", ctypes.c_int,
+     [_h, _dp, _dp, _i64, ctypes.c_int32, ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
+    ("gogp_batch_observe_gradient", ctypes.c_int,
+     [_h, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), _dp, _i64, _dp, _dp, ctypes.POINTER(ctypes.c_int)]),
+    ("gogp_batch_produce", ctypes.c_int,
+     [_h, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), _dp, _i64, ctypes.POINTER(_i64), _dp, _dp, _dp, _dp,
+      ctypes.POINTER(ctypes.c_int)]),
     ("gogp_produce", ctypes.c_int, [_h, _dp, _i64, _dp, _dp]),
     ("gogp_n", _i64, [_h]),
     ("gogp_get_alpha", ctypes.c_int, [_h, _dp]),

@@ -253,6 +253,12 @@ extern "C" void gogp_destroy(gogp_handle *h) {
   free_n_buffers(h);
   free_m_buffers(h);
   free_cand_buffers(h);
+  (void)hipFree(h->bt_X);
+  (void)hipFree(h->bt_y);
+  (void)hipFree(h->bt_din);
+  (void)hipFree(h->bt_dout);
+  if (h->bt_hin) (void)hipHostFree(h->bt_hin);
+  if (h->bt_hout) (void)hipHostFree(h->bt_hout);
   (void)hipFree(h->scalars);
   (void)hipFree(h->dscr);
   (void)hipFree(h->D64);
@@ -421,8 +427,8 @@ extern "C" int gogp_set_events(gogp_handle *h, const double *events, int nevents
 }
 
 // ---- parameters ---------------------------------------------------------------------------
-// DevParams of the handle's current natural parameters (theta_s, theta_n)
-static void fill_params(const gogp_handle *h, DevParams &p) {
+// DevParams of the natural parameters ts (similarity), tn (noise)
+static void fill_params_theta(const gogp_handle *h, const double *ts, const double *tn, DevParams &p) {
   const gogp_desc &d = h->desc;
   memset(&p, 0, sizeof p);
   p.ndim = d.ndim;
@@ -433,19 +439,19 @@ static void fill_params(const gogp_handle *h, DevParams &p) {
     const gogp_term &T = d.terms[t];
     p.kind[t] = T.kind;
     p.ard[t] = T.ard;
-    p.c[t] = T.scale_idx >= 0 ? h->theta_s[T.scale_idx] : 1.0;
+    p.c[t] = T.scale_idx >= 0 ? ts[T.scale_idx] : 1.0;
     p.w[t] = 0.0;
     if (T.kind == GOGP_K_PERIODIC)
-      p.w[t] = M_PI / (T.period_mult * h->theta_s[T.period_idx]);
+      p.w[t] = M_PI / (T.period_mult * ts[T.period_idx]);
     for (int j = 0; j < d.ndim; ++j)
-      p.inv_len[t][j] = 1.0 / h->theta_s[T.len_idx + (T.ard ? j : 0)];
+      p.inv_len[t][j] = 1.0 / ts[T.len_idx + (T.ard ? j : 0)];
   }
   if (d.noise_kind == GOGP_NOISE_CONSTANT || d.noise_kind == GOGP_NOISE_CONSTANT_PARAM) {
     // kernel/noise.go:27-30; tutorial/anynoise/kernel/kernel.go:31-33 (the parameter is unused)
     p.noise_var = d.noise_std * d.noise_std;
     p.dnoise = 0.0;
   } else {
-    const double sd = h->theta_n[0];
+    const double sd = tn[0];
     p.noise_var = d.noise_scale * sd * sd;  // kernel/noise.go:47-49
     p.dnoise = 2.0 * p.noise_var;
   }
@@ -456,6 +462,11 @@ static void fill_params(const gogp_handle *h, DevParams &p) {
     p.ev_to[e] = h->events[e][1];
     p.ev_disc[e] = h->events[e][2];
   }
+}
+
+// ... of the handle's current natural parameters (theta_s, theta_n)
+static void fill_params(const gogp_handle *h, DevParams &p) {
+  fill_params_theta(h, h->theta_s.data(), h->theta_n.data(), p);
 }
 
 int gogp_upload_params(gogp_handle *h) {
@@ -532,7 +543,8 @@ struct FactorResult {
   int64_t notpd = -1;
   std::string msg;
 };
-static FactorResult judge_scalars(const gogp_handle *h, const double *hs, bool fp32, bool refine) {
+// n: the number of observations the scalars belong to (-1: the handle's own; a batch pair: its member's)
+static FactorResult judge_scalars(const gogp_handle *h, const double *hs, bool fp32, bool refine, int64_t n = -1) {
   FactorResult r;
   long long info = 0;
   memcpy(&info, hs + 8, sizeof info);
@@ -549,7 +561,7 @@ static FactorResult judge_scalars(const gogp_handle *h, const double *hs, bool f
   const double ztz = refine ? hs[6] : hs[1];  // y^T alpha (refined) / z^T z
   r.yta = ztz;
   // gp/gp.go:244-253
-  r.lml = -0.5 * (double)h->n * log(2 * M_PI) - 0.5 * logdet - 0.5 * ztz;
+  r.lml = -0.5 * (double)(n < 0 ? h->n : n) * log(2 * M_PI) - 0.5 * logdet - 0.5 * ztz;
   // gonum's Cholesky solves return a Condition error when its condition estimate exceeds
   // 1e16 (mat.ConditionTolerance), which gp/gp.go:233-236 passes on (Absorb: error, Observe:
   // panic).  (max L_ii / min L_ii)^2 is a lower bound of cond_2(K); beyond 1e16 the matrix is
@@ -1247,13 +1259,18 @@ static int ensure_alpha(gogp_handle *h) {
   return GOGP_OK;
 }
 
+// NULL, or what is wrong with the natural parameters ts / tn
+static const char *theta_refusal(const gogp_handle *h, const double *ts, const double *tn) {
+  for (int i = 0; i < h->ns; ++i)
+    if (!(ts[i] > 0.0) || !std::isfinite(ts[i])) return "similarity parameters must be positive and finite";
+  for (int i = 0; i < h->nn; ++i)
+    if (!std::isfinite(tn[i])) return "noise parameter must be finite";
+  return nullptr;
+}
+
 static int set_theta_natural(gogp_handle *h, const double *ts, const double *tn) {
   // validate everything first: a refused vector leaves the handle's parameters as they were
-  for (int i = 0; i < h->ns; ++i)
-    if (!(ts[i] > 0.0) || !std::isfinite(ts[i]))
-      return fail(h, GOGP_EARG, "similarity parameters must be positive and finite");
-  for (int i = 0; i < h->nn; ++i)
-    if (!std::isfinite(tn[i])) return fail(h, GOGP_EARG, "noise parameter must be finite");
+  if (const char *why = theta_refusal(h, ts, tn)) return fail(h, GOGP_EARG, why);
   for (int i = 0; i < h->ns; ++i) h->theta_s[i] = ts[i];
   for (int i = 0; i < h->nn; ++i) h->theta_n[i] = tn[i];
   return GOGP_OK;
@@ -1960,6 +1977,168 @@ extern "C" int gogp_observe_gradient_candidates(gogp_handle *h, int k, const dou
   h->theta_n = sv.theta_n;
   if (first != GOGP_OK && rc == GOGP_OK) h->err = first_msg;
   return first;
+}
+
+// ---- batches of independent small GPs: many members, each with its own n and theta, in ONE launch ---------------------
+// The forecast harness of the reference (tutorial/tutorial.go:88-197) fits every prefix X[:end] of the data separately;
+// each window on its own is one latency-bound evaluation of a few dozen rows.  Here the members are row ranges of one
+// uploaded data set, and one call evaluates k (member, log theta) pairs: one copy of the pairs' parameters in, one launch
+// (diag256.hip: batch_eval_kernel, a workgroup per pair), one copy of the results out.  fp64 whatever the precision
+// options; the handle's own data, factorisation and candidates are not touched.
+extern "C" int gogp_batch_set_data(gogp_handle *h, const double *X, const double *y, int64_t rows, int32_t nmembers,
+                                   const int64_t *offset, const int64_t *n) {
+  if (!h) return GOGP_EARG;
+  if (h->dist) return fail(h, GOGP_EARG, "batch: not supported on a sharded handle");
+  if (rows < 0 || nmembers < 0 || (rows > 0 && (!X || !y)) || (nmembers > 0 && (!offset || !n)))
+    return fail(h, GOGP_EARG, "batch_set_data: bad arguments");
+  for (int32_t b = 0; b < nmembers; ++b)
+    if (n[b] < 0 || n[b] > GOGP_BATCH_MAX_N || offset[b] < 0 || offset[b] > rows - n[b])
+      return fail(h, GOGP_EARG, "batch_set_data: every member needs 0 <= n <= GOGP_BATCH_MAX_N rows inside the data");
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipStreamSynchronize(h->s));
+  if (rows > h->bt_cap_rows || !h->bt_X) {
+    (void)hipFree(h->bt_X);
+    (void)hipFree(h->bt_y);
+    h->bt_X = h->bt_y = nullptr;
+    h->bt_cap_rows = 0;
+    h->bt_have = false;
+    const int64_t cap = std::max<int64_t>(rows, 1);
+    // (+ GOGP_MAX_NDIM doubles of slack, as the handle's own X)
+    HIPCHK(h, hipMalloc(&h->bt_X, ((size_t)cap * h->D + GOGP_MAX_NDIM) * sizeof(double)));
+    HIPCHK(h, hipMalloc(&h->bt_y, (size_t)cap * sizeof(double)));
+    h->bt_cap_rows = cap;
+  }
+  if (rows > 0) {
+    HIPCHK(h, hipMemcpy(h->bt_X, X, (size_t)rows * h->D * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(h->bt_y, y, (size_t)rows * sizeof(double), hipMemcpyHostToDevice));
+  }
+  h->bt_rows = rows;
+  h->bt_off.assign(offset, offset + nmembers);
+  h->bt_n.assign(n, n + nmembers);
+  h->bt_have = true;
+  return GOGP_OK;
+}
+
+// device + pinned staging of at least `bytes` (grown, never shrunk)
+static int bt_reserve(gogp_handle *h, char **dev, char **host, size_t *cap, size_t bytes) {
+  if (bytes <= *cap) return GOGP_OK;
+  (void)hipFree(*dev);
+  if (*host) (void)hipHostFree(*host);
+  *dev = *host = nullptr;
+  *cap = 0;
+  HIPCHK(h, hipMalloc((void **)dev, bytes));
+  HIPCHK(h, hipHostMalloc((void **)host, bytes, hipHostMallocDefault));
+  *cap = bytes;
+  return GOGP_OK;
+}
+
+// both entry points: produce == (zoff != NULL)
+static int batch_eval(gogp_handle *h, int32_t k, const int32_t *members, const double *x, int64_t len,
+                      const int64_t *zoff, const double *Z, double *lmls, double *grads, double *mu, double *sigma,
+                      int *status) {
+  const bool produce = zoff != nullptr;
+  if (!h) return GOGP_EARG;
+  if (h->dist) return fail(h, GOGP_EARG, "batch: not supported on a sharded handle");
+  if (k < 0 || (k > 0 && (!members || !x || !lmls || (!produce && !grads))))
+    return fail(h, GOGP_EARG, "batch: bad arguments");
+  if (len != h->P) return fail(h, GOGP_EARG, "len(x)");
+  if (!h->bt_have) return fail(h, GOGP_ESTATE, "batch: no batch data (gogp_batch_set_data)");
+  const int64_t nmem = (int64_t)h->bt_n.size();
+  for (int32_t i = 0; i < k; ++i)
+    if (members[i] < 0 || members[i] >= nmem) return fail(h, GOGP_EARG, "batch: member index out of range");
+  int64_t mz = 0;  // test points: rows 0 .. zoff[k] - 1 of Z
+  if (produce) {
+    if (zoff[0] < 0) return fail(h, GOGP_EARG, "batch_produce: zoff must be non-negative and non-decreasing");
+    for (int32_t i = 0; i < k; ++i)
+      if (zoff[i + 1] < zoff[i]) return fail(h, GOGP_EARG, "batch_produce: zoff must be non-negative and non-decreasing");
+    mz = zoff[k];
+    if (mz > 0 && (!Z || !mu || !sigma)) return fail(h, GOGP_EARG, "batch_produce: bad arguments");
+  }
+  if (k == 0) return GOGP_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  const size_t items_bytes = align_up((size_t)k * sizeof(BatchItem), 256);
+  const size_t in_bytes = items_bytes + (size_t)mz * h->D * sizeof(double);
+  const size_t out_bytes = ((size_t)k * BATCH_ROW + 2 * (size_t)mz) * sizeof(double);
+  int rc = bt_reserve(h, &h->bt_din, &h->bt_hin, &h->bt_in_cap, in_bytes);
+  if (rc == GOGP_OK) rc = bt_reserve(h, (char **)&h->bt_dout, (char **)&h->bt_hout, &h->bt_out_cap, out_bytes);
+  if (rc != GOGP_OK) return rc;
+  // the pairs' parameters (gp/gp.go:378-385: theta = exp(x)), with the fill of the single-handle path; a pair with
+  // unusable parameters is evaluated at theta = 1 and reported as GOGP_EARG
+  std::vector<int> st((size_t)k, GOGP_OK);
+  BatchItem *items = reinterpret_cast<BatchItem *>(h->bt_hin);
+  std::vector<double> th((size_t)std::max(h->P, 1));
+  for (int32_t i = 0; i < k; ++i) {
+    for (int q = 0; q < h->P; ++q) th[(size_t)q] = exp(x[(size_t)i * len + q]);
+    if (theta_refusal(h, th.data(), th.data() + h->ns)) {
+      st[(size_t)i] = GOGP_EARG;
+      std::fill(th.begin(), th.end(), 1.0);
+    }
+    BatchItem &it = items[i];
+    fill_params_theta(h, th.data(), th.data() + h->ns, it.P);
+    it.off = (long)h->bt_off[(size_t)members[i]];
+    it.n = (long)h->bt_n[(size_t)members[i]];
+    it.zoff = produce ? (long)zoff[i] : 0;
+    it.m = produce ? (long)(zoff[i + 1] - zoff[i]) : 0;
+  }
+  if (mz > 0) memcpy(h->bt_hin + items_bytes, Z, (size_t)mz * h->D * sizeof(double));
+  hipStream_t s = h->s;
+  double *drows = h->bt_dout, *dmu = drows + (size_t)k * BATCH_ROW, *dsig = dmu + mz;
+  HIPCHK(h, hipMemcpyAsync(h->bt_din, h->bt_hin, in_bytes, hipMemcpyHostToDevice, s));
+  launch_batch_eval(s, reinterpret_cast<const BatchItem *>(h->bt_din), k, h->bt_X, h->bt_y,
+                    reinterpret_cast<const double *>(h->bt_din + items_bytes), drows, dmu, dsig, h->ard_dims, produce,
+                    h->ev());
+  HIPCHK(h, hipMemcpyAsync(h->bt_hout, h->bt_dout, out_bytes, hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipStreamSynchronize(s));
+  HIPCHK(h, hipGetLastError());
+  // every pair judged as gogp_observe would judge a handle holding its member's data
+  const double *hmu = h->bt_hout + (size_t)k * BATCH_ROW, *hsig = hmu + mz;
+  int first = GOGP_OK;
+  std::string first_msg;
+  for (int32_t i = 0; i < k; ++i) {
+    const double *row = h->bt_hout + (size_t)i * BATCH_ROW;
+    const BatchItem &it = items[i];
+    double *g = produce ? nullptr : grads + (size_t)i * len;
+    if (g)
+      for (int64_t q = 0; q < len; ++q) g[q] = 0.0;
+    lmls[i] = NAN;
+    bool values = false;
+    if (st[(size_t)i] != GOGP_OK) {
+      if (first_msg.empty()) first_msg = "batch: parameters must be positive and finite";
+    } else if (it.n == 0) {  // gp/gp.go:101-104, 343-347, 427-430
+      lmls[i] = 0.0;
+      values = true;
+    } else {
+      const FactorResult fr = judge_scalars(h, row, false, false, it.n);
+      st[(size_t)i] = fr.rc;
+      if (fr.rc != GOGP_OK && first_msg.empty()) first_msg = fr.msg;
+      if (fr.rc != GOGP_ENOTPD) {
+        lmls[i] = fr.lml;
+        if (g) assemble_gradient(h, row + 16, it.P.dnoise, g);
+        values = true;
+      }
+    }
+    if (produce)
+      for (long j = it.zoff; j < it.zoff + it.m; ++j) {
+        mu[j] = values ? (it.n == 0 ? 0.0 : hmu[j]) : NAN;
+        sigma[j] = values ? hsig[j] : NAN;
+      }
+    if (status) status[i] = st[(size_t)i];
+    if (first == GOGP_OK && st[(size_t)i] != GOGP_OK) first = st[(size_t)i];
+  }
+  if (first != GOGP_OK) h->err = first_msg;
+  return first;
+}
+
+extern "C" int gogp_batch_observe_gradient(gogp_handle *h, int32_t k, const int32_t *members, const double *x,
+                                           int64_t len, double *lmls, double *grads, int *status) {
+  return batch_eval(h, k, members, x, len, nullptr, nullptr, lmls, grads, nullptr, nullptr, status);
+}
+
+extern "C" int gogp_batch_produce(gogp_handle *h, int32_t k, const int32_t *members, const double *x, int64_t len,
+                                  const int64_t *zoff, const double *Z, double *lmls, double *mu, double *sigma,
+                                  int *status) {
+  if (!zoff) return fail(h, GOGP_EARG, "batch_produce: zoff is NULL");
+  return batch_eval(h, k, members, x, len, zoff, Z, lmls, nullptr, mu, sigma, status);
 }
 
 extern "C" int gogp_graph_info(const gogp_handle *h, int64_t *nodes, int *refused) {

@@ -255,6 +255,17 @@ void launch_panel128_slabs(hipStream_t s, const double *A, int64_t ld, double *L
 // alpha and (want_kinv) K^-1, left where the general path leaves them (A: K^-1 lower, L, Dinv: leading dimension 256)
 void launch_tiny_eval(hipStream_t s, const DevParams *P, const double *X, const double *y, int64_t n, double *A, double *L,
                       double *Dinv, double *z, double *alpha, long long *info, bool want_kinv, bool ev = false);
+// diag256.hip: batches of small GPs (gogp_batch_*), one workgroup per (member, theta) pair.  Pair b evaluates rows
+// off .. off + n - 1 (n <= 128) of the batch data at P and writes row b of `rows` (BATCH_ROW doubles: the scalars of
+// judge_scalars in [0..15], the NACC gradient slot sums from [16] on) or, produce, mu / sigma of Z's rows zoff .. zoff + m - 1
+struct BatchItem {
+  DevParams P;
+  long off, n;
+  long zoff, m;
+};
+constexpr int BATCH_ROW = NACC + 16;
+void launch_batch_eval(hipStream_t s, const BatchItem *items, int k, const double *X, const double *y, const double *Z,
+                       double *rows, double *mu, double *sigma, int ard_dims, bool produce, bool ev);
 // dense inverses of nblk consecutive 256 x 256 diagonal blocks of a finished factor (block b at L + b * 256 * (ld + 1))
 void launch_dinv256_blocks(hipStream_t s, const double *L, int64_t ld, double *Dinv, int nblk);
 void launch_diag256_inv_only_ld512(hipStream_t s, const double *L, int64_t ld, double *Dinv);  // Dinv: ld 512

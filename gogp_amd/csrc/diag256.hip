@@ -792,6 +792,256 @@ __global__ __launch_bounds__(NT) void GOGP_EVN(tiny_eval_kernel)(const DevParams
       }
 }
 
+// ---- batches of independent small GPs: one workgroup per (member, theta) pair, ONE launch -------------------------------
+// gogp_batch_observe_gradient / gogp_batch_produce (api.hip): pair b = blockIdx.x evaluates member items[b] (rows off ..
+// off + n - 1 of the batch data, n <= 128) at its own parameters items[b].P.  The Gram matrix, the factor, X = L^-1, z,
+// alpha and K^-1 are formed by the code of tiny_eval_kernel above; nothing leaves LDS but the results:
+//   rows[b][0..15]: the scalars judge_scalars (api.hip) reads -- [0] sum 2 log L_ii, [1] z^T z, [3] / [4] min / max L_ii,
+//                   [8] first failing pivot + 1 (a pair that is not positive definite stops there: its workgroup only);
+//                   log-determinant and z^T z are summed in the order of lml_scalars_kernel (solve.hip)
+//   !PRODUCE: rows[b][16 + q]: the NACC slot sums of the gradient reduction (grad.hip's weights: W = alpha alpha^T - K^-1
+//             over the lower triangle, off-diagonal terms twice, the pair's discount on the similarity slots only),
+//             formed from K^-1 in LDS with the member's rows read from X; ARD_D > 0: per-dimension accumulators in
+//             passes of ARD_D dimensions, as grad.hip does
+//   PRODUCE:  mu[j], sigma[j] for the pair's test points j = zoff .. zoff + m - 1 of Z (gp/gp.go:269-278, 322-357):
+//             k* into LDS, v = X k*, mu = k*^T alpha, sigma = sqrt(k(z, z) - v^T v), unclamped
+template <int ARD_D, bool PRODUCE>
+__global__ __launch_bounds__(NT) void GOGP_EVN(batch_eval_kernel)(const BatchItem *__restrict__ items,
+                                                          const double *__restrict__ X, const double *__restrict__ y,
+                                                          const double *__restrict__ Z, double *__restrict__ rows,
+                                                          double *__restrict__ mu, double *__restrict__ sigma,
+                                                          int ard_dims) {
+  const BatchItem &it = items[blockIdx.x];
+  const DevParams &P = it.P;
+  const int D = P.ndim;
+  const long n = it.n;
+  X += it.off * D;
+  y += it.off;
+  double *row = rows + (long)blockIdx.x * BATCH_ROW;
+  __shared__ __attribute__((aligned(16))) double S[128 * SLD];
+  __shared__ __attribute__((aligned(16))) double G[GSIZE];
+  __shared__ double rinv_s[8 * 16];
+  __shared__ double ys[128], zs[128];  // ys: y, then alpha
+  __shared__ double sc[2][3];          // the two waves' log-determinant, min and max L_ii
+  __shared__ long long info_s;
+  __shared__ unsigned long long em[GOGP_EV ? 128 : 1];
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, w = tid >> 6;
+  if (tid == 0) info_s = 0;
+  if (GOGP_EV) {
+    if (tid < 128) em[tid] = event_mask(P, tid < n ? X[(long)tid * D + P.ev_axis] : 0.0);
+    __syncthreads();
+  }
+  // ---- the Gram matrix (as tiny_eval_kernel) -----------------------------------------------------------------------------
+  for (int idx = tid; idx < 128 * 128; idx += NT) {
+    const int i = idx >> 7, j = idx & 127;
+    double k = 0.0;
+    if (j <= i) {
+      if (i < n) {
+        const double *xi = X + (long)i * D, *xj = X + (long)j * D;
+        k = simil_value(P, [&](int d) { return xi[d]; }, [&](int d) { return xj[d]; });
+        if (GOGP_EV) k *= event_discount(P, em[i], em[j]);
+        if (i == j) k += P.noise_var;
+      } else {
+        k = (i == j) ? 1.0 : 0.0;
+      }
+    }
+    S[i * SLD + j] = k;
+  }
+  if (tid < 128) ys[tid] = tid < n ? y[tid] : 0.0;
+  __syncthreads();
+  potrf128_lds(S, G, rinv_s, tid, 0, n, &info_s);  // (ends with a barrier)
+  const long long info = info_s;
+  if (info != 0) {  // workgroup-uniform: this pair stops here
+    if (tid < 16) row[tid] = 0.0;
+    if (tid == 0) reinterpret_cast<long long *>(row)[8] = info;
+    return;
+  }
+  // ---- log-determinant, min / max L_ii: element i in thread i, as lml_scalars_kernel --------------------------------------
+  if (tid < 128) {
+    double a = 0.0, dmin = INFINITY, dmax = 0.0;
+    if (tid < n) {
+      const double lii = S[tid * SLD + tid];
+      a = 2.0 * log(lii);
+      dmin = dmax = lii;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      a += __shfl_xor(a, o);
+      dmin = fmin(dmin, __shfl_xor(dmin, o));
+      dmax = fmax(dmax, __shfl_xor(dmax, o));
+    }
+    if (lane == 0) {
+      sc[w][0] = a;
+      sc[w][1] = dmin;
+      sc[w][2] = dmax;
+    }
+  }
+  __syncthreads();
+  invert128_lds(S, G, tid);  // S = X = L^-1 (lower)
+  // ---- z = X y, alpha = X^T z (as tiny_eval_kernel) ------------------------------------------------------------------------
+  {
+    const int i = tid >> 2, p = tid & 3;
+    double a = 0.0;
+    for (int k = p; k <= i; k += 4) a += S[i * SLD + k] * ys[k];
+    a += __shfl_xor(a, 1);
+    a += __shfl_xor(a, 2);
+    if (p == 0) zs[i] = a;
+  }
+  __syncthreads();
+  {
+    const int j = tid >> 2, p = tid & 3;
+    double a = 0.0;
+    for (int k = j + p; k < 128; k += 4) a += S[k * SLD + j] * zs[k];
+    a += __shfl_xor(a, 1);
+    a += __shfl_xor(a, 2);
+    if (p == 0) ys[j] = a;  // alpha (every reader of y is past the barrier above)
+  }
+  if (tid < 128) {  // z^T z over i < n, then the scalars row
+    double b = tid < n ? zs[tid] * zs[tid] : 0.0;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) b += __shfl_xor(b, o);
+    if (lane == 0) G[w] = b;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    double r[16];
+#pragma unroll
+    for (int q = 0; q < 16; ++q) r[q] = 0.0;
+    r[0] = (0.0 + sc[0][0]) + sc[1][0];
+    r[1] = (0.0 + G[0]) + G[1];
+    r[3] = fmin(fmin(INFINITY, sc[0][1]), sc[1][1]);
+    r[4] = fmax(fmax(0.0, sc[0][2]), sc[1][2]);
+#pragma unroll
+    for (int q = 0; q < 16; ++q) row[q] = r[q];
+  }
+  __syncthreads();  // G is reused below
+  if (PRODUCE) {
+    // ---- the pair's test points, one after the other: k* into G, v = X k* (row tid / 4, as z above) ---------------------
+    double *ks = G, *red = G + 128;  // red: [8][2]
+    const long j1 = it.zoff + it.m;
+    for (long j = it.zoff; j < j1; ++j) {
+      const double *zj = Z + j * D;
+      if (tid < 128) {
+        double k = 0.0;
+        if (tid < n) {
+          const double *xi = X + (long)tid * D;
+          k = simil_value(P, [&](int d) { return xi[d]; }, [&](int d) { return zj[d]; });
+          if (GOGP_EV) k *= event_discount(P, em[tid], event_mask(P, zj[P.ev_axis]));
+        }
+        ks[tid] = k;
+      }
+      __syncthreads();
+      const int i = tid >> 2, p = tid & 3;
+      double a = 0.0;
+      for (int k = p; k <= i; k += 4) a += S[i * SLD + k] * ks[k];
+      a += __shfl_xor(a, 1);
+      a += __shfl_xor(a, 2);
+      double q = (p == 0) ? a * a : 0.0, mm = (p == 0) ? ks[i] * ys[i] : 0.0;
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        q += __shfl_xor(q, o);
+        mm += __shfl_xor(mm, o);
+      }
+      if (lane == 0) {
+        red[2 * w] = q;
+        red[2 * w + 1] = mm;
+      }
+      __syncthreads();
+      if (tid == 0) {
+        double qs = 0.0, ms = 0.0;
+        for (int u = 0; u < NW; ++u) {
+          qs += red[2 * u];
+          ms += red[2 * u + 1];
+        }
+        const double prior = simil_value(P, [&](int d) { return zj[d]; }, [&](int d) { return zj[d]; });
+        mu[j] = ms;
+        sigma[j] = sqrt(prior - qs);
+      }
+      __syncthreads();  // ks and red are overwritten by the next point
+    }
+    return;
+  }
+  // ---- K^-1 = X^T X (as tiny_eval_kernel), then W = alpha alpha^T - K^-1 into the lower tiles of S --------------------------
+  for (int idx = tid; idx < 128 * 128; idx += NT) {
+    const int i = idx >> 7, j = idx & 127;
+    if (j < i) {
+      const double v = S[i * SLD + j];
+      S[j * SLD + i] = v;
+      S[i * SLD + j] = 0.0;
+    }
+  }
+  __syncthreads();
+  {
+    f64x4 c[2][4];
+    wg_gemm128<true, TRI_SYM>(c, S, G, nullptr, 0, tid);  // (ends with a barrier: S is free)
+    const int fr = lane & 15, fk = lane >> 4;
+    const int wr = w >> 1, wc = w & 1;
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+      for (int nn = 0; nn < 4; ++nn)
+        if (GOGP_CT(nn) <= GOGP_RT(m)) {
+#pragma unroll
+          for (int v = 0; v < 4; ++v) {
+            const int i = GOGP_RT(m) * 16 + fk + 4 * v, j = GOGP_CT(nn) * 16 + fr;
+            S[i * SLD + j] = ys[i] * ys[j] - c[m][nn][v];
+          }
+        }
+  }
+  __syncthreads();
+  // ---- the gradient reduction over the lower triangle (grad.hip's terms), thread tid: elements tid, tid + 512, ... ---------
+  double *red = G;  // [8][NACC]
+  for (int ard0 = 0;; ard0 += (ARD_D > 0 ? ARD_D : 1)) {
+    double acc[ACC_TRACE + 1];
+#pragma unroll
+    for (int q = 0; q <= ACC_TRACE; ++q) acc[q] = 0.0;
+    double ard[ARD_D > 0 ? ARD_D : 1];
+#pragma unroll
+    for (int q = 0; q < (ARD_D > 0 ? ARD_D : 1); ++q) ard[q] = 0.0;
+    for (int idx = tid; idx < 128 * 128; idx += NT) {
+      const int i = idx >> 7, j = idx & 127;
+      if (j <= i && i < n) {
+        const double wv = S[i * SLD + j];
+        double wgt = (j < i) ? 2.0 * wv : wv;
+        if (GOGP_EV) wgt *= event_discount(P, em[i], em[j]);
+        const double *xi = X + (long)i * D, *xj = X + (long)j * D;
+        simil_grad_accum<ARD_D>(
+            P, [&](int d) { return xi[d]; }, [&](int d) { return xj[d]; }, wgt, acc, ard, ard0);
+        if (i == j) acc[ACC_TRACE] += wv;
+      }
+    }
+#pragma unroll
+    for (int q = 0; q <= ACC_TRACE; ++q) {
+      double v = acc[q];
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+      if (lane == 0) red[w * NACC + q] = v;
+    }
+    if (ARD_D > 0) {
+#pragma unroll
+      for (int q = 0; q < (ARD_D > 0 ? ARD_D : 1); ++q) {
+        double v = ard[q];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+        if (lane == 0) red[w * NACC + ACC_ARD0 + q] = v;
+      }
+    }
+    __syncthreads();
+    // the first pass writes every slot (zeros in the dead ones), a later pass only the slots of its own dimensions
+    if (tid < NACC) {
+      const bool base = tid <= ACC_TRACE, mine = tid >= ACC_ARD0 && tid < ACC_ARD0 + ARD_D;
+      double v = 0.0;
+      if (base || mine)
+        for (int u = 0; u < NW; ++u) v += red[u * NACC + tid];
+      if (ard0 == 0) row[16 + tid] = v;
+      else if (mine && tid + ard0 < NACC) row[16 + tid + ard0] = v;
+    }
+    if (ARD_D == 0 || ard0 + ARD_D >= ard_dims) break;
+    __syncthreads();  // red is rewritten by the next pass
+  }
+}
+
 #if !GOGP_EV  // second pass (the product library only): tiny_eval_kernel again, with event discounts, as tiny_eval_kernel_ev
 #ifndef GOGP_BUILD_TESTHOOKS
 #undef GOGP_EV
@@ -816,6 +1066,24 @@ void launch_tiny_eval(hipStream_t s, const DevParams *P, const double *X, const 
 #endif
 
 #ifndef GOGP_BUILD_TESTHOOKS
+// one workgroup per pair; the events instances exist without ARD only (gogp_set_events refuses ARD)
+void launch_batch_eval(hipStream_t s, const BatchItem *items, int k, const double *X, const double *y, const double *Z,
+                       double *rows, double *mu, double *sigma, int ard_dims, bool produce, bool ev) {
+  const dim3 grid((unsigned)k), blk(NT);
+  if (produce) {
+    if (ev)
+      GOGP_KLAUNCH((batch_eval_kernel_ev<0, true>), grid, blk, 0, s, items, X, y, Z, rows, mu, sigma, 0);
+    else
+      GOGP_KLAUNCH((batch_eval_kernel<0, true>), grid, blk, 0, s, items, X, y, Z, rows, mu, sigma, 0);
+  } else if (ev) {
+    GOGP_KLAUNCH((batch_eval_kernel_ev<0, false>), grid, blk, 0, s, items, X, y, Z, rows, mu, sigma, 0);
+  } else if (ard_dims > 0) {
+    GOGP_KLAUNCH((batch_eval_kernel<16, false>), grid, blk, 0, s, items, X, y, Z, rows, mu, sigma, ard_dims);
+  } else {
+    GOGP_KLAUNCH((batch_eval_kernel<0, false>), grid, blk, 0, s, items, X, y, Z, rows, mu, sigma, 0);
+  }
+}
+
 void launch_dinv256_blocks(hipStream_t s, const double *L, int64_t ld, double *Dinv, int nblk) {
   GOGP_KLAUNCH(dinv256_blocks_kernel, dim3((unsigned)nblk, 1, (unsigned)gogp::tl_batch.k), dim3(NT), 0, s, L, (long)ld, Dinv,
                gogp::tl_batch.stride);

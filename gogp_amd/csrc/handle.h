@@ -82,6 +82,16 @@ struct gogp_handle {
     size_t stride = 0;
     const void *arena = nullptr, *dX = nullptr, *dy = nullptr, *hostP = nullptr, *hscal = nullptr;
   } cand_graph_key, cand_seen_key;  // what the graph was captured for / what the last call asked for
+  // batches of small GPs (gogp_batch_*): the members' data (row ranges of one uploaded X / y) and the staging of one
+  // call -- the pairs' BatchItems + test points in (pinned -> device: one copy), result rows + mu + sigma out
+  double *bt_X = nullptr, *bt_y = nullptr;  // bt_cap_rows x D (+ GOGP_MAX_NDIM slack), bt_cap_rows
+  int64_t bt_rows = 0, bt_cap_rows = 0;
+  std::vector<int64_t> bt_off, bt_n;
+  bool bt_have = false;
+  char *bt_din = nullptr, *bt_hin = nullptr;
+  size_t bt_in_cap = 0;
+  double *bt_dout = nullptr, *bt_hout = nullptr;
+  size_t bt_out_cap = 0;
   // sharded evaluation (gogp_dist_init_*): 2-D block-cyclic state, nullptr on a single GPU
   gogp::Dist2D *dist = nullptr;
   hipStream_t sl = nullptr;  // forward substitution steps (low priority, off the chain)

@@ -320,6 +320,76 @@ class GP:
             self._check(rc if rc not in soft else _lib.GOGP_EARG)
         return lmls, grads, status
 
+    # ---- batches of independent small GPs (gogp_batch_*): many members, each with its own n and theta, ONE launch ----
+    def set_batch(self, X, Y, members):
+        """Upload the batch data: X (rows x NDim), Y (rows) and the members, a list of (offset, n) row ranges of them
+        (ranges may overlap: forecast windows are prefixes of the same data; n <= GOGP_BATCH_MAX_N).  Replaces the
+        previous batch data; the GP's own data and state are not touched."""
+        Xa = _arr(X).reshape(-1, self.NDim)
+        Ya = _arr(Y).reshape(-1)
+        if len(Xa) != len(Ya):
+            raise ValueError("len(X) != len(Y)")
+        mem = np.asarray(members, dtype=np.int64).reshape(-1, 2)
+        off = np.ascontiguousarray(mem[:, 0])
+        n = np.ascontiguousarray(mem[:, 1])
+        p64 = ctypes.POINTER(ctypes.c_int64)
+        self._check(_lib.lib().gogp_batch_set_data(self._h, _dp(Xa), _dp(Ya), len(Ya), len(mem),
+                                                   off.ctypes.data_as(p64), n.ctypes.data_as(p64)))
+        self._batch_members = len(mem)
+
+    def _batch_args(self, xs, members):
+        P = self._ns + self._nn
+        xs = _arr(xs)
+        xs = xs.reshape(-1, P) if P else xs.reshape(len(xs), 0)
+        k = xs.shape[0]
+        mem = np.arange(k) if members is None else np.asarray(members)
+        mem = np.ascontiguousarray(mem.astype(np.int32).reshape(-1))
+        if len(mem) != k:
+            raise ValueError("len(members) != len(xs)")
+        st = np.full(k, -1, dtype=np.intc)
+        return xs, k, P, mem, st
+
+    def _batch_status(self, rc, st):
+        # the call itself refused (nothing evaluated: no status written) or failed: raise; per-pair outcomes
+        # (GOGP_ENOTPD, GOGP_ECOND, GOGP_EARG of a non-finite row) are returned in status
+        if rc != _lib.GOGP_OK and (len(st) == 0 or (st < 0).any() or
+                                   rc not in (_lib.GOGP_ENOTPD, _lib.GOGP_ECOND, _lib.GOGP_EARG)):
+            self._check(rc)
+        return st.astype(int)
+
+    def batch_observe_gradient(self, xs, members=None):
+        """LML and gradient of k (member, log theta) pairs -- rows of xs, member members[i] (default: member i) -- in
+        ONE launch (gogp_batch_observe_gradient): what Observe(xs[i]) + Gradient() on a GP holding that member's data
+        would return.  Returns (lmls[k], grads[k x P], status[k]); a pair whose matrix is not positive definite has
+        status GOGP_ENOTPD, lml NaN and a zero gradient, one with non-finite parameters GOGP_EARG."""
+        xs, k, P, mem, st = self._batch_args(xs, members)
+        lmls, grads = np.zeros(k), np.zeros((k, P))
+        ip = ctypes.POINTER(ctypes.c_int)
+        rc = _lib.lib().gogp_batch_observe_gradient(self._h, k, mem.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                                    _dp(xs), P, _dp(lmls), _dp(grads), st.ctypes.data_as(ip))
+        return lmls, grads, self._batch_status(rc, st)
+
+    def batch_produce(self, xs, Zs, members=None):
+        """LML at xs[i] and the forecasts at the test points Zs[i] (an array of rows) of k (member, log theta) pairs in
+        ONE launch (gogp_batch_produce): what Observe(xs[i]) + Produce(Zs[i]) on a GP holding that member's data would
+        give.  Returns (lmls[k], [mu_i], [sigma_i], status[k]); NaN where the status is GOGP_ENOTPD or GOGP_EARG."""
+        xs, k, P, mem, st = self._batch_args(xs, members)
+        Zl = [_arr(z).reshape(-1, self.NDim) for z in Zs]
+        if len(Zl) != k:
+            raise ValueError("len(Zs) != len(xs)")
+        zoff = np.zeros(k + 1, dtype=np.int64)
+        zoff[1:] = np.cumsum([len(z) for z in Zl])
+        Z = np.ascontiguousarray(np.concatenate(Zl, axis=0)) if k else np.zeros((0, self.NDim))
+        m = int(zoff[-1])
+        lmls, mu, sigma = np.zeros(k), np.zeros(m), np.zeros(m)
+        ip = ctypes.POINTER(ctypes.c_int)
+        rc = _lib.lib().gogp_batch_produce(self._h, k, mem.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _dp(xs), P,
+                                           zoff.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), _dp(Z), _dp(lmls),
+                                           _dp(mu), _dp(sigma), st.ctypes.data_as(ip))
+        status = self._batch_status(rc, st)
+        return (lmls, [mu[zoff[i]:zoff[i + 1]] for i in range(k)], [sigma[zoff[i]:zoff[i + 1]] for i in range(k)],
+                status)
+
     def profile_read_launches(self):
         """Per launch of the tile kernel since profile_enable(True): arrays (start ms, end ms, flops, tag);
         tag = mode * 1e8 + (K / 16) * 1e5 + tiles.  Call before profile_read (which resets)."""

@@ -33,6 +33,10 @@ class Result:
     history: List[float] = field(default_factory=list)
 
 
+#: the ValueError of a run whose starting point is not feasible (K not usable there)
+INFEASIBLE_START = "initial point is not feasible"
+
+
 def func_grad(m):
     """infer.FuncGrad(m) (tutorial/tutorial.go:131): closures returning the
     NEGATED log-likelihood and gradient of an elemental model."""
@@ -69,7 +73,7 @@ def _lbfgs_steps(x0, major_iterations, gradient_threshold, history_size, max_ste
     evals = 1
     (f, g), = yield ("eval", x[None, :], True)
     if not np.isfinite(f):
-        raise ValueError("initial point is not feasible")
+        raise ValueError(INFEASIBLE_START)
     S: List[np.ndarray] = []
     Yv: List[np.ndarray] = []
     hist = [-f]
@@ -252,6 +256,41 @@ def lbfgs_multistart(m, x0s, major_iterations: int = 1000, gradient_threshold: f
     done = [r for r in results if r is not None]
     if done:
         m.Observe(max(done, key=lambda r: r.lml).x)
+    return results
+
+
+def lbfgs_lockstep(evaluate, x0s, major_iterations: int = 1000, gradient_threshold: float = 1e-6,
+                   history_size: int = 10, max_step_log: float = 2.0) -> List[Optional[Result]]:
+    """k L-BFGS runs in lock-step, run i from row i of ``x0s`` on an objective of its OWN (a forecast window, one
+    of many short series): every round asks ``evaluate(indices, xs)`` for the current trial point of every run that
+    is still going -- run indices[j] at xs[j] -- which returns a list of (f, g) per row: f the NEGATED objective
+    (inf where it is not usable) and g its gradient (negated as well; None only where f is not finite).  With
+    GP.batch_observe_gradient behind it, one round is one launch.  The loop of ``lbfgs_multistart`` with a separate
+    objective per run: each run takes exactly the path ``lbfgs`` takes alone on the same values.  Returns the k
+    Results; a run whose start is not feasible gets None (``lbfgs`` raises ValueError(INFEASIBLE_START) there)."""
+    x0s = np.atleast_2d(np.asarray(x0s, dtype=float))
+    gens = [_lbfgs_steps(x0, major_iterations, gradient_threshold, history_size, max_step_log, 1, None)
+            for x0 in x0s]
+    results: List[Optional[Result]] = [None] * len(gens)
+    pending = {i: next(gen) for i, gen in enumerate(gens)}
+    last = {}  # run -> the point of its last "eval" (a "grad" request asks for the gradient there)
+    while pending:
+        idx = sorted(pending)
+        xs = []
+        for i in idx:
+            req = pending[i]
+            if req[0] == "eval":
+                last[i] = req[1][0]
+            xs.append(last[i])
+        ans = evaluate(idx, np.array(xs))
+        for j, i in enumerate(idx):
+            try:
+                pending[i] = gens[i].send([ans[j]] if pending[i][0] == "eval" else ans[j][1])
+            except StopIteration as stop:
+                results[i] = stop.value
+                del pending[i]
+            except ValueError:  # infeasible start: this run yields nothing
+                del pending[i]
     return results
 
 

@@ -233,6 +233,34 @@ int gogp_observe_gradient_candidates(gogp_handle *h, int k, const double *x, int
  * No reference counterpart. */
 int gogp_graph_info(const gogp_handle *h, int64_t *nodes, int *refused);
 
+/* Batches of independent small GPs: many data sets, each with its own n and its own theta, evaluated in ONE launch
+ * (one workgroup per (member, theta) pair; one host-to-device copy of the pairs' parameters, one device-to-host copy
+ * of the results).  Counterpart: the reference's forecast harness, which fits the hyperparameters separately on every
+ * prefix X[:end] of the data (tutorial/tutorial.go:88-197), and any set of short series fitted with one kernel.
+ * The batch is fp64 whatever the options "precision" and "gradient_precision" are; "cond_limit_log10" and the
+ * handle's event discounts (gogp_set_events) apply.  Sharded handle: GOGP_EARG.  Hyperparameters-only form. */
+#define GOGP_BATCH_MAX_N 128
+/* Members are row ranges [offset[b], offset[b]+n[b]) of one uploaded X (rows x ndim) / y; ranges may
+   overlap (forecast windows are prefixes of the same data).  n[b] <= GOGP_BATCH_MAX_N (else GOGP_EARG).
+   Replaces the previous batch data; the handle's own data, factorisation, candidates arena are untouched. */
+int gogp_batch_set_data(gogp_handle *h, const double *X, const double *y, int64_t rows,
+                        int32_t nmembers, const int64_t *offset, const int64_t *n);
+/* k evaluations: member members[i] at log theta x[i*len .. +len) (len = P; hyperparameters-only form).
+   lmls[i], grads[i*len ..], status[i] as gogp_observe + gogp_gradient on a handle holding that member's
+   data would give, with the per-candidate contract of gogp_observe_gradient_candidates (ENOTPD: NaN and
+   zeros; ECOND: values returned; EARG: non-finite parameters).  Members may repeat.  ONE launch.
+   A member with n = 0: LML 0 and a zero gradient (gp/gp.go:101-104, 427-430).  A pair's results do not depend on
+   the other pairs of the call (bit for bit).  Returns the first non-zero status; status may be NULL. */
+int gogp_batch_observe_gradient(gogp_handle *h, int32_t k, const int32_t *members, const double *x,
+                                int64_t len, double *lmls, double *grads, int *status);
+/* Same k (member, log theta) pairs; test points of pair i are rows zoff[i] .. zoff[i+1] of Z (m x ndim):
+   LML at x and mu / sigma as gogp_observe + gogp_produce would give.  ONE launch.
+   zoff (k + 1 entries) is non-negative and non-decreasing; mu[j], sigma[j] belong to row j of Z.  sigma is unclamped
+   as in gogp_produce; n = 0: mu = 0, sigma = sqrt(prior) (gp/gp.go:343-347).  ENOTPD / EARG: lml, mu, sigma NaN. */
+int gogp_batch_produce(gogp_handle *h, int32_t k, const int32_t *members, const double *x, int64_t len,
+                       const int64_t *zoff /* k+1 */, const double *Z, double *lmls, double *mu,
+                       double *sigma, int *status);
+
 /* gp.GP.Produce (gp/gp.go:258-360): predictive mean and standard deviation of
  * the latent function at m points Z (row-major m x ndim).  sigma_j =
  * sqrt(k(z_j,z_j) - (Kstar^T K^-1 Kstar)_jj), unclamped like the reference
