@@ -131,7 +131,7 @@ static void drop_cand_graph(gogp_handle *h) {
   if (h->cand_graph) (void)hipGraphExecDestroy(h->cand_graph);
   h->cand_graph = nullptr;
   // "captured on its second identical use" starts over: what was seen was seen under the old options / buffers
-  h->cand_seen_key = decltype(h->cand_seen_key)();
+  h->cand_seen_key = CandGraphKey();
 }
 // the capture / replay stream belongs to the handle's pooled stream set (streams are never destroyed,
 // see "stream sets" below): created on first use, handed on with the set
@@ -318,7 +318,7 @@ extern "C" int gogp_create(const gogp_desc *desc, int device, gogp_handle **out)
   if (e == hipSuccess) e = hipMalloc(&h->devP, sizeof(DevParams));
   if (e == hipSuccess) e = hipHostMalloc((void **)&h->hostP, sizeof(DevParams), hipHostMallocDefault);
   if (e == hipSuccess)
-    e = hipHostMalloc((void **)&h->hscal, (NACC + 16) * sizeof(double), hipHostMallocDefault);
+    e = hipHostMalloc((void **)&h->hscal, BATCH_ROW * sizeof(double), hipHostMallocDefault);
   if (e != hipSuccess) {
     g_create_error = std::string("HIP initialisation failed: ") + hipGetErrorString(e);
     gogp_destroy(h);
@@ -491,11 +491,11 @@ static hipError_t cand_copy_in(gogp_handle *h, void *dst, const void *src, size_
     e = gogp::rec_memcpy_async((char *)dst + (size_t)c * h->cand_stride, src, bytes, hipMemcpyDeviceToDevice, s);
   return e;
 }
-// device results of every candidate into its row of the pinned staging block (rows of NACC + 16 doubles)
+// device results of every candidate into its row of the pinned staging block (rows of BATCH_ROW doubles, HS_*)
 static hipError_t cand_d2h(gogp_handle *h, double *hdst, const void *dsrc, size_t bytes, hipStream_t s) {
   hipError_t e = hipSuccess;
   for (int c = 0; c < h->batch_k && e == hipSuccess; ++c)
-    e = gogp::rec_memcpy_async(hdst + (size_t)c * (NACC + 16), (const char *)dsrc + (size_t)c * h->cand_stride, bytes,
+    e = gogp::rec_memcpy_async(hdst + (size_t)c * BATCH_ROW, (const char *)dsrc + (size_t)c * h->cand_stride, bytes,
                                hipMemcpyDeviceToHost, s);
   return e;
 }
@@ -536,7 +536,7 @@ static void d64_init(gogp_handle *, hipStream_t, const double *, int64_t, int, i
 
 // What the scalars of one factorisation say (row of the pinned staging block: [0] 2 sum log L_ii,
 // [1] z^T z, [3], [4] min / max L_ii, [5] fp64 log-determinant of the fp32 path, [6] y^T alpha of the
-// refined alpha, [8] first failing pivot + 1).
+// refined alpha, [HS_INFO] first failing pivot + 1).
 struct FactorResult {
   int rc = GOGP_OK;
   double lml = 0.0, cond_lb = 1.0, yta = 0.0;
@@ -547,7 +547,7 @@ struct FactorResult {
 static FactorResult judge_scalars(const gogp_handle *h, const double *hs, bool fp32, bool refine, int64_t n = -1) {
   FactorResult r;
   long long info = 0;
-  memcpy(&info, hs + 8, sizeof info);
+  memcpy(&info, hs + HS_INFO, sizeof info);
   char buf[160];
   if (info != 0) {
     r.rc = GOGP_ENOTPD;
@@ -575,6 +575,36 @@ static FactorResult judge_scalars(const gogp_handle *h, const double *hs, bool f
     r.rc = GOGP_ECOND;
   }
   return r;
+}
+
+// The end of a factorisation whose scalars are on their way to h->hscal on the main stream: in a batched evaluation the
+// caller synchronises and judges every candidate from its own row; otherwise wait, judge and keep the result.
+// kinv: K^-1 came with the factor (tiny_factorize).
+static int finish_factorize(gogp_handle *h, bool fp32, bool refine, bool kinv) {
+  h->alpha_pending = true;
+  if (h->batch_mode) {
+    h->factored = h->have_alpha = true;
+    if (kinv) h->have_kinv = true;
+    return GOGP_OK;
+  }
+  HIPCHK(h, hipStreamSynchronize(h->s));
+  HIPCHK(h, hipGetLastError());
+  const FactorResult fr = judge_scalars(h, h->hscal, fp32, refine);
+  if (fr.rc == GOGP_ENOTPD) {
+    h->alpha_pending = h->kinv_pending = false;
+    h->tinv_valid = h->tinv_pending = false;
+    h->trtri_done = h->trtri_pending = false;
+    h->notpd = fr.notpd;
+    h->err = fr.msg;
+    return GOGP_ENOTPD;
+  }
+  h->lml = fr.lml;
+  h->yta = fr.yta;
+  h->factored = h->have_alpha = true;
+  if (kinv) h->have_kinv = true;
+  h->cond_lb = fr.cond_lb;
+  if (fr.rc == GOGP_ECOND) h->err = fr.msg;
+  return fr.rc;
 }
 
 // ---- factorisation: Gram + blocked right-looking Cholesky + forward solve ----------------
@@ -1126,7 +1156,7 @@ static int factorize_t(gogp_handle *h, bool eager) {
     order(h, EV_ALPHA, sp, s);
   }
   HIPCHK(h, cand_d2h(h, h->hscal, h->scalars, 7 * sizeof(double), s));
-  HIPCHK(h, cand_d2h(h, h->hscal + 8, h->info, sizeof(long long), s));
+  HIPCHK(h, cand_d2h(h, h->hscal + HS_INFO, h->info, sizeof(long long), s));
   if (refine) {
     if (eager) (void)gogp::rec_event_record(ev(h, EV_TRTRI), st);
   } else if (eager && !mixed) {
@@ -1144,35 +1174,10 @@ static int factorize_t(gogp_handle *h, bool eager) {
       launch_trsv_bwd_step(sp, L, ld, Dinv, b, npanel, h->w, h->alpha);
     (void)gogp::rec_event_record(ev(h, EV_ALPHA), sp);
   }
-  h->alpha_pending = true;
-  if (h->batch_mode) {  // the caller synchronises and judges every candidate from its own row of hscal
-    h->factored = true;
-    h->have_alpha = true;
-    return GOGP_OK;
-  }
-  HIPCHK(h, hipStreamSynchronize(s));
-  HIPCHK(h, hipGetLastError());
-  const FactorResult fr = judge_scalars(h, h->hscal, sizeof(T) == 4, refine);
-  if (fr.rc == GOGP_ENOTPD) {
-    (void)hipStreamSynchronize(sp);
-    (void)hipStreamSynchronize(st);
-    (void)hipStreamSynchronize(s2);
-    (void)hipStreamSynchronize(h->sl);
-    (void)hipStreamSynchronize(h->sk);
-    h->alpha_pending = h->kinv_pending = false;
-    h->tinv_valid = h->tinv_pending = false;
-    h->trtri_done = h->trtri_pending = false;
-    h->notpd = fr.notpd;
-    h->err = fr.msg;
-    return GOGP_ENOTPD;
-  }
-  h->lml = fr.lml;
-  h->yta = fr.yta;
-  h->factored = true;
-  h->have_alpha = true;
-  h->cond_lb = fr.cond_lb;
-  if (fr.rc == GOGP_ECOND) h->err = fr.msg;
-  return fr.rc;
+  const int rcf = finish_factorize(h, sizeof(T) == 4, refine, false);
+  if (rcf == GOGP_ENOTPD)  // nothing of the failed factorisation may still run on the other streams
+    for (hipStream_t q : {sp, st, s2, h->sl, h->sk}) (void)hipStreamSynchronize(q);
+  return rcf;
 }
 
 // ---- option "tiny" (default on): N <= 128 observations, the whole factorisation in ONE launch (diag256.hip: tiny_eval_kernel)
@@ -1215,32 +1220,8 @@ static int tiny_factorize(gogp_handle *h, bool eager) {
   launch_lml_scalars(s, h->bufL, h->npad, h->z, nullptr, nullptr, h->n, h->scalars);
   (void)gogp::rec_event_record(ev(h, EV_ALPHA), s);
   HIPCHK(h, cand_d2h(h, h->hscal, h->scalars, 7 * sizeof(double), s));
-  HIPCHK(h, cand_d2h(h, h->hscal + 8, h->info, sizeof(long long), s));
-  h->alpha_pending = true;
-  if (h->batch_mode) {  // the caller synchronises and judges every candidate from its own row of hscal
-    h->factored = true;
-    h->have_alpha = true;
-    h->have_kinv = eager;
-    return GOGP_OK;
-  }
-  HIPCHK(h, hipStreamSynchronize(s));
-  HIPCHK(h, hipGetLastError());
-  const FactorResult fr = judge_scalars(h, h->hscal, false, false);
-  if (fr.rc == GOGP_ENOTPD) {
-    h->alpha_pending = false;
-    h->tinv_valid = h->tinv_pending = false;
-    h->notpd = fr.notpd;
-    h->err = fr.msg;
-    return GOGP_ENOTPD;
-  }
-  h->lml = fr.lml;
-  h->yta = fr.yta;
-  h->factored = true;
-  h->have_alpha = true;
-  h->have_kinv = eager;
-  h->cond_lb = fr.cond_lb;
-  if (fr.rc == GOGP_ECOND) h->err = fr.msg;
-  return fr.rc;
+  HIPCHK(h, cand_d2h(h, h->hscal + HS_INFO, h->info, sizeof(long long), s));
+  return finish_factorize(h, false, false, eager);
 }
 
 static int factorize(gogp_handle *h, bool eager) {
@@ -1456,6 +1437,32 @@ static void fp32_gradient_identities(const gogp_handle *h, double *a, double tra
   if (d.nterms == 1 && d.terms[0].scale_idx >= 0) a[0] = (yta - (double)h->n) - noise_var * trace_w;
 }
 
+// Enqueue on the main stream: the gradient's slot sums over the current K^-1 into the pinned row(s) at HS_GRAD, and with
+// `trace` tr(alpha alpha^T - K^-1) in fp64 from the float Y itself (solve.hip: launch_trace_from_y) into HS_TRACE, NaN
+// without.  rw (fp32 path) / w (mixed gradient: the substitution's scratch, done with) and scalars[7] are free here.
+static int enqueue_grad_sums(gogp_handle *h, bool trace) {
+  hipStream_t s = h->s;
+  auto reduce = [&](auto *kinv) {
+    AuxTimer tm(h, GOGP_PROF_GRAD, s);
+    launch_grad_reduce(s, h->devP, h->D, h->ard_dims, h->dX, h->alpha, kinv, h->npad, h->n, h->npad, h->gpart, h->gout,
+                       h->radial1, h->ard_mfma_min, h->ev());
+  };
+  if (h->prec == 32)
+    reduce(reinterpret_cast<const float *>(h->bufA));
+  else if (mixed_gradient(h))
+    reduce((const float *)h->g32A);
+  else
+    reduce((const double *)h->bufA);
+  HIPCHK(h, cand_d2h(h, h->hscal + HS_GRAD, h->gout, NACC * sizeof(double), s));
+  h->hscal[HS_TRACE] = NAN;
+  if (trace) {
+    launch_trace_from_y(s, h->prec == 32 ? reinterpret_cast<const float *>(h->bufY) : (const float *)h->g32Y, h->npad, h->n,
+                        h->npad, h->alpha, h->prec == 32 ? h->rw : h->w, h->scalars + 7);
+    HIPCHK(h, hipMemcpyAsync(h->hscal + HS_TRACE, h->scalars + 7, sizeof(double), hipMemcpyDeviceToHost, s));
+  }
+  return GOGP_OK;
+}
+
 extern "C" int gogp_gradient(gogp_handle *h, double *grad, int64_t len) {
   if (!h || !grad) return fail(h, GOGP_EARG, "gradient: NULL");
   if (!h->observed) return fail(h, GOGP_ESTATE, "Gradient before Observe");
@@ -1471,48 +1478,28 @@ extern "C" int gogp_gradient(gogp_handle *h, double *grad, int64_t len) {
     return fail(h, GOGP_EARG, "gradient_precision = 32: the full Observe form is not supported");
   if (!h->grad_valid && h->dist) {
     // sharded: every rank reduces its own tiles of K^-1, one all-reduce of the slot sums
-    int rc = gogp_dist_gradient_sums(h, h->hscal + 16);
+    int rc = gogp_dist_gradient_sums(h, h->hscal + HS_GRAD);
     if (rc != GOGP_OK) return rc;
     // float tiles: the output-scale component from its closed form (fp32_gradient_identities); the trace slot already
     // holds |alpha|^2 - |Y|_F^2 from fp64 sums over the shards' chunks of Y (dist2d.hip: gogp_dist_gradient_sums)
     if (h->prec == 32 && h->trace_fp64)
-      fp32_gradient_identities(h, h->hscal + 16, h->hscal[16 + ACC_TRACE], h->yta, h->hostP->noise_var);
+      fp32_gradient_identities(h, h->hscal + HS_GRAD, h->hscal[HS_GRAD + ACC_TRACE], h->yta, h->hostP->noise_var);
   } else if (!h->grad_valid) {
     int rc = compute_kinv(h);
     if (rc != GOGP_OK) return rc;
     rc = ensure_alpha(h);
     if (rc != GOGP_OK) return rc;
-    hipStream_t s = h->s;
-    {
-      AuxTimer tm(h, GOGP_PROF_GRAD, s);
-      if (h->prec == 32)
-        launch_grad_reduce(s, h->devP, h->D, h->ard_dims, h->dX, h->alpha,
-                           reinterpret_cast<const float *>(h->bufA), h->npad, h->n, h->npad, h->gpart, h->gout, h->radial1, h->ard_mfma_min, h->ev());
-      else if (mixed_gradient(h))
-        launch_grad_reduce(s, h->devP, h->D, h->ard_dims, h->dX, h->alpha, (const float *)h->g32A, h->npad, h->n,
-                           h->npad, h->gpart, h->gout, h->radial1, h->ard_mfma_min, h->ev());
-      else
-        launch_grad_reduce(s, h->devP, h->D, h->ard_dims, h->dX, h->alpha, h->bufA, h->npad, h->n,
-                           h->npad, h->gpart, h->gout, h->radial1, h->ard_mfma_min, h->ev());
-    }
-    HIPCHK(h, cand_d2h(h, h->hscal + 16, h->gout, NACC * sizeof(double), s));
-    h->hscal[9] = NAN;
     const bool f32k = h->prec == 32 || mixed_gradient(h);  // K^-1 and Y are float
-    if (f32k && h->trace_fp64 && (h->prec == 32 ? h->bufY : (double *)h->g32Y) && h->trtri_done) {
-      // tr(alpha alpha^T - K^-1) in fp64 from Y itself (solve.hip: launch_trace_from_y); rw (fp32 path) / w (mixed
-      // gradient: the substitution's scratch, done with) and scalars[7] are free here
-      launch_trace_from_y(s, h->prec == 32 ? reinterpret_cast<const float *>(h->bufY) : (const float *)h->g32Y, h->npad, h->n,
-                          h->npad, h->alpha, h->prec == 32 ? h->rw : h->w, h->scalars + 7);
-      HIPCHK(h, hipMemcpyAsync(h->hscal + 9, h->scalars + 7, sizeof(double), hipMemcpyDeviceToHost, s));
-    }
-    HIPCHK(h, hipStreamSynchronize(s));
+    rc = enqueue_grad_sums(h, f32k && h->trace_fp64 && (h->prec == 32 ? h->bufY : (double *)h->g32Y) && h->trtri_done);
+    if (rc != GOGP_OK) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->s));
     HIPCHK(h, hipGetLastError());
-    if (f32k && std::isfinite(h->hscal[9]))
-      fp32_gradient_identities(h, h->hscal + 16, h->hscal[9], h->yta, h->hostP->noise_var);
+    if (f32k && std::isfinite(h->hscal[HS_TRACE]))
+      fp32_gradient_identities(h, h->hscal + HS_GRAD, h->hscal[HS_TRACE], h->yta, h->hostP->noise_var);
   }
   if (!h->grad_valid) {
     h->grad_cache.assign(h->P, 0.0);
-    assemble_gradient(h, h->hscal + 16, h->hostP->dnoise, h->grad_cache.data());
+    assemble_gradient(h, h->hscal + HS_GRAD, h->hostP->dnoise, h->grad_cache.data());
     h->grad_valid = true;
   }
   for (int i = 0; i < h->P; ++i) grad[i] = h->grad_cache[i];
@@ -1534,6 +1521,43 @@ extern "C" int gogp_gradient(gogp_handle *h, double *grad, int64_t len) {
     for (int64_t i = 0; i < n; ++i) grad[h->P + n * h->D + i] = -grad[h->P + n * h->D + i];
   }
   return GOGP_OK;
+}
+
+// ---- one evaluation of many (the candidates call, batch_eval): parameters in, results out ----------------------------
+// DevParams of log parameters x (gp/gp.go:378-385: theta = exp(x)).  Unusable parameters are replaced by theta = 1 and
+// reported as GOGP_EARG: that evaluation is still launched with the others, and its status says so.
+static int fill_params_log(const gogp_handle *h, const double *x, DevParams &p) {
+  std::vector<double> th((size_t)std::max(h->P, 1));
+  for (int i = 0; i < h->P; ++i) th[(size_t)i] = exp(x[i]);
+  int rc = GOGP_OK;
+  if (theta_refusal(h, th.data(), th.data() + h->ns)) {
+    rc = GOGP_EARG;
+    std::fill(th.begin(), th.end(), 1.0);
+  }
+  fill_params_theta(h, th.data(), th.data() + h->ns, p);
+  return rc;
+}
+
+// The status of one evaluation of n observations at parameters p from its pinned row (HS_*): its LML into *lml and,
+// g != nullptr, its gradient (len entries) into g; NaN and zeros when the parameters were refused (st, fill_params_log)
+// or the matrix is not positive definite.  The first failure's message goes to first_msg.
+static int judge_row(const gogp_handle *h, double *row, bool fp32, int64_t n, const DevParams &p, int st,
+                     const char *refused, double *lml, double *g, int64_t len, std::string &first_msg) {
+  *lml = NAN;
+  if (g) std::fill(g, g + len, 0.0);
+  if (st != GOGP_OK) {
+    if (first_msg.empty()) first_msg = refused;
+    return st;
+  }
+  const FactorResult fr = judge_scalars(h, row, fp32, fp32, n);
+  if (fr.rc != GOGP_OK && first_msg.empty()) first_msg = fr.msg;
+  if (fr.rc != GOGP_ENOTPD) {
+    *lml = fr.lml;
+    if (fp32 && std::isfinite(row[HS_TRACE]))
+      fp32_gradient_identities(h, row + HS_GRAD, row[HS_TRACE], fr.yta, p.noise_var);
+    if (g) assemble_gradient(h, row + HS_GRAD, p.dnoise, g);
+  }
+  return fr.rc;
 }
 
 // ---- several candidates at once ---------------------------------------------------------------------
@@ -1575,32 +1599,29 @@ static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 constexpr int64_t GRAPH_MAX_NPAD = 1024;           // option "graph" = 1: one chain in enqueue order
 constexpr int64_t GRAPH_EXPLICIT_MAX_NPAD = 8192;  // option "graph" = 2: the sweep's dependencies as edges
 
-struct CandLayout {
-  size_t devP, info, scalars, gout, bufA, bufL, bufY, Dinv, z, w, alpha, gpart, total;
-};
-static CandLayout cand_layout(int64_t npad, size_t esz = sizeof(double)) {
-  CandLayout L;
+// the per-candidate buffers of the arena slot at `base`; *bytes: the size of a slot
+static EvalBufs cand_layout(char *base, int64_t npad, size_t esz, size_t *bytes = nullptr) {
+  EvalBufs b;
   size_t o = 0;
-  auto take = [&](size_t bytes) {
-    const size_t at = o;
-    o += align_up(bytes, 256);
-    return at;
+  auto take = [&](auto *&p, size_t n) {
+    p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(reinterpret_cast<uintptr_t>(base) + o);
+    o += align_up(n, 256);
   };
   const size_t nn = (size_t)npad * (size_t)npad * esz;  // matrices: float on the fp32 path
-  L.devP = take(sizeof(DevParams));
-  L.info = take(sizeof(long long));
-  L.scalars = take(8 * sizeof(double));
-  L.gout = take(NACC * sizeof(double));
-  L.z = take((size_t)npad * sizeof(double));
-  L.w = take((size_t)npad * sizeof(double));
-  L.alpha = take((size_t)npad * sizeof(double));
-  L.gpart = take((size_t)grad_reduce_blocks(npad) * NACC * sizeof(double));
-  L.Dinv = take((size_t)(npad / PANEL) * PANEL * PANEL * esz);
-  L.bufA = take(nn);
-  L.bufL = take(nn);
-  L.bufY = take(nn);
-  L.total = align_up(o, 4096);
-  return L;
+  take(b.devP, sizeof(DevParams));
+  take(b.info, sizeof(long long));
+  take(b.scalars, 8 * sizeof(double));
+  take(b.gout, NACC * sizeof(double));
+  take(b.z, (size_t)npad * sizeof(double));
+  take(b.w, (size_t)npad * sizeof(double));
+  take(b.alpha, (size_t)npad * sizeof(double));
+  take(b.gpart, (size_t)grad_reduce_blocks(npad) * NACC * sizeof(double));
+  take(b.Dinv, (size_t)(npad / PANEL) * PANEL * PANEL * esz);
+  take(b.bufA, nn);
+  take(b.bufL, nn);
+  take(b.bufY, nn);
+  if (bytes) *bytes = align_up(o, 4096);
+  return b;
 }
 
 static int ensure_candidates(gogp_handle *h, int k) {
@@ -1612,8 +1633,7 @@ static int ensure_candidates(gogp_handle *h, int k) {
     h->cand_hscal = nullptr;
     h->cand_host_k = 0;
     HIPCHK(h, hipHostMalloc((void **)&h->cand_hostP, (size_t)k * sizeof(DevParams), hipHostMallocDefault));
-    HIPCHK(h, hipHostMalloc((void **)&h->cand_hscal, (size_t)k * (NACC + 16) * sizeof(double),
-                            hipHostMallocDefault));
+    HIPCHK(h, hipHostMalloc((void **)&h->cand_hscal, (size_t)k * BATCH_ROW * sizeof(double), hipHostMallocDefault));
     h->cand_host_k = k;
   }
   if (k > h->cand_cap_k || h->npad > h->cand_cap_npad) {
@@ -1625,13 +1645,18 @@ static int ensure_candidates(gogp_handle *h, int k) {
     h->cand_cap_k = 0;
     h->cand_cap_npad = 0;
     const int64_t cap = std::max(h->npad, h->cand_cap_npad);
-    const CandLayout L = cand_layout(cap, h->esz());
-    HIPCHK(h, hipMalloc((void **)&h->cand_arena, L.total * (size_t)k));
-    h->cand_stride = L.total;
+    size_t stride = 0;
+    (void)cand_layout(nullptr, cap, h->esz(), &stride);
+    HIPCHK(h, hipMalloc((void **)&h->cand_arena, stride * (size_t)k));
+    h->cand_stride = stride;
     h->cand_cap_k = k;
     h->cand_cap_npad = cap;
   }
   return GOGP_OK;
+}
+
+static CandGraphKey cand_graph_key(const gogp_handle *h, int k) {
+  return {k, h->n, h->cand_cap_npad, h->cand_stride, h->cand_arena, h->dX, h->dy, h->cand_hostP, h->cand_hscal};
 }
 
 extern "C" int gogp_observe_gradient_candidates(gogp_handle *h, int k, const double *xs, int64_t len,
@@ -1707,31 +1732,11 @@ extern "C" int gogp_observe_gradient_candidates(gogp_handle *h, int k, const dou
   if (rc != GOGP_OK) return rc;
 
   // ---- the handle works in arena slot 0 for the duration of the call ---------------------------------
-  struct Saved {
-    DevParams *devP;
-    long long *info;
-    double *scalars, *gout, *bufA, *bufL, *bufY, *Dinv, *z, *w, *alpha, *gpart, *hscal;
-    int64_t cap_y, notpd;
-    bool factored, have_alpha, have_kinv, observed, with_obs, grad_valid, trtri_done;
-    double lml, cond_lb;
-    std::vector<double> theta_s, theta_n;
-  } sv{h->devP, h->info, h->scalars, h->gout, h->bufA, h->bufL, h->bufY, h->Dinv, h->z, h->w, h->alpha,
-       h->gpart, h->hscal, h->cap_y, h->notpd, h->factored, h->have_alpha, h->have_kinv, h->observed,
-       h->with_obs, h->grad_valid, h->trtri_done, h->lml, h->cond_lb, h->theta_s, h->theta_n};
-  const CandLayout L = cand_layout(h->cand_cap_npad, h->esz());
-  char *a0 = h->cand_arena;
-  h->devP = (DevParams *)(a0 + L.devP);
-  h->info = (long long *)(a0 + L.info);
-  h->scalars = (double *)(a0 + L.scalars);
-  h->gout = (double *)(a0 + L.gout);
-  h->bufA = (double *)(a0 + L.bufA);
-  h->bufL = (double *)(a0 + L.bufL);
-  h->bufY = (double *)(a0 + L.bufY);
-  h->Dinv = (double *)(a0 + L.Dinv);
-  h->z = (double *)(a0 + L.z);
-  h->w = (double *)(a0 + L.w);
-  h->alpha = (double *)(a0 + L.alpha);
-  h->gpart = (double *)(a0 + L.gpart);
+  const EvalBufs saved_bufs = *h;
+  const EvalState saved_state = *h;
+  double *const saved_hscal = h->hscal;
+  const int64_t saved_cap_y = h->cap_y;
+  static_cast<EvalBufs &>(*h) = cand_layout(h->cand_arena, h->cand_cap_npad, h->esz());
   h->hscal = h->cand_hscal;
   h->cap_y = h->cand_cap_npad;
   h->with_obs = false;
@@ -1741,18 +1746,8 @@ extern "C" int gogp_observe_gradient_candidates(gogp_handle *h, int k, const dou
   gogp::tl_batch.stride = (long)h->cand_stride;
   std::vector<int> st((size_t)k, GOGP_OK);
 
-  // parameters of every candidate (gp/gp.go:378-385: theta = exp(x)) into pinned host memory; a
-  // candidate with unusable parameters is evaluated at theta = 1 and reported as GOGP_EARG
-  for (int c = 0; c < k; ++c) {
-    std::vector<double> th((size_t)h->P);
-    for (int i = 0; i < h->P; ++i) th[(size_t)i] = exp(xs[(size_t)c * len + i]);
-    if (set_theta_natural(h, th.data(), th.data() + h->ns) != GOGP_OK) {
-      st[(size_t)c] = GOGP_EARG;
-      std::fill(th.begin(), th.end(), 1.0);
-      (void)set_theta_natural(h, th.data(), th.data() + h->ns);
-    }
-    fill_params(h, h->cand_hostP[c]);
-  }
+  // parameters of every candidate into pinned host memory
+  for (int c = 0; c < k; ++c) st[(size_t)c] = fill_params_log(h, xs + (size_t)c * len, h->cand_hostP[c]);
   // the whole launch sequence: parameter upload, fused sweep, K^-1, gradient sums, results to the host
   auto enqueue = [&]() -> int {
     for (int c = 0; c < k; ++c)
@@ -1765,22 +1760,8 @@ extern "C" int gogp_observe_gradient_candidates(gogp_handle *h, int k, const dou
     if (r != GOGP_OK) return r;
     r = ensure_alpha(h);
     if (r != GOGP_OK) return r;
-    {
-      AuxTimer tm(h, GOGP_PROF_GRAD, h->s);
-      if (f32)
-        launch_grad_reduce(h->s, h->devP, h->D, h->ard_dims, h->dX, h->alpha, reinterpret_cast<const float *>(h->bufA),
-                           h->npad, h->n, h->npad, h->gpart, h->gout, h->radial1, h->ard_mfma_min, h->ev());
-      else
-        launch_grad_reduce(h->s, h->devP, h->D, h->ard_dims, h->dX, h->alpha, h->bufA, h->npad, h->n, h->npad,
-                           h->gpart, h->gout, h->radial1, h->ard_mfma_min, h->ev());
-    }
-    HIPCHK(h, cand_d2h(h, h->hscal + 16, h->gout, NACC * sizeof(double), h->s));
-    h->hscal[9] = NAN;
-    if (f32 && h->trace_fp64) {  // the fp32 path's closed-form components (fp32_gradient_identities)
-      launch_trace_from_y(h->s, reinterpret_cast<const float *>(h->bufY), h->npad, h->n, h->npad, h->alpha, h->rw,
-                          h->scalars + 7);
-      HIPCHK(h, hipMemcpyAsync(h->hscal + 9, h->scalars + 7, sizeof(double), hipMemcpyDeviceToHost, h->s));
-    }
+    r = enqueue_grad_sums(h, f32 && h->trace_fp64);  // the fp32 path's closed-form components (fp32_gradient_identities)
+    if (r != GOGP_OK) return r;
     // every stream joins the main one (the end of a captured graph; harmless otherwise)
     size_t slot = EV_BASE + 4 * (size_t)(h->npad / PANEL);  // the four event slots behind the panels' own
     for (hipStream_t q : {h->sp, h->s2, h->st, h->sl, h->sk}) order(h, slot++, q, h->s);
@@ -1797,109 +1778,67 @@ extern "C" int gogp_observe_gradient_candidates(gogp_handle *h, int k, const dou
     const bool dag = h->use_graph >= 2;  // 3: the same recorder as ONE chain in enqueue order (diagnostics)
     const bool graph = h->use_graph && h->prec == 64 && !h->prof.on && !h->graph_failed &&
                        h->npad <= (dag ? GRAPH_EXPLICIT_MAX_NPAD : GRAPH_MAX_NPAD);
-    auto &key = h->cand_graph_key;
-    auto same = [&](const decltype(h->cand_graph_key) &q) {
-      return q.k == k && q.n == h->n && q.superpanel == h->superpanel + 16 * h->superpanel_head + 256 * h->head_remaining + 4096 * h->use_graph && q.arena == h->cand_arena &&
-             q.stride == h->cand_stride && q.cap_npad == h->cand_cap_npad && q.kinv_fused == h->kinv_fused &&
-             q.dX == h->dX && q.dy == h->dy && q.hostP == h->cand_hostP && q.hscal == h->cand_hscal;
-    };
-    const bool hit = graph && h->cand_graph && same(key);
+    const CandGraphKey key = cand_graph_key(h, k);
+    const bool hit = graph && h->cand_graph && h->cand_graph_key == key;
     // capture only a sequence that was asked for twice in a row (an expanding-window loop changes n
     // with every call: capturing each time would cost more than the replay saves)
-    const bool seen = graph && same(h->cand_seen_key);
-    h->cand_seen_key.k = k;
-    h->cand_seen_key.n = h->n;
-    h->cand_seen_key.superpanel = h->superpanel + 16 * h->superpanel_head + 256 * h->head_remaining + 4096 * h->use_graph;
-    h->cand_seen_key.arena = h->cand_arena;
-    h->cand_seen_key.stride = h->cand_stride;
-    h->cand_seen_key.cap_npad = h->cand_cap_npad;
-    h->cand_seen_key.kinv_fused = h->kinv_fused;
-    h->cand_seen_key.dX = h->dX;
-    h->cand_seen_key.dy = h->dy;
-    h->cand_seen_key.hostP = h->cand_hostP;
-    h->cand_seen_key.hscal = h->cand_hscal;
+    const bool seen = graph && h->cand_seen_key == key;
+    h->cand_seen_key = key;
     if (hit || seen) {
-      if (!hit && dag) {
-        // No stream is captured: the launch sequence is replayed into a recorder that adds one node per launch /
-        // copy with explicit dependencies (graphrec.h), so hipStreamEndCapture's trouble with the sweep's fork / join
-        // pattern (round 2) never arises.
+      if (!hit) {
         drop_cand_graph(h);
         HIPCHK(h, graph_stream(h));
+        hipGraph_t gr = nullptr;
+        hipError_t eg = hipSuccess;
         gogp::GraphRec rec;
-        rec.chain = h->use_graph == 3;
-        HIPCHK(h, hipGraphCreate(&rec.graph, 0));
-        gogp::tl_rec = &rec;
-        r = enqueue();
-        gogp::tl_rec = nullptr;
-        hipError_t ei = (r == GOGP_OK) ? rec.err : hipSuccess;
-        if (r == GOGP_OK && ei == hipSuccess) ei = hipGraphInstantiate(&h->cand_graph, rec.graph, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(rec.graph);
+        if (dag) {
+          // No stream is captured: the launch sequence is replayed into a recorder that adds one node per launch /
+          // copy with explicit dependencies (graphrec.h), so hipStreamEndCapture's trouble with the sweep's fork / join
+          // pattern (round 2) never arises.
+          rec.chain = h->use_graph == 3;
+          HIPCHK(h, hipGraphCreate(&rec.graph, 0));
+          gogp::tl_rec = &rec;
+          r = enqueue();
+          gogp::tl_rec = nullptr;
+          gr = rec.graph;
+          eg = rec.err;
+        } else {
+          // Captured on ONE stream (the five work streams aliased to it for the duration): a linear
+          // graph.  hipStreamEndCapture of this ROCm (7.0 runtime bundled with torch) recurses without
+          // end on the sweep's fork / join pattern across streams, so the graph path is limited to
+          // sizes where the evaluation is a single dependent chain anyway (see the caller).
+          hipStream_t keep[6] = {h->s, h->sp, h->s2, h->st, h->sl, h->sk};
+          h->s = h->sp = h->s2 = h->st = h->sl = h->sk = h->sg;
+          eg = hipStreamBeginCapture(h->sg, hipStreamCaptureModeRelaxed);
+          if (eg == hipSuccess) {
+            r = enqueue();
+            eg = hipStreamEndCapture(h->sg, &gr);
+          }
+          h->s = keep[0];
+          h->sp = keep[1];
+          h->s2 = keep[2];
+          h->st = keep[3];
+          h->sl = keep[4];
+          h->sk = keep[5];
+        }
+        if (r == GOGP_OK && eg == hipSuccess) eg = hipGraphInstantiate(&h->cand_graph, gr, nullptr, nullptr, 0);
+        if (gr) (void)hipGraphDestroy(gr);
         if (r != GOGP_OK) return r;
-        if (ei != hipSuccess) {
+        if (eg != hipSuccess && dag) {
           // the runtime refused the graph: remember it, say why, and evaluate on the streams (never retried)
           (void)hipGetLastError();
           h->cand_graph = nullptr;
           h->graph_failed = true;
-          h->graph_note = std::string("hipGraph not usable (") + hipGetErrorString(ei) + "): stream path";
+          h->graph_note = std::string("hipGraph not usable (") + hipGetErrorString(eg) + "): stream path";
           r = enqueue();
           if (r != GOGP_OK) return r;
           for (hipStream_t q : work_streams(h)) HIPCHK(h, hipStreamSynchronize(q));
           HIPCHK(h, hipGetLastError());
           return GOGP_OK;
         }
-        h->graph_nodes = rec.nodes;
-        key.k = k;
-        key.n = h->n;
-        key.superpanel = h->superpanel + 16 * h->superpanel_head + 256 * h->head_remaining + 4096 * h->use_graph;
-        key.arena = h->cand_arena;
-        key.stride = h->cand_stride;
-        key.cap_npad = h->cand_cap_npad;
-        key.kinv_fused = h->kinv_fused;
-        key.dX = h->dX;
-        key.dy = h->dy;
-        key.hostP = h->cand_hostP;
-        key.hscal = h->cand_hscal;
-      } else if (!hit) {
-        drop_cand_graph(h);
-        hipGraph_t gr = nullptr;
-        // Captured on ONE stream (the five work streams aliased to it for the duration): a linear
-        // graph.  hipStreamEndCapture of this ROCm (7.0 runtime bundled with torch) recurses without
-        // end on the sweep's fork / join pattern across streams, so the graph path is limited to
-        // sizes where the evaluation is a single dependent chain anyway (see the caller).
-        HIPCHK(h, graph_stream(h));
-        hipStream_t keep[6] = {h->s, h->sp, h->s2, h->st, h->sl, h->sk};
-        h->s = h->sp = h->s2 = h->st = h->sl = h->sk = h->sg;
-        const hipError_t eb = hipStreamBeginCapture(h->sg, hipStreamCaptureModeRelaxed);
-        hipError_t ec = eb;
-        if (eb == hipSuccess) {
-          r = enqueue();
-          ec = hipStreamEndCapture(h->sg, &gr);
-        }
-        h->s = keep[0];
-        h->sp = keep[1];
-        h->s2 = keep[2];
-        h->st = keep[3];
-        h->sl = keep[4];
-        h->sk = keep[5];
-        if (r != GOGP_OK) {
-          if (gr) (void)hipGraphDestroy(gr);
-          return r;
-        }
-        HIPCHK(h, ec);
-        const hipError_t ei = hipGraphInstantiate(&h->cand_graph, gr, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(gr);
-        HIPCHK(h, ei);
-        key.k = k;
-        key.n = h->n;
-        key.superpanel = h->superpanel + 16 * h->superpanel_head + 256 * h->head_remaining + 4096 * h->use_graph;
-        key.arena = h->cand_arena;
-        key.stride = h->cand_stride;
-        key.cap_npad = h->cand_cap_npad;
-        key.kinv_fused = h->kinv_fused;
-        key.dX = h->dX;
-        key.dy = h->dy;
-        key.hostP = h->cand_hostP;
-        key.hscal = h->cand_hscal;
+        HIPCHK(h, eg);
+        if (dag) h->graph_nodes = rec.nodes;
+        h->cand_graph_key = key;
       }
       HIPCHK(h, hipGraphLaunch(h->cand_graph, h->sg));
       HIPCHK(h, hipStreamSynchronize(h->sg));
@@ -1919,24 +1858,9 @@ extern "C" int gogp_observe_gradient_candidates(gogp_handle *h, int k, const dou
   int first = rc;
   if (rc == GOGP_OK) {
     for (int c = 0; c < k; ++c) {
-      const double *hs = h->hscal + (size_t)c * (NACC + 16);
-      double *g = grads + (size_t)c * len;
-      for (int64_t i = 0; i < len; ++i) g[i] = 0.0;
-      lmls[c] = NAN;
-      if (st[(size_t)c] == GOGP_OK) {
-        const bool f32 = h->prec == 32;
-        const FactorResult fr = judge_scalars(h, hs, f32, f32);
-        st[(size_t)c] = fr.rc;
-        if (fr.rc != GOGP_ENOTPD) {
-          lmls[c] = fr.lml;
-          if (f32 && std::isfinite(hs[9]))
-            fp32_gradient_identities(h, const_cast<double *>(hs) + 16, hs[9], fr.yta, h->cand_hostP[c].noise_var);
-          assemble_gradient(h, hs + 16, h->cand_hostP[c].dnoise, g);
-        }
-        if (fr.rc != GOGP_OK && first_msg.empty()) first_msg = fr.msg;
-      } else if (first_msg.empty()) {
-        first_msg = "candidates: parameters must be positive and finite";
-      }
+      st[(size_t)c] = judge_row(h, h->hscal + (size_t)c * BATCH_ROW, h->prec == 32, h->n, h->cand_hostP[c], st[(size_t)c],
+                                "candidates: parameters must be positive and finite", &lmls[c], grads + (size_t)c * len,
+                                len, first_msg);
       if (first == GOGP_OK && st[(size_t)c] != GOGP_OK) first = st[(size_t)c];
     }
   }
@@ -1948,33 +1872,11 @@ extern "C" int gogp_observe_gradient_candidates(gogp_handle *h, int k, const dou
   gogp::tl_batch.stride = 0;
   h->batch_k = 1;
   h->batch_mode = false;
-  h->devP = sv.devP;
-  h->info = sv.info;
-  h->scalars = sv.scalars;
-  h->gout = sv.gout;
-  h->bufA = sv.bufA;
-  h->bufL = sv.bufL;
-  h->bufY = sv.bufY;
-  h->Dinv = sv.Dinv;
-  h->z = sv.z;
-  h->w = sv.w;
-  h->alpha = sv.alpha;
-  h->gpart = sv.gpart;
-  h->hscal = sv.hscal;
-  h->cap_y = sv.cap_y;
-  h->notpd = sv.notpd;
-  h->factored = sv.factored;
-  h->have_alpha = sv.have_alpha;
-  h->have_kinv = sv.have_kinv;
-  h->observed = sv.observed;
-  h->with_obs = sv.with_obs;
-  h->grad_valid = sv.grad_valid;
-  h->trtri_done = sv.trtri_done;
+  static_cast<EvalBufs &>(*h) = saved_bufs;
+  static_cast<EvalState &>(*h) = saved_state;
+  h->hscal = saved_hscal;
+  h->cap_y = saved_cap_y;
   h->trtri_pending = h->alpha_pending = h->kinv_pending = false;
-  h->lml = sv.lml;
-  h->cond_lb = sv.cond_lb;
-  h->theta_s = sv.theta_s;
-  h->theta_n = sv.theta_n;
   if (first != GOGP_OK && rc == GOGP_OK) h->err = first_msg;
   return first;
 }
@@ -2062,19 +1964,12 @@ static int batch_eval(gogp_handle *h, int32_t k, const int32_t *members, const d
   int rc = bt_reserve(h, &h->bt_din, &h->bt_hin, &h->bt_in_cap, in_bytes);
   if (rc == GOGP_OK) rc = bt_reserve(h, (char **)&h->bt_dout, (char **)&h->bt_hout, &h->bt_out_cap, out_bytes);
   if (rc != GOGP_OK) return rc;
-  // the pairs' parameters (gp/gp.go:378-385: theta = exp(x)), with the fill of the single-handle path; a pair with
-  // unusable parameters is evaluated at theta = 1 and reported as GOGP_EARG
+  // the pairs' parameters, with the fill of the candidates call
   std::vector<int> st((size_t)k, GOGP_OK);
   BatchItem *items = reinterpret_cast<BatchItem *>(h->bt_hin);
-  std::vector<double> th((size_t)std::max(h->P, 1));
   for (int32_t i = 0; i < k; ++i) {
-    for (int q = 0; q < h->P; ++q) th[(size_t)q] = exp(x[(size_t)i * len + q]);
-    if (theta_refusal(h, th.data(), th.data() + h->ns)) {
-      st[(size_t)i] = GOGP_EARG;
-      std::fill(th.begin(), th.end(), 1.0);
-    }
     BatchItem &it = items[i];
-    fill_params_theta(h, th.data(), th.data() + h->ns, it.P);
+    st[(size_t)i] = fill_params_log(h, x + (size_t)i * len, it.P);
     it.off = (long)h->bt_off[(size_t)members[i]];
     it.n = (long)h->bt_n[(size_t)members[i]];
     it.zoff = produce ? (long)zoff[i] : 0;
@@ -2095,28 +1990,16 @@ static int batch_eval(gogp_handle *h, int32_t k, const int32_t *members, const d
   int first = GOGP_OK;
   std::string first_msg;
   for (int32_t i = 0; i < k; ++i) {
-    const double *row = h->bt_hout + (size_t)i * BATCH_ROW;
     const BatchItem &it = items[i];
     double *g = produce ? nullptr : grads + (size_t)i * len;
-    if (g)
-      for (int64_t q = 0; q < len; ++q) g[q] = 0.0;
-    lmls[i] = NAN;
-    bool values = false;
-    if (st[(size_t)i] != GOGP_OK) {
-      if (first_msg.empty()) first_msg = "batch: parameters must be positive and finite";
-    } else if (it.n == 0) {  // gp/gp.go:101-104, 343-347, 427-430
+    if (st[(size_t)i] == GOGP_OK && it.n == 0) {  // gp/gp.go:101-104, 343-347, 427-430
       lmls[i] = 0.0;
-      values = true;
+      if (g) std::fill(g, g + len, 0.0);
     } else {
-      const FactorResult fr = judge_scalars(h, row, false, false, it.n);
-      st[(size_t)i] = fr.rc;
-      if (fr.rc != GOGP_OK && first_msg.empty()) first_msg = fr.msg;
-      if (fr.rc != GOGP_ENOTPD) {
-        lmls[i] = fr.lml;
-        if (g) assemble_gradient(h, row + 16, it.P.dnoise, g);
-        values = true;
-      }
+      st[(size_t)i] = judge_row(h, h->bt_hout + (size_t)i * BATCH_ROW, false, it.n, it.P, st[(size_t)i],
+                                "batch: parameters must be positive and finite", &lmls[i], g, len, first_msg);
     }
+    const bool values = st[(size_t)i] == GOGP_OK || st[(size_t)i] == GOGP_ECOND;
     if (produce)
       for (long j = it.zoff; j < it.zoff + it.m; ++j) {
         mu[j] = values ? (it.n == 0 ? 0.0 : hmu[j]) : NAN;

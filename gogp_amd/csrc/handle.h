@@ -16,7 +16,49 @@ using gogp::GemmProfile;
 
 constexpr int REFINE_SLABS = 8;  // column slabs of the residual kernel (gram.hip: launch_residual)
 
-struct gogp_handle {
+// One evaluation's row of pinned staging (hscal; a candidate's row of cand_hscal; a batch pair's row of common.h: BATCH_ROW
+// doubles): the factorisation's scalars in [0 .. 7] (api.hip: judge_scalars), then these
+constexpr int HS_INFO = 8;    // first failing pivot + 1 (a long long; 0: positive definite)
+constexpr int HS_TRACE = 9;   // fp32 K^-1: tr(alpha alpha^T - K^-1) summed in fp64 from Y (NaN: not computed)
+constexpr int HS_GRAD = 16;   // the gradient's NACC slot sums
+static_assert(HS_GRAD + gogp::NACC == gogp::BATCH_ROW, "the pinned row is a batch row");
+
+// The device buffers of one evaluation: the handle's own, or an arena slot of a candidates call (api.hip: cand_layout)
+struct EvalBufs {
+  DevParams *devP = nullptr;
+  long long *info = nullptr;
+  double *scalars = nullptr;  // 8 doubles
+  double *gout = nullptr;
+  double *bufA = nullptr, *bufL = nullptr, *bufY = nullptr, *Dinv = nullptr;
+  double *z = nullptr, *w = nullptr, *alpha = nullptr;
+  double *gpart = nullptr;
+};
+
+// What an evaluation leaves in the handle; a candidates call saves it and puts it back
+struct EvalState {
+  bool factored = false, have_alpha = false, have_kinv = false;
+  bool observed = false, with_obs = false;
+  bool grad_valid = false;
+  bool trtri_done = false;  // Y = L^-T of the current factor is (being) computed
+  double lml = 0.0;
+  double cond_lb = 1.0;     // (max L_ii / min L_ii)^2 of the last factorisation
+  int64_t notpd = -1;
+};
+
+// What a captured candidates graph was recorded for: its size and the raw pointers it holds.  No option is part of it:
+// gogp_set_option and gogp_set_events drop the graph (api.hip: drop_cand_graph) before they change what is launched.
+struct CandGraphKey {
+  int k = 0;
+  int64_t n = 0, cap_npad = 0;
+  size_t stride = 0;
+  const void *arena = nullptr, *dX = nullptr, *dy = nullptr, *hostP = nullptr, *hscal = nullptr;
+  bool operator==(const CandGraphKey &o) const {
+    return k == o.k && n == o.n && cap_npad == o.cap_npad && stride == o.stride && arena == o.arena && dX == o.dX &&
+           dy == o.dy && hostP == o.hostP && hscal == o.hscal;
+  }
+};
+
+struct gogp_handle : EvalBufs, EvalState {
   gogp_desc desc;
   int device = 0;
   int ns = 0, nn = 0, P = 0, D = 0;
@@ -29,11 +71,8 @@ struct gogp_handle {
   bool ev() const { return nevents > 0; }
   int64_t n = 0, npad = 0;
   int nblk = 0;  // 128-blocks
-  // device buffers
+  // device buffers (and those of EvalBufs)
   double *dX = nullptr, *dy = nullptr;
-  double *bufA = nullptr, *bufL = nullptr, *bufY = nullptr, *Dinv = nullptr;
-  double *z = nullptr, *w = nullptr, *alpha = nullptr;
-  double *scalars = nullptr;  // 8 doubles
   double *dscr = nullptr;     // fp32 path: fp64 scratch of the diagonal-block kernel (3 x 256 x 256)
   double *D64 = nullptr;      // fp32 path: the diagonal blocks accumulated in fp64 (diagsyrk.hip), npad / 256 blocks of 256 x 256
   int64_t cap_d64 = 0;        // ... allocated for this npad
@@ -43,11 +82,8 @@ struct gogp_handle {
   size_t esz() const { return prec == 32 ? sizeof(float) : sizeof(double); }
   int refine_steps = 1;       // fp32 path: iterative-refinement steps of alpha against the fp64 K
   double *rw = nullptr, *rz = nullptr, *rd = nullptr, *rpart = nullptr;  // its scratch
-  long long *info = nullptr;
-  double *gpart = nullptr, *gout = nullptr;
-  DevParams *devP = nullptr;
   DevParams *hostP = nullptr;  // pinned
-  double *hscal = nullptr;     // pinned staging, NACC + 16 doubles
+  double *hscal = nullptr;     // pinned staging, one row (HS_*)
   int64_t cap_npad = 0;        // allocation size of the N-dependent buffers
   int64_t cap_y = 0;           // npad bufY was allocated for (it is allocated lazily)
   // produce workspace
@@ -64,7 +100,7 @@ struct gogp_handle {
   int cand_cap_k = 0;
   int64_t cand_cap_npad = 0;
   DevParams *cand_hostP = nullptr;  // pinned, cand_host_k entries
-  double *cand_hscal = nullptr;     // pinned, cand_host_k x (NACC + 16) doubles
+  double *cand_hscal = nullptr;     // pinned, cand_host_k rows (HS_*)
   int cand_host_k = 0;
   int batch_k = 1;              // > 1 only while a batched evaluation is being enqueued
   bool batch_mode = false;      // a batched evaluation is being enqueued (also with k = 1)
@@ -76,12 +112,7 @@ struct gogp_handle {
   std::string graph_note;
   hipGraphExec_t cand_graph = nullptr;
   hipStream_t sg = nullptr;     // capture / replay stream of that graph (created on first use)
-  struct {
-    int k = 0, superpanel = 0, kinv_fused = 0;
-    int64_t n = 0, cap_npad = 0;
-    size_t stride = 0;
-    const void *arena = nullptr, *dX = nullptr, *dy = nullptr, *hostP = nullptr, *hscal = nullptr;
-  } cand_graph_key, cand_seen_key;  // what the graph was captured for / what the last call asked for
+  CandGraphKey cand_graph_key, cand_seen_key;  // what the graph was captured for / what the last call asked for
   // batches of small GPs (gogp_batch_*): the members' data (row ranges of one uploaded X / y) and the staging of one
   // call -- the pairs' BatchItems + test points in (pinned -> device: one copy), result rows + mu + sigma out
   double *bt_X = nullptr, *bt_y = nullptr;  // bt_cap_rows x D (+ GOGP_MAX_NDIM slack), bt_cap_rows
@@ -142,22 +173,16 @@ struct gogp_handle {
   int kinv_fused = -1;          // ... and accumulates K^-1 = sum_P Y_P Y_P^T behind it, one rank-k update
                                // per super-panel of Y (0: one LAUUM launch over the finished Y in Gradient; -1: by size)
   bool kinv_pending = false;   // K^-1 is being accumulated on sk (wait for EV_KINV)
-  bool trtri_done = false;     // Y = L^-T of the current factor is (being) computed
-  bool trtri_pending = false;  // ... and still running on st/s2 (wait for EV_TRTRI)
+  bool trtri_pending = false;  // Y = L^-T (trtri_done) is still running on st/s2 (wait for EV_TRTRI)
   bool ydone_valid = false;    // EV_YDONE was recorded by the factorisation trtri_pending refers to
   bool alpha_pending = false;   // alpha was enqueued on sp; consumers on s wait for ev_alpha
-  // state
+  // state (and that of EvalState)
   std::vector<double> theta_s, theta_n;
-  bool have_data = false, factored = false, have_alpha = false, have_kinv = false;
-  bool observed = false, with_obs = false;
-  double lml = 0.0;
+  bool have_data = false;
   double yta = 0.0;      // y^T alpha of the last factorisation (fp32 path: of the refined alpha)
   int trace_fp64 = 1;    // fp32 path: tr(alpha alpha^T - K^-1) summed in fp64 from Y, scale component by its identity
-  double cond_lb = 1.0;  // (max L_ii / min L_ii)^2 of the last factorisation
   double cond_limit = 1e16;  // gonum's mat.ConditionTolerance
   std::vector<double> grad_cache;
-  bool grad_valid = false;
-  int64_t notpd = -1;
   std::string err;
   GemmProfile prof;
   // HIP-event timing of the O(N^2) kernels (gogp_profile_read_aux): class -> event pairs

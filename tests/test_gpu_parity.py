@@ -1449,6 +1449,89 @@ def test_candidates_one_not_positive_definite(gpmod):
     g.close()
 
 
+@pytest.mark.parametrize("n", [40, 600])
+def test_candidates_leave_the_handle_alone_after_refused_ones(gpmod, n):
+    """The candidates call works in an arena slot and puts the handle's own buffers and state back on the way out, also
+    when some candidates fail: a good one, a refused one (non-finite x: GOGP_EARG = 1) and one whose matrix is not
+    positive definite (GOGP_ENOTPD = 2).  Afterwards LML, Gradient (recomputed from the handle's own K^-1) and Produce
+    are bit for bit what they were -- on the one-launch form (n <= 128) and on the general sweep.  Inputs 100 apart and a
+    duplicated last one: at length 1 and noise 1e-13 K is the identity but for that pair, whose pivot is exactly 0."""
+    rng = np.random.default_rng(n)
+    X = 100.0 * np.arange(n, dtype=float)[:, None]
+    X[-1] = X[-2]
+    y = np.sin(X[:, 0] / 300.0) + 0.1 * rng.normal(size=n)
+    simil, noise = kernel.Scaled(kernel.Normal), kernel.UniformNoise
+    x_own, x_good, x_bad = np.log([120.0, 120.0, 0.3]), np.log([150.0, 150.0, 0.2]), np.log([1.0, 1.0, 1e-13])
+    x_refused = np.array([np.nan, 0.0, 0.0])
+    Z = 100.0 * rng.uniform(0, n, (7, 1))
+    g = gpmod.GP(1, simil, noise, X=X, Y=y)
+    with pytest.raises(gpmod.FactorizeError):
+        g.Observe(x_bad)
+    want_good = (g.Observe(x_good), g.Gradient())
+    g.Observe(x_own)
+    before = (g.LML(), g.Gradient(), *g.Produce(Z))
+    g.Observe(x_own)  # no cached gradient: Gradient() below reads the handle's own K^-1 and alpha again
+    for rep in range(3):  # streams, then captured into a graph, then replayed
+        lmls, grads, status = g.observe_gradient_candidates(np.stack([x_good, x_refused, x_bad]), strict=False)
+        assert list(status) == [0, 1, 2]
+        assert lmls[0] == want_good[0]
+        np.testing.assert_array_equal(grads[0], want_good[1])
+        assert np.isnan(lmls[1]) and np.isnan(lmls[2]) and not grads[1:].any()
+        if rep == 0:
+            after = (g.LML(), g.Gradient(), *g.Produce(Z))
+            assert after[0] == before[0]
+            for a, b in zip(after[1:], before[1:]):
+                np.testing.assert_array_equal(a, b)
+    after = (g.LML(), g.Gradient(), *g.Produce(Z))
+    assert after[0] == before[0]
+    for a, b in zip(after[1:], before[1:]):
+        np.testing.assert_array_equal(a, b)
+    g.close()
+
+
+@pytest.mark.parametrize("graph", [1, 2])
+def test_candidates_graph_follows_option_changes_between_replays(gpmod, graph):
+    """A captured candidates graph is dropped by every option change (gogp_set_option), so the key it is replayed
+    under holds no option.  Replayed, then super-panel width changed and changed back, then head_remaining 0 and 32
+    (default 16) with replays in between: every LML and gradient bit for bit those of a graph = 0 handle with the
+    same options."""
+    rng = np.random.default_rng(700 + graph)
+    n, D, k = 700, 3, 3
+    X, y = _data(rng, n, D)
+    simil, noise = kernel.Scaled(kernel.Normal), kernel.UniformNoise
+    base = np.log([1.0, 0.7, 0.2])
+    g, ref = gpmod.GP(D, simil, noise, X=X, Y=y), gpmod.GP(D, simil, noise, X=X, Y=y)
+    g.set_option("graph", graph)
+    ref.set_option("graph", 0)
+    calls = [0]
+
+    def replay(times):
+        for _ in range(times):
+            xs = base[None, :] + 0.02 * ((np.arange(k)[:, None] + calls[0]) % 5)
+            calls[0] += 1
+            lmls, grads, st = g.observe_gradient_candidates(xs)
+            want = ref.observe_gradient_candidates(xs)
+            assert list(st) == [0] * k
+            np.testing.assert_array_equal(lmls, want[0])
+            np.testing.assert_array_equal(grads, want[1])
+
+    def set_both(name, value):
+        g.set_option(name, value)
+        ref.set_option(name, value)
+
+    replay(3)  # seen, captured, replayed
+    set_both("superpanel", 3)
+    set_both("superpanel", 2)
+    replay(3)
+    set_both("head_remaining", 0)
+    replay(3)
+    set_both("head_remaining", 32)
+    replay(3)
+    assert not g.graph_info()[1]
+    g.close()
+    ref.close()
+
+
 @pytest.mark.perf
 def test_later_handles_as_fast_as_the_first(gpmod):
     """Stream sets are pooled (api.hip): a GP created after others were closed must run as
