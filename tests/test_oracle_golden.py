@@ -285,3 +285,49 @@ def test_oracle_constant_noise_with_parameter():
         xm[j] -= 1e-5
         fd = (o.Observe(xp) - o.Observe(xm)) / 2e-5
         assert abs(g[j] - fd) <= 1e-4 * max(1.0, abs(g[j])), (j, g[j], fd)
+
+
+# ---------------------------------------------------------------------------
+# the record behind tests/test_schedule_regimes_gpu.py (tests/golden/make_schedule_regimes.py)
+# ---------------------------------------------------------------------------
+def test_schedule_regimes_record_covers_the_case_table(golden_dir):
+    """schedule_regimes.json holds exactly the cases of tests/cases.py, every one with a usable tolerance record and
+    the condition the per-component gradient check rests on; the generator's inputs of every case reproduce the
+    recorded checksums, and the oracle on the smallest case the recorded LML and gradient; the thresholds the case
+    table straddles are still the ones the library's source states."""
+    import importlib.util
+    from cases import REGIME_CASES, REGIME_FAMILIES, REGIME_SIZES, REGIME_THRESHOLDS, regime_inputs
+    with open(os.path.join(golden_dir, "schedule_regimes.json")) as f:
+        cases = json.load(f)["cases"]
+    assert [(c["family"], c["n"]) for c in cases] == REGIME_CASES
+    spec = importlib.util.spec_from_file_location("make_schedule_regimes",
+                                                  os.path.join(golden_dir, "make_schedule_regimes.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    for c in cases:
+        assert c["n"] in REGIME_SIZES and c["n"] % 256 != 0
+        again = gen.checksums(c["family"], c["n"])
+        assert all(c[k] == v for k, v in again.items()), (c["family"], c["n"])
+        assert len(c["grad_disagreement"]) == len(c["grad"]) == len(c["log_theta"])
+        assert 0 < c["lml_disagreement"] < 1e-11 and 0 < min(c["grad_disagreement"])
+        assert max(c["grad_disagreement"]) < 1e-7
+        assert c["min_component_ratio"] >= gen.MIN_COMPONENT_RATIO and c["cond_diag"] < 1e3
+        assert 0 < c["rho_ref"] < 0.125   # min(1, 8 rho_ref) binds: the GPU factor is held to LAPACK's, not to 1
+    c = min(cases, key=lambda c: (c["n"], c["ndim"]))
+    D, simil, noise = REGIME_FAMILIES[c["family"]][:3]
+    X, y, _, x = regime_inputs(c["family"], c["n"])
+    o = FastOracle(D, simil, noise)
+    o.set_data(X, y)
+    assert abs(o.Observe(x) - c["lml"]) <= 1e-11 * abs(c["lml"])
+    np.testing.assert_allclose(o.Gradient(), c["grad"], rtol=1e-7, atol=0)
+    src = os.path.join(os.path.dirname(os.path.dirname(golden_dir)), "gogp_amd", "csrc")
+    with open(os.path.join(src, "api.hip")) as f:
+        api = f.read()
+    with open(os.path.join(src, "handle.h")) as f:
+        handle = f.read()
+    t = REGIME_THRESHOLDS
+    assert "int head_remaining = %d;" % (t["superpanel_head"] // 256) in handle
+    assert "h->npad <= %d ? 1 : 0" % t["chain_prio"] in api
+    assert "(h->npad <= %d || !eager) ? 2 : 0" % t["chain_split"] in api
+    assert "GRAPH_EXPLICIT_MAX_NPAD = %d;" % t["graph_explicit"] in api
+    assert "(npad <= %d || " % t["kinv_fused"] in api
