@@ -74,6 +74,11 @@ SYMBOLS = [
     ("gogp_batch_produce", ctypes.c_int,
      [_h, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), _dp, _i64, ctypes.POINTER(_i64), _dp, _dp, _dp, _dp,
       ctypes.POINTER(ctypes.c_int)]),
+    ("gogp_batch_observe_full_gradient", ctypes.c_int,
+     [_h, ctypes.c_int32, _dp, ctypes.POINTER(_i64), _dp, _dp, ctypes.POINTER(ctypes.c_int)]),
+    ("gogp_batch_produce_full", ctypes.c_int,
+     [_h, ctypes.c_int32, _dp, ctypes.POINTER(_i64), ctypes.POINTER(_i64), _dp, _dp, _dp, _dp,
+      ctypes.POINTER(ctypes.c_int)]),
     ("gogp_produce", ctypes.c_int, [_h, _dp, _i64, _dp, _dp]),
     ("gogp_n", _i64, [_h]),
     ("gogp_get_alpha", ctypes.c_int, [_h, _dp]),

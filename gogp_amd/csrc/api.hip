@@ -1934,20 +1934,29 @@ static int bt_reserve(gogp_handle *h, char **dev, char **host, size_t *cap, size
   return GOGP_OK;
 }
 
-// both entry points: produce == (zoff != NULL)
-static int batch_eval(gogp_handle *h, int32_t k, const int32_t *members, const double *x, int64_t len,
+// all four entry points: produce == (zoff != NULL); the full Observe form == (xoff != NULL): pair i is
+// x[xoff[i] .. xoff[i+1]) = [log theta | X_i | y_i] and carries its own observations, no batch data, no members
+static int batch_eval(gogp_handle *h, int32_t k, const int32_t *members, const double *x, int64_t len, const int64_t *xoff,
                       const int64_t *zoff, const double *Z, double *lmls, double *grads, double *mu, double *sigma,
                       int *status) {
-  const bool produce = zoff != nullptr;
+  const bool produce = zoff != nullptr, full = xoff != nullptr;
   if (!h) return GOGP_EARG;
   if (h->dist) return fail(h, GOGP_EARG, "batch: not supported on a sharded handle");
-  if (k < 0 || (k > 0 && (!members || !x || !lmls || (!produce && !grads))))
+  if (k < 0 || (k > 0 && ((!full && !members) || !x || !lmls || (!produce && !grads))))
     return fail(h, GOGP_EARG, "batch: bad arguments");
-  if (len != h->P) return fail(h, GOGP_EARG, "len(x)");
-  if (!h->bt_have) return fail(h, GOGP_ESTATE, "batch: no batch data (gogp_batch_set_data)");
-  const int64_t nmem = (int64_t)h->bt_n.size();
-  for (int32_t i = 0; i < k; ++i)
-    if (members[i] < 0 || members[i] >= nmem) return fail(h, GOGP_EARG, "batch: member index out of range");
+  int64_t nx = 0;  // full form: the doubles of the k vectors, x[xoff[0] .. xoff[k])
+  if (full) {
+    if (xoff[0] < 0) return fail(h, GOGP_EARG, "batch: xoff must be non-negative and non-decreasing");
+    for (int32_t i = 0; i < k; ++i)
+      if (xoff[i + 1] < xoff[i]) return fail(h, GOGP_EARG, "batch: xoff must be non-negative and non-decreasing");
+    nx = xoff[k] - xoff[0];
+  } else {
+    if (len != h->P) return fail(h, GOGP_EARG, "len(x)");
+    if (!h->bt_have) return fail(h, GOGP_ESTATE, "batch: no batch data (gogp_batch_set_data)");
+    const int64_t nmem = (int64_t)h->bt_n.size();
+    for (int32_t i = 0; i < k; ++i)
+      if (members[i] < 0 || members[i] >= nmem) return fail(h, GOGP_EARG, "batch: member index out of range");
+  }
   int64_t mz = 0;  // test points: rows 0 .. zoff[k] - 1 of Z
   if (produce) {
     if (zoff[0] < 0) return fail(h, GOGP_EARG, "batch_produce: zoff must be non-negative and non-decreasing");
@@ -1958,48 +1967,96 @@ static int batch_eval(gogp_handle *h, int32_t k, const int32_t *members, const d
   }
   if (k == 0) return GOGP_OK;
   HIPCHK(h, hipSetDevice(h->device));
+  // the pairs: parameters with the fill of the candidates call; full form: the length rules of gp/gp.go:386-400 per pair.
+  // A refused pair is launched with no observations (and theta = 1) and reported in its status.
+  const int64_t P = h->P, D = h->D;
+  std::vector<int> st((size_t)k, GOGP_OK);
+  std::vector<const char *> why((size_t)k, "batch: parameters must be positive and finite");
+  std::vector<int64_t> ns((size_t)k, 0);
+  int64_t out_doubles = 0;
+  if (full) {
+    for (int32_t i = 0; i < k; ++i) {
+      const int64_t li = xoff[i + 1] - xoff[i], rest = li - P;
+      const double *xi = x + xoff[i];
+      if (rest < 0 || rest % (D + 1) != 0) {
+        st[(size_t)i] = GOGP_EARG;
+        why[(size_t)i] = "len(x)";
+      } else if (rest / (D + 1) > GOGP_BATCH_MAX_N) {
+        st[(size_t)i] = GOGP_EARG;
+        why[(size_t)i] = "batch: a pair needs n <= GOGP_BATCH_MAX_N observations";
+      } else if (!std::all_of(xi + P, xi + li, [](double v) { return std::isfinite(v); })) {
+        st[(size_t)i] = GOGP_EARG;
+        why[(size_t)i] = "batch: non-finite observations";
+      } else {
+        ns[(size_t)i] = rest / (D + 1);
+      }
+      out_doubles += BATCH_ROW + (produce ? 0 : ns[(size_t)i] * (D + 1));
+    }
+  } else {
+    out_doubles = (int64_t)k * BATCH_ROW;
+  }
   const size_t items_bytes = align_up((size_t)k * sizeof(BatchItem), 256);
-  const size_t in_bytes = items_bytes + (size_t)mz * h->D * sizeof(double);
-  const size_t out_bytes = ((size_t)k * BATCH_ROW + 2 * (size_t)mz) * sizeof(double);
+  const size_t z_bytes = (size_t)mz * h->D * sizeof(double);
+  const size_t in_bytes = items_bytes + z_bytes + (size_t)nx * sizeof(double);
+  const size_t out_bytes = ((size_t)out_doubles + 2 * (size_t)mz) * sizeof(double);
   int rc = bt_reserve(h, &h->bt_din, &h->bt_hin, &h->bt_in_cap, in_bytes);
   if (rc == GOGP_OK) rc = bt_reserve(h, (char **)&h->bt_dout, (char **)&h->bt_hout, &h->bt_out_cap, out_bytes);
   if (rc != GOGP_OK) return rc;
-  // the pairs' parameters, with the fill of the candidates call
-  std::vector<int> st((size_t)k, GOGP_OK);
   BatchItem *items = reinterpret_cast<BatchItem *>(h->bt_hin);
+  const std::vector<double> log_one((size_t)std::max<int64_t>(P, 1), 0.0);
+  int64_t roff = 0;
   for (int32_t i = 0; i < k; ++i) {
     BatchItem &it = items[i];
-    st[(size_t)i] = fill_params_log(h, x + (size_t)i * len, it.P);
-    it.off = (long)h->bt_off[(size_t)members[i]];
-    it.n = (long)h->bt_n[(size_t)members[i]];
+    if (full) {
+      const bool refused = st[(size_t)i] != GOGP_OK;
+      const int fst = fill_params_log(h, refused ? log_one.data() : x + xoff[i], it.P);
+      if (!refused) st[(size_t)i] = fst;
+      it.off = (long)(xoff[i] - xoff[0] + P);
+      it.n = (long)ns[(size_t)i];
+    } else {
+      st[(size_t)i] = fill_params_log(h, x + (size_t)i * len, it.P);
+      it.off = (long)h->bt_off[(size_t)members[i]];
+      it.n = (long)h->bt_n[(size_t)members[i]];
+    }
     it.zoff = produce ? (long)zoff[i] : 0;
     it.m = produce ? (long)(zoff[i + 1] - zoff[i]) : 0;
+    it.roff = (long)roff;
+    roff += BATCH_ROW + ((full && !produce) ? it.n * (D + 1) : 0);
   }
-  if (mz > 0) memcpy(h->bt_hin + items_bytes, Z, (size_t)mz * h->D * sizeof(double));
+  if (mz > 0) memcpy(h->bt_hin + items_bytes, Z, z_bytes);
+  if (nx > 0) memcpy(h->bt_hin + items_bytes + z_bytes, x + xoff[0], (size_t)nx * sizeof(double));
   hipStream_t s = h->s;
-  double *drows = h->bt_dout, *dmu = drows + (size_t)k * BATCH_ROW, *dsig = dmu + mz;
+  double *drows = h->bt_dout, *dmu = drows + out_doubles, *dsig = dmu + mz;
+  const double *dZ = reinterpret_cast<const double *>(h->bt_din + items_bytes);
   HIPCHK(h, hipMemcpyAsync(h->bt_din, h->bt_hin, in_bytes, hipMemcpyHostToDevice, s));
-  launch_batch_eval(s, reinterpret_cast<const BatchItem *>(h->bt_din), k, h->bt_X, h->bt_y,
-                    reinterpret_cast<const double *>(h->bt_din + items_bytes), drows, dmu, dsig, h->ard_dims, produce,
-                    h->ev());
+  if (full)
+    launch_batch_eval_full(s, reinterpret_cast<const BatchItem *>(h->bt_din), k,
+                           reinterpret_cast<const double *>(h->bt_din + items_bytes + z_bytes), dZ, drows, dmu, dsig,
+                           h->ard_dims, produce, h->ev());
+  else
+    launch_batch_eval(s, reinterpret_cast<const BatchItem *>(h->bt_din), k, h->bt_X, h->bt_y, dZ, drows, dmu, dsig,
+                      h->ard_dims, produce, h->ev());
   HIPCHK(h, hipMemcpyAsync(h->bt_hout, h->bt_dout, out_bytes, hipMemcpyDeviceToHost, s));
   HIPCHK(h, hipStreamSynchronize(s));
   HIPCHK(h, hipGetLastError());
   // every pair judged as gogp_observe would judge a handle holding its member's data
-  const double *hmu = h->bt_hout + (size_t)k * BATCH_ROW, *hsig = hmu + mz;
+  const double *hmu = h->bt_hout + out_doubles, *hsig = hmu + mz;
   int first = GOGP_OK;
   std::string first_msg;
   for (int32_t i = 0; i < k; ++i) {
     const BatchItem &it = items[i];
-    double *g = produce ? nullptr : grads + (size_t)i * len;
+    const int64_t gl = full ? xoff[i + 1] - xoff[i] : len;
+    double *g = produce ? nullptr : (full ? grads + xoff[i] : grads + (size_t)i * len);
+    double *row = h->bt_hout + it.roff;
     if (st[(size_t)i] == GOGP_OK && it.n == 0) {  // gp/gp.go:101-104, 343-347, 427-430
       lmls[i] = 0.0;
-      if (g) std::fill(g, g + len, 0.0);
+      if (g) std::fill(g, g + gl, 0.0);
     } else {
-      st[(size_t)i] = judge_row(h, h->bt_hout + (size_t)i * BATCH_ROW, false, it.n, it.P, st[(size_t)i],
-                                "batch: parameters must be positive and finite", &lmls[i], g, len, first_msg);
+      st[(size_t)i] = judge_row(h, row, false, it.n, it.P, st[(size_t)i], why[(size_t)i], &lmls[i], g, gl, first_msg);
     }
     const bool values = st[(size_t)i] == GOGP_OK || st[(size_t)i] == GOGP_ECOND;
+    // gp/gp.go:118-129 (inputs) and :488-493 (outputs: -alpha), behind the slot sums of the pair's block
+    if (full && g && values && it.n > 0) std::copy(row + BATCH_ROW, row + BATCH_ROW + it.n * (D + 1), g + P);
     if (produce)
       for (long j = it.zoff; j < it.zoff + it.m; ++j) {
         mu[j] = values ? (it.n == 0 ? 0.0 : hmu[j]) : NAN;
@@ -2014,14 +2071,29 @@ static int batch_eval(gogp_handle *h, int32_t k, const int32_t *members, const d
 
 extern "C" int gogp_batch_observe_gradient(gogp_handle *h, int32_t k, const int32_t *members, const double *x,
                                            int64_t len, double *lmls, double *grads, int *status) {
-  return batch_eval(h, k, members, x, len, nullptr, nullptr, lmls, grads, nullptr, nullptr, status);
+  return batch_eval(h, k, members, x, len, nullptr, nullptr, nullptr, lmls, grads, nullptr, nullptr, status);
 }
 
 extern "C" int gogp_batch_produce(gogp_handle *h, int32_t k, const int32_t *members, const double *x, int64_t len,
                                   const int64_t *zoff, const double *Z, double *lmls, double *mu, double *sigma,
                                   int *status) {
   if (!zoff) return fail(h, GOGP_EARG, "batch_produce: zoff is NULL");
-  return batch_eval(h, k, members, x, len, zoff, Z, lmls, nullptr, mu, sigma, status);
+  return batch_eval(h, k, members, x, len, nullptr, zoff, Z, lmls, nullptr, mu, sigma, status);
+}
+
+// The full Observe form of the two (gp/gp.go:386-400: X and y re-sliced out of x; :118-129, 488-493: the gradient by the
+// inputs and the outputs): the forecast windows of the case studies that infer their inputs or outputs
+// (tutorial/anynoise/main.go:47, tutorial/warpedtime/main.go:59: OPTINP) in one launch.
+extern "C" int gogp_batch_observe_full_gradient(gogp_handle *h, int32_t k, const double *x, const int64_t *xoff,
+                                                double *lmls, double *grads, int *status) {
+  if (h && !xoff) return fail(h, GOGP_EARG, "batch: xoff is NULL");
+  return batch_eval(h, k, nullptr, x, 0, xoff, nullptr, nullptr, lmls, grads, nullptr, nullptr, status);
+}
+
+extern "C" int gogp_batch_produce_full(gogp_handle *h, int32_t k, const double *x, const int64_t *xoff, const int64_t *zoff,
+                                       const double *Z, double *lmls, double *mu, double *sigma, int *status) {
+  if (h && (!xoff || !zoff)) return fail(h, GOGP_EARG, "batch_produce: xoff or zoff is NULL");
+  return batch_eval(h, k, nullptr, x, 0, xoff, zoff, Z, lmls, nullptr, mu, sigma, status);
 }
 
 extern "C" int gogp_graph_info(const gogp_handle *h, int64_t *nodes, int *refused) {

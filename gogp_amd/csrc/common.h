@@ -258,14 +258,21 @@ void launch_tiny_eval(hipStream_t s, const DevParams *P, const double *X, const 
 // diag256.hip: batches of small GPs (gogp_batch_*), one workgroup per (member, theta) pair.  Pair b evaluates rows
 // off .. off + n - 1 (n <= 128) of the batch data at P and writes row b of `rows` (BATCH_ROW doubles: the scalars of
 // judge_scalars in [0..15], the NACC gradient slot sums from [16] on) or, produce, mu / sigma of Z's rows zoff .. zoff + m - 1
+// Full Observe form (gogp_batch_*_full): the pair's observations ride in its own parameter vector.  X is the upload of
+// the k vectors; the pair's inputs (n x D) start at double `off` of it and its outputs follow them; its results go to
+// the block at double `roff` of `rows`: the BATCH_ROW doubles above, then (Observe) the n * D input gradients and the
+// n output gradients -alpha.
 struct BatchItem {
   DevParams P;
   long off, n;
   long zoff, m;
+  long roff;  // full form only
 };
 constexpr int BATCH_ROW = NACC + 16;
 void launch_batch_eval(hipStream_t s, const BatchItem *items, int k, const double *X, const double *y, const double *Z,
                        double *rows, double *mu, double *sigma, int ard_dims, bool produce, bool ev);
+void launch_batch_eval_full(hipStream_t s, const BatchItem *items, int k, const double *x, const double *Z, double *rows,
+                            double *mu, double *sigma, int ard_dims, bool produce, bool ev);
 // dense inverses of nblk consecutive 256 x 256 diagonal blocks of a finished factor (block b at L + b * 256 * (ld + 1))
 void launch_dinv256_blocks(hipStream_t s, const double *L, int64_t ld, double *Dinv, int nblk);
 void launch_diag256_inv_only_ld512(hipStream_t s, const double *L, int64_t ld, double *Dinv);  // Dinv: ld 512

@@ -805,7 +805,15 @@ __global__ __launch_bounds__(NT) void GOGP_EVN(tiny_eval_kernel)(const DevParams
 //             passes of ARD_D dimensions, as grad.hip does
 //   PRODUCE:  mu[j], sigma[j] for the pair's test points j = zoff .. zoff + m - 1 of Z (gp/gp.go:269-278, 322-357):
 //             k* into LDS, v = X k*, mu = k*^T alpha, sigma = sqrt(k(z, z) - v^T v), unclamped
-template <int ARD_D, bool PRODUCE>
+// FULL (gogp_batch_observe_full_gradient / gogp_batch_produce_full): the full Observe form (gp/gp.go:386-397).  The
+// pair's observations ride in its own parameter vector: X is the upload of the k vectors, the pair's inputs start at
+// double it.off of it, its outputs follow them, and its results go to the block at double it.roff of `rows`.  Everything
+// above is the same code on those data; !PRODUCE adds, behind the slot sums,
+//   row[BATCH_ROW + i * D + d]: dLML/dx_{i,d} = sum_{j != i} W_ij dk(x_i, x_j)/dx_{i,d} over the FULL symmetric W
+//                               (gp/gp.go:118-129; grad.hip: xgrad_kernel), W mirrored in place in S; four threads per
+//                               row, columns p, p + 4, ..., summed in a fixed order; passes of 16 dimensions
+//   row[BATCH_ROW + n * D + i]: dLML/dy_i = -alpha_i (gp/gp.go:488-493)
+template <int ARD_D, bool PRODUCE, bool FULL = false>
 __global__ __launch_bounds__(NT) void GOGP_EVN(batch_eval_kernel)(const BatchItem *__restrict__ items,
                                                           const double *__restrict__ X, const double *__restrict__ y,
                                                           const double *__restrict__ Z, double *__restrict__ rows,
@@ -815,9 +823,14 @@ __global__ __launch_bounds__(NT) void GOGP_EVN(batch_eval_kernel)(const BatchIte
   const DevParams &P = it.P;
   const int D = P.ndim;
   const long n = it.n;
-  X += it.off * D;
-  y += it.off;
-  double *row = rows + (long)blockIdx.x * BATCH_ROW;
+  if (FULL) {
+    X += it.off;
+    y = X + n * D;
+  } else {
+    X += it.off * D;
+    y += it.off;
+  }
+  double *row = FULL ? rows + it.roff : rows + (long)blockIdx.x * BATCH_ROW;
   __shared__ __attribute__((aligned(16))) double S[128 * SLD];
   __shared__ __attribute__((aligned(16))) double G[GSIZE];
   __shared__ double rinv_s[8 * 16];
@@ -1040,6 +1053,42 @@ __global__ __launch_bounds__(NT) void GOGP_EVN(batch_eval_kernel)(const BatchIte
     if (ARD_D == 0 || ard0 + ARD_D >= ard_dims) break;
     __syncthreads();  // red is rewritten by the next pass
   }
+  if (FULL) {
+    // ---- the input pass.  Every thread is past the last pass's barrier: S is read no more, so the upper triangle takes
+    // the transpose of the lower one (consecutive lanes read consecutive doubles of a row and write doubles SLD apart:
+    // 260 dwords = 4 banks mod 32, so the 16 lanes of a store group land on 8 bank pairs, 2-way -- 16 K elements, once)
+    for (int idx = tid; idx < 128 * 128; idx += NT) {
+      const int i = idx >> 7, j = idx & 127;
+      if (j < i) S[j * SLD + i] = S[i * SLD + j];
+    }
+    __syncthreads();
+    const int i = tid >> 2, p = tid & 3;
+    const double *xi = X + (long)i * D;  // (read only under i < n)
+    double *gx = row + BATCH_ROW;
+    for (int d0 = 0; d0 < D; d0 += 16) {
+      double acc[16];
+#pragma unroll
+      for (int q = 0; q < 16; ++q) acc[q] = 0.0;
+      if (i < n) {
+        for (int j = p; j < n; j += 4) {
+          if (j == i) continue;
+          double W = S[i * SLD + j];
+          if (GOGP_EV) W *= event_discount(P, em[i], em[j]);
+          const double *xj = X + (long)j * D;
+          simil_xgrad_accum<16>(
+              P, [&](int d) { return xi[d]; }, [&](int d) { return xj[d]; }, W, acc, d0);
+        }
+      }
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {
+        double v = acc[q];
+        v += __shfl_xor(v, 1);
+        v += __shfl_xor(v, 2);
+        if (p == 0 && i < n && d0 + q < D) gx[(long)i * D + d0 + q] = v;
+      }
+    }
+    if (tid < n) gx[n * D + tid] = -ys[tid];
+  }
 }
 
 #if !GOGP_EV  // second pass (the product library only): tiny_eval_kernel again, with event discounts, as tiny_eval_kernel_ev
@@ -1081,6 +1130,24 @@ void launch_batch_eval(hipStream_t s, const BatchItem *items, int k, const doubl
     GOGP_KLAUNCH((batch_eval_kernel<16, false>), grid, blk, 0, s, items, X, y, Z, rows, mu, sigma, ard_dims);
   } else {
     GOGP_KLAUNCH((batch_eval_kernel<0, false>), grid, blk, 0, s, items, X, y, Z, rows, mu, sigma, 0);
+  }
+}
+
+// the full Observe form: the same instances with the pairs' data taken from their own vectors (x: the upload of them)
+void launch_batch_eval_full(hipStream_t s, const BatchItem *items, int k, const double *x, const double *Z, double *rows,
+                            double *mu, double *sigma, int ard_dims, bool produce, bool ev) {
+  const dim3 grid((unsigned)k), blk(NT);
+  if (produce) {
+    if (ev)
+      GOGP_KLAUNCH((batch_eval_kernel_ev<0, true, true>), grid, blk, 0, s, items, x, x, Z, rows, mu, sigma, 0);
+    else
+      GOGP_KLAUNCH((batch_eval_kernel<0, true, true>), grid, blk, 0, s, items, x, x, Z, rows, mu, sigma, 0);
+  } else if (ev) {
+    GOGP_KLAUNCH((batch_eval_kernel_ev<0, false, true>), grid, blk, 0, s, items, x, x, Z, rows, mu, sigma, 0);
+  } else if (ard_dims > 0) {
+    GOGP_KLAUNCH((batch_eval_kernel<16, false, true>), grid, blk, 0, s, items, x, x, Z, rows, mu, sigma, ard_dims);
+  } else {
+    GOGP_KLAUNCH((batch_eval_kernel<0, false, true>), grid, blk, 0, s, items, x, x, Z, rows, mu, sigma, 0);
   }
 }
 

@@ -390,6 +390,51 @@ class GP:
         return (lmls, [mu[zoff[i]:zoff[i + 1]] for i in range(k)], [sigma[zoff[i]:zoff[i + 1]] for i in range(k)],
                 status)
 
+    # ---- the full Observe form of the batch: every pair carries its observations in its own vector -------------------
+    def _batch_full_args(self, xs):
+        xl = [_arr(x).reshape(-1) for x in xs]
+        k = len(xl)
+        xoff = np.zeros(k + 1, dtype=np.int64)
+        xoff[1:] = np.cumsum([v.size for v in xl])
+        x = np.ascontiguousarray(np.concatenate(xl)) if k else np.zeros(0)
+        if x.size == 0:
+            x = np.zeros(1)  # (never read: a valid pointer for the call)
+        return x, xoff, k, np.full(k, -1, dtype=np.intc)
+
+    def batch_observe_full_gradient(self, xs):
+        """LML and gradient of k GPs that carry their observations in their own vectors, xs[i] = [log theta | X_i | y_i]
+        (lengths differ; n_i <= GOGP_BATCH_MAX_N), in ONE launch (gogp_batch_observe_full_gradient): what
+        Observe(xs[i]) + Gradient() on a GP of its own would return.  Returns (lmls[k], [grad_i], status[k]); a pair
+        whose matrix is not positive definite has status GOGP_ENOTPD, lml NaN and a zero gradient; a bad length,
+        n_i > GOGP_BATCH_MAX_N or non-finite entries GOGP_EARG.  The GP's own data and state are not touched."""
+        x, xoff, k, st = self._batch_full_args(xs)
+        lmls, grads = np.zeros(k), np.zeros(x.size)
+        rc = _lib.lib().gogp_batch_observe_full_gradient(self._h, k, _dp(x),
+                                                         xoff.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), _dp(lmls),
+                                                         _dp(grads), st.ctypes.data_as(ctypes.POINTER(ctypes.c_int)))
+        return lmls, [grads[xoff[i]:xoff[i + 1]] for i in range(k)], self._batch_status(rc, st)
+
+    def batch_produce_full(self, xs, Zs):
+        """LML at xs[i] (full Observe form) and the forecasts at the test points Zs[i] in ONE launch
+        (gogp_batch_produce_full): what Observe(xs[i]) + Produce(Zs[i]) on a GP of its own would give.  Returns
+        (lmls[k], [mu_i], [sigma_i], status[k]); NaN where the status is GOGP_ENOTPD or GOGP_EARG."""
+        x, xoff, k, st = self._batch_full_args(xs)
+        Zl = [_arr(z).reshape(-1, self.NDim) for z in Zs]
+        if len(Zl) != k:
+            raise ValueError("len(Zs) != len(xs)")
+        zoff = np.zeros(k + 1, dtype=np.int64)
+        zoff[1:] = np.cumsum([len(z) for z in Zl])
+        Z = np.ascontiguousarray(np.concatenate(Zl, axis=0)) if k else np.zeros((0, self.NDim))
+        m = int(zoff[-1])
+        lmls, mu, sigma = np.zeros(k), np.zeros(m), np.zeros(m)
+        p64 = ctypes.POINTER(ctypes.c_int64)
+        rc = _lib.lib().gogp_batch_produce_full(self._h, k, _dp(x), xoff.ctypes.data_as(p64), zoff.ctypes.data_as(p64),
+                                                _dp(Z), _dp(lmls), _dp(mu), _dp(sigma),
+                                                st.ctypes.data_as(ctypes.POINTER(ctypes.c_int)))
+        status = self._batch_status(rc, st)
+        return (lmls, [mu[zoff[i]:zoff[i + 1]] for i in range(k)], [sigma[zoff[i]:zoff[i + 1]] for i in range(k)],
+                status)
+
     def profile_read_launches(self):
         """Per launch of the tile kernel since profile_enable(True): arrays (start ms, end ms, flops, tag);
         tag = mode * 1e8 + (K / 16) * 1e5 + tiles.  Call before profile_read (which resets)."""

@@ -267,8 +267,12 @@ def lbfgs_lockstep(evaluate, x0s, major_iterations: int = 1000, gradient_thresho
     (inf where it is not usable) and g its gradient (negated as well; None only where f is not finite).  With
     GP.batch_observe_gradient behind it, one round is one launch.  The loop of ``lbfgs_multistart`` with a separate
     objective per run: each run takes exactly the path ``lbfgs`` takes alone on the same values.  Returns the k
-    Results; a run whose start is not feasible gets None (``lbfgs`` raises ValueError(INFEASIBLE_START) there)."""
-    x0s = np.atleast_2d(np.asarray(x0s, dtype=float))
+    Results; a run whose start is not feasible gets None (``lbfgs`` raises ValueError(INFEASIBLE_START) there).
+    The starting points may differ in length (windows that carry their own inputs and outputs in x, the full
+    Observe form): then ``xs`` is a list of vectors instead of a 2-D array."""
+    ragged = len({np.size(x0) for x0 in x0s}) > 1
+    x0s = [np.asarray(x0, dtype=float).reshape(-1) for x0 in x0s] if ragged else \
+        np.atleast_2d(np.asarray(x0s, dtype=float))
     gens = [_lbfgs_steps(x0, major_iterations, gradient_threshold, history_size, max_step_log, 1, None)
             for x0 in x0s]
     results: List[Optional[Result]] = [None] * len(gens)
@@ -282,7 +286,7 @@ def lbfgs_lockstep(evaluate, x0s, major_iterations: int = 1000, gradient_thresho
             if req[0] == "eval":
                 last[i] = req[1][0]
             xs.append(last[i])
-        ans = evaluate(idx, np.array(xs))
+        ans = evaluate(idx, xs if ragged else np.array(xs))
         for j, i in enumerate(idx):
             try:
                 pending[i] = gens[i].send([ans[j]] if pending[i][0] == "eval" else ans[j][1])

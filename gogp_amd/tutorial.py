@@ -44,6 +44,11 @@ SEED: Optional[int] = None  # not in the reference: fixes the starting-point jit
 #: gp.Model around it, and a GP with those methods; otherwise it changes nothing.  Same starting points (the
 #: jitter is drawn in window order), same rows in the same order and format, and ``gp`` is left where the
 #: sequential harness leaves it (the last window's data, observed at its final x).
+#: With OPTINP on, the windows carry their inputs and outputs in x and go through the full-form batch
+#: (GP.batch_observe_full_gradient / batch_produce_full).  ``m`` is then the GP itself or a model with a
+#: ``window_objective()`` method (priors.AnyNoiseModel, priors.WarpedTimeModel): a fresh host-side object per window
+#: that adds the priors -- which memoise at the window's start vector -- and applies the model's edit of the
+#: gradient.  A model without it runs the sequential loop.
 BATCH = False
 BATCH_MAX_N = 128  # include/gogp_hip.h: GOGP_BATCH_MAX_N
 
@@ -96,7 +101,7 @@ def Evaluate(gp, m, theta, rdr, wtr, log=sys.stderr) -> None:
     print("Forecasting...", file=log)
     priors = _batch_priors(gp, m)
     if priors is not None:
-        _forecast_batched(gp, m, priors[0], theta, X, Y, meany, stdy, rng, wtr, log)
+        _forecast_batched(gp, m, priors[0], theta, X, Y, meany, stdy, rng, wtr, log, full=OPTINP)
     else:
         for end in range(len(X)):
             # Randomize the initial values of hyperparameters (:119-121)
@@ -173,8 +178,17 @@ def _forecast_window(gp, m, theta, X, Y, end, jitter, meany, stdy, wtr, log) -> 
 
 
 def _batch_priors(gp, m):
-    """(priors,) when BATCH applies (priors None: ``m`` is the GP itself), else None."""
-    if not (BATCH and ALG == "lbfgs" and not OPTINP):
+    """(priors,) when BATCH applies (priors None: ``m`` is the GP itself), else None.  With OPTINP: (factory,), the
+    model's ``window_objective`` (None: ``m`` is the GP itself)."""
+    if not (BATCH and ALG == "lbfgs"):
+        return None
+    if OPTINP:
+        if not all(hasattr(gp, a) for a in ("batch_observe_full_gradient", "batch_produce_full")):
+            return None
+        if m is gp:
+            return (None,)
+        if getattr(m, "GP", None) is gp and callable(getattr(m, "window_objective", None)):
+            return (m.window_objective,)
         return None
     if not all(hasattr(gp, a) for a in ("set_batch", "batch_observe_gradient", "batch_produce")):
         return None
@@ -185,46 +199,59 @@ def _batch_priors(gp, m):
     return None
 
 
-def _forecast_batched(gp, m, priors, theta, X, Y, meany, stdy, rng, wtr, log) -> None:
+def _forecast_batched(gp, m, priors, theta, X, Y, meany, stdy, rng, wtr, log, full=False) -> None:
     """The windows of _forecast_window as batches of small GPs (BATCH): every window's starting point first (the
     jitter in window order: the starts of the sequential harness), the initial LML of every window in one call,
     the L-BFGS runs of the windows in lock-step (one call per round), then the final LML and the one-point forecast
     of every window in one call.  Windows of more than BATCH_MAX_N rows, and a window whose initial LML cannot be
-    formed (the sequential harness raises there), take the sequential code at their turn."""
+    formed (the sequential harness raises there), take the sequential code at their turn.
+    ``full`` (OPTINP): every window carries its inputs and outputs in x (:100-110), the vectors differ in length and go
+    through the full-form batch; ``priors`` is then the model's window_objective, called once per window."""
     ntheta = len(theta)
     jitters, starts = [], []
-    for _ in range(len(X)):
+    for end in range(len(X)):
         jitters.append(0.1 * rng.standard_normal(ntheta))  # (:119-121)
-        x = theta.copy()
+        x = np.concatenate([theta, X[:end].reshape(-1), Y[:end]]) if full else theta.copy()
         x[:ntheta] += jitters[-1]
         starts.append(x)
     wins = [end for end in range(len(X)) if end <= BATCH_MAX_N]  # window end holds n = end rows
     member = {end: i for i, end in enumerate(wins)}
+    objective = {e: priors() for e in wins} if full and priors is not None else {}
 
-    def model_value(x, lml, grad):  # gp/model.go:17-28, as gp.Model adds the priors
+    def model_value(x, lml, grad, e=None):  # gp/model.go:17-28, as gp.Model adds the priors
         if priors is None:
             return lml, grad
+        if full:  # ... and as the model around it edits the gradient
+            return objective[e].value_grad(x, lml, grad)
         v = lml + priors.Observe(x)
         pg = np.asarray(priors.Gradient(), dtype=float)
         g = np.array(grad, dtype=float)
         g[:len(pg)] += pg
         return v, g
 
+    def observe_gradient(xs, ends):
+        if full:
+            return gp.batch_observe_full_gradient(list(xs))
+        return gp.batch_observe_gradient(xs, members=[member[e] for e in ends])
+
     done = {}  # end -> (lml0, x, lml, mu, sigma, note)
     if wins:
-        gp.set_batch(X, Y, [(0, end) for end in wins])
-        l0, g0, s0 = gp.batch_observe_gradient(np.array([starts[e] for e in wins]))
-        lml0 = {e: model_value(starts[e], float(l0[i]), g0[i])[0] for i, e in enumerate(wins) if s0[i] == 0}
+        if full:
+            l0, g0, s0 = observe_gradient([starts[e] for e in wins], wins)
+        else:
+            gp.set_batch(X, Y, [(0, end) for end in wins])
+            l0, g0, s0 = gp.batch_observe_gradient(np.array([starts[e] for e in wins]))
+        lml0 = {e: model_value(starts[e], float(l0[i]), g0[i], e)[0] for i, e in enumerate(wins) if s0[i] == 0}
         runs = [e for e in wins if e in lml0 and e > MINOPT]
 
         def evaluate(idx, xs):
-            lm, gr, st = gp.batch_observe_gradient(xs, members=[member[runs[i]] for i in idx])
+            lm, gr, st = observe_gradient(xs, [runs[i] for i in idx])
             out = []
             for j in range(len(xs)):
                 if st[j] != 0 or not np.isfinite(lm[j]):
                     out.append((np.inf, None))
                     continue
-                v, g = model_value(xs[j], float(lm[j]), gr[j])
+                v, g = model_value(xs[j], float(lm[j]), gr[j], runs[idx[j]])
                 out.append((-v, -g) if np.isfinite(v) else (np.inf, None))
             return out
 
@@ -240,10 +267,18 @@ def _forecast_batched(gp, m, priors, theta, X, Y, meany, stdy, rng, wtr, log) ->
             xfin[e] = r.x
         fin = sorted(lml0)
         if fin:
-            lf, mus, sigmas, sf = gp.batch_produce(np.array([xfin[e] for e in fin]), [X[e:e + 1] for e in fin],
-                                                   members=[member[e] for e in fin])
+            if full:
+                lf, mus, sigmas, sf = gp.batch_produce_full([xfin[e] for e in fin], [X[e:e + 1] for e in fin])
+            else:
+                lf, mus, sigmas, sf = gp.batch_produce(np.array([xfin[e] for e in fin]), [X[e:e + 1] for e in fin],
+                                                       members=[member[e] for e in fin])
             for i, e in enumerate(fin):
-                lml = float(lf[i]) if priors is None else float(lf[i]) + priors.Observe(xfin[e])
+                if priors is None:
+                    lml = float(lf[i])
+                elif full:
+                    lml = objective[e].value(xfin[e], float(lf[i]))
+                else:
+                    lml = float(lf[i]) + priors.Observe(xfin[e])
                 mu, sigma = mus[i][0], sigmas[i][0]
                 if sf[i] != 0:
                     mu = sigma = float("nan")
@@ -262,6 +297,7 @@ def _forecast_batched(gp, m, priors, theta, X, Y, meany, stdy, rng, wtr, log) ->
     # the GP as the sequential harness leaves it: the last window's data, observed at its final x
     last = len(X) - 1
     if last in done:
-        gp.X, gp.Y = X[:last], Y[:last]
+        if not full:  # (full: Observe re-slices X and Y out of x)
+            gp.X, gp.Y = X[:last], Y[:last]
         if done[last][6] == 0:
             m.Observe(done[last][1])

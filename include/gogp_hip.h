@@ -238,7 +238,8 @@ int gogp_graph_info(const gogp_handle *h, int64_t *nodes, int *refused);
  * of the results).  Counterpart: the reference's forecast harness, which fits the hyperparameters separately on every
  * prefix X[:end] of the data (tutorial/tutorial.go:88-197), and any set of short series fitted with one kernel.
  * The batch is fp64 whatever the options "precision" and "gradient_precision" are; "cond_limit_log10" and the
- * handle's event discounts (gogp_set_events) apply.  Sharded handle: GOGP_EARG.  Hyperparameters-only form. */
+ * handle's event discounts (gogp_set_events) apply.  Sharded handle: GOGP_EARG.  Hyperparameters-only form (the full
+ * form: gogp_batch_observe_full_gradient / gogp_batch_produce_full below). */
 #define GOGP_BATCH_MAX_N 128
 /* Members are row ranges [offset[b], offset[b]+n[b]) of one uploaded X (rows x ndim) / y; ranges may
    overlap (forecast windows are prefixes of the same data).  n[b] <= GOGP_BATCH_MAX_N (else GOGP_EARG).
@@ -260,6 +261,28 @@ int gogp_batch_observe_gradient(gogp_handle *h, int32_t k, const int32_t *member
 int gogp_batch_produce(gogp_handle *h, int32_t k, const int32_t *members, const double *x, int64_t len,
                        const int64_t *zoff /* k+1 */, const double *Z, double *lmls, double *mu,
                        double *sigma, int *status);
+
+/* The full Observe form of the batch (gp/gp.go:366-369, 386-400): every pair carries its own observations in its
+ * parameter vector, x_i = [log theta | X_i (n_i x ndim) | y_i (n_i)] = x[xoff[i] .. xoff[i+1]), n_i = (len_i - P) /
+ * (ndim + 1) <= GOGP_BATCH_MAX_N; the vectors differ in length.  Counterpart: the forecast windows of the case studies
+ * that infer their inputs or outputs (OPTINP: tutorial/anynoise/main.go:47, tutorial/warpedtime/main.go:59;
+ * tutorial/tutorial.go:100-110), one gogp_observe_full + gogp_gradient each in the reference's order of work.  No batch
+ * data is needed or touched, nor the handle's own data, factorisation and candidates arena.  fp64 whatever "precision"
+ * and "gradient_precision" are.  Sharded handle: GOGP_EARG.  Still one copy in, ONE launch, one copy out. */
+/* lmls[i] and grads[xoff[i] .. xoff[i+1]) (laid out as x: hyperparameters, dLML/dX_i of gp/gp.go:118-129, dLML/dy_i =
+   -alpha of :488-493) as gogp_observe_full + gogp_gradient on a handle of its own would return them; the hyperparameter
+   part is bit for bit that of gogp_batch_observe_gradient on the same data.  Per pair, with the others still evaluated:
+   len_i < P, a remainder (the reference: panic("len(x)"), gp/gp.go:398-400), n_i > GOGP_BATCH_MAX_N, non-finite
+   parameters or observations: GOGP_EARG (LML NaN, gradient zeros); GOGP_ENOTPD: LML NaN, gradient zeros; GOGP_ECOND:
+   values returned; n_i = 0: LML 0, zeros.  A pair's results do not depend on the other pairs of the call (bit for bit).
+   xoff (k + 1 entries) is non-negative and non-decreasing.  Returns the first non-zero status; status may be NULL. */
+int gogp_batch_observe_full_gradient(gogp_handle *h, int32_t k, const double *x, const int64_t *xoff /* k+1 */,
+                                     double *lmls /* k */, double *grads /* xoff[k], laid out as x */, int *status);
+/* The same pairs with test points as gogp_batch_produce: LML at x_i and mu / sigma as gogp_observe_full + gogp_produce
+   would give (gp/gp.go:269-278, 322-357); n_i = 0: mu = 0, sigma = sqrt(prior).  ENOTPD / EARG: lml, mu, sigma NaN. */
+int gogp_batch_produce_full(gogp_handle *h, int32_t k, const double *x, const int64_t *xoff /* k+1 */,
+                            const int64_t *zoff /* k+1 */, const double *Z, double *lmls, double *mu, double *sigma,
+                            int *status);
 
 /* gp.GP.Produce (gp/gp.go:258-360): predictive mean and standard deviation of
  * the latent function at m points Z (row-major m x ndim).  sigma_j =

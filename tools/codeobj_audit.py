@@ -42,6 +42,10 @@ SGPR_SPILL_ALLOW = {
     # gradient w.r.t. the inputs (full Observe form, the anynoise / warpedtime case studies): N <= a few
     # hundred in the reference; 32 per-dimension accumulators
     r"xgrad_kernel<32>": 100,
+    # the full Observe form of the batch with an ARD term: the slot reduction's 16 per-dimension accumulators and the
+    # input pass's 16 share one kernel, and the length table of the 16 dimensions of a pass stays in SGPRs across both
+    # pair loops (the plain and the events instance: 47 and 45, inside the limit).  N <= 128 rows per workgroup
+    r"batch_eval_kernel<16, false, true>": 65,
 }
 #: kernels that may use AGPRs: none.  (Round 3 allowed grad_ard_mfma_kernel 64 of them "as MFMA accumulators"; with
 #: __launch_bounds__(256, 2) the compiler keeps every instance inside 226 architectural VGPRs and uses no AGPR at
