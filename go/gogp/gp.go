@@ -225,6 +225,53 @@ func (gp *GP) Absorb(x [][]float64, y []float64) (err error) {
 	return gp.err(rc) // GOGP_ECOND: gonum's Condition error, returned as gp/gp.go:233-236 does
 }
 
+// Append appends observations to the absorbed ones at the parameters of the last Absorb / Observe
+// (gogp_append): the state Absorb on all observations would leave, without a new factorisation.
+// No reference counterpart (tutorial/tutorial.go:118-142 refactorises every step).  An empty process
+// absorbs them at ThetaSimil / ThetaNoise.  When the enlarged matrix is not positive definite the
+// error is returned and the process is as it was.
+func (gp *GP) Append(x [][]float64, y []float64) (err error) {
+	gp.defaults()
+	if len(x) != len(y) {
+		return fmt.Errorf("gogp: len(x) != len(y)")
+	}
+	if len(gp.Y) == 0 {
+		if err = gp.pushData(); err != nil {
+			return err
+		}
+		tn := gp.ThetaNoise
+		if len(tn) == 0 {
+			tn = []float64{0}
+		}
+		if err = gp.err(C.gogp_absorb(gp.handle(), dptr(gp.ThetaSimil), dptr(tn))); err != nil {
+			return err
+		}
+	} else if gp.changed() {
+		return fmt.Errorf("gogp: Append: X / Y were assigned since the last Absorb / Observe; Absorb them")
+	}
+	m := len(y)
+	if m == 0 {
+		return nil
+	}
+	flat := make([]float64, m*gp.NDim)
+	for i, row := range x {
+		copy(flat[i*gp.NDim:], row)
+	}
+	rc := C.gogp_append(gp.handle(), dptr(flat), dptr(y), C.int64_t(m))
+	if rc != C.GOGP_OK && rc != C.GOGP_ECOND {
+		return gp.err(rc)
+	}
+	// the device holds the grown data: X / Y follow without a new upload
+	gp.X = append(gp.X[:len(gp.X):len(gp.X)], x...)
+	gp.Y = append(gp.Y[:len(gp.Y):len(gp.Y)], y...)
+	gp.dirty, gp.upN = false, len(gp.Y)
+	gp.upX, gp.upY = &gp.X[0], &gp.Y[0]
+	if err = gp.fetchState(); err != nil {
+		return err
+	}
+	return gp.err(rc)
+}
+
 // Factor returns the lower Cholesky factor, row-major n x n (gonum's mat.Cholesky keeps
 // U = L^T: gp.GP.L of the reference, gp/gp.go:35).
 func (gp *GP) Factor() ([]float64, error) {

@@ -109,6 +109,9 @@ static void free_n_buffers(gogp_handle *h) {
   (void)hipFree(h->small_ws);
   h->small_ws = nullptr;
   h->small_ws_bytes = 0;
+  (void)hipFree(h->app_ws);
+  h->app_ws = nullptr;
+  h->app_ws_bytes = 0;
   (void)hipFree(h->TX);
   (void)hipFree(h->Tmt);
   h->TX = h->Tmt = nullptr;
@@ -601,6 +604,7 @@ static int finish_factorize(gogp_handle *h, bool fp32, bool refine, bool kinv) {
   h->lml = fr.lml;
   h->yta = fr.yta;
   h->factored = h->have_alpha = true;
+  h->z_valid = true;
   if (kinv) h->have_kinv = true;
   h->cond_lb = fr.cond_lb;
   if (fr.rc == GOGP_ECOND) h->err = fr.msg;
@@ -1254,6 +1258,7 @@ static int set_theta_natural(gogp_handle *h, const double *ts, const double *tn)
   if (const char *why = theta_refusal(h, ts, tn)) return fail(h, GOGP_EARG, why);
   for (int i = 0; i < h->ns; ++i) h->theta_s[i] = ts[i];
   for (int i = 0; i < h->nn; ++i) h->theta_n[i] = tn[i];
+  h->have_theta = true;
   return GOGP_OK;
 }
 
@@ -2219,10 +2224,11 @@ static void produce_solve_t(gogp_handle *h, hipStream_t s, int64_t m, int64_t mp
 // Few test points (option "produce_small_max", default 64; fp64 matrices): Kstar, the mean, and V = L^-1 Kstar by the
 // persistent substitution kernel of trsm_small.hip -- one pass over the factor (8 N^2 / 2 bytes) instead of the
 // ~36-launch GEMM chain.  The reference's forecast harness asks for ONE point per step (tutorial/tutorial.go:178-179).
-static int produce_small(gogp_handle *h, hipStream_t s, int64_t m, int64_t mpad, double *dmu, double *dq) {
-  const int64_t npad = h->npad, ld = npad;
-  const size_t one = (trsm_small_workspace_bytes(std::max(npad, h->cap_npad)) + 255) / 256 * 256;
-  const size_t need = 2 * one;  // 33 .. 64 points: two launches of <= 32 columns side by side
+// the workspace of the persistent substitution kernel: two launches of <= 32 columns side by side (33 .. 64 points);
+// *one: the bytes of one launch's part
+static int ensure_small_ws(gogp_handle *h, size_t *one_out) {
+  const size_t one = (trsm_small_workspace_bytes(std::max(h->npad, h->cap_npad)) + 255) / 256 * 256;
+  const size_t need = 2 * one;
   if (!h->small_ws || h->small_ws_bytes < need) {
     (void)hipFree(h->small_ws);
     h->small_ws = nullptr;
@@ -2230,6 +2236,14 @@ static int produce_small(gogp_handle *h, hipStream_t s, int64_t m, int64_t mpad,
     HIPCHK(h, hipMalloc(&h->small_ws, need));
     h->small_ws_bytes = need;
   }
+  *one_out = one;
+  return GOGP_OK;
+}
+static int produce_small(gogp_handle *h, hipStream_t s, int64_t m, int64_t mpad, double *dmu, double *dq) {
+  const int64_t npad = h->npad, ld = npad;
+  size_t one = 0;
+  const int rcw = ensure_small_ws(h, &one);
+  if (rcw != GOGP_OK) return rcw;
   const bool f32 = h->prec == 32;  // float factor / inverses / Kstar: widened as the kernel reads them, sums in fp64
   {
     AuxTimer tm(h, GOGP_PROF_CROSS, s);
@@ -2424,6 +2438,7 @@ extern "C" int gogp_set_factor(gogp_handle *h, const double *theta_simil,
   for (hipStream_t q : work_streams(h)) HIPCHK(h, hipStreamSynchronize(q));
   h->trtri_done = h->trtri_pending = h->kinv_pending = false;
   h->tinv_valid = false;  // Produce on a restored factor substitutes panel by panel
+  h->z_valid = false;     // no z = L^-1 y comes with a restored factor (gogp_append recomputes it)
   if (h->n == 0) return GOGP_OK;
   if (h->dist) return gogp_dist_set_factor(h, Lin, alpha);  // collective: every rank keeps its own tiles
   rc = gogp_upload_params(h);
@@ -2467,6 +2482,280 @@ extern "C" int gogp_set_factor(gogp_handle *h, const double *theta_simil,
   HIPCHK(h, hipStreamSynchronize(s));
   h->lml = -0.5 * (double)n * log(2 * M_PI) - 0.5 * h->hscal[0] - 0.5 * h->hscal[2];
   return GOGP_OK;
+}
+
+// ---- append ---------------------------------------------------------------------------------------
+// m observations join the factored process at the parameters of the last Absorb / Observe / set_factor (no reference
+// counterpart: tutorial/tutorial.go:118-142 refactorises).  With K = [K11 B^T; B C] and K11 = L11 L11^T:
+//   L21 = B L11^-T,  S = C - L21 L21^T,  L22 = chol(S),  z2 = L22^-1 (y2 - L21 z1),  alpha = L^-T z
+// in chunks of <= 64 rows: the cross kernel builds B, the persistent substitution kernel (trsm_small.hip) V = L21^T in
+// one pass over the factor, append.hip's two kernels the rest; the block inverses the new rows touch are refreshed
+// between chunks; ONE backward substitution, the LML and the host copy at the end.
+// Leading dimension: ld = npad, so a call that crosses a multiple of 256 restrides the factor ONCE, for the final
+// npad, into bufA -- dead here: K was consumed by the factorisation and a K^-1 in it is invalidated anyway -- and swaps
+// the two pointers; beyond the capacity a new set of buffers is allocated (an eighth more than needed: a stream of
+// single appends then reallocates rarely).  The chunks pass over the rows that exist so far only.
+// Rollback (a pivot of S <= 0, in any chunk): the old factor was never written -- restrided: it still lies in the
+// other buffer, the pointers are swapped back; in place: the new rows lay on identity padding rows, which are put back
+// -- the one old block inverse the new rows share is restored from a copy, the data tails are zeroed again.
+struct AppendSaved {
+  double *dX, *dy, *bufA, *bufL, *Dinv, *z, *w, *alpha, *gpart;
+  int64_t cap_npad, n, npad;
+  int nblk;
+  EvalState es;
+};
+
+static int ensure_append_ws(gogp_handle *h, int64_t npad) {
+  const size_t need = ((size_t)PANEL * PANEL + (size_t)(npad / PANEL) * gogp::APPEND_PART) * sizeof(double);
+  if (h->app_ws && h->app_ws_bytes >= need) return GOGP_OK;
+  (void)hipFree(h->app_ws);
+  h->app_ws = nullptr;
+  h->app_ws_bytes = 0;
+  HIPCHK(h, hipMalloc(&h->app_ws, need));
+  h->app_ws_bytes = need;
+  return GOGP_OK;
+}
+
+extern "C" int gogp_append(gogp_handle *h, const double *X2, const double *y2, int64_t m) {
+  if (!h) return GOGP_EARG;
+  if (m < 0) return fail(h, GOGP_EARG, "append: m < 0");
+  if (m == 0) return GOGP_OK;
+  if (!X2 || !y2) return fail(h, GOGP_EARG, "append: NULL");
+  if (h->prec == 32)
+    return fail(h, GOGP_EARG, "append: not supported on a precision = 32 handle (the update is fp64 throughout)");
+  if (h->dist) return fail(h, GOGP_EARG, "append: not supported on a sharded handle");
+  for (int64_t i = 0; i < m * h->D; ++i)
+    if (!std::isfinite(X2[i])) return fail(h, GOGP_EARG, "append: non-finite input");
+  for (int64_t i = 0; i < m; ++i)
+    if (!std::isfinite(y2[i])) return fail(h, GOGP_EARG, "append: non-finite output");
+  if (!h->have_data) return fail(h, GOGP_ESTATE, "append: no data (gogp_set_data)");
+  if (h->n > 0 && !h->factored) return fail(h, GOGP_ESTATE, "append: nothing absorbed");
+  HIPCHK(h, hipSetDevice(h->device));
+  if (h->n == 0) {  // an empty process: Absorb of the m rows at the handle's parameters
+    if (!h->have_theta) return fail(h, GOGP_ESTATE, "append: no parameters (Absorb, Observe or set_factor first)");
+    const std::vector<double> ts = h->theta_s, tn = h->theta_n;
+    int rc = gogp_set_data(h, X2, y2, m);
+    if (rc != GOGP_OK) return rc;
+    rc = gogp_absorb(h, ts.data(), tn.data());
+    if (rc != GOGP_OK && rc != GOGP_ECOND) {  // empty again
+      const int64_t np = h->notpd;
+      const std::string e = h->err;
+      (void)gogp_set_data(h, nullptr, nullptr, 0);
+      h->lml = 0.0;
+      h->notpd = np;
+      h->err = e;
+    }
+    return rc;
+  }
+  // nothing of an earlier call may still run: an eager Observe's inverse reads bufL and writes bufA
+  for (hipStream_t q : work_streams(h)) HIPCHK(h, hipStreamSynchronize(q));
+  h->trtri_pending = h->alpha_pending = h->kinv_pending = false;
+  h->tinv_valid = h->tinv_pending = false;
+  h->ydone_valid = false;
+  h->kinv_c1 = 0;
+  hipStream_t s = h->s;
+  const int D = h->D;
+  const int64_t n0 = h->n, npad0 = h->npad, n1 = n0 + m, npad1 = ((n1 + PANEL - 1) / PANEL) * PANEL;
+  const bool restride = npad1 != npad0, grow = npad1 > h->cap_npad;
+  int rc = gogp_upload_params(h);
+  if (rc != GOGP_OK) return rc;
+  rc = ensure_append_ws(h, std::max(npad1, h->cap_npad));
+  if (rc != GOGP_OK) return rc;
+  double *dsave = static_cast<double *>(h->app_ws), *part = dsave + (size_t)PANEL * PANEL;
+  const size_t vb0 = (size_t)npad0 * sizeof(double), vb1 = (size_t)npad1 * sizeof(double);
+  if (!h->z_valid) {  // a restored factor: z = L^-1 y by the substitution steps
+    HIPCHK(h, hipMemcpyAsync(h->w, h->dy, vb0, hipMemcpyDeviceToDevice, s));
+    const int np0 = (int)(npad0 / PANEL);
+    for (int b = 0; b < np0; ++b) launch_trsv_fwd_step(s, h->bufL, npad0, h->Dinv, b, np0, h->w, h->z);
+    h->z_valid = true;
+  }
+  AppendSaved old{h->dX, h->dy, h->bufA, h->bufL, h->Dinv, h->z, h->w, h->alpha, h->gpart, h->cap_npad, n0, npad0, h->nblk,
+                  static_cast<const EvalState &>(*h)};
+  // the one old block inverse the new rows share
+  const bool save_blk = (n0 % PANEL) != 0;
+  const int64_t b0 = n0 / PANEL;
+  const size_t blk = (size_t)PANEL * PANEL;
+  if (save_blk) HIPCHK(h, hipMemcpyAsync(dsave, h->Dinv + (size_t)b0 * blk, blk * sizeof(double), hipMemcpyDeviceToDevice, s));
+  const size_t xslack = GOGP_MAX_NDIM;
+  if (grow) {
+    const int64_t cap = npad1 + ((npad1 / 8 + PANEL - 1) / PANEL) * PANEL;
+    const size_t nn = (size_t)cap * (size_t)cap * sizeof(double);
+    double *nX = nullptr, *ny = nullptr, *nA = nullptr, *nL = nullptr, *nD = nullptr, *nz = nullptr, *nw = nullptr,
+           *na = nullptr, *ng = nullptr;
+    hipError_t e = hipMalloc(&nX, ((size_t)cap * D + xslack) * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc(&ny, (size_t)cap * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc(&nA, nn);
+    if (e == hipSuccess) e = hipMalloc(&nL, nn);
+    if (e == hipSuccess) e = hipMalloc(&nD, (size_t)(cap / PANEL) * blk * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc(&nz, (size_t)cap * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc(&nw, (size_t)cap * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc(&na, (size_t)cap * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc(&ng, (size_t)grad_reduce_blocks(cap) * NACC * sizeof(double));
+    if (e != hipSuccess) {
+      for (double *p : {nX, ny, nA, nL, nD, nz, nw, na, ng}) (void)hipFree(p);
+      (void)hipGetLastError();
+      return fail(h, GOGP_ENOMEM, "append: out of device memory");
+    }
+    HIPCHK(h, hipMemsetAsync(nX, 0, ((size_t)cap * D + xslack) * sizeof(double), s));
+    HIPCHK(h, hipMemsetAsync(ny, 0, (size_t)cap * sizeof(double), s));
+    HIPCHK(h, hipMemsetAsync(nz, 0, (size_t)cap * sizeof(double), s));
+    HIPCHK(h, hipMemcpyAsync(nX, old.dX, (size_t)n0 * D * sizeof(double), hipMemcpyDeviceToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(ny, old.dy, (size_t)n0 * sizeof(double), hipMemcpyDeviceToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(nz, old.z, (size_t)n0 * sizeof(double), hipMemcpyDeviceToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(nD, old.Dinv, (size_t)(npad0 / PANEL) * blk * sizeof(double), hipMemcpyDeviceToDevice, s));
+    h->dX = nX;
+    h->dy = ny;
+    h->bufA = nA;
+    h->bufL = nL;
+    h->Dinv = nD;
+    h->z = nz;
+    h->w = nw;
+    h->alpha = na;
+    h->gpart = ng;
+    h->cap_npad = cap;
+    launch_append_restride(s, old.bufL, npad0, npad0, h->bufL, npad1, npad1);
+  } else {
+    if (restride) {
+      launch_append_restride(s, old.bufL, npad0, npad0, old.bufA, npad1, npad1);
+      h->bufL = old.bufA;
+      h->bufA = old.bufL;
+    }
+    // the data tails: the rows between the old and the new end may never have been written
+    HIPCHK(h, hipMemsetAsync(h->dX + (size_t)n0 * D, 0, ((size_t)(npad1 - n0) * D + xslack) * sizeof(double), s));
+    HIPCHK(h, hipMemsetAsync(h->dy + n0, 0, (size_t)(npad1 - n0) * sizeof(double), s));
+    HIPCHK(h, hipMemsetAsync(h->z + n0, 0, (size_t)(npad1 - n0) * sizeof(double), s));
+  }
+  h->npad = npad1;
+  h->nblk = (int)(npad1 / TILE);
+  const int64_t ld = npad1;
+  int64_t ncur = n0, touched = n0;  // rows < touched of the new factor rows may have been written
+  // put everything back as it was before the call (the factor itself was never overwritten)
+  auto rollback = [&]() {
+    for (hipStream_t q : {s, h->s2}) (void)hipStreamSynchronize(q);
+    if (grow) {
+      for (double *p : {h->dX, h->dy, h->bufA, h->bufL, h->Dinv, h->z, h->w, h->alpha, h->gpart}) (void)hipFree(p);
+      h->dX = old.dX;
+      h->dy = old.dy;
+      h->Dinv = old.Dinv;
+      h->z = old.z;
+      h->w = old.w;
+      h->alpha = old.alpha;
+      h->gpart = old.gpart;
+      h->cap_npad = old.cap_npad;
+    } else {
+      if (!restride) launch_append_identity_rows(s, old.bufL, npad0, n0, std::min(touched, npad0), npad0);
+      if (save_blk) (void)hipMemcpyAsync(h->Dinv + (size_t)b0 * blk, dsave, blk * sizeof(double), hipMemcpyDeviceToDevice, s);
+      (void)hipMemsetAsync(h->dX + (size_t)n0 * D, 0, ((size_t)(npad1 - n0) * D + xslack) * sizeof(double), s);
+      (void)hipMemsetAsync(h->dy + n0, 0, (size_t)(npad1 - n0) * sizeof(double), s);
+      (void)hipMemsetAsync(h->z + n0, 0, (size_t)(npad1 - n0) * sizeof(double), s);
+    }
+    h->bufA = old.bufA;
+    h->bufL = old.bufL;
+    h->n = n0;
+    h->npad = npad0;
+    h->nblk = old.nblk;
+    static_cast<EvalState &>(*h) = old.es;
+    if (restride && !grow) h->have_kinv = false;  // bufA held the restrided copy
+    (void)hipStreamSynchronize(s);
+    free_m_buffers(h);  // sized for the npad that did not come to be
+  };
+  HIPCHK(h, hipMemcpyAsync(h->dX + (size_t)n0 * D, X2, (size_t)m * D * sizeof(double), hipMemcpyHostToDevice, s));
+  HIPCHK(h, hipMemcpyAsync(h->dy + n0, y2, (size_t)m * sizeof(double), hipMemcpyHostToDevice, s));
+  HIPCHK(h, hipMemsetAsync(h->info, 0, sizeof(long long), s));
+  rc = ensure_m(h, 64, TILE);
+  size_t one = 0;
+  if (rc == GOGP_OK) rc = ensure_small_ws(h, &one);
+  if (rc != GOGP_OK) {
+    const std::string e = h->err;
+    rollback();
+    h->err = e;
+    return rc;
+  }
+  unsigned *htmo = reinterpret_cast<unsigned *>(h->hscal + 10);
+  const size_t ev0 = EV_BASE + 4 * (size_t)(npad1 / PANEL) + 8;  // Produce's event slots
+  for (int64_t off = 0; off < m; off += 64) {
+    const int mc = (int)std::min<int64_t>(64, m - off), m1 = std::min(mc, 32);
+    const int64_t npc = ((ncur + PANEL - 1) / PANEL) * PANEL;  // the rows that exist so far, in whole blocks
+    const double *Xc = h->dX + (size_t)ncur * D, *yc = h->dy + ncur;
+    double *Lrow = h->bufL + (size_t)ncur * ld;
+    touched = ncur + mc;
+    launch_cross(s, h->devP, D, h->dX, ncur, npc, Xc, mc, TILE, h->KsT, ld, h->ev());  // B, as Produce's Kstar^T
+    unsigned *tmo = nullptr, *tmo2 = nullptr;
+    htmo[0] = htmo[1] = 0;
+    if (mc > 32) {  // the second 32 columns beside the first, as Produce (every stream is idle here)
+      order(h, ev0 + 1, s, h->s2);
+      launch_trsm_small(h->s2, h->bufL, ld, h->Dinv, h->KsT, ld, npc, 32, mc - 32, (char *)h->small_ws + one, h->pvec, &tmo2);
+      HIPCHK(h, hipMemcpyAsync(htmo + 1, tmo2, sizeof(unsigned), hipMemcpyDeviceToHost, h->s2));
+    }
+    launch_trsm_small(s, h->bufL, ld, h->Dinv, h->KsT, ld, npc, 0, m1, h->small_ws, h->pvec, &tmo);
+    HIPCHK(h, hipMemcpyAsync(htmo, tmo, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+    if (mc > 32) order(h, ev0 + PRODUCE_GROUPS + 1, h->s2, s);
+    gogp::TsSolution v0 = gogp::trsm_small_solution(npc, 0, m1, h->small_ws), v1 = v0;
+    if (mc > 32) v1 = gogp::trsm_small_solution(npc, 32, mc - 32, (char *)h->small_ws + one);
+    launch_append_gram(s, v0, v1, m1, mc, npc, ncur, h->z, part, Lrow, ld);
+    launch_append_commit(s, h->devP, Xc, yc, mc, ncur, part, (int)(npc / PANEL), Lrow, ld, h->z + ncur, h->info, h->ev());
+    HIPCHK(h, hipMemcpyAsync(h->hscal + HS_INFO, h->info, sizeof(long long), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    HIPCHK(h, hipGetLastError());
+    if ((htmo[0] | htmo[1]) != 0u) {
+      // a workgroup of the substitution kernel gave up waiting: this chunk again with one chain of substitution steps
+      // per new row (solve.hip), whose solutions lie row by row in Vt
+      const int nbc = (int)(npc / PANEL);
+      for (int j = 0; j < mc; ++j) {
+        HIPCHK(h, hipMemcpyAsync(h->w, h->KsT + (size_t)j * ld, (size_t)npc * sizeof(double), hipMemcpyDeviceToDevice, s));
+        for (int b = 0; b < nbc; ++b) launch_trsv_fwd_step(s, h->bufL, ld, h->Dinv, b, nbc, h->w, h->Vt + (size_t)j * ld);
+      }
+      gogp::TsSolution vr;
+      vr.p = h->Vt;
+      vr.kind = gogp::TS_SOL_ROWS;
+      vr.width = (int)ld;
+      HIPCHK(h, hipMemsetAsync(h->info, 0, sizeof(long long), s));
+      launch_append_gram(s, vr, vr, mc, mc, npc, ncur, h->z, part, Lrow, ld);
+      launch_append_commit(s, h->devP, Xc, yc, mc, ncur, part, nbc, Lrow, ld, h->z + ncur, h->info, h->ev());
+      HIPCHK(h, hipMemcpyAsync(h->hscal + HS_INFO, h->info, sizeof(long long), hipMemcpyDeviceToHost, s));
+      HIPCHK(h, hipStreamSynchronize(s));
+      HIPCHK(h, hipGetLastError());
+    }
+    long long info = 0;
+    memcpy(&info, h->hscal + HS_INFO, sizeof info);
+    if (info != 0) {
+      rollback();
+      h->notpd = (int64_t)info - 1;  // global: the commit kernel counts from the rows that existed
+      char buf[160];
+      snprintf(buf, sizeof buf, "Factorize: matrix is not positive definite (pivot %lld)", (long long)h->notpd);
+      h->err = buf;
+      return GOGP_ENOTPD;
+    }
+    for (int64_t b = ncur / PANEL; b <= (ncur + mc - 1) / PANEL; ++b)
+      launch_diag256_inv_only(s, h->bufL + (size_t)b * PANEL * (ld + 1), ld, h->Dinv + (size_t)b * blk);
+    ncur += mc;
+  }
+  h->n = n1;
+  // alpha = L^-T z over the whole new factor, the LML from y^T alpha as gogp_set_factor
+  const int np1 = (int)(npad1 / PANEL);
+  HIPCHK(h, hipMemcpyAsync(h->w, h->z, vb1, hipMemcpyDeviceToDevice, s));
+  for (int b = np1 - 1; b >= 0; --b) launch_trsv_bwd_step(s, h->bufL, ld, h->Dinv, b, np1, h->w, h->alpha);
+  launch_lml_scalars(s, h->bufL, ld, h->z, h->dy, h->alpha, n1, h->scalars);
+  HIPCHK(h, hipMemcpyAsync(h->hscal, h->scalars, 7 * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipStreamSynchronize(s));
+  HIPCHK(h, hipGetLastError());
+  if (grow) {
+    for (double *p : {old.dX, old.dy, old.bufA, old.bufL, old.Dinv, old.z, old.w, old.alpha, old.gpart}) (void)hipFree(p);
+    drop_cand_graph(h);
+  }
+  h->hscal[6] = h->hscal[2];  // y^T alpha where judge_scalars looks for the quadratic term of a refined alpha
+  const long long zero = 0;
+  memcpy(h->hscal + HS_INFO, &zero, sizeof zero);
+  const FactorResult fr = judge_scalars(h, h->hscal, false, true);
+  h->lml = fr.lml;
+  h->yta = fr.yta;
+  h->cond_lb = fr.cond_lb;
+  h->notpd = -1;
+  h->factored = h->have_alpha = true;
+  h->observed = h->with_obs = h->grad_valid = h->have_kinv = h->trtri_done = false;
+  h->z_valid = true;
+  if (fr.rc == GOGP_ECOND) h->err = fr.msg;
+  return fr.rc;
 }
 
 // ---- measurement hooks -----------------------------------------------------------------------------

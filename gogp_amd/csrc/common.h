@@ -349,6 +349,33 @@ void launch_trsm_small(hipStream_t s, const double *L, int64_t ld, const double 
                        int64_t npad, int j0, int cnt, void *ws, double *dq, unsigned **tmo_dev);
 void launch_trsm_small(hipStream_t s, const float *L, int64_t ld, const float *Dinv, const float *KsT, int64_t ldk,
                        int64_t npad, int j0, int cnt, void *ws, double *dq, unsigned **tmo_dev);  // fp32 path
+// ... and where that launch leaves V: TS_SOL_PAIRED element (row k, rhs j) at ((k >> 1) * width + j) * 2 + (k & 1) doubles,
+// TS_SOL_COMPACT at k * width + j doubles, TS_SOL_GRANULE (one right-hand side) 16 bytes per row: {tag, low word, tag, high word}
+// (TS_SOL_ROWS, never that kernel's: at j * width + k doubles -- one solution per row, as the substitution steps of solve.hip leave it)
+enum { TS_SOL_PAIRED = 0, TS_SOL_COMPACT = 1, TS_SOL_GRANULE = 2, TS_SOL_ROWS = 3 };
+struct TsSolution {
+  const void *p = nullptr;
+  int kind = TS_SOL_PAIRED, width = 32;
+};
+TsSolution trsm_small_solution(int64_t npad, int j0, int cnt, void *ws);
+// append.hip: the kernels of gogp_append (api.hip) -- rows n .. n + m - 1 (m <= 64) join a factor of n rows.
+// V = L11^-1 B^T (npc rows, the columns j < m0 in v0 and the rest in v1, as launch_trsm_small left them).
+// launch_append_gram: one workgroup per 256 rows of V writes its part of G = V^T V (lower 16 x 16 tiles) and of V^T z to
+// part[slab] (APPEND_PART doubles each) and its columns k < n of the new rows L21 = V^T to Lnew (row j at Lnew + j * ld).
+// launch_append_commit: one workgroup sums the parts in slab order, forms S = C - G (C from X2, the m new inputs, with the
+// noise on the diagonal), factors it, and -- positive definite -- writes L22 behind L21, z2 = L22^-1 (y2 - V^T z) to
+// z2out; else *info = n + pivot + 1 (first failure wins) and nothing else is written.
+constexpr int APPEND_PART = 64 * 64 + 64;
+void launch_append_gram(hipStream_t s, TsSolution v0, TsSolution v1, int m0, int m, int64_t npc, int64_t n,
+                        const double *z, double *part, double *Lnew, int64_t ld);
+void launch_append_commit(hipStream_t s, const DevParams *p, const double *X2, const double *y2, int m, int64_t n,
+                          const double *part, int nslab, double *Lnew, int64_t ld, double *z2out, long long *info,
+                          bool ev);
+// rows r0 .. r1 - 1 of L (columns < ncols) := rows of the identity
+void launch_append_identity_rows(hipStream_t s, double *L, int64_t ld, int64_t r0, int64_t r1, int64_t ncols);
+// dst (npad1 rows, ld1) := src (npad0 rows, ld0) on the 256-blocks of the lower triangle, identity on the new ones
+void launch_append_restride(hipStream_t s, const double *src, int64_t ld0, int64_t npad0, double *dst, int64_t ld1,
+                            int64_t npad1);
 void launch_fill(hipStream_t s, double *p, int64_t count, double v);
 void launch_axpy(hipStream_t s, double *a, const double *b, int64_t count);  // a += b
 void launch_dot(hipStream_t s, const double *a, const double *b, int64_t n, double *out);  // out[0] = a.b

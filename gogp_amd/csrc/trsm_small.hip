@@ -609,4 +609,28 @@ void launch_trsm_small(hipStream_t s, const float *L, int64_t ld, const float *D
   launch_trsm_small_t<float>(s, L, ld, Dinv, KsT, ldk, npad, j0, cnt, ws, dq, tmo_dev);
 }
 
+// Where a launch of launch_trsm_small (same npad, j0, cnt, ws) leaves its solution V, for kernels that read it behind
+// the launch on the same stream (append.hip): the layout follows the kernel instance the launcher picks.
+TsSolution trsm_small_solution(int64_t npad, int j0, int cnt, void *ws) {
+  TsSolution r;
+  char *p = (char *)ws;
+  if (j0 == 0 && cnt == 1) {  // launch_trsv_granule: [tmo (16 B) | Vg | Wg]
+    r.p = p + 16;
+    r.kind = TS_SOL_GRANULE;
+    r.width = 1;
+    return r;
+  }
+  const int nb = (int)(npad / PANEL);
+  const size_t fbytes = ((size_t)(2 * nb + 8) * sizeof(unsigned) + 15) / 16 * 16;
+  r.p = p + (fbytes + 255) / 256 * 256;
+  if (cnt <= 8) {
+    r.kind = TS_SOL_COMPACT;
+    r.width = cnt <= 1 ? 1 : cnt <= 2 ? 2 : cnt <= 4 ? 4 : 8;
+  } else {
+    r.kind = TS_SOL_PAIRED;
+    r.width = cnt <= 16 ? 16 : 32;
+  }
+  return r;
+}
+
 }  // namespace gogp

@@ -173,6 +173,37 @@ class GP:
         self._with_obs = False
         self._check(_lib.lib().gogp_absorb(self._h, _dp(ts), _dp(tn)))
 
+    # ---- no reference counterpart (the reference refactorises: tutorial/tutorial.go:118-142) ----
+    def Append(self, x, y) -> None:
+        """Append observations to the absorbed ones at the parameters of the last Absorb / Observe / restore
+        (gogp_append): the state Absorb on all observations would leave, without a new factorisation.  An empty
+        process absorbs them at ThetaSimil / ThetaNoise.  Raises FactorizeError (``pivot``: the global index) and
+        leaves the process as it was when the enlarged matrix is not positive definite."""
+        xa = _arr(x).reshape(-1, self.NDim)
+        ya = _arr(y).reshape(-1)
+        if len(xa) != len(ya):
+            raise ValueError("len(x) != len(y)")
+        L = _lib.lib()
+        if len(self._Y) == 0:
+            # an empty process: pending (empty) data first, and the parameters the append is to use
+            self._push_data()
+            ts = _arr(self.ThetaSimil)
+            tn = _arr(self.ThetaNoise) if self._nn else np.zeros(1)
+            if ts.size != self._ns:
+                raise ValueError("len(ThetaSimil)")
+            self._check(L.gogp_absorb(self._h, _dp(ts), _dp(tn)))
+        elif self._data_dirty:
+            # the device no longer holds X / Y: nothing there to append to
+            raise GogpError(_lib.GOGP_ESTATE, "Append: X / Y were assigned since the last Absorb / Observe; Absorb them")
+        if len(ya) == 0:
+            return
+        rc = L.gogp_append(self._h, _dp(xa), _dp(ya), len(ya))
+        if rc in (_lib.GOGP_OK, _lib.GOGP_ECOND):  # stored (GOGP_ECOND: and reported, as Absorb)
+            self._X = np.concatenate([self._X.reshape(-1, self.NDim), xa])
+            self._Y = np.concatenate([self._Y, ya])
+            self._with_obs = False
+        self._check(rc)
+
     # ---- gp.GP.LML (gp/gp.go:244-253) -----------------------------------------------
     def LML(self) -> float:
         v = ctypes.c_double(0.0)

@@ -62,6 +62,30 @@ class GP {
     return ra != GOGP_OK ? ra : rc;  // GOGP_ECOND: gonum's Condition error, gp/gp.go:233-236
   }
 
+  // Append observations to the absorbed ones at the parameters of the last Absorb / Observe (gogp_append; no reference
+  // counterpart: tutorial/tutorial.go:118-142 refactorises).  An empty process absorbs them at ThetaSimil / ThetaNoise.
+  // GOGP_ENOTPD: nothing changed.  GOGP_ESTATE: X / Y were re-assigned since the last upload (Absorb them instead).
+  int Append(const std::vector<std::vector<double>> &x, const std::vector<double> &y) {
+    if (x.size() != y.size()) return GOGP_EARG;
+    if (Y.empty()) {
+      int rc = push();
+      if (rc != GOGP_OK) return rc;
+      double zero = 0.0;
+      rc = gogp_absorb(h_, ThetaSimil.data(), ThetaNoise.empty() ? &zero : ThetaNoise.data());
+      if (rc != GOGP_OK) return rc;
+    } else if (dirty_) {
+      return GOGP_ESTATE;
+    }
+    if (y.empty()) return GOGP_OK;
+    std::vector<double> flat = pack(x);
+    const int rc = gogp_append(h_, flat.data(), y.data(), (int64_t)y.size());
+    if (rc != GOGP_OK && rc != GOGP_ECOND) return rc;
+    X.insert(X.end(), x.begin(), x.end());
+    Y.insert(Y.end(), y.begin(), y.end());
+    const int ra = fetch_alpha();
+    return ra != GOGP_OK ? ra : rc;
+  }
+
   // Assign the observations (gp.GP.X / gp.GP.Y); uploaded on the next Absorb / Observe.
   void SetData(const std::vector<std::vector<double>> &x, const std::vector<double> &y) {
     X = x;

@@ -311,6 +311,17 @@ int gogp_set_factor(gogp_handle *h, const double *theta_simil,
                     const double *theta_noise, const double *L /* n*n */,
                     const double *alpha /* n */);
 
+/* Append m observations to the factored process at the parameters of the last
+ * Absorb / Observe / set_factor: afterwards the handle is in the state gogp_absorb on the
+ * n + m observations would leave (factor, alpha, LML, Produce; no gradient: gogp_gradient
+ * returns GOGP_ESTATE as after Absorb), in O((n + m)^2 m) work and two passes over the factor.
+ * No reference counterpart (the reference refactorises: tutorial/tutorial.go:118-142).
+ * m == 0: nothing happens.  An empty process (n == 0, data set, parameters given): Absorb of the m rows.
+ * GOGP_EARG: NULL or non-finite inputs, a precision = 32 handle, a sharded handle.  GOGP_ESTATE: not factored.
+ * GOGP_ENOTPD: the handle holds exactly the state it had before the call (gogp_n, factor, Produce);
+ * gogp_notpd_index is the global index of the failing pivot.  GOGP_ECOND: stored and reported, as Absorb. */
+int gogp_append(gogp_handle *h, const double *X2 /* m x ndim */, const double *y2 /* m */, int64_t m);
+
 /* ---- one evaluation sharded over several GPUs: 2-D block-cyclic ---------------------
  * One process per GPU.  The ranks form a Pr x Pc process grid (rank = pr*Pc + pc; Pr must
  * divide Pc: 1x1, 1x2, 2x2, 2x4 for 1/2/4/8 GPUs, gogp_dist_grid).  The Gram matrix is cut into
