@@ -313,6 +313,24 @@ func (gp *GP) Produce(x [][]float64) (mu, sigma []float64, err error) {
 	return mu, sigma, nil
 }
 
+// ProduceGradient computes predictions and their derivatives with respect to
+// the test points: dmu[i*NDim+d] = d mu_i / d x[i][d], dsigma likewise (no
+// reference counterpart).
+func (gp *GP) ProduceGradient(x [][]float64) (mu, sigma, dmu, dsigma []float64, err error) {
+	gp.defaults()
+	m := len(x)
+	flat := make([]float64, m*gp.NDim)
+	for i, row := range x {
+		copy(flat[i*gp.NDim:], row)
+	}
+	mu, sigma = make([]float64, m), make([]float64, m)
+	dmu, dsigma = make([]float64, m*gp.NDim), make([]float64, m*gp.NDim)
+	if err = gp.err(C.gogp_produce_gradient(gp.handle(), dptr(flat), C.int64_t(m), dptr(mu), dptr(sigma), dptr(dmu), dptr(dsigma))); err != nil {
+		return nil, nil, nil, nil, err
+	}
+	return mu, sigma, dmu, dsigma, nil
+}
+
 // Observe computes the log marginal likelihood of log-transformed
 // hyperparameters [, inputs, outputs] (gp/gp.go:374-413).  Panics where the
 // reference panics.

@@ -80,6 +80,7 @@ SYMBOLS = [
      [_h, ctypes.c_int32, _dp, ctypes.POINTER(_i64), ctypes.POINTER(_i64), _dp, _dp, _dp, _dp,
       ctypes.POINTER(ctypes.c_int)]),
     ("gogp_produce", ctypes.c_int, [_h, _dp, _i64, _dp, _dp]),
+    ("gogp_produce_gradient", ctypes.c_int, [_h, _dp, _i64, _dp, _dp, _dp, _dp]),
     ("gogp_n", _i64, [_h]),
     ("gogp_get_alpha", ctypes.c_int, [_h, _dp]),
     ("gogp_get_factor", ctypes.c_int, [_h, _dp]),

@@ -158,8 +158,10 @@ static void free_m_buffers(gogp_handle *h) {
   (void)hipFree(h->KsT);
   (void)hipFree(h->Vt);
   (void)hipFree(h->pvec);
-  h->dZ = h->KsT = h->Vt = h->pvec = nullptr;
+  (void)hipFree(h->pg_ws);
+  h->dZ = h->KsT = h->Vt = h->pvec = h->pg_ws = nullptr;
   h->cap_m = h->cap_mp_npad = 0;
+  h->pg_ws_doubles = 0;
 }
 
 // ---- stream sets ------------------------------------------------------------------------
@@ -2337,6 +2339,84 @@ extern "C" int gogp_produce(gogp_handle *h, const double *Z, int64_t m, double *
     h->err = buf;
     return GOGP_EHIP;
   }
+  return GOGP_OK;
+}
+
+// ---- produce with derivatives -------------------------------------------------------------------
+// W^T = V^T L^-1 behind produce_solve_t, on the main stream: the block backward substitution over the rows of Vt
+// (one test point each), from the last column panel to the first.  Per step two launches of the skinny NN kernel
+// (pgrad.hip): W^T[:, p] = R[:, p] inv(L_pp) into KsT (whose Kstar^T the forward pass has consumed), then
+// R[:, j] -= W^T[:, p] L[p, j] for every column j left of the panel, in place in Vt.  A step is a super-panel of
+// `produce_panels` 256-panels where the forward pass has assembled T^-1 (2 launches per 1024 columns), one 256-panel
+// through its Dinv block otherwise.
+static void produce_backward(gogp_handle *h, hipStream_t s, int64_t m) {
+  const int64_t npad = h->npad, ld = npad, rows16 = (m + 15) / 16;
+  double *V = h->Vt, *W = h->KsT;
+  const int npanel = (int)(npad / PANEL);
+  const bool use_tinv = h->produce_tinv && h->lookahead && h->TX && h->tinv_valid && h->tinv_sig == tinv_signature(h);
+  const int pw = use_tinv ? h->produce_panels : 1;
+  for (int P0 = (npanel - 1) / pw * pw; P0 >= 0; P0 -= pw) {
+    const int nsub = std::min(pw, npanel - P0), K = nsub * PANEL;
+    const int64_t C0 = (int64_t)P0 * PANEL;
+    const double *Binv = use_tinv ? h->TX + C0 * h->tinv_ld : h->Dinv + (size_t)P0 * PANEL * PANEL;
+    launch_bwd_panel(s, rows16, V + C0, ld, Binv, use_tinv ? h->tinv_ld : (int64_t)PANEL, W + C0, ld, K, K, true, false);
+    launch_bwd_panel(s, rows16, W + C0, ld, h->bufL + C0 * ld, ld, V, ld, C0, K, false, true);
+  }
+}
+
+extern "C" int gogp_produce_gradient(gogp_handle *h, const double *Z, int64_t m, double *mu, double *sigma,
+                                     double *dmu_out, double *dsigma_out) {
+  if (!h || m < 0 || (m > 0 && (!Z || !mu || !sigma || !dmu_out || !dsigma_out)))
+    return fail(h, GOGP_EARG, "produce_gradient: NULL");
+  if (h->prec == 32) return fail(h, GOGP_EARG, "produce_gradient: precision = 32 handles are not supported");
+  if (h->dist) return fail(h, GOGP_EARG, "produce_gradient: sharded handles are not supported");
+  if (m == 0) return GOGP_OK;
+  if (h->n > 0 && !h->factored) return fail(h, GOGP_ESTATE, "ProduceGradient: nothing absorbed");
+  HIPCHK(h, hipSetDevice(h->device));
+  const int64_t mpad = ((m + TILE - 1) / TILE) * TILE;
+  const int D = h->D;
+  int rc = ensure_m(h, m, mpad);
+  if (rc != GOGP_OK) return rc;
+  hipStream_t s = h->s;
+  double *prior = h->pvec, *dmu = h->pvec + mpad, *dq = h->pvec + 2 * mpad, *dsig = h->pvec + 3 * mpad;
+  if (h->n == 0) {
+    rc = gogp_upload_params(h);  // no observations: parameters may not have been uploaded yet
+    if (rc != GOGP_OK) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->dZ, Z, (size_t)m * D * sizeof(double), hipMemcpyHostToDevice, s));
+    launch_prior(s, h->devP, h->dZ, m, prior);
+    launch_sigma(s, prior, nullptr, m, dsig);
+    HIPCHK(h, hipMemcpyAsync(sigma, dsig, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    for (int64_t j = 0; j < m; ++j) mu[j] = 0.0;
+    for (int64_t j = 0; j < m * D; ++j) dmu_out[j] = dsigma_out[j] = 0.0;  // the prior does not depend on z
+    return GOGP_OK;
+  }
+  const int nslab = gogp::pgrad_slabs(h->npad, m, nullptr);
+  const size_t md = (size_t)m * D, need = md * (2 * (size_t)nslab + 2);
+  if (!h->pg_ws || h->pg_ws_doubles < need) {
+    (void)hipFree(h->pg_ws);
+    h->pg_ws = nullptr;
+    h->pg_ws_doubles = 0;
+    HIPCHK(h, hipMalloc(&h->pg_ws, need * sizeof(double)));
+    h->pg_ws_doubles = need;
+  }
+  double *part = h->pg_ws, *ddmu = part + 2 * (size_t)nslab * md, *ddsig = ddmu + md;
+  HIPCHK(h, hipMemcpyAsync(h->dZ, Z, (size_t)m * D * sizeof(double), hipMemcpyHostToDevice, s));
+  launch_prior(s, h->devP, h->dZ, m, prior);
+  rc = ensure_alpha(h);
+  if (rc != GOGP_OK) return rc;
+  // always the tile route of Produce, whatever m: it leaves V^T in Vt, row by row, where the backward pass starts
+  // (the persistent few-point kernel keeps its solution in a layout of its own)
+  produce_solve_t<double>(h, s, m, mpad, dmu, dq);
+  launch_sigma(s, prior, dq, m, dsig);
+  produce_backward(h, s, m);
+  launch_pgrad(s, h->devP, D, h->dX, h->n, h->npad, h->dZ, m, h->alpha, h->KsT, h->npad, dsig, part, ddmu, ddsig, h->ev());
+  HIPCHK(h, hipMemcpyAsync(mu, dmu, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipMemcpyAsync(sigma, dsig, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipMemcpyAsync(dmu_out, ddmu, md * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipMemcpyAsync(dsigma_out, ddsig, md * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipStreamSynchronize(s));
+  HIPCHK(h, hipGetLastError());
   return GOGP_OK;
 }
 

@@ -282,6 +282,17 @@ void launch_pack_lower(hipStream_t s, const double *in, int64_t n, int64_t npad,
                        int64_t ld);
 void launch_sigma(hipStream_t s, const double *prior, const double *q, int64_t m,
                   double *sigma);
+// pgrad.hip (gogp_produce_gradient).  launch_bwd_panel: C (16 rows16 x ncols, ncols a multiple of 64) = A B (sub: C - A B)
+// with A 16 rows16 x K and B K x ncols row-major, K a multiple of 32; tri: B[k][j] == 0 for k < j.  The rows are taken
+// in groups of 64: beyond 32 rows, A and C must hold a multiple of 64.
+void launch_bwd_panel(hipStream_t s, int64_t rows16, const double *A, int64_t lda, const double *B, int64_t ldb,
+                      double *C, int64_t ldc, int64_t ncols, int K, bool tri, bool sub);
+// dmu[j][d] = sum_i alpha_i dk(z_j, x_i)/dz_jd, dsigma[j][d] = -2 sum_i Wt[j][i] dk(z_j, x_i)/dz_jd / (2 sigma_j);
+// part: 2 * pgrad_slabs(npad, m) * m * ndim doubles of scratch
+int pgrad_slabs(int64_t npad, int64_t m, int *tiles_per_slab);
+void launch_pgrad(hipStream_t s, const DevParams *p, int ndim, const double *X, int64_t n, int64_t npad,
+                  const double *Z, int64_t m, const double *alpha, const double *Wt, int64_t ld, const double *sigma,
+                  double *part, double *dmu, double *dsigma, bool ev);
 int grad_reduce_blocks(int64_t npad);
 
 // fused gradient reduction over lower tiles of Kinv; out: NACC doubles

@@ -89,6 +89,8 @@ struct gogp_handle : EvalBufs, EvalState {
   // produce workspace
   double *dZ = nullptr, *KsT = nullptr, *Vt = nullptr, *pvec = nullptr;
   int64_t cap_m = 0, cap_mp_npad = 0;
+  double *pg_ws = nullptr;     // gogp_produce_gradient: partial sums of pgrad_kernel + the two derivative arrays
+  size_t pg_ws_doubles = 0;
   hipStream_t s = nullptr;   // main stream: Gram, big trailing updates, reductions
   hipStream_t sp = nullptr;  // panel stream (high priority): diagonal blocks, TRSM-as-GEMM,
                              // skinny updates, substitution steps -- overlaps the big updates

@@ -221,6 +221,24 @@ class GP:
             self._check(_lib.lib().gogp_produce(self._h, _dp(z), m, _dp(mu), _dp(sigma)))
         return mu, sigma
 
+    def ProduceGradient(self, x):
+        """Produce and the derivatives of the forecast with respect to the test points:
+        (mu, sigma, dmu, dsigma) with dmu[j, d] = d mu_j / d x[j, d] and dsigma[j, d] =
+        d sigma_j / d x[j, d], both of shape (m, NDim).  mu and sigma are what Produce(x)
+        returns.  No reference counterpart: gp.GP.Produce returns mu and sigma only.  sigma
+        is not clamped: a row of dsigma whose sigma^2 is not positive is NaN / inf.  fp64,
+        unsharded handles only."""
+        z = _arr(x).reshape(-1, self.NDim)
+        m = len(z)
+        mu, sigma = np.zeros(m), np.zeros(m)
+        dmu, dsigma = np.zeros((m, self.NDim)), np.zeros((m, self.NDim))
+        if m:
+            if self._data_dirty and len(self._Y) == 0:
+                self._push_data()
+            self._check(_lib.lib().gogp_produce_gradient(self._h, _dp(z), m, _dp(mu), _dp(sigma), _dp(dmu),
+                                                         _dp(dsigma)))
+        return mu, sigma, dmu, dsigma
+
     # ---- gp.GP.Observe (gp/gp.go:374-413) ---------------------------------------------
     def Observe(self, x) -> float:
         """x = log-transformed hyperparameters [| inputs | outputs].  Raises where

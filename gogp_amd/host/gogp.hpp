@@ -111,6 +111,18 @@ class GP {
     return gogp_produce(h_, flat.data(), (int64_t)x.size(), mu.data(), sigma.data()) == GOGP_OK;
   }
 
+  // Produce and d mu / d x, d sigma / d x (row-major x.size() x NDim); no reference counterpart
+  bool ProduceGradient(const std::vector<std::vector<double>> &x, std::vector<double> &mu, std::vector<double> &sigma,
+                       std::vector<double> &dmu, std::vector<double> &dsigma) {
+    std::vector<double> flat = pack(x);
+    mu.assign(x.size(), 0.0);
+    sigma.assign(x.size(), 0.0);
+    dmu.assign(flat.size(), 0.0);
+    dsigma.assign(flat.size(), 0.0);
+    return gogp_produce_gradient(h_, flat.data(), (int64_t)x.size(), mu.data(), sigma.data(), dmu.data(),
+                                 dsigma.data()) == GOGP_OK;
+  }
+
   // gp/gp.go:374-413
   double Observe(const std::vector<double> &x) {
     const size_t P = ThetaSimil.size() + ThetaNoise.size();

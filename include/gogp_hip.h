@@ -291,6 +291,18 @@ int gogp_batch_produce_full(gogp_handle *h, int32_t k, const double *x, const in
  * observations: mu = 0, sigma = sqrt(prior) (gp/gp.go:343-347). */
 int gogp_produce(gogp_handle *h, const double *Z, int64_t m, double *mu,
                  double *sigma);
+/* gogp_produce and the derivatives of the forecast with respect to the test points (no reference counterpart):
+ *   dmu[j][d]    = d mu_j / d z_jd    = sum_i alpha_i dk(z_j, x_i)/dz_jd
+ *   dsigma[j][d] = d sigma_j / d z_jd = -2 sum_i (K^-1 Kstar)_ij dk(z_j, x_i)/dz_jd / (2 sigma_j)
+ * both row-major m x ndim.  mu and sigma are what gogp_produce returns for the same Z; sigma is not clamped, so a row
+ * of dsigma with sigma_j^2 <= 0 is what the division yields (NaN / inf).  With event discounts the pair's derivative
+ * carries the pair's discount (piecewise constant in z; undefined for a z exactly on a boundary).  Same preconditions
+ * and error codes as gogp_produce: m == 0 is OK, GOGP_ESTATE before anything is absorbed; with no observations
+ * mu = 0, sigma = sqrt(prior) and both derivative arrays are zero.  GOGP_EARG for a precision = 32 handle and for a
+ * sharded handle (the restriction of gogp_append).  Works in every state in which gogp_produce works and leaves the
+ * handle's state as it found it.  Two calls with the same arguments return bit-identical arrays. */
+int gogp_produce_gradient(gogp_handle *h, const double *Z, int64_t m, double *mu, double *sigma,
+                          double *dmu /* m x ndim */, double *dsigma /* m x ndim */);
 
 /* ---- cached state (gp.GP.L, gp.GP.Alpha: gp/gp.go:35-36,255-257) ---------- */
 int64_t gogp_n(const gogp_handle *h);
