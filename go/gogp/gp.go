@@ -16,6 +16,7 @@ import (
 	"fmt"
 	"math"
 	"runtime"
+	"sort"
 	"unsafe"
 )
 
@@ -266,6 +267,56 @@ func (gp *GP) Append(x [][]float64, y []float64) (err error) {
 	gp.Y = append(gp.Y[:len(gp.Y):len(gp.Y)], y...)
 	gp.dirty, gp.upN = false, len(gp.Y)
 	gp.upX, gp.upY = &gp.X[0], &gp.Y[0]
+	if err = gp.fetchState(); err != nil {
+		return err
+	}
+	return gp.err(rc)
+}
+
+// Remove removes the observations with the indices idx (any order, no duplicates) from the absorbed
+// ones (gogp_remove): the state Absorb on the kept rows would leave, without a new factorisation and
+// at the parameters of the last Absorb / Observe.  No reference counterpart; the counterpart of
+// Append, with which a bounded window slides: Remove([]int{0}), then Append(new).
+func (gp *GP) Remove(idx []int) (err error) {
+	gp.defaults()
+	s := make([]int64, len(idx))
+	for i, v := range idx {
+		s[i] = int64(v)
+	}
+	sort.Slice(s, func(a, b int) bool { return s[a] < s[b] })
+	for j, v := range s {
+		if v < 0 || v >= int64(len(gp.Y)) || (j > 0 && v == s[j-1]) {
+			return fmt.Errorf("gogp: Remove: index %d out of range or repeated", v)
+		}
+	}
+	if gp.changed() {
+		return fmt.Errorf("gogp: Remove: X / Y were assigned since the last Absorb / Observe; Absorb them")
+	}
+	if len(s) == 0 {
+		return nil
+	}
+	rc := C.gogp_remove(gp.handle(), (*C.int64_t)(unsafe.Pointer(&s[0])), C.int64_t(len(s)))
+	if rc != C.GOGP_OK && rc != C.GOGP_ECOND {
+		return gp.err(rc)
+	}
+	// the device holds the compacted data: X / Y follow without a new upload
+	k, j := 0, 0
+	X, Y := make([][]float64, 0, len(gp.Y)-len(s)), make([]float64, 0, len(gp.Y)-len(s))
+	for i := range gp.Y {
+		if j < len(s) && s[j] == int64(i) {
+			j++
+			continue
+		}
+		X, Y = append(X, gp.X[i]), append(Y, gp.Y[i])
+		k++
+	}
+	gp.X, gp.Y = X, Y
+	gp.dirty, gp.upN = false, k
+	if k > 0 {
+		gp.upX, gp.upY = &gp.X[0], &gp.Y[0]
+	} else {
+		gp.upX, gp.upY = nil, nil
+	}
 	if err = gp.fetchState(); err != nil {
 		return err
 	}

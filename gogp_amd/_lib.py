@@ -88,6 +88,7 @@ SYMBOLS = [
     ("gogp_get_factor_diag", ctypes.c_int, [_h, _dp]),
     ("gogp_set_factor", ctypes.c_int, [_h, _dp, _dp, _dp, _dp]),
     ("gogp_append", ctypes.c_int, [_h, _dp, _dp, ctypes.c_int64]),
+    ("gogp_remove", ctypes.c_int, [_h, ctypes.POINTER(_i64), ctypes.c_int64]),
     ("gogp_dist_grid", ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
     ("gogp_dist_unique_id", ctypes.c_int, [ctypes.c_void_p]),
     ("gogp_dist_init_rccl", ctypes.c_int,

@@ -112,6 +112,9 @@ static void free_n_buffers(gogp_handle *h) {
   (void)hipFree(h->app_ws);
   h->app_ws = nullptr;
   h->app_ws_bytes = 0;
+  (void)hipFree(h->rm_ws);
+  h->rm_ws = nullptr;
+  h->rm_ws_bytes = 0;
   (void)hipFree(h->TX);
   (void)hipFree(h->Tmt);
   h->TX = h->Tmt = nullptr;
@@ -2823,6 +2826,137 @@ extern "C" int gogp_append(gogp_handle *h, const double *X2, const double *y2, i
     for (double *p : {old.dX, old.dy, old.bufA, old.bufL, old.Dinv, old.z, old.w, old.alpha, old.gpart}) (void)hipFree(p);
     drop_cand_graph(h);
   }
+  h->hscal[6] = h->hscal[2];  // y^T alpha where judge_scalars looks for the quadratic term of a refined alpha
+  const long long zero = 0;
+  memcpy(h->hscal + HS_INFO, &zero, sizeof zero);
+  const FactorResult fr = judge_scalars(h, h->hscal, false, true);
+  h->lml = fr.lml;
+  h->yta = fr.yta;
+  h->cond_lb = fr.cond_lb;
+  h->notpd = -1;
+  h->factored = h->have_alpha = true;
+  h->observed = h->with_obs = h->grad_valid = h->have_kinv = h->trtri_done = false;
+  h->z_valid = true;
+  if (fr.rc == GOGP_ECOND) h->err = fr.msg;
+  return fr.rc;
+}
+
+// ---- remove ---------------------------------------------------------------------------------------
+// The observations idx[0] < ... < idx[m-1] leave the factored process (no reference counterpart; the counterpart of
+// gogp_append).  With kept = the other rows, Lt = L[kept, kept] is lower triangular with a positive diagonal and
+//   K[kept, kept] = Lt Lt^T + W W^T,  W = L[kept, idx]:
+// a gather and a rank-m update by Householder reflectors (remove.hip) -- a sum, so the result is positive definite by
+// construction: no GOGP_ENOTPD, no rollback.  Neither the similarity kernel nor theta is evaluated.
+// Launch sequence, all on the main stream: the gather of Lt into bufA at ld = npad(n - m) -- dead here as in gogp_append
+// -- and of X / y into the workspace; per pass of <= REMOVE_W columns of W (REMOVE_W_SMALL when m is that small) the
+// gather of those columns from the OLD factor, a snapshot of the diagonal 128-blocks, and one launch per 128-column
+// block from the block of the pass's first affected column; the block inverses from the first affected 256-block (all
+// of them when npad shrinks); z by the forward chain on the compacted y, alpha by the backward chain, the LML scalars;
+// one host copy, one synchronise.  The old factor is only read; the pointers are swapped at the end.
+// Measured (profiles/remove.txt): slower than gogp_set_data + gogp_absorb for removals from the front at
+// N = 4096 and for 64 rows at once at N = 16384; no automatic fallback.
+static int ensure_remove_ws(gogp_handle *h, size_t need) {
+  if (h->rm_ws && h->rm_ws_bytes >= need) return GOGP_OK;
+  (void)hipFree(h->rm_ws);
+  h->rm_ws = nullptr;
+  h->rm_ws_bytes = 0;
+  HIPCHK(h, hipMalloc(&h->rm_ws, need));
+  h->rm_ws_bytes = need;
+  return GOGP_OK;
+}
+
+extern "C" int gogp_remove(gogp_handle *h, const int64_t *idx, int64_t m) {
+  if (!h) return GOGP_EARG;
+  if (m < 0) return fail(h, GOGP_EARG, "remove: m < 0");
+  if (m == 0) return GOGP_OK;
+  if (!idx) return fail(h, GOGP_EARG, "remove: NULL");
+  if (h->prec == 32)
+    return fail(h, GOGP_EARG, "remove: not supported on a precision = 32 handle (the update is fp64 throughout)");
+  if (h->dist) return fail(h, GOGP_EARG, "remove: not supported on a sharded handle");
+  if (!h->have_data || h->n == 0 || !h->factored) return fail(h, GOGP_ESTATE, "remove: nothing absorbed");
+  const int64_t n0 = h->n, npad0 = h->npad;
+  for (int64_t j = 0; j < m; ++j) {
+    if (idx[j] < 0 || idx[j] >= n0) return fail(h, GOGP_EARG, "remove: index out of range");
+    if (j > 0 && idx[j] <= idx[j - 1]) return fail(h, GOGP_EARG, "remove: indices must be strictly increasing");
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  if (m == n0) {  // the empty process, at the parameters it had
+    const int rc = gogp_set_data(h, nullptr, nullptr, 0);
+    if (rc != GOGP_OK) return rc;
+    h->lml = 0.0;
+    h->with_obs = false;
+    h->z_valid = false;
+    h->notpd = -1;
+    return GOGP_OK;
+  }
+  // nothing of an earlier call may still run: an eager Observe's inverse reads bufL and writes bufA
+  for (hipStream_t q : work_streams(h)) HIPCHK(h, hipStreamSynchronize(q));
+  h->trtri_pending = h->alpha_pending = h->kinv_pending = false;
+  h->tinv_valid = h->tinv_pending = false;
+  h->ydone_valid = false;
+  h->kinv_c1 = 0;
+  h->have_kinv = false;  // bufA is written from here on
+  hipStream_t s = h->s;
+  const int D = h->D;
+  const int64_t n1 = n0 - m, npad1 = ((n1 + PANEL - 1) / PANEL) * PANEL, ld = npad1;
+  const bool restride = npad1 != npad0;
+  std::vector<int> hmap((size_t)(n1 + m));  // new index -> old index, then the removed rows
+  {
+    int64_t j = 0, k = 0;
+    for (int64_t i = 0; i < n0; ++i) {
+      if (j < m && idx[j] == i)
+        hmap[(size_t)(n1 + j++)] = (int)i;
+      else
+        hmap[(size_t)k++] = (int)i;
+    }
+  }
+  const size_t nints = (size_t)((n1 + m + 1) / 2) * 2;
+  const size_t need = nints * sizeof(int) +
+                      ((size_t)gogp::REMOVE_W * npad1 + (size_t)npad1 * TILE + (size_t)npad1 * (D + 1)) * sizeof(double);
+  int rc = ensure_remove_ws(h, need);
+  if (rc != GOGP_OK) return rc;
+  int *dmap = static_cast<int *>(h->rm_ws), *drem = dmap + n1;
+  double *W = reinterpret_cast<double *>(dmap + nints), *snap = W + (size_t)gogp::REMOVE_W * npad1;
+  double *Xt = snap + (size_t)npad1 * TILE, *yt = Xt + (size_t)npad1 * D;
+  double *Lold = h->bufL, *Lnew = h->bufA;
+  HIPCHK(h, hipMemcpyAsync(dmap, hmap.data(), (size_t)(n1 + m) * sizeof(int), hipMemcpyHostToDevice, s));
+  launch_remove_gather(s, Lold, npad0, dmap, n1, Lnew, npad1);
+  launch_remove_rows(s, h->dX, dmap, n1, D, Xt);
+  launch_remove_rows(s, h->dy, dmap, n1, 1, yt);
+  const int mw = m <= gogp::REMOVE_W_SMALL ? gogp::REMOVE_W_SMALL : gogp::REMOVE_W;
+  const int64_t first = std::min<int64_t>(idx[0], n1 - 1);  // the first column the call can change
+  for (int64_t off = 0; off < m; off += mw) {
+    const int mc = (int)std::min<int64_t>(mw, m - off);
+    const int64_t c0 = idx[off] - off;  // the first kept row behind the pass's first removed one, as a new index
+    if (c0 >= n1) break;                // the rest was behind every kept row: W is zero
+    const int64_t cb0 = (c0 / TILE) * TILE;
+    launch_remove_w(s, Lold, npad0, dmap, drem + off, mc, mw, cb0, n1, npad1, W);
+    launch_remove_snap(s, Lnew, ld, (int)(cb0 / TILE), (int)((n1 + TILE - 1) / TILE - cb0 / TILE), snap);
+    for (int64_t kb = cb0; kb < n1; kb += TILE) launch_remove_block(s, Lnew, ld, snap, W, mw, kb, n1);
+  }
+  // the data, compacted, and zero tails as gogp_set_data leaves them
+  HIPCHK(h, hipMemcpyAsync(h->dX, Xt, (size_t)n1 * D * sizeof(double), hipMemcpyDeviceToDevice, s));
+  HIPCHK(h, hipMemcpyAsync(h->dy, yt, (size_t)n1 * sizeof(double), hipMemcpyDeviceToDevice, s));
+  HIPCHK(h, hipMemsetAsync(h->dX + (size_t)n1 * D, 0, ((size_t)(npad0 - n1) * D + GOGP_MAX_NDIM) * sizeof(double), s));
+  HIPCHK(h, hipMemsetAsync(h->dy + n1, 0, (size_t)(npad0 - n1) * sizeof(double), s));
+  const int np1 = (int)(npad1 / PANEL);
+  const size_t blk = (size_t)PANEL * PANEL;
+  for (int b = restride ? 0 : (int)(first / PANEL); b < np1; ++b)
+    launch_diag256_inv_only(s, Lnew + (size_t)b * PANEL * (ld + 1), ld, h->Dinv + (size_t)b * blk);
+  const size_t vb1 = (size_t)npad1 * sizeof(double);
+  HIPCHK(h, hipMemcpyAsync(h->w, h->dy, vb1, hipMemcpyDeviceToDevice, s));
+  for (int b = 0; b < np1; ++b) launch_trsv_fwd_step(s, Lnew, ld, h->Dinv, b, np1, h->w, h->z);
+  HIPCHK(h, hipMemcpyAsync(h->w, h->z, vb1, hipMemcpyDeviceToDevice, s));
+  for (int b = np1 - 1; b >= 0; --b) launch_trsv_bwd_step(s, Lnew, ld, h->Dinv, b, np1, h->w, h->alpha);
+  launch_lml_scalars(s, Lnew, ld, h->z, h->dy, h->alpha, n1, h->scalars);
+  HIPCHK(h, hipMemcpyAsync(h->hscal, h->scalars, 7 * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipStreamSynchronize(s));
+  HIPCHK(h, hipGetLastError());
+  h->bufL = Lnew;
+  h->bufA = Lold;
+  h->n = n1;
+  h->npad = npad1;
+  h->nblk = (int)(npad1 / TILE);
   h->hscal[6] = h->hscal[2];  // y^T alpha where judge_scalars looks for the quadratic term of a refined alpha
   const long long zero = 0;
   memcpy(h->hscal + HS_INFO, &zero, sizeof zero);

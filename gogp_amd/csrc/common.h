@@ -387,6 +387,23 @@ void launch_append_identity_rows(hipStream_t s, double *L, int64_t ld, int64_t r
 // dst (npad1 rows, ld1) := src (npad0 rows, ld0) on the 256-blocks of the lower triangle, identity on the new ones
 void launch_append_restride(hipStream_t s, const double *src, int64_t ld0, int64_t npad0, double *dst, int64_t ld1,
                             int64_t npad1);
+// remove.hip: the kernels of gogp_remove (api.hip) -- n - n1 rows leave a factor; map[i] (i < n1) is the old index of new
+// row i, rem[j] the old index of removed row j.
+// launch_remove_gather: dst (npad1 rows, ld npad1) := src[map, map] on the lower triangle, zero above it inside the
+// diagonal 256-blocks, identity on the padding.  launch_remove_rows: dst[i] := src[map[i]] for rows of `width` doubles.
+// launch_remove_w: W (mw columns of npad1 doubles each, column-major) := src[map, rem[0 .. mc)] for the rows r0 <= i < npad1,
+// zero above the diagonal of src, on the padding and in the columns mc <= j < mw.
+// launch_remove_snap: snap[b] := the diagonal 128-block b of L, b0 <= b < b0 + nb.
+// launch_remove_block: the rank-mw update of columns kb .. kb + 127 (kb a multiple of 128) of L by W, whose rows < kb
+// are not read; the rows kb .. of W are consumed, the ones below the block updated.  mw: REMOVE_W_SMALL or REMOVE_W.
+constexpr int REMOVE_W = 32, REMOVE_W_SMALL = 4;
+void launch_remove_gather(hipStream_t s, const double *src, int64_t ld0, const int *map, int64_t n1, double *dst,
+                          int64_t npad1);
+void launch_remove_rows(hipStream_t s, const double *src, const int *map, int64_t n1, int width, double *dst);
+void launch_remove_w(hipStream_t s, const double *src, int64_t ld0, const int *map, const int *rem, int mc, int mw, int64_t r0,
+                     int64_t n1, int64_t npad1, double *W);
+void launch_remove_snap(hipStream_t s, const double *L, int64_t ld, int b0, int nb, double *snap);
+void launch_remove_block(hipStream_t s, double *L, int64_t ld, const double *snap, double *W, int mw, int64_t kb, int64_t n1);
 void launch_fill(hipStream_t s, double *p, int64_t count, double v);
 void launch_axpy(hipStream_t s, double *a, const double *b, int64_t count);  // a += b
 void launch_dot(hipStream_t s, const double *a, const double *b, int64_t n, double *out);  // out[0] = a.b

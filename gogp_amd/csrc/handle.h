@@ -185,6 +185,8 @@ struct gogp_handle : EvalBufs, EvalState {
   bool z_valid = false;     // z = L^-1 y of the current factor is in `z` (not after gogp_set_factor, which stores none)
   void *app_ws = nullptr;   // gogp_append: the saved block inverse + the partial sums of its Gram kernel (append.hip)
   size_t app_ws_bytes = 0;
+  void *rm_ws = nullptr;    // gogp_remove: index maps, a pass's columns of W, the diagonal-block snapshot, compacted X / y (remove.hip)
+  size_t rm_ws_bytes = 0;
   double yta = 0.0;      // y^T alpha of the last factorisation (fp32 path: of the refined alpha)
   int trace_fp64 = 1;    // fp32 path: tr(alpha alpha^T - K^-1) summed in fp64 from Y, scale component by its identity
   double cond_limit = 1e16;  // gonum's mat.ConditionTolerance

@@ -16,6 +16,7 @@ All arithmetic runs on the GPU through libgogp_hip.so; there is no CPU path.
 from __future__ import annotations
 
 import ctypes
+import operator
 from typing import List, Optional, Sequence
 
 import numpy as np
@@ -201,6 +202,33 @@ class GP:
         if rc in (_lib.GOGP_OK, _lib.GOGP_ECOND):  # stored (GOGP_ECOND: and reported, as Absorb)
             self._X = np.concatenate([self._X.reshape(-1, self.NDim), xa])
             self._Y = np.concatenate([self._Y, ya])
+            self._with_obs = False
+        self._check(rc)
+
+    def Remove(self, idx) -> None:
+        """Remove the observations with the indices ``idx`` (any iterable of ints; sorted here) from the absorbed
+        ones (gogp_remove): the state Absorb on the kept rows, in their order, would leave, without a new
+        factorisation and at the parameters of the last Absorb / Observe / restore.  The counterpart of Append; with
+        it a bounded window slides: ``Remove([0])``, then ``Append(new)``.  Duplicates and indices outside
+        ``[0, len(Y))`` raise ValueError before the library is called."""
+        ia = sorted(operator.index(i) for i in idx)
+        n = len(self._Y)
+        if any(i < 0 or i >= n for i in ia):
+            raise ValueError("Remove: index out of range")
+        if any(a == b for a, b in zip(ia, ia[1:])):
+            raise ValueError("Remove: duplicate index")
+        if self._data_dirty:
+            # the device no longer holds X / Y: nothing there to remove from
+            raise GogpError(_lib.GOGP_ESTATE, "Remove: X / Y were assigned since the last Absorb / Observe; Absorb them")
+        if not ia:
+            return
+        arr = np.ascontiguousarray(ia, dtype=np.int64)
+        rc = _lib.lib().gogp_remove(self._h, arr.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), len(arr))
+        if rc in (_lib.GOGP_OK, _lib.GOGP_ECOND):  # stored (GOGP_ECOND: and reported, as Absorb)
+            keep = np.ones(n, dtype=bool)
+            keep[arr] = False
+            self._X = np.ascontiguousarray(self._X.reshape(-1, self.NDim)[keep])
+            self._Y = np.ascontiguousarray(self._Y[keep])
             self._with_obs = False
         self._check(rc)
 

@@ -13,7 +13,9 @@
 // after every Absorb / Observe, L lazily by Factor() (the reference documents L, Alpha, X,
 // ThetaSimil, ThetaNoise as the state Produce depends on: gp/gp.go:35-36,255-257).
 #pragma once
+#include <algorithm>
 #include <cmath>
+#include <cstdint>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -82,6 +84,37 @@ class GP {
     if (rc != GOGP_OK && rc != GOGP_ECOND) return rc;
     X.insert(X.end(), x.begin(), x.end());
     Y.insert(Y.end(), y.begin(), y.end());
+    const int ra = fetch_alpha();
+    return ra != GOGP_OK ? ra : rc;
+  }
+
+  // Remove the observations idx (any order, no duplicates) from the absorbed ones (gogp_remove; no reference
+  // counterpart): the state Absorb on the kept rows would leave, without a new factorisation.  With Append a bounded
+  // window slides: Remove({0}), then Append(new).  GOGP_EARG (duplicates, out of range): nothing changed.
+  // GOGP_ESTATE: X / Y were re-assigned since the last upload (Absorb them instead).
+  int Remove(const std::vector<int64_t> &idx) {
+    std::vector<int64_t> s(idx);
+    std::sort(s.begin(), s.end());
+    for (size_t j = 0; j < s.size(); ++j)
+      if (s[j] < 0 || s[j] >= (int64_t)Y.size() || (j > 0 && s[j] == s[j - 1])) return GOGP_EARG;
+    if (dirty_) return GOGP_ESTATE;
+    if (s.empty()) return GOGP_OK;
+    const int rc = gogp_remove(h_, s.data(), (int64_t)s.size());
+    if (rc != GOGP_OK && rc != GOGP_ECOND) return rc;
+    size_t k = 0, j = 0;
+    for (size_t i = 0; i < Y.size(); ++i) {
+      if (j < s.size() && s[j] == (int64_t)i) {
+        ++j;
+        continue;
+      }
+      if (k != i) {
+        X[k] = std::move(X[i]);
+        Y[k] = Y[i];
+      }
+      ++k;
+    }
+    X.resize(k);
+    Y.resize(k);
     const int ra = fetch_alpha();
     return ra != GOGP_OK ? ra : rc;
   }

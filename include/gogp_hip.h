@@ -334,6 +334,30 @@ int gogp_set_factor(gogp_handle *h, const double *theta_simil,
  * gogp_notpd_index is the global index of the failing pivot.  GOGP_ECOND: stored and reported, as Absorb. */
 int gogp_append(gogp_handle *h, const double *X2 /* m x ndim */, const double *y2 /* m */, int64_t m);
 
+/* Remove the observations idx[0] < idx[1] < ... < idx[m-1] from the factored process: afterwards the handle is in
+ * the state gogp_absorb on the kept rows, in their original order, would leave -- gogp_n = n - m, the device-side X / y
+ * compacted, factor, alpha, LML and the block inverses of Produce in place (gogp_produce, gogp_produce_gradient,
+ * gogp_append, gogp_get_factor* and gogp_get_alpha work; no gradient: gogp_gradient returns GOGP_ESTATE as after
+ * Absorb, and a stored K^-1 is invalidated) -- in O(n^2 m) work: a gather of the kept rows and columns of the factor
+ * and a rank-m update of it by orthogonal (Householder) transformations, ceil(m / 32) passes over the trailing factor.
+ * The counterpart of gogp_append; no reference counterpart (the reference refactorises: tutorial/tutorial.go:118-142).
+ * Neither the similarity kernel nor the parameters are evaluated: theta stays that of the last Absorb / Observe /
+ * set_factor, and the call works after each of them and after gogp_append alike, with or without event discounts.
+ * The kept matrix is positive definite by construction (a sum, never a downdate): there is no GOGP_ENOTPD.  Rows of
+ * the factor above idx[0] keep their bits.  Batch data, the candidates arena and event discounts are untouched.  Two
+ * identical call sequences return bit-identical factors.
+ * m == 0: nothing happens.  m == n: the empty process (gogp_n = 0, LML 0, Produce: mu = 0, sigma = sqrt(prior); a
+ * following gogp_append absorbs).
+ * GOGP_EARG: idx == NULL with m > 0, an index outside [0, n), indices not strictly increasing, a precision = 32
+ * handle, a sharded handle (the restrictions of gogp_append); the handle is exactly as it was.  GOGP_ESTATE: not
+ * factored.  GOGP_ECOND: stored and reported, as Absorb ((max L_ii / min L_ii)^2 against cond_limit_log10).
+ * Measured on one MI355X (profiles/remove.txt, D = 8): at N = 16384 one row from the front 20 ms, one from the middle
+ * 12 ms, the last 4.5 ms against 31 ms for gogp_set_data + gogp_absorb of the kept rows.  SLOWER than refactorising,
+ * and there is no automatic fallback: the first 64 rows at N = 16384 (52 ms against 31; the first 16: 30 against 31),
+ * and at N = 4096 every removal from the front (1 / 16 / 64 rows: 4.7 / 7.2 / 12.6 ms against 2.9).  The cost is one
+ * dependent launch per 128 columns behind the first removed row, per pass of 32 removed rows. */
+int gogp_remove(gogp_handle *h, const int64_t *idx /* m, strictly increasing */, int64_t m);
+
 /* ---- one evaluation sharded over several GPUs: 2-D block-cyclic ---------------------
  * One process per GPU.  The ranks form a Pr x Pc process grid (rank = pr*Pc + pc; Pr must
  * divide Pc: 1x1, 1x2, 2x2, 2x4 for 1/2/4/8 GPUs, gogp_dist_grid).  The Gram matrix is cut into
