@@ -382,6 +382,49 @@ func (gp *GP) ProduceGradient(x [][]float64) (mu, sigma, dmu, dsigma []float64, 
 	return mu, sigma, dmu, dsigma, nil
 }
 
+// ProduceCovariance computes the predicted means and the joint covariance of
+// the latent function at the test points: cov[i*m+j], symmetric, no noise term
+// (no reference counterpart).
+func (gp *GP) ProduceCovariance(x [][]float64) (mu, cov []float64, err error) {
+	gp.defaults()
+	m := len(x)
+	flat := make([]float64, m*gp.NDim)
+	for i, row := range x {
+		copy(flat[i*gp.NDim:], row)
+	}
+	mu, cov = make([]float64, m), make([]float64, m*m)
+	if err = gp.err(C.gogp_produce_covariance(gp.handle(), dptr(flat), C.int64_t(m), dptr(mu), dptr(cov))); err != nil {
+		return nil, nil, err
+	}
+	return mu, cov, nil
+}
+
+// Sample draws len(xi)/len(x) joint samples at the test points from the
+// caller's standard normals xi (row-major ns x m): samples[s*m+j] =
+// mu[j] + (C xi[s])[j], C the lower Cholesky factor of the covariance +
+// diagAdd I (no reference counterpart).
+func (gp *GP) Sample(x [][]float64, xi []float64, diagAdd float64) (samples []float64, err error) {
+	gp.defaults()
+	m := len(x)
+	ns := 0
+	if m > 0 {
+		ns = len(xi) / m
+		if ns*m != len(xi) {
+			return nil, fmt.Errorf("gogp: len(xi) = %d is no multiple of %d test points", len(xi), m)
+		}
+	}
+	flat := make([]float64, m*gp.NDim)
+	for i, row := range x {
+		copy(flat[i*gp.NDim:], row)
+	}
+	mu := make([]float64, m)
+	samples = make([]float64, ns*m)
+	if err = gp.err(C.gogp_produce_samples(gp.handle(), dptr(flat), C.int64_t(m), dptr(xi), C.int64_t(ns), C.double(diagAdd), dptr(mu), dptr(samples))); err != nil {
+		return nil, err
+	}
+	return samples, nil
+}
+
 // Observe computes the log marginal likelihood of log-transformed
 // hyperparameters [, inputs, outputs] (gp/gp.go:374-413).  Panics where the
 // reference panics.

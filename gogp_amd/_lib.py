@@ -19,6 +19,7 @@ HOOKS_PATH = os.path.join(_HERE, "libgogp_testhooks.so")
 GOGP_OK, GOGP_EARG, GOGP_ENOTPD, GOGP_EHIP, GOGP_ESTATE, GOGP_ENOMEM, GOGP_ECOND = 0, 1, 2, 3, 4, 5, 6
 GOGP_MAX_CANDIDATES = 16
 GOGP_BATCH_MAX_N = 128
+GOGP_COV_MAX_M = 4096
 
 #: every symbol include/gogp_hip.h declares: (name, restype, argtypes)
 _dp = ctypes.POINTER(ctypes.c_double)
@@ -81,6 +82,8 @@ SYMBOLS = [
       ctypes.POINTER(ctypes.c_int)]),
     ("gogp_produce", ctypes.c_int, [_h, _dp, _i64, _dp, _dp]),
     ("gogp_produce_gradient", ctypes.c_int, [_h, _dp, _i64, _dp, _dp, _dp, _dp]),
+    ("gogp_produce_covariance", ctypes.c_int, [_h, _dp, _i64, _dp, _dp]),
+    ("gogp_produce_samples", ctypes.c_int, [_h, _dp, _i64, _dp, _i64, ctypes.c_double, _dp, _dp]),
     ("gogp_n", _i64, [_h]),
     ("gogp_get_alpha", ctypes.c_int, [_h, _dp]),
     ("gogp_get_factor", ctypes.c_int, [_h, _dp]),

@@ -162,9 +162,10 @@ static void free_m_buffers(gogp_handle *h) {
   (void)hipFree(h->Vt);
   (void)hipFree(h->pvec);
   (void)hipFree(h->pg_ws);
-  h->dZ = h->KsT = h->Vt = h->pvec = h->pg_ws = nullptr;
+  (void)hipFree(h->pc_ws);
+  h->dZ = h->KsT = h->Vt = h->pvec = h->pg_ws = h->pc_ws = nullptr;
   h->cap_m = h->cap_mp_npad = 0;
-  h->pg_ws_doubles = 0;
+  h->pg_ws_doubles = h->pc_ws_doubles = 0;
 }
 
 // ---- stream sets ------------------------------------------------------------------------
@@ -2420,6 +2421,171 @@ extern "C" int gogp_produce_gradient(gogp_handle *h, const double *Z, int64_t m,
   HIPCHK(h, hipMemcpyAsync(dsigma_out, ddsig, md * sizeof(double), hipMemcpyDeviceToHost, s));
   HIPCHK(h, hipStreamSynchronize(s));
   HIPCHK(h, hipGetLastError());
+  return GOGP_OK;
+}
+
+// ---- joint predictive covariance and posterior samples ----------------------------------------------
+// Both calls: Produce's tile route for every m (it leaves V^T in Vt row by row, as gogp_produce_gradient needs it), then
+// the split-K product Vt Vt^T and its finalising kernel (pcov.hip) on the main stream.  Workspace pc_ws, grown on demand:
+//   covariance:  part | cov (m x m)
+//   samples:     part | S = cov + diag_add I, identity-padded to mp = a multiple of 256 | C, its lower factor | one
+//                block inverse | xi, zero-padded to nsp x mp (nsp a multiple of 128) | xi C^T | samples (ns x m) | pivot word
+static int ensure_pc_ws(gogp_handle *h, size_t need) {
+  if (!h->pc_ws || h->pc_ws_doubles < need) {
+    (void)hipFree(h->pc_ws);
+    h->pc_ws = nullptr;
+    h->pc_ws_doubles = 0;
+    HIPCHK(h, hipMalloc(&h->pc_ws, need * sizeof(double)));
+    h->pc_ws_doubles = need;
+  }
+  return GOGP_OK;
+}
+// doubles of the SYRK's partial tiles for m test points on the current factor
+static size_t pcov_part_doubles(gogp_handle *h, int64_t m) {
+  if (h->n == 0) return 0;
+  const size_t tiles = (size_t)((m + 63) / 64), pairs = tiles * (tiles + 1) / 2;
+  return (size_t)gogp::pcov_slabs(h->npad, m, h->ncu, nullptr) * pairs * 4096;
+}
+// What the two calls share, up to the point where the handle's buffers are in place: arguments, state, sizes
+static int pcov_prepare(gogp_handle *h, const char *who, int64_t m, int64_t *mpad) {
+  char buf[160];
+  if (h->prec == 32) {
+    snprintf(buf, sizeof buf, "%s: precision = 32 handles are not supported", who);
+    return fail(h, GOGP_EARG, buf);
+  }
+  if (h->dist) {
+    snprintf(buf, sizeof buf, "%s: sharded handles are not supported", who);
+    return fail(h, GOGP_EARG, buf);
+  }
+  if (m > GOGP_COV_MAX_M) {
+    snprintf(buf, sizeof buf, "%s: more than GOGP_COV_MAX_M = %d test points", who, GOGP_COV_MAX_M);
+    return fail(h, GOGP_EARG, buf);
+  }
+  if (m == 0) return GOGP_OK;
+  if (h->n > 0 && !h->factored) {
+    snprintf(buf, sizeof buf, "%s: nothing absorbed", who);
+    return fail(h, GOGP_ESTATE, buf);
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  if (h->ncu <= 0) {
+    HIPCHK(h, hipDeviceGetAttribute(&h->ncu, hipDeviceAttributeMultiprocessorCount, h->device));
+    if (h->ncu <= 0) h->ncu = 1;
+  }
+  *mpad = ((m + TILE - 1) / TILE) * TILE;
+  return ensure_m(h, m, *mpad);
+}
+// Z up, the mean into pvec + mpad and V^T into Vt (n == 0: the mean is zero and there is no V)
+static int pcov_forward(gogp_handle *h, const double *Z, int64_t m, int64_t mpad) {
+  hipStream_t s = h->s;
+  double *dmu = h->pvec + mpad, *dq = h->pvec + 2 * mpad;
+  if (h->n == 0) {
+    const int rc = gogp_upload_params(h);  // no observations: parameters may not have been uploaded yet
+    if (rc != GOGP_OK) return rc;
+  }
+  HIPCHK(h, hipMemcpyAsync(h->dZ, Z, (size_t)m * h->D * sizeof(double), hipMemcpyHostToDevice, s));
+  if (h->n == 0) {
+    HIPCHK(h, hipMemsetAsync(dmu, 0, (size_t)m * sizeof(double), s));
+    return GOGP_OK;
+  }
+  const int rc = ensure_alpha(h);
+  if (rc != GOGP_OK) return rc;
+  produce_solve_t<double>(h, s, m, mpad, dmu, dq);
+  return GOGP_OK;
+}
+
+extern "C" int gogp_produce_covariance(gogp_handle *h, const double *Z, int64_t m, double *mu, double *cov) {
+  if (!h || m < 0 || (m > 0 && (!Z || !mu || !cov))) return fail(h, GOGP_EARG, "produce_covariance: NULL");
+  int64_t mpad = 0;
+  int rc = pcov_prepare(h, "produce_covariance", m, &mpad);
+  if (rc != GOGP_OK || m == 0) return rc;
+  const size_t npart = pcov_part_doubles(h, m), mm = (size_t)m * m;
+  rc = ensure_pc_ws(h, npart + mm);
+  if (rc != GOGP_OK) return rc;
+  double *part = h->pc_ws, *dcov = part + npart;
+  hipStream_t s = h->s;
+  rc = pcov_forward(h, Z, m, mpad);
+  if (rc != GOGP_OK) return rc;
+  launch_pcov(s, h->devP, h->dZ, m, h->n > 0 ? h->Vt : nullptr, h->npad, h->npad, h->ncu, part, 0.0, dcov, m, m, h->ev());
+  HIPCHK(h, hipMemcpyAsync(mu, h->pvec + mpad, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipMemcpyAsync(cov, dcov, mm * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipStreamSynchronize(s));
+  HIPCHK(h, hipGetLastError());
+  return GOGP_OK;
+}
+
+extern "C" int gogp_produce_samples(gogp_handle *h, const double *Z, int64_t m, const double *xi, int64_t ns,
+                                    double diag_add, double *mu, double *samples) {
+  if (!h || m < 0 || ns < 0 || (m > 0 && (!Z || !mu)) || (m > 0 && ns > 0 && (!xi || !samples)))
+    return fail(h, GOGP_EARG, "produce_samples: NULL");
+  if (!(diag_add >= 0.0) || !std::isfinite(diag_add))
+    return fail(h, GOGP_EARG, "produce_samples: diag_add must be finite and not negative");
+  int64_t mpad = 0;
+  int rc = pcov_prepare(h, "produce_samples", m, &mpad);
+  if (rc != GOGP_OK || m == 0) return rc;
+  for (int64_t i = 0; i < ns * m; ++i)
+    if (!std::isfinite(xi[i])) return fail(h, GOGP_EARG, "produce_samples: xi contains a value that is not finite");
+  hipStream_t s = h->s;
+  double *dmu = h->pvec + mpad;
+  if (ns == 0) {  // the mean alone
+    rc = pcov_forward(h, Z, m, mpad);
+    if (rc != GOGP_OK) return rc;
+    HIPCHK(h, hipMemcpyAsync(mu, dmu, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    HIPCHK(h, hipGetLastError());
+    return GOGP_OK;
+  }
+  const int64_t mp = ((m + PANEL - 1) / PANEL) * PANEL, nsp = ((ns + TILE - 1) / TILE) * TILE;
+  const size_t npart = pcov_part_doubles(h, m), mm = (size_t)mp * mp, nx = (size_t)nsp * mp;
+  rc = ensure_pc_ws(h, npart + 2 * mm + (size_t)PANEL * PANEL + 2 * nx + (size_t)ns * m + 1);
+  if (rc != GOGP_OK) return rc;
+  double *part = h->pc_ws, *S = part + npart, *C = S + mm, *Dp = C + mm, *dxi = Dp + (size_t)PANEL * PANEL,
+         *G = dxi + nx, *dsamp = G + nx;
+  long long *info = reinterpret_cast<long long *>(dsamp + (size_t)ns * m);
+  rc = pcov_forward(h, Z, m, mpad);
+  if (rc != GOGP_OK) return rc;
+  launch_pcov(s, h->devP, h->dZ, m, h->n > 0 ? h->Vt : nullptr, h->npad, h->npad, h->ncu, part, diag_add, S, mp, mp, h->ev());
+  // S = C C^T, right-looking in 256-panels on the main stream: the diagonal block and its inverse, the panel under it
+  // through that inverse, the trailing lower tiles (the factorisation's chain_split = 0 form; m <= 4096: <= 16 panels)
+  HIPCHK(h, hipMemsetAsync(C, 0, mm * sizeof(double), s));
+  HIPCHK(h, hipMemsetAsync(info, 0, sizeof(long long), s));
+  for (int64_t c0 = 0; c0 < mp; c0 += PANEL) {
+    const int64_t c2 = c0 + PANEL;
+    launch_diag256(s, S + c0 * mp + c0, mp, C + c0 * mp + c0, mp, Dp, c0, m, info);
+    const int mt2 = (int)((mp - c2) / TILE);
+    if (mt2 > 0) {
+      GemmGrid gtri;
+      gtri.ktri = h->ktri;
+      launch_gemm_nt(s, GEMM_RECT, mt2, 2, PANEL, 1.0, S + c2 * mp + c0, mp, Dp, PANEL, 0.0, C + c2 * mp + c0, mp, nullptr,
+                     &gtri);
+      launch_gemm_nt(s, GEMM_LOWER, mt2, mt2, PANEL, -1.0, C + c2 * mp + c0, mp, C + c2 * mp + c0, mp, 1.0,
+                     S + c2 * mp + c2, mp, nullptr);
+    }
+  }
+  long long *hinfo = reinterpret_cast<long long *>(h->hscal + 12);  // a staging word of this call's own: HS_INFO keeps K's
+  HIPCHK(h, hipMemcpyAsync(hinfo, info, sizeof(long long), hipMemcpyDeviceToHost, s));
+  // samples = mu + xi C^T: xi up in one copy, one product (B = C as stored: zero above the diagonal), samples down in one
+  HIPCHK(h, hipMemsetAsync(dxi, 0, nx * sizeof(double), s));
+  HIPCHK(h, hipMemcpy2DAsync(dxi, (size_t)mp * sizeof(double), xi, (size_t)m * sizeof(double), (size_t)m * sizeof(double),
+                             (size_t)ns, hipMemcpyHostToDevice, s));
+  GemmGrid gx;
+  gx.ktri = h->ktri;
+  gx.small_below = h->produce_small_below;
+  launch_gemm_nt(s, GEMM_RECT, (int)(nsp / TILE), (int)(mp / TILE), mp, 1.0, dxi, mp, C, mp, 0.0, G, mp, nullptr, &gx);
+  launch_pcov_add_mu(s, G, mp, dmu, ns, m, dsamp);
+  HIPCHK(h, hipMemcpyAsync(mu, dmu, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipStreamSynchronize(s));
+  HIPCHK(h, hipGetLastError());
+  if (*hinfo != 0) {  // nothing is written to samples; the fitted process is untouched
+    char buf[200];
+    h->notpd = (int64_t)*hinfo - 1;
+    snprintf(buf, sizeof buf,
+             "produce_samples: the predictive covariance (+ diag_add) of the test points is not positive definite "
+             "(pivot %lld of the test points)", (long long)h->notpd);
+    h->err = buf;
+    return GOGP_ENOTPD;
+  }
+  HIPCHK(h, hipMemcpyAsync(samples, dsamp, (size_t)ns * m * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipStreamSynchronize(s));
   return GOGP_OK;
 }
 

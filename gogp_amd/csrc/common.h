@@ -293,6 +293,16 @@ int pgrad_slabs(int64_t npad, int64_t m, int *tiles_per_slab);
 void launch_pgrad(hipStream_t s, const DevParams *p, int ndim, const double *X, int64_t n, int64_t npad,
                   const double *Z, int64_t m, const double *alpha, const double *Wt, int64_t ld, const double *sigma,
                   double *part, double *dmu, double *dsigma, bool ev);
+// pcov.hip (gogp_produce_covariance, gogp_produce_samples).  launch_pcov: out (mo x mo, ldo; mo >= m) = k(Z, Z) - Vt Vt^T
+// on its leading m x m (+ diag_add on the diagonal), both triangles from the same value, identity on the rest; Vt: m rows
+// (one test point each) of npad columns, nullptr = no observations.  part: pcov_slabs(...) * pairs * 4096 doubles of
+// scratch, pairs = t (t + 1) / 2 with t = ceil(m / 64).  pcov_slabs: the split of the npad columns over workgroups for
+// `ncu` compute units (a slab is a whole number of 256-column panels).
+int pcov_slabs(int64_t npad, int64_t m, int ncu, int *cols_per_slab);
+void launch_pcov(hipStream_t s, const DevParams *p, const double *Z, int64_t m, const double *Vt, int64_t ld,
+                 int64_t npad, int ncu, double *part, double diag_add, double *out, int64_t mo, int64_t ldo, bool ev);
+// out (ns x m, compact) = mu (broadcast over the rows) + G (ns rows of ldg doubles)
+void launch_pcov_add_mu(hipStream_t s, const double *G, int64_t ldg, const double *mu, int64_t ns, int64_t m, double *out);
 int grad_reduce_blocks(int64_t npad);
 
 // fused gradient reduction over lower tiles of Kinv; out: NACC doubles

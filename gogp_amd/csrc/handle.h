@@ -91,6 +91,9 @@ struct gogp_handle : EvalBufs, EvalState {
   int64_t cap_m = 0, cap_mp_npad = 0;
   double *pg_ws = nullptr;     // gogp_produce_gradient: partial sums of pgrad_kernel + the two derivative arrays
   size_t pg_ws_doubles = 0;
+  double *pc_ws = nullptr;     // gogp_produce_covariance / gogp_produce_samples: the SYRK's partial tiles, the covariance,
+  size_t pc_ws_doubles = 0;    // and for samples its factor, a block inverse, xi, the product and the pivot word (pcov.hip)
+  int ncu = 0;                 // compute units of the device (0: not asked yet): the slab policy of pcov.hip
   hipStream_t s = nullptr;   // main stream: Gram, big trailing updates, reductions
   hipStream_t sp = nullptr;  // panel stream (high priority): diagonal blocks, TRSM-as-GEMM,
                              // skinny updates, substitution steps -- overlaps the big updates

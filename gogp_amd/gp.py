@@ -267,6 +267,56 @@ class GP:
                                                          _dp(dsigma)))
         return mu, sigma, dmu, dsigma
 
+    def _test_points(self, x) -> np.ndarray:
+        z = _arr(x)
+        if z.ndim == 2 and z.shape[1] != self.NDim:
+            raise ValueError("test points have %d columns, the GP has NDim = %d" % (z.shape[1], self.NDim))
+        return z.reshape(-1, self.NDim)
+
+    def ProduceCovariance(self, x):
+        """(mu, cov): Produce's mu and the joint covariance of the latent function at the m test
+        points, cov = k(Z, Z) - Kstar^T K^-1 Kstar (m x m, exactly symmetric, no noise term:
+        sqrt(diag(cov)) is Produce's sigma to rounding).  No reference counterpart: gp.GP.Produce
+        keeps the diagonal only.  At most GOGP_COV_MAX_M points; fp64, unsharded handles only."""
+        z = self._test_points(x)
+        m = len(z)
+        mu, cov = np.zeros(m), np.zeros((m, m))
+        if m:
+            if self._data_dirty and len(self._Y) == 0:
+                self._push_data()
+            self._check(_lib.lib().gogp_produce_covariance(self._h, _dp(z), m, _dp(mu), _dp(cov)))
+        return mu, cov
+
+    def Sample(self, x, ns: int = 1, rng=None, xi=None, diag_add: float = 0.0) -> np.ndarray:
+        """ns joint draws (ns x m) at the m test points: mu + C xi with C the lower Cholesky factor
+        of ProduceCovariance(x)'s cov + diag_add I.  diag_add = 0 draws the latent function, the
+        noise variance draws noisy observations, a small value is jitter where cov is numerically
+        singular.  xi: the standard normals to use (ns x m); drawn on the host from `rng`
+        (default np.random.default_rng()) when None.  Raises FactorizeError (pivot = index among
+        the test points) when cov + diag_add I is not positive definite."""
+        z = self._test_points(x)
+        m = len(z)
+        if xi is None:
+            ns = int(ns)
+            if ns < 0:
+                raise ValueError("ns < 0")
+            xi = (np.random.default_rng() if rng is None else rng).standard_normal((ns, m))
+        else:
+            xi = _arr(xi)
+            if xi.ndim == 1 and m > 0 and xi.size == m:
+                xi = xi.reshape(1, m)
+            if xi.ndim != 2 or xi.shape[1] != m:
+                raise ValueError("xi must have shape (ns, %d), not %r" % (m, xi.shape))
+            ns = xi.shape[0]
+        xi = np.ascontiguousarray(xi, dtype=np.float64)
+        mu, out = np.zeros(m), np.zeros((ns, m))
+        if m:
+            if self._data_dirty and len(self._Y) == 0:
+                self._push_data()
+            self._check(_lib.lib().gogp_produce_samples(self._h, _dp(z), m, _dp(xi), ns, float(diag_add), _dp(mu),
+                                                        _dp(out)))
+        return out
+
     # ---- gp.GP.Observe (gp/gp.go:374-413) ---------------------------------------------
     def Observe(self, x) -> float:
         """x = log-transformed hyperparameters [| inputs | outputs].  Raises where

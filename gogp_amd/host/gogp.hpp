@@ -156,6 +156,28 @@ class GP {
                                  dsigma.data()) == GOGP_OK;
   }
 
+  // mu and the joint covariance of the latent function at the test points (row-major x.size() x x.size(), symmetric);
+  // no reference counterpart
+  bool ProduceCovariance(const std::vector<std::vector<double>> &x, std::vector<double> &mu, std::vector<double> &cov) {
+    std::vector<double> flat = pack(x);
+    mu.assign(x.size(), 0.0);
+    cov.assign(x.size() * x.size(), 0.0);
+    return gogp_produce_covariance(h_, flat.data(), (int64_t)x.size(), mu.data(), cov.data()) == GOGP_OK;
+  }
+
+  // ns = xi.size() / x.size() joint draws mu + C xi[s] (row-major ns x x.size()) from the caller's standard normals,
+  // C the lower Cholesky factor of the covariance + diag_add I; no reference counterpart
+  bool Sample(const std::vector<std::vector<double>> &x, const std::vector<double> &xi, double diag_add,
+              std::vector<double> &mu, std::vector<double> &samples) {
+    std::vector<double> flat = pack(x);
+    const size_t m = x.size(), ns = m ? xi.size() / m : 0;
+    if (m && ns * m != xi.size()) throw Error(GOGP_EARG, "len(xi)");
+    mu.assign(m, 0.0);
+    samples.assign(ns * m, 0.0);
+    return gogp_produce_samples(h_, flat.data(), (int64_t)m, xi.data(), (int64_t)ns, diag_add, mu.data(),
+                                samples.data()) == GOGP_OK;
+  }
+
   // gp/gp.go:374-413
   double Observe(const std::vector<double> &x) {
     const size_t P = ThetaSimil.size() + ThetaNoise.size();
