@@ -92,29 +92,17 @@ extern "C" int64_t gogp_n(const gogp_handle *h) { return h ? h->n : 0; }
 
 // ---- lifecycle ---------------------------------------------------------------------
 static void free_n_buffers(gogp_handle *h) {
-  (void)hipFree(h->dX);
-  (void)hipFree(h->dy);
-  (void)hipFree(h->bufA);
-  (void)hipFree(h->bufL);
+  nbufs_free(nbufs_of(h));
+  nbufs_put(h, NBufs());
   (void)hipFree(h->bufY);
-  (void)hipFree(h->Dinv);
-  (void)hipFree(h->z);
-  (void)hipFree(h->w);
-  (void)hipFree(h->alpha);
-  (void)hipFree(h->gpart);
+  h->bufY = nullptr;
   (void)hipFree(h->rw);
   (void)hipFree(h->rz);
   (void)hipFree(h->rd);
   (void)hipFree(h->rpart);
-  (void)hipFree(h->small_ws);
-  h->small_ws = nullptr;
-  h->small_ws_bytes = 0;
-  (void)hipFree(h->app_ws);
-  h->app_ws = nullptr;
-  h->app_ws_bytes = 0;
-  (void)hipFree(h->rm_ws);
-  h->rm_ws = nullptr;
-  h->rm_ws_bytes = 0;
+  h->small_ws.release();
+  h->app_ws.release();
+  h->rm_ws.release();
   (void)hipFree(h->TX);
   (void)hipFree(h->Tmt);
   h->TX = h->Tmt = nullptr;
@@ -127,8 +115,6 @@ static void free_n_buffers(gogp_handle *h) {
   h->g32A = h->g32L = h->g32Y = h->g32D = nullptr;
   h->g32_cap = 0;
   h->rw = h->rz = h->rd = h->rpart = nullptr;
-  h->dX = h->dy = h->bufA = h->bufL = h->bufY = h->Dinv = nullptr;
-  h->z = h->w = h->alpha = h->gpart = nullptr;
   h->cap_npad = 0;
   h->cap_y = 0;
 }
@@ -161,11 +147,10 @@ static void free_m_buffers(gogp_handle *h) {
   (void)hipFree(h->KsT);
   (void)hipFree(h->Vt);
   (void)hipFree(h->pvec);
-  (void)hipFree(h->pg_ws);
-  (void)hipFree(h->pc_ws);
-  h->dZ = h->KsT = h->Vt = h->pvec = h->pg_ws = h->pc_ws = nullptr;
+  h->pg_ws.release();
+  h->pc_ws.release();
+  h->dZ = h->KsT = h->Vt = h->pvec = nullptr;
   h->cap_m = h->cap_mp_npad = 0;
-  h->pg_ws_doubles = h->pc_ws_doubles = 0;
 }
 
 // ---- stream sets ------------------------------------------------------------------------
@@ -347,17 +332,9 @@ static int ensure_n(gogp_handle *h, int64_t n) {
   h->trtri_done = false;
   if (npad > h->cap_npad) {
     free_n_buffers(h);
-    const size_t nn = (size_t)npad * (size_t)npad * h->esz();  // matrices: float on the fp32 path
-    // (+ GOGP_MAX_NDIM doubles of slack: grad.hip reads a few coordinates past the last row)
-    HIPCHK(h, hipMalloc(&h->dX, ((size_t)npad * h->D + GOGP_MAX_NDIM) * sizeof(double)));
-    HIPCHK(h, hipMalloc(&h->dy, (size_t)npad * sizeof(double)));
-    HIPCHK(h, hipMalloc(&h->bufA, nn));
-    HIPCHK(h, hipMalloc(&h->bufL, nn));
-    HIPCHK(h, hipMalloc(&h->Dinv, (size_t)(npad / PANEL) * PANEL * PANEL * h->esz()));
-    HIPCHK(h, hipMalloc(&h->z, (size_t)npad * sizeof(double)));
-    HIPCHK(h, hipMalloc(&h->w, (size_t)npad * sizeof(double)));
-    HIPCHK(h, hipMalloc(&h->alpha, (size_t)npad * sizeof(double)));
-    HIPCHK(h, hipMalloc(&h->gpart, (size_t)grad_reduce_blocks(npad) * NACC * sizeof(double)));
+    NBufs nb;
+    HIPCHK(h, nbufs_alloc(h, npad, &nb));
+    nbufs_put(h, nb);
     if (h->prec == 32) {  // scratch of the iterative refinement of alpha
       HIPCHK(h, hipMalloc(&h->rw, (size_t)npad * sizeof(double)));
       HIPCHK(h, hipMalloc(&h->rz, (size_t)npad * sizeof(double)));
@@ -2131,6 +2108,8 @@ static int ensure_m(gogp_handle *h, int64_t m, int64_t mpad) {
 }
 
 constexpr int PRODUCE_GROUPS = 4;
+// Produce's event slots, behind the factorisation's own
+static inline size_t produce_event_base(int64_t npad) { return EV_BASE + 4 * (size_t)(npad / PANEL) + 8; }
 // Kstar, mean and the blocked solve of Produce on matrices of element type T
 template <class T>
 static void produce_solve_t(gogp_handle *h, hipStream_t s, int64_t m, int64_t mpad, double *dmu, double *dq) {
@@ -2171,7 +2150,7 @@ static void produce_solve_t(gogp_handle *h, hipStream_t s, int64_t m, int64_t mp
   // evaluation's flops that Produce does not depend on: everything on the main stream then
   const bool busy = h->trtri_pending || h->kinv_pending;
   hipStream_t sasm = busy ? s : h->sk;
-  const size_t evt0 = EV_BASE + 4 * (size_t)npanel + 8 + 2 * PRODUCE_GROUPS;  // one event per super-panel behind the others
+  const size_t evt0 = produce_event_base(npad) + 2 * PRODUCE_GROUPS;  // one event per super-panel behind the others
   if (assemble) {
     if (sasm != s) order(h, EV_TINV, s, sasm);  // behind whatever last wrote the factor (s is ordered behind the factorisation)
     for (int P0 = 0, nsub = 0; P0 < npanel; P0 += nsub) {
@@ -2185,7 +2164,7 @@ static void produce_solve_t(gogp_handle *h, hipStream_t s, int64_t m, int64_t mp
   hipStream_t gs[PRODUCE_GROUPS] = {s, h->s2, h->st, h->sp};
   int ngroups = (h->lookahead && !busy) ? std::min(h->produce_groups, std::min(mt, PRODUCE_GROUPS)) : 1;
   if (ngroups < 1) ngroups = 1;
-  const size_t ev0 = EV_BASE + 4 * (size_t)npanel + 8;  // behind the factorisation's own event slots
+  const size_t ev0 = produce_event_base(npad);
   for (int g = 1; g < ngroups; ++g) order(h, ev0 + g, s, gs[g]);  // Kstar^T (and whatever s held) first
   for (int g = 0; g < ngroups; ++g) {
     hipStream_t sg = gs[g];
@@ -2232,18 +2211,9 @@ static void produce_solve_t(gogp_handle *h, hipStream_t s, int64_t m, int64_t mp
 // ~36-launch GEMM chain.  The reference's forecast harness asks for ONE point per step (tutorial/tutorial.go:178-179).
 // the workspace of the persistent substitution kernel: two launches of <= 32 columns side by side (33 .. 64 points);
 // *one: the bytes of one launch's part
-static int ensure_small_ws(gogp_handle *h, size_t *one_out) {
-  const size_t one = (trsm_small_workspace_bytes(std::max(h->npad, h->cap_npad)) + 255) / 256 * 256;
-  const size_t need = 2 * one;
-  if (!h->small_ws || h->small_ws_bytes < need) {
-    (void)hipFree(h->small_ws);
-    h->small_ws = nullptr;
-    h->small_ws_bytes = 0;
-    HIPCHK(h, hipMalloc(&h->small_ws, need));
-    h->small_ws_bytes = need;
-  }
-  *one_out = one;
-  return GOGP_OK;
+static int ensure_small_ws(gogp_handle *h, size_t *one) {
+  *one = (trsm_small_workspace_bytes(std::max(h->npad, h->cap_npad)) + 255) / 256 * 256;
+  return h->small_ws.reserve(h, 2 * *one);
 }
 static int produce_small(gogp_handle *h, hipStream_t s, int64_t m, int64_t mpad, double *dmu, double *dq) {
   const int64_t npad = h->npad, ld = npad;
@@ -2251,18 +2221,17 @@ static int produce_small(gogp_handle *h, hipStream_t s, int64_t m, int64_t mpad,
   const int rcw = ensure_small_ws(h, &one);
   if (rcw != GOGP_OK) return rcw;
   const bool f32 = h->prec == 32;  // float factor / inverses / Kstar: widened as the kernel reads them, sums in fp64
-  {
-    AuxTimer tm(h, GOGP_PROF_CROSS, s);
-    if (f32)
-      launch_cross(s, h->devP, h->D, h->dX, h->n, npad, h->dZ, m, mpad, reinterpret_cast<float *>(h->KsT), ld, h->ev());
-    else
-      launch_cross(s, h->devP, h->D, h->dX, h->n, npad, h->dZ, m, mpad, h->KsT, ld, h->ev());  // gp/gp.go:322-332
-  }
-  // mean = Kstar^T alpha (gp/gp.go:335)
+  auto cross_and_mean = [&](auto *Ks) {
+    {
+      AuxTimer tm(h, GOGP_PROF_CROSS, s);
+      launch_cross(s, h->devP, h->D, h->dX, h->n, npad, h->dZ, m, mpad, Ks, ld, h->ev());  // gp/gp.go:322-332
+    }
+    launch_rownorm_dot(s, Ks, ld, h->alpha, npad, m, dmu, nullptr);  // mean = Kstar^T alpha (gp/gp.go:335)
+  };
   if (f32)
-    launch_rownorm_dot(s, reinterpret_cast<const float *>(h->KsT), ld, h->alpha, npad, m, dmu, nullptr);
+    cross_and_mean(reinterpret_cast<float *>(h->KsT));
   else
-    launch_rownorm_dot(s, h->KsT, ld, h->alpha, npad, m, dmu, nullptr);
+    cross_and_mean(h->KsT);
   auto solve = [&](hipStream_t q, int j0, int cnt, void *ws, unsigned **tm) {
     if (f32)
       launch_trsm_small(q, reinterpret_cast<const float *>(h->bufL), ld, reinterpret_cast<const float *>(h->Dinv),
@@ -2271,75 +2240,123 @@ static int produce_small(gogp_handle *h, hipStream_t s, int64_t m, int64_t mpad,
       launch_trsm_small(q, h->bufL, ld, h->Dinv, h->KsT, ld, npad, j0, cnt, ws, dq, tm);
   };
   unsigned *tmo = nullptr, *tmo2 = nullptr;
-  unsigned *htmo = reinterpret_cast<unsigned *>(h->hscal + 10);
+  unsigned *htmo = hs_tmo(h);
   htmo[0] = htmo[1] = 0;
   const int m1 = (int)std::min<int64_t>(m, 32);
-  const size_t ev0 = EV_BASE + 4 * (size_t)(npad / PANEL) + 8;  // Produce's event slots behind the factorisation's own
+  const size_t ev0 = produce_event_base(npad);
   // (right behind an eager Observe s2 carries the triangular inverse: both launches on the main stream then)
   hipStream_t s2nd = (h->trtri_pending || h->kinv_pending) ? s : h->s2;
   if (m > 32) {
     // the second 32 columns on a second stream, beside the first (both launches read the same factor at the same
     // time: what one pulls into the Infinity Cache the other finds there)
     if (s2nd != s) order(h, ev0 + 1, s, s2nd);
-    solve(s2nd, 32, (int)m - 32, (char *)h->small_ws + one, &tmo2);
+    solve(s2nd, 32, (int)m - 32, h->small_ws.as<char>() + one, &tmo2);
     HIPCHK(h, hipMemcpyAsync(htmo + 1, tmo2, sizeof(unsigned), hipMemcpyDeviceToHost, s2nd));
   }
-  solve(s, 0, m1, h->small_ws, &tmo);
+  solve(s, 0, m1, h->small_ws.p, &tmo);
   HIPCHK(h, hipMemcpyAsync(htmo, tmo, sizeof(unsigned), hipMemcpyDeviceToHost, s));
   if (m > 32 && s2nd != s) order(h, ev0 + PRODUCE_GROUPS + 1, s2nd, s);
+  return GOGP_OK;
+}
+
+// ---- what the Produce calls share ------------------------------------------------------------------
+// The test points' vectors on the device, mpad doubles each (pvec)
+struct ProducePlan {
+  int64_t mpad = 0;
+  double *prior = nullptr, *mu = nullptr, *q = nullptr, *sigma = nullptr;
+};
+// Up to the point where the handle's buffers are in place: the refusals (refuse != nullptr: fp32 and sharded handles,
+// under that name; cov: more than GOGP_COV_MAX_M points), the state (under the name `who`), the device, the sizes.
+// m == 0 returns GOGP_OK with nothing done; so does a sharded handle with observations, whose Produce has buffers of
+// its own (gogp_dist_produce).
+static int produce_prepare(gogp_handle *h, const char *refuse, const char *who, int64_t m, bool cov, ProducePlan *pp) {
+  char buf[160];
+  if (refuse && h->prec == 32) {
+    snprintf(buf, sizeof buf, "%s: precision = 32 handles are not supported", refuse);
+    return fail(h, GOGP_EARG, buf);
+  }
+  if (refuse && h->dist) {
+    snprintf(buf, sizeof buf, "%s: sharded handles are not supported", refuse);
+    return fail(h, GOGP_EARG, buf);
+  }
+  if (cov && m > GOGP_COV_MAX_M) {
+    snprintf(buf, sizeof buf, "%s: more than GOGP_COV_MAX_M = %d test points", who, GOGP_COV_MAX_M);
+    return fail(h, GOGP_EARG, buf);
+  }
+  if (m == 0) return GOGP_OK;
+  if (h->n > 0 && !h->factored) {
+    snprintf(buf, sizeof buf, "%s: nothing absorbed", who);
+    return fail(h, GOGP_ESTATE, buf);
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  if (h->dist && h->n > 0) return GOGP_OK;
+  if (cov && h->ncu <= 0) {  // the slab policy of pcov.hip
+    HIPCHK(h, hipDeviceGetAttribute(&h->ncu, hipDeviceAttributeMultiprocessorCount, h->device));
+    if (h->ncu <= 0) h->ncu = 1;
+  }
+  const int64_t mpad = ((m + TILE - 1) / TILE) * TILE;
+  const int rc = ensure_m(h, m, mpad);
+  if (rc != GOGP_OK) return rc;
+  *pp = ProducePlan{mpad, h->pvec, h->pvec + mpad, h->pvec + 2 * mpad, h->pvec + 3 * mpad};
+  return GOGP_OK;
+}
+// Z up, optionally the prior (gp/gp.go:269-278); with observations the main stream then waits for alpha and, `tile`,
+// runs Produce's tile route: the mean into pp.mu, |V_j|^2 into pp.q, V^T into Vt row by row
+static int produce_forward(gogp_handle *h, const double *Z, int64_t m, const ProducePlan &pp, bool prior, bool tile) {
+  hipStream_t s = h->s;
+  if (h->n == 0) {
+    const int rc = gogp_upload_params(h);  // no observations: parameters may not have been uploaded yet
+    if (rc != GOGP_OK) return rc;
+  }
+  HIPCHK(h, hipMemcpyAsync(h->dZ, Z, (size_t)m * h->D * sizeof(double), hipMemcpyHostToDevice, s));
+  if (prior) launch_prior(s, h->devP, h->dZ, m, pp.prior);
+  if (h->n == 0) return GOGP_OK;
+  const int rc = ensure_alpha(h);
+  if (rc != GOGP_OK) return rc;
+  if (tile) produce_solve_t<double>(h, s, m, pp.mpad, pp.mu, pp.q);
+  return GOGP_OK;
+}
+// No observations (gp/gp.go:343-347), behind produce_forward with the prior: sigma = sqrt(prior), mu = 0
+static int produce_of_the_prior(gogp_handle *h, const ProducePlan &pp, int64_t m, double *mu, double *sigma) {
+  launch_sigma(h->s, pp.prior, nullptr, m, pp.sigma);
+  HIPCHK(h, hipMemcpyAsync(sigma, pp.sigma, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, h->s));
+  HIPCHK(h, hipStreamSynchronize(h->s));
+  for (int64_t j = 0; j < m; ++j) mu[j] = 0.0;
   return GOGP_OK;
 }
 
 extern "C" int gogp_produce(gogp_handle *h, const double *Z, int64_t m, double *mu,
                             double *sigma) {
   if (!h || m < 0 || (m > 0 && (!Z || !mu || !sigma))) return fail(h, GOGP_EARG, "produce: NULL");
-  if (m == 0) return GOGP_OK;
-  if (h->n > 0 && !h->factored) return fail(h, GOGP_ESTATE, "Produce: nothing absorbed");
-  HIPCHK(h, hipSetDevice(h->device));
+  ProducePlan pp;
+  int rc = produce_prepare(h, nullptr, "Produce", m, false, &pp);
+  if (rc != GOGP_OK || m == 0) return rc;
   if (h->dist && h->n > 0) return gogp_dist_produce(h, Z, m, mu, sigma);
-  const int64_t mpad = ((m + TILE - 1) / TILE) * TILE;
-  int rc = ensure_m(h, m, mpad);
-  if (rc != GOGP_OK) return rc;
   hipStream_t s = h->s;
-  double *prior = h->pvec, *dmu = h->pvec + mpad, *dq = h->pvec + 2 * mpad,
-         *dsig = h->pvec + 3 * mpad;
-  if (h->n == 0 || !h->factored) {
-    // no observations: parameters may not have been uploaded yet
-    rc = gogp_upload_params(h);
-    if (rc != GOGP_OK) return rc;
-  }
-  HIPCHK(h, hipMemcpyAsync(h->dZ, Z, (size_t)m * h->D * sizeof(double), hipMemcpyHostToDevice, s));
-  launch_prior(s, h->devP, h->dZ, m, prior);  // gp/gp.go:269-278
-  if (h->n == 0) {                            // gp/gp.go:343-347
-    launch_sigma(s, prior, nullptr, m, dsig);
-    HIPCHK(h, hipMemcpyAsync(sigma, dsig, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipStreamSynchronize(s));
-    for (int64_t j = 0; j < m; ++j) mu[j] = 0.0;
-    return GOGP_OK;
-  }
-  rc = ensure_alpha(h);
+  rc = produce_forward(h, Z, m, pp, true, false);
   if (rc != GOGP_OK) return rc;
+  if (h->n == 0) return produce_of_the_prior(h, pp, m, mu, sigma);
   // (float matrices: up to 16 test points -- measured at N = 65536: M = 1 / 16 / 64 in 4.5 / 5.0 / 11.2 ms against 7.5 on
   // the float tile-kernel chain, N = 16384: 0.92 / 0.94 / 1.53 against 1.07: the float chain is twice as fast as the fp64 one)
   const bool small = m <= h->produce_small_max && (h->prec == 64 || m <= 16);
   if (small) {
-    rc = produce_small(h, s, m, mpad, dmu, dq);
+    rc = produce_small(h, s, m, pp.mpad, pp.mu, pp.q);
     if (rc != GOGP_OK) return rc;
   } else if (h->prec == 32)
-    produce_solve_t<float>(h, s, m, mpad, dmu, dq);
+    produce_solve_t<float>(h, s, m, pp.mpad, pp.mu, pp.q);
   else
-    produce_solve_t<double>(h, s, m, mpad, dmu, dq);
-  launch_sigma(s, prior, dq, m, dsig);
-  HIPCHK(h, hipMemcpyAsync(mu, dmu, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
-  HIPCHK(h, hipMemcpyAsync(sigma, dsig, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
+    produce_solve_t<double>(h, s, m, pp.mpad, pp.mu, pp.q);
+  launch_sigma(s, pp.prior, pp.q, m, pp.sigma);
+  HIPCHK(h, hipMemcpyAsync(mu, pp.mu, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipMemcpyAsync(sigma, pp.sigma, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
   HIPCHK(h, hipStreamSynchronize(s));
   HIPCHK(h, hipGetLastError());
-  if (small && (reinterpret_cast<const unsigned *>(h->hscal + 10)[0] | reinterpret_cast<const unsigned *>(h->hscal + 10)[1]) != 0u) {
+  const unsigned tmo = small ? hs_tmo(h)[0] | hs_tmo(h)[1] : 0u;
+  if (tmo != 0u) {
     // a workgroup of the persistent substitution gave up waiting for another one (trsm_small.hip): the numbers are
     // not to be trusted -- say so instead of returning them
     char buf[160];
-    snprintf(buf, sizeof buf, "Produce: the substitution kernel timed out waiting for a workgroup (code 0x%x)",
-             reinterpret_cast<const unsigned *>(h->hscal + 10)[0] | reinterpret_cast<const unsigned *>(h->hscal + 10)[1]);
+    snprintf(buf, sizeof buf, "Produce: the substitution kernel timed out waiting for a workgroup (code 0x%x)", tmo);
     h->err = buf;
     return GOGP_EHIP;
   }
@@ -2372,51 +2389,33 @@ extern "C" int gogp_produce_gradient(gogp_handle *h, const double *Z, int64_t m,
                                      double *dmu_out, double *dsigma_out) {
   if (!h || m < 0 || (m > 0 && (!Z || !mu || !sigma || !dmu_out || !dsigma_out)))
     return fail(h, GOGP_EARG, "produce_gradient: NULL");
-  if (h->prec == 32) return fail(h, GOGP_EARG, "produce_gradient: precision = 32 handles are not supported");
-  if (h->dist) return fail(h, GOGP_EARG, "produce_gradient: sharded handles are not supported");
-  if (m == 0) return GOGP_OK;
-  if (h->n > 0 && !h->factored) return fail(h, GOGP_ESTATE, "ProduceGradient: nothing absorbed");
-  HIPCHK(h, hipSetDevice(h->device));
-  const int64_t mpad = ((m + TILE - 1) / TILE) * TILE;
+  ProducePlan pp;
+  int rc = produce_prepare(h, "produce_gradient", "ProduceGradient", m, false, &pp);
+  if (rc != GOGP_OK || m == 0) return rc;
   const int D = h->D;
-  int rc = ensure_m(h, m, mpad);
-  if (rc != GOGP_OK) return rc;
   hipStream_t s = h->s;
-  double *prior = h->pvec, *dmu = h->pvec + mpad, *dq = h->pvec + 2 * mpad, *dsig = h->pvec + 3 * mpad;
   if (h->n == 0) {
-    rc = gogp_upload_params(h);  // no observations: parameters may not have been uploaded yet
+    rc = produce_forward(h, Z, m, pp, true, true);
+    if (rc == GOGP_OK) rc = produce_of_the_prior(h, pp, m, mu, sigma);
     if (rc != GOGP_OK) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->dZ, Z, (size_t)m * D * sizeof(double), hipMemcpyHostToDevice, s));
-    launch_prior(s, h->devP, h->dZ, m, prior);
-    launch_sigma(s, prior, nullptr, m, dsig);
-    HIPCHK(h, hipMemcpyAsync(sigma, dsig, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipStreamSynchronize(s));
-    for (int64_t j = 0; j < m; ++j) mu[j] = 0.0;
     for (int64_t j = 0; j < m * D; ++j) dmu_out[j] = dsigma_out[j] = 0.0;  // the prior does not depend on z
     return GOGP_OK;
   }
   const int nslab = gogp::pgrad_slabs(h->npad, m, nullptr);
-  const size_t md = (size_t)m * D, need = md * (2 * (size_t)nslab + 2);
-  if (!h->pg_ws || h->pg_ws_doubles < need) {
-    (void)hipFree(h->pg_ws);
-    h->pg_ws = nullptr;
-    h->pg_ws_doubles = 0;
-    HIPCHK(h, hipMalloc(&h->pg_ws, need * sizeof(double)));
-    h->pg_ws_doubles = need;
-  }
-  double *part = h->pg_ws, *ddmu = part + 2 * (size_t)nslab * md, *ddsig = ddmu + md;
-  HIPCHK(h, hipMemcpyAsync(h->dZ, Z, (size_t)m * D * sizeof(double), hipMemcpyHostToDevice, s));
-  launch_prior(s, h->devP, h->dZ, m, prior);
-  rc = ensure_alpha(h);
+  const size_t md = (size_t)m * D;
+  rc = h->pg_ws.reserve(h, md * (2 * (size_t)nslab + 2) * sizeof(double));
   if (rc != GOGP_OK) return rc;
+  double *part = h->pg_ws.as<double>(), *ddmu = part + 2 * (size_t)nslab * md, *ddsig = ddmu + md;
   // always the tile route of Produce, whatever m: it leaves V^T in Vt, row by row, where the backward pass starts
   // (the persistent few-point kernel keeps its solution in a layout of its own)
-  produce_solve_t<double>(h, s, m, mpad, dmu, dq);
-  launch_sigma(s, prior, dq, m, dsig);
+  rc = produce_forward(h, Z, m, pp, true, true);
+  if (rc != GOGP_OK) return rc;
+  launch_sigma(s, pp.prior, pp.q, m, pp.sigma);
   produce_backward(h, s, m);
-  launch_pgrad(s, h->devP, D, h->dX, h->n, h->npad, h->dZ, m, h->alpha, h->KsT, h->npad, dsig, part, ddmu, ddsig, h->ev());
-  HIPCHK(h, hipMemcpyAsync(mu, dmu, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
-  HIPCHK(h, hipMemcpyAsync(sigma, dsig, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
+  launch_pgrad(s, h->devP, D, h->dX, h->n, h->npad, h->dZ, m, h->alpha, h->KsT, h->npad, pp.sigma, part, ddmu, ddsig,
+               h->ev());
+  HIPCHK(h, hipMemcpyAsync(mu, pp.mu, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipMemcpyAsync(sigma, pp.sigma, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
   HIPCHK(h, hipMemcpyAsync(dmu_out, ddmu, md * sizeof(double), hipMemcpyDeviceToHost, s));
   HIPCHK(h, hipMemcpyAsync(dsigma_out, ddsig, md * sizeof(double), hipMemcpyDeviceToHost, s));
   HIPCHK(h, hipStreamSynchronize(s));
@@ -2430,83 +2429,33 @@ extern "C" int gogp_produce_gradient(gogp_handle *h, const double *Z, int64_t m,
 //   covariance:  part | cov (m x m)
 //   samples:     part | S = cov + diag_add I, identity-padded to mp = a multiple of 256 | C, its lower factor | one
 //                block inverse | xi, zero-padded to nsp x mp (nsp a multiple of 128) | xi C^T | samples (ns x m) | pivot word
-static int ensure_pc_ws(gogp_handle *h, size_t need) {
-  if (!h->pc_ws || h->pc_ws_doubles < need) {
-    (void)hipFree(h->pc_ws);
-    h->pc_ws = nullptr;
-    h->pc_ws_doubles = 0;
-    HIPCHK(h, hipMalloc(&h->pc_ws, need * sizeof(double)));
-    h->pc_ws_doubles = need;
-  }
-  return GOGP_OK;
-}
 // doubles of the SYRK's partial tiles for m test points on the current factor
 static size_t pcov_part_doubles(gogp_handle *h, int64_t m) {
   if (h->n == 0) return 0;
   const size_t tiles = (size_t)((m + 63) / 64), pairs = tiles * (tiles + 1) / 2;
   return (size_t)gogp::pcov_slabs(h->npad, m, h->ncu, nullptr) * pairs * 4096;
 }
-// What the two calls share, up to the point where the handle's buffers are in place: arguments, state, sizes
-static int pcov_prepare(gogp_handle *h, const char *who, int64_t m, int64_t *mpad) {
-  char buf[160];
-  if (h->prec == 32) {
-    snprintf(buf, sizeof buf, "%s: precision = 32 handles are not supported", who);
-    return fail(h, GOGP_EARG, buf);
-  }
-  if (h->dist) {
-    snprintf(buf, sizeof buf, "%s: sharded handles are not supported", who);
-    return fail(h, GOGP_EARG, buf);
-  }
-  if (m > GOGP_COV_MAX_M) {
-    snprintf(buf, sizeof buf, "%s: more than GOGP_COV_MAX_M = %d test points", who, GOGP_COV_MAX_M);
-    return fail(h, GOGP_EARG, buf);
-  }
-  if (m == 0) return GOGP_OK;
-  if (h->n > 0 && !h->factored) {
-    snprintf(buf, sizeof buf, "%s: nothing absorbed", who);
-    return fail(h, GOGP_ESTATE, buf);
-  }
-  HIPCHK(h, hipSetDevice(h->device));
-  if (h->ncu <= 0) {
-    HIPCHK(h, hipDeviceGetAttribute(&h->ncu, hipDeviceAttributeMultiprocessorCount, h->device));
-    if (h->ncu <= 0) h->ncu = 1;
-  }
-  *mpad = ((m + TILE - 1) / TILE) * TILE;
-  return ensure_m(h, m, *mpad);
-}
-// Z up, the mean into pvec + mpad and V^T into Vt (n == 0: the mean is zero and there is no V)
-static int pcov_forward(gogp_handle *h, const double *Z, int64_t m, int64_t mpad) {
-  hipStream_t s = h->s;
-  double *dmu = h->pvec + mpad, *dq = h->pvec + 2 * mpad;
-  if (h->n == 0) {
-    const int rc = gogp_upload_params(h);  // no observations: parameters may not have been uploaded yet
-    if (rc != GOGP_OK) return rc;
-  }
-  HIPCHK(h, hipMemcpyAsync(h->dZ, Z, (size_t)m * h->D * sizeof(double), hipMemcpyHostToDevice, s));
-  if (h->n == 0) {
-    HIPCHK(h, hipMemsetAsync(dmu, 0, (size_t)m * sizeof(double), s));
-    return GOGP_OK;
-  }
-  const int rc = ensure_alpha(h);
-  if (rc != GOGP_OK) return rc;
-  produce_solve_t<double>(h, s, m, mpad, dmu, dq);
-  return GOGP_OK;
+// Z up, the mean into pp.mu and V^T into Vt (n == 0: the mean is zero and there is no V)
+static int pcov_forward(gogp_handle *h, const double *Z, int64_t m, const ProducePlan &pp) {
+  const int rc = produce_forward(h, Z, m, pp, false, true);
+  if (rc == GOGP_OK && h->n == 0) HIPCHK(h, hipMemsetAsync(pp.mu, 0, (size_t)m * sizeof(double), h->s));
+  return rc;
 }
 
 extern "C" int gogp_produce_covariance(gogp_handle *h, const double *Z, int64_t m, double *mu, double *cov) {
   if (!h || m < 0 || (m > 0 && (!Z || !mu || !cov))) return fail(h, GOGP_EARG, "produce_covariance: NULL");
-  int64_t mpad = 0;
-  int rc = pcov_prepare(h, "produce_covariance", m, &mpad);
+  ProducePlan pp;
+  int rc = produce_prepare(h, "produce_covariance", "produce_covariance", m, true, &pp);
   if (rc != GOGP_OK || m == 0) return rc;
   const size_t npart = pcov_part_doubles(h, m), mm = (size_t)m * m;
-  rc = ensure_pc_ws(h, npart + mm);
+  rc = h->pc_ws.reserve(h, (npart + mm) * sizeof(double));
   if (rc != GOGP_OK) return rc;
-  double *part = h->pc_ws, *dcov = part + npart;
+  double *part = h->pc_ws.as<double>(), *dcov = part + npart;
   hipStream_t s = h->s;
-  rc = pcov_forward(h, Z, m, mpad);
+  rc = pcov_forward(h, Z, m, pp);
   if (rc != GOGP_OK) return rc;
   launch_pcov(s, h->devP, h->dZ, m, h->n > 0 ? h->Vt : nullptr, h->npad, h->npad, h->ncu, part, 0.0, dcov, m, m, h->ev());
-  HIPCHK(h, hipMemcpyAsync(mu, h->pvec + mpad, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipMemcpyAsync(mu, pp.mu, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
   HIPCHK(h, hipMemcpyAsync(cov, dcov, mm * sizeof(double), hipMemcpyDeviceToHost, s));
   HIPCHK(h, hipStreamSynchronize(s));
   HIPCHK(h, hipGetLastError());
@@ -2519,15 +2468,15 @@ extern "C" int gogp_produce_samples(gogp_handle *h, const double *Z, int64_t m, 
     return fail(h, GOGP_EARG, "produce_samples: NULL");
   if (!(diag_add >= 0.0) || !std::isfinite(diag_add))
     return fail(h, GOGP_EARG, "produce_samples: diag_add must be finite and not negative");
-  int64_t mpad = 0;
-  int rc = pcov_prepare(h, "produce_samples", m, &mpad);
+  ProducePlan pp;
+  int rc = produce_prepare(h, "produce_samples", "produce_samples", m, true, &pp);
   if (rc != GOGP_OK || m == 0) return rc;
   for (int64_t i = 0; i < ns * m; ++i)
     if (!std::isfinite(xi[i])) return fail(h, GOGP_EARG, "produce_samples: xi contains a value that is not finite");
   hipStream_t s = h->s;
-  double *dmu = h->pvec + mpad;
+  double *dmu = pp.mu;
   if (ns == 0) {  // the mean alone
-    rc = pcov_forward(h, Z, m, mpad);
+    rc = pcov_forward(h, Z, m, pp);
     if (rc != GOGP_OK) return rc;
     HIPCHK(h, hipMemcpyAsync(mu, dmu, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
     HIPCHK(h, hipStreamSynchronize(s));
@@ -2536,12 +2485,12 @@ extern "C" int gogp_produce_samples(gogp_handle *h, const double *Z, int64_t m, 
   }
   const int64_t mp = ((m + PANEL - 1) / PANEL) * PANEL, nsp = ((ns + TILE - 1) / TILE) * TILE;
   const size_t npart = pcov_part_doubles(h, m), mm = (size_t)mp * mp, nx = (size_t)nsp * mp;
-  rc = ensure_pc_ws(h, npart + 2 * mm + (size_t)PANEL * PANEL + 2 * nx + (size_t)ns * m + 1);
+  rc = h->pc_ws.reserve(h, (npart + 2 * mm + (size_t)PANEL * PANEL + 2 * nx + (size_t)ns * m + 1) * sizeof(double));
   if (rc != GOGP_OK) return rc;
-  double *part = h->pc_ws, *S = part + npart, *C = S + mm, *Dp = C + mm, *dxi = Dp + (size_t)PANEL * PANEL,
+  double *part = h->pc_ws.as<double>(), *S = part + npart, *C = S + mm, *Dp = C + mm, *dxi = Dp + (size_t)PANEL * PANEL,
          *G = dxi + nx, *dsamp = G + nx;
   long long *info = reinterpret_cast<long long *>(dsamp + (size_t)ns * m);
-  rc = pcov_forward(h, Z, m, mpad);
+  rc = pcov_forward(h, Z, m, pp);
   if (rc != GOGP_OK) return rc;
   launch_pcov(s, h->devP, h->dZ, m, h->n > 0 ? h->Vt : nullptr, h->npad, h->npad, h->ncu, part, diag_add, S, mp, mp, h->ev());
   // S = C C^T, right-looking in 256-panels on the main stream: the diagonal block and its inverse, the panel under it
@@ -2561,7 +2510,7 @@ extern "C" int gogp_produce_samples(gogp_handle *h, const double *Z, int64_t m, 
                      S + c2 * mp + c2, mp, nullptr);
     }
   }
-  long long *hinfo = reinterpret_cast<long long *>(h->hscal + 12);  // a staging word of this call's own: HS_INFO keeps K's
+  long long *hinfo = reinterpret_cast<long long *>(h->hscal + HS_PIVOT);  // a staging word of this call's own: HS_INFO keeps K's
   HIPCHK(h, hipMemcpyAsync(hinfo, info, sizeof(long long), hipMemcpyDeviceToHost, s));
   // samples = mu + xi C^T: xi up in one copy, one product (B = C as stored: zero above the diagonal), samples down in one
   HIPCHK(h, hipMemsetAsync(dxi, 0, nx * sizeof(double), s));
@@ -2698,18 +2647,15 @@ extern "C" int gogp_set_factor(gogp_handle *h, const double *theta_simil,
   HIPCHK(h, hipMalloc(&tmp, (size_t)n * n * sizeof(double)));
   hipError_t e = hipMemcpyAsync(tmp, Lin, (size_t)n * n * sizeof(double), hipMemcpyHostToDevice, s);
   if (e == hipSuccess) {
-    if (h->prec == 32) {
-      float *L32 = reinterpret_cast<float *>(h->bufL), *D32 = reinterpret_cast<float *>(h->Dinv);
-      launch_pack_lower(s, tmp, n, npad, L32, npad);
+    auto pack = [&](auto *L, auto *Dv) {  // the factor and its block inverses in the handle's element type
+      launch_pack_lower(s, tmp, n, npad, L, npad);
       for (int b = 0; b < (int)(npad / PANEL); ++b)
-        diag_inv_only(h, s, L32 + (size_t)b * PANEL * npad + (size_t)b * PANEL, npad,
-                      D32 + (size_t)b * PANEL * PANEL);
-    } else {
-      launch_pack_lower(s, tmp, n, npad, h->bufL, npad);
-      for (int b = 0; b < (int)(npad / PANEL); ++b)
-        diag_inv_only(h, s, h->bufL + (size_t)b * PANEL * npad + (size_t)b * PANEL, npad,
-                      h->Dinv + (size_t)b * PANEL * PANEL);
-    }
+        diag_inv_only(h, s, L + (size_t)b * PANEL * npad + (size_t)b * PANEL, npad, Dv + (size_t)b * PANEL * PANEL);
+    };
+    if (h->prec == 32)
+      pack(reinterpret_cast<float *>(h->bufL), reinterpret_cast<float *>(h->Dinv));
+    else
+      pack(h->bufL, h->Dinv);
     e = hipMemsetAsync(h->alpha, 0, (size_t)npad * sizeof(double), s);
   }
   if (e == hipSuccess)
@@ -2748,21 +2694,49 @@ extern "C" int gogp_set_factor(gogp_handle *h, const double *theta_simil,
 // other buffer, the pointers are swapped back; in place: the new rows lay on identity padding rows, which are put back
 // -- the one old block inverse the new rows share is restored from a copy, the data tails are zeroed again.
 struct AppendSaved {
-  double *dX, *dy, *bufA, *bufL, *Dinv, *z, *w, *alpha, *gpart;
+  NBufs bufs;
   int64_t cap_npad, n, npad;
   int nblk;
   EvalState es;
 };
 
-static int ensure_append_ws(gogp_handle *h, int64_t npad) {
-  const size_t need = ((size_t)PANEL * PANEL + (size_t)(npad / PANEL) * gogp::APPEND_PART) * sizeof(double);
-  if (h->app_ws && h->app_ws_bytes >= need) return GOGP_OK;
-  (void)hipFree(h->app_ws);
-  h->app_ws = nullptr;
-  h->app_ws_bytes = 0;
-  HIPCHK(h, hipMalloc(&h->app_ws, need));
-  h->app_ws_bytes = need;
+// What gogp_append and gogp_remove start with: nothing of an earlier call may still run -- an eager Observe's inverse
+// reads bufL and writes bufA -- and nothing that was pending or assembled for the old factor holds for the new one
+static int begin_factor_update(gogp_handle *h) {
+  for (hipStream_t q : work_streams(h)) HIPCHK(h, hipStreamSynchronize(q));
+  h->trtri_pending = h->alpha_pending = h->kinv_pending = false;
+  h->tinv_valid = h->tinv_pending = false;
+  h->ydone_valid = false;
+  h->kinv_c1 = 0;
   return GOGP_OK;
+}
+// ... and end with, on the main stream s behind z of the n1 rows: alpha = L^-T z over the whole new factor L (leading
+// dimension ld = its npad), the LML from y^T alpha as gogp_set_factor, one host copy, one synchronise; then `adopt` --
+// the caller's part that must not run before the device is done: freeing what the old factor lay in, making L the
+// handle's -- and the judging of the scalars
+template <class Adopt>
+static int finish_factor_update(gogp_handle *h, const double *L, int64_t ld, int64_t n1, hipStream_t s, Adopt adopt) {
+  const int np1 = (int)(ld / PANEL);
+  HIPCHK(h, hipMemcpyAsync(h->w, h->z, (size_t)ld * sizeof(double), hipMemcpyDeviceToDevice, s));
+  for (int b = np1 - 1; b >= 0; --b) launch_trsv_bwd_step(s, L, ld, h->Dinv, b, np1, h->w, h->alpha);
+  launch_lml_scalars(s, L, ld, h->z, h->dy, h->alpha, n1, h->scalars);
+  HIPCHK(h, hipMemcpyAsync(h->hscal, h->scalars, 7 * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipStreamSynchronize(s));
+  HIPCHK(h, hipGetLastError());
+  adopt();
+  h->hscal[6] = h->hscal[2];  // y^T alpha where judge_scalars looks for the quadratic term of a refined alpha
+  const long long zero = 0;
+  memcpy(h->hscal + HS_INFO, &zero, sizeof zero);
+  const FactorResult fr = judge_scalars(h, h->hscal, false, true);
+  h->lml = fr.lml;
+  h->yta = fr.yta;
+  h->cond_lb = fr.cond_lb;
+  h->notpd = -1;
+  h->factored = h->have_alpha = true;
+  h->observed = h->with_obs = h->grad_valid = h->have_kinv = h->trtri_done = false;
+  h->z_valid = true;
+  if (fr.rc == GOGP_ECOND) h->err = fr.msg;
+  return fr.rc;
 }
 
 extern "C" int gogp_append(gogp_handle *h, const double *X2, const double *y2, int64_t m) {
@@ -2796,71 +2770,47 @@ extern "C" int gogp_append(gogp_handle *h, const double *X2, const double *y2, i
     }
     return rc;
   }
-  // nothing of an earlier call may still run: an eager Observe's inverse reads bufL and writes bufA
-  for (hipStream_t q : work_streams(h)) HIPCHK(h, hipStreamSynchronize(q));
-  h->trtri_pending = h->alpha_pending = h->kinv_pending = false;
-  h->tinv_valid = h->tinv_pending = false;
-  h->ydone_valid = false;
-  h->kinv_c1 = 0;
+  int rc = begin_factor_update(h);
+  if (rc != GOGP_OK) return rc;
   hipStream_t s = h->s;
   const int D = h->D;
   const int64_t n0 = h->n, npad0 = h->npad, n1 = n0 + m, npad1 = ((n1 + PANEL - 1) / PANEL) * PANEL;
   const bool restride = npad1 != npad0, grow = npad1 > h->cap_npad;
-  int rc = gogp_upload_params(h);
+  rc = gogp_upload_params(h);
   if (rc != GOGP_OK) return rc;
-  rc = ensure_append_ws(h, std::max(npad1, h->cap_npad));
+  const size_t blk = (size_t)PANEL * PANEL;
+  rc = h->app_ws.reserve(h, (blk + (size_t)(std::max(npad1, h->cap_npad) / PANEL) * gogp::APPEND_PART) * sizeof(double));
   if (rc != GOGP_OK) return rc;
-  double *dsave = static_cast<double *>(h->app_ws), *part = dsave + (size_t)PANEL * PANEL;
-  const size_t vb0 = (size_t)npad0 * sizeof(double), vb1 = (size_t)npad1 * sizeof(double);
+  double *dsave = h->app_ws.as<double>(), *part = dsave + blk;
+  const size_t vb0 = (size_t)npad0 * sizeof(double);
   if (!h->z_valid) {  // a restored factor: z = L^-1 y by the substitution steps
     HIPCHK(h, hipMemcpyAsync(h->w, h->dy, vb0, hipMemcpyDeviceToDevice, s));
     const int np0 = (int)(npad0 / PANEL);
     for (int b = 0; b < np0; ++b) launch_trsv_fwd_step(s, h->bufL, npad0, h->Dinv, b, np0, h->w, h->z);
     h->z_valid = true;
   }
-  AppendSaved old{h->dX, h->dy, h->bufA, h->bufL, h->Dinv, h->z, h->w, h->alpha, h->gpart, h->cap_npad, n0, npad0, h->nblk,
-                  static_cast<const EvalState &>(*h)};
+  const AppendSaved saved{nbufs_of(h), h->cap_npad, n0, npad0, h->nblk, static_cast<const EvalState &>(*h)};
+  const NBufs &old = saved.bufs;
   // the one old block inverse the new rows share
   const bool save_blk = (n0 % PANEL) != 0;
   const int64_t b0 = n0 / PANEL;
-  const size_t blk = (size_t)PANEL * PANEL;
   if (save_blk) HIPCHK(h, hipMemcpyAsync(dsave, h->Dinv + (size_t)b0 * blk, blk * sizeof(double), hipMemcpyDeviceToDevice, s));
   const size_t xslack = GOGP_MAX_NDIM;
   if (grow) {
     const int64_t cap = npad1 + ((npad1 / 8 + PANEL - 1) / PANEL) * PANEL;
-    const size_t nn = (size_t)cap * (size_t)cap * sizeof(double);
-    double *nX = nullptr, *ny = nullptr, *nA = nullptr, *nL = nullptr, *nD = nullptr, *nz = nullptr, *nw = nullptr,
-           *na = nullptr, *ng = nullptr;
-    hipError_t e = hipMalloc(&nX, ((size_t)cap * D + xslack) * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&ny, (size_t)cap * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&nA, nn);
-    if (e == hipSuccess) e = hipMalloc(&nL, nn);
-    if (e == hipSuccess) e = hipMalloc(&nD, (size_t)(cap / PANEL) * blk * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&nz, (size_t)cap * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&nw, (size_t)cap * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&na, (size_t)cap * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&ng, (size_t)grad_reduce_blocks(cap) * NACC * sizeof(double));
-    if (e != hipSuccess) {
-      for (double *p : {nX, ny, nA, nL, nD, nz, nw, na, ng}) (void)hipFree(p);
+    NBufs nb;
+    if (nbufs_alloc(h, cap, &nb) != hipSuccess) {
       (void)hipGetLastError();
       return fail(h, GOGP_ENOMEM, "append: out of device memory");
     }
-    HIPCHK(h, hipMemsetAsync(nX, 0, ((size_t)cap * D + xslack) * sizeof(double), s));
-    HIPCHK(h, hipMemsetAsync(ny, 0, (size_t)cap * sizeof(double), s));
-    HIPCHK(h, hipMemsetAsync(nz, 0, (size_t)cap * sizeof(double), s));
-    HIPCHK(h, hipMemcpyAsync(nX, old.dX, (size_t)n0 * D * sizeof(double), hipMemcpyDeviceToDevice, s));
-    HIPCHK(h, hipMemcpyAsync(ny, old.dy, (size_t)n0 * sizeof(double), hipMemcpyDeviceToDevice, s));
-    HIPCHK(h, hipMemcpyAsync(nz, old.z, (size_t)n0 * sizeof(double), hipMemcpyDeviceToDevice, s));
-    HIPCHK(h, hipMemcpyAsync(nD, old.Dinv, (size_t)(npad0 / PANEL) * blk * sizeof(double), hipMemcpyDeviceToDevice, s));
-    h->dX = nX;
-    h->dy = ny;
-    h->bufA = nA;
-    h->bufL = nL;
-    h->Dinv = nD;
-    h->z = nz;
-    h->w = nw;
-    h->alpha = na;
-    h->gpart = ng;
+    HIPCHK(h, hipMemsetAsync(nb.dX, 0, ((size_t)cap * D + xslack) * sizeof(double), s));
+    HIPCHK(h, hipMemsetAsync(nb.dy, 0, (size_t)cap * sizeof(double), s));
+    HIPCHK(h, hipMemsetAsync(nb.z, 0, (size_t)cap * sizeof(double), s));
+    HIPCHK(h, hipMemcpyAsync(nb.dX, old.dX, (size_t)n0 * D * sizeof(double), hipMemcpyDeviceToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(nb.dy, old.dy, (size_t)n0 * sizeof(double), hipMemcpyDeviceToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(nb.z, old.z, (size_t)n0 * sizeof(double), hipMemcpyDeviceToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(nb.Dinv, old.Dinv, (size_t)(npad0 / PANEL) * blk * sizeof(double), hipMemcpyDeviceToDevice, s));
+    nbufs_put(h, nb);
     h->cap_npad = cap;
     launch_append_restride(s, old.bufL, npad0, npad0, h->bufL, npad1, npad1);
   } else {
@@ -2882,15 +2832,9 @@ extern "C" int gogp_append(gogp_handle *h, const double *X2, const double *y2, i
   auto rollback = [&]() {
     for (hipStream_t q : {s, h->s2}) (void)hipStreamSynchronize(q);
     if (grow) {
-      for (double *p : {h->dX, h->dy, h->bufA, h->bufL, h->Dinv, h->z, h->w, h->alpha, h->gpart}) (void)hipFree(p);
-      h->dX = old.dX;
-      h->dy = old.dy;
-      h->Dinv = old.Dinv;
-      h->z = old.z;
-      h->w = old.w;
-      h->alpha = old.alpha;
-      h->gpart = old.gpart;
-      h->cap_npad = old.cap_npad;
+      nbufs_free(nbufs_of(h));
+      nbufs_put(h, old);
+      h->cap_npad = saved.cap_npad;
     } else {
       if (!restride) launch_append_identity_rows(s, old.bufL, npad0, n0, std::min(touched, npad0), npad0);
       if (save_blk) (void)hipMemcpyAsync(h->Dinv + (size_t)b0 * blk, dsave, blk * sizeof(double), hipMemcpyDeviceToDevice, s);
@@ -2902,8 +2846,8 @@ extern "C" int gogp_append(gogp_handle *h, const double *X2, const double *y2, i
     h->bufL = old.bufL;
     h->n = n0;
     h->npad = npad0;
-    h->nblk = old.nblk;
-    static_cast<EvalState &>(*h) = old.es;
+    h->nblk = saved.nblk;
+    static_cast<EvalState &>(*h) = saved.es;
     if (restride && !grow) h->have_kinv = false;  // bufA held the restrided copy
     (void)hipStreamSynchronize(s);
     free_m_buffers(h);  // sized for the npad that did not come to be
@@ -2920,8 +2864,8 @@ extern "C" int gogp_append(gogp_handle *h, const double *X2, const double *y2, i
     h->err = e;
     return rc;
   }
-  unsigned *htmo = reinterpret_cast<unsigned *>(h->hscal + 10);
-  const size_t ev0 = EV_BASE + 4 * (size_t)(npad1 / PANEL) + 8;  // Produce's event slots
+  unsigned *htmo = hs_tmo(h);
+  const size_t ev0 = produce_event_base(npad1);
   for (int64_t off = 0; off < m; off += 64) {
     const int mc = (int)std::min<int64_t>(64, m - off), m1 = std::min(mc, 32);
     const int64_t npc = ((ncur + PANEL - 1) / PANEL) * PANEL;  // the rows that exist so far, in whole blocks
@@ -2933,14 +2877,14 @@ extern "C" int gogp_append(gogp_handle *h, const double *X2, const double *y2, i
     htmo[0] = htmo[1] = 0;
     if (mc > 32) {  // the second 32 columns beside the first, as Produce (every stream is idle here)
       order(h, ev0 + 1, s, h->s2);
-      launch_trsm_small(h->s2, h->bufL, ld, h->Dinv, h->KsT, ld, npc, 32, mc - 32, (char *)h->small_ws + one, h->pvec, &tmo2);
+      launch_trsm_small(h->s2, h->bufL, ld, h->Dinv, h->KsT, ld, npc, 32, mc - 32, h->small_ws.as<char>() + one, h->pvec, &tmo2);
       HIPCHK(h, hipMemcpyAsync(htmo + 1, tmo2, sizeof(unsigned), hipMemcpyDeviceToHost, h->s2));
     }
-    launch_trsm_small(s, h->bufL, ld, h->Dinv, h->KsT, ld, npc, 0, m1, h->small_ws, h->pvec, &tmo);
+    launch_trsm_small(s, h->bufL, ld, h->Dinv, h->KsT, ld, npc, 0, m1, h->small_ws.p, h->pvec, &tmo);
     HIPCHK(h, hipMemcpyAsync(htmo, tmo, sizeof(unsigned), hipMemcpyDeviceToHost, s));
     if (mc > 32) order(h, ev0 + PRODUCE_GROUPS + 1, h->s2, s);
-    gogp::TsSolution v0 = gogp::trsm_small_solution(npc, 0, m1, h->small_ws), v1 = v0;
-    if (mc > 32) v1 = gogp::trsm_small_solution(npc, 32, mc - 32, (char *)h->small_ws + one);
+    gogp::TsSolution v0 = gogp::trsm_small_solution(npc, 0, m1, h->small_ws.p), v1 = v0;
+    if (mc > 32) v1 = gogp::trsm_small_solution(npc, 32, mc - 32, h->small_ws.as<char>() + one);
     launch_append_gram(s, v0, v1, m1, mc, npc, ncur, h->z, part, Lrow, ld);
     launch_append_commit(s, h->devP, Xc, yc, mc, ncur, part, (int)(npc / PANEL), Lrow, ld, h->z + ncur, h->info, h->ev());
     HIPCHK(h, hipMemcpyAsync(h->hscal + HS_INFO, h->info, sizeof(long long), hipMemcpyDeviceToHost, s));
@@ -2980,31 +2924,11 @@ extern "C" int gogp_append(gogp_handle *h, const double *X2, const double *y2, i
     ncur += mc;
   }
   h->n = n1;
-  // alpha = L^-T z over the whole new factor, the LML from y^T alpha as gogp_set_factor
-  const int np1 = (int)(npad1 / PANEL);
-  HIPCHK(h, hipMemcpyAsync(h->w, h->z, vb1, hipMemcpyDeviceToDevice, s));
-  for (int b = np1 - 1; b >= 0; --b) launch_trsv_bwd_step(s, h->bufL, ld, h->Dinv, b, np1, h->w, h->alpha);
-  launch_lml_scalars(s, h->bufL, ld, h->z, h->dy, h->alpha, n1, h->scalars);
-  HIPCHK(h, hipMemcpyAsync(h->hscal, h->scalars, 7 * sizeof(double), hipMemcpyDeviceToHost, s));
-  HIPCHK(h, hipStreamSynchronize(s));
-  HIPCHK(h, hipGetLastError());
-  if (grow) {
-    for (double *p : {old.dX, old.dy, old.bufA, old.bufL, old.Dinv, old.z, old.w, old.alpha, old.gpart}) (void)hipFree(p);
+  return finish_factor_update(h, h->bufL, ld, n1, s, [&] {
+    if (!grow) return;
+    nbufs_free(old);
     drop_cand_graph(h);
-  }
-  h->hscal[6] = h->hscal[2];  // y^T alpha where judge_scalars looks for the quadratic term of a refined alpha
-  const long long zero = 0;
-  memcpy(h->hscal + HS_INFO, &zero, sizeof zero);
-  const FactorResult fr = judge_scalars(h, h->hscal, false, true);
-  h->lml = fr.lml;
-  h->yta = fr.yta;
-  h->cond_lb = fr.cond_lb;
-  h->notpd = -1;
-  h->factored = h->have_alpha = true;
-  h->observed = h->with_obs = h->grad_valid = h->have_kinv = h->trtri_done = false;
-  h->z_valid = true;
-  if (fr.rc == GOGP_ECOND) h->err = fr.msg;
-  return fr.rc;
+  });
 }
 
 // ---- remove ---------------------------------------------------------------------------------------
@@ -3021,16 +2945,6 @@ extern "C" int gogp_append(gogp_handle *h, const double *X2, const double *y2, i
 // one host copy, one synchronise.  The old factor is only read; the pointers are swapped at the end.
 // Measured (profiles/remove.txt): slower than gogp_set_data + gogp_absorb for removals from the front at
 // N = 4096 and for 64 rows at once at N = 16384; no automatic fallback.
-static int ensure_remove_ws(gogp_handle *h, size_t need) {
-  if (h->rm_ws && h->rm_ws_bytes >= need) return GOGP_OK;
-  (void)hipFree(h->rm_ws);
-  h->rm_ws = nullptr;
-  h->rm_ws_bytes = 0;
-  HIPCHK(h, hipMalloc(&h->rm_ws, need));
-  h->rm_ws_bytes = need;
-  return GOGP_OK;
-}
-
 extern "C" int gogp_remove(gogp_handle *h, const int64_t *idx, int64_t m) {
   if (!h) return GOGP_EARG;
   if (m < 0) return fail(h, GOGP_EARG, "remove: m < 0");
@@ -3055,12 +2969,8 @@ extern "C" int gogp_remove(gogp_handle *h, const int64_t *idx, int64_t m) {
     h->notpd = -1;
     return GOGP_OK;
   }
-  // nothing of an earlier call may still run: an eager Observe's inverse reads bufL and writes bufA
-  for (hipStream_t q : work_streams(h)) HIPCHK(h, hipStreamSynchronize(q));
-  h->trtri_pending = h->alpha_pending = h->kinv_pending = false;
-  h->tinv_valid = h->tinv_pending = false;
-  h->ydone_valid = false;
-  h->kinv_c1 = 0;
+  int rc = begin_factor_update(h);
+  if (rc != GOGP_OK) return rc;
   h->have_kinv = false;  // bufA is written from here on
   hipStream_t s = h->s;
   const int D = h->D;
@@ -3079,9 +2989,9 @@ extern "C" int gogp_remove(gogp_handle *h, const int64_t *idx, int64_t m) {
   const size_t nints = (size_t)((n1 + m + 1) / 2) * 2;
   const size_t need = nints * sizeof(int) +
                       ((size_t)gogp::REMOVE_W * npad1 + (size_t)npad1 * TILE + (size_t)npad1 * (D + 1)) * sizeof(double);
-  int rc = ensure_remove_ws(h, need);
+  rc = h->rm_ws.reserve(h, need);
   if (rc != GOGP_OK) return rc;
-  int *dmap = static_cast<int *>(h->rm_ws), *drem = dmap + n1;
+  int *dmap = h->rm_ws.as<int>(), *drem = dmap + n1;
   double *W = reinterpret_cast<double *>(dmap + nints), *snap = W + (size_t)gogp::REMOVE_W * npad1;
   double *Xt = snap + (size_t)npad1 * TILE, *yt = Xt + (size_t)npad1 * D;
   double *Lold = h->bufL, *Lnew = h->bufA;
@@ -3112,30 +3022,13 @@ extern "C" int gogp_remove(gogp_handle *h, const int64_t *idx, int64_t m) {
   const size_t vb1 = (size_t)npad1 * sizeof(double);
   HIPCHK(h, hipMemcpyAsync(h->w, h->dy, vb1, hipMemcpyDeviceToDevice, s));
   for (int b = 0; b < np1; ++b) launch_trsv_fwd_step(s, Lnew, ld, h->Dinv, b, np1, h->w, h->z);
-  HIPCHK(h, hipMemcpyAsync(h->w, h->z, vb1, hipMemcpyDeviceToDevice, s));
-  for (int b = np1 - 1; b >= 0; --b) launch_trsv_bwd_step(s, Lnew, ld, h->Dinv, b, np1, h->w, h->alpha);
-  launch_lml_scalars(s, Lnew, ld, h->z, h->dy, h->alpha, n1, h->scalars);
-  HIPCHK(h, hipMemcpyAsync(h->hscal, h->scalars, 7 * sizeof(double), hipMemcpyDeviceToHost, s));
-  HIPCHK(h, hipStreamSynchronize(s));
-  HIPCHK(h, hipGetLastError());
-  h->bufL = Lnew;
-  h->bufA = Lold;
-  h->n = n1;
-  h->npad = npad1;
-  h->nblk = (int)(npad1 / TILE);
-  h->hscal[6] = h->hscal[2];  // y^T alpha where judge_scalars looks for the quadratic term of a refined alpha
-  const long long zero = 0;
-  memcpy(h->hscal + HS_INFO, &zero, sizeof zero);
-  const FactorResult fr = judge_scalars(h, h->hscal, false, true);
-  h->lml = fr.lml;
-  h->yta = fr.yta;
-  h->cond_lb = fr.cond_lb;
-  h->notpd = -1;
-  h->factored = h->have_alpha = true;
-  h->observed = h->with_obs = h->grad_valid = h->have_kinv = h->trtri_done = false;
-  h->z_valid = true;
-  if (fr.rc == GOGP_ECOND) h->err = fr.msg;
-  return fr.rc;
+  return finish_factor_update(h, Lnew, ld, n1, s, [&] {
+    h->bufL = Lnew;
+    h->bufA = Lold;
+    h->n = n1;
+    h->npad = npad1;
+    h->nblk = (int)(npad1 / TILE);
+  });
 }
 
 // ---- measurement hooks -----------------------------------------------------------------------------

@@ -20,7 +20,10 @@ constexpr int REFINE_SLABS = 8;  // column slabs of the residual kernel (gram.hi
 // doubles): the factorisation's scalars in [0 .. 7] (api.hip: judge_scalars), then these
 constexpr int HS_INFO = 8;    // first failing pivot + 1 (a long long; 0: positive definite)
 constexpr int HS_TRACE = 9;   // fp32 K^-1: tr(alpha alpha^T - K^-1) summed in fp64 from Y (NaN: not computed)
+constexpr int HS_TMO = 10;    // the two time-out words (unsigned) of the persistent substitution kernel's launches (trsm_small.hip)
+constexpr int HS_PIVOT = 12;  // gogp_produce_samples: first failing pivot + 1 of the test points' covariance (HS_INFO keeps K's)
 constexpr int HS_GRAD = 16;   // the gradient's NACC slot sums
+static_assert(HS_INFO < HS_TMO && HS_TMO < HS_PIVOT && HS_PIVOT < HS_GRAD, "the staging words lie below the gradient's sums");
 static_assert(HS_GRAD + gogp::NACC == gogp::BATCH_ROW, "the pinned row is a batch row");
 
 // The device buffers of one evaluation: the handle's own, or an arena slot of a candidates call (api.hip: cand_layout)
@@ -32,6 +35,30 @@ struct EvalBufs {
   double *bufA = nullptr, *bufL = nullptr, *bufY = nullptr, *Dinv = nullptr;
   double *z = nullptr, *w = nullptr, *alpha = nullptr;
   double *gpart = nullptr;
+};
+
+// The buffers sized by the number of observations that gogp_set_data allocates and gogp_append replaces as one set
+// (bufY and the fp32 path's scratch have capacities of their own).  nbufs_alloc holds their sizes.
+struct NBufs {
+  double *dX = nullptr, *dy = nullptr, *bufA = nullptr, *bufL = nullptr, *Dinv = nullptr;
+  double *z = nullptr, *w = nullptr, *alpha = nullptr, *gpart = nullptr;
+};
+
+// Device bytes grown on demand and never shrunk: the scratch of one family of calls, whose contents no call expects to
+// find again.  Not a general allocator: buffers tied to a validity flag or a typed capacity keep their own code.
+struct gogp_handle;
+struct Workspace {
+  void *p = nullptr;
+  size_t bytes = 0;  // capacity
+  // at least `need` bytes; on failure the old block is gone, the capacity is 0 and h->err says why (GOGP_ENOMEM / GOGP_EHIP)
+  inline int reserve(gogp_handle *h, size_t need);
+  void release() {
+    (void)hipFree(p);
+    p = nullptr;
+    bytes = 0;
+  }
+  template <class T>
+  T *as() const { return static_cast<T *>(p); }
 };
 
 // What an evaluation leaves in the handle; a candidates call saves it and puts it back
@@ -89,10 +116,10 @@ struct gogp_handle : EvalBufs, EvalState {
   // produce workspace
   double *dZ = nullptr, *KsT = nullptr, *Vt = nullptr, *pvec = nullptr;
   int64_t cap_m = 0, cap_mp_npad = 0;
-  double *pg_ws = nullptr;     // gogp_produce_gradient: partial sums of pgrad_kernel + the two derivative arrays
-  size_t pg_ws_doubles = 0;
-  double *pc_ws = nullptr;     // gogp_produce_covariance / gogp_produce_samples: the SYRK's partial tiles, the covariance,
-  size_t pc_ws_doubles = 0;    // and for samples its factor, a block inverse, xi, the product and the pivot word (pcov.hip)
+  // released with the M buffers (api.hip: free_m_buffers)
+  Workspace pg_ws;             // gogp_produce_gradient: partial sums of pgrad_kernel + the two derivative arrays
+  Workspace pc_ws;             // gogp_produce_covariance / gogp_produce_samples: the SYRK's partial tiles, the covariance,
+                               // and for samples its factor, a block inverse, xi, the product and the pivot word (pcov.hip)
   int ncu = 0;                 // compute units of the device (0: not asked yet): the slab policy of pcov.hip
   hipStream_t s = nullptr;   // main stream: Gram, big trailing updates, reductions
   hipStream_t sp = nullptr;  // panel stream (high priority): diagonal blocks, TRSM-as-GEMM,
@@ -167,8 +194,7 @@ struct gogp_handle : EvalBufs, EvalState {
   // Produce for few test points (M <= produce_small_max, fp64, one GPU): ONE persistent launch that reads the factor
   // once (trsm_small.hip) instead of the tile-kernel chain; 0: off
   int produce_small_max = 64;
-  void *small_ws = nullptr;    // its workspace (solution / w blocks, counters, partial sums)
-  size_t small_ws_bytes = 0;
+  Workspace small_ws;          // its workspace (solution / w blocks, counters, partial sums); released with the N buffers
   int produce_groups = 2;      // Produce: independent substitution chains (streams) over the test points' tile rows
   int krag = 1;                // the inverse's updates skip the zero triangle of a super-panel of Y (common.h: GemmGrid::krag0)
   int ard_mfma_min = 1;        // ARD kernels (one radial term) with at least this many dimensions reduce the
@@ -186,10 +212,9 @@ struct gogp_handle : EvalBufs, EvalState {
   bool have_data = false;
   bool have_theta = false;  // theta_s / theta_n were given by an Absorb, Observe or set_factor
   bool z_valid = false;     // z = L^-1 y of the current factor is in `z` (not after gogp_set_factor, which stores none)
-  void *app_ws = nullptr;   // gogp_append: the saved block inverse + the partial sums of its Gram kernel (append.hip)
-  size_t app_ws_bytes = 0;
-  void *rm_ws = nullptr;    // gogp_remove: index maps, a pass's columns of W, the diagonal-block snapshot, compacted X / y (remove.hip)
-  size_t rm_ws_bytes = 0;
+  // released with the N buffers (api.hip: free_n_buffers)
+  Workspace app_ws;         // gogp_append: the saved block inverse + the partial sums of its Gram kernel (append.hip)
+  Workspace rm_ws;          // gogp_remove: index maps, a pass's columns of W, the diagonal-block snapshot, compacted X / y (remove.hip)
   double yta = 0.0;      // y^T alpha of the last factorisation (fp32 path: of the refined alpha)
   int trace_fp64 = 1;    // fp32 path: tr(alpha alpha^T - K^-1) summed in fp64 from Y, scale component by its identity
   double cond_limit = 1e16;  // gonum's mat.ConditionTolerance
@@ -238,6 +263,51 @@ struct AuxTimer {
       return (e_ == hipErrorOutOfMemory) ? GOGP_ENOMEM : GOGP_EHIP;                     \
     }                                                                                  \
   } while (0)
+
+inline int Workspace::reserve(gogp_handle *h, size_t need) {
+  if (p && bytes >= need) return GOGP_OK;
+  release();
+  HIPCHK(h, hipMalloc(&p, need));
+  bytes = need;
+  return GOGP_OK;
+}
+
+// the two time-out words of the pinned staging row (HS_TMO)
+static inline unsigned *hs_tmo(const gogp_handle *h) { return reinterpret_cast<unsigned *>(h->hscal + HS_TMO); }
+
+// ---- the set of N-sized buffers ----------------------------------------------------------------
+static inline void nbufs_free(const NBufs &b) {
+  for (double *q : {b.dX, b.dy, b.bufA, b.bufL, b.Dinv, b.z, b.w, b.alpha, b.gpart}) (void)hipFree(q);
+}
+// A whole set for `cap` (a multiple of PANEL) observations into *b, or nothing.  Matrices are float on the fp32 path.
+static inline hipError_t nbufs_alloc(const gogp_handle *h, int64_t cap, NBufs *b) {
+  const size_t nn = (size_t)cap * (size_t)cap * h->esz(), vec = (size_t)cap * sizeof(double);
+  // (+ GOGP_MAX_NDIM doubles of slack: grad.hip reads a few coordinates past the last row)
+  hipError_t e = hipMalloc(&b->dX, ((size_t)cap * h->D + GOGP_MAX_NDIM) * sizeof(double));
+  if (e == hipSuccess) e = hipMalloc(&b->dy, vec);
+  if (e == hipSuccess) e = hipMalloc(&b->bufA, nn);
+  if (e == hipSuccess) e = hipMalloc(&b->bufL, nn);
+  if (e == hipSuccess) e = hipMalloc(&b->Dinv, (size_t)(cap / gogp::PANEL) * gogp::PANEL * gogp::PANEL * h->esz());
+  if (e == hipSuccess) e = hipMalloc(&b->z, vec);
+  if (e == hipSuccess) e = hipMalloc(&b->w, vec);
+  if (e == hipSuccess) e = hipMalloc(&b->alpha, vec);
+  if (e == hipSuccess) e = hipMalloc(&b->gpart, (size_t)gogp::grad_reduce_blocks(cap) * gogp::NACC * sizeof(double));
+  if (e != hipSuccess) {
+    nbufs_free(*b);
+    *b = NBufs();
+  }
+  return e;
+}
+static inline NBufs nbufs_of(const gogp_handle *h) {
+  NBufs b;
+  b.dX = h->dX, b.dy = h->dy, b.bufA = h->bufA, b.bufL = h->bufL, b.Dinv = h->Dinv;
+  b.z = h->z, b.w = h->w, b.alpha = h->alpha, b.gpart = h->gpart;
+  return b;
+}
+static inline void nbufs_put(gogp_handle *h, const NBufs &b) {
+  h->dX = b.dX, h->dy = b.dy, h->bufA = b.bufA, h->bufL = b.bufL, h->Dinv = b.Dinv;
+  h->z = b.z, h->w = b.w, h->alpha = b.alpha, h->gpart = b.gpart;
+}
 
 // every work stream of the handle (the communication stream of a sharded handle is dist2d's)
 static inline std::array<hipStream_t, 6> work_streams(const gogp_handle *h) {
