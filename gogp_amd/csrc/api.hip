@@ -24,6 +24,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <initializer_list>
 #include <mutex>
 #include <new>
 #include <thread>
@@ -510,15 +511,6 @@ static int ensure_d64(gogp_handle *h) {
   h->cap_d64 = cap;
   return GOGP_OK;
 }
-// D64 blocks first .. first + nblk - 1 -= their rows of L[:, k0 : k0 + K] times themselves (float operands, fp64 sums)
-static void d64_update(gogp_handle *h, hipStream_t s, const float *L, int64_t ld, int64_t k0, int64_t K, int first, int nblk) {
-  launch_diag_syrk_f64(s, L + (int64_t)first * PANEL * ld + k0, ld, K, h->D64 + (size_t)first * PANEL * PANEL, nblk);
-}
-static void d64_update(gogp_handle *, hipStream_t, const double *, int64_t, int64_t, int64_t, int, int) {}
-static void d64_init(gogp_handle *h, hipStream_t s, const float *A, int64_t ld, int first, int nblk) {
-  launch_widen_diag_blocks(s, A + (int64_t)first * PANEL * (ld + 1), ld, h->D64 + (size_t)first * PANEL * PANEL, nblk);
-}
-static void d64_init(gogp_handle *, hipStream_t, const double *, int64_t, int, int) {}
 
 // What the scalars of one factorisation say (row of the pinned staging block: [0] 2 sum log L_ii,
 // [1] z^T z, [3], [4] min / max L_ii, [5] fp64 log-determinant of the fp32 path, [6] y^T alpha of the
@@ -595,15 +587,6 @@ static int finish_factorize(gogp_handle *h, bool fp32, bool refine, bool kinv) {
 }
 
 // ---- factorisation: Gram + blocked right-looking Cholesky + forward solve ----------------
-// One super-step of the triangular inverse Y = L^-T (upper): column panels
-// P0 .. P0+nsub-1 (256 wide each), then ONE rank-(nsub*256) update of everything
-// to the right:
-//   per sub-panel p:  Y[c0:c2, c0:c2] = inv(L_pp)^T ;  Y[0:c0, c0:c2] = R[0:c0, c0:c2] inv(L_pp)^T
-//                     R[0:c2, c2:CE] -= Y[0:c2, c0:c2] L[c2:CE, c0:c2]^T      (inside the super-panel)
-//   R[0:CE, CE:]   -= Y[0:CE, C0:CE] L[CE:, C0:CE]^T                          (updates, s2)
-// R occupies the strictly upper 256-block triangle of bufA (zero-initialised),
-// which the Cholesky sweep never touches: the step only needs the panels of L it
-// names and their diagonal inverses, so it runs right behind their factorisation.
 // One 256x256 diagonal block: factor + dense inverse (diag256.hip, always fp64 arithmetic).  On
 // the fp32 path the block is widened into fp64 scratch, factored and inverted there, and the
 // factor and the inverse are rounded to float once; the log-determinant is accumulated from
@@ -650,6 +633,12 @@ static void diag_inv_only(gogp_handle *h, hipStream_t s, const float *L, int64_t
 static inline int chain_prio_of(const gogp_handle *h) {
   return h->chain_prio < 0 ? (h->npad <= 6144 ? 1 : 0) : h->chain_prio;
 }
+// the grid options of a tile-kernel launch on one of the two chains
+static inline GemmGrid chain_grid(const gogp_handle *h) {
+  GemmGrid g;
+  g.prio = chain_prio_of(h);
+  return g;
+}
 
 // superpanel_head = -1 (default): 3 panels in fp64, 4 on the fp32 path, whose bulk updates run twice as fast
 // beside the same fp64 diagonal-block chain (N = 32768: 311.6 -> 309.4 ms, N = 65536: 2322 -> 2303 ms; 6: 312.5)
@@ -657,6 +646,37 @@ static inline int superpanel_width(const gogp_handle *h, int npanel, int P0) {
   const int head = h->superpanel_head < 0 ? (h->prec == 32 ? 4 : 3) : h->superpanel_head;
   const int sw = (head > 0 && npanel - P0 > h->head_remaining) ? head : h->superpanel;
   return (npanel - P0 < sw) ? npanel - P0 : sw;
+}
+// One super-panel of the sweep: 256-panels P0 .. P0 + nsub - 1, columns C0 .. CE; prevP0: the one before it (-1: none),
+// next_nsub: the width of the one after it (0: none)
+struct SuperPanel {
+  int P0, nsub, prevP0, next_nsub;
+  int64_t C0() const { return (int64_t)P0 * PANEL; }
+  int64_t CE() const { return C0() + (int64_t)nsub * PANEL; }
+};
+// the super-panels of the handle's matrix in the order of the sweep: the Cholesky sweep and the triangular inverse,
+// fused behind it or lazy, walk the same ones
+static std::vector<SuperPanel> superpanels(const gogp_handle *h) {
+  const int npanel = (int)(h->npad / PANEL);
+  std::vector<SuperPanel> v;
+  for (int P0 = 0; P0 < npanel; P0 += v.back().nsub) {
+    const int nsub = superpanel_width(h, npanel, P0);
+    if (!v.empty()) v.back().next_nsub = nsub;
+    v.push_back({P0, nsub, v.empty() ? -1 : v.back().P0, 0});
+  }
+  return v;
+}
+// Updates inside a super-panel are grouped like a binary counter: after its panel q (columns up to c2) the next
+// grp = lowbit(q + 1) block columns, c2 .. ce, receive the LAST grp panels, columns k0 .. c2, at once (K = 256 grp).
+// Every block column has all earlier panels of the super-panel when its turn comes; for two panels per super-panel this
+// is the single K = 256 update of the second column.
+struct InnerGroup {
+  int grp;
+  int64_t k0, ce;
+};
+static inline InnerGroup inner_group(int q, int64_t c2, int64_t CE) {
+  const int done = q + 1, grp = done & -done;
+  return {grp, c2 - (int64_t)grp * PANEL, std::min(c2 + (int64_t)grp * PANEL, CE)};
 }
 
 // ---- T^-1 of the super-panels' diagonal blocks (for Produce) --------------------------------------------------------
@@ -734,22 +754,26 @@ struct InvBufs {
   T *A, *Y;
   const T *L, *Dinv;
 };
+// One super-step of the triangular inverse Y = L^-T (upper): column panels
+// P0 .. P0+nsub-1 (256 wide each), then ONE rank-(nsub*256) update of everything
+// to the right:
+//   per sub-panel p:  Y[c0:c2, c0:c2] = inv(L_pp)^T ;  Y[0:c0, c0:c2] = R[0:c0, c0:c2] inv(L_pp)^T
+//                     R[0:c2, c2:CE] -= Y[0:c2, c0:c2] L[c2:CE, c0:c2]^T      (inside the super-panel)
+//   R[0:CE, CE:]   -= Y[0:CE, C0:CE] L[CE:, C0:CE]^T                          (updates, s2)
+// R occupies the strictly upper 256-block triangle of bufA (zero-initialised),
+// which the Cholesky sweep never touches: the step only needs the panels of L it
+// names and their diagonal inverses, so it runs right behind their factorisation.
 template <class T>
-static InvBufs<T> own_bufs(gogp_handle *h) {
-  return {reinterpret_cast<T *>(h->bufA), reinterpret_cast<T *>(h->bufY), reinterpret_cast<const T *>(h->bufL),
-          reinterpret_cast<const T *>(h->Dinv)};
-}
-template <class T>
-static void trtri_superstep(gogp_handle *h, const InvBufs<T> &B, int P0, int nsub, int prevP0, int next_nsub,
-                            hipStream_t st, hipStream_t s2) {
+static void trtri_superstep(gogp_handle *h, const InvBufs<T> &B, const SuperPanel &P, hipStream_t st, hipStream_t s2) {
   const int64_t npad = h->npad, ld = npad;
   T *R = B.A, *Y = B.Y;
   const T *L = B.L;
   GemmProfile *pf = &h->prof;
-  const int64_t C0 = (int64_t)P0 * PANEL, CE = C0 + (int64_t)nsub * PANEL;
+  const int P0 = P.P0;
+  const int64_t C0 = P.C0(), CE = P.CE();
   // R[0:C0, C0:CE] is final: its last update (the previous super-step's next-columns update)
   // ran on this chain stream, in order
-  for (int q = 0; q < nsub; ++q) {
+  for (int q = 0; q < P.nsub; ++q) {
     const int p = P0 + q;
     const int64_t c0 = (int64_t)p * PANEL, c2 = c0 + PANEL;
     const T *Dp = B.Dinv + (size_t)p * PANEL * PANEL;
@@ -757,21 +781,17 @@ static void trtri_superstep(gogp_handle *h, const InvBufs<T> &B, int P0, int nsu
     if (c2 < CE)  // block below the diagonal inside the super-panel: part of the K range
       launch_zero_block(st, Y + c2 * ld + c0, ld, CE - c2, PANEL);
     if (c0 > 0) {
-      GemmGrid gtri;  // Dp is lower triangular: the first tile column only needs k < 128
+      GemmGrid gtri = chain_grid(h);  // Dp is lower triangular: the first tile column only needs k < 128
       gtri.ktri = h->ktri;
-      gtri.prio = chain_prio_of(h);
       launch_gemm_nt(st, GEMM_RECT, (int)(c0 / TILE), 2, PANEL, 1.0, R + c0, ld, Dp, PANEL, 0.0,
                       Y + c0, ld, pf, &gtri);
     }
-    if (c2 < CE) {  // same binary grouping as the Cholesky sweep's updates inside a super-panel
-      const int done = q + 1, grp = done & -done;
-      const int64_t k0 = c2 - (int64_t)grp * PANEL;
-      const int64_t ce = (c2 + (int64_t)grp * PANEL < CE) ? c2 + (int64_t)grp * PANEL : CE;
-      GemmGrid gch;
-      gch.prio = chain_prio_of(h);
-      if (h->krag) gch.krag0 = (int)(k0 / TILE);  // rows >= k0 of Y[:, k0:c2] are zero left of their diagonal tile
-      launch_gemm_nt(st, GEMM_RECT, (int)(c2 / TILE), (int)((ce - c2) / TILE), (int64_t)grp * PANEL,
-                      -1.0, Y + k0, ld, L + c2 * ld + k0, ld, 1.0, R + c2, ld, pf, &gch);
+    if (c2 < CE) {  // the Cholesky chain's grouping of the updates inside a super-panel
+      const InnerGroup g = inner_group(q, c2, CE);
+      GemmGrid gch = chain_grid(h);
+      if (h->krag) gch.krag0 = (int)(g.k0 / TILE);  // rows >= k0 of Y[:, k0:c2] are zero left of their diagonal tile
+      launch_gemm_nt(st, GEMM_RECT, (int)(c2 / TILE), (int)((g.ce - c2) / TILE), (int64_t)g.grp * PANEL,
+                      -1.0, Y + g.k0, ld, L + c2 * ld + g.k0, ld, 1.0, R + c2, ld, pf, &gch);
     }
   }
   order(h, EV_BASE + 4 * P0 + 2, st, s2);  // column panels P0.. of Y are final
@@ -779,17 +799,16 @@ static void trtri_superstep(gogp_handle *h, const InvBufs<T> &B, int P0, int nsu
   if (nt > 0) {
     const int64_t Kw = CE - C0;
     const int mr = (int)(CE / TILE);
-    const int ntn = nt < 2 * next_nsub ? nt : 2 * next_nsub;  // next super-panel's columns
+    const int ntn = nt < 2 * P.next_nsub ? nt : 2 * P.next_nsub;  // next super-panel's columns
     // The next super-step's columns stay on the CHAIN stream (as in the Cholesky sweep: no
     // event hop on the chain); they were last touched by the previous super-step's bulk update.
     if (P0 > 0 && st != s2)
-      (void)gogp::rec_stream_wait(st, ev(h, EV_BASE + 4 * prevP0 + 3));
+      (void)gogp::rec_stream_wait(st, ev(h, EV_BASE + 4 * P.prevP0 + 3));
     // The super-panel of Y is upper triangular in its own block rows C0 .. CE: tile row C0/128 + i only sums
     // k >= i * 128 (krag0) -- half of the K range of those rows, 0.1 TFLOP of an N = 16384 evaluation that is
     // no longer launched (4.58 -> 4.50 TFLOP; the evaluation's time does not move: 71.43 -> 71.35 ms, the
     // inverse's bulk stream has that much slack behind its chain).
-    GemmGrid gch, gbulk;
-    gch.prio = chain_prio_of(h);
+    GemmGrid gch = chain_grid(h), gbulk;
     if (h->krag) gch.krag0 = gbulk.krag0 = (int)(C0 / TILE);
     launch_gemm_nt(st, GEMM_RECT, mr, ntn, Kw, -1.0, Y + C0, ld, L + CE * ld + C0, ld, 1.0,
                     R + CE, ld, pf, &gch);
@@ -830,23 +849,51 @@ static int ensure_g32(gogp_handle *h) {
 }
 // one super-step of the inverse in float: float copies of the super-panel of L (rows C0.., its columns) and of its
 // block inverses, then the same launches as the fp64 sweep on the fp32 tile kernel
-static void mixed_superstep(gogp_handle *h, int P0, int nsub, int prevP0, int next_nsub, hipStream_t st, hipStream_t s2,
-                            bool fuse_kinv) {
-  const int64_t npad = h->npad, ld = npad;
-  const int64_t C0 = (int64_t)P0 * PANEL, W = (int64_t)nsub * PANEL, CE = C0 + W;
+static void mixed_superstep(gogp_handle *h, const SuperPanel &P, hipStream_t st, hipStream_t s2) {
+  const int64_t npad = h->npad, ld = npad, C0 = P.C0(), W = P.CE() - C0;
   launch_convert_block(st, h->bufL + C0 * ld + C0, ld, h->g32L + C0 * ld + C0, ld, (int)(npad - C0), (int)W);
-  launch_convert_block(st, h->Dinv + (size_t)P0 * PANEL * PANEL, PANEL, h->g32D + (size_t)P0 * PANEL * PANEL, PANEL,
+  launch_convert_block(st, h->Dinv + (size_t)P.P0 * PANEL * PANEL, PANEL, h->g32D + (size_t)P.P0 * PANEL * PANEL, PANEL,
                        (int)W, PANEL);
   const InvBufs<float> B{h->g32A, h->g32Y, h->g32L, h->g32D};
-  trtri_superstep<float>(h, B, P0, nsub, prevP0, next_nsub, st, s2);
-  if (fuse_kinv) {
-    (void)gogp::rec_stream_wait(h->sk, ev(h, EV_BASE + 4 * P0 + 2));
-    GemmGrid gk;
-    gk.new_row0 = (int)(C0 / TILE);
-    if (h->krag) gk.krag0 = (int)(C0 / TILE);
-    const float *Yp = h->g32Y + C0;
-    launch_gemm_nt(h->sk, GEMM_LOWER, (int)(CE / TILE), (int)(CE / TILE), W, 1.0, Yp, ld, Yp, ld, 1.0, h->g32A, ld,
-                   &h->prof, &gk);
+  trtri_superstep<float>(h, B, P, st, s2);
+}
+
+// K^-1 = Y Y^T = sum over the column panels of Y, right behind the super-step that made columns C0 .. CE of Y: the
+// rank-(CE - C0) update K^-1[0:CE, 0:CE] (+)= Y[0:CE, C0:CE] Y[0:CE, C0:CE]^T on the lower tiles of A (block rows
+// C0.. are new: overwritten).  That corner of A is dead (panels < CE of L are final) and
+// disjoint from R.  The updates wait for nothing but their panel of Y and grow towards the
+// end of the sweep, where the two chains leave most of the GPU idle: lowest priority.
+template <class T>
+static void kinv_accumulate(gogp_handle *h, const T *Y, T *A, int64_t C0, int64_t CE) {
+  (void)gogp::rec_stream_wait(h->sk, ev(h, EV_BASE + 4 * (size_t)(C0 / PANEL) + 2));
+  GemmGrid gk;
+  gk.new_row0 = (int)(C0 / TILE);
+  if (h->krag) gk.krag0 = (int)(C0 / TILE);
+  launch_gemm_nt(h->sk, GEMM_LOWER, (int)(CE / TILE), (int)(CE / TILE), CE - C0, 1.0, Y + C0, h->npad, Y + C0, h->npad,
+                 1.0, A, h->npad, &h->prof, &gk);
+}
+
+// R of the triangular inverse := 0: the strictly upper block triangle of bufA, or of the mixed gradient's float buffer
+template <class T>
+static void zero_inverse_rhs(gogp_handle *h, bool mixed, hipStream_t s) {
+  if (mixed)
+    launch_zero_upper_blocks(s, h->g32A, h->npad, h->npad);
+  else
+    launch_zero_upper_blocks(s, reinterpret_cast<T *>(h->bufA), h->npad, h->npad);
+}
+// one super-step of the inverse in the handle's own buffers or the mixed gradient's (chain on st, bulk updates on s2),
+// with fuse_kinv its panel's share of K^-1 behind it
+template <class T>
+static void inverse_superstep(gogp_handle *h, bool mixed, const SuperPanel &P, hipStream_t st, hipStream_t s2,
+                              bool fuse_kinv) {
+  if (mixed) {
+    mixed_superstep(h, P, st, s2);
+    if (fuse_kinv) kinv_accumulate<float>(h, h->g32Y, h->g32A, P.C0(), P.CE());
+  } else {
+    const InvBufs<T> B{reinterpret_cast<T *>(h->bufA), reinterpret_cast<T *>(h->bufY), reinterpret_cast<const T *>(h->bufL),
+                       reinterpret_cast<const T *>(h->Dinv)};
+    trtri_superstep<T>(h, B, P, st, s2);
+    if (fuse_kinv) kinv_accumulate<T>(h, B.Y, B.A, P.C0(), P.CE());
   }
 }
 
@@ -854,7 +901,7 @@ static void mixed_superstep(gogp_handle *h, int P0, int nsub, int prevP0, int ne
 // 0: the 256-block kernel factors and inverts the diagonal block on one compute unit, then a K = 256 panel solve on the
 // tile kernel.  2: the chain per 128 columns is ONE launch (panel128.hip: every workgroup factors the diagonal 128-block
 // redundantly and forward-substitutes its own 64 panel rows on the way: no block inverse and no solve launch on the
-// chain); the 256 x 256 block inverses are formed off the chain from the finished factor (dinv_blocks below).
+// chain); the 256 x 256 block inverses are formed off the chain from the finished factor (Sweep::panels_final).
 // -1 (default): 2 where the evaluation is latency-bound (npad <= 8192) and wherever no inverse runs beside the
 // factorisation (Absorb, eager = 0); 0 above that size beside the inverse, where the GPU is throughput-bound and the
 // redundant factorisations of form 2 cost more than its shorter chain saves.  Measured (tools/split_probe.py, DESIGN.md
@@ -871,299 +918,310 @@ static void fused_panel(gogp_handle *h, hipStream_t sp, double *A, double *L, in
                         GemmProfile *pf) {
   const int64_t c1 = c0 + TILE, c2 = c0 + PANEL;
   const int mt1 = (int)((npad - c1) / TILE);
-  GemmGrid gch;
-  gch.prio = chain_prio_of(h);
+  const GemmGrid gch = chain_grid(h);
   launch_panel128_slabs(sp, A + c0 * ld + c0, ld, L + c0 * ld + c0, ld, 0, npad - c1, c0, h->n, h->info, h->chain_slabs);
   launch_gemm_nt(sp, GEMM_RECT, mt1, 1, TILE, -1.0, L + c1 * ld + c0, ld, L + c1 * ld + c0, ld, 1.0, A + c1 * ld + c1, ld,
                  pf, &gch);
   launch_panel128_slabs(sp, A + c0 * ld + c0, ld, L + c0 * ld + c0, ld, 1, npad - c2, c0, h->n, h->info, h->chain_slabs);
 }
-static void fused_panel(gogp_handle *, hipStream_t, float *, float *, int64_t, int64_t, int64_t, GemmProfile *) {}
-static void dinv_blocks(hipStream_t s, const double *L, double *Dinv, int64_t ld, int P0, int nsub) {
-  launch_dinv256_blocks(s, L + (int64_t)P0 * PANEL * (ld + 1), ld, Dinv + (size_t)P0 * PANEL * PANEL, nsub);
-}
-static void dinv_blocks(hipStream_t, const float *, float *, int64_t, int, int) {}
 
-template <class T>
-static int factorize_t(gogp_handle *h, bool eager) {
-  const int64_t npad = h->npad, ld = npad;
-  hipStream_t s = h->s;
-  // without lookahead everything runs in order on the main stream
-  hipStream_t sp = h->lookahead ? h->sp : h->s;
-  // streams of the fused triangular-inverse sweep (only with lookahead + eager)
-  eager = eager && h->lookahead;
-  hipStream_t st = h->st, s2 = h->s2;
-  if (h->trtri_pending) {
-    // a previous Observe left its triangular inverse running: it reads L / Dinv
-    (void)gogp::rec_stream_wait(s, ev(h, EV_TRTRI));
-    (void)gogp::rec_stream_wait(sp, ev(h, EV_TRTRI));
-    h->trtri_pending = false;
-  }
-  if (h->kinv_pending) {
-    // ... and K^-1 accumulating in bufA
-    (void)gogp::rec_stream_wait(s, ev(h, EV_KINV));
-    (void)gogp::rec_stream_wait(sp, ev(h, EV_KINV));
-    h->kinv_pending = false;
-  }
-  if (h->kinv_c1 > 0 && !h->have_kinv) {
-    // ... or the first of K^-1's two launches (option "kinv_split") that no Gradient picked up
-    (void)gogp::rec_stream_wait(s, ev(h, EV_KINV));
-    (void)gogp::rec_stream_wait(sp, ev(h, EV_KINV));
-  }
+// ---- what every evaluation starts and ends with -------------------------------------------------------------------------
+// Entry of an evaluation that makes a new factor: `streams` -- the ones that write L, Dinv and bufA first -- wait for
+// what a previous evaluation left running, and everything the handle says about the old factor is reset, here only.
+static void begin_evaluation(gogp_handle *h, std::initializer_list<hipStream_t> streams) {
+  auto wait = [&](int e) {
+    for (hipStream_t q : streams) (void)gogp::rec_stream_wait(q, ev(h, e));
+  };
+  if (h->trtri_pending) wait(EV_TRTRI);  // a previous Observe left its triangular inverse running: it reads L / Dinv
+  if (h->kinv_pending) wait(EV_KINV);    // ... and K^-1 accumulating in bufA
+  // ... or the first of K^-1's two launches (option "kinv_split") that no Gradient picked up
+  if (h->kinv_c1 > 0 && !h->have_kinv) wait(EV_KINV);
+  h->trtri_pending = h->kinv_pending = false;
   h->factored = h->have_alpha = h->have_kinv = h->grad_valid = false;
-  h->alpha_pending = false;
-  h->trtri_done = false;
+  h->alpha_pending = h->trtri_done = h->ydone_valid = h->d64_active = false;
   h->notpd = -1;
   h->kinv_c1 = 0;
+  if (!h->batch_mode) h->tinv_valid = false;  // Produce assembles T^-1 of the new factor on its first call
+}
+// the factorisation's scalars and its pivot word on their way to the pinned row(s) that judge_scalars reads
+static hipError_t enqueue_result_scalars(gogp_handle *h, hipStream_t s) {
+  const hipError_t e = cand_d2h(h, h->hscal, h->scalars, 7 * sizeof(double), s);
+  return e != hipSuccess ? e : cand_d2h(h, h->hscal + HS_INFO, h->info, sizeof(long long), s);
+}
+
+// dst = L^-1 w (fwd) / L^-T src (bwd) on stream q, one step per 256-panel.  The steps use up w; bwd copies src there first.
+template <class T>
+static void substitute_fwd(gogp_handle *h, hipStream_t q, const T *L, const T *Dinv, double *w, double *dst) {
+  const int npanel = (int)(h->npad / PANEL);
+  for (int b = 0; b < npanel; ++b) launch_trsv_fwd_step(q, L, h->npad, Dinv, b, npanel, w, dst);
+}
+template <class T>
+static hipError_t substitute_bwd(gogp_handle *h, hipStream_t q, const T *L, const T *Dinv, const double *src, double *w,
+                                 double *dst) {
+  const int npanel = (int)(h->npad / PANEL);
+  const hipError_t e = hipMemcpyAsync(w, src, (size_t)h->npad * sizeof(double), hipMemcpyDeviceToDevice, q);
+  for (int b = npanel - 1; b >= 0 && e == hipSuccess; --b) launch_trsv_bwd_step(q, L, h->npad, Dinv, b, npanel, w, dst);
+  return e;
+}
+
+// ---- the sweep in stages ---------------------------------------------------------------------------------------------------
+// What the stages of one factorize_t share: the matrices in the handle's element type, the streams, and what the options
+// choose.  The stages stand in the order they enqueue; factorize_t below them is the algorithm.
+template <class T>
+struct Sweep {
+  static constexpr bool fp32 = sizeof(T) == 4;
+  gogp_handle *h;
+  bool eager;  // the triangular inverse runs behind the sweep, on st and s2 (needs lookahead)
+  T *A = reinterpret_cast<T *>(h->bufA), *L = reinterpret_cast<T *>(h->bufL), *Dinv = reinterpret_cast<T *>(h->Dinv);
+  int64_t npad = h->npad, ld = npad;
+  int npanel = (int)(npad / PANEL);
+  GemmProfile *pf = &h->prof;
+  hipStream_t s = h->s, st = h->st, s2 = h->s2;
+  hipStream_t sp = h->lookahead ? h->sp : h->s;  // without lookahead everything runs in order on the main stream
+  // The forward substitution z = L^-1 y needs each panel once it is final and nothing
+  // needs z before the end: it runs on the low-priority stream, off the chain.
+  hipStream_t sz = h->lookahead ? h->sl : sp;
+  bool mixed = !fp32 && mixed_gradient(h);
   // option "kinv_fused": -1 (default) fuses up to npad = 10240 (measured: N = 1024 .. 8192 5-10 % faster,
   // N = 16384 1.7 % slower than one LAUUM launch over the finished Y, which runs at the longest K)
   // (the mixed gradient fuses at every size: its rank-k updates are fp32 and fill CUs the fp64 Cholesky chain leaves
   // idle -- N = 16384: 52.2 -> 51.1 ms)
-  const bool fuse_kinv = eager && (h->kinv_fused < 0 ? (npad <= 10240 || (std::is_same<T, double>::value && mixed_gradient(h)))
-                                                     : h->kinv_fused != 0);
-  int rc = gogp_upload_params(h);
-  if (rc != GOGP_OK) return rc;
-  const bool mixed = std::is_same<T, double>::value && mixed_gradient(h);
-  if (eager && !mixed) {
-    rc = ensure_y(h);
-    if (rc != GOGP_OK) return rc;
-  }
-  if (mixed) {
-    rc = ensure_g32(h);
-    if (rc != GOGP_OK) return rc;
-  }
-  // the panel stream joins whatever the main stream still holds from the previous call
-  // (bufA's last readers) and the parameter upload
-  if (sp != s) order(h, EV_ENTRY, s, sp);
-  HIPCHK(h, cand_memset(h, h->info, sizeof(long long), sp));
-  // Gram matrix: the first super-panel's block columns on the panel stream -- the chain
-  // starts ~30 us later instead of after the whole 0.5 ms build -- the rest on the main stream
-  {
-    AuxTimer tm(h, GOGP_PROF_GRAM, s);  // the main-stream part: all but the first block columns
-    launch_gram_lower_split(sp, s, h->devP, h->D, h->dX, h->n, npad, reinterpret_cast<T *>(h->bufA), ld,
-                            (int64_t)superpanel_width(h, (int)(npad / PANEL), 0) * PANEL, h->ev());
-  }
-  // fp32 path, option "diag_fp64": the diagonal blocks leave the float matrix here -- widened once, every later
-  // contribution summed in fp64 (diagsyrk.hip); the first super-panel's on the chain stream, the rest behind the build
-  h->d64_active = sizeof(T) == 4 && h->diag_fp64 != 0;
-  if (h->d64_active) {
-    rc = ensure_d64(h);
-    if (rc != GOGP_OK) return rc;
-    const int np = (int)(npad / PANEL), w0 = std::min(np, superpanel_width(h, np, 0));
-    d64_init(h, sp, reinterpret_cast<const T *>(h->bufA), ld, 0, w0);
-    if (np > w0) d64_init(h, s, reinterpret_cast<const T *>(h->bufA), ld, w0, np - w0);
-  }
-  (void)gogp::rec_event_record(ev(h, EV_GRAM), s);  // the whole lower triangle is written (s after sp's part
-                                            // is NOT implied: consumers of columns < 512 are on sp)
-  if (eager) {
-    // R := 0 on the strictly upper block triangle (after whatever used bufA last)
-    (void)gogp::rec_stream_wait(s2, ev(h, EV_GRAM));
-    (void)gogp::rec_stream_wait(st, ev(h, EV_GRAM));
-    if (mixed)
-      launch_zero_upper_blocks(s2, h->g32A, ld, npad);  // R lives in the float buffer of the mixed gradient
-    else
-      launch_zero_upper_blocks(s2, reinterpret_cast<T *>(h->bufA), ld, npad);
-    order(h, EV_INIT, s2, st);  // st also writes R (updates inside a super-panel)
-  }
-  T *A = reinterpret_cast<T *>(h->bufA), *L = reinterpret_cast<T *>(h->bufL);
-  T *Dinv = reinterpret_cast<T *>(h->Dinv);
-  GemmProfile *pf = &h->prof;
-  const int npanel = (int)(npad / PANEL);
+  bool fuse_kinv = eager && (h->kinv_fused < 0 ? (npad <= 10240 || mixed) : h->kinv_fused != 0);
+  int split = fp32 ? 0 : chain_split_of(h, eager);  // the form of the chain: 0 or 2
 
-  if (!h->batch_mode) h->tinv_valid = false;  // Produce assembles T^-1 of the new factor on its first call
-  if (sizeof(T) == 4) HIPCHK(h, hipMemsetAsync(h->scalars + 5, 0, sizeof(double), sp));  // fp64 logdet
-  // working copy of y for the forward substitution (runs on the panel stream)
-  HIPCHK(h, cand_copy_in(h, h->w, h->dy, (size_t)npad * sizeof(double), sp));
-  // The forward substitution z = L^-1 y needs each panel once it is final and nothing
-  // needs z before the end: it runs on the low-priority stream, off the chain.
-  hipStream_t sz = h->lookahead ? h->sl : sp;
-  if (sz != sp) order(h, EV_W, sp, sz);
-  // Right-looking blocked Cholesky in super-panels of SW 256-wide panels: the
-  // dependency chain (diagonal blocks, panel solves, updates inside the
-  // super-panel) runs on the panel stream with 256-wide steps; the trailing
-  // matrix gets ONE rank-(SW*256) update per super-panel on the main stream
-  // (next super-panel's block columns first: look-ahead).
-  const int split = std::is_same<T, double>::value ? chain_split_of(h, eager) : 0;  // the form of the chain: 0 or 2
-  int prevP0 = -1;
-  for (int P0 = 0, nsub = 0; P0 < npanel; prevP0 = P0, P0 += nsub) {
-    nsub = superpanel_width(h, npanel, P0);
-    const int next_nsub = (P0 + nsub < npanel) ? superpanel_width(h, npanel, P0 + nsub) : 0;
-    const int64_t C0 = (int64_t)P0 * PANEL, CE = C0 + (int64_t)nsub * PANEL;
-    for (int q = 0; q < nsub; ++q) {
-      const int p = P0 + q;
+  // fp32 path, option "diag_fp64": blocks first .. first + nblk - 1 of the fp64 strip := those of the float matrix, widened
+  void d64_init(hipStream_t q, int first, int nblk) const {
+    if constexpr (fp32)
+      launch_widen_diag_blocks(q, A + (int64_t)first * PANEL * (ld + 1), ld, h->D64 + (size_t)first * PANEL * PANEL, nblk);
+  }
+  // ... -= their rows of L[:, k0 : k0 + K] times themselves (float operands, fp64 sums); nothing without the option
+  void d64_update(hipStream_t q, int64_t k0, int64_t K, int first, int nblk) const {
+    if constexpr (fp32) {
+      if (h->d64_active)
+        launch_diag_syrk_f64(q, L + (int64_t)first * PANEL * ld + k0, ld, K, h->D64 + (size_t)first * PANEL * PANEL, nblk);
+    }
+  }
+
+  // The Gram matrix into A, the fp64 strip of its diagonal blocks, and R := 0 for the inverse behind the sweep
+  int build_gram() const {
+    // the panel stream joins whatever the main stream still holds from the previous call
+    // (bufA's last readers) and the parameter upload
+    if (sp != s) order(h, EV_ENTRY, s, sp);
+    HIPCHK(h, cand_memset(h, h->info, sizeof(long long), sp));
+    const int w0 = superpanel_width(h, npanel, 0);
+    // Gram matrix: the first super-panel's block columns on the panel stream -- the chain
+    // starts ~30 us later instead of after the whole 0.5 ms build -- the rest on the main stream
+    {
+      AuxTimer tm(h, GOGP_PROF_GRAM, s);  // the main-stream part: all but the first block columns
+      launch_gram_lower_split(sp, s, h->devP, h->D, h->dX, h->n, npad, A, ld, (int64_t)w0 * PANEL, h->ev());
+    }
+    // fp32 path, option "diag_fp64": the diagonal blocks leave the float matrix here -- widened once, every later
+    // contribution summed in fp64 (diagsyrk.hip); the first super-panel's on the chain stream, the rest behind the build
+    h->d64_active = fp32 && h->diag_fp64 != 0;
+    if (h->d64_active) {
+      const int rc = ensure_d64(h);
+      if (rc != GOGP_OK) return rc;
+      d64_init(sp, 0, w0);
+      if (npanel > w0) d64_init(s, w0, npanel - w0);
+    }
+    (void)gogp::rec_event_record(ev(h, EV_GRAM), s);  // the whole lower triangle is written (s after sp's part
+                                              // is NOT implied: consumers of columns < 512 are on sp)
+    if (eager) {
+      // R := 0 on the strictly upper block triangle (after whatever used bufA last)
+      (void)gogp::rec_stream_wait(s2, ev(h, EV_GRAM));
+      (void)gogp::rec_stream_wait(st, ev(h, EV_GRAM));
+      zero_inverse_rhs<T>(h, mixed, s2);
+      order(h, EV_INIT, s2, st);  // st also writes R (updates inside a super-panel)
+    }
+    return GOGP_OK;
+  }
+
+  // The dependency chain of one super-panel, in 256-wide steps: diagonal block, panel solve, updates inside it
+  void chain_superpanel(const SuperPanel &P) const {
+    const int64_t CE = P.CE();
+    for (int q = 0; q < P.nsub; ++q) {
+      const int p = P.P0 + q;
       const int64_t c0 = (int64_t)p * PANEL, c2 = c0 + PANEL;
-      T *Dp = Dinv + (size_t)p * PANEL * PANEL;
-      const int mt2 = (int)((npad - c2) / TILE);
-      if (split)
-        fused_panel(h, sp, A, L, ld, c0, npad, pf);
-      else  // 256x256 diagonal block: factor + dense inverse, one workgroup
-        diag_block(h, sp, A + c0 * ld + c0, ld, L + c0 * ld + c0, ld, Dp, c0);
-      // L[c2:, c0:c2] = A[c2:, c0:c2] * inv(L_pp)^T   (one K=256 GEMM)
-      if (mt2 > 0 && !split) {
-        GemmGrid gtri;  // Dp is lower triangular: the first tile column only needs k < 128
-        gtri.ktri = h->ktri;
-        gtri.prio = chain_prio_of(h);
-        launch_gemm_nt(sp, GEMM_RECT, mt2, 2, PANEL, 1.0, A + c2 * ld + c0, ld, Dp, PANEL, 0.0,
-                        L + c2 * ld + c0, ld, pf, &gtri);
+      if constexpr (!fp32) {
+        if (split) fused_panel(h, sp, A, L, ld, c0, npad, pf);
       }
-      // fp32 path: the rest of the super-panel's diagonal blocks take this panel's contribution in fp64
-      if (h->d64_active && c2 < CE) d64_update(h, sp, L, ld, c0, PANEL, p + 1, (int)((CE - c2) / PANEL));
-      // Updates inside the super-panel, grouped like a binary counter: after panel q the
-      // next g = lowbit(q+1) block columns receive the LAST g panels at once (K = 256 g), each
-      // column from its own diagonal block down (the blocks above belong to R of the fused
-      // triangular inverse) -- one trapezoid launch.  Every block column has all earlier
-      // panels of the super-panel when its turn comes; for two panels per super-panel this is
-      // the single K=256 update of the second column.
+      if (!split) {
+        T *Dp = Dinv + (size_t)p * PANEL * PANEL;
+        // 256x256 diagonal block: factor + dense inverse, one workgroup
+        diag_block(h, sp, A + c0 * ld + c0, ld, L + c0 * ld + c0, ld, Dp, c0);
+        // L[c2:, c0:c2] = A[c2:, c0:c2] * inv(L_pp)^T   (one K=256 GEMM)
+        const int mt2 = (int)((npad - c2) / TILE);
+        if (mt2 > 0) {
+          GemmGrid gtri = chain_grid(h);  // Dp is lower triangular: the first tile column only needs k < 128
+          gtri.ktri = h->ktri;
+          launch_gemm_nt(sp, GEMM_RECT, mt2, 2, PANEL, 1.0, A + c2 * ld + c0, ld, Dp, PANEL, 0.0,
+                          L + c2 * ld + c0, ld, pf, &gtri);
+        }
+      }
       if (c2 < CE) {
-        const int done = q + 1, grp = done & -done;
-        const int64_t k0 = c2 - (int64_t)grp * PANEL;
-        const int64_t ce = (c2 + (int64_t)grp * PANEL < CE) ? c2 + (int64_t)grp * PANEL : CE;
-        GemmGrid gch;
-        gch.prio = chain_prio_of(h);
-        launch_gemm_nt(sp, GEMM_TRAP, (int)((npad - c2) / TILE), (int)((ce - c2) / TILE),
-                        (int64_t)grp * PANEL, -1.0, L + c2 * ld + k0, ld, L + c2 * ld + k0, ld, 1.0,
+        // fp32 path: the rest of the super-panel's diagonal blocks take this panel's contribution in fp64
+        d64_update(sp, c0, PANEL, p + 1, (int)((CE - c2) / PANEL));
+        // The updates inside the super-panel (inner_group), each column from its own diagonal block down (the
+        // blocks above belong to R of the fused triangular inverse) -- one trapezoid launch.
+        const InnerGroup g = inner_group(q, c2, CE);
+        const GemmGrid gch = chain_grid(h);
+        launch_gemm_nt(sp, GEMM_TRAP, (int)((npad - c2) / TILE), (int)((g.ce - c2) / TILE),
+                        (int64_t)g.grp * PANEL, -1.0, L + c2 * ld + g.k0, ld, L + c2 * ld + g.k0, ld, 1.0,
                         A + c2 * ld + c2, ld, pf, &gch);
       }
     }
-    order(h, EV_BASE + 4 * P0, sp, s);  // panels P0 .. P0+nsub-1 of L are final
-    if (sz != sp) (void)gogp::rec_stream_wait(sz, ev(h, EV_BASE + 4 * P0));
+  }
 
-    if (split) {
-      // the inverses of the super-panel's diagonal blocks, off the chain: the substitution steps right below and the
-      // triangular inverse (st) are their first readers
-      dinv_blocks(sz, L, Dinv, ld, P0, nsub);
-      if (eager) {
-        (void)gogp::rec_event_record(ev(h, EV_BASE + 5 * (size_t)npanel + 32 + (size_t)P0), sz);
-        (void)gogp::rec_stream_wait(st, ev(h, EV_BASE + 5 * (size_t)npanel + 32 + (size_t)P0));
+  // Panels P0 .. P0+nsub-1 of L are final: off the chain, chain form 2's block inverses and the substitution's steps
+  void panels_final(const SuperPanel &P) const {
+    order(h, EV_BASE + 4 * P.P0, sp, s);
+    if (sz != sp) (void)gogp::rec_stream_wait(sz, ev(h, EV_BASE + 4 * P.P0));
+    if constexpr (!fp32) {
+      if (split) {
+        // the inverses of the super-panel's diagonal blocks, off the chain: the substitution steps right below and the
+        // triangular inverse (st) are their first readers
+        launch_dinv256_blocks(sz, L + (int64_t)P.P0 * PANEL * (ld + 1), ld, Dinv + (size_t)P.P0 * PANEL * PANEL, P.nsub);
+        if (eager) {
+          (void)gogp::rec_event_record(ev(h, EV_BASE + 5 * (size_t)npanel + 32 + (size_t)P.P0), sz);
+          (void)gogp::rec_stream_wait(st, ev(h, EV_BASE + 5 * (size_t)npanel + 32 + (size_t)P.P0));
+        }
       }
     }
-    for (int q = 0; q < nsub; ++q)
-      launch_trsv_fwd_step(sz, L, ld, Dinv, P0 + q, npanel, h->w, h->z);
-    // ---- trailing update, rank nsub*256 ------------------------------------------------------
+    for (int q = 0; q < P.nsub; ++q) launch_trsv_fwd_step(sz, L, ld, Dinv, P.P0 + q, npanel, h->w, h->z);
+  }
+
+  // The super-panel's rank-(nsub*256) update of the trailing matrix
+  void trailing_update(const SuperPanel &P) const {
+    const int64_t C0 = P.C0(), CE = P.CE();
     const int mtE = (int)((npad - CE) / TILE);
-    if (mtE > 0) {
-      const int64_t Kw = CE - C0;
-      const int ntn = mtE < 2 * next_nsub ? mtE : 2 * next_nsub;
-      // The next super-panel's block columns, each from its diagonal block down, stay on the
-      // CHAIN stream: the critical path (diag -> panel solve -> these updates -> diag) then
-      // never crosses streams (two event hops of ~15 us per super-panel otherwise).  They
-      // only wait for the previous super-panel's bulk update of these columns, which in
-      // steady state finished long ago.
-      (void)gogp::rec_stream_wait(sp, ev(h, P0 > 0 ? EV_BASE + 4 * prevP0 + 1 : EV_GRAM));
-      // ONE trapezoid launch for all of them (rows CE.., columns CE .. CE + ntn*128, the
-      // strictly upper 256-blocks -- R of the triangular inverse -- skipped): separate
-      // launches would run one after the other on this in-order stream
-      GemmGrid gch;
-      gch.prio = chain_prio_of(h);
-      launch_gemm_nt(sp, GEMM_TRAP, mtE, ntn, Kw, -1.0, L + CE * ld + C0, ld, L + CE * ld + C0, ld,
-                      1.0, A + CE * ld + CE, ld, pf, &gch);
-      // fp32 path: ... and so do the next super-panel's diagonal blocks, in fp64 (diagsyrk.hip)
-      if (h->d64_active) d64_update(h, sp, L, ld, C0, Kw, (int)(CE / PANEL), ntn / 2);
-      // the rest of the trailing matrix, lower tiles only (main stream)
-      if (mtE > ntn) {
-        const int64_t C3 = CE + (int64_t)ntn * TILE;
-        launch_gemm_nt(s, GEMM_LOWER, mtE - ntn, mtE - ntn, Kw, -1.0, L + C3 * ld + C0, ld,
-                        L + C3 * ld + C0, ld, 1.0, A + C3 * ld + C3, ld, pf);
-        if (h->d64_active) d64_update(h, s, L, ld, C0, Kw, (int)(C3 / PANEL), (mtE - ntn) / 2);
-      }
-      (void)gogp::rec_event_record(ev(h, EV_BASE + 4 * P0 + 1), s);  // bulk update of super-panel P0 done
+    if (mtE <= 0) return;
+    const int64_t Kw = CE - C0;
+    const int ntn = mtE < 2 * P.next_nsub ? mtE : 2 * P.next_nsub;
+    // The next super-panel's block columns, each from its diagonal block down, stay on the
+    // CHAIN stream: the critical path (diag -> panel solve -> these updates -> diag) then
+    // never crosses streams (two event hops of ~15 us per super-panel otherwise).  They
+    // only wait for the previous super-panel's bulk update of these columns, which in
+    // steady state finished long ago.
+    (void)gogp::rec_stream_wait(sp, ev(h, P.P0 > 0 ? EV_BASE + 4 * P.prevP0 + 1 : EV_GRAM));
+    // ONE trapezoid launch for all of them (rows CE.., columns CE .. CE + ntn*128, the
+    // strictly upper 256-blocks -- R of the triangular inverse -- skipped): separate
+    // launches would run one after the other on this in-order stream
+    const GemmGrid gch = chain_grid(h);
+    launch_gemm_nt(sp, GEMM_TRAP, mtE, ntn, Kw, -1.0, L + CE * ld + C0, ld, L + CE * ld + C0, ld,
+                    1.0, A + CE * ld + CE, ld, pf, &gch);
+    // fp32 path: ... and so do the next super-panel's diagonal blocks, in fp64 (diagsyrk.hip)
+    d64_update(sp, C0, Kw, (int)(CE / PANEL), ntn / 2);
+    // the rest of the trailing matrix, lower tiles only (main stream)
+    if (mtE > ntn) {
+      const int64_t C3 = CE + (int64_t)ntn * TILE;
+      launch_gemm_nt(s, GEMM_LOWER, mtE - ntn, mtE - ntn, Kw, -1.0, L + C3 * ld + C0, ld,
+                      L + C3 * ld + C0, ld, 1.0, A + C3 * ld + C3, ld, pf);
+      d64_update(s, C0, Kw, (int)(C3 / PANEL), (mtE - ntn) / 2);
     }
-    // ---- fused sweep: the same super-step of the triangular inverse right behind ----------
-    if (eager) {
-      (void)gogp::rec_stream_wait(st, ev(h, EV_BASE + 4 * P0));
-      if (mixed)
-        mixed_superstep(h, P0, nsub, prevP0, next_nsub, st, s2, fuse_kinv);
-      else
-        trtri_superstep<T>(h, own_bufs<T>(h), P0, nsub, prevP0, next_nsub, st, s2);
-      if (std::is_same<T, double>::value && !fuse_kinv && !mixed && !h->batch_mode && h->kinv_split > 0 &&
-          h->kinv_c1 == 0 && CE < npad && CE * 100 >= npad * (int64_t)h->kinv_split) {
-        // ---- option "kinv_split" (sizes above the fused ones): the part of K^-1 = Y Y^T that the finished column
-        // panels of Y determine -- K^-1[0:CE, 0:CE] = sum over k < CE -- as ONE ragged-K launch now, at the lowest
-        // priority, into the dead corner of bufA (as the fused updates below); Gradient's launch then only sums
-        // k >= CE on top of it, in the same order of k: bit-identical.  N = 16384, alternating runs on one box:
-        // 71.98-72.19 ms without, 71.65-71.85 with 60 % (50 %: 71.8, 30-40 %: 72.0, 80 %: 71.75, 90 %: 72.2);
-        // N = 32768: no difference (547.5 / 550.7 against 550.0 / 547.6).
-        (void)gogp::rec_stream_wait(h->sk, ev(h, EV_BASE + 4 * P0 + 2));
-        const T *Y0 = reinterpret_cast<const T *>(h->bufY);
-        launch_gemm_nt(h->sk, GEMM_LAUUM, (int)(CE / TILE), (int)(CE / TILE), CE, 1.0, Y0, ld, Y0, ld, 0.0, A, ld, pf);
-        (void)gogp::rec_event_record(ev(h, EV_KINV), h->sk);
-        h->kinv_c1 = CE;
-      }
-      if (fuse_kinv && !mixed) {
-        // ---- and K^-1 = Y Y^T = sum over the column panels of Y, right behind: the rank-(nsub*256)
-        // update K^-1[0:CE, 0:CE] (+)= Y[0:CE, C0:CE] Y[0:CE, C0:CE]^T on the lower tiles (block rows
-        // C0.. are new: overwritten).  That corner of bufA is dead (panels < CE of L are final) and
-        // disjoint from R.  The updates wait for nothing but their panel of Y and grow towards the
-        // end of the sweep, where the two chains leave most of the GPU idle: lowest priority.
-        (void)gogp::rec_stream_wait(h->sk, ev(h, EV_BASE + 4 * P0 + 2));
-        GemmGrid gk;
-        gk.new_row0 = (int)(C0 / TILE);
-        if (h->krag) gk.krag0 = (int)(C0 / TILE);
-        const T *Yp = reinterpret_cast<const T *>(h->bufY) + C0;
-        launch_gemm_nt(h->sk, GEMM_LOWER, (int)(CE / TILE), (int)(CE / TILE), CE - C0, 1.0, Yp, ld, Yp, ld,
-                       1.0, A, ld, pf, &gk);
-      }
+    (void)gogp::rec_event_record(ev(h, EV_BASE + 4 * P.P0 + 1), s);  // bulk update of super-panel P0 done
+  }
+
+  // The fused sweep: the same super-step of the triangular inverse right behind, and K^-1 behind that
+  void inverse_behind(const SuperPanel &P) const {
+    const int64_t CE = P.CE();
+    (void)gogp::rec_stream_wait(st, ev(h, EV_BASE + 4 * P.P0));
+    inverse_superstep<T>(h, mixed, P, st, s2, fuse_kinv);
+    if (!fp32 && !fuse_kinv && !mixed && !h->batch_mode && h->kinv_split > 0 && h->kinv_c1 == 0 && CE < npad &&
+        CE * 100 >= npad * (int64_t)h->kinv_split) {
+      // ---- option "kinv_split" (sizes above the fused ones): the part of K^-1 = Y Y^T that the finished column
+      // panels of Y determine -- K^-1[0:CE, 0:CE] = sum over k < CE -- as ONE ragged-K launch now, at the lowest
+      // priority, into the dead corner of bufA (as the fused updates: kinv_accumulate); Gradient's launch then only
+      // sums k >= CE on top of it, in the same order of k: bit-identical.  N = 16384, alternating runs on one box:
+      // 71.98-72.19 ms without, 71.65-71.85 with 60 % (50 %: 71.8, 30-40 %: 72.0, 80 %: 71.75, 90 %: 72.2);
+      // N = 32768: no difference (547.5 / 550.7 against 550.0 / 547.6).
+      (void)gogp::rec_stream_wait(h->sk, ev(h, EV_BASE + 4 * P.P0 + 2));
+      const T *Y0 = reinterpret_cast<const T *>(h->bufY);
+      launch_gemm_nt(h->sk, GEMM_LAUUM, (int)(CE / TILE), (int)(CE / TILE), CE, 1.0, Y0, ld, Y0, ld, 0.0, A, ld, pf);
+      (void)gogp::rec_event_record(ev(h, EV_KINV), h->sk);
+      h->kinv_c1 = CE;
     }
   }
-  if (fuse_kinv) {
+
+  // alpha = K^-1 y, one of three ways, around the result scalars' copies to the host: the refinement's scalar goes
+  // with them, the other two ways are not needed for the LML and follow them
+  int finish_alpha() const {
+    if (fp32) {
+      // fp32 path: alpha by substitution with the fp32 factor, then `refine_steps` steps of
+      // iterative refinement against the EXACT Gram matrix (recomputed in fp64 on the fly, never
+      // read back from its rounded copy): r = y - K alpha, alpha += K~^-1 r.  The quadratic term of
+      // the LML is y^T alpha of the refined alpha (fp64).  All of it on the chain stream, which is
+      // idle after the last panel; the triangular inverse keeps running on its own streams.
+      if (sz != sp) (void)gogp::rec_stream_wait(sp, ev(h, EV_FWD));
+      HIPCHK(h, substitute_bwd(h, sp, L, Dinv, h->z, h->w, h->alpha));
+      for (int it = 0; it < h->refine_steps; ++it) {
+        launch_residual(sp, h->devP, h->D, h->dX, h->n, npad, h->alpha, h->dy, h->rpart, REFINE_SLABS, h->rw,
+                        h->radial1, h->ev());
+        substitute_fwd(h, sp, L, Dinv, h->rw, h->rz);
+        HIPCHK(h, substitute_bwd(h, sp, L, Dinv, h->rz, h->rw, h->rd));
+        launch_axpy(sp, h->alpha, h->rd, npad);
+      }
+      launch_dot(sp, h->dy, h->alpha, h->n, h->scalars + 6);
+      order(h, EV_ALPHA, sp, s);
+    }
+    HIPCHK(h, enqueue_result_scalars(h, s));
+    if (fp32) {
+      if (eager) (void)gogp::rec_event_record(ev(h, EV_TRTRI), st);
+    } else if (eager && !mixed) {
+      // alpha = K^-1 y = Y (L^-1 y) = Y z: one bandwidth-bound pass over Y once the
+      // triangular inverse is complete (st), instead of 64 dependent substitution steps
+      (void)gogp::rec_stream_wait(st, ev(h, EV_FWD));
+      launch_alpha_from_y(st, reinterpret_cast<const T *>(h->bufY), ld, h->z, npad, h->alpha);
+      (void)gogp::rec_event_record(ev(h, EV_ALPHA), st);
+      (void)gogp::rec_event_record(ev(h, EV_TRTRI), st);
+    } else {
+      // backward substitution alpha = L^-T z on the panel stream: not needed for LML
+      if (sz != sp) (void)gogp::rec_stream_wait(sp, ev(h, EV_FWD));
+      HIPCHK(h, substitute_bwd(h, sp, L, Dinv, h->z, h->w, h->alpha));
+      (void)gogp::rec_event_record(ev(h, EV_ALPHA), sp);
+    }
+    return GOGP_OK;
+  }
+};
+
+// Right-looking blocked Cholesky in super-panels of SW 256-wide panels: the
+// dependency chain (diagonal blocks, panel solves, updates inside the
+// super-panel) runs on the panel stream with 256-wide steps; the trailing
+// matrix gets ONE rank-(SW*256) update per super-panel on the main stream
+// (next super-panel's block columns first: look-ahead).
+template <class T>
+static int factorize_t(gogp_handle *h, bool eager) {
+  const Sweep<T> c{h, eager && h->lookahead != 0};
+  begin_evaluation(h, {c.s, c.sp});
+  int rc = gogp_upload_params(h);
+  if (rc == GOGP_OK && (c.mixed || c.eager)) rc = c.mixed ? ensure_g32(h) : ensure_y(h);
+  if (rc == GOGP_OK) rc = c.build_gram();
+  if (rc != GOGP_OK) return rc;
+  if (c.fp32) HIPCHK(h, hipMemsetAsync(h->scalars + 5, 0, sizeof(double), c.sp));  // fp64 logdet
+  // working copy of y for the forward substitution, whose steps follow the chain on sz
+  HIPCHK(h, cand_copy_in(h, h->w, h->dy, (size_t)c.npad * sizeof(double), c.sp));
+  if (c.sz != c.sp) order(h, EV_W, c.sp, c.sz);
+  for (const SuperPanel &P : superpanels(h)) {
+    c.chain_superpanel(P);
+    c.panels_final(P);
+    c.trailing_update(P);
+    if (c.eager) c.inverse_behind(P);
+  }
+  if (c.fuse_kinv) {
     (void)gogp::rec_event_record(ev(h, EV_KINV), h->sk);
     h->kinv_pending = true;
   }
-
-  h->ydone_valid = false;
-  if (eager) {
-    (void)gogp::rec_event_record(ev(h, EV_TRTRI), st);
-    (void)gogp::rec_event_record(ev(h, EV_YDONE), st);  // K^-1 = Y Y^T may start here; alpha = Y z (below) runs beside it
-    h->ydone_valid = true;
-    h->trtri_done = true;
-    h->trtri_pending = true;
+  if (c.eager) {
+    (void)gogp::rec_event_record(ev(h, EV_TRTRI), c.st);
+    (void)gogp::rec_event_record(ev(h, EV_YDONE), c.st);  // K^-1 = Y Y^T may start here; alpha = Y z (finish_alpha) runs beside it
+    h->ydone_valid = h->trtri_done = h->trtri_pending = true;
   }
-  order(h, EV_FWD, sz, s);  // z complete
-  launch_lml_scalars(s, L, ld, h->z, nullptr, nullptr, h->n, h->scalars);
-  const bool refine = sizeof(T) == 4;
-  if (refine) {
-    // fp32 path: alpha by substitution with the fp32 factor, then `refine_steps` steps of
-    // iterative refinement against the EXACT Gram matrix (recomputed in fp64 on the fly, never
-    // read back from its rounded copy): r = y - K alpha, alpha += K~^-1 r.  The quadratic term of
-    // the LML is y^T alpha of the refined alpha (fp64).  All of it on the chain stream, which is
-    // idle after the last panel; the triangular inverse keeps running on its own streams.
-    if (sz != sp) (void)gogp::rec_stream_wait(sp, ev(h, EV_FWD));
-    HIPCHK(h, hipMemcpyAsync(h->w, h->z, (size_t)npad * sizeof(double), hipMemcpyDeviceToDevice, sp));
-    for (int b = npanel - 1; b >= 0; --b) launch_trsv_bwd_step(sp, L, ld, Dinv, b, npanel, h->w, h->alpha);
-    const size_t vb = (size_t)npad * sizeof(double);
-    for (int it = 0; it < h->refine_steps; ++it) {
-      launch_residual(sp, h->devP, h->D, h->dX, h->n, npad, h->alpha, h->dy, h->rpart, REFINE_SLABS, h->rw,
-                      h->radial1, h->ev());
-      for (int b = 0; b < npanel; ++b) launch_trsv_fwd_step(sp, L, ld, Dinv, b, npanel, h->rw, h->rz);
-      HIPCHK(h, hipMemcpyAsync(h->rw, h->rz, vb, hipMemcpyDeviceToDevice, sp));
-      for (int b = npanel - 1; b >= 0; --b) launch_trsv_bwd_step(sp, L, ld, Dinv, b, npanel, h->rw, h->rd);
-      launch_axpy(sp, h->alpha, h->rd, npad);
-    }
-    launch_dot(sp, h->dy, h->alpha, h->n, h->scalars + 6);
-    order(h, EV_ALPHA, sp, s);
-  }
-  HIPCHK(h, cand_d2h(h, h->hscal, h->scalars, 7 * sizeof(double), s));
-  HIPCHK(h, cand_d2h(h, h->hscal + HS_INFO, h->info, sizeof(long long), s));
-  if (refine) {
-    if (eager) (void)gogp::rec_event_record(ev(h, EV_TRTRI), st);
-  } else if (eager && !mixed) {
-    // alpha = K^-1 y = Y (L^-1 y) = Y z: one bandwidth-bound pass over Y once the
-    // triangular inverse is complete (st), instead of 64 dependent substitution steps
-    (void)gogp::rec_stream_wait(st, ev(h, EV_FWD));
-    launch_alpha_from_y(st, reinterpret_cast<const T *>(h->bufY), ld, h->z, npad, h->alpha);
-    (void)gogp::rec_event_record(ev(h, EV_ALPHA), st);
-    (void)gogp::rec_event_record(ev(h, EV_TRTRI), st);
-  } else {
-    // backward substitution alpha = L^-T z on the panel stream: not needed for LML
-    if (sz != sp) (void)gogp::rec_stream_wait(sp, ev(h, EV_FWD));
-    HIPCHK(h, hipMemcpyAsync(h->w, h->z, (size_t)npad * sizeof(double), hipMemcpyDeviceToDevice, sp));
-    for (int b = npanel - 1; b >= 0; --b)
-      launch_trsv_bwd_step(sp, L, ld, Dinv, b, npanel, h->w, h->alpha);
-    (void)gogp::rec_event_record(ev(h, EV_ALPHA), sp);
-  }
-  const int rcf = finish_factorize(h, sizeof(T) == 4, refine, false);
+  order(h, EV_FWD, c.sz, c.s);  // z complete
+  launch_lml_scalars(c.s, c.L, c.ld, h->z, nullptr, nullptr, h->n, h->scalars);
+  rc = c.finish_alpha();
+  if (rc != GOGP_OK) return rc;
+  const int rcf = finish_factorize(h, c.fp32, c.fp32, false);  // the fp32 path's alpha is the refined one
   if (rcf == GOGP_ENOTPD)  // nothing of the failed factorisation may still run on the other streams
-    for (hipStream_t q : {sp, st, s2, h->sl, h->sk}) (void)hipStreamSynchronize(q);
+    for (hipStream_t q : {c.sp, c.st, c.s2, h->sl, h->sk}) (void)hipStreamSynchronize(q);
   return rcf;
 }
 
@@ -1177,20 +1235,7 @@ static inline bool tiny_ok(const gogp_handle *h) {
 }
 static int tiny_factorize(gogp_handle *h, bool eager) {
   hipStream_t s = h->s;
-  for (bool *pend : {&h->trtri_pending, &h->kinv_pending}) {
-    if (*pend) {  // a previous (general-path) evaluation left its inverse running: it reads L / Dinv and writes bufA
-      (void)gogp::rec_stream_wait(s, ev(h, pend == &h->trtri_pending ? EV_TRTRI : EV_KINV));
-      *pend = false;
-    }
-  }
-  if (h->kinv_c1 > 0 && !h->have_kinv) (void)gogp::rec_stream_wait(s, ev(h, EV_KINV));
-  h->factored = h->have_alpha = h->have_kinv = h->grad_valid = false;
-  h->alpha_pending = false;
-  h->trtri_done = false;
-  h->ydone_valid = false;
-  h->notpd = -1;
-  h->kinv_c1 = 0;
-  h->d64_active = false;
+  begin_evaluation(h, {s});
   int rc = gogp_upload_params(h);
   if (rc != GOGP_OK) return rc;
   // whatever the chain / substitution streams still hold from a previous general-path call (the backward substitution of
@@ -1201,13 +1246,11 @@ static int tiny_factorize(gogp_handle *h, bool eager) {
     order(h, EV_ENTRY, h->sp, s);
     order(h, EV_W, h->sl, s);
   }
-  if (!h->batch_mode) h->tinv_valid = false;
   HIPCHK(h, cand_memset(h, h->info, sizeof(long long), s));
   launch_tiny_eval(s, h->devP, h->dX, h->dy, h->n, h->bufA, h->bufL, h->Dinv, h->z, h->alpha, h->info, eager, h->ev());
   launch_lml_scalars(s, h->bufL, h->npad, h->z, nullptr, nullptr, h->n, h->scalars);
   (void)gogp::rec_event_record(ev(h, EV_ALPHA), s);
-  HIPCHK(h, cand_d2h(h, h->hscal, h->scalars, 7 * sizeof(double), s));
-  HIPCHK(h, cand_d2h(h, h->hscal + HS_INFO, h->info, sizeof(long long), s));
+  HIPCHK(h, enqueue_result_scalars(h, s));
   return finish_factorize(h, false, false, eager);
 }
 
@@ -1345,21 +1388,9 @@ static int compute_kinv_t(gogp_handle *h) {
     hipStream_t sp = h->lookahead ? h->sp : h->s;
     const int rcy = mixed ? ensure_g32(h) : ensure_y(h);
     if (rcy != GOGP_OK) return rcy;
-    if (mixed)
-      launch_zero_upper_blocks(s, h->g32A, ld, npad);
-    else
-      launch_zero_upper_blocks(s, reinterpret_cast<T *>(h->bufA), ld, npad);
+    zero_inverse_rhs<T>(h, mixed, s);
     order(h, EV_INIT, s, sp);
-    const int npanel = (int)(npad / PANEL);
-    int prevP0 = -1;
-    for (int P0 = 0, nsub = 0; P0 < npanel; prevP0 = P0, P0 += nsub) {
-      nsub = superpanel_width(h, npanel, P0);
-      const int next_nsub = (P0 + nsub < npanel) ? superpanel_width(h, npanel, P0 + nsub) : 0;
-      if (mixed)
-        mixed_superstep(h, P0, nsub, prevP0, next_nsub, sp, s, false);
-      else
-        trtri_superstep<T>(h, own_bufs<T>(h), P0, nsub, prevP0, next_nsub, sp, s);
-    }
+    for (const SuperPanel &P : superpanels(h)) inverse_superstep<T>(h, mixed, P, sp, s, false);
     order(h, EV_TRTRI, sp, s);
     h->trtri_done = true;
   } else if (h->trtri_pending) {
