@@ -47,6 +47,12 @@ class CGemmOpts(ctypes.Structure):
                     cblk0=0, pr=0, Pr=1, pc=0, Pc=1, beta0=-1, k=1, bstride=0)
 
 
+class CGemmPlan(ctypes.Structure):
+    """gogp_test_gemm_plan_out (include/gogp_testhooks.h)."""
+    _fields_ = [("tile", ctypes.c_int32), ("waves", ctypes.c_int32), ("grid_x", ctypes.c_int64),
+                ("grid_z", ctypes.c_int64), ("flops", ctypes.c_double), ("tag", ctypes.c_int64)]
+
+
 SYMBOLS = [
     ("gogp_desc_check", ctypes.c_int, [_descp]),
     ("gogp_desc_ntheta_noise", ctypes.c_int, [_descp]),
@@ -129,6 +135,9 @@ HOOK_SYMBOLS = [
     ("gogp_test_gemm_nt", ctypes.c_int,
      [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _i64, ctypes.c_double, ctypes.c_double]
      + [ctypes.c_void_p, _i64, _i64, _i64] * 3 + [ctypes.POINTER(CGemmOpts)]),
+    ("gogp_test_gemm_plan", ctypes.c_int,
+     [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _i64, ctypes.POINTER(CGemmOpts),
+      ctypes.POINTER(CGemmPlan)]),
     ("gogp_test_diag_syrk", ctypes.c_int,
      [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, _i64, _i64, _i64, _i64, _i64, _dp, _i64, ctypes.c_int]),
     ("gogp_test_diag256_product", ctypes.c_int,

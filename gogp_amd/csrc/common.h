@@ -64,13 +64,13 @@ struct GemmProfile {
   double flops = 0;
   int64_t launches = 0;
   // per launch, in launch order (the events are pool[2i], pool[2i+1]): flops and a tag
-  // mode * 1e6 + tiles-across * 1e3... see gogp_profile_read_launches
+  // mode * 1e8 + (K / 16) * 1e5 + min(tiles, 99999) (gemm_plan.h) -- see gogp_profile_read_launches
   std::vector<double> lflops;
   std::vector<int64_t> ltag;
 };
 
 // Tile filter of the tile kernel in a sharded (2-D block-cyclic) evaluation (GemmArgs in
-// dgemm.hip): the launch covers LOCAL 128-tiles starting at local row / column block
+// gemm_tile.h): the launch covers LOCAL 128-tiles starting at local row / column block
 // rblk0 / cblk0 (a distribution block = 2^tpb_shift tiles); this rank sits at (pr, pc) of
 // the Pr x Pc process grid.  rule 1: keep the tiles of the GLOBAL lower triangle; rule 2:
 // the same, and tiles of global row block beta0 overwrite C (beta = 0) while the others
@@ -159,7 +159,7 @@ void launch_gemm_nt(hipStream_t s, GemmMode mode, int mt, int nt, int64_t K, dou
                     GemmProfile *prof, const GemmGrid *grid = nullptr);  // = launch_dgemm_nt
 void launch_gemm_nt(hipStream_t s, GemmMode mode, int mt, int nt, int64_t K, double alpha, const float *A,
                     int64_t lda, const float *B, int64_t ldb, double beta, float *C, int64_t ldc,
-                    GemmProfile *prof, const GemmGrid *grid = nullptr);  // sgemm.hip
+                    GemmProfile *prof, const GemmGrid *grid = nullptr);  // sgemm.hip; both: gemm_tile.h, launch_tile_gemm
 void launch_gram_lower_split(hipStream_t s_first, hipStream_t s_rest, const DevParams *p, int ndim,
                              const double *X, int64_t n, int64_t npad, float *K, int64_t ld,
                              int64_t wcols, bool ev = false);

@@ -5,6 +5,7 @@
 #include <stdio.h>
 
 #include "common.h"
+#include "gemm_plan.h"  // for gogp_test_gemm_plan
 #include "../../include/gogp_testhooks.h"
 
 struct gogp_handle;
@@ -237,32 +238,72 @@ bool device_ok(int device) {
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return false;
   return device < 0 || hipSetDevice(device) == hipSuccess;
 }
+// the launcher's arguments proper (no buffers): false for what the kernels cannot honour
+bool gemm_launch_args_ok(int precision, int mode, int mt, int nt, int64_t K, const gogp_test_gemm_opts &o) {
+  if (precision != 64 && precision != 32) return false;
+  if (mode < GEMM_RECT || mode > GEMM_TRAP || mt <= 0 || nt <= 0 || K <= 0) return false;
+  const int64_t kstep = precision == 64 ? GEMM_BK : SGEMM_BK, al = 16 / (precision / 8);  // al: elements per 16 B
+  if (K % kstep || K > (1 << 30)) return false;
+  if ((mode == GEMM_LOWER || mode == GEMM_LAUUM) && mt != nt) return false;
+  if (o.k < 1 || o.k > 64 || o.bstride < 0 || o.bstride % al || (o.k > 1 && o.bstride == 0)) return false;
+  if (precision == 32 && (o.k > 1 || o.kbeg0 != 0)) return false;  // the fp32 kernel has neither
+  if (o.kbeg0 < 0 || o.kbeg0 % kstep || o.kbeg0 > K || (o.kbeg0 && mode != GEMM_LAUUM)) return false;
+  if (o.new_row0 < -1 || (o.new_row0 >= 0 && mode != GEMM_LOWER)) return false;
+  if (o.ktri && mode != GEMM_RECT) return false;
+  if (o.krag0 < -1 || (o.krag0 >= 0 && (o.ktri || (mode != GEMM_RECT && mode != GEMM_LOWER)))) return false;
+  // the first k-step of tile row ti >= krag0 is loaded at k = (ti - krag0) * tile before the loop count is known
+  if (o.krag0 >= 0 && o.krag0 < mt && K < (int64_t)(mt - o.krag0) * TILE) return false;
+  if (o.rule < 0 || o.rule > 2 || (o.rule && mode != GEMM_RECT)) return false;
+  if (o.rule && (o.tpb_shift < 0 || o.tpb_shift > 8 || o.rblk0 < 0 || o.cblk0 < 0 || o.Pr < 1 || o.Pc < 1 ||
+                 o.pr < 0 || o.pr >= o.Pr || o.pc < 0 || o.pc >= o.Pc))
+    return false;
+  return true;
+}
+const gogp_test_gemm_opts GEMM_OPTS_DEFAULT = {0, -1, -1, 0, 384, 0, 0, 0, 0, 0, 0, 1, 0, 1, -1, 1, 0};
+GemmGrid gemm_grid_of(const gogp_test_gemm_opts &o) {
+  GemmGrid g;
+  g.ktri = o.ktri;
+  g.krag0 = o.krag0;
+  g.new_row0 = o.new_row0;
+  g.kbeg0 = o.kbeg0;
+  g.small_below = o.small_below;
+  g.prio = o.prio;
+  g.rule = o.rule;
+  g.tpb_shift = o.tpb_shift;
+  g.rblk0 = o.rblk0;
+  g.cblk0 = o.cblk0;
+  g.pr = o.pr;
+  g.Pr = o.Pr;
+  g.pc = o.pc;
+  g.Pc = o.Pc;
+  g.beta0 = o.beta0;
+  return g;
+}
 }  // namespace
+
+extern "C" int gogp_test_gemm_plan(int precision, int mode, int mt, int nt, int64_t K, const gogp_test_gemm_opts *opt,
+                                   gogp_test_gemm_plan_out *out) {
+  const gogp_test_gemm_opts o = opt ? *opt : GEMM_OPTS_DEFAULT;
+  if (!out || !gemm_launch_args_ok(precision, mode, mt, nt, K, o)) return GOGP_EARG;
+  const GemmGrid g = gemm_grid_of(o);
+  const GemmPlan p = gemm_plan((GemmMode)mode, mt, nt, K, &g, o.k, precision == 64 ? GEMM_F64 : GEMM_F32);
+  out->tile = p.tile;
+  out->waves = p.waves;
+  out->grid_x = p.gridx;
+  out->grid_z = p.gridz;
+  out->flops = p.flops;
+  out->tag = p.tag;
+  return GOGP_OK;
+}
 
 extern "C" int gogp_test_gemm_nt(int device, int precision, int mode, int mt, int nt, int64_t K, double alpha,
                                  double beta, const void *A, int64_t a_len, int64_t a_off, int64_t lda, const void *B,
                                  int64_t b_len, int64_t b_off, int64_t ldb, void *C, int64_t c_len, int64_t c_off,
                                  int64_t ldc, const gogp_test_gemm_opts *opt) {
-  gogp_test_gemm_opts o = {0, -1, -1, 0, 384, 0, 0, 0, 0, 0, 0, 1, 0, 1, -1, 1, 0};
-  if (opt) o = *opt;
-  if (!A || !B || !C || (precision != 64 && precision != 32)) return GOGP_EARG;
-  if (mode < GEMM_RECT || mode > GEMM_TRAP || mt <= 0 || nt <= 0 || K <= 0) return GOGP_EARG;
-  const int64_t es = precision / 8, kstep = precision == 64 ? GEMM_BK : 32, al = 16 / es;  // al: elements per 16 B
-  if (K % kstep || K > (1 << 30)) return GOGP_EARG;
-  if ((mode == GEMM_LOWER || mode == GEMM_LAUUM) && mt != nt) return GOGP_EARG;
+  const gogp_test_gemm_opts o = opt ? *opt : GEMM_OPTS_DEFAULT;
+  if (!A || !B || !C || !gemm_launch_args_ok(precision, mode, mt, nt, K, o)) return GOGP_EARG;
+  const int64_t es = precision / 8, al = 16 / es;  // al: elements per 16 B
   if (alpha == 0.0 || (precision == 32 && (float)alpha == 0.0f)) return GOGP_EARG;  // accumulators start at (beta/alpha) C
-  if (o.k < 1 || o.k > 64 || o.bstride < 0 || o.bstride % al || (o.k > 1 && o.bstride == 0)) return GOGP_EARG;
-  if (precision == 32 && (o.k > 1 || o.kbeg0 != 0)) return GOGP_EARG;  // the fp32 kernel has neither
-  if (o.kbeg0 < 0 || o.kbeg0 % kstep || o.kbeg0 > K || (o.kbeg0 && mode != GEMM_LAUUM)) return GOGP_EARG;
-  if (o.new_row0 < -1 || (o.new_row0 >= 0 && mode != GEMM_LOWER)) return GOGP_EARG;
-  if (o.ktri && mode != GEMM_RECT) return GOGP_EARG;
-  if (o.krag0 < -1 || (o.krag0 >= 0 && (o.ktri || (mode != GEMM_RECT && mode != GEMM_LOWER)))) return GOGP_EARG;
-  // the first k-step of tile row ti >= krag0 is loaded at k = (ti - krag0) * tile before the loop count is known
-  if (o.krag0 >= 0 && o.krag0 < mt && K < (int64_t)(mt - o.krag0) * TILE) return GOGP_EARG;
-  if (o.rule < 0 || o.rule > 2 || (o.rule && mode != GEMM_RECT)) return GOGP_EARG;
-  if (o.rule && (o.tpb_shift < 0 || o.tpb_shift > 8 || o.rblk0 < 0 || o.cblk0 < 0 || o.Pr < 1 || o.Pc < 1 ||
-                 o.pr < 0 || o.pr >= o.Pr || o.pc < 0 || o.pc >= o.Pc))
-    return GOGP_EARG;
   if (lda % al || ldb % al || ldc % al || a_off % al || b_off % al || c_off % al) return GOGP_EARG;
   const int64_t M = (int64_t)mt * TILE, N = (int64_t)nt * TILE;
   if (!covers(a_len, a_off, lda, M, K, o.k, o.bstride) || !covers(b_len, b_off, ldb, N, K, o.k, o.bstride) ||
@@ -278,22 +319,7 @@ extern "C" int gogp_test_gemm_nt(int device, int precision, int mode, int mt, in
   if (e == hipSuccess) e = hipMemcpy(dB, B, (size_t)(b_len * es), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(dC, C, (size_t)(c_len * es), hipMemcpyHostToDevice);
   if (e == hipSuccess) {
-    GemmGrid g;
-    g.ktri = o.ktri;
-    g.krag0 = o.krag0;
-    g.new_row0 = o.new_row0;
-    g.kbeg0 = o.kbeg0;
-    g.small_below = o.small_below;
-    g.prio = o.prio;
-    g.rule = o.rule;
-    g.tpb_shift = o.tpb_shift;
-    g.rblk0 = o.rblk0;
-    g.cblk0 = o.cblk0;
-    g.pr = o.pr;
-    g.Pr = o.Pr;
-    g.pc = o.pc;
-    g.Pc = o.Pc;
-    g.beta0 = o.beta0;
+    const GemmGrid g = gemm_grid_of(o);
     tl_batch.k = o.k;
     tl_batch.stride = (long)(o.bstride * es);
     if (precision == 64)

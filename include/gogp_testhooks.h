@@ -53,6 +53,18 @@ int gogp_test_gemm_nt(int device, int precision, int mode, int mt, int nt, int64
                       int64_t b_off, int64_t ldb, void *C, int64_t c_len, int64_t c_off, int64_t ldc,
                       const gogp_test_gemm_opts *opt);
 
+/* What the launcher of the tile kernel would launch for these arguments (gemm_plan, gogp_amd/csrc/gemm_plan.h): the
+ * instance (tile 64 or 128, 4 or 8 waves), the grid, the flops it books on the profile (all opt->k candidates) and its
+ * launch tag.  Never touches the device.  GOGP_EARG for the arguments gogp_test_gemm_nt refuses (buffers aside). */
+typedef struct gogp_test_gemm_plan_out {
+  int32_t tile, waves;
+  int64_t grid_x, grid_z;
+  double flops;
+  int64_t tag;
+} gogp_test_gemm_plan_out;
+int gogp_test_gemm_plan(int precision, int mode, int mt, int nt, int64_t K, const gogp_test_gemm_opts *opt,
+                        gogp_test_gemm_plan_out *out);
+
 /* The fp32 path's fp64 update of the diagonal blocks (diagsyrk.hip): D64 block b (bs x bs, bs = 256 or 512) -= R_b R_b^T
  * with R_b the bs x K floats at L + l_off + b * row_stride (leading dimension ld), for b < nblocks.  bs = 256 drives
  * launch_diag_syrk_f64 (row_stride must be 256 ld), bs = 512 launch_diag_syrk_f64_tiles.  GOGP_EARG for K not a

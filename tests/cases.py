@@ -98,3 +98,14 @@ def factor_residual_ratio(L, K):
     del B
     ij = np.unravel_index(int(np.argmax(R)), R.shape)
     return float(R[ij]) / gamma, (int(ij[0]), int(ij[1]))
+
+
+def tile_instance(prec, mode, mt, nt, k=1, small_below=384):
+    """(tile, waves) the tile kernel's launcher picks (gogp_amd/csrc/gemm_plan.h) -- the model that
+    tests/test_tile_kernels.py builds its references on and tests/test_gemm_plan_cpu.py pins the plan against."""
+    tiles = (mt * (mt + 1) // 2 if mode in ("LOWER", "LAUUM") else mt * nt) * k
+    if mode == "LAUUM":
+        return 128, 8
+    if tiles < small_below or (prec == 64 and 512 < tiles <= 768):
+        return 64, 4
+    return (128, 8) if tiles >= 3072 else (128, 4)

@@ -81,6 +81,29 @@ def test_gemm_hook_accepts_the_valid_neighbours(hk):
         assert gemm(hk, **ok) in (_lib.GOGP_OK, _lib.GOGP_EHIP), ok
 
 
+def gemm_plan(hk, prec=64, mode=0, mt=2, nt=2, K=32, out=True, **opts):
+    res = _lib.CGemmPlan()
+    return hk.gogp_test_gemm_plan(prec, mode, mt, nt, K, ctypes.byref(_lib.CGemmOpts(**dict(_lib.CGemmOpts.DEFAULTS, **opts))),
+                                  ctypes.byref(res) if out else None)
+
+
+PLAN_REFUSED = [dict(prec=16), dict(prec=0), dict(mode=4), dict(mode=-1), dict(mt=0), dict(nt=-1), dict(K=0), dict(K=24),
+                dict(prec=32, K=48), dict(mode=1, mt=2, nt=3), dict(prec=32, k=2, bstride=1 << 20),
+                dict(prec=32, mode=2, kbeg0=32), dict(mode=0, kbeg0=16), dict(mode=1, ktri=1), dict(rule=3),
+                dict(k=2, bstride=0), dict(out=False)]
+
+
+@pytest.mark.parametrize("bad", PLAN_REFUSED, ids=[",".join("%s=%s" % kv for kv in d.items()) for d in PLAN_REFUSED])
+def test_gemm_plan_hook_refuses(hk, bad):
+    assert gemm_plan(hk, **bad) == _lib.GOGP_EARG
+
+
+def test_gemm_plan_hook_accepts_the_valid_neighbours(hk):
+    for ok in (dict(), dict(prec=32, K=64), dict(mode=3), dict(mode=1, mt=3, nt=3), dict(mode=2, kbeg0=16),
+               dict(k=2, bstride=1 << 16), dict(rule=2, Pr=2, pr=1, beta0=1, tpb_shift=1)):
+        assert gemm_plan(hk, **ok) == _lib.GOGP_OK, ok
+
+
 def syrk(hk, bs=256, ld=32, K=32, l_off=0, row_stride=None, nblocks=1, l_len=None, d_len=None):
     row_stride = bs * ld if row_stride is None else row_stride
     l_len = l_len or l_off + (nblocks - 1) * row_stride + (bs - 1) * ld + K

@@ -22,6 +22,8 @@ diagonal distribution block, the K ranges of ktri / krag0).
 import numpy as np
 import pytest
 
+from cases import tile_instance as instance  # gemm_plan.h
+
 pytestmark = pytest.mark.gpu
 
 T = 128
@@ -37,16 +39,6 @@ def gpm():
 
 def nan_of(dt):
     return NAN64 if dt == np.float64 else NAN32
-
-
-def instance(prec, mode, mt, nt, k=1, small_below=384):
-    """(tile, waves) the launcher picks (dgemm.hip / sgemm.hip: launch_*gemm_nt)."""
-    tiles = (mt * (mt + 1) // 2 if mode in ("LOWER", "LAUUM") else mt * nt) * k
-    if mode == "LAUUM":
-        return 128, 8
-    if tiles < small_below or (prec == 64 and 512 < tiles <= 768):
-        return 64, 4
-    return (128, 8) if tiles >= 3072 else (128, 4)
 
 
 def dyadic(rng, shape, bits=20):

@@ -13,7 +13,7 @@
 namespace gogp {
 
 template <int NWG_PER_CU>
-__global__ __launch_bounds__(512, 4) void dgemm_persist_kernel(GemmArgs g, int ntiles) {
+__global__ __launch_bounds__(512, 4) void dgemm_persist_kernel(GemmArgs<double> g, int ntiles) {
   constexpr int BT = 128, NW = 8;
   constexpr int MT = BT / 32, NTW = BT / 64, WT = BT / 2, WTN = BT / 4;
   constexpr int NQ = BT * 8 / (NW * 64), SROWS = NW * 8;
@@ -168,7 +168,7 @@ int main() {
   CK(hipEventCreate(&e0));
   CK(hipEventCreate(&e1));
   for (int K : {256, 512, 768, 1024, 2048}) {
-    GemmArgs g{};
+    GemmArgs<double> g{};
     g.A = A; g.B = B; g.lda = KMAX; g.ldb = KMAX; g.ldc = N; g.mt = mt; g.nt = nt; g.nkt = K / 16;
     g.alpha = -1.0; g.beta = 1.0; g.kend = K; g.Pr = g.Pc = 1;
     g.new_row0 = g.krag0 = 0x7fffffff; g.bstride = 0;
