@@ -142,6 +142,25 @@ HOOK_SYMBOLS = [
      [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, _i64, _i64, _i64, _i64, _i64, _dp, _i64, ctypes.c_int]),
     ("gogp_test_diag256_product", ctypes.c_int,
      [ctypes.c_int, ctypes.c_int, _dp, _i64, _dp, _i64, _dp, _i64, _i64, ctypes.POINTER(ctypes.c_longlong)]),
+    # the kernels that consume the factor (tests/test_substitution_kernels.py)
+    ("gogp_test_trsm_small_workspace", _i64, [_i64]),
+    ("gogp_test_trsm_small", ctypes.c_int,
+     [ctypes.c_int, ctypes.c_int, _i64, ctypes.c_void_p, _i64, _i64, ctypes.c_void_p, ctypes.c_void_p, _i64, _i64,
+      ctypes.c_int, ctypes.c_int, _dp, _i64, ctypes.c_void_p, _i64, ctypes.POINTER(ctypes.c_int),
+      ctypes.POINTER(ctypes.c_int), ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_uint)]),
+    ("gogp_test_trsv_steps", ctypes.c_int,
+     [ctypes.c_int, ctypes.c_int, ctypes.c_int, _i64, ctypes.c_void_p, _i64, _i64, ctypes.c_void_p, ctypes.c_int,
+      ctypes.c_int, ctypes.c_int, _i64, _dp, _i64, _dp, _i64]),
+    ("gogp_test_alpha_from_y", ctypes.c_int,
+     [ctypes.c_int, ctypes.c_int, _i64, ctypes.c_void_p, _i64, _i64, _dp, _i64, _dp, _i64]),
+    ("gogp_test_rownorm_dot", ctypes.c_int,
+     [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, _i64, _i64, _i64, _i64, _dp, _i64, _dp, _i64, _dp, _i64]),
+    ("gogp_test_tinv", ctypes.c_int,
+     [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, _i64, _i64, ctypes.c_int,
+      ctypes.c_void_p]),
+    ("gogp_test_blockmm", ctypes.c_int,
+     [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, _i64] + [ctypes.POINTER(_i64)] * 6
+     + [ctypes.POINTER(ctypes.c_int), ctypes.c_double, ctypes.c_int, _i64]),
     # per-rank replay of the sharded sweep (tools/sharded_replay.py): a transport that reads recorded panels
     ("gogp_test_dist_init_replay", ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int] * 4),
 ]

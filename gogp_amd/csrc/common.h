@@ -378,7 +378,8 @@ struct TsSolution {
   const void *p = nullptr;
   int kind = TS_SOL_PAIRED, width = 32;
 };
-TsSolution trsm_small_solution(int64_t npad, int j0, int cnt, void *ws);
+// (f32: the launch was the float overload's, which has no granule form: one right-hand side is TS_SOL_COMPACT of width 1)
+TsSolution trsm_small_solution(int64_t npad, int j0, int cnt, void *ws, bool f32 = false);
 // append.hip: the kernels of gogp_append (api.hip) -- rows n .. n + m - 1 (m <= 64) join a factor of n rows.
 // V = L11^-1 B^T (npc rows, the columns j < m0 in v0 and the rest in v1, as launch_trsm_small left them).
 // launch_append_gram: one workgroup per 256 rows of V writes its part of G = V^T V (lower 16 x 16 tiles) and of V^T z to

@@ -677,3 +677,238 @@ extern "C" int gogp_bench_gemm(int device, int mode, int mt, int nt, int64_t K, 
   (void)hipFree(dC);
   return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
 }
+
+// ---- the kernels that consume the factor, through their product launchers on host buffers
+// (tests/test_substitution_kernels.py): the one-pass substitution of trsm_small.hip, and of solve.hip the substitution
+// steps, alpha_from_y, rownorm_dot, tinv_init and the batched 256-block product.  Same rules as gogp_test_gemm_nt: every
+// argument is checked before the device is touched, every array goes to the device whole and every output comes back whole.
+namespace {
+// a host array's copy on the device: up() allocates and uploads (n == 0 or h == nullptr: nothing), down() copies back
+struct DevCopy {
+  char *d = nullptr;
+  size_t bytes = 0;
+  hipError_t up(const void *h, size_t n) {
+    if (!h || !n) return hipSuccess;
+    bytes = n;
+    hipError_t e = hipMalloc(&d, n);
+    if (e == hipSuccess) e = hipMemcpy(d, h, n, hipMemcpyHostToDevice);
+    return e;
+  }
+  hipError_t down(void *h) const { return d ? hipMemcpy(h, d, bytes, hipMemcpyDeviceToHost) : hipSuccess; }
+  template <class T>
+  T *as() const {
+    return reinterpret_cast<T *>(d);
+  }
+  ~DevCopy() { (void)hipFree(d); }
+};
+hipError_t launched() {
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? hipDeviceSynchronize() : e;
+}
+bool prec_ok(int precision) { return precision == 64 || precision == 32; }
+constexpr int64_t TH_NPAD_MAX = 1 << 17;
+}  // namespace
+
+extern "C" int64_t gogp_test_trsm_small_workspace(int64_t npad) {
+  if (npad <= 0 || npad % PANEL || npad > TH_NPAD_MAX) return -1;
+  return (int64_t)trsm_small_workspace_bytes(npad);
+}
+
+extern "C" int gogp_test_trsm_small(int device, int precision, int64_t npad, const void *L, int64_t l_len, int64_t ld,
+                                    const void *Dinv, const void *KsT, int64_t k_len, int64_t ldk, int j0, int cnt,
+                                    double *dq, int64_t dq_len, void *sol, int64_t sol_len, int *kind, int *width,
+                                    int64_t *sol_off, unsigned *tmo) {
+  if (!L || !Dinv || !KsT || !dq || !sol || !kind || !width || !sol_off || !tmo || !prec_ok(precision)) return GOGP_EARG;
+  if (npad <= 0 || npad % PANEL || npad > TH_NPAD_MAX || ld % 2 || j0 < 0 || cnt < 1 || cnt > 32) return GOGP_EARG;
+  const bool granule = precision == 64 && j0 == 0 && cnt == 1;  // reads row 0 of KsT alone
+  const int64_t krows = granule ? 1 : j0 + (cnt <= 16 ? 16 : 32);  // the counter kernels read whole 16-column tiles
+  if (!covers(l_len, 0, ld, npad, npad, 1, 0) || !covers(k_len, 0, ldk, krows, npad, 1, 0) || dq_len < j0 + cnt)
+    return GOGP_EARG;
+  const size_t wsb = trsm_small_workspace_bytes(npad);
+  if (sol_len < 0 || (size_t)sol_len != wsb) return GOGP_EARG;
+  if (!device_ok(device)) return GOGP_EHIP;
+  const size_t es = precision / 8;
+  DevCopy dL, dD, dK, dQ, dW;
+  hipError_t e = dL.up(L, (size_t)l_len * es);
+  if (e == hipSuccess) e = dD.up(Dinv, (size_t)npad * PANEL * es);
+  if (e == hipSuccess) e = dK.up(KsT, (size_t)k_len * es);
+  if (e == hipSuccess) e = dQ.up(dq, (size_t)dq_len * sizeof(double));
+  if (e == hipSuccess) e = dW.up(sol, wsb);
+  unsigned *dtmo = nullptr;
+  if (e == hipSuccess) {
+    if (precision == 64)
+      launch_trsm_small(0, dL.as<double>(), ld, dD.as<double>(), dK.as<double>(), ldk, npad, j0, cnt, dW.d, dQ.as<double>(),
+                        &dtmo);
+    else
+      launch_trsm_small(0, dL.as<float>(), ld, dD.as<float>(), dK.as<float>(), ldk, npad, j0, cnt, dW.d, dQ.as<double>(),
+                        &dtmo);
+    e = launched();
+  }
+  if (e == hipSuccess && !dtmo) e = hipErrorUnknown;
+  if (e == hipSuccess) e = hipMemcpy(tmo, dtmo, sizeof(unsigned), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = dQ.down(dq);
+  if (e == hipSuccess) e = dW.down(sol);
+  const TsSolution r = trsm_small_solution(npad, j0, cnt, dW.d, precision == 32);
+  *kind = r.kind;
+  *width = r.width;
+  *sol_off = dW.d ? (int64_t)((const char *)r.p - dW.d) : -1;
+  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+}
+
+extern "C" int gogp_test_trsv_steps(int device, int precision, int dir, int64_t npad, const void *L, int64_t l_len,
+                                    int64_t ld, const void *Dinv, int b0, int b1, int k, int64_t bstride, double *w,
+                                    int64_t w_len, double *out, int64_t out_len) {
+  if (!L || !Dinv || !w || !out || !prec_ok(precision) || (dir != 0 && dir != 1)) return GOGP_EARG;
+  if (npad <= 0 || npad % PANEL || npad > TH_NPAD_MAX) return GOGP_EARG;
+  const int nb = (int)(npad / PANEL);
+  const int64_t al = 16 / (precision / 8);  // 16-B loads of the matrix rows
+  if (ld % al || b0 < 0 || b1 < b0 || b1 >= nb || k < 1 || k > 64) return GOGP_EARG;
+  if (k > 1 && (precision != 64 || dir != 0 || bstride < npad * PANEL || bstride % 2)) return GOGP_EARG;  // as the product
+  if (k == 1) bstride = 0;
+  if (!covers(l_len, 0, ld, npad, npad, k, bstride) || !covers(w_len, 0, npad, 1, npad, k, bstride) ||
+      !covers(out_len, 0, npad, 1, npad, k, bstride))
+    return GOGP_EARG;
+  if (!device_ok(device)) return GOGP_EHIP;
+  const size_t es = precision / 8;
+  DevCopy dL, dD, dw, dout;
+  hipError_t e = dL.up(L, (size_t)l_len * es);
+  if (e == hipSuccess) e = dD.up(Dinv, (size_t)((k - 1) * bstride + npad * PANEL) * es);
+  if (e == hipSuccess) e = dw.up(w, (size_t)w_len * sizeof(double));
+  if (e == hipSuccess) e = dout.up(out, (size_t)out_len * sizeof(double));
+  if (e == hipSuccess) {
+    tl_batch.k = k;
+    tl_batch.stride = (long)(bstride * 8);
+    for (int i = 0; i <= b1 - b0; ++i) {
+      const int b = dir == 0 ? b0 + i : b1 - i;
+      if (precision == 64 && dir == 0)
+        launch_trsv_fwd_step(0, dL.as<double>(), ld, dD.as<double>(), b, nb, dw.as<double>(), dout.as<double>());
+      else if (precision == 64)
+        launch_trsv_bwd_step(0, dL.as<double>(), ld, dD.as<double>(), b, nb, dw.as<double>(), dout.as<double>());
+      else if (dir == 0)
+        launch_trsv_fwd_step(0, dL.as<float>(), ld, dD.as<float>(), b, nb, dw.as<double>(), dout.as<double>());
+      else
+        launch_trsv_bwd_step(0, dL.as<float>(), ld, dD.as<float>(), b, nb, dw.as<double>(), dout.as<double>());
+    }
+    tl_batch.k = 1;
+    tl_batch.stride = 0;
+    e = launched();
+  }
+  if (e == hipSuccess) e = dw.down(w);
+  if (e == hipSuccess) e = dout.down(out);
+  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+}
+
+extern "C" int gogp_test_alpha_from_y(int device, int precision, int64_t npad, const void *Y, int64_t y_len, int64_t ld,
+                                      const double *z, int64_t z_len, double *alpha, int64_t alpha_len) {
+  if (!Y || !z || !alpha || !prec_ok(precision)) return GOGP_EARG;
+  if (npad <= 0 || npad % 2 || npad > TH_NPAD_MAX || ld % 2) return GOGP_EARG;  // pairs of columns
+  if (!covers(y_len, 0, ld, npad, npad, 1, 0) || z_len < npad || alpha_len < npad) return GOGP_EARG;
+  if (!device_ok(device)) return GOGP_EHIP;
+  DevCopy dY, dz, da;
+  hipError_t e = dY.up(Y, (size_t)y_len * (precision / 8));
+  if (e == hipSuccess) e = dz.up(z, (size_t)z_len * sizeof(double));
+  if (e == hipSuccess) e = da.up(alpha, (size_t)alpha_len * sizeof(double));
+  if (e == hipSuccess) {
+    if (precision == 64)
+      launch_alpha_from_y(0, dY.as<double>(), ld, dz.as<double>(), npad, da.as<double>());
+    else
+      launch_alpha_from_y(0, dY.as<float>(), ld, dz.as<double>(), npad, da.as<double>());
+    e = launched();
+  }
+  if (e == hipSuccess) e = da.down(alpha);
+  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+}
+
+extern "C" int gogp_test_rownorm_dot(int device, int precision, const void *V, int64_t v_len, int64_t ld, int64_t ncols,
+                                     int64_t m, const double *vec, int64_t vec_len, double *dot, int64_t dot_len,
+                                     double *sq, int64_t sq_len) {
+  if (!V || !prec_ok(precision) || m <= 0 || m > 65535 || ncols <= 0) return GOGP_EARG;
+  if (!covers(v_len, 0, ld, m, ncols, 1, 0) || (vec && vec_len < ncols) || (dot && dot_len < m) || (sq && sq_len < m))
+    return GOGP_EARG;
+  if (!device_ok(device)) return GOGP_EHIP;
+  DevCopy dV, dvec, ddot, dsq;
+  hipError_t e = dV.up(V, (size_t)v_len * (precision / 8));
+  if (e == hipSuccess) e = dvec.up(vec, vec ? (size_t)vec_len * sizeof(double) : 0);
+  if (e == hipSuccess) e = ddot.up(dot, dot ? (size_t)dot_len * sizeof(double) : 0);
+  if (e == hipSuccess) e = dsq.up(sq, sq ? (size_t)sq_len * sizeof(double) : 0);
+  if (e == hipSuccess) {
+    if (precision == 64)
+      launch_rownorm_dot(0, dV.as<double>(), ld, dvec.as<double>(), ncols, m, ddot.as<double>(), dsq.as<double>());
+    else
+      launch_rownorm_dot(0, dV.as<float>(), ld, dvec.as<double>(), ncols, m, ddot.as<double>(), dsq.as<double>());
+    e = launched();
+  }
+  if (e == hipSuccess && dot) e = ddot.down(dot);
+  if (e == hipSuccess && sq) e = dsq.down(sq);
+  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+}
+
+extern "C" int gogp_test_tinv(int device, int precision, int nsub, const void *Dinv, void *X, int64_t x_len, int64_t tld,
+                              int with_xt, void *XT) {
+  if (!Dinv || !X || !prec_ok(precision) || nsub < 1 || nsub > 16 || (with_xt && !XT)) return GOGP_EARG;
+  const int64_t n = (int64_t)nsub * PANEL;
+  if (!covers(x_len, 0, tld, n, n, 1, 0)) return GOGP_EARG;
+  if (!device_ok(device)) return GOGP_EHIP;
+  const size_t es = precision / 8;
+  DevCopy dD, dX, dXT;
+  hipError_t e = dD.up(Dinv, (size_t)n * PANEL * es);
+  if (e == hipSuccess) e = dX.up(X, (size_t)x_len * es);
+  if (e == hipSuccess && with_xt) e = dXT.up(XT, (size_t)x_len * es);
+  if (e == hipSuccess) {
+    if (precision == 64)
+      launch_tinv_init(0, dD.as<double>(), dX.as<double>(), dXT.as<double>(), nsub, tld);
+    else
+      launch_tinv_init(0, dD.as<float>(), dX.as<float>(), dXT.as<float>(), nsub, tld);
+    e = launched();
+  }
+  if (e == hipSuccess) e = dX.down(X);
+  if (e == hipSuccess && with_xt) e = dXT.down(XT);
+  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+}
+
+extern "C" int gogp_test_blockmm(int device, int precision, int nprod, void *arena, int64_t arena_len, const int64_t *a_off,
+                                 const int64_t *lda, const int64_t *b_off, const int64_t *ldb, const int64_t *c_off,
+                                 const int64_t *ldc, const int *K, double alpha, int k, int64_t bstride) {
+  if (!arena || !a_off || !lda || !b_off || !ldb || !c_off || !ldc || !K || !prec_ok(precision)) return GOGP_EARG;
+  if (nprod < 1 || nprod > 6 || k < 1 || k > 64 || (k > 1 && (precision != 64 || bstride <= 0))) return GOGP_EARG;
+  if (k == 1) bstride = 0;
+  for (int b = 0; b < nprod; ++b) {
+    if (K[b] <= 0 || K[b] % 32) return GOGP_EARG;
+    if (!covers(arena_len, a_off[b], lda[b], PANEL, K[b], k, bstride) ||
+        !covers(arena_len, b_off[b], ldb[b], K[b], PANEL, k, bstride) ||
+        !covers(arena_len, c_off[b], ldc[b], PANEL, PANEL, k, bstride))
+      return GOGP_EARG;
+  }
+  if (!device_ok(device)) return GOGP_EHIP;
+  const size_t es = precision / 8;
+  DevCopy dA;
+  hipError_t e = dA.up(arena, (size_t)arena_len * es);
+  if (e == hipSuccess) {
+    tl_batch.k = k;
+    tl_batch.stride = (long)(bstride * (int64_t)es);
+    if (precision == 64) {
+      const double *A[6], *B[6];
+      double *C[6];
+      for (int b = 0; b < nprod; ++b) {
+        A[b] = dA.as<double>() + a_off[b];
+        B[b] = dA.as<double>() + b_off[b];
+        C[b] = dA.as<double>() + c_off[b];
+      }
+      launch_blockmm(0, nprod, A, lda, B, ldb, C, ldc, K, alpha);
+    } else {
+      const float *A[6], *B[6];
+      float *C[6];
+      for (int b = 0; b < nprod; ++b) {
+        A[b] = dA.as<float>() + a_off[b];
+        B[b] = dA.as<float>() + b_off[b];
+        C[b] = dA.as<float>() + c_off[b];
+      }
+      launch_blockmm(0, nprod, A, lda, B, ldb, C, ldc, K, alpha);
+    }
+    tl_batch.k = 1;
+    tl_batch.stride = 0;
+    e = launched();
+  }
+  if (e == hipSuccess) e = dA.down(arena);
+  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+}

@@ -610,11 +610,12 @@ void launch_trsm_small(hipStream_t s, const float *L, int64_t ld, const float *D
 }
 
 // Where a launch of launch_trsm_small (same npad, j0, cnt, ws) leaves its solution V, for kernels that read it behind
-// the launch on the same stream (append.hip): the layout follows the kernel instance the launcher picks.
-TsSolution trsm_small_solution(int64_t npad, int j0, int cnt, void *ws) {
+// the launch on the same stream (append.hip): the layout follows the kernel instance the launcher picks (f32: the float
+// overload, which takes the counter kernel for one right-hand side too).
+TsSolution trsm_small_solution(int64_t npad, int j0, int cnt, void *ws, bool f32) {
   TsSolution r;
   char *p = (char *)ws;
-  if (j0 == 0 && cnt == 1) {  // launch_trsv_granule: [tmo (16 B) | Vg | Wg]
+  if (!f32 && j0 == 0 && cnt == 1) {  // launch_trsv_granule: [tmo (16 B) | Vg | Wg]
     r.p = p + 16;
     r.kind = TS_SOL_GRANULE;
     r.width = 1;

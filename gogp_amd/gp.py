@@ -783,3 +783,125 @@ def diag256_product(A: np.ndarray, variant: int = 0, row0: int = 0, nvalid: int 
     if rc != _lib.GOGP_OK:
         raise GogpError(rc, "test_diag256_product")
     return L, Dinv, info.value
+
+
+# ---- the kernels that consume the factor (include/gogp_testhooks.h; tests/test_substitution_kernels.py) ------------
+def _mat(a, what):
+    if not isinstance(a, np.ndarray) or a.dtype not in (np.float64, np.float32) or not a.flags.c_contiguous:
+        raise TypeError("%s: a C-contiguous float64 / float32 array" % what)
+    return a
+
+
+def _prec(*arrs):
+    if len({a.dtype for a in arrs}) != 1:
+        raise TypeError("the matrices must share one dtype")
+    return 64 if arrs[0].dtype == np.float64 else 32
+
+
+def _vec(a, what):
+    if not isinstance(a, np.ndarray) or a.dtype != np.float64 or not a.flags.c_contiguous:
+        raise TypeError("%s: a C-contiguous float64 array" % what)
+    return a
+
+
+def trsm_small_workspace(npad: int) -> int:
+    """Bytes of the workspace of one launch of the one-pass substitution."""
+    n = _lib.hooks().gogp_test_trsm_small_workspace(npad)
+    if n < 0:
+        raise GogpError(_lib.GOGP_EARG, "test_trsm_small_workspace")
+    return int(n)
+
+
+def trsm_small_check(npad: int, L: np.ndarray, ld: int, Dinv: np.ndarray, KsT: np.ndarray, ldk: int, j0: int, cnt: int,
+                     dq: np.ndarray, ws=None, device: int = -1):
+    """One launch_trsm_small (test hook gogp_test_trsm_small) on flat host arrays.  ws: the workspace's initial bytes
+    (uint8, trsm_small_workspace(npad) of them; default zeros).  Returns (dq, ws, kind, width, sol_off, tmo): copies of
+    dq and of the whole workspace after the launch, what trsm_small_solution reports, and the time-out word."""
+    L, Dinv, KsT = _mat(L, "L"), _mat(Dinv, "Dinv"), _mat(KsT, "KsT")
+    prec = _prec(L, Dinv, KsT)
+    if Dinv.size != npad * 256:
+        raise ValueError("Dinv: npad / 256 blocks of 256 x 256")
+    dq = _vec(dq, "dq").copy()
+    nbytes = trsm_small_workspace(npad)
+    ws = np.zeros(nbytes, np.uint8) if ws is None else np.ascontiguousarray(ws, dtype=np.uint8).copy()
+    kind, width, tmo, off = ctypes.c_int(-1), ctypes.c_int(-1), ctypes.c_uint(0), ctypes.c_int64(-1)
+    rc = _lib.hooks().gogp_test_trsm_small(device, prec, npad, L.ctypes.data, L.size, ld, Dinv.ctypes.data,
+                                           KsT.ctypes.data, KsT.size, ldk, j0, cnt, _dp(dq), dq.size, ws.ctypes.data,
+                                           ws.size, ctypes.byref(kind), ctypes.byref(width), ctypes.byref(off),
+                                           ctypes.byref(tmo))
+    if rc != _lib.GOGP_OK:
+        raise GogpError(rc, "test_trsm_small")
+    return dq, ws, kind.value, width.value, off.value, tmo.value
+
+
+def trsv_steps_check(direction: str, npad: int, L: np.ndarray, ld: int, Dinv: np.ndarray, b0: int, b1: int,
+                     w: np.ndarray, out: np.ndarray, k: int = 1, bstride: int = 0, device: int = -1):
+    """The product's substitution steps b0 .. b1 (test hook gogp_test_trsv_steps): "fwd" ascending (out = z), "bwd"
+    descending (out = alpha).  Returns copies of (w, out) after the steps."""
+    L, Dinv = _mat(L, "L"), _mat(Dinv, "Dinv")
+    prec = _prec(L, Dinv)
+    if Dinv.size != (k - 1) * bstride + npad * 256:
+        raise ValueError("Dinv: (k - 1) * bstride + npad * 256 elements")
+    w, out = _vec(w, "w").copy(), _vec(out, "out").copy()
+    rc = _lib.hooks().gogp_test_trsv_steps(device, prec, {"fwd": 0, "bwd": 1}[direction], npad, L.ctypes.data, L.size,
+                                           ld, Dinv.ctypes.data, b0, b1, k, bstride, _dp(w), w.size, _dp(out), out.size)
+    if rc != _lib.GOGP_OK:
+        raise GogpError(rc, "test_trsv_steps")
+    return w, out
+
+
+def alpha_from_y_check(npad: int, Y: np.ndarray, ld: int, z: np.ndarray, alpha: np.ndarray, device: int = -1):
+    """launch_alpha_from_y (test hook gogp_test_alpha_from_y); returns a copy of alpha after the launch."""
+    Y, z, alpha = _mat(Y, "Y"), _vec(z, "z"), _vec(alpha, "alpha").copy()
+    rc = _lib.hooks().gogp_test_alpha_from_y(device, _prec(Y), npad, Y.ctypes.data, Y.size, ld, _dp(z), z.size,
+                                             _dp(alpha), alpha.size)
+    if rc != _lib.GOGP_OK:
+        raise GogpError(rc, "test_alpha_from_y")
+    return alpha
+
+
+def rownorm_dot_check(V: np.ndarray, ld: int, ncols: int, m: int, vec=None, dot=None, sq=None, device: int = -1):
+    """launch_rownorm_dot (test hook gogp_test_rownorm_dot); vec, dot, sq: each None or an array.  Returns copies of
+    (dot, sq) after the launch (None where None went in)."""
+    V = _mat(V, "V")
+    vec = None if vec is None else _vec(vec, "vec")
+    dot = None if dot is None else _vec(dot, "dot").copy()
+    sq = None if sq is None else _vec(sq, "sq").copy()
+    size = lambda a: 0 if a is None else a.size  # noqa: E731
+    rc = _lib.hooks().gogp_test_rownorm_dot(device, _prec(V), V.ctypes.data, V.size, ld, ncols, m, _dp(vec), size(vec),
+                                            _dp(dot), size(dot), _dp(sq), size(sq))
+    if rc != _lib.GOGP_OK:
+        raise GogpError(rc, "test_rownorm_dot")
+    return dot, sq
+
+
+def tinv_check(nsub: int, Dinv: np.ndarray, X: np.ndarray, tld: int, XT=None, device: int = -1):
+    """launch_tinv_init (test hook gogp_test_tinv); returns copies of (X, XT) after the launch."""
+    Dinv, X = _mat(Dinv, "Dinv"), _mat(X, "X").copy()
+    arrs = [Dinv, X]
+    if XT is not None:
+        XT = _mat(XT, "XT").copy()
+        arrs.append(XT)
+        if XT.size != X.size:
+            raise ValueError("XT: as many elements as X")
+    if Dinv.size != nsub * 65536:
+        raise ValueError("Dinv: nsub blocks of 256 x 256")
+    rc = _lib.hooks().gogp_test_tinv(device, _prec(*arrs), nsub, Dinv.ctypes.data, X.ctypes.data, X.size, tld,
+                                     int(XT is not None), None if XT is None else XT.ctypes.data)
+    if rc != _lib.GOGP_OK:
+        raise GogpError(rc, "test_tinv")
+    return X, XT
+
+
+def blockmm_check(arena: np.ndarray, prods, alpha: float = 1.0, k: int = 1, bstride: int = 0, device: int = -1):
+    """launch_blockmm (test hook gogp_test_blockmm) on one arena; prods: up to six (a_off, lda, b_off, ldb, c_off, ldc,
+    K).  Returns a copy of the arena after the launch."""
+    arena = _mat(arena, "arena").copy()
+    n = len(prods)
+    cols = [(ctypes.c_int64 * max(n, 1))(*[int(p[i]) for p in prods]) for i in range(6)]
+    K = (ctypes.c_int * max(n, 1))(*[int(p[6]) for p in prods])
+    rc = _lib.hooks().gogp_test_blockmm(device, _prec(arena), n, arena.ctypes.data, arena.size, *cols, K, alpha, k,
+                                        bstride)
+    if rc != _lib.GOGP_OK:
+        raise GogpError(rc, "test_blockmm")
+    return arena

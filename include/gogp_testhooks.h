@@ -78,6 +78,56 @@ int gogp_test_diag_syrk(int device, int bs, const float *L, int64_t l_len, int64
 int gogp_test_diag256_product(int device, int variant, const double *A, int64_t ld, double *L, int64_t ldl,
                               double *Dinv, int64_t row0, int64_t nvalid, long long *info);
 
+/* ---- the kernels that consume the factor, through their product launchers (tests/test_substitution_kernels.py).
+ * As gogp_test_gemm_nt: precision 64 (double) or 32 (float) is the element type of the MATRICES (vectors, sums of squares
+ * and solutions are doubles either way); lengths count elements; every array is copied to the device whole and every
+ * in / out array whole back; GOGP_EARG, before the device is touched, for anything a launch cannot honour or that the
+ * arrays do not cover. */
+
+/* Bytes of the workspace of one launch of the one-pass substitution (trsm_small_workspace_bytes); -1: bad npad. */
+int64_t gogp_test_trsm_small_workspace(int64_t npad);
+
+/* One launch_trsm_small (trsm_small.hip): V = L^-1 Kstar for the right-hand sides j0 .. j0 + cnt - 1 (rows of KsT, leading
+ * dimension ldk; cnt <= 32) by the blocked substitution with the GIVEN block inverses Dinv (npad / 256 blocks of 256 x 256,
+ * npad * 256 elements).  L: npad rows of ld.  dq (in / out): dq[j] = |V_j|^2 for those j.  sol (in / out, sol_len bytes =
+ * gogp_test_trsm_small_workspace(npad)): the launch's workspace -- its initial contents go to the device, so a test can
+ * hand in what an earlier launch left there.  kind, width, sol_off: what trsm_small_solution says for this launch --
+ * the layout (common.h: TS_SOL_*) and the byte offset of V in the workspace.  tmo: the time-out word (0: fine).  The
+ * instances on 16-column tiles read the rows j0 .. j0 + 15 (cnt <= 16) or .. j0 + 31 of KsT: k_len must cover them. */
+int gogp_test_trsm_small(int device, int precision, int64_t npad, const void *L, int64_t l_len, int64_t ld,
+                         const void *Dinv, const void *KsT, int64_t k_len, int64_t ldk, int j0, int cnt, double *dq,
+                         int64_t dq_len, void *sol, int64_t sol_len, int *kind, int *width, int64_t *sol_off,
+                         unsigned *tmo);
+
+/* The substitution steps of solve.hip as the product runs them: dir 0 launch_trsv_fwd_step for b = b0 .. b1 ascending
+ * (out = z), dir 1 launch_trsv_bwd_step for b = b1 .. b0 descending (out = alpha); w in / out.  k > 1 (fp64 forward
+ * only, as in the product): k candidates, candidate c's L, Dinv, w and out lying c * bstride ELEMENTS after candidate
+ * 0's.  Dinv holds (k - 1) * bstride + npad * 256 elements. */
+int gogp_test_trsv_steps(int device, int precision, int dir, int64_t npad, const void *L, int64_t l_len, int64_t ld,
+                         const void *Dinv, int b0, int b1, int k, int64_t bstride, double *w, int64_t w_len, double *out,
+                         int64_t out_len);
+
+/* launch_alpha_from_y: alpha_i = sum_{q >= q0(i)} Y[i][q] z[q], q0 the first column of row i's 256-block. */
+int gogp_test_alpha_from_y(int device, int precision, int64_t npad, const void *Y, int64_t y_len, int64_t ld,
+                           const double *z, int64_t z_len, double *alpha, int64_t alpha_len);
+
+/* launch_rownorm_dot over the m rows of V (ncols columns, ld): dot_j = V_j . vec, sq_j = |V_j|^2; vec, dot and sq may
+ * each be NULL, as for the launcher. */
+int gogp_test_rownorm_dot(int device, int precision, const void *V, int64_t v_len, int64_t ld, int64_t ncols, int64_t m,
+                          const double *vec, int64_t vec_len, double *dot, int64_t dot_len, double *sq, int64_t sq_len);
+
+/* launch_tinv_init: the diagonal 256-blocks of X (256 nsub rows of tld; in / out) := Dinv_i (nsub blocks), zeros above
+ * them; with_xt: XT (x_len elements too; in / out) the same for the transpose. */
+int gogp_test_tinv(int device, int precision, int nsub, const void *Dinv, void *X, int64_t x_len, int64_t tld, int with_xt,
+                   void *XT);
+
+/* launch_blockmm: nprod (<= 6) products C_b (256 x 256, ldc) = alpha A_b (256 x K_b, lda) B_b (K_b x 256, ldb), plain
+ * A B, all operands at element offsets into ONE arena (in / out), K_b multiples of 32; k > 1 (fp64 only): candidates
+ * bstride elements apart. */
+int gogp_test_blockmm(int device, int precision, int nprod, void *arena, int64_t arena_len, const int64_t *a_off,
+                      const int64_t *lda, const int64_t *b_off, const int64_t *ldb, const int64_t *c_off,
+                      const int64_t *ldc, const int *K, double alpha, int k, int64_t bstride);
+
 /* Benchmark hook for the tile kernel: `reps` launches of one shape (mode 0 RECT
  * mt x nt tiles, 1 LOWER mt x mt, 2 LAUUM mt x mt with K = mt*128) on device
  * buffers; returns ms per launch and TFLOP/s on the flops launched. */

@@ -5,7 +5,14 @@ The primitives are the reference's (kernel/kernel.go:23-26,44-47,70-73,89-92,
 kernel/noise.go:27-30,47-49); the compositions mirror its tutorials
 (tutorial/barebones/kernel/kernel.go:14-31, tutorial/hyperpriors/kernel/kernel.go:23-24).
 """
+import numpy as _np
+
 from gogp_amd import kernel
+
+#: NaNs with a payload: the sentinels of the kernel tests (tests/test_tile_kernels.py, tests/test_substitution_kernels.py)
+#: for every element a launch must neither read nor write -- they come back bit for bit or the test fails
+NAN64 = _np.array([0x7FF8DEAD0000BEEF], dtype=_np.uint64).view(_np.float64)[0]
+NAN32 = _np.array([0x7FC0BEEF], dtype=_np.uint32).view(_np.float32)[0]
 
 CASES = [
     ("normal1d", 1, kernel.Normal, kernel.ConstantNoise(0.1), [0.3], []),

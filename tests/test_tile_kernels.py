@@ -22,13 +22,12 @@ diagonal distribution block, the K ranges of ktri / krag0).
 import numpy as np
 import pytest
 
+from cases import NAN32, NAN64
 from cases import tile_instance as instance  # gemm_plan.h
 
 pytestmark = pytest.mark.gpu
 
 T = 128
-NAN64 = np.array([0x7FF8DEAD0000BEEF], dtype=np.uint64).view(np.float64)[0]
-NAN32 = np.array([0x7FC0BEEF], dtype=np.uint32).view(np.float32)[0]
 
 
 @pytest.fixture(scope="module")
