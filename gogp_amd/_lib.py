@@ -47,6 +47,19 @@ class CGemmOpts(ctypes.Structure):
                     cblk0=0, pr=0, Pr=1, pc=0, Pc=1, beta0=-1, k=1, bstride=0)
 
 
+class CKParams(ctypes.Structure):
+    """gogp_test_kparams (include/gogp_testhooks.h): the kernels' DevParams, stated field by field."""
+    _T, _D, _E = 4, 64, 32  # GOGP_MAX_TERMS, GOGP_MAX_NDIM, GOGP_MAX_EVENTS
+    _fields_ = [("ndim", ctypes.c_int32), ("nterms", ctypes.c_int32), ("kind", ctypes.c_int32 * _T),
+                ("ard", ctypes.c_int32 * _T), ("c", ctypes.c_double * _T), ("w", ctypes.c_double * _T),
+                ("inv_len", (ctypes.c_double * _D) * _T), ("noise_var", ctypes.c_double), ("dnoise", ctypes.c_double),
+                ("nevents", ctypes.c_int32), ("ev_axis", ctypes.c_int32), ("ev_from", ctypes.c_double * _E),
+                ("ev_to", ctypes.c_double * _E), ("ev_disc", ctypes.c_double * _E)]
+
+
+GOGP_TEST_NACC = 16 + 64  # include/gogp_testhooks.h
+
+
 class CGemmPlan(ctypes.Structure):
     """gogp_test_gemm_plan_out (include/gogp_testhooks.h)."""
     _fields_ = [("tile", ctypes.c_int32), ("waves", ctypes.c_int32), ("grid_x", ctypes.c_int64),
@@ -161,6 +174,18 @@ HOOK_SYMBOLS = [
     ("gogp_test_blockmm", ctypes.c_int,
      [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, _i64] + [ctypes.POINTER(_i64)] * 6
      + [ctypes.POINTER(ctypes.c_int), ctypes.c_double, ctypes.c_int, _i64]),
+    # the kernels that turn K^-1 into the gradient (tests/test_grad_kernels.py)
+    ("gogp_test_grad_blocks", ctypes.c_int, [_i64, _i64, _i64, ctypes.c_int]),
+    ("gogp_test_grad_reduce", ctypes.c_int,
+     [ctypes.c_int, ctypes.c_int, ctypes.POINTER(CKParams)] + [ctypes.c_int] * 4
+     + [_dp, _i64, _dp, _i64, ctypes.c_void_p, _i64, _i64, _i64, _i64, ctypes.c_int, ctypes.c_int, _i64, _dp, _i64, _dp]),
+    ("gogp_test_grad_reduce_local", ctypes.c_int,
+     [ctypes.c_int, ctypes.c_int, ctypes.POINTER(CKParams)] + [ctypes.c_int] * 4
+     + [_dp, _i64, _dp, _i64, ctypes.c_void_p, _i64, _i64, _i64, _i64, _i64, _i64] + [ctypes.c_int] * 7
+     + [_i64, _dp, _i64, _dp]),
+    ("gogp_test_xgrad", ctypes.c_int,
+     [ctypes.c_int, ctypes.POINTER(CKParams), ctypes.c_int, _dp, _i64, _dp, _i64, _dp, _i64, _i64, _i64, _i64, _dp,
+      _i64]),
     # per-rank replay of the sharded sweep (tools/sharded_replay.py): a transport that reads recorded panels
     ("gogp_test_dist_init_replay", ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int] * 4),
 ]

@@ -186,7 +186,8 @@ void launch_convert_block(hipStream_t s, const double *src, int64_t lds_, float 
                           int cols);
 void launch_grad_reduce(hipStream_t s, const DevParams *p, int ndim, int ard_dims, const double *X,
                         const double *alpha, const float *Kinv, int64_t ld, int64_t n, int64_t npad,
-                        double *partials, double *out, bool radial1 = false, int mfma_min_dims = 1, bool ev = false);
+                        double *partials, double *out, bool radial1 = false, int mfma_min_dims = 1, bool ev = false,
+                        int max_blocks = 0);
 
 void launch_gram_lower(hipStream_t s, const DevParams *p, int ndim, const double *X,
                        int64_t n, int64_t npad, double *K, int64_t ld, bool ev = false);
@@ -306,21 +307,29 @@ void launch_pcov_add_mu(hipStream_t s, const double *G, int64_t ldg, const doubl
 int grad_reduce_blocks(int64_t npad);
 
 // fused gradient reduction over lower tiles of Kinv; out: NACC doubles
+// Contract on the operands: X holds npad rows of ndim doubles and GOGP_MAX_NDIM ZEROED doubles of slack behind them, and
+// its rows n .. npad - 1 are FINITE (the product zero-fills them); p->inv_len[t][d] is 0 for d >= ndim.  The last ARD pass
+// of the one-radial-term instances does not test d < ndim per slot: it multiplies the coordinates that follow a live
+// row's own -- the next row's, or the slack -- by inv_len = 0 (grad.hip).  Of alpha and Kinv only the elements i < n,
+// j <= i are used (alpha's first n; the whole 64 x 64 tile of Kinv may be LOADED: npad rows of ld >= npad).
+// max_blocks > 0 caps the grid below the GR_BLOCKS_MAX rule (tests: workgroups that walk several tiles at a small size).
 void launch_grad_reduce(hipStream_t s, const DevParams *p, int ndim, int ard_dims,
                         const double *X, const double *alpha, const double *Kinv, int64_t ld, int64_t n,
                         int64_t npad, double *partials, double *out, bool radial1 = false, int mfma_min_dims = 1,
-                        bool ev = false);
+                        bool ev = false, int max_blocks = 0);
 // the same over the LOCAL tiles (mrows x ncols, leading dimension ld) of a 2-D block-cyclic
 // K^-1: tiles of the global lower triangle only; `partials` needs grad_reduce_blocks_local
 int grad_reduce_blocks_local(int64_t mrows, int64_t ncols);
 void launch_grad_reduce_local(hipStream_t s, const DevParams *p, int ndim, int ard_dims,
                               const double *X, const double *alpha, const double *Kinv, int64_t ld,
                               int64_t n, int64_t mrows, int64_t ncols, BlockMap map, double *partials,
-                              double *out, bool radial1 = false, int mfma_min_dims = 1, bool ev = false);
+                              double *out, bool radial1 = false, int mfma_min_dims = 1, bool ev = false,
+                              int max_blocks = 0);
 void launch_grad_reduce_local(hipStream_t s, const DevParams *p, int ndim, int ard_dims,
                               const double *X, const double *alpha, const float *Kinv, int64_t ld,
                               int64_t n, int64_t mrows, int64_t ncols, BlockMap map, double *partials,
-                              double *out, bool radial1 = false, int mfma_min_dims = 1, bool ev = false);
+                              double *out, bool radial1 = false, int mfma_min_dims = 1, bool ev = false,
+                              int max_blocks = 0);
 
 // grad_mfma.hip: the reduction pass for ONE radial term with ARD length scales, distances and per-dimension sums
 // on the matrix cores; ntc == 0: lower triangle of an unsharded K^-1 (nt x nt tiles of 64, candidate batching

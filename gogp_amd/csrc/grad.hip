@@ -264,19 +264,22 @@ template <int AD, bool LOCAL, class KT, bool R1, bool EV = false, class... Args>
 static void gr_launch(dim3 grid, hipStream_t s, int ndim, Args... args) {
   const size_t lds = gr_lds_bytes(ndim, AD, EV);
   if (lds > 64 * 1024) {
-    static bool raised = false;  // per instance (template): the attribute sticks to the function
-    if (!raised) {
-      const void *fn;
-      if constexpr (EV) fn = reinterpret_cast<const void *>(&grad_reduce_kernel_ev<AD, LOCAL, KT, R1>);
-      else fn = reinterpret_cast<const void *>(&grad_reduce_kernel<AD, LOCAL, KT, R1>);
-      (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gr_lds_bytes(GOGP_MAX_NDIM, AD, EV));
-      raised = true;
-    }
+    // per launch, not once per process: the attribute belongs to the function ON THE CURRENT DEVICE, and a process may
+    // launch the same instance on several (cheap next to the kernel; grad_mfma.hip and launch_xgrad do the same)
+    const void *fn;
+    if constexpr (EV) fn = reinterpret_cast<const void *>(&grad_reduce_kernel_ev<AD, LOCAL, KT, R1>);
+    else fn = reinterpret_cast<const void *>(&grad_reduce_kernel<AD, LOCAL, KT, R1>);
+    (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gr_lds_bytes(GOGP_MAX_NDIM, AD, EV));
   }
   if constexpr (EV)
     GOGP_KLAUNCH((grad_reduce_kernel_ev<AD, LOCAL, KT, R1>), grid, dim3(256), lds, s, args...);
   else
     GOGP_KLAUNCH((grad_reduce_kernel<AD, LOCAL, KT, R1>), grid, dim3(256), lds, s, args...);
+}
+
+// max_blocks > 0 caps the grid (tests: a small problem whose workgroups walk several tiles); 0: GR_BLOCKS_MAX alone
+static inline int gr_cap_blocks(int blocks, int max_blocks) {
+  return max_blocks > 0 && max_blocks < blocks ? max_blocks : blocks;
 }
 
 int grad_reduce_blocks(int64_t npad) {
@@ -289,10 +292,10 @@ template <class KT>
 static void grad_reduce_t(hipStream_t s, const DevParams *p, int ndim, int ard_dims,
                           const double *X, const double *alpha, const KT *Kinv, int64_t ld,
                           int64_t n, int64_t npad, double *partials, double *out, bool radial1, int mfma_min,
-                          bool ev) {
+                          bool ev, int max_blocks) {
   const int nt = (int)(npad / 64);
   const int ntiles = nt * (nt + 1) / 2;
-  const int blocks = grad_reduce_blocks(npad);
+  const int blocks = gr_cap_blocks(grad_reduce_blocks(npad), max_blocks);
   const unsigned nz = (unsigned)tl_batch.k;
 // More than 16 ARD dimensions: passes of 16 per-dimension accumulators each.  (Instances with 32 / 64
 // accumulators need more than 256 VGPRs; the code hipcc (ROCm 7.2) generates for them -- VGPRs that carry
@@ -342,13 +345,15 @@ static void grad_reduce_t(hipStream_t s, const DevParams *p, int ndim, int ard_d
 }
 void launch_grad_reduce(hipStream_t s, const DevParams *p, int ndim, int ard_dims,
                         const double *X, const double *alpha, const double *Kinv, int64_t ld,
-                        int64_t n, int64_t npad, double *partials, double *out, bool radial1, int mfma_min, bool ev) {
-  grad_reduce_t(s, p, ndim, ard_dims, X, alpha, Kinv, ld, n, npad, partials, out, radial1, mfma_min, ev);
+                        int64_t n, int64_t npad, double *partials, double *out, bool radial1, int mfma_min, bool ev,
+                        int max_blocks) {
+  grad_reduce_t(s, p, ndim, ard_dims, X, alpha, Kinv, ld, n, npad, partials, out, radial1, mfma_min, ev, max_blocks);
 }
 void launch_grad_reduce(hipStream_t s, const DevParams *p, int ndim, int ard_dims,
                         const double *X, const double *alpha, const float *Kinv, int64_t ld,
-                        int64_t n, int64_t npad, double *partials, double *out, bool radial1, int mfma_min, bool ev) {
-  grad_reduce_t(s, p, ndim, ard_dims, X, alpha, Kinv, ld, n, npad, partials, out, radial1, mfma_min, ev);
+                        int64_t n, int64_t npad, double *partials, double *out, bool radial1, int mfma_min, bool ev,
+                        int max_blocks) {
+  grad_reduce_t(s, p, ndim, ard_dims, X, alpha, Kinv, ld, n, npad, partials, out, radial1, mfma_min, ev, max_blocks);
 }
 
 int grad_reduce_blocks_local(int64_t mrows, int64_t ncols) {
@@ -360,10 +365,10 @@ template <class KT>
 static void grad_reduce_local_t(hipStream_t s, const DevParams *p, int ndim, int ard_dims,
                                 const double *X, const double *alpha, const KT *Kinv, int64_t ld,
                                 int64_t n, int64_t mrows, int64_t ncols, BlockMap map, double *partials,
-                                double *out, bool radial1, int mfma_min, bool ev) {
+                                double *out, bool radial1, int mfma_min, bool ev, int max_blocks) {
   const int nt = (int)(mrows / 64), ntc = (int)(ncols / 64);
   const int ntiles = nt * ntc;
-  const int blocks = grad_reduce_blocks_local(mrows, ncols);
+  const int blocks = gr_cap_blocks(grad_reduce_blocks_local(mrows, ncols), max_blocks);
 #define GOGP_LAUNCH_GRL(AD, A0)                                                                   \
   do {                                                                                            \
     if (radial1)                                                                                  \
@@ -405,16 +410,16 @@ static void grad_reduce_local_t(hipStream_t s, const DevParams *p, int ndim, int
 void launch_grad_reduce_local(hipStream_t s, const DevParams *p, int ndim, int ard_dims,
                               const double *X, const double *alpha, const double *Kinv, int64_t ld,
                               int64_t n, int64_t mrows, int64_t ncols, BlockMap map, double *partials,
-                              double *out, bool radial1, int mfma_min, bool ev) {
+                              double *out, bool radial1, int mfma_min, bool ev, int max_blocks) {
   grad_reduce_local_t(s, p, ndim, ard_dims, X, alpha, Kinv, ld, n, mrows, ncols, map, partials, out, radial1, mfma_min,
-                      ev);
+                      ev, max_blocks);
 }
 void launch_grad_reduce_local(hipStream_t s, const DevParams *p, int ndim, int ard_dims,
                               const double *X, const double *alpha, const float *Kinv, int64_t ld,
                               int64_t n, int64_t mrows, int64_t ncols, BlockMap map, double *partials,
-                              double *out, bool radial1, int mfma_min, bool ev) {
+                              double *out, bool radial1, int mfma_min, bool ev, int max_blocks) {
   grad_reduce_local_t(s, p, ndim, ard_dims, X, alpha, Kinv, ld, n, mrows, ncols, map, partials, out, radial1, mfma_min,
-                      ev);
+                      ev, max_blocks);
 }
 
 // ---- gradient w.r.t. the inputs (full Observe form) ------------------------------

@@ -2,6 +2,7 @@
 // Built into gogp_amd/libgogp_testhooks.so, which links libgogp_hip.so and calls its
 // internal launchers; none of this is part of the product ABI (include/gogp_hip.h).
 #include <cstdlib>
+#include <cstring>
 #include <stdio.h>
 
 #include "common.h"
@@ -910,5 +911,211 @@ extern "C" int gogp_test_blockmm(int device, int precision, int nprod, void *are
     e = launched();
   }
   if (e == hipSuccess) e = dA.down(arena);
+  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+}
+
+// ---- the kernels that turn K^-1 into the gradient, through their product launchers (tests/test_grad_kernels.py) ----------
+namespace {
+static_assert(GOGP_TEST_NACC == NACC, "GOGP_TEST_NACC mirrors NACC");
+constexpr int64_t GR_NPAD_MAX = 1 << 15;
+// the launchers' selection arguments and the parameters they go with
+bool kparams_ok(const gogp_test_kparams *kp, int k, int ard_dims, int radial1, int mfma_min, int ev) {
+  if (!kp || k < 1) return false;
+  for (int c = 0; c < k; ++c) {
+    const gogp_test_kparams &q = kp[c];
+    if (q.ndim < 1 || q.ndim > GOGP_MAX_NDIM || q.nterms < 1 || q.nterms > GOGP_MAX_TERMS) return false;
+    if (q.ndim != kp[0].ndim || q.nterms != kp[0].nterms) return false;  // one launch sequence: one kernel shape
+    int nard = 0;
+    for (int t = 0; t < q.nterms; ++t) {
+      if (q.kind[t] < GOGP_K_NORMAL || q.kind[t] > GOGP_K_PERIODIC || q.kind[t] != kp[0].kind[t]) return false;
+      nard += q.ard[t] != 0;
+      for (int d = q.ndim; d < GOGP_MAX_NDIM; ++d)
+        if (q.inv_len[t][d] != 0.0) return false;  // the ARD pass relies on it (common.h: launch_grad_reduce)
+    }
+    if (nard > 1 || ard_dims != (nard ? q.ndim : 0)) return false;  // one ARD term at most; ard_dims is 0 or ndim
+    if (radial1 && (q.nterms != 1 || q.kind[0] == GOGP_K_PERIODIC)) return false;
+    if (q.nevents < 0 || q.nevents > GOGP_MAX_EVENTS || q.ev_axis < 0 || q.ev_axis >= q.ndim) return false;
+  }
+  if (ev && ard_dims > 0) return false;  // no instance has both (gogp_set_events refuses ARD)
+  return mfma_min >= 1;
+}
+DevParams to_dev(const gogp_test_kparams &q) {
+  DevParams p;
+  memset(&p, 0, sizeof p);
+  p.ndim = q.ndim;
+  p.nterms = q.nterms;
+  for (int t = 0; t < GOGP_MAX_TERMS; ++t) {
+    p.kind[t] = q.kind[t];
+    p.ard[t] = q.ard[t];
+    p.c[t] = q.c[t];
+    p.w[t] = q.w[t];
+    for (int d = 0; d < GOGP_MAX_NDIM; ++d) p.inv_len[t][d] = q.inv_len[t][d];
+  }
+  p.noise_var = q.noise_var;
+  p.dnoise = q.dnoise;
+  p.nevents = q.nevents;
+  p.ev_axis = q.ev_axis;
+  for (int e = 0; e < GOGP_MAX_EVENTS; ++e) {
+    p.ev_from[e] = q.ev_from[e];
+    p.ev_to[e] = q.ev_to[e];
+    p.ev_disc[e] = q.ev_disc[e];
+  }
+  return p;
+}
+// k parameter blocks / k rows of NACC, candidate c at c * stride bytes (stride 0 with k == 1)
+hipError_t up_strided(DevCopy &d, const void *h, size_t item, int k, size_t stride) {
+  std::vector<char> buf((size_t)(k - 1) * stride + item, 0);
+  for (int c = 0; c < k; ++c) memcpy(buf.data() + (size_t)c * stride, (const char *)h + (size_t)c * item, item);
+  return d.up(buf.data(), buf.size());
+}
+hipError_t down_strided(const DevCopy &d, void *h, size_t item, int k, size_t stride) {
+  std::vector<char> buf(d.bytes);
+  const hipError_t e = d.down(buf.data());
+  for (int c = 0; c < k && e == hipSuccess; ++c) memcpy((char *)h + (size_t)c * item, buf.data() + (size_t)c * stride, item);
+  return e;
+}
+int blocks_of(int64_t npad, int64_t mrows, int64_t ncols, int max_blocks) {
+  if (max_blocks < 0) return -1;
+  int b;
+  if (mrows == 0) {
+    if (ncols != 0 || npad <= 0 || npad % 64 || npad > GR_NPAD_MAX) return -1;
+    b = grad_reduce_blocks(npad);
+  } else {
+    if (mrows <= 0 || ncols <= 0 || mrows % 64 || ncols % 64 || mrows > GR_NPAD_MAX || ncols > GR_NPAD_MAX) return -1;
+    b = grad_reduce_blocks_local(mrows, ncols);
+  }
+  return max_blocks > 0 && max_blocks < b ? max_blocks : b;
+}
+}  // namespace
+
+extern "C" int gogp_test_grad_blocks(int64_t npad, int64_t mrows, int64_t ncols, int max_blocks) {
+  return blocks_of(npad, mrows, ncols, max_blocks);
+}
+
+extern "C" int gogp_test_grad_reduce(int device, int precision, const gogp_test_kparams *kparams, int ard_dims, int radial1,
+                                     int mfma_min, int ev, const double *X, int64_t x_len, const double *alpha,
+                                     int64_t alpha_len, const void *Kinv, int64_t kinv_len, int64_t ld, int64_t n,
+                                     int64_t npad, int max_blocks, int k, int64_t bstride, double *partials,
+                                     int64_t partials_len, double *out) {
+  if (!kparams || !X || !alpha || !Kinv || !partials || !out || !prec_ok(precision)) return GOGP_EARG;
+  if (k < 1 || k > GOGP_MAX_CANDIDATES || (k > 1 && precision != 64)) return GOGP_EARG;  // candidates: the fp64 path's
+  if (!kparams_ok(kparams, k, ard_dims, radial1, mfma_min, ev)) return GOGP_EARG;
+  const int blocks = blocks_of(npad, 0, 0, max_blocks);
+  if (blocks < 1 || n < 1 || n > npad || ld < npad) return GOGP_EARG;
+  const int ndim = kparams[0].ndim;
+  const int64_t prow = (int64_t)blocks * NACC;
+  if (k == 1) bstride = 0;
+  // every per-candidate buffer shares the byte stride: it must hold the largest of them
+  else if (bstride < (npad - 1) * ld + npad || bstride < prow || bstride * 8 < (int64_t)sizeof(DevParams)) return GOGP_EARG;
+  if (x_len < npad * ndim + GOGP_MAX_NDIM || !covers(alpha_len, 0, npad, 1, npad, k, bstride) ||
+      !covers(kinv_len, 0, ld, npad, npad, k, bstride) || !covers(partials_len, 0, prow, 1, prow, k, bstride))
+    return GOGP_EARG;
+  if (!device_ok(device)) return GOGP_EHIP;
+  std::vector<DevParams> hp;
+  for (int c = 0; c < k; ++c) hp.push_back(to_dev(kparams[c]));
+  const size_t sb = (size_t)bstride * 8;
+  DevCopy dP, dX, da, dK, dpart, dout;
+  hipError_t e = up_strided(dP, hp.data(), sizeof(DevParams), k, sb);
+  if (e == hipSuccess) e = dX.up(X, (size_t)x_len * sizeof(double));
+  if (e == hipSuccess) e = da.up(alpha, (size_t)alpha_len * sizeof(double));
+  if (e == hipSuccess) e = dK.up(Kinv, (size_t)kinv_len * (precision / 8));
+  if (e == hipSuccess) e = dpart.up(partials, (size_t)partials_len * sizeof(double));
+  if (e == hipSuccess) e = up_strided(dout, out, NACC * sizeof(double), k, sb);
+  if (e == hipSuccess) {
+    tl_batch.k = k;
+    tl_batch.stride = (long)sb;
+    if (precision == 64)
+      launch_grad_reduce(0, dP.as<DevParams>(), ndim, ard_dims, dX.as<double>(), da.as<double>(), dK.as<double>(), ld, n,
+                         npad, dpart.as<double>(), dout.as<double>(), radial1 != 0, mfma_min, ev != 0, max_blocks);
+    else
+      launch_grad_reduce(0, dP.as<DevParams>(), ndim, ard_dims, dX.as<double>(), da.as<double>(), dK.as<float>(), ld, n,
+                         npad, dpart.as<double>(), dout.as<double>(), radial1 != 0, mfma_min, ev != 0, max_blocks);
+    tl_batch.k = 1;
+    tl_batch.stride = 0;
+    e = launched();
+  }
+  if (e == hipSuccess) e = dpart.down(partials);
+  if (e == hipSuccess) e = down_strided(dout, out, NACC * sizeof(double), k, sb);
+  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+}
+
+extern "C" int gogp_test_grad_reduce_local(int device, int precision, const gogp_test_kparams *kparams, int ard_dims,
+                                           int radial1, int mfma_min, int ev, const double *X, int64_t x_len,
+                                           const double *alpha, int64_t alpha_len, const void *Kinv, int64_t kinv_len,
+                                           int64_t ld, int64_t n, int64_t npad, int64_t mrows, int64_t ncols, int nb_shift,
+                                           int pr, int Pr, int pc, int Pc, int max_blocks, int k, int64_t bstride,
+                                           double *partials, int64_t partials_len, double *out) {
+  (void)bstride;
+  if (!kparams || !X || !alpha || !Kinv || !partials || !out || !prec_ok(precision)) return GOGP_EARG;
+  if (k != 1) return GOGP_EARG;  // launch_grad_reduce_local has no candidate batch
+  if (!kparams_ok(kparams, 1, ard_dims, radial1, mfma_min, ev)) return GOGP_EARG;
+  if (mrows <= 0 || ncols <= 0) return GOGP_EARG;
+  const int blocks = blocks_of(npad, mrows, ncols, max_blocks);
+  if (blocks < 1 || npad <= 0 || npad % 64 || npad > GR_NPAD_MAX || n < 1 || n > npad || ld < ncols) return GOGP_EARG;
+  if (nb_shift < 6 || nb_shift > 14 || Pr < 1 || Pc < 1 || pr < 0 || pr >= Pr || pc < 0 || pc >= Pc) return GOGP_EARG;
+  BlockMap map;
+  map.nb_shift = nb_shift;
+  map.pr = pr;
+  map.Pr = Pr;
+  map.pc = pc;
+  map.Pc = Pc;
+  // the last local row / column must be a global one inside the padded matrix (the kernels read X and alpha there)
+  if (map.grow(mrows - 1) >= npad || map.gcol(ncols - 1) >= npad) return GOGP_EARG;
+  const int ndim = kparams[0].ndim;
+  const int64_t prow = (int64_t)blocks * NACC;
+  if (x_len < npad * ndim + GOGP_MAX_NDIM || alpha_len < npad || !covers(kinv_len, 0, ld, mrows, ncols, 1, 0) ||
+      partials_len < prow)
+    return GOGP_EARG;
+  if (!device_ok(device)) return GOGP_EHIP;
+  const DevParams hp = to_dev(kparams[0]);
+  DevCopy dP, dX, da, dK, dpart, dout;
+  hipError_t e = dP.up(&hp, sizeof hp);
+  if (e == hipSuccess) e = dX.up(X, (size_t)x_len * sizeof(double));
+  if (e == hipSuccess) e = da.up(alpha, (size_t)alpha_len * sizeof(double));
+  if (e == hipSuccess) e = dK.up(Kinv, (size_t)kinv_len * (precision / 8));
+  if (e == hipSuccess) e = dpart.up(partials, (size_t)partials_len * sizeof(double));
+  if (e == hipSuccess) e = dout.up(out, NACC * sizeof(double));
+  if (e == hipSuccess) {
+    if (precision == 64)
+      launch_grad_reduce_local(0, dP.as<DevParams>(), ndim, ard_dims, dX.as<double>(), da.as<double>(), dK.as<double>(), ld,
+                               n, mrows, ncols, map, dpart.as<double>(), dout.as<double>(), radial1 != 0, mfma_min, ev != 0,
+                               max_blocks);
+    else
+      launch_grad_reduce_local(0, dP.as<DevParams>(), ndim, ard_dims, dX.as<double>(), da.as<double>(), dK.as<float>(), ld,
+                               n, mrows, ncols, map, dpart.as<double>(), dout.as<double>(), radial1 != 0, mfma_min, ev != 0,
+                               max_blocks);
+    e = launched();
+  }
+  if (e == hipSuccess) e = dpart.down(partials);
+  if (e == hipSuccess) e = dout.down(out);
+  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+}
+
+extern "C" int gogp_test_xgrad(int device, const gogp_test_kparams *kparams, int ev, const double *X, int64_t x_len,
+                               const double *alpha, int64_t alpha_len, double *Kinv, int64_t kinv_len, int64_t ld, int64_t n,
+                               int64_t npad, double *gx, int64_t gx_len) {
+  if (!kparams || !X || !alpha || !Kinv || !gx) return GOGP_EARG;
+  int nard = 0;
+  for (int t = 0; t < GOGP_MAX_TERMS && kparams->nterms >= 1 && t < kparams->nterms; ++t) nard += kparams->ard[t] != 0;
+  if (!kparams_ok(kparams, 1, nard == 1 ? kparams->ndim : 0, 0, 1, 0)) return GOGP_EARG;
+  if (npad <= 0 || npad % 64 || npad > GR_NPAD_MAX || n < 1 || n > npad || ld < npad) return GOGP_EARG;
+  const int ndim = kparams->ndim;
+  if (x_len < npad * ndim || alpha_len < npad || !covers(kinv_len, 0, ld, npad, npad, 1, 0) || gx_len < npad * ndim)
+    return GOGP_EARG;
+  if (!device_ok(device)) return GOGP_EHIP;
+  const DevParams hp = to_dev(*kparams);
+  DevCopy dP, dX, da, dK, dg;
+  hipError_t e = dP.up(&hp, sizeof hp);
+  if (e == hipSuccess) e = dX.up(X, (size_t)x_len * sizeof(double));
+  if (e == hipSuccess) e = da.up(alpha, (size_t)alpha_len * sizeof(double));
+  if (e == hipSuccess) e = dK.up(Kinv, (size_t)kinv_len * sizeof(double));
+  if (e == hipSuccess) e = dg.up(gx, (size_t)gx_len * sizeof(double));
+  if (e == hipSuccess) {
+    launch_xgrad(0, dP.as<DevParams>(), ndim, dX.as<double>(), da.as<double>(), dK.as<double>(), ld, n, npad, dg.as<double>(),
+                 ev != 0);
+    e = launched();
+  }
+  if (e == hipSuccess) e = dK.down(Kinv);
+  if (e == hipSuccess) e = dg.down(gx);
   return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
 }

@@ -905,3 +905,89 @@ def blockmm_check(arena: np.ndarray, prods, alpha: float = 1.0, k: int = 1, bstr
     if rc != _lib.GOGP_OK:
         raise GogpError(rc, "test_blockmm")
     return arena
+
+
+# ---- the kernels that turn K^-1 into the gradient (include/gogp_testhooks.h; tests/test_grad_kernels.py) -------------
+NACC = _lib.GOGP_TEST_NACC
+ACC_TRACE, ACC_ARD0 = 12, 16
+
+
+def kparams(ndim: int, terms, noise_var: float = 0.0, dnoise: float = 0.0, events=(), ev_axis: int = 0):
+    """A gogp_test_kparams.  terms: dicts with kind, and optionally ard (False), c (1.0), w (0.0) and inv_len (a number, or
+    ndim of them for an ARD term); events: (from, to, discount) triples."""
+    if not 1 <= ndim <= 64 or not 1 <= len(terms) <= 4 or len(events) > 32:
+        raise ValueError("kparams: 1..64 dimensions, 1..4 terms, at most 32 events")
+    p = _lib.CKParams()
+    p.ndim, p.nterms, p.noise_var, p.dnoise, p.nevents, p.ev_axis = ndim, len(terms), noise_var, dnoise, len(events), ev_axis
+    for t, T in enumerate(terms):
+        p.kind[t], p.ard[t], p.c[t], p.w[t] = int(T["kind"]), int(bool(T.get("ard"))), T.get("c", 1.0), T.get("w", 0.0)
+        il = np.broadcast_to(np.asarray(T.get("inv_len", 1.0), float), (ndim,))
+        for d in range(ndim):
+            p.inv_len[t][d] = il[d]
+    for e, (frm, to, disc) in enumerate(events):
+        p.ev_from[e], p.ev_to[e], p.ev_disc[e] = frm, to, disc
+    return p
+
+
+def grad_blocks(npad: int, max_blocks: int = 0, mrows: int = 0, ncols: int = 0) -> int:
+    """Workgroups (rows of `partials`) of launch_grad_reduce, or with mrows, ncols of launch_grad_reduce_local."""
+    b = _lib.hooks().gogp_test_grad_blocks(npad, mrows, ncols, max_blocks)
+    if b < 0:
+        raise GogpError(_lib.GOGP_EARG, "test_grad_blocks")
+    return int(b)
+
+
+def _kp_array(kp):
+    kps = list(kp) if isinstance(kp, (list, tuple)) else [kp]
+    return (_lib.CKParams * len(kps))(*kps), len(kps)
+
+
+def grad_reduce_check(kp, X: np.ndarray, alpha: np.ndarray, Kinv: np.ndarray, ld: int, n: int, npad: int,
+                      partials: np.ndarray, out: np.ndarray, ard_dims: int = 0, radial1: bool = False, mfma_min: int = 1,
+                      ev: bool = False, max_blocks: int = 0, bstride: int = 0, device: int = -1):
+    """launch_grad_reduce (test hook gogp_test_grad_reduce) on flat host arrays; kp: one kparams(), or a list of k of them
+    (candidates, bstride elements apart).  Returns copies of (partials, out) after the launch; out is k x NACC."""
+    arr, k = _kp_array(kp)
+    X, alpha, Kinv = _vec(X, "X"), _vec(alpha, "alpha"), _mat(Kinv, "Kinv")
+    partials, out = _vec(partials, "partials").copy(), _vec(out, "out").copy()
+    if out.size != k * NACC:
+        raise ValueError("out: k x NACC")
+    rc = _lib.hooks().gogp_test_grad_reduce(device, _prec(Kinv), arr, ard_dims, int(radial1), mfma_min, int(ev), _dp(X),
+                                            X.size, _dp(alpha), alpha.size, Kinv.ctypes.data, Kinv.size, ld, n, npad,
+                                            max_blocks, k, bstride, _dp(partials), partials.size, _dp(out))
+    if rc != _lib.GOGP_OK:
+        raise GogpError(rc, "test_grad_reduce")
+    return partials, out.reshape(k, NACC)
+
+
+def grad_reduce_local_check(kp, X: np.ndarray, alpha: np.ndarray, Kinv: np.ndarray, ld: int, n: int, npad: int, mrows: int,
+                            ncols: int, grid, partials: np.ndarray, out: np.ndarray, ard_dims: int = 0,
+                            radial1: bool = False, mfma_min: int = 1, ev: bool = False, max_blocks: int = 0,
+                            nb_shift: int = 9, device: int = -1):
+    """launch_grad_reduce_local (test hook gogp_test_grad_reduce_local); grid = (pr, Pr, pc, Pc).  Returns copies of
+    (partials, out) after the launch."""
+    arr, k = _kp_array(kp)
+    X, alpha, Kinv = _vec(X, "X"), _vec(alpha, "alpha"), _mat(Kinv, "Kinv")
+    partials, out = _vec(partials, "partials").copy(), _vec(out, "out").copy()
+    if out.size != NACC:
+        raise ValueError("out: NACC")
+    pr, Pr, pc, Pc = grid
+    rc = _lib.hooks().gogp_test_grad_reduce_local(device, _prec(Kinv), arr, ard_dims, int(radial1), mfma_min, int(ev),
+                                                  _dp(X), X.size, _dp(alpha), alpha.size, Kinv.ctypes.data, Kinv.size, ld,
+                                                  n, npad, mrows, ncols, nb_shift, pr, Pr, pc, Pc, max_blocks, k, 0,
+                                                  _dp(partials), partials.size, _dp(out))
+    if rc != _lib.GOGP_OK:
+        raise GogpError(rc, "test_grad_reduce_local")
+    return partials, out
+
+
+def xgrad_check(kp, X: np.ndarray, alpha: np.ndarray, Kinv: np.ndarray, ld: int, n: int, npad: int, gx: np.ndarray,
+                ev: bool = False, device: int = -1):
+    """launch_xgrad (test hook gogp_test_xgrad); returns copies of (Kinv, gx) after the launch."""
+    X, alpha = _vec(X, "X"), _vec(alpha, "alpha")
+    Kinv, gx = _vec(Kinv, "Kinv").copy(), _vec(gx, "gx").copy()
+    rc = _lib.hooks().gogp_test_xgrad(device, ctypes.byref(kp), int(ev), _dp(X), X.size, _dp(alpha), alpha.size, _dp(Kinv),
+                                      Kinv.size, ld, n, npad, _dp(gx), gx.size)
+    if rc != _lib.GOGP_OK:
+        raise GogpError(rc, "test_xgrad")
+    return Kinv, gx

@@ -11,6 +11,8 @@
 
 #include <stdint.h>
 
+#include "gogp_hip.h" /* GOGP_MAX_TERMS, GOGP_MAX_NDIM, GOGP_MAX_EVENTS */
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -127,6 +129,57 @@ int gogp_test_tinv(int device, int precision, int nsub, const void *Dinv, void *
 int gogp_test_blockmm(int device, int precision, int nprod, void *arena, int64_t arena_len, const int64_t *a_off,
                       const int64_t *lda, const int64_t *b_off, const int64_t *ldb, const int64_t *c_off,
                       const int64_t *ldc, const int *K, double alpha, int k, int64_t bstride);
+
+/* ---- the kernels that turn K^-1 into the gradient, through their product launchers (tests/test_grad_kernels.py):
+ * grad_reduce_kernel and grad_final_kernel (grad.hip), grad_ard_mfma_kernel (grad_mfma.hip), mirror_lower_kernel and
+ * xgrad_kernel (grad.hip).  The rules of the hooks above: lengths count elements, every array goes to the device whole and
+ * every in / out array whole back, GOGP_EARG before the device is touched for anything a launch cannot honour or the
+ * arrays do not cover. */
+
+/* Every field of the kernels' DevParams (gogp_amd/csrc/common.h) that they read, stated directly -- not derived from a
+ * descriptor and natural parameters as the product does: inv_len[t][d] = 1 / l_d of term t (0 for d >= ndim), w[t] =
+ * pi / period of a periodic term, c[t] its output scale. */
+typedef struct gogp_test_kparams {
+  int32_t ndim, nterms;
+  int32_t kind[GOGP_MAX_TERMS], ard[GOGP_MAX_TERMS];
+  double c[GOGP_MAX_TERMS], w[GOGP_MAX_TERMS], inv_len[GOGP_MAX_TERMS][GOGP_MAX_NDIM];
+  double noise_var, dnoise;
+  int32_t nevents, ev_axis;
+  double ev_from[GOGP_MAX_EVENTS], ev_to[GOGP_MAX_EVENTS], ev_disc[GOGP_MAX_EVENTS];
+} gogp_test_kparams;
+
+#define GOGP_TEST_NACC (16 + GOGP_MAX_NDIM) /* slot sums of the reduction (common.h: NACC) */
+
+/* Workgroups launch_grad_reduce (mrows == 0: npad x npad, lower tiles) or launch_grad_reduce_local (mrows x ncols local
+ * tiles) starts for max_blocks: `partials` holds that many rows of GOGP_TEST_NACC.  -1: bad arguments.  No device. */
+int gogp_test_grad_blocks(int64_t npad, int64_t mrows, int64_t ncols, int max_blocks);
+
+/* launch_grad_reduce.  precision: element type of Kinv (64 / 32; npad rows of ld >= npad).  kparams: k structs.  X:
+ * npad * ndim + GOGP_MAX_NDIM doubles (the slack the product allocates zeroed).  ard_dims: 0 or ndim (exactly when one
+ * term has ard set); radial1: one term, not periodic; ev: the instances with event discounts (never with ard_dims).
+ * max_blocks: 0 or a cap on the grid.  k > 1 (precision 64 only): candidates -- X is shared; candidate c's alpha, Kinv and
+ * partials lie c * bstride ELEMENTS after candidate 0's in their host arrays (on the device every per-candidate buffer,
+ * the parameters included, c * bstride * 8 bytes after candidate 0's: bstride must cover each of them).  partials (in /
+ * out): gogp_test_grad_blocks rows; out (in / out): k x GOGP_TEST_NACC, compact. */
+int gogp_test_grad_reduce(int device, int precision, const gogp_test_kparams *kparams, int ard_dims, int radial1,
+                          int mfma_min, int ev, const double *X, int64_t x_len, const double *alpha, int64_t alpha_len,
+                          const void *Kinv, int64_t kinv_len, int64_t ld, int64_t n, int64_t npad, int max_blocks, int k,
+                          int64_t bstride, double *partials, int64_t partials_len, double *out);
+
+/* launch_grad_reduce_local: the same over the mrows x ncols local tiles (ld >= ncols) of a 2-D block-cyclic K^-1 of npad
+ * rows, distribution blocks of 2^nb_shift, this rank at (pr, pc) of the Pr x Pc grid (common.h: BlockMap).  X and alpha
+ * are the global ones.  The launcher has no candidates: k must be 1. */
+int gogp_test_grad_reduce_local(int device, int precision, const gogp_test_kparams *kparams, int ard_dims, int radial1,
+                                int mfma_min, int ev, const double *X, int64_t x_len, const double *alpha,
+                                int64_t alpha_len, const void *Kinv, int64_t kinv_len, int64_t ld, int64_t n, int64_t npad,
+                                int64_t mrows, int64_t ncols, int nb_shift, int pr, int Pr, int pc, int Pc, int max_blocks,
+                                int k, int64_t bstride, double *partials, int64_t partials_len, double *out);
+
+/* launch_xgrad: mirrors the lower triangle of Kinv (npad rows of ld; in / out) to the upper one outside the diagonal
+ * 32 x 32 blocks, then gx (npad x ndim; in / out) rows < n := sum_j (alpha_i alpha_j - Kinv_ij) dk(x_i, x_j) / dx_i. */
+int gogp_test_xgrad(int device, const gogp_test_kparams *kparams, int ev, const double *X, int64_t x_len,
+                    const double *alpha, int64_t alpha_len, double *Kinv, int64_t kinv_len, int64_t ld, int64_t n,
+                    int64_t npad, double *gx, int64_t gx_len);
 
 /* Benchmark hook for the tile kernel: `reps` launches of one shape (mode 0 RECT
  * mt x nt tiles, 1 LOWER mt x mt, 2 LAUUM mt x mt with K = mt*128) on device
