@@ -399,6 +399,32 @@ func (gp *GP) ProduceCovariance(x [][]float64) (mu, cov []float64, err error) {
 	return mu, cov, nil
 }
 
+// LOO computes the leave-one-out cross-validation predictions at the current
+// parameters: mean, standard deviation and log density of every observation
+// under the process fitted to the others, and the sum of the log densities (no
+// reference counterpart).
+func (gp *GP) LOO() (mu, sigma, logp []float64, total float64, err error) {
+	gp.defaults()
+	n := int(C.gogp_n(gp.handle()))
+	mu, sigma, logp = make([]float64, n), make([]float64, n), make([]float64, n)
+	var t C.double
+	if err = gp.err(C.gogp_loo(gp.handle(), dptr(mu), dptr(sigma), dptr(logp), &t)); err != nil {
+		return nil, nil, nil, 0, err
+	}
+	return mu, sigma, logp, float64(t), nil
+}
+
+// LOOGradient computes the gradient of the LOO score with respect to the
+// log-transformed hyperparameters (no reference counterpart).
+func (gp *GP) LOOGradient() ([]float64, error) {
+	gp.defaults()
+	g := make([]float64, len(gp.ThetaSimil)+len(gp.ThetaNoise))
+	if err := gp.err(C.gogp_loo_gradient(gp.handle(), dptr(g), C.int64_t(len(g)))); err != nil {
+		return nil, err
+	}
+	return g, nil
+}
+
 // Sample draws len(xi)/len(x) joint samples at the test points from the
 // caller's standard normals xi (row-major ns x m): samples[s*m+j] =
 // mu[j] + (C xi[s])[j], C the lower Cholesky factor of the covariance +

@@ -83,6 +83,8 @@ SYMBOLS = [
     ("gogp_observe_full", ctypes.c_int, [_h, _dp, _i64, _dp]),
     ("gogp_lml", ctypes.c_int, [_h, _dp]),
     ("gogp_gradient", ctypes.c_int, [_h, _dp, _i64]),
+    ("gogp_loo", ctypes.c_int, [_h, _dp, _dp, _dp, _dp]),
+    ("gogp_loo_gradient", ctypes.c_int, [_h, _dp, _i64]),
     ("gogp_observe_gradient_batch", ctypes.c_int,
      [ctypes.POINTER(_h), ctypes.c_int, _dp, _i64, _dp, _dp, ctypes.POINTER(ctypes.c_int)]),
     ("gogp_observe_gradient_candidates", ctypes.c_int,

@@ -104,6 +104,8 @@ static void free_n_buffers(gogp_handle *h) {
   h->small_ws.release();
   h->app_ws.release();
   h->rm_ws.release();
+  h->loo_vec.release();
+  h->loo_mat.release();
   (void)hipFree(h->TX);
   (void)hipFree(h->Tmt);
   h->TX = h->Tmt = nullptr;
@@ -1542,6 +1544,103 @@ extern "C" int gogp_gradient(gogp_handle *h, double *grad, int64_t len) {
   return GOGP_OK;
 }
 
+// ---- leave-one-out cross-validation (loo.hip) ----------------------------------------------------------------------
+// No reference counterpart (its forecast harness refits per prefix).  Both calls read the explicit K^-1 the gradient
+// leaves in bufA (lower tiles) and alpha, and write only workspaces of their own: the handle's state afterwards is
+// what a gogp_gradient at this point would have left -- K^-1 formed -- and nothing a later call reads has changed.
+struct LooVecs {
+  double *mu, *sigma, *logp, *v, *sc, *u, *zero, *part;
+};
+// The refusals of both calls, then -- with observations -- K^-1 and alpha ordered on the main stream and the vectors in
+// place.  *empty: n == 0, nothing to launch.
+static int loo_prepare(gogp_handle *h, const char *who, LooVecs *lv, bool *empty) {
+  char buf[160];
+  const char *refuse = h->prec == 32        ? "precision = 32 handles"
+                       : mixed_gradient(h) ? "gradient_precision = 32 (a float K^-1)"
+                       : h->dist           ? "sharded handles"
+                                           : nullptr;
+  if (refuse) {
+    snprintf(buf, sizeof buf, "%s: %s are not supported", who, refuse);
+    return fail(h, GOGP_EARG, buf);
+  }
+  *empty = h->n == 0;
+  if (*empty) return GOGP_OK;
+  if (!h->factored) {
+    snprintf(buf, sizeof buf, "%s: nothing absorbed", who);
+    return fail(h, GOGP_ESTATE, buf);
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  int rc = compute_kinv(h);
+  if (rc == GOGP_OK) rc = ensure_alpha(h);
+  const size_t np = (size_t)h->npad;
+  if (rc == GOGP_OK) rc = h->loo_vec.reserve(h, (7 * np + np / PANEL) * sizeof(double));
+  if (rc != GOGP_OK) return rc;
+  double *q = h->loo_vec.as<double>();
+  *lv = LooVecs{q, q + np, q + 2 * np, q + 3 * np, q + 4 * np, q + 5 * np, q + 6 * np, q + 7 * np};
+  launch_loo_stats(h->s, h->bufA, h->npad, h->alpha, h->dy, h->n, h->npad, lv->mu, lv->sigma, lv->logp, lv->v, lv->sc,
+                   lv->part);
+  return GOGP_OK;
+}
+
+extern "C" int gogp_loo(gogp_handle *h, double *mu, double *sigma, double *logp, double *total) {
+  if (!h) return GOGP_EARG;
+  LooVecs lv;
+  bool empty = false;
+  const int rc = loo_prepare(h, "LOO", &lv, &empty);
+  if (rc != GOGP_OK) return rc;
+  if (total) *total = 0.0;
+  if (empty) return GOGP_OK;
+  hipStream_t s = h->s;
+  const size_t vec = (size_t)h->n * sizeof(double);
+  std::vector<double> part((size_t)(h->npad / PANEL));
+  if (mu) HIPCHK(h, hipMemcpyAsync(mu, lv.mu, vec, hipMemcpyDeviceToHost, s));
+  if (sigma) HIPCHK(h, hipMemcpyAsync(sigma, lv.sigma, vec, hipMemcpyDeviceToHost, s));
+  if (logp) HIPCHK(h, hipMemcpyAsync(logp, lv.logp, vec, hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipMemcpyAsync(part.data(), lv.part, part.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipStreamSynchronize(s));
+  HIPCHK(h, hipGetLastError());
+  double t = 0.0;
+  for (double b : part) t += b;  // the block sums, in block order
+  if (total) *total = t;
+  return GOGP_OK;
+}
+
+extern "C" int gogp_loo_gradient(gogp_handle *h, double *grad, int64_t len) {
+  if (!h || !grad) return fail(h, GOGP_EARG, "LOO gradient: NULL");
+  if (len != h->P) return fail(h, GOGP_EARG, "LOO gradient: wrong length");
+  LooVecs lv;
+  bool empty = false;
+  int rc = loo_prepare(h, "LOO gradient", &lv, &empty);
+  if (rc != GOGP_OK) return rc;
+  for (int64_t i = 0; i < len; ++i) grad[i] = 0.0;
+  if (empty) return GOGP_OK;
+  hipStream_t s = h->s;
+  const int64_t npad = h->npad, ld = npad;
+  const size_t mat = (size_t)npad * (size_t)npad;
+  rc = h->loo_mat.reserve(h, 2 * mat * sizeof(double));
+  if (rc != GOGP_OK) return rc;
+  double *B = h->loo_mat.as<double>(), *G = B + mat;
+  // B = K^-1 diag(s), u = K^-1 v (its partial sums in G, which is free until the product)
+  launch_loo_scale_symv(s, h->bufA, ld, h->n, npad, lv.sc, lv.v, B, ld, G, lv.u);
+  // G = B B^T - u alpha^T - alpha u^T = -2 W on the lower tiles
+  launch_gemm_nt(s, GEMM_LOWER, h->nblk, h->nblk, npad, 1.0, (const double *)B, ld, (const double *)B, ld, 0.0, G, ld,
+                 &h->prof);
+  launch_loo_rank2(s, G, ld, h->n, npad, lv.u, h->alpha);
+  // sum_ab (0 0^T - G)_ab dK_ab per slot: the reduction of the LML gradient with G for K^-1 and zeros for alpha
+  HIPCHK(h, hipMemsetAsync(lv.zero, 0, (size_t)npad * sizeof(double), s));
+  {
+    AuxTimer tm(h, GOGP_PROF_GRAD, s);
+    launch_grad_reduce(s, h->devP, h->D, h->ard_dims, h->dX, lv.zero, (const double *)G, ld, h->n, npad, h->gpart, h->gout,
+                       h->radial1, h->ard_mfma_min, h->ev());
+  }
+  double acc[NACC];
+  HIPCHK(h, hipMemcpyAsync(acc, h->gout, sizeof acc, hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipStreamSynchronize(s));
+  HIPCHK(h, hipGetLastError());
+  assemble_gradient(h, acc, h->hostP->dnoise, grad);
+  return GOGP_OK;
+}
+
 // ---- one evaluation of many (the candidates call, batch_eval): parameters in, results out ----------------------------
 // DevParams of log parameters x (gp/gp.go:378-385: theta = exp(x)).  Unusable parameters are replaced by theta = 1 and
 // reported as GOGP_EARG: that evaluation is still launched with the others, and its status says so.
@@ -2668,6 +2767,7 @@ extern "C" int gogp_set_factor(gogp_handle *h, const double *theta_simil,
   h->trtri_done = h->trtri_pending = h->kinv_pending = false;
   h->tinv_valid = false;  // Produce on a restored factor substitutes panel by panel
   h->z_valid = false;     // no z = L^-1 y comes with a restored factor (gogp_append recomputes it)
+  h->kinv_c1 = 0;         // ... and no partial K^-1 of an earlier sweep belongs to it (compute_kinv: gogp_loo)
   if (h->n == 0) return GOGP_OK;
   if (h->dist) return gogp_dist_set_factor(h, Lin, alpha);  // collective: every rank keeps its own tiles
   rc = gogp_upload_params(h);

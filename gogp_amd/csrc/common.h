@@ -424,6 +424,16 @@ void launch_remove_w(hipStream_t s, const double *src, int64_t ld0, const int *m
                      int64_t n1, int64_t npad1, double *W);
 void launch_remove_snap(hipStream_t s, const double *L, int64_t ld, int b0, int nb, double *snap);
 void launch_remove_block(hipStream_t s, double *L, int64_t ld, const double *snap, double *W, int mw, int64_t kb, int64_t n1);
+// loo.hip (gogp_loo, gogp_loo_gradient): the passes over K^-1 (lower triangle, ld) behind leave-one-out cross-validation.
+// launch_loo_stats: mu, sigma, log p of the rows i < n, v_i = alpha_i / kappa_i and s_i (zero from row n on; npad doubles
+// each) and the npad / 256 block sums of log p in `part`.  launch_loo_scale_symv: B (npad x npad, ldb) = K^-1 diag(s) in
+// full and u = K^-1 v, both exactly zero from row / column n on; upart: npad / 64 * npad doubles of scratch.
+// launch_loo_rank2: G_ij -= u_i alpha_j + alpha_i u_j on the lower 64-tiles.
+void launch_loo_stats(hipStream_t s, const double *Kinv, int64_t ld, const double *alpha, const double *y, int64_t n,
+                      int64_t npad, double *mu, double *sigma, double *logp, double *v, double *sc, double *part);
+void launch_loo_scale_symv(hipStream_t s, const double *Kinv, int64_t ld, int64_t n, int64_t npad, const double *sc,
+                           const double *v, double *B, int64_t ldb, double *upart, double *u);
+void launch_loo_rank2(hipStream_t s, double *G, int64_t ld, int64_t n, int64_t npad, const double *u, const double *alpha);
 void launch_fill(hipStream_t s, double *p, int64_t count, double v);
 void launch_axpy(hipStream_t s, double *a, const double *b, int64_t count);  // a += b
 void launch_dot(hipStream_t s, const double *a, const double *b, int64_t n, double *out);  // out[0] = a.b

@@ -215,6 +215,8 @@ struct gogp_handle : EvalBufs, EvalState {
   // released with the N buffers (api.hip: free_n_buffers)
   Workspace app_ws;         // gogp_append: the saved block inverse + the partial sums of its Gram kernel (append.hip)
   Workspace rm_ws;          // gogp_remove: index maps, a pass's columns of W, the diagonal-block snapshot, compacted X / y (remove.hip)
+  Workspace loo_vec;        // gogp_loo / gogp_loo_gradient: mu, sigma, log p, v, s, u, a zero vector and the block sums (loo.hip)
+  Workspace loo_mat;        // gogp_loo_gradient: B = K^-1 diag(s) and G = B B^T - u alpha^T - alpha u^T, npad x npad each
   double yta = 0.0;      // y^T alpha of the last factorisation (fp32 path: of the refined alpha)
   int trace_fp64 = 1;    // fp32 path: tr(alpha alpha^T - K^-1) summed in fp64 from Y, scale component by its identity
   double cond_limit = 1e16;  // gonum's mat.ConditionTolerance

@@ -357,6 +357,31 @@ class GP:
         self._check(_lib.lib().gogp_gradient(self._h, _dp(g), g.size))
         return g
 
+    # ---- leave-one-out cross-validation (no reference counterpart: its forecast harness refits per prefix) ----
+    def LOO(self):
+        """(mu, sigma, logp), n entries each: the prediction of Y[i] -- mean, standard deviation with the noise,
+        log density of the observed value -- by the process fitted to the other n - 1 observations, at the
+        parameters of the last Absorb / Observe / restore, from the explicit K^-1 (gogp_loo; Rasmussen & Williams
+        5.4.2).  ``logp.sum()`` is the LOO-CV score.  Works after Absorb, Observe, Append, Remove and restore and
+        leaves the process as it found it.  fp64, unsharded handles only."""
+        n = int(_lib.lib().gogp_n(self._h))
+        mu, sigma, logp = np.zeros(n), np.zeros(n), np.zeros(n)
+        self._check(_lib.lib().gogp_loo(self._h, _dp(mu), _dp(sigma), _dp(logp), None))
+        return mu, sigma, logp
+
+    def LOOScore(self) -> float:
+        """The LOO-CV score sum(logp) alone, summed on the device in a fixed order (gogp_loo with NULL arrays)."""
+        v = ctypes.c_double(0.0)
+        self._check(_lib.lib().gogp_loo(self._h, None, None, None, ctypes.byref(v)))
+        return v.value
+
+    def LOOGradient(self) -> np.ndarray:
+        """d (LOO-CV score) / d log theta, one entry per hyperparameter (gogp_loo_gradient): one extra symmetric
+        product for all of them."""
+        g = np.zeros(self._ns + self._nn)
+        self._check(_lib.lib().gogp_loo_gradient(self._h, _dp(g), g.size))
+        return g
+
     # ---- cached computations: gp.GP.L, gp.GP.Alpha (gp/gp.go:34-37) ----------------------
     @property
     def Alpha(self) -> np.ndarray:
@@ -634,6 +659,35 @@ class Model:
     def Gradient(self) -> np.ndarray:
         g = self._gGrad.copy()
         g[:len(self._pGrad)] += self._pGrad
+        return g
+
+
+class LOOModel:
+    """Model with the leave-one-out cross-validation score in the place of the LML: Observe(x) runs gp.Observe(x) and
+    returns GP.LOOScore() (+ the log prior), Gradient() returns GP.LOOGradient() (+ the prior's).  optimize.lbfgs and
+    optimize.Adam.Step then fit the hyperparameters (x = log theta, no observations in x) to the LOO objective.  The
+    batched line search (``line_search_candidates`` > 1) evaluates the LML and is not offered: the GP is ``gp`` here,
+    not ``GP``."""
+
+    def __init__(self, gp: GP, Priors=None):
+        self.gp = gp
+        self.Priors = Priors
+        self._x = None
+
+    def Observe(self, x) -> float:
+        self._x = _arr(x).reshape(-1).copy()
+        if self._x.size != self.gp._ns + self.gp._nn:
+            raise ValueError("len(x): the LOO objective takes the hyperparameters only")
+        self.gp.Observe(self._x)
+        v = self.gp.LOOScore()
+        return v + self.Priors.Observe(self._x) if self.Priors is not None else v
+
+    def Gradient(self) -> np.ndarray:
+        g = self.gp.LOOGradient()
+        if self.Priors is not None:
+            self.Priors.Observe(self._x)
+            pg = np.asarray(self.Priors.Gradient(), dtype=float)
+            g[:len(pg)] += pg
         return g
 
 

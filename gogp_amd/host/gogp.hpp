@@ -165,6 +165,25 @@ class GP {
     return gogp_produce_covariance(h_, flat.data(), (int64_t)x.size(), mu.data(), cov.data()) == GOGP_OK;
   }
 
+  // Leave-one-out cross-validation at the current parameters (gogp_loo): the prediction of Y[i] by the process fitted
+  // to the other observations -- mean, standard deviation, log density -- and the sum of the log densities; no
+  // reference counterpart
+  double LOO(std::vector<double> &mu, std::vector<double> &sigma, std::vector<double> &logp) {
+    const size_t n = (size_t)gogp_n(h_);
+    mu.assign(n, 0.0);
+    sigma.assign(n, 0.0);
+    logp.assign(n, 0.0);
+    double total = 0.0;
+    check(gogp_loo(h_, mu.data(), sigma.data(), logp.data(), &total));
+    return total;
+  }
+  // d (LOO score) / d log theta, one entry per hyperparameter (gogp_loo_gradient)
+  std::vector<double> LOOGradient() {
+    std::vector<double> g(ThetaSimil.size() + ThetaNoise.size(), 0.0);
+    check(gogp_loo_gradient(h_, g.data(), (int64_t)g.size()));
+    return g;
+  }
+
   // ns = xi.size() / x.size() joint draws mu + C xi[s] (row-major ns x x.size()) from the caller's standard normals,
   // C the lower Cholesky factor of the covariance + diag_add I; no reference counterpart
   bool Sample(const std::vector<std::vector<double>> &x, const std::vector<double> &xi, double diag_add,

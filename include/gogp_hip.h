@@ -194,6 +194,37 @@ int gogp_lml(gogp_handle *h, double *lml);
  * (gp/gp.go:427-430). */
 int gogp_gradient(gogp_handle *h, double *grad, int64_t len);
 
+/* Leave-one-out cross-validation (Rasmussen & Williams 5.4.2) at the parameters of the last gogp_absorb /
+ * gogp_observe[_full] / gogp_set_factor; no reference counterpart (its forecast harness refits per prefix).  From the
+ * explicit K^-1 the gradient leaves on the device, kappa_i = [K^-1]_ii, and alpha:
+ *     mu_i = y_i - alpha_i / kappa_i,  sigma_i = sqrt(1 / kappa_i),
+ *     logp_i = 1/2 log kappa_i - 1/2 alpha_i^2 / kappa_i - 1/2 log 2 pi,  total = sum_i logp_i
+ * -- the prediction of y_i, noise included, by the process fitted to the other n - 1 observations.  mu, sigma, logp:
+ * n doubles each, any of them may be NULL; total may be NULL.
+ * gogp_loo_gradient: d total / d log theta, P = ntheta_simil + ntheta_noise entries (`len` must be P; also after
+ * gogp_observe_full: the observations' own derivatives are not formed).  One extra symmetric product for all
+ * parameters: sum_ab W_ab dK_ab with W = 1/2 (u alpha^T + alpha u^T) - K^-1 diag(w) K^-1, v_i = alpha_i / kappa_i,
+ * u = K^-1 v, w_i = 1/2 (1 + alpha_i^2 / kappa_i) / kappa_i, reduced by the kernels of gogp_gradient, so every kernel
+ * family, ARD and the event discounts of gogp_set_events are covered.
+ * Works wherever gogp_produce works with the data on the device: after Absorb (no Observe needed), Observe in either
+ * form, gogp_append, gogp_remove and gogp_set_factor.  Where K^-1 is not there yet (Absorb, option "eager" = 0, after
+ * Append / Remove / set_factor) the call forms it as gogp_gradient does.  The handle is left as it was found: a
+ * gogp_gradient, gogp_produce, gogp_get_factor or gogp_append made afterwards returns the bits it would have returned
+ * before.  Two identical calls return identical bits (fixed-order sums, no atomics).  n == 0: total = 0, the arrays
+ * are not written, the gradient is zeros.  Nothing is clamped: for a positive definite K every kappa_i > 0, otherwise
+ * the values are what the divisions yield (as sigma of gogp_produce).
+ * GOGP_ESTATE before anything is factored; GOGP_EARG for len != P, a precision = 32 handle, "gradient_precision" = 32
+ * (a float K^-1) and a sharded handle (the restrictions of gogp_append).
+ * Device memory: gogp_loo 7 vectors of npad doubles; gogp_loo_gradient also two npad x npad fp64 matrices (4.3 GB at
+ * n = 16384), allocated on first use and kept until the data's buffers are released.
+ * Cost, measured on one MI355X with K^-1 in place (profiles/loo.txt; D = 8, beside Observe + Gradient on the same
+ * build): gogp_loo 0.08 / 0.07 / 0.10 ms at n = 1024 / 4096 / 16384 -- one 5 us kernel over the diagonal, the rest is
+ * the copies and the synchronise; gogp_loo_gradient 0.13 / 1.50 / 67.8 ms against 0.68 / 3.1 / 70.9 ms for
+ * Observe + Gradient, i.e. one more evaluation at n = 16384, of which the product B B^T is 65 ms (n^3 flops at
+ * 68 TFLOP/s), the pass over K^-1 0.84 ms, the rank-2 correction 0.44 ms and the reduction 0.60 ms. */
+int gogp_loo(gogp_handle *h, double *mu, double *sigma, double *logp, double *total);
+int gogp_loo_gradient(gogp_handle *h, double *grad, int64_t len);
+
 /* k independent Observe + Gradient evaluations at once: handle hs[i] (each created and given
  * its data separately; they may hold the same data) evaluates x[i*len .. (i+1)*len) from its own
  * host thread, so the dependent launch chains of the k evaluations overlap on the GPU.
