@@ -188,6 +188,26 @@ HOOK_SYMBOLS = [
     ("gogp_test_xgrad", ctypes.c_int,
      [ctypes.c_int, ctypes.POINTER(CKParams), ctypes.c_int, _dp, _i64, _dp, _i64, _dp, _i64, _i64, _i64, _i64, _dp,
       _i64]),
+    # the kernels of Append, Remove, ProduceGradient's product and ProduceCovariance (tests/test_update_kernels.py)
+    ("gogp_test_append_gram", ctypes.c_int,
+     [ctypes.c_int] + [ctypes.c_void_p, _i64, ctypes.c_int, ctypes.c_int, _i64] * 2
+     + [ctypes.c_int, ctypes.c_int, _i64, _i64, _dp, _i64, _dp, _i64, _dp, _i64, _i64]),
+    ("gogp_test_append_commit", ctypes.c_int,
+     [ctypes.c_int, ctypes.POINTER(CKParams), ctypes.c_int, _dp, _i64, _dp, _i64, ctypes.c_int, _i64, _dp, _i64,
+      ctypes.c_int, _dp, _i64, _i64, _dp, _i64, ctypes.POINTER(ctypes.c_longlong)]),
+    ("gogp_test_remove_gather", ctypes.c_int,
+     [ctypes.c_int, _dp, _i64, _i64, ctypes.POINTER(ctypes.c_int), _i64, _i64, _dp, _i64, _i64]),
+    ("gogp_test_remove_w", ctypes.c_int,
+     [ctypes.c_int, _dp, _i64, _i64, ctypes.POINTER(ctypes.c_int), _i64, ctypes.POINTER(ctypes.c_int), _i64, ctypes.c_int,
+      ctypes.c_int, _i64, _i64, _i64, _dp, _i64]),
+    ("gogp_test_remove_block", ctypes.c_int,
+     [ctypes.c_int, _dp, _i64, _i64, ctypes.c_int, ctypes.c_int, _dp, _i64, _dp, _i64, ctypes.c_int, _i64, _i64, _i64]),
+    ("gogp_test_bwd_panel", ctypes.c_int,
+     [ctypes.c_int, _i64] + [_dp, _i64, _i64, _i64] * 3 + [_i64, _i64, ctypes.c_int, ctypes.c_int]),
+    ("gogp_test_pcov_slabs", ctypes.c_int, [_i64, _i64, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
+    ("gogp_test_pcov", ctypes.c_int,
+     [ctypes.c_int, ctypes.POINTER(CKParams), ctypes.c_int, _dp, _i64, _i64, _dp, _i64, _i64, _i64, ctypes.c_int, _dp, _i64,
+      ctypes.c_double, _dp, _i64, _i64, _i64]),
     # per-rank replay of the sharded sweep (tools/sharded_replay.py): a transport that reads recorded panels
     ("gogp_test_dist_init_replay", ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int] * 4),
 ]

@@ -1119,3 +1119,231 @@ extern "C" int gogp_test_xgrad(int device, const gogp_test_kparams *kparams, int
   if (e == hipSuccess) e = dg.down(gx);
   return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
 }
+
+// ---- the kernels that update a factor or consume Produce's V^T, through their product launchers
+// (tests/test_update_kernels.py): append_gram_kernel and append_commit_kernel (append.hip), the gather, W, snapshot and
+// block kernels of remove.hip, bwd_panel_kernel (pgrad.hip) and the two kernels of launch_pcov (pcov.hip).  The rules of the
+// hooks above.
+namespace {
+// bytes a solution of `cols` right-hand sides over npc rows occupies from its first byte on; -1: not a layout
+int64_t sol_bytes(int kind, int width, int cols, int64_t npc) {
+  if (cols < 0 || width < 1) return -1;
+  switch (kind) {
+    case TS_SOL_PAIRED: return cols <= width ? npc * width * 8 : -1;  // npc is even
+    case TS_SOL_COMPACT: return cols <= width ? npc * width * 8 : -1;
+    case TS_SOL_GRANULE: return width == 1 && cols <= 1 ? npc * 16 : -1;
+    case TS_SOL_ROWS: return width >= npc ? (cols ? ((int64_t)(cols - 1) * width + npc) * 8 : 0) : -1;
+    default: return -1;
+  }
+}
+bool sol_ok(const void *p, int64_t len, int kind, int width, int64_t off, int cols, int64_t npc) {
+  const int64_t need = sol_bytes(kind, width, cols, npc);
+  if (need < 0) return false;
+  if (cols == 0) return true;  // never read
+  return p && off >= 0 && off % (kind == TS_SOL_GRANULE ? 16 : 8) == 0 && off + need <= len;
+}
+// the one-term-at-most ARD count kparams_ok wants stated
+int ard_dims_of(const gogp_test_kparams *kp) {
+  if (!kp || kp->nterms < 1 || kp->nterms > GOGP_MAX_TERMS) return 0;
+  int nard = 0;
+  for (int t = 0; t < kp->nterms; ++t) nard += kp->ard[t] != 0;
+  return nard == 1 ? kp->ndim : 0;
+}
+// every entry of an index list names a row of a matrix of leading dimension ld0 that src (src_len elements) holds whole
+bool rows_ok(const int *idx, int64_t cnt, int64_t ld0, int64_t src_len) {
+  for (int64_t i = 0; i < cnt; ++i)
+    if (idx[i] < 0 || idx[i] >= ld0 || ((int64_t)idx[i] + 1) * ld0 > src_len) return false;
+  return true;
+}
+constexpr int64_t UP_NPAD_MAX = 1 << 15;
+}  // namespace
+
+extern "C" int gogp_test_append_gram(int device, const void *sol0, int64_t sol0_len, int kind0, int width0, int64_t off0,
+                                     const void *sol1, int64_t sol1_len, int kind1, int width1, int64_t off1, int m0, int m,
+                                     int64_t npc, int64_t n, const double *z, int64_t z_len, double *part, int64_t part_len,
+                                     double *Lnew, int64_t lnew_len, int64_t ld) {
+  if (!z || !part || !Lnew || m < 1 || m > 64 || m0 < 0 || m0 > m) return GOGP_EARG;
+  if (npc <= 0 || npc % PANEL || npc > UP_NPAD_MAX || n < 0 || n > npc || ld < n) return GOGP_EARG;
+  if (!sol_ok(sol0, sol0_len, kind0, width0, off0, m0, npc) || !sol_ok(sol1, sol1_len, kind1, width1, off1, m - m0, npc))
+    return GOGP_EARG;
+  if (z_len < npc || part_len < npc / PANEL * APPEND_PART || lnew_len <= 0) return GOGP_EARG;
+  if (n > 0 && !covers(lnew_len, 0, ld, m, n, 1, 0)) return GOGP_EARG;
+  if (!device_ok(device)) return GOGP_EHIP;
+  DevCopy d0, d1, dz, dpart, dL;
+  hipError_t e = d0.up(m0 ? sol0 : nullptr, (size_t)sol0_len);
+  if (e == hipSuccess) e = d1.up(m - m0 ? sol1 : nullptr, (size_t)sol1_len);
+  if (e == hipSuccess) e = dz.up(z, (size_t)z_len * sizeof(double));
+  if (e == hipSuccess) e = dpart.up(part, (size_t)part_len * sizeof(double));
+  if (e == hipSuccess) e = dL.up(Lnew, (size_t)lnew_len * sizeof(double));
+  if (e == hipSuccess) {
+    TsSolution v0, v1;
+    v0.p = d0.d ? d0.d + off0 : nullptr;
+    v0.kind = kind0;
+    v0.width = width0;
+    v1.p = d1.d ? d1.d + off1 : nullptr;
+    v1.kind = kind1;
+    v1.width = width1;
+    launch_append_gram(0, v0, v1, m0, m, npc, n, dz.as<double>(), dpart.as<double>(), dL.as<double>(), ld);
+    e = launched();
+  }
+  if (e == hipSuccess) e = dpart.down(part);
+  if (e == hipSuccess) e = dL.down(Lnew);
+  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+}
+
+extern "C" int gogp_test_append_commit(int device, const gogp_test_kparams *kparams, int ev, const double *X2, int64_t x2_len,
+                                       const double *y2, int64_t y2_len, int m, int64_t n, const double *part,
+                                       int64_t part_len, int nslab, double *Lnew, int64_t lnew_len, int64_t ld, double *z2,
+                                       int64_t z2_len, long long *info) {
+  if (!kparams || !X2 || !y2 || !part || !Lnew || !z2 || !info) return GOGP_EARG;
+  if (!kparams_ok(kparams, 1, ard_dims_of(kparams), 0, 1, ev)) return GOGP_EARG;
+  if (m < 1 || m > 64 || n < 0 || n > UP_NPAD_MAX || nslab < 1 || nslab > UP_NPAD_MAX / PANEL) return GOGP_EARG;
+  if (x2_len < (int64_t)m * kparams->ndim || y2_len < m || z2_len < m || part_len < (int64_t)nslab * APPEND_PART)
+    return GOGP_EARG;
+  if (!covers(lnew_len, 0, ld, m, n + m, 1, 0)) return GOGP_EARG;
+  if (!device_ok(device)) return GOGP_EHIP;
+  const DevParams hp = to_dev(*kparams);
+  DevCopy dP, dX, dy, dpart, dL, dz, di;
+  hipError_t e = dP.up(&hp, sizeof hp);
+  if (e == hipSuccess) e = dX.up(X2, (size_t)x2_len * sizeof(double));
+  if (e == hipSuccess) e = dy.up(y2, (size_t)y2_len * sizeof(double));
+  if (e == hipSuccess) e = dpart.up(part, (size_t)part_len * sizeof(double));
+  if (e == hipSuccess) e = dL.up(Lnew, (size_t)lnew_len * sizeof(double));
+  if (e == hipSuccess) e = dz.up(z2, (size_t)z2_len * sizeof(double));
+  if (e == hipSuccess) e = di.up(info, sizeof(long long));
+  if (e == hipSuccess) {
+    launch_append_commit(0, dP.as<DevParams>(), dX.as<double>(), dy.as<double>(), m, n, dpart.as<double>(), nslab,
+                         dL.as<double>(), ld, dz.as<double>(), di.as<long long>(), ev != 0);
+    e = launched();
+  }
+  if (e == hipSuccess) e = dL.down(Lnew);
+  if (e == hipSuccess) e = dz.down(z2);
+  if (e == hipSuccess) e = di.down(info);
+  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+}
+
+extern "C" int gogp_test_remove_gather(int device, const double *src, int64_t src_len, int64_t ld0, const int *map,
+                                       int64_t map_len, int64_t n1, double *dst, int64_t dst_len, int64_t npad1) {
+  if (!src || !map || !dst || npad1 <= 0 || npad1 % PANEL || npad1 > UP_NPAD_MAX || n1 < 1 || n1 > npad1) return GOGP_EARG;
+  if (ld0 < 1 || map_len < n1 || dst_len < npad1 * npad1 || !rows_ok(map, n1, ld0, src_len)) return GOGP_EARG;
+  if (!device_ok(device)) return GOGP_EHIP;
+  DevCopy ds, dm, dd;
+  hipError_t e = ds.up(src, (size_t)src_len * sizeof(double));
+  if (e == hipSuccess) e = dm.up(map, (size_t)map_len * sizeof(int));
+  if (e == hipSuccess) e = dd.up(dst, (size_t)dst_len * sizeof(double));
+  if (e == hipSuccess) {
+    launch_remove_gather(0, ds.as<double>(), ld0, dm.as<int>(), n1, dd.as<double>(), npad1);
+    e = launched();
+  }
+  if (e == hipSuccess) e = dd.down(dst);
+  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+}
+
+extern "C" int gogp_test_remove_w(int device, const double *src, int64_t src_len, int64_t ld0, const int *map,
+                                  int64_t map_len, const int *rem, int64_t rem_len, int mc, int mw, int64_t r0, int64_t n1,
+                                  int64_t npad1, double *W, int64_t w_len) {
+  if (!src || !map || !rem || !W || npad1 <= 0 || npad1 % PANEL || npad1 > UP_NPAD_MAX || n1 < 1 || n1 > npad1)
+    return GOGP_EARG;
+  if (mw < 1 || mw > REMOVE_W || mc < 1 || mc > mw || r0 < 0 || r0 >= npad1) return GOGP_EARG;
+  if (ld0 < 1 || map_len < n1 || rem_len < mc || w_len < (int64_t)mw * npad1) return GOGP_EARG;
+  if (!rows_ok(map, n1, ld0, src_len) || !rows_ok(rem, mc, ld0, src_len)) return GOGP_EARG;
+  if (!device_ok(device)) return GOGP_EHIP;
+  DevCopy ds, dm, dr, dW;
+  hipError_t e = ds.up(src, (size_t)src_len * sizeof(double));
+  if (e == hipSuccess) e = dm.up(map, (size_t)map_len * sizeof(int));
+  if (e == hipSuccess) e = dr.up(rem, (size_t)rem_len * sizeof(int));
+  if (e == hipSuccess) e = dW.up(W, (size_t)w_len * sizeof(double));
+  if (e == hipSuccess) {
+    launch_remove_w(0, ds.as<double>(), ld0, dm.as<int>(), dr.as<int>(), mc, mw, r0, n1, npad1, dW.as<double>());
+    e = launched();
+  }
+  if (e == hipSuccess) e = dW.down(W);
+  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+}
+
+extern "C" int gogp_test_remove_block(int device, double *L, int64_t l_len, int64_t ld, int snap_b0, int snap_nb,
+                                      double *snap, int64_t snap_len, double *W, int64_t w_len, int mw, int64_t kb0,
+                                      int64_t kb1, int64_t n1) {
+  if (!L || !snap || !W || ld <= 0 || ld % PANEL || ld > UP_NPAD_MAX || n1 < 1 || n1 > ld) return GOGP_EARG;
+  if (mw != REMOVE_W_SMALL && mw != REMOVE_W) return GOGP_EARG;
+  if (kb0 < 0 || kb0 % TILE || kb1 < kb0 || kb1 % TILE || kb1 + TILE > ld) return GOGP_EARG;  // the block's rows of W: < ldw = ld
+  if (snap_b0 < 0 || snap_nb < 0 || (int64_t)(snap_b0 + snap_nb) * TILE > ld) return GOGP_EARG;
+  if (l_len < ld * ld || w_len < (int64_t)mw * ld || snap_len < (kb1 / TILE + 1) * (int64_t)(TILE * TILE) ||
+      snap_len < (int64_t)(snap_b0 + snap_nb) * (TILE * TILE))
+    return GOGP_EARG;
+  if (!device_ok(device)) return GOGP_EHIP;
+  DevCopy dL, ds, dW;
+  hipError_t e = dL.up(L, (size_t)l_len * sizeof(double));
+  if (e == hipSuccess) e = ds.up(snap, (size_t)snap_len * sizeof(double));
+  if (e == hipSuccess) e = dW.up(W, (size_t)w_len * sizeof(double));
+  if (e == hipSuccess) {
+    launch_remove_snap(0, dL.as<double>(), ld, snap_b0, snap_nb, ds.as<double>());
+    for (int64_t kb = kb0; kb <= kb1; kb += TILE)
+      launch_remove_block(0, dL.as<double>(), ld, ds.as<double>(), dW.as<double>(), mw, kb, n1);
+    e = launched();
+  }
+  if (e == hipSuccess) e = dL.down(L);
+  if (e == hipSuccess) e = ds.down(snap);
+  if (e == hipSuccess) e = dW.down(W);
+  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+}
+
+extern "C" int gogp_test_bwd_panel(int device, int64_t rows16, const double *A, int64_t a_len, int64_t a_off, int64_t lda,
+                                   const double *B, int64_t b_len, int64_t b_off, int64_t ldb, double *C, int64_t c_len,
+                                   int64_t c_off, int64_t ldc, int64_t ncols, int64_t K, int tri, int sub) {
+  if (!A || !B || !C || rows16 < 1 || rows16 > 4096 || ncols <= 0 || ncols % 64 || ncols > UP_NPAD_MAX) return GOGP_EARG;
+  if (K <= 0 || K % 32 || K > UP_NPAD_MAX) return GOGP_EARG;
+  // beyond 32 rows the kernel takes whole groups of 64 (common.h): A and C must hold them
+  const int64_t rows = rows16 <= 2 ? 16 * rows16 : (rows16 + 3) / 4 * 64;
+  if (!covers(a_len, a_off, lda, rows, K, 1, 0) || !covers(b_len, b_off, ldb, K, ncols, 1, 0) ||
+      !covers(c_len, c_off, ldc, rows, ncols, 1, 0))
+    return GOGP_EARG;
+  if (!device_ok(device)) return GOGP_EHIP;
+  DevCopy dA, dB, dC;
+  hipError_t e = dA.up(A, (size_t)a_len * sizeof(double));
+  if (e == hipSuccess) e = dB.up(B, (size_t)b_len * sizeof(double));
+  if (e == hipSuccess) e = dC.up(C, (size_t)c_len * sizeof(double));
+  if (e == hipSuccess) {
+    launch_bwd_panel(0, rows16, dA.as<double>() + a_off, lda, dB.as<double>() + b_off, ldb, dC.as<double>() + c_off, ldc,
+                     ncols, (int)K, tri != 0, sub != 0);
+    e = launched();
+  }
+  if (e == hipSuccess) e = dC.down(C);
+  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+}
+
+extern "C" int gogp_test_pcov_slabs(int64_t npad, int64_t m, int ncu, int *cols_per_slab) {
+  if (npad <= 0 || npad % PANEL || npad > (1 << 20) || m < 1 || m > GOGP_COV_MAX_M || ncu < 1 || ncu > 4096) return -1;
+  return pcov_slabs(npad, m, ncu, cols_per_slab);
+}
+
+extern "C" int gogp_test_pcov(int device, const gogp_test_kparams *kparams, int ev, const double *Z, int64_t z_len, int64_t m,
+                              const double *Vt, int64_t vt_len, int64_t ld, int64_t npad, int ncu, double *part,
+                              int64_t part_len, double diag_add, double *out, int64_t out_len, int64_t mo, int64_t ldo) {
+  if (!kparams || !Z || !out || !kparams_ok(kparams, 1, ard_dims_of(kparams), 0, 1, ev)) return GOGP_EARG;
+  if (m < 1 || m > GOGP_COV_MAX_M || mo < m || mo > GOGP_COV_MAX_M || z_len < m * kparams->ndim) return GOGP_EARG;
+  if (!covers(out_len, 0, ldo, mo, mo, 1, 0)) return GOGP_EARG;
+  if (Vt) {
+    int cps = 0;
+    const int nslab = gogp_test_pcov_slabs(npad, m, ncu, &cps);
+    const int64_t tiles = (m + 63) / 64, pairs = tiles * (tiles + 1) / 2;
+    if (nslab < 1 || npad > UP_NPAD_MAX || ld % 2 || !covers(vt_len, 0, ld, m, npad, 1, 0)) return GOGP_EARG;  // 16-B loads
+    if (!part || part_len < nslab * pairs * 4096) return GOGP_EARG;
+  }
+  if (!device_ok(device)) return GOGP_EHIP;
+  const DevParams hp = to_dev(*kparams);
+  DevCopy dP, dZ, dV, dpart, dout;
+  hipError_t e = dP.up(&hp, sizeof hp);
+  if (e == hipSuccess) e = dZ.up(Z, (size_t)z_len * sizeof(double));
+  if (e == hipSuccess && Vt) e = dV.up(Vt, (size_t)vt_len * sizeof(double));
+  if (e == hipSuccess && part && part_len > 0) e = dpart.up(part, (size_t)part_len * sizeof(double));
+  if (e == hipSuccess) e = dout.up(out, (size_t)out_len * sizeof(double));
+  if (e == hipSuccess) {
+    launch_pcov(0, dP.as<DevParams>(), dZ.as<double>(), m, dV.as<double>(), ld, npad, ncu, dpart.as<double>(), diag_add,
+                dout.as<double>(), mo, ldo, ev != 0);
+    e = launched();
+  }
+  if (e == hipSuccess && part) e = dpart.down(part);
+  if (e == hipSuccess) e = dout.down(out);
+  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+}

@@ -1045,3 +1045,120 @@ def xgrad_check(kp, X: np.ndarray, alpha: np.ndarray, Kinv: np.ndarray, ld: int,
     if rc != _lib.GOGP_OK:
         raise GogpError(rc, "test_xgrad")
     return Kinv, gx
+
+
+# ---- the kernels of Append, Remove, ProduceGradient's skinny product and ProduceCovariance (include/gogp_testhooks.h;
+# tests/test_update_kernels.py) ------------------------------------------------------------------------------------------
+TS_SOL_ROWS = 3
+
+
+def _raw(a, what):
+    if a is None:
+        return None, 0
+    if not isinstance(a, np.ndarray) or a.dtype != np.uint8 or not a.flags.c_contiguous:
+        raise TypeError("%s: a C-contiguous uint8 array" % what)
+    return a.ctypes.data, a.size
+
+
+def _ints(a, what):
+    if not isinstance(a, np.ndarray) or a.dtype != np.int32 or not a.flags.c_contiguous:
+        raise TypeError("%s: a C-contiguous int32 array" % what)
+    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
+
+
+def append_gram_check(src0, src1, m0: int, m: int, npc: int, n: int, z: np.ndarray, part: np.ndarray, Lnew: np.ndarray,
+                      ld: int, device: int = -1):
+    """launch_append_gram (test hook gogp_test_append_gram).  src0, src1: (raw bytes or None, kind, width, byte offset) of
+    the two sources of V.  Returns copies of (part, Lnew) after the launch."""
+    (r0, k0, w0, o0), (r1, k1, w1, o1) = src0, src1
+    p0, n0 = _raw(r0, "src0")
+    p1, n1 = _raw(r1, "src1")
+    z, part, Lnew = _vec(z, "z"), _vec(part, "part").copy(), _vec(Lnew, "Lnew").copy()
+    rc = _lib.hooks().gogp_test_append_gram(device, p0, n0, k0, w0, o0, p1, n1, k1, w1, o1, m0, m, npc, n, _dp(z), z.size,
+                                            _dp(part), part.size, _dp(Lnew), Lnew.size, ld)
+    if rc != _lib.GOGP_OK:
+        raise GogpError(rc, "test_append_gram")
+    return part, Lnew
+
+
+def append_commit_check(kp, X2: np.ndarray, y2: np.ndarray, m: int, n: int, part: np.ndarray, nslab: int, Lnew: np.ndarray,
+                        ld: int, z2: np.ndarray, info: int = 0, ev: bool = False, device: int = -1):
+    """launch_append_commit (test hook gogp_test_append_commit); returns copies of (Lnew, z2) and info after the launch."""
+    X2, y2, part = _vec(X2, "X2"), _vec(y2, "y2"), _vec(part, "part")
+    Lnew, z2 = _vec(Lnew, "Lnew").copy(), _vec(z2, "z2").copy()
+    inf = ctypes.c_longlong(info)
+    rc = _lib.hooks().gogp_test_append_commit(device, ctypes.byref(kp), int(ev), _dp(X2), X2.size, _dp(y2), y2.size, m, n,
+                                              _dp(part), part.size, nslab, _dp(Lnew), Lnew.size, ld, _dp(z2), z2.size,
+                                              ctypes.byref(inf))
+    if rc != _lib.GOGP_OK:
+        raise GogpError(rc, "test_append_commit")
+    return Lnew, z2, int(inf.value)
+
+
+def remove_gather_check(src: np.ndarray, ld0: int, map_: np.ndarray, n1: int, dst: np.ndarray, npad1: int,
+                        device: int = -1):
+    """launch_remove_gather (test hook gogp_test_remove_gather); returns a copy of dst after the launch."""
+    src, dst = _vec(src, "src"), _vec(dst, "dst").copy()
+    rc = _lib.hooks().gogp_test_remove_gather(device, _dp(src), src.size, ld0, _ints(map_, "map"), map_.size, n1, _dp(dst),
+                                              dst.size, npad1)
+    if rc != _lib.GOGP_OK:
+        raise GogpError(rc, "test_remove_gather")
+    return dst
+
+
+def remove_w_check(src: np.ndarray, ld0: int, map_: np.ndarray, rem: np.ndarray, mc: int, mw: int, r0: int, n1: int,
+                   npad1: int, W: np.ndarray, device: int = -1):
+    """launch_remove_w (test hook gogp_test_remove_w); returns a copy of W after the launch."""
+    src, W = _vec(src, "src"), _vec(W, "W").copy()
+    rc = _lib.hooks().gogp_test_remove_w(device, _dp(src), src.size, ld0, _ints(map_, "map"), map_.size, _ints(rem, "rem"),
+                                         rem.size, mc, mw, r0, n1, npad1, _dp(W), W.size)
+    if rc != _lib.GOGP_OK:
+        raise GogpError(rc, "test_remove_w")
+    return W
+
+
+def remove_block_check(L: np.ndarray, ld: int, W: np.ndarray, mw: int, kb0: int, kb1: int, n1: int, snap: np.ndarray,
+                       snap_b0: int, snap_nb: int, device: int = -1):
+    """launch_remove_snap (blocks snap_b0 .. snap_b0 + snap_nb - 1), then launch_remove_block for kb = kb0, kb0 + 128, ..,
+    kb1 (test hook gogp_test_remove_block).  Returns copies of (L, W, snap) after the launches."""
+    L, W, snap = _vec(L, "L").copy(), _vec(W, "W").copy(), _vec(snap, "snap").copy()
+    rc = _lib.hooks().gogp_test_remove_block(device, _dp(L), L.size, ld, snap_b0, snap_nb, _dp(snap), snap.size, _dp(W),
+                                             W.size, mw, kb0, kb1, n1)
+    if rc != _lib.GOGP_OK:
+        raise GogpError(rc, "test_remove_block")
+    return L, W, snap
+
+
+def bwd_panel_check(rows16: int, A: np.ndarray, a_off: int, lda: int, B: np.ndarray, b_off: int, ldb: int, C: np.ndarray,
+                    c_off: int, ldc: int, ncols: int, K: int, tri: bool = False, sub: bool = False, device: int = -1):
+    """launch_bwd_panel (test hook gogp_test_bwd_panel); returns a copy of C after the launch."""
+    A, B, C = _vec(A, "A"), _vec(B, "B"), _vec(C, "C").copy()
+    rc = _lib.hooks().gogp_test_bwd_panel(device, rows16, _dp(A), A.size, a_off, lda, _dp(B), B.size, b_off, ldb, _dp(C),
+                                          C.size, c_off, ldc, ncols, K, int(tri), int(sub))
+    if rc != _lib.GOGP_OK:
+        raise GogpError(rc, "test_bwd_panel")
+    return C
+
+
+def pcov_slabs(npad: int, m: int, ncu: int):
+    """(slabs, columns per slab) of launch_pcov for ncu compute units.  No device."""
+    cps = ctypes.c_int(0)
+    ns = _lib.hooks().gogp_test_pcov_slabs(npad, m, ncu, ctypes.byref(cps))
+    if ns < 0:
+        raise GogpError(_lib.GOGP_EARG, "test_pcov_slabs")
+    return int(ns), int(cps.value)
+
+
+def pcov_check(kp, Z: np.ndarray, m: int, Vt, ld: int, npad: int, ncu: int, part, out: np.ndarray, mo: int, ldo: int,
+               diag_add: float = 0.0, ev: bool = False, device: int = -1):
+    """launch_pcov (test hook gogp_test_pcov) with the number of compute units given; Vt None: the prior Gram matrix (part
+    may be None then).  Returns copies of (part, out) after the launch."""
+    Z, out = _vec(Z, "Z"), _vec(out, "out").copy()
+    Vt = None if Vt is None else _vec(Vt, "Vt")
+    part = None if part is None else _vec(part, "part").copy()
+    size = lambda a: 0 if a is None else a.size  # noqa: E731
+    rc = _lib.hooks().gogp_test_pcov(device, ctypes.byref(kp), int(ev), _dp(Z), Z.size, m, _dp(Vt), size(Vt), ld, npad, ncu,
+                                     _dp(part), size(part), diag_add, _dp(out), out.size, mo, ldo)
+    if rc != _lib.GOGP_OK:
+        raise GogpError(rc, "test_pcov")
+    return part, out

@@ -181,6 +181,66 @@ int gogp_test_xgrad(int device, const gogp_test_kparams *kparams, int ev, const 
                     const double *alpha, int64_t alpha_len, double *Kinv, int64_t kinv_len, int64_t ld, int64_t n,
                     int64_t npad, double *gx, int64_t gx_len);
 
+/* ---- the kernels that update a factor or consume Produce's V^T, through their product launchers
+ * (tests/test_update_kernels.py): append_gram_kernel and append_commit_kernel (append.hip), the kernels of remove.hip,
+ * bwd_panel_kernel (pgrad.hip) and the two kernels of launch_pcov (pcov.hip).  The rules of the hooks above: lengths count
+ * elements (BYTES for the raw solution buffers, as sol_len of gogp_test_trsm_small), every array goes to the device whole
+ * and every in / out array whole back, GOGP_EARG before the device is touched. */
+
+/* launch_append_gram: V (npc rows, a multiple of 256; m <= 64 right-hand sides) is read from two raw buffers -- the columns
+ * j < m0 from sol0, the others (as column j - m0) from sol1 --, each in the layout `kind` (common.h: TS_SOL_*; 3 = ROWS, one
+ * solution per row of `width` doubles) of `width`, beginning `off` bytes into the buffer.  A buffer no column is read from
+ * may be NULL.  z: npc doubles.  part (in / out): npc / 256 slots of 64 * 64 + 64 doubles.  Lnew (in / out): m rows of ld,
+ * columns k < n <= npc are written. */
+int gogp_test_append_gram(int device, const void *sol0, int64_t sol0_len, int kind0, int width0, int64_t off0,
+                          const void *sol1, int64_t sol1_len, int kind1, int width1, int64_t off1, int m0, int m,
+                          int64_t npc, int64_t n, const double *z, int64_t z_len, double *part, int64_t part_len,
+                          double *Lnew, int64_t lnew_len, int64_t ld);
+
+/* launch_append_commit: S = k(X2, X2) + noise - sum of the nslab parts, its factor to Lnew (in / out; m rows of ld) columns
+ * n .. n + m - 1, z2 (in / out) = L22^-1 (y2 - sum of the parts' V^T z); not positive definite: *info (in / out) = n + pivot
+ * + 1 unless it was non-zero already, nothing else written. */
+int gogp_test_append_commit(int device, const gogp_test_kparams *kparams, int ev, const double *X2, int64_t x2_len,
+                            const double *y2, int64_t y2_len, int m, int64_t n, const double *part, int64_t part_len,
+                            int nslab, double *Lnew, int64_t lnew_len, int64_t ld, double *z2, int64_t z2_len,
+                            long long *info);
+
+/* launch_remove_gather: dst (in / out; npad1 x npad1) from src (leading dimension ld0) through map (n1 old row indices,
+ * every one a row src holds whole). */
+int gogp_test_remove_gather(int device, const double *src, int64_t src_len, int64_t ld0, const int *map, int64_t map_len,
+                            int64_t n1, double *dst, int64_t dst_len, int64_t npad1);
+
+/* launch_remove_w: W (in / out; mw <= 32 columns of npad1 doubles) rows r0 .. npad1 - 1 from src[map, rem[0 .. mc)]. */
+int gogp_test_remove_w(int device, const double *src, int64_t src_len, int64_t ld0, const int *map, int64_t map_len,
+                       const int *rem, int64_t rem_len, int mc, int mw, int64_t r0, int64_t n1, int64_t npad1, double *W,
+                       int64_t w_len);
+
+/* launch_remove_snap for the 128-blocks snap_b0 .. snap_b0 + snap_nb - 1 (none with snap_nb == 0: the snapshot is what the
+ * caller hands in), then launch_remove_block for kb = kb0, kb0 + 128, .. kb1 (kb1 == kb0: one step; the product loops to the
+ * last kb < n1).  L (in / out): ld x ld, ld a multiple of 256; W (in / out): mw (4 or 32) columns of ld doubles; snap
+ * (in / out): 128 x 128 doubles per block, block b at b * 16384. */
+int gogp_test_remove_block(int device, double *L, int64_t l_len, int64_t ld, int snap_b0, int snap_nb, double *snap,
+                           int64_t snap_len, double *W, int64_t w_len, int mw, int64_t kb0, int64_t kb1, int64_t n1);
+
+/* launch_bwd_panel: C (in / out) = A B, or C - A B with sub; A 16 rows16 x K, B K x ncols, C 16 rows16 x ncols at element
+ * offsets into their arrays; ncols a multiple of 64, K of 32.  Beyond 32 rows the kernel works on groups of 64 rows: A and
+ * C must hold 64 ceil(rows16 / 4) rows then (GOGP_EARG otherwise). */
+int gogp_test_bwd_panel(int device, int64_t rows16, const double *A, int64_t a_len, int64_t a_off, int64_t lda,
+                        const double *B, int64_t b_len, int64_t b_off, int64_t ldb, double *C, int64_t c_len, int64_t c_off,
+                        int64_t ldc, int64_t ncols, int64_t K, int tri, int sub);
+
+/* pcov_slabs: the number of slabs launch_pcov splits npad columns into for m test points on ncu compute units, and the
+ * columns per slab.  -1: bad arguments.  No device. */
+int gogp_test_pcov_slabs(int64_t npad, int64_t m, int ncu, int *cols_per_slab);
+
+/* launch_pcov with the number of compute units GIVEN: out (in / out; mo rows of ldo) = k(Z, Z) - Vt Vt^T (+ diag_add on the
+ * diagonal) on the leading m x m, identity up to mo.  Vt: m rows of ld (even) doubles, npad columns read; NULL: the prior
+ * Gram matrix (part may be NULL then).  part (in / out): gogp_test_pcov_slabs x pairs x 4096 doubles, pairs = t (t + 1) / 2,
+ * t = ceil(m / 64). */
+int gogp_test_pcov(int device, const gogp_test_kparams *kparams, int ev, const double *Z, int64_t z_len, int64_t m,
+                   const double *Vt, int64_t vt_len, int64_t ld, int64_t npad, int ncu, double *part, int64_t part_len,
+                   double diag_add, double *out, int64_t out_len, int64_t mo, int64_t ldo);
+
 /* Benchmark hook for the tile kernel: `reps` launches of one shape (mode 0 RECT
  * mt x nt tiles, 1 LOWER mt x mt, 2 LAUUM mt x mt with K = mt*128) on device
  * buffers; returns ms per launch and TFLOP/s on the flops launched. */

@@ -588,25 +588,31 @@ void gogp_oracle_grad_reduce_omp(const gogp_desc *d, const double *theta_s, cons
                                  const double *alpha, const double *Kinv, int64_t n,
                                  double *out) {
   int D = d->ndim, ns = d->ntheta_simil;
-  for (int p = 0; p <= ns; p++) out[p] = 0.0;
+  /* The sums cancel heavily on ill-conditioned problems (tests/golden/fp32_illcond_matern32.npz: the order in which
+   * double accumulators met the rows moved the scale component by 6e-10 relative from run to run, dynamic schedule).
+   * Long double accumulators put the order's effect 2^11 lower: the result no longer depends on the schedule or the
+   * number of threads beyond 1e-12. */
+  long double tot[GOGP_MAX_NDIM + 16];
+  for (int p = 0; p <= ns; p++) tot[p] = 0.0L;
 #pragma omp parallel
   {
-    double acc[GOGP_MAX_NDIM + 16];
+    long double acc[GOGP_MAX_NDIM + 16];
     double g[3 * GOGP_MAX_NDIM + 16];
-    for (int p = 0; p <= ns; p++) acc[p] = 0.0;
+    for (int p = 0; p <= ns; p++) acc[p] = 0.0L;
 #pragma omp for schedule(dynamic, 16)
     for (int64_t i = 0; i < n; i++) {
       for (int64_t j = 0; j <= i; j++) {
         double w = alpha[i] * alpha[j] - Kinv[i * n + j];
         double wgt = (j < i) ? 2.0 * w : w;
         gogp_oracle_simil(d, theta_s, X + i * D, X + j * D, g);
-        for (int p = 0; p < ns; p++) acc[p] += wgt * g[p] * theta_s[p];
+        for (int p = 0; p < ns; p++) acc[p] += (long double)wgt * g[p] * theta_s[p];
         if (i == j) acc[ns] += w;
       }
     }
 #pragma omp critical
-    for (int p = 0; p <= ns; p++) out[p] += (p < ns ? 0.5 : 1.0) * acc[p];
+    for (int p = 0; p <= ns; p++) tot[p] += (p < ns ? 0.5L : 1.0L) * acc[p];
   }
+  for (int p = 0; p <= ns; p++) out[p] = (double)tot[p];
 }
 
 /* gx (n x ndim) : gx[i][d] = sum_{j != i} W_ij dk(x_i, x_j)/dx_{i,d},  W = alpha alpha^T - Kinv
