@@ -81,6 +81,7 @@ type GP struct {
 	// tutorial/tutorial.go:114-115) is detected by comparing the slice headers below, and
 	// in-place edits of the same backing arrays must call Touch().
 	dirty      bool
+	nout       int // output columns of SetOutputs
 	upX        *[]float64 // &gp.X[0] at the time of the last upload
 	upY        *float64   // &gp.Y[0] at the time of the last upload
 	upN        int
@@ -423,6 +424,85 @@ func (gp *GP) LOOGradient() ([]float64, error) {
 		return nil, err
 	}
 	return g, nil
+}
+
+// SetOutputs gives the process T output columns (y row-major n x T, n =
+// len(gp.Y), T <= 128) observed at its inputs and sharing its kernel and
+// hyperparameters; they are evaluated on one factorisation (no reference
+// counterpart).  Pending X / Y are uploaded first.  T == 0 clears them; whatever
+// replaces or resizes the data drops them.
+func (gp *GP) SetOutputs(y []float64, T int) error {
+	gp.defaults()
+	if T == 0 {
+		gp.nout = 0
+		return gp.err(C.gogp_multi_set_outputs(gp.handle(), nil, 0, 0))
+	}
+	if err := gp.pushData(); err != nil {
+		return err
+	}
+	if T < 0 || len(y) != len(gp.Y)*T {
+		return fmt.Errorf("len(y)")
+	}
+	p := dptr(y)
+	var none C.double
+	if p == nil {
+		p = &none
+	}
+	if err := gp.err(C.gogp_multi_set_outputs(gp.handle(), p, C.int64_t(len(gp.Y)), C.int32_t(T))); err != nil {
+		return err
+	}
+	gp.nout = T
+	return nil
+}
+
+// MultiLML computes the log marginal likelihood of every output column of
+// SetOutputs at the current parameters, and their sum.
+func (gp *GP) MultiLML() (total float64, lml []float64, err error) {
+	gp.defaults()
+	lml = make([]float64, gp.nout)
+	var t C.double
+	if err = gp.err(C.gogp_multi_lml(gp.handle(), &t, dptr(lml))); err != nil {
+		return 0, nil, err
+	}
+	return float64(t), lml, nil
+}
+
+// MultiGradient computes the gradient of that sum with respect to the
+// log-transformed hyperparameters.
+func (gp *GP) MultiGradient() ([]float64, error) {
+	gp.defaults()
+	g := make([]float64, len(gp.ThetaSimil)+len(gp.ThetaNoise))
+	if err := gp.err(C.gogp_multi_gradient(gp.handle(), dptr(g), C.int64_t(len(g)))); err != nil {
+		return nil, err
+	}
+	return g, nil
+}
+
+// MultiAlpha returns A = K^-1 Y of the output columns, row-major n x T.
+func (gp *GP) MultiAlpha() ([]float64, error) {
+	gp.defaults()
+	n := int(C.gogp_n(gp.handle()))
+	a := make([]float64, n*gp.nout+1)
+	if err := gp.err(C.gogp_multi_get_alpha(gp.handle(), dptr(a))); err != nil {
+		return nil, err
+	}
+	return a[:n*gp.nout], nil
+}
+
+// MultiProduce computes the predictive means of every output column at the
+// test points (row-major len(x) x T) and the standard deviation they share.
+func (gp *GP) MultiProduce(x [][]float64) (mu, sigma []float64, err error) {
+	gp.defaults()
+	m := len(x)
+	flat := make([]float64, m*gp.NDim)
+	for i, row := range x {
+		copy(flat[i*gp.NDim:], row)
+	}
+	buf, sigma := make([]float64, m*gp.nout+1), make([]float64, m)
+	if err = gp.err(C.gogp_multi_produce(gp.handle(), dptr(flat), C.int64_t(m), dptr(buf), dptr(sigma))); err != nil {
+		return nil, nil, err
+	}
+	return buf[:m*gp.nout], sigma, nil
 }
 
 // Sample draws len(xi)/len(x) joint samples at the test points from the

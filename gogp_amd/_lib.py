@@ -20,6 +20,7 @@ GOGP_OK, GOGP_EARG, GOGP_ENOTPD, GOGP_EHIP, GOGP_ESTATE, GOGP_ENOMEM, GOGP_ECOND
 GOGP_MAX_CANDIDATES = 16
 GOGP_BATCH_MAX_N = 128
 GOGP_COV_MAX_M = 4096
+GOGP_MULTI_MAX_T = 128
 
 #: every symbol include/gogp_hip.h declares: (name, restype, argtypes)
 _dp = ctypes.POINTER(ctypes.c_double)
@@ -85,6 +86,11 @@ SYMBOLS = [
     ("gogp_gradient", ctypes.c_int, [_h, _dp, _i64]),
     ("gogp_loo", ctypes.c_int, [_h, _dp, _dp, _dp, _dp]),
     ("gogp_loo_gradient", ctypes.c_int, [_h, _dp, _i64]),
+    ("gogp_multi_set_outputs", ctypes.c_int, [_h, _dp, _i64, ctypes.c_int32]),
+    ("gogp_multi_lml", ctypes.c_int, [_h, _dp, _dp]),
+    ("gogp_multi_gradient", ctypes.c_int, [_h, _dp, _i64]),
+    ("gogp_multi_get_alpha", ctypes.c_int, [_h, _dp]),
+    ("gogp_multi_produce", ctypes.c_int, [_h, _dp, _i64, _dp, _dp]),
     ("gogp_observe_gradient_batch", ctypes.c_int,
      [ctypes.POINTER(_h), ctypes.c_int, _dp, _i64, _dp, _dp, ctypes.POINTER(ctypes.c_int)]),
     ("gogp_observe_gradient_candidates", ctypes.c_int,
@@ -208,6 +214,8 @@ HOOK_SYMBOLS = [
     ("gogp_test_pcov", ctypes.c_int,
      [ctypes.c_int, ctypes.POINTER(CKParams), ctypes.c_int, _dp, _i64, _i64, _dp, _i64, _i64, _i64, ctypes.c_int, _dp, _i64,
       ctypes.c_double, _dp, _i64, _i64, _i64]),
+    ("gogp_test_multi_weight", ctypes.c_int,
+     [ctypes.c_int, _dp, _i64, _i64, ctypes.c_int, _dp, _i64, _i64, _i64, _i64, _dp, _i64]),
     # per-rank replay of the sharded sweep (tools/sharded_replay.py): a transport that reads recorded panels
     ("gogp_test_dist_init_replay", ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int] * 4),
 ]

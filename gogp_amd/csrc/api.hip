@@ -106,6 +106,11 @@ static void free_n_buffers(gogp_handle *h) {
   h->rm_ws.release();
   h->loo_vec.release();
   h->loo_mat.release();
+  h->multi_vec.release();
+  h->multi_mean.release();
+  h->multi_mat.release();
+  h->multi_T = 0;
+  h->multi_solved = false;
   (void)hipFree(h->TX);
   (void)hipFree(h->Tmt);
   h->TX = h->Tmt = nullptr;
@@ -332,6 +337,7 @@ static int ensure_n(gogp_handle *h, int64_t n) {
   h->npad = npad;
   h->nblk = (int)(npad / TILE);
   h->factored = h->have_alpha = h->have_kinv = h->observed = h->grad_valid = false;
+  h->multi_solved = false;
   h->trtri_done = false;
   if (npad > h->cap_npad) {
     free_n_buffers(h);
@@ -368,6 +374,7 @@ static int set_data_impl(gogp_handle *h, const double *X, const double *y, int64
   int rc = h->dist ? gogp_dist_ensure_n(h, n) : ensure_n(h, n);
   if (rc != GOGP_OK) return rc;
   h->have_data = true;
+  h->multi_T = 0;  // the outputs of gogp_multi_set_outputs belonged to the data that was replaced
   if (n == 0) return GOGP_OK;
   // zero padding rows, then copy
   HIPCHK(h, hipMemsetAsync(h->dX, 0, ((size_t)h->npad * h->D + GOGP_MAX_NDIM) * sizeof(double), h->s));
@@ -410,6 +417,7 @@ extern "C" int gogp_set_events(gogp_handle *h, const double *events, int nevents
   for (int e = 0; e < nevents; ++e)
     for (int f = 0; f < 3; ++f) h->events[e][f] = events[3 * e + f];
   h->factored = h->have_alpha = h->have_kinv = h->observed = h->grad_valid = false;
+  h->multi_solved = false;
   h->trtri_done = h->trtri_pending = h->alpha_pending = h->kinv_pending = false;
   h->tinv_valid = h->tinv_pending = false;
   return GOGP_OK;
@@ -579,6 +587,7 @@ static int finish_factorize(gogp_handle *h, bool fp32, bool refine, bool kinv) {
     return GOGP_ENOTPD;
   }
   h->lml = fr.lml;
+  h->logdet2 = h->hscal[0];
   h->yta = fr.yta;
   h->factored = h->have_alpha = true;
   h->z_valid = true;
@@ -940,6 +949,7 @@ static void begin_evaluation(gogp_handle *h, std::initializer_list<hipStream_t> 
   if (h->kinv_c1 > 0 && !h->have_kinv) wait(EV_KINV);
   h->trtri_pending = h->kinv_pending = false;
   h->factored = h->have_alpha = h->have_kinv = h->grad_valid = false;
+  h->multi_solved = false;
   h->alpha_pending = h->trtri_done = h->ydone_valid = h->d64_active = false;
   h->notpd = -1;
   h->kinv_c1 = 0;
@@ -2240,18 +2250,13 @@ static int ensure_m(gogp_handle *h, int64_t m, int64_t mpad) {
 constexpr int PRODUCE_GROUPS = 4;
 // Produce's event slots, behind the factorisation's own
 static inline size_t produce_event_base(int64_t npad) { return EV_BASE + 4 * (size_t)(npad / PANEL) + 8; }
-// Kstar, mean and the blocked solve of Produce on matrices of element type T
+// The blocked solve of Produce on matrices of element type T, from the mpad right-hand-side rows that lie in KsT (Produce:
+// Kstar^T; gogp_multi_*: Y^T): V^T = R L^-T into Vt, row by row, and -- dq != nullptr -- |V_j|^2 of the first m rows
 template <class T>
-static void produce_solve_t(gogp_handle *h, hipStream_t s, int64_t m, int64_t mpad, double *dmu, double *dq) {
+static void produce_substitute_t(gogp_handle *h, hipStream_t s, int64_t m, int64_t mpad, double *dq) {
   const int64_t npad = h->npad, ld = npad;
   T *R = reinterpret_cast<T *>(h->KsT), *V = reinterpret_cast<T *>(h->Vt);
   const T *L = reinterpret_cast<const T *>(h->bufL), *Dinv = reinterpret_cast<const T *>(h->Dinv);
-  {
-    AuxTimer tm(h, GOGP_PROF_CROSS, s);
-    launch_cross(s, h->devP, h->D, h->dX, h->n, npad, h->dZ, m, mpad, R, ld, h->ev());  // gp/gp.go:322-332
-  }
-  // mean = Kstar^T alpha (gp/gp.go:335)
-  launch_rownorm_dot(s, R, ld, h->alpha, npad, m, dmu, nullptr);
   // V^T = Kstar^T L^-T by blocked substitution on the GEMM kernel
   // Produce launches are not part of the Observe+Gradient metric: they are event-timed only when the caller enabled
   // profiling around Produce itself (bench.py: the `produce.roofline` field)
@@ -2333,7 +2338,22 @@ static void produce_solve_t(gogp_handle *h, hipStream_t s, int64_t m, int64_t mp
   }
   for (int g = 1; g < ngroups; ++g) order(h, ev0 + PRODUCE_GROUPS + g, gs[g], s);
   // (Kstar^T K^-1 Kstar)_jj = |V_j|^2 : only the diagonal of gp/gp.go:341-342 is read (:356)
-  launch_rownorm_dot(s, V, ld, nullptr, npad, m, nullptr, dq);
+  if (dq) launch_rownorm_dot(s, V, ld, nullptr, npad, m, nullptr, dq);
+}
+// Kstar^T into KsT (zero rows from m on, zero columns from n on)
+template <class T>
+static void produce_cross_t(gogp_handle *h, hipStream_t s, int64_t m, int64_t mpad) {
+  AuxTimer tm(h, GOGP_PROF_CROSS, s);
+  launch_cross(s, h->devP, h->D, h->dX, h->n, h->npad, h->dZ, m, mpad, reinterpret_cast<T *>(h->KsT), h->npad,
+               h->ev());  // gp/gp.go:322-332
+}
+// Kstar, mean and the blocked solve of Produce on matrices of element type T
+template <class T>
+static void produce_solve_t(gogp_handle *h, hipStream_t s, int64_t m, int64_t mpad, double *dmu, double *dq) {
+  produce_cross_t<T>(h, s, m, mpad);
+  // mean = Kstar^T alpha (gp/gp.go:335)
+  launch_rownorm_dot(s, reinterpret_cast<const T *>(h->KsT), h->npad, h->alpha, h->npad, m, dmu, nullptr);
+  produce_substitute_t<T>(h, s, m, mpad, dq);
 }
 
 // Few test points (option "produce_small_max", default 64; fp64 matrices): Kstar, the mean, and V = L^-1 Kstar by the
@@ -2548,6 +2568,219 @@ extern "C" int gogp_produce_gradient(gogp_handle *h, const double *Z, int64_t m,
   HIPCHK(h, hipMemcpyAsync(sigma, pp.sigma, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
   HIPCHK(h, hipMemcpyAsync(dmu_out, ddmu, md * sizeof(double), hipMemcpyDeviceToHost, s));
   HIPCHK(h, hipMemcpyAsync(dsigma_out, ddsig, md * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipStreamSynchronize(s));
+  HIPCHK(h, hipGetLastError());
+  return GOGP_OK;
+}
+
+// ---- T output columns on one factorisation (multi.hip) ------------------------------------------------------------
+// No reference counterpart (gp.GP holds one output vector).  Y^T and the solutions A^T = (K^-1 Y)^T lie in multi_vec,
+// GOGP_MULTI_MAX_T rows of npad doubles each.  The solutions come from the factor -- Y^T into KsT, Produce's forward and
+// ProduceGradient's backward substitution -- on first need after a factorisation and are kept (multi_solved).  The calls
+// write workspaces of their own, Produce's (whose contents no call expects to find again) and, as gogp_gradient would,
+// K^-1: the handle's state afterwards is what a gogp_gradient at this point would have left.
+static double *multi_yt(const gogp_handle *h) { return h->multi_vec.as<double>(); }
+static double *multi_at(const gogp_handle *h) { return multi_yt(h) + (size_t)GOGP_MULTI_MAX_T * h->npad; }
+// NULL, or the kind of handle the multi-output calls refuse (LOO's refusals)
+static const char *multi_refusal(const gogp_handle *h) {
+  return h->prec == 32        ? "precision = 32 handles"
+         : mixed_gradient(h) ? "gradient_precision = 32 (a float K^-1)"
+         : h->dist           ? "sharded handles"
+                             : nullptr;
+}
+
+extern "C" int gogp_multi_set_outputs(gogp_handle *h, const double *Y, int64_t n, int32_t T) {
+  if (!h) return GOGP_EARG;
+  if (T == 0 && !Y) {  // clear
+    h->multi_T = 0;
+    h->multi_solved = false;
+    return GOGP_OK;
+  }
+  if (const char *refuse = multi_refusal(h)) {
+    char buf[160];
+    snprintf(buf, sizeof buf, "multi_set_outputs: %s are not supported", refuse);
+    return fail(h, GOGP_EARG, buf);
+  }
+  if (!h->have_data) return fail(h, GOGP_ESTATE, "multi_set_outputs: no data (gogp_set_data)");
+  if (!Y || n != h->n || T < 1 || T > GOGP_MULTI_MAX_T)
+    return fail(h, GOGP_EARG, "multi_set_outputs: need Y, n == gogp_n and 1 <= T <= GOGP_MULTI_MAX_T");
+  for (int64_t i = 0; i < n * T; ++i)
+    if (!std::isfinite(Y[i])) return fail(h, GOGP_EARG, "multi_set_outputs: non-finite output");
+  h->multi_solved = false;
+  if (n > 0) {
+    HIPCHK(h, hipSetDevice(h->device));
+    const int64_t npad = h->npad;
+    const size_t rows = (size_t)GOGP_MULTI_MAX_T * npad;
+    h->multi_T = 0;  // until the new ones are in place
+    const int rc = h->multi_vec.reserve(h, 2 * rows * sizeof(double));
+    if (rc != GOGP_OK) return rc;
+    std::vector<double> yt((size_t)T * npad, 0.0);
+    for (int64_t i = 0; i < n; ++i)
+      for (int t = 0; t < T; ++t) yt[(size_t)t * npad + i] = Y[i * T + t];
+    HIPCHK(h, hipMemsetAsync(multi_yt(h), 0, rows * sizeof(double), h->s));
+    HIPCHK(h, hipMemcpyAsync(multi_yt(h), yt.data(), yt.size() * sizeof(double), hipMemcpyHostToDevice, h->s));
+    HIPCHK(h, hipStreamSynchronize(h->s));
+  }
+  h->multi_T = T;
+  return GOGP_OK;
+}
+
+// A^T = (K^-1 Y)^T of the current factor into its buffer, on the main stream
+static int multi_solve(gogp_handle *h) {
+  if (h->multi_solved) return GOGP_OK;
+  const int T = h->multi_T;
+  int rc = ensure_alpha(h);  // the main stream behind the factorisation
+  if (rc == GOGP_OK) rc = ensure_m(h, T, TILE);
+  if (rc != GOGP_OK) return rc;
+  hipStream_t s = h->s;
+  const size_t row = (size_t)h->npad * sizeof(double);
+  static_assert(GOGP_MULTI_MAX_T == TILE, "the outputs are one tile row of right-hand sides");
+  HIPCHK(h, hipMemcpyAsync(h->KsT, multi_yt(h), TILE * row, hipMemcpyDeviceToDevice, s));
+  produce_substitute_t<double>(h, s, T, TILE, nullptr);  // V^T = Y^T L^-T into Vt
+  produce_backward(h, s, T);                             // A^T = V^T L^-1 into KsT
+  HIPCHK(h, hipMemcpyAsync(multi_at(h), h->KsT, (size_t)T * row, hipMemcpyDeviceToDevice, s));
+  if (T < TILE) HIPCHK(h, hipMemsetAsync(multi_at(h) + (size_t)T * h->npad, 0, (size_t)(TILE - T) * row, s));
+  h->multi_solved = true;
+  return GOGP_OK;
+}
+
+// The refusals and the state of the four calls that work on the outputs (under the name `who`), then -- with
+// observations -- the solutions in place on the main stream.  *empty: n == 0, nothing to launch.
+static int multi_prepare(gogp_handle *h, const char *who, bool *empty) {
+  char buf[160];
+  if (const char *refuse = multi_refusal(h)) {
+    snprintf(buf, sizeof buf, "%s: %s are not supported", who, refuse);
+    return fail(h, GOGP_EARG, buf);
+  }
+  if (h->multi_T == 0) {
+    snprintf(buf, sizeof buf, "%s: no outputs (gogp_multi_set_outputs)", who);
+    return fail(h, GOGP_ESTATE, buf);
+  }
+  *empty = h->n == 0;
+  if (*empty) return GOGP_OK;
+  if (!h->factored) {
+    snprintf(buf, sizeof buf, "%s: nothing absorbed", who);
+    return fail(h, GOGP_ESTATE, buf);
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  return multi_solve(h);
+}
+
+extern "C" int gogp_multi_lml(gogp_handle *h, double *total, double *lml) {
+  if (!h || !total) return fail(h, GOGP_EARG, "multi_lml: NULL");
+  bool empty = false;
+  int rc = multi_prepare(h, "multi_lml", &empty);
+  if (rc != GOGP_OK) return rc;
+  const int T = h->multi_T;
+  *total = 0.0;
+  if (empty) {
+    for (int t = 0; lml && t < T; ++t) lml[t] = 0.0;
+    return GOGP_OK;
+  }
+  rc = h->multi_mean.reserve(h, GOGP_MULTI_MAX_T * sizeof(double));
+  if (rc != GOGP_OK) return rc;
+  hipStream_t s = h->s;
+  double dots[GOGP_MULTI_MAX_T];
+  launch_multi_dots(s, multi_yt(h), multi_at(h), h->npad, h->n, T, h->multi_mean.as<double>());
+  HIPCHK(h, hipMemcpyAsync(dots, h->multi_mean.p, (size_t)T * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipStreamSynchronize(s));
+  HIPCHK(h, hipGetLastError());
+  double sum = 0.0;
+  for (int t = 0; t < T; ++t) {  // as judge_scalars, with y_t^T alpha_t for the quadratic term; summed in column order
+    const double l = -0.5 * (double)h->n * log(2 * M_PI) - 0.5 * h->logdet2 - 0.5 * dots[t];
+    if (lml) lml[t] = l;
+    sum += l;
+  }
+  *total = sum;
+  return GOGP_OK;
+}
+
+extern "C" int gogp_multi_gradient(gogp_handle *h, double *grad, int64_t len) {
+  if (!h || !grad) return fail(h, GOGP_EARG, "multi_gradient: NULL");
+  if (len != h->P) return fail(h, GOGP_EARG, "multi_gradient: wrong length");
+  bool empty = false;
+  int rc = multi_prepare(h, "multi_gradient", &empty);
+  if (rc != GOGP_OK) return rc;
+  for (int64_t i = 0; i < len; ++i) grad[i] = 0.0;
+  if (empty) return GOGP_OK;
+  rc = compute_kinv(h);
+  if (rc != GOGP_OK) return rc;
+  hipStream_t s = h->s;
+  const int64_t npad = h->npad, ld = npad;
+  const size_t mat = (size_t)npad * (size_t)npad;
+  rc = h->multi_mat.reserve(h, (mat + (size_t)npad) * sizeof(double));
+  if (rc != GOGP_OK) return rc;
+  double *G = h->multi_mat.as<double>(), *zero = G + mat;
+  // G = T K^-1 - A A^T on the lower tiles
+  launch_multi_weight(s, multi_at(h), npad, h->multi_T, h->bufA, ld, h->n, npad, G);
+  // sum_ab (0 0^T - G)_ab dK_ab per slot: the reduction of the LML gradient with G for K^-1 and zeros for alpha
+  HIPCHK(h, hipMemsetAsync(zero, 0, (size_t)npad * sizeof(double), s));
+  {
+    AuxTimer tm(h, GOGP_PROF_GRAD, s);
+    launch_grad_reduce(s, h->devP, h->D, h->ard_dims, h->dX, zero, (const double *)G, ld, h->n, npad, h->gpart, h->gout,
+                       h->radial1, h->ard_mfma_min, h->ev());
+  }
+  double acc[NACC];
+  HIPCHK(h, hipMemcpyAsync(acc, h->gout, sizeof acc, hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipStreamSynchronize(s));
+  HIPCHK(h, hipGetLastError());
+  assemble_gradient(h, acc, h->hostP->dnoise, grad);
+  return GOGP_OK;
+}
+
+extern "C" int gogp_multi_get_alpha(gogp_handle *h, double *A) {
+  if (!h || !A) return fail(h, GOGP_EARG, "multi_get_alpha: NULL");
+  bool empty = false;
+  const int rc = multi_prepare(h, "multi_get_alpha", &empty);
+  if (rc != GOGP_OK || empty) return rc;
+  const int T = h->multi_T;
+  const int64_t n = h->n, npad = h->npad;
+  std::vector<double> at((size_t)T * npad);
+  HIPCHK(h, hipMemcpyAsync(at.data(), multi_at(h), at.size() * sizeof(double), hipMemcpyDeviceToHost, h->s));
+  HIPCHK(h, hipStreamSynchronize(h->s));
+  HIPCHK(h, hipGetLastError());
+  for (int64_t i = 0; i < n; ++i)
+    for (int t = 0; t < T; ++t) A[i * T + t] = at[(size_t)t * npad + i];
+  return GOGP_OK;
+}
+
+extern "C" int gogp_multi_produce(gogp_handle *h, const double *Z, int64_t m, double *mu, double *sigma) {
+  if (!h || m < 0 || (m > 0 && (!Z || !mu))) return fail(h, GOGP_EARG, "multi_produce: NULL");
+  bool empty = false;
+  int rc = multi_prepare(h, "multi_produce", &empty);
+  if (rc != GOGP_OK) return rc;
+  ProducePlan pp;
+  rc = produce_prepare(h, "multi_produce", "multi_produce", m, false, &pp);
+  if (rc != GOGP_OK || m == 0) return rc;
+  const int T = h->multi_T;
+  hipStream_t s = h->s;
+  rc = produce_forward(h, Z, m, pp, true, false);  // Z up, the prior, the main stream behind alpha
+  if (rc != GOGP_OK) return rc;
+  if (empty) {  // no observations (gp/gp.go:343-347): sigma = sqrt(prior), mu = 0
+    launch_sigma(s, pp.prior, nullptr, m, pp.sigma);
+    if (sigma) HIPCHK(h, hipMemcpyAsync(sigma, pp.sigma, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    HIPCHK(h, hipGetLastError());
+    for (int64_t j = 0; j < m * T; ++j) mu[j] = 0.0;
+    return GOGP_OK;
+  }
+  rc = h->multi_mean.reserve(h, (size_t)pp.mpad * GOGP_MULTI_MAX_T * sizeof(double));
+  if (rc != GOGP_OK) return rc;
+  // always the tile route of Produce, whatever m (as gogp_produce_gradient): Kstar^T row by row in KsT
+  produce_cross_t<double>(h, s, m, pp.mpad);
+  // the means, Kstar^T A, in one launch of the tile kernel -- before the substitution uses up Kstar^T
+  GemmGrid gm;
+  gm.small_below = h->produce_small_below;
+  launch_gemm_nt(s, GEMM_RECT, (int)(pp.mpad / TILE), 1, h->npad, 1.0, (const double *)h->KsT, h->npad,
+                 (const double *)multi_at(h), h->npad, 0.0, h->multi_mean.as<double>(), (int64_t)GOGP_MULTI_MAX_T,
+                 h->prof.on ? &h->prof : nullptr, &gm);
+  if (sigma) {
+    produce_substitute_t<double>(h, s, m, pp.mpad, pp.q);
+    launch_sigma(s, pp.prior, pp.q, m, pp.sigma);
+    HIPCHK(h, hipMemcpyAsync(sigma, pp.sigma, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
+  }
+  HIPCHK(h, hipMemcpy2DAsync(mu, (size_t)T * sizeof(double), h->multi_mean.p, (size_t)GOGP_MULTI_MAX_T * sizeof(double),
+                             (size_t)T * sizeof(double), (size_t)m, hipMemcpyDeviceToHost, s));
   HIPCHK(h, hipStreamSynchronize(s));
   HIPCHK(h, hipGetLastError());
   return GOGP_OK;
@@ -2768,6 +3001,7 @@ extern "C" int gogp_set_factor(gogp_handle *h, const double *theta_simil,
   h->tinv_valid = false;  // Produce on a restored factor substitutes panel by panel
   h->z_valid = false;     // no z = L^-1 y comes with a restored factor (gogp_append recomputes it)
   h->kinv_c1 = 0;         // ... and no partial K^-1 of an earlier sweep belongs to it (compute_kinv: gogp_loo)
+  h->multi_solved = false;  // ... nor do the solutions of gogp_multi_*
   if (h->n == 0) return GOGP_OK;
   if (h->dist) return gogp_dist_set_factor(h, Lin, alpha);  // collective: every rank keeps its own tiles
   rc = gogp_upload_params(h);
@@ -2807,6 +3041,7 @@ extern "C" int gogp_set_factor(gogp_handle *h, const double *theta_simil,
   HIPCHK(h, hipMemcpyAsync(h->hscal, h->scalars, 3 * sizeof(double), hipMemcpyDeviceToHost, s));
   HIPCHK(h, hipStreamSynchronize(s));
   h->lml = -0.5 * (double)n * log(2 * M_PI) - 0.5 * h->hscal[0] - 0.5 * h->hscal[2];
+  h->logdet2 = h->hscal[0];
   return GOGP_OK;
 }
 
@@ -2839,6 +3074,8 @@ static int begin_factor_update(gogp_handle *h) {
   h->tinv_valid = h->tinv_pending = false;
   h->ydone_valid = false;
   h->kinv_c1 = 0;
+  h->multi_T = 0;  // the outputs of gogp_multi_set_outputs belong to the rows as they were
+  h->multi_solved = false;
   return GOGP_OK;
 }
 // ... and end with, on the main stream s behind z of the n1 rows: alpha = L^-T z over the whole new factor L (leading
@@ -2860,6 +3097,7 @@ static int finish_factor_update(gogp_handle *h, const double *L, int64_t ld, int
   memcpy(h->hscal + HS_INFO, &zero, sizeof zero);
   const FactorResult fr = judge_scalars(h, h->hscal, false, true);
   h->lml = fr.lml;
+  h->logdet2 = h->hscal[0];
   h->yta = fr.yta;
   h->cond_lb = fr.cond_lb;
   h->notpd = -1;
@@ -3332,6 +3570,8 @@ extern "C" int gogp_set_option(gogp_handle *h, const char *name, int64_t value) 
       free_cand_buffers(h);  // the candidates' arena slots are laid out for the matrices' element type
       h->prec = (int)value;
       h->have_data = h->factored = h->have_alpha = h->have_kinv = h->observed = h->grad_valid = false;
+      h->multi_T = 0;  // (free_n_buffers dropped the outputs of gogp_multi_set_outputs; said here too)
+      h->multi_solved = false;
       h->trtri_done = h->trtri_pending = h->alpha_pending = h->kinv_pending = false;
     }
     return GOGP_OK;

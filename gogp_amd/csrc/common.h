@@ -434,6 +434,13 @@ void launch_loo_stats(hipStream_t s, const double *Kinv, int64_t ld, const doubl
 void launch_loo_scale_symv(hipStream_t s, const double *Kinv, int64_t ld, int64_t n, int64_t npad, const double *sc,
                            const double *v, double *B, int64_t ldb, double *upart, double *u);
 void launch_loo_rank2(hipStream_t s, double *G, int64_t ld, int64_t n, int64_t npad, const double *u, const double *alpha);
+// multi.hip (gogp_multi_*): T output columns on one factorisation.  At / Yt: one output per row of ld >= npad doubles.
+// launch_multi_weight: G (ldk, as Kinv) = T Kinv - A A^T on the elements j <= i < n of the lower 64-tiles of npad, exact
+// zeros on the rest of those tiles, nothing outside them; At must hold T rounded up to a multiple of 4 rows, the rows
+// from T on zero; of Kinv only j <= i < n is read.  launch_multi_dots: dots[t] = sum_{i < n} Yt[t][i] At[t][i], t < T.
+void launch_multi_weight(hipStream_t s, const double *At, int64_t ld, int T, const double *Kinv, int64_t ldk, int64_t n,
+                         int64_t npad, double *G);
+void launch_multi_dots(hipStream_t s, const double *Yt, const double *At, int64_t ld, int64_t n, int T, double *dots);
 void launch_fill(hipStream_t s, double *p, int64_t count, double v);
 void launch_axpy(hipStream_t s, double *a, const double *b, int64_t count);  // a += b
 void launch_dot(hipStream_t s, const double *a, const double *b, int64_t n, double *out);  // out[0] = a.b

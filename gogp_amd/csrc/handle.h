@@ -68,7 +68,8 @@ struct EvalState {
   bool grad_valid = false;
   bool trtri_done = false;  // Y = L^-T of the current factor is (being) computed
   double lml = 0.0;
-  double cond_lb = 1.0;     // (max L_ii / min L_ii)^2 of the last factorisation
+  double logdet2 = 0.0;     // 2 sum_i log L_ii of the factor `lml` belongs to (fp64 handles; gogp_multi_lml)
+  double cond_lb = 1.0;    // (max L_ii / min L_ii)^2 of the last factorisation
   int64_t notpd = -1;
 };
 
@@ -217,6 +218,12 @@ struct gogp_handle : EvalBufs, EvalState {
   Workspace rm_ws;          // gogp_remove: index maps, a pass's columns of W, the diagonal-block snapshot, compacted X / y (remove.hip)
   Workspace loo_vec;        // gogp_loo / gogp_loo_gradient: mu, sigma, log p, v, s, u, a zero vector and the block sums (loo.hip)
   Workspace loo_mat;        // gogp_loo_gradient: B = K^-1 diag(s) and G = B B^T - u alpha^T - alpha u^T, npad x npad each
+  // T output columns on the handle's factorisation (gogp_multi_*, multi.hip); all released with the N buffers
+  int multi_T = 0;             // outputs set (gogp_multi_set_outputs) for the current data; 0: none
+  bool multi_solved = false;   // A = K^-1 Y of the current factor is in multi_vec: cleared wherever have_alpha is
+  Workspace multi_vec;      // Y^T, then A^T: GOGP_MULTI_MAX_T rows of npad doubles each, zero from column n and from row T on
+  Workspace multi_mean;     // gogp_multi_produce: Kstar^T A, mpad x GOGP_MULTI_MAX_T; gogp_multi_lml: the T dots
+  Workspace multi_mat;      // gogp_multi_gradient: G = T K^-1 - A A^T and a zero vector, (npad + 1) x npad
   double yta = 0.0;      // y^T alpha of the last factorisation (fp32 path: of the refined alpha)
   int trace_fp64 = 1;    // fp32 path: tr(alpha alpha^T - K^-1) summed in fp64 from Y, scale component by its identity
   double cond_limit = 1e16;  // gonum's mat.ConditionTolerance

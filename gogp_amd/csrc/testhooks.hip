@@ -1347,3 +1347,33 @@ extern "C" int gogp_test_pcov(int device, const gogp_test_kparams *kparams, int 
   if (e == hipSuccess) e = dout.down(out);
   return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
 }
+
+// ---- multi_weight_kernel (multi.hip) through its product launcher (tests/test_multi_output_gpu.py).  The rules of the
+// hooks above; the product keeps A^T with zero rows up to a multiple of 4, so the hook appends them to its device copy.
+extern "C" int gogp_test_multi_weight(int device, const double *At, int64_t at_len, int64_t ld, int T, const double *Kinv,
+                                      int64_t kinv_len, int64_t ldk, int64_t n, int64_t npad, double *G, int64_t g_len) {
+  if (!At || !Kinv || !G || T < 1 || T > GOGP_MULTI_MAX_T) return GOGP_EARG;
+  if (npad <= 0 || npad % PANEL || npad > UP_NPAD_MAX || n < 1 || n > npad) return GOGP_EARG;
+  if (!covers(at_len, 0, ld, T, npad, 1, 0) || !covers(kinv_len, 0, ldk, npad, npad, 1, 0) ||
+      !covers(g_len, 0, ldk, npad, npad, 1, 0))
+    return GOGP_EARG;
+  if (!device_ok(device)) return GOGP_EHIP;
+  const int T4 = (T + 3) / 4 * 4;
+  const size_t at_bytes = (size_t)std::max<int64_t>(at_len, (int64_t)T4 * ld) * sizeof(double);
+  DevCopy dK, dG;
+  double *dA = nullptr;
+  hipError_t e = hipMalloc(&dA, at_bytes);
+  if (e == hipSuccess) e = hipMemset(dA, 0, at_bytes);
+  // (the rows of the caller's array: T of them, the last one possibly shorter than ld)
+  if (e == hipSuccess)
+    e = hipMemcpy(dA, At, (size_t)std::min<int64_t>(at_len, (int64_t)T * ld) * sizeof(double), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = dK.up(Kinv, (size_t)kinv_len * sizeof(double));
+  if (e == hipSuccess) e = dG.up(G, (size_t)g_len * sizeof(double));
+  if (e == hipSuccess) {
+    launch_multi_weight(0, dA, ld, T, dK.as<double>(), ldk, n, npad, dG.as<double>());
+    e = launched();
+  }
+  if (e == hipSuccess) e = dG.down(G);
+  (void)hipFree(dA);
+  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+}

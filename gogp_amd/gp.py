@@ -382,6 +382,63 @@ class GP:
         self._check(_lib.lib().gogp_loo_gradient(self._h, _dp(g), g.size))
         return g
 
+    # ---- multi-output: T output columns on one factorisation (no reference counterpart) ----
+    def SetOutputs(self, Y) -> None:
+        """T output columns observed at the process's inputs, sharing its kernel and hyperparameters (n x T,
+        T <= 128; gogp_multi_set_outputs).  Independent of ``Y``, which stays the process's own output vector.  The
+        outputs belong to the data on the device: Absorb, the full Observe form, Append, Remove and assigning X / Y
+        drop them.  ``None`` clears them.  fp64, unsharded handles only."""
+        L = _lib.lib()
+        if Y is None:
+            self._check(L.gogp_multi_set_outputs(self._h, None, 0, 0))
+            self._T = 0
+            return
+        self._push_data()
+        ya = _arr(Y)
+        n = len(self._Y)
+        if ya.ndim == 1:
+            ya = ya.reshape(n, -1) if n else ya.reshape(0, ya.size)
+        if ya.ndim != 2:
+            raise ValueError("SetOutputs: Y must be n x T")
+        ya = np.ascontiguousarray(ya)
+        buf = ya if ya.size else np.zeros(1)  # (no observations: a pointer the library may look at)
+        self._check(L.gogp_multi_set_outputs(self._h, _dp(buf), ya.shape[0], ya.shape[1]))
+        self._T = ya.shape[1]
+
+    def MultiLML(self):
+        """(total, per_output): the log marginal likelihood of every output column at the parameters of the last
+        Absorb / Observe / restore, and their sum in column order (gogp_multi_lml)."""
+        T = getattr(self, "_T", 0)
+        total, per = ctypes.c_double(0.0), np.zeros(max(T, 1))
+        self._check(_lib.lib().gogp_multi_lml(self._h, ctypes.byref(total), _dp(per)))
+        return total.value, per[:T]
+
+    def MultiGradient(self) -> np.ndarray:
+        """d (sum of the outputs' LML) / d log theta, one entry per hyperparameter (gogp_multi_gradient): one pass
+        over K^-1 for all outputs and all parameters."""
+        g = np.zeros(self._ns + self._nn)
+        self._check(_lib.lib().gogp_multi_gradient(self._h, _dp(g), g.size))
+        return g
+
+    @property
+    def MultiAlpha(self) -> np.ndarray:
+        """A = K^-1 Y, n x T (gogp_multi_get_alpha)."""
+        T = getattr(self, "_T", 0)
+        a = np.zeros((int(_lib.lib().gogp_n(self._h)), T))
+        buf = a if a.size else np.zeros(1)
+        self._check(_lib.lib().gogp_multi_get_alpha(self._h, _dp(buf)))
+        return a
+
+    def MultiProduce(self, x):
+        """(mu, sigma): the predictive means of every output at the test points, m x T, and the standard deviation
+        they share, m entries, as Produce returns it (gogp_multi_produce)."""
+        z = _arr(x).reshape(-1, self.NDim)
+        m, T = len(z), getattr(self, "_T", 0)
+        mu, sigma = np.zeros((m, T)), np.zeros(m)
+        buf = mu if mu.size else np.zeros(1)
+        self._check(_lib.lib().gogp_multi_produce(self._h, _dp(z) if m else None, m, _dp(buf), _dp(sigma) if m else None))
+        return mu, sigma
+
     # ---- cached computations: gp.GP.L, gp.GP.Alpha (gp/gp.go:34-37) ----------------------
     @property
     def Alpha(self) -> np.ndarray:
@@ -684,6 +741,35 @@ class LOOModel:
 
     def Gradient(self) -> np.ndarray:
         g = self.gp.LOOGradient()
+        if self.Priors is not None:
+            self.Priors.Observe(self._x)
+            pg = np.asarray(self.Priors.Gradient(), dtype=float)
+            g[:len(pg)] += pg
+        return g
+
+
+class MultiModel:
+    """Model with the sum of the LML of the T output columns of GP.SetOutputs in the place of the LML: Observe(x) runs
+    gp.Observe(x) and returns GP.MultiLML()'s total (+ the log prior, counted once), Gradient() returns
+    GP.MultiGradient() (+ the prior's).  optimize.lbfgs and optimize.Adam.Step then fit the shared hyperparameters
+    (x = log theta, no observations in x) to all outputs at the price of one factorisation per evaluation.  As with
+    LOOModel the batched line search is not offered: the GP is ``gp`` here, not ``GP``."""
+
+    def __init__(self, gp: GP, Priors=None):
+        self.gp = gp
+        self.Priors = Priors
+        self._x = None
+
+    def Observe(self, x) -> float:
+        self._x = _arr(x).reshape(-1).copy()
+        if self._x.size != self.gp._ns + self.gp._nn:
+            raise ValueError("len(x): the multi-output objective takes the hyperparameters only")
+        self.gp.Observe(self._x)
+        v = self.gp.MultiLML()[0]
+        return v + self.Priors.Observe(self._x) if self.Priors is not None else v
+
+    def Gradient(self) -> np.ndarray:
+        g = self.gp.MultiGradient()
         if self.Priors is not None:
             self.Priors.Observe(self._x)
             pg = np.asarray(self.Priors.Gradient(), dtype=float)
@@ -1162,3 +1248,16 @@ def pcov_check(kp, Z: np.ndarray, m: int, Vt, ld: int, npad: int, ncu: int, part
     if rc != _lib.GOGP_OK:
         raise GogpError(rc, "test_pcov")
     return part, out
+
+
+def multi_weight_check(At: np.ndarray, ld: int, T: int, Kinv: np.ndarray, ldk: int, n: int, npad: int, G: np.ndarray,
+                       device: int = -1) -> np.ndarray:
+    """launch_multi_weight (test hook gogp_test_multi_weight): G = T Kinv - A A^T on the elements j <= i < n of the lower
+    64 x 64 tiles, zeros on the rest of them; At holds one column of A per row of ld.  Returns a copy of G after the
+    launch."""
+    At, Kinv, G = _vec(At, "At"), _vec(Kinv, "Kinv"), _vec(G, "G").copy()
+    rc = _lib.hooks().gogp_test_multi_weight(device, _dp(At), At.size, ld, T, _dp(Kinv), Kinv.size, ldk, n, npad, _dp(G),
+                                            G.size)
+    if rc != _lib.GOGP_OK:
+        raise GogpError(rc, "test_multi_weight")
+    return G

@@ -184,6 +184,51 @@ class GP {
     return g;
   }
 
+  // Multi-output (gogp_multi_*): T output columns observed at the inputs X, sharing the kernel and the hyperparameters,
+  // on one factorisation; no reference counterpart.  SetOutputs: Yt row-major n x T, n = Y.size(), T <= GOGP_MULTI_MAX_T
+  // (pending X / Y are uploaded first; T == 0 clears); the outputs are dropped by whatever replaces or resizes the data.
+  void SetOutputs(const std::vector<double> &Yt, int T) {
+    if (T == 0) {
+      check(gogp_multi_set_outputs(h_, nullptr, 0, 0));
+      T_ = 0;
+      return;
+    }
+    check(push());
+    if (T < 0 || Yt.size() != Y.size() * (size_t)T) throw Error(GOGP_EARG, "len(Yt)");
+    const double none = 0.0;
+    check(gogp_multi_set_outputs(h_, Yt.empty() ? &none : Yt.data(), (int64_t)Y.size(), T));
+    T_ = T;
+  }
+  // the sum of the outputs' LML; lml: one entry per output
+  double MultiLML(std::vector<double> &lml) {
+    lml.assign((size_t)T_, 0.0);
+    double total = 0.0;
+    check(gogp_multi_lml(h_, &total, lml.empty() ? nullptr : lml.data()));
+    return total;
+  }
+  // d (that sum) / d log theta, one entry per hyperparameter
+  std::vector<double> MultiGradient() {
+    std::vector<double> g(ThetaSimil.size() + ThetaNoise.size(), 0.0);
+    check(gogp_multi_gradient(h_, g.data(), (int64_t)g.size()));
+    return g;
+  }
+  // A = K^-1 Yt, row-major n x T
+  std::vector<double> MultiAlpha() {
+    std::vector<double> a((size_t)gogp_n(h_) * (size_t)T_ + 1, 0.0);
+    check(gogp_multi_get_alpha(h_, a.data()));
+    a.pop_back();
+    return a;
+  }
+  // mu row-major x.size() x T, sigma (shared by the outputs) x.size()
+  bool MultiProduce(const std::vector<std::vector<double>> &x, std::vector<double> &mu, std::vector<double> &sigma) {
+    std::vector<double> flat = pack(x);
+    mu.assign(x.size() * (size_t)T_, 0.0);
+    sigma.assign(x.size(), 0.0);
+    const double none = 0.0;
+    return gogp_multi_produce(h_, flat.data(), (int64_t)x.size(), mu.empty() ? const_cast<double *>(&none) : mu.data(),
+                              sigma.data()) == GOGP_OK;
+  }
+
   // ns = xi.size() / x.size() joint draws mu + C xi[s] (row-major ns x x.size()) from the caller's standard normals,
   // C the lower Cholesky factor of the covariance + diag_add I; no reference counterpart
   bool Sample(const std::vector<std::vector<double>> &x, const std::vector<double> &xi, double diag_add,
@@ -285,6 +330,7 @@ class GP {
   gogp_handle *h_ = nullptr;
   size_t last_len_ = 0;
   bool dirty_ = true;
+  int T_ = 0;  // output columns of SetOutputs
 
   std::vector<double> pack(const std::vector<std::vector<double>> &x) const {
     std::vector<double> flat(x.size() * (size_t)NDim);

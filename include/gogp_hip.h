@@ -225,6 +225,50 @@ int gogp_gradient(gogp_handle *h, double *grad, int64_t len);
 int gogp_loo(gogp_handle *h, double *mu, double *sigma, double *logp, double *total);
 int gogp_loo_gradient(gogp_handle *h, double *grad, int64_t len);
 
+/* Multi-output: T output columns Y = [y_1 .. y_T] observed at the handle's inputs, sharing its kernel and
+ * hyperparameters, on ONE factorisation; no reference counterpart (gp.GP holds one output vector).  The columns are
+ * independent: no cross-output covariance, no per-output theta.  With A = K^-1 Y
+ *     lml_t = -1/2 y_t^T a_t - sum_i log L_ii - n/2 log 2 pi,   total = sum_t lml_t (in column order),
+ *     d total / d log theta = 1/2 sum_ab (A A^T - T K^-1)_ab dK_ab,   mu[j][t] = sum_i k(z_j, x_i) A[i][t].
+ * gogp_multi_set_outputs copies Y (n x T row-major, n == gogp_n(h), 1 <= T <= GOGP_MULTI_MAX_T) to the device; it needs
+ * data but no factorisation and does not touch the handle's own y, alpha, LML, factor or K^-1.  T == 0 with Y == NULL
+ * clears the outputs.  They are dropped by whatever replaces or resizes the data -- gogp_set_data[_device],
+ * gogp_observe_full, gogp_append, gogp_remove, a change of option "precision" -- and the other calls then return
+ * GOGP_ESTATE until outputs are set again.
+ * The other four calls work at the parameters of the last gogp_absorb / gogp_observe[_full] / gogp_set_factor, in every
+ * state in which gogp_loo works.  A comes from the factor (Produce's forward and gogp_produce_gradient's backward
+ * substitution with Y^T as the right-hand sides, so lml has the accuracy of gogp_lml), is solved on first need after a
+ * factorisation and kept.  gogp_multi_lml: total, and lml (T doubles) unless NULL.  gogp_multi_gradient: d total /
+ * d log theta, `len` == P whichever Observe form ran last; K^-1 is formed as gogp_gradient forms it where it is not
+ * there, one pass writes G = T K^-1 - A A^T and the kernels of gogp_gradient reduce it, so every kernel family, ARD and
+ * the event discounts are covered.  gogp_multi_get_alpha: A, n x T row-major.  gogp_multi_produce: mu (m x T
+ * row-major) and sigma (m doubles, shared by the outputs: as gogp_produce returns it, no noise, unclamped; may be NULL,
+ * which saves the substitution); m == 0 is OK.
+ * The handle is left as it was found: a gogp_gradient, gogp_produce, gogp_get_factor, gogp_loo or gogp_append made
+ * afterwards returns the bits it would have returned without these calls.  Two identical calls return identical bits
+ * (fixed-order sums, no atomics).  n == 0: total, lml and the gradient are zeros, mu zeros and sigma = sqrt(prior).
+ * GOGP_ESTATE before outputs are set and before anything is factored; GOGP_EARG for NULL pointers, n != gogp_n(h), T
+ * outside 1 .. GOGP_MULTI_MAX_T, a non-finite output, len != P, a precision = 32 handle, "gradient_precision" = 32 (a
+ * float K^-1) and a sharded handle (the restrictions of gogp_loo).
+ * Device memory: Y^T and A^T, 128 rows of npad doubles each (33 MB at n = 16384), a tile row of Produce's workspace,
+ * mpad x 128 doubles for the means; gogp_multi_gradient also one npad x npad fp64 matrix (2.1 GB at n = 16384),
+ * allocated on first use; all kept until the data's buffers are released.
+ * Cost, measured on one MI355X (profiles/multi_output.txt; D = 8, T = 1 / 8 / 128, beside Observe + Gradient on the same
+ * build, every call ending in a synchronise): at n = 16384 the first gogp_multi_lml behind a factorisation -- the two
+ * substitutions and the dots -- 3.8 / 3.8 / 4.9 ms, again 0.04 - 0.08 ms; gogp_multi_gradient with K^-1 in place 1.13 /
+ * 1.13 / 2.17 ms; gogp_multi_produce at m = 256 3.3 / 3.3 / 3.6 ms; a whole evaluation Observe + multi_lml +
+ * multi_gradient 80.5 / 80.1 / 82.9 ms against 71.7 ms for ONE Observe + Gradient, i.e. 1.12 / 0.14 / 0.009 of T separate
+ * evaluations (n = 4096: 4.3 / 4.3 / 4.7 against 3.2 ms, 1.34 / 0.18 / 0.011; n = 1024: 0.89 / 0.95 / 0.95 against
+ * 0.69 ms, 1.30 / 0.18 / 0.011).  For ONE output the calls lose to gogp_observe + gogp_gradient at every size: use those.
+ * gogp_multi_set_outputs and gogp_multi_get_alpha transpose on the host: 30.9 and 11.1 ms at n = 16384, T = 128
+ * (0.29 and 0.17 ms at T = 8). */
+#define GOGP_MULTI_MAX_T 128 /* one 128-tile of right-hand-side rows */
+int gogp_multi_set_outputs(gogp_handle *h, const double *Y /* n x T row-major */, int64_t n, int32_t T);
+int gogp_multi_lml(gogp_handle *h, double *total, double *lml /* T, may be NULL */);
+int gogp_multi_gradient(gogp_handle *h, double *grad, int64_t len /* P */);
+int gogp_multi_get_alpha(gogp_handle *h, double *A /* n x T row-major */);
+int gogp_multi_produce(gogp_handle *h, const double *Z, int64_t m, double *mu /* m x T */, double *sigma /* m */);
+
 /* k independent Observe + Gradient evaluations at once: handle hs[i] (each created and given
  * its data separately; they may hold the same data) evaluates x[i*len .. (i+1)*len) from its own
  * host thread, so the dependent launch chains of the k evaluations overlap on the GPU.

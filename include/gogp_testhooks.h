@@ -241,6 +241,13 @@ int gogp_test_pcov(int device, const gogp_test_kparams *kparams, int ev, const d
                    const double *Vt, int64_t vt_len, int64_t ld, int64_t npad, int ncu, double *part, int64_t part_len,
                    double diag_add, double *out, int64_t out_len, int64_t mo, int64_t ldo);
 
+/* launch_multi_weight (multi.hip): G (in / out; npad rows of ldk, as Kinv) = T Kinv - A A^T on the elements j <= i < n of the
+ * lower 64 x 64 tiles of npad, exact zeros on the rest of those tiles, nothing outside them.  At: T (1 .. GOGP_MULTI_MAX_T)
+ * rows of ld doubles, npad columns read, row t = column t of A; the hook appends the zero rows up to a multiple of 4 that the
+ * product keeps.  Of Kinv only j <= i < n is read.  npad a multiple of 256, 1 <= n <= npad. */
+int gogp_test_multi_weight(int device, const double *At, int64_t at_len, int64_t ld, int T, const double *Kinv,
+                           int64_t kinv_len, int64_t ldk, int64_t n, int64_t npad, double *G, int64_t g_len);
+
 /* Benchmark hook for the tile kernel: `reps` launches of one shape (mode 0 RECT
  * mt x nt tiles, 1 LOWER mt x mt, 2 LAUUM mt x mt with K = mt*128) on device
  * buffers; returns ms per launch and TFLOP/s on the flops launched. */
