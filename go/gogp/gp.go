@@ -505,6 +505,60 @@ func (gp *GP) MultiProduce(x [][]float64) (mu, sigma []float64, err error) {
 	return buf[:m*gp.nout], sigma, nil
 }
 
+// SetSparse gives the process the data of the inducing-point approximation
+// (no reference counterpart): N observations x (row-major N x NDim), y and M <=
+// 4096 inducing points u (row-major M x NDim), kept on the device beside X / Y,
+// which they do not touch.  An empty u clears them.
+func (gp *GP) SetSparse(x, y, u []float64) error {
+	gp.defaults()
+	if len(u) == 0 {
+		return gp.err(C.gogp_sparse_set_data(gp.handle(), nil, nil, 0, nil, 0))
+	}
+	if len(x) != len(y)*gp.NDim || len(u)%gp.NDim != 0 {
+		return fmt.Errorf("len(x), len(u)")
+	}
+	return gp.err(C.gogp_sparse_set_data(gp.handle(), dptr(x), dptr(y), C.int64_t(len(y)), dptr(u), C.int64_t(len(u)/gp.NDim)))
+}
+
+// SparseObserve computes the collapsed variational bound of Titsias (2009) of
+// the sparse data at x = log theta: a lower bound of its log marginal
+// likelihood at O(N M^2).
+func (gp *GP) SparseObserve(x []float64) (float64, error) {
+	gp.defaults()
+	var b C.double
+	if err := gp.err(C.gogp_sparse_observe(gp.handle(), dptr(x), C.int64_t(len(x)), &b)); err != nil {
+		return float64(b), err
+	}
+	return float64(b), nil
+}
+
+// SparseGradient computes the gradient of that bound with respect to the
+// log-transformed hyperparameters, at the parameters of the last SparseObserve.
+func (gp *GP) SparseGradient() ([]float64, error) {
+	gp.defaults()
+	g := make([]float64, len(gp.ThetaSimil)+len(gp.ThetaNoise))
+	if err := gp.err(C.gogp_sparse_gradient(gp.handle(), dptr(g), C.int64_t(len(g)))); err != nil {
+		return nil, err
+	}
+	return g, nil
+}
+
+// SparseProduce computes the predictive mean and standard deviation of the
+// sparse approximation at the test points (latent and unclamped, as Produce).
+func (gp *GP) SparseProduce(x [][]float64) (mu, sigma []float64, err error) {
+	gp.defaults()
+	m := len(x)
+	flat := make([]float64, m*gp.NDim)
+	for i, row := range x {
+		copy(flat[i*gp.NDim:], row)
+	}
+	mu, sigma = make([]float64, m), make([]float64, m)
+	if err = gp.err(C.gogp_sparse_produce(gp.handle(), dptr(flat), C.int64_t(m), dptr(mu), dptr(sigma))); err != nil {
+		return nil, nil, err
+	}
+	return mu, sigma, nil
+}
+
 // Sample draws len(xi)/len(x) joint samples at the test points from the
 // caller's standard normals xi (row-major ns x m): samples[s*m+j] =
 // mu[j] + (C xi[s])[j], C the lower Cholesky factor of the covariance +

@@ -21,6 +21,7 @@ GOGP_MAX_CANDIDATES = 16
 GOGP_BATCH_MAX_N = 128
 GOGP_COV_MAX_M = 4096
 GOGP_MULTI_MAX_T = 128
+GOGP_SPARSE_MAX_M = 4096
 
 #: every symbol include/gogp_hip.h declares: (name, restype, argtypes)
 _dp = ctypes.POINTER(ctypes.c_double)
@@ -91,6 +92,10 @@ SYMBOLS = [
     ("gogp_multi_gradient", ctypes.c_int, [_h, _dp, _i64]),
     ("gogp_multi_get_alpha", ctypes.c_int, [_h, _dp]),
     ("gogp_multi_produce", ctypes.c_int, [_h, _dp, _i64, _dp, _dp]),
+    ("gogp_sparse_set_data", ctypes.c_int, [_h, _dp, _dp, _i64, _dp, _i64]),
+    ("gogp_sparse_observe", ctypes.c_int, [_h, _dp, _i64, _dp]),
+    ("gogp_sparse_gradient", ctypes.c_int, [_h, _dp, _i64]),
+    ("gogp_sparse_produce", ctypes.c_int, [_h, _dp, _i64, _dp, _dp]),
     ("gogp_observe_gradient_batch", ctypes.c_int,
      [ctypes.POINTER(_h), ctypes.c_int, _dp, _i64, _dp, _dp, ctypes.POINTER(ctypes.c_int)]),
     ("gogp_observe_gradient_candidates", ctypes.c_int,
@@ -216,6 +221,12 @@ HOOK_SYMBOLS = [
       ctypes.c_double, _dp, _i64, _i64, _i64]),
     ("gogp_test_multi_weight", ctypes.c_int,
      [ctypes.c_int, _dp, _i64, _i64, ctypes.c_int, _dp, _i64, _i64, _i64, _i64, _dp, _i64]),
+    ("gogp_bench_sparse_syrk", ctypes.c_int, [ctypes.c_int, _i64, _i64, ctypes.c_int, _dp, _dp]),
+    ("gogp_test_sparse_syrk", ctypes.c_int,
+     [ctypes.c_int, _dp, _i64, _i64, _i64, _i64, _i64, _dp, _i64, _dp, _i64, _i64, _dp, _i64]),
+    ("gogp_test_sparse_grad", ctypes.c_int,
+     [ctypes.c_int, ctypes.POINTER(CKParams), _dp, _i64, _i64, _dp, _i64, _i64, _dp, _i64, _i64, _dp, _i64, _dp, _i64,
+      ctypes.c_double, ctypes.c_int, _dp]),
     # per-rank replay of the sharded sweep (tools/sharded_replay.py): a transport that reads recorded panels
     ("gogp_test_dist_init_replay", ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int] * 4),
 ]

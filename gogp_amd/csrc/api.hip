@@ -239,6 +239,8 @@ static hipError_t graph_stream(gogp_handle *h) {
   return hipSuccess;
 }
 
+static void sparse_free(gogp_handle *h);  // the inducing-point state (gogp_sparse_*), below
+
 static void release_streams(gogp_handle *h) {
   std::lock_guard<std::mutex> lock(g_pool_mutex);
   if (h->stream_set) static_cast<StreamSet *>(h->stream_set)->in_use = false;
@@ -252,6 +254,7 @@ extern "C" void gogp_destroy(gogp_handle *h) {
   (void)hipSetDevice(h->device);
   if (h->s) (void)hipStreamSynchronize(h->s);
   gogp_dist_destroy(h);
+  sparse_free(h);
   free_n_buffers(h);
   free_m_buffers(h);
   free_cand_buffers(h);
@@ -2901,6 +2904,364 @@ extern "C" int gogp_produce_samples(gogp_handle *h, const double *Z, int64_t m, 
   return GOGP_OK;
 }
 
+// ---- inducing-point approximation (sparse.hip) ----------------------------------------------------------------------
+// No reference counterpart.  The collapsed bound of Titsias (2009) on M inducing points; the formulas are in DESIGN.md
+// section 4, "Sparse".  The process on the inducing points is a private dense handle (sp_ind): Kuu + eps I is its Gram
+// matrix (constant noise of std sqrt(eps)), so its factor, V^T of a chunk (Produce's forward substitution on the tile
+// route with the chunk's rows as test points), Y = L^-T and the reduction over the (U, U) pairs all come from the code
+// of the dense path.  Everything runs on that handle's main stream.  The M x M work on B = I + V V^T / s2 is done here
+// with the tile kernel: a 256-panel Cholesky (as gogp_produce_samples), the triangular inverse panel by panel
+// (the recurrence of trtri_superstep: column panel i of Y = C^-T is -Y[:i, :i] C[i, :i]^T inv(C_ii)^T), B^-1 = Y Y^T.
+struct SparseBufs {
+  double *Bacc, *Bm, *C, *Y, *Binv, *Pm, *Gm, *Yu;  // Mp x Mp; the gradient reuses Bacc / C / Y for T / S / a product
+  double *Dinv, *tmp;                          // Mp / 256 block inverses; Mp x 256
+  double *r, *g, *mvec, *zero;                 // Mp doubles each
+  double *scal, *gsum, *gpart;                 // 8; NACC; SG partial rows
+  long long *info;
+};
+// the buffers at `base` (nullptr: the sizes alone); returns the bytes they take
+static size_t sparse_layout(double *base, int64_t Mp, SparseBufs *b) {
+  const size_t mm = (size_t)Mp * Mp;
+  size_t off = 0;
+  auto take = [&](size_t cnt) {
+    double *q = base ? base + off : nullptr;
+    off += cnt;
+    return q;
+  };
+  b->Bacc = take(mm), b->Bm = take(mm), b->C = take(mm), b->Y = take(mm), b->Binv = take(mm), b->Pm = take(mm);
+  b->Gm = take(mm), b->Yu = take(mm);
+  b->Dinv = take((size_t)(Mp / PANEL) * PANEL * PANEL);
+  b->tmp = take((size_t)Mp * PANEL);
+  b->r = take(Mp), b->g = take(Mp), b->mvec = take(Mp), b->zero = take(Mp);
+  b->scal = take(8), b->gsum = take(NACC), b->gpart = take((size_t)SPARSE_GRAD_BLOCKS_MAX * NACC);
+  b->info = reinterpret_cast<long long *>(take(1));
+  return off * sizeof(double);
+}
+static int64_t sparse_mp(const gogp_handle *h) { return ((h->sp_M + PANEL - 1) / PANEL) * PANEL; }
+
+static void sparse_free(gogp_handle *h) {
+  if (h->sp_ind) gogp_destroy(h->sp_ind);
+  h->sp_ind = nullptr;
+  (void)hipFree(h->sp_X);
+  (void)hipFree(h->sp_y);
+  h->sp_X = h->sp_y = nullptr;
+  h->sp_ws.release();
+  h->sp_vec.release();
+  h->sp_N = h->sp_M = 0;
+  h->sp_have = h->sp_observed = false;
+}
+
+// NULL, or the kind of handle the sparse calls refuse
+static const char *sparse_refusal(const gogp_handle *h) {
+  return h->prec == 32 ? "precision = 32 handles are not supported"
+         : h->dist     ? "sharded handles are not supported"
+         : h->ev()     ? "event discounts are out of scope of the inducing-point approximation (clear them with gogp_set_events)"
+                       : nullptr;
+}
+static int sparse_refuse(gogp_handle *h, const char *who) {
+  char buf[200];
+  snprintf(buf, sizeof buf, "%s: %s", who, sparse_refusal(h));
+  return fail(h, GOGP_EARG, buf);
+}
+// an error of the inducing process under the name of the sparse call
+static int sparse_fail_from(gogp_handle *h, const char *who, int rc) {
+  h->err = std::string(who) + ": " + (h->sp_ind ? h->sp_ind->err : std::string("no inducing process"));
+  return rc;
+}
+
+extern "C" int gogp_sparse_set_data(gogp_handle *h, const double *X, const double *y, int64_t N, const double *U, int64_t M) {
+  if (!h) return GOGP_EARG;
+  if (M == 0 && !U) {  // clear
+    HIPCHK(h, hipSetDevice(h->device));
+    sparse_free(h);
+    return GOGP_OK;
+  }
+  if (sparse_refusal(h)) return sparse_refuse(h, "sparse_set_data");
+  if (!U || M < 1 || M > GOGP_SPARSE_MAX_M)
+    return fail(h, GOGP_EARG, "sparse_set_data: need U and 1 <= M <= GOGP_SPARSE_MAX_M");
+  if (N < 0 || (N > 0 && (!X || !y))) return fail(h, GOGP_EARG, "sparse_set_data: need X and y for N > 0, N >= 0");
+  const int D = h->D;
+  for (int64_t i = 0; i < M * D; ++i)
+    if (!std::isfinite(U[i])) return fail(h, GOGP_EARG, "sparse_set_data: non-finite inducing point");
+  for (int64_t i = 0; i < N * D; ++i)
+    if (!std::isfinite(X[i])) return fail(h, GOGP_EARG, "sparse_set_data: non-finite input");
+  for (int64_t i = 0; i < N; ++i)
+    if (!std::isfinite(y[i])) return fail(h, GOGP_EARG, "sparse_set_data: non-finite output");
+  HIPCHK(h, hipSetDevice(h->device));
+  sparse_free(h);
+  // the inducing process: the handle's similarity terms, constant noise (its std is set per Observe), no tiny path (the
+  // general sweep leaves Y = L^-T in its buffer)
+  gogp_desc d = h->desc;
+  d.noise_kind = GOGP_NOISE_CONSTANT;
+  d.noise_std = pow(10.0, 0.5 * h->sp_jitter_log10);
+  gogp_handle *ind = nullptr;
+  int rc = gogp_create(&d, h->device, &ind);
+  if (rc != GOGP_OK) return fail(h, rc, "sparse_set_data: the inducing process could not be created");
+  h->sp_ind = ind;
+  ind->tiny = 0;
+  std::vector<double> y0((size_t)M, 0.0);
+  rc = gogp_set_data(ind, U, y0.data(), M);
+  if (rc != GOGP_OK) {
+    rc = sparse_fail_from(h, "sparse_set_data", rc);
+    sparse_free(h);
+    return rc;
+  }
+  h->sp_M = M;
+  h->sp_N = N;
+  const int64_t Mp = sparse_mp(h);
+  SparseBufs b;
+  rc = h->sp_ws.reserve(h, sparse_layout(nullptr, Mp, &b));
+  if (rc != GOGP_OK) {
+    sparse_free(h);
+    return rc;
+  }
+  sparse_layout(h->sp_ws.as<double>(), Mp, &b);
+  hipStream_t s = ind->s;
+  hipError_t e = hipSuccess;
+  h->sp_yty = 0.0;
+  if (N > 0) {
+    const size_t xb = ((size_t)N * D + GOGP_MAX_NDIM) * sizeof(double);
+    e = hipMalloc(&h->sp_X, xb);
+    if (e == hipSuccess) e = hipMalloc(&h->sp_y, (size_t)N * sizeof(double));
+    if (e == hipSuccess) e = hipMemsetAsync(h->sp_X, 0, xb, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(h->sp_X, X, (size_t)N * D * sizeof(double), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(h->sp_y, y, (size_t)N * sizeof(double), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) {
+      launch_sparse_sumsq(s, h->sp_y, N, b.scal);
+      e = hipMemcpyAsync(&h->sp_yty, b.scal, sizeof(double), hipMemcpyDeviceToHost, s);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+  }
+  if (e != hipSuccess) {
+    sparse_free(h);
+    HIPCHK(h, e);
+  }
+  h->sp_have = true;
+  return GOGP_OK;
+}
+
+// C C^T = Bm (256-panel Cholesky on the main stream), Y = C^-T panel by panel, Binv = Y Y^T in full
+static void sparse_factor_b(gogp_handle *ind, hipStream_t s, const SparseBufs &b, int64_t M, int64_t Mp) {
+  GemmGrid gtri;
+  gtri.ktri = ind->ktri;
+  for (int64_t c0 = 0; c0 < Mp; c0 += PANEL) {
+    const int64_t c2 = c0 + PANEL;
+    double *Dp = b.Dinv + (size_t)(c0 / PANEL) * PANEL * PANEL;
+    launch_diag256(s, b.Bm + c0 * Mp + c0, Mp, b.C + c0 * Mp + c0, Mp, Dp, c0, M, b.info);
+    const int mt2 = (int)((Mp - c2) / TILE);
+    if (mt2 > 0) {
+      launch_gemm_nt(s, GEMM_RECT, mt2, 2, PANEL, 1.0, b.Bm + c2 * Mp + c0, Mp, Dp, PANEL, 0.0, b.C + c2 * Mp + c0, Mp, nullptr,
+                     &gtri);
+      launch_gemm_nt(s, GEMM_LOWER, mt2, mt2, PANEL, -1.0, b.C + c2 * Mp + c0, Mp, b.C + c2 * Mp + c0, Mp, 1.0,
+                     b.Bm + c2 * Mp + c2, Mp, nullptr);
+    }
+  }
+  for (int64_t c0 = 0; c0 < Mp; c0 += PANEL) {
+    const double *Dp = b.Dinv + (size_t)(c0 / PANEL) * PANEL * PANEL;
+    launch_ydiag(s, Dp, b.Y + c0 * Mp + c0, Mp);
+    if (c0 > 0) {
+      const int mt = (int)(c0 / TILE);
+      launch_gemm_nt(s, GEMM_RECT, mt, 2, c0, 1.0, b.Y, Mp, b.C + c0 * Mp, Mp, 0.0, b.tmp, PANEL, nullptr);
+      launch_gemm_nt(s, GEMM_RECT, mt, 2, PANEL, -1.0, b.tmp, PANEL, Dp, PANEL, 0.0, b.Y + c0, Mp, nullptr);
+    }
+  }
+  const int nt = (int)(Mp / TILE);
+  launch_gemm_nt(s, GEMM_RECT, nt, nt, Mp, 1.0, b.Y, Mp, b.Y, Mp, 0.0, b.Binv, Mp, nullptr);
+}
+
+extern "C" int gogp_sparse_observe(gogp_handle *h, const double *x, int64_t len, double *bound) {
+  if (!h || !x || !bound) return fail(h, GOGP_EARG, "sparse_observe: NULL");
+  if (sparse_refusal(h)) return sparse_refuse(h, "sparse_observe");
+  if (len != h->P) return fail(h, GOGP_EARG, "sparse_observe: len(x)");
+  for (int64_t i = 0; i < len; ++i)
+    if (!std::isfinite(x[i])) return fail(h, GOGP_EARG, "sparse_observe: non-finite parameter");
+  if (!h->sp_have) return fail(h, GOGP_ESTATE, "sparse_observe: no sparse data (gogp_sparse_set_data)");
+  HIPCHK(h, hipSetDevice(h->device));
+  gogp_handle *ind = h->sp_ind;
+  h->sp_observed = false;
+  *bound = NAN;
+  // the parameters on the host: noise variance, its derivative, the output scales
+  std::vector<double> th(h->P > 0 ? h->P : 1);
+  for (int i = 0; i < h->P; ++i) th[i] = exp(x[i]);
+  if (const char *why = theta_refusal(h, th.data(), th.data() + h->ns)) return fail(h, GOGP_EARG, why);
+  DevParams hp;
+  fill_params_theta(h, th.data(), th.data() + h->ns, hp);
+  if (!(hp.noise_var > 0.0) || !std::isfinite(hp.noise_var))
+    return fail(h, GOGP_EARG, "sparse_observe: the noise variance must be positive and finite");
+  ind->desc.noise_std = pow(10.0, 0.5 * h->sp_jitter_log10);
+  ind->cond_limit = h->cond_limit;
+  int rc = gogp_observe(ind, x, ind->P, nullptr);
+  if (rc == GOGP_ENOTPD) {
+    char buf[200];
+    h->notpd = ind->notpd;
+    snprintf(buf, sizeof buf, "sparse_observe: Kuu + jitter is not positive definite (inducing point %lld)", (long long)h->notpd);
+    h->err = buf;
+    return rc;
+  }
+  if (rc != GOGP_OK && rc != GOGP_ECOND) return sparse_fail_from(h, "sparse_observe", rc);
+  const int rcond = rc;
+  if (rcond == GOGP_ECOND) h->err = "sparse_observe: the factor of Kuu + jitter exceeds the condition limit";
+  const int64_t N = h->sp_N, M = h->sp_M, Mp = sparse_mp(h);
+  const double s2 = hp.noise_var;
+  h->sp_s2 = s2;
+  h->sp_dnoise = hp.dnoise;
+  h->sp_cterm.assign(hp.c, hp.c + h->desc.nterms);
+  h->sp_csum = 0.0;
+  for (int t = 0; t < h->desc.nterms; ++t) h->sp_csum += hp.c[t];
+  if (N == 0) {
+    *bound = 0.0;
+    h->sp_observed = true;
+    return rcond;
+  }
+  SparseBufs b;
+  sparse_layout(h->sp_ws.as<double>(), Mp, &b);
+  hipStream_t s = ind->s;
+  rc = ensure_alpha(ind);  // the main stream behind the factorisation
+  if (rc != GOGP_OK) return sparse_fail_from(h, "sparse_observe", rc);
+  const size_t mm = (size_t)Mp * Mp;
+  HIPCHK(h, hipMemsetAsync(b.Bacc, 0, 4 * mm * sizeof(double), s));  // Bacc, Bm, C, Y
+  HIPCHK(h, hipMemsetAsync(b.r, 0, 4 * (size_t)Mp * sizeof(double), s));  // r, g, mvec, zero
+  HIPCHK(h, hipMemsetAsync(b.info, 0, sizeof(long long), s));
+  // first pass over the data: V^T of every chunk, B_acc += V V^T, r += V y
+  const int64_t chunk = std::min(h->sp_chunk, ((N + TILE - 1) / TILE) * TILE);
+  rc = ensure_m(ind, chunk, chunk);
+  if (rc != GOGP_OK) return sparse_fail_from(h, "sparse_observe", rc);
+  for (int64_t f0 = 0; f0 < N; f0 += chunk) {
+    const int64_t m = std::min(chunk, N - f0), mpad = ((m + TILE - 1) / TILE) * TILE;
+    launch_cross(s, ind->devP, ind->D, ind->dX, M, Mp, h->sp_X + f0 * ind->D, m, mpad, ind->KsT, Mp, false);
+    produce_substitute_t<double>(ind, s, m, mpad, nullptr);
+    launch_sparse_syrk(s, ind->Vt, Mp, m, M, Mp, h->sp_y + f0, b.Bacc, Mp, b.r);
+  }
+  // the M x M work: B, its factor, B^-1, g = B^-1 r and the scalars
+  launch_sparse_finish_b(s, b.Bacc, Mp, 1.0 / s2, b.Bm);
+  HIPCHK(h, hipMemcpyAsync(b.Pm, b.Bm, mm * sizeof(double), hipMemcpyDeviceToDevice, s));  // the factorisation consumes Bm
+  sparse_factor_b(ind, s, b, M, Mp);
+  HIPCHK(h, hipMemcpyAsync(b.Bm, b.Pm, mm * sizeof(double), hipMemcpyDeviceToDevice, s));
+  launch_rownorm_dot(s, b.Binv, Mp, b.r, Mp, M, b.g, nullptr);
+  launch_sparse_scalars(s, b.C, b.Bm, b.Binv, b.r, b.g, M, Mp, b.scal);
+  long long info = 0;
+  HIPCHK(h, hipMemcpyAsync(h->sp_scal, b.scal, 5 * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipMemcpyAsync(&info, b.info, sizeof info, hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipStreamSynchronize(s));
+  HIPCHK(h, hipGetLastError());
+  if (info != 0) return fail(h, GOGP_EHIP, "sparse_observe: the factorisation of B = I + V V^T / s2 met a non-positive pivot");
+  const double logdetB = h->sp_scal[0], trBmM = h->sp_scal[1], rtg = h->sp_scal[3];
+  const double t0 = (double)N * h->sp_csum;
+  *bound = -0.5 * (double)N * log(2 * M_PI) - 0.5 * logdetB - 0.5 * (double)N * log(s2) - h->sp_yty / (2 * s2) +
+           rtg / (2 * s2 * s2) - (t0 - s2 * trBmM) / (2 * s2);
+  h->sp_observed = true;
+  return rcond;
+}
+
+extern "C" int gogp_sparse_gradient(gogp_handle *h, double *grad, int64_t len) {
+  if (!h || !grad) return fail(h, GOGP_EARG, "sparse_gradient: NULL");
+  if (sparse_refusal(h)) return sparse_refuse(h, "sparse_gradient");
+  if (len != h->P) return fail(h, GOGP_EARG, "sparse_gradient: wrong length");
+  if (!h->sp_have) return fail(h, GOGP_ESTATE, "sparse_gradient: no sparse data (gogp_sparse_set_data)");
+  if (!h->sp_observed) return fail(h, GOGP_ESTATE, "sparse_gradient before sparse_observe");
+  for (int64_t i = 0; i < len; ++i) grad[i] = 0.0;
+  const int64_t N = h->sp_N, M = h->sp_M, Mp = sparse_mp(h);
+  if (N == 0) return GOGP_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  gogp_handle *ind = h->sp_ind;
+  SparseBufs b;
+  sparse_layout(h->sp_ws.as<double>(), Mp, &b);
+  hipStream_t s = ind->s;
+  int rc = compute_kinv(ind);  // Y = L^-T of the inducing process in its bufY, the main stream behind it
+  if (rc != GOGP_OK) return sparse_fail_from(h, "sparse_gradient", rc);
+  const double s2 = h->sp_s2, s4 = 1.0 / (s2 * s2);
+  // (the upper triangle of the inducing process's bufY: what lies below its super-panels is not part of Y)
+  launch_sparse_copy_upper(s, ind->bufY, Mp, b.Yu);
+  const double *Yu = b.Yu;
+  double *T = b.Bacc, *S = b.C, *W1 = b.Y;
+  const int nt = (int)(Mp / TILE);
+  // T and S, then P = Yu T Yu^T / (2 s2), G = Yu S Yu^T / 2 (both triangles), m = Yu g
+  launch_sparse_weights(s, b.Bm, b.Binv, b.g, Mp, s4, T, S);
+  launch_gemm_nt(s, GEMM_RECT, nt, nt, Mp, 1.0, Yu, Mp, T, Mp, 0.0, W1, Mp, nullptr);
+  launch_gemm_nt(s, GEMM_RECT, nt, nt, Mp, 1.0 / (2 * s2), W1, Mp, Yu, Mp, 0.0, b.Pm, Mp, nullptr);
+  launch_gemm_nt(s, GEMM_RECT, nt, nt, Mp, 1.0, Yu, Mp, S, Mp, 0.0, W1, Mp, nullptr);
+  // (the reduction of the LML gradient forms sum_ab (alpha_a alpha_b - Kinv_ab) dK_ab: G goes in negated, alpha zero)
+  launch_gemm_nt(s, GEMM_RECT, nt, nt, Mp, -0.5, W1, Mp, Yu, Mp, 0.0, b.Gm, Mp, nullptr);
+  launch_rownorm_dot(s, Yu, Mp, b.g, Mp, M, b.mvec, nullptr);
+  launch_grad_reduce(s, ind->devP, ind->D, ind->ard_dims, ind->dX, b.zero, (const double *)b.Gm, Mp, M, Mp, ind->gpart,
+                     ind->gout, ind->radial1, ind->ard_mfma_min, false);
+  // second pass over the data: the chunk's cross-covariance again, Wt = Ks^T 2 P, the pair reduction
+  const int64_t chunk = std::min(h->sp_chunk, ((N + TILE - 1) / TILE) * TILE);
+  rc = ensure_m(ind, chunk, chunk);
+  if (rc != GOGP_OK) return sparse_fail_from(h, "sparse_gradient", rc);
+  GemmGrid gw;
+  gw.small_below = ind->produce_small_below;
+  for (int64_t f0 = 0; f0 < N; f0 += chunk) {
+    const int64_t m = std::min(chunk, N - f0), mpad = ((m + TILE - 1) / TILE) * TILE;
+    launch_cross(s, ind->devP, ind->D, ind->dX, M, Mp, h->sp_X + f0 * ind->D, m, mpad, ind->KsT, Mp, false);
+    launch_gemm_nt(s, GEMM_RECT, (int)(mpad / TILE), nt, Mp, 2.0, (const double *)ind->KsT, Mp, (const double *)b.Pm, Mp,
+                   0.0, ind->Vt, Mp, nullptr, &gw);
+    launch_sparse_grad(s, ind->devP, ind->D, ind->ard_dims, h->sp_X + f0 * ind->D, m, ind->dX, M, ind->Vt, Mp, h->sp_y + f0,
+                       b.mvec, s4, b.gpart, b.gsum, f0 > 0);
+  }
+  double acc[NACC], accu[NACC];
+  HIPCHK(h, hipMemcpyAsync(acc, b.gsum, sizeof acc, hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipMemcpyAsync(accu, ind->gout, sizeof accu, hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipStreamSynchronize(s));
+  HIPCHK(h, hipGetLastError());
+  // assemble_gradient halves the slot sums (the LML's 1/2 tr): (W, dKuf) + (G, dKuu) go in doubled
+  for (int q = 0; q < NACC; ++q) acc[q] = 2.0 * (acc[q] + accu[q]);
+  acc[ACC_TRACE] = 0.0;
+  assemble_gradient(h, acc, 0.0, grad);
+  // the diagonal term -1/(2 s2) sum_f dk(x_f, x_f): the output scales alone
+  for (int t = 0; t < h->desc.nterms; ++t)
+    if (h->desc.terms[t].scale_idx >= 0) grad[h->desc.terms[t].scale_idx] -= (double)N * h->sp_cterm[t] / (2 * s2);
+  if (h->nn > 0) {
+    const double trBmM = h->sp_scal[1], trBinv = h->sp_scal[2], rtg = h->sp_scal[3], gtg = h->sp_scal[4];
+    const double t0 = (double)N * h->sp_csum, s6 = s2 * s2 * s2;
+    const double dF = ((double)M - trBinv) / (2 * s2) - (double)N / (2 * s2) + h->sp_yty / (2 * s2 * s2) - rtg / s6 +
+                      (rtg - gtg) / (2 * s6) + (t0 - s2 * trBmM) / (2 * s2 * s2);
+    grad[h->ns] = h->sp_dnoise * dF;
+  }
+  return GOGP_OK;
+}
+
+extern "C" int gogp_sparse_produce(gogp_handle *h, const double *Z, int64_t m, double *mu, double *sigma) {
+  if (!h || m < 0 || (m > 0 && (!Z || !mu || !sigma))) return fail(h, GOGP_EARG, "sparse_produce: NULL");
+  if (sparse_refusal(h)) return sparse_refuse(h, "sparse_produce");
+  if (!h->sp_have) return fail(h, GOGP_ESTATE, "sparse_produce: no sparse data (gogp_sparse_set_data)");
+  if (!h->sp_observed) return fail(h, GOGP_ESTATE, "sparse_produce before sparse_observe");
+  for (int64_t i = 0; i < m * h->D; ++i)
+    if (!std::isfinite(Z[i])) return fail(h, GOGP_EARG, "sparse_produce: non-finite test point");
+  if (m == 0) return GOGP_OK;
+  gogp_handle *ind = h->sp_ind;
+  const int64_t M = h->sp_M, Mp = sparse_mp(h);
+  ProducePlan pp;
+  int rc = produce_prepare(ind, nullptr, "sparse_produce", m, false, &pp);
+  if (rc != GOGP_OK) return sparse_fail_from(h, "sparse_produce", rc);
+  rc = h->sp_vec.reserve(h, (size_t)pp.mpad * sizeof(double));
+  if (rc != GOGP_OK) return rc;
+  hipStream_t s = ind->s;
+  const bool empty = h->sp_N == 0;
+  // the tile route of Produce on the inducing process, whatever m: it leaves v^T = (L^-1 k(U, z))^T in Vt row by row
+  // and |v|^2 in pp.q
+  rc = produce_forward(ind, Z, m, pp, true, !empty);
+  if (rc != GOGP_OK) return sparse_fail_from(h, "sparse_produce", rc);
+  if (empty) {  // no observations: the prior
+    rc = produce_of_the_prior(ind, pp, m, mu, sigma);
+    return rc == GOGP_OK ? rc : sparse_fail_from(h, "sparse_produce", rc);
+  }
+  SparseBufs b;
+  sparse_layout(h->sp_ws.as<double>(), Mp, &b);
+  double *dot = h->sp_vec.as<double>();
+  launch_rownorm_dot(s, (const double *)ind->Vt, Mp, b.g, Mp, m, dot, nullptr);
+  GemmGrid gm;
+  gm.small_below = ind->produce_small_below;
+  launch_gemm_nt(s, GEMM_RECT, (int)(pp.mpad / TILE), (int)(Mp / TILE), Mp, 1.0, (const double *)ind->Vt, Mp,
+                 (const double *)b.Binv, Mp, 0.0, ind->KsT, Mp, nullptr, &gm);
+  launch_sparse_predict(s, ind->KsT, ind->Vt, Mp, M, m, pp.prior, pp.q, dot, 1.0 / h->sp_s2, pp.mu, pp.sigma);
+  HIPCHK(h, hipMemcpyAsync(mu, pp.mu, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipMemcpyAsync(sigma, pp.sigma, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipStreamSynchronize(s));
+  HIPCHK(h, hipGetLastError());
+  return GOGP_OK;
+}
+
 // ---- cached state --------------------------------------------------------------------------------
 extern "C" int gogp_get_alpha(gogp_handle *h, double *alpha) {
   if (!h || (h->n > 0 && !alpha)) return GOGP_EARG;
@@ -3644,6 +4005,17 @@ extern "C" int gogp_set_option(gogp_handle *h, const char *name, int64_t value) 
   if (strcmp(name, "cond_limit_log10") == 0) {  // gonum: mat.ConditionTolerance (a package variable), 1e16
     if (value < 1 || value > 300) return fail(h, GOGP_EARG, "cond_limit_log10 must be 1..300");
     h->cond_limit = pow(10.0, (double)value);
+    return GOGP_OK;
+  }
+  if (strcmp(name, "sparse_jitter_log10") == 0) {  // gogp_sparse_*: Kuu + 10^value I is factored (absolute), from the next sparse_observe on
+    if (value < -14 || value > -2) return fail(h, GOGP_EARG, "sparse_jitter_log10 must be -14..-2");
+    h->sp_jitter_log10 = (int)value;
+    h->sp_observed = false;
+    return GOGP_OK;
+  }
+  if (strcmp(name, "sparse_chunk") == 0) {  // gogp_sparse_*: rows of X per pass
+    if (value < 256 || value > 65536 || value % 256) return fail(h, GOGP_EARG, "sparse_chunk must be a multiple of 256 in 256..65536");
+    h->sp_chunk = value;
     return GOGP_OK;
   }
   if (strcmp(name, "superpanel") == 0) {

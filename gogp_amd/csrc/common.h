@@ -441,6 +441,31 @@ void launch_loo_rank2(hipStream_t s, double *G, int64_t ld, int64_t n, int64_t n
 void launch_multi_weight(hipStream_t s, const double *At, int64_t ld, int T, const double *Kinv, int64_t ldk, int64_t n,
                          int64_t npad, double *G);
 void launch_multi_dots(hipStream_t s, const double *Yt, const double *At, int64_t ld, int64_t n, int T, double *dots);
+// sparse.hip (gogp_sparse_*): the inducing-point approximation.  Vt: `rows` rows (one observation of the chunk each) of
+// ld >= Mp doubles, as Produce's forward substitution leaves V^T; Mp a multiple of 64.
+// launch_sparse_syrk: Bacc (ldb) += Vt^T Vt on the whole lower 64-tiles of Mp x Mp and r += Vt^T y (rows doubles); rows
+// >= `rows` of Vt are not read and its columns >= M count as exact zeros.  launch_sparse_grad: out (NACC slot sums,
+// `accumulate`: added to what out holds) = sum_{f < rows, u < M} (Wt[f][u] + y_f mvec_u s4) dk(x_f, u_u)/dlog theta;
+// partials: sparse_grad_blocks(rows, M) * NACC doubles of scratch.  The element-wise passes: B (full) = I + Bacc / s2 from
+// the lower tiles; T = I - Binv - g g^T s4 and S = 2 I - B - Binv - g g^T s4; the five scalars of the bound (sparse.hip);
+// sum y^2; mu = dot / s2 and sigma = sqrt(prior - q + rowdot(A, V)) of Produce.
+void launch_sparse_syrk(hipStream_t s, const double *Vt, int64_t ld, int64_t rows, int64_t M, int64_t Mp, const double *y,
+                        double *Bacc, int64_t ldb, double *r);
+constexpr int SPARSE_GRAD_BLOCKS_MAX = 2048;  // workgroups (rows of `partials`) of launch_sparse_grad at most
+int sparse_grad_blocks(int64_t rows, int64_t M);
+void launch_sparse_grad(hipStream_t s, const DevParams *p, int ndim, int ard_dims, const double *X, int64_t rows,
+                        const double *U, int64_t M, const double *Wt, int64_t ldw, const double *y, const double *mvec,
+                        double s4, double *partials, double *out, bool accumulate);
+void launch_sparse_finish_b(hipStream_t s, const double *Bacc, int64_t Mp, double inv_s2, double *B);
+void launch_sparse_copy_upper(hipStream_t s, const double *src, int64_t Mp, double *dst);  // zeros below the diagonal
+void launch_sparse_weights(hipStream_t s, const double *B, const double *Binv, const double *g, int64_t Mp, double s4,
+                           double *T, double *S);
+void launch_sparse_scalars(hipStream_t s, const double *C, const double *B, const double *Binv, const double *r,
+                           const double *g, int64_t M, int64_t Mp, double *out);
+void launch_sparse_sumsq(hipStream_t s, const double *y, int64_t n, double *out);
+void launch_sparse_predict(hipStream_t s, const double *A, const double *V, int64_t ld, int64_t ncols, int64_t m,
+                           const double *prior, const double *q, const double *dot, double inv_s2, double *mu,
+                           double *sigma);
 void launch_fill(hipStream_t s, double *p, int64_t count, double v);
 void launch_axpy(hipStream_t s, double *a, const double *b, int64_t count);  // a += b
 void launch_dot(hipStream_t s, const double *a, const double *b, int64_t n, double *out);  // out[0] = a.b

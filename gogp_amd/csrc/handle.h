@@ -224,6 +224,20 @@ struct gogp_handle : EvalBufs, EvalState {
   Workspace multi_vec;      // Y^T, then A^T: GOGP_MULTI_MAX_T rows of npad doubles each, zero from column n and from row T on
   Workspace multi_mean;     // gogp_multi_produce: Kstar^T A, mpad x GOGP_MULTI_MAX_T; gogp_multi_lml: the T dots
   Workspace multi_mat;      // gogp_multi_gradient: G = T K^-1 - A A^T and a zero vector, (npad + 1) x npad
+  // the inducing-point approximation (gogp_sparse_*, sparse.hip): a data set of its own and a private dense handle for
+  // the process on the inducing points; nothing of the handle's own data, factor or workspaces is touched
+  gogp_handle *sp_ind = nullptr;   // the inducing process: same similarity terms, constant noise sqrt(jitter), data U, y = 0
+  double *sp_X = nullptr, *sp_y = nullptr;  // N x D (+ GOGP_MAX_NDIM slack) and N doubles, resident
+  int64_t sp_N = 0, sp_M = 0;
+  bool sp_have = false, sp_observed = false;
+  int sp_jitter_log10 = -8;        // option "sparse_jitter_log10"
+  int64_t sp_chunk = 8192;         // option "sparse_chunk": rows of X per pass
+  Workspace sp_ws;                 // the Mp x Mp matrices, block inverses, vectors and slot sums (api.hip: sparse_layout)
+  Workspace sp_vec;                // gogp_sparse_produce: one dot product per test point
+  double sp_yty = 0.0;             // y^T y of the sparse data
+  double sp_s2 = 0.0, sp_dnoise = 0.0, sp_csum = 0.0;  // of the last gogp_sparse_observe: noise variance, its derivative, sum of the output scales
+  double sp_scal[5] = {};          // ... and its scalars (sparse.hip: sparse_scalars_kernel)
+  std::vector<double> sp_cterm;    // ... and every term's output scale
   double yta = 0.0;      // y^T alpha of the last factorisation (fp32 path: of the refined alpha)
   int trace_fp64 = 1;    // fp32 path: tr(alpha alpha^T - K^-1) summed in fp64 from Y, scale component by its identity
   double cond_limit = 1e16;  // gonum's mat.ConditionTolerance

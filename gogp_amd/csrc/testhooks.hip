@@ -1377,3 +1377,100 @@ extern "C" int gogp_test_multi_weight(int device, const double *At, int64_t at_l
   (void)hipFree(dA);
   return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
 }
+
+// ---- sparse_syrk_kernel and sparse_grad_kernel (sparse.hip) through their product launchers
+// (tests/test_sparse_gpu.py).  The rules of the hooks above.
+extern "C" int gogp_test_sparse_syrk(int device, const double *Vt, int64_t vt_len, int64_t ld, int64_t rows, int64_t M,
+                                     int64_t Mp, const double *y, int64_t y_len, double *Bacc, int64_t b_len, int64_t ldb,
+                                     double *r, int64_t r_len) {
+  if (!Vt || !y || !Bacc || !r) return GOGP_EARG;
+  if (Mp <= 0 || Mp % 64 || Mp > GOGP_SPARSE_MAX_M || M < 1 || M > Mp || rows < 1 || rows > (1 << 16)) return GOGP_EARG;
+  if (!covers(vt_len, 0, ld, rows, Mp, 1, 0) || !covers(b_len, 0, ldb, Mp, Mp, 1, 0) || y_len < rows || r_len < Mp)
+    return GOGP_EARG;
+  if (!device_ok(device)) return GOGP_EHIP;
+  DevCopy dV, dy, dB, dr;
+  hipError_t e = dV.up(Vt, (size_t)vt_len * sizeof(double));
+  if (e == hipSuccess) e = dy.up(y, (size_t)y_len * sizeof(double));
+  if (e == hipSuccess) e = dB.up(Bacc, (size_t)b_len * sizeof(double));
+  if (e == hipSuccess) e = dr.up(r, (size_t)r_len * sizeof(double));
+  if (e == hipSuccess) {
+    launch_sparse_syrk(0, dV.as<double>(), ld, rows, M, Mp, dy.as<double>(), dB.as<double>(), ldb, dr.as<double>());
+    e = launched();
+  }
+  if (e == hipSuccess) e = dB.down(Bacc);
+  if (e == hipSuccess) e = dr.down(r);
+  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+}
+
+extern "C" int gogp_test_sparse_grad(int device, const gogp_test_kparams *kparams, const double *X, int64_t x_len, int64_t rows,
+                                     const double *U, int64_t u_len, int64_t M, const double *Wt, int64_t wt_len, int64_t ldw,
+                                     const double *y, int64_t y_len, const double *mvec, int64_t m_len, double s4,
+                                     int accumulate, double *out /* GOGP_TEST_NACC */) {
+  if (!kparams || !X || !U || !Wt || !y || !mvec || !out) return GOGP_EARG;
+  if (!kparams_ok(kparams, 1, ard_dims_of(kparams), 0, 1, 0) || kparams->nevents != 0) return GOGP_EARG;
+  if (rows < 1 || rows > (1 << 16) || M < 1 || M > GOGP_SPARSE_MAX_M || !std::isfinite(s4)) return GOGP_EARG;
+  if (x_len < rows * kparams->ndim || u_len < M * kparams->ndim || y_len < rows || m_len < M) return GOGP_EARG;
+  if (!covers(wt_len, 0, ldw, rows, M, 1, 0)) return GOGP_EARG;
+  if (!device_ok(device)) return GOGP_EHIP;
+  const DevParams hp = to_dev(*kparams);
+  DevCopy dP, dX, dU, dW, dy, dm, dout;
+  double *part = nullptr;
+  hipError_t e = dP.up(&hp, sizeof hp);
+  if (e == hipSuccess) e = dX.up(X, (size_t)x_len * sizeof(double));
+  if (e == hipSuccess) e = dU.up(U, (size_t)u_len * sizeof(double));
+  if (e == hipSuccess) e = dW.up(Wt, (size_t)wt_len * sizeof(double));
+  if (e == hipSuccess) e = dy.up(y, (size_t)y_len * sizeof(double));
+  if (e == hipSuccess) e = dm.up(mvec, (size_t)m_len * sizeof(double));
+  if (e == hipSuccess) e = dout.up(out, (size_t)NACC * sizeof(double));
+  if (e == hipSuccess) e = hipMalloc(&part, (size_t)sparse_grad_blocks(rows, M) * NACC * sizeof(double));
+  if (e == hipSuccess) {
+    launch_sparse_grad(0, dP.as<DevParams>(), kparams->ndim, ard_dims_of(kparams), dX.as<double>(), rows, dU.as<double>(), M,
+                       dW.as<double>(), ldw, dy.as<double>(), dm.as<double>(), s4, part, dout.as<double>(), accumulate != 0);
+    e = launched();
+  }
+  if (e == hipSuccess) e = dout.down(out);
+  (void)hipFree(part);
+  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+}
+
+// Benchmark hook for sparse_syrk_kernel: `reps` launches on device buffers (Vt: rows x Mp, Mp = M rounded up to 256);
+// ms per launch and TFLOP/s on the flops of the lower 64-tiles
+extern "C" int gogp_bench_sparse_syrk(int device, int64_t rows, int64_t M, int reps, double *ms_per_launch, double *tflops) {
+  if (rows < 1 || rows > (1 << 16) || M < 1 || M > GOGP_SPARSE_MAX_M || reps < 1) return GOGP_EARG;
+  if (!device_ok(device)) return GOGP_EHIP;
+  const int64_t Mp = (M + PANEL - 1) / PANEL * PANEL;
+  double *dV = nullptr, *dy = nullptr, *dB = nullptr, *dr = nullptr;
+  hipError_t e = hipMalloc(&dV, (size_t)rows * Mp * sizeof(double));
+  if (e == hipSuccess) e = hipMalloc(&dy, (size_t)rows * sizeof(double));
+  if (e == hipSuccess) e = hipMalloc(&dB, (size_t)Mp * Mp * sizeof(double));
+  if (e == hipSuccess) e = hipMalloc(&dr, (size_t)Mp * sizeof(double));
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  float ms = 0.f;
+  if (e == hipSuccess) {
+    launch_fill(0, dV, rows * Mp, 0.5);
+    launch_fill(0, dy, rows, 0.25);
+    launch_fill(0, dB, Mp * Mp, 0.0);
+    launch_fill(0, dr, Mp, 0.0);
+    (void)hipEventCreate(&e0);
+    (void)hipEventCreate(&e1);
+    for (int w = 0; w < 2; ++w) launch_sparse_syrk(0, dV, Mp, rows, M, Mp, dy, dB, Mp, dr);
+    (void)hipDeviceSynchronize();
+    (void)hipEventRecord(e0, 0);
+    for (int r = 0; r < reps; ++r) launch_sparse_syrk(0, dV, Mp, rows, M, Mp, dy, dB, Mp, dr);
+    (void)hipEventRecord(e1, 0);
+    e = hipEventSynchronize(e1);
+    (void)hipEventElapsedTime(&ms, e0, e1);
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+  }
+  (void)hipFree(dV);
+  (void)hipFree(dy);
+  (void)hipFree(dB);
+  (void)hipFree(dr);
+  if (e != hipSuccess) return e == hipErrorOutOfMemory ? GOGP_ENOMEM : GOGP_EHIP;
+  const int64_t nt = Mp / 64;
+  const double flops = (double)(nt * (nt + 1) / 2) * 64.0 * 64.0 * 2.0 * (double)rows * reps;
+  if (ms_per_launch) *ms_per_launch = ms / reps;
+  if (tflops) *tflops = flops / (ms * 1e-3) / 1e12;
+  return GOGP_OK;
+}

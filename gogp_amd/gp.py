@@ -439,6 +439,48 @@ class GP:
         self._check(_lib.lib().gogp_multi_produce(self._h, _dp(z) if m else None, m, _dp(buf), _dp(sigma) if m else None))
         return mu, sigma
 
+    # ---- sparse: the collapsed bound on M inducing points (no reference counterpart) ----
+    def SetSparse(self, X, Y, U) -> None:
+        """Data of the inducing-point approximation (gogp_sparse_set_data): N observations X (N x NDim), Y and
+        M <= 4096 inducing points U (M x NDim), kept on the device beside the process's own X / Y, which they do not
+        touch.  ``U = None`` clears them.  fp64, unsharded handles without event discounts only."""
+        L = _lib.lib()
+        if U is None:
+            self._check(L.gogp_sparse_set_data(self._h, None, None, 0, None, 0))
+            return
+        u = np.ascontiguousarray(_arr(U).reshape(-1, self.NDim))
+        x = np.ascontiguousarray(_arr(X).reshape(-1, self.NDim))
+        y = np.ascontiguousarray(_arr(Y).reshape(-1))
+        if len(x) != len(y):
+            raise ValueError("SetSparse: len(X) != len(Y)")
+        n = len(y)
+        self._check(L.gogp_sparse_set_data(self._h, _dp(x) if n else None, _dp(y) if n else None, n,
+                                           _dp(u if len(u) else np.zeros(1)), len(u)))
+
+    def SparseObserve(self, x) -> float:
+        """The collapsed variational bound of Titsias (2009) at x = log theta (gogp_sparse_observe): a lower bound of
+        the LML of the sparse data that costs O(N M^2)."""
+        xa = np.ascontiguousarray(_arr(x).reshape(-1))
+        v = ctypes.c_double(0.0)
+        self._check(_lib.lib().gogp_sparse_observe(self._h, _dp(xa if xa.size else np.zeros(1)), xa.size, ctypes.byref(v)))
+        return v.value
+
+    def SparseGradient(self) -> np.ndarray:
+        """d bound / d log theta at the parameters of the last SparseObserve (gogp_sparse_gradient)."""
+        g = np.zeros(self._ns + self._nn)
+        self._check(_lib.lib().gogp_sparse_gradient(self._h, _dp(g if g.size else np.zeros(1)), g.size))
+        return g
+
+    def SparseProduce(self, x):
+        """(mu, sigma) of the sparse approximation at the test points, latent and unclamped as Produce
+        (gogp_sparse_produce)."""
+        z = np.ascontiguousarray(_arr(x).reshape(-1, self.NDim))
+        m = len(z)
+        mu, sigma = np.zeros(m), np.zeros(m)
+        self._check(_lib.lib().gogp_sparse_produce(self._h, _dp(z) if m else None, m, _dp(mu) if m else None,
+                                                   _dp(sigma) if m else None))
+        return mu, sigma
+
     # ---- cached computations: gp.GP.L, gp.GP.Alpha (gp/gp.go:34-37) ----------------------
     @property
     def Alpha(self) -> np.ndarray:
@@ -770,6 +812,33 @@ class MultiModel:
 
     def Gradient(self) -> np.ndarray:
         g = self.gp.MultiGradient()
+        if self.Priors is not None:
+            self.Priors.Observe(self._x)
+            pg = np.asarray(self.Priors.Gradient(), dtype=float)
+            g[:len(pg)] += pg
+        return g
+
+
+class SparseModel:
+    """Model with the collapsed bound of GP.SetSparse in the place of the LML: Observe(x) returns GP.SparseObserve(x)
+    (+ the log prior), Gradient() returns GP.SparseGradient() (+ the prior's).  optimize.lbfgs and optimize.Adam.Step
+    then maximise the bound over x = log theta.  As with LOOModel the batched line search is not offered: the GP is
+    ``gp`` here, not ``GP``."""
+
+    def __init__(self, gp: GP, Priors=None):
+        self.gp = gp
+        self.Priors = Priors
+        self._x = None
+
+    def Observe(self, x) -> float:
+        self._x = _arr(x).reshape(-1).copy()
+        if self._x.size != self.gp._ns + self.gp._nn:
+            raise ValueError("len(x): the sparse objective takes the hyperparameters only")
+        v = self.gp.SparseObserve(self._x)
+        return v + self.Priors.Observe(self._x) if self.Priors is not None else v
+
+    def Gradient(self) -> np.ndarray:
+        g = self.gp.SparseGradient()
         if self.Priors is not None:
             self.Priors.Observe(self._x)
             pg = np.asarray(self.Priors.Gradient(), dtype=float)

@@ -229,6 +229,38 @@ class GP {
                               sigma.data()) == GOGP_OK;
   }
 
+  // Sparse (gogp_sparse_*): the collapsed variational bound of Titsias (2009) for N observations on M <=
+  // GOGP_SPARSE_MAX_M inducing points, O(N M^2); no reference counterpart.  SetSparse: a data set of its own (x row-major
+  // N x NDim, y, u row-major M x NDim), resident on the device beside X / Y, which it does not touch; M == 0 clears it.
+  void SetSparse(const std::vector<double> &x, const std::vector<double> &y, const std::vector<double> &u) {
+    if (u.empty()) {
+      check(gogp_sparse_set_data(h_, nullptr, nullptr, 0, nullptr, 0));
+      return;
+    }
+    if (x.size() != y.size() * (size_t)NDim || u.size() % (size_t)NDim) throw Error(GOGP_EARG, "len(x), len(u)");
+    check(gogp_sparse_set_data(h_, y.empty() ? nullptr : x.data(), y.empty() ? nullptr : y.data(), (int64_t)y.size(), u.data(),
+                               (int64_t)(u.size() / (size_t)NDim)));
+  }
+  // the bound at x = log theta
+  double SparseObserve(const std::vector<double> &x) {
+    double bound = 0.0;
+    check(gogp_sparse_observe(h_, x.data(), (int64_t)x.size(), &bound));
+    return bound;
+  }
+  // d bound / d log theta at the parameters of the last SparseObserve
+  std::vector<double> SparseGradient() {
+    std::vector<double> g(ThetaSimil.size() + ThetaNoise.size(), 0.0);
+    check(gogp_sparse_gradient(h_, g.data(), (int64_t)g.size()));
+    return g;
+  }
+  // mu and sigma of the sparse approximation at the test points (latent, unclamped, as Produce)
+  bool SparseProduce(const std::vector<std::vector<double>> &x, std::vector<double> &mu, std::vector<double> &sigma) {
+    std::vector<double> flat = pack(x);
+    mu.assign(x.size(), 0.0);
+    sigma.assign(x.size(), 0.0);
+    return gogp_sparse_produce(h_, flat.data(), (int64_t)x.size(), mu.data(), sigma.data()) == GOGP_OK;
+  }
+
   // ns = xi.size() / x.size() joint draws mu + C xi[s] (row-major ns x x.size()) from the caller's standard normals,
   // C the lower Cholesky factor of the covariance + diag_add I; no reference counterpart
   bool Sample(const std::vector<std::vector<double>> &x, const std::vector<double> &xi, double diag_add,

@@ -269,6 +269,46 @@ int gogp_multi_gradient(gogp_handle *h, double *grad, int64_t len /* P */);
 int gogp_multi_get_alpha(gogp_handle *h, double *A /* n x T row-major */);
 int gogp_multi_produce(gogp_handle *h, const double *Z, int64_t m, double *mu /* m x T */, double *sigma /* m */);
 
+/* Sparse (inducing-point) approximation: the collapsed variational bound of Titsias (2009) for N observations (X, y) on
+ * M <= GOGP_SPARSE_MAX_M inducing points U, with the handle's kernel; no reference counterpart.  It costs O(N M^2) and
+ * O(M^2 + chunk M) device memory instead of O(N^3) and O(N^2), is a lower bound of the exact LML and equals it for
+ * U = X.  With k the similarity at theta, s2 the noise variance, eps the jitter:
+ *     Kuu = k(U, U) + eps I = L L^T,  V = L^-1 k(U, X),  B = I + V V^T / s2,  r = V y,  g = B^-1 r,  t0 = sum_f k(x_f, x_f),
+ *     bound = -N/2 log 2 pi - 1/2 log|B| - N/2 log s2 - y^T y / (2 s2) + r^T g / (2 s2^2) - (t0 - s2 (tr B - M)) / (2 s2),
+ *     mu(z) = v^T g / s2,   sigma(z)^2 = k(z, z) - |v|^2 + v^T B^-1 v,   v = L^-1 k(U, z)
+ * (latent and unclamped, as gogp_produce).  DESIGN.md section 4, "Sparse", has the gradient.
+ * gogp_sparse_set_data copies X (N x D), y and U (M x D) to the device, where they stay: a data set of its own, as the
+ * batch data is.  N == 0 is legal; M == 0 with U == NULL clears it.  gogp_sparse_observe evaluates the bound at
+ * x = log theta (len == P, the handle's parameters); gogp_sparse_gradient its derivative in log theta at the parameters
+ * of the last gogp_sparse_observe; gogp_sparse_produce the predictive mean and standard deviation at m test points (m == 0
+ * is OK).  N == 0: bound 0, zero gradient, mu = 0, sigma = sqrt(prior).
+ * The data goes through in chunks of option "sparse_chunk" rows, twice for the gradient; nothing of size N^2 is
+ * allocated and nothing is copied from the host inside observe or gradient.  The handle's own data, factor, K^-1, batch
+ * data, candidates arena and multi-output state are not touched: a gogp_produce or gogp_gradient made afterwards returns
+ * the bits it would have returned without these calls, and the sparse data survives a gogp_set_data.  Two identical call
+ * sequences return identical bits (fixed-order sums, no atomics); results across chunk sizes agree to rounding only.
+ * GOGP_EARG: NULL pointers or non-finite values, M outside 1 .. GOGP_SPARSE_MAX_M, len != P, a precision = 32 handle, a
+ * sharded handle, a handle with event discounts set (events are out of scope here).  GOGP_ESTATE: any call before
+ * gogp_sparse_set_data; gradient or produce before observe.  GOGP_ENOTPD: Kuu + eps I has a non-positive pivot -- the
+ * bound is NaN and gogp_notpd_index is the inducing point (B >= I never fails).  GOGP_ECOND: (max L_ii / min L_ii)^2 of
+ * Kuu's factor exceeds the handle's limit; the values are still returned, as in gogp_absorb.
+ * Options: "sparse_jitter_log10" -14 .. -2 (default -8): eps = 10^value, absolute; "sparse_chunk" a multiple of 256 in
+ * 256 .. 65536 (default 8192).
+ * Device memory: X and y, eight Mp x Mp fp64 matrices (Mp = M rounded up to 256; 1.1 GB at M = 4096), a dense handle for
+ * the M inducing points and two chunk x Mp matrices (2 x 268 MB at the defaults and M = 4096).
+ * Cost, measured on one MI355X (profiles/sparse.txt; D = 8, default options, medians, every call ending in a synchronise):
+ * gogp_sparse_observe / observe + gradient at N = 65536: 14.1 / 15.5 ms (M = 512), 23.9 / 35.0 ms (M = 2048), 72.1 /
+ * 115.2 ms (M = 4096); N = 262144: 53.7 / 58.7, 87.1 / 126.9, 257.4 / 403.0 ms; N = 1048576: 212.1 / 231.1, 339.1 / 491.9,
+ * 999.6 / 1552.9 ms; gogp_sparse_produce of 1024 points 0.2 - 1.3 ms.  At N = 16384, M = 4096 observe + gradient takes
+ * 43.0 ms beside 71.3 ms for the dense gogp_observe + gogp_gradient (bound -10664.90 beside the LML -10662.82).  The new
+ * SYRK runs well below the tile kernel: 27.6 against 60.9 TFLOP/s for GEMM_LOWER at M = 4096, K = 8192 (20.4 against 45.8
+ * at M = 2048, 1.6 against 7.9 at M = 512); it is not tuned. */
+#define GOGP_SPARSE_MAX_M 4096
+int gogp_sparse_set_data(gogp_handle *h, const double *X, const double *y, int64_t N, const double *U, int64_t M);
+int gogp_sparse_observe(gogp_handle *h, const double *x /* log theta */, int64_t len /* P */, double *bound);
+int gogp_sparse_gradient(gogp_handle *h, double *grad, int64_t len /* P */);
+int gogp_sparse_produce(gogp_handle *h, const double *Z, int64_t m, double *mu, double *sigma);
+
 /* k independent Observe + Gradient evaluations at once: handle hs[i] (each created and given
  * its data separately; they may hold the same data) evaluates x[i*len .. (i+1)*len) from its own
  * host thread, so the dependent launch chains of the k evaluations overlap on the GPU.
@@ -623,6 +663,8 @@ int gogp_profile_read_aux(gogp_handle *h, int cls, double *ms, int64_t *launches
  *   "produce_small_max" 0..64   gogp_produce with up to this many test points (fp32 path: up to 16 of them): ONE
  *                          persistent launch that reads the factor once (trsm_small.hip; float factors are widened in
  *                          registers, the sums are fp64) instead of the tile-kernel chain; 0: never  (default 64)
+ *   "sparse_jitter_log10" -14..-2   gogp_sparse_*: eps = 10^value (absolute) on the diagonal of Kuu (default -8)
+ *   "sparse_chunk" 256..65536, a multiple of 256   gogp_sparse_*: rows of X per pass         (default 8192)
  * No reference counterpart (gp.GP.Parallel, gp/gp.go:30-31, only switches goroutines on). */
 int gogp_set_option(gogp_handle *h, const char *name, int64_t value);
 

@@ -248,11 +248,28 @@ int gogp_test_pcov(int device, const gogp_test_kparams *kparams, int ev, const d
 int gogp_test_multi_weight(int device, const double *At, int64_t at_len, int64_t ld, int T, const double *Kinv,
                            int64_t kinv_len, int64_t ldk, int64_t n, int64_t npad, double *G, int64_t g_len);
 
+/* launch_sparse_syrk (sparse.hip): Bacc (in / out; Mp rows of ldb) += Vt^T Vt on the whole lower 64 x 64 tiles of Mp x Mp and
+ * r (in / out; Mp doubles) += Vt^T y.  Vt: `rows` (1 .. 65536) rows of ld doubles, Mp columns read, of which the columns
+ * >= M count as exact zeros; Mp a multiple of 64 up to GOGP_SPARSE_MAX_M, 1 <= M <= Mp. */
+int gogp_test_sparse_syrk(int device, const double *Vt, int64_t vt_len, int64_t ld, int64_t rows, int64_t M, int64_t Mp,
+                          const double *y, int64_t y_len, double *Bacc, int64_t b_len, int64_t ldb, double *r, int64_t r_len);
+/* launch_sparse_grad (sparse.hip): out (in / out; GOGP_TEST_NACC slot sums; `accumulate`: added to what it holds) =
+ * sum_{f < rows, u < M} (Wt[f][u] + y_f mvec_u s4) dk(x_f, u_u) / dlog theta.  X: rows x ndim, U: M x ndim, Wt: rows rows of
+ * ldw >= M doubles; no event discounts. */
+int gogp_test_sparse_grad(int device, const gogp_test_kparams *kparams, const double *X, int64_t x_len, int64_t rows,
+                          const double *U, int64_t u_len, int64_t M, const double *Wt, int64_t wt_len, int64_t ldw,
+                          const double *y, int64_t y_len, const double *mvec, int64_t m_len, double s4, int accumulate,
+                          double *out /* GOGP_TEST_NACC */);
+
 /* Benchmark hook for the tile kernel: `reps` launches of one shape (mode 0 RECT
  * mt x nt tiles, 1 LOWER mt x mt, 2 LAUUM mt x mt with K = mt*128) on device
  * buffers; returns ms per launch and TFLOP/s on the flops launched. */
 int gogp_bench_gemm(int device, int mode, int mt, int nt, int64_t K, int reps,
                     double *ms_per_launch, double *tflops);
+
+/* Benchmark hook for sparse_syrk_kernel (sparse.hip): `reps` launches on device buffers, Vt rows x Mp with Mp = M rounded up to
+ * 256; returns ms per launch and TFLOP/s on the flops of the lower 64-tiles. */
+int gogp_bench_sparse_syrk(int device, int64_t rows, int64_t M, int reps, double *ms_per_launch, double *tflops);
 
 /* Diagnostic hook for the diagonal-block kernel: factor + invert one 256x256 SPD
  * block given on the host (row-major, lower triangle used); returns the factor,
