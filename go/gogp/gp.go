@@ -82,6 +82,7 @@ type GP struct {
 	// in-place edits of the same backing arrays must call Touch().
 	dirty      bool
 	nout       int // output columns of SetOutputs
+	sparseM    int // inducing points of SetSparse
 	upX        *[]float64 // &gp.X[0] at the time of the last upload
 	upY        *float64   // &gp.Y[0] at the time of the last upload
 	upN        int
@@ -511,13 +512,18 @@ func (gp *GP) MultiProduce(x [][]float64) (mu, sigma []float64, err error) {
 // which they do not touch.  An empty u clears them.
 func (gp *GP) SetSparse(x, y, u []float64) error {
 	gp.defaults()
+	gp.sparseM = 0
 	if len(u) == 0 {
 		return gp.err(C.gogp_sparse_set_data(gp.handle(), nil, nil, 0, nil, 0))
 	}
 	if len(x) != len(y)*gp.NDim || len(u)%gp.NDim != 0 {
 		return fmt.Errorf("len(x), len(u)")
 	}
-	return gp.err(C.gogp_sparse_set_data(gp.handle(), dptr(x), dptr(y), C.int64_t(len(y)), dptr(u), C.int64_t(len(u)/gp.NDim)))
+	if err := gp.err(C.gogp_sparse_set_data(gp.handle(), dptr(x), dptr(y), C.int64_t(len(y)), dptr(u), C.int64_t(len(u)/gp.NDim))); err != nil {
+		return err
+	}
+	gp.sparseM = len(u) / gp.NDim
+	return nil
 }
 
 // SparseObserve computes the collapsed variational bound of Titsias (2009) of
@@ -541,6 +547,33 @@ func (gp *GP) SparseGradient() ([]float64, error) {
 		return nil, err
 	}
 	return g, nil
+}
+
+// SetInducing replaces the inducing points of SetSparse by u (row-major
+// M x NDim, the same M) and nothing else: x, y and every device buffer stay.
+// SparseObserve has to follow before a gradient or a forecast.
+func (gp *GP) SetInducing(u []float64) error {
+	gp.defaults()
+	if len(u) == 0 || len(u)%gp.NDim != 0 {
+		return fmt.Errorf("len(u)")
+	}
+	return gp.err(C.gogp_sparse_set_inducing(gp.handle(), dptr(u), C.int64_t(len(u)/gp.NDim)))
+}
+
+// SparseGradientInducing computes SparseGradient and, from the same pass over
+// the data, the derivative of the bound in the inducing points of SetSparse
+// (row-major M x NDim).
+func (gp *GP) SparseGradientInducing() (grad, dU []float64, err error) {
+	gp.defaults()
+	if gp.sparseM < 1 {
+		return nil, nil, fmt.Errorf("SparseGradientInducing before SetSparse")
+	}
+	grad = make([]float64, len(gp.ThetaSimil)+len(gp.ThetaNoise))
+	dU = make([]float64, gp.sparseM*gp.NDim)
+	if err = gp.err(C.gogp_sparse_gradient_inducing(gp.handle(), dptr(grad), C.int64_t(len(grad)), dptr(dU))); err != nil {
+		return nil, nil, err
+	}
+	return grad, dU, nil
 }
 
 // SparseProduce computes the predictive mean and standard deviation of the

@@ -96,6 +96,8 @@ SYMBOLS = [
     ("gogp_sparse_observe", ctypes.c_int, [_h, _dp, _i64, _dp]),
     ("gogp_sparse_gradient", ctypes.c_int, [_h, _dp, _i64]),
     ("gogp_sparse_produce", ctypes.c_int, [_h, _dp, _i64, _dp, _dp]),
+    ("gogp_sparse_set_inducing", ctypes.c_int, [_h, _dp, _i64]),
+    ("gogp_sparse_gradient_inducing", ctypes.c_int, [_h, _dp, _i64, _dp]),
     ("gogp_observe_gradient_batch", ctypes.c_int,
      [ctypes.POINTER(_h), ctypes.c_int, _dp, _i64, _dp, _dp, ctypes.POINTER(ctypes.c_int)]),
     ("gogp_observe_gradient_candidates", ctypes.c_int,
@@ -227,6 +229,11 @@ HOOK_SYMBOLS = [
     ("gogp_test_sparse_grad", ctypes.c_int,
      [ctypes.c_int, ctypes.POINTER(CKParams), _dp, _i64, _i64, _dp, _i64, _i64, _dp, _i64, _i64, _dp, _i64, _dp, _i64,
       ctypes.c_double, ctypes.c_int, _dp]),
+    ("gogp_test_sparse_ugrad", ctypes.c_int,
+     [ctypes.c_int, ctypes.POINTER(CKParams), _dp, _i64, _i64, _dp, _i64, _i64, _dp, _i64, _i64, _dp, _i64, _dp, _i64,
+      ctypes.c_double, ctypes.c_int, _dp, _i64]),
+    ("gogp_test_sparse_ugrad_slabs", ctypes.c_int, [_i64, _i64, ctypes.POINTER(ctypes.c_int)]),
+    ("gogp_test_sparse_ugrad_slabs_bound", ctypes.c_int, [_i64, _i64]),
     # per-rank replay of the sharded sweep (tools/sharded_replay.py): a transport that reads recorded panels
     ("gogp_test_dist_init_replay", ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int] * 4),
 ]

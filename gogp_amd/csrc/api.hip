@@ -2947,6 +2947,7 @@ static void sparse_free(gogp_handle *h) {
   h->sp_X = h->sp_y = nullptr;
   h->sp_ws.release();
   h->sp_vec.release();
+  h->sp_ug.release();
   h->sp_N = h->sp_M = 0;
   h->sp_have = h->sp_observed = false;
 }
@@ -3153,22 +3154,38 @@ extern "C" int gogp_sparse_observe(gogp_handle *h, const double *x, int64_t len,
   return rcond;
 }
 
-extern "C" int gogp_sparse_gradient(gogp_handle *h, double *grad, int64_t len) {
-  if (!h || !grad) return fail(h, GOGP_EARG, "sparse_gradient: NULL");
-  if (sparse_refusal(h)) return sparse_refuse(h, "sparse_gradient");
-  if (len != h->P) return fail(h, GOGP_EARG, "sparse_gradient: wrong length");
-  if (!h->sp_have) return fail(h, GOGP_ESTATE, "sparse_gradient: no sparse data (gogp_sparse_set_data)");
-  if (!h->sp_observed) return fail(h, GOGP_ESTATE, "sparse_gradient before sparse_observe");
+// gogp_sparse_gradient (dU == nullptr) and gogp_sparse_gradient_inducing: with dU, the second pass over the data also
+// reduces the (U, X) pairs on dk/du (launch_sparse_ugrad: the chunk's Wt, mvec, y and s4 of launch_sparse_grad) and
+// the (U, U) pairs go through the input-gradient reduction of the full Observe form (launch_xgrad) with a zero alpha
+// and -G as its K^-1:  dU = 2 (U, U part) + (U, X part) -- u_a enters Kuu through row a and column a.
+static int sparse_gradient_impl(gogp_handle *h, const char *who, double *grad, int64_t len, double *dU) {
+  auto msg = [&](const char *what) { return std::string(who) + what; };
+  if (sparse_refusal(h)) return sparse_refuse(h, who);
+  if (len != h->P) return fail(h, GOGP_EARG, msg(": wrong length").c_str());
+  if (!h->sp_have) return fail(h, GOGP_ESTATE, msg(": no sparse data (gogp_sparse_set_data)").c_str());
+  if (!h->sp_observed) return fail(h, GOGP_ESTATE, msg(" before sparse_observe").c_str());
   for (int64_t i = 0; i < len; ++i) grad[i] = 0.0;
   const int64_t N = h->sp_N, M = h->sp_M, Mp = sparse_mp(h);
+  const int64_t md = M * h->D;
+  if (dU)
+    for (int64_t i = 0; i < md; ++i) dU[i] = 0.0;
   if (N == 0) return GOGP_OK;
   HIPCHK(h, hipSetDevice(h->device));
   gogp_handle *ind = h->sp_ind;
   SparseBufs b;
   sparse_layout(h->sp_ws.as<double>(), Mp, &b);
   hipStream_t s = ind->s;
+  const int64_t chunk = std::min(h->sp_chunk, ((N + TILE - 1) / TILE) * TILE);
+  double *upart = nullptr, *dux = nullptr, *duu = nullptr;  // the slab partials, the (U, X) and the (U, U) part
+  if (dU) {
+    // (the bound over every chunk length up to `chunk`: a ragged last chunk may take more slabs than a full one)
+    const size_t np = (size_t)sparse_ugrad_slabs_bound(chunk, M) * (size_t)md;
+    const int rcw = h->sp_ug.reserve(h, (np + 2 * (size_t)md) * sizeof(double));
+    if (rcw != GOGP_OK) return rcw;
+    upart = h->sp_ug.as<double>(), dux = upart + np, duu = dux + md;
+  }
   int rc = compute_kinv(ind);  // Y = L^-T of the inducing process in its bufY, the main stream behind it
-  if (rc != GOGP_OK) return sparse_fail_from(h, "sparse_gradient", rc);
+  if (rc != GOGP_OK) return sparse_fail_from(h, who, rc);
   const double s2 = h->sp_s2, s4 = 1.0 / (s2 * s2);
   // (the upper triangle of the inducing process's bufY: what lies below its super-panels is not part of Y)
   launch_sparse_copy_upper(s, ind->bufY, Mp, b.Yu);
@@ -3185,10 +3202,11 @@ extern "C" int gogp_sparse_gradient(gogp_handle *h, double *grad, int64_t len) {
   launch_rownorm_dot(s, Yu, Mp, b.g, Mp, M, b.mvec, nullptr);
   launch_grad_reduce(s, ind->devP, ind->D, ind->ard_dims, ind->dX, b.zero, (const double *)b.Gm, Mp, M, Mp, ind->gpart,
                      ind->gout, ind->radial1, ind->ard_mfma_min, false);
+  // (launch_xgrad mirrors its matrix in place: behind the reduction that has read Gm)
+  if (dU) launch_xgrad(s, ind->devP, ind->D, ind->dX, b.zero, b.Gm, Mp, M, Mp, duu, false);
   // second pass over the data: the chunk's cross-covariance again, Wt = Ks^T 2 P, the pair reduction
-  const int64_t chunk = std::min(h->sp_chunk, ((N + TILE - 1) / TILE) * TILE);
   rc = ensure_m(ind, chunk, chunk);
-  if (rc != GOGP_OK) return sparse_fail_from(h, "sparse_gradient", rc);
+  if (rc != GOGP_OK) return sparse_fail_from(h, who, rc);
   GemmGrid gw;
   gw.small_below = ind->produce_small_below;
   for (int64_t f0 = 0; f0 < N; f0 += chunk) {
@@ -3198,12 +3216,23 @@ extern "C" int gogp_sparse_gradient(gogp_handle *h, double *grad, int64_t len) {
                    0.0, ind->Vt, Mp, nullptr, &gw);
     launch_sparse_grad(s, ind->devP, ind->D, ind->ard_dims, h->sp_X + f0 * ind->D, m, ind->dX, M, ind->Vt, Mp, h->sp_y + f0,
                        b.mvec, s4, b.gpart, b.gsum, f0 > 0);
+    if (dU)
+      launch_sparse_ugrad(s, ind->devP, ind->D, h->sp_X + f0 * ind->D, m, ind->dX, M, ind->Vt, Mp, h->sp_y + f0, b.mvec, s4,
+                          upart, dux, f0 > 0);
   }
   double acc[NACC], accu[NACC];
+  std::vector<double> hu;
   HIPCHK(h, hipMemcpyAsync(acc, b.gsum, sizeof acc, hipMemcpyDeviceToHost, s));
   HIPCHK(h, hipMemcpyAsync(accu, ind->gout, sizeof accu, hipMemcpyDeviceToHost, s));
+  if (dU) {
+    hu.resize((size_t)md);
+    HIPCHK(h, hipMemcpyAsync(dU, dux, (size_t)md * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(hu.data(), duu, (size_t)md * sizeof(double), hipMemcpyDeviceToHost, s));
+  }
   HIPCHK(h, hipStreamSynchronize(s));
   HIPCHK(h, hipGetLastError());
+  if (dU)
+    for (int64_t i = 0; i < md; ++i) dU[i] = 2.0 * hu[(size_t)i] + dU[i];
   // assemble_gradient halves the slot sums (the LML's 1/2 tr): (W, dKuf) + (G, dKuu) go in doubled
   for (int q = 0; q < NACC; ++q) acc[q] = 2.0 * (acc[q] + accu[q]);
   acc[ACC_TRACE] = 0.0;
@@ -3219,6 +3248,33 @@ extern "C" int gogp_sparse_gradient(gogp_handle *h, double *grad, int64_t len) {
     grad[h->ns] = h->sp_dnoise * dF;
   }
   return GOGP_OK;
+}
+
+extern "C" int gogp_sparse_gradient(gogp_handle *h, double *grad, int64_t len) {
+  if (!h || !grad) return fail(h, GOGP_EARG, "sparse_gradient: NULL");
+  return sparse_gradient_impl(h, "sparse_gradient", grad, len, nullptr);
+}
+
+extern "C" int gogp_sparse_gradient_inducing(gogp_handle *h, double *grad, int64_t len, double *dU) {
+  if (!h || !grad || !dU) return fail(h, GOGP_EARG, "sparse_gradient_inducing: NULL");
+  return sparse_gradient_impl(h, "sparse_gradient_inducing", grad, len, dU);
+}
+
+// The inducing points alone: the inducing process is given (U, y = 0) again -- its buffers are sized by M, which stays --
+// and X, y, the workspaces and the options are kept.
+extern "C" int gogp_sparse_set_inducing(gogp_handle *h, const double *U, int64_t M) {
+  if (!h) return GOGP_EARG;
+  if (sparse_refusal(h)) return sparse_refuse(h, "sparse_set_inducing");
+  if (!U) return fail(h, GOGP_EARG, "sparse_set_inducing: NULL");
+  if (!h->sp_have) return fail(h, GOGP_ESTATE, "sparse_set_inducing: no sparse data (gogp_sparse_set_data)");
+  if (M != h->sp_M) return fail(h, GOGP_EARG, "sparse_set_inducing: M differs from the M of gogp_sparse_set_data");
+  for (int64_t i = 0; i < M * h->D; ++i)
+    if (!std::isfinite(U[i])) return fail(h, GOGP_EARG, "sparse_set_inducing: non-finite inducing point");
+  HIPCHK(h, hipSetDevice(h->device));
+  h->sp_observed = false;
+  std::vector<double> y0((size_t)M, 0.0);
+  const int rc = gogp_set_data(h->sp_ind, U, y0.data(), M);
+  return rc == GOGP_OK ? rc : sparse_fail_from(h, "sparse_set_inducing", rc);
 }
 
 extern "C" int gogp_sparse_produce(gogp_handle *h, const double *Z, int64_t m, double *mu, double *sigma) {

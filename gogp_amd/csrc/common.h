@@ -456,6 +456,14 @@ int sparse_grad_blocks(int64_t rows, int64_t M);
 void launch_sparse_grad(hipStream_t s, const DevParams *p, int ndim, int ard_dims, const double *X, int64_t rows,
                         const double *U, int64_t M, const double *Wt, int64_t ldw, const double *y, const double *mvec,
                         double s4, double *partials, double *out, bool accumulate);
+// launch_sparse_ugrad: dU (M x ndim; `accumulate`: added to what it holds) = sum_{f < rows} (Wt[f][u] + y_f mvec_u s4)
+// dk(u_u, x_f)/du_u, the arguments of launch_sparse_grad; part: sparse_ugrad_slabs(rows, M) * M * ndim doubles of scratch
+// (shared by launches of up to `rows` rows: sparse_ugrad_slabs_bound(rows, M) * M * ndim).
+int sparse_ugrad_slabs(int64_t rows, int64_t M, int *tps_out);  // slabs of row tiles and the 64-row tiles of one
+int sparse_ugrad_slabs_bound(int64_t rows, int64_t M);  // >= sparse_ugrad_slabs(r, M) for every r <= rows (it is not monotone)
+void launch_sparse_ugrad(hipStream_t s, const DevParams *p, int ndim, const double *X, int64_t rows, const double *U,
+                         int64_t M, const double *Wt, int64_t ldw, const double *y, const double *mvec, double s4,
+                         double *part, double *dU, bool accumulate);
 void launch_sparse_finish_b(hipStream_t s, const double *Bacc, int64_t Mp, double inv_s2, double *B);
 void launch_sparse_copy_upper(hipStream_t s, const double *src, int64_t Mp, double *dst);  // zeros below the diagonal
 void launch_sparse_weights(hipStream_t s, const double *B, const double *Binv, const double *g, int64_t Mp, double s4,

@@ -234,6 +234,7 @@ struct gogp_handle : EvalBufs, EvalState {
   int64_t sp_chunk = 8192;         // option "sparse_chunk": rows of X per pass
   Workspace sp_ws;                 // the Mp x Mp matrices, block inverses, vectors and slot sums (api.hip: sparse_layout)
   Workspace sp_vec;                // gogp_sparse_produce: one dot product per test point
+  Workspace sp_ug;                 // gogp_sparse_gradient_inducing: the slab partials of launch_sparse_ugrad and two M x D arrays
   double sp_yty = 0.0;             // y^T y of the sparse data
   double sp_s2 = 0.0, sp_dnoise = 0.0, sp_csum = 0.0;  // of the last gogp_sparse_observe: noise variance, its derivative, sum of the output scales
   double sp_scal[5] = {};          // ... and its scalars (sparse.hip: sparse_scalars_kernel)

@@ -4,13 +4,16 @@
 //     Kuu + eps I = L L^T,   V = L^-1 k(U, X)  (M x N),   B = I + V V^T / s2,   r = V y,   g = B^-1 r,
 //     F = -N/2 log 2 pi - 1/2 log|B| - N/2 log s2 - y^T y / (2 s2) + r^T g / (2 s2^2) - (t0 - s2 (tr B - M)) / (2 s2).
 // The data goes through in chunks of rows; a chunk's V^T (rows x Mp, row-major) is what Produce's forward substitution
-// leaves with the chunk's rows as test points.  Two kernels carry the O(N M^2) and O(N M) work:
+// leaves with the chunk's rows as test points.  Three kernels carry the O(N M^2) and O(N M) work:
 //   sparse_syrk_kernel   B_acc (lower 64-tiles of Mp x Mp) += Vt^T Vt and r += Vt^T y_chunk on v_mfma_f64_16x16x4_f64;
 //   sparse_grad_kernel   sum over (observation f, inducing point u) of (Wt[f][u] + y_f m_u / s2^2) dk(x_f, u_u)/dlog theta
-//                        into the NACC slot layout of common.h.
+//                        into the NACC slot layout of common.h;
+//   sparse_ugrad_kernel  the same pairs and weights on dk(u_u, x_f)/du_u: the (U, X) part of d bound / d U.
 // The rest are the element-wise passes over the M x M matrices and the M vectors.
 //
 // Every sum has a fixed order (no atomics): two identical calls give the same bits.
+#include <algorithm>
+
 #include "kern_eval.h"
 
 namespace gogp {
@@ -235,6 +238,148 @@ void launch_sparse_grad(hipStream_t s, const DevParams *p, int ndim, int ard_dim
     for (int a0 = 0; a0 < ard_dims; a0 += 8)
       sg_launch<8>(blocks, s, ndim, p, X, (long)rows, U, (long)M, Wt, (long)ldw, y, mvec, s4, ntc, ntiles, partials, a0);
   GOGP_KLAUNCH(sparse_grad_final_kernel, dim3(NACC), dim3(256), 0, s, partials, blocks, out, accumulate ? 1 : 0);
+}
+
+// ---- the derivative in the inducing points: the (U, X) pairs ---------------------------------------------------------
+// part[slab][u][d] = sum over the rows f of the slab's 64-row tiles of (Wt[f][u] + y_f m_u s4) dk(u_u, x_f)/du_ud,
+// f < rows, u < M, d0 <= d < min(D, d0 + DMAX).  Workgroup (column tile of 64 inducing points, slab of `tps` row tiles);
+// the thread (tx, ty) owns inducing point c0 + tx -- a wave reads a row of Wt along its 64 lanes -- and the rows
+// 16 ty .. 16 ty + 15 of every tile, through simil_xgrad_accum with xa = the inducing point.  The U tile is staged once,
+// transposed ([D][64]: the lanes read consecutive doubles), the X tile [64][D] per row tile (a wave reads one address).
+// The four ty sums are added through LDS, which takes the place of the tiles once they are read, as
+// ((ty 0 + ty 1) + ty 2) + ty 3; sparse_ugrad_final_kernel adds the slabs in index order.  No atomics.
+constexpr int SU_TPS_MIN = 4;  // row tiles per slab at least: one staging of the U tile and one row of partials per 256 rows
+
+template <int DMAX>
+__global__ __launch_bounds__(256) void sparse_ugrad_kernel(const DevParams *__restrict__ Pp, const double *__restrict__ X,
+                                                           long rows, const double *__restrict__ U, long M,
+                                                           const double *__restrict__ Wt, long ldw,
+                                                           const double *__restrict__ y, const double *__restrict__ mvec,
+                                                           double s4, int tps, double *__restrict__ part, int d0) {
+  extern __shared__ double sm[];
+  const DevParams &P = *Pp;
+  const int D = P.ndim;
+  double *Xi = sm;             // [64][D]
+  double *UjT = sm + 64 * D;   // [D][64]
+  double *yi = UjT + 64 * D;   // [64]
+  double *red = sm;            // [3][DMAX][64], after the last tile
+  const int tid = threadIdx.x;
+  const int tx = tid & 63, ty = tid >> 6;
+  const long c0 = (long)blockIdx.x * 64, gj = c0 + tx;
+  const bool live = gj < M;
+  const int ntr = (int)((rows + 63) / 64);
+  const int t0 = (int)blockIdx.y * tps, t1 = t0 + tps < ntr ? t0 + tps : ntr;
+
+  for (int idx = tid; idx < 64 * D; idx += 256) {
+    const int d = idx >> 6, r = idx & 63;
+    UjT[idx] = (c0 + r < M) ? U[(c0 + r) * D + d] : 0.0;
+  }
+  const double mjv = live ? mvec[gj] * s4 : 0.0;
+  // (from dimension d0: the pass's own coordinates lie at constant offsets -- as uj[d * 64], d = d0 + q, hipcc keeps the
+  // 16 offsets of an instance in SGPRs across the pair loop and spills them)
+  const double *uj = UjT + d0 * 64 + tx;
+  // per-thread addresses (in VGPRs: the kernel's arguments need not stay live in SGPRs across the pair loop)
+  const double *wp = Wt + (long)t0 * 64 * ldw + (ty * 16) * ldw + gj;  // row 16 ty of the tile, column gj
+  double *pp = part + ((long)blockIdx.y * M + gj) * D + d0;
+  double acc[DMAX];
+#pragma unroll
+  for (int q = 0; q < DMAX; ++q) acc[q] = 0.0;
+
+  for (int t = t0; t < t1; ++t, wp += 64 * ldw) {
+    const long r0 = (long)t * 64;
+    const int nr = rows - r0 < 64 ? (int)(rows - r0) : 64;  // live rows of the tile
+    __syncthreads();  // previous tile's readers are done
+    for (int idx = tid; idx < 64 * D; idx += 256) Xi[idx] = (idx < nr * D) ? X[r0 * D + idx] : 0.0;
+    if (tid < 64) yi[tid] = (tid < nr) ? y[r0 + tid] : 0.0;
+    __syncthreads();
+    if (live) {
+      const int rend = nr - ty * 16 < 16 ? nr - ty * 16 : 16;
+      const double *xi = Xi + (ty * 16) * D;
+      const double *w = wp;
+      for (int rr = 0; rr < rend; ++rr, xi += D, w += ldw) {
+        const double wgt = *w + yi[ty * 16 + rr] * mjv;
+        simil_xgrad_accum<DMAX>(
+            P, [&](int d) { return uj[(d - d0) * 64]; }, [&](int d) { return xi[d]; }, wgt, acc, d0);
+      }
+    }
+  }
+
+  __syncthreads();  // the tiles are read: their place takes the sums
+  if (ty > 0) {
+#pragma unroll
+    for (int q = 0; q < DMAX; ++q) red[((ty - 1) * DMAX + q) * 64 + tx] = acc[q];
+  }
+  __syncthreads();
+  if (ty == 0 && live) {
+#pragma unroll
+    for (int q = 0; q < DMAX; ++q)
+      if (d0 + q < D)
+        pp[q] = ((acc[q] + red[q * 64 + tx]) + red[(DMAX + q) * 64 + tx]) + red[(2 * DMAX + q) * 64 + tx];
+  }
+}
+
+// dU[u][d] (+)= the slabs' sums in index order
+__global__ __launch_bounds__(256) void sparse_ugrad_final_kernel(const double *__restrict__ part, int nslab, long md,
+                                                                 double *__restrict__ dU, int accumulate) {
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= md) return;
+  double v = 0.0;
+  for (int sl = 0; sl < nslab; ++sl) v += part[(long)sl * md + idx];
+  dU[idx] = accumulate ? dU[idx] + v : v;
+}
+
+// The slabs of launch_sparse_ugrad and the row tiles of one (*tps_out): a function of (rows, M) alone.  The grid
+// (column tiles x slabs) stays within SPARSE_GRAD_BLOCKS_MAX workgroups, as sparse_grad_blocks caps its own.
+int sparse_ugrad_slabs(int64_t rows, int64_t M, int *tps_out) {
+  const int64_t ntr = (rows + 63) / 64, ntc = (M + 63) / 64;
+  const int64_t most = std::max<int64_t>(1, SPARSE_GRAD_BLOCKS_MAX / std::max<int64_t>(1, ntc));
+  const int64_t tps = std::max<int64_t>(SU_TPS_MIN, (ntr + most - 1) / most);
+  if (tps_out) *tps_out = (int)tps;
+  return (int)std::max<int64_t>(1, (ntr + tps - 1) / tps);
+}
+
+// An upper bound of sparse_ugrad_slabs(r, M) over every r <= rows: what a buffer of partials shared by launches of up
+// to `rows` rows holds.  The slab count itself is not monotone in the rows: beyond SU_TPS_MIN * most row tiles the slabs
+// grow longer and their number falls, so a ragged last chunk may take more slabs than the full chunks before it.  With
+// tps == SU_TPS_MIN the count is ceil(ntr / SU_TPS_MIN) and ntr <= SU_TPS_MIN * most; with tps = ceil(ntr / most) it is
+// ceil(ntr / ceil(ntr / most)) <= most.
+int sparse_ugrad_slabs_bound(int64_t rows, int64_t M) {
+  const int64_t ntr = (rows + 63) / 64, ntc = (M + 63) / 64;
+  const int64_t most = std::max<int64_t>(1, SPARSE_GRAD_BLOCKS_MAX / std::max<int64_t>(1, ntc));
+  return (int)std::max<int64_t>(1, std::min<int64_t>((ntr + SU_TPS_MIN - 1) / SU_TPS_MIN, most));
+}
+
+template <int DM>
+static void su_launch(dim3 grid, hipStream_t s, int ndim, const DevParams *p, const double *X, long rows, const double *U,
+                      long M, const double *Wt, long ldw, const double *y, const double *mvec, double s4, int tps,
+                      double *part, int d0) {
+  auto doubles = [](int nd) { return (size_t)std::max(128 * nd + 64, 3 * DM * 64); };
+  const size_t lds = doubles(ndim) * sizeof(double);
+  if (lds > 64 * 1024)  // D = 64: raised explicitly, per launch (the attribute belongs to the function on the current device)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&sparse_ugrad_kernel<DM>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)(doubles(GOGP_MAX_NDIM) * sizeof(double)));
+  GOGP_KLAUNCH(sparse_ugrad_kernel<DM>, grid, dim3(256), lds, s, p, X, rows, U, M, Wt, ldw, y, mvec, s4, tps, part, d0);
+}
+
+void launch_sparse_ugrad(hipStream_t s, const DevParams *p, int ndim, const double *X, int64_t rows, const double *U,
+                         int64_t M, const double *Wt, int64_t ldw, const double *y, const double *mvec, double s4,
+                         double *part, double *dU, bool accumulate) {
+  if (rows <= 0 || M <= 0) return;
+  int tps = 1;
+  const int nslab = sparse_ugrad_slabs(rows, M, &tps);
+  const dim3 grid((unsigned)((M + 63) / 64), (unsigned)nslab);
+  // instances of 4 / 8 / 16 accumulators, passes of 16 beyond (launch_xgrad's event instances: inside the register
+  // limits of the code-object audit)
+#define GOGP_LAUNCH_SU(DM, D0) \
+  su_launch<DM>(grid, s, ndim, p, X, (long)rows, U, (long)M, Wt, (long)ldw, y, mvec, s4, tps, part, D0)
+  if (ndim <= 4) GOGP_LAUNCH_SU(4, 0);
+  else if (ndim <= 8) GOGP_LAUNCH_SU(8, 0);
+  else
+    for (int d0 = 0; d0 < ndim; d0 += 16) GOGP_LAUNCH_SU(16, d0);
+#undef GOGP_LAUNCH_SU
+  const long md = (long)M * ndim;
+  GOGP_KLAUNCH(sparse_ugrad_final_kernel, dim3((unsigned)((md + 255) / 256)), dim3(256), 0, s, part, nslab, md, dU,
+               accumulate ? 1 : 0);
 }
 
 // ---- element-wise passes over the Mp x Mp matrices ---------------------------------------------------------------------

@@ -1433,6 +1433,49 @@ extern "C" int gogp_test_sparse_grad(int device, const gogp_test_kparams *kparam
   return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
 }
 
+extern "C" int gogp_test_sparse_ugrad_slabs(int64_t rows, int64_t M, int *tiles_per_slab) {
+  if (rows < 1 || rows > (1 << 16) || M < 1 || M > GOGP_SPARSE_MAX_M) return 0;
+  return sparse_ugrad_slabs(rows, M, tiles_per_slab);
+}
+
+extern "C" int gogp_test_sparse_ugrad_slabs_bound(int64_t rows, int64_t M) {
+  if (rows < 1 || rows > (1 << 16) || M < 1 || M > GOGP_SPARSE_MAX_M) return 0;
+  return sparse_ugrad_slabs_bound(rows, M);
+}
+
+extern "C" int gogp_test_sparse_ugrad(int device, const gogp_test_kparams *kparams, const double *X, int64_t x_len, int64_t rows,
+                                      const double *U, int64_t u_len, int64_t M, const double *Wt, int64_t wt_len, int64_t ldw,
+                                      const double *y, int64_t y_len, const double *mvec, int64_t m_len, double s4,
+                                      int accumulate, double *dU, int64_t du_len) {
+  if (!kparams || !X || !U || !Wt || !y || !mvec || !dU) return GOGP_EARG;
+  if (!kparams_ok(kparams, 1, ard_dims_of(kparams), 0, 1, 0) || kparams->nevents != 0) return GOGP_EARG;
+  if (rows < 1 || rows > (1 << 16) || M < 1 || M > GOGP_SPARSE_MAX_M || !std::isfinite(s4)) return GOGP_EARG;
+  if (x_len < rows * kparams->ndim || u_len < M * kparams->ndim || y_len < rows || m_len < M || du_len < M * kparams->ndim)
+    return GOGP_EARG;
+  if (!covers(wt_len, 0, ldw, rows, M, 1, 0)) return GOGP_EARG;
+  if (!device_ok(device)) return GOGP_EHIP;
+  const DevParams hp = to_dev(*kparams);
+  DevCopy dP, dX, dUp, dW, dy, dm, dout;
+  double *part = nullptr;
+  hipError_t e = dP.up(&hp, sizeof hp);
+  if (e == hipSuccess) e = dX.up(X, (size_t)x_len * sizeof(double));
+  if (e == hipSuccess) e = dUp.up(U, (size_t)u_len * sizeof(double));
+  if (e == hipSuccess) e = dW.up(Wt, (size_t)wt_len * sizeof(double));
+  if (e == hipSuccess) e = dy.up(y, (size_t)y_len * sizeof(double));
+  if (e == hipSuccess) e = dm.up(mvec, (size_t)m_len * sizeof(double));
+  if (e == hipSuccess) e = dout.up(dU, (size_t)du_len * sizeof(double));
+  if (e == hipSuccess)
+    e = hipMalloc(&part, (size_t)sparse_ugrad_slabs(rows, M, nullptr) * (size_t)M * kparams->ndim * sizeof(double));
+  if (e == hipSuccess) {
+    launch_sparse_ugrad(0, dP.as<DevParams>(), kparams->ndim, dX.as<double>(), rows, dUp.as<double>(), M, dW.as<double>(), ldw,
+                        dy.as<double>(), dm.as<double>(), s4, part, dout.as<double>(), accumulate != 0);
+    e = launched();
+  }
+  if (e == hipSuccess) e = dout.down(dU);
+  (void)hipFree(part);
+  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+}
+
 // Benchmark hook for sparse_syrk_kernel: `reps` launches on device buffers (Vt: rows x Mp, Mp = M rounded up to 256);
 // ms per launch and TFLOP/s on the flops of the lower 64-tiles
 extern "C" int gogp_bench_sparse_syrk(int device, int64_t rows, int64_t M, int reps, double *ms_per_launch, double *tflops) {

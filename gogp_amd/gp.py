@@ -79,6 +79,7 @@ class GP:
         self.Parallel = Parallel
         #: HIP device index of the handle (-1: the device current at construction)
         self.device = int(device)
+        self._sparse_m = 0  # inducing points of SetSparse
         self._h = ctypes.c_void_p()
         L = _lib.lib()
         rc = L.gogp_create(ctypes.byref(self._desc), int(device), ctypes.byref(self._h))
@@ -447,6 +448,7 @@ class GP:
         L = _lib.lib()
         if U is None:
             self._check(L.gogp_sparse_set_data(self._h, None, None, 0, None, 0))
+            self._sparse_m = 0
             return
         u = np.ascontiguousarray(_arr(U).reshape(-1, self.NDim))
         x = np.ascontiguousarray(_arr(X).reshape(-1, self.NDim))
@@ -456,6 +458,14 @@ class GP:
         n = len(y)
         self._check(L.gogp_sparse_set_data(self._h, _dp(x) if n else None, _dp(y) if n else None, n,
                                            _dp(u if len(u) else np.zeros(1)), len(u)))
+        self._sparse_m = len(u)
+
+    def SetInducing(self, U) -> None:
+        """Replace the inducing points of SetSparse by U (M x NDim, the same M) and nothing else
+        (gogp_sparse_set_inducing): X, Y and every device buffer stay.  SparseObserve has to follow before a gradient
+        or a forecast."""
+        u = np.ascontiguousarray(_arr(U).reshape(-1, self.NDim))
+        self._check(_lib.lib().gogp_sparse_set_inducing(self._h, _dp(u if len(u) else np.zeros(1)), len(u)))
 
     def SparseObserve(self, x) -> float:
         """The collapsed variational bound of Titsias (2009) at x = log theta (gogp_sparse_observe): a lower bound of
@@ -470,6 +480,18 @@ class GP:
         g = np.zeros(self._ns + self._nn)
         self._check(_lib.lib().gogp_sparse_gradient(self._h, _dp(g if g.size else np.zeros(1)), g.size))
         return g
+
+    def SparseGradientInducing(self):
+        """(grad, dU): SparseGradient() and, from the same pass over the data, the derivative of the bound in the
+        inducing points, M x NDim (gogp_sparse_gradient_inducing).  Where Kuu is ill-conditioned (thousands of
+        inducing points at the default jitter of 1e-8) dU loses its digits before grad does: set option
+        "sparse_jitter_log10" to -6 or more to learn that many (include/gogp_hip.h has the measurements)."""
+        g = np.zeros(self._ns + self._nn)
+        if self._sparse_m < 1:  # (the library writes M x NDim doubles: never into a buffer sized without M)
+            raise GogpError(_lib.GOGP_ESTATE, "SparseGradientInducing before SetSparse")
+        du = np.zeros((self._sparse_m, self.NDim))
+        self._check(_lib.lib().gogp_sparse_gradient_inducing(self._h, _dp(g if g.size else np.zeros(1)), g.size, _dp(du)))
+        return g, du
 
     def SparseProduce(self, x):
         """(mu, sigma) of the sparse approximation at the test points, latent and unclamped as Produce
@@ -823,24 +845,40 @@ class SparseModel:
     """Model with the collapsed bound of GP.SetSparse in the place of the LML: Observe(x) returns GP.SparseObserve(x)
     (+ the log prior), Gradient() returns GP.SparseGradient() (+ the prior's).  optimize.lbfgs and optimize.Adam.Step
     then maximise the bound over x = log theta.  As with LOOModel the batched line search is not offered: the GP is
-    ``gp`` here, not ``GP``."""
+    ``gp`` here, not ``GP``.
 
-    def __init__(self, gp: GP, Priors=None):
+    ``inducing=True`` learns the inducing points too: x = [log theta (P) | U row-major (M * NDim)], with M of the last
+    GP.SetSparse.  Observe moves the inducing points (GP.SetInducing) and evaluates the bound, Gradient returns
+    GP.SparseGradientInducing()'s two parts in that order (the priors are on the hyperparameters alone)."""
+
+    def __init__(self, gp: GP, Priors=None, inducing=False):
         self.gp = gp
         self.Priors = Priors
+        self.inducing = bool(inducing)
         self._x = None
 
     def Observe(self, x) -> float:
         self._x = _arr(x).reshape(-1).copy()
-        if self._x.size != self.gp._ns + self.gp._nn:
+        p = self.gp._ns + self.gp._nn
+        if self.inducing:
+            m = self.gp._sparse_m
+            if self._x.size != p + m * self.gp.NDim:
+                raise ValueError("len(x): the sparse objective with inducing points takes the hyperparameters and "
+                                 "M x NDim coordinates")
+            self.gp.SetInducing(self._x[p:].reshape(m, self.gp.NDim))
+        elif self._x.size != p:
             raise ValueError("len(x): the sparse objective takes the hyperparameters only")
-        v = self.gp.SparseObserve(self._x)
-        return v + self.Priors.Observe(self._x) if self.Priors is not None else v
+        v = self.gp.SparseObserve(self._x[:p])
+        return v + self.Priors.Observe(self._x[:p]) if self.Priors is not None else v
 
     def Gradient(self) -> np.ndarray:
-        g = self.gp.SparseGradient()
+        if self.inducing:
+            g, du = self.gp.SparseGradientInducing()
+            g = np.concatenate([g, du.reshape(-1)])
+        else:
+            g = self.gp.SparseGradient()
         if self.Priors is not None:
-            self.Priors.Observe(self._x)
+            self.Priors.Observe(self._x[:self.gp._ns + self.gp._nn])
             pg = np.asarray(self.Priors.Gradient(), dtype=float)
             g[:len(pg)] += pg
         return g

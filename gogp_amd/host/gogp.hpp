@@ -233,6 +233,7 @@ class GP {
   // GOGP_SPARSE_MAX_M inducing points, O(N M^2); no reference counterpart.  SetSparse: a data set of its own (x row-major
   // N x NDim, y, u row-major M x NDim), resident on the device beside X / Y, which it does not touch; M == 0 clears it.
   void SetSparse(const std::vector<double> &x, const std::vector<double> &y, const std::vector<double> &u) {
+    sparse_m_ = 0;
     if (u.empty()) {
       check(gogp_sparse_set_data(h_, nullptr, nullptr, 0, nullptr, 0));
       return;
@@ -240,6 +241,7 @@ class GP {
     if (x.size() != y.size() * (size_t)NDim || u.size() % (size_t)NDim) throw Error(GOGP_EARG, "len(x), len(u)");
     check(gogp_sparse_set_data(h_, y.empty() ? nullptr : x.data(), y.empty() ? nullptr : y.data(), (int64_t)y.size(), u.data(),
                                (int64_t)(u.size() / (size_t)NDim)));
+    sparse_m_ = u.size() / (size_t)NDim;
   }
   // the bound at x = log theta
   double SparseObserve(const std::vector<double> &x) {
@@ -251,6 +253,21 @@ class GP {
   std::vector<double> SparseGradient() {
     std::vector<double> g(ThetaSimil.size() + ThetaNoise.size(), 0.0);
     check(gogp_sparse_gradient(h_, g.data(), (int64_t)g.size()));
+    return g;
+  }
+  // Replace the inducing points of SetSparse by u (row-major M x NDim, the same M) and nothing else: x, y and every device
+  // buffer stay.  SparseObserve has to follow before a gradient or a forecast.
+  void SetInducing(const std::vector<double> &u) {
+    if (u.empty() || u.size() % (size_t)NDim) throw Error(GOGP_EARG, "len(u)");
+    check(gogp_sparse_set_inducing(h_, u.data(), (int64_t)(u.size() / (size_t)NDim)));
+  }
+  // SparseGradient and, from the same pass over the data, d bound / d U of the inducing points of SetSparse (dU:
+  // row-major M x NDim)
+  std::vector<double> SparseGradientInducing(std::vector<double> &dU) {
+    if (sparse_m_ < 1) throw Error(GOGP_ESTATE, "SparseGradientInducing before SetSparse");
+    std::vector<double> g(ThetaSimil.size() + ThetaNoise.size(), 0.0);
+    dU.assign(sparse_m_ * (size_t)NDim, 0.0);
+    check(gogp_sparse_gradient_inducing(h_, g.data(), (int64_t)g.size(), dU.data()));
     return g;
   }
   // mu and sigma of the sparse approximation at the test points (latent, unclamped, as Produce)
@@ -363,6 +380,7 @@ class GP {
   size_t last_len_ = 0;
   bool dirty_ = true;
   int T_ = 0;  // output columns of SetOutputs
+  size_t sparse_m_ = 0;  // inducing points of SetSparse
 
   std::vector<double> pack(const std::vector<std::vector<double>> &x) const {
     std::vector<double> flat(x.size() * (size_t)NDim);

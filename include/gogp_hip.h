@@ -302,12 +302,42 @@ int gogp_multi_produce(gogp_handle *h, const double *Z, int64_t m, double *mu /*
  * 999.6 / 1552.9 ms; gogp_sparse_produce of 1024 points 0.2 - 1.3 ms.  At N = 16384, M = 4096 observe + gradient takes
  * 43.0 ms beside 71.3 ms for the dense gogp_observe + gogp_gradient (bound -10664.90 beside the LML -10662.82).  The new
  * SYRK runs well below the tile kernel: 27.6 against 60.9 TFLOP/s for GEMM_LOWER at M = 4096, K = 8192 (20.4 against 45.8
- * at M = 2048, 1.6 against 7.9 at M = 512); it is not tuned. */
+ * at M = 2048, 1.6 against 7.9 at M = 512); it is not tuned.
+ * Learning the inducing points.  gogp_sparse_gradient_inducing returns gogp_sparse_gradient's grad (bit for bit) and, from
+ * the same second pass over the data, the derivative of the bound in the inducing points.  With W (M x N), G (M x M,
+ * symmetric), P and m of DESIGN.md section 4, "Sparse" (W = 2 P Kuf + m y^T / s2^2):
+ *     dU[a][d] = sum_f W_af dk(u_a, x_f)/du_ad  +  2 sum_b G_ab dk(u_a, u_b)/du_ad
+ * (u_a enters Kuu through row a and column a; the jitter and t0 do not depend on U; a pair of coincident points
+ * contributes exact zeros).  The same preconditions and error codes as gogp_sparse_gradient, GOGP_EARG for dU == NULL;
+ * N == 0: zeros in both.  It takes, beyond the memory above, slabs x M x D doubles of slab partials and two M x D arrays;
+ * slabs = min(ceil(chunk / 256), floor(2048 / ceil(M / 64))), the most any chunk of up to "sparse_chunk" rows needs (one
+ * slab per 256 rows, longer slabs once M / 64 x slabs would exceed 2048 workgroups -- the count is not monotone in the
+ * rows, so a ragged last chunk may take more slabs than a full one; the buffer is sized by the bound).
+ * gogp_sparse_set_inducing replaces U and nothing else: X, y, every buffer and the options stay, nothing of size N is
+ * copied.  M must equal the M of gogp_sparse_set_data (GOGP_EARG otherwise, as for NULL, a non-finite value or a refused
+ * kind of handle; GOGP_ESTATE before gogp_sparse_set_data).  Gradient and produce return GOGP_ESTATE until the next
+ * gogp_sparse_observe, from which on every sparse call returns the bits of a fresh handle given
+ * gogp_sparse_set_data(X, y, U).
+ * Measured on the same build (profiles/sparse_inducing.txt, the rules above): observe + gradient_inducing at N = 65536
+ * 16.5 / 36.3 / 118.8 ms for M = 512 / 2048 / 4096 (observe + gradient: 15.4 / 34.6 / 115.2), N = 1048576: 244.0 / 494.6 /
+ * 1590.2 ms (231.3 / 477.9 / 1557.0); gogp_sparse_set_inducing 0.06 - 0.15 ms beside 2.4 - 8.6 ms for gogp_sparse_set_data.
+ * Accuracy: dU along its own direction against a central difference of the bound agrees to 8e-6 .. 6.7e-3 at
+ * "sparse_jitter_log10" = -6 at every size; at the default -8 to 1e-4 .. 3e-3 for M <= 2048, but at M = 4096 (random subset
+ * of the inputs, cond(Kuu + eps I) ~ 1e12) it is off by 0.09 / 0.5 / 0.9 of |dU| at N = 65536 / 262144 / 1048576: the rounding
+ * of P and G, ~cond * 1e-16, against parts that cancel -- a supposition from how the error scales with the jitter (a tenth
+ * to a fiftieth per decade), not isolated by forming P and G in higher precision.  The call does not refuse the
+ * combination: the conditioning depends on where the points lie, not on M and the jitter alone.  Learn that many inducing
+ * points at a jitter of 1e-6 or more. */
 #define GOGP_SPARSE_MAX_M 4096
 int gogp_sparse_set_data(gogp_handle *h, const double *X, const double *y, int64_t N, const double *U, int64_t M);
 int gogp_sparse_observe(gogp_handle *h, const double *x /* log theta */, int64_t len /* P */, double *bound);
 int gogp_sparse_gradient(gogp_handle *h, double *grad, int64_t len /* P */);
 int gogp_sparse_produce(gogp_handle *h, const double *Z, int64_t m, double *mu, double *sigma);
+/* Replace the inducing points; X, y, buffers and options stay.  M must equal the M of gogp_sparse_set_data. */
+int gogp_sparse_set_inducing(gogp_handle *h, const double *U /* M x ndim */, int64_t M);
+/* gogp_sparse_gradient and, from the same pass over the data, d bound / d U.  NOT a usable gradient where Kuu + eps I is
+ * ill-conditioned: M = 4096 at the default "sparse_jitter_log10" = -8 is off by 0.09 .. 0.9 of |dU| (above); use -6 there. */
+int gogp_sparse_gradient_inducing(gogp_handle *h, double *grad /* P */, int64_t len, double *dU /* M x ndim */);
 
 /* k independent Observe + Gradient evaluations at once: handle hs[i] (each created and given
  * its data separately; they may hold the same data) evaluates x[i*len .. (i+1)*len) from its own

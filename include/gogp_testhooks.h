@@ -260,6 +260,19 @@ int gogp_test_sparse_grad(int device, const gogp_test_kparams *kparams, const do
                           const double *U, int64_t u_len, int64_t M, const double *Wt, int64_t wt_len, int64_t ldw,
                           const double *y, int64_t y_len, const double *mvec, int64_t m_len, double s4, int accumulate,
                           double *out /* GOGP_TEST_NACC */);
+/* launch_sparse_ugrad (sparse.hip): dU (in / out; M x ndim of du_len doubles; `accumulate`: added to what it holds, what lies
+ * beyond M x ndim is left alone) = sum_{f < rows} (Wt[f][u] + y_f mvec_u s4) dk(u_u, x_f) / du_u: the arguments of
+ * gogp_test_sparse_grad. */
+int gogp_test_sparse_ugrad(int device, const gogp_test_kparams *kparams, const double *X, int64_t x_len, int64_t rows,
+                           const double *U, int64_t u_len, int64_t M, const double *Wt, int64_t wt_len, int64_t ldw,
+                           const double *y, int64_t y_len, const double *mvec, int64_t m_len, double s4, int accumulate,
+                           double *dU /* in / out, M x ndim */, int64_t du_len);
+/* sparse_ugrad_slabs: the slabs of row tiles launch_sparse_ugrad splits `rows` rows into for M inducing points and the
+ * 64-row tiles of one (the last may hold fewer); no device is touched.  0 for rows or M out of range. */
+int gogp_test_sparse_ugrad_slabs(int64_t rows, int64_t M, int *tiles_per_slab);
+/* sparse_ugrad_slabs_bound: the slabs gogp_sparse_gradient_inducing sizes its partials by for chunks of up to `rows` rows: at
+ * least gogp_test_sparse_ugrad_slabs(r, M) for every r <= rows (the slab count is not monotone in the rows).  0 out of range. */
+int gogp_test_sparse_ugrad_slabs_bound(int64_t rows, int64_t M);
 
 /* Benchmark hook for the tile kernel: `reps` launches of one shape (mode 0 RECT
  * mt x nt tiles, 1 LOWER mt x mt, 2 LAUUM mt x mt with K = mt*128) on device
