@@ -83,6 +83,7 @@ type GP struct {
 	dirty      bool
 	nout       int // output columns of SetOutputs
 	sparseM    int // inducing points of SetSparse
+	sparseT    int // output columns of SetSparseOutputs
 	upX        *[]float64 // &gp.X[0] at the time of the last upload
 	upY        *float64   // &gp.Y[0] at the time of the last upload
 	upN        int
@@ -513,6 +514,7 @@ func (gp *GP) MultiProduce(x [][]float64) (mu, sigma []float64, err error) {
 func (gp *GP) SetSparse(x, y, u []float64) error {
 	gp.defaults()
 	gp.sparseM = 0
+	gp.sparseT = 0 // (the library drops the outputs of SetSparseOutputs with the data)
 	if len(u) == 0 {
 		return gp.err(C.gogp_sparse_set_data(gp.handle(), nil, nil, 0, nil, 0))
 	}
@@ -590,6 +592,88 @@ func (gp *GP) SparseProduce(x [][]float64) (mu, sigma []float64, err error) {
 		return nil, nil, err
 	}
 	return mu, sigma, nil
+}
+
+// SetSparseOutputs gives the sparse data nout <= 128 output columns observed
+// at the inputs of SetSparse (no reference counterpart): yt is row-major
+// N x nout with the N of SetSparse and stays on the device as given.  nout == 0
+// clears them; SetSparse drops them, SetInducing keeps them.
+func (gp *GP) SetSparseOutputs(yt []float64, nout int) error {
+	gp.defaults()
+	gp.sparseT = 0
+	if nout == 0 {
+		return gp.err(C.gogp_sparse_multi_set_outputs(gp.handle(), nil, 0, 0))
+	}
+	if nout < 0 || len(yt)%nout != 0 {
+		return fmt.Errorf("len(yt)")
+	}
+	buf := yt
+	if len(buf) == 0 {
+		buf = make([]float64, 1)
+	}
+	if err := gp.err(C.gogp_sparse_multi_set_outputs(gp.handle(), dptr(buf), C.int64_t(len(yt)/nout), C.int32_t(nout))); err != nil {
+		return err
+	}
+	gp.sparseT = nout
+	return nil
+}
+
+// SparseMultiObserve computes the collapsed bound of every output column of
+// SetSparseOutputs at x = log theta, on one pass over the data, and their sum
+// in column order.
+func (gp *GP) SparseMultiObserve(x []float64) (total float64, bounds []float64, err error) {
+	gp.defaults()
+	var t C.double
+	buf := make([]float64, gp.sparseT+1)
+	if err = gp.err(C.gogp_sparse_multi_observe(gp.handle(), dptr(x), C.int64_t(len(x)), &t, dptr(buf))); err != nil {
+		return 0, nil, err
+	}
+	return float64(t), buf[:gp.sparseT], nil
+}
+
+// SparseMultiGradient computes the gradient of that sum with respect to the
+// log-transformed hyperparameters, at the parameters of the last
+// SparseMultiObserve.
+func (gp *GP) SparseMultiGradient() ([]float64, error) {
+	gp.defaults()
+	g := make([]float64, len(gp.ThetaSimil)+len(gp.ThetaNoise))
+	if err := gp.err(C.gogp_sparse_multi_gradient(gp.handle(), dptr(g), C.int64_t(len(g)))); err != nil {
+		return nil, err
+	}
+	return g, nil
+}
+
+// SparseMultiGradientInducing computes SparseMultiGradient and, from the same
+// pass over the data, the derivative of the sum in the inducing points of
+// SetSparse (dU: row-major M x NDim).
+func (gp *GP) SparseMultiGradientInducing() (grad, dU []float64, err error) {
+	gp.defaults()
+	if gp.sparseM < 1 {
+		return nil, nil, fmt.Errorf("SparseMultiGradientInducing before SetSparse")
+	}
+	grad = make([]float64, len(gp.ThetaSimil)+len(gp.ThetaNoise))
+	dU = make([]float64, gp.sparseM*gp.NDim)
+	if err = gp.err(C.gogp_sparse_multi_gradient_inducing(gp.handle(), dptr(grad), C.int64_t(len(grad)), dptr(dU))); err != nil {
+		return nil, nil, err
+	}
+	return grad, dU, nil
+}
+
+// SparseMultiProduce computes the predictive means of every output at the test
+// points (row-major len(x) x nout) and the standard deviation they share
+// (latent and unclamped, as SparseProduce).
+func (gp *GP) SparseMultiProduce(x [][]float64) (mu, sigma []float64, err error) {
+	gp.defaults()
+	m := len(x)
+	flat := make([]float64, m*gp.NDim)
+	for i, row := range x {
+		copy(flat[i*gp.NDim:], row)
+	}
+	buf, sigma := make([]float64, m*gp.sparseT+1), make([]float64, m)
+	if err = gp.err(C.gogp_sparse_multi_produce(gp.handle(), dptr(flat), C.int64_t(m), dptr(buf), dptr(sigma))); err != nil {
+		return nil, nil, err
+	}
+	return buf[:m*gp.sparseT], sigma, nil
 }
 
 // Sample draws len(xi)/len(x) joint samples at the test points from the

@@ -22,6 +22,7 @@ GOGP_BATCH_MAX_N = 128
 GOGP_COV_MAX_M = 4096
 GOGP_MULTI_MAX_T = 128
 GOGP_SPARSE_MAX_M = 4096
+GOGP_SPARSE_MULTI_MAX_T = 128
 
 #: every symbol include/gogp_hip.h declares: (name, restype, argtypes)
 _dp = ctypes.POINTER(ctypes.c_double)
@@ -98,6 +99,11 @@ SYMBOLS = [
     ("gogp_sparse_produce", ctypes.c_int, [_h, _dp, _i64, _dp, _dp]),
     ("gogp_sparse_set_inducing", ctypes.c_int, [_h, _dp, _i64]),
     ("gogp_sparse_gradient_inducing", ctypes.c_int, [_h, _dp, _i64, _dp]),
+    ("gogp_sparse_multi_set_outputs", ctypes.c_int, [_h, _dp, _i64, ctypes.c_int32]),
+    ("gogp_sparse_multi_observe", ctypes.c_int, [_h, _dp, _i64, _dp, _dp]),
+    ("gogp_sparse_multi_gradient", ctypes.c_int, [_h, _dp, _i64]),
+    ("gogp_sparse_multi_gradient_inducing", ctypes.c_int, [_h, _dp, _i64, _dp]),
+    ("gogp_sparse_multi_produce", ctypes.c_int, [_h, _dp, _i64, _dp, _dp]),
     ("gogp_observe_gradient_batch", ctypes.c_int,
      [ctypes.POINTER(_h), ctypes.c_int, _dp, _i64, _dp, _dp, ctypes.POINTER(ctypes.c_int)]),
     ("gogp_observe_gradient_candidates", ctypes.c_int,
@@ -224,6 +230,7 @@ HOOK_SYMBOLS = [
     ("gogp_test_multi_weight", ctypes.c_int,
      [ctypes.c_int, _dp, _i64, _i64, ctypes.c_int, _dp, _i64, _i64, _i64, _i64, _dp, _i64]),
     ("gogp_bench_sparse_syrk", ctypes.c_int, [ctypes.c_int, _i64, _i64, ctypes.c_int, _dp, _dp]),
+    ("gogp_bench_sparse_xty", ctypes.c_int, [ctypes.c_int, _i64, _i64, _i64, ctypes.c_int, _dp, _dp]),
     ("gogp_test_sparse_syrk", ctypes.c_int,
      [ctypes.c_int, _dp, _i64, _i64, _i64, _i64, _i64, _dp, _i64, _dp, _i64, _i64, _dp, _i64]),
     ("gogp_test_sparse_grad", ctypes.c_int,
@@ -234,6 +241,10 @@ HOOK_SYMBOLS = [
       ctypes.c_double, ctypes.c_int, _dp, _i64]),
     ("gogp_test_sparse_ugrad_slabs", ctypes.c_int, [_i64, _i64, ctypes.POINTER(ctypes.c_int)]),
     ("gogp_test_sparse_ugrad_slabs_bound", ctypes.c_int, [_i64, _i64]),
+    ("gogp_test_sparse_xty", ctypes.c_int,
+     [ctypes.c_int, _dp, _i64, _i64, _i64, _i64, _i64, _dp, _i64, _i64, _i64, _dp, _i64, _i64]),
+    ("gogp_test_sparse_xty_slabs", ctypes.c_int, [_i64, _i64, _i64, ctypes.POINTER(ctypes.c_int64)]),
+    ("gogp_test_sparse_xty_slabs_bound", ctypes.c_int, [_i64, _i64, _i64]),
     # per-rank replay of the sharded sweep (tools/sharded_replay.py): a transport that reads recorded panels
     ("gogp_test_dist_init_replay", ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int] * 4),
 ]

@@ -2939,6 +2939,42 @@ static size_t sparse_layout(double *base, int64_t Mp, SparseBufs *b) {
 }
 static int64_t sparse_mp(const gogp_handle *h) { return ((h->sp_M + PANEL - 1) / PANEL) * PANEL; }
 
+// The multi-output state (gogp_sparse_multi_*): what the multi observe leaves beside the shared Mp x Mp matrices.  Every
+// matrix is padded to the tile kernel's 128 (SM_TP = GOGP_SPARSE_MULTI_MAX_T columns or rows, exact zeros from T on), so
+// the GEMM_RECT launches take them as they lie: Rt = R^T and Gt = Gamma^T are SM_TP x Mp (a row per output: the dots
+// kernel and the products Gamma^T = Rt Binv, Mm = Yu Gt^T, mu = Vt Gt^T read them), Gam = Gamma and Mm = Yu Gamma are
+// Mp x SM_TP (Gamma Gamma^T and the second pass's rank-T launch read those).
+constexpr int64_t SM_TP = GOGP_SPARSE_MULTI_MAX_T;
+static_assert(SM_TP == TILE, "the multi-output matrices are one tile of outputs wide");
+struct SparseMultiBufs {
+  double *Rt, *Gt, *Gam, *Mm;  // SM_TP x Mp, SM_TP x Mp, Mp x SM_TP, Mp x SM_TP
+  double *dots;                // 2 SM_TP: r_t . gamma_t, gamma_t . gamma_t
+};
+static size_t sparse_multi_layout(double *base, int64_t Mp, SparseMultiBufs *b) {
+  const size_t mt = (size_t)Mp * SM_TP;
+  b->Rt = base, b->Gt = base ? base + mt : nullptr, b->Gam = base ? base + 2 * mt : nullptr;
+  b->Mm = base ? base + 3 * mt : nullptr, b->dots = base ? base + 4 * mt : nullptr;
+  return (4 * mt + 2 * SM_TP) * sizeof(double);
+}
+// bytes of the scratch sized by the chunk: the partials of launch_sparse_xty for every chunk length up to `chunk`, then
+// (from *ypad_off doubles on) the chunk's rows of Y padded to chunk x SM_TP for the second pass
+static size_t sparse_multi_scratch(int64_t chunk, int64_t M, int T, size_t *ypad_off) {
+  const size_t np = sparse_xty_part_doubles(chunk, M, T);
+  if (ypad_off) *ypad_off = np;
+  return (np + (size_t)chunk * SM_TP) * sizeof(double);
+}
+static void sparse_multi_free(gogp_handle *h) {
+  (void)hipFree(h->sp_Y);
+  h->sp_Y = nullptr;
+  h->sp_T = 0;
+  h->sp_mobserved = false;
+  h->sp_myty.clear();
+  h->sp_mdots.clear();
+  h->sp_mws.release();
+  h->sp_mscr.release();
+  h->sp_mmu.release();
+}
+
 static void sparse_free(gogp_handle *h) {
   if (h->sp_ind) gogp_destroy(h->sp_ind);
   h->sp_ind = nullptr;
@@ -2948,6 +2984,7 @@ static void sparse_free(gogp_handle *h) {
   h->sp_ws.release();
   h->sp_vec.release();
   h->sp_ug.release();
+  sparse_multi_free(h);
   h->sp_N = h->sp_M = 0;
   h->sp_have = h->sp_observed = false;
 }
@@ -3041,6 +3078,49 @@ extern "C" int gogp_sparse_set_data(gogp_handle *h, const double *X, const doubl
   return GOGP_OK;
 }
 
+// The T output columns of the multi flavour: N x T row-major, uploaded as given (no transpose on the host: the kernels
+// take the row-major layout), y_t^T y_t of every column once, and the state buffers sized by Mp.
+extern "C" int gogp_sparse_multi_set_outputs(gogp_handle *h, const double *Y, int64_t N, int32_t T) {
+  if (!h) return GOGP_EARG;
+  if (T == 0 && !Y) {  // clear
+    HIPCHK(h, hipSetDevice(h->device));
+    sparse_multi_free(h);
+    return GOGP_OK;
+  }
+  if (sparse_refusal(h)) return sparse_refuse(h, "sparse_multi_set_outputs");
+  if (T < 1 || T > GOGP_SPARSE_MULTI_MAX_T)
+    return fail(h, GOGP_EARG, "sparse_multi_set_outputs: need 1 <= T <= GOGP_SPARSE_MULTI_MAX_T");
+  if (!h->sp_have) return fail(h, GOGP_ESTATE, "sparse_multi_set_outputs: no sparse data (gogp_sparse_set_data)");
+  if (N != h->sp_N) return fail(h, GOGP_EARG, "sparse_multi_set_outputs: N differs from the N of gogp_sparse_set_data");
+  if (N > 0 && !Y) return fail(h, GOGP_EARG, "sparse_multi_set_outputs: NULL");
+  for (int64_t i = 0; i < N * T; ++i)
+    if (!std::isfinite(Y[i])) return fail(h, GOGP_EARG, "sparse_multi_set_outputs: non-finite output");
+  HIPCHK(h, hipSetDevice(h->device));
+  sparse_multi_free(h);
+  SparseMultiBufs mb;
+  const int rc = h->sp_mws.reserve(h, sparse_multi_layout(nullptr, sparse_mp(h), &mb));
+  if (rc != GOGP_OK) return rc;
+  sparse_multi_layout(h->sp_mws.as<double>(), sparse_mp(h), &mb);
+  h->sp_myty.assign((size_t)T, 0.0);
+  if (N > 0) {
+    hipStream_t s = h->sp_ind->s;
+    const size_t yb = (size_t)N * T * sizeof(double);
+    hipError_t e = hipMalloc(&h->sp_Y, yb);
+    if (e == hipSuccess) e = hipMemcpyAsync(h->sp_Y, Y, yb, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) {
+      launch_sparse_multi_sumsq(s, h->sp_Y, T, N, T, mb.dots);
+      e = hipMemcpyAsync(h->sp_myty.data(), mb.dots, (size_t)T * sizeof(double), hipMemcpyDeviceToHost, s);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+      sparse_multi_free(h);
+      HIPCHK(h, e);
+    }
+  }
+  h->sp_T = T;
+  return GOGP_OK;
+}
+
 // C C^T = Bm (256-panel Cholesky on the main stream), Y = C^-T panel by panel, Binv = Y Y^T in full
 static void sparse_factor_b(gogp_handle *ind, hipStream_t s, const SparseBufs &b, int64_t M, int64_t Mp) {
   GemmGrid gtri;
@@ -3070,17 +3150,25 @@ static void sparse_factor_b(gogp_handle *ind, hipStream_t s, const SparseBufs &b
   launch_gemm_nt(s, GEMM_RECT, nt, nt, Mp, 1.0, b.Y, Mp, b.Y, Mp, 0.0, b.Binv, Mp, nullptr);
 }
 
-extern "C" int gogp_sparse_observe(gogp_handle *h, const double *x, int64_t len, double *bound) {
-  if (!h || !x || !bound) return fail(h, GOGP_EARG, "sparse_observe: NULL");
-  if (sparse_refusal(h)) return sparse_refuse(h, "sparse_observe");
-  if (len != h->P) return fail(h, GOGP_EARG, "sparse_observe: len(x)");
+// gogp_sparse_observe (bounds == nullptr, `multi` false) and gogp_sparse_multi_observe: one body.  The multi flavour adds
+// R^T += Yc^T Vt behind every chunk's launch_sparse_syrk (whose r = V y of the single output it leaves unused), takes
+// Gamma = B^-1 R in the place of g = B^-1 r and the per-output dots in the place of r^T g; everything else -- the
+// cross-covariances, the substitution, B, its factor, B^-1 and the scalars of B -- is the same launches in the same order.
+static int sparse_observe_impl(gogp_handle *h, const char *who, bool multi, const double *x, int64_t len, double *bound,
+                               double *bounds) {
+  auto msg = [&](const char *what) { return std::string(who) + what; };
+  if (sparse_refusal(h)) return sparse_refuse(h, who);
+  if (len != h->P) return fail(h, GOGP_EARG, msg(": len(x)").c_str());
   for (int64_t i = 0; i < len; ++i)
-    if (!std::isfinite(x[i])) return fail(h, GOGP_EARG, "sparse_observe: non-finite parameter");
-  if (!h->sp_have) return fail(h, GOGP_ESTATE, "sparse_observe: no sparse data (gogp_sparse_set_data)");
+    if (!std::isfinite(x[i])) return fail(h, GOGP_EARG, msg(": non-finite parameter").c_str());
+  if (!h->sp_have) return fail(h, GOGP_ESTATE, msg(": no sparse data (gogp_sparse_set_data)").c_str());
+  if (multi && h->sp_T < 1) return fail(h, GOGP_ESTATE, msg(": no outputs (gogp_sparse_multi_set_outputs)").c_str());
   HIPCHK(h, hipSetDevice(h->device));
   gogp_handle *ind = h->sp_ind;
-  h->sp_observed = false;
+  const int nT = multi ? h->sp_T : 0;
+  h->sp_observed = h->sp_mobserved = false;  // the last observe of either flavour owns the shared workspace
   *bound = NAN;
+  for (int t = 0; t < nT && bounds; ++t) bounds[t] = NAN;
   // the parameters on the host: noise variance, its derivative, the output scales
   std::vector<double> th(h->P > 0 ? h->P : 1);
   for (int i = 0; i < h->P; ++i) th[i] = exp(x[i]);
@@ -3088,20 +3176,20 @@ extern "C" int gogp_sparse_observe(gogp_handle *h, const double *x, int64_t len,
   DevParams hp;
   fill_params_theta(h, th.data(), th.data() + h->ns, hp);
   if (!(hp.noise_var > 0.0) || !std::isfinite(hp.noise_var))
-    return fail(h, GOGP_EARG, "sparse_observe: the noise variance must be positive and finite");
+    return fail(h, GOGP_EARG, msg(": the noise variance must be positive and finite").c_str());
   ind->desc.noise_std = pow(10.0, 0.5 * h->sp_jitter_log10);
   ind->cond_limit = h->cond_limit;
   int rc = gogp_observe(ind, x, ind->P, nullptr);
   if (rc == GOGP_ENOTPD) {
     char buf[200];
     h->notpd = ind->notpd;
-    snprintf(buf, sizeof buf, "sparse_observe: Kuu + jitter is not positive definite (inducing point %lld)", (long long)h->notpd);
+    snprintf(buf, sizeof buf, "%s: Kuu + jitter is not positive definite (inducing point %lld)", who, (long long)h->notpd);
     h->err = buf;
     return rc;
   }
-  if (rc != GOGP_OK && rc != GOGP_ECOND) return sparse_fail_from(h, "sparse_observe", rc);
+  if (rc != GOGP_OK && rc != GOGP_ECOND) return sparse_fail_from(h, who, rc);
   const int rcond = rc;
-  if (rcond == GOGP_ECOND) h->err = "sparse_observe: the factor of Kuu + jitter exceeds the condition limit";
+  if (rcond == GOGP_ECOND) h->err = msg(": the factor of Kuu + jitter exceeds the condition limit");
   const int64_t N = h->sp_N, M = h->sp_M, Mp = sparse_mp(h);
   const double s2 = hp.noise_var;
   h->sp_s2 = s2;
@@ -3111,14 +3199,16 @@ extern "C" int gogp_sparse_observe(gogp_handle *h, const double *x, int64_t len,
   for (int t = 0; t < h->desc.nterms; ++t) h->sp_csum += hp.c[t];
   if (N == 0) {
     *bound = 0.0;
-    h->sp_observed = true;
+    for (int t = 0; t < nT && bounds; ++t) bounds[t] = 0.0;
+    if (multi) h->sp_mdots.assign(2 * (size_t)nT, 0.0);
+    (multi ? h->sp_mobserved : h->sp_observed) = true;
     return rcond;
   }
   SparseBufs b;
   sparse_layout(h->sp_ws.as<double>(), Mp, &b);
   hipStream_t s = ind->s;
   rc = ensure_alpha(ind);  // the main stream behind the factorisation
-  if (rc != GOGP_OK) return sparse_fail_from(h, "sparse_observe", rc);
+  if (rc != GOGP_OK) return sparse_fail_from(h, who, rc);
   const size_t mm = (size_t)Mp * Mp;
   HIPCHK(h, hipMemsetAsync(b.Bacc, 0, 4 * mm * sizeof(double), s));  // Bacc, Bm, C, Y
   HIPCHK(h, hipMemsetAsync(b.r, 0, 4 * (size_t)Mp * sizeof(double), s));  // r, g, mvec, zero
@@ -3126,44 +3216,94 @@ extern "C" int gogp_sparse_observe(gogp_handle *h, const double *x, int64_t len,
   // first pass over the data: V^T of every chunk, B_acc += V V^T, r += V y
   const int64_t chunk = std::min(h->sp_chunk, ((N + TILE - 1) / TILE) * TILE);
   rc = ensure_m(ind, chunk, chunk);
-  if (rc != GOGP_OK) return sparse_fail_from(h, "sparse_observe", rc);
+  if (rc != GOGP_OK) return sparse_fail_from(h, who, rc);
+  SparseMultiBufs mb = {};
+  double *xpart = nullptr;
+  if (multi) {
+    // (the bound over every chunk length up to `chunk`: a ragged last chunk may take more slabs than a full one)
+    const int rcw = h->sp_mscr.reserve(h, sparse_multi_scratch(chunk, M, nT, nullptr));
+    if (rcw != GOGP_OK) return rcw;
+    xpart = h->sp_mscr.as<double>();
+    sparse_multi_layout(h->sp_mws.as<double>(), Mp, &mb);
+    HIPCHK(h, hipMemsetAsync(mb.Rt, 0, (size_t)Mp * SM_TP * sizeof(double), s));
+  }
   for (int64_t f0 = 0; f0 < N; f0 += chunk) {
     const int64_t m = std::min(chunk, N - f0), mpad = ((m + TILE - 1) / TILE) * TILE;
     launch_cross(s, ind->devP, ind->D, ind->dX, M, Mp, h->sp_X + f0 * ind->D, m, mpad, ind->KsT, Mp, false);
     produce_substitute_t<double>(ind, s, m, mpad, nullptr);
     launch_sparse_syrk(s, ind->Vt, Mp, m, M, Mp, h->sp_y + f0, b.Bacc, Mp, b.r);
+    if (multi) launch_sparse_xty(s, ind->Vt, Mp, m, M, h->sp_Y + f0 * nT, nT, nT, xpart, mb.Rt, Mp);
   }
   // the M x M work: B, its factor, B^-1, g = B^-1 r and the scalars
   launch_sparse_finish_b(s, b.Bacc, Mp, 1.0 / s2, b.Bm);
   HIPCHK(h, hipMemcpyAsync(b.Pm, b.Bm, mm * sizeof(double), hipMemcpyDeviceToDevice, s));  // the factorisation consumes Bm
   sparse_factor_b(ind, s, b, M, Mp);
   HIPCHK(h, hipMemcpyAsync(b.Bm, b.Pm, mm * sizeof(double), hipMemcpyDeviceToDevice, s));
-  launch_rownorm_dot(s, b.Binv, Mp, b.r, Mp, M, b.g, nullptr);
+  if (multi) {
+    // Gamma^T = R^T B^-1 and Gamma = B^-1 R (B^-1 is symmetric in full), then the dots of every output
+    const int nt = (int)(Mp / TILE);
+    launch_gemm_nt(s, GEMM_RECT, 1, nt, Mp, 1.0, (const double *)mb.Rt, Mp, (const double *)b.Binv, Mp, 0.0, mb.Gt, Mp, nullptr);
+    launch_gemm_nt(s, GEMM_RECT, nt, 1, Mp, 1.0, (const double *)b.Binv, Mp, (const double *)mb.Rt, Mp, 0.0, mb.Gam, SM_TP,
+                   nullptr);
+    launch_sparse_multi_dots(s, mb.Rt, mb.Gt, Mp, M, nT, nT, mb.dots);
+    h->sp_mdots.assign(2 * (size_t)nT, 0.0);
+    HIPCHK(h, hipMemcpyAsync(h->sp_mdots.data(), mb.dots, 2 * (size_t)nT * sizeof(double), hipMemcpyDeviceToHost, s));
+  } else {
+    launch_rownorm_dot(s, b.Binv, Mp, b.r, Mp, M, b.g, nullptr);
+  }
   launch_sparse_scalars(s, b.C, b.Bm, b.Binv, b.r, b.g, M, Mp, b.scal);
   long long info = 0;
   HIPCHK(h, hipMemcpyAsync(h->sp_scal, b.scal, 5 * sizeof(double), hipMemcpyDeviceToHost, s));
   HIPCHK(h, hipMemcpyAsync(&info, b.info, sizeof info, hipMemcpyDeviceToHost, s));
   HIPCHK(h, hipStreamSynchronize(s));
   HIPCHK(h, hipGetLastError());
-  if (info != 0) return fail(h, GOGP_EHIP, "sparse_observe: the factorisation of B = I + V V^T / s2 met a non-positive pivot");
+  if (info != 0)
+    return fail(h, GOGP_EHIP, msg(": the factorisation of B = I + V V^T / s2 met a non-positive pivot").c_str());
   const double logdetB = h->sp_scal[0], trBmM = h->sp_scal[1], rtg = h->sp_scal[3];
   const double t0 = (double)N * h->sp_csum;
+  if (multi) {  // bound_t = c0 - y_t^T y_t / (2 s2) + r_t^T gamma_t / (2 s2^2), their sum in column order
+    const double c0 = -0.5 * (double)N * log(2 * M_PI) - 0.5 * logdetB - 0.5 * (double)N * log(s2) - (t0 - s2 * trBmM) / (2 * s2);
+    double total = 0.0;
+    for (int t = 0; t < nT; ++t) {
+      const double bt = c0 - h->sp_myty[(size_t)t] / (2 * s2) + h->sp_mdots[(size_t)t] / (2 * s2 * s2);
+      if (bounds) bounds[t] = bt;
+      total += bt;
+    }
+    *bound = total;
+    h->sp_mobserved = true;
+    return rcond;
+  }
   *bound = -0.5 * (double)N * log(2 * M_PI) - 0.5 * logdetB - 0.5 * (double)N * log(s2) - h->sp_yty / (2 * s2) +
            rtg / (2 * s2 * s2) - (t0 - s2 * trBmM) / (2 * s2);
   h->sp_observed = true;
   return rcond;
 }
 
+extern "C" int gogp_sparse_observe(gogp_handle *h, const double *x, int64_t len, double *bound) {
+  if (!h || !x || !bound) return fail(h, GOGP_EARG, "sparse_observe: NULL");
+  return sparse_observe_impl(h, "sparse_observe", false, x, len, bound, nullptr);
+}
+
+extern "C" int gogp_sparse_multi_observe(gogp_handle *h, const double *x, int64_t len, double *total, double *bounds) {
+  if (!h || !x || !total) return fail(h, GOGP_EARG, "sparse_multi_observe: NULL");
+  return sparse_observe_impl(h, "sparse_multi_observe", true, x, len, total, bounds);
+}
+
 // gogp_sparse_gradient (dU == nullptr) and gogp_sparse_gradient_inducing: with dU, the second pass over the data also
 // reduces the (U, X) pairs on dk/du (launch_sparse_ugrad: the chunk's Wt, mvec, y and s4 of launch_sparse_grad) and
 // the (U, U) pairs go through the input-gradient reduction of the full Observe form (launch_xgrad) with a zero alpha
 // and -G as its K^-1:  dU = 2 (U, U part) + (U, X part) -- u_a enters Kuu through row a and column a.
-static int sparse_gradient_impl(gogp_handle *h, const char *who, double *grad, int64_t len, double *dU) {
+// The multi flavour (gogp_sparse_multi_gradient*): T and S carry the number of outputs and Gamma Gamma^T in the place of
+// g g^T, the rank-one term y_f m_u / s2^2 of the weights becomes the rank-T term Yc Mm^T / s2^2, which one more
+// GEMM_RECT launch adds to the chunk's Wt, and the pair reductions run unchanged with the zero vector as mvec.
+static int sparse_gradient_impl(gogp_handle *h, const char *who, bool multi, double *grad, int64_t len, double *dU) {
   auto msg = [&](const char *what) { return std::string(who) + what; };
   if (sparse_refusal(h)) return sparse_refuse(h, who);
   if (len != h->P) return fail(h, GOGP_EARG, msg(": wrong length").c_str());
   if (!h->sp_have) return fail(h, GOGP_ESTATE, msg(": no sparse data (gogp_sparse_set_data)").c_str());
-  if (!h->sp_observed) return fail(h, GOGP_ESTATE, msg(" before sparse_observe").c_str());
+  if (multi && h->sp_T < 1) return fail(h, GOGP_ESTATE, msg(": no outputs (gogp_sparse_multi_set_outputs)").c_str());
+  if (!(multi ? h->sp_mobserved : h->sp_observed))
+    return fail(h, GOGP_ESTATE, msg(multi ? " before sparse_multi_observe" : " before sparse_observe").c_str());
   for (int64_t i = 0; i < len; ++i) grad[i] = 0.0;
   const int64_t N = h->sp_N, M = h->sp_M, Mp = sparse_mp(h);
   const int64_t md = M * h->D;
@@ -3184,6 +3324,17 @@ static int sparse_gradient_impl(gogp_handle *h, const char *who, double *grad, i
     if (rcw != GOGP_OK) return rcw;
     upart = h->sp_ug.as<double>(), dux = upart + np, duu = dux + md;
   }
+  const int nT = multi ? h->sp_T : 1;
+  const int64_t kT = ((nT + GEMM_BK - 1) / GEMM_BK) * GEMM_BK;  // the K of the rank-T launch: T padded with zeros
+  SparseMultiBufs mb = {};
+  double *ypad = nullptr;
+  if (multi) {
+    size_t yoff = 0;
+    const int rcw = h->sp_mscr.reserve(h, sparse_multi_scratch(chunk, M, nT, &yoff));
+    if (rcw != GOGP_OK) return rcw;
+    ypad = h->sp_mscr.as<double>() + yoff;
+    sparse_multi_layout(h->sp_mws.as<double>(), Mp, &mb);
+  }
   int rc = compute_kinv(ind);  // Y = L^-T of the inducing process in its bufY, the main stream behind it
   if (rc != GOGP_OK) return sparse_fail_from(h, who, rc);
   const double s2 = h->sp_s2, s4 = 1.0 / (s2 * s2);
@@ -3193,13 +3344,23 @@ static int sparse_gradient_impl(gogp_handle *h, const char *who, double *grad, i
   double *T = b.Bacc, *S = b.C, *W1 = b.Y;
   const int nt = (int)(Mp / TILE);
   // T and S, then P = Yu T Yu^T / (2 s2), G = Yu S Yu^T / 2 (both triangles), m = Yu g
-  launch_sparse_weights(s, b.Bm, b.Binv, b.g, Mp, s4, T, S);
+  if (multi) {  // (Gamma Gamma^T goes through W1, which the next product overwrites)
+    launch_gemm_nt(s, GEMM_RECT, nt, nt, SM_TP, 1.0, (const double *)mb.Gam, SM_TP, (const double *)mb.Gam, SM_TP, 0.0, W1, Mp,
+                   nullptr);
+    launch_sparse_multi_weights(s, b.Bm, b.Binv, W1, Mp, nT, s4, T, S);
+  } else {
+    launch_sparse_weights(s, b.Bm, b.Binv, b.g, Mp, s4, T, S);
+  }
   launch_gemm_nt(s, GEMM_RECT, nt, nt, Mp, 1.0, Yu, Mp, T, Mp, 0.0, W1, Mp, nullptr);
   launch_gemm_nt(s, GEMM_RECT, nt, nt, Mp, 1.0 / (2 * s2), W1, Mp, Yu, Mp, 0.0, b.Pm, Mp, nullptr);
   launch_gemm_nt(s, GEMM_RECT, nt, nt, Mp, 1.0, Yu, Mp, S, Mp, 0.0, W1, Mp, nullptr);
   // (the reduction of the LML gradient forms sum_ab (alpha_a alpha_b - Kinv_ab) dK_ab: G goes in negated, alpha zero)
   launch_gemm_nt(s, GEMM_RECT, nt, nt, Mp, -0.5, W1, Mp, Yu, Mp, 0.0, b.Gm, Mp, nullptr);
-  launch_rownorm_dot(s, Yu, Mp, b.g, Mp, M, b.mvec, nullptr);
+  if (multi)  // Mm = Yu Gamma, M x T
+    launch_gemm_nt(s, GEMM_RECT, nt, 1, Mp, 1.0, Yu, Mp, (const double *)mb.Gt, Mp, 0.0, mb.Mm, SM_TP, nullptr);
+  else
+    launch_rownorm_dot(s, Yu, Mp, b.g, Mp, M, b.mvec, nullptr);
+  const double *mvec = multi ? b.zero : b.mvec;
   launch_grad_reduce(s, ind->devP, ind->D, ind->ard_dims, ind->dX, b.zero, (const double *)b.Gm, Mp, M, Mp, ind->gpart,
                      ind->gout, ind->radial1, ind->ard_mfma_min, false);
   // (launch_xgrad mirrors its matrix in place: behind the reduction that has read Gm)
@@ -3214,10 +3375,15 @@ static int sparse_gradient_impl(gogp_handle *h, const char *who, double *grad, i
     launch_cross(s, ind->devP, ind->D, ind->dX, M, Mp, h->sp_X + f0 * ind->D, m, mpad, ind->KsT, Mp, false);
     launch_gemm_nt(s, GEMM_RECT, (int)(mpad / TILE), nt, Mp, 2.0, (const double *)ind->KsT, Mp, (const double *)b.Pm, Mp,
                    0.0, ind->Vt, Mp, nullptr, &gw);
+    if (multi) {  // Wt += Yc Mm^T / s2^2
+      launch_sparse_multi_pad(s, h->sp_Y + f0 * nT, nT, m, nT, kT, mpad, ypad, SM_TP);
+      launch_gemm_nt(s, GEMM_RECT, (int)(mpad / TILE), nt, kT, s4, (const double *)ypad, SM_TP, (const double *)mb.Mm, SM_TP,
+                     1.0, ind->Vt, Mp, nullptr, &gw);
+    }
     launch_sparse_grad(s, ind->devP, ind->D, ind->ard_dims, h->sp_X + f0 * ind->D, m, ind->dX, M, ind->Vt, Mp, h->sp_y + f0,
-                       b.mvec, s4, b.gpart, b.gsum, f0 > 0);
+                       mvec, s4, b.gpart, b.gsum, f0 > 0);
     if (dU)
-      launch_sparse_ugrad(s, ind->devP, ind->D, h->sp_X + f0 * ind->D, m, ind->dX, M, ind->Vt, Mp, h->sp_y + f0, b.mvec, s4,
+      launch_sparse_ugrad(s, ind->devP, ind->D, h->sp_X + f0 * ind->D, m, ind->dX, M, ind->Vt, Mp, h->sp_y + f0, mvec, s4,
                           upart, dux, f0 > 0);
   }
   double acc[NACC], accu[NACC];
@@ -3239,8 +3405,16 @@ static int sparse_gradient_impl(gogp_handle *h, const char *who, double *grad, i
   assemble_gradient(h, acc, 0.0, grad);
   // the diagonal term -1/(2 s2) sum_f dk(x_f, x_f): the output scales alone
   for (int t = 0; t < h->desc.nterms; ++t)
-    if (h->desc.terms[t].scale_idx >= 0) grad[h->desc.terms[t].scale_idx] -= (double)N * h->sp_cterm[t] / (2 * s2);
-  if (h->nn > 0) {
+    if (h->desc.terms[t].scale_idx >= 0) grad[h->desc.terms[t].scale_idx] -= (double)nT * (double)N * h->sp_cterm[t] / (2 * s2);
+  if (h->nn > 0 && multi) {  // the sums over the outputs in column order
+    double yty = 0.0, rtg = 0.0, gtg = 0.0;
+    for (int t = 0; t < nT; ++t) yty += h->sp_myty[(size_t)t], rtg += h->sp_mdots[(size_t)t], gtg += h->sp_mdots[(size_t)(nT + t)];
+    const double trBmM = h->sp_scal[1], trBinv = h->sp_scal[2];
+    const double t0 = (double)N * h->sp_csum, s6 = s2 * s2 * s2;
+    const double dF = (double)nT * (((double)M - trBinv) / (2 * s2) - (double)N / (2 * s2) + (t0 - s2 * trBmM) / (2 * s2 * s2)) +
+                      yty / (2 * s2 * s2) - rtg / s6 + (rtg - gtg) / (2 * s6);
+    grad[h->ns] = h->sp_dnoise * dF;
+  } else if (h->nn > 0) {
     const double trBmM = h->sp_scal[1], trBinv = h->sp_scal[2], rtg = h->sp_scal[3], gtg = h->sp_scal[4];
     const double t0 = (double)N * h->sp_csum, s6 = s2 * s2 * s2;
     const double dF = ((double)M - trBinv) / (2 * s2) - (double)N / (2 * s2) + h->sp_yty / (2 * s2 * s2) - rtg / s6 +
@@ -3252,12 +3426,22 @@ static int sparse_gradient_impl(gogp_handle *h, const char *who, double *grad, i
 
 extern "C" int gogp_sparse_gradient(gogp_handle *h, double *grad, int64_t len) {
   if (!h || !grad) return fail(h, GOGP_EARG, "sparse_gradient: NULL");
-  return sparse_gradient_impl(h, "sparse_gradient", grad, len, nullptr);
+  return sparse_gradient_impl(h, "sparse_gradient", false, grad, len, nullptr);
+}
+
+extern "C" int gogp_sparse_multi_gradient(gogp_handle *h, double *grad, int64_t len) {
+  if (!h || !grad) return fail(h, GOGP_EARG, "sparse_multi_gradient: NULL");
+  return sparse_gradient_impl(h, "sparse_multi_gradient", true, grad, len, nullptr);
 }
 
 extern "C" int gogp_sparse_gradient_inducing(gogp_handle *h, double *grad, int64_t len, double *dU) {
   if (!h || !grad || !dU) return fail(h, GOGP_EARG, "sparse_gradient_inducing: NULL");
-  return sparse_gradient_impl(h, "sparse_gradient_inducing", grad, len, dU);
+  return sparse_gradient_impl(h, "sparse_gradient_inducing", false, grad, len, dU);
+}
+
+extern "C" int gogp_sparse_multi_gradient_inducing(gogp_handle *h, double *grad, int64_t len, double *dU) {
+  if (!h || !grad || !dU) return fail(h, GOGP_EARG, "sparse_multi_gradient_inducing: NULL");
+  return sparse_gradient_impl(h, "sparse_multi_gradient_inducing", true, grad, len, dU);
 }
 
 // The inducing points alone: the inducing process is given (U, y = 0) again -- its buffers are sized by M, which stays --
@@ -3271,7 +3455,7 @@ extern "C" int gogp_sparse_set_inducing(gogp_handle *h, const double *U, int64_t
   for (int64_t i = 0; i < M * h->D; ++i)
     if (!std::isfinite(U[i])) return fail(h, GOGP_EARG, "sparse_set_inducing: non-finite inducing point");
   HIPCHK(h, hipSetDevice(h->device));
-  h->sp_observed = false;
+  h->sp_observed = h->sp_mobserved = false;
   std::vector<double> y0((size_t)M, 0.0);
   const int rc = gogp_set_data(h->sp_ind, U, y0.data(), M);
   return rc == GOGP_OK ? rc : sparse_fail_from(h, "sparse_set_inducing", rc);
@@ -3312,6 +3496,55 @@ extern "C" int gogp_sparse_produce(gogp_handle *h, const double *Z, int64_t m, d
                  (const double *)b.Binv, Mp, 0.0, ind->KsT, Mp, nullptr, &gm);
   launch_sparse_predict(s, ind->KsT, ind->Vt, Mp, M, m, pp.prior, pp.q, dot, 1.0 / h->sp_s2, pp.mu, pp.sigma);
   HIPCHK(h, hipMemcpyAsync(mu, pp.mu, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipMemcpyAsync(sigma, pp.sigma, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipStreamSynchronize(s));
+  HIPCHK(h, hipGetLastError());
+  return GOGP_OK;
+}
+
+// gogp_sparse_produce for the T outputs of the multi observe: sigma as there (the outputs share it), the m x T means
+// from one product, mu = Vt Gamma / s2.
+extern "C" int gogp_sparse_multi_produce(gogp_handle *h, const double *Z, int64_t m, double *mu, double *sigma) {
+  if (!h || m < 0 || (m > 0 && (!Z || !mu || !sigma))) return fail(h, GOGP_EARG, "sparse_multi_produce: NULL");
+  if (sparse_refusal(h)) return sparse_refuse(h, "sparse_multi_produce");
+  if (!h->sp_have) return fail(h, GOGP_ESTATE, "sparse_multi_produce: no sparse data (gogp_sparse_set_data)");
+  if (h->sp_T < 1) return fail(h, GOGP_ESTATE, "sparse_multi_produce: no outputs (gogp_sparse_multi_set_outputs)");
+  if (!h->sp_mobserved) return fail(h, GOGP_ESTATE, "sparse_multi_produce before sparse_multi_observe");
+  for (int64_t i = 0; i < m * h->D; ++i)
+    if (!std::isfinite(Z[i])) return fail(h, GOGP_EARG, "sparse_multi_produce: non-finite test point");
+  if (m == 0) return GOGP_OK;
+  gogp_handle *ind = h->sp_ind;
+  const int64_t M = h->sp_M, Mp = sparse_mp(h);
+  const int nT = h->sp_T;
+  ProducePlan pp;
+  int rc = produce_prepare(ind, nullptr, "sparse_multi_produce", m, false, &pp);
+  if (rc != GOGP_OK) return sparse_fail_from(h, "sparse_multi_produce", rc);
+  rc = h->sp_mmu.reserve(h, (size_t)pp.mpad * SM_TP * sizeof(double));
+  if (rc != GOGP_OK) return rc;
+  hipStream_t s = ind->s;
+  const bool empty = h->sp_N == 0;
+  rc = produce_forward(ind, Z, m, pp, true, !empty);
+  if (rc != GOGP_OK) return sparse_fail_from(h, "sparse_multi_produce", rc);
+  if (empty) {  // no observations: the prior, a zero mean for every output
+    std::vector<double> mu0((size_t)m);
+    rc = produce_of_the_prior(ind, pp, m, mu0.data(), sigma);
+    for (int64_t i = 0; i < m * nT; ++i) mu[i] = 0.0;
+    return rc == GOGP_OK ? rc : sparse_fail_from(h, "sparse_multi_produce", rc);
+  }
+  SparseBufs b;
+  sparse_layout(h->sp_ws.as<double>(), Mp, &b);
+  SparseMultiBufs mb;
+  sparse_multi_layout(h->sp_mws.as<double>(), Mp, &mb);
+  double *dmu = h->sp_mmu.as<double>();
+  GemmGrid gm;
+  gm.small_below = ind->produce_small_below;
+  launch_gemm_nt(s, GEMM_RECT, (int)(pp.mpad / TILE), 1, Mp, 1.0 / h->sp_s2, (const double *)ind->Vt, Mp, (const double *)mb.Gt,
+                 Mp, 0.0, dmu, SM_TP, nullptr, &gm);
+  launch_gemm_nt(s, GEMM_RECT, (int)(pp.mpad / TILE), (int)(Mp / TILE), Mp, 1.0, (const double *)ind->Vt, Mp,
+                 (const double *)b.Binv, Mp, 0.0, ind->KsT, Mp, nullptr, &gm);
+  launch_sparse_multi_sigma(s, ind->KsT, ind->Vt, Mp, M, m, pp.prior, pp.q, pp.sigma);
+  HIPCHK(h, hipMemcpy2DAsync(mu, (size_t)nT * sizeof(double), dmu, (size_t)SM_TP * sizeof(double), (size_t)nT * sizeof(double),
+                             (size_t)m, hipMemcpyDeviceToHost, s));
   HIPCHK(h, hipMemcpyAsync(sigma, pp.sigma, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
   HIPCHK(h, hipStreamSynchronize(s));
   HIPCHK(h, hipGetLastError());
@@ -4066,7 +4299,7 @@ extern "C" int gogp_set_option(gogp_handle *h, const char *name, int64_t value) 
   if (strcmp(name, "sparse_jitter_log10") == 0) {  // gogp_sparse_*: Kuu + 10^value I is factored (absolute), from the next sparse_observe on
     if (value < -14 || value > -2) return fail(h, GOGP_EARG, "sparse_jitter_log10 must be -14..-2");
     h->sp_jitter_log10 = (int)value;
-    h->sp_observed = false;
+    h->sp_observed = h->sp_mobserved = false;
     return GOGP_OK;
   }
   if (strcmp(name, "sparse_chunk") == 0) {  // gogp_sparse_*: rows of X per pass

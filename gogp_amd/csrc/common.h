@@ -474,6 +474,28 @@ void launch_sparse_sumsq(hipStream_t s, const double *y, int64_t n, double *out)
 void launch_sparse_predict(hipStream_t s, const double *A, const double *V, int64_t ld, int64_t ncols, int64_t m,
                            const double *prior, const double *q, const double *dot, double inv_s2, double *mu,
                            double *sigma);
+// Multi-output (gogp_sparse_multi_*).  launch_sparse_xty: Rt (T rounded up to 64 rows of ldr doubles; the columns below
+// M rounded up to 64) += Yc^T Vt, Yc: rows x T of ldy doubles per row; rows >= `rows` are not read, columns >= M of Vt and
+// >= T of Yc count as exact zeros.  One workgroup per (inducing tile, output tile, slab of rows); the slabs' sums are
+// added in index order.  part: sparse_xty_part_doubles(rows, M, T) doubles of scratch, which covers every launch of up
+// to `rows` rows (sparse_xty_slabs_bound >= sparse_xty_slabs(r, M, T) for every r <= rows).
+int sparse_xty_slabs(int64_t rows, int64_t M, int64_t T, int64_t *rows_per_slab);
+int sparse_xty_slabs_bound(int64_t rows, int64_t M, int64_t T);
+size_t sparse_xty_part_doubles(int64_t rows, int64_t M, int64_t T);
+void launch_sparse_xty(hipStream_t s, const double *Vt, int64_t ld, int64_t rows, int64_t M, const double *Y, int64_t ldy,
+                       int64_t T, double *part, double *Rt, int64_t ldr);
+// Tm = T (I - Binv) - GG s4 and S = T (2 I - B - Binv) - GG s4; out[t] = r_t . gamma_t and out[tstride + t] = gamma_t .
+// gamma_t from the rows of Rt / Gt; out[t] = sum_i Y[i][t]^2; Yp (rpad x kp, ldp) = the rows of Y padded with exact
+// zeros (rpad a multiple of 128, kp of 16); sigma of launch_sparse_predict alone.
+void launch_sparse_multi_weights(hipStream_t s, const double *B, const double *Binv, const double *GG, int64_t Mp, int T,
+                                 double s4, double *Tm, double *S);
+void launch_sparse_multi_dots(hipStream_t s, const double *Rt, const double *Gt, int64_t ld, int64_t M, int T, int tstride,
+                              double *out);
+void launch_sparse_multi_sumsq(hipStream_t s, const double *Y, int64_t ldy, int64_t n, int T, double *out);
+void launch_sparse_multi_pad(hipStream_t s, const double *Y, int64_t ldy, int64_t rows, int64_t T, int64_t kp, int64_t rpad,
+                             double *Yp, int64_t ldp);
+void launch_sparse_multi_sigma(hipStream_t s, const double *A, const double *V, int64_t ld, int64_t ncols, int64_t m,
+                               const double *prior, const double *q, double *sigma);
 void launch_fill(hipStream_t s, double *p, int64_t count, double v);
 void launch_axpy(hipStream_t s, double *a, const double *b, int64_t count);  // a += b
 void launch_dot(hipStream_t s, const double *a, const double *b, int64_t n, double *out);  // out[0] = a.b

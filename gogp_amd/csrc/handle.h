@@ -239,6 +239,16 @@ struct gogp_handle : EvalBufs, EvalState {
   double sp_s2 = 0.0, sp_dnoise = 0.0, sp_csum = 0.0;  // of the last gogp_sparse_observe: noise variance, its derivative, sum of the output scales
   double sp_scal[5] = {};          // ... and its scalars (sparse.hip: sparse_scalars_kernel)
   std::vector<double> sp_cterm;    // ... and every term's output scale
+  // gogp_sparse_multi_*: T output columns on the sparse data (api.hip).  sp_observed / sp_mobserved: whose observe the
+  // shared Mp x Mp workspace holds -- the last observe of either flavour clears the other's flag.
+  double *sp_Y = nullptr;          // N x T row-major as given, resident
+  int sp_T = 0;
+  bool sp_mobserved = false;
+  std::vector<double> sp_myty;     // y_t^T y_t, from gogp_sparse_multi_set_outputs
+  std::vector<double> sp_mdots;    // of the last gogp_sparse_multi_observe: r_t^T gamma_t (T), then gamma_t^T gamma_t (T)
+  Workspace sp_mws;                // state of the multi observe, sized by gogp_sparse_multi_set_outputs (api.hip: SparseMultiBufs)
+  Workspace sp_mscr;               // scratch sized by the chunk: the partials of launch_sparse_xty, the padded chunk of Y
+  Workspace sp_mmu;                // gogp_sparse_multi_produce: mpad x 128 means
   double yta = 0.0;      // y^T alpha of the last factorisation (fp32 path: of the refined alpha)
   int trace_fp64 = 1;    // fp32 path: tr(alpha alpha^T - K^-1) summed in fp64 from Y, scale component by its identity
   double cond_limit = 1e16;  // gonum's mat.ConditionTolerance

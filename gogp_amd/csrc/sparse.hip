@@ -10,6 +10,9 @@
 //                        into the NACC slot layout of common.h;
 //   sparse_ugrad_kernel  the same pairs and weights on dk(u_u, x_f)/du_u: the (U, X) part of d bound / d U.
 // The rest are the element-wise passes over the M x M matrices and the M vectors.
+// Multi-output (gogp_sparse_multi_*: T columns Y on the same pass; DESIGN.md section 4, "Sparse multi-output") adds
+//   sparse_xty_kernel    R^T (T x Mp) += Yc^T Vt on the same MFMA and LDS layout, K split into slabs added in order,
+// and small kernels for T and S with Gamma Gamma^T, the per-output dots, the padded chunk of Y and Produce's sigma.
 //
 // Every sum has a fixed order (no atomics): two identical calls give the same bits.
 #include <algorithm>
@@ -96,6 +99,104 @@ void launch_sparse_syrk(hipStream_t s, const double *Vt, int64_t ld, int64_t row
   const int nt = (int)(Mp / 64);
   GOGP_KLAUNCH(sparse_syrk_kernel, dim3((unsigned)(nt * (nt + 1) / 2)), dim3(256), 0, s, Vt, (long)ld, (long)rows, (long)M,
                y, Bacc, (long)ldb, r);
+}
+
+// ---- multi-output: R^T (+)= Yc^T Vt ---------------------------------------------------------------------------------------
+// part[slab] (ldp doubles per row) = Yc^T Vt over the rows of the slab, on the 64 x 64 tile (output tile blockIdx.y,
+// inducing tile blockIdx.x): part[slab][t][j] = sum_k Yc[k][t] Vt[k][j], k in [slab * rps, min(rows, (slab + 1) * rps)).
+// Vt as sparse_syrk_kernel takes it, Yc: rows x T with ldy doubles per row; both k-major, so both slices are kept as they
+// lie in memory (sparse_syrk_kernel's LDS layout and fragment maps; the A operand is the slice of Yc, so the C fragment's
+// consecutive columns are consecutive inducing points and the stores run along a row of R^T).  Rows >= `rows` are never
+// read; columns >= M of Vt and >= T of Yc are replaced by exact zeros on the way into LDS, so the padded elements of
+// the tile receive exact zeros.  rps is a multiple of SS_KC.  Every element of the tile is written: the partials need no
+// clearing, and sparse_xty_final_kernel adds the slabs in index order.
+__global__ __launch_bounds__(256, 2) void sparse_xty_kernel(const double *__restrict__ Vt, long ld, long rows, long M,
+                                                            const double *__restrict__ Y, long ldy, long T, long rps,
+                                                            double *__restrict__ part, long ldp, long slab_stride) {
+  __shared__ double As[SS_KC * SS_S], Bs[SS_KC * SS_S];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const long c0 = (long)blockIdx.x * 64, t0 = (long)blockIdx.y * 64;
+  const long kb = (long)blockIdx.z * rps, ke = kb + rps < rows ? kb + rps : rows;
+  const int fr = lane & 15, fk = lane >> 4;
+  const bool alive = t0 + lane < T, blive = c0 + lane < M;
+  sp_f64x4 acc[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) acc[t] = (sp_f64x4){0.0, 0.0, 0.0, 0.0};
+  for (long k0 = kb; k0 < ke; k0 += SS_KC) {
+    if (k0 > kb) __syncthreads();  // the previous pass's readers are done
+#pragma unroll
+    for (int rr = 0; rr < SS_KC / 4; ++rr) {
+      const int k = w + 4 * rr;
+      const bool klive = k0 + k < ke;
+      As[k * SS_S + lane] = (klive && alive) ? Y[(k0 + k) * ldy + t0 + lane] : 0.0;
+      Bs[k * SS_S + lane] = (klive && blive) ? Vt[(k0 + k) * ld + c0 + lane] : 0.0;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int kk = 0; kk < SS_KC; kk += 4) {
+      const double a = As[(kk + fk) * SS_S + 16 * w + fr];
+#pragma unroll
+      for (int t = 0; t < 4; ++t)
+        acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, Bs[(kk + fk) * SS_S + 16 * t + fr], acc[t], 0, 0, 0);
+    }
+  }
+  // C fragment: column = lane & 15, row = (lane >> 4) + 4 v
+  double *out = part + (long)blockIdx.z * slab_stride;
+#pragma unroll
+  for (int v = 0; v < 4; ++v) {
+    const long gi = t0 + 16 * w + fk + 4 * v;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) out[gi * ldp + c0 + 16 * t + fr] = acc[t][v];
+  }
+}
+
+// Rt[t][j] += the slabs' sums in index order, t < tt, j < mc
+__global__ __launch_bounds__(256) void sparse_xty_final_kernel(const double *__restrict__ part, int nslab, long slab_stride,
+                                                               long ldp, long tt, long mc, double *__restrict__ Rt,
+                                                               long ldr) {
+  const long j = (long)blockIdx.x * 256 + threadIdx.x, t = blockIdx.y;
+  if (j >= mc || t >= tt) return;
+  double v = 0.0;
+  for (int sl = 0; sl < nslab; ++sl) v += part[(long)sl * slab_stride + t * ldp + j];
+  Rt[t * ldr + j] += v;
+}
+
+// The slabs of launch_sparse_xty and the rows of one (*rps_out, a multiple of SS_KC): a function of (rows, M, T) alone.
+// The grid (tiles x slabs) stays near SX_BLOCKS workgroups, two per CU's SIMD pair, and a slab has SX_ROWS_MIN rows at
+// least, so that a workgroup's epilogue stays small beside its k loop.
+constexpr int SX_BLOCKS = 1024, SX_ROWS_MIN = 256;
+static int64_t sx_most(int64_t M, int64_t T) {
+  const int64_t tiles = std::max<int64_t>(1, ((M + 63) / 64) * ((T + 63) / 64));
+  return std::max<int64_t>(1, SX_BLOCKS / tiles);
+}
+int sparse_xty_slabs(int64_t rows, int64_t M, int64_t T, int64_t *rps_out) {
+  const int64_t most = sx_most(M, T);
+  const int64_t per = ((rows + most - 1) / most + SS_KC - 1) / SS_KC * SS_KC;
+  const int64_t rps = std::max<int64_t>(SX_ROWS_MIN, per);
+  if (rps_out) *rps_out = rps;
+  return (int)std::max<int64_t>(1, (rows + rps - 1) / rps);
+}
+// An upper bound of sparse_xty_slabs(r, M, T) over every r <= rows, monotone in the rows: a slab has SX_ROWS_MIN rows
+// at least, so the count is at most ceil(r / SX_ROWS_MIN); with rps == SX_ROWS_MIN, r <= SX_ROWS_MIN * most, so that is
+// within `most`, and with rps >= ceil(r / most) the count ceil(r / rps) is within `most` too.
+int sparse_xty_slabs_bound(int64_t rows, int64_t M, int64_t T) {
+  return (int)std::max<int64_t>(1, std::min<int64_t>((rows + SX_ROWS_MIN - 1) / SX_ROWS_MIN, sx_most(M, T)));
+}
+// doubles of the partials of one launch of up to `rows` rows
+size_t sparse_xty_part_doubles(int64_t rows, int64_t M, int64_t T) {
+  return (size_t)sparse_xty_slabs_bound(rows, M, T) * (size_t)((T + 63) / 64 * 64) * (size_t)((M + 63) / 64 * 64);
+}
+
+void launch_sparse_xty(hipStream_t s, const double *Vt, int64_t ld, int64_t rows, int64_t M, const double *Y, int64_t ldy,
+                       int64_t T, double *part, double *Rt, int64_t ldr) {
+  if (rows <= 0 || M <= 0 || T <= 0) return;
+  int64_t rps = 0;
+  const int nslab = sparse_xty_slabs(rows, M, T, &rps);
+  const long mc = (long)((M + 63) / 64 * 64), tt = (long)((T + 63) / 64 * 64);
+  GOGP_KLAUNCH(sparse_xty_kernel, dim3((unsigned)(mc / 64), (unsigned)(tt / 64), (unsigned)nslab), dim3(256), 0, s, Vt,
+               (long)ld, (long)rows, (long)M, Y, (long)ldy, (long)T, (long)rps, part, mc, tt * mc);
+  GOGP_KLAUNCH(sparse_xty_final_kernel, dim3((unsigned)((mc + 255) / 256), (unsigned)tt), dim3(256), 0, s, part, nslab,
+               tt * mc, mc, tt, mc, Rt, (long)ldr);
 }
 
 // ---- the rectangular pair reduction ----------------------------------------------------------------------------------
@@ -462,6 +563,103 @@ __global__ __launch_bounds__(256) void sparse_predict_kernel(const double *__res
     mu[j] = dot[j] * inv_s2;
     sigma[j] = sqrt(prior[j] - q[j] + t);
   }
+}
+
+// ---- multi-output: the small kernels ------------------------------------------------------------------------------------
+// Tm = nT (I - Binv) - GG s4 and S = nT (2 I - B - Binv) - GG s4, GG = Gamma Gamma^T, nT = the number of outputs
+__global__ __launch_bounds__(256) void sparse_multi_weights_kernel(const double *__restrict__ B,
+                                                                   const double *__restrict__ Binv,
+                                                                   const double *__restrict__ GG, long Mp, double nT,
+                                                                   double s4, double *__restrict__ Tm,
+                                                                   double *__restrict__ S) {
+  const long i = blockIdx.y, j = (long)blockIdx.x * 256 + threadIdx.x;
+  if (j >= Mp) return;
+  const double e = i == j ? 1.0 : 0.0, bi = Binv[i * Mp + j], gg = GG[i * Mp + j] * s4;
+  Tm[i * Mp + j] = nT * (e - bi) - gg;
+  S[i * Mp + j] = nT * (2.0 * e - B[i * Mp + j] - bi) - gg;
+}
+// out[t] = r_t^T gamma_t and out[tstride + t] = gamma_t^T gamma_t over i < M, the rows t of Rt and Gt (ld doubles per
+// row): one workgroup per output, every thread its elements i = tid, tid + 256, .. in that order, then a fixed tree
+__global__ __launch_bounds__(256) void sparse_multi_dots_kernel(const double *__restrict__ Rt, const double *__restrict__ Gt,
+                                                                long ld, long M, int tstride, double *__restrict__ out) {
+  __shared__ double red[4][2];
+  const long t = blockIdx.x;
+  double a = 0.0, c = 0.0;
+  for (long i = threadIdx.x; i < M; i += 256) {
+    const double g = Gt[t * ld + i];
+    a += Rt[t * ld + i] * g;
+    c += g * g;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    a += __shfl_xor(a, o);
+    c += __shfl_xor(c, o);
+  }
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][0] = a, red[threadIdx.x >> 6][1] = c;
+  __syncthreads();
+  if (threadIdx.x < 2)
+    out[threadIdx.x * tstride + t] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+}
+// out[t] = sum_{i < n} Y[i][t]^2 (Y: n x T, ldy doubles per row), the same summation, one workgroup per output
+__global__ __launch_bounds__(256) void sparse_multi_sumsq_kernel(const double *__restrict__ Y, long ldy, long n,
+                                                                 double *__restrict__ out) {
+  __shared__ double red[4];
+  const long t = blockIdx.x;
+  double v = 0.0;
+  for (long i = threadIdx.x; i < n; i += 256) v += Y[i * ldy + t] * Y[i * ldy + t];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  if (threadIdx.x == 0) out[t] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+// Yp (rpad rows of ldp doubles) = the chunk's rows of Y (rows x T, ldy doubles per row), exact zeros in the rows from
+// `rows` on and the columns T .. kp - 1: the A operand of the second pass's rank-T launch
+__global__ __launch_bounds__(256) void sparse_multi_pad_kernel(const double *__restrict__ Y, long ldy, long rows, long T,
+                                                               long kp, double *__restrict__ Yp, long ldp) {
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x, i = idx / kp, k = idx - i * kp;  // idx < rpad * kp: the grid
+  Yp[i * ldp + k] = (i < rows && k < T) ? Y[i * ldy + k] : 0.0;
+}
+// Produce: sigma_j of sparse_predict_kernel alone (the outputs share it; their means come from one product)
+__global__ __launch_bounds__(256) void sparse_multi_sigma_kernel(const double *__restrict__ A, const double *__restrict__ V,
+                                                                 long ld, long ncols, long m,
+                                                                 const double *__restrict__ prior,
+                                                                 const double *__restrict__ q, double *__restrict__ sigma) {
+  const long j = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (j >= m) return;
+  const int lane = threadIdx.x & 63;
+  double t = 0.0;
+  for (long i = lane; i < ncols; i += 64) t += A[j * ld + i] * V[j * ld + i];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o);
+  if (lane == 0) sigma[j] = sqrt(prior[j] - q[j] + t);
+}
+
+void launch_sparse_multi_weights(hipStream_t s, const double *B, const double *Binv, const double *GG, int64_t Mp, int T,
+                                 double s4, double *Tm, double *S) {
+  GOGP_KLAUNCH(sparse_multi_weights_kernel, dim3((unsigned)(Mp / 256), (unsigned)Mp), dim3(256), 0, s, B, Binv, GG, (long)Mp,
+               (double)T, s4, Tm, S);
+}
+void launch_sparse_multi_dots(hipStream_t s, const double *Rt, const double *Gt, int64_t ld, int64_t M, int T, int tstride,
+                              double *out) {
+  if (T <= 0) return;
+  GOGP_KLAUNCH(sparse_multi_dots_kernel, dim3((unsigned)T), dim3(256), 0, s, Rt, Gt, (long)ld, (long)M, tstride, out);
+}
+void launch_sparse_multi_sumsq(hipStream_t s, const double *Y, int64_t ldy, int64_t n, int T, double *out) {
+  if (T <= 0) return;
+  GOGP_KLAUNCH(sparse_multi_sumsq_kernel, dim3((unsigned)T), dim3(256), 0, s, Y, (long)ldy, (long)n, out);
+}
+void launch_sparse_multi_pad(hipStream_t s, const double *Y, int64_t ldy, int64_t rows, int64_t T, int64_t kp, int64_t rpad,
+                             double *Yp, int64_t ldp) {
+  if (rpad <= 0 || kp <= 0 || (rpad * kp) % 256) return;  // (rpad a multiple of 128 and kp of 16: whole workgroups)
+  GOGP_KLAUNCH(sparse_multi_pad_kernel, dim3((unsigned)(rpad * kp / 256)), dim3(256), 0, s, Y, (long)ldy, (long)rows,
+               (long)T, (long)kp, Yp, (long)ldp);
+}
+void launch_sparse_multi_sigma(hipStream_t s, const double *A, const double *V, int64_t ld, int64_t ncols, int64_t m,
+                               const double *prior, const double *q, double *sigma) {
+  if (m <= 0) return;
+  GOGP_KLAUNCH(sparse_multi_sigma_kernel, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, s, A, V, (long)ld, (long)ncols, (long)m,
+               prior, q, sigma);
 }
 
 void launch_sparse_finish_b(hipStream_t s, const double *Bacc, int64_t Mp, double inv_s2, double *B) {

@@ -1476,6 +1476,83 @@ extern "C" int gogp_test_sparse_ugrad(int device, const gogp_test_kparams *kpara
   return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
 }
 
+// launch_sparse_xty on host arrays: R (in / out) += Y^T Vt.  The partials are sized as the product sizes them.
+extern "C" int gogp_test_sparse_xty(int device, const double *Vt, int64_t vt_len, int64_t ld, int64_t rows, int64_t M,
+                                    int64_t Mp, const double *Y, int64_t y_len, int64_t ldy, int64_t T, double *R,
+                                    int64_t r_len, int64_t ldr) {
+  if (!Vt || !Y || !R) return GOGP_EARG;
+  if (Mp <= 0 || Mp % 64 || Mp > GOGP_SPARSE_MAX_M || M < 1 || M > Mp || rows < 1 || rows > (1 << 16)) return GOGP_EARG;
+  if (T < 1 || T > GOGP_SPARSE_MULTI_MAX_T) return GOGP_EARG;
+  const int64_t tt = (T + 63) / 64 * 64, mc = (M + 63) / 64 * 64;
+  if (!covers(vt_len, 0, ld, rows, M, 1, 0) || !covers(y_len, 0, ldy, rows, T, 1, 0) || !covers(r_len, 0, ldr, tt, mc, 1, 0))
+    return GOGP_EARG;
+  if (!device_ok(device)) return GOGP_EHIP;
+  DevCopy dV, dY, dR;
+  double *part = nullptr;
+  hipError_t e = dV.up(Vt, (size_t)vt_len * sizeof(double));
+  if (e == hipSuccess) e = dY.up(Y, (size_t)y_len * sizeof(double));
+  if (e == hipSuccess) e = dR.up(R, (size_t)r_len * sizeof(double));
+  if (e == hipSuccess) e = hipMalloc(&part, sparse_xty_part_doubles(rows, M, T) * sizeof(double));
+  if (e == hipSuccess) {
+    launch_sparse_xty(0, dV.as<double>(), ld, rows, M, dY.as<double>(), ldy, T, part, dR.as<double>(), ldr);
+    e = launched();
+  }
+  if (e == hipSuccess) e = dR.down(R);
+  (void)hipFree(part);
+  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+}
+
+extern "C" int gogp_test_sparse_xty_slabs(int64_t rows, int64_t M, int64_t T, int64_t *rows_per_slab) {
+  if (rows < 1 || rows > (1 << 16) || M < 1 || M > GOGP_SPARSE_MAX_M || T < 1 || T > GOGP_SPARSE_MULTI_MAX_T) return 0;
+  return sparse_xty_slabs(rows, M, T, rows_per_slab);
+}
+
+extern "C" int gogp_test_sparse_xty_slabs_bound(int64_t rows, int64_t M, int64_t T) {
+  if (rows < 1 || rows > (1 << 16) || M < 1 || M > GOGP_SPARSE_MAX_M || T < 1 || T > GOGP_SPARSE_MULTI_MAX_T) return 0;
+  return sparse_xty_slabs_bound(rows, M, T);
+}
+
+// Benchmark hook for launch_sparse_xty (the kernel and its ordered final sum): `reps` launches on device buffers (Vt: rows
+// x Mp, Mp = M rounded up to 256; Y: rows x T); ms per launch and TFLOP/s on 2 rows M T flops
+extern "C" int gogp_bench_sparse_xty(int device, int64_t rows, int64_t M, int64_t T, int reps, double *ms_per_launch,
+                                     double *tflops) {
+  if (rows < 1 || rows > (1 << 16) || M < 1 || M > GOGP_SPARSE_MAX_M || T < 1 || T > GOGP_SPARSE_MULTI_MAX_T || reps < 1)
+    return GOGP_EARG;
+  if (!device_ok(device)) return GOGP_EHIP;
+  const int64_t Mp = (M + PANEL - 1) / PANEL * PANEL;
+  double *dV = nullptr, *dY = nullptr, *dR = nullptr, *dP = nullptr;
+  hipError_t e = hipMalloc(&dV, (size_t)rows * Mp * sizeof(double));
+  if (e == hipSuccess) e = hipMalloc(&dY, (size_t)rows * T * sizeof(double));
+  if (e == hipSuccess) e = hipMalloc(&dR, (size_t)GOGP_SPARSE_MULTI_MAX_T * Mp * sizeof(double));
+  if (e == hipSuccess) e = hipMalloc(&dP, sparse_xty_part_doubles(rows, M, T) * sizeof(double));
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  float ms = 0.f;
+  if (e == hipSuccess) {
+    launch_fill(0, dV, rows * Mp, 0.5);
+    launch_fill(0, dY, rows * T, 0.25);
+    launch_fill(0, dR, GOGP_SPARSE_MULTI_MAX_T * Mp, 0.0);
+    (void)hipEventCreate(&e0);
+    (void)hipEventCreate(&e1);
+    for (int w = 0; w < 2; ++w) launch_sparse_xty(0, dV, Mp, rows, M, dY, T, T, dP, dR, Mp);
+    (void)hipDeviceSynchronize();
+    (void)hipEventRecord(e0, 0);
+    for (int r = 0; r < reps; ++r) launch_sparse_xty(0, dV, Mp, rows, M, dY, T, T, dP, dR, Mp);
+    (void)hipEventRecord(e1, 0);
+    e = hipEventSynchronize(e1);
+    (void)hipEventElapsedTime(&ms, e0, e1);
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+  }
+  (void)hipFree(dV);
+  (void)hipFree(dY);
+  (void)hipFree(dR);
+  (void)hipFree(dP);
+  if (e != hipSuccess) return e == hipErrorOutOfMemory ? GOGP_ENOMEM : GOGP_EHIP;
+  if (ms_per_launch) *ms_per_launch = ms / reps;
+  if (tflops) *tflops = 2.0 * (double)rows * (double)M * (double)T * reps / (ms * 1e-3) / 1e12;
+  return GOGP_OK;
+}
+
 // Benchmark hook for sparse_syrk_kernel: `reps` launches on device buffers (Vt: rows x Mp, Mp = M rounded up to 256);
 // ms per launch and TFLOP/s on the flops of the lower 64-tiles
 extern "C" int gogp_bench_sparse_syrk(int device, int64_t rows, int64_t M, int reps, double *ms_per_launch, double *tflops) {

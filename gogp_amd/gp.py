@@ -80,6 +80,7 @@ class GP:
         #: HIP device index of the handle (-1: the device current at construction)
         self.device = int(device)
         self._sparse_m = 0  # inducing points of SetSparse
+        self._sparse_t = 0  # output columns of SetSparseOutputs
         self._h = ctypes.c_void_p()
         L = _lib.lib()
         rc = L.gogp_create(ctypes.byref(self._desc), int(device), ctypes.byref(self._h))
@@ -448,7 +449,7 @@ class GP:
         L = _lib.lib()
         if U is None:
             self._check(L.gogp_sparse_set_data(self._h, None, None, 0, None, 0))
-            self._sparse_m = 0
+            self._sparse_m = self._sparse_t = 0
             return
         u = np.ascontiguousarray(_arr(U).reshape(-1, self.NDim))
         x = np.ascontiguousarray(_arr(X).reshape(-1, self.NDim))
@@ -459,6 +460,7 @@ class GP:
         self._check(L.gogp_sparse_set_data(self._h, _dp(x) if n else None, _dp(y) if n else None, n,
                                            _dp(u if len(u) else np.zeros(1)), len(u)))
         self._sparse_m = len(u)
+        self._sparse_t = 0  # (the library drops the outputs of SetSparseOutputs with the data they rode on)
 
     def SetInducing(self, U) -> None:
         """Replace the inducing points of SetSparse by U (M x NDim, the same M) and nothing else
@@ -501,6 +503,64 @@ class GP:
         mu, sigma = np.zeros(m), np.zeros(m)
         self._check(_lib.lib().gogp_sparse_produce(self._h, _dp(z) if m else None, m, _dp(mu) if m else None,
                                                    _dp(sigma) if m else None))
+        return mu, sigma
+
+    # ---- sparse multi-output: T output columns on one pass over the sparse data ----
+    def SetSparseOutputs(self, Y) -> None:
+        """The T <= 128 output columns observed at the inputs of SetSparse (gogp_sparse_multi_set_outputs): Y is N x T
+        (a vector is one column), copied to the device as given.  ``Y = None`` clears them; SetSparse drops them,
+        SetInducing keeps them."""
+        L = _lib.lib()
+        if Y is None:
+            self._check(L.gogp_sparse_multi_set_outputs(self._h, None, 0, 0))
+            self._sparse_t = 0
+            return
+        ya = _arr(Y)
+        if ya.ndim == 1:
+            ya = ya.reshape(-1, 1)
+        if ya.ndim != 2:
+            raise ValueError("SetSparseOutputs: Y must be N x T")
+        ya = np.ascontiguousarray(ya)
+        buf = ya if ya.size else np.zeros(1)  # (no observations: a pointer the library may look at)
+        self._check(L.gogp_sparse_multi_set_outputs(self._h, _dp(buf), ya.shape[0], ya.shape[1]))
+        self._sparse_t = ya.shape[1]
+
+    def SparseMultiObserve(self, x):
+        """(total, bounds): the collapsed bound of every output column at x = log theta and their sum in column order
+        (gogp_sparse_multi_observe): one pass over the data for all of them."""
+        xa = np.ascontiguousarray(_arr(x).reshape(-1))
+        T = getattr(self, "_sparse_t", 0)
+        total, per = ctypes.c_double(0.0), np.zeros(max(T, 1))
+        self._check(_lib.lib().gogp_sparse_multi_observe(self._h, _dp(xa if xa.size else np.zeros(1)), xa.size,
+                                                         ctypes.byref(total), _dp(per)))
+        return total.value, per[:T]
+
+    def SparseMultiGradient(self) -> np.ndarray:
+        """d total / d log theta at the parameters of the last SparseMultiObserve (gogp_sparse_multi_gradient)."""
+        g = np.zeros(self._ns + self._nn)
+        self._check(_lib.lib().gogp_sparse_multi_gradient(self._h, _dp(g if g.size else np.zeros(1)), g.size))
+        return g
+
+    def SparseMultiGradientInducing(self):
+        """(grad, dU): SparseMultiGradient() and, from the same pass over the data, the derivative of the total in the
+        inducing points, M x NDim (gogp_sparse_multi_gradient_inducing); the caveats of SparseGradientInducing."""
+        g = np.zeros(self._ns + self._nn)
+        if getattr(self, "_sparse_m", 0) < 1:  # (the library writes M x NDim doubles: never into a buffer sized without M)
+            raise GogpError(_lib.GOGP_ESTATE, "SparseMultiGradientInducing before SetSparse")
+        du = np.zeros((self._sparse_m, self.NDim))
+        self._check(_lib.lib().gogp_sparse_multi_gradient_inducing(self._h, _dp(g if g.size else np.zeros(1)), g.size,
+                                                                   _dp(du)))
+        return g, du
+
+    def SparseMultiProduce(self, x):
+        """(mu, sigma): the means of every output at the test points, m x T, and the standard deviation they share, m
+        entries, latent and unclamped as SparseProduce (gogp_sparse_multi_produce)."""
+        z = np.ascontiguousarray(_arr(x).reshape(-1, self.NDim))
+        m, T = len(z), getattr(self, "_sparse_t", 0)
+        mu, sigma = np.zeros((m, T)), np.zeros(m)
+        buf = mu if mu.size else np.zeros(1)
+        self._check(_lib.lib().gogp_sparse_multi_produce(self._h, _dp(z) if m else None, m, _dp(buf) if m else None,
+                                                         _dp(sigma) if m else None))
         return mu, sigma
 
     # ---- cached computations: gp.GP.L, gp.GP.Alpha (gp/gp.go:34-37) ----------------------
@@ -836,6 +896,44 @@ class MultiModel:
         g = self.gp.MultiGradient()
         if self.Priors is not None:
             self.Priors.Observe(self._x)
+            pg = np.asarray(self.Priors.Gradient(), dtype=float)
+            g[:len(pg)] += pg
+        return g
+
+
+class SparseMultiModel:
+    """SparseModel with the sum of the bounds of the T output columns of GP.SetSparseOutputs in the place of the bound:
+    Observe(x) returns GP.SparseMultiObserve(x)'s total (+ the log prior, counted once), Gradient() returns
+    GP.SparseMultiGradient() (+ the prior's); ``inducing=True`` as in SparseModel, with GP.SparseMultiGradientInducing()."""
+
+    def __init__(self, gp: GP, Priors=None, inducing=False):
+        self.gp = gp
+        self.Priors = Priors
+        self.inducing = bool(inducing)
+        self._x = None
+
+    def Observe(self, x) -> float:
+        self._x = _arr(x).reshape(-1).copy()
+        p = self.gp._ns + self.gp._nn
+        if self.inducing:
+            m = self.gp._sparse_m
+            if self._x.size != p + m * self.gp.NDim:
+                raise ValueError("len(x): the sparse multi-output objective with inducing points takes the "
+                                 "hyperparameters and M x NDim coordinates")
+            self.gp.SetInducing(self._x[p:].reshape(m, self.gp.NDim))
+        elif self._x.size != p:
+            raise ValueError("len(x): the sparse multi-output objective takes the hyperparameters only")
+        v = self.gp.SparseMultiObserve(self._x[:p])[0]
+        return v + self.Priors.Observe(self._x[:p]) if self.Priors is not None else v
+
+    def Gradient(self) -> np.ndarray:
+        if self.inducing:
+            g, du = self.gp.SparseMultiGradientInducing()
+            g = np.concatenate([g, du.reshape(-1)])
+        else:
+            g = self.gp.SparseMultiGradient()
+        if self.Priors is not None:
+            self.Priors.Observe(self._x[:self.gp._ns + self.gp._nn])
             pg = np.asarray(self.Priors.Gradient(), dtype=float)
             g[:len(pg)] += pg
         return g

@@ -234,6 +234,7 @@ class GP {
   // N x NDim, y, u row-major M x NDim), resident on the device beside X / Y, which it does not touch; M == 0 clears it.
   void SetSparse(const std::vector<double> &x, const std::vector<double> &y, const std::vector<double> &u) {
     sparse_m_ = 0;
+    sparse_t_ = 0;  // (the library drops the outputs of SetSparseOutputs with the data)
     if (u.empty()) {
       check(gogp_sparse_set_data(h_, nullptr, nullptr, 0, nullptr, 0));
       return;
@@ -276,6 +277,51 @@ class GP {
     mu.assign(x.size(), 0.0);
     sigma.assign(x.size(), 0.0);
     return gogp_sparse_produce(h_, flat.data(), (int64_t)x.size(), mu.data(), sigma.data()) == GOGP_OK;
+  }
+
+  // Sparse multi-output (gogp_sparse_multi_*): T <= GOGP_SPARSE_MULTI_MAX_T output columns at the inputs of SetSparse on
+  // one pass over the data; no reference counterpart.  SetSparseOutputs: Yt row-major N x T with the N of SetSparse, kept
+  // on the device as given; T == 0 clears.  SetSparse drops the outputs, SetInducing keeps them.
+  void SetSparseOutputs(const std::vector<double> &Yt, int T) {
+    sparse_t_ = 0;
+    if (T == 0) {
+      check(gogp_sparse_multi_set_outputs(h_, nullptr, 0, 0));
+      return;
+    }
+    if (T < 0 || Yt.size() % (size_t)T) throw Error(GOGP_EARG, "len(Yt)");
+    const double none = 0.0;
+    check(gogp_sparse_multi_set_outputs(h_, Yt.empty() ? &none : Yt.data(), (int64_t)(Yt.size() / (size_t)T), T));
+    sparse_t_ = T;
+  }
+  // the sum of the outputs' bounds at x = log theta; bounds: one entry per output
+  double SparseMultiObserve(const std::vector<double> &x, std::vector<double> &bounds) {
+    bounds.assign((size_t)sparse_t_, 0.0);
+    double total = 0.0;
+    check(gogp_sparse_multi_observe(h_, x.data(), (int64_t)x.size(), &total, bounds.empty() ? nullptr : bounds.data()));
+    return total;
+  }
+  // d (that sum) / d log theta at the parameters of the last SparseMultiObserve
+  std::vector<double> SparseMultiGradient() {
+    std::vector<double> g(ThetaSimil.size() + ThetaNoise.size(), 0.0);
+    check(gogp_sparse_multi_gradient(h_, g.data(), (int64_t)g.size()));
+    return g;
+  }
+  // SparseMultiGradient and, from the same pass over the data, d (that sum) / d U (dU: row-major M x NDim)
+  std::vector<double> SparseMultiGradientInducing(std::vector<double> &dU) {
+    if (sparse_m_ < 1) throw Error(GOGP_ESTATE, "SparseMultiGradientInducing before SetSparse");
+    std::vector<double> g(ThetaSimil.size() + ThetaNoise.size(), 0.0);
+    dU.assign(sparse_m_ * (size_t)NDim, 0.0);
+    check(gogp_sparse_multi_gradient_inducing(h_, g.data(), (int64_t)g.size(), dU.data()));
+    return g;
+  }
+  // mu row-major x.size() x T, sigma (shared by the outputs) x.size()
+  bool SparseMultiProduce(const std::vector<std::vector<double>> &x, std::vector<double> &mu, std::vector<double> &sigma) {
+    std::vector<double> flat = pack(x);
+    mu.assign(x.size() * (size_t)sparse_t_, 0.0);
+    sigma.assign(x.size(), 0.0);
+    const double none = 0.0;
+    return gogp_sparse_multi_produce(h_, flat.data(), (int64_t)x.size(), mu.empty() ? const_cast<double *>(&none) : mu.data(),
+                                     sigma.data()) == GOGP_OK;
   }
 
   // ns = xi.size() / x.size() joint draws mu + C xi[s] (row-major ns x x.size()) from the caller's standard normals,
@@ -381,6 +427,7 @@ class GP {
   bool dirty_ = true;
   int T_ = 0;  // output columns of SetOutputs
   size_t sparse_m_ = 0;  // inducing points of SetSparse
+  int sparse_t_ = 0;     // output columns of SetSparseOutputs
 
   std::vector<double> pack(const std::vector<std::vector<double>> &x) const {
     std::vector<double> flat(x.size() * (size_t)NDim);

@@ -339,6 +339,51 @@ int gogp_sparse_set_inducing(gogp_handle *h, const double *U /* M x ndim */, int
  * ill-conditioned: M = 4096 at the default "sparse_jitter_log10" = -8 is off by 0.09 .. 0.9 of |dU| (above); use -6 there. */
 int gogp_sparse_gradient_inducing(gogp_handle *h, double *grad /* P */, int64_t len, double *dU /* M x ndim */);
 
+/* Sparse multi-output: T <= GOGP_SPARSE_MULTI_MAX_T output columns Y (N x T) observed at the inputs of the sparse data, under
+ * one kernel, noise, jitter and set of inducing points, on ONE pass over the data: the cross-covariances, the substitution,
+ * B, its factor, B^-1 and the second pass's 2 P k(U, X) do not depend on y.  With L, V, B, Yu = L^-T, t0 of the sparse section:
+ *     R = V Y (M x T),  Gamma = B^-1 R,  c0 = -N/2 log 2 pi - 1/2 log|B| - N/2 log s2 - (t0 - s2 (tr B - M)) / (2 s2),
+ *     bound_t = c0 - y_t^T y_t / (2 s2) + r_t^T gamma_t / (2 s2^2),   total = sum_t bound_t (column order),
+ *     mu(z)[t] = v^T gamma_t / s2,   sigma(z) as gogp_sparse_produce, shared by the outputs
+ * ("Sparse multi-output", has the gradient; for T = 1 it is the single-output form).
+ * gogp_sparse_multi_set_outputs copies Y to the device as given (row-major, no transpose on the host), where it stays; it
+ * needs gogp_sparse_set_data first and N equal to its N.  T == 0 with Y == NULL clears the outputs; gogp_sparse_set_data
+ * drops them, gogp_sparse_set_inducing keeps them.  The y of gogp_sparse_set_data does not enter any result of these calls.
+ * gogp_sparse_multi_observe returns the total and (bounds != NULL) the T bounds; gogp_sparse_multi_gradient the derivative
+ * of the total in log theta; gogp_sparse_multi_gradient_inducing that and d total / d U; gogp_sparse_multi_produce the
+ * m x T means and the m standard deviations.  Inside observe and gradient nothing is copied from the host.
+ * State: the multi calls and the single-output calls share the Mp x Mp workspace, and the last observe of either flavour
+ * owns it: gradient / produce of the other flavour return GOGP_ESTATE until that flavour's own observe, and after
+ * gogp_sparse_set_inducing both do.  A single-output observe / gradient / produce made after any multi sequence returns
+ * the bits a fresh handle returns; the handle's dense state is not touched (as above).  Two identical call sequences return
+ * identical bits; results across chunk sizes agree to rounding.  Options "sparse_chunk" and "sparse_jitter_log10" apply.
+ * GOGP_EARG: NULL pointers, a non-finite value in Y / Z / x, T outside 1 .. GOGP_SPARSE_MULTI_MAX_T, N != the sparse N,
+ * len != P, the kinds of handle the sparse calls refuse.  GOGP_ESTATE: before the sparse data or the outputs are set;
+ * gradient / produce before the multi observe.  GOGP_ENOTPD / GOGP_ECOND: as gogp_sparse_observe (ENOTPD: total and bounds
+ * are NaN).  N == 0: total 0, bounds zeros, gradient and dU zeros, mu zeros, sigma = sqrt(prior); m == 0 is OK.
+ * Device memory beyond the sparse section's: Y, four 128 x Mp matrices, the slab partials of the one new pass (R += V Y:
+ * slabs x T' x M' doubles, T' and M' rounded up to 64, slabs = min(ceil(chunk / 256), floor(1024 / (M'/64 T'/64))), which
+ * covers every chunk length) and chunk x 128 doubles.
+ * Cost, measured on one MI355X (tools/sparse_multi_probe.py, profiles/sparse_multi.txt, which carries the build id of the
+ * library before these figures were written here; D = 8, default options, medians of 5 rounds, every call ending in a
+ * synchronise), observe + gradient in ms for T = 1 / 8 / 128 beside the single-output observe + gradient of the same build:
+ * N = 65536, M = 512: 16.14 / 16.14 / 16.33 beside 15.51; M = 4096: 117.40 / 117.26 / 118.90 beside 114.31; N = 1048576,
+ * M = 512: 240.24 / 240.85 / 244.87 beside 231.41; M = 4096: 1583.9 / 1584.6 / 1610.9 beside 1550.0.  So T outputs cost 1.02 -
+ * 1.06 single-output evaluations: 0.128 - 0.130 of T separate ones at T = 8, 0.0081 - 0.0083 at T = 128, and the calls win
+ * from T = 8 of the T measured (1, 8, 128).  At T = 1 they LOSE by 2.2 - 4.0 %: use the single-output calls for one column.
+ * observe alone (T = 1 / 128): 14.53 / 14.66, 73.70 / 74.81, 219.4 / 222.0, 1021.5 / 1036.5 ms; with dU 17.24 / 17.40,
+ * 120.57 / 122.60, 252.7 / 257.5, 1616.9 / 1643.2 ms; gogp_sparse_multi_produce of 1024 points 0.20 - 0.26 ms (M = 512) and
+ * 1.38 - 1.52 ms (M = 4096).  The one new pass, R += V Y with its ordered final sum, is 1.9 - 3.8 % of observe (0.065 ms per
+ * chunk of 8192 rows at M = 512, 0.30 ms at M = 4096, nearly the same for every T: a tile is 64 outputs wide whatever T; 16
+ * and 29 TFLOP/s at T = 128).  gogp_sparse_multi_set_outputs at T = 128: 3.7 - 3.8 ms at N = 65536, 53.7 - 65.2 ms at
+ * N = 1048576 (1 GB over the host link, the finiteness check and the column sums). */
+#define GOGP_SPARSE_MULTI_MAX_T 128
+int gogp_sparse_multi_set_outputs(gogp_handle *h, const double *Y /* N x T row-major */, int64_t N, int32_t T);
+int gogp_sparse_multi_observe(gogp_handle *h, const double *x, int64_t len /* P */, double *total, double *bounds /* T, may be NULL */);
+int gogp_sparse_multi_gradient(gogp_handle *h, double *grad, int64_t len /* P */);
+int gogp_sparse_multi_gradient_inducing(gogp_handle *h, double *grad, int64_t len, double *dU /* M x ndim */);
+int gogp_sparse_multi_produce(gogp_handle *h, const double *Z, int64_t m, double *mu /* m x T */, double *sigma /* m */);
+
 /* k independent Observe + Gradient evaluations at once: handle hs[i] (each created and given
  * its data separately; they may hold the same data) evaluates x[i*len .. (i+1)*len) from its own
  * host thread, so the dependent launch chains of the k evaluations overlap on the GPU.

@@ -273,6 +273,18 @@ int gogp_test_sparse_ugrad_slabs(int64_t rows, int64_t M, int *tiles_per_slab);
 /* sparse_ugrad_slabs_bound: the slabs gogp_sparse_gradient_inducing sizes its partials by for chunks of up to `rows` rows: at
  * least gogp_test_sparse_ugrad_slabs(r, M) for every r <= rows (the slab count is not monotone in the rows).  0 out of range. */
 int gogp_test_sparse_ugrad_slabs_bound(int64_t rows, int64_t M);
+/* launch_sparse_xty (sparse.hip): R (in / out; T rounded up to 64 rows of ldr doubles, row t = output t, of which the columns
+ * below M rounded up to 64 are touched) += Y^T Vt.  Vt: `rows` (1 .. 65536) rows of ld doubles, of which the columns >= M count
+ * as exact zeros and are never multiplied; Y: `rows` rows of ldy >= T doubles, 1 <= T <= GOGP_SPARSE_MULTI_MAX_T, the columns
+ * >= T likewise.  Mp a multiple of 64 up to GOGP_SPARSE_MAX_M, 1 <= M <= Mp <= ldr. */
+int gogp_test_sparse_xty(int device, const double *Vt, int64_t vt_len, int64_t ld, int64_t rows, int64_t M, int64_t Mp,
+                         const double *Y, int64_t y_len, int64_t ldy, int64_t T, double *R, int64_t r_len, int64_t ldr);
+/* sparse_xty_slabs: the slabs of rows launch_sparse_xty splits `rows` rows into for M inducing points and T outputs, and the
+ * rows of one (the last may hold fewer); sparse_xty_slabs_bound: the slabs gogp_sparse_multi_observe sizes its partials by for
+ * chunks of up to `rows` rows, at least gogp_test_sparse_xty_slabs(r, M, T) for every r <= rows.  No device is touched; 0 for
+ * an argument out of range. */
+int gogp_test_sparse_xty_slabs(int64_t rows, int64_t M, int64_t T, int64_t *rows_per_slab);
+int gogp_test_sparse_xty_slabs_bound(int64_t rows, int64_t M, int64_t T);
 
 /* Benchmark hook for the tile kernel: `reps` launches of one shape (mode 0 RECT
  * mt x nt tiles, 1 LOWER mt x mt, 2 LAUUM mt x mt with K = mt*128) on device
@@ -283,6 +295,10 @@ int gogp_bench_gemm(int device, int mode, int mt, int nt, int64_t K, int reps,
 /* Benchmark hook for sparse_syrk_kernel (sparse.hip): `reps` launches on device buffers, Vt rows x Mp with Mp = M rounded up to
  * 256; returns ms per launch and TFLOP/s on the flops of the lower 64-tiles. */
 int gogp_bench_sparse_syrk(int device, int64_t rows, int64_t M, int reps, double *ms_per_launch, double *tflops);
+
+/* Benchmark hook for launch_sparse_xty (sparse.hip; the kernel and its ordered final sum): `reps` launches on device buffers,
+ * Vt rows x Mp with Mp = M rounded up to 256, Y rows x T; returns ms per launch and TFLOP/s on 2 rows M T flops. */
+int gogp_bench_sparse_xty(int device, int64_t rows, int64_t M, int64_t T, int reps, double *ms_per_launch, double *tflops);
 
 /* Diagnostic hook for the diagonal-block kernel: factor + invert one 256x256 SPD
  * block given on the host (row-major, lower triangle used); returns the factor,
