@@ -249,6 +249,31 @@ HOOK_SYMBOLS = [
     ("gogp_test_dist_init_replay", ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int] * 4),
 ]
 
+#: the hooks of the small finishing kernels of leave-one-out, multi-output and sparse (tests/test_finish_kernels.py), as
+#: gp.finish_check reads them: name -> arguments after `device`, in order, each "name:kind" with kind a (array read, followed
+#: by its length), o (in / out array, followed by its length), l (int64), i (int) or d (double)
+_FINISH_SPEC = {
+    "loo_stats": "Kinv:a ld:l alpha:a y:a n:l npad:l mu:o sigma:o logp:o v:o sc:o part:o",
+    "loo_scale_symv": "Kinv:a ld:l n:l npad:l sc:a v:a B:o ldb:l upart:o u:o",
+    "loo_rank2": "G:o ld:l n:l npad:l u:a alpha:a",
+    "multi_dots": "Yt:a At:a ld:l n:l T:i dots:o",
+    "sparse_finish_b": "Bacc:a Mp:l inv_s2:d B:o",
+    "sparse_copy_upper": "src:a Mp:l dst:o",
+    "sparse_weights": "B:a Binv:a g:a Mp:l s4:d T:o S:o",
+    "sparse_multi_weights": "B:a Binv:a GG:a Mp:l T:i s4:d Tm:o S:o",
+    "sparse_scalars": "C:a B:a Binv:a r:a g:a M:l Mp:l out:o",
+    "sparse_sumsq": "y:a n:l out:o",
+    "sparse_predict": "A:a V:a ld:l ncols:l m:l prior:a q:a dot:a inv_s2:d mu:o sigma:o",
+    "sparse_multi_sigma": "A:a V:a ld:l ncols:l m:l prior:a q:a sigma:o",
+    "sparse_multi_dots": "Rt:a Gt:a ld:l M:l T:i tstride:i out:o",
+    "sparse_multi_sumsq": "Y:a ldy:l n:l T:i out:o",
+    "sparse_multi_pad": "Y:a ldy:l rows:l T:l kp:l rpad:l Yp:o ldp:l",
+}
+FINISH_HOOKS = {k: [tuple(t.split(":")) for t in v.split()] for k, v in _FINISH_SPEC.items()}
+_FINISH_CTYPES = {"a": [_dp, _i64], "o": [_dp, _i64], "l": [_i64], "i": [ctypes.c_int], "d": [ctypes.c_double]}
+HOOK_SYMBOLS += [("gogp_test_" + k, ctypes.c_int, [ctypes.c_int] + [t for _, kind in spec for t in _FINISH_CTYPES[kind]])
+                 for k, spec in FINISH_HOOKS.items()]
+
 
 def build(force: bool = False) -> str:
     """Compile every HIP source for gfx950 into gogp_amd/libgogp_hip.so

@@ -3376,6 +3376,8 @@ static int sparse_gradient_impl(gogp_handle *h, const char *who, bool multi, dou
     launch_gemm_nt(s, GEMM_RECT, (int)(mpad / TILE), nt, Mp, 2.0, (const double *)ind->KsT, Mp, (const double *)b.Pm, Mp,
                    0.0, ind->Vt, Mp, nullptr, &gw);
     if (multi) {  // Wt += Yc Mm^T / s2^2
+      // (mpad is a multiple of TILE and kT of GEMM_BK: whole workgroups of 256 elements, which the launcher requires)
+      static_assert((TILE * GEMM_BK) % 256 == 0, "launch_sparse_multi_pad launches nothing unless rpad * kp % 256 == 0");
       launch_sparse_multi_pad(s, h->sp_Y + f0 * nT, nT, m, nT, kT, mpad, ypad, SM_TP);
       launch_gemm_nt(s, GEMM_RECT, (int)(mpad / TILE), nt, kT, s4, (const double *)ypad, SM_TP, (const double *)mb.Mm, SM_TP,
                      1.0, ind->Vt, Mp, nullptr, &gw);

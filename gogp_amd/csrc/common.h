@@ -429,6 +429,10 @@ void launch_remove_block(hipStream_t s, double *L, int64_t ld, const double *sna
 // each) and the npad / 256 block sums of log p in `part`.  launch_loo_scale_symv: B (npad x npad, ldb) = K^-1 diag(s) in
 // full and u = K^-1 v, both exactly zero from row / column n on; upart: npad / 64 * npad doubles of scratch.
 // launch_loo_rank2: G_ij -= u_i alpha_j + alpha_i u_j on the lower 64-tiles.
+// PRECONDITIONS (tests/test_finish_kernels.py holds the kernels to them): launch_loo_scale_symv reads sc and v, and
+// launch_loo_rank2 reads u, over all npad rows -- they must be finite and zero from row n on, as launch_loo_stats and
+// launch_loo_scale_symv leave them; G must be finite on the lower 64-tiles, whose elements with i >= n or j >= n then
+// keep their bits.  Of Kinv the stats read the diagonal elements i < n alone, of alpha and y the rows i < n.
 void launch_loo_stats(hipStream_t s, const double *Kinv, int64_t ld, const double *alpha, const double *y, int64_t n,
                       int64_t npad, double *mu, double *sigma, double *logp, double *v, double *sc, double *part);
 void launch_loo_scale_symv(hipStream_t s, const double *Kinv, int64_t ld, int64_t n, int64_t npad, const double *sc,
@@ -486,7 +490,9 @@ void launch_sparse_xty(hipStream_t s, const double *Vt, int64_t ld, int64_t rows
                        int64_t T, double *part, double *Rt, int64_t ldr);
 // Tm = T (I - Binv) - GG s4 and S = T (2 I - B - Binv) - GG s4; out[t] = r_t . gamma_t and out[tstride + t] = gamma_t .
 // gamma_t from the rows of Rt / Gt; out[t] = sum_i Y[i][t]^2; Yp (rpad x kp, ldp) = the rows of Y padded with exact
-// zeros (rpad a multiple of 128, kp of 16); sigma of launch_sparse_predict alone.
+// zeros (rpad a multiple of 128, kp of 16: rpad * kp must be a multiple of 256 -- the launcher starts whole workgroups and
+// launches NOTHING otherwise; its one caller asserts it); sigma of launch_sparse_predict alone.  The four Mp x Mp
+// element-wise launchers take Mp a multiple of 256 (Mp / 256 workgroups per row).
 void launch_sparse_multi_weights(hipStream_t s, const double *B, const double *Binv, const double *GG, int64_t Mp, int T,
                                  double s4, double *Tm, double *S);
 void launch_sparse_multi_dots(hipStream_t s, const double *Rt, const double *Gt, int64_t ld, int64_t M, int T, int tstride,

@@ -3,7 +3,9 @@
 // internal launchers; none of this is part of the product ABI (include/gogp_hip.h).
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <stdio.h>
+#include <vector>
 
 #include "common.h"
 #include "gemm_plan.h"  // for gogp_test_gemm_plan
@@ -1510,6 +1512,204 @@ extern "C" int gogp_test_sparse_xty_slabs(int64_t rows, int64_t M, int64_t T, in
 extern "C" int gogp_test_sparse_xty_slabs_bound(int64_t rows, int64_t M, int64_t T) {
   if (rows < 1 || rows > (1 << 16) || M < 1 || M > GOGP_SPARSE_MAX_M || T < 1 || T > GOGP_SPARSE_MULTI_MAX_T) return 0;
   return sparse_xty_slabs_bound(rows, M, T);
+}
+
+// ---- the small kernels that finish leave-one-out, multi-output and sparse evaluations, through their product launchers
+// (tests/test_finish_kernels.py): the kernels of loo.hip, multi_dots_kernel (multi.hip) and the element-wise, scalar and
+// Produce kernels of sparse.hip.  The rules of the hooks above: every argument is checked before the device is touched,
+// every array goes to the device whole and every in / out array comes back whole.
+namespace {
+struct FinArr {
+  const double *h;
+  int64_t len;
+  bool out;
+};
+bool fin_have(std::initializer_list<FinArr> arrs) {
+  for (const FinArr &a : arrs)
+    if (!a.h || a.len <= 0) return false;
+  return true;
+}
+// uploads the arrays, runs `launch` on their device copies (in the order given) and brings the in / out ones back
+template <class F>
+int fin_run(int device, std::initializer_list<FinArr> arrs, F &&launch) {
+  if (!device_ok(device)) return GOGP_EHIP;
+  std::vector<DevCopy> dc(arrs.size());
+  std::vector<double *> d;
+  hipError_t e = hipSuccess;
+  size_t i = 0;
+  for (const FinArr &a : arrs) {
+    if (e == hipSuccess) e = dc[i].up(a.h, (size_t)a.len * sizeof(double));
+    d.push_back(dc[i++].as<double>());
+  }
+  if (e == hipSuccess) {
+    launch(d.data());
+    e = launched();
+  }
+  i = 0;
+  for (const FinArr &a : arrs) {
+    if (e == hipSuccess && a.out) e = dc[i].down(const_cast<double *>(a.h));
+    ++i;
+  }
+  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+}
+bool fin_npad_ok(int64_t n, int64_t npad) {
+  return npad > 0 && npad % PANEL == 0 && npad <= UP_NPAD_MAX && n >= 1 && n <= npad;
+}
+// the Mp x Mp element-wise launchers start Mp / 256 workgroups per row: any other Mp would drop columns silently
+bool fin_mp_ok(int64_t Mp) { return Mp > 0 && Mp % 256 == 0 && Mp <= GOGP_SPARSE_MAX_M; }
+constexpr int64_t FIN_ROWS_MAX = 1 << 24;   // rows of the sums of squares
+constexpr int64_t FIN_M_MAX = 4 * 65535;    // test points of the Produce kernels: one wave each, four per workgroup
+}  // namespace
+
+extern "C" int gogp_test_loo_stats(int device, const double *Kinv, int64_t kinv_len, int64_t ld, const double *alpha,
+                                   int64_t alpha_len, const double *y, int64_t y_len, int64_t n, int64_t npad, double *mu,
+                                   int64_t mu_len, double *sigma, int64_t sigma_len, double *logp, int64_t logp_len, double *v,
+                                   int64_t v_len, double *sc, int64_t sc_len, double *part, int64_t part_len) {
+  const std::initializer_list<FinArr> arrs = {{Kinv, kinv_len, false}, {alpha, alpha_len, false}, {y, y_len, false},
+                                              {mu, mu_len, true},      {sigma, sigma_len, true},  {logp, logp_len, true},
+                                              {v, v_len, true},        {sc, sc_len, true},        {part, part_len, true}};
+  if (!fin_have(arrs) || !fin_npad_ok(n, npad) || !covers(kinv_len, 0, ld, npad, npad, 1, 0)) return GOGP_EARG;
+  if (alpha_len < n || y_len < n || mu_len < n || sigma_len < n || logp_len < n) return GOGP_EARG;
+  if (v_len < npad || sc_len < npad || part_len < npad / PANEL) return GOGP_EARG;
+  return fin_run(device, arrs, [&](double **d) {
+    launch_loo_stats(0, d[0], ld, d[1], d[2], n, npad, d[3], d[4], d[5], d[6], d[7], d[8]);
+  });
+}
+
+extern "C" int gogp_test_loo_scale_symv(int device, const double *Kinv, int64_t kinv_len, int64_t ld, int64_t n, int64_t npad,
+                                        const double *sc, int64_t sc_len, const double *v, int64_t v_len, double *B,
+                                        int64_t b_len, int64_t ldb, double *upart, int64_t upart_len, double *u,
+                                        int64_t u_len) {
+  const std::initializer_list<FinArr> arrs = {{Kinv, kinv_len, false}, {sc, sc_len, false},      {v, v_len, false},
+                                              {B, b_len, true},        {upart, upart_len, true}, {u, u_len, true}};
+  if (!fin_have(arrs) || !fin_npad_ok(n, npad)) return GOGP_EARG;
+  if (!covers(kinv_len, 0, ld, npad, npad, 1, 0) || !covers(b_len, 0, ldb, npad, npad, 1, 0)) return GOGP_EARG;
+  if (sc_len < npad || v_len < npad || u_len < npad || upart_len < npad / 64 * npad) return GOGP_EARG;
+  return fin_run(device, arrs, [&](double **d) {
+    launch_loo_scale_symv(0, d[0], ld, n, npad, d[1], d[2], d[3], ldb, d[4], d[5]);
+  });
+}
+
+extern "C" int gogp_test_loo_rank2(int device, double *G, int64_t g_len, int64_t ld, int64_t n, int64_t npad, const double *u,
+                                   int64_t u_len, const double *alpha, int64_t alpha_len) {
+  const std::initializer_list<FinArr> arrs = {{G, g_len, true}, {u, u_len, false}, {alpha, alpha_len, false}};
+  if (!fin_have(arrs) || !fin_npad_ok(n, npad) || !covers(g_len, 0, ld, npad, npad, 1, 0)) return GOGP_EARG;
+  if (u_len < npad || alpha_len < n) return GOGP_EARG;
+  return fin_run(device, arrs, [&](double **d) { launch_loo_rank2(0, d[0], ld, n, npad, d[1], d[2]); });
+}
+
+extern "C" int gogp_test_multi_dots(int device, const double *Yt, int64_t yt_len, const double *At, int64_t at_len, int64_t ld,
+                                    int64_t n, int T, double *dots, int64_t dots_len) {
+  const std::initializer_list<FinArr> arrs = {{Yt, yt_len, false}, {At, at_len, false}, {dots, dots_len, true}};
+  if (!fin_have(arrs) || T < 1 || T > GOGP_MULTI_MAX_T || n < 1 || n > UP_NPAD_MAX || dots_len < T) return GOGP_EARG;
+  if (!covers(yt_len, 0, ld, T, n, 1, 0) || !covers(at_len, 0, ld, T, n, 1, 0)) return GOGP_EARG;
+  return fin_run(device, arrs, [&](double **d) { launch_multi_dots(0, d[0], d[1], ld, n, T, d[2]); });
+}
+
+extern "C" int gogp_test_sparse_finish_b(int device, const double *Bacc, int64_t bacc_len, int64_t Mp, double inv_s2, double *B,
+                                         int64_t b_len) {
+  const std::initializer_list<FinArr> arrs = {{Bacc, bacc_len, false}, {B, b_len, true}};
+  if (!fin_have(arrs) || !fin_mp_ok(Mp) || !std::isfinite(inv_s2) || bacc_len < Mp * Mp || b_len < Mp * Mp) return GOGP_EARG;
+  return fin_run(device, arrs, [&](double **d) { launch_sparse_finish_b(0, d[0], Mp, inv_s2, d[1]); });
+}
+
+extern "C" int gogp_test_sparse_copy_upper(int device, const double *src, int64_t src_len, int64_t Mp, double *dst,
+                                           int64_t dst_len) {
+  const std::initializer_list<FinArr> arrs = {{src, src_len, false}, {dst, dst_len, true}};
+  if (!fin_have(arrs) || !fin_mp_ok(Mp) || src_len < Mp * Mp || dst_len < Mp * Mp) return GOGP_EARG;
+  return fin_run(device, arrs, [&](double **d) { launch_sparse_copy_upper(0, d[0], Mp, d[1]); });
+}
+
+extern "C" int gogp_test_sparse_weights(int device, const double *B, int64_t b_len, const double *Binv, int64_t binv_len,
+                                        const double *g, int64_t g_len, int64_t Mp, double s4, double *T, int64_t t_len,
+                                        double *S, int64_t s_len) {
+  const std::initializer_list<FinArr> arrs = {
+      {B, b_len, false}, {Binv, binv_len, false}, {g, g_len, false}, {T, t_len, true}, {S, s_len, true}};
+  if (!fin_have(arrs) || !fin_mp_ok(Mp) || !std::isfinite(s4) || g_len < Mp) return GOGP_EARG;
+  if (b_len < Mp * Mp || binv_len < Mp * Mp || t_len < Mp * Mp || s_len < Mp * Mp) return GOGP_EARG;
+  return fin_run(device, arrs, [&](double **d) { launch_sparse_weights(0, d[0], d[1], d[2], Mp, s4, d[3], d[4]); });
+}
+
+extern "C" int gogp_test_sparse_multi_weights(int device, const double *B, int64_t b_len, const double *Binv, int64_t binv_len,
+                                              const double *GG, int64_t gg_len, int64_t Mp, int T, double s4, double *Tm,
+                                              int64_t tm_len, double *S, int64_t s_len) {
+  const std::initializer_list<FinArr> arrs = {
+      {B, b_len, false}, {Binv, binv_len, false}, {GG, gg_len, false}, {Tm, tm_len, true}, {S, s_len, true}};
+  if (!fin_have(arrs) || !fin_mp_ok(Mp) || !std::isfinite(s4) || T < 1 || T > GOGP_SPARSE_MULTI_MAX_T) return GOGP_EARG;
+  if (b_len < Mp * Mp || binv_len < Mp * Mp || gg_len < Mp * Mp || tm_len < Mp * Mp || s_len < Mp * Mp) return GOGP_EARG;
+  return fin_run(device, arrs, [&](double **d) { launch_sparse_multi_weights(0, d[0], d[1], d[2], Mp, T, s4, d[3], d[4]); });
+}
+
+extern "C" int gogp_test_sparse_scalars(int device, const double *C, int64_t c_len, const double *B, int64_t b_len,
+                                        const double *Binv, int64_t binv_len, const double *r, int64_t r_len, const double *g,
+                                        int64_t g_len, int64_t M, int64_t Mp, double *out, int64_t out_len) {
+  const std::initializer_list<FinArr> arrs = {{C, c_len, false}, {B, b_len, false}, {Binv, binv_len, false},
+                                              {r, r_len, false}, {g, g_len, false}, {out, out_len, true}};
+  if (!fin_have(arrs) || M < 1 || M > Mp || Mp > GOGP_SPARSE_MAX_M || r_len < M || g_len < M || out_len < 5) return GOGP_EARG;
+  if (!covers(c_len, 0, Mp, M, M, 1, 0) || !covers(b_len, 0, Mp, M, M, 1, 0) || !covers(binv_len, 0, Mp, M, M, 1, 0))
+    return GOGP_EARG;
+  return fin_run(device, arrs, [&](double **d) { launch_sparse_scalars(0, d[0], d[1], d[2], d[3], d[4], M, Mp, d[5]); });
+}
+
+extern "C" int gogp_test_sparse_sumsq(int device, const double *y, int64_t y_len, int64_t n, double *out, int64_t out_len) {
+  const std::initializer_list<FinArr> arrs = {{y, y_len, false}, {out, out_len, true}};
+  if (!fin_have(arrs) || n < 1 || n > FIN_ROWS_MAX || y_len < n) return GOGP_EARG;
+  return fin_run(device, arrs, [&](double **d) { launch_sparse_sumsq(0, d[0], n, d[1]); });
+}
+
+extern "C" int gogp_test_sparse_predict(int device, const double *A, int64_t a_len, const double *V, int64_t v_len, int64_t ld,
+                                        int64_t ncols, int64_t m, const double *prior, int64_t prior_len, const double *q,
+                                        int64_t q_len, const double *dot, int64_t dot_len, double inv_s2, double *mu,
+                                        int64_t mu_len, double *sigma, int64_t sigma_len) {
+  const std::initializer_list<FinArr> arrs = {{A, a_len, false},     {V, v_len, false},     {prior, prior_len, false},
+                                              {q, q_len, false},     {dot, dot_len, false}, {mu, mu_len, true},
+                                              {sigma, sigma_len, true}};
+  if (!fin_have(arrs) || m < 1 || m > FIN_M_MAX || !std::isfinite(inv_s2)) return GOGP_EARG;
+  if (!covers(a_len, 0, ld, m, ncols, 1, 0) || !covers(v_len, 0, ld, m, ncols, 1, 0)) return GOGP_EARG;
+  if (prior_len < m || q_len < m || dot_len < m || mu_len < m || sigma_len < m) return GOGP_EARG;
+  return fin_run(device, arrs, [&](double **d) {
+    launch_sparse_predict(0, d[0], d[1], ld, ncols, m, d[2], d[3], d[4], inv_s2, d[5], d[6]);
+  });
+}
+
+extern "C" int gogp_test_sparse_multi_dots(int device, const double *Rt, int64_t rt_len, const double *Gt, int64_t gt_len,
+                                           int64_t ld, int64_t M, int T, int tstride, double *out, int64_t out_len) {
+  const std::initializer_list<FinArr> arrs = {{Rt, rt_len, false}, {Gt, gt_len, false}, {out, out_len, true}};
+  if (!fin_have(arrs) || M < 1 || M > GOGP_SPARSE_MAX_M || T < 1 || T > GOGP_SPARSE_MULTI_MAX_T) return GOGP_EARG;
+  if (tstride < T || out_len < (int64_t)tstride + T) return GOGP_EARG;
+  if (!covers(rt_len, 0, ld, T, M, 1, 0) || !covers(gt_len, 0, ld, T, M, 1, 0)) return GOGP_EARG;
+  return fin_run(device, arrs, [&](double **d) { launch_sparse_multi_dots(0, d[0], d[1], ld, M, T, tstride, d[2]); });
+}
+
+extern "C" int gogp_test_sparse_multi_sumsq(int device, const double *Y, int64_t y_len, int64_t ldy, int64_t n, int T,
+                                            double *out, int64_t out_len) {
+  const std::initializer_list<FinArr> arrs = {{Y, y_len, false}, {out, out_len, true}};
+  if (!fin_have(arrs) || n < 1 || n > FIN_ROWS_MAX || T < 1 || T > GOGP_SPARSE_MULTI_MAX_T || out_len < T) return GOGP_EARG;
+  if (!covers(y_len, 0, ldy, n, T, 1, 0)) return GOGP_EARG;  // (ldy < T is refused here)
+  return fin_run(device, arrs, [&](double **d) { launch_sparse_multi_sumsq(0, d[0], ldy, n, T, d[1]); });
+}
+
+extern "C" int gogp_test_sparse_multi_pad(int device, const double *Y, int64_t y_len, int64_t ldy, int64_t rows, int64_t T,
+                                          int64_t kp, int64_t rpad, double *Yp, int64_t yp_len, int64_t ldp) {
+  const std::initializer_list<FinArr> arrs = {{Y, y_len, false}, {Yp, yp_len, true}};
+  if (!fin_have(arrs) || rpad < 1 || rpad > (1 << 16) || kp < 1 || kp > (1 << 12) || rows < 1 || rows > rpad || T < 1 || T > kp)
+    return GOGP_EARG;
+  if ((rpad * kp) % 256) return GOGP_EARG;  // the launcher starts whole workgroups of 256 elements or none at all
+  if (!covers(y_len, 0, ldy, rows, T, 1, 0) || !covers(yp_len, 0, ldp, rpad, kp, 1, 0)) return GOGP_EARG;  // ldy < T, ldp < kp
+  return fin_run(device, arrs, [&](double **d) { launch_sparse_multi_pad(0, d[0], ldy, rows, T, kp, rpad, d[1], ldp); });
+}
+
+extern "C" int gogp_test_sparse_multi_sigma(int device, const double *A, int64_t a_len, const double *V, int64_t v_len,
+                                            int64_t ld, int64_t ncols, int64_t m, const double *prior, int64_t prior_len,
+                                            const double *q, int64_t q_len, double *sigma, int64_t sigma_len) {
+  const std::initializer_list<FinArr> arrs = {
+      {A, a_len, false}, {V, v_len, false}, {prior, prior_len, false}, {q, q_len, false}, {sigma, sigma_len, true}};
+  if (!fin_have(arrs) || m < 1 || m > FIN_M_MAX) return GOGP_EARG;
+  if (!covers(a_len, 0, ld, m, ncols, 1, 0) || !covers(v_len, 0, ld, m, ncols, 1, 0)) return GOGP_EARG;
+  if (prior_len < m || q_len < m || sigma_len < m) return GOGP_EARG;
+  return fin_run(device, arrs, [&](double **d) {
+    launch_sparse_multi_sigma(0, d[0], d[1], ld, ncols, m, d[2], d[3], d[4]);
+  });
 }
 
 // Benchmark hook for launch_sparse_xty (the kernel and its ordered final sum): `reps` launches on device buffers (Vt: rows

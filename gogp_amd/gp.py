@@ -1466,3 +1466,29 @@ def multi_weight_check(At: np.ndarray, ld: int, T: int, Kinv: np.ndarray, ldk: i
     if rc != _lib.GOGP_OK:
         raise GogpError(rc, "test_multi_weight")
     return G
+
+
+# ---- the small finishing kernels of leave-one-out, multi-output and sparse (include/gogp_testhooks.h;
+# tests/test_finish_kernels.py) ----------------------------------------------------------------------------------------
+def finish_check(which: str, device: int = -1, **args):
+    """The test hook gogp_test_<which> of one of the launchers in _lib.FINISH_HOOKS, whose table names the arguments: flat
+    float64 arrays (their lengths are passed along) and scalars, all by keyword.  Returns copies of the in / out arrays
+    after the launch, in the order of the table (a single array if there is one)."""
+    spec = _lib.FINISH_HOOKS[which]
+    if set(args) != {name for name, _ in spec}:
+        raise TypeError("finish_check(%s): the arguments are %s" % (which, ", ".join(name for name, _ in spec)))
+    call, outs = [device], []
+    for name, kind in spec:
+        v = args[name]
+        if kind in "ao":
+            v = _vec(v, name).reshape(-1)
+            if kind == "o":
+                v = v.copy()
+                outs.append(v)
+            call += [_dp(v), v.size]
+        else:
+            call.append(float(v) if kind == "d" else int(v))
+    rc = getattr(_lib.hooks(), "gogp_test_" + which)(*call)
+    if rc != _lib.GOGP_OK:
+        raise GogpError(rc, "test_" + which)
+    return outs[0] if len(outs) == 1 else tuple(outs)

@@ -286,6 +286,79 @@ int gogp_test_sparse_xty(int device, const double *Vt, int64_t vt_len, int64_t l
 int gogp_test_sparse_xty_slabs(int64_t rows, int64_t M, int64_t T, int64_t *rows_per_slab);
 int gogp_test_sparse_xty_slabs_bound(int64_t rows, int64_t M, int64_t T);
 
+/* ---- the small kernels that finish a leave-one-out, multi-output or sparse evaluation, through their product launchers
+ * (tests/test_finish_kernels.py): the four kernels of loo.hip, multi_dots_kernel (multi.hip) and the element-wise, scalar and
+ * Produce kernels of sparse.hip.  The rules of the hooks above: lengths count elements, every array goes to the device whole
+ * and every in / out array whole back, GOGP_EARG before the device is touched for anything a launch cannot honour or the
+ * arrays do not cover.  npad: a multiple of 256, 1 <= n <= npad. */
+
+/* launch_loo_stats: Kinv npad rows of ld >= npad, of which only the diagonal elements i < n are read; alpha, y: n doubles
+ * read.  mu, sigma, logp (in / out): the rows i < n written.  v, sc (in / out, npad doubles): written in full, exact zeros
+ * from row n on.  part (in / out): npad / 256 block sums of log p, a block without a live row exactly 0. */
+int gogp_test_loo_stats(int device, const double *Kinv, int64_t kinv_len, int64_t ld, const double *alpha, int64_t alpha_len,
+                        const double *y, int64_t y_len, int64_t n, int64_t npad, double *mu, int64_t mu_len, double *sigma,
+                        int64_t sigma_len, double *logp, int64_t logp_len, double *v, int64_t v_len, double *sc, int64_t sc_len,
+                        double *part, int64_t part_len);
+/* launch_loo_scale_symv (loo_scale_symv_kernel, then loo_u_final_kernel): B (in / out; npad rows of ldb >= npad) = K^-1
+ * diag(sc) on npad x npad, u (in / out; npad doubles) = K^-1 v, both exactly zero from row / column n on; upart (in / out):
+ * npad / 64 slots of npad doubles, every one written.  Of Kinv (npad rows of ld) only j <= i < n is read.  PRECONDITION of the
+ * launcher: sc and v (npad doubles each) are finite and zero from row n on -- the kernel multiplies the masked zeros of the
+ * rows and columns >= n by them. */
+int gogp_test_loo_scale_symv(int device, const double *Kinv, int64_t kinv_len, int64_t ld, int64_t n, int64_t npad,
+                             const double *sc, int64_t sc_len, const double *v, int64_t v_len, double *B, int64_t b_len,
+                             int64_t ldb, double *upart, int64_t upart_len, double *u, int64_t u_len);
+/* launch_loo_rank2: G (in / out; npad rows of ld) -= u alpha^T + alpha u^T on the whole lower 64 x 64 tiles.  alpha: n doubles
+ * read (zero beyond).  PRECONDITION of the launcher: u (npad doubles) is finite and zero from row n on, and G is finite on
+ * those tiles: the elements with i >= n or j >= n then keep their bits. */
+int gogp_test_loo_rank2(int device, double *G, int64_t g_len, int64_t ld, int64_t n, int64_t npad, const double *u,
+                        int64_t u_len, const double *alpha, int64_t alpha_len);
+/* launch_multi_dots: dots[t] (in / out) = sum_{i < n} Yt[t][i] At[t][i], t < T <= GOGP_MULTI_MAX_T; Yt, At: T rows of
+ * ld >= n. */
+int gogp_test_multi_dots(int device, const double *Yt, int64_t yt_len, const double *At, int64_t at_len, int64_t ld, int64_t n,
+                         int T, double *dots, int64_t dots_len);
+/* The four Mp x Mp element-wise launchers of sparse.hip (leading dimension Mp): Mp a multiple of 256 -- their grid is Mp / 256
+ * workgroups per row -- up to GOGP_SPARSE_MAX_M; every matrix holds Mp * Mp elements at least, g holds Mp.
+ * finish_b: B (in / out) = I + Bacc inv_s2 in both triangles from the elements a >= b of Bacc.  copy_upper: dst (in / out) =
+ * src on j >= i, +0.0 below.  weights: T = I - Binv - g g^T s4, S = 2 I - B - Binv - g g^T s4.  multi_weights: Tm =
+ * T (I - Binv) - GG s4, S = T (2 I - B - Binv) - GG s4 with T (1 .. GOGP_SPARSE_MULTI_MAX_T) the number of outputs. */
+int gogp_test_sparse_finish_b(int device, const double *Bacc, int64_t bacc_len, int64_t Mp, double inv_s2, double *B,
+                              int64_t b_len);
+int gogp_test_sparse_copy_upper(int device, const double *src, int64_t src_len, int64_t Mp, double *dst, int64_t dst_len);
+int gogp_test_sparse_weights(int device, const double *B, int64_t b_len, const double *Binv, int64_t binv_len, const double *g,
+                             int64_t g_len, int64_t Mp, double s4, double *T, int64_t t_len, double *S, int64_t s_len);
+int gogp_test_sparse_multi_weights(int device, const double *B, int64_t b_len, const double *Binv, int64_t binv_len,
+                                   const double *GG, int64_t gg_len, int64_t Mp, int T, double s4, double *Tm, int64_t tm_len,
+                                   double *S, int64_t s_len);
+/* launch_sparse_scalars: out[0 .. 4] (in / out) = sum_{i < M} of 2 log C_ii, B_ii - 1, Binv_ii, r_i g_i, g_i^2; of the
+ * matrices (leading dimension Mp, 1 <= M <= Mp <= GOGP_SPARSE_MAX_M) only the diagonal elements i < M are read, of r and g the
+ * first M. */
+int gogp_test_sparse_scalars(int device, const double *C, int64_t c_len, const double *B, int64_t b_len, const double *Binv,
+                             int64_t binv_len, const double *r, int64_t r_len, const double *g, int64_t g_len, int64_t M,
+                             int64_t Mp, double *out, int64_t out_len);
+/* launch_sparse_sumsq: out[0] (in / out) = sum_{i < n} y_i^2. */
+int gogp_test_sparse_sumsq(int device, const double *y, int64_t y_len, int64_t n, double *out, int64_t out_len);
+/* launch_sparse_predict: mu_j (in / out) = dot_j inv_s2, sigma_j (in / out) = sqrt(prior_j - q_j + sum_{i < ncols} A[j][i]
+ * V[j][i]) for j < m <= 4 * 65535, unclamped; A, V: m rows of ld >= ncols.  launch_sparse_multi_sigma: the sigma alone. */
+int gogp_test_sparse_predict(int device, const double *A, int64_t a_len, const double *V, int64_t v_len, int64_t ld,
+                             int64_t ncols, int64_t m, const double *prior, int64_t prior_len, const double *q, int64_t q_len,
+                             const double *dot, int64_t dot_len, double inv_s2, double *mu, int64_t mu_len, double *sigma,
+                             int64_t sigma_len);
+int gogp_test_sparse_multi_sigma(int device, const double *A, int64_t a_len, const double *V, int64_t v_len, int64_t ld,
+                                 int64_t ncols, int64_t m, const double *prior, int64_t prior_len, const double *q,
+                                 int64_t q_len, double *sigma, int64_t sigma_len);
+/* launch_sparse_multi_dots: out[t] (in / out) = sum_{i < M} Rt[t][i] Gt[t][i] and out[tstride + t] = sum_{i < M} Gt[t][i]^2,
+ * t < T <= tstride; Rt, Gt: T rows of ld >= M.  launch_sparse_multi_sumsq: out[t] = sum_{i < n} Y[i][t]^2, Y: n rows of
+ * ldy >= T. */
+int gogp_test_sparse_multi_dots(int device, const double *Rt, int64_t rt_len, const double *Gt, int64_t gt_len, int64_t ld,
+                                int64_t M, int T, int tstride, double *out, int64_t out_len);
+int gogp_test_sparse_multi_sumsq(int device, const double *Y, int64_t y_len, int64_t ldy, int64_t n, int T, double *out,
+                                 int64_t out_len);
+/* launch_sparse_multi_pad: Yp (in / out; rpad rows of ldp >= kp) = the `rows` <= rpad rows of Y (ldy >= T, T <= kp) on
+ * rpad x kp, +0.0 outside rows x T.  rpad * kp must be a multiple of 256: the launcher starts whole workgroups, and would
+ * return without a launch otherwise (the hook refuses instead). */
+int gogp_test_sparse_multi_pad(int device, const double *Y, int64_t y_len, int64_t ldy, int64_t rows, int64_t T, int64_t kp,
+                               int64_t rpad, double *Yp, int64_t yp_len, int64_t ldp);
+
 /* Benchmark hook for the tile kernel: `reps` launches of one shape (mode 0 RECT
  * mt x nt tiles, 1 LOWER mt x mt, 2 LAUUM mt x mt with K = mt*128) on device
  * buffers; returns ms per launch and TFLOP/s on the flops launched. */
