@@ -428,6 +428,53 @@ func (gp *GP) LOOGradient() ([]float64, error) {
 	return g, nil
 }
 
+// Blocks returns start for BlockCV: n rows in consecutive blocks of length
+// rows, the last one shorter where length does not divide n.
+func Blocks(n, length int) []int64 {
+	start := []int64{}
+	for s := 0; s < n && length > 0; s += length {
+		start = append(start, int64(s))
+	}
+	return append(start, int64(n))
+}
+
+// BlockCV computes the leave-block-out cross-validation predictions at the
+// current parameters (gogp_blockcv): the rows are cut into the consecutive
+// blocks [start[f], start[f+1]), start[0] = 0, start[F] = n, 1 .. 128 rows
+// each, and every block is predicted jointly by the process fitted to all the
+// other blocks.  mu, sigma: per row; logp: the joint log density per block;
+// total: their sum (no reference counterpart).  Folds that are not contiguous:
+// permute the rows before assigning X / Y.
+func (gp *GP) BlockCV(start []int64) (mu, sigma, logp []float64, total float64, err error) {
+	gp.defaults()
+	if len(start) == 0 {
+		return nil, nil, nil, 0, fmt.Errorf("gogp: BlockCV: start needs F + 1 entries")
+	}
+	n, f := int(C.gogp_n(gp.handle())), len(start)-1
+	mu, sigma, logp = make([]float64, n), make([]float64, n), make([]float64, f)
+	var t C.double
+	rc := C.gogp_blockcv(gp.handle(), (*C.int64_t)(unsafe.Pointer(&start[0])), C.int64_t(f), dptr(mu), dptr(sigma), dptr(logp), &t)
+	if err = gp.err(rc); err != nil {
+		return nil, nil, nil, 0, err
+	}
+	return mu, sigma, logp, float64(t), nil
+}
+
+// BlockCVGradient computes the gradient of the BlockCV score with respect to
+// the log-transformed hyperparameters (no reference counterpart).
+func (gp *GP) BlockCVGradient(start []int64) ([]float64, error) {
+	gp.defaults()
+	if len(start) == 0 {
+		return nil, fmt.Errorf("gogp: BlockCVGradient: start needs F + 1 entries")
+	}
+	g := make([]float64, len(gp.ThetaSimil)+len(gp.ThetaNoise))
+	rc := C.gogp_blockcv_gradient(gp.handle(), (*C.int64_t)(unsafe.Pointer(&start[0])), C.int64_t(len(start)-1), dptr(g), C.int64_t(len(g)))
+	if err := gp.err(rc); err != nil {
+		return nil, err
+	}
+	return g, nil
+}
+
 // SetOutputs gives the process T output columns (y row-major n x T, n =
 // len(gp.Y), T <= 128) observed at its inputs and sharing its kernel and
 // hyperparameters; they are evaluated on one factorisation (no reference

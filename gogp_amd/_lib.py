@@ -21,6 +21,7 @@ GOGP_MAX_CANDIDATES = 16
 GOGP_BATCH_MAX_N = 128
 GOGP_COV_MAX_M = 4096
 GOGP_MULTI_MAX_T = 128
+GOGP_BLOCKCV_MAX = 128
 GOGP_SPARSE_MAX_M = 4096
 GOGP_SPARSE_MULTI_MAX_T = 128
 
@@ -88,6 +89,10 @@ SYMBOLS = [
     ("gogp_gradient", ctypes.c_int, [_h, _dp, _i64]),
     ("gogp_loo", ctypes.c_int, [_h, _dp, _dp, _dp, _dp]),
     ("gogp_loo_gradient", ctypes.c_int, [_h, _dp, _i64]),
+    ("gogp_blockcv_check", ctypes.c_int, [ctypes.POINTER(_i64), _i64, _i64]),
+    ("gogp_blockcv_groups", ctypes.c_int, [ctypes.POINTER(_i64), _i64, ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
+    ("gogp_blockcv", ctypes.c_int, [_h, ctypes.POINTER(_i64), _i64, _dp, _dp, _dp, _dp]),
+    ("gogp_blockcv_gradient", ctypes.c_int, [_h, ctypes.POINTER(_i64), _i64, _dp, _i64]),
     ("gogp_multi_set_outputs", ctypes.c_int, [_h, _dp, _i64, ctypes.c_int32]),
     ("gogp_multi_lml", ctypes.c_int, [_h, _dp, _dp]),
     ("gogp_multi_gradient", ctypes.c_int, [_h, _dp, _i64]),
@@ -245,6 +250,12 @@ HOOK_SYMBOLS = [
      [ctypes.c_int, _dp, _i64, _i64, _i64, _i64, _i64, _dp, _i64, _i64, _i64, _dp, _i64, _i64]),
     ("gogp_test_sparse_xty_slabs", ctypes.c_int, [_i64, _i64, _i64, ctypes.POINTER(ctypes.c_int64)]),
     ("gogp_test_sparse_xty_slabs_bound", ctypes.c_int, [_i64, _i64, _i64]),
+    # the two kernels of leave-block-out cross-validation (tests/test_blockcv_kernels.py)
+    ("gogp_test_blockcv_groups", ctypes.c_int,
+     [ctypes.c_int, _dp, _i64, _i64, _dp, _i64, _dp, _i64, _i64, ctypes.POINTER(_i64), _i64] + [_dp, _i64] * 6
+     + [ctypes.POINTER(_i64), _i64]),
+    ("gogp_test_blockcv_apply", ctypes.c_int,
+     [ctypes.c_int, _dp, _i64, _i64, _i64, _i64, _i64, ctypes.POINTER(_i64), _i64, _dp, _i64]),
     # per-rank replay of the sharded sweep (tools/sharded_replay.py): a transport that reads recorded panels
     ("gogp_test_dist_init_replay", ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int] * 4),
 ]

@@ -106,6 +106,8 @@ static void free_n_buffers(gogp_handle *h) {
   h->rm_ws.release();
   h->loo_vec.release();
   h->loo_mat.release();
+  h->bcv_vec.release();
+  h->bcv_s.release();
   h->multi_vec.release();
   h->multi_mean.release();
   h->multi_mat.release();
@@ -1644,6 +1646,159 @@ extern "C" int gogp_loo_gradient(gogp_handle *h, double *grad, int64_t len) {
   {
     AuxTimer tm(h, GOGP_PROF_GRAD, s);
     launch_grad_reduce(s, h->devP, h->D, h->ard_dims, h->dX, lv.zero, (const double *)G, ld, h->n, npad, h->gpart, h->gout,
+                       h->radial1, h->ard_mfma_min, h->ev());
+  }
+  double acc[NACC];
+  HIPCHK(h, hipMemcpyAsync(acc, h->gout, sizeof acc, hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipStreamSynchronize(s));
+  HIPCHK(h, hipGetLastError());
+  assemble_gradient(h, acc, h->hostP->dnoise, grad);
+  return GOGP_OK;
+}
+
+// ---- leave-block-out cross-validation (blockcv.hip) -----------------------------------------------------------------
+// No reference counterpart.  The contract and the data flow of the LOO calls above, with consecutive blocks of rows
+// held out together: one in-LDS factorisation per group of blocks of K^-1's diagonal, and for the gradient one
+// block-diagonal right-multiplication of K^-1 ahead of LOO's own product, rank-2 correction and reduction.
+extern "C" int gogp_blockcv_check(const int64_t *start, int64_t F, int64_t n) {
+  if (!start || F < 0 || n < 0 || start[0] != 0) return GOGP_EARG;
+  for (int64_t f = 0; f < F; ++f) {
+    const int64_t len = start[f + 1] - start[f];
+    if (len < 1 || len > GOGP_BLOCKCV_MAX) return GOGP_EARG;
+  }
+  return start[F] == n ? GOGP_OK : GOGP_EARG;
+}
+
+extern "C" int gogp_blockcv_groups(const int64_t *start, int64_t F, int64_t *first, int64_t *ngroups) {
+  if (!start || !first || !ngroups || F < 0) return GOGP_EARG;
+  if (gogp_blockcv_check(start, F, start[F]) != GOGP_OK) return GOGP_EARG;
+  *ngroups = blockcv_pack(start, F, first);
+  return GOGP_OK;
+}
+
+struct BlockCvVecs {
+  double *mu, *sigma, *v, *ones, *u, *zero, *logp, *Sg;
+  int64_t *bstart, *gfirst;
+  int ngroups;
+};
+// The refusals of both calls, then -- with observations -- K^-1 and alpha ordered on the main stream, the workspaces in
+// place, the group kernel run and its pivots judged (the main stream is idle on return).  *empty: n == 0.
+static int blockcv_prepare(gogp_handle *h, const char *who, const int64_t *start, int64_t F, BlockCvVecs *bv, bool *empty) {
+  char buf[200];
+  const char *refuse = h->prec == 32        ? "precision = 32 handles"
+                       : mixed_gradient(h) ? "gradient_precision = 32 (a float K^-1)"
+                       : h->dist           ? "sharded handles"
+                                           : nullptr;
+  if (refuse) {
+    snprintf(buf, sizeof buf, "%s: %s are not supported", who, refuse);
+    return fail(h, GOGP_EARG, buf);
+  }
+  if (gogp_blockcv_check(start, F, h->n) != GOGP_OK) {
+    snprintf(buf, sizeof buf,
+             "%s: start must hold F + 1 strictly increasing entries from 0 to n = %lld, blocks of at most %d rows", who,
+             (long long)h->n, GOGP_BLOCKCV_MAX);
+    return fail(h, GOGP_EARG, buf);
+  }
+  *empty = h->n == 0;
+  if (*empty) return GOGP_OK;
+  if (!h->factored) {
+    snprintf(buf, sizeof buf, "%s: nothing absorbed", who);
+    return fail(h, GOGP_ESTATE, buf);
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  int rc = compute_kinv(h);
+  if (rc == GOGP_OK) rc = ensure_alpha(h);
+  if (rc != GOGP_OK) return rc;
+  // the tables: block starts, the groups' first blocks, then room for the groups' pivots
+  std::vector<int64_t> tab((size_t)(2 * F + 3));
+  int64_t *first = tab.data() + F + 1;
+  for (int64_t f = 0; f <= F; ++f) tab[(size_t)f] = start[f];
+  const int ng = blockcv_pack(start, F, first);
+  const size_t np = (size_t)h->npad, ntab = (size_t)(F + 1) + (size_t)(ng + 1);
+  rc = h->bcv_vec.reserve(h, (7 * np + ntab + (size_t)ng) * sizeof(double));
+  if (rc == GOGP_OK) rc = h->bcv_s.reserve(h, (size_t)ng * 128 * 128 * sizeof(double));
+  if (rc != GOGP_OK) return rc;
+  double *q = h->bcv_vec.as<double>();
+  int64_t *dtab = reinterpret_cast<int64_t *>(q + 7 * np);
+  long long *dinfo = reinterpret_cast<long long *>(dtab + ntab);
+  *bv = BlockCvVecs{q, q + np, q + 2 * np, q + 3 * np, q + 4 * np, q + 5 * np, q + 6 * np, h->bcv_s.as<double>(),
+                    dtab, dtab + F + 1, ng};
+  hipStream_t s = h->s;
+  // v, ones, u and the zero vector: zero from row n on (the LOO passes read them over all npad rows)
+  HIPCHK(h, hipMemsetAsync(bv->v, 0, 4 * np * sizeof(double), s));
+  HIPCHK(h, hipMemcpyAsync(dtab, tab.data(), ntab * sizeof(int64_t), hipMemcpyHostToDevice, s));
+  launch_blockcv_groups(s, h->bufA, h->npad, h->alpha, h->dy, bv->bstart, bv->gfirst, ng, bv->mu, bv->sigma, bv->v, bv->ones,
+                        bv->logp, bv->Sg, dinfo);
+  std::vector<long long> info((size_t)ng);
+  HIPCHK(h, hipMemcpyAsync(info.data(), dinfo, (size_t)ng * sizeof(long long), hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipStreamSynchronize(s));
+  HIPCHK(h, hipGetLastError());
+  for (int g = 0; g < ng; ++g)
+    if (info[(size_t)g] != 0) {  // the first failing row: the groups are in row order
+      const int64_t row = (int64_t)info[(size_t)g] - 1;
+      int64_t f = first[g];
+      while (start[f + 1] <= row) ++f;
+      h->notpd = row;
+      snprintf(buf, sizeof buf,
+               "%s: block %lld (rows %lld .. %lld) of K^-1 is not positive definite (pivot at row %lld): K is numerically "
+               "singular", who, (long long)f, (long long)start[f], (long long)start[f + 1] - 1, (long long)row);
+      h->err = buf;
+      return GOGP_ENOTPD;
+    }
+  return GOGP_OK;
+}
+
+extern "C" int gogp_blockcv(gogp_handle *h, const int64_t *start, int64_t F, double *mu, double *sigma, double *logp,
+                            double *total) {
+  if (!h) return GOGP_EARG;
+  BlockCvVecs bv;
+  bool empty = false;
+  const int rc = blockcv_prepare(h, "block CV", start, F, &bv, &empty);
+  if (rc != GOGP_OK) return rc;
+  if (total) *total = 0.0;
+  if (empty) return GOGP_OK;
+  hipStream_t s = h->s;
+  const size_t vec = (size_t)h->n * sizeof(double);
+  std::vector<double> lp((size_t)F);
+  if (mu) HIPCHK(h, hipMemcpyAsync(mu, bv.mu, vec, hipMemcpyDeviceToHost, s));
+  if (sigma) HIPCHK(h, hipMemcpyAsync(sigma, bv.sigma, vec, hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipMemcpyAsync(lp.data(), bv.logp, lp.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipStreamSynchronize(s));
+  HIPCHK(h, hipGetLastError());
+  double t = 0.0;
+  for (int64_t f = 0; f < F; ++f) {  // the blocks' log densities, in block order
+    t += lp[(size_t)f];
+    if (logp) logp[f] = lp[(size_t)f];
+  }
+  if (total) *total = t;
+  return GOGP_OK;
+}
+
+extern "C" int gogp_blockcv_gradient(gogp_handle *h, const int64_t *start, int64_t F, double *grad, int64_t len) {
+  if (!h || !grad) return fail(h, GOGP_EARG, "block CV gradient: NULL");
+  if (len != h->P) return fail(h, GOGP_EARG, "block CV gradient: wrong length");
+  BlockCvVecs bv;
+  bool empty = false;
+  int rc = blockcv_prepare(h, "block CV gradient", start, F, &bv, &empty);
+  if (rc != GOGP_OK) return rc;
+  for (int64_t i = 0; i < len; ++i) grad[i] = 0.0;
+  if (empty) return GOGP_OK;
+  hipStream_t s = h->s;
+  const int64_t npad = h->npad, ld = npad;
+  const size_t mat = (size_t)npad * (size_t)npad;
+  rc = h->loo_mat.reserve(h, 2 * mat * sizeof(double));
+  if (rc != GOGP_OK) return rc;
+  double *B = h->loo_mat.as<double>(), *G = B + mat;
+  // B = K^-1 in full (a scale vector of ones), u = K^-1 v (its partial sums in G, which is free until the product) ...
+  launch_loo_scale_symv(s, h->bufA, ld, h->n, npad, bv.ones, bv.v, B, ld, G, bv.u);
+  // ... B <- B blockdiag(S_g) in place, and from here on gogp_loo_gradient: G = B B^T - u alpha^T - alpha u^T = -2 W
+  launch_blockcv_apply(s, B, ld, h->n, bv.bstart, bv.gfirst, bv.ngroups, bv.Sg);
+  launch_gemm_nt(s, GEMM_LOWER, h->nblk, h->nblk, npad, 1.0, (const double *)B, ld, (const double *)B, ld, 0.0, G, ld,
+                 &h->prof);
+  launch_loo_rank2(s, G, ld, h->n, npad, bv.u, h->alpha);
+  {
+    AuxTimer tm(h, GOGP_PROF_GRAD, s);
+    launch_grad_reduce(s, h->devP, h->D, h->ard_dims, h->dX, bv.zero, (const double *)G, ld, h->n, npad, h->gpart, h->gout,
                        h->radial1, h->ard_mfma_min, h->ev());
   }
   double acc[NACC];

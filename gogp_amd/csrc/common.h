@@ -438,6 +438,20 @@ void launch_loo_stats(hipStream_t s, const double *Kinv, int64_t ld, const doubl
 void launch_loo_scale_symv(hipStream_t s, const double *Kinv, int64_t ld, int64_t n, int64_t npad, const double *sc,
                            const double *v, double *B, int64_t ldb, double *upart, double *u);
 void launch_loo_rank2(hipStream_t s, double *G, int64_t ld, int64_t n, int64_t npad, const double *u, const double *alpha);
+// blockcv.hip (gogp_blockcv, gogp_blockcv_gradient): leave-block-out cross-validation.  bstart (F + 1 block starts) and
+// gfirst (ngroups + 1 first blocks of the groups, from blockcv_pack) are device arrays.  blockcv_pack: the greedy packing
+// of consecutive blocks into groups of at most 128 columns; first needs F + 1 entries, returns the number of groups.
+// launch_blockcv_groups, one workgroup per group: of Kinv (ld) only the elements j <= i < n inside the blocks are read;
+// writes mu, sigma, v and ones (= 1.0) at the rows < n, logp[f] per block, the groups' 128 x 128 S_g (ngroups * 16384
+// doubles; exact zeros off the blocks) and info[g] = first failing pivot's row + 1, or 0 (a failing group writes nothing
+// else).  launch_blockcv_apply: Q (at least ceil(n / 64) * 64 rows of ld doubles) <- Q blockdiag(S_g) in place on the rows
+// r0 < n of the 64-row slices and the columns < n; nothing else of Q is read or written.
+int blockcv_pack(const int64_t *start, int64_t F, int64_t *first);
+void launch_blockcv_groups(hipStream_t s, const double *Kinv, int64_t ld, const double *alpha, const double *y,
+                           const int64_t *bstart, const int64_t *gfirst, int ngroups, double *mu, double *sigma, double *v,
+                           double *ones, double *logp, double *Sg, long long *info);
+void launch_blockcv_apply(hipStream_t s, double *Q, int64_t ld, int64_t n, const int64_t *bstart, const int64_t *gfirst,
+                          int ngroups, const double *Sg);
 // multi.hip (gogp_multi_*): T output columns on one factorisation.  At / Yt: one output per row of ld >= npad doubles.
 // launch_multi_weight: G (ldk, as Kinv) = T Kinv - A A^T on the elements j <= i < n of the lower 64-tiles of npad, exact
 // zeros on the rest of those tiles, nothing outside them; At must hold T rounded up to a multiple of 4 rows, the rows

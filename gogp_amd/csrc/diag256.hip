@@ -455,6 +455,9 @@ __device__ void wg_gemm128(f64x4 (&c)[2][4], const double *S, double *G, const d
 
 }  // namespace
 
+// blockcv.hip compiles this file with -DGOGP_DIAG256_DEVICE_ONLY (and a namespace of its own) for the device functions
+// above alone: none of the kernels and launchers below exists in that translation unit.
+#ifndef GOGP_DIAG256_DEVICE_ONLY
 // A (ld): lower triangle of the 256x256 block (DO_POTRF) or an existing factor
 // (!DO_POTRF); Lout (ldl): factor out (DO_POTRF only); Dinv: dense 256x256
 // inverse of the factor, leading dimension 256.
@@ -654,11 +657,13 @@ __global__ __launch_bounds__(NT) void dinv256_blocks_kernel(const double *__rest
   diag256_body<false, false, 256>(S, G, rinv_s, L + b * 256 * (ld + 1), ld, nullptr, 0L, Dinv + b * 65536L, 0L, 0L, nullptr,
                                   nullptr);
 }
+#endif  // !GOGP_DIAG256_DEVICE_ONLY
 
 #define GOGP_EV 0
 #define GOGP_EVN(name) name
 #endif  // GOGP_EV
 
+#ifndef GOGP_DIAG256_DEVICE_ONLY
 // ---- tutorial-sized evaluations: N <= 128 observations in ONE workgroup, ONE launch ---------------------------------------
 // The reference's own case studies fit 20 ... 44 observations (tutorial/data/*.csv; BASELINE configs[0]: N = 64).  At that
 // size the general sweep is fifteen dependent launches of a few microseconds each (kernel trace at N = 64: 0.34 ms per
@@ -1090,8 +1095,10 @@ __global__ __launch_bounds__(NT) void GOGP_EVN(batch_eval_kernel)(const BatchIte
     if (tid < n) gx[n * D + tid] = -ys[tid];
   }
 }
+#endif  // !GOGP_DIAG256_DEVICE_ONLY
 
 #if !GOGP_EV  // second pass (the product library only): tiny_eval_kernel again, with event discounts, as tiny_eval_kernel_ev
+#ifndef GOGP_DIAG256_DEVICE_ONLY
 #ifndef GOGP_BUILD_TESTHOOKS
 #undef GOGP_EV
 #undef GOGP_EVN
@@ -1199,6 +1206,7 @@ void launch_diag256_stamped(hipStream_t s, const double *A, double *Lout, double
                      Dinv, 0L, 256L, info, stamps, 0L);
 }
 #endif
+#endif  // !GOGP_DIAG256_DEVICE_ONLY
 
 }  // namespace GOGP_NS
 #endif  // !GOGP_EV

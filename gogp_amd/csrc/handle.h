@@ -218,6 +218,8 @@ struct gogp_handle : EvalBufs, EvalState {
   Workspace rm_ws;          // gogp_remove: index maps, a pass's columns of W, the diagonal-block snapshot, compacted X / y (remove.hip)
   Workspace loo_vec;        // gogp_loo / gogp_loo_gradient: mu, sigma, log p, v, s, u, a zero vector and the block sums (loo.hip)
   Workspace loo_mat;        // gogp_loo_gradient: B = K^-1 diag(s) and G = B B^T - u alpha^T - alpha u^T, npad x npad each
+  Workspace bcv_vec;        // gogp_blockcv / gogp_blockcv_gradient: the vectors, the block and group tables, the pivots (blockcv.hip)
+  Workspace bcv_s;          // ... and the groups' 128 x 128 S_g; the gradient's two matrices are loo_mat
   // T output columns on the handle's factorisation (gogp_multi_*, multi.hip); all released with the N buffers
   int multi_T = 0;             // outputs set (gogp_multi_set_outputs) for the current data; 0: none
   bool multi_solved = false;   // A = K^-1 Y of the current factor is in multi_vec: cleared wherever have_alpha is

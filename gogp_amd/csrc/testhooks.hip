@@ -1598,6 +1598,68 @@ extern "C" int gogp_test_loo_rank2(int device, double *G, int64_t g_len, int64_t
   return fin_run(device, arrs, [&](double **d) { launch_loo_rank2(0, d[0], ld, n, npad, d[1], d[2]); });
 }
 
+// ---- the two kernels of leave-block-out cross-validation (blockcv.hip; tests/test_blockcv_kernels.py) ------------------
+namespace {
+// the block and group tables of `start` on the device, as api.hip lays them out: [F + 1 starts | ngroups + 1 firsts]
+struct BcvTables {
+  DevCopy d;
+  int ngroups = 0;
+  int64_t F = 0;
+  hipError_t up(const int64_t *start, int64_t F_) {
+    F = F_;
+    std::vector<int64_t> tab((size_t)(2 * F + 3));
+    for (int64_t f = 0; f <= F; ++f) tab[(size_t)f] = start[f];
+    ngroups = blockcv_pack(start, F, tab.data() + F + 1);
+    return d.up(tab.data(), (size_t)(F + 1 + ngroups + 1) * sizeof(int64_t));
+  }
+  const int64_t *bstart() const { return d.as<int64_t>(); }
+  const int64_t *gfirst() const { return d.as<int64_t>() + F + 1; }
+};
+}  // namespace
+
+extern "C" int gogp_test_blockcv_groups(int device, const double *Kinv, int64_t kinv_len, int64_t ld, const double *alpha,
+                                        int64_t alpha_len, const double *y, int64_t y_len, int64_t n, const int64_t *start,
+                                        int64_t F, double *mu, int64_t mu_len, double *sigma, int64_t sigma_len, double *v,
+                                        int64_t v_len, double *ones, int64_t ones_len, double *logp, int64_t logp_len,
+                                        double *Sg, int64_t sg_len, int64_t *info, int64_t info_len) {
+  const std::initializer_list<FinArr> arrs = {{Kinv, kinv_len, false}, {alpha, alpha_len, false}, {y, y_len, false},
+                                              {mu, mu_len, true},      {sigma, sigma_len, true},  {v, v_len, true},
+                                              {ones, ones_len, true},  {logp, logp_len, true},    {Sg, sg_len, true}};
+  if (!fin_have(arrs) || !info || n < 1 || n > UP_NPAD_MAX || F < 1 || gogp_blockcv_check(start, F, n) != GOGP_OK)
+    return GOGP_EARG;
+  if (!covers(kinv_len, 0, ld, n, n, 1, 0) || alpha_len < n || y_len < n) return GOGP_EARG;
+  if (mu_len < n || sigma_len < n || v_len < n || ones_len < n || logp_len < F) return GOGP_EARG;
+  std::vector<int64_t> first((size_t)F + 1);
+  const int64_t ng = blockcv_pack(start, F, first.data());
+  if (sg_len < ng * 128 * 128 || info_len < ng) return GOGP_EARG;
+  if (!device_ok(device)) return GOGP_EHIP;
+  BcvTables tab;
+  DevCopy dinfo;
+  hipError_t e = tab.up(start, F);
+  if (e == hipSuccess) e = dinfo.up(info, (size_t)info_len * sizeof(int64_t));
+  if (e != hipSuccess) return GOGP_EHIP;
+  return fin_run(device, arrs, [&](double **d) {
+    launch_blockcv_groups(0, d[0], ld, d[1], d[2], tab.bstart(), tab.gfirst(), tab.ngroups, d[3], d[4], d[5], d[6], d[7], d[8],
+                          dinfo.as<long long>());
+    if (launched() == hipSuccess) (void)dinfo.down(info);
+  });
+}
+
+extern "C" int gogp_test_blockcv_apply(int device, double *Q, int64_t q_len, int64_t q_off, int64_t ld, int64_t rows, int64_t n,
+                                       const int64_t *start, int64_t F, const double *Sg, int64_t sg_len) {
+  const std::initializer_list<FinArr> arrs = {{Q, q_len, true}, {Sg, sg_len, false}};
+  if (!fin_have(arrs) || n < 1 || n > UP_NPAD_MAX || F < 1 || gogp_blockcv_check(start, F, n) != GOGP_OK) return GOGP_EARG;
+  if (rows % 64 || rows < n || !covers(q_len, q_off, ld, rows, n, 1, 0)) return GOGP_EARG;
+  std::vector<int64_t> first((size_t)F + 1);
+  if (sg_len < (int64_t)blockcv_pack(start, F, first.data()) * 128 * 128) return GOGP_EARG;
+  if (!device_ok(device)) return GOGP_EHIP;
+  BcvTables tab;
+  if (tab.up(start, F) != hipSuccess) return GOGP_EHIP;
+  return fin_run(device, arrs, [&](double **d) {
+    launch_blockcv_apply(0, d[0] + q_off, ld, n, tab.bstart(), tab.gfirst(), tab.ngroups, d[1]);
+  });
+}
+
 extern "C" int gogp_test_multi_dots(int device, const double *Yt, int64_t yt_len, const double *At, int64_t at_len, int64_t ld,
                                     int64_t n, int T, double *dots, int64_t dots_len) {
   const std::initializer_list<FinArr> arrs = {{Yt, yt_len, false}, {At, at_len, false}, {dots, dots_len, true}};

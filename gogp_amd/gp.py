@@ -58,6 +58,26 @@ def _arr(a) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(a, dtype=np.float64))
 
 
+def _ip(a: np.ndarray):
+    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+
+
+def _starts(start) -> np.ndarray:
+    """The F + 1 block starts of the block cross-validation calls as the int64 array the library reads."""
+    st = np.ascontiguousarray(np.asarray(start, dtype=np.int64).reshape(-1))
+    if st.size < 1:
+        raise ValueError("start: F + 1 entries, from 0 to n")
+    return st
+
+
+def blocks(n: int, length: int) -> np.ndarray:
+    """``start`` of GP.BlockCV for n rows in consecutive blocks of ``length`` rows, the last one shorter where length
+    does not divide n: [0, length, 2 length, ..., n].  n = 0 gives [0]."""
+    if n < 0 or length < 1:
+        raise ValueError("blocks: n >= 0 and length >= 1")
+    return np.append(np.arange(0, n, length, dtype=np.int64), np.int64(n))
+
+
 class GP:
     """Type GP is the barebone implementation of GP (gp/gp.go:19-38)."""
 
@@ -382,6 +402,35 @@ class GP:
         product for all of them."""
         g = np.zeros(self._ns + self._nn)
         self._check(_lib.lib().gogp_loo_gradient(self._h, _dp(g), g.size))
+        return g
+
+    # ---- leave-block-out cross-validation (no reference counterpart) ----
+    def BlockCV(self, start):
+        """(mu, sigma, logp) of leave-block-out cross-validation (gogp_blockcv): the rows are cut into the F
+        consecutive blocks [start[f], start[f + 1]) -- start[0] = 0, start[F] = n, 1 .. 128 rows each; ``blocks(n,
+        length)`` builds equal ones -- and every block is predicted jointly by the process fitted to all the other
+        blocks.  mu, sigma (with the noise): n entries, the held-out prediction of every row; logp: F entries, the joint
+        log density of each block's observed values; ``logp.sum()`` is the score.  For time-ordered data this is the
+        hold-out that LOO is not; blocks of one row give LOO's values.  Works where LOO works and leaves the process as
+        it found it.  Folds that are not contiguous: permute the rows before setting the data."""
+        st = _starts(start)
+        n = int(_lib.lib().gogp_n(self._h))
+        mu, sigma, logp = np.zeros(n), np.zeros(n), np.zeros(st.size - 1)
+        self._check(_lib.lib().gogp_blockcv(self._h, _ip(st), st.size - 1, _dp(mu), _dp(sigma), _dp(logp), None))
+        return mu, sigma, logp
+
+    def BlockCVScore(self, start) -> float:
+        """The block cross-validation score sum(logp) alone, added in block order (gogp_blockcv with NULL arrays)."""
+        st = _starts(start)
+        v = ctypes.c_double(0.0)
+        self._check(_lib.lib().gogp_blockcv(self._h, _ip(st), st.size - 1, None, None, None, ctypes.byref(v)))
+        return v.value
+
+    def BlockCVGradient(self, start) -> np.ndarray:
+        """d (block cross-validation score) / d log theta, one entry per hyperparameter (gogp_blockcv_gradient)."""
+        st = _starts(start)
+        g = np.zeros(self._ns + self._nn)
+        self._check(_lib.lib().gogp_blockcv_gradient(self._h, _ip(st), st.size - 1, _dp(g), g.size))
         return g
 
     # ---- multi-output: T output columns on one factorisation (no reference counterpart) ----
@@ -865,6 +914,35 @@ class LOOModel:
 
     def Gradient(self) -> np.ndarray:
         g = self.gp.LOOGradient()
+        if self.Priors is not None:
+            self.Priors.Observe(self._x)
+            pg = np.asarray(self.Priors.Gradient(), dtype=float)
+            g[:len(pg)] += pg
+        return g
+
+
+class BlockCVModel:
+    """LOOModel with the leave-block-out score of GP.BlockCVScore(start) in the place of the LOO score: Observe(x) runs
+    gp.Observe(x) and returns the score (+ the log prior), Gradient() returns GP.BlockCVGradient(start) (+ the
+    prior's).  ``start`` is fixed at construction (``blocks(n, length)`` for equal blocks).  As with LOOModel the
+    batched line search is not offered: the GP is ``gp`` here, not ``GP``."""
+
+    def __init__(self, gp: GP, start, Priors=None):
+        self.gp = gp
+        self.start = _starts(start).copy()
+        self.Priors = Priors
+        self._x = None
+
+    def Observe(self, x) -> float:
+        self._x = _arr(x).reshape(-1).copy()
+        if self._x.size != self.gp._ns + self.gp._nn:
+            raise ValueError("len(x): the block cross-validation objective takes the hyperparameters only")
+        self.gp.Observe(self._x)
+        v = self.gp.BlockCVScore(self.start)
+        return v + self.Priors.Observe(self._x) if self.Priors is not None else v
+
+    def Gradient(self) -> np.ndarray:
+        g = self.gp.BlockCVGradient(self.start)
         if self.Priors is not None:
             self.Priors.Observe(self._x)
             pg = np.asarray(self.Priors.Gradient(), dtype=float)

@@ -184,6 +184,36 @@ class GP {
     return g;
   }
 
+  // Leave-block-out cross-validation at the current parameters (gogp_blockcv): the rows are cut into the consecutive
+  // blocks [start[f], start[f + 1]) -- start[0] = 0, start[F] = n, 1 .. GOGP_BLOCKCV_MAX rows each; blocks() builds equal
+  // ones -- and every block is predicted jointly by the process fitted to all the other blocks.  mu, sigma: per row; logp:
+  // the joint log density per block; returns their sum.  No reference counterpart.  Folds that are not contiguous:
+  // permute the rows before assigning X / Y.
+  static std::vector<int64_t> blocks(int64_t n, int64_t length) {
+    std::vector<int64_t> start;
+    for (int64_t s = 0; s < n && length > 0; s += length) start.push_back(s);
+    start.push_back(n);
+    return start;
+  }
+  double BlockCV(const std::vector<int64_t> &start, std::vector<double> &mu, std::vector<double> &sigma,
+                 std::vector<double> &logp) {
+    if (start.empty()) throw std::invalid_argument("gogp: BlockCV: start needs F + 1 entries");
+    const size_t n = (size_t)gogp_n(h_);
+    mu.assign(n, 0.0);
+    sigma.assign(n, 0.0);
+    logp.assign(start.size() - 1, 0.0);
+    double total = 0.0;
+    check(gogp_blockcv(h_, start.data(), (int64_t)start.size() - 1, mu.data(), sigma.data(), logp.data(), &total));
+    return total;
+  }
+  // d (BlockCV score) / d log theta, one entry per hyperparameter (gogp_blockcv_gradient)
+  std::vector<double> BlockCVGradient(const std::vector<int64_t> &start) {
+    if (start.empty()) throw std::invalid_argument("gogp: BlockCVGradient: start needs F + 1 entries");
+    std::vector<double> g(ThetaSimil.size() + ThetaNoise.size(), 0.0);
+    check(gogp_blockcv_gradient(h_, start.data(), (int64_t)start.size() - 1, g.data(), (int64_t)g.size()));
+    return g;
+  }
+
   // Multi-output (gogp_multi_*): T output columns observed at the inputs X, sharing the kernel and the hyperparameters,
   // on one factorisation; no reference counterpart.  SetOutputs: Yt row-major n x T, n = Y.size(), T <= GOGP_MULTI_MAX_T
   // (pending X / Y are uploaded first; T == 0 clears); the outputs are dropped by whatever replaces or resizes the data.

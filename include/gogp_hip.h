@@ -225,6 +225,56 @@ int gogp_gradient(gogp_handle *h, double *grad, int64_t len);
 int gogp_loo(gogp_handle *h, double *mu, double *sigma, double *logp, double *total);
 int gogp_loo_gradient(gogp_handle *h, double *grad, int64_t len);
 
+/* Leave-block-out ("h-block", leave-out-k; Rasmussen & Williams 5.4.2) cross-validation at the parameters of the last
+ * gogp_absorb / gogp_observe[_full] / gogp_set_factor; no reference counterpart.  The rows are cut into F consecutive
+ * blocks B_f = [start[f], start[f + 1]), start[0] = 0, start[F] = n, of 1 .. GOGP_BLOCKCV_MAX rows each, and every block
+ * is predicted jointly by the process fitted to all the other blocks: for time-ordered data the hold-out that leave-one-
+ * out is not (its held-out point sits between neighbours one step away).  From the explicit K^-1 = Q the gradient leaves
+ * on the device and alpha, per block with Q_BB = C C^T (lower Cholesky), X = C^-1, w = X alpha_B, v_B = X^T w:
+ *     mu_B = y_B - v_B,  sigma_i = sqrt((X^T X)_ii)  (noise included, as gogp_loo),
+ *     logp_f = -1/2 |w|^2 + sum_i log C_ii - |B_f| / 2 log 2 pi = log p(y_B | every other block),  total = sum_f logp_f
+ * (added in block order).  mu, sigma: n doubles; logp: F doubles; any of them and total may be NULL.  Blocks of one row
+ * give gogp_loo's values.
+ * gogp_blockcv_gradient: d total / d log theta, P entries (`len` must be P), as gogp_loo_gradient: sum_ab W_ab dK_ab with
+ * W = 1/2 (u alpha^T + alpha u^T) - 1/2 Q M Q, v the stacked v_B, u = Q v, M = blockdiag(X^T X + v_B v_B^T), whose
+ * square root S_B = X^T + gamma v_B w^T, gamma = 1 / (sqrt(1 + |w|^2) + 1), needs no second factorisation; Q blockdiag(S_B)
+ * then takes the place of gogp_loo_gradient's K^-1 diag(s), so every kernel family, ARD and the event discounts of
+ * gogp_set_events are covered.
+ * gogp_blockcv_check (host only): GOGP_OK for a `start` as described -- start[0] == 0, strictly increasing, start[F] == n,
+ * every block of at most GOGP_BLOCKCV_MAX rows -- else GOGP_EARG.  gogp_blockcv_groups (host only): how the calls pack
+ * consecutive blocks, greedily and in order, into groups of at most 128 rows, each factored by one workgroup (blocks of
+ * one row cost n / 128 workgroups, not n): group g holds the blocks first[g] .. first[g + 1] - 1; first has room for
+ * F + 1 entries, *ngroups <= 2 n / 129 + 1.
+ * Contract (gogp_loo's, restated for blocks): works wherever gogp_loo works -- after Absorb, Observe in either form,
+ * gogp_append, gogp_remove and gogp_set_factor -- and forms K^-1 as gogp_gradient does where it is missing.  The handle
+ * is left as it was found: a gogp_gradient, gogp_produce, gogp_get_factor, gogp_loo, gogp_loo_gradient or gogp_append made
+ * afterwards returns the bits it would have returned without these calls.  Two identical calls return identical bits
+ * (fixed-order sums, no atomics); the result depends on K^-1, alpha, y and start alone.  n == 0 (F == 0, start = {0}):
+ * total = 0, the arrays are not written, the gradient is zeros.
+ * GOGP_EARG: what gogp_blockcv_check refuses, len != P, a precision = 32 handle, "gradient_precision" = 32 and a sharded
+ * handle (gogp_loo's refusals).  GOGP_ESTATE before anything is factored.  GOGP_ENOTPD: a block of K^-1 has a
+ * non-positive pivot, which happens only when K is numerically singular; gogp_notpd_index is the row, gogp_last_error
+ * names the block, nothing is promised for the outputs and the fitted process is untouched.  Nothing is clamped.
+ * Out of scope: blocks longer than GOGP_BLOCKCV_MAX rows (the per-block factorisation lives in LDS; longer folds would
+ * go through the factorisation launches of gogp_produce_samples); buffer zones around a block ("hv-block");
+ * non-contiguous folds -- row order carries no meaning for the process, so a caller who wants random folds permutes the
+ * rows before gogp_set_data; the fp32 and sharded paths.
+ * Device memory: gogp_blockcv 7 vectors of npad doubles, the tables of start and the groups' 128 x 128 square roots
+ * (ngroups x 128 KB: under 34 MB at n = 16384); gogp_blockcv_gradient also gogp_loo_gradient's two npad x npad matrices,
+ * which it shares.
+ * Cost, measured on one MI355X with K^-1 in place (profiles/blockcv.txt; D = 8, blocks of 1 / 16 / 128 rows, beside
+ * gogp_loo, gogp_loo_gradient and Observe + Gradient on the same build): gogp_blockcv 0.13 - 0.14 ms at n = 1024 and
+ * 4096, 0.15 - 0.19 ms at n = 16384, against 0.08 - 0.10 ms for gogp_loo -- the group kernel is 48 - 66 us whatever n and
+ * the block length, the rest is the upload of start, the copies and two synchronises; gogp_blockcv_gradient 0.22 - 0.23 /
+ * 1.70 - 1.73 / 71.2 - 71.6 ms at n = 1024 / 4096 / 16384 against 0.13 / 1.50 / 68.4 ms for gogp_loo_gradient and
+ * 0.67 / 3.1 / 71.2 ms for Observe + Gradient: at n = 16384 the block multiply is 2.4 ms, 3.6 % of the product behind it
+ * (66.5 ms).  For blocks of one row gogp_loo remains the call: the same numbers to 1e-14 at about half the time. */
+#define GOGP_BLOCKCV_MAX 128
+int gogp_blockcv_check(const int64_t *start, int64_t F, int64_t n);
+int gogp_blockcv_groups(const int64_t *start, int64_t F, int64_t *first, int64_t *ngroups);
+int gogp_blockcv(gogp_handle *h, const int64_t *start, int64_t F, double *mu, double *sigma, double *logp, double *total);
+int gogp_blockcv_gradient(gogp_handle *h, const int64_t *start, int64_t F, double *grad, int64_t len);
+
 /* Multi-output: T output columns Y = [y_1 .. y_T] observed at the handle's inputs, sharing its kernel and
  * hyperparameters, on ONE factorisation; no reference counterpart (gp.GP holds one output vector).  The columns are
  * independent: no cross-output covariance, no per-output theta.  With A = K^-1 Y

@@ -312,6 +312,23 @@ int gogp_test_loo_scale_symv(int device, const double *Kinv, int64_t kinv_len, i
  * those tiles: the elements with i >= n or j >= n then keep their bits. */
 int gogp_test_loo_rank2(int device, double *G, int64_t g_len, int64_t ld, int64_t n, int64_t npad, const double *u,
                         int64_t u_len, const double *alpha, int64_t alpha_len);
+/* The two kernels of leave-block-out cross-validation (blockcv.hip; tests/test_blockcv_kernels.py) on caller-supplied
+ * matrices.  start, F: as gogp_blockcv_check accepts them for n (else GOGP_EARG); the packing into groups is
+ * gogp_blockcv_groups'.
+ * launch_blockcv_groups: Kinv n rows of ld >= n, of which only the elements j <= i inside a block are read; alpha, y: n
+ * doubles read.  In / out: mu, sigma, v, ones (n doubles: every row written, ones with 1.0), logp (F doubles), Sg
+ * (ngroups x 128 x 128 doubles: S_B on the diagonal blocks of each group, exact zeros elsewhere) and info (ngroups
+ * entries: the first failing pivot's row + 1, or 0; a failing group writes nothing else). */
+int gogp_test_blockcv_groups(int device, const double *Kinv, int64_t kinv_len, int64_t ld, const double *alpha,
+                             int64_t alpha_len, const double *y, int64_t y_len, int64_t n, const int64_t *start, int64_t F,
+                             double *mu, int64_t mu_len, double *sigma, int64_t sigma_len, double *v, int64_t v_len,
+                             double *ones, int64_t ones_len, double *logp, int64_t logp_len, double *Sg, int64_t sg_len,
+                             int64_t *info, int64_t info_len);
+/* launch_blockcv_apply: the matrix at Q + q_off (in / out; `rows` rows of ld >= n, rows a multiple of 64 and >= n)
+ * <- itself times blockdiag(S_g), in place, on the 64-row slices that hold a row < n and the columns < n; nothing else of
+ * Q is read or written.  Sg: ngroups x 128 x 128 doubles, read. */
+int gogp_test_blockcv_apply(int device, double *Q, int64_t q_len, int64_t q_off, int64_t ld, int64_t rows, int64_t n,
+                            const int64_t *start, int64_t F, const double *Sg, int64_t sg_len);
 /* launch_multi_dots: dots[t] (in / out) = sum_{i < n} Yt[t][i] At[t][i], t < T <= GOGP_MULTI_MAX_T; Yt, At: T rows of
  * ld >= n. */
 int gogp_test_multi_dots(int device, const double *Yt, int64_t yt_len, const double *At, int64_t at_len, int64_t ld, int64_t n,
