@@ -402,6 +402,87 @@ func (gp *GP) ProduceCovariance(x [][]float64) (mu, cov []float64, err error) {
 	return mu, cov, nil
 }
 
+// Likelihoods of LaplaceObserve (enum gogp_lik_kind).
+const (
+	BernoulliLogit = int(C.GOGP_LIK_BERNOULLI_LOGIT) // Y in {0, 1}
+	PoissonLog     = int(C.GOGP_LIK_POISSON_LOG)     // Y: counts
+)
+
+// ErrNoConvergence is returned by LaplaceObserve when Newton's iteration did
+// not reach the tolerance; the last iterate is stored and its value returned.
+var ErrNoConvergence = fmt.Errorf("gogp_hip: laplace: Newton did not reach the tolerance")
+
+// LaplaceObserve computes the approximate log marginal likelihood of Y under
+// the likelihood lik at x = log theta by the Laplace approximation around the
+// mode found by a damped Newton iteration (no reference counterpart). It drops
+// the regression state: Gradient, Produce and the rest need a new Absorb or
+// Observe. Unlike Observe, whose signature is the reference's and which must
+// panic where the reference does, this call has an error result: GOGP_ECOND
+// and GOGP_ENOCONV both come back as errors (ErrNoConvergence for the latter)
+// together with the stored value, as Absorb returns GOGP_ECOND; nothing panics.
+func (gp *GP) LaplaceObserve(x []float64, lik int) (float64, error) {
+	gp.defaults()
+	if err := gp.pushData(); err != nil {
+		return 0, err
+	}
+	gp.withObs = false
+	var z C.double
+	rc := C.gogp_laplace_observe(gp.handle(), C.int32_t(lik), dptr(x), C.int64_t(len(x)), &z)
+	if rc == C.GOGP_OK || rc == C.GOGP_ECOND || rc == C.GOGP_ENOCONV {
+		ns := len(gp.ThetaSimil)
+		for i := range gp.ThetaSimil {
+			gp.ThetaSimil[i] = math.Exp(x[i])
+		}
+		for i := range gp.ThetaNoise {
+			gp.ThetaNoise[i] = math.Exp(x[ns+i])
+		}
+	}
+	if rc == C.GOGP_ENOCONV {
+		return float64(z), ErrNoConvergence
+	}
+	return float64(z), gp.err(rc)
+}
+
+// LaplaceGradient computes the gradient of LaplaceObserve with respect to the
+// log-transformed hyperparameters, the movement of the mode included.
+func (gp *GP) LaplaceGradient() ([]float64, error) {
+	gp.defaults()
+	g := make([]float64, len(gp.ThetaSimil)+len(gp.ThetaNoise))
+	if err := gp.err(C.gogp_laplace_gradient(gp.handle(), dptr(g), C.int64_t(len(g)))); err != nil {
+		return nil, err
+	}
+	return g, nil
+}
+
+// LaplaceMode returns the latent values f and a = K^-1 f at the mode and the
+// Newton steps the last LaplaceObserve took.
+func (gp *GP) LaplaceMode() (f, a []float64, iterations int, err error) {
+	n := int(C.gogp_n(gp.handle()))
+	f, a = make([]float64, n), make([]float64, n)
+	var it C.int32_t
+	if err = gp.err(C.gogp_laplace_get_mode(gp.handle(), dptr(f), dptr(a), &it)); err != nil {
+		return nil, nil, 0, err
+	}
+	return f, a, int(it), nil
+}
+
+// LaplaceProduce computes the latent mean and standard deviation (no noise, as
+// Produce) and the response-scale prediction at the test points: E[y*] for
+// PoissonLog, P(y* = 1) for BernoulliLogit.
+func (gp *GP) LaplaceProduce(x [][]float64) (mu, sigma, mean []float64, err error) {
+	m := len(x)
+	flat := make([]float64, m*gp.NDim)
+	for i, row := range x {
+		copy(flat[i*gp.NDim:], row)
+	}
+	mu, sigma, mean = make([]float64, m), make([]float64, m), make([]float64, m)
+	rc := C.gogp_laplace_produce(gp.handle(), dptr(flat), C.int64_t(m), dptr(mu), dptr(sigma), dptr(mean))
+	if err = gp.err(rc); err != nil {
+		return nil, nil, nil, err
+	}
+	return mu, sigma, mean, nil
+}
+
 // LOO computes the leave-one-out cross-validation predictions at the current
 // parameters: mean, standard deviation and log density of every observation
 // under the process fitted to the others, and the sum of the log densities (no

@@ -17,6 +17,8 @@ LIB_PATH = os.path.join(_HERE, "libgogp_hip.so")
 HOOKS_PATH = os.path.join(_HERE, "libgogp_testhooks.so")
 
 GOGP_OK, GOGP_EARG, GOGP_ENOTPD, GOGP_EHIP, GOGP_ESTATE, GOGP_ENOMEM, GOGP_ECOND = 0, 1, 2, 3, 4, 5, 6
+GOGP_ENOCONV = 7  # gogp_laplace_observe: Newton did not reach the tolerance (the last iterate is stored)
+GOGP_LIK_BERNOULLI_LOGIT, GOGP_LIK_POISSON_LOG = 0, 1
 GOGP_MAX_CANDIDATES = 16
 GOGP_BATCH_MAX_N = 128
 GOGP_COV_MAX_M = 4096
@@ -93,6 +95,11 @@ SYMBOLS = [
     ("gogp_blockcv_groups", ctypes.c_int, [ctypes.POINTER(_i64), _i64, ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
     ("gogp_blockcv", ctypes.c_int, [_h, ctypes.POINTER(_i64), _i64, _dp, _dp, _dp, _dp]),
     ("gogp_blockcv_gradient", ctypes.c_int, [_h, ctypes.POINTER(_i64), _i64, _dp, _i64]),
+    ("gogp_laplace_check", ctypes.c_int, [ctypes.c_int32, _dp, _i64]),
+    ("gogp_laplace_observe", ctypes.c_int, [_h, ctypes.c_int32, _dp, _i64, _dp]),
+    ("gogp_laplace_gradient", ctypes.c_int, [_h, _dp, _i64]),
+    ("gogp_laplace_get_mode", ctypes.c_int, [_h, _dp, _dp, ctypes.POINTER(ctypes.c_int32)]),
+    ("gogp_laplace_produce", ctypes.c_int, [_h, _dp, _i64, _dp, _dp, _dp]),
     ("gogp_multi_set_outputs", ctypes.c_int, [_h, _dp, _i64, ctypes.c_int32]),
     ("gogp_multi_lml", ctypes.c_int, [_h, _dp, _dp]),
     ("gogp_multi_gradient", ctypes.c_int, [_h, _dp, _i64]),
@@ -284,6 +291,24 @@ FINISH_HOOKS = {k: [tuple(t.split(":")) for t in v.split()] for k, v in _FINISH_
 _FINISH_CTYPES = {"a": [_dp, _i64], "o": [_dp, _i64], "l": [_i64], "i": [ctypes.c_int], "d": [ctypes.c_double]}
 HOOK_SYMBOLS += [("gogp_test_" + k, ctypes.c_int, [ctypes.c_int] + [t for _, kind in spec for t in _FINISH_CTYPES[kind]])
                  for k, spec in FINISH_HOOKS.items()]
+
+
+#: the hooks of the kernels of the Laplace approximation (tests/test_laplace_kernels.py), as gp.laplace_kernel_check reads
+#: them: the notation of _FINISH_SPEC
+_LAPLACE_SPEC = {
+    "lap_site": "lik:i f:a y:a a:a n:l npad:l g:o W:o sw:o b:o rho:o part:o out:o",
+    "lap_scale_gram": "A:o ld:l n:l npad:l sw:a wcols:l",
+    "lap_step": "b:a sw:a beta:a n:l npad:l rhs:o a1:o",
+    "lap_interp": "a:a a1:a f:a f1:a t:d n:l npad:l at:o ft:o",
+    "lap_weight_vectors": "Binv:a ld:l rho:a n:l npad:l sv:o",
+    "lap_symv_u": "Binv:a ld:l n:l npad:l v:a sv:a sw:a upart:o u:o",
+    "lap_weight": "G:o ld:l n:l npad:l sw:a u:a a:a",
+    "lap_colscale": "KsT:o ld:l rows:l npad:l sw:a",
+    "lap_mean": "lik:i mu:a sigma:a m:l mean:o",
+}
+LAPLACE_HOOKS = {k: [tuple(t.split(":")) for t in v.split()] for k, v in _LAPLACE_SPEC.items()}
+HOOK_SYMBOLS += [("gogp_test_" + k, ctypes.c_int, [ctypes.c_int] + [t for _, kind in spec for t in _FINISH_CTYPES[kind]])
+                 for k, spec in LAPLACE_HOOKS.items()]
 
 
 def build(force: bool = False) -> str:

@@ -106,6 +106,8 @@ static void free_n_buffers(gogp_handle *h) {
   h->rm_ws.release();
   h->loo_vec.release();
   h->loo_mat.release();
+  h->lap_ws.release();
+  h->lap_observed = h->lap_grad_valid = h->lap_warm_valid = false;
   h->bcv_vec.release();
   h->bcv_s.release();
   h->multi_vec.release();
@@ -344,6 +346,7 @@ static int ensure_n(gogp_handle *h, int64_t n) {
   h->factored = h->have_alpha = h->have_kinv = h->observed = h->grad_valid = false;
   h->multi_solved = false;
   h->trtri_done = false;
+  h->lap_observed = h->lap_grad_valid = h->lap_warm_valid = false;  // the Laplace fit and its warm start belonged to the old data
   if (npad > h->cap_npad) {
     free_n_buffers(h);
     NBufs nb;
@@ -423,6 +426,7 @@ extern "C" int gogp_set_events(gogp_handle *h, const double *events, int nevents
     for (int f = 0; f < 3; ++f) h->events[e][f] = events[3 * e + f];
   h->factored = h->have_alpha = h->have_kinv = h->observed = h->grad_valid = false;
   h->multi_solved = false;
+  h->lap_observed = h->lap_grad_valid = false;
   h->trtri_done = h->trtri_pending = h->alpha_pending = h->kinv_pending = false;
   h->tinv_valid = h->tinv_pending = false;
   return GOGP_OK;
@@ -955,6 +959,7 @@ static void begin_evaluation(gogp_handle *h, std::initializer_list<hipStream_t> 
   h->trtri_pending = h->kinv_pending = false;
   h->factored = h->have_alpha = h->have_kinv = h->grad_valid = false;
   h->multi_solved = false;
+  h->lap_observed = h->lap_grad_valid = false;  // a new factor replaces a Laplace fit's (gogp_laplace_observe sets them behind its own)
   h->alpha_pending = h->trtri_done = h->ydone_valid = h->d64_active = false;
   h->notpd = -1;
   h->kinv_c1 = 0;
@@ -1031,6 +1036,10 @@ struct Sweep {
     {
       AuxTimer tm(h, GOGP_PROF_GRAM, s);  // the main-stream part: all but the first block columns
       launch_gram_lower_split(sp, s, h->devP, h->D, h->dX, h->n, npad, A, ld, (int64_t)w0 * PANEL, h->ev());
+      // a Laplace observe in progress: B = I + diag(sw) K diag(sw), right behind each part on its own stream
+      if constexpr (!fp32) {
+        if (h->lap_sw) launch_lap_scale_gram(sp, s, A, ld, h->n, npad, h->lap_sw, (int64_t)w0 * PANEL);
+      }
     }
     // fp32 path, option "diag_fp64": the diagonal blocks leave the float matrix here -- widened once, every later
     // contribution summed in fp64 (diagsyrk.hip); the first super-panel's on the chain stream, the rest behind the build
@@ -1215,7 +1224,8 @@ static int factorize_t(gogp_handle *h, bool eager) {
   if (rc != GOGP_OK) return rc;
   if (c.fp32) HIPCHK(h, hipMemsetAsync(h->scalars + 5, 0, sizeof(double), c.sp));  // fp64 logdet
   // working copy of y for the forward substitution, whose steps follow the chain on sz
-  HIPCHK(h, cand_copy_in(h, h->w, h->dy, (size_t)c.npad * sizeof(double), c.sp));
+  // (a Laplace observe: of its Newton step's right-hand side)
+  HIPCHK(h, cand_copy_in(h, h->w, h->lap_rhs ? h->lap_rhs : h->dy, (size_t)c.npad * sizeof(double), c.sp));
   if (c.sz != c.sp) order(h, EV_W, c.sp, c.sz);
   for (const SuperPanel &P : superpanels(h)) {
     c.chain_superpanel(P);
@@ -1315,6 +1325,7 @@ extern "C" int gogp_absorb(gogp_handle *h, const double *theta_simil,
   h->observed = false;  // gp/gp.go:85-86: no gradient after Absorb
   h->with_obs = false;
   h->grad_valid = false;
+  h->lap_observed = h->lap_grad_valid = false;
   if (h->n == 0) {  // gp/gp.go:101-104
     h->lml = 0.0;
     h->factored = false;
@@ -1336,6 +1347,7 @@ static int observe_theta(gogp_handle *h, const double *x, double *lml) {
   int rc = set_theta_natural(h, th.data(), th.data() + h->ns);
   if (rc != GOGP_OK) return rc;
   h->grad_valid = false;
+  h->lap_observed = h->lap_grad_valid = false;
   if (h->n == 0) {
     h->lml = 0.0;
     h->factored = false;
@@ -3708,6 +3720,322 @@ extern "C" int gogp_sparse_multi_produce(gogp_handle *h, const double *Z, int64_
   return GOGP_OK;
 }
 
+// ---- non-Gaussian likelihoods by the Laplace approximation (laplace.hip) -----------------------------------------------
+// No reference counterpart.  The formulas are in laplace.hip and DESIGN.md section 4 "Laplace".  Every Newton step is
+// one non-eager factorize_t<double> of B = I + diag(sw) K diag(sw) -- the Gram stage scales K (Sweep::build_gram), the
+// sweep's working copy is the step's right-hand side, so z = L^-1 rhs and beta = B^-1 rhs (in h->alpha) come with the
+// factor -- around two matrix-free products with K and a few passes over vectors; the host reads five doubles per
+// evaluation of psi.  The general sweep runs at every n (the one-launch path of tiny_factorize builds K itself).
+struct LapVecs {
+  double *a, *f, *a1, *f1, *at, *ft, *g, *W, *sw, *b, *rho, *kv, *rhs, *sv, *u, *awarm, *kpart, *part, *out;
+};
+static size_t lap_layout(double *q, int64_t npad, LapVecs *v) {
+  const size_t np = (size_t)npad;
+  double **vec[] = {&v->a, &v->f, &v->a1, &v->f1, &v->at, &v->ft, &v->g, &v->W, &v->sw, &v->b, &v->rho, &v->kv, &v->rhs,
+                    &v->sv, &v->u, &v->awarm};
+  size_t off = 0;
+  auto at = [&](size_t count) {  // (q == nullptr: the size alone is asked for)
+    double *p = q ? q + off : nullptr;
+    off += count;
+    return p;
+  };
+  for (double **p : vec) *p = at(np);
+  v->kpart = at((size_t)REFINE_SLABS * np);  // the slabs of launch_kmatvec_share
+  v->part = at(5 * (np / PANEL));
+  v->out = at(8);
+  return off * sizeof(double);
+}
+static int lap_vecs(gogp_handle *h, LapVecs *v) {
+  const int rc = h->lap_ws.reserve(h, lap_layout(nullptr, std::max(h->npad, h->cap_npad), v));
+  if (rc != GOGP_OK) return rc;
+  lap_layout(h->lap_ws.as<double>(), h->npad, v);
+  return GOGP_OK;
+}
+static inline bool lap_lik_ok(int32_t lik) { return lik == GOGP_LIK_BERNOULLI_LOGIT || lik == GOGP_LIK_POISSON_LOG; }
+static const char *lap_refusal(const gogp_handle *h) {
+  return h->prec == 32         ? "precision = 32 handles"
+         : h->grad_prec == 32 ? "gradient_precision = 32"
+         : h->dist            ? "sharded handles"
+                              : nullptr;
+}
+static int lap_refuse(gogp_handle *h, const char *who) {
+  const char *why = lap_refusal(h);
+  if (!why) return GOGP_OK;
+  char buf[160];
+  snprintf(buf, sizeof buf, "%s: %s are not supported", who, why);
+  return fail(h, GOGP_EARG, buf);
+}
+
+extern "C" int gogp_laplace_check(int32_t lik, const double *y, int64_t n) {
+  if (!lap_lik_ok(lik) || n < 0 || (n > 0 && !y)) return GOGP_EARG;
+  for (int64_t i = 0; i < n; ++i) {
+    const double v = y[i];
+    const bool ok = lik == GOGP_LIK_BERNOULLI_LOGIT ? (v == 0.0 || v == 1.0)
+                                                    : (v >= 0.0 && v <= 9007199254740992.0 && v == floor(v));
+    if (!ok) return GOGP_EARG;
+  }
+  return GOGP_OK;
+}
+
+// v -> K v on the main stream (kv and kpart of the workspace are free between the steps)
+static void lap_kmatvec(gogp_handle *h, const LapVecs &v, const double *in, double *out) {
+  launch_kmatvec_share(h->s, h->devP, h->D, h->dX, h->n, h->npad, in, 0, 1, v.kpart, REFINE_SLABS, out, h->radial1, h->ev());
+}
+// The site functions at (a, f) into the workspace and hs[0 .. 4] (laplace.hip: launch_lap_site) on the host
+static int lap_sites(gogp_handle *h, const LapVecs &v, int lik, const double *a, const double *f, double *hs) {
+  launch_lap_site(h->s, lik, f, h->dy, a, h->n, h->npad, v.g, v.W, v.sw, v.b, v.rho, v.part, v.out);
+  HIPCHK(h, hipMemcpyAsync(hs, v.out, 5 * sizeof(double), hipMemcpyDeviceToHost, h->s));
+  HIPCHK(h, hipStreamSynchronize(h->s));
+  HIPCHK(h, hipGetLastError());
+  return GOGP_OK;
+}
+// One factorisation of B at the site vectors in the workspace, with rhs as the sweep's right-hand side: beta = B^-1 rhs
+// is in h->alpha and ordered on the main stream afterwards.  What it says about a REGRESSION state is taken back.
+static int lap_factorize(gogp_handle *h, const LapVecs &v) {
+  h->lap_sw = v.sw;
+  h->lap_rhs = v.rhs;
+  int rc = factorize_t<double>(h, false);
+  h->lap_sw = h->lap_rhs = nullptr;
+  if (rc == GOGP_OK || rc == GOGP_ECOND) {
+    const int rca = ensure_alpha(h);
+    if (rca != GOGP_OK) rc = rca;
+  }
+  h->factored = h->have_alpha = h->observed = h->with_obs = h->z_valid = false;
+  return rc;
+}
+
+// The Newton iteration from a = 0 (or, `warm`, the stored a^); on return *conv says whether the tolerance was reached.
+// GOGP_OK / GOGP_ECOND: B's factor at the last iterate is in place, h->lap_iters and *psi belong to it.
+static int lap_newton(gogp_handle *h, const LapVecs &v, int lik, bool warm, bool *conv, double *psi_out) {
+  hipStream_t s = h->s;
+  const int64_t n = h->n, npad = h->npad;
+  const size_t vec = (size_t)npad * sizeof(double);
+  const double tol = pow(10.0, (double)h->lap_tol_log10);
+  if (warm) {
+    HIPCHK(h, hipMemcpyAsync(v.a, v.awarm, vec, hipMemcpyDeviceToDevice, s));
+    lap_kmatvec(h, v, v.a, v.f);
+  } else {
+    HIPCHK(h, hipMemsetAsync(v.a, 0, vec, s));
+    HIPCHK(h, hipMemsetAsync(v.f, 0, vec, s));
+  }
+  double hs[5];
+  int rc = lap_sites(h, v, lik, v.a, v.f, hs);
+  if (rc != GOGP_OK) return rc;
+  if (hs[4] >= 0.0) {
+    char buf[160];
+    snprintf(buf, sizeof buf, "laplace_observe: y[%lld] is not a value of the likelihood", (long long)hs[4]);
+    return fail(h, GOGP_EARG, buf);
+  }
+  double psi = -0.5 * hs[1] + hs[0];
+  bool stuck = false;
+  int rcf = GOGP_OK;
+  h->lap_iters = 0;
+  *conv = false;
+  for (;;) {
+    *conv = hs[2] <= tol * std::max(1.0, hs[3]);
+    const bool stop = *conv || stuck || h->lap_iters >= h->lap_max_iter;
+    // rhs = sw o (K b); at the last iterate the factor alone is wanted and the right-hand side is whatever rhs holds
+    if (!stop) {
+      lap_kmatvec(h, v, v.b, v.kv);
+      launch_lap_vec(s, nullptr, v.sw, v.kv, n, npad, v.rhs);
+    } else {
+      HIPCHK(h, hipMemsetAsync(v.rhs, 0, vec, s));
+    }
+    rcf = lap_factorize(h, v);
+    if (rcf != GOGP_OK && rcf != GOGP_ECOND) return rcf;
+    if (stop) break;
+    // a+ = b - sw o beta, f+ = K a+
+    launch_lap_vec(s, v.b, v.sw, h->alpha, n, npad, v.a1);
+    lap_kmatvec(h, v, v.a1, v.f1);
+    // damping: f is linear in a, so a halving costs passes over vectors only
+    double t = 1.0;
+    int halvings = 0;
+    for (;;) {
+      launch_lap_interp(s, v.a, v.a1, v.f, v.f1, t, n, npad, v.at, v.ft);
+      rc = lap_sites(h, v, lik, v.at, v.ft, hs);
+      if (rc != GOGP_OK) return rc;
+      const double psit = -0.5 * hs[1] + hs[0];
+      // "psi does not increase", to the rounding of its two sums: a step that gains less than that is taken as it is
+      if (psit >= psi - 1e-12 * std::max(1.0, fabs(psi))) {
+        psi = psit;
+        break;
+      }
+      if (++halvings > 20) {
+        stuck = true;
+        break;
+      }
+      t *= 0.5;
+    }
+    if (stuck) {  // back to the iterate the step started from, and its site vectors
+      rc = lap_sites(h, v, lik, v.a, v.f, hs);
+      if (rc != GOGP_OK) return rc;
+      hs[2] = INFINITY;  // (not converged, whatever the residual says)
+      continue;
+    }
+    HIPCHK(h, hipMemcpyAsync(v.a, v.at, vec, hipMemcpyDeviceToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(v.f, v.ft, vec, hipMemcpyDeviceToDevice, s));
+    ++h->lap_iters;
+  }
+  if (stuck) *conv = false;
+  *psi_out = psi;
+  return rcf;
+}
+
+extern "C" int gogp_laplace_observe(gogp_handle *h, int32_t lik, const double *x, int64_t len, double *lml) {
+  if (!h || !x) return fail(h, GOGP_EARG, "laplace_observe: NULL");
+  if (lml) *lml = NAN;
+  if (len != h->P) return fail(h, GOGP_EARG, "laplace_observe: len(x)");
+  if (!lap_lik_ok(lik)) return fail(h, GOGP_EARG, "laplace_observe: unknown likelihood");
+  int rc = lap_refuse(h, "laplace_observe");
+  if (rc != GOGP_OK) return rc;
+  if (!h->have_data) return fail(h, GOGP_ESTATE, "laplace_observe: no data (gogp_set_data)");
+  HIPCHK(h, hipSetDevice(h->device));
+  std::vector<double> th(h->P > 0 ? h->P : 1);
+  for (int i = 0; i < h->P; ++i) th[i] = exp(x[i]);
+  rc = set_theta_natural(h, th.data(), th.data() + h->ns);
+  if (rc != GOGP_OK) return rc;
+  // the regression state goes, as with gogp_set_data; so does an earlier Laplace fit
+  h->factored = h->have_alpha = h->observed = h->with_obs = h->grad_valid = h->z_valid = false;
+  h->multi_solved = false;
+  h->lap_observed = h->lap_grad_valid = false;
+  h->lap_lik = lik;
+  h->lap_iters = 0;
+  if (h->n == 0) {
+    h->lap_observed = true;
+    if (lml) *lml = 0.0;
+    return GOGP_OK;
+  }
+  LapVecs v;
+  rc = lap_vecs(h, &v);
+  if (rc == GOGP_OK) rc = gogp_upload_params(h);  // the products with K come before the first factorisation's own upload
+  if (rc != GOGP_OK) return rc;
+  const bool warm = h->lap_warm && h->lap_warm_valid && h->lap_warm_lik == lik && h->lap_warm_n == h->n;
+  bool conv = false;
+  double psi = NAN;
+  rc = lap_newton(h, v, lik, warm, &conv, &psi);
+  // a warm start that went nowhere (theta moved far): once more from a = 0
+  if (warm && !conv && (rc == GOGP_OK || rc == GOGP_ECOND)) rc = lap_newton(h, v, lik, false, &conv, &psi);
+  if (rc != GOGP_OK && rc != GOGP_ECOND) return rc;
+  const double z = psi - 0.5 * h->logdet2;
+  h->lml = z;
+  h->lap_observed = true;
+  if (conv) {
+    HIPCHK(h, hipMemcpyAsync(v.awarm, v.a, (size_t)h->npad * sizeof(double), hipMemcpyDeviceToDevice, h->s));
+    HIPCHK(h, hipStreamSynchronize(h->s));
+    h->lap_warm_valid = true;
+    h->lap_warm_lik = lik;
+    h->lap_warm_n = h->n;
+  }
+  if (lml) *lml = z;
+  if (rc == GOGP_ECOND) return rc;
+  if (!conv) return fail(h, GOGP_ENOCONV, "laplace_observe: Newton did not reach the tolerance");
+  return GOGP_OK;
+}
+
+extern "C" int gogp_laplace_gradient(gogp_handle *h, double *grad, int64_t len) {
+  if (!h || !grad) return fail(h, GOGP_EARG, "laplace_gradient: NULL");
+  if (len != h->P) return fail(h, GOGP_EARG, "laplace_gradient: wrong length");
+  int rc = lap_refuse(h, "laplace_gradient");
+  if (rc != GOGP_OK) return rc;
+  if (!h->lap_observed) return fail(h, GOGP_ESTATE, "laplace_gradient before laplace_observe");
+  for (int64_t i = 0; i < len; ++i) grad[i] = 0.0;
+  if (h->n == 0) return GOGP_OK;
+  if (!h->lap_grad_valid) {
+    HIPCHK(h, hipSetDevice(h->device));
+    LapVecs v;
+    rc = lap_vecs(h, &v);
+    if (rc == GOGP_OK) rc = compute_kinv(h);  // B^-1 = Y Y^T into bufA, as after an Absorb
+    if (rc != GOGP_OK) return rc;
+    hipStream_t s = h->s;
+    const int64_t n = h->n, npad = h->npad, ld = npad;
+    // s from the diagonal; u = s - sw o (B^-1 (sw o (K s))) -- the symmetric product's slot sums go through Y, which is
+    // done with once B^-1 exists
+    launch_lap_weight_vectors(s, h->bufA, ld, v.rho, n, npad, v.sv);
+    lap_kmatvec(h, v, v.sv, v.kv);
+    launch_lap_vec(s, nullptr, v.sw, v.kv, n, npad, v.rhs);
+    launch_lap_symv_u(s, h->bufA, ld, n, npad, v.rhs, v.sv, v.sw, h->bufY, v.u);
+    h->trtri_done = h->ydone_valid = false;
+    // G over B^-1, in place, then the LML gradient's reduction with a^ for alpha and G for K^-1
+    launch_lap_weight(s, h->bufA, ld, n, npad, v.sw, v.u, v.a);
+    h->have_kinv = false;
+    {
+      AuxTimer tm(h, GOGP_PROF_GRAD, s);
+      launch_grad_reduce(s, h->devP, h->D, h->ard_dims, h->dX, v.a, (const double *)h->bufA, ld, n, npad, h->gpart, h->gout,
+                         h->radial1, h->ard_mfma_min, h->ev());
+    }
+    double acc[NACC];
+    HIPCHK(h, hipMemcpyAsync(acc, h->gout, sizeof acc, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    HIPCHK(h, hipGetLastError());
+    h->lap_grad.assign(h->P, 0.0);
+    assemble_gradient(h, acc, h->hostP->dnoise, h->lap_grad.data());
+    h->lap_grad_valid = true;
+  }
+  for (int i = 0; i < h->P; ++i) grad[i] = h->lap_grad[i];
+  return GOGP_OK;
+}
+
+extern "C" int gogp_laplace_get_mode(gogp_handle *h, double *f, double *a, int32_t *iterations) {
+  if (!h) return GOGP_EARG;
+  if (!h->lap_observed) return fail(h, GOGP_ESTATE, "laplace_get_mode before laplace_observe");
+  if (iterations) *iterations = h->lap_iters;
+  if (h->n == 0 || (!f && !a)) return GOGP_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  LapVecs v;
+  const int rc = lap_vecs(h, &v);
+  if (rc != GOGP_OK) return rc;
+  const size_t bytes = (size_t)h->n * sizeof(double);
+  if (f) HIPCHK(h, hipMemcpyAsync(f, v.f, bytes, hipMemcpyDeviceToHost, h->s));
+  if (a) HIPCHK(h, hipMemcpyAsync(a, v.a, bytes, hipMemcpyDeviceToHost, h->s));
+  HIPCHK(h, hipStreamSynchronize(h->s));
+  return GOGP_OK;
+}
+
+extern "C" int gogp_laplace_produce(gogp_handle *h, const double *Z, int64_t m, double *mu, double *sigma, double *mean) {
+  if (!h || m < 0 || (m > 0 && (!Z || !mu || !sigma))) return fail(h, GOGP_EARG, "laplace_produce: NULL");
+  int rc = lap_refuse(h, "laplace_produce");
+  if (rc != GOGP_OK) return rc;
+  if (!h->lap_observed) return fail(h, GOGP_ESTATE, "laplace_produce before laplace_observe");
+  if (m == 0) return GOGP_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  const int64_t mpad = ((m + TILE - 1) / TILE) * TILE;
+  rc = ensure_m(h, m, mpad);
+  if (rc != GOGP_OK) return rc;
+  const ProducePlan pp{mpad, h->pvec, h->pvec + mpad, h->pvec + 2 * mpad, h->pvec + 3 * mpad};
+  hipStream_t s = h->s;
+  if (h->n == 0) {
+    rc = gogp_upload_params(h);
+    if (rc != GOGP_OK) return rc;
+  }
+  HIPCHK(h, hipMemcpyAsync(h->dZ, Z, (size_t)m * h->D * sizeof(double), hipMemcpyHostToDevice, s));
+  launch_prior(s, h->devP, h->dZ, m, pp.prior);
+  if (h->n == 0) {
+    launch_sigma(s, pp.prior, nullptr, m, pp.sigma);
+    HIPCHK(h, hipMemsetAsync(pp.mu, 0, (size_t)m * sizeof(double), s));
+  } else {
+    LapVecs v;
+    rc = lap_vecs(h, &v);
+    if (rc != GOGP_OK) return rc;
+    // the tile route for every m: the mean from the unscaled cross-covariance, its columns scaled by sw ahead of the
+    // forward substitution with B's factor
+    produce_cross_t<double>(h, s, m, mpad);
+    launch_rownorm_dot(s, (const double *)h->KsT, h->npad, v.a, h->npad, m, pp.mu, nullptr);
+    launch_lap_colscale(s, h->KsT, h->npad, mpad, h->npad, v.sw);
+    produce_substitute_t<double>(h, s, m, mpad, pp.q);
+    launch_sigma(s, pp.prior, pp.q, m, pp.sigma);
+  }
+  const size_t bytes = (size_t)m * sizeof(double);
+  if (mean) {
+    launch_lap_mean(s, h->lap_lik, pp.mu, pp.sigma, m, pp.q);  // (q is done with)
+    HIPCHK(h, hipMemcpyAsync(mean, pp.q, bytes, hipMemcpyDeviceToHost, s));
+  }
+  HIPCHK(h, hipMemcpyAsync(mu, pp.mu, bytes, hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipMemcpyAsync(sigma, pp.sigma, bytes, hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipStreamSynchronize(s));
+  HIPCHK(h, hipGetLastError());
+  return GOGP_OK;
+}
+
 // ---- cached state --------------------------------------------------------------------------------
 extern "C" int gogp_get_alpha(gogp_handle *h, double *alpha) {
   if (!h || (h->n > 0 && !alpha)) return GOGP_EARG;
@@ -3809,6 +4137,7 @@ extern "C" int gogp_set_factor(gogp_handle *h, const double *theta_simil,
   h->z_valid = false;     // no z = L^-1 y comes with a restored factor (gogp_append recomputes it)
   h->kinv_c1 = 0;         // ... and no partial K^-1 of an earlier sweep belongs to it (compute_kinv: gogp_loo)
   h->multi_solved = false;  // ... nor do the solutions of gogp_multi_*
+  h->lap_observed = h->lap_grad_valid = false;  // ... nor does a Laplace fit, whose factor this one replaces
   if (h->n == 0) return GOGP_OK;
   if (h->dist) return gogp_dist_set_factor(h, Lin, alpha);  // collective: every rank keeps its own tiles
   rc = gogp_upload_params(h);
@@ -3883,6 +4212,7 @@ static int begin_factor_update(gogp_handle *h) {
   h->kinv_c1 = 0;
   h->multi_T = 0;  // the outputs of gogp_multi_set_outputs belong to the rows as they were
   h->multi_solved = false;
+  h->lap_observed = h->lap_grad_valid = h->lap_warm_valid = false;  // a Laplace fit (and its warm start) belongs to the rows as they were
   return GOGP_OK;
 }
 // ... and end with, on the main stream s behind z of the n1 rows: alpha = L^-T z over the whole new factor L (leading
@@ -4377,6 +4707,7 @@ extern "C" int gogp_set_option(gogp_handle *h, const char *name, int64_t value) 
       free_cand_buffers(h);  // the candidates' arena slots are laid out for the matrices' element type
       h->prec = (int)value;
       h->have_data = h->factored = h->have_alpha = h->have_kinv = h->observed = h->grad_valid = false;
+      h->lap_observed = h->lap_grad_valid = h->lap_warm_valid = false;  // (free_n_buffers dropped the Laplace fit too)
       h->multi_T = 0;  // (free_n_buffers dropped the outputs of gogp_multi_set_outputs; said here too)
       h->multi_solved = false;
       h->trtri_done = h->trtri_pending = h->alpha_pending = h->kinv_pending = false;
@@ -4462,6 +4793,21 @@ extern "C" int gogp_set_option(gogp_handle *h, const char *name, int64_t value) 
   if (strcmp(name, "sparse_chunk") == 0) {  // gogp_sparse_*: rows of X per pass
     if (value < 256 || value > 65536 || value % 256) return fail(h, GOGP_EARG, "sparse_chunk must be a multiple of 256 in 256..65536");
     h->sp_chunk = value;
+    return GOGP_OK;
+  }
+  if (strcmp(name, "laplace_max_iter") == 0) {  // gogp_laplace_observe: Newton steps at the most
+    if (value < 1 || value > 200) return fail(h, GOGP_EARG, "laplace_max_iter must be 1..200");
+    h->lap_max_iter = (int)value;
+    return GOGP_OK;
+  }
+  if (strcmp(name, "laplace_tol_log10") == 0) {  // ... its stationarity tolerance 10^value
+    if (value < -14 || value > -4) return fail(h, GOGP_EARG, "laplace_tol_log10 must be -14..-4");
+    h->lap_tol_log10 = (int)value;
+    return GOGP_OK;
+  }
+  if (strcmp(name, "laplace_warm") == 0) {  // ... 1: start from the last converged mode of the same data and likelihood
+    if (value < 0 || value > 1) return fail(h, GOGP_EARG, "laplace_warm must be 0 or 1");
+    h->lap_warm = (int)value;
     return GOGP_OK;
   }
   if (strcmp(name, "superpanel") == 0) {

@@ -516,6 +516,32 @@ void launch_sparse_multi_pad(hipStream_t s, const double *Y, int64_t ldy, int64_
                              double *Yp, int64_t ldp);
 void launch_sparse_multi_sigma(hipStream_t s, const double *A, const double *V, int64_t ld, int64_t ncols, int64_t m,
                                const double *prior, const double *q, double *sigma);
+// laplace.hip (gogp_laplace_*): the passes around the factorisation of B = I + diag(sw) K diag(sw).  Vectors hold npad
+// doubles (npad a multiple of 256) and leave every launcher zero from row n on.
+// launch_lap_site: g, W, sw = sqrt(W), b = W f + g, rho of the rows i < n; part: 5 * npad / 256 doubles of block results;
+// out[0 .. 4] = sum log p, sum a f, max |a - g|, max |a|, the first row whose y the likelihood refuses or -1.
+// launch_lap_scale_gram: A := diag(sw) A diag(sw) + I on the elements i, j < n of the lower 64-tiles, right behind
+// launch_gram_lower_split with the same streams and column split.  launch_lap_vec: out = q o r (p == nullptr) or
+// p - q o r.  launch_lap_interp: at = a + t (a1 - a), ft = f + t (f1 - f).  launch_lap_weight_vectors: sv_i = 1/2 (1 -
+// Binv_ii) rho_i.  launch_lap_symv_u: u = sv - sw o (Binv v) from the elements j <= i < n of Binv; upart: npad / 64 * npad
+// doubles of scratch.  launch_lap_weight: in place, G = diag(sw) Binv diag(sw) - u a^T - a u^T on j <= i < n, exact zeros
+// on the rest of the lower 64-tiles.  launch_lap_colscale: KsT (rows x ld) := KsT diag(sw).  launch_lap_mean: the
+// response-scale prediction from the latent mu and sigma.
+void launch_lap_site(hipStream_t s, int lik, const double *f, const double *y, const double *a, int64_t n, int64_t npad,
+                     double *g, double *W, double *sw, double *b, double *rho, double *part, double *out);
+void launch_lap_scale_gram(hipStream_t s_first, hipStream_t s_rest, double *A, int64_t ld, int64_t n, int64_t npad,
+                           const double *sw, int64_t wcols);
+void launch_lap_vec(hipStream_t s, const double *p, const double *q, const double *r, int64_t n, int64_t npad, double *out);
+void launch_lap_interp(hipStream_t s, const double *a, const double *a1, const double *f, const double *f1, double t,
+                       int64_t n, int64_t npad, double *at, double *ft);
+void launch_lap_weight_vectors(hipStream_t s, const double *Binv, int64_t ld, const double *rho, int64_t n, int64_t npad,
+                               double *sv);
+void launch_lap_symv_u(hipStream_t s, const double *Binv, int64_t ld, int64_t n, int64_t npad, const double *v,
+                       const double *sv, const double *sw, double *upart, double *u);
+void launch_lap_weight(hipStream_t s, double *G, int64_t ld, int64_t n, int64_t npad, const double *sw, const double *u,
+                       const double *a);
+void launch_lap_colscale(hipStream_t s, double *KsT, int64_t ld, int64_t rows, int64_t npad, const double *sw);
+void launch_lap_mean(hipStream_t s, int lik, const double *mu, const double *sigma, int64_t m, double *mean);
 void launch_fill(hipStream_t s, double *p, int64_t count, double v);
 void launch_axpy(hipStream_t s, double *a, const double *b, int64_t count);  // a += b
 void launch_dot(hipStream_t s, const double *a, const double *b, int64_t n, double *out);  // out[0] = a.b

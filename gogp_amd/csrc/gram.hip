@@ -391,6 +391,17 @@ void launch_kmatvec_share(hipStream_t s, const DevParams *p, int ndim, const dou
   const int t0 = std::min(ntile, part_idx * per), t1 = std::min(ntile, (part_idx + 1) * per);
   const int tps = std::max(1, (t1 - t0 + nslab - 1) / nslab);
   const size_t lds = (size_t)(128 * ndim + 64 + 256) * sizeof(double);
+  // 63 dimensions and up need more than 64 KB: said to the runtime, per launch (grad.hip: gr_launch).  Before, such a
+  // launch -- the sharded fp32 refinement at D >= 63, this function's only other caller -- was left to what the runtime
+  // tolerates.  Should the attribute be refused, the launch below fails and the caller's hipGetLastError reports it.
+  if (lds + 64 * 8 > 64 * 1024) {
+    const int cap = (int)((128 * GOGP_MAX_NDIM + 64 + 256 + 64) * sizeof(double));
+    const void *fn = ev ? (radial1 ? reinterpret_cast<const void *>(&kmatvec_kernel_ev<true>)
+                                   : reinterpret_cast<const void *>(&kmatvec_kernel_ev<false>))
+                        : (radial1 ? reinterpret_cast<const void *>(&kmatvec_kernel<true>)
+                                   : reinterpret_cast<const void *>(&kmatvec_kernel<false>));
+    (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, cap);
+  }
   if (ev && radial1)
     GOGP_KLAUNCH((kmatvec_kernel_ev<true>), dim3((unsigned)ntile, (unsigned)nslab), dim3(256), lds + 64 * 8, s, p, X,
                  (long)n, v, (long)npad, tps, part, t0, t1);

@@ -251,6 +251,20 @@ struct gogp_handle : EvalBufs, EvalState {
   Workspace sp_mws;                // state of the multi observe, sized by gogp_sparse_multi_set_outputs (api.hip: SparseMultiBufs)
   Workspace sp_mscr;               // scratch sized by the chunk: the partials of launch_sparse_xty, the padded chunk of Y
   Workspace sp_mmu;                // gogp_sparse_multi_produce: mpad x 128 means
+  // the Laplace approximation (gogp_laplace_*, laplace.hip; api.hip: LapVecs).  B's factor lies in bufL / Dinv, B^-1 and
+  // then the gradient's weight matrix in bufA; only vectors are its own (released with the N buffers).
+  Workspace lap_ws;
+  bool lap_observed = false;     // a Laplace observe's factor, mode and site vectors are in place (also with n == 0)
+  bool lap_grad_valid = false;   // lap_grad belongs to them (bufA then holds the weight matrix, not B^-1)
+  std::vector<double> lap_grad;
+  int lap_lik = 0, lap_iters = 0;
+  int lap_max_iter = 50, lap_tol_log10 = -10, lap_warm = 0;  // options "laplace_max_iter", "laplace_tol_log10", "laplace_warm"
+  bool lap_warm_valid = false;   // the workspace holds a converged a^ of lap_warm_lik for the current data (lap_warm_n rows)
+  int lap_warm_lik = 0;
+  int64_t lap_warm_n = 0;
+  // set only while a Laplace observe factors (api.hip: Sweep::build_gram, factorize_t): the Gram stage scales K into
+  // B = I + diag(lap_sw) K diag(lap_sw) and the forward substitution's working copy comes from lap_rhs instead of dy
+  const double *lap_sw = nullptr, *lap_rhs = nullptr;
   double yta = 0.0;      // y^T alpha of the last factorisation (fp32 path: of the refined alpha)
   int trace_fp64 = 1;    // fp32 path: tr(alpha alpha^T - K^-1) summed in fp64 from Y, scale component by its identity
   double cond_limit = 1e16;  // gonum's mat.ConditionTolerance

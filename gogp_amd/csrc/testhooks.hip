@@ -1856,3 +1856,100 @@ extern "C" int gogp_bench_sparse_syrk(int device, int64_t rows, int64_t M, int r
   if (tflops) *tflops = flops / (ms * 1e-3) / 1e12;
   return GOGP_OK;
 }
+
+// ---- the kernels of the Laplace approximation (laplace.hip; tests/test_laplace_kernels.py) --------------------------------
+// The rules of the finishing hooks above: every argument is checked before the device is touched, every array goes to
+// the device whole and every in / out array comes back whole.
+namespace {
+bool lap_lik_known(int lik) { return lik == GOGP_LIK_BERNOULLI_LOGIT || lik == GOGP_LIK_POISSON_LOG; }
+}  // namespace
+
+extern "C" int gogp_test_lap_site(int device, int lik, const double *f, int64_t f_len, const double *y, int64_t y_len,
+                                  const double *a, int64_t a_len, int64_t n, int64_t npad, double *g, int64_t g_len,
+                                  double *W, int64_t w_len, double *sw, int64_t sw_len, double *b, int64_t b_len, double *rho,
+                                  int64_t rho_len, double *part, int64_t part_len, double *out, int64_t out_len) {
+  const std::initializer_list<FinArr> arrs = {{f, f_len, false},  {y, y_len, false}, {a, a_len, false},  {g, g_len, true},
+                                              {W, w_len, true},   {sw, sw_len, true}, {b, b_len, true},  {rho, rho_len, true},
+                                              {part, part_len, true}, {out, out_len, true}};
+  if (!fin_have(arrs) || !fin_npad_ok(n, npad) || !lap_lik_known(lik)) return GOGP_EARG;
+  if (f_len < n || y_len < n || a_len < n) return GOGP_EARG;
+  if (g_len < npad || w_len < npad || sw_len < npad || b_len < npad || rho_len < npad) return GOGP_EARG;
+  if (part_len < 5 * (npad / PANEL) || out_len < 5) return GOGP_EARG;
+  return fin_run(device, arrs, [&](double **d) {
+    launch_lap_site(0, lik, d[0], d[1], d[2], n, npad, d[3], d[4], d[5], d[6], d[7], d[8], d[9]);
+  });
+}
+
+extern "C" int gogp_test_lap_scale_gram(int device, double *A, int64_t a_len, int64_t ld, int64_t n, int64_t npad,
+                                        const double *sw, int64_t sw_len, int64_t wcols) {
+  const std::initializer_list<FinArr> arrs = {{A, a_len, true}, {sw, sw_len, false}};
+  if (!fin_have(arrs) || !fin_npad_ok(n, npad) || !covers(a_len, 0, ld, npad, npad, 1, 0)) return GOGP_EARG;
+  if (sw_len < n || wcols < 0 || wcols % 64) return GOGP_EARG;
+  return fin_run(device, arrs, [&](double **d) { launch_lap_scale_gram(0, 0, d[0], ld, n, npad, d[1], wcols); });
+}
+
+extern "C" int gogp_test_lap_step(int device, const double *b, int64_t b_len, const double *sw, int64_t sw_len,
+                                  const double *beta, int64_t beta_len, int64_t n, int64_t npad, double *rhs, int64_t rhs_len,
+                                  double *a1, int64_t a1_len) {
+  const std::initializer_list<FinArr> arrs = {{b, b_len, false}, {sw, sw_len, false}, {beta, beta_len, false},
+                                              {rhs, rhs_len, true}, {a1, a1_len, true}};
+  if (!fin_have(arrs) || !fin_npad_ok(n, npad)) return GOGP_EARG;
+  if (b_len < n || sw_len < n || beta_len < n || rhs_len < npad || a1_len < npad) return GOGP_EARG;
+  return fin_run(device, arrs, [&](double **d) {
+    launch_lap_vec(0, nullptr, d[1], d[2], n, npad, d[3]);  // rhs = sw o beta
+    launch_lap_vec(0, d[0], d[1], d[2], n, npad, d[4]);     // a1 = b - sw o beta
+  });
+}
+
+extern "C" int gogp_test_lap_interp(int device, const double *a, int64_t a_len, const double *a1, int64_t a1_len,
+                                    const double *f, int64_t f_len, const double *f1, int64_t f1_len, double t, int64_t n,
+                                    int64_t npad, double *at, int64_t at_len, double *ft, int64_t ft_len) {
+  const std::initializer_list<FinArr> arrs = {{a, a_len, false}, {a1, a1_len, false}, {f, f_len, false},
+                                              {f1, f1_len, false}, {at, at_len, true}, {ft, ft_len, true}};
+  if (!fin_have(arrs) || !fin_npad_ok(n, npad) || !std::isfinite(t)) return GOGP_EARG;
+  if (a_len < n || a1_len < n || f_len < n || f1_len < n || at_len < npad || ft_len < npad) return GOGP_EARG;
+  return fin_run(device, arrs, [&](double **d) { launch_lap_interp(0, d[0], d[1], d[2], d[3], t, n, npad, d[4], d[5]); });
+}
+
+extern "C" int gogp_test_lap_weight_vectors(int device, const double *Binv, int64_t binv_len, int64_t ld, const double *rho,
+                                            int64_t rho_len, int64_t n, int64_t npad, double *sv, int64_t sv_len) {
+  const std::initializer_list<FinArr> arrs = {{Binv, binv_len, false}, {rho, rho_len, false}, {sv, sv_len, true}};
+  if (!fin_have(arrs) || !fin_npad_ok(n, npad) || !covers(binv_len, 0, ld, npad, npad, 1, 0)) return GOGP_EARG;
+  if (rho_len < n || sv_len < npad) return GOGP_EARG;
+  return fin_run(device, arrs, [&](double **d) { launch_lap_weight_vectors(0, d[0], ld, d[1], n, npad, d[2]); });
+}
+
+extern "C" int gogp_test_lap_symv_u(int device, const double *Binv, int64_t binv_len, int64_t ld, int64_t n, int64_t npad,
+                                    const double *v, int64_t v_len, const double *sv, int64_t sv_len, const double *sw,
+                                    int64_t sw_len, double *upart, int64_t upart_len, double *u, int64_t u_len) {
+  const std::initializer_list<FinArr> arrs = {{Binv, binv_len, false}, {v, v_len, false},       {sv, sv_len, false},
+                                              {sw, sw_len, false},     {upart, upart_len, true}, {u, u_len, true}};
+  if (!fin_have(arrs) || !fin_npad_ok(n, npad) || !covers(binv_len, 0, ld, npad, npad, 1, 0)) return GOGP_EARG;
+  if (v_len < npad || sv_len < n || sw_len < n || u_len < npad || upart_len < npad / 64 * npad) return GOGP_EARG;
+  return fin_run(device, arrs, [&](double **d) { launch_lap_symv_u(0, d[0], ld, n, npad, d[1], d[2], d[3], d[4], d[5]); });
+}
+
+extern "C" int gogp_test_lap_weight(int device, double *G, int64_t g_len, int64_t ld, int64_t n, int64_t npad,
+                                    const double *sw, int64_t sw_len, const double *u, int64_t u_len, const double *a,
+                                    int64_t a_len) {
+  const std::initializer_list<FinArr> arrs = {{G, g_len, true}, {sw, sw_len, false}, {u, u_len, false}, {a, a_len, false}};
+  if (!fin_have(arrs) || !fin_npad_ok(n, npad) || !covers(g_len, 0, ld, npad, npad, 1, 0)) return GOGP_EARG;
+  if (sw_len < n || u_len < n || a_len < n) return GOGP_EARG;
+  return fin_run(device, arrs, [&](double **d) { launch_lap_weight(0, d[0], ld, n, npad, d[1], d[2], d[3]); });
+}
+
+extern "C" int gogp_test_lap_colscale(int device, double *KsT, int64_t k_len, int64_t ld, int64_t rows, int64_t npad,
+                                      const double *sw, int64_t sw_len) {
+  const std::initializer_list<FinArr> arrs = {{KsT, k_len, true}, {sw, sw_len, false}};
+  if (!fin_have(arrs) || npad <= 0 || npad % PANEL || npad > UP_NPAD_MAX || rows < 1 || rows > FIN_M_MAX) return GOGP_EARG;
+  if (!covers(k_len, 0, ld, rows, npad, 1, 0) || sw_len < npad) return GOGP_EARG;
+  return fin_run(device, arrs, [&](double **d) { launch_lap_colscale(0, d[0], ld, rows, npad, d[1]); });
+}
+
+extern "C" int gogp_test_lap_mean(int device, int lik, const double *mu, int64_t mu_len, const double *sigma,
+                                  int64_t sigma_len, int64_t m, double *mean, int64_t mean_len) {
+  const std::initializer_list<FinArr> arrs = {{mu, mu_len, false}, {sigma, sigma_len, false}, {mean, mean_len, true}};
+  if (!fin_have(arrs) || !lap_lik_known(lik) || m < 1 || m > FIN_M_MAX) return GOGP_EARG;
+  if (mu_len < m || sigma_len < m || mean_len < m) return GOGP_EARG;
+  return fin_run(device, arrs, [&](double **d) { launch_lap_mean(0, lik, d[0], d[1], m, d[2]); });
+}

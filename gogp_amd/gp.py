@@ -48,6 +48,28 @@ class ConditionError(GogpError):
         super().__init__(_lib.GOGP_ECOND, msg)
 
 
+class ConvergenceError(GogpError):
+    """gogp_laplace_observe: Newton's iteration for the mode of the Laplace approximation did not reach the tolerance
+    (GOGP_ENOCONV).  The last iterate was stored before the error was reported, as with ConditionError: ``lml`` is its
+    approximate log marginal likelihood, and LaplaceGradient / LaplaceMode / LaplaceProduce work on it."""
+
+    def __init__(self, msg: str, lml: float = float("nan")):
+        super().__init__(_lib.GOGP_ENOCONV, msg)
+        self.lml = lml
+
+
+#: the likelihoods of GP.LaplaceObserve, by name (enum gogp_lik_kind)
+LIKELIHOODS = {"bernoulli": _lib.GOGP_LIK_BERNOULLI_LOGIT, "poisson": _lib.GOGP_LIK_POISSON_LOG}
+
+
+def _lik(lik) -> int:
+    if isinstance(lik, str):
+        if lik not in LIKELIHOODS:
+            raise ValueError("lik: one of %s" % ", ".join(sorted(LIKELIHOODS)))
+        return LIKELIHOODS[lik]
+    return int(lik)
+
+
 def _dp(a: Optional[np.ndarray]):
     if a is None:
         return None
@@ -403,6 +425,56 @@ class GP:
         g = np.zeros(self._ns + self._nn)
         self._check(_lib.lib().gogp_loo_gradient(self._h, _dp(g), g.size))
         return g
+
+    # ---- non-Gaussian likelihoods by the Laplace approximation (no reference counterpart) ----
+    def LaplaceObserve(self, x, lik) -> float:
+        """The approximate log marginal likelihood of Y under the likelihood ``lik`` -- "bernoulli" (logit link, Y in
+        {0, 1}) or "poisson" (log link, counts) -- at x = log theta, by the Laplace approximation around the mode that a
+        damped Newton iteration finds (gogp_laplace_observe; Rasmussen & Williams 3.4).  The noise parameter keeps its
+        slot: it is the latent nugget.  Drops the regression state (Gradient, Produce, LOO ... need a new Absorb /
+        Observe).  Raises ConvergenceError where Newton does not reach the tolerance (the last iterate is stored) and
+        ConditionError as Observe does.  fp64, unsharded handles only."""
+        xa = _arr(x).reshape(-1)
+        if xa.size != self._ns + self._nn:
+            raise ValueError("len(x): the Laplace objective takes the hyperparameters only")
+        self._push_data()
+        self._with_obs = False
+        z = ctypes.c_double(0.0)
+        rc = _lib.lib().gogp_laplace_observe(self._h, _lik(lik), _dp(xa), xa.size, ctypes.byref(z))
+        if rc in (_lib.GOGP_OK, _lib.GOGP_ECOND, _lib.GOGP_ENOCONV):  # stored (and, but for GOGP_OK, reported)
+            theta = np.exp(xa)
+            self.ThetaSimil = list(theta[:self._ns])
+            self.ThetaNoise = list(theta[self._ns:])
+        if rc == _lib.GOGP_ENOCONV:
+            raise ConvergenceError(_lib.lib().gogp_last_error(self._h).decode(), z.value)
+        self._check(rc)
+        return z.value
+
+    def LaplaceGradient(self) -> np.ndarray:
+        """d LaplaceObserve / d log theta, one entry per hyperparameter, the movement of the mode included
+        (gogp_laplace_gradient)."""
+        g = np.zeros(self._ns + self._nn)
+        self._check(_lib.lib().gogp_laplace_gradient(self._h, _dp(g), g.size))
+        return g
+
+    def LaplaceMode(self):
+        """(f, a, iterations) of the last LaplaceObserve: the latent values at the mode, a = K^-1 f, and the Newton
+        steps taken (gogp_laplace_get_mode)."""
+        n = int(_lib.lib().gogp_n(self._h))
+        f, a, it = np.zeros(n), np.zeros(n), ctypes.c_int32(0)
+        self._check(_lib.lib().gogp_laplace_get_mode(self._h, _dp(f), _dp(a), ctypes.byref(it)))
+        return f, a, int(it.value)
+
+    def LaplaceProduce(self, Z, mean: bool = True):
+        """(mu, sigma, mean) at the test points Z after a LaplaceObserve: the latent mean and standard deviation (no
+        noise, as Produce) and the response-scale prediction -- E[y*] for "poisson", P(y* = 1) for "bernoulli"; None
+        with ``mean=False`` (gogp_laplace_produce)."""
+        za = _arr(Z).reshape(-1, self.NDim)
+        m = za.shape[0]
+        mu, sigma = np.zeros(m), np.zeros(m)
+        mn = np.zeros(m) if mean else None
+        self._check(_lib.lib().gogp_laplace_produce(self._h, _dp(za), m, _dp(mu), _dp(sigma), _dp(mn)))
+        return mu, sigma, mn
 
     # ---- leave-block-out cross-validation (no reference counterpart) ----
     def BlockCV(self, start):
@@ -914,6 +986,34 @@ class LOOModel:
 
     def Gradient(self) -> np.ndarray:
         g = self.gp.LOOGradient()
+        if self.Priors is not None:
+            self.Priors.Observe(self._x)
+            pg = np.asarray(self.Priors.Gradient(), dtype=float)
+            g[:len(pg)] += pg
+        return g
+
+
+class LaplaceModel:
+    """Model with the Laplace approximation's log marginal likelihood under the likelihood ``lik`` ("bernoulli" /
+    "poisson") in the place of the LML: Observe(x) returns GP.LaplaceObserve(x, lik) (+ the log prior), Gradient()
+    GP.LaplaceGradient() (+ the prior's).  optimize.lbfgs and optimize.Adam.Step then fit x = log theta.  Sets the
+    option "laplace_warm": every evaluation starts Newton's iteration from the previous mode.  As with LOOModel the
+    batched line search is not offered: the GP is ``gp`` here, not ``GP``."""
+
+    def __init__(self, gp: GP, lik, Priors=None):
+        self.gp = gp
+        self.lik = _lik(lik)
+        self.Priors = Priors
+        self._x = None
+        gp.set_option("laplace_warm", 1)
+
+    def Observe(self, x) -> float:
+        self._x = _arr(x).reshape(-1).copy()
+        v = self.gp.LaplaceObserve(self._x, self.lik)
+        return v + self.Priors.Observe(self._x) if self.Priors is not None else v
+
+    def Gradient(self) -> np.ndarray:
+        g = self.gp.LaplaceGradient()
         if self.Priors is not None:
             self.Priors.Observe(self._x)
             pg = np.asarray(self.Priors.Gradient(), dtype=float)
@@ -1552,9 +1652,18 @@ def finish_check(which: str, device: int = -1, **args):
     """The test hook gogp_test_<which> of one of the launchers in _lib.FINISH_HOOKS, whose table names the arguments: flat
     float64 arrays (their lengths are passed along) and scalars, all by keyword.  Returns copies of the in / out arrays
     after the launch, in the order of the table (a single array if there is one)."""
-    spec = _lib.FINISH_HOOKS[which]
+    return _table_check(_lib.FINISH_HOOKS, which, device, args, "finish_check")
+
+
+def laplace_kernel_check(which: str, device: int = -1, **args):
+    """finish_check for the kernels of the Laplace approximation (_lib.LAPLACE_HOOKS)."""
+    return _table_check(_lib.LAPLACE_HOOKS, which, device, args, "laplace_kernel_check")
+
+
+def _table_check(table, which: str, device: int, args, caller: str):
+    spec = table[which]
     if set(args) != {name for name, _ in spec}:
-        raise TypeError("finish_check(%s): the arguments are %s" % (which, ", ".join(name for name, _ in spec)))
+        raise TypeError("%s(%s): the arguments are %s" % (caller, which, ", ".join(name for name, _ in spec)))
     call, outs = [device], []
     for name, kind in spec:
         v = args[name]

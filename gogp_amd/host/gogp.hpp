@@ -184,6 +184,48 @@ class GP {
     return g;
   }
 
+  // Non-Gaussian likelihoods by the Laplace approximation (gogp_laplace_*; no reference counterpart).  LaplaceObserve:
+  // the approximate log marginal likelihood of Y under `lik` (GOGP_LIK_BERNOULLI_LOGIT: Y in {0, 1};
+  // GOGP_LIK_POISSON_LOG: counts) at x = log theta, the mode found by a damped Newton iteration; drops the regression
+  // state.  Returns the status, as Absorb does (nothing is thrown here): GOGP_OK, GOGP_ECOND or GOGP_ENOCONV (Newton did
+  // not reach the tolerance) store the fit and *z -- GOGP_ENOCONV is reported exactly as GOGP_ECOND is -- anything else
+  // is a failure.
+  int LaplaceObserve(const std::vector<double> &x, int32_t lik, double *z) {
+    int rc = push();
+    if (rc != GOGP_OK) return rc;
+    rc = gogp_laplace_observe(h_, lik, x.data(), (int64_t)x.size(), z);
+    if (rc == GOGP_OK || rc == GOGP_ECOND || rc == GOGP_ENOCONV) {
+      for (size_t i = 0; i < ThetaSimil.size(); ++i) ThetaSimil[i] = std::exp(x[i]);
+      for (size_t i = 0; i < ThetaNoise.size(); ++i) ThetaNoise[i] = std::exp(x[ThetaSimil.size() + i]);
+    }
+    return rc;
+  }
+  // d LaplaceObserve / d log theta, the movement of the mode included (gogp_laplace_gradient)
+  std::vector<double> LaplaceGradient() {
+    std::vector<double> g(ThetaSimil.size() + ThetaNoise.size(), 0.0);
+    check(gogp_laplace_gradient(h_, g.data(), (int64_t)g.size()));
+    return g;
+  }
+  // the latent values f and a = K^-1 f at the mode; returns the Newton steps of the last LaplaceObserve
+  int LaplaceMode(std::vector<double> &f, std::vector<double> &a) {
+    const size_t n = (size_t)gogp_n(h_);
+    f.assign(n, 0.0);
+    a.assign(n, 0.0);
+    int32_t it = 0;
+    check(gogp_laplace_get_mode(h_, f.data(), a.data(), &it));
+    return (int)it;
+  }
+  // latent mu and sigma (no noise, as Produce) and the response-scale prediction at the test points: E[y*] (poisson),
+  // P(y* = 1) (bernoulli); throws on any status but GOGP_OK, as LaplaceGradient and LaplaceMode do
+  void LaplaceProduce(const std::vector<std::vector<double>> &x, std::vector<double> &mu, std::vector<double> &sigma,
+                      std::vector<double> &mean) {
+    std::vector<double> flat = pack(x);
+    mu.assign(x.size(), 0.0);
+    sigma.assign(x.size(), 0.0);
+    mean.assign(x.size(), 0.0);
+    check(gogp_laplace_produce(h_, flat.data(), (int64_t)x.size(), mu.data(), sigma.data(), mean.data()));
+  }
+
   // Leave-block-out cross-validation at the current parameters (gogp_blockcv): the rows are cut into the consecutive
   // blocks [start[f], start[f + 1]) -- start[0] = 0, start[F] = n, 1 .. GOGP_BLOCKCV_MAX rows each; blocks() builds equal
   // ones -- and every block is predicted jointly by the process fitted to all the other blocks.  mu, sigma: per row; logp:

@@ -40,6 +40,8 @@ extern "C" {
                          still stored (as in gonum, which fills the result and returns the
                          error); the host shim decides: Absorb returns it as an error,
                          Observe panics, exactly where the reference does.          */
+#define GOGP_ENOCONV 7 /* gogp_laplace_observe: Newton did not reach the tolerance; the last
+                         iterate's values are returned and stored                          */
 
 /* ---- kernel descriptors --------------------------------------------------
  * The reference accepts any Go value implementing
@@ -274,6 +276,56 @@ int gogp_blockcv_check(const int64_t *start, int64_t F, int64_t n);
 int gogp_blockcv_groups(const int64_t *start, int64_t F, int64_t *first, int64_t *ngroups);
 int gogp_blockcv(gogp_handle *h, const int64_t *start, int64_t F, double *mu, double *sigma, double *logp, double *total);
 int gogp_blockcv_gradient(gogp_handle *h, const int64_t *start, int64_t F, double *grad, int64_t len);
+
+/* Non-Gaussian likelihoods by the Laplace approximation (Rasmussen & Williams 3.4, 5.5.1); no reference counterpart.
+ * y is the handle's y (gogp_set_data), K the Gram matrix exactly as gogp_absorb builds it -- the similarity plus the
+ * noise variance on the diagonal, which acts as the latent nugget -- so every parameter keeps its slot and its
+ * derivative.  With pi = 1 / (1 + exp(-f)):
+ *     GOGP_LIK_BERNOULLI_LOGIT  log p(y|f) = y f - softplus(f)            y in {0, 1}
+ *     GOGP_LIK_POISSON_LOG      log p(y|f) = y f - exp(f) - lgamma(y + 1) y a non-negative integer
+ * gogp_laplace_observe: theta = exp(x) (`len` must be P), the mode f^ = K a^ of psi(a) = -1/2 a^T f + sum_i log p(y_i|f_i)
+ * by Newton's iteration (R&W Alg. 3.1) -- per step one factorisation of B = I + W^1/2 K W^1/2 (W = -d2 log p / df2), two
+ * substitutions and two products with K -- damped: the step is halved while psi does not increase beyond the rounding
+ * of its sums (1e-12 max(1, |psi|)), 20 times at the most.  Converged when |a - dlog p/df|_inf <= tol max(1, |a|_inf);
+ * B is then factored once more AT the mode, and *lml = Z = psi(a^) - sum_i log L_ii.
+ * gogp_laplace_gradient: dZ/dlog theta, P entries, implicit part (the mode moves with theta) included.  R&W eq. 5.23 and
+ * the s2 line of Alg. 5.1 carry a sign error; the sign here is the one a central difference of Z confirms.
+ * gogp_laplace_get_mode: f^ and a^ (n doubles each) and the Newton steps the last observe took; any may be NULL.
+ * gogp_laplace_produce: at the m test points Z the latent mean mu = k*^T a^ and standard deviation sigma, sigma^2 =
+ * k(z, z) - |L^-1 (W^1/2 k*)|^2 (no noise, not clamped: as gogp_produce), and -- `mean` may be NULL -- the response-scale
+ * prediction: Poisson E[y*] = exp(mu + sigma^2 / 2), Bernoulli P(y* = 1) = int pi(f) N(f | mu, sigma^2) df by a fixed
+ * 32-point Gauss-Hermite rule.
+ * gogp_laplace_check (host only): GOGP_OK when the likelihood accepts every y[i], else GOGP_EARG.
+ * Options (gogp_set_option): "laplace_max_iter" 1..200 (50), "laplace_tol_log10" -14..-4 (-10), "laplace_warm" 0 | 1 (0;
+ * 1: an observe starts from the last converged a^ of the same data and likelihood instead of a = 0).
+ * State: the calls work in the handle's own N-sized buffers -- B's factor lies where K's does, B^-1 and then the
+ * gradient's weight matrix where K^-1 does -- plus a few vectors.  A Laplace observe DROPS the regression state, as
+ * gogp_set_data does: gogp_gradient, gogp_produce, gogp_loo, gogp_append and the rest return GOGP_ESTATE until the next
+ * gogp_absorb / gogp_observe, which then return the bits a fresh handle returns.  Whatever factors or replaces the data
+ * (set_data, absorb, observe, append, remove, set_factor, set_events) and the options that resize buffers drop the
+ * Laplace state.  Sparse data, batch data, the candidates arena and the multi-output Y are untouched.  Two identical
+ * call sequences return identical bits; with "laplace_warm" = 0 an observe does not depend on earlier Laplace calls.
+ * GOGP_EARG: NULL, len != P, an unknown lik, a non-finite parameter, a y the likelihood refuses (found on the device),
+ * precision = 32, gradient_precision = 32, a sharded handle.  GOGP_ESTATE: no data; gradient, mode or produce before a
+ * Laplace observe.  GOGP_ENOTPD: a pivot of B failed (B >= I cannot fail in exact arithmetic), *lml = NaN.  GOGP_ECOND:
+ * as gogp_absorb, on B's factor.  GOGP_ENOCONV: "laplace_max_iter" steps or 20 halvings without convergence; *lml is
+ * the last iterate's, and gradient and produce work on it.  n == 0: *lml = 0, a zero gradient, mu = 0, sigma =
+ * sqrt(prior), mean = the likelihood's mean at that prior.
+ * Out of scope: other likelihoods, multi-class, EP / variational inference, the sparse, batch, candidates, fp32 and
+ * sharded paths, the full Observe form, Append / Remove on a Laplace fit.
+ * Device memory: 24 vectors of npad doubles and a few block results; no matrix beyond the handle's own.
+ * Cost, measured on one MI355X (profiles/laplace.txt; D = 8, n = 1024 / 4096 / 16384, wall time with the synchronise): one
+ * Newton iteration, everything included (a cold observe over its factorisations of B), 0.70 / 2.8 / 31.9 ms against 0.64 /
+ * 2.9 / 30.6 ms for gogp_absorb (1.10 / 0.97 / 1.04 of it); an observe of s Newton steps factors s + 1 times: from a = 0, s = 4 - 5 (Bernoulli) 3.5 / 16.9 / 192 ms, s = 8 - 9 (Poisson) 6.3 /
+ * 25.8 / 320 ms; warm at the same theta 0.69 / 3.0 / 31.9 ms; gogp_laplace_gradient 0.36 / 1.86 / 49.7 ms (the lazy inverse
+ * and three passes over B^-1); gogp_laplace_produce of 1024 points 0.21 / 0.67 / 5.7 ms against 0.18 / 0.63 / 5.2 ms for
+ * gogp_produce, of one point 0.13 / 0.38 / 2.04 ms against 0.09 / 0.15 / 0.43 ms (the tile route for every m). */
+enum gogp_lik_kind { GOGP_LIK_BERNOULLI_LOGIT = 0, GOGP_LIK_POISSON_LOG = 1 };
+int gogp_laplace_check(int32_t lik, const double *y, int64_t n);
+int gogp_laplace_observe(gogp_handle *h, int32_t lik, const double *x, int64_t len, double *lml);
+int gogp_laplace_gradient(gogp_handle *h, double *grad, int64_t len);
+int gogp_laplace_get_mode(gogp_handle *h, double *f, double *a, int32_t *iterations);
+int gogp_laplace_produce(gogp_handle *h, const double *Z, int64_t m, double *mu, double *sigma, double *mean);
 
 /* Multi-output: T output columns Y = [y_1 .. y_T] observed at the handle's inputs, sharing its kernel and
  * hyperparameters, on ONE factorisation; no reference counterpart (gp.GP holds one output vector).  The columns are
@@ -731,6 +783,10 @@ int gogp_profile_read_aux(gogp_handle *h, int cls, double *ms, int64_t *launches
  *                          the exact (fp64, recomputed) Gram matrix                    (default 1)
  *   "cond_limit_log10" 1..300  GOGP_ECOND threshold 10^value -- gonum's package variable
  *                          mat.ConditionTolerance                                   (default 16)
+ *   "laplace_max_iter" 1..200   gogp_laplace_observe: Newton steps at the most                (default 50)
+ *   "laplace_tol_log10" -14..-4 ... its stationarity tolerance 10^value                     (default -10)
+ *   "laplace_warm" 0 | 1        ... 1: start from the last converged mode of the same data and likelihood
+ *                          instead of a = 0 (back to a = 0 where that start does not converge)  (default 0)
  *   "superpanel_head" -1..8, "head_remaining" >= 0   wider super-panels while more than head_remaining
  *                          panels are still to come (the chain has slack there; bulk updates with a longer
  *                          K are more efficient); 0 switches it off; -1: 3, on the fp32 path 4

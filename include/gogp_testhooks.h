@@ -420,6 +420,41 @@ int gogp_test_panel128_slabs(int device, const double *A, double *Lout, int64_t 
  * real shape, so the wall time of Observe + Gradient is the rank's compute time; the values returned mean nothing. */
 int gogp_test_dist_init_replay(void *h, int rank, int nranks, int prow, int pcol);
 
+/* The kernels of the Laplace approximation in isolation (laplace.hip; tests/test_laplace_kernels.py), under the rules
+ * of the finishing hooks above: arguments are checked before the device is touched (GOGP_EARG), every array goes up
+ * whole and every in / out array comes back whole.  npad: a multiple of 256, 1 <= n <= npad; vectors written by a
+ * kernel hold npad doubles and are zero from row n on.  lik: enum gogp_lik_kind.
+ * lap_site: g, W, sw, b = W f + g, rho of (f, y); part: 5 rows of npad / 256 block results; out[0 .. 4] = sum log p,
+ * sum a f, max |a - g|, max |a|, the first row whose y is refused or -1.  lap_scale_gram: A := diag(sw) A diag(sw) + I on
+ * i, j < n of the lower 64-tiles, the block columns below wcols and the remaining triangle in two launches.  lap_step:
+ * rhs = sw o beta and a1 = b - sw o beta.  lap_interp: at = a + t (a1 - a), ft = f + t (f1 - f).  lap_weight_vectors:
+ * sv_i = 1/2 (1 - Binv_ii) rho_i.  lap_symv_u: u = sv - sw o (Binv v) from the elements j <= i < n of Binv (v zero from
+ * row n on; upart: npad / 64 * npad doubles).  lap_weight: in place, G = diag(sw) G diag(sw) - u a^T - a u^T on j <= i < n,
+ * exact zeros on the rest of the lower 64-tiles.  lap_colscale: KsT (rows x ld) := KsT diag(sw) on npad columns.
+ * lap_mean: the response-scale prediction from the latent mu and sigma. */
+int gogp_test_lap_site(int device, int lik, const double *f, int64_t f_len, const double *y, int64_t y_len, const double *a,
+                       int64_t a_len, int64_t n, int64_t npad, double *g, int64_t g_len, double *W, int64_t w_len, double *sw,
+                       int64_t sw_len, double *b, int64_t b_len, double *rho, int64_t rho_len, double *part, int64_t part_len,
+                       double *out, int64_t out_len);
+int gogp_test_lap_scale_gram(int device, double *A, int64_t a_len, int64_t ld, int64_t n, int64_t npad, const double *sw,
+                             int64_t sw_len, int64_t wcols);
+int gogp_test_lap_step(int device, const double *b, int64_t b_len, const double *sw, int64_t sw_len, const double *beta,
+                       int64_t beta_len, int64_t n, int64_t npad, double *rhs, int64_t rhs_len, double *a1, int64_t a1_len);
+int gogp_test_lap_interp(int device, const double *a, int64_t a_len, const double *a1, int64_t a1_len, const double *f,
+                         int64_t f_len, const double *f1, int64_t f1_len, double t, int64_t n, int64_t npad, double *at,
+                         int64_t at_len, double *ft, int64_t ft_len);
+int gogp_test_lap_weight_vectors(int device, const double *Binv, int64_t binv_len, int64_t ld, const double *rho,
+                                 int64_t rho_len, int64_t n, int64_t npad, double *sv, int64_t sv_len);
+int gogp_test_lap_symv_u(int device, const double *Binv, int64_t binv_len, int64_t ld, int64_t n, int64_t npad, const double *v,
+                         int64_t v_len, const double *sv, int64_t sv_len, const double *sw, int64_t sw_len, double *upart,
+                         int64_t upart_len, double *u, int64_t u_len);
+int gogp_test_lap_weight(int device, double *G, int64_t g_len, int64_t ld, int64_t n, int64_t npad, const double *sw,
+                         int64_t sw_len, const double *u, int64_t u_len, const double *a, int64_t a_len);
+int gogp_test_lap_colscale(int device, double *KsT, int64_t k_len, int64_t ld, int64_t rows, int64_t npad, const double *sw,
+                           int64_t sw_len);
+int gogp_test_lap_mean(int device, int lik, const double *mu, int64_t mu_len, const double *sigma, int64_t sigma_len, int64_t m,
+                       double *mean, int64_t mean_len);
+
 #ifdef __cplusplus
 }
 #endif
