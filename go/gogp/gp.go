@@ -82,6 +82,7 @@ type GP struct {
 	// in-place edits of the same backing arrays must call Touch().
 	dirty      bool
 	nout       int // output columns of SetOutputs
+	nbasis     int // basis columns of SetBasis
 	sparseM    int // inducing points of SetSparse
 	sparseT    int // output columns of SetSparseOutputs
 	upX        *[]float64 // &gp.X[0] at the time of the last upload
@@ -633,6 +634,97 @@ func (gp *GP) MultiProduce(x [][]float64) (mu, sigma []float64, err error) {
 		return nil, nil, err
 	}
 	return buf[:m*gp.nout], sigma, nil
+}
+
+// SetBasis gives the process the basis functions of a mean h(x)^T beta (h
+// row-major n x p, n = len(gp.Y), p <= 64, p < n) whose coefficients are
+// integrated out under a flat prior (Rasmussen & Williams section 2.7; no
+// reference counterpart).  Pending X / Y are uploaded first.  p == 0 clears the
+// basis; whatever replaces or resizes the data drops it.
+func (gp *GP) SetBasis(h []float64, p int) error {
+	gp.defaults()
+	if p == 0 {
+		gp.nbasis = 0
+		return gp.err(C.gogp_basis_set(gp.handle(), nil, 0, 0))
+	}
+	if err := gp.pushData(); err != nil {
+		return err
+	}
+	if p < 0 || len(h) != len(gp.Y)*p {
+		return fmt.Errorf("gogp: len(h) = %d, want %d x %d", len(h), len(gp.Y), p)
+	}
+	if err := gp.err(C.gogp_basis_set(gp.handle(), dptr(h), C.int64_t(len(gp.Y)), C.int32_t(p))); err != nil {
+		return err
+	}
+	gp.nbasis = p
+	return nil
+}
+
+// BasisLML computes the log marginal likelihood with the coefficients of the
+// mean integrated out, at the current parameters.
+func (gp *GP) BasisLML() (float64, error) {
+	gp.defaults()
+	var v C.double
+	if err := gp.err(C.gogp_basis_lml(gp.handle(), &v)); err != nil {
+		return 0, err
+	}
+	return float64(v), nil
+}
+
+// BasisGradient computes the gradient of BasisLML with respect to the
+// log-transformed hyperparameters.
+func (gp *GP) BasisGradient() ([]float64, error) {
+	gp.defaults()
+	g := make([]float64, len(gp.ThetaSimil)+len(gp.ThetaNoise))
+	if err := gp.err(C.gogp_basis_gradient(gp.handle(), dptr(g), C.int64_t(len(g)))); err != nil {
+		return nil, err
+	}
+	return g, nil
+}
+
+// BasisBeta returns the estimate of the mean's coefficients and its covariance
+// (H^T K^-1 H)^-1, row-major p x p.
+func (gp *GP) BasisBeta() (beta, cov []float64, err error) {
+	gp.defaults()
+	p := gp.nbasis
+	beta, cov = make([]float64, p+1), make([]float64, p*p+1)
+	if err = gp.err(C.gogp_basis_get_beta(gp.handle(), dptr(beta), dptr(cov))); err != nil {
+		return nil, nil, err
+	}
+	return beta[:p], cov[:p*p], nil
+}
+
+// BasisAlpha returns K^-1 (y - H beta).
+func (gp *GP) BasisAlpha() ([]float64, error) {
+	gp.defaults()
+	n := int(C.gogp_n(gp.handle()))
+	a := make([]float64, n+1)
+	if err := gp.err(C.gogp_basis_get_alpha(gp.handle(), dptr(a))); err != nil {
+		return nil, err
+	}
+	return a[:n], nil
+}
+
+// BasisProduce computes the predictive mean and standard deviation at the test
+// points x whose basis functions are the rows of hz (row-major len(x) x p):
+// Produce's mean plus the mean's contribution, the deviation widened by the
+// uncertainty of the coefficients.
+func (gp *GP) BasisProduce(x [][]float64, hz []float64) (mu, sigma []float64, err error) {
+	gp.defaults()
+	m := len(x)
+	if len(hz) != m*gp.nbasis {
+		return nil, nil, fmt.Errorf("gogp: len(hz) = %d, want %d x %d", len(hz), m, gp.nbasis)
+	}
+	flat := make([]float64, m*gp.NDim+1)
+	for i, row := range x {
+		copy(flat[i*gp.NDim:], row)
+	}
+	hbuf := append(append([]float64{}, hz...), 0)
+	mu, sigma = make([]float64, m+1), make([]float64, m+1)
+	if err = gp.err(C.gogp_basis_produce(gp.handle(), dptr(flat), dptr(hbuf), C.int64_t(m), dptr(mu), dptr(sigma))); err != nil {
+		return nil, nil, err
+	}
+	return mu[:m], sigma[:m], nil
 }
 
 // SetSparse gives the process the data of the inducing-point approximation

@@ -111,6 +111,12 @@ SYMBOLS = [
     ("gogp_sparse_produce", ctypes.c_int, [_h, _dp, _i64, _dp, _dp]),
     ("gogp_sparse_set_inducing", ctypes.c_int, [_h, _dp, _i64]),
     ("gogp_sparse_gradient_inducing", ctypes.c_int, [_h, _dp, _i64, _dp]),
+    ("gogp_basis_set", ctypes.c_int, [_h, _dp, _i64, ctypes.c_int32]),
+    ("gogp_basis_lml", ctypes.c_int, [_h, _dp]),
+    ("gogp_basis_gradient", ctypes.c_int, [_h, _dp, _i64]),
+    ("gogp_basis_get_beta", ctypes.c_int, [_h, _dp, _dp]),
+    ("gogp_basis_get_alpha", ctypes.c_int, [_h, _dp]),
+    ("gogp_basis_produce", ctypes.c_int, [_h, _dp, _dp, _i64, _dp, _dp]),
     ("gogp_sparse_multi_set_outputs", ctypes.c_int, [_h, _dp, _i64, ctypes.c_int32]),
     ("gogp_sparse_multi_observe", ctypes.c_int, [_h, _dp, _i64, _dp, _dp]),
     ("gogp_sparse_multi_gradient", ctypes.c_int, [_h, _dp, _i64]),
@@ -309,6 +315,21 @@ _LAPLACE_SPEC = {
 LAPLACE_HOOKS = {k: [tuple(t.split(":")) for t in v.split()] for k, v in _LAPLACE_SPEC.items()}
 HOOK_SYMBOLS += [("gogp_test_" + k, ctypes.c_int, [ctypes.c_int] + [t for _, kind in spec for t in _FINISH_CTYPES[kind]])
                  for k, spec in LAPLACE_HOOKS.items()]
+
+
+#: the hooks of the kernels of the explicit basis functions (tests/test_basis_kernels.py), as gp.basis_kernel_check reads
+#: them: the notation of _FINISH_SPEC
+_BASIS_SPEC = {
+    "basis_symm": "Kinv:a ldk:l n:l npad:l Ht:a ld:l p:i part:o Wt:o",
+    "basis_gram": "Ht:a Wt:a ld:l alpha:a n:l p:i part:o Ag:o",
+    "basis_finish": "Ag:a p:i LA:o Ainv:o beta:o scal:o info:o",
+    "basis_cols": "Wt:a ld:l n:l p:i LA:a beta:a alpha:a Ct:o",
+    "basis_predict": "Hz:a KW:a ldkw:l m:l p:i beta:a Ainv:a mu0:a prior:a q:a mu:o sigma:o",
+}
+BASIS_HOOKS = {k: [tuple(t.split(":")) for t in v.split()] for k, v in _BASIS_SPEC.items()}
+HOOK_SYMBOLS += [("gogp_test_" + k, ctypes.c_int, [ctypes.c_int] + [t for _, kind in spec for t in _FINISH_CTYPES[kind]])
+                 for k, spec in BASIS_HOOKS.items()]
+HOOK_SYMBOLS += [("gogp_test_basis_symm_slabs", ctypes.c_int, [_i64]), ("gogp_test_basis_gram_slabs", ctypes.c_int, [_i64])]
 
 
 def build(force: bool = False) -> str:

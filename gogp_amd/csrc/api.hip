@@ -115,6 +115,11 @@ static void free_n_buffers(gogp_handle *h) {
   h->multi_mat.release();
   h->multi_T = 0;
   h->multi_solved = false;
+  h->basis_vec.release();
+  h->basis_part.release();
+  h->basis_mean.release();
+  h->basis_p = 0;
+  h->basis_solved = false;
   (void)hipFree(h->TX);
   (void)hipFree(h->Tmt);
   h->TX = h->Tmt = nullptr;
@@ -345,6 +350,7 @@ static int ensure_n(gogp_handle *h, int64_t n) {
   h->nblk = (int)(npad / TILE);
   h->factored = h->have_alpha = h->have_kinv = h->observed = h->grad_valid = false;
   h->multi_solved = false;
+  h->basis_solved = false;
   h->trtri_done = false;
   h->lap_observed = h->lap_grad_valid = h->lap_warm_valid = false;  // the Laplace fit and its warm start belonged to the old data
   if (npad > h->cap_npad) {
@@ -383,6 +389,8 @@ static int set_data_impl(gogp_handle *h, const double *X, const double *y, int64
   if (rc != GOGP_OK) return rc;
   h->have_data = true;
   h->multi_T = 0;  // the outputs of gogp_multi_set_outputs belonged to the data that was replaced
+  h->basis_p = 0;  // ... and so did the basis of gogp_basis_set
+  h->basis_solved = false;
   if (n == 0) return GOGP_OK;
   // zero padding rows, then copy
   HIPCHK(h, hipMemsetAsync(h->dX, 0, ((size_t)h->npad * h->D + GOGP_MAX_NDIM) * sizeof(double), h->s));
@@ -426,6 +434,7 @@ extern "C" int gogp_set_events(gogp_handle *h, const double *events, int nevents
     for (int f = 0; f < 3; ++f) h->events[e][f] = events[3 * e + f];
   h->factored = h->have_alpha = h->have_kinv = h->observed = h->grad_valid = false;
   h->multi_solved = false;
+  h->basis_solved = false;
   h->lap_observed = h->lap_grad_valid = false;
   h->trtri_done = h->trtri_pending = h->alpha_pending = h->kinv_pending = false;
   h->tinv_valid = h->tinv_pending = false;
@@ -959,6 +968,7 @@ static void begin_evaluation(gogp_handle *h, std::initializer_list<hipStream_t> 
   h->trtri_pending = h->kinv_pending = false;
   h->factored = h->have_alpha = h->have_kinv = h->grad_valid = false;
   h->multi_solved = false;
+  h->basis_solved = false;
   h->lap_observed = h->lap_grad_valid = false;  // a new factor replaces a Laplace fit's (gogp_laplace_observe sets them behind its own)
   h->alpha_pending = h->trtri_done = h->ydone_valid = h->d64_active = false;
   h->notpd = -1;
@@ -2882,7 +2892,7 @@ extern "C" int gogp_multi_gradient(gogp_handle *h, double *grad, int64_t len) {
   if (rc != GOGP_OK) return rc;
   double *G = h->multi_mat.as<double>(), *zero = G + mat;
   // G = T K^-1 - A A^T on the lower tiles
-  launch_multi_weight(s, multi_at(h), npad, h->multi_T, h->bufA, ld, h->n, npad, G);
+  launch_multi_weight(s, multi_at(h), npad, h->multi_T, h->bufA, ld, h->n, npad, (double)h->multi_T, G);
   // sum_ab (0 0^T - G)_ab dK_ab per slot: the reduction of the LML gradient with G for K^-1 and zeros for alpha
   HIPCHK(h, hipMemsetAsync(zero, 0, (size_t)npad * sizeof(double), s));
   {
@@ -2951,6 +2961,253 @@ extern "C" int gogp_multi_produce(gogp_handle *h, const double *Z, int64_t m, do
   }
   HIPCHK(h, hipMemcpy2DAsync(mu, (size_t)T * sizeof(double), h->multi_mean.p, (size_t)GOGP_MULTI_MAX_T * sizeof(double),
                              (size_t)T * sizeof(double), (size_t)m, hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipStreamSynchronize(s));
+  HIPCHK(h, hipGetLastError());
+  return GOGP_OK;
+}
+
+// ---- explicit basis functions: a marginalised linear mean (basis.hip) ------------------------------------------------
+// No reference counterpart (gp.GP has mean zero).  Rasmussen & Williams section 2.7 in the flat-prior limit; the formulas
+// are in DESIGN.md section 4, "Explicit basis functions".  basis_vec holds H^T and W^T = (K^-1 H)^T (TILE rows of npad
+// doubles each, zero from row p and column n on: the tile kernel and Produce's substitution take them as they lie), the
+// p + 1 rows [Q | alpha~]^T and the p x p results; everything is computed on first need after a factorisation and kept
+// (basis_solved).  W comes from the explicit K^-1 by basis_symm_kernel where that matrix is there or on its way, from
+// the factor by multi_solve's two substitutions otherwise (option "basis_symm").  The calls write workspaces of their
+// own, Produce's and, as gogp_gradient would, K^-1: the contract of gogp_multi_*.  G shares multi_mat with
+// gogp_multi_gradient: both write it whole before they read it, inside one call.
+constexpr int BASIS_CROWS = (GOGP_BASIS_MAX_P + 1 + 3) / 4 * 4;
+constexpr size_t BASIS_PP = (size_t)GOGP_BASIS_MAX_P * GOGP_BASIS_MAX_P, BASIS_AG = (size_t)GOGP_BASIS_MAX_P * (GOGP_BASIS_MAX_P + 1);
+static_assert(GOGP_BASIS_MAX_P <= TILE, "the basis columns are one tile row of right-hand sides");
+struct BasisBufs {
+  double *Ht, *Wt, *Ct, *Ag, *LA, *Ainv, *beta, *scal, *gpart;
+  long long *info;
+};
+static size_t basis_layout(double *base, int64_t npad, BasisBufs *b) {
+  size_t off = 0;
+  auto take = [&](size_t cnt) {
+    double *q = base ? base + off : nullptr;
+    off += cnt;
+    return q;
+  };
+  b->Ht = take((size_t)TILE * npad), b->Wt = take((size_t)TILE * npad), b->Ct = take((size_t)BASIS_CROWS * npad);
+  b->Ag = take(BASIS_AG), b->LA = take(BASIS_PP), b->Ainv = take(BASIS_PP), b->beta = take(GOGP_BASIS_MAX_P);
+  b->scal = take(8), b->gpart = take((size_t)gogp::BASIS_GRAM_SLABS_MAX * BASIS_AG);
+  b->info = reinterpret_cast<long long *>(take(1));
+  return off * sizeof(double);
+}
+static BasisBufs basis_bufs(const gogp_handle *h) {
+  BasisBufs b;
+  (void)basis_layout(h->basis_vec.as<double>(), h->npad, &b);
+  return b;
+}
+
+extern "C" int gogp_basis_set(gogp_handle *h, const double *H, int64_t n, int32_t p) {
+  if (!h) return GOGP_EARG;
+  if (p == 0 && !H) {  // clear
+    h->basis_p = 0;
+    h->basis_solved = false;
+    return GOGP_OK;
+  }
+  if (const char *refuse = multi_refusal(h)) {
+    char buf[160];
+    snprintf(buf, sizeof buf, "basis_set: %s are not supported", refuse);
+    return fail(h, GOGP_EARG, buf);
+  }
+  if (!h->have_data) return fail(h, GOGP_ESTATE, "basis_set: no data (gogp_set_data)");
+  if (!H || n != h->n || p < 1 || p > GOGP_BASIS_MAX_P)
+    return fail(h, GOGP_EARG, "basis_set: need H, n == gogp_n and 1 <= p <= GOGP_BASIS_MAX_P");
+  if (n <= p) return fail(h, GOGP_EARG, "basis_set: needs more observations than basis columns (n > p)");
+  for (int64_t i = 0; i < n * p; ++i)
+    if (!std::isfinite(H[i])) return fail(h, GOGP_EARG, "basis_set: non-finite basis value");
+  HIPCHK(h, hipSetDevice(h->device));
+  const int64_t npad = h->npad;
+  h->basis_p = 0;  // until the new one is in place
+  h->basis_solved = false;
+  BasisBufs b;
+  const int rc = h->basis_vec.reserve(h, basis_layout(nullptr, std::max(npad, h->cap_npad), &b));
+  if (rc != GOGP_OK) return rc;
+  b = basis_bufs(h);
+  std::vector<double> ht((size_t)p * npad, 0.0);
+  for (int64_t i = 0; i < n; ++i)
+    for (int c = 0; c < p; ++c) ht[(size_t)c * npad + i] = H[i * p + c];
+  HIPCHK(h, hipMemsetAsync(b.Ht, 0, 2 * (size_t)TILE * npad * sizeof(double), h->s));  // H^T and W^T
+  HIPCHK(h, hipMemcpyAsync(b.Ht, ht.data(), ht.size() * sizeof(double), hipMemcpyHostToDevice, h->s));
+  HIPCHK(h, hipStreamSynchronize(h->s));
+  h->basis_p = p;
+  return GOGP_OK;
+}
+
+// W, [A | g], the factor of A, beta and [Q | alpha~] of the current factor and basis, on the main stream
+static int basis_solve(gogp_handle *h) {
+  if (h->basis_solved) return GOGP_OK;
+  const int p = h->basis_p;
+  const int64_t n = h->n, npad = h->npad;
+  int rc = ensure_alpha(h);  // the main stream behind the factorisation
+  if (rc != GOGP_OK) return rc;
+  hipStream_t s = h->s;
+  const BasisBufs b = basis_bufs(h);
+  const size_t row = (size_t)npad * sizeof(double);
+  const bool symm = h->basis_symm == 1 || (h->basis_symm < 0 && (h->have_kinv || h->kinv_pending));
+  if (symm) {
+    rc = compute_kinv(h);
+    if (rc == GOGP_OK)
+      rc = h->basis_part.reserve(h, (size_t)gogp::basis_symm_slabs(n) * (size_t)((p + 3) / 4 * 4) * row);
+    if (rc != GOGP_OK) return rc;
+    launch_basis_symm(s, h->bufA, npad, n, npad, b.Ht, npad, p, h->basis_part.as<double>(), b.Wt);
+  } else {  // multi_solve's route: H^T into KsT, Produce's forward and ProduceGradient's backward substitution
+    rc = ensure_m(h, p, TILE);
+    if (rc != GOGP_OK) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->KsT, b.Ht, TILE * row, hipMemcpyDeviceToDevice, s));
+    produce_substitute_t<double>(h, s, p, TILE, nullptr);
+    produce_backward(h, s, p);
+    HIPCHK(h, hipMemcpyAsync(b.Wt, h->KsT, (size_t)p * row, hipMemcpyDeviceToDevice, s));
+    HIPCHK(h, hipMemsetAsync(b.Wt + (size_t)p * npad, 0, (size_t)(TILE - p) * row, s));
+  }
+  launch_basis_gram(s, b.Ht, b.Wt, npad, h->alpha, n, p, b.gpart, b.Ag);
+  launch_basis_finish(s, b.Ag, p, b.LA, b.Ainv, b.beta, b.scal, b.info);
+  long long info = 0;
+  double scal[2];
+  h->basis_beta.assign((size_t)p, 0.0);
+  h->basis_cov.assign((size_t)p * p, 0.0);
+  HIPCHK(h, hipMemcpyAsync(&info, b.info, sizeof info, hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipStreamSynchronize(s));
+  HIPCHK(h, hipGetLastError());
+  if (info != 0) {
+    char buf[200];
+    snprintf(buf, sizeof buf,
+             "basis: H^T K^-1 H is not positive definite (pivot %lld): the basis columns are linearly dependent",
+             info - 1);
+    h->err = buf;
+    return GOGP_ECOND;
+  }
+  launch_basis_cols(s, b.Wt, npad, n, p, b.LA, b.beta, h->alpha, b.Ct);
+  HIPCHK(h, hipMemcpyAsync(scal, b.scal, sizeof scal, hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipMemcpyAsync(h->basis_beta.data(), b.beta, (size_t)p * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipMemcpyAsync(h->basis_cov.data(), b.Ainv, (size_t)p * p * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipStreamSynchronize(s));
+  HIPCHK(h, hipGetLastError());
+  h->basis_logdet = scal[0];
+  h->basis_gtb = scal[1];
+  h->basis_solved = true;
+  return GOGP_OK;
+}
+
+// The refusals and the state of the calls that work on the basis (under the name `who`), then the solutions in place
+static int basis_prepare(gogp_handle *h, const char *who) {
+  char buf[160];
+  if (const char *refuse = multi_refusal(h)) {
+    snprintf(buf, sizeof buf, "%s: %s are not supported", who, refuse);
+    return fail(h, GOGP_EARG, buf);
+  }
+  if (h->basis_p == 0) {
+    snprintf(buf, sizeof buf, "%s: no basis (gogp_basis_set)", who);
+    return fail(h, GOGP_ESTATE, buf);
+  }
+  if (h->n <= h->basis_p) {
+    snprintf(buf, sizeof buf, "%s: needs more observations than basis columns (n > p)", who);
+    return fail(h, GOGP_EARG, buf);
+  }
+  if (!h->factored) {
+    snprintf(buf, sizeof buf, "%s: nothing absorbed", who);
+    return fail(h, GOGP_ESTATE, buf);
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  return basis_solve(h);
+}
+
+extern "C" int gogp_basis_lml(gogp_handle *h, double *lml) {
+  if (!h || !lml) return fail(h, GOGP_EARG, "basis_lml: NULL");
+  const int rc = basis_prepare(h, "basis_lml");
+  if (rc != GOGP_OK) return rc;
+  // R&W eq. 2.45: the handle's own LML, + 1/2 g^T beta - 1/2 log|A| + p/2 log 2 pi
+  *lml = h->lml + 0.5 * h->basis_gtb - 0.5 * h->basis_logdet + 0.5 * (double)h->basis_p * log(2 * M_PI);
+  return GOGP_OK;
+}
+
+extern "C" int gogp_basis_gradient(gogp_handle *h, double *grad, int64_t len) {
+  if (!h || !grad) return fail(h, GOGP_EARG, "basis_gradient: NULL");
+  if (len != h->P) return fail(h, GOGP_EARG, "basis_gradient: wrong length");
+  if (h->basis_p != 0 && h->with_obs) return fail(h, GOGP_EARG, "basis_gradient: the full Observe form is not supported");
+  int rc = basis_prepare(h, "basis_gradient");
+  if (rc != GOGP_OK) return rc;
+  for (int64_t i = 0; i < len; ++i) grad[i] = 0.0;
+  rc = compute_kinv(h);
+  if (rc != GOGP_OK) return rc;
+  hipStream_t s = h->s;
+  const int64_t npad = h->npad, ld = npad;
+  const size_t mat = (size_t)npad * (size_t)npad;
+  rc = h->multi_mat.reserve(h, (mat + (size_t)npad) * sizeof(double));
+  if (rc != GOGP_OK) return rc;
+  double *G = h->multi_mat.as<double>(), *zero = G + mat;
+  // G = K^-1 - [Q | alpha~][Q | alpha~]^T on the lower tiles, then the reduction of the LML gradient with G for K^-1 and
+  // zeros for alpha (gogp_multi_gradient)
+  launch_multi_weight(s, basis_bufs(h).Ct, npad, h->basis_p + 1, h->bufA, ld, h->n, npad, 1.0, G);
+  HIPCHK(h, hipMemsetAsync(zero, 0, (size_t)npad * sizeof(double), s));
+  {
+    AuxTimer tm(h, GOGP_PROF_GRAD, s);
+    launch_grad_reduce(s, h->devP, h->D, h->ard_dims, h->dX, zero, (const double *)G, ld, h->n, npad, h->gpart, h->gout,
+                       h->radial1, h->ard_mfma_min, h->ev());
+  }
+  double acc[NACC];
+  HIPCHK(h, hipMemcpyAsync(acc, h->gout, sizeof acc, hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipStreamSynchronize(s));
+  HIPCHK(h, hipGetLastError());
+  assemble_gradient(h, acc, h->hostP->dnoise, grad);
+  return GOGP_OK;
+}
+
+extern "C" int gogp_basis_get_beta(gogp_handle *h, double *beta, double *cov) {
+  if (!h || !beta) return fail(h, GOGP_EARG, "basis_get_beta: NULL");
+  const int rc = basis_prepare(h, "basis_get_beta");
+  if (rc != GOGP_OK) return rc;
+  const size_t p = (size_t)h->basis_p;
+  for (size_t i = 0; i < p; ++i) beta[i] = h->basis_beta[i];
+  for (size_t i = 0; cov && i < p * p; ++i) cov[i] = h->basis_cov[i];
+  return GOGP_OK;
+}
+
+extern "C" int gogp_basis_get_alpha(gogp_handle *h, double *alpha) {
+  if (!h || !alpha) return fail(h, GOGP_EARG, "basis_get_alpha: NULL");
+  const int rc = basis_prepare(h, "basis_get_alpha");
+  if (rc != GOGP_OK) return rc;
+  HIPCHK(h, hipMemcpyAsync(alpha, basis_bufs(h).Ct + (size_t)h->basis_p * h->npad, (size_t)h->n * sizeof(double),
+                           hipMemcpyDeviceToHost, h->s));
+  HIPCHK(h, hipStreamSynchronize(h->s));
+  HIPCHK(h, hipGetLastError());
+  return GOGP_OK;
+}
+
+extern "C" int gogp_basis_produce(gogp_handle *h, const double *Z, const double *Hz, int64_t m, double *mu, double *sigma) {
+  if (!h || m < 0 || (m > 0 && (!Z || !Hz || !mu))) return fail(h, GOGP_EARG, "basis_produce: NULL");
+  int rc = basis_prepare(h, "basis_produce");
+  if (rc != GOGP_OK) return rc;
+  const int p = h->basis_p;
+  for (int64_t i = 0; i < m * p; ++i)
+    if (!std::isfinite(Hz[i])) return fail(h, GOGP_EARG, "basis_produce: non-finite basis value");
+  ProducePlan pp;
+  rc = produce_prepare(h, "basis_produce", "basis_produce", m, false, &pp);
+  if (rc != GOGP_OK || m == 0) return rc;
+  hipStream_t s = h->s;
+  rc = produce_forward(h, Z, m, pp, true, false);  // Z up, the prior, the main stream behind alpha
+  if (rc != GOGP_OK) return rc;
+  const size_t mp = (size_t)pp.mpad;
+  rc = h->basis_mean.reserve(h, mp * (TILE + GOGP_BASIS_MAX_P + 1) * sizeof(double));
+  if (rc != GOGP_OK) return rc;
+  double *KW = h->basis_mean.as<double>(), *dHz = KW + mp * TILE, *dmu = dHz + mp * GOGP_BASIS_MAX_P;
+  const BasisBufs b = basis_bufs(h);
+  HIPCHK(h, hipMemcpyAsync(dHz, Hz, (size_t)m * p * sizeof(double), hipMemcpyHostToDevice, s));
+  // always the tile route of Produce, whatever m (as gogp_multi_produce): Kstar^T row by row in KsT
+  produce_cross_t<double>(h, s, m, pp.mpad);
+  launch_rownorm_dot(s, (const double *)h->KsT, h->npad, h->alpha, h->npad, m, pp.mu, nullptr);  // mu_0 = Kstar^T alpha
+  // Kstar^T W in one launch of the tile kernel -- before the substitution uses up Kstar^T
+  GemmGrid gm;
+  gm.small_below = h->produce_small_below;
+  launch_gemm_nt(s, GEMM_RECT, (int)(pp.mpad / TILE), 1, h->npad, 1.0, (const double *)h->KsT, h->npad, (const double *)b.Wt,
+                 h->npad, 0.0, KW, (int64_t)TILE, h->prof.on ? &h->prof : nullptr, &gm);
+  if (sigma) produce_substitute_t<double>(h, s, m, pp.mpad, pp.q);
+  launch_basis_predict(s, dHz, KW, TILE, m, p, b.beta, b.Ainv, pp.mu, pp.prior, pp.q, dmu, sigma ? pp.sigma : nullptr);
+  HIPCHK(h, hipMemcpyAsync(mu, dmu, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (sigma) HIPCHK(h, hipMemcpyAsync(sigma, pp.sigma, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
   HIPCHK(h, hipStreamSynchronize(s));
   HIPCHK(h, hipGetLastError());
   return GOGP_OK;
@@ -3897,6 +4154,7 @@ extern "C" int gogp_laplace_observe(gogp_handle *h, int32_t lik, const double *x
   // the regression state goes, as with gogp_set_data; so does an earlier Laplace fit
   h->factored = h->have_alpha = h->observed = h->with_obs = h->grad_valid = h->z_valid = false;
   h->multi_solved = false;
+  h->basis_solved = false;
   h->lap_observed = h->lap_grad_valid = false;
   h->lap_lik = lik;
   h->lap_iters = 0;
@@ -4137,6 +4395,7 @@ extern "C" int gogp_set_factor(gogp_handle *h, const double *theta_simil,
   h->z_valid = false;     // no z = L^-1 y comes with a restored factor (gogp_append recomputes it)
   h->kinv_c1 = 0;         // ... and no partial K^-1 of an earlier sweep belongs to it (compute_kinv: gogp_loo)
   h->multi_solved = false;  // ... nor do the solutions of gogp_multi_*
+  h->basis_solved = false;  // ... or of gogp_basis_*
   h->lap_observed = h->lap_grad_valid = false;  // ... nor does a Laplace fit, whose factor this one replaces
   if (h->n == 0) return GOGP_OK;
   if (h->dist) return gogp_dist_set_factor(h, Lin, alpha);  // collective: every rank keeps its own tiles
@@ -4212,6 +4471,8 @@ static int begin_factor_update(gogp_handle *h) {
   h->kinv_c1 = 0;
   h->multi_T = 0;  // the outputs of gogp_multi_set_outputs belong to the rows as they were
   h->multi_solved = false;
+  h->basis_p = 0;  // ... and so does the basis of gogp_basis_set
+  h->basis_solved = false;
   h->lap_observed = h->lap_grad_valid = h->lap_warm_valid = false;  // a Laplace fit (and its warm start) belongs to the rows as they were
   return GOGP_OK;
 }
@@ -4640,6 +4901,12 @@ extern "C" int gogp_set_option(gogp_handle *h, const char *name, int64_t value) 
     h->produce_tinv = value != 0;
     return GOGP_OK;
   }
+  if (strcmp(name, "basis_symm") == 0) {  // gogp_basis_*: W = K^-1 H from the explicit K^-1 (1), from the factor (0), -1: whichever is there
+    if (value < -1 || value > 1) return fail(h, GOGP_EARG, "basis_symm must be -1, 0 or 1");
+    h->basis_symm = (int)value;
+    h->basis_solved = false;
+    return GOGP_OK;
+  }
   if (strcmp(name, "produce_panels") == 0) {  // Produce: 256-panels per super-panel of its substitution
     if (value < 1 || value > 8) return fail(h, GOGP_EARG, "produce_panels must be 1..8");
     h->produce_panels = (int)value;
@@ -4710,6 +4977,8 @@ extern "C" int gogp_set_option(gogp_handle *h, const char *name, int64_t value) 
       h->lap_observed = h->lap_grad_valid = h->lap_warm_valid = false;  // (free_n_buffers dropped the Laplace fit too)
       h->multi_T = 0;  // (free_n_buffers dropped the outputs of gogp_multi_set_outputs; said here too)
       h->multi_solved = false;
+      h->basis_p = 0;
+      h->basis_solved = false;
       h->trtri_done = h->trtri_pending = h->alpha_pending = h->kinv_pending = false;
     }
     return GOGP_OK;

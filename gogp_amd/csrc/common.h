@@ -453,12 +453,35 @@ void launch_blockcv_groups(hipStream_t s, const double *Kinv, int64_t ld, const 
 void launch_blockcv_apply(hipStream_t s, double *Q, int64_t ld, int64_t n, const int64_t *bstart, const int64_t *gfirst,
                           int ngroups, const double *Sg);
 // multi.hip (gogp_multi_*): T output columns on one factorisation.  At / Yt: one output per row of ld >= npad doubles.
-// launch_multi_weight: G (ldk, as Kinv) = T Kinv - A A^T on the elements j <= i < n of the lower 64-tiles of npad, exact
+// launch_multi_weight: G (ldk, as Kinv) = scale Kinv - A A^T (gogp_multi_*: scale = T) on the elements j <= i < n of the lower 64-tiles of npad, exact
 // zeros on the rest of those tiles, nothing outside them; At must hold T rounded up to a multiple of 4 rows, the rows
 // from T on zero; of Kinv only j <= i < n is read.  launch_multi_dots: dots[t] = sum_{i < n} Yt[t][i] At[t][i], t < T.
 void launch_multi_weight(hipStream_t s, const double *At, int64_t ld, int T, const double *Kinv, int64_t ldk, int64_t n,
-                         int64_t npad, double *G);
+                         int64_t npad, double scale, double *G);
 void launch_multi_dots(hipStream_t s, const double *Yt, const double *At, int64_t ld, int64_t n, int T, double *dots);
+// basis.hip (gogp_basis_*): explicit basis functions.  Ht / Wt: one basis column per row of ld >= npad doubles, p <= 64.
+// launch_basis_symm: Wt (p rounded up to a multiple of 4 rows) = (Kinv H)^T from the symmetric Kinv (ldk) of which only
+// the elements j <= i < n are read; columns >= n and rows >= p of Wt exact zeros; of Ht the rows < p and the columns < n
+// are read; part: basis_symm_slabs(n) * p4 * ld doubles of scratch.  launch_basis_gram: Ag (p x (p + 1)) = Ht [Wt^T |
+// alpha] over the observations < n; part: basis_gram_slabs(n) * p (p + 1) doubles.  launch_basis_finish: from Ag the
+// factor LA (p x p), Ainv (p x p), beta (p), scal = {log|A|, g^T beta} and info = 0 or the first bad pivot + 1 (nothing
+// else is written then).  launch_basis_cols: Ct ((p + 1) rounded up to a multiple of 4 rows of ld doubles) = [W LA^-T |
+// alpha - W beta]^T, zero rows behind and zero columns >= n.  launch_basis_predict: mu = mu0 + R beta and sigma (unless
+// NULL) = sqrt(prior - q + diag(R Ainv R^T)), R = Hz (m x p) - KW (ldkw doubles per row).
+constexpr int BASIS_SYMM_SLABS_MAX = 16, BASIS_GRAM_SLABS_MAX = 64;
+int basis_symm_slabs(int64_t n);
+int basis_gram_slabs(int64_t n);
+void launch_basis_symm(hipStream_t s, const double *Kinv, int64_t ldk, int64_t n, int64_t npad, const double *Ht, int64_t ld,
+                       int p, double *part, double *Wt);
+void launch_basis_gram(hipStream_t s, const double *Ht, const double *Wt, int64_t ld, const double *alpha, int64_t n, int p,
+                       double *part, double *Ag);
+void launch_basis_finish(hipStream_t s, const double *Ag, int p, double *LA, double *Ainv, double *beta, double *scal,
+                         long long *info);
+void launch_basis_cols(hipStream_t s, const double *Wt, int64_t ld, int64_t n, int p, const double *LA, const double *beta,
+                       const double *alpha, double *Ct);
+void launch_basis_predict(hipStream_t s, const double *Hz, const double *KW, int64_t ldkw, int64_t m, int p,
+                          const double *beta, const double *Ainv, const double *mu0, const double *prior, const double *q,
+                          double *mu, double *sigma);
 // sparse.hip (gogp_sparse_*): the inducing-point approximation.  Vt: `rows` rows (one observation of the chunk each) of
 // ld >= Mp doubles, as Produce's forward substitution leaves V^T; Mp a multiple of 64.
 // launch_sparse_syrk: Bacc (ldb) += Vt^T Vt on the whole lower 64-tiles of Mp x Mp and r += Vt^T y (rows doubles); rows

@@ -226,6 +226,15 @@ struct gogp_handle : EvalBufs, EvalState {
   Workspace multi_vec;      // Y^T, then A^T: GOGP_MULTI_MAX_T rows of npad doubles each, zero from column n and from row T on
   Workspace multi_mean;     // gogp_multi_produce: Kstar^T A, mpad x GOGP_MULTI_MAX_T; gogp_multi_lml: the T dots
   Workspace multi_mat;      // gogp_multi_gradient: G = T K^-1 - A A^T and a zero vector, (npad + 1) x npad
+  // explicit basis functions on the handle's factorisation (gogp_basis_*, basis.hip); all released with the N buffers
+  int basis_p = 0;             // basis columns set (gogp_basis_set) for the current data; 0: none
+  bool basis_solved = false;   // W, A's factor, beta and [Q | alpha~] of the current factor are in basis_vec: cleared wherever multi_solved is
+  int basis_symm = -1;         // option "basis_symm": W from the explicit K^-1 (1), from the factor (0), -1: from K^-1 where it is there
+  Workspace basis_vec;      // H^T, W^T, [Q | alpha~]^T and the p x p results (api.hip: BasisBufs)
+  Workspace basis_part;     // the slabs' partial sums of basis_symm_kernel
+  Workspace basis_mean;     // gogp_basis_produce: Kstar^T W (mpad x 128), H_z, mu
+  double basis_logdet = 0.0, basis_gtb = 0.0;  // log|A| and g^T beta of the solved state
+  std::vector<double> basis_beta, basis_cov;   // ... and beta (p) and A^-1 (p x p)
   // the inducing-point approximation (gogp_sparse_*, sparse.hip): a data set of its own and a private dense handle for
   // the process on the inducing points; nothing of the handle's own data, factor or workspaces is touched
   gogp_handle *sp_ind = nullptr;   // the inducing process: same similarity terms, constant noise sqrt(jitter), data U, y = 0

@@ -28,7 +28,7 @@ __device__ __forceinline__ void multi_lower_tile(int t, int &ti, int &tj) {
   tj = t - ti * (ti + 1) / 2;
 }
 
-// G (ldk doubles per row, as Kinv) = T Kinv - A A^T on the elements j <= i < n of the lower 64 x 64 tiles, one
+// G (ldk doubles per row, as Kinv) = scale Kinv - A A^T (gogp_multi_*: scale = T; gogp_basis_*: 1) on the elements j <= i < n of the lower 64 x 64 tiles, one
 // workgroup per tile (ti, tj), tj <= ti; every other element of those tiles -- i >= n, j >= n, the upper half of a
 // diagonal tile -- is written as an exact zero, and nothing outside them is written.  At: T4 rows (T rounded up to a
 // multiple of 4, the rows from T on zero) of ld doubles, row t = column t of A, contiguous along the observations: both
@@ -39,7 +39,7 @@ __device__ __forceinline__ void multi_lower_tile(int t, int &ti, int &tj) {
 // the accumulators stay in architectural VGPRs -- tools/codeobj_audit.py allows no AGPR.)
 __global__ __launch_bounds__(256, 2) void multi_weight_kernel(const double *__restrict__ At, long ld, int T, int T4,
                                                            const double *__restrict__ Kinv, long ldk, long n,
-                                                           double *__restrict__ G) {
+                                                           double scale, double *__restrict__ G) {
   __shared__ double As[MW_KC * MW_S], Bs[MW_KC * MW_S];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   int ti, tj;
@@ -72,7 +72,6 @@ __global__ __launch_bounds__(256, 2) void multi_weight_kernel(const double *__re
     }
   }
   // C fragment: column = lane & 15, row = (lane >> 4) + 4 v
-  const double scale = (double)T;
 #pragma unroll
   for (int v = 0; v < 4; ++v) {
     const long gi = r0 + 16 * w + fk + 4 * v;
@@ -102,10 +101,10 @@ __global__ __launch_bounds__(256) void multi_dots_kernel(const double *__restric
 }
 
 void launch_multi_weight(hipStream_t s, const double *At, int64_t ld, int T, const double *Kinv, int64_t ldk, int64_t n,
-                         int64_t npad, double *G) {
+                         int64_t npad, double scale, double *G) {
   const int nt = (int)(npad / 64);
   GOGP_KLAUNCH(multi_weight_kernel, dim3((unsigned)(nt * (nt + 1) / 2)), dim3(256), 0, s, At, (long)ld, T, (T + 3) / 4 * 4,
-               Kinv, (long)ldk, (long)n, G);
+               Kinv, (long)ldk, (long)n, scale, G);
 }
 
 void launch_multi_dots(hipStream_t s, const double *Yt, const double *At, int64_t ld, int64_t n, int T, double *dots) {

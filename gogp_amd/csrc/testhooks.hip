@@ -1372,7 +1372,7 @@ extern "C" int gogp_test_multi_weight(int device, const double *At, int64_t at_l
   if (e == hipSuccess) e = dK.up(Kinv, (size_t)kinv_len * sizeof(double));
   if (e == hipSuccess) e = dG.up(G, (size_t)g_len * sizeof(double));
   if (e == hipSuccess) {
-    launch_multi_weight(0, dA, ld, T, dK.as<double>(), ldk, n, npad, dG.as<double>());
+    launch_multi_weight(0, dA, ld, T, dK.as<double>(), ldk, n, npad, (double)T, dG.as<double>());
     e = launched();
   }
   if (e == hipSuccess) e = dG.down(G);
@@ -1952,4 +1952,99 @@ extern "C" int gogp_test_lap_mean(int device, int lik, const double *mu, int64_t
   if (!fin_have(arrs) || !lap_lik_known(lik) || m < 1 || m > FIN_M_MAX) return GOGP_EARG;
   if (mu_len < m || sigma_len < m || mean_len < m) return GOGP_EARG;
   return fin_run(device, arrs, [&](double **d) { launch_lap_mean(0, lik, d[0], d[1], m, d[2]); });
+}
+
+// ---- the kernels of basis.hip through their product launchers (tests/test_basis_kernels.py).  The rules of the hooks
+// above.
+namespace {
+bool basis_p_ok(int p) { return p >= 1 && p <= GOGP_BASIS_MAX_P; }
+}  // namespace
+extern "C" int gogp_test_basis_symm_slabs(int64_t n) { return n >= 1 && n <= UP_NPAD_MAX ? basis_symm_slabs(n) : 0; }
+extern "C" int gogp_test_basis_gram_slabs(int64_t n) { return n >= 1 && n <= UP_NPAD_MAX ? basis_gram_slabs(n) : 0; }
+
+extern "C" int gogp_test_basis_symm(int device, const double *Kinv, int64_t kinv_len, int64_t ldk, int64_t n, int64_t npad,
+                                    const double *Ht, int64_t ht_len, int64_t ld, int p, double *part, int64_t part_len,
+                                    double *Wt, int64_t wt_len) {
+  const std::initializer_list<FinArr> arrs = {{Kinv, kinv_len, false}, {Ht, ht_len, false}, {part, part_len, true},
+                                              {Wt, wt_len, true}};
+  if (!fin_have(arrs) || !fin_npad_ok(n, npad) || !basis_p_ok(p) || ld < npad || ldk < npad) return GOGP_EARG;
+  const int64_t p4 = (p + 3) / 4 * 4;
+  if (!covers(kinv_len, 0, ldk, npad, npad, 1, 0) || ht_len < (int64_t)p * ld || wt_len < p4 * ld ||
+      part_len < (int64_t)basis_symm_slabs(n) * p4 * ld)
+    return GOGP_EARG;
+  return fin_run(device, arrs, [&](double **d) { launch_basis_symm(0, d[0], ldk, n, npad, d[1], ld, p, d[2], d[3]); });
+}
+
+extern "C" int gogp_test_basis_gram(int device, const double *Ht, int64_t ht_len, const double *Wt, int64_t wt_len, int64_t ld,
+                                    const double *alpha, int64_t alpha_len, int64_t n, int p, double *part, int64_t part_len,
+                                    double *Ag, int64_t ag_len) {
+  const std::initializer_list<FinArr> arrs = {{Ht, ht_len, false}, {Wt, wt_len, false}, {alpha, alpha_len, false},
+                                              {part, part_len, true}, {Ag, ag_len, true}};
+  if (!fin_have(arrs) || !basis_p_ok(p) || n < 1 || n > UP_NPAD_MAX || ld < n) return GOGP_EARG;
+  const int64_t total = (int64_t)p * (p + 1);
+  if (ht_len < (int64_t)p * ld || wt_len < (int64_t)p * ld || alpha_len < n || ag_len < total ||
+      part_len < (int64_t)basis_gram_slabs(n) * total)
+    return GOGP_EARG;
+  return fin_run(device, arrs, [&](double **d) { launch_basis_gram(0, d[0], d[1], ld, d[2], n, p, d[3], d[4]); });
+}
+
+extern "C" int gogp_test_basis_finish(int device, const double *Ag, int64_t ag_len, int p, double *LA, int64_t la_len,
+                                      double *Ainv, int64_t ainv_len, double *beta, int64_t beta_len, double *scal,
+                                      int64_t scal_len, double *info, int64_t info_len) {
+  const std::initializer_list<FinArr> arrs = {{Ag, ag_len, false}, {LA, la_len, true}, {Ainv, ainv_len, true},
+                                              {beta, beta_len, true}, {scal, scal_len, true}};
+  if (!fin_have(arrs) || !info || info_len < 1 || !basis_p_ok(p)) return GOGP_EARG;
+  const int64_t pp = (int64_t)p * p;
+  if (ag_len < pp + p || la_len < pp || ainv_len < pp || beta_len < p || scal_len < 2) return GOGP_EARG;
+  // the info word is a long long on the device: it travels in the caller's double and is converted on the way back
+  const std::initializer_list<FinArr> all = {{Ag, ag_len, false}, {LA, la_len, true}, {Ainv, ainv_len, true},
+                                             {beta, beta_len, true}, {scal, scal_len, true}, {info, info_len, true}};
+  const int rc = fin_run(device, all, [&](double **d) {
+    launch_basis_finish(0, d[0], p, d[1], d[2], d[3], d[4], reinterpret_cast<long long *>(d[5]));
+  });
+  if (rc != GOGP_OK) return rc;
+  long long word;
+  memcpy(&word, info, sizeof word);
+  info[0] = (double)word;
+  return GOGP_OK;
+}
+
+extern "C" int gogp_test_basis_cols(int device, const double *Wt, int64_t wt_len, int64_t ld, int64_t n, int p,
+                                    const double *LA, int64_t la_len, const double *beta, int64_t beta_len,
+                                    const double *alpha, int64_t alpha_len, double *Ct, int64_t ct_len) {
+  const std::initializer_list<FinArr> arrs = {{Wt, wt_len, false}, {LA, la_len, false}, {beta, beta_len, false},
+                                              {alpha, alpha_len, false}, {Ct, ct_len, true}};
+  if (!fin_have(arrs) || !basis_p_ok(p) || n < 1 || ld < n || ld > UP_NPAD_MAX) return GOGP_EARG;
+  const int64_t rows = (p + 1 + 3) / 4 * 4;
+  if (wt_len < (int64_t)p * ld || la_len < (int64_t)p * p || beta_len < p || alpha_len < n || ct_len < rows * ld)
+    return GOGP_EARG;
+  return fin_run(device, arrs, [&](double **d) { launch_basis_cols(0, d[0], ld, n, p, d[1], d[2], d[3], d[4]); });
+}
+
+extern "C" int gogp_test_basis_predict(int device, const double *Hz, int64_t hz_len, const double *KW, int64_t kw_len,
+                                       int64_t ldkw, int64_t m, int p, const double *beta, int64_t beta_len,
+                                       const double *Ainv, int64_t ainv_len, const double *mu0, int64_t mu0_len,
+                                       const double *prior, int64_t prior_len, const double *q, int64_t q_len, double *mu,
+                                       int64_t mu_len, double *sigma, int64_t sigma_len) {
+  const bool ws = sigma != nullptr;
+  if ((!ws && sigma_len != 0) || !basis_p_ok(p) || m < 1 || m > FIN_M_MAX || ldkw < p) return GOGP_EARG;
+  if (hz_len < m * p || kw_len < (m - 1) * ldkw + p || beta_len < p || ainv_len < (int64_t)p * p || mu0_len < m ||
+      prior_len < m || q_len < m || mu_len < m || (ws && sigma_len < m))
+    return GOGP_EARG;
+  if (ws) {
+    const std::initializer_list<FinArr> arrs = {{Hz, hz_len, false}, {KW, kw_len, false}, {beta, beta_len, false},
+                                                {Ainv, ainv_len, false}, {mu0, mu0_len, false}, {prior, prior_len, false},
+                                                {q, q_len, false}, {mu, mu_len, true}, {sigma, sigma_len, true}};
+    if (!fin_have(arrs)) return GOGP_EARG;
+    return fin_run(device, arrs, [&](double **d) {
+      launch_basis_predict(0, d[0], d[1], ldkw, m, p, d[2], d[3], d[4], d[5], d[6], d[7], d[8]);
+    });
+  }
+  const std::initializer_list<FinArr> arrs = {{Hz, hz_len, false}, {KW, kw_len, false}, {beta, beta_len, false},
+                                              {Ainv, ainv_len, false}, {mu0, mu0_len, false}, {prior, prior_len, false},
+                                              {q, q_len, false}, {mu, mu_len, true}};
+  if (!fin_have(arrs)) return GOGP_EARG;
+  return fin_run(device, arrs, [&](double **d) {
+    launch_basis_predict(0, d[0], d[1], ldkw, m, p, d[2], d[3], d[4], d[5], d[6], d[7], nullptr);
+  });
 }

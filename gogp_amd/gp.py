@@ -562,6 +562,72 @@ class GP:
         self._check(_lib.lib().gogp_multi_produce(self._h, _dp(z) if m else None, m, _dp(buf), _dp(sigma) if m else None))
         return mu, sigma
 
+    # ---- explicit basis functions: a marginalised linear mean (no reference counterpart) ----
+    def SetBasis(self, H) -> None:
+        """The basis functions of a mean h(x)^T beta at the process's inputs (n x p, p <= 64, p < n; gogp_basis_set;
+        gogp_amd.basis builds such matrices); beta is integrated out under a flat prior (Rasmussen & Williams section
+        2.7).  The basis belongs to the data on the device: the full Observe form, Append, Remove and assigning X / Y
+        drop it.  ``None`` clears it.  fp64, unsharded handles only.  Option "basis_symm" (-1 | 0 | 1) chooses how
+        K^-1 H is formed: from the explicit K^-1 where a gradient has left it on the device (the default), or always
+        from the factor (0) / from K^-1 (1)."""
+        L = _lib.lib()
+        if H is None:
+            self._check(L.gogp_basis_set(self._h, None, 0, 0))
+            self._p = 0
+            return
+        self._push_data()
+        ha = _arr(H)
+        n = len(self._Y)
+        if ha.ndim == 1:
+            ha = ha.reshape(n, -1) if n else ha.reshape(0, ha.size)
+        if ha.ndim != 2:
+            raise ValueError("SetBasis: H must be n x p")
+        ha = np.ascontiguousarray(ha)
+        buf = ha if ha.size else np.zeros(1)
+        self._check(L.gogp_basis_set(self._h, _dp(buf), ha.shape[0], ha.shape[1]))
+        self._p = ha.shape[1]
+
+    def BasisLML(self) -> float:
+        """The log marginal likelihood with beta integrated out (R&W eq. 2.45 in the flat-prior limit) at the
+        parameters of the last Absorb / Observe / restore (gogp_basis_lml)."""
+        v = ctypes.c_double(0.0)
+        self._check(_lib.lib().gogp_basis_lml(self._h, ctypes.byref(v)))
+        return v.value
+
+    def BasisGradient(self) -> np.ndarray:
+        """d BasisLML / d log theta, one entry per hyperparameter (gogp_basis_gradient)."""
+        g = np.zeros(self._ns + self._nn)
+        self._check(_lib.lib().gogp_basis_gradient(self._h, _dp(g), g.size))
+        return g
+
+    def BasisBeta(self):
+        """(beta, cov): the estimate of the mean's coefficients, p entries, and its covariance (H^T K^-1 H)^-1, p x p
+        (gogp_basis_get_beta)."""
+        p = max(getattr(self, "_p", 0), 1)
+        beta, cov = np.zeros(p), np.zeros((p, p))
+        self._check(_lib.lib().gogp_basis_get_beta(self._h, _dp(beta), _dp(cov)))
+        return beta, cov
+
+    @property
+    def BasisAlpha(self) -> np.ndarray:
+        """alpha~ = K^-1 (y - H beta), n entries (gogp_basis_get_alpha)."""
+        a = np.zeros(max(int(_lib.lib().gogp_n(self._h)), 1))
+        self._check(_lib.lib().gogp_basis_get_alpha(self._h, _dp(a)))
+        return a
+
+    def BasisProduce(self, x, Hz):
+        """(mu, sigma) at the test points ``x`` whose basis functions are the rows of ``Hz`` (m x p): Produce's mean plus
+        the mean's contribution, and the standard deviation widened by the uncertainty of beta (gogp_basis_produce)."""
+        z = _arr(x).reshape(-1, self.NDim)
+        m = len(z)
+        hz = np.ascontiguousarray(_arr(Hz).reshape(m, -1)) if m else np.zeros((0, 0))
+        if m and hz.shape[1] != getattr(self, "_p", 0):
+            raise ValueError("BasisProduce: Hz must be m x p")
+        mu, sigma = np.zeros(m), np.zeros(m)
+        self._check(_lib.lib().gogp_basis_produce(self._h, _dp(z) if m else None, _dp(hz) if m else None, m,
+                                                  _dp(mu) if m else None, _dp(sigma) if m else None))
+        return mu, sigma
+
     # ---- sparse: the collapsed bound on M inducing points (no reference counterpart) ----
     def SetSparse(self, X, Y, U) -> None:
         """Data of the inducing-point approximation (gogp_sparse_set_data): N observations X (N x NDim), Y and
@@ -1072,6 +1138,34 @@ class MultiModel:
 
     def Gradient(self) -> np.ndarray:
         g = self.gp.MultiGradient()
+        if self.Priors is not None:
+            self.Priors.Observe(self._x)
+            pg = np.asarray(self.Priors.Gradient(), dtype=float)
+            g[:len(pg)] += pg
+        return g
+
+
+class BasisModel:
+    """Model with GP.BasisLML in the place of the LML: Observe(x) runs gp.Observe(x) and returns GP.BasisLML() (+ the log
+    prior), Gradient() returns GP.BasisGradient() (+ the prior's).  optimize.lbfgs and optimize.Adam.Step then fit the
+    hyperparameters (x = log theta, no observations in x) with the coefficients of the mean of GP.SetBasis integrated
+    out.  As with MultiModel the batched line search is not offered: the GP is ``gp`` here, not ``GP``."""
+
+    def __init__(self, gp: GP, Priors=None):
+        self.gp = gp
+        self.Priors = Priors
+        self._x = None
+
+    def Observe(self, x) -> float:
+        self._x = _arr(x).reshape(-1).copy()
+        if self._x.size != self.gp._ns + self.gp._nn:
+            raise ValueError("len(x): the basis objective takes the hyperparameters only")
+        self.gp.Observe(self._x)
+        v = self.gp.BasisLML()
+        return v + self.Priors.Observe(self._x) if self.Priors is not None else v
+
+    def Gradient(self) -> np.ndarray:
+        g = self.gp.BasisGradient()
         if self.Priors is not None:
             self.Priors.Observe(self._x)
             pg = np.asarray(self.Priors.Gradient(), dtype=float)
@@ -1658,6 +1752,16 @@ def finish_check(which: str, device: int = -1, **args):
 def laplace_kernel_check(which: str, device: int = -1, **args):
     """finish_check for the kernels of the Laplace approximation (_lib.LAPLACE_HOOKS)."""
     return _table_check(_lib.LAPLACE_HOOKS, which, device, args, "laplace_kernel_check")
+
+
+def basis_kernel_check(which: str, device: int = -1, **args):
+    """finish_check for the kernels of the explicit basis functions (_lib.BASIS_HOOKS)."""
+    return _table_check(_lib.BASIS_HOOKS, which, device, args, "basis_kernel_check")
+
+
+def basis_slabs(n: int):
+    """(symm, gram): the slabs launch_basis_symm and launch_basis_gram split n observations into."""
+    return int(_lib.hooks().gogp_test_basis_symm_slabs(n)), int(_lib.hooks().gogp_test_basis_gram_slabs(n))
 
 
 def _table_check(table, which: str, device: int, args, caller: str):

@@ -351,6 +351,59 @@ class GP {
     return gogp_sparse_produce(h_, flat.data(), (int64_t)x.size(), mu.data(), sigma.data()) == GOGP_OK;
   }
 
+  // Explicit basis functions (gogp_basis_*): a mean h(x)^T beta with beta integrated out under a flat prior (Rasmussen &
+  // Williams section 2.7); no reference counterpart.  SetBasis: H row-major n x p, n = Y.size(), p <= GOGP_BASIS_MAX_P,
+  // p < n (pending X / Y are uploaded first; p == 0 clears); the basis is dropped by whatever replaces or resizes the data.
+  void SetBasis(const std::vector<double> &H, int p) {
+    if (p == 0) {
+      check(gogp_basis_set(h_, nullptr, 0, 0));
+      p_ = 0;
+      return;
+    }
+    check(push());
+    if (p < 0 || H.size() != Y.size() * (size_t)p) throw Error(GOGP_EARG, "len(H)");
+    const double none = 0.0;
+    check(gogp_basis_set(h_, H.empty() ? &none : H.data(), (int64_t)Y.size(), p));
+    p_ = p;
+  }
+  // the log marginal likelihood with beta integrated out, at the parameters of the last Absorb / Observe
+  double BasisLML() {
+    double lml = 0.0;
+    check(gogp_basis_lml(h_, &lml));
+    return lml;
+  }
+  // d BasisLML / d log theta, one entry per hyperparameter
+  std::vector<double> BasisGradient() {
+    std::vector<double> g(ThetaSimil.size() + ThetaNoise.size(), 0.0);
+    check(gogp_basis_gradient(h_, g.data(), (int64_t)g.size()));
+    return g;
+  }
+  // beta (p) and its covariance (H^T K^-1 H)^-1 (row-major p x p)
+  std::vector<double> BasisBeta(std::vector<double> &cov) {
+    std::vector<double> beta((size_t)p_ + 1, 0.0);
+    cov.assign((size_t)p_ * (size_t)p_ + 1, 0.0);
+    check(gogp_basis_get_beta(h_, beta.data(), cov.data()));
+    beta.pop_back();
+    cov.pop_back();
+    return beta;
+  }
+  // alpha~ = K^-1 (y - H beta)
+  std::vector<double> BasisAlpha() {
+    std::vector<double> a((size_t)gogp_n(h_) + 1, 0.0);
+    check(gogp_basis_get_alpha(h_, a.data()));
+    a.pop_back();
+    return a;
+  }
+  // mu and sigma at the test points x whose basis functions are the rows of Hz (row-major x.size() x p)
+  bool BasisProduce(const std::vector<std::vector<double>> &x, const std::vector<double> &Hz, std::vector<double> &mu,
+                    std::vector<double> &sigma) {
+    if (Hz.size() != x.size() * (size_t)p_) throw Error(GOGP_EARG, "len(Hz)");
+    std::vector<double> flat = pack(x);
+    mu.assign(x.size(), 0.0);
+    sigma.assign(x.size(), 0.0);
+    return gogp_basis_produce(h_, flat.data(), Hz.data(), (int64_t)x.size(), mu.data(), sigma.data()) == GOGP_OK;
+  }
+
   // Sparse multi-output (gogp_sparse_multi_*): T <= GOGP_SPARSE_MULTI_MAX_T output columns at the inputs of SetSparse on
   // one pass over the data; no reference counterpart.  SetSparseOutputs: Yt row-major N x T with the N of SetSparse, kept
   // on the device as given; T == 0 clears.  SetSparse drops the outputs, SetInducing keeps them.
@@ -498,6 +551,7 @@ class GP {
   size_t last_len_ = 0;
   bool dirty_ = true;
   int T_ = 0;  // output columns of SetOutputs
+  int p_ = 0;  // basis columns of SetBasis
   size_t sparse_m_ = 0;  // inducing points of SetSparse
   int sparse_t_ = 0;     // output columns of SetSparseOutputs
 

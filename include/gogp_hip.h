@@ -371,6 +371,43 @@ int gogp_multi_gradient(gogp_handle *h, double *grad, int64_t len /* P */);
 int gogp_multi_get_alpha(gogp_handle *h, double *A /* n x T row-major */);
 int gogp_multi_produce(gogp_handle *h, const double *Z, int64_t m, double *mu /* m x T */, double *sigma /* m */);
 
+/* Explicit basis functions: a mean h(x)^T beta whose coefficients are integrated out under a flat prior (Rasmussen &
+ * Williams section 2.7, eq. 2.41 - 2.45 in the limit B^-1 -> 0); no reference counterpart (gp.GP has mean zero).  H is
+ * n x p, row i holding h(x_i); with K the handle's Gram matrix (noise included) and alpha = K^-1 y
+ *     W = K^-1 H,  A = H^T W = L_A L_A^T,  g = H^T alpha,  beta = A^-1 g,  cov(beta) = A^-1,  alpha~ = alpha - W beta,
+ *     lml_b = gogp_lml + 1/2 g^T beta - 1/2 log|A| + p/2 log 2 pi,
+ *     d lml_b / d log theta = 1/2 sum_ab (alpha~ alpha~^T + Q Q^T - K^-1)_ab dK_ab,  Q = W L_A^-T,
+ *     mu_b = mu_0 + R beta,  sigma_b^2 = sigma_0^2 + diag(R A^-1 R^T),  R = H_z - Kstar^T W  (mu_0, sigma_0: gogp_produce).
+ * gogp_basis_set copies H (n x p row-major, n == gogp_n(h), 1 <= p <= GOGP_BASIS_MAX_P, p < n, every entry finite) to
+ * the device; it needs data but no factorisation and touches nothing of the handle's own state.  p == 0 with H == NULL
+ * clears the basis.  It is dropped by whatever replaces or resizes the data (the list of gogp_multi_set_outputs), and
+ * the other calls then return GOGP_ESTATE until a basis is set again.
+ * The other calls work at the parameters of the last gogp_absorb / gogp_observe / gogp_set_factor, in every state in which
+ * gogp_multi_lml works; W, the factor of A, beta and alpha~ are computed on first need after a factorisation and kept.
+ * W = K^-1 H comes from the explicit K^-1 (one symmetric product on the matrix cores, basis.hip) where that matrix is on
+ * the device or on its way -- behind gogp_observe or any gradient -- and from the factor by two substitutions otherwise,
+ * so a gogp_basis_produce behind gogp_absorb or gogp_set_factor does not form an inverse; option "basis_symm" forces a
+ * route.  gogp_basis_gradient (`len` == P) forms K^-1 as gogp_gradient does where it is not there, one pass writes G =
+ * K^-1 - [Q | alpha~][Q | alpha~]^T and the kernels of gogp_gradient reduce it: every kernel family, ARD and the event
+ * discounts are covered; it is refused behind gogp_observe_full.  gogp_basis_get_beta: beta (p) and, unless NULL, its
+ * covariance A^-1 (p x p).  gogp_basis_get_alpha: alpha~ (n).  gogp_basis_produce: Hz is m x p row-major, the basis at
+ * the test points; sigma may be NULL, which saves the substitution; m == 0 is OK.
+ * The handle is left as a gogp_gradient (gogp_basis_produce: a gogp_produce) at this point would have left it, and two
+ * identical calls return identical bits (fixed-order sums, no atomics).
+ * GOGP_EARG: NULL pointers, n != gogp_n(h), p outside 1 .. GOGP_BASIS_MAX_P, n <= p, a non-finite entry of H or Hz,
+ * len != P, the full Observe form, a precision = 32 handle, "gradient_precision" = 32, a sharded handle.  GOGP_ECOND: a
+ * pivot of A is not positive and finite -- the basis columns are linearly dependent; gogp_last_error names the pivot.
+ * Device memory: H^T and W^T, 128 rows of npad doubles each, 68 rows for [Q | alpha~]^T, the slabs of the symmetric
+ * product (at most 16 x p x npad doubles); gogp_basis_gradient shares the npad x npad matrix of gogp_multi_gradient. */
+#define GOGP_BASIS_MAX_P 64
+int gogp_basis_set(gogp_handle *h, const double *H /* n x p row-major */, int64_t n, int32_t p);
+int gogp_basis_lml(gogp_handle *h, double *lml);
+int gogp_basis_gradient(gogp_handle *h, double *grad, int64_t len /* P */);
+int gogp_basis_get_beta(gogp_handle *h, double *beta /* p */, double *cov /* p x p, may be NULL */);
+int gogp_basis_get_alpha(gogp_handle *h, double *alpha /* n */);
+int gogp_basis_produce(gogp_handle *h, const double *Z, const double *Hz /* m x p */, int64_t m, double *mu,
+                       double *sigma /* m, may be NULL */);
+
 /* Sparse (inducing-point) approximation: the collapsed variational bound of Titsias (2009) for N observations (X, y) on
  * M <= GOGP_SPARSE_MAX_M inducing points U, with the handle's kernel; no reference counterpart.  It costs O(N M^2) and
  * O(M^2 + chunk M) device memory instead of O(N^3) and O(N^2), is a lower bound of the exact LML and equals it for
@@ -844,6 +881,9 @@ int gogp_profile_read_aux(gogp_handle *h, int cls, double *ms, int64_t *launches
  *   "produce_small_max" 0..64   gogp_produce with up to this many test points (fp32 path: up to 16 of them): ONE
  *                          persistent launch that reads the factor once (trsm_small.hip; float factors are widened in
  *                          registers, the sums are fp64) instead of the tile-kernel chain; 0: never  (default 64)
+ *   "basis_symm"   -1 | 0 | 1   gogp_basis_*: W = K^-1 H by the symmetric product with the explicit K^-1 (1: formed first
+ *                          where it is not there), by two substitutions through the factor (0), -1: the product where
+ *                          K^-1 is on the device or on its way, the substitutions otherwise       (default -1)
  *   "sparse_jitter_log10" -14..-2   gogp_sparse_*: eps = 10^value (absolute) on the diagonal of Kuu (default -8)
  *   "sparse_chunk" 256..65536, a multiple of 256   gogp_sparse_*: rows of X per pass         (default 8192)
  * No reference counterpart (gp.GP.Parallel, gp/gp.go:30-31, only switches goroutines on). */

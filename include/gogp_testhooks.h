@@ -248,6 +248,35 @@ int gogp_test_pcov(int device, const gogp_test_kparams *kparams, int ev, const d
 int gogp_test_multi_weight(int device, const double *At, int64_t at_len, int64_t ld, int T, const double *Kinv,
                            int64_t kinv_len, int64_t ldk, int64_t n, int64_t npad, double *G, int64_t g_len);
 
+/* ---- the kernels of basis.hip through their product launchers (tests/test_basis_kernels.py).  The rules of the hooks
+ * above: lengths count elements, every array goes to the device whole and every in / out array whole back, GOGP_EARG before
+ * the device is touched.  npad a multiple of 256, 1 <= n <= npad, 1 <= p <= GOGP_BASIS_MAX_P, p4 = p rounded up to 4.
+ * gogp_test_basis_symm_slabs / gram_slabs: the slabs the launchers split n observations into (no device is touched).
+ * basis_symm: Wt (in / out; at least p4 rows of ld >= npad) = (Kinv H)^T, of the symmetric Kinv (npad rows of ldk) only
+ * j <= i < n read; Ht: p rows of ld; part (in / out): slabs * p4 * ld.  Rows < p4 of Wt are written whole (ld columns).
+ * basis_gram: Ag (in / out; p (p + 1)) = Ht [Wt^T | alpha]; part: slabs * p (p + 1).  basis_finish: LA, Ainv (p p),
+ * beta (p), scal (2), info (1: 0 or the first bad pivot + 1, as a double; the others are then left as they were).
+ * basis_cols: Ct (in / out; (p + 1 rounded up to 4) rows of ld).  basis_predict: mu, sigma (m; sigma_len == 0 with
+ * sigma NULL: not computed); Hz m x p, KW m rows of ldkw >= p. */
+int gogp_test_basis_symm_slabs(int64_t n);
+int gogp_test_basis_gram_slabs(int64_t n);
+int gogp_test_basis_symm(int device, const double *Kinv, int64_t kinv_len, int64_t ldk, int64_t n, int64_t npad,
+                         const double *Ht, int64_t ht_len, int64_t ld, int p, double *part, int64_t part_len, double *Wt,
+                         int64_t wt_len);
+int gogp_test_basis_gram(int device, const double *Ht, int64_t ht_len, const double *Wt, int64_t wt_len, int64_t ld,
+                         const double *alpha, int64_t alpha_len, int64_t n, int p, double *part, int64_t part_len, double *Ag,
+                         int64_t ag_len);
+int gogp_test_basis_finish(int device, const double *Ag, int64_t ag_len, int p, double *LA, int64_t la_len, double *Ainv,
+                           int64_t ainv_len, double *beta, int64_t beta_len, double *scal, int64_t scal_len, double *info,
+                           int64_t info_len);
+int gogp_test_basis_cols(int device, const double *Wt, int64_t wt_len, int64_t ld, int64_t n, int p, const double *LA,
+                         int64_t la_len, const double *beta, int64_t beta_len, const double *alpha, int64_t alpha_len,
+                         double *Ct, int64_t ct_len);
+int gogp_test_basis_predict(int device, const double *Hz, int64_t hz_len, const double *KW, int64_t kw_len, int64_t ldkw,
+                            int64_t m, int p, const double *beta, int64_t beta_len, const double *Ainv, int64_t ainv_len,
+                            const double *mu0, int64_t mu0_len, const double *prior, int64_t prior_len, const double *q,
+                            int64_t q_len, double *mu, int64_t mu_len, double *sigma, int64_t sigma_len);
+
 /* launch_sparse_syrk (sparse.hip): Bacc (in / out; Mp rows of ldb) += Vt^T Vt on the whole lower 64 x 64 tiles of Mp x Mp and
  * r (in / out; Mp doubles) += Vt^T y.  Vt: `rows` (1 .. 65536) rows of ld doubles, Mp columns read, of which the columns
  * >= M count as exact zeros; Mp a multiple of 64 up to GOGP_SPARSE_MAX_M, 1 <= M <= Mp. */
