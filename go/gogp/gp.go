@@ -209,12 +209,70 @@ func (gp *GP) defaults() { // gp/gp.go:45-57
 	}
 }
 
-// Absorb absorbs observations into the process (gp/gp.go:80-87).
-func (gp *GP) Absorb(x [][]float64, y []float64) (err error) {
+// SetNoiseVariances sets known noise variances, one per observation: K = k(X, X) + sigma^2(theta) I +
+// diag(v), every v[i] finite and >= 0 (gogp_set_noise_variances; no reference counterpart).  nil
+// clears them.  Stored results are dropped: Absorb or Observe again.  The variances belong to the
+// data: re-assigning X / Y (and so Absorb) clears them, AppendNoisy / Append and Remove carry them.
+func (gp *GP) SetNoiseVariances(v []float64) error {
+	if v == nil {
+		if gp.changed() {
+			return nil // nothing of the current data is on the device yet
+		}
+		return gp.err(C.gogp_set_noise_variances(gp.handle(), nil, 0))
+	}
+	if len(v) != len(gp.Y) {
+		return fmt.Errorf("gogp: SetNoiseVariances: one variance per observation")
+	}
+	if err := gp.pushData(); err != nil {
+		return err
+	}
+	return gp.err(C.gogp_set_noise_variances(gp.handle(), dptr(v), C.int64_t(len(v))))
+}
+
+// NoiseVariances returns what the device holds for the current observations (zeros when none are set).
+func (gp *GP) NoiseVariances() ([]float64, error) {
+	if gp.changed() {
+		return make([]float64, len(gp.Y)), nil
+	}
+	v := make([]float64, int(C.gogp_n(gp.handle())))
+	if err := gp.err(C.gogp_get_noise_variances(gp.handle(), dptr(v))); err != nil {
+		return nil, err
+	}
+	return v, nil
+}
+
+// NoiseVariancesGradient returns dLML/dv[i] = 1/2 (Alpha[i]^2 - [K^-1]_ii) at the current parameters
+// and variances (gogp_noise_variances_gradient); also with no variances set.
+func (gp *GP) NoiseVariancesGradient() ([]float64, error) {
+	dv := make([]float64, int(C.gogp_n(gp.handle())))
+	if err := gp.err(C.gogp_noise_variances_gradient(gp.handle(), dptr(dv))); err != nil {
+		return nil, err
+	}
+	return dv, nil
+}
+
+// AbsorbNoisy is Absorb with the observations' noise variances v (SetNoiseVariances).
+func (gp *GP) AbsorbNoisy(x [][]float64, y, v []float64) error {
+	return gp.absorb(x, y, v)
+}
+
+// Absorb absorbs observations into the process (gp/gp.go:80-87).  Noise variances of the previous
+// data are cleared.
+func (gp *GP) Absorb(x [][]float64, y []float64) error {
+	return gp.absorb(x, y, nil)
+}
+
+func (gp *GP) absorb(x [][]float64, y, v []float64) (err error) {
 	gp.defaults()
 	gp.X, gp.Y = x, y
+	gp.dirty = true // also when the same slices come again: the upload drops the old variances
 	if err = gp.pushData(); err != nil {
 		return err
+	}
+	if v != nil {
+		if err = gp.SetNoiseVariances(v); err != nil {
+			return err
+		}
 	}
 	tn := gp.ThetaNoise
 	if len(tn) == 0 {
@@ -235,9 +293,15 @@ func (gp *GP) Absorb(x [][]float64, y []float64) (err error) {
 // No reference counterpart (tutorial/tutorial.go:118-142 refactorises every step).  An empty process
 // absorbs them at ThetaSimil / ThetaNoise.  When the enlarged matrix is not positive definite the
 // error is returned and the process is as it was.
-func (gp *GP) Append(x [][]float64, y []float64) (err error) {
+func (gp *GP) Append(x [][]float64, y []float64) error {
+	return gp.AppendNoisy(x, y, nil)
+}
+
+// AppendNoisy is Append with the new observations' noise variances v (gogp_append_noisy); nil: zeros.
+// With v on a process without variances the old rows get zeros.
+func (gp *GP) AppendNoisy(x [][]float64, y, v []float64) (err error) {
 	gp.defaults()
-	if len(x) != len(y) {
+	if len(x) != len(y) || (v != nil && len(v) != len(y)) {
 		return fmt.Errorf("gogp: len(x) != len(y)")
 	}
 	if len(gp.Y) == 0 {
@@ -262,7 +326,12 @@ func (gp *GP) Append(x [][]float64, y []float64) (err error) {
 	for i, row := range x {
 		copy(flat[i*gp.NDim:], row)
 	}
-	rc := C.gogp_append(gp.handle(), dptr(flat), dptr(y), C.int64_t(m))
+	var rc C.int
+	if v == nil {
+		rc = C.gogp_append(gp.handle(), dptr(flat), dptr(y), C.int64_t(m))
+	} else {
+		rc = C.gogp_append_noisy(gp.handle(), dptr(flat), dptr(y), dptr(v), C.int64_t(m))
+	}
 	if rc != C.GOGP_OK && rc != C.GOGP_ECOND {
 		return gp.err(rc)
 	}

@@ -149,6 +149,11 @@ SYMBOLS = [
     ("gogp_get_factor_diag", ctypes.c_int, [_h, _dp]),
     ("gogp_set_factor", ctypes.c_int, [_h, _dp, _dp, _dp, _dp]),
     ("gogp_append", ctypes.c_int, [_h, _dp, _dp, ctypes.c_int64]),
+    ("gogp_append_noisy", ctypes.c_int, [_h, _dp, _dp, _dp, ctypes.c_int64]),
+    ("gogp_noise_variances_check", ctypes.c_int, [_dp, _i64]),
+    ("gogp_set_noise_variances", ctypes.c_int, [_h, _dp, _i64]),
+    ("gogp_get_noise_variances", ctypes.c_int, [_h, _dp]),
+    ("gogp_noise_variances_gradient", ctypes.c_int, [_h, _dp]),
     ("gogp_remove", ctypes.c_int, [_h, ctypes.POINTER(_i64), ctypes.c_int64]),
     ("gogp_dist_grid", ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
     ("gogp_dist_unique_id", ctypes.c_int, [ctypes.c_void_p]),
@@ -231,6 +236,9 @@ HOOK_SYMBOLS = [
      + [ctypes.c_int, ctypes.c_int, _i64, _i64, _dp, _i64, _dp, _i64, _dp, _i64, _i64]),
     ("gogp_test_append_commit", ctypes.c_int,
      [ctypes.c_int, ctypes.POINTER(CKParams), ctypes.c_int, _dp, _i64, _dp, _i64, ctypes.c_int, _i64, _dp, _i64,
+      ctypes.c_int, _dp, _i64, _i64, _dp, _i64, ctypes.POINTER(ctypes.c_longlong)]),
+    ("gogp_test_nv_append_commit", ctypes.c_int,
+     [ctypes.c_int, ctypes.POINTER(CKParams), ctypes.c_int, _dp, _i64, _dp, _i64, _dp, _i64, ctypes.c_int, _i64, _dp, _i64,
       ctypes.c_int, _dp, _i64, _i64, _dp, _i64, ctypes.POINTER(ctypes.c_longlong)]),
     ("gogp_test_remove_gather", ctypes.c_int,
      [ctypes.c_int, _dp, _i64, _i64, ctypes.POINTER(ctypes.c_int), _i64, _i64, _dp, _i64, _i64]),
@@ -330,6 +338,18 @@ BASIS_HOOKS = {k: [tuple(t.split(":")) for t in v.split()] for k, v in _BASIS_SP
 HOOK_SYMBOLS += [("gogp_test_" + k, ctypes.c_int, [ctypes.c_int] + [t for _, kind in spec for t in _FINISH_CTYPES[kind]])
                  for k, spec in BASIS_HOOKS.items()]
 HOOK_SYMBOLS += [("gogp_test_basis_symm_slabs", ctypes.c_int, [_i64]), ("gogp_test_basis_gram_slabs", ctypes.c_int, [_i64])]
+
+
+#: the hooks of the kernels of the per-observation noise variances (tests/test_noise_variances_kernels.py), as
+#: gp.noise_variances_kernel_check reads them: the notation of _FINISH_SPEC (the append fold goes through
+#: gogp_test_nv_append_commit above: gp.nv_append_commit_check)
+_NOISEVAR_SPEC = {
+    "nv_diag_add": "A:o ld:l n:l npad:l v:a wcols:l",
+    "nv_gradient": "Kinv:a ld:l alpha:a n:l npad:l dv:o",
+}
+NOISEVAR_HOOKS = {k: [tuple(t.split(":")) for t in v.split()] for k, v in _NOISEVAR_SPEC.items()}
+HOOK_SYMBOLS += [("gogp_test_" + k, ctypes.c_int, [ctypes.c_int] + [t for _, kind in spec for t in _FINISH_CTYPES[kind]])
+                 for k, spec in NOISEVAR_HOOKS.items()]
 
 
 def build(force: bool = False) -> str:

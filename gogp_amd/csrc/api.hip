@@ -108,6 +108,11 @@ static void free_n_buffers(gogp_handle *h) {
   h->loo_mat.release();
   h->lap_ws.release();
   h->lap_observed = h->lap_grad_valid = h->lap_warm_valid = false;
+  (void)hipFree(h->nv);
+  h->nv = nullptr;
+  h->nv_cap = 0;
+  h->nv_set = false;
+  h->nv_ws.release();
   h->bcv_vec.release();
   h->bcv_s.release();
   h->multi_vec.release();
@@ -391,6 +396,7 @@ static int set_data_impl(gogp_handle *h, const double *X, const double *y, int64
   h->multi_T = 0;  // the outputs of gogp_multi_set_outputs belonged to the data that was replaced
   h->basis_p = 0;  // ... and so did the basis of gogp_basis_set
   h->basis_solved = false;
+  h->nv_set = false;  // ... and the variances of gogp_set_noise_variances
   if (n == 0) return GOGP_OK;
   // zero padding rows, then copy
   HIPCHK(h, hipMemsetAsync(h->dX, 0, ((size_t)h->npad * h->D + GOGP_MAX_NDIM) * sizeof(double), h->s));
@@ -1049,6 +1055,8 @@ struct Sweep {
       // a Laplace observe in progress: B = I + diag(sw) K diag(sw), right behind each part on its own stream
       if constexpr (!fp32) {
         if (h->lap_sw) launch_lap_scale_gram(sp, s, A, ld, h->n, npad, h->lap_sw, (int64_t)w0 * PANEL);
+        // per-observation noise variances: A_ii += v_i, each part behind the Gram launch that wrote its columns
+        if (h->nv_set) launch_nv_diag_add(sp, s, A, ld, h->n, h->nv, (int64_t)w0 * PANEL);
       }
     }
     // fp32 path, option "diag_fp64": the diagonal blocks leave the float matrix here -- widened once, every later
@@ -1268,7 +1276,8 @@ static int factorize_t(gogp_handle *h, bool eager) {
 // where the general path leaves it -- L, the block inverse, z, alpha, K^-1 (Observe) -- so Gradient, Produce, the factor
 // export and the lazy inverse after Absorb run unchanged; only Y = L^-T is not formed (nobody needs it once K^-1 exists).
 static inline bool tiny_ok(const gogp_handle *h) {
-  return h->tiny && !h->dist && h->prec == 64 && h->npad == PANEL && h->n <= TILE && !mixed_gradient(h);
+  // (tiny_eval_kernel builds its own Gram matrix: a handle with noise variances takes the general sweep)
+  return h->tiny && !h->dist && h->prec == 64 && h->npad == PANEL && h->n <= TILE && !mixed_gradient(h) && !h->nv_set;
 }
 static int tiny_factorize(gogp_handle *h, bool eager) {
   hipStream_t s = h->s;
@@ -1678,6 +1687,110 @@ extern "C" int gogp_loo_gradient(gogp_handle *h, double *grad, int64_t len) {
   return GOGP_OK;
 }
 
+// ---- per-observation noise variances (noisevar.hip) -------------------------------------------------------------------
+// K = k(X, X) + s2(theta) I + diag(v), v known per observation (no reference counterpart: gp.GP has one noise level).
+// Device state only: Sweep::build_gram adds v behind the Gram build, and everything behind the factorisation -- Produce,
+// the gradient, LOO, the multi-output and basis calls -- works from the factor, alpha and K^-1 and never looks at the
+// diagonal of K again.  gogp_append_noisy and gogp_remove, which do rebuild diagonal entries, carry v themselves.
+extern "C" int gogp_noise_variances_check(const double *v, int64_t n) {
+  if (n < 0 || (n > 0 && !v)) return GOGP_EARG;
+  for (int64_t i = 0; i < n; ++i)
+    if (!std::isfinite(v[i]) || v[i] < 0.0) return GOGP_EARG;
+  return GOGP_OK;
+}
+
+// NULL, or why this handle takes no noise variances
+static const char *nv_refusal(const gogp_handle *h) {
+  return h->prec == 32       ? "noise variances: not supported on a precision = 32 handle"
+         : mixed_gradient(h) ? "noise variances: not supported with gradient_precision = 32 (its closed-form scale "
+                               "component assumes K = c F + s2 I)"
+         : h->dist           ? "noise variances: not supported on a sharded handle"
+                             : nullptr;
+}
+
+// h->nv holds at least `cap` doubles; a new block is zero throughout (the old contents are not kept)
+static int nv_reserve(gogp_handle *h, int64_t cap) {
+  if (h->nv && h->nv_cap >= cap) return GOGP_OK;
+  (void)hipFree(h->nv);
+  h->nv = nullptr;
+  h->nv_cap = 0;
+  h->nv_set = false;
+  HIPCHK(h, hipMalloc(&h->nv, (size_t)cap * sizeof(double)));
+  h->nv_cap = cap;
+  return GOGP_OK;
+}
+
+extern "C" int gogp_set_noise_variances(gogp_handle *h, const double *v, int64_t n) {
+  if (!h) return GOGP_EARG;
+  const bool clear = !v && n == 0;
+  if (!clear)
+    if (const char *why = nv_refusal(h)) return fail(h, GOGP_EARG, why);
+  if (!h->have_data) return fail(h, GOGP_ESTATE, "set_noise_variances: no data (gogp_set_data)");
+  if (!clear) {
+    if (n != h->n) return fail(h, GOGP_EARG, "set_noise_variances: n must be gogp_n (one variance per observation)");
+    if (gogp_noise_variances_check(v, n) != GOGP_OK)
+      return fail(h, GOGP_EARG, "set_noise_variances: every variance must be finite and >= 0");
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  // nothing enqueued may still read the old variances; stored results (factor, alpha, K^-1) no longer match the matrix
+  for (hipStream_t q : work_streams(h)) HIPCHK(h, hipStreamSynchronize(q));
+  // (dropped first: a failed upload below leaves a handle without variances and without results, never one whose
+  // results belong to other variances than it holds)
+  h->factored = h->have_alpha = h->have_kinv = h->observed = h->grad_valid = false;
+  h->z_valid = false;
+  h->multi_solved = false;
+  h->basis_solved = false;
+  h->lap_observed = h->lap_grad_valid = false;
+  h->trtri_done = h->trtri_pending = h->alpha_pending = h->kinv_pending = false;
+  h->tinv_valid = h->tinv_pending = false;
+  h->nv_set = false;
+  if (clear || n == 0) return GOGP_OK;
+  const int rc = nv_reserve(h, std::max(h->cap_npad, h->npad));
+  if (rc != GOGP_OK) return rc;
+  HIPCHK(h, hipMemsetAsync(h->nv, 0, (size_t)h->nv_cap * sizeof(double), h->s));
+  HIPCHK(h, hipMemcpyAsync(h->nv, v, (size_t)n * sizeof(double), hipMemcpyHostToDevice, h->s));
+  HIPCHK(h, hipStreamSynchronize(h->s));
+  h->nv_set = true;
+  return GOGP_OK;
+}
+
+extern "C" int gogp_get_noise_variances(gogp_handle *h, double *v) {
+  if (!h) return GOGP_EARG;
+  if (!h->have_data) return fail(h, GOGP_ESTATE, "get_noise_variances: no data (gogp_set_data)");
+  if (h->n == 0) return GOGP_OK;
+  if (!v) return fail(h, GOGP_EARG, "get_noise_variances: NULL");
+  if (!h->nv_set) {
+    for (int64_t i = 0; i < h->n; ++i) v[i] = 0.0;
+    return GOGP_OK;
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipMemcpyAsync(v, h->nv, (size_t)h->n * sizeof(double), hipMemcpyDeviceToHost, h->s));
+  HIPCHK(h, hipStreamSynchronize(h->s));
+  return GOGP_OK;
+}
+
+// dLML/dv_i = 1/2 (alpha_i^2 - [K^-1]_ii): the preparation and the contract of gogp_loo -- K^-1 formed, nothing a later
+// call reads changed -- and one launch over the diagonal.  Holds with no variances set (the derivative at v = 0).
+extern "C" int gogp_noise_variances_gradient(gogp_handle *h, double *dv) {
+  if (!h) return GOGP_EARG;
+  if (const char *why = nv_refusal(h)) return fail(h, GOGP_EARG, why);
+  if (!h->have_data) return fail(h, GOGP_ESTATE, "noise_variances_gradient: no data (gogp_set_data)");
+  if (h->n == 0) return GOGP_OK;
+  if (!dv) return fail(h, GOGP_EARG, "noise_variances_gradient: NULL");
+  if (!h->factored) return fail(h, GOGP_ESTATE, "noise_variances_gradient: nothing absorbed");
+  HIPCHK(h, hipSetDevice(h->device));
+  int rc = compute_kinv(h);
+  if (rc == GOGP_OK) rc = ensure_alpha(h);
+  if (rc == GOGP_OK) rc = h->nv_ws.reserve(h, (size_t)std::max(h->npad, h->cap_npad) * sizeof(double));
+  if (rc != GOGP_OK) return rc;
+  hipStream_t s = h->s;
+  launch_nv_gradient(s, h->bufA, h->npad, h->alpha, h->n, h->nv_ws.as<double>());
+  HIPCHK(h, hipMemcpyAsync(dv, h->nv_ws.p, (size_t)h->n * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipStreamSynchronize(s));
+  HIPCHK(h, hipGetLastError());
+  return GOGP_OK;
+}
+
 // ---- leave-block-out cross-validation (blockcv.hip) -----------------------------------------------------------------
 // No reference counterpart.  The contract and the data flow of the LOO calls above, with consecutive blocks of rows
 // held out together: one in-LDS factorisation per group of blocks of K^-1's diagonal, and for the gradient one
@@ -1973,6 +2086,8 @@ extern "C" int gogp_observe_gradient_candidates(gogp_handle *h, int k, const dou
   if (k > GOGP_MAX_CANDIDATES) return fail(h, GOGP_EARG, "candidates: k > GOGP_MAX_CANDIDATES");
   if (len != h->P) return fail(h, GOGP_EARG, "len(x)");  // gp/gp.go:398-400
   if (!h->have_data) return fail(h, GOGP_ESTATE, "candidates: no data (gogp_set_data)");
+  if (h->nv_set)
+    return fail(h, GOGP_EARG, "candidates: not supported while noise variances are set (the arena slots' sweeps do not add them)");
   if (h->dist) {
     // Sharded handle: the k candidates are evaluated one after the other in the shards' own tiles (an arena of k more
     // shards is exactly what a sharded evaluation has no memory for, and at the sizes that are sharded one evaluation
@@ -4146,6 +4261,8 @@ extern "C" int gogp_laplace_observe(gogp_handle *h, int32_t lik, const double *x
   int rc = lap_refuse(h, "laplace_observe");
   if (rc != GOGP_OK) return rc;
   if (!h->have_data) return fail(h, GOGP_ESTATE, "laplace_observe: no data (gogp_set_data)");
+  if (h->nv_set)
+    return fail(h, GOGP_EARG, "laplace_observe: not supported while noise variances are set (its matrix-free products with K do not carry them)");
   HIPCHK(h, hipSetDevice(h->device));
   std::vector<double> th(h->P > 0 ? h->P : 1);
   for (int i = 0; i < h->P; ++i) th[i] = exp(x[i]);
@@ -4506,11 +4623,19 @@ static int finish_factor_update(gogp_handle *h, const double *L, int64_t ld, int
   return fr.rc;
 }
 
-extern "C" int gogp_append(gogp_handle *h, const double *X2, const double *y2, int64_t m) {
+// v2: the new rows' noise variances (gogp_set_noise_variances), NULL: zeros.  They reach the new block's diagonal as
+// -v2 folded into the first slab's partial sums (noisevar.hip), so that the commit kernel is today's; the handle's
+// vector grows with the data's buffers, and a failed call leaves it as it was.
+extern "C" int gogp_append_noisy(gogp_handle *h, const double *X2, const double *y2, const double *v2, int64_t m) {
   if (!h) return GOGP_EARG;
   if (m < 0) return fail(h, GOGP_EARG, "append: m < 0");
   if (m == 0) return GOGP_OK;
   if (!X2 || !y2) return fail(h, GOGP_EARG, "append: NULL");
+  if (v2) {
+    if (const char *why = nv_refusal(h)) return fail(h, GOGP_EARG, why);
+    if (gogp_noise_variances_check(v2, m) != GOGP_OK)
+      return fail(h, GOGP_EARG, "append: every noise variance must be finite and >= 0");
+  }
   if (h->prec == 32)
     return fail(h, GOGP_EARG, "append: not supported on a precision = 32 handle (the update is fp64 throughout)");
   if (h->dist) return fail(h, GOGP_EARG, "append: not supported on a sharded handle");
@@ -4526,7 +4651,8 @@ extern "C" int gogp_append(gogp_handle *h, const double *X2, const double *y2, i
     const std::vector<double> ts = h->theta_s, tn = h->theta_n;
     int rc = gogp_set_data(h, X2, y2, m);
     if (rc != GOGP_OK) return rc;
-    rc = gogp_absorb(h, ts.data(), tn.data());
+    if (v2) rc = gogp_set_noise_variances(h, v2, m);
+    if (rc == GOGP_OK) rc = gogp_absorb(h, ts.data(), tn.data());
     if (rc != GOGP_OK && rc != GOGP_ECOND) {  // empty again
       const int64_t np = h->notpd;
       const std::string e = h->err;
@@ -4595,6 +4721,22 @@ extern "C" int gogp_append(gogp_handle *h, const double *X2, const double *y2, i
   h->nblk = (int)(npad1 / TILE);
   const int64_t ld = npad1;
   int64_t ncur = n0, touched = n0;  // rows < touched of the new factor rows may have been written
+  // the noise variances: [the old rows' (zeros if none were set) | v2 (zeros if NULL) | zeros], in place where the
+  // block is large enough, else in a new one of the data buffers' capacity; the old block lives until the call succeeds
+  const bool nv_was_set = h->nv_set, nv_use = nv_was_set || v2 != nullptr;
+  double *const nv_old = h->nv;
+  const int64_t nv_old_cap = h->nv_cap;
+  bool nv_fresh = false;
+  auto nv_rollback = [&]() {
+    if (nv_fresh) {
+      (void)hipFree(h->nv);
+      h->nv = nv_old;
+      h->nv_cap = nv_old_cap;
+    } else if (nv_use && h->nv && h->nv_cap > n0) {
+      (void)hipMemsetAsync(h->nv + n0, 0, (size_t)std::min<int64_t>(m, h->nv_cap - n0) * sizeof(double), s);
+    }
+    h->nv_set = nv_was_set;
+  };
   // put everything back as it was before the call (the factor itself was never overwritten)
   auto rollback = [&]() {
     for (hipStream_t q : {s, h->s2}) (void)hipStreamSynchronize(q);
@@ -4609,6 +4751,7 @@ extern "C" int gogp_append(gogp_handle *h, const double *X2, const double *y2, i
       (void)hipMemsetAsync(h->dy + n0, 0, (size_t)(npad1 - n0) * sizeof(double), s);
       (void)hipMemsetAsync(h->z + n0, 0, (size_t)(npad1 - n0) * sizeof(double), s);
     }
+    nv_rollback();
     h->bufA = old.bufA;
     h->bufL = old.bufL;
     h->n = n0;
@@ -4619,6 +4762,30 @@ extern "C" int gogp_append(gogp_handle *h, const double *X2, const double *y2, i
     (void)hipStreamSynchronize(s);
     free_m_buffers(h);  // sized for the npad that did not come to be
   };
+  if (nv_use) {
+    const int64_t need = std::max(h->cap_npad, npad1);
+    hipError_t e = hipSuccess;
+    if (!h->nv || h->nv_cap < need) {
+      double *q = nullptr;
+      e = hipMalloc(&q, (size_t)need * sizeof(double));
+      if (e == hipSuccess) {
+        h->nv = q;
+        h->nv_cap = need;
+        nv_fresh = true;
+        e = hipMemsetAsync(q, 0, (size_t)need * sizeof(double), s);
+      }
+      if (e == hipSuccess && nv_was_set) e = hipMemcpyAsync(q, nv_old, (size_t)n0 * sizeof(double), hipMemcpyDeviceToDevice, s);
+    } else if (!nv_was_set) {  // a block of earlier data: nothing in it holds
+      e = hipMemsetAsync(h->nv, 0, (size_t)h->nv_cap * sizeof(double), s);
+    }
+    if (e == hipSuccess && v2) e = hipMemcpyAsync(h->nv + n0, v2, (size_t)m * sizeof(double), hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      rollback();
+      return fail(h, e == hipErrorOutOfMemory ? GOGP_ENOMEM : GOGP_EHIP, "append: the noise variances could not be stored");
+    }
+    h->nv_set = true;
+  }
   HIPCHK(h, hipMemcpyAsync(h->dX + (size_t)n0 * D, X2, (size_t)m * D * sizeof(double), hipMemcpyHostToDevice, s));
   HIPCHK(h, hipMemcpyAsync(h->dy + n0, y2, (size_t)m * sizeof(double), hipMemcpyHostToDevice, s));
   HIPCHK(h, hipMemsetAsync(h->info, 0, sizeof(long long), s));
@@ -4653,6 +4820,7 @@ extern "C" int gogp_append(gogp_handle *h, const double *X2, const double *y2, i
     gogp::TsSolution v0 = gogp::trsm_small_solution(npc, 0, m1, h->small_ws.p), v1 = v0;
     if (mc > 32) v1 = gogp::trsm_small_solution(npc, 32, mc - 32, h->small_ws.as<char>() + one);
     launch_append_gram(s, v0, v1, m1, mc, npc, ncur, h->z, part, Lrow, ld);
+    if (v2) launch_nv_append_fold(s, part, h->nv + ncur, mc);
     launch_append_commit(s, h->devP, Xc, yc, mc, ncur, part, (int)(npc / PANEL), Lrow, ld, h->z + ncur, h->info, h->ev());
     HIPCHK(h, hipMemcpyAsync(h->hscal + HS_INFO, h->info, sizeof(long long), hipMemcpyDeviceToHost, s));
     HIPCHK(h, hipStreamSynchronize(s));
@@ -4671,6 +4839,7 @@ extern "C" int gogp_append(gogp_handle *h, const double *X2, const double *y2, i
       vr.width = (int)ld;
       HIPCHK(h, hipMemsetAsync(h->info, 0, sizeof(long long), s));
       launch_append_gram(s, vr, vr, mc, mc, npc, ncur, h->z, part, Lrow, ld);
+      if (v2) launch_nv_append_fold(s, part, h->nv + ncur, mc);
       launch_append_commit(s, h->devP, Xc, yc, mc, ncur, part, nbc, Lrow, ld, h->z + ncur, h->info, h->ev());
       HIPCHK(h, hipMemcpyAsync(h->hscal + HS_INFO, h->info, sizeof(long long), hipMemcpyDeviceToHost, s));
       HIPCHK(h, hipStreamSynchronize(s));
@@ -4692,10 +4861,15 @@ extern "C" int gogp_append(gogp_handle *h, const double *X2, const double *y2, i
   }
   h->n = n1;
   return finish_factor_update(h, h->bufL, ld, n1, s, [&] {
+    if (nv_fresh) (void)hipFree(nv_old);
     if (!grow) return;
     nbufs_free(old);
     drop_cand_graph(h);
   });
+}
+
+extern "C" int gogp_append(gogp_handle *h, const double *X2, const double *y2, int64_t m) {
+  return gogp_append_noisy(h, X2, y2, nullptr, m);
 }
 
 // ---- remove ---------------------------------------------------------------------------------------
@@ -4755,17 +4929,18 @@ extern "C" int gogp_remove(gogp_handle *h, const int64_t *idx, int64_t m) {
   }
   const size_t nints = (size_t)((n1 + m + 1) / 2) * 2;
   const size_t need = nints * sizeof(int) +
-                      ((size_t)gogp::REMOVE_W * npad1 + (size_t)npad1 * TILE + (size_t)npad1 * (D + 1)) * sizeof(double);
+                      ((size_t)gogp::REMOVE_W * npad1 + (size_t)npad1 * TILE + (size_t)npad1 * (D + 2)) * sizeof(double);
   rc = h->rm_ws.reserve(h, need);
   if (rc != GOGP_OK) return rc;
   int *dmap = h->rm_ws.as<int>(), *drem = dmap + n1;
   double *W = reinterpret_cast<double *>(dmap + nints), *snap = W + (size_t)gogp::REMOVE_W * npad1;
-  double *Xt = snap + (size_t)npad1 * TILE, *yt = Xt + (size_t)npad1 * D;
+  double *Xt = snap + (size_t)npad1 * TILE, *yt = Xt + (size_t)npad1 * D, *vt = yt + npad1;  // (vt: the noise variances)
   double *Lold = h->bufL, *Lnew = h->bufA;
   HIPCHK(h, hipMemcpyAsync(dmap, hmap.data(), (size_t)(n1 + m) * sizeof(int), hipMemcpyHostToDevice, s));
   launch_remove_gather(s, Lold, npad0, dmap, n1, Lnew, npad1);
   launch_remove_rows(s, h->dX, dmap, n1, D, Xt);
   launch_remove_rows(s, h->dy, dmap, n1, 1, yt);
+  if (h->nv_set) launch_remove_rows(s, h->nv, dmap, n1, 1, vt);
   const int mw = m <= gogp::REMOVE_W_SMALL ? gogp::REMOVE_W_SMALL : gogp::REMOVE_W;
   const int64_t first = std::min<int64_t>(idx[0], n1 - 1);  // the first column the call can change
   for (int64_t off = 0; off < m; off += mw) {
@@ -4782,6 +4957,10 @@ extern "C" int gogp_remove(gogp_handle *h, const int64_t *idx, int64_t m) {
   HIPCHK(h, hipMemcpyAsync(h->dy, yt, (size_t)n1 * sizeof(double), hipMemcpyDeviceToDevice, s));
   HIPCHK(h, hipMemsetAsync(h->dX + (size_t)n1 * D, 0, ((size_t)(npad0 - n1) * D + GOGP_MAX_NDIM) * sizeof(double), s));
   HIPCHK(h, hipMemsetAsync(h->dy + n1, 0, (size_t)(npad0 - n1) * sizeof(double), s));
+  if (h->nv_set) {
+    HIPCHK(h, hipMemcpyAsync(h->nv, vt, (size_t)n1 * sizeof(double), hipMemcpyDeviceToDevice, s));
+    HIPCHK(h, hipMemsetAsync(h->nv + n1, 0, (size_t)(npad0 - n1) * sizeof(double), s));
+  }
   const int np1 = (int)(npad1 / PANEL);
   const size_t blk = (size_t)PANEL * PANEL;
   for (int b = restride ? 0 : (int)(first / PANEL); b < np1; ++b)
@@ -4935,6 +5114,8 @@ extern "C" int gogp_set_option(gogp_handle *h, const char *name, int64_t value) 
     // above the 1e-4 the reference checks its own gradient to, gp_test.go:170,248) -- refused rather than shipped.
     if (value == 32 && (h->desc.nterms != 1 || h->desc.terms[0].scale_idx < 0))
       return fail(h, GOGP_EARG, "gradient_precision = 32 is offered for one-term kernels with an output scale only");
+    if (value == 32 && h->nv_set)  // its closed-form scale component assumes K = c F + s2 I
+      return fail(h, GOGP_EARG, "gradient_precision = 32 is not supported while noise variances are set");
     HIPCHK(h, hipSetDevice(h->device));
     for (hipStream_t q : work_streams(h)) HIPCHK(h, hipStreamSynchronize(q));
     h->grad_prec = (int)value;

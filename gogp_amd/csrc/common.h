@@ -565,6 +565,16 @@ void launch_lap_weight(hipStream_t s, double *G, int64_t ld, int64_t n, int64_t 
                        const double *a);
 void launch_lap_colscale(hipStream_t s, double *KsT, int64_t ld, int64_t rows, int64_t npad, const double *sw);
 void launch_lap_mean(hipStream_t s, int lik, const double *mu, const double *sigma, int64_t m, double *mean);
+// noisevar.hip (gogp_set_noise_variances): per-observation noise variances v on the diagonal of K.
+// launch_nv_diag_add: A_ii += v_i for i < n, right behind launch_gram_lower_split with the same streams and column
+// split: the rows i < wcols on s_first, the rest on s_rest; nothing else of A is read or written.
+// launch_nv_gradient: dv_i = 1/2 (alpha_i^2 - Kinv_ii) for i < n, one fused multiply-add per row; reads the diagonal of
+// Kinv only.  launch_nv_append_fold: part[i * 64 + i] -= v2_i for i < m <= 64 on the first slab's partial sums of
+// append_gram_kernel, so that append_commit_kernel's S = C - sum carries v2 on its diagonal.
+void launch_nv_diag_add(hipStream_t s_first, hipStream_t s_rest, double *A, int64_t ld, int64_t n, const double *v,
+                        int64_t wcols);
+void launch_nv_gradient(hipStream_t s, const double *Kinv, int64_t ld, const double *alpha, int64_t n, double *dv);
+void launch_nv_append_fold(hipStream_t s, double *part, const double *v2, int m);
 void launch_fill(hipStream_t s, double *p, int64_t count, double v);
 void launch_axpy(hipStream_t s, double *a, const double *b, int64_t count);  // a += b
 void launch_dot(hipStream_t s, const double *a, const double *b, int64_t n, double *out);  // out[0] = a.b

@@ -274,7 +274,14 @@ struct gogp_handle : EvalBufs, EvalState {
   // set only while a Laplace observe factors (api.hip: Sweep::build_gram, factorize_t): the Gram stage scales K into
   // B = I + diag(lap_sw) K diag(lap_sw) and the forward substitution's working copy comes from lap_rhs instead of dy
   const double *lap_sw = nullptr, *lap_rhs = nullptr;
-  double yta = 0.0;      // y^T alpha of the last factorisation (fp32 path: of the refined alpha)
+  // per-observation noise variances (gogp_set_noise_variances, noisevar.hip): K = k(X, X) + s2 I + diag(nv).  nv_cap
+  // doubles, zero from row n on; released with the N buffers, grown with them by gogp_append.  nv_set: they apply to
+  // the current data -- the sweep adds them behind the Gram build, gogp_append / gogp_remove carry them.
+  double *nv = nullptr;
+  int64_t nv_cap = 0;
+  bool nv_set = false;
+  Workspace nv_ws;          // gogp_noise_variances_gradient: dv (npad doubles)
+  double yta = 0.0;     // y^T alpha of the last factorisation (fp32 path: of the refined alpha)
   int trace_fp64 = 1;    // fp32 path: tr(alpha alpha^T - K^-1) summed in fp64 from Y, scale component by its identity
   double cond_limit = 1e16;  // gonum's mat.ConditionTolerance
   std::vector<double> grad_cache;

@@ -1193,11 +1193,14 @@ extern "C" int gogp_test_append_gram(int device, const void *sol0, int64_t sol0_
   return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
 }
 
-extern "C" int gogp_test_append_commit(int device, const gogp_test_kparams *kparams, int ev, const double *X2, int64_t x2_len,
-                                       const double *y2, int64_t y2_len, int m, int64_t n, const double *part,
-                                       int64_t part_len, int nslab, double *Lnew, int64_t lnew_len, int64_t ld, double *z2,
-                                       int64_t z2_len, long long *info) {
+// v2 != nullptr: launch_nv_append_fold (noisevar.hip) on the parts first, as gogp_append_noisy does; part_out != nullptr:
+// the parts come back whole
+static int test_append_commit(int device, const gogp_test_kparams *kparams, int ev, const double *X2, int64_t x2_len,
+                              const double *y2, int64_t y2_len, const double *v2, int64_t v2_len, int m, int64_t n,
+                              const double *part, double *part_out, int64_t part_len, int nslab, double *Lnew,
+                              int64_t lnew_len, int64_t ld, double *z2, int64_t z2_len, long long *info) {
   if (!kparams || !X2 || !y2 || !part || !Lnew || !z2 || !info) return GOGP_EARG;
+  if (v2 && v2_len < m) return GOGP_EARG;
   if (!kparams_ok(kparams, 1, ard_dims_of(kparams), 0, 1, ev)) return GOGP_EARG;
   if (m < 1 || m > 64 || n < 0 || n > UP_NPAD_MAX || nslab < 1 || nslab > UP_NPAD_MAX / PANEL) return GOGP_EARG;
   if (x2_len < (int64_t)m * kparams->ndim || y2_len < m || z2_len < m || part_len < (int64_t)nslab * APPEND_PART)
@@ -1205,15 +1208,17 @@ extern "C" int gogp_test_append_commit(int device, const gogp_test_kparams *kpar
   if (!covers(lnew_len, 0, ld, m, n + m, 1, 0)) return GOGP_EARG;
   if (!device_ok(device)) return GOGP_EHIP;
   const DevParams hp = to_dev(*kparams);
-  DevCopy dP, dX, dy, dpart, dL, dz, di;
+  DevCopy dP, dX, dy, dv, dpart, dL, dz, di;
   hipError_t e = dP.up(&hp, sizeof hp);
   if (e == hipSuccess) e = dX.up(X2, (size_t)x2_len * sizeof(double));
   if (e == hipSuccess) e = dy.up(y2, (size_t)y2_len * sizeof(double));
+  if (e == hipSuccess && v2) e = dv.up(v2, (size_t)v2_len * sizeof(double));
   if (e == hipSuccess) e = dpart.up(part, (size_t)part_len * sizeof(double));
   if (e == hipSuccess) e = dL.up(Lnew, (size_t)lnew_len * sizeof(double));
   if (e == hipSuccess) e = dz.up(z2, (size_t)z2_len * sizeof(double));
   if (e == hipSuccess) e = di.up(info, sizeof(long long));
   if (e == hipSuccess) {
+    if (v2) launch_nv_append_fold(0, dpart.as<double>(), dv.as<double>(), m);
     launch_append_commit(0, dP.as<DevParams>(), dX.as<double>(), dy.as<double>(), m, n, dpart.as<double>(), nslab,
                          dL.as<double>(), ld, dz.as<double>(), di.as<long long>(), ev != 0);
     e = launched();
@@ -1221,7 +1226,25 @@ extern "C" int gogp_test_append_commit(int device, const gogp_test_kparams *kpar
   if (e == hipSuccess) e = dL.down(Lnew);
   if (e == hipSuccess) e = dz.down(z2);
   if (e == hipSuccess) e = di.down(info);
+  if (e == hipSuccess && part_out) e = dpart.down(part_out);
   return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+}
+
+extern "C" int gogp_test_append_commit(int device, const gogp_test_kparams *kparams, int ev, const double *X2, int64_t x2_len,
+                                       const double *y2, int64_t y2_len, int m, int64_t n, const double *part,
+                                       int64_t part_len, int nslab, double *Lnew, int64_t lnew_len, int64_t ld, double *z2,
+                                       int64_t z2_len, long long *info) {
+  return test_append_commit(device, kparams, ev, X2, x2_len, y2, y2_len, nullptr, 0, m, n, part, nullptr, part_len, nslab,
+                            Lnew, lnew_len, ld, z2, z2_len, info);
+}
+
+extern "C" int gogp_test_nv_append_commit(int device, const gogp_test_kparams *kparams, int ev, const double *X2,
+                                          int64_t x2_len, const double *y2, int64_t y2_len, const double *v2, int64_t v2_len,
+                                          int m, int64_t n, double *part, int64_t part_len, int nslab, double *Lnew,
+                                          int64_t lnew_len, int64_t ld, double *z2, int64_t z2_len, long long *info) {
+  if ((v2 == nullptr) != (v2_len == 0)) return GOGP_EARG;
+  return test_append_commit(device, kparams, ev, X2, x2_len, y2, y2_len, v2, v2_len, m, n, part, part, part_len, nslab,
+                            Lnew, lnew_len, ld, z2, z2_len, info);
 }
 
 extern "C" int gogp_test_remove_gather(int device, const double *src, int64_t src_len, int64_t ld0, const int *map,
@@ -2047,4 +2070,22 @@ extern "C" int gogp_test_basis_predict(int device, const double *Hz, int64_t hz_
   return fin_run(device, arrs, [&](double **d) {
     launch_basis_predict(0, d[0], d[1], ldkw, m, p, d[2], d[3], d[4], d[5], d[6], d[7], nullptr);
   });
+}
+
+// ---- the kernels of the per-observation noise variances (noisevar.hip; tests/test_noise_variances_kernels.py), under the
+// rules of the finishing hooks above ------------------------------------------------------------------------------------
+extern "C" int gogp_test_nv_diag_add(int device, double *A, int64_t a_len, int64_t ld, int64_t n, int64_t npad,
+                                     const double *v, int64_t v_len, int64_t wcols) {
+  const std::initializer_list<FinArr> arrs = {{A, a_len, true}, {v, v_len, false}};
+  if (!fin_have(arrs) || !fin_npad_ok(n, npad) || !covers(a_len, 0, ld, npad, npad, 1, 0)) return GOGP_EARG;
+  if (v_len < n || wcols < 0 || wcols % 64) return GOGP_EARG;
+  return fin_run(device, arrs, [&](double **d) { launch_nv_diag_add(0, 0, d[0], ld, n, d[1], wcols); });
+}
+
+extern "C" int gogp_test_nv_gradient(int device, const double *Kinv, int64_t kinv_len, int64_t ld, const double *alpha,
+                                     int64_t alpha_len, int64_t n, int64_t npad, double *dv, int64_t dv_len) {
+  const std::initializer_list<FinArr> arrs = {{Kinv, kinv_len, false}, {alpha, alpha_len, false}, {dv, dv_len, true}};
+  if (!fin_have(arrs) || !fin_npad_ok(n, npad) || !covers(kinv_len, 0, ld, npad, npad, 1, 0)) return GOGP_EARG;
+  if (alpha_len < n || dv_len < n) return GOGP_EARG;
+  return fin_run(device, arrs, [&](double **d) { launch_nv_gradient(0, d[0], ld, d[1], n, d[2]); });
 }

@@ -205,12 +205,50 @@ class GP:
                                                     ctypes.c_void_p(dy_ptr), int(n)))
         self._data_dirty = False
 
+    # ---- per-observation noise variances (no reference counterpart: gp.GP has one noise level) ----
+    def SetNoiseVariances(self, v) -> None:
+        """Known noise variances, one per observation: K = k(X, X) + sigma^2(theta) I + diag(v), every v[i] finite and
+        >= 0 (gogp_set_noise_variances).  ``None`` clears them.  Stored results are dropped: Absorb or Observe again
+        before Gradient, Produce, LOO ...; every call behind the factorisation then sees the variances.  They belong
+        to the data: assigning ``X`` / ``Y`` (and so Absorb(x, y) without ``v``, and the full form of Observe) clears
+        them; Append and Remove carry them.  fp64, unsharded handles; the candidates path, the Laplace calls, the
+        batches of small GPs and the sparse calls do not take them."""
+        if v is None:
+            if not self._data_dirty:
+                self._check(_lib.lib().gogp_set_noise_variances(self._h, None, 0))
+            return
+        va = _arr(v).reshape(-1)
+        if va.size != len(self._Y):
+            raise ValueError("SetNoiseVariances: one variance per observation")
+        self._push_data()
+        self._check(_lib.lib().gogp_set_noise_variances(self._h, _dp(va), va.size))
+
+    @property
+    def NoiseVariances(self) -> np.ndarray:
+        """The noise variances the device holds for the current observations (zeros when none are set)."""
+        if self._data_dirty:
+            return np.zeros(len(self._Y))
+        v = np.zeros(int(_lib.lib().gogp_n(self._h)))
+        self._check(_lib.lib().gogp_get_noise_variances(self._h, _dp(v)))
+        return v
+
+    def NoiseVariancesGradient(self) -> np.ndarray:
+        """dLML/dv[i] = 1/2 (Alpha[i]^2 - [K^-1]_ii), n entries, at the parameters and variances of the last Absorb /
+        Observe / Append / Remove / restore (gogp_noise_variances_gradient); also with no variances set (the
+        derivative at v = 0).  Works wherever LOO works and leaves the process as it found it."""
+        dv = np.zeros(int(_lib.lib().gogp_n(self._h)))
+        self._check(_lib.lib().gogp_noise_variances_gradient(self._h, _dp(dv)))
+        return dv
+
     # ---- gp.GP.Absorb (gp/gp.go:80-87) -----------------------------------------------
-    def Absorb(self, x, y) -> None:
+    def Absorb(self, x, y, v=None) -> None:
         """Absorb absorbs observations into the process.  Parameters are taken
-        from ThetaSimil / ThetaNoise (natural scale, gp/gp_test.go:29)."""
+        from ThetaSimil / ThetaNoise (natural scale, gp/gp_test.go:29).  ``v``: the observations' noise variances
+        (SetNoiseVariances); None: none, also when the previous data had some."""
         self.X, self.Y = x, y
         self._push_data()
+        if v is not None:
+            self.SetNoiseVariances(v)
         ts = _arr(self.ThetaSimil)
         tn = _arr(self.ThetaNoise) if self._nn else np.zeros(1)
         if ts.size != self._ns:
@@ -219,15 +257,22 @@ class GP:
         self._check(_lib.lib().gogp_absorb(self._h, _dp(ts), _dp(tn)))
 
     # ---- no reference counterpart (the reference refactorises: tutorial/tutorial.go:118-142) ----
-    def Append(self, x, y) -> None:
+    def Append(self, x, y, v=None) -> None:
         """Append observations to the absorbed ones at the parameters of the last Absorb / Observe / restore
-        (gogp_append): the state Absorb on all observations would leave, without a new factorisation.  An empty
-        process absorbs them at ThetaSimil / ThetaNoise.  Raises FactorizeError (``pivot``: the global index) and
-        leaves the process as it was when the enlarged matrix is not positive definite."""
+        (gogp_append_noisy): the state Absorb on all observations would leave, without a new factorisation.  An empty
+        process absorbs them at ThetaSimil / ThetaNoise.  ``v``: the new observations' noise variances
+        (SetNoiseVariances); None: zeros.  With ``v`` on a process without variances the old rows get zeros.  Raises
+        FactorizeError (``pivot``: the global index) and leaves the process, its variances included, as it was when
+        the enlarged matrix is not positive definite."""
         xa = _arr(x).reshape(-1, self.NDim)
         ya = _arr(y).reshape(-1)
         if len(xa) != len(ya):
             raise ValueError("len(x) != len(y)")
+        va = None
+        if v is not None:
+            va = _arr(v).reshape(-1)
+            if len(va) != len(ya):
+                raise ValueError("len(v) != len(y)")
         L = _lib.lib()
         if len(self._Y) == 0:
             # an empty process: pending (empty) data first, and the parameters the append is to use
@@ -242,7 +287,7 @@ class GP:
             raise GogpError(_lib.GOGP_ESTATE, "Append: X / Y were assigned since the last Absorb / Observe; Absorb them")
         if len(ya) == 0:
             return
-        rc = L.gogp_append(self._h, _dp(xa), _dp(ya), len(ya))
+        rc = L.gogp_append_noisy(self._h, _dp(xa), _dp(ya), _dp(va), len(ya))
         if rc in (_lib.GOGP_OK, _lib.GOGP_ECOND):  # stored (GOGP_ECOND: and reported, as Absorb)
             self._X = np.concatenate([self._X.reshape(-1, self.NDim), xa])
             self._Y = np.concatenate([self._Y, ya])
@@ -1059,6 +1104,45 @@ class LOOModel:
         return g
 
 
+class HeteroscedasticModel:
+    """Model whose per-observation noise variances come from a log-linear noise model fitted with the
+    hyperparameters: x = [log theta (P) | phi (q)], v = exp(G phi) with ``G`` an n x q design matrix -- one-hot columns
+    give one noise level per instrument, a column of ones plus time a drifting level.  Observe(x) sets v
+    (GP.SetNoiseVariances) and runs gp.Observe(log theta); Gradient() returns [gp.Gradient() | G^T (v o dv)] with dv
+    = GP.NoiseVariancesGradient().  ``Priors`` (Observe / Gradient over the first entries of x) is added as in Model.
+    For optimize.lbfgs and optimize.Adam.Step with the sequential drivers only: the candidates path refuses
+    variances (the GP is ``gp`` here, not ``GP``)."""
+
+    def __init__(self, gp: GP, G, Priors=None):
+        self.gp = gp
+        self.G = _arr(G)
+        if self.G.ndim != 2:
+            raise ValueError("G: an n x q matrix")
+        self.Priors = Priors
+        self._x = None
+        self._v = None
+
+    def Observe(self, x) -> float:
+        self._x = _arr(x).reshape(-1).copy()
+        P, (n, q) = self.gp._ns + self.gp._nn, self.G.shape
+        if self._x.size != P + q:
+            raise ValueError("len(x): the hyperparameters and one coefficient per column of G")
+        if n != len(self.gp.Y):
+            raise ValueError("G: one row per observation")
+        self._v = np.exp(self.G @ self._x[P:])
+        self.gp.SetNoiseVariances(self._v)
+        v = self.gp.Observe(self._x[:P])
+        return v + self.Priors.Observe(self._x) if self.Priors is not None else v
+
+    def Gradient(self) -> np.ndarray:
+        g = np.concatenate([self.gp.Gradient(), self.G.T @ (self._v * self.gp.NoiseVariancesGradient())])
+        if self.Priors is not None:
+            self.Priors.Observe(self._x)
+            pg = np.asarray(self.Priors.Gradient(), dtype=float)
+            g[:len(pg)] += pg
+        return g
+
+
 class LaplaceModel:
     """Model with the Laplace approximation's log marginal likelihood under the likelihood ``lik`` ("bernoulli" /
     "poisson") in the place of the LML: Observe(x) returns GP.LaplaceObserve(x, lik) (+ the log prior), Gradient()
@@ -1658,6 +1742,23 @@ def append_commit_check(kp, X2: np.ndarray, y2: np.ndarray, m: int, n: int, part
     return Lnew, z2, int(inf.value)
 
 
+def nv_append_commit_check(kp, X2: np.ndarray, y2: np.ndarray, v2, m: int, n: int, part: np.ndarray, nslab: int,
+                           Lnew: np.ndarray, ld: int, z2: np.ndarray, info: int = 0, ev: bool = False, device: int = -1):
+    """append_commit_check with the new rows' noise variances v2 folded into the parts first (launch_nv_append_fold, as
+    gogp_append_noisy; test hook gogp_test_nv_append_commit).  v2 = None: launch_append_commit alone.  Returns copies of
+    (Lnew, z2), info and the parts after the launches."""
+    X2, y2, part = _vec(X2, "X2"), _vec(y2, "y2"), _vec(part, "part").copy()
+    v2 = None if v2 is None else _vec(v2, "v2")
+    Lnew, z2 = _vec(Lnew, "Lnew").copy(), _vec(z2, "z2").copy()
+    inf = ctypes.c_longlong(info)
+    rc = _lib.hooks().gogp_test_nv_append_commit(device, ctypes.byref(kp), int(ev), _dp(X2), X2.size, _dp(y2), y2.size,
+                                                 _dp(v2), 0 if v2 is None else v2.size, m, n, _dp(part), part.size, nslab,
+                                                 _dp(Lnew), Lnew.size, ld, _dp(z2), z2.size, ctypes.byref(inf))
+    if rc != _lib.GOGP_OK:
+        raise GogpError(rc, "test_nv_append_commit")
+    return Lnew, z2, int(inf.value), part
+
+
 def remove_gather_check(src: np.ndarray, ld0: int, map_: np.ndarray, n1: int, dst: np.ndarray, npad1: int,
                         device: int = -1):
     """launch_remove_gather (test hook gogp_test_remove_gather); returns a copy of dst after the launch."""
@@ -1752,6 +1853,11 @@ def finish_check(which: str, device: int = -1, **args):
 def laplace_kernel_check(which: str, device: int = -1, **args):
     """finish_check for the kernels of the Laplace approximation (_lib.LAPLACE_HOOKS)."""
     return _table_check(_lib.LAPLACE_HOOKS, which, device, args, "laplace_kernel_check")
+
+
+def noise_variances_kernel_check(which: str, device: int = -1, **args):
+    """finish_check for the kernels of the per-observation noise variances (_lib.NOISEVAR_HOOKS)."""
+    return _table_check(_lib.NOISEVAR_HOOKS, which, device, args, "noise_variances_kernel_check")
 
 
 def basis_kernel_check(which: str, device: int = -1, **args):

@@ -52,11 +52,17 @@ class GP {
   GP(const GP &) = delete;
   GP &operator=(const GP &) = delete;
 
-  // gp/gp.go:80-87
-  int Absorb(const std::vector<std::vector<double>> &x, const std::vector<double> &y) {
+  // gp/gp.go:80-87.  v: the observations' noise variances (SetNoiseVariances); empty: none, also when the previous
+  // data had some.
+  int Absorb(const std::vector<std::vector<double>> &x, const std::vector<double> &y,
+             const std::vector<double> &v = std::vector<double>()) {
     SetData(x, y);
     int rc = push();
     if (rc != GOGP_OK) return rc;
+    if (!v.empty()) {
+      rc = SetNoiseVariances(v);
+      if (rc != GOGP_OK) return rc;
+    }
     double zero = 0.0;
     rc = gogp_absorb(h_, ThetaSimil.data(), ThetaNoise.empty() ? &zero : ThetaNoise.data());
     if (rc != GOGP_OK && rc != GOGP_ECOND) return rc;  // gp/gp.go:228-230
@@ -67,8 +73,10 @@ class GP {
   // Append observations to the absorbed ones at the parameters of the last Absorb / Observe (gogp_append; no reference
   // counterpart: tutorial/tutorial.go:118-142 refactorises).  An empty process absorbs them at ThetaSimil / ThetaNoise.
   // GOGP_ENOTPD: nothing changed.  GOGP_ESTATE: X / Y were re-assigned since the last upload (Absorb them instead).
-  int Append(const std::vector<std::vector<double>> &x, const std::vector<double> &y) {
-    if (x.size() != y.size()) return GOGP_EARG;
+  // v: the new observations' noise variances (gogp_append_noisy); empty: zeros.
+  int Append(const std::vector<std::vector<double>> &x, const std::vector<double> &y,
+             const std::vector<double> &v = std::vector<double>()) {
+    if (x.size() != y.size() || (!v.empty() && v.size() != y.size())) return GOGP_EARG;
     if (Y.empty()) {
       int rc = push();
       if (rc != GOGP_OK) return rc;
@@ -80,7 +88,8 @@ class GP {
     }
     if (y.empty()) return GOGP_OK;
     std::vector<double> flat = pack(x);
-    const int rc = gogp_append(h_, flat.data(), y.data(), (int64_t)y.size());
+    const int rc = v.empty() ? gogp_append(h_, flat.data(), y.data(), (int64_t)y.size())
+                             : gogp_append_noisy(h_, flat.data(), y.data(), v.data(), (int64_t)y.size());
     if (rc != GOGP_OK && rc != GOGP_ECOND) return rc;
     X.insert(X.end(), x.begin(), x.end());
     Y.insert(Y.end(), y.begin(), y.end());
@@ -117,6 +126,30 @@ class GP {
     Y.resize(k);
     const int ra = fetch_alpha();
     return ra != GOGP_OK ? ra : rc;
+  }
+
+  // Per-observation noise variances: K = k(X, X) + sigma^2(theta) I + diag(v), every v[i] finite and >= 0
+  // (gogp_set_noise_variances; no reference counterpart).  An empty v clears them.  Stored results are dropped: Absorb
+  // or Observe again.  They belong to the data: SetData (and so Absorb without v) clears them, Append and Remove carry
+  // them.  Returns the status; GOGP_EARG: a wrong length, a negative or non-finite value, a handle that takes none.
+  int SetNoiseVariances(const std::vector<double> &v) {
+    if (v.empty()) return dirty_ ? GOGP_OK : gogp_set_noise_variances(h_, nullptr, 0);
+    if (v.size() != Y.size()) return GOGP_EARG;
+    const int rc = push();
+    if (rc != GOGP_OK) return rc;
+    return gogp_set_noise_variances(h_, v.data(), (int64_t)v.size());
+  }
+  // what the device holds for the current observations (zeros when none are set)
+  std::vector<double> NoiseVariances() {
+    std::vector<double> v(dirty_ ? Y.size() : (size_t)gogp_n(h_), 0.0);
+    if (!dirty_ && !v.empty()) check(gogp_get_noise_variances(h_, v.data()));
+    return v;
+  }
+  // dLML / dv[i] = 1/2 (Alpha[i]^2 - [K^-1]_ii) at the current parameters and variances (gogp_noise_variances_gradient)
+  std::vector<double> NoiseVariancesGradient() {
+    std::vector<double> dv((size_t)gogp_n(h_), 0.0);
+    check(gogp_noise_variances_gradient(h_, dv.empty() ? nullptr : dv.data()));
+    return dv;
   }
 
   // Assign the observations (gp.GP.X / gp.GP.Y); uploaded on the next Absorb / Observe.

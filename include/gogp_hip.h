@@ -712,6 +712,59 @@ int gogp_append(gogp_handle *h, const double *X2 /* m x ndim */, const double *y
  * dependent launch per 128 columns behind the first removed row, per pass of 32 removed rows. */
 int gogp_remove(gogp_handle *h, const int64_t *idx /* m, strictly increasing */, int64_t m);
 
+/* ---- per-observation noise variances ----------------------------------------------------------
+ * K = k_theta(X, X) + sigma^2(theta) I + diag(v): every observation carries a known noise variance v_i, finite and
+ * >= 0, on top of the handle's noise kind, which keeps its parameter slot and its derivative -- measurements with their
+ * own error bars, means of n_i replicates (sigma^2 / n_i), series from instruments of different quality.  No reference
+ * counterpart (gp.GP has one noise level on every observation).  A fixed diag(v) has no derivative in theta, and every
+ * call behind the factorisation works from the factor, alpha and K^-1: with variances set, gogp_absorb / gogp_observe,
+ * gogp_gradient, gogp_produce*, gogp_loo*, gogp_blockcv*, gogp_multi_*, gogp_basis_* and gogp_get_factor* are those of
+ * the model above at no extra cost but one or two O(n) launches behind the Gram build.  Handles with variances and
+ * n <= 128 take the general sweep instead of the one-launch form (option "tiny").  With none set no launch changes.
+ *
+ * gogp_noise_variances_check: host only; GOGP_OK when every v_i is finite and >= 0 (n == 0: OK), else GOGP_EARG.
+ *
+ * gogp_set_noise_variances: needs data (GOGP_ESTATE before gogp_set_data) and n == gogp_n(h) (GOGP_EARG); the values are
+ * copied to the device.  v == NULL with n == 0 clears.  Stored results no longer match and are dropped, exactly as by
+ * gogp_set_events: until the next gogp_absorb / gogp_observe the calls gogp_gradient, gogp_produce, gogp_loo ... return
+ * GOGP_ESTATE.  Clearing, followed by an Observe, returns the bits of a handle that never had variances.
+ *   Dropped by: whatever replaces the data -- gogp_set_data[_device], gogp_observe_full with observations in x -- and
+ *               a change of option "precision" (the list that applies to gogp_multi_set_outputs).
+ *   Carried by: gogp_append* (new rows: v2, or zeros) and gogp_remove (compacted with the rows).
+ *   Untouched by: the sparse, batch, multi-output and basis setters and gogp_set_factor.  A restore that wants to
+ *               append later calls gogp_set_data, then gogp_set_noise_variances, then gogp_set_factor.
+ * GOGP_EARG, each said in gogp_last_error: a negative or non-finite variance; a precision = 32 handle; gradient_precision
+ * = 32 (its closed-form scale component assumes K = c F + sigma^2 I; the option is refused in turn while variances are
+ * set); a sharded handle.  While variances are set gogp_observe_gradient_candidates (the arena slots' sweeps do not add
+ * them) and gogp_laplace_observe (its matrix-free products with K do not carry them) return GOGP_EARG.  The batches of
+ * small GPs (gogp_batch_*) and the sparse calls (gogp_sparse_*) have data of their own: the variances do not apply to
+ * them.
+ *
+ * gogp_get_noise_variances: what the device holds for the gogp_n observations; zeros when none are set.
+ *
+ * gogp_noise_variances_gradient: dv_i = dLML/dv_i = 1/2 (alpha_i^2 - [K^-1]_ii), one kernel over the diagonal of the
+ * explicit K^-1.  Works wherever gogp_loo works, by the same preparation, also with no variances set (the derivative at
+ * v = 0), and leaves the handle as gogp_loo leaves it: K^-1 formed, nothing a later call reads changed.  Two identical
+ * calls return identical bits.  n == 0: nothing is written.  With it the variances can be learnt through any host-side
+ * noise model v(phi): dLML/dphi = sum_i dv_i dv_i/dphi (gogp_amd/gp.py: HeteroscedasticModel).
+ *
+ * gogp_append_noisy: gogp_append with the new rows' variances v2 (m values, checked as above) on the diagonal of the new
+ * block; gogp_append is this call with v2 == NULL, which means zeros.  With v2 given on a handle without variances the
+ * vector is created with zeros for the old rows.  The vector grows with the data's buffers.  The empty process absorbs
+ * the m rows with v2 set.  On GOGP_ENOTPD the handle, its variances included, is exactly as it was before the call.
+ *
+ * Measured on one MI355X (profiles/noise_variances.txt, D = 8, medians of alternating rounds): Observe + Gradient with
+ * variances against without 0.678 / 3.185 / 71.40 ms against 0.684 / 3.163 / 71.25 ms at N = 1024 / 4096 / 16384, every
+ * difference inside the spread of repeated identical runs (0.09 / 0.42 / 1.16 ms); N = 64 / 128, general sweep against one
+ * launch: 0.37 / 0.36 ms against 0.19 / 0.21 ms; gogp_noise_variances_gradient with K^-1 in place 0.03 ms beside 0.08 -
+ * 0.10 ms for gogp_loo; gogp_append_noisy of 1 / 64 rows at N = 16384 2.47 / 3.92 ms against 2.49 / 3.96 ms for gogp_append. */
+int gogp_noise_variances_check(const double *v, int64_t n);
+int gogp_set_noise_variances(gogp_handle *h, const double *v /* n; NULL with n == 0 clears */, int64_t n);
+int gogp_get_noise_variances(gogp_handle *h, double *v /* gogp_n */);
+int gogp_noise_variances_gradient(gogp_handle *h, double *dv /* gogp_n */);
+int gogp_append_noisy(gogp_handle *h, const double *X2 /* m x ndim */, const double *y2 /* m */,
+                      const double *v2 /* m, may be NULL */, int64_t m);
+
 /* ---- one evaluation sharded over several GPUs: 2-D block-cyclic ---------------------
  * One process per GPU.  The ranks form a Pr x Pc process grid (rank = pr*Pc + pc; Pr must
  * divide Pc: 1x1, 1x2, 2x2, 2x4 for 1/2/4/8 GPUs, gogp_dist_grid).  The Gram matrix is cut into

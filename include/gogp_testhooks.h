@@ -205,6 +205,14 @@ int gogp_test_append_commit(int device, const gogp_test_kparams *kparams, int ev
                             int nslab, double *Lnew, int64_t lnew_len, int64_t ld, double *z2, int64_t z2_len,
                             long long *info);
 
+/* gogp_test_append_commit behind launch_nv_append_fold (noisevar.hip), as gogp_append_noisy launches them: the first
+ * part's diagonal takes -v2 (m values), so that S = k(X2, X2) + noise + diag(v2) - sum of the parts.  v2 == NULL with
+ * v2_len == 0: launch_append_commit alone.  part is in / out here: it comes back whole. */
+int gogp_test_nv_append_commit(int device, const gogp_test_kparams *kparams, int ev, const double *X2, int64_t x2_len,
+                               const double *y2, int64_t y2_len, const double *v2, int64_t v2_len, int m, int64_t n,
+                               double *part, int64_t part_len, int nslab, double *Lnew, int64_t lnew_len, int64_t ld,
+                               double *z2, int64_t z2_len, long long *info);
+
 /* launch_remove_gather: dst (in / out; npad1 x npad1) from src (leading dimension ld0) through map (n1 old row indices,
  * every one a row src holds whole). */
 int gogp_test_remove_gather(int device, const double *src, int64_t src_len, int64_t ld0, const int *map, int64_t map_len,
@@ -483,6 +491,15 @@ int gogp_test_lap_colscale(int device, double *KsT, int64_t k_len, int64_t ld, i
                            int64_t sw_len);
 int gogp_test_lap_mean(int device, int lik, const double *mu, int64_t mu_len, const double *sigma, int64_t sigma_len, int64_t m,
                        double *mean, int64_t mean_len);
+
+/* The kernels of the per-observation noise variances in isolation (noisevar.hip; tests/test_noise_variances_kernels.py),
+ * under the same rules.  nv_diag_add: A_ii += v_i for i < n in two launches, the rows below wcols and the rest; nothing
+ * else of A (in / out; npad rows of ld) is read or written.  nv_gradient: dv_i = 1/2 (alpha_i^2 - Kinv_ii) for i < n, one
+ * fused multiply-add per row; only the diagonal of Kinv is read.  (The append fold: gogp_test_nv_append_commit above.) */
+int gogp_test_nv_diag_add(int device, double *A, int64_t a_len, int64_t ld, int64_t n, int64_t npad, const double *v,
+                          int64_t v_len, int64_t wcols);
+int gogp_test_nv_gradient(int device, const double *Kinv, int64_t kinv_len, int64_t ld, const double *alpha,
+                          int64_t alpha_len, int64_t n, int64_t npad, double *dv, int64_t dv_len);
 
 #ifdef __cplusplus
 }
