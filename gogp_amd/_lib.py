@@ -352,6 +352,49 @@ HOOK_SYMBOLS += [("gogp_test_" + k, ctypes.c_int, [ctypes.c_int] + [t for _, kin
                  for k, spec in NOISEVAR_HOOKS.items()]
 
 
+#: the hooks of the kernels of the sharded path (dist2d.hip and its helpers in solve.hip) and of the rest of solve.hip
+#: (tests/test_shard_kernels.py), as gp.shard_kernel_check reads them: the notation of _FINISH_SPEC and, beyond it, A / O: an
+#: array (read, in / out) of float64 or float32 as the argument `precision` says (P: as `precision2` says, in / out), f: a
+#: float32 array read, and n / r / B: a float64 / int64 / `precision`-typed array read that may be None (NULL, length 0)
+_MAP = "nb_shift:i Pr:i Pc:i pr:i pc:i"
+_SHARD_SPEC = {
+    "gather_rows": "y:a rows:l %s yloc:o" % _MAP,
+    "gather_x": "X:a a:a D:i n:l rows:l %s Xloc:o aloc:o" % _MAP,
+    "scatter_tile": "precision:i src:A nb:i n:l row0:l col0:l diag:i r0:l dst:o",
+    "gather_rows_of_l": "precision:i Lch:A mloc:i nloc:i %s rows:r n:l diag_only:i out:o" % _MAP,
+    "scatter_stage": "precision:i stage:a lds:l Lch:O nloc:i mloc:i bi:i nb:i",
+    "transpose_rect": "precision:i src:A lds:l dst:O ldd:l rows:l cols:i",
+    "transpose_sq": "precision:i src:A lds:l dst:O ldd:l n:i",
+    "copy_block": "dst:o src:a ld:l nb:i rows:l",
+    "residual_block": "precision:i W:O Ks:A U:a ld:l recv:n nrecv:i nb:i rows:l",
+    "pack_blocks": "dst:o src:a nblk:i blk:l first:i stride:i",
+    "convert_block": "precision:i precision2:i src:A lds:l dst:P ldd:l rows:i cols:i",
+    "chunk_tdot": "precision:i chunk:A rows:l nb:i v:a part:o out:o",
+    "chunk_alpha": "precision:i Ych:A mloc:i nloc:i %s z:a out:o" % _MAP,
+    "chunk_sumsq": "precision:i Ych:A mloc:i nloc:i %s n:l part:o out:o" % _MAP,
+    "lml_scalars": "precision:i L:A ld:l z:a y:a alpha:n n:l k:i bstride:l scalars:o",
+    "alpha_from_y_batched": "Y:a ld:l z:a npad:l k:i bstride:l alpha:o",
+    "trace_from_y": "Y:f ld:l n:l npad:l alpha:a part:o out:o",
+    "zero_upper_blocks": "precision:i R:O ld:l npad:l k:i bstride:l",
+    "ydiag": "precision:i Dinv:A Y:O ld:l k:i bstride:l",
+    "zero_block": "precision:i B:O ld:l rows:l cols:l k:i bstride:l",
+    "extract_lower": "precision:i L:A ld:l n:l out:o",
+    "pack_lower": "precision:i src:a n:l npad:l L:O ld:l",
+    "sigma": "prior:a q:n m:l sigma:o",
+    "logdet_block": "L:a ld:l row0:l n:l nb:i acc:o",
+    "dot": "a:a b:a n:l out:o",
+    "sumsq_info": "z:a n:l info:r out:o",
+    "vector_op": "op:i precision:i a:O b:B count:l f:d",
+}
+SHARD_HOOKS = {k: [tuple(t.split(":")) for t in v.split()] for k, v in _SHARD_SPEC.items()}
+#: the ops of gogp_test_vector_op
+VECTOR_OPS = {"fill": 0, "axpy": 1, "add_vec": 2, "scale": 3, "residual_from": 4, "add_inplace": 5, "info_to_double": 6}
+_SHARD_CTYPES = dict(_FINISH_CTYPES, **{k: [ctypes.c_void_p, _i64] for k in "AOPBfrn"})
+HOOK_SYMBOLS += [("gogp_test_" + k, ctypes.c_int, [ctypes.c_int] + [t for _, kind in spec for t in _SHARD_CTYPES[kind]])
+                 for k, spec in SHARD_HOOKS.items()]
+HOOK_SYMBOLS += [("gogp_test_chunk_tdot_scratch", _i64, [_i64, ctypes.c_int])]
+
+
 def build(force: bool = False) -> str:
     """Compile every HIP source for gfx950 into gogp_amd/libgogp_hip.so
     (hipcc cross-compiles without a GPU)."""

@@ -224,7 +224,9 @@ void launch_trsv_bwd_step(hipStream_t s, const double *L, int64_t ld, const doub
                           int b, int nblk, double *zwork, double *alpha);
 
 // scalars[0] = sum_i 2 log L_ii, scalars[1] = sum z_i^2, scalars[2] = sum y_i alpha_i
-// (i < n; the last only when alpha != nullptr)
+// (i < n; the last only when alpha != nullptr: exactly 0 otherwise), scalars[3], [4] = min, max L_ii; scalars[5 ..] are left
+// alone.  Reads the diagonal of L and z, y, alpha on i < n only; one workgroup, any n >= 0.  Batched: L, z, alpha and
+// scalars lie tl_batch.stride bytes apart per candidate, y is shared.
 void launch_lml_scalars(hipStream_t s, const double *L, int64_t ld, const double *z,
                         const double *y, const double *alpha, int64_t n, double *scalars);
 // potrf + dense inverse of one 256x256 diagonal block (diag256.hip); Dinv has
@@ -354,10 +356,17 @@ void launch_xgrad(hipStream_t s, const DevParams *p, int ndim, const double *X,
 void launch_rownorm_dot(hipStream_t s, const double *V, int64_t ld, const double *vec,
                         int64_t ncols, int64_t m, double *dot, double *sq);
 
+// +0.0 on the strictly upper 256-blocks of npad x npad; nothing else is touched (npad <= 256: no launch).  Pairs of
+// columns are stored: npad and ld even, R 8-B (float) / 16-B aligned.
 void launch_zero_upper_blocks(hipStream_t s, double *R, int64_t ld, int64_t npad);
+// npad and ld even (pairs of columns, 16-B loads of z).  Of every row i < npad the columns q0(i) .. npad - 1 are read (q0:
+// first column of the row's 256-block), padding included; what lies left of q0(i) is never read.
 void launch_alpha_from_y(hipStream_t s, const double *Y, int64_t ld, const double *z,
                          int64_t npad, double *alpha);
+// +0.0 on rows x cols.  Pairs of columns are stored: cols and ld even (an odd cols would write one column too many), B
+// 8-B (float) / 16-B aligned.
 void launch_zero_block(hipStream_t s, double *B, int64_t ld, int64_t rows, int64_t cols);
+// Ydiag (256 x 256, ld) = Dinv^T; Dinv contiguous 256 x 256.
 void launch_ydiag(hipStream_t s, const double *Dinv, double *Ydiag, int64_t ld);
 // T^-1 of a super-panel's diagonal block (api.hip: assemble_tinv): diagonal / zero blocks, and nprod (<= 6) products
 // C_b (256 x 256) = alpha A_b (256 x K_b) B_b (K_b x 256), row-major, in one launch (solve.hip)
@@ -367,7 +376,9 @@ void launch_blockmm(hipStream_t s, int nprod, const double *const *A, const int6
                     const int64_t *ldb, double *const *C, const int64_t *ldc, const int *K, double alpha);
 void launch_blockmm(hipStream_t s, int nprod, const float *const *A, const int64_t *lda, const float *const *B,
                     const int64_t *ldb, float *const *C, const int64_t *ldc, const int *K, double alpha);
-// fp32 path: out[0] = sum_{i<n} alpha_i^2 - |Y|_F^2 (= tr(alpha alpha^T - K^-1)) in fp64 from Y = L^-T; part: n doubles
+// fp32 path: out[0] = sum_{i<n} alpha_i^2 - |Y|_F^2 (= tr(alpha alpha^T - K^-1)) in fp64 from Y = L^-T; part: n doubles.
+// Of the rows i < n the columns q0(i) .. npad - 1 are READ -- the padding columns n .. npad - 1 too, which must hold zeros
+// for the trace to be that of the n x n block; what lies left of q0(i) (the row's 256-block start) is never read.
 void launch_trace_from_y(hipStream_t s, const float *Y, int64_t ld, int64_t n, int64_t npad, const double *alpha,
                          double *part, double *out);
 // trsm_small.hip: V = L^-1 Kstar for the right-hand sides j0 .. j0 + cnt - 1 (rows of KsT, cnt <= 32) in ONE persistent
@@ -575,34 +586,89 @@ void launch_nv_diag_add(hipStream_t s_first, hipStream_t s_rest, double *A, int6
                         int64_t wcols);
 void launch_nv_gradient(hipStream_t s, const double *Kinv, int64_t ld, const double *alpha, int64_t n, double *dv);
 void launch_nv_append_fold(hipStream_t s, double *part, const double *v2, int m);
-void launch_fill(hipStream_t s, double *p, int64_t count, double v);
+void launch_fill(hipStream_t s, double *p, int64_t count, double v);  // grid-stride loop, grid capped at 4096 workgroups
 void launch_axpy(hipStream_t s, double *a, const double *b, int64_t count);  // a += b
-void launch_dot(hipStream_t s, const double *a, const double *b, int64_t n, double *out);  // out[0] = a.b
-// helpers of the sharded evaluation (solve.hip)
+void launch_dot(hipStream_t s, const double *a, const double *b, int64_t n, double *out);  // out[0] = a.b; one workgroup
+// helpers of the sharded evaluation (solve.hip); tests/test_shard_kernels.py holds the kernels to what is stated here
+// dst (n x n, ldd) = src^T; n a multiple of 32: whole 32 x 32 tiles are moved (n < 32 launches nothing)
 void launch_transpose_sq(hipStream_t s, const double *src, int64_t lds_, double *dst, int64_t ldd,
                          int n);
 void launch_transpose_sq(hipStream_t s, const float *src, int64_t lds_, float *dst, int64_t ldd, int n);
+// dst block d (blk doubles) = src block first + d stride, d < nblk; blk even and both pointers 16-B aligned (pairs of
+// doubles are moved: an odd blk drops its last one); only the selected source blocks are read
 void launch_pack_blocks(hipStream_t s, double *dst, const double *src, int nblk, int64_t blk,
                         int first, int stride);
+// out[c] = sum_{r < rows} chunk[r][c] v[r], c < nb.  nb a multiple of 64 (the grid is nb / 64 column groups: other
+// columns would never be written), rows >= 1; chunk and v are read on the rows < `rows` only; of part the first
+// ceil(rows / 256) slabs of nb doubles are written
 int64_t chunk_tdot_scratch(int64_t max_rows, int nb);  // doubles of `part` scratch
 void launch_chunk_tdot(hipStream_t s, const double *chunk, int64_t rows, int nb, const double *v,
                        double *part, double *out);
 void launch_chunk_tdot(hipStream_t s, const float *chunk, int64_t rows, int nb, const double *v,
                        double *part, double *out);
+// out[global row] = sum over this rank's chunks with global block column gP >= the row's global block row gI of
+// Ych[bj][bi][r][.] . z[gP nb ..], for EVERY local row, padding rows included; the rest of out is left alone and the
+// chunks with gP < gI are never read.  nb even, the chunks 8-B (float) / 16-B aligned, z 16-B aligned
 void launch_chunk_alpha(hipStream_t s, const double *Ych, int mloc, int nloc, int nb, BlockMap map,
                         const double *z, double *out);
 void launch_chunk_alpha(hipStream_t s, const float *Ych, int mloc, int nloc, int nb, BlockMap map,
                         const double *z, double *out);
-// out[0] = |Y_local|_F^2 over this rank's chunks of Y (rows < n), fp64; part: mloc * nb doubles
+// out[0] = |Y_local|_F^2 over this rank's chunks of Y (rows < n), fp64; part: mloc * nb doubles.  The local rows with
+// global index >= n are not read at all (their part[] is exactly 0), nor the chunks with gP < gI; alignment as chunk_alpha
 void launch_chunk_sumsq(hipStream_t s, const double *Ych, int mloc, int nloc, int nb, BlockMap map, int64_t n, double *part,
                         double *out);
 void launch_chunk_sumsq(hipStream_t s, const float *Ych, int mloc, int nloc, int nb, BlockMap map, int64_t n, double *part,
                         double *out);
+// acc[0] += sum_{i < nb, row0 + i < n} 2 log L_ii: ACCUMULATES; the other L_ii are not read
 void launch_logdet_block(hipStream_t s, const double *L, int64_t ld, int64_t row0, int64_t n, int nb,
                          double *acc);
+// out[0] = sum_{i < n} z_i^2 and, info given, out[1] = (double)*info (out[1] left alone otherwise); one workgroup
 void launch_sumsq_info(hipStream_t s, const double *z, int64_t n, const long long *info, double *out);
 void launch_info_to_double(hipStream_t s, const long long *info, double *out);
 void launch_extract_lower(hipStream_t s, const double *L, int64_t ld, int64_t n,
                           double *out);
+// dist2d.hip: the kernels of the sharded evaluation that work on one rank's buffers.  Nothing below reads or writes
+// beyond what is stated; "global row" is BlockMap::grow of the local one.
+// launch_gather_rows: yloc[i] = y[global row of i], i < rows -- y must hold every global row a local one maps to (the
+// padded length), there is no n here.  launch_gather_x: Xloc (rows x D), aloc = X, a at the global rows < n, exact zeros
+// for the others; X and a are not read from row n on.
+void launch_gather_rows(hipStream_t s, const double *y, double *yloc, int64_t rows, BlockMap map);
+void launch_gather_x(hipStream_t s, const double *X, const double *a, int D, int64_t n, int64_t rows, BlockMap map,
+                     double *Xloc, double *aloc);
+// launch_scatter_tile: dst[r * n + c] = src tile (nb x nb, contiguous) for the global rows row0 <= r < min(row0 + nb, n)
+// and columns col0 <= c < min(col0 + nb, n), diag: c <= r only; dst has n columns and may be offset by a band start (the
+// caller passes dst - r0 * n).  Rows / columns of src at or beyond n are not read.
+void launch_scatter_tile(hipStream_t s, const double *src, int nb, double *dst, int64_t n, int64_t row0, int64_t col0,
+                         int diag);
+void launch_scatter_tile(hipStream_t s, const float *src, int nb, double *dst, int64_t n, int64_t row0, int64_t col0,
+                         int diag);
+// launch_gather_rows_of_l: diag_only 0: out (nrows x n) row k = row rows[k] of L on the columns this rank's tiles hold
+// (<= rows[k]), rows[k] in [0, n) -- the kernel indexes the chunks with them unchecked; diag_only 1 (rows unused): out[r] =
+// L_rr for the r < n whose diagonal tile is this rank's.  Everything else of out is left alone (the caller zeroes it).
+void launch_gather_rows_of_l(hipStream_t s, const double *Lch, int mloc, int nloc, int nb, BlockMap map,
+                             const int64_t *rows, int64_t nrows, int64_t n, int diag_only, double *out);
+void launch_gather_rows_of_l(hipStream_t s, const float *Lch, int mloc, int nloc, int nb, BlockMap map, const int64_t *rows,
+                             int64_t nrows, int64_t n, int diag_only, double *out);
+// launch_scatter_stage: stage (nb rows of lds_ >= nloc * nb doubles: one local tile row, this rank's tile columns side by
+// side) into the tiles (bj, bi), bj < nloc, of the chunks Lch[bj][bi][r][c]; bi < mloc; rounds once to T.
+void launch_scatter_stage(hipStream_t s, const double *stage, int64_t lds_, double *Lch, int nloc, int mloc, int bi, int nb);
+void launch_scatter_stage(hipStream_t s, const double *stage, int64_t lds_, float *Lch, int nloc, int mloc, int bi, int nb);
+// launch_transpose_rect: dst (cols x rows, ldd) = src (rows x cols, lds_)^T; rows and cols multiples of 32 (whole tiles; a
+// remainder is neither read nor written).
+void launch_transpose_rect(hipStream_t s, const double *src, int64_t lds_, double *dst, int64_t ldd, int64_t rows, int cols);
+void launch_transpose_rect(hipStream_t s, const float *src, int64_t lds_, float *dst, int64_t ldd, int64_t rows, int cols);
+// launch_copy_block: dst (rows x nb, contiguous) = the rows x nb block at src (ld).  launch_residual_block: W (rows x nb,
+// contiguous) = Ks block - (U block + recv[0] + .. + recv[nrecv - 1]) with Ks, U of leading dimension ld and the nrecv
+// received blocks rows x nb contiguous, one behind the other; summed in fp64 in that order, rounded to T once.
+void launch_copy_block(hipStream_t s, double *dst, const double *src, int64_t ld, int nb, int64_t rows);
+void launch_residual_block(hipStream_t s, double *W, const double *Ks, const double *U, int64_t ld, const double *recv,
+                           int nrecv, int nb, int64_t rows);
+void launch_residual_block(hipStream_t s, float *W, const float *Ks, const double *U, int64_t ld, const double *recv,
+                           int nrecv, int nb, int64_t rows);
+void launch_residual_from(hipStream_t s, double *kv, const double *y, int64_t count);  // kv := y - kv
+void launch_add_inplace(hipStream_t s, double *a, const double *b, int64_t count);    // a += b; grid-stride, 1024 workgroups
+void launch_add_inplace(hipStream_t s, float *a, const float *b, int64_t count);
+void launch_scale(hipStream_t s, double *a, double f, int64_t count);                 // a *= f
+void launch_add_vec(hipStream_t s, double *a, const double *b, int64_t count);        // a += b
 
 }  // namespace gogp

@@ -408,7 +408,7 @@ __global__ void residual_from_kernel(double *__restrict__ kv, const double *__re
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < count) kv[i] = y[i] - kv[i];
 }
-static void launch_residual_from(hipStream_t s, double *kv, const double *y, int64_t count) {  // kv := y - kv
+void gogp::launch_residual_from(hipStream_t s, double *kv, const double *y, int64_t count) {  // kv := y - kv
   if (count <= 0) return;
   hipLaunchKernelGGL(residual_from_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, kv, y, (long)count);
 }
@@ -417,6 +417,10 @@ __global__ void gather_rows_kernel(const double *__restrict__ y, double *__restr
                                    BlockMap map) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < rows) yloc[i] = y[map.grow(i)];
+}
+void gogp::launch_gather_rows(hipStream_t s, const double *y, double *yloc, int64_t rows, BlockMap map) {
+  if (rows <= 0) return;
+  hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, y, yloc, (long)rows, map);
 }
 
 // ---- the diagonal tile: factor + inverse of one nb x nb block on the chain stream -----------
@@ -523,8 +527,7 @@ static int dist_factorize_t(gogp_handle *h, bool want_kinv) {
   HIPCHK(h, hipMemsetAsync(d->red, 0, ((size_t)npad + 1 + d->nranks) * sizeof(double), s));
   HIPCHK(h, hipMemsetAsync(d->ared, 0, (size_t)npad * sizeof(double), s));
   const long lrows = (long)mloc * nb;
-  hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((lrows + 255) / 256)), dim3(256), 0, s, h->dy,
-                     d->yloc, lrows, d->map());
+  launch_gather_rows(s, h->dy, d->yloc, lrows, d->map());
   // every rank builds its own tiles of K (X is replicated): no communication for the O(N^2) step;
   // the strictly upper blocks are zero-filled (R)
   launch_gram_local(s, h->devP, h->D, h->dX, h->n, (int64_t)mloc * nb, (int64_t)nloc * nb, d->map(), A,
@@ -814,8 +817,7 @@ static int dist_factorize_t(gogp_handle *h, bool want_kinv) {
                            REFINE_SLABS, h->rw, h->radial1, h->ev());
       TRCHK(d->tr->allreduce(sc, h->rw, npad, &e_));
       launch_residual_from(sc, h->rw, h->dy, npad);  // rw := y - K alpha, then its local rows
-      hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((lrows + 255) / 256)), dim3(256), 0, sc, h->rw,
-                         d->rloc, lrows, d->map());
+      launch_gather_rows(sc, h->rw, d->rloc, lrows, d->map());
       // both reduction vectors start from zero: every rank fills only its own panels / rows
       HIPCHK(h, hipMemsetAsync(d->red, 0, (size_t)npad * sizeof(double), sc));
       HIPCHK(h, hipMemsetAsync(d->ared, 0, (size_t)npad * sizeof(double), sc));
@@ -904,6 +906,20 @@ __global__ void scatter_tile_kernel(const T *__restrict__ src, int nb, double *_
     if (gc < n && (!diag || gc <= r)) dst[r * n + gc] = (double)src[(long)blockIdx.x * nb + c];
   }
 }
+template <class T>
+static void scatter_tile_t(hipStream_t s, const T *src, int nb, double *dst, int64_t n, int64_t row0, int64_t col0,
+                           int diag) {
+  hipLaunchKernelGGL(scatter_tile_kernel<T>, dim3(nb), dim3(256), 0, s, src, nb, dst, (long)n, (long)row0, (long)col0,
+                     diag);
+}
+void gogp::launch_scatter_tile(hipStream_t s, const double *src, int nb, double *dst, int64_t n, int64_t row0,
+                               int64_t col0, int diag) {
+  scatter_tile_t(s, src, nb, dst, n, row0, col0, diag);
+}
+void gogp::launch_scatter_tile(hipStream_t s, const float *src, int nb, double *dst, int64_t n, int64_t row0,
+                               int64_t col0, int diag) {
+  scatter_tile_t(s, src, nb, dst, n, row0, col0, diag);
+}
 
 // Collective agreement before a large collective: every rank contributes its own failure flag; if any
 // rank failed (an allocation, a bad argument) ALL return the error instead of some of them blocking in the
@@ -965,9 +981,8 @@ static int dist_get_factor_t(gogp_handle *h, double *Lout) {
         const int64_t gP = (int64_t)bj * d->Pc + d->pc;
         if (gI < gP || gP * nb >= n) continue;
         // (the kernel's destination is the band: row index relative to r0)
-        hipLaunchKernelGGL(scatter_tile_kernel<T>, dim3(nb), dim3(256), 0, d->sc,
-                           d->lchunk<T>(bj) + (size_t)bi * nb * nb, nb, tmp - (size_t)r0 * n, (long)n, (long)gI * nb,
-                           (long)gP * nb, gI == gP ? 1 : 0);
+        launch_scatter_tile(d->sc, d->lchunk<T>(bj) + (size_t)bi * nb * nb, nb, tmp - (size_t)r0 * n, n, gI * nb,
+                            gP * nb, gI == gP ? 1 : 0);
       }
     }
     if (e == hipSuccess) rc = d->tr->allreduce(d->sc, tmp, rows * n, &terr);
@@ -1016,13 +1031,29 @@ __global__ void gather_rows_of_l_kernel(const T *__restrict__ Lch, int mloc, int
     }
   }
 }
+template <class T>
+static void gather_rows_of_l_t(hipStream_t s, const T *Lch, int mloc, int nloc, int nb, BlockMap map, const int64_t *rows,
+                               int64_t nrows, int64_t n, int diag_only, double *out) {
+  const int64_t nblocks = diag_only ? n : nrows;
+  if (nblocks <= 0) return;
+  hipLaunchKernelGGL(gather_rows_of_l_kernel<T>, dim3((unsigned)nblocks), dim3(256), 0, s, Lch, mloc, nloc, nb, map,
+                     reinterpret_cast<const long *>(rows), (long)nrows, (long)n, diag_only, out);
+}
+void gogp::launch_gather_rows_of_l(hipStream_t s, const double *Lch, int mloc, int nloc, int nb, BlockMap map,
+                                   const int64_t *rows, int64_t nrows, int64_t n, int diag_only, double *out) {
+  gather_rows_of_l_t(s, Lch, mloc, nloc, nb, map, rows, nrows, n, diag_only, out);
+}
+void gogp::launch_gather_rows_of_l(hipStream_t s, const float *Lch, int mloc, int nloc, int nb, BlockMap map,
+                                   const int64_t *rows, int64_t nrows, int64_t n, int diag_only, double *out) {
+  gather_rows_of_l_t(s, Lch, mloc, nloc, nb, map, rows, nrows, n, diag_only, out);
+}
 
 template <class T>
 static int dist_get_factor_part_t(gogp_handle *h, const int64_t *rows, int64_t nrows, double *out) {
   Dist2D *d = h->dist;
   const int64_t n = h->n;
   const bool diag_only = rows == nullptr;
-  const int64_t count = diag_only ? n : nrows * n, nblocks = diag_only ? n : nrows;
+  const int64_t count = diag_only ? n : nrows * n;
   for (hipStream_t qs : {h->s, h->sp, h->st, h->s2, d->sc}) HIPCHK(h, hipStreamSynchronize(qs));
   int bad = 0;
   for (int64_t k = 0; !diag_only && k < nrows; ++k)
@@ -1049,9 +1080,8 @@ static int dist_get_factor_part_t(gogp_handle *h, const int64_t *rows, int64_t n
       e = hipMemcpyAsync(drows, rows, (size_t)nrows * sizeof(long), hipMemcpyHostToDevice, d->sc);
   }
   if (e == hipSuccess)
-    hipLaunchKernelGGL(gather_rows_of_l_kernel<T>, dim3((unsigned)nblocks), dim3(256), 0, d->sc,
-                       d->mat<T>(d->Lch), d->mloc, d->nloc, d->nb, d->map(), drows, (long)nrows, (long)n,
-                       diag_only ? 1 : 0, tmp);
+    launch_gather_rows_of_l(d->sc, d->mat<T>(d->Lch), d->mloc, d->nloc, d->nb, d->map(),
+                            reinterpret_cast<const int64_t *>(drows), nrows, n, diag_only ? 1 : 0, tmp);
   int rc = GOGP_OK;
   std::string terr;
   if (e == hipSuccess) rc = d->tr->allreduce(d->sc, tmp, count, &terr);
@@ -1092,6 +1122,21 @@ __global__ void scatter_stage_kernel(const double *__restrict__ stage, long lds_
   const int bj = (int)(cc / nb), c = (int)(cc - (long)bj * nb);
   Lch[((size_t)bj * mloc + bi) * nb * nb + (size_t)r * nb + c] = (T)stage[(long)r * lds_ + cc];
 }
+template <class T>
+static void scatter_stage_t(hipStream_t s, const double *stage, int64_t lds_, T *Lch, int nloc, int mloc, int bi, int nb) {
+  const size_t stage_elems = (size_t)nb * nloc * nb;
+  if (!stage_elems) return;
+  hipLaunchKernelGGL(scatter_stage_kernel<T>, dim3((unsigned)((stage_elems + 255) / 256)), dim3(256), 0, s, stage,
+                     (long)lds_, Lch, nloc, mloc, bi, nb);
+}
+void gogp::launch_scatter_stage(hipStream_t s, const double *stage, int64_t lds_, double *Lch, int nloc, int mloc, int bi,
+                                int nb) {
+  scatter_stage_t(s, stage, lds_, Lch, nloc, mloc, bi, nb);
+}
+void gogp::launch_scatter_stage(hipStream_t s, const double *stage, int64_t lds_, float *Lch, int nloc, int mloc, int bi,
+                                int nb) {
+  scatter_stage_t(s, stage, lds_, Lch, nloc, mloc, bi, nb);
+}
 
 template <class T>
 static int dist_set_factor_t(gogp_handle *h, const double *Lin, const double *alpha) {
@@ -1130,8 +1175,7 @@ static int dist_set_factor_t(gogp_handle *h, const double *Lin, const double *al
     }
     e = hipMemcpyAsync(dst, hst, stage_elems * sizeof(double), hipMemcpyHostToDevice, s);
     if (e == hipSuccess) {
-      hipLaunchKernelGGL(scatter_stage_kernel<T>, dim3((unsigned)((stage_elems + 255) / 256)), dim3(256), 0, s, dst,
-                         (long)nloc * nb, d->mat<T>(d->Lch), nloc, mloc, bi, nb);
+      launch_scatter_stage(s, dst, (int64_t)nloc * nb, d->mat<T>(d->Lch), nloc, mloc, bi, nb);
       e = hipStreamSynchronize(s);  // the staging buffer is refilled by the next tile row
     }
   }
@@ -1196,6 +1240,12 @@ __global__ void gather_x_kernel(const double *__restrict__ X, const double *__re
   for (int k = 0; k < D; ++k) Xloc[i * D + k] = (g < n) ? X[g * D + k] : 0.0;
   aloc[i] = (g < n) ? a[g] : 0.0;
 }
+void gogp::launch_gather_x(hipStream_t s, const double *X, const double *a, int D, int64_t n, int64_t rows, BlockMap map,
+                           double *Xloc, double *aloc) {
+  if (rows <= 0) return;
+  hipLaunchKernelGGL(gather_x_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, X, a, D, (long)n, (long)rows,
+                     map, Xloc, aloc);
+}
 
 // dst (cols x rows, ldd) = src (rows x cols, lds)^T; rows, cols multiples of 32
 template <class T>
@@ -1248,6 +1298,56 @@ __global__ void add_vec_kernel(double *__restrict__ a, const double *__restrict_
   if (i < count) a[i] += b[i];
 }
 
+template <class T>
+static void transpose_rect_t(hipStream_t s, const T *src, int64_t lds_, T *dst, int64_t ldd, int64_t rows, int cols) {
+  if (rows < 32 || cols < 32) return;
+  hipLaunchKernelGGL(transpose_rect_kernel<T>, dim3((unsigned)((rows / 32) * (cols / 32))), dim3(256), 0, s, src,
+                     (long)lds_, dst, (long)ldd, cols / 32);
+}
+template <class T>
+static void residual_block_t(hipStream_t s, T *W, const T *Ks, const double *U, int64_t ld, const double *recv, int nrecv,
+                             int nb, int64_t rows) {
+  if (rows <= 0 || nb <= 0) return;
+  hipLaunchKernelGGL(residual_block_kernel<T>, dim3((unsigned)((rows * nb + 255) / 256)), dim3(256), 0, s, W, Ks, U,
+                     (long)ld, recv, nrecv, nb, (long)rows);
+}
+namespace gogp {
+void launch_transpose_rect(hipStream_t s, const double *src, int64_t lds_, double *dst, int64_t ldd, int64_t rows,
+                           int cols) {
+  transpose_rect_t(s, src, lds_, dst, ldd, rows, cols);
+}
+void launch_transpose_rect(hipStream_t s, const float *src, int64_t lds_, float *dst, int64_t ldd, int64_t rows, int cols) {
+  transpose_rect_t(s, src, lds_, dst, ldd, rows, cols);
+}
+void launch_add_inplace(hipStream_t s, double *a, const double *b, int64_t count) {
+  hipLaunchKernelGGL(add_inplace_kernel<double>, dim3(1024), dim3(256), 0, s, a, b, (long)count);
+}
+void launch_add_inplace(hipStream_t s, float *a, const float *b, int64_t count) {
+  hipLaunchKernelGGL(add_inplace_kernel<float>, dim3(1024), dim3(256), 0, s, a, b, (long)count);
+}
+void launch_scale(hipStream_t s, double *a, double f, int64_t count) {
+  if (count <= 0) return;
+  hipLaunchKernelGGL(scale_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, a, f, (long)count);
+}
+void launch_add_vec(hipStream_t s, double *a, const double *b, int64_t count) {
+  if (count <= 0) return;
+  hipLaunchKernelGGL(add_vec_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, a, b, (long)count);
+}
+void launch_copy_block(hipStream_t s, double *dst, const double *src, int64_t ld, int nb, int64_t rows) {
+  if (rows <= 0 || nb <= 0) return;
+  hipLaunchKernelGGL(copy_block_kernel<double>, dim3((unsigned)((rows * nb + 255) / 256)), dim3(256), 0, s, dst, src,
+                     (long)ld, nb, (long)rows);
+}
+void launch_residual_block(hipStream_t s, double *W, const double *Ks, const double *U, int64_t ld, const double *recv,
+                           int nrecv, int nb, int64_t rows) {
+  residual_block_t(s, W, Ks, U, ld, recv, nrecv, nb, rows);
+}
+void launch_residual_block(hipStream_t s, float *W, const float *Ks, const double *U, int64_t ld, const double *recv,
+                           int nrecv, int nb, int64_t rows) {
+  residual_block_t(s, W, Ks, U, ld, recv, nrecv, nb, rows);
+}
+}  // namespace gogp
+
 // Float shards: V = L^-1 Kstar by a distributed blocked forward substitution with the float L tiles
 // and the (fp64-computed) tile inverses, instead of V = Y^T Kstar with the explicit fp32 inverse --
 // sigma^2 = prior - |V|^2 cancels, and the substitution's error does not grow with cond(L).
@@ -1290,7 +1390,6 @@ static int produce_v_by_substitution(gogp_handle *h, Dist2D *d, const T *KsT, in
     return fail(h, GOGP_ENOMEM, "Produce: out of device memory");
   }
   const T *Dinv = d->mat<T>(d->Dinv);
-  const unsigned cb = (unsigned)((blk + 255) / 256);
   std::vector<XferOp> ops;
   std::string terr;
   int rc = GOGP_OK;
@@ -1301,8 +1400,7 @@ static int produce_v_by_substitution(gogp_handle *h, Dist2D *d, const T *KsT, in
     // ---- a. partial sums of block Q to the owner
     ops.clear();
     if (in_row && !owner) {
-      hipLaunchKernelGGL(copy_block_kernel<double>, dim3(cb), dim3(256), 0, s, sendb, UT + (size_t)bi * nb,
-                         (long)lrows, nb, (long)mpad);
+      launch_copy_block(s, sendb, UT + (size_t)bi * nb, lrows, nb, mpad);
       rec(h, E(Q, 0), s);
       wait(h, sc, E(Q, 0));
       ops.push_back(xop<double>(d->rank_of(pr, kc), true, sendb, (int64_t)blk));
@@ -1320,12 +1418,11 @@ static int produce_v_by_substitution(gogp_handle *h, Dist2D *d, const T *KsT, in
     if (owner) {
       rec(h, E(Q, 1), sc);
       wait(h, s, E(Q, 1));
-      hipLaunchKernelGGL(residual_block_kernel<T>, dim3(cb), dim3(256), 0, s, Wq, KsT + (size_t)bi * nb,
-                         UT + (size_t)bi * nb, (long)lrows, recv, Pc - 1, nb, (long)mpad);
+      launch_residual_block(s, Wq, KsT + (size_t)bi * nb, UT + (size_t)bi * nb, lrows, recv, Pc - 1, nb, mpad);
       // V_Q^T (mpad x nb) = W_Q^T inv(L_QQ)^T
       launch_gemm_nt(s, GEMM_RECT, mt, d->tpb, nb, 1.0, Wq, nb, Dinv + (size_t)Q * nb2, nb, 0.0, Vq, nb, nullptr);
       launch_rownorm_dot(s, Vq, nb, nullptr, nb, m, nullptr, qtmp);
-      hipLaunchKernelGGL(add_vec_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, qsum, qtmp, (long)m);
+      launch_add_vec(s, qsum, qtmp, m);
       rec(h, E(Q, 2), s);
       wait(h, sc, E(Q, 2));
     }
@@ -1420,8 +1517,7 @@ static int dist_produce_t(gogp_handle *h, const double *Z, int64_t m, double *mu
     HIPCHK(h, e);
   }
   launch_prior(s, h->devP, dZ, m, prior);  // gp/gp.go:269-278
-  hipLaunchKernelGGL(gather_x_kernel, dim3((unsigned)((lrows + 255) / 256)), dim3(256), 0, s, h->dX,
-                     h->alpha, h->D, (long)h->n, (long)lrows, d->map(), Xloc, aloc);
+  launch_gather_x(s, h->dX, h->alpha, h->D, h->n, lrows, d->map(), Xloc, aloc);
   // local rows are in increasing global order: the valid ones (global row < n) form a prefix
   int64_t nvalid = 0;
   {
@@ -1436,8 +1532,7 @@ static int dist_produce_t(gogp_handle *h, const double *Z, int64_t m, double *mu
   launch_cross(s, h->devP, h->D, Xloc, nvalid, lrows, dZ, m, mpad, Ks, lrows, h->ev());
   launch_rownorm_dot(s, Ks, lrows, aloc, lrows, m, red2, nullptr);  // partial mu = Kstar^T alpha (:335)
   if (Pc > 1)  // the Pc ranks of a process row hold the same tile rows
-    hipLaunchKernelGGL(scale_kernel, dim3((unsigned)((mpad + 255) / 256)), dim3(256), 0, s, red2, 1.0 / Pc,
-                       (long)mpad);
+    launch_scale(s, red2, 1.0 / Pc, mpad);
   const int mt = (int)(mpad / TILE);
   if (by_substitution) {
     const int rcs = produce_v_by_substitution<T>(h, d, Ks, lrows, mpad, m, red2 + mpad, qtmp, s, sc);
@@ -1451,8 +1546,7 @@ static int dist_produce_t(gogp_handle *h, const double *Z, int64_t m, double *mu
     const int bi0 = first_gt(P, pr, Pr);
     if (bi0 <= 0) continue;
     const int64_t K = (int64_t)bi0 * nb;
-    hipLaunchKernelGGL(transpose_rect_kernel<T>, dim3((unsigned)((K / 32) * (nb / 32))), dim3(256), 0, s,
-                       d->ychunk<T>(bj), (long)nb, Yt, (long)K, nb / 32);
+    launch_transpose_rect(s, d->ychunk<T>(bj), nb, Yt, K, K, nb);
     launch_gemm_nt(s, GEMM_RECT, mt, d->tpb, K, 1.0, Ks, lrows, Yt, K, 0.0, Vt + (size_t)bj * nb, lcols,
                    nullptr);
   }
@@ -1479,14 +1573,12 @@ static int dist_produce_t(gogp_handle *h, const double *Z, int64_t m, double *mu
     rec(h, EV_FWD, sc);
     wait(h, s, EV_FWD);
     for (int i = 0; i < Pr - 1; ++i)
-      hipLaunchKernelGGL(add_inplace_kernel<T>, dim3(1024), dim3(256), 0, s, Vt, Vr + (size_t)i * mpad * lcols,
-                         (long)(mpad * lcols));
+      launch_add_inplace(s, Vt, Vr + (size_t)i * mpad * lcols, mpad * lcols);
   }
   // |V_j|^2 over my tile columns; every rank of a process column holds the same sums
   if (!by_substitution) launch_rownorm_dot(s, Vt, lcols, nullptr, lcols, m, nullptr, red2 + mpad);
   if (Pr > 1 && !by_substitution)
-    hipLaunchKernelGGL(scale_kernel, dim3((unsigned)((mpad + 255) / 256)), dim3(256), 0, s, red2 + mpad,
-                       1.0 / Pr, (long)mpad);
+    launch_scale(s, red2 + mpad, 1.0 / Pr, mpad);
   rec(h, EV_W, s);
   wait(h, sc, EV_W);
   {

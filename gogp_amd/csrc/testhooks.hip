@@ -2089,3 +2089,476 @@ extern "C" int gogp_test_nv_gradient(int device, const double *Kinv, int64_t kin
   if (alpha_len < n || dv_len < n) return GOGP_EARG;
   return fin_run(device, arrs, [&](double **d) { launch_nv_gradient(0, d[0], ld, d[1], n, d[2]); });
 }
+
+// ---- the kernels of the sharded path (dist2d.hip and the "helpers of the sharded evaluation" of solve.hip) and the rest of
+// solve.hip -- the LML scalars, the fp64 trace, the layout kernels around the factor, the one-line vector kernels --
+// through their product launchers (tests/test_shard_kernels.py).  The rules of the hooks above: every argument is checked
+// before the device is touched, every array goes to the device whole and every in / out array comes back whole.  Arrays
+// typed `void *` hold doubles (precision 64) or floats (32); lengths count elements.
+namespace {
+struct ShArr {
+  const void *h;
+  int64_t len;
+  int es;  // bytes per element
+  bool out;
+  bool opt = false;  // may be NULL (with length 0)
+};
+bool sh_have(std::initializer_list<ShArr> arrs) {
+  for (const ShArr &a : arrs) {
+    if (a.opt && !a.h) {
+      if (a.len != 0) return false;
+      continue;
+    }
+    if (!a.h || a.len <= 0) return false;
+  }
+  return true;
+}
+template <class F>
+int sh_run(int device, std::initializer_list<ShArr> arrs, F &&launch) {
+  if (!device_ok(device)) return GOGP_EHIP;
+  std::vector<DevCopy> dc(arrs.size());
+  std::vector<char *> d;
+  hipError_t e = hipSuccess;
+  size_t i = 0;
+  for (const ShArr &a : arrs) {
+    if (e == hipSuccess) e = dc[i].up(a.h, a.h ? (size_t)a.len * (size_t)a.es : 0);
+    d.push_back(dc[i++].d);
+  }
+  if (e == hipSuccess) {
+    launch(d.data());
+    tl_batch.k = 1;
+    tl_batch.stride = 0;
+    e = launched();
+  }
+  i = 0;
+  for (const ShArr &a : arrs) {
+    if (e == hipSuccess && a.out && a.h) e = dc[i].down(const_cast<void *>(a.h));
+    ++i;
+  }
+  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+}
+#define SH_D(i) reinterpret_cast<double *>(d[i])
+#define SH_F(i) reinterpret_cast<float *>(d[i])
+constexpr int64_t SH_COUNT_MAX = 1 << 26;
+// the block map of rank (pr, pc) of a Pr x Pc grid with tiles of 2^nb_shift; false for what no rank can be
+bool sh_map(int nb_shift, int Pr, int Pc, int pr, int pc, BlockMap *m) {
+  if (nb_shift < 5 || nb_shift > 10 || Pr < 1 || Pr > 8 || Pc < 1 || Pc > 8 || pr < 0 || pr >= Pr || pc < 0 || pc >= Pc)
+    return false;
+  m->nb_shift = nb_shift;
+  m->Pr = Pr;
+  m->Pc = Pc;
+  m->pr = pr;
+  m->pc = pc;
+  return true;
+}
+// local tile counts of one rank: the product pads so that the grid divides the tile count, NB = mloc Pr = nloc Pc
+bool sh_tiles(int mloc, int nloc, const BlockMap &m) {
+  return mloc >= 1 && nloc >= 1 && mloc <= 64 && nloc <= 64 && (int64_t)mloc * m.Pr == (int64_t)nloc * m.Pc;
+}
+// candidate batch of a launcher that reads tl_batch: k == 1 (stride ignored) or 2 .. 16 candidates `bstride` elements apart
+bool sh_batch(int precision, int k, int64_t *bstride) {
+  if (k < 1 || k > GOGP_MAX_CANDIDATES) return false;
+  if (k == 1) {
+    *bstride = 0;
+    return true;
+  }
+  return precision == 64 && *bstride > 0 && *bstride % 2 == 0;  // the float launchers do not batch
+}
+void sh_set_batch(int k, int64_t bstride) {
+  tl_batch.k = k;
+  tl_batch.stride = (long)(bstride * 8);
+}
+}  // namespace
+
+extern "C" int64_t gogp_test_chunk_tdot_scratch(int64_t rows, int nb) {
+  if (rows < 1 || rows > SH_COUNT_MAX || nb < 64 || nb > 1024 || nb % 64) return -1;
+  return chunk_tdot_scratch(rows, nb);
+}
+
+extern "C" int gogp_test_gather_rows(int device, const double *y, int64_t y_len, int64_t rows, int nb_shift, int Pr, int Pc,
+                                     int pr, int pc, double *yloc, int64_t yloc_len) {
+  const std::initializer_list<ShArr> arrs = {{y, y_len, 8, false}, {yloc, yloc_len, 8, true}};
+  BlockMap m;
+  if (!sh_have(arrs) || !sh_map(nb_shift, Pr, Pc, pr, pc, &m)) return GOGP_EARG;
+  if (rows < 1 || rows > SH_COUNT_MAX || rows % (1 << nb_shift) || yloc_len < rows || y_len < m.grow(rows - 1) + 1)
+    return GOGP_EARG;
+  return sh_run(device, arrs, [&](char **d) { launch_gather_rows(0, SH_D(0), SH_D(1), rows, m); });
+}
+
+extern "C" int gogp_test_gather_x(int device, const double *X, int64_t x_len, const double *a, int64_t a_len, int D, int64_t n,
+                                  int64_t rows, int nb_shift, int Pr, int Pc, int pr, int pc, double *Xloc, int64_t xloc_len,
+                                  double *aloc, int64_t aloc_len) {
+  const std::initializer_list<ShArr> arrs = {{X, x_len, 8, false}, {a, a_len, 8, false}, {Xloc, xloc_len, 8, true},
+                                             {aloc, aloc_len, 8, true}};
+  BlockMap m;
+  if (!sh_have(arrs) || !sh_map(nb_shift, Pr, Pc, pr, pc, &m) || D < 1 || D > GOGP_MAX_NDIM) return GOGP_EARG;
+  if (rows < 1 || rows > SH_COUNT_MAX || rows % (1 << nb_shift) || n < 1 || n > SH_COUNT_MAX) return GOGP_EARG;
+  if (x_len < n * D || a_len < n || xloc_len < rows * D || aloc_len < rows) return GOGP_EARG;
+  return sh_run(device, arrs, [&](char **d) { launch_gather_x(0, SH_D(0), SH_D(1), D, n, rows, m, SH_D(2), SH_D(3)); });
+}
+
+extern "C" int gogp_test_scatter_tile(int device, int precision, const void *src, int64_t src_len, int nb, int64_t n,
+                                      int64_t row0, int64_t col0, int diag, int64_t r0, double *dst, int64_t dst_len) {
+  if (!prec_ok(precision)) return GOGP_EARG;
+  const std::initializer_list<ShArr> arrs = {{src, src_len, precision / 8, false}, {dst, dst_len, 8, true}};
+  if (!sh_have(arrs) || nb < 1 || nb > 1024 || n < 1 || n > TH_NPAD_MAX || (diag != 0 && diag != 1)) return GOGP_EARG;
+  if (r0 < 0 || row0 < r0 || row0 >= n || col0 < 0 || col0 >= n || src_len < (int64_t)nb * nb) return GOGP_EARG;
+  const int64_t rend = row0 + nb < n ? row0 + nb : n;  // dst is the band of the rows from r0 on
+  if (dst_len < (rend - r0) * n) return GOGP_EARG;
+  return sh_run(device, arrs, [&](char **d) {
+    if (precision == 64)
+      launch_scatter_tile(0, SH_D(0), nb, SH_D(1) - r0 * n, n, row0, col0, diag);
+    else
+      launch_scatter_tile(0, SH_F(0), nb, SH_D(1) - r0 * n, n, row0, col0, diag);
+  });
+}
+
+extern "C" int gogp_test_gather_rows_of_l(int device, int precision, const void *Lch, int64_t lch_len, int mloc, int nloc,
+                                          int nb_shift, int Pr, int Pc, int pr, int pc, const int64_t *rows, int64_t rows_len,
+                                          int64_t n, int diag_only, double *out, int64_t out_len) {
+  if (!prec_ok(precision) || (diag_only != 0 && diag_only != 1)) return GOGP_EARG;
+  const std::initializer_list<ShArr> arrs = {{Lch, lch_len, precision / 8, false}, {rows, rows_len, 8, false, diag_only == 1},
+                                             {out, out_len, 8, true}};
+  BlockMap m;
+  if (!sh_have(arrs) || !sh_map(nb_shift, Pr, Pc, pr, pc, &m) || !sh_tiles(mloc, nloc, m)) return GOGP_EARG;
+  const int64_t nb = 1 << nb_shift;
+  if (diag_only && rows) return GOGP_EARG;
+  if (n < 1 || n > (int64_t)mloc * Pr * nb || lch_len < (int64_t)nloc * mloc * nb * nb) return GOGP_EARG;
+  if (rows_len > 65535 || out_len < (diag_only ? n : rows_len * n)) return GOGP_EARG;
+  for (int64_t k = 0; k < rows_len; ++k)
+    if (rows[k] < 0 || rows[k] >= n) return GOGP_EARG;  // the kernel indexes the chunks with them
+  return sh_run(device, arrs, [&](char **d) {
+    const int64_t *dr = reinterpret_cast<const int64_t *>(d[1]);
+    if (precision == 64)
+      launch_gather_rows_of_l(0, SH_D(0), mloc, nloc, (int)nb, m, dr, rows_len, n, diag_only, SH_D(2));
+    else
+      launch_gather_rows_of_l(0, SH_F(0), mloc, nloc, (int)nb, m, dr, rows_len, n, diag_only, SH_D(2));
+  });
+}
+
+extern "C" int gogp_test_scatter_stage(int device, int precision, const double *stage, int64_t stage_len, int64_t lds_,
+                                       void *Lch, int64_t lch_len, int nloc, int mloc, int bi, int nb) {
+  if (!prec_ok(precision)) return GOGP_EARG;
+  const std::initializer_list<ShArr> arrs = {{stage, stage_len, 8, false}, {Lch, lch_len, precision / 8, true}};
+  if (!sh_have(arrs) || nloc < 1 || nloc > 64 || mloc < 1 || mloc > 64 || bi < 0 || bi >= mloc || nb < 1 || nb > 1024)
+    return GOGP_EARG;
+  if (!covers(stage_len, 0, lds_, nb, (int64_t)nloc * nb, 1, 0) || lch_len < (int64_t)nloc * mloc * nb * nb) return GOGP_EARG;
+  return sh_run(device, arrs, [&](char **d) {
+    if (precision == 64)
+      launch_scatter_stage(0, SH_D(0), lds_, SH_D(1), nloc, mloc, bi, nb);
+    else
+      launch_scatter_stage(0, SH_D(0), lds_, SH_F(1), nloc, mloc, bi, nb);
+  });
+}
+
+extern "C" int gogp_test_transpose_rect(int device, int precision, const void *src, int64_t src_len, int64_t lds_, void *dst,
+                                        int64_t dst_len, int64_t ldd, int64_t rows, int cols) {
+  if (!prec_ok(precision)) return GOGP_EARG;
+  const std::initializer_list<ShArr> arrs = {{src, src_len, precision / 8, false}, {dst, dst_len, precision / 8, true}};
+  if (!sh_have(arrs) || rows < 32 || cols < 32 || rows % 32 || cols % 32 || rows > (1 << 16) || cols > (1 << 16))
+    return GOGP_EARG;
+  if (!covers(src_len, 0, lds_, rows, cols, 1, 0) || !covers(dst_len, 0, ldd, cols, rows, 1, 0)) return GOGP_EARG;
+  return sh_run(device, arrs, [&](char **d) {
+    if (precision == 64)
+      launch_transpose_rect(0, SH_D(0), lds_, SH_D(1), ldd, rows, cols);
+    else
+      launch_transpose_rect(0, SH_F(0), lds_, SH_F(1), ldd, rows, cols);
+  });
+}
+
+extern "C" int gogp_test_transpose_sq(int device, int precision, const void *src, int64_t src_len, int64_t lds_, void *dst,
+                                      int64_t dst_len, int64_t ldd, int n) {
+  if (!prec_ok(precision)) return GOGP_EARG;
+  const std::initializer_list<ShArr> arrs = {{src, src_len, precision / 8, false}, {dst, dst_len, precision / 8, true}};
+  if (!sh_have(arrs) || n < 32 || n % 32 || n > (1 << 13)) return GOGP_EARG;
+  if (!covers(src_len, 0, lds_, n, n, 1, 0) || !covers(dst_len, 0, ldd, n, n, 1, 0)) return GOGP_EARG;
+  return sh_run(device, arrs, [&](char **d) {
+    if (precision == 64)
+      launch_transpose_sq(0, SH_D(0), lds_, SH_D(1), ldd, n);
+    else
+      launch_transpose_sq(0, SH_F(0), lds_, SH_F(1), ldd, n);
+  });
+}
+
+extern "C" int gogp_test_copy_block(int device, double *dst, int64_t dst_len, const double *src, int64_t src_len, int64_t ld,
+                                    int nb, int64_t rows) {
+  const std::initializer_list<ShArr> arrs = {{dst, dst_len, 8, true}, {src, src_len, 8, false}};
+  if (!sh_have(arrs) || nb < 1 || nb > 1024 || rows < 1 || rows > (1 << 16)) return GOGP_EARG;
+  if (dst_len < rows * nb || !covers(src_len, 0, ld, rows, nb, 1, 0)) return GOGP_EARG;
+  return sh_run(device, arrs, [&](char **d) { launch_copy_block(0, SH_D(0), SH_D(1), ld, nb, rows); });
+}
+
+extern "C" int gogp_test_residual_block(int device, int precision, void *W, int64_t w_len, const void *Ks, int64_t ks_len,
+                                        const double *U, int64_t u_len, int64_t ld, const double *recv, int64_t recv_len,
+                                        int nrecv, int nb, int64_t rows) {
+  if (!prec_ok(precision) || nrecv < 0 || nrecv > 64) return GOGP_EARG;
+  const std::initializer_list<ShArr> arrs = {{W, w_len, precision / 8, true}, {Ks, ks_len, precision / 8, false},
+                                             {U, u_len, 8, false}, {recv, recv_len, 8, false, nrecv == 0}};
+  if (!sh_have(arrs) || nb < 1 || nb > 1024 || rows < 1 || rows > (1 << 16) || (nrecv == 0 && recv)) return GOGP_EARG;
+  if (w_len < rows * nb || !covers(ks_len, 0, ld, rows, nb, 1, 0) || !covers(u_len, 0, ld, rows, nb, 1, 0) ||
+      recv_len < (int64_t)nrecv * rows * nb)
+    return GOGP_EARG;
+  return sh_run(device, arrs, [&](char **d) {
+    if (precision == 64)
+      launch_residual_block(0, SH_D(0), SH_D(1), SH_D(2), ld, SH_D(3), nrecv, nb, rows);
+    else
+      launch_residual_block(0, SH_F(0), SH_F(1), SH_D(2), ld, SH_D(3), nrecv, nb, rows);
+  });
+}
+
+extern "C" int gogp_test_pack_blocks(int device, double *dst, int64_t dst_len, const double *src, int64_t src_len, int nblk,
+                                     int64_t blk, int first, int stride) {
+  const std::initializer_list<ShArr> arrs = {{dst, dst_len, 8, true}, {src, src_len, 8, false}};
+  if (!sh_have(arrs) || nblk < 1 || nblk > 65535 || blk < 2 || blk % 2 || blk > SH_COUNT_MAX || first < 0 || stride < 1 ||
+      first > 4096 || stride > 4096)
+    return GOGP_EARG;
+  if (dst_len < (int64_t)nblk * blk || src_len < ((int64_t)first + (int64_t)(nblk - 1) * stride + 1) * blk) return GOGP_EARG;
+  return sh_run(device, arrs, [&](char **d) { launch_pack_blocks(0, SH_D(0), SH_D(1), nblk, blk, first, stride); });
+}
+
+extern "C" int gogp_test_convert_block(int device, int precision, int precision2, const void *src, int64_t src_len,
+                                       int64_t lds_, void *dst, int64_t dst_len, int64_t ldd, int rows, int cols) {
+  if (!prec_ok(precision) || !prec_ok(precision2) || (precision == 32 && precision2 == 32)) return GOGP_EARG;
+  const std::initializer_list<ShArr> arrs = {{src, src_len, precision / 8, false}, {dst, dst_len, precision2 / 8, true}};
+  if (!sh_have(arrs) || rows < 1 || rows > (1 << 16) || cols < 1 || cols > (1 << 16)) return GOGP_EARG;
+  if (!covers(src_len, 0, lds_, rows, cols, 1, 0) || !covers(dst_len, 0, ldd, rows, cols, 1, 0)) return GOGP_EARG;
+  return sh_run(device, arrs, [&](char **d) {
+    if (precision == 32)
+      launch_convert_block(0, SH_F(0), lds_, SH_D(1), ldd, rows, cols);
+    else if (precision2 == 32)
+      launch_convert_block(0, SH_D(0), lds_, SH_F(1), ldd, rows, cols);
+    else
+      launch_convert_block(0, (const double *)SH_D(0), lds_, SH_D(1), ldd, rows, cols);
+  });
+}
+
+extern "C" int gogp_test_chunk_tdot(int device, int precision, const void *chunk, int64_t chunk_len, int64_t rows, int nb,
+                                    const double *v, int64_t v_len, double *part, int64_t part_len, double *out,
+                                    int64_t out_len) {
+  if (!prec_ok(precision)) return GOGP_EARG;
+  const std::initializer_list<ShArr> arrs = {{chunk, chunk_len, precision / 8, false}, {v, v_len, 8, false},
+                                             {part, part_len, 8, true}, {out, out_len, 8, true}};
+  // the grid is nb / 64 column groups: any other nb would leave columns unwritten
+  if (!sh_have(arrs) || rows < 1 || rows > (1 << 20) || nb < 64 || nb > 1024 || nb % 64) return GOGP_EARG;
+  if (chunk_len < rows * nb || v_len < rows || part_len < chunk_tdot_scratch(rows, nb) || out_len < nb) return GOGP_EARG;
+  return sh_run(device, arrs, [&](char **d) {
+    if (precision == 64)
+      launch_chunk_tdot(0, SH_D(0), rows, nb, SH_D(1), SH_D(2), SH_D(3));
+    else
+      launch_chunk_tdot(0, SH_F(0), rows, nb, SH_D(1), SH_D(2), SH_D(3));
+  });
+}
+
+extern "C" int gogp_test_chunk_alpha(int device, int precision, const void *Ych, int64_t ych_len, int mloc, int nloc,
+                                     int nb_shift, int Pr, int Pc, int pr, int pc, const double *z, int64_t z_len, double *out,
+                                     int64_t out_len) {
+  if (!prec_ok(precision)) return GOGP_EARG;
+  const std::initializer_list<ShArr> arrs = {{Ych, ych_len, precision / 8, false}, {z, z_len, 8, false}, {out, out_len, 8, true}};
+  BlockMap m;
+  if (!sh_have(arrs) || !sh_map(nb_shift, Pr, Pc, pr, pc, &m) || !sh_tiles(mloc, nloc, m)) return GOGP_EARG;
+  const int64_t nb = 1 << nb_shift, npad = (int64_t)mloc * Pr * nb;
+  if (ych_len < (int64_t)nloc * mloc * nb * nb || z_len < npad || out_len < npad) return GOGP_EARG;
+  return sh_run(device, arrs, [&](char **d) {
+    if (precision == 64)
+      launch_chunk_alpha(0, SH_D(0), mloc, nloc, (int)nb, m, SH_D(1), SH_D(2));
+    else
+      launch_chunk_alpha(0, SH_F(0), mloc, nloc, (int)nb, m, SH_D(1), SH_D(2));
+  });
+}
+
+extern "C" int gogp_test_chunk_sumsq(int device, int precision, const void *Ych, int64_t ych_len, int mloc, int nloc,
+                                     int nb_shift, int Pr, int Pc, int pr, int pc, int64_t n, double *part, int64_t part_len,
+                                     double *out, int64_t out_len) {
+  if (!prec_ok(precision)) return GOGP_EARG;
+  const std::initializer_list<ShArr> arrs = {{Ych, ych_len, precision / 8, false}, {part, part_len, 8, true},
+                                             {out, out_len, 8, true}};
+  BlockMap m;
+  if (!sh_have(arrs) || !sh_map(nb_shift, Pr, Pc, pr, pc, &m) || !sh_tiles(mloc, nloc, m)) return GOGP_EARG;
+  const int64_t nb = 1 << nb_shift, npad = (int64_t)mloc * Pr * nb;
+  if (n < 1 || n > npad || ych_len < (int64_t)nloc * mloc * nb * nb || part_len < mloc * nb || out_len < 1) return GOGP_EARG;
+  return sh_run(device, arrs, [&](char **d) {
+    if (precision == 64)
+      launch_chunk_sumsq(0, SH_D(0), mloc, nloc, (int)nb, m, n, SH_D(1), SH_D(2));
+    else
+      launch_chunk_sumsq(0, SH_F(0), mloc, nloc, (int)nb, m, n, SH_D(1), SH_D(2));
+  });
+}
+
+extern "C" int gogp_test_lml_scalars(int device, int precision, const void *L, int64_t l_len, int64_t ld, const double *z,
+                                     int64_t z_len, const double *y, int64_t y_len, const double *alpha, int64_t alpha_len,
+                                     int64_t n, int k, int64_t bstride, double *scalars, int64_t scalars_len) {
+  if (!prec_ok(precision)) return GOGP_EARG;
+  const std::initializer_list<ShArr> arrs = {{L, l_len, precision / 8, false}, {z, z_len, 8, false}, {y, y_len, 8, false},
+                                             {alpha, alpha_len, 8, false, true}, {scalars, scalars_len, 8, true}};
+  if (!sh_have(arrs) || !sh_batch(precision, k, &bstride) || n < 1 || n > TH_NPAD_MAX) return GOGP_EARG;
+  if (!covers(l_len, 0, ld, n, n, k, bstride) || !covers(z_len, 0, n, 1, n, k, bstride) || y_len < n ||
+      (alpha && !covers(alpha_len, 0, n, 1, n, k, bstride)) || !covers(scalars_len, 0, 5, 1, 5, k, bstride))
+    return GOGP_EARG;
+  return sh_run(device, arrs, [&](char **d) {
+    sh_set_batch(k, bstride);
+    if (precision == 64)
+      launch_lml_scalars(0, SH_D(0), ld, SH_D(1), SH_D(2), SH_D(3), n, SH_D(4));
+    else
+      launch_lml_scalars(0, SH_F(0), ld, SH_D(1), SH_D(2), SH_D(3), n, SH_D(4));
+  });
+}
+
+extern "C" int gogp_test_alpha_from_y_batched(int device, const double *Y, int64_t y_len, int64_t ld, const double *z,
+                                              int64_t z_len, int64_t npad, int k, int64_t bstride, double *alpha,
+                                              int64_t alpha_len) {
+  const std::initializer_list<ShArr> arrs = {{Y, y_len, 8, false}, {z, z_len, 8, false}, {alpha, alpha_len, 8, true}};
+  if (!sh_have(arrs) || !sh_batch(64, k, &bstride) || npad <= 0 || npad % 2 || npad > TH_NPAD_MAX || ld % 2) return GOGP_EARG;
+  if (!covers(y_len, 0, ld, npad, npad, k, bstride) || !covers(z_len, 0, npad, 1, npad, k, bstride) ||
+      !covers(alpha_len, 0, npad, 1, npad, k, bstride))
+    return GOGP_EARG;
+  return sh_run(device, arrs, [&](char **d) {
+    sh_set_batch(k, bstride);
+    launch_alpha_from_y(0, (const double *)SH_D(0), ld, SH_D(1), npad, SH_D(2));
+  });
+}
+
+extern "C" int gogp_test_trace_from_y(int device, const float *Y, int64_t y_len, int64_t ld, int64_t n, int64_t npad,
+                                      const double *alpha, int64_t alpha_len, double *part, int64_t part_len, double *out,
+                                      int64_t out_len) {
+  const std::initializer_list<ShArr> arrs = {{Y, y_len, 4, false}, {alpha, alpha_len, 8, false}, {part, part_len, 8, true},
+                                             {out, out_len, 8, true}};
+  if (!sh_have(arrs) || npad <= 0 || npad % PANEL || npad > TH_NPAD_MAX || n < 1 || n > npad) return GOGP_EARG;
+  if (!covers(y_len, 0, ld, n, npad, 1, 0) || alpha_len < n || part_len < n || out_len < 1) return GOGP_EARG;
+  return sh_run(device, arrs, [&](char **d) { launch_trace_from_y(0, SH_F(0), ld, n, npad, SH_D(1), SH_D(2), SH_D(3)); });
+}
+
+extern "C" int gogp_test_zero_upper_blocks(int device, int precision, void *R, int64_t r_len, int64_t ld, int64_t npad, int k,
+                                           int64_t bstride) {
+  if (!prec_ok(precision)) return GOGP_EARG;
+  const std::initializer_list<ShArr> arrs = {{R, r_len, precision / 8, true}};
+  if (!sh_have(arrs) || !sh_batch(precision, k, &bstride) || npad <= 0 || npad % PANEL || npad > (1 << 15) || ld % 2)
+    return GOGP_EARG;
+  if (!covers(r_len, 0, ld, npad, npad, k, bstride)) return GOGP_EARG;
+  return sh_run(device, arrs, [&](char **d) {
+    sh_set_batch(k, bstride);
+    if (precision == 64)
+      launch_zero_upper_blocks(0, SH_D(0), ld, npad);
+    else
+      launch_zero_upper_blocks(0, SH_F(0), ld, npad);
+  });
+}
+
+extern "C" int gogp_test_ydiag(int device, int precision, const void *Dinv, int64_t dinv_len, void *Y, int64_t y_len,
+                               int64_t ld, int k, int64_t bstride) {
+  if (!prec_ok(precision)) return GOGP_EARG;
+  const std::initializer_list<ShArr> arrs = {{Dinv, dinv_len, precision / 8, false}, {Y, y_len, precision / 8, true}};
+  if (!sh_have(arrs) || !sh_batch(precision, k, &bstride)) return GOGP_EARG;
+  if (!covers(dinv_len, 0, PANEL, PANEL, PANEL, k, bstride) || !covers(y_len, 0, ld, PANEL, PANEL, k, bstride))
+    return GOGP_EARG;
+  return sh_run(device, arrs, [&](char **d) {
+    sh_set_batch(k, bstride);
+    if (precision == 64)
+      launch_ydiag(0, SH_D(0), SH_D(1), ld);
+    else
+      launch_ydiag(0, SH_F(0), SH_F(1), ld);
+  });
+}
+
+extern "C" int gogp_test_zero_block(int device, int precision, void *B, int64_t b_len, int64_t ld, int64_t rows, int64_t cols,
+                                    int k, int64_t bstride) {
+  if (!prec_ok(precision)) return GOGP_EARG;
+  const std::initializer_list<ShArr> arrs = {{B, b_len, precision / 8, true}};
+  // pairs of columns are stored: an odd cols would write one column more, an odd ld misalign the pairs
+  if (!sh_have(arrs) || !sh_batch(precision, k, &bstride) || rows < 1 || rows > 65535 || cols < 2 || cols % 2 || ld % 2 ||
+      cols > (1 << 20))
+    return GOGP_EARG;
+  if (!covers(b_len, 0, ld, rows, cols, k, bstride)) return GOGP_EARG;
+  return sh_run(device, arrs, [&](char **d) {
+    sh_set_batch(k, bstride);
+    if (precision == 64)
+      launch_zero_block(0, SH_D(0), ld, rows, cols);
+    else
+      launch_zero_block(0, SH_F(0), ld, rows, cols);
+  });
+}
+
+extern "C" int gogp_test_extract_lower(int device, int precision, const void *L, int64_t l_len, int64_t ld, int64_t n,
+                                       double *out, int64_t out_len) {
+  if (!prec_ok(precision)) return GOGP_EARG;
+  const std::initializer_list<ShArr> arrs = {{L, l_len, precision / 8, false}, {out, out_len, 8, true}};
+  if (!sh_have(arrs) || n < 1 || n > 65535 || !covers(l_len, 0, ld, n, n, 1, 0) || out_len < n * n) return GOGP_EARG;
+  return sh_run(device, arrs, [&](char **d) {
+    if (precision == 64)
+      launch_extract_lower(0, SH_D(0), ld, n, SH_D(1));
+    else
+      launch_extract_lower(0, SH_F(0), ld, n, SH_D(1));
+  });
+}
+
+extern "C" int gogp_test_pack_lower(int device, int precision, const double *src, int64_t src_len, int64_t n, int64_t npad,
+                                    void *L, int64_t l_len, int64_t ld) {
+  if (!prec_ok(precision)) return GOGP_EARG;
+  const std::initializer_list<ShArr> arrs = {{src, src_len, 8, false}, {L, l_len, precision / 8, true}};
+  if (!sh_have(arrs) || n < 1 || n > npad || npad > 65535 || src_len < n * n || !covers(l_len, 0, ld, npad, npad, 1, 0))
+    return GOGP_EARG;
+  return sh_run(device, arrs, [&](char **d) {
+    if (precision == 64)
+      launch_pack_lower(0, SH_D(0), n, npad, SH_D(1), ld);
+    else
+      launch_pack_lower(0, SH_D(0), n, npad, SH_F(1), ld);
+  });
+}
+
+extern "C" int gogp_test_sigma(int device, const double *prior, int64_t prior_len, const double *q, int64_t q_len, int64_t m,
+                               double *sigma, int64_t sigma_len) {
+  const std::initializer_list<ShArr> arrs = {{prior, prior_len, 8, false}, {q, q_len, 8, false, true}, {sigma, sigma_len, 8, true}};
+  if (!sh_have(arrs) || m < 1 || m > SH_COUNT_MAX || prior_len < m || (q && q_len < m) || sigma_len < m) return GOGP_EARG;
+  return sh_run(device, arrs, [&](char **d) { launch_sigma(0, SH_D(0), SH_D(1), m, SH_D(2)); });
+}
+
+extern "C" int gogp_test_logdet_block(int device, const double *L, int64_t l_len, int64_t ld, int64_t row0, int64_t n, int nb,
+                                      double *acc, int64_t acc_len) {
+  const std::initializer_list<ShArr> arrs = {{L, l_len, 8, false}, {acc, acc_len, 8, true}};
+  if (!sh_have(arrs) || nb < 1 || nb > 1024 || row0 < 0 || n < 0 || n > TH_NPAD_MAX || row0 > TH_NPAD_MAX) return GOGP_EARG;
+  if (!covers(l_len, 0, ld, nb, nb, 1, 0) || acc_len < 1) return GOGP_EARG;
+  return sh_run(device, arrs, [&](char **d) { launch_logdet_block(0, SH_D(0), ld, row0, n, nb, SH_D(1)); });
+}
+
+extern "C" int gogp_test_dot(int device, const double *a, int64_t a_len, const double *b, int64_t b_len, int64_t n, double *out,
+                             int64_t out_len) {
+  const std::initializer_list<ShArr> arrs = {{a, a_len, 8, false}, {b, b_len, 8, false}, {out, out_len, 8, true}};
+  if (!sh_have(arrs) || n < 1 || n > SH_COUNT_MAX || a_len < n || b_len < n || out_len < 1) return GOGP_EARG;
+  return sh_run(device, arrs, [&](char **d) { launch_dot(0, SH_D(0), SH_D(1), n, SH_D(2)); });
+}
+
+extern "C" int gogp_test_sumsq_info(int device, const double *z, int64_t z_len, int64_t n, const int64_t *info,
+                                    int64_t info_len, double *out, int64_t out_len) {
+  const std::initializer_list<ShArr> arrs = {{z, z_len, 8, false}, {info, info_len, 8, false, true}, {out, out_len, 8, true}};
+  if (!sh_have(arrs) || n < 1 || n > SH_COUNT_MAX || z_len < n || out_len < (info ? 2 : 1)) return GOGP_EARG;
+  return sh_run(device, arrs, [&](char **d) {
+    launch_sumsq_info(0, SH_D(0), n, reinterpret_cast<const long long *>(d[1]), SH_D(2));
+  });
+}
+
+// the one-line vector kernels: op 0 fill (a := f), 1 axpy (a += b), 2 add_vec (a += b), 3 scale (a *= f), 4 residual_from
+// (a := b - a), 5 add_inplace (a += b; the one op with a float instance), 6 info_to_double (a[0] := the int64 whose bits
+// b[0] holds; count 1).  fill and scale take no b: NULL with length 0.
+extern "C" int gogp_test_vector_op(int device, int op, int precision, void *a, int64_t a_len, const void *b, int64_t b_len,
+                                   int64_t count, double f) {
+  if (!prec_ok(precision) || op < 0 || op > 6 || (precision == 32 && op != 5)) return GOGP_EARG;
+  const bool no_b = op == 0 || op == 3;
+  const std::initializer_list<ShArr> arrs = {{a, a_len, precision / 8, true}, {b, b_len, precision / 8, false, no_b}};
+  if (!sh_have(arrs) || count < 1 || count > SH_COUNT_MAX || a_len < count || (op == 6 && count != 1)) return GOGP_EARG;
+  if (no_b ? b != nullptr : b_len < count) return GOGP_EARG;
+  return sh_run(device, arrs, [&](char **d) {
+    switch (op) {
+      case 0: launch_fill(0, SH_D(0), count, f); break;
+      case 1: launch_axpy(0, SH_D(0), SH_D(1), count); break;
+      case 2: launch_add_vec(0, SH_D(0), SH_D(1), count); break;
+      case 3: launch_scale(0, SH_D(0), f, count); break;
+      case 4: launch_residual_from(0, SH_D(0), SH_D(1), count); break;
+      case 5:
+        if (precision == 64)
+          launch_add_inplace(0, SH_D(0), SH_D(1), count);
+        else
+          launch_add_inplace(0, SH_F(0), SH_F(1), count);
+        break;
+      default: launch_info_to_double(0, reinterpret_cast<const long long *>(d[1]), SH_D(0)); break;
+    }
+  });
+}

@@ -1865,6 +1865,20 @@ def basis_kernel_check(which: str, device: int = -1, **args):
     return _table_check(_lib.BASIS_HOOKS, which, device, args, "basis_kernel_check")
 
 
+def shard_kernel_check(which: str, device: int = -1, **args):
+    """finish_check for the kernels of the sharded path and the rest of solve.hip (_lib.SHARD_HOOKS): arrays typed by
+    `precision` are float64 or float32, and the optional ones may be None."""
+    return _table_check(_lib.SHARD_HOOKS, which, device, args, "shard_kernel_check")
+
+
+def chunk_tdot_scratch(rows: int, nb: int) -> int:
+    """Doubles of `part` scratch launch_chunk_tdot needs for up to `rows` rows.  No device."""
+    r = int(_lib.hooks().gogp_test_chunk_tdot_scratch(rows, nb))
+    if r < 0:
+        raise GogpError(_lib.GOGP_EARG, "test_chunk_tdot_scratch")
+    return r
+
+
 def basis_slabs(n: int):
     """(symm, gram): the slabs launch_basis_symm and launch_basis_gram split n observations into."""
     return int(_lib.hooks().gogp_test_basis_symm_slabs(n)), int(_lib.hooks().gogp_test_basis_gram_slabs(n))
@@ -1875,9 +1889,23 @@ def _table_check(table, which: str, device: int, args, caller: str):
     if set(args) != {name for name, _ in spec}:
         raise TypeError("%s(%s): the arguments are %s" % (caller, which, ", ".join(name for name, _ in spec)))
     call, outs = [device], []
+    typed = {"A": "precision", "O": "precision", "P": "precision2", "B": "precision"}
     for name, kind in spec:
         v = args[name]
-        if kind in "ao":
+        if kind in "nrB" and v is None:
+            call += [None, 0]
+        elif kind in "AOPBfrn":  # arrays by their own element type (_lib._SHARD_SPEC)
+            want = {"f": np.float32, "r": np.int64, "n": np.float64}.get(kind)
+            if want is None:
+                want = {64: np.float64, 32: np.float32}.get(int(args[typed[kind]]))
+            if not isinstance(v, np.ndarray) or v.dtype != want or not v.flags.c_contiguous:
+                raise TypeError("%s: a C-contiguous %s array" % (name, np.dtype(want).name if want else "float"))
+            v = v.reshape(-1)
+            if kind in "OP":
+                v = v.copy()
+                outs.append(v)
+            call += [ctypes.c_void_p(v.ctypes.data), v.size]
+        elif kind in "ao":
             v = _vec(v, name).reshape(-1)
             if kind == "o":
                 v = v.copy()

@@ -501,6 +501,81 @@ int gogp_test_nv_diag_add(int device, double *A, int64_t a_len, int64_t ld, int6
 int gogp_test_nv_gradient(int device, const double *Kinv, int64_t kinv_len, int64_t ld, const double *alpha,
                           int64_t alpha_len, int64_t n, int64_t npad, double *dv, int64_t dv_len);
 
+/* The kernels of the sharded path -- dist2d.hip and the "helpers of the sharded evaluation" of solve.hip -- and the rest of
+ * solve.hip (the LML scalars, the fp64 trace, the layout kernels around the factor, the one-line vector kernels) in
+ * isolation, through their product launchers (tests/test_shard_kernels.py), under the rules of the hooks above: arguments
+ * are checked before the device is touched (GOGP_EARG), every array goes up whole and every in / out array comes back
+ * whole.  `void *` arrays hold doubles (precision 64) or floats (32); lengths count elements.  The preconditions of the
+ * launchers stand in csrc/common.h; the hooks refuse what breaks them.
+ * Block map: this rank sits at (pr, pc) of a Pr x Pc grid (1 .. 8 each) with tiles of nb = 2^nb_shift (5 .. 10); local tile
+ * counts must satisfy mloc Pr = nloc Pc, as the product pads.  Chunk buffers: nloc chunks of (mloc nb) x nb.
+ * Batched launchers (lml_scalars, alpha_from_y_batched, zero_upper_blocks, ydiag, zero_block): k candidates `bstride`
+ * ELEMENTS apart (even; precision 64 only when k > 1), set in tl_batch around the launch and restored to {1, 0}.
+ * scatter_tile: dst is the band of the rows from r0 on (the launcher gets dst - r0 n).  gather_rows_of_l: rows NULL and
+ * rows_len 0 with diag_only 1.  residual_block: recv NULL with nrecv 0.  convert_block: src has `precision`, dst
+ * `precision2` (not both 32).  chunk_tdot: part holds gogp_test_chunk_tdot_scratch(rows, nb) doubles (-1: bad arguments).
+ * lml_scalars, sigma: alpha / q may be NULL (length 0).  sumsq_info: info NULL or one int64.
+ * vector_op: 0 fill (a := f), 1 axpy, 2 add_vec (a += b), 3 scale (a *= f), 4 residual_from (a := b - a), 5 add_inplace
+ * (a += b; precision 32 allowed), 6 info_to_double (a[0] := (double) the int64 in b[0]; count 1); fill and scale take
+ * b NULL with length 0. */
+int64_t gogp_test_chunk_tdot_scratch(int64_t rows, int nb);
+int gogp_test_gather_rows(int device, const double *y, int64_t y_len, int64_t rows, int nb_shift, int Pr, int Pc, int pr, int
+    pc, double *yloc, int64_t yloc_len);
+int gogp_test_gather_x(int device, const double *X, int64_t x_len, const double *a, int64_t a_len, int D, int64_t n, int64_t
+    rows, int nb_shift, int Pr, int Pc, int pr, int pc, double *Xloc, int64_t xloc_len, double *aloc, int64_t aloc_len);
+int gogp_test_scatter_tile(int device, int precision, const void *src, int64_t src_len, int nb, int64_t n, int64_t row0,
+    int64_t col0, int diag, int64_t r0, double *dst, int64_t dst_len);
+int gogp_test_gather_rows_of_l(int device, int precision, const void *Lch, int64_t lch_len, int mloc, int nloc, int nb_shift,
+    int Pr, int Pc, int pr, int pc, const int64_t *rows, int64_t rows_len, int64_t n, int diag_only, double *out, int64_t
+    out_len);
+int gogp_test_scatter_stage(int device, int precision, const double *stage, int64_t stage_len, int64_t lds, void *Lch, int64_t
+    lch_len, int nloc, int mloc, int bi, int nb);
+int gogp_test_transpose_rect(int device, int precision, const void *src, int64_t src_len, int64_t lds, void *dst, int64_t
+    dst_len, int64_t ldd, int64_t rows, int cols);
+int gogp_test_transpose_sq(int device, int precision, const void *src, int64_t src_len, int64_t lds, void *dst, int64_t
+    dst_len, int64_t ldd, int n);
+int gogp_test_copy_block(int device, double *dst, int64_t dst_len, const double *src, int64_t src_len, int64_t ld, int nb,
+    int64_t rows);
+int gogp_test_residual_block(int device, int precision, void *W, int64_t w_len, const void *Ks, int64_t ks_len, const double
+    *U, int64_t u_len, int64_t ld, const double *recv, int64_t recv_len, int nrecv, int nb, int64_t rows);
+int gogp_test_pack_blocks(int device, double *dst, int64_t dst_len, const double *src, int64_t src_len, int nblk, int64_t blk,
+    int first, int stride);
+int gogp_test_convert_block(int device, int precision, int precision2, const void *src, int64_t src_len, int64_t lds, void
+    *dst, int64_t dst_len, int64_t ldd, int rows, int cols);
+int gogp_test_chunk_tdot(int device, int precision, const void *chunk, int64_t chunk_len, int64_t rows, int nb, const double
+    *v, int64_t v_len, double *part, int64_t part_len, double *out, int64_t out_len);
+int gogp_test_chunk_alpha(int device, int precision, const void *Ych, int64_t ych_len, int mloc, int nloc, int nb_shift, int
+    Pr, int Pc, int pr, int pc, const double *z, int64_t z_len, double *out, int64_t out_len);
+int gogp_test_chunk_sumsq(int device, int precision, const void *Ych, int64_t ych_len, int mloc, int nloc, int nb_shift, int
+    Pr, int Pc, int pr, int pc, int64_t n, double *part, int64_t part_len, double *out, int64_t out_len);
+int gogp_test_lml_scalars(int device, int precision, const void *L, int64_t l_len, int64_t ld, const double *z, int64_t z_len,
+    const double *y, int64_t y_len, const double *alpha, int64_t alpha_len, int64_t n, int k, int64_t bstride, double
+    *scalars, int64_t scalars_len);
+int gogp_test_alpha_from_y_batched(int device, const double *Y, int64_t y_len, int64_t ld, const double *z, int64_t z_len,
+    int64_t npad, int k, int64_t bstride, double *alpha, int64_t alpha_len);
+int gogp_test_trace_from_y(int device, const float *Y, int64_t y_len, int64_t ld, int64_t n, int64_t npad, const double
+    *alpha, int64_t alpha_len, double *part, int64_t part_len, double *out, int64_t out_len);
+int gogp_test_zero_upper_blocks(int device, int precision, void *R, int64_t r_len, int64_t ld, int64_t npad, int k, int64_t
+    bstride);
+int gogp_test_ydiag(int device, int precision, const void *Dinv, int64_t dinv_len, void *Y, int64_t y_len, int64_t ld, int k,
+    int64_t bstride);
+int gogp_test_zero_block(int device, int precision, void *B, int64_t b_len, int64_t ld, int64_t rows, int64_t cols, int k,
+    int64_t bstride);
+int gogp_test_extract_lower(int device, int precision, const void *L, int64_t l_len, int64_t ld, int64_t n, double *out,
+    int64_t out_len);
+int gogp_test_pack_lower(int device, int precision, const double *src, int64_t src_len, int64_t n, int64_t npad, void *L,
+    int64_t l_len, int64_t ld);
+int gogp_test_sigma(int device, const double *prior, int64_t prior_len, const double *q, int64_t q_len, int64_t m, double
+    *sigma, int64_t sigma_len);
+int gogp_test_logdet_block(int device, const double *L, int64_t l_len, int64_t ld, int64_t row0, int64_t n, int nb, double
+    *acc, int64_t acc_len);
+int gogp_test_dot(int device, const double *a, int64_t a_len, const double *b, int64_t b_len, int64_t n, double *out, int64_t
+    out_len);
+int gogp_test_sumsq_info(int device, const double *z, int64_t z_len, int64_t n, const int64_t *info, int64_t info_len, double
+    *out, int64_t out_len);
+int gogp_test_vector_op(int device, int op, int precision, void *a, int64_t a_len, const void *b, int64_t b_len, int64_t
+    count, double f);
+
 #ifdef __cplusplus
 }
 #endif
