@@ -851,6 +851,44 @@ func (gp *GP) SetInducing(u []float64) error {
 	return gp.err(C.gogp_sparse_set_inducing(gp.handle(), dptr(u), C.int64_t(len(u)/gp.NDim)))
 }
 
+// SelectInducing chooses at most m inducing points among the rows of x
+// (row-major N x NDim) at logtheta by greedy conditional-variance selection:
+// a partial Cholesky factorisation of k(x, x) with diagonal pivoting (no
+// reference counterpart; the noise does not enter).  It stops once no residual
+// variance exceeds tol (tol < 0: the jitter 10^"sparse_jitter_log10"), so idx
+// (the rows in pick order), u (= x[idx], row-major) and pivots (the residual
+// variances at the picks) hold the points taken, m at most; trace is the
+// trace term t0 - tr Qff of the bound for them.  x == nil selects among the
+// rows of the sparse data already on the device (SetSparse), without sending
+// them again.  Nothing of the process's state changes.
+func (gp *GP) SelectInducing(logtheta, x []float64, m int, tol float64) (idx []int64, u, pivots []float64, trace float64, err error) {
+	gp.defaults()
+	if len(x)%gp.NDim != 0 {
+		return nil, nil, nil, 0, fmt.Errorf("len(x)")
+	}
+	cnt := m
+	if cnt < 1 {
+		cnt = 1
+	}
+	idx, pivots, u = make([]int64, cnt), make([]float64, cnt), make([]float64, cnt*gp.NDim)
+	var taken C.int64_t
+	var tr C.double
+	ip := (*C.int64_t)(unsafe.Pointer(&idx[0]))
+	var rc C.int
+	if x == nil {
+		rc = C.gogp_sparse_select_inducing_resident(gp.handle(), dptr(logtheta), C.int64_t(len(logtheta)), C.int64_t(m),
+			C.double(tol), ip, dptr(pivots), dptr(u), &taken, &tr)
+	} else {
+		rc = C.gogp_sparse_select_inducing(gp.handle(), dptr(logtheta), C.int64_t(len(logtheta)), dptr(x),
+			C.int64_t(len(x)/gp.NDim), C.int64_t(m), C.double(tol), ip, dptr(pivots), dptr(u), &taken, &tr)
+	}
+	if err = gp.err(rc); err != nil {
+		return nil, nil, nil, 0, err
+	}
+	k := int(taken)
+	return idx[:k], u[:k*gp.NDim], pivots[:k], float64(tr), nil
+}
+
 // SparseGradientInducing computes SparseGradient and, from the same pass over
 // the data, the derivative of the bound in the inducing points of SetSparse
 // (row-major M x NDim).

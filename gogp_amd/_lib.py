@@ -122,6 +122,10 @@ SYMBOLS = [
     ("gogp_sparse_multi_gradient", ctypes.c_int, [_h, _dp, _i64]),
     ("gogp_sparse_multi_gradient_inducing", ctypes.c_int, [_h, _dp, _i64, _dp]),
     ("gogp_sparse_multi_produce", ctypes.c_int, [_h, _dp, _i64, _dp, _dp]),
+    ("gogp_sparse_select_inducing", ctypes.c_int,
+     [_h, _dp, _i64, _dp, _i64, _i64, ctypes.c_double, ctypes.POINTER(_i64), _dp, _dp, ctypes.POINTER(_i64), _dp]),
+    ("gogp_sparse_select_inducing_resident", ctypes.c_int,
+     [_h, _dp, _i64, _i64, ctypes.c_double, ctypes.POINTER(_i64), _dp, _dp, ctypes.POINTER(_i64), _dp]),
     ("gogp_observe_gradient_batch", ctypes.c_int,
      [ctypes.POINTER(_h), ctypes.c_int, _dp, _i64, _dp, _dp, ctypes.POINTER(ctypes.c_int)]),
     ("gogp_observe_gradient_candidates", ctypes.c_int,
@@ -271,6 +275,14 @@ HOOK_SYMBOLS = [
      [ctypes.c_int, _dp, _i64, _i64, _i64, _i64, _i64, _dp, _i64, _i64, _i64, _dp, _i64, _i64]),
     ("gogp_test_sparse_xty_slabs", ctypes.c_int, [_i64, _i64, _i64, ctypes.POINTER(ctypes.c_int64)]),
     ("gogp_test_sparse_xty_slabs_bound", ctypes.c_int, [_i64, _i64, _i64]),
+    # greedy selection of inducing points (tests/test_select_inducing_kernels.py)
+    ("gogp_test_select_step", ctypes.c_int,
+     [ctypes.c_int, ctypes.POINTER(CKParams), _dp, _i64, _i64, _dp, _i64, _i64, _i64, ctypes.c_double, _dp, _i64,
+      ctypes.POINTER(ctypes.c_ubyte), _i64, _dp, ctypes.POINTER(_i64), _i64, ctypes.c_int, _dp, ctypes.POINTER(_i64), _i64,
+      ctypes.POINTER(_i64), _dp]),
+    ("gogp_test_select_run", ctypes.c_int,
+     [ctypes.c_int, ctypes.POINTER(CKParams), _dp, _i64, _i64, _i64, ctypes.c_double, ctypes.c_int, _dp, _i64,
+      ctypes.POINTER(_i64), _dp, _dp, _i64, _dp, _i64, _dp, _i64, ctypes.POINTER(_i64), _dp]),
     # the two kernels of leave-block-out cross-validation (tests/test_blockcv_kernels.py)
     ("gogp_test_blockcv_groups", ctypes.c_int,
      [ctypes.c_int, _dp, _i64, _i64, _dp, _i64, _dp, _i64, _i64, ctypes.POINTER(_i64), _i64] + [_dp, _i64] * 6

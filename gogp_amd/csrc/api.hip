@@ -4092,6 +4092,107 @@ extern "C" int gogp_sparse_multi_produce(gogp_handle *h, const double *Z, int64_
   return GOGP_OK;
 }
 
+// ---- choosing the inducing points (select.hip) ------------------------------------------------------------------------
+// gogp_sparse_select_inducing (X given: uploaded for the call) and gogp_sparse_select_inducing_resident (X == nullptr
+// with resident: the rows of sp_X): one body.  Every buffer is the call's own -- the parameters too, so that devP keeps
+// what the last evaluation uploaded -- on the handle's main stream, freed before the call returns: nothing of the handle
+// changes but its error string.
+static int sparse_select_impl(gogp_handle *h, const char *who, bool resident, const double *x, int64_t len, const double *X,
+                              int64_t N, int64_t M, double tol, int64_t *idx, double *pivots, double *U, int64_t *m_out,
+                              double *trace) {
+  auto msg = [&](const char *what) { return std::string(who) + what; };
+  if (!h) return GOGP_EARG;
+  if (!x || !idx || !m_out) return fail(h, GOGP_EARG, msg(": NULL").c_str());
+  if (sparse_refusal(h)) return sparse_refuse(h, who);
+  if (len != h->P) return fail(h, GOGP_EARG, msg(": len(x)").c_str());
+  for (int64_t i = 0; i < len; ++i)
+    if (!std::isfinite(x[i])) return fail(h, GOGP_EARG, msg(": non-finite parameter").c_str());
+  if (M < 1 || M > GOGP_SPARSE_MAX_M) return fail(h, GOGP_EARG, msg(": need 1 <= M <= GOGP_SPARSE_MAX_M").c_str());
+  if (std::isnan(tol) || tol == INFINITY) return fail(h, GOGP_EARG, msg(": tol must be finite or negative").c_str());
+  const int D = h->D;
+  if (resident) {
+    if (!h->sp_have) return fail(h, GOGP_ESTATE, msg(": no sparse data (gogp_sparse_set_data)").c_str());
+    N = h->sp_N;
+  } else {
+    if (N < 0 || (N > 0 && !X)) return fail(h, GOGP_EARG, msg(": need X for N > 0, N >= 0").c_str());
+    for (int64_t i = 0; i < N * D; ++i)
+      if (!std::isfinite(X[i])) return fail(h, GOGP_EARG, msg(": non-finite input").c_str());
+  }
+  std::vector<double> th(h->P > 0 ? h->P : 1);
+  for (int i = 0; i < h->P; ++i) th[i] = exp(x[i]);
+  if (const char *why = theta_refusal(h, th.data(), th.data() + h->ns)) return fail(h, GOGP_EARG, why);
+  if (tol < 0.0) tol = pow(10.0, (double)h->sp_jitter_log10);
+  *m_out = 0;
+  if (N == 0) {
+    if (trace) *trace = 0.0;
+    return GOGP_OK;
+  }
+  DevParams hp;
+  fill_params_theta(h, th.data(), th.data() + h->ns, hp);
+  HIPCHK(h, hipSetDevice(h->device));
+  hipStream_t s = h->s;
+  const int64_t cols = std::min(M, N);
+  SelectBufs b;
+  const size_t small = select_layout(nullptr, N, M, D, &b);
+  const size_t xbytes = resident ? 0 : (size_t)N * D * sizeof(double);
+  const size_t lbytes = (size_t)cols * (size_t)b.ldn * sizeof(double);
+  char *work = nullptr;
+  double *dXc = nullptr, *Lt = nullptr;
+  DevParams *dP = nullptr;
+  auto release = [&]() {
+    (void)hipFree(work);
+    (void)hipFree(dXc);
+    (void)hipFree(Lt);
+    (void)hipFree(dP);
+  };
+  hipError_t e = hipMalloc(&Lt, lbytes);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    char buf[200];
+    snprintf(buf, sizeof buf, "%s: the transient factor (%lld columns of %lld doubles, %.3f GB) could not be allocated: %s",
+             who, (long long)cols, (long long)b.ldn, (double)lbytes * 1e-9, hipGetErrorString(e));
+    h->err = buf;
+    return e == hipErrorOutOfMemory ? GOGP_ENOMEM : GOGP_EHIP;
+  }
+  e = hipMalloc(&work, small);
+  if (e == hipSuccess && !resident) e = hipMalloc(&dXc, xbytes);
+  if (e == hipSuccess) e = hipMalloc(&dP, sizeof(DevParams));
+  if (e == hipSuccess) e = hipMemcpyAsync(dP, &hp, sizeof hp, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess && !resident) e = hipMemcpyAsync(dXc, X, xbytes, hipMemcpyHostToDevice, s);
+  int64_t m = 0;
+  if (e == hipSuccess) {
+    select_layout(work, N, M, D, &b);
+    b.Lt = Lt;
+    e = select_run(s, dP, D, resident ? h->sp_X : dXc, N, M, tol, 0, nullptr, b, &m);
+  }
+  std::vector<long long> hpiv((size_t)(m > 0 ? m : 1));
+  if (e == hipSuccess && m > 0) {
+    e = hipMemcpyAsync(hpiv.data(), b.piv, (size_t)m * sizeof(long long), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && pivots) e = hipMemcpyAsync(pivots, b.pv, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && U) e = hipMemcpyAsync(U, b.U, (size_t)m * D * sizeof(double), hipMemcpyDeviceToHost, s);
+  }
+  if (e == hipSuccess && trace) e = hipMemcpyAsync(trace, b.trace, sizeof(double), hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  else (void)hipStreamSynchronize(s);  // nothing enqueued may outlive the buffers
+  release();
+  HIPCHK(h, e);
+  for (int64_t j = 0; j < m; ++j) idx[j] = (int64_t)hpiv[(size_t)j];
+  *m_out = m;
+  return GOGP_OK;
+}
+
+extern "C" int gogp_sparse_select_inducing(gogp_handle *h, const double *x, int64_t len, const double *X, int64_t N, int64_t M,
+                                           double tol, int64_t *idx, double *pivots, double *U, int64_t *m_out,
+                                           double *trace) {
+  return sparse_select_impl(h, "sparse_select_inducing", false, x, len, X, N, M, tol, idx, pivots, U, m_out, trace);
+}
+
+extern "C" int gogp_sparse_select_inducing_resident(gogp_handle *h, const double *x, int64_t len, int64_t M, double tol,
+                                                    int64_t *idx, double *pivots, double *U, int64_t *m_out, double *trace) {
+  return sparse_select_impl(h, "sparse_select_inducing_resident", true, x, len, nullptr, 0, M, tol, idx, pivots, U, m_out,
+                            trace);
+}
+
 // ---- non-Gaussian likelihoods by the Laplace approximation (laplace.hip) -----------------------------------------------
 // No reference counterpart.  The formulas are in laplace.hip and DESIGN.md section 4 "Laplace".  Every Newton step is
 // one non-eager factorize_t<double> of B = I + diag(sw) K diag(sw) -- the Gram stage scales K (Sweep::build_gram), the

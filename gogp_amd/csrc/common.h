@@ -550,6 +550,39 @@ void launch_sparse_multi_pad(hipStream_t s, const double *Y, int64_t ldy, int64_
                              double *Yp, int64_t ldp);
 void launch_sparse_multi_sigma(hipStream_t s, const double *A, const double *V, int64_t ld, int64_t ncols, int64_t m,
                                const double *prior, const double *q, double *sigma);
+// select.hip (gogp_sparse_select_inducing): greedy pivoted Cholesky of k(X, X), one launch per step (the algorithm is at
+// the head of select.hip).  SelectBufs: the factor Lt (column t at Lt + t * ldn, ldn = N rounded up to 256; min(M, N)
+// columns) and the small buffers select_layout places at `base` (nullptr: the bytes alone, its return value): d (ldn),
+// the double-buffered partial maxima, piv / pv (M), the step count, the trace, U (M x ndim) and the selection mask.
+// launch_select_init: d_i = k(x_i, x_i) (d0 given: d0_i), the mask cleared, the first partials.  launch_select_step: step
+// j on `blocks` workgroups (the same for every launch of a run: the partials are one per workgroup); it writes nothing
+// once piv[j - 1] < 0 or the best residual is not > tol.  launch_select_final: trace and (gather) U = X[piv[0 .. m)].
+// select_run: the whole loop on stream s -- piv cleared to -1, init, up to min(M, N) steps with a look at the step count
+// every SELECT_SYNC_STEPS launches, final -- synchronised; *m_out = the steps taken.  max_blocks > 0 caps the grid below
+// select_blocks' rule (tests: workgroups that stride over several row blocks at a small N).
+struct SelPair {
+  double v;
+  long long i;
+};
+struct SelectBufs {
+  double *Lt = nullptr;
+  int64_t ldn = 0;
+  double *d = nullptr, *pv = nullptr, *trace = nullptr, *U = nullptr;
+  SelPair *part = nullptr;
+  long long *piv = nullptr, *state = nullptr;
+  unsigned char *sel = nullptr;
+};
+constexpr int SELECT_BLOCKS_MAX = 1024;  // workgroups of a step at most: the pairs every workgroup of the next one reduces
+constexpr int SELECT_SYNC_STEPS = 256;
+int select_blocks(int64_t N, int max_blocks);
+size_t select_layout(char *base, int64_t N, int64_t M, int ndim, SelectBufs *b);
+void launch_select_init(hipStream_t s, const DevParams *p, const double *X, int64_t N, int blocks, const double *d0,
+                        const SelectBufs &b);
+void launch_select_step(hipStream_t s, const DevParams *p, int ndim, const double *X, int64_t N, int blocks, int j,
+                        double tol, const SelectBufs &b);
+void launch_select_final(hipStream_t s, const double *X, int64_t N, int ndim, const SelectBufs &b, bool gather);
+hipError_t select_run(hipStream_t s, const DevParams *p, int ndim, const double *X, int64_t N, int64_t M, double tol,
+                      int max_blocks, const double *d0, const SelectBufs &b, int64_t *m_out);
 // laplace.hip (gogp_laplace_*): the passes around the factorisation of B = I + diag(sw) K diag(sw).  Vectors hold npad
 // doubles (npad a multiple of 256) and leave every launcher zero from row n on.
 // launch_lap_site: g, W, sw = sqrt(W), b = W f + g, rho of the rows i < n; part: 5 * npad / 256 doubles of block results;

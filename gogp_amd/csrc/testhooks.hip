@@ -1537,6 +1537,114 @@ extern "C" int gogp_test_sparse_xty_slabs_bound(int64_t rows, int64_t M, int64_t
   return sparse_xty_slabs_bound(rows, M, T);
 }
 
+// ---- greedy selection of inducing points (select.hip; tests/test_select_inducing_kernels.py) ----------------------------
+// The rules of the hooks above: every argument is checked before the device is touched, every array goes to the device
+// whole and every in / out array comes back whole.
+namespace {
+constexpr int64_t SEL_N_MAX = 1 << 22;
+bool select_args_ok(const gogp_test_kparams *kp, int64_t x_len, int64_t N, double tol, int max_blocks) {
+  if (!kp || !kparams_ok(kp, 1, ard_dims_of(kp), 0, 1, 0) || kp->nevents != 0) return false;
+  if (N < 1 || N > SEL_N_MAX || x_len < N * kp->ndim) return false;
+  return std::isfinite(tol) && tol >= 0.0 && max_blocks >= 0;
+}
+}  // namespace
+
+extern "C" int gogp_test_select_step(int device, const gogp_test_kparams *kparams, const double *X, int64_t x_len, int64_t N,
+                                     double *Lt, int64_t lt_len, int64_t ldn, int64_t j, double tol, double *d, int64_t d_len,
+                                     unsigned char *sel, int64_t sel_len, const double *part_v, const int64_t *part_i,
+                                     int64_t part_len, int max_blocks, double *out_v, int64_t *out_i, int64_t out_len,
+                                     int64_t *p, double *dp) {
+  if (!X || !Lt || !d || !sel || !part_v || !part_i || !out_v || !out_i || !p || !dp) return GOGP_EARG;
+  if (!select_args_ok(kparams, x_len, N, tol, max_blocks)) return GOGP_EARG;
+  if (j < 0 || j >= GOGP_SPARSE_MAX_M || ldn < N || ldn % 256 || lt_len < (j + 1) * ldn || d_len < N || sel_len < N)
+    return GOGP_EARG;
+  const int blocks = select_blocks(N, max_blocks);
+  if (part_len != blocks || out_len < blocks) return GOGP_EARG;
+  for (int q = 0; q < blocks; ++q)
+    if (part_i[q] < 0 || part_i[q] >= N) return GOGP_EARG;  // the kernel reads row part_i of X and of the factor
+  if (!device_ok(device)) return GOGP_EHIP;
+  const DevParams hp = to_dev(*kparams);
+  const int D = kparams->ndim;
+  SelectBufs b;
+  const size_t small = select_layout(nullptr, N, j + 1, D, &b);
+  DevCopy dP, dX, dL, dW;
+  std::vector<char> work(small, 0);
+  select_layout(work.data(), N, j + 1, D, &b);
+  memcpy(b.d, d, (size_t)N * sizeof(double));
+  memcpy(b.sel, sel, (size_t)N);
+  SelPair *pin = b.part + (size_t)(j & 1) * SELECT_BLOCKS_MAX;
+  for (int q = 0; q < blocks; ++q) pin[q].v = part_v[q], pin[q].i = part_i[q];
+  for (int64_t t = 0; t <= j; ++t) b.piv[t] = t < j ? 0 : -1;  // the earlier steps recorded pivots
+  hipError_t e = dP.up(&hp, sizeof hp);
+  if (e == hipSuccess) e = dX.up(X, (size_t)x_len * sizeof(double));
+  if (e == hipSuccess) e = dL.up(Lt, (size_t)lt_len * sizeof(double));
+  if (e == hipSuccess) e = dW.up(work.data(), small);
+  if (e == hipSuccess) {
+    SelectBufs db;
+    select_layout(dW.d, N, j + 1, D, &db);
+    db.Lt = dL.as<double>();
+    db.ldn = ldn;
+    launch_select_step(0, dP.as<DevParams>(), D, dX.as<double>(), N, blocks, (int)j, tol, db);
+    e = launched();
+  }
+  if (e == hipSuccess) e = dL.down(Lt);
+  if (e == hipSuccess) e = dW.down(work.data());
+  if (e != hipSuccess) return GOGP_EHIP;
+  memcpy(d, b.d, (size_t)N * sizeof(double));
+  memcpy(sel, b.sel, (size_t)N);
+  const SelPair *pout = b.part + (size_t)((j + 1) & 1) * SELECT_BLOCKS_MAX;
+  *p = b.piv[j];
+  *dp = b.pv[j];
+  for (int q = 0; q < blocks && *p >= 0; ++q) out_v[q] = pout[q].v, out_i[q] = pout[q].i;
+  return GOGP_OK;
+}
+
+extern "C" int gogp_test_select_run(int device, const gogp_test_kparams *kparams, const double *X, int64_t x_len, int64_t N,
+                                    int64_t M, double tol, int max_blocks, const double *d0, int64_t d0_len, int64_t *idx,
+                                    double *pivots, double *U, int64_t u_len, double *Lt, int64_t lt_len, double *d,
+                                    int64_t d_len, int64_t *m_out, double *trace) {
+  if (!X || !idx || !pivots || !m_out || !trace) return GOGP_EARG;
+  if (!select_args_ok(kparams, x_len, N, tol, max_blocks)) return GOGP_EARG;
+  if (M < 1 || M > GOGP_SPARSE_MAX_M) return GOGP_EARG;
+  const int D = kparams->ndim;
+  SelectBufs b;
+  const size_t small = select_layout(nullptr, N, M, D, &b);
+  const int64_t cols = std::min(M, N);
+  if ((d0 && d0_len < N) || (U && u_len < M * D) || (Lt && lt_len < cols * b.ldn) || (d && d_len < N)) return GOGP_EARG;
+  if (!device_ok(device)) return GOGP_EHIP;
+  const DevParams hp = to_dev(*kparams);
+  DevCopy dP, dX, d0c;
+  char *work = nullptr;
+  double *dL = nullptr;
+  const size_t lbytes = (size_t)cols * (size_t)b.ldn * sizeof(double);
+  hipError_t e = dP.up(&hp, sizeof hp);
+  if (e == hipSuccess) e = dX.up(X, (size_t)x_len * sizeof(double));
+  if (e == hipSuccess && d0) e = d0c.up(d0, (size_t)d0_len * sizeof(double));
+  if (e == hipSuccess) e = hipMalloc(&work, small);
+  if (e == hipSuccess) e = hipMalloc(&dL, lbytes);
+  if (e == hipSuccess) e = hipMemset(dL, 0xff, lbytes);  // NaN: what no step wrote shows
+  int64_t m = 0;
+  if (e == hipSuccess) {
+    select_layout(work, N, M, D, &b);
+    b.Lt = dL;
+    e = select_run(0, dP.as<DevParams>(), D, dX.as<double>(), N, M, tol, max_blocks, d0 ? d0c.as<double>() : nullptr, b, &m);
+  }
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  std::vector<long long> hpiv((size_t)M);
+  if (e == hipSuccess) e = hipMemcpy(hpiv.data(), b.piv, (size_t)M * sizeof(long long), hipMemcpyDeviceToHost);
+  if (e == hipSuccess && m > 0) e = hipMemcpy(pivots, b.pv, (size_t)m * sizeof(double), hipMemcpyDeviceToHost);
+  if (e == hipSuccess && U && m > 0) e = hipMemcpy(U, b.U, (size_t)m * D * sizeof(double), hipMemcpyDeviceToHost);
+  if (e == hipSuccess && Lt) e = hipMemcpy(Lt, dL, lbytes, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && d) e = hipMemcpy(d, b.d, (size_t)N * sizeof(double), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(trace, b.trace, sizeof(double), hipMemcpyDeviceToHost);
+  (void)hipFree(work);
+  (void)hipFree(dL);
+  if (e != hipSuccess) return GOGP_EHIP;
+  for (int64_t t = 0; t < m; ++t) idx[t] = (int64_t)hpiv[(size_t)t];
+  *m_out = m;
+  return GOGP_OK;
+}
+
 // ---- the small kernels that finish leave-one-out, multi-output and sparse evaluations, through their product launchers
 // (tests/test_finish_kernels.py): the kernels of loo.hip, multi_dots_kernel (multi.hip) and the element-wise, scalar and
 // Produce kernels of sparse.hip.  The rules of the hooks above: every argument is checked before the device is touched,

@@ -701,6 +701,40 @@ class GP:
         u = np.ascontiguousarray(_arr(U).reshape(-1, self.NDim))
         self._check(_lib.lib().gogp_sparse_set_inducing(self._h, _dp(u if len(u) else np.zeros(1)), len(u)))
 
+    def SelectInducing(self, x, M: int, X=None, tol=None):
+        """(idx, U, pivots, trace): greedy conditional-variance selection of at most M inducing points among the rows of
+        X at x = log theta (gogp_sparse_select_inducing) -- a partial Cholesky factorisation of k(X, X) with diagonal
+        pivoting; the noise does not enter.  ``X = None`` selects among the rows of the sparse data already on the device
+        (gogp_sparse_select_inducing_resident).  The selection stops once no residual variance exceeds ``tol`` (None: the
+        jitter 10^"sparse_jitter_log10"), so the arrays are cut to the m <= M points taken: idx their rows in pick order,
+        U = X[idx], pivots the residual variances at the picks, trace = t0 - tr Qff for these inducing points.  Nothing of
+        the process's state changes."""
+        xa = np.ascontiguousarray(_arr(x).reshape(-1))
+        M = int(M)
+        cap = max(M, 1)
+        idx, piv, U = np.zeros(cap, dtype=np.int64), np.zeros(cap), np.zeros((cap, self.NDim))
+        m, tr = ctypes.c_int64(0), ctypes.c_double(0.0)
+        t = -1.0 if tol is None else float(tol)
+        L = _lib.lib()
+        if X is None:
+            rc = L.gogp_sparse_select_inducing_resident(self._h, _dp(xa if xa.size else np.zeros(1)), xa.size, M, t,
+                                                        _ip(idx), _dp(piv), _dp(U), ctypes.byref(m), ctypes.byref(tr))
+        else:
+            xs = np.ascontiguousarray(_arr(X).reshape(-1, self.NDim))
+            rc = L.gogp_sparse_select_inducing(self._h, _dp(xa if xa.size else np.zeros(1)), xa.size,
+                                               _dp(xs) if len(xs) else None, len(xs), M, t, _ip(idx), _dp(piv), _dp(U),
+                                               ctypes.byref(m), ctypes.byref(tr))
+        self._check(rc)
+        k = m.value
+        return idx[:k].copy(), U[:k].copy(), piv[:k].copy(), tr.value
+
+    def SetSparseGreedy(self, X, Y, M: int, x, tol=None) -> np.ndarray:
+        """SelectInducing(x, M, X, tol) followed by SetSparse(X, Y, U) with the points it took; returns their rows idx
+        (m <= M of them: the sparse data then has m inducing points)."""
+        idx, U, _, _ = self.SelectInducing(x, M, X=X, tol=tol)
+        self.SetSparse(X, Y, U)
+        return idx
+
     def SparseObserve(self, x) -> float:
         """The collapsed variational bound of Titsias (2009) at x = log theta (gogp_sparse_observe): a lower bound of
         the LML of the sparse data that costs O(N M^2)."""
@@ -1325,6 +1359,22 @@ class SparseModel:
         v = self.gp.SparseObserve(self._x[:p])
         return v + self.Priors.Observe(self._x[:p]) if self.Priors is not None else v
 
+    def reselect(self, x, tol=None) -> np.ndarray:
+        """Re-select the inducing points among the rows of the sparse data at x = log theta (the first P entries of x) by
+        GP.SelectInducing's resident form and move them there (GP.SetInducing); returns the rows taken.  The number of
+        inducing points is fixed by GP.SetSparse: where the selection stops short of it, this raises and changes nothing.
+        An explicit call only -- the model never re-selects by itself; an Observe has to follow."""
+        p = self.gp._ns + self.gp._nn
+        m = self.gp._sparse_m
+        if m < 1:
+            raise GogpError(_lib.GOGP_ESTATE, "reselect before SetSparse")
+        idx, U, _, _ = self.gp.SelectInducing(_arr(x).reshape(-1)[:p], m, X=None, tol=tol)
+        if len(idx) < m:
+            raise GogpError(_lib.GOGP_ESTATE, "reselect: the selection stopped at %d of the %d inducing points of SetSparse; "
+                            "they stay as they were" % (len(idx), m))
+        self.gp.SetInducing(U)
+        return idx
+
     def Gradient(self) -> np.ndarray:
         if self.inducing:
             g, du = self.gp.SparseGradientInducing()
@@ -1848,6 +1898,56 @@ def finish_check(which: str, device: int = -1, **args):
     float64 arrays (their lengths are passed along) and scalars, all by keyword.  Returns copies of the in / out arrays
     after the launch, in the order of the table (a single array if there is one)."""
     return _table_check(_lib.FINISH_HOOKS, which, device, args, "finish_check")
+
+
+def select_blocks(N: int, max_blocks: int = 0) -> int:
+    """Workgroups of a step of the greedy selection (select.hip: select_blocks): one per 256 rows, 1024 at most,
+    max_blocks where that is positive and smaller.  Workgroup b owns the rows i with (i // 256) % workgroups == b."""
+    nb = max(1, min((N + 255) // 256, 1024))
+    return max_blocks if 0 < max_blocks < nb else nb
+
+
+def select_step_check(kp, X: np.ndarray, N: int, Lt: np.ndarray, ldn: int, j: int, tol: float, d: np.ndarray,
+                      sel: np.ndarray, part_v: np.ndarray, part_i: np.ndarray, max_blocks: int = 0, device: int = -1):
+    """One step of the greedy selection (test hook gogp_test_select_step) on flat host arrays: Lt j + 1 columns of ldn
+    (column-major), d (N), sel (N, uint8), the previous launch's partial maxima (values, rows).  Returns copies after the
+    launch: (Lt, d, sel, out_v, out_i, p, dp), p = -1 where the step stopped."""
+    X, Lt, d = _vec(X, "X"), _vec(Lt, "Lt").copy(), _vec(d, "d").copy()
+    sel = np.ascontiguousarray(np.asarray(sel, dtype=np.uint8)).copy()
+    part_v = _vec(part_v, "part_v")
+    part_i = np.ascontiguousarray(np.asarray(part_i, dtype=np.int64))
+    nb = max(part_v.size, 1)
+    out_v, out_i = np.full(nb, np.nan), np.full(nb, -1, dtype=np.int64)
+    p, dp = ctypes.c_int64(-2), ctypes.c_double(np.nan)
+    rc = _lib.hooks().gogp_test_select_step(device, kp, _dp(X), X.size, N, _dp(Lt), Lt.size, ldn, j, tol, _dp(d), d.size,
+                                            sel.ctypes.data_as(ctypes.POINTER(ctypes.c_ubyte)), sel.size, _dp(part_v),
+                                            _ip(part_i), min(part_v.size, part_i.size), max_blocks, _dp(out_v), _ip(out_i),
+                                            out_v.size, ctypes.byref(p), ctypes.byref(dp))
+    if rc != _lib.GOGP_OK:
+        raise GogpError(rc, "test_select_step")
+    return Lt, d, sel, out_v, out_i, p.value, dp.value
+
+
+def select_run_check(kp, X: np.ndarray, N: int, M: int, tol: float, max_blocks: int = 0, d0=None, device: int = -1):
+    """The whole greedy selection (test hook gogp_test_select_run) with the grid capped at max_blocks and, d0 given, d0 in
+    the place of the initial diagonal.  Returns (idx, pivots, U, Lt, d, trace) cut to the m steps taken: Lt as m columns of
+    N rows (column-major on the device, returned as an N x m array), d the final residuals."""
+    X = _vec(X, "X")
+    D = kp.ndim
+    ldn = (N + 255) // 256 * 256
+    cols = max(min(M, N), 1)
+    idx, piv, U = np.zeros(max(M, 1), dtype=np.int64), np.zeros(max(M, 1)), np.zeros(max(M, 1) * D)
+    Lt, d = np.zeros(cols * max(ldn, 1)), np.zeros(max(N, 1))
+    d0a = None if d0 is None else _vec(d0, "d0")
+    m, tr = ctypes.c_int64(0), ctypes.c_double(0.0)
+    rc = _lib.hooks().gogp_test_select_run(device, kp, _dp(X), X.size, N, M, tol, max_blocks, _dp(d0a),
+                                           0 if d0a is None else d0a.size, _ip(idx), _dp(piv), _dp(U), U.size, _dp(Lt),
+                                           Lt.size, _dp(d), d.size, ctypes.byref(m), ctypes.byref(tr))
+    if rc != _lib.GOGP_OK:
+        raise GogpError(rc, "test_select_run")
+    k = m.value
+    L = Lt.reshape(cols, max(ldn, 1))[:k, :N].T.copy()
+    return idx[:k].copy(), piv[:k].copy(), U.reshape(-1, D)[:k].copy(), L, d[:N].copy(), tr.value
 
 
 def laplace_kernel_check(which: str, device: int = -1, **args):

@@ -367,6 +367,22 @@ class GP {
     if (u.empty() || u.size() % (size_t)NDim) throw Error(GOGP_EARG, "len(u)");
     check(gogp_sparse_set_inducing(h_, u.data(), (int64_t)(u.size() / (size_t)NDim)));
   }
+  // Greedy conditional-variance selection of at most M inducing points among the n rows of x (row-major n x NDim) at
+  // logtheta (gogp_sparse_select_inducing): a partial Cholesky factorisation of k(x, x) with diagonal pivoting; the noise
+  // does not enter.  It stops once no residual variance exceeds tol (tol < 0: the jitter 10^"sparse_jitter_log10"), so
+  // idx (the rows in pick order), u (row-major, = x[idx]) and pivots (the residual variances at the picks) hold the
+  // m <= M points taken; returns the trace term t0 - tr Qff for them.  Nothing of the process's state changes.
+  double SelectInducing(const std::vector<double> &logtheta, const std::vector<double> &x, int64_t M, double tol,
+                        std::vector<int64_t> &idx, std::vector<double> &u, std::vector<double> &pivots) {
+    if (x.size() % (size_t)NDim) throw Error(GOGP_EARG, "len(x)");
+    return select(logtheta, &x, M, tol, idx, u, pivots);
+  }
+  // ... among the rows of the sparse data already on the device (gogp_sparse_select_inducing_resident): re-selecting at
+  // the current parameters without sending the data again.  SetInducing(u) moves the points there when m == M.
+  double SelectInducingResident(const std::vector<double> &logtheta, int64_t M, double tol, std::vector<int64_t> &idx,
+                                std::vector<double> &u, std::vector<double> &pivots) {
+    return select(logtheta, nullptr, M, tol, idx, u, pivots);
+  }
   // SparseGradient and, from the same pass over the data, d bound / d U of the inducing points of SetSparse (dU:
   // row-major M x NDim)
   std::vector<double> SparseGradientInducing(std::vector<double> &dU) {
@@ -593,6 +609,27 @@ class GP {
     for (size_t i = 0; i < x.size(); ++i)
       for (int d = 0; d < NDim; ++d) flat[i * NDim + d] = x[i][d];
     return flat;
+  }
+  // the two forms of the greedy selection: x == nullptr is the resident one
+  double select(const std::vector<double> &logtheta, const std::vector<double> *x, int64_t M, double tol,
+                std::vector<int64_t> &idx, std::vector<double> &u, std::vector<double> &pivots) {
+    const size_t cap = M > 0 ? (size_t)M : 1;
+    idx.assign(cap, 0);
+    pivots.assign(cap, 0.0);
+    u.assign(cap * (size_t)NDim, 0.0);
+    int64_t m = 0;
+    double trace = 0.0;
+    if (x)
+      check(gogp_sparse_select_inducing(h_, logtheta.data(), (int64_t)logtheta.size(), x->empty() ? nullptr : x->data(),
+                                        (int64_t)(x->size() / (size_t)NDim), M, tol, idx.data(), pivots.data(), u.data(), &m,
+                                        &trace));
+    else
+      check(gogp_sparse_select_inducing_resident(h_, logtheta.data(), (int64_t)logtheta.size(), M, tol, idx.data(),
+                                                 pivots.data(), u.data(), &m, &trace));
+    idx.resize((size_t)m);
+    pivots.resize((size_t)m);
+    u.resize((size_t)m * (size_t)NDim);
+    return trace;
   }
   int push() {
     if (!dirty_) return GOGP_OK;

@@ -523,6 +523,53 @@ int gogp_sparse_multi_gradient(gogp_handle *h, double *grad, int64_t len /* P */
 int gogp_sparse_multi_gradient_inducing(gogp_handle *h, double *grad, int64_t len, double *dU /* M x ndim */);
 int gogp_sparse_multi_produce(gogp_handle *h, const double *Z, int64_t m, double *mu /* m x T */, double *sigma /* m */);
 
+/* Sparse: choosing the inducing points.  Greedy conditional-variance selection (Burt, Rasmussen & van der Wilk, 2019 /
+ * 2020): a partial Cholesky factorisation of k(X, X) with diagonal pivoting, which at every step takes the row whose
+ * variance given the rows already chosen is largest.  X (N x ndim), the similarity k at theta = exp(x), a cap M and a
+ * tolerance tol >= 0; the noise does not enter:
+ *     d_i = k(x_i, x_i)                                      i < N
+ *     for j = 0 .. M-1:
+ *         p = the LOWEST index among the maximisers of d      (ties: lowest index; all d equal at j = 0, so idx[0] = 0)
+ *         if not (d_p > tol): stop, m = j                     (also stops on NaN)
+ *         idx[j] = p,  pivots[j] = d_p
+ *         l_i = (k(x_i, x_p) - sum_{t<j} L[i][t] L[p][t]) / sqrt(d_p)   for rows not yet selected
+ *         l_p = sqrt(d_p);  l_i = 0 exactly for rows selected earlier
+ *         L[:, j] = l;  d_i -= l_i^2;  d_p = 0 exactly (selected rows keep d = 0)
+ *     m = number of steps taken;  trace = sum_i d_i  (= tr K - |L|_F^2 = t0 - tr Qff for U = X[idx])
+ * pivots is non-increasing up to rounding; L[idx] equals chol(k(U, U)) in pivot order, so the Cholesky pivots of Kuu stay
+ * above tol; a duplicated row is never picked twice; the selection greedily minimises the trace term of the bound.
+ * gogp_sparse_select_inducing uploads X for the call; gogp_sparse_select_inducing_resident selects among the rows of the
+ * sparse data already on the device (GOGP_ESTATE before gogp_sparse_set_data): re-selecting at the current theta during
+ * an optimisation without sending N rows again.  One body.  idx (M), pivots (M), U (M x ndim): the entries from m on are
+ * left alone; pivots, U and trace may be NULL.  tol < 0 means 10^"sparse_jitter_log10": a residual variance below the
+ * jitter is indistinguishable from it.  M > N is legal and gives m <= N; N == 0 gives m = 0, trace = 0 and GOGP_OK.
+ * Nothing of the handle changes -- dense data / factor / K^-1, sparse data and its observed state, batch data, candidates,
+ * multi-output, basis and Laplace state: every later call returns the bits it would have returned without this one.
+ * Two identical calls return identical bits (one launch per step, no atomics, every sum in a fixed order).
+ * GOGP_EARG: h, x, idx or m_out NULL, X NULL with N > 0, N < 0, len != P, a non-finite value in x or X, M outside
+ * 1 .. GOGP_SPARSE_MAX_M, tol = +inf or NaN, the kinds of handle the sparse calls refuse (precision = 32, sharded, event
+ * discounts).  GOGP_ENOMEM: the transient factor could not be allocated (gogp_last_error carries the size).
+ * Device memory, allocated by the call on the handle's main stream and freed before it returns: the factor, min(M, N)
+ * columns of N rounded up to 256 doubles (34 GB at N = 1048576, M = 4096), X (the first form) and O(N + M ndim) beside it.
+ * Cost: one launch and one pass over the factor per step, 8 N j bytes at step j, 4 N m^2 bytes in all.  Measured on one
+ * MI355X (tools/select_inducing_probe.py, profiles/select_inducing.txt, which carries the build id of the library before
+ * these figures were written here; D = 8, tol = 0 so that m = M, the resident form, medians of 5): M = 512 / 2048 / 4096
+ * at N = 65536 13.8 / 202 / 785 ms, at N = 262144 54.6 / 793 / 3136 ms, at N = 1048576 218 / 3040 / 11581 ms -- 5.0 .. 6.1
+ * TB/s of that byte count beside the ~6.3 TB/s of HBM, and 0.9 / 6 / 7 evaluations of bound + gradient: a one-off before an
+ * optimisation, not part of its loop.  Against a random subset of the same M at the same theta: (max L_ii / min L_ii)^2 of
+ * the factor of Kuu + 1e-8 I falls by a factor of 50 .. 400, and at M = 4096 and the default jitter d bound / d U agrees
+ * with a central difference to 7e-5 .. 4e-4 where the random subset is off by 0.09 .. 0.9 of its norm (above).  The bound
+ * itself is LOWER for the greedy points in every cell of that workload (N = 65536, M = 512: -28836 against -13996; trace
+ * term 61.6 against 29.3): the rows of largest residual variance of uniform inputs in eight dimensions lie near the corners.
+ * On the test suite's families in one to three dimensions the trace term falls by a factor of 2 .. 17.  DESIGN.md section 4,
+ * "Sparse: choosing the inducing points". */
+int gogp_sparse_select_inducing(gogp_handle *h, const double *x /* log theta */, int64_t len /* P */,
+                                const double *X /* N x ndim */, int64_t N, int64_t M, double tol,
+                                int64_t *idx /* M */, double *pivots /* M */, double *U /* M x ndim */,
+                                int64_t *m_out, double *trace);
+int gogp_sparse_select_inducing_resident(gogp_handle *h, const double *x, int64_t len, int64_t M, double tol,
+                                         int64_t *idx, double *pivots, double *U, int64_t *m_out, double *trace);
+
 /* k independent Observe + Gradient evaluations at once: handle hs[i] (each created and given
  * its data separately; they may hold the same data) evaluates x[i*len .. (i+1)*len) from its own
  * host thread, so the dependent launch chains of the k evaluations overlap on the GPU.

@@ -323,6 +323,28 @@ int gogp_test_sparse_xty(int device, const double *Vt, int64_t vt_len, int64_t l
 int gogp_test_sparse_xty_slabs(int64_t rows, int64_t M, int64_t T, int64_t *rows_per_slab);
 int gogp_test_sparse_xty_slabs_bound(int64_t rows, int64_t M, int64_t T);
 
+/* Greedy selection of inducing points (select.hip; the algorithm: include/gogp_hip.h, gogp_sparse_select_inducing).
+ * gogp_test_select_step: ONE step j (0 <= j < GOGP_SPARSE_MAX_M) of launch_select_step on host arrays.  X: N rows (1 <= N <=
+ * 2^22) of kparams->ndim; Lt (in / out): j + 1 columns of ldn doubles (ldn >= N, a multiple of 256), column t at Lt + t ldn --
+ * the columns < j are read on the rows < N, column j receives the new column on the rows < N, nothing else is touched; d
+ * (in / out, N), sel (in / out, N: 1 = selected earlier); part_v / part_i: the previous launch's partial maxima, one (value,
+ * row) pair per workgroup, part_len == the workgroups of the launch = min(ceil(N / 256), 1024), or max_blocks where that is
+ * positive and smaller (workgroup b owns the rows i with (i / 256) mod workgroups == b), every part_i in [0, N).  out_v /
+ * out_i (out_len >= workgroups): the new partials; *p, *dp: the pivot and its residual, *p = -1 (and nothing else written)
+ * where the step stops: not (dp > tol).  tol finite, >= 0.  No event discounts.
+ * gogp_test_select_run: the whole loop (select_run) with max_blocks forced and, d0 != NULL, d0 (N) in the place of the
+ * initial diagonal k(x_i, x_i).  idx, pivots: M entries, the first *m_out written; optional (NULL or with their lengths) U
+ * (M x ndim), Lt (min(M, N) columns of N rounded up to 256; NaN where no step wrote) and d (N, the final residuals). */
+int gogp_test_select_step(int device, const gogp_test_kparams *kparams, const double *X, int64_t x_len, int64_t N,
+                          double *Lt, int64_t lt_len, int64_t ldn, int64_t j, double tol, double *d, int64_t d_len,
+                          unsigned char *sel, int64_t sel_len, const double *part_v, const int64_t *part_i,
+                          int64_t part_len, int max_blocks, double *out_v, int64_t *out_i, int64_t out_len, int64_t *p,
+                          double *dp);
+int gogp_test_select_run(int device, const gogp_test_kparams *kparams, const double *X, int64_t x_len, int64_t N, int64_t M,
+                         double tol, int max_blocks, const double *d0, int64_t d0_len, int64_t *idx, double *pivots,
+                         double *U, int64_t u_len, double *Lt, int64_t lt_len, double *d, int64_t d_len, int64_t *m_out,
+                         double *trace);
+
 /* ---- the small kernels that finish a leave-one-out, multi-output or sparse evaluation, through their product launchers
  * (tests/test_finish_kernels.py): the four kernels of loo.hip, multi_dots_kernel (multi.hip) and the element-wise, scalar and
  * Produce kernels of sparse.hip.  The rules of the hooks above: lengths count elements, every array goes to the device whole
