@@ -406,6 +406,21 @@ HOOK_SYMBOLS += [("gogp_test_" + k, ctypes.c_int, [ctypes.c_int] + [t for _, kin
                  for k, spec in SHARD_HOOKS.items()]
 HOOK_SYMBOLS += [("gogp_test_chunk_tdot_scratch", _i64, [_i64, ctypes.c_int])]
 
+#: the hooks of the kernels of gram.hip and of pgrad.hip's forecast derivatives (tests/test_gram_kernels.py; gp.gram_*_check,
+#: gp.cross_check, gp.prior_check, gp.kmatvec_check, gp.pgrad_check)
+_kpp, _vp, _ci = ctypes.POINTER(CKParams), ctypes.c_void_p, ctypes.c_int
+HOOK_SYMBOLS += [
+    ("gogp_test_gram_split", _ci, [_ci, _ci, _kpp, _ci, _dp, _i64, _i64, _i64, _i64, _ci, _i64, _vp, _i64, _i64]),
+    ("gogp_test_gram_local", _ci, [_ci, _ci, _kpp, _ci, _dp, _i64, _i64, _i64, _i64, _i64] + [_ci] * 5 + [_vp, _i64, _i64]),
+    ("gogp_test_cross", _ci, [_ci, _ci, _kpp, _ci, _dp, _i64, _i64, _i64, _dp, _i64, _i64, _i64, _vp, _i64, _i64]),
+    ("gogp_test_prior", _ci, [_ci, _kpp, _dp, _i64, _i64, _dp, _i64]),
+    ("gogp_test_kmatvec", _ci,
+     [_ci, _kpp, _ci, _ci, _dp, _i64, _i64, _i64, _dp, _i64, _dp, _i64, _ci, _ci, _ci, _dp, _i64, _dp, _i64]),
+    ("gogp_test_pgrad_slabs", _ci, [_i64, _i64, ctypes.POINTER(ctypes.c_int)]),
+    ("gogp_test_pgrad", _ci, [_ci, _kpp, _ci, _dp, _i64, _i64, _i64, _dp, _i64, _i64, _dp, _i64, _dp, _i64, _i64, _dp, _i64]
+     + [_dp, _i64] * 3),
+]
+
 
 def build(force: bool = False) -> str:
     """Compile every HIP source for gfx950 into gogp_amd/libgogp_hip.so

@@ -189,11 +189,21 @@ void launch_grad_reduce(hipStream_t s, const DevParams *p, int ndim, int ard_dim
                         double *partials, double *out, bool radial1 = false, int mfma_min_dims = 1, bool ev = false,
                         int max_blocks = 0);
 
-void launch_gram_lower(hipStream_t s, const DevParams *p, int ndim, const double *X,
-                       int64_t n, int64_t npad, double *K, int64_t ld, bool ev = false);
+// gram.hip.  What every launcher of it below relies on (the test hooks of include/gogp_testhooks.h refuse the rest):
+//  - npad, mpad, mrows, ncols are positive multiples of 64 and ld covers the padded width; the kernels write WHOLE
+//    64 x 64 tiles, so the output holds all npad (cross: mpad; local: mrows) rows.
+//  - X holds npad rows of ndim doubles that may be READ, whatever they hold: with one radial term (nterms == 1, not
+//    periodic) gram_kernel<false>, gram_local_kernel and kmatvec_kernel<true> read rows n .. npad - 1 unguarded, through
+//    scalar loads, and keep them out of every result.  Z (launch_cross, launch_prior) and v are read guarded: rows < m / n.
+//  - radial1 (launch_residual, launch_kmatvec_share) may be set only with one radial term; false there selects the
+//    generic instance, which returns the same.
+//  - ev is never combined with an ARD term (gogp_set_events refuses it).
+//  - launch_gram_lower_split: wcols is a multiple of 64 and at least 64 (0 would launch an empty grid); beyond npad it is
+//    clipped, and the second launch is skipped.  Tiles above the diagonal are not written.
 // Local tiles (mrows x ncols) of a 2-D block-cyclic Gram matrix: tiles of the global lower
 // triangle get kernel values (identity padding for rows >= n), distribution blocks strictly
-// above the diagonal are zero-filled (the work area R of the triangular inverse).
+// above the diagonal are zero-filled (the work area R of the triangular inverse); the 64-tiles above the diagonal
+// inside a diagonal distribution block (nb >= 128) are not written.
 void launch_gram_local(hipStream_t s, const DevParams *p, int ndim, const double *X, int64_t n,
                        int64_t mrows, int64_t ncols, BlockMap map, double *K, int64_t ld, bool ev = false);
 void launch_gram_local(hipStream_t s, const DevParams *p, int ndim, const double *X, int64_t n,

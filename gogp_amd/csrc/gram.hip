@@ -91,7 +91,8 @@ __global__ __launch_bounds__(256) void GOGP_EVN(gram_kernel)(const DevParams *__
     // inside.  The column coordinate is read from LDS once per dimension instead of once per
     // (row, dimension), and the rows' coordinates are wave-uniform: they come straight from X
     // through scalar loads (X is padded to npad rows), not through LDS.  Same operations in the same
-    // order per pair as simil_value() -- bit-identical -- at 1/32 of its LDS reads.
+    // order per pair as simil_value() -- bit-identical (tests/test_gram_kernels.py holds this path, gram_local_kernel's
+    // and kmatvec_kernel<true>'s to it against the generic one) -- at 1/32 of its LDS reads.
     const int rbase = __builtin_amdgcn_readfirstlane(ty) * 16;
     const double *xr = Rsrc + (r0 + rbase) * D;
     double s[16];
@@ -358,12 +359,30 @@ __global__ void kmatvec_finish_kernel(const double *__restrict__ part, int nslab
   r[i] = (i < n) ? (y ? y[i] - s : s) : 0.0;
 }
 
+// Dynamic LDS beyond 64 KB is said to the runtime per kernel function before the launch (grad.hip: gr_launch), with the
+// most the function can be asked for (GOGP_MAX_NDIM dimensions, events).  Whether the runtime refuses such a launch
+// without the attribute has NOT been measured: the launch sites below asked for up to 66560 bytes without it until
+// they were found by reading.  Should the attribute be refused, the launch that follows fails and the caller's
+// hipGetLastError reports it.
+static void allow_lds(const void *fn, size_t lds, size_t cap) {
+  if (lds > 64 * 1024) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cap);
+}
+constexpr size_t KMATVEC_LDS_CAP = (128 * GOGP_MAX_NDIM + 64 + 256 + 64) * sizeof(double);
+constexpr size_t GRAM_LDS_CAP = (2 * 64 * GOGP_MAX_NDIM + 128) * sizeof(double);
+static const void *kmatvec_fn(bool radial1, bool ev) {
+  return ev ? (radial1 ? reinterpret_cast<const void *>(&kmatvec_kernel_ev<true>)
+                       : reinterpret_cast<const void *>(&kmatvec_kernel_ev<false>))
+            : (radial1 ? reinterpret_cast<const void *>(&kmatvec_kernel<true>)
+                       : reinterpret_cast<const void *>(&kmatvec_kernel<false>));
+}
+
 void launch_residual(hipStream_t s, const DevParams *p, int ndim, const double *X, int64_t n,
                      int64_t npad, const double *v, const double *y, double *part, int nslab, double *r,
                      bool radial1, bool ev) {
   const int ntile = (int)(npad / 64);
   const int tps = (ntile + nslab - 1) / nslab;
   const size_t lds = (size_t)(128 * ndim + 64 + 256) * sizeof(double);
+  allow_lds(kmatvec_fn(radial1, ev), lds + (ev ? 64 * 8 : 0), KMATVEC_LDS_CAP);  // 62 dimensions and up
   if (ev && radial1)
     GOGP_KLAUNCH((kmatvec_kernel_ev<true>), dim3((unsigned)ntile, (unsigned)nslab), dim3(256), lds + 64 * 8, s, p, X,
                  (long)n, v, (long)npad, tps, part, 0, ntile);
@@ -391,17 +410,10 @@ void launch_kmatvec_share(hipStream_t s, const DevParams *p, int ndim, const dou
   const int t0 = std::min(ntile, part_idx * per), t1 = std::min(ntile, (part_idx + 1) * per);
   const int tps = std::max(1, (t1 - t0 + nslab - 1) / nslab);
   const size_t lds = (size_t)(128 * ndim + 64 + 256) * sizeof(double);
-  // 63 dimensions and up need more than 64 KB: said to the runtime, per launch (grad.hip: gr_launch).  Before, such a
-  // launch -- the sharded fp32 refinement at D >= 63, this function's only other caller -- was left to what the runtime
-  // tolerates.  Should the attribute be refused, the launch below fails and the caller's hipGetLastError reports it.
-  if (lds + 64 * 8 > 64 * 1024) {
-    const int cap = (int)((128 * GOGP_MAX_NDIM + 64 + 256 + 64) * sizeof(double));
-    const void *fn = ev ? (radial1 ? reinterpret_cast<const void *>(&kmatvec_kernel_ev<true>)
-                                   : reinterpret_cast<const void *>(&kmatvec_kernel_ev<false>))
-                        : (radial1 ? reinterpret_cast<const void *>(&kmatvec_kernel<true>)
-                                   : reinterpret_cast<const void *>(&kmatvec_kernel<false>));
-    (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, cap);
-  }
+  // 62 dimensions and up need more than 64 KB (66048 bytes at D = 62; 512 more with events): said to the runtime, per
+  // launch (allow_lds above).  Before, such a launch -- the sharded fp32 refinement at D >= 62, this function's only other
+  // caller -- was left to what the runtime tolerates.
+  allow_lds(kmatvec_fn(radial1, ev), lds + (ev ? 64 * 8 : 0), KMATVEC_LDS_CAP);
   if (ev && radial1)
     GOGP_KLAUNCH((kmatvec_kernel_ev<true>), dim3((unsigned)ntile, (unsigned)nslab), dim3(256), lds + 64 * 8, s, p, X,
                  (long)n, v, (long)npad, tps, part, t0, t1);
@@ -428,25 +440,7 @@ __global__ void prior_kernel(const DevParams *__restrict__ Pp, const double *__r
       P, [&](int d) { return z[d]; }, [&](int d) { return z[d]; });
 }
 
-template <class T>
-static void gram_lower_t(hipStream_t s, const DevParams *p, int ndim, const double *X, int64_t n,
-                         int64_t npad, T *K, int64_t ld, bool ev) {
-  const int nt = (int)(npad / 64);
-  const int ntiles = nt * (nt + 1) / 2;
-  const size_t lds = (size_t)2 * 64 * ndim * sizeof(double);
-  if (ev)
-    GOGP_KLAUNCH((gram_kernel_ev<false, T>), dim3(ntiles), dim3(256), lds + 128 * 8, s, p, X, (long)n, X, (long)n, K,
-                 (long)ld, nt, 0, 0, 0L);
-  else
-    GOGP_KLAUNCH((gram_kernel<false, T>), dim3(ntiles), dim3(256), lds, s, p, X, (long)n, X,
-                       (long)n, K, (long)ld, nt, 0, 0, 0L);
-}
-void launch_gram_lower(hipStream_t s, const DevParams *p, int ndim, const double *X, int64_t n,
-                       int64_t npad, double *K, int64_t ld, bool ev) {
-  gram_lower_t(s, p, ndim, X, n, npad, K, ld, ev);
-}
-
-// The same lower triangle in two launches: block columns [0, wcols) on `s_first` (the panel
+// The lower triangle in two launches: block columns [0, wcols) on `s_first` (the panel
 // chain can start on them while the rest is still being written), the remaining triangle on
 // `s_rest`.  wcols is a multiple of 64.
 template <class T>
@@ -460,6 +454,7 @@ static void gram_lower_split_t(hipStream_t s_first, hipStream_t s_rest, const De
   const unsigned nz = (unsigned)tl_batch.k;
   const int nr = nt - w;
   if (ev) {
+    allow_lds(reinterpret_cast<const void *>(&gram_kernel_ev<false, T>), lds + 128 * 8, GRAM_LDS_CAP);  // D = 64
     GOGP_KLAUNCH((gram_kernel_ev<false, T>), dim3(nt * w, 1, nz), dim3(256), lds + 128 * 8, s_first, p, X, (long)n, X,
                  (long)n, K, (long)ld, nt, w, 0, tl_batch.stride);
     if (nr > 0)
@@ -490,6 +485,7 @@ static void gram_local_t(hipStream_t s, const DevParams *p, int ndim, const doub
   const int ntr = (int)(mrows / 64), ntc = (int)(ncols / 64);
   if (ntr <= 0 || ntc <= 0) return;
   const size_t lds = (size_t)2 * 64 * ndim * sizeof(double);
+  if (ev) allow_lds(reinterpret_cast<const void *>(&gram_local_kernel_ev<T>), lds + 128 * 8, GRAM_LDS_CAP);  // D = 64
   if (ev)
     GOGP_KLAUNCH((gram_local_kernel_ev<T>), dim3(ntr * ntc), dim3(256), lds + 128 * 8, s, p, X, (long)n, K, (long)ld,
                  ntc, map);
@@ -511,6 +507,7 @@ static void cross_t(hipStream_t s, const DevParams *p, int ndim, const double *X
                     int64_t npad, const double *Z, int64_t m, int64_t mpad, T *KsT, int64_t ld, bool ev) {
   const int ntr = (int)(mpad / 64), ntc = (int)(npad / 64);
   const size_t lds = (size_t)2 * 64 * ndim * sizeof(double);
+  if (ev) allow_lds(reinterpret_cast<const void *>(&gram_kernel_ev<true, T>), lds + 128 * 8, GRAM_LDS_CAP);  // D = 64
   if (ev)
     GOGP_KLAUNCH((gram_kernel_ev<true, T>), dim3(ntr * ntc), dim3(256), lds + 128 * 8, s, p, Z, (long)m, X, (long)n, KsT,
                  (long)ld, ntc, 0, 0, 0L);

@@ -2670,3 +2670,200 @@ extern "C" int gogp_test_vector_op(int device, int op, int precision, void *a, i
     }
   });
 }
+
+// ---- the kernels of gram.hip and the forecast-derivative kernels of pgrad.hip, through their product launchers
+// (tests/test_gram_kernels.py).  The rules of the hooks above.  What they refuse beyond the arrays' lengths follows from
+// the kernels (common.h states it at the launchers): whole 64 x 64 tiles are written, so npad / mpad / mrows / ncols are
+// positive multiples of 64 and the output holds all of their rows; the one-radial-term paths read rows n .. npad - 1 of X
+// unguarded, so X holds npad rows (and GOGP_MAX_NDIM doubles of slack, the convention of gogp_test_grad_reduce); wcols == 0
+// would launch an empty grid; radial1 goes with one radial term only; no instance has events and an ARD term.
+namespace {
+bool gram_args_ok(const gogp_test_kparams *kp, int k, int radial1, int ev) {
+  if ((ev != 0 && ev != 1) || (radial1 != 0 && radial1 != 1)) return false;
+  return kparams_ok(kp, k, ard_dims_of(kp), radial1, 1, ev);  // (two ARD terms: ard_dims_of is 0, which kparams_ok refuses)
+}
+bool pad_ok(int64_t npad) { return npad > 0 && npad % 64 == 0 && npad <= GR_NPAD_MAX; }
+}  // namespace
+
+extern "C" int gogp_test_gram_split(int device, int precision, const gogp_test_kparams *kparams, int ev, const double *X,
+                                    int64_t x_len, int64_t n, int64_t npad, int64_t wcols, int k, int64_t bstride, void *K,
+                                    int64_t k_len, int64_t ld) {
+  if (!kparams || !X || !K || !prec_ok(precision) || !sh_batch(precision, k, &bstride)) return GOGP_EARG;
+  if (!gram_args_ok(kparams, k, 0, ev) || !pad_ok(npad) || n < 1 || n > npad || ld < npad) return GOGP_EARG;
+  if (wcols < 64 || wcols % 64 || wcols > GR_NPAD_MAX) return GOGP_EARG;
+  // every per-candidate buffer shares the stride: it must hold the matrix and the parameters
+  if (k > 1 && (bstride < (npad - 1) * ld + npad || bstride * 8 < (int64_t)sizeof(DevParams))) return GOGP_EARG;
+  const int ndim = kparams[0].ndim;
+  if (x_len < npad * ndim + GOGP_MAX_NDIM || !covers(k_len, 0, ld, npad, npad, k, bstride)) return GOGP_EARG;
+  if (!device_ok(device)) return GOGP_EHIP;
+  std::vector<DevParams> hp;
+  for (int c = 0; c < k; ++c) hp.push_back(to_dev(kparams[c]));
+  DevCopy dP, dX, dK;
+  hipError_t e = up_strided(dP, hp.data(), sizeof(DevParams), k, (size_t)bstride * 8);
+  if (e == hipSuccess) e = dX.up(X, (size_t)x_len * sizeof(double));
+  if (e == hipSuccess) e = dK.up(K, (size_t)k_len * (precision / 8));
+  if (e == hipSuccess) {
+    sh_set_batch(k, bstride);
+    if (precision == 64)
+      launch_gram_lower_split(0, 0, dP.as<DevParams>(), ndim, dX.as<double>(), n, npad, dK.as<double>(), ld, wcols, ev != 0);
+    else
+      launch_gram_lower_split(0, 0, dP.as<DevParams>(), ndim, dX.as<double>(), n, npad, dK.as<float>(), ld, wcols, ev != 0);
+    sh_set_batch(1, 0);
+    e = launched();
+  }
+  if (e == hipSuccess) e = dK.down(K);
+  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+}
+
+extern "C" int gogp_test_gram_local(int device, int precision, const gogp_test_kparams *kparams, int ev, const double *X,
+                                    int64_t x_len, int64_t n, int64_t npad, int64_t mrows, int64_t ncols, int nb_shift, int pr,
+                                    int Pr, int pc, int Pc, void *K, int64_t k_len, int64_t ld) {
+  if (!kparams || !X || !K || !prec_ok(precision)) return GOGP_EARG;
+  if (!gram_args_ok(kparams, 1, 0, ev) || !pad_ok(npad) || !pad_ok(mrows) || !pad_ok(ncols) || n < 1 || n > npad || ld < ncols)
+    return GOGP_EARG;
+  if (nb_shift < 6 || nb_shift > 14 || Pr < 1 || Pc < 1 || pr < 0 || pr >= Pr || pc < 0 || pc >= Pc) return GOGP_EARG;
+  BlockMap map;
+  map.nb_shift = nb_shift;
+  map.pr = pr;
+  map.Pr = Pr;
+  map.pc = pc;
+  map.Pc = Pc;
+  // the last local row / column must be a global one inside the padded matrix (the kernel reads X there)
+  if (map.grow(mrows - 1) >= npad || map.gcol(ncols - 1) >= npad) return GOGP_EARG;
+  const int ndim = kparams->ndim;
+  if (x_len < npad * ndim + GOGP_MAX_NDIM || !covers(k_len, 0, ld, mrows, ncols, 1, 0)) return GOGP_EARG;
+  if (!device_ok(device)) return GOGP_EHIP;
+  const DevParams hp = to_dev(*kparams);
+  DevCopy dP, dX, dK;
+  hipError_t e = dP.up(&hp, sizeof hp);
+  if (e == hipSuccess) e = dX.up(X, (size_t)x_len * sizeof(double));
+  if (e == hipSuccess) e = dK.up(K, (size_t)k_len * (precision / 8));
+  if (e == hipSuccess) {
+    if (precision == 64)
+      launch_gram_local(0, dP.as<DevParams>(), ndim, dX.as<double>(), n, mrows, ncols, map, dK.as<double>(), ld, ev != 0);
+    else
+      launch_gram_local(0, dP.as<DevParams>(), ndim, dX.as<double>(), n, mrows, ncols, map, dK.as<float>(), ld, ev != 0);
+    e = launched();
+  }
+  if (e == hipSuccess) e = dK.down(K);
+  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+}
+
+extern "C" int gogp_test_cross(int device, int precision, const gogp_test_kparams *kparams, int ev, const double *X,
+                               int64_t x_len, int64_t n, int64_t npad, const double *Z, int64_t z_len, int64_t m, int64_t mpad,
+                               void *KsT, int64_t k_len, int64_t ld) {
+  if (!kparams || !X || !Z || !KsT || !prec_ok(precision)) return GOGP_EARG;
+  if (!gram_args_ok(kparams, 1, 0, ev) || !pad_ok(npad) || !pad_ok(mpad) || n < 1 || n > npad || m < 1 || m > mpad || ld < npad)
+    return GOGP_EARG;
+  const int ndim = kparams->ndim;
+  if (x_len < npad * ndim + GOGP_MAX_NDIM || z_len < mpad * ndim || !covers(k_len, 0, ld, mpad, npad, 1, 0)) return GOGP_EARG;
+  if (!device_ok(device)) return GOGP_EHIP;
+  const DevParams hp = to_dev(*kparams);
+  DevCopy dP, dX, dZ, dK;
+  hipError_t e = dP.up(&hp, sizeof hp);
+  if (e == hipSuccess) e = dX.up(X, (size_t)x_len * sizeof(double));
+  if (e == hipSuccess) e = dZ.up(Z, (size_t)z_len * sizeof(double));
+  if (e == hipSuccess) e = dK.up(KsT, (size_t)k_len * (precision / 8));
+  if (e == hipSuccess) {
+    if (precision == 64)
+      launch_cross(0, dP.as<DevParams>(), ndim, dX.as<double>(), n, npad, dZ.as<double>(), m, mpad, dK.as<double>(), ld, ev != 0);
+    else
+      launch_cross(0, dP.as<DevParams>(), ndim, dX.as<double>(), n, npad, dZ.as<double>(), m, mpad, dK.as<float>(), ld, ev != 0);
+    e = launched();
+  }
+  if (e == hipSuccess) e = dK.down(KsT);
+  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+}
+
+extern "C" int gogp_test_prior(int device, const gogp_test_kparams *kparams, const double *Z, int64_t z_len, int64_t m,
+                               double *prior, int64_t prior_len) {
+  if (!kparams || !Z || !prior || !gram_args_ok(kparams, 1, 0, 0)) return GOGP_EARG;
+  if (m < 1 || m > SH_COUNT_MAX || z_len < m * kparams->ndim || prior_len < m) return GOGP_EARG;
+  if (!device_ok(device)) return GOGP_EHIP;
+  const DevParams hp = to_dev(*kparams);
+  DevCopy dP, dZ, dp;
+  hipError_t e = dP.up(&hp, sizeof hp);
+  if (e == hipSuccess) e = dZ.up(Z, (size_t)z_len * sizeof(double));
+  if (e == hipSuccess) e = dp.up(prior, (size_t)prior_len * sizeof(double));
+  if (e == hipSuccess) {
+    launch_prior(0, dP.as<DevParams>(), dZ.as<double>(), m, dp.as<double>());
+    e = launched();
+  }
+  if (e == hipSuccess) e = dp.down(prior);
+  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+}
+
+extern "C" int gogp_test_kmatvec(int device, const gogp_test_kparams *kparams, int radial1, int ev, const double *X,
+                                 int64_t x_len, int64_t n, int64_t npad, const double *v, int64_t v_len, const double *y,
+                                 int64_t y_len, int part_idx, int nparts, int nslab, double *part, int64_t part_len,
+                                 double *out, int64_t out_len) {
+  if (!kparams || !X || !v || !part || !out || !gram_args_ok(kparams, 1, radial1, ev)) return GOGP_EARG;
+  if (!pad_ok(npad) || n < 1 || n > npad || nslab < 1 || nslab > 64 || nparts < 1 || nparts > 64 || part_idx < 0 ||
+      part_idx >= nparts)
+    return GOGP_EARG;
+  if (y ? (nparts != 1 || y_len < n) : y_len != 0) return GOGP_EARG;  // launch_residual takes every column
+  const int ndim = kparams->ndim;
+  if (x_len < npad * ndim + GOGP_MAX_NDIM || v_len < npad || part_len < (int64_t)nslab * npad || out_len < npad) return GOGP_EARG;
+  if (!device_ok(device)) return GOGP_EHIP;
+  const DevParams hp = to_dev(*kparams);
+  DevCopy dP, dX, dv, dy, dpart, dout;
+  hipError_t e = dP.up(&hp, sizeof hp);
+  if (e == hipSuccess) e = dX.up(X, (size_t)x_len * sizeof(double));
+  if (e == hipSuccess) e = dv.up(v, (size_t)v_len * sizeof(double));
+  if (e == hipSuccess) e = dy.up(y, (size_t)y_len * sizeof(double));
+  if (e == hipSuccess) e = dpart.up(part, (size_t)part_len * sizeof(double));
+  if (e == hipSuccess) e = dout.up(out, (size_t)out_len * sizeof(double));
+  if (e == hipSuccess) {
+    if (y)
+      launch_residual(0, dP.as<DevParams>(), ndim, dX.as<double>(), n, npad, dv.as<double>(), dy.as<double>(),
+                      dpart.as<double>(), nslab, dout.as<double>(), radial1 != 0, ev != 0);
+    else
+      launch_kmatvec_share(0, dP.as<DevParams>(), ndim, dX.as<double>(), n, npad, dv.as<double>(), part_idx, nparts,
+                           dpart.as<double>(), nslab, dout.as<double>(), radial1 != 0, ev != 0);
+    e = launched();
+  }
+  if (e == hipSuccess) e = dpart.down(part);
+  if (e == hipSuccess) e = dout.down(out);
+  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+}
+
+extern "C" int gogp_test_pgrad_slabs(int64_t npad, int64_t m, int *tiles_per_slab) {
+  if (npad <= 0 || npad % 64 || npad > TH_NPAD_MAX || m < 1 || m > SH_COUNT_MAX) return -1;
+  return pgrad_slabs(npad, m, tiles_per_slab);
+}
+
+extern "C" int gogp_test_pgrad(int device, const gogp_test_kparams *kparams, int ev, const double *X, int64_t x_len, int64_t n,
+                               int64_t npad, const double *Z, int64_t z_len, int64_t m, const double *alpha, int64_t alpha_len,
+                               const double *Wt, int64_t wt_len, int64_t ld, const double *sigma, int64_t sigma_len,
+                               double *part, int64_t part_len, double *dmu, int64_t dmu_len, double *dsigma,
+                               int64_t dsigma_len) {
+  if (!kparams || !X || !Z || !alpha || !Wt || !sigma || !part || !dmu || !dsigma) return GOGP_EARG;
+  if (!gram_args_ok(kparams, 1, 0, ev) || !pad_ok(npad) || n < 1 || n > npad || m < 1 || m > (1 << 16) || ld < npad)
+    return GOGP_EARG;
+  const int ndim = kparams->ndim;
+  const int64_t md = m * ndim, nslab = pgrad_slabs(npad, m, nullptr);
+  if (x_len < npad * ndim || z_len < md || alpha_len < npad || !covers(wt_len, 0, ld, m, npad, 1, 0) || sigma_len < m ||
+      part_len < 2 * nslab * md || dmu_len < md || dsigma_len < md)
+    return GOGP_EARG;
+  if (!device_ok(device)) return GOGP_EHIP;
+  const DevParams hp = to_dev(*kparams);
+  DevCopy dP, dX, dZ, da, dW, ds, dpart, dm, dsg;
+  hipError_t e = dP.up(&hp, sizeof hp);
+  if (e == hipSuccess) e = dX.up(X, (size_t)x_len * sizeof(double));
+  if (e == hipSuccess) e = dZ.up(Z, (size_t)z_len * sizeof(double));
+  if (e == hipSuccess) e = da.up(alpha, (size_t)alpha_len * sizeof(double));
+  if (e == hipSuccess) e = dW.up(Wt, (size_t)wt_len * sizeof(double));
+  if (e == hipSuccess) e = ds.up(sigma, (size_t)sigma_len * sizeof(double));
+  if (e == hipSuccess) e = dpart.up(part, (size_t)part_len * sizeof(double));
+  if (e == hipSuccess) e = dm.up(dmu, (size_t)dmu_len * sizeof(double));
+  if (e == hipSuccess) e = dsg.up(dsigma, (size_t)dsigma_len * sizeof(double));
+  if (e == hipSuccess) {
+    launch_pgrad(0, dP.as<DevParams>(), ndim, dX.as<double>(), n, npad, dZ.as<double>(), m, da.as<double>(), dW.as<double>(),
+                 ld, ds.as<double>(), dpart.as<double>(), dm.as<double>(), dsg.as<double>(), ev != 0);
+    e = launched();
+  }
+  if (e == hipSuccess) e = dpart.down(part);
+  if (e == hipSuccess) e = dm.down(dmu);
+  if (e == hipSuccess) e = dsg.down(dsigma);
+  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+}

@@ -2017,3 +2017,89 @@ def _table_check(table, which: str, device: int, args, caller: str):
     if rc != _lib.GOGP_OK:
         raise GogpError(rc, "test_" + which)
     return outs[0] if len(outs) == 1 else tuple(outs)
+
+
+# ---- the kernels of gram.hip and the forecast-derivative kernels of pgrad.hip (include/gogp_testhooks.h;
+# tests/test_gram_kernels.py).  Every wrapper works on flat host arrays and returns copies of the in / out arrays after the
+# launch; a refusal or a device error raises GogpError.
+def gram_split_check(kp, X: np.ndarray, n: int, npad: int, wcols: int, K: np.ndarray, ld: int, ev: bool = False,
+                     bstride: int = 0, device: int = -1):
+    """launch_gram_lower_split (test hook gogp_test_gram_split); kp: one kparams(), or a list of k of them (candidates,
+    matrix and parameters bstride elements apart).  K: float64 or float32."""
+    arr, k = _kp_array(kp)
+    X, K = _vec(X, "X"), _mat(K, "K").copy()
+    rc = _lib.hooks().gogp_test_gram_split(device, _prec(K), arr, int(ev), _dp(X), X.size, n, npad, wcols, k, bstride,
+                                           K.ctypes.data, K.size, ld)
+    if rc != _lib.GOGP_OK:
+        raise GogpError(rc, "test_gram_split")
+    return K
+
+
+def gram_local_check(kp, X: np.ndarray, n: int, npad: int, mrows: int, ncols: int, grid, K: np.ndarray, ld: int,
+                     nb_shift: int = 9, ev: bool = False, device: int = -1):
+    """launch_gram_local (test hook gogp_test_gram_local); grid = (pr, Pr, pc, Pc)."""
+    X, K = _vec(X, "X"), _mat(K, "K").copy()
+    pr, Pr, pc, Pc = grid
+    rc = _lib.hooks().gogp_test_gram_local(device, _prec(K), ctypes.byref(kp), int(ev), _dp(X), X.size, n, npad, mrows,
+                                           ncols, nb_shift, pr, Pr, pc, Pc, K.ctypes.data, K.size, ld)
+    if rc != _lib.GOGP_OK:
+        raise GogpError(rc, "test_gram_local")
+    return K
+
+
+def cross_check(kp, X: np.ndarray, n: int, npad: int, Z: np.ndarray, m: int, mpad: int, KsT: np.ndarray, ld: int,
+                ev: bool = False, device: int = -1):
+    """launch_cross (test hook gogp_test_cross); KsT: float64 or float32."""
+    X, Z, KsT = _vec(X, "X"), _vec(Z, "Z"), _mat(KsT, "KsT").copy()
+    rc = _lib.hooks().gogp_test_cross(device, _prec(KsT), ctypes.byref(kp), int(ev), _dp(X), X.size, n, npad, _dp(Z), Z.size,
+                                      m, mpad, KsT.ctypes.data, KsT.size, ld)
+    if rc != _lib.GOGP_OK:
+        raise GogpError(rc, "test_cross")
+    return KsT
+
+
+def prior_check(kp, Z: np.ndarray, m: int, prior: np.ndarray, device: int = -1):
+    """launch_prior (test hook gogp_test_prior)."""
+    Z, prior = _vec(Z, "Z"), _vec(prior, "prior").copy()
+    rc = _lib.hooks().gogp_test_prior(device, ctypes.byref(kp), _dp(Z), Z.size, m, _dp(prior), prior.size)
+    if rc != _lib.GOGP_OK:
+        raise GogpError(rc, "test_prior")
+    return prior
+
+
+def kmatvec_check(kp, X: np.ndarray, n: int, npad: int, v: np.ndarray, y, part: np.ndarray, nslab: int, out: np.ndarray,
+                  part_idx: int = 0, nparts: int = 1, radial1: bool = False, ev: bool = False, device: int = -1):
+    """launch_residual (y given: out = y - K v) or launch_kmatvec_share (y None: the share part_idx of nparts of K v)
+    (test hook gogp_test_kmatvec); returns copies of (part, out)."""
+    X, v = _vec(X, "X"), _vec(v, "v")
+    y = None if y is None else _vec(y, "y")
+    part, out = _vec(part, "part").copy(), _vec(out, "out").copy()
+    rc = _lib.hooks().gogp_test_kmatvec(device, ctypes.byref(kp), int(radial1), int(ev), _dp(X), X.size, n, npad, _dp(v),
+                                        v.size, _dp(y), 0 if y is None else y.size, part_idx, nparts, nslab, _dp(part),
+                                        part.size, _dp(out), out.size)
+    if rc != _lib.GOGP_OK:
+        raise GogpError(rc, "test_kmatvec")
+    return part, out
+
+
+def pgrad_slabs(npad: int, m: int):
+    """(slabs, 64-row tiles per slab) of launch_pgrad.  No device."""
+    tps = ctypes.c_int(0)
+    ns = _lib.hooks().gogp_test_pgrad_slabs(npad, m, ctypes.byref(tps))
+    if ns < 0:
+        raise GogpError(_lib.GOGP_EARG, "test_pgrad_slabs")
+    return int(ns), int(tps.value)
+
+
+def pgrad_check(kp, X: np.ndarray, n: int, npad: int, Z: np.ndarray, m: int, alpha: np.ndarray, Wt: np.ndarray, ld: int,
+                sigma: np.ndarray, part: np.ndarray, dmu: np.ndarray, dsigma: np.ndarray, ev: bool = False,
+                device: int = -1):
+    """launch_pgrad (test hook gogp_test_pgrad); returns copies of (part, dmu, dsigma)."""
+    X, Z, alpha, Wt, sigma = _vec(X, "X"), _vec(Z, "Z"), _vec(alpha, "alpha"), _vec(Wt, "Wt"), _vec(sigma, "sigma")
+    part, dmu, dsigma = _vec(part, "part").copy(), _vec(dmu, "dmu").copy(), _vec(dsigma, "dsigma").copy()
+    rc = _lib.hooks().gogp_test_pgrad(device, ctypes.byref(kp), int(ev), _dp(X), X.size, n, npad, _dp(Z), Z.size, m,
+                                      _dp(alpha), alpha.size, _dp(Wt), Wt.size, ld, _dp(sigma), sigma.size, _dp(part),
+                                      part.size, _dp(dmu), dmu.size, _dp(dsigma), dsigma.size)
+    if rc != _lib.GOGP_OK:
+        raise GogpError(rc, "test_pgrad")
+    return part, dmu, dsigma

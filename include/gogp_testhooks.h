@@ -598,6 +598,52 @@ int gogp_test_sumsq_info(int device, const double *z, int64_t z_len, int64_t n, 
 int gogp_test_vector_op(int device, int op, int precision, void *a, int64_t a_len, const void *b, int64_t b_len, int64_t
     count, double f);
 
+/* ---- the kernels of gram.hip and the forecast-derivative kernels of pgrad.hip through their product launchers
+ * (tests/test_gram_kernels.py).  The rules of the hooks above.  Refused with GOGP_EARG besides short arrays: npad, mpad,
+ * mrows, ncols that are not positive multiples of 64 (whole 64 x 64 tiles are written: the output holds all of their
+ * rows, ld covers the padded width); X shorter than npad * ndim + GOGP_MAX_NDIM doubles (with one radial term the kernels
+ * read rows n .. npad - 1 of X unguarded; the slack is gogp_test_grad_reduce's convention); wcols that is not a multiple of
+ * 64 or below 64; radial1 without exactly one radial (non-periodic) term -- radial1 = 0 on such a kernel is legal and
+ * selects the generic instance; ev with an ARD term.  Z, v, alpha and Wt are read on their first m / n rows only. */
+
+/* launch_gram_lower_split (both launches on stream 0): K (in / out; npad rows of ld; float with precision 32) = the lower
+ * 64-tiles of the Gram matrix, identity on the padding.  k candidates (fp64 only beyond 1): kparams holds k structs, X is
+ * shared, candidate c's matrix AND parameters lie c * bstride elements (of 8 bytes) on. */
+int gogp_test_gram_split(int device, int precision, const gogp_test_kparams *kparams, int ev, const double *X, int64_t x_len,
+                         int64_t n, int64_t npad, int64_t wcols, int k, int64_t bstride, void *K, int64_t k_len, int64_t ld);
+
+/* launch_gram_local: the mrows x ncols local tiles (K: in / out, ld >= ncols) of rank (pr, pc) of a Pr x Pc grid with
+ * distribution blocks of 2^nb_shift; the last local row and column must be global ones below npad. */
+int gogp_test_gram_local(int device, int precision, const gogp_test_kparams *kparams, int ev, const double *X, int64_t x_len,
+                         int64_t n, int64_t npad, int64_t mrows, int64_t ncols, int nb_shift, int pr, int Pr, int pc, int Pc,
+                         void *K, int64_t k_len, int64_t ld);
+
+/* launch_cross: KsT (in / out; mpad rows of ld >= npad) [j][i] = k(x_i, z_j), zero for i >= n or j >= m.  Z: mpad rows. */
+int gogp_test_cross(int device, int precision, const gogp_test_kparams *kparams, int ev, const double *X, int64_t x_len,
+                    int64_t n, int64_t npad, const double *Z, int64_t z_len, int64_t m, int64_t mpad, void *KsT, int64_t k_len,
+                    int64_t ld);
+
+/* launch_prior: prior (in / out) [j] = k(z_j, z_j), j < m. */
+int gogp_test_prior(int device, const gogp_test_kparams *kparams, const double *Z, int64_t z_len, int64_t m, double *prior,
+                    int64_t prior_len);
+
+/* y given: launch_residual, out = y - K v (nparts must be 1); y NULL (length 0): launch_kmatvec_share(part_idx, nparts),
+ * out = the share's columns of K v.  Rows >= n of out are zero.  part (in / out): nslab x npad; out (in / out): npad. */
+int gogp_test_kmatvec(int device, const gogp_test_kparams *kparams, int radial1, int ev, const double *X, int64_t x_len,
+                      int64_t n, int64_t npad, const double *v, int64_t v_len, const double *y, int64_t y_len, int part_idx,
+                      int nparts, int nslab, double *part, int64_t part_len, double *out, int64_t out_len);
+
+/* pgrad_slabs itself: the slabs launch_pgrad splits npad rows into for m test points, and the 64-row tiles per slab.
+ * -1: bad arguments.  No device. */
+int gogp_test_pgrad_slabs(int64_t npad, int64_t m, int *tiles_per_slab);
+
+/* launch_pgrad: dmu, dsigma (in / out; m x ndim) and part (in / out; 2 x gogp_test_pgrad_slabs x m x ndim).  Wt: m rows of
+ * ld >= npad; alpha: npad; sigma: m. */
+int gogp_test_pgrad(int device, const gogp_test_kparams *kparams, int ev, const double *X, int64_t x_len, int64_t n,
+                    int64_t npad, const double *Z, int64_t z_len, int64_t m, const double *alpha, int64_t alpha_len,
+                    const double *Wt, int64_t wt_len, int64_t ld, const double *sigma, int64_t sigma_len, double *part,
+                    int64_t part_len, double *dmu, int64_t dmu_len, double *dsigma, int64_t dsigma_len);
+
 #ifdef __cplusplus
 }
 #endif

@@ -206,6 +206,20 @@ def test_three_dimensions_axis_one(n):
     g.close()
 
 
+def test_sixty_four_dimensions_axis_three():
+    """GOGP_MAX_NDIM dimensions with events, beyond the one-launch path (N = 130): the Gram and cross launches ask for
+    1024 D + 1024 = 66560 bytes of dynamic LDS there, more than 64 KB."""
+    n, D = 130, 64
+    rng = np.random.default_rng(13)
+    X = rng.uniform(-1.5, 1.5, (n, D))
+    y = np.sin(X[:, 3]) + 0.1 * X.sum(1)
+    ev = [(-0.5, 0.2, 0.4), (0.6, 1.0, 0.3)]
+    g, r = _gp(D, ev, X, y, axis=3), _ref(D, ev, X, y, axis=3)
+    Z = rng.uniform(-1.5, 1.5, (20, D))
+    _check(g, r, np.log([1.1, 8.0, 0.5]), [Z])
+    g.close()
+
+
 def _fp32_case():
     X, y = _synth(2500, seed=21)
     return X, y, np.log([1.0, 0.3, 3.0]), np.random.default_rng(3).uniform(-2, 2, (32, 1))
