@@ -3,7 +3,6 @@
 // internal launchers; none of this is part of the product ABI (include/gogp_hip.h).
 #include <cstdlib>
 #include <cstring>
-#include <initializer_list>
 #include <stdio.h>
 #include <vector>
 
@@ -181,54 +180,11 @@ int mfma_f64_peak(int iters, double *tflops, double *cyc_per_mfma, double *clock
 
 using namespace gogp;
 
-extern "C" int gogp_mfma_f64_peak(int device, int iters, double *tflops, double *cyc_per_mfma,
-                                  double *clock_mhz) {
-  if (!tflops || iters <= 0) return GOGP_EARG;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return GOGP_EHIP;
-  if (device >= 0 && hipSetDevice(device) != hipSuccess) return GOGP_EHIP;
-  return mfma_f64_peak(iters, tflops, cyc_per_mfma, clock_mhz);
-}
-
-extern "C" int gogp_mfma_f32_peak(int device, int iters, double *tflops, double *cyc_per_mfma,
-                                  double *clock_mhz) {
-  if (!tflops || iters <= 0) return GOGP_EARG;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return GOGP_EHIP;
-  if (device >= 0 && hipSetDevice(device) != hipSuccess) return GOGP_EHIP;
-  return mfma_f32_peak(iters, tflops, cyc_per_mfma, clock_mhz);
-}
-
-extern "C" int gogp_test_dgemm_nt(int device, int64_t M, int64_t N, int64_t K, double alpha,
-                                  const double *A, const double *B, double beta, double *C) {
-  if (!A || !B || !C || M <= 0 || N <= 0 || K <= 0) return GOGP_EARG;
-  if (M % TILE || N % TILE || K % GEMM_BK) return GOGP_EARG;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return GOGP_EHIP;
-  if (device >= 0 && hipSetDevice(device) != hipSuccess) return GOGP_EHIP;
-  double *dA = nullptr, *dB = nullptr, *dC = nullptr;
-  hipError_t e = hipMalloc(&dA, (size_t)M * K * sizeof(double));
-  if (e == hipSuccess) e = hipMalloc(&dB, (size_t)N * K * sizeof(double));
-  if (e == hipSuccess) e = hipMalloc(&dC, (size_t)M * N * sizeof(double));
-  if (e == hipSuccess) e = hipMemcpy(dA, A, (size_t)M * K * sizeof(double), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(dB, B, (size_t)N * K * sizeof(double), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(dC, C, (size_t)M * N * sizeof(double), hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    launch_dgemm_nt(0, GEMM_RECT, (int)(M / TILE), (int)(N / TILE), K, alpha, dA, K, dB, K, beta,
-                    dC, N, nullptr);
-    e = hipDeviceSynchronize();
-  }
-  if (e == hipSuccess) e = hipMemcpy(C, dC, (size_t)M * N * sizeof(double), hipMemcpyDeviceToHost);
-  (void)hipFree(dA);
-  (void)hipFree(dB);
-  (void)hipFree(dC);
-  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
-}
-
-// ---- the product launchers of the tile kernel, the fp64 diagonal-block update and the diagonal-block kernel on host
-// buffers (tests/test_tile_kernels.py).  Every argument is checked BEFORE the device is touched: a test mistake comes back
-// as GOGP_EARG, never as an access outside the buffers.  Each array is copied to the device whole and (outputs) back whole,
-// so a test sees the elements a launch must leave alone as well as those it writes.
+// ---- shared helpers of the hooks below ----------------------------------------------------------------------------------
+// A gogp_test_* hook drives product launchers on host buffers, and every one has the same form.  It checks every argument
+// BEFORE the device is touched: a test mistake comes back as GOGP_EARG, never as an access outside the buffers.  Then it
+// hands run() one line per array and a callable that launches: each array is copied to the device whole and (in / out
+// arrays) back whole, so a test sees the elements a launch must leave alone as well as those it writes.
 namespace {
 // off + (k - 1) * stride + (rows - 1) * ld + cols <= len, all in elements
 bool covers(int64_t len, int64_t off, int64_t ld, int64_t rows, int64_t cols, int64_t k, int64_t stride) {
@@ -241,6 +197,213 @@ bool device_ok(int device) {
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return false;
   return device < 0 || hipSetDevice(device) == hipSuccess;
 }
+bool prec_ok(int precision) { return precision == 64 || precision == 32; }
+hipError_t launched() {
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? hipDeviceSynchronize() : e;
+}
+// the largest sizes the hooks take: of the substitution and layout kernels, of the gradient and Gram kernels, of the
+// kernels that update or finish a factor, and of the element counts of the vector kernels
+constexpr int64_t TH_NPAD_MAX = 1 << 17;
+constexpr int64_t GR_NPAD_MAX = 1 << 15;
+constexpr int64_t UP_NPAD_MAX = 1 << 15;
+constexpr int64_t SH_COUNT_MAX = 1 << 26;
+
+static_assert(GOGP_TEST_NACC == NACC, "GOGP_TEST_NACC mirrors NACC");
+// the launchers' selection arguments and the parameters they go with
+bool kparams_ok(const gogp_test_kparams *kp, int k, int ard_dims, int radial1, int mfma_min, int ev) {
+  if (!kp || k < 1) return false;
+  for (int c = 0; c < k; ++c) {
+    const gogp_test_kparams &q = kp[c];
+    if (q.ndim < 1 || q.ndim > GOGP_MAX_NDIM || q.nterms < 1 || q.nterms > GOGP_MAX_TERMS) return false;
+    if (q.ndim != kp[0].ndim || q.nterms != kp[0].nterms) return false;  // one launch sequence: one kernel shape
+    int nard = 0;
+    for (int t = 0; t < q.nterms; ++t) {
+      if (q.kind[t] < GOGP_K_NORMAL || q.kind[t] > GOGP_K_PERIODIC || q.kind[t] != kp[0].kind[t]) return false;
+      nard += q.ard[t] != 0;
+      for (int d = q.ndim; d < GOGP_MAX_NDIM; ++d)
+        if (q.inv_len[t][d] != 0.0) return false;  // the ARD pass relies on it (common.h: launch_grad_reduce)
+    }
+    if (nard > 1 || ard_dims != (nard ? q.ndim : 0)) return false;  // one ARD term at most; ard_dims is 0 or ndim
+    if (radial1 && (q.nterms != 1 || q.kind[0] == GOGP_K_PERIODIC)) return false;
+    if (q.nevents < 0 || q.nevents > GOGP_MAX_EVENTS || q.ev_axis < 0 || q.ev_axis >= q.ndim) return false;
+  }
+  if (ev && ard_dims > 0) return false;  // no instance has both (gogp_set_events refuses ARD)
+  return mfma_min >= 1;
+}
+DevParams to_dev(const gogp_test_kparams &q) {
+  DevParams p;
+  memset(&p, 0, sizeof p);
+  p.ndim = q.ndim;
+  p.nterms = q.nterms;
+  for (int t = 0; t < GOGP_MAX_TERMS; ++t) {
+    p.kind[t] = q.kind[t];
+    p.ard[t] = q.ard[t];
+    p.c[t] = q.c[t];
+    p.w[t] = q.w[t];
+    for (int d = 0; d < GOGP_MAX_NDIM; ++d) p.inv_len[t][d] = q.inv_len[t][d];
+  }
+  p.noise_var = q.noise_var;
+  p.dnoise = q.dnoise;
+  p.nevents = q.nevents;
+  p.ev_axis = q.ev_axis;
+  for (int e = 0; e < GOGP_MAX_EVENTS; ++e) {
+    p.ev_from[e] = q.ev_from[e];
+    p.ev_to[e] = q.ev_to[e];
+    p.ev_disc[e] = q.ev_disc[e];
+  }
+  return p;
+}
+// the one-term-at-most ARD count kparams_ok wants stated
+int ard_dims_of(const gogp_test_kparams *kp) {
+  if (!kp || kp->nterms < 1 || kp->nterms > GOGP_MAX_TERMS) return 0;
+  int nard = 0;
+  for (int t = 0; t < kp->nterms; ++t) nard += kp->ard[t] != 0;
+  return nard == 1 ? kp->ndim : 0;
+}
+
+// candidate batch of a launcher that reads tl_batch: k == 1 (stride ignored) or 2 .. 16 candidates `bstride` elements apart
+bool batch_ok(int precision, int k, int64_t *bstride) {
+  if (k < 1 || k > GOGP_MAX_CANDIDATES) return false;
+  if (k == 1) {
+    *bstride = 0;
+    return true;
+  }
+  return precision == 64 && *bstride > 0 && *bstride % 2 == 0;  // the float launchers do not batch
+}
+// called inside a run() callable, which puts tl_batch back to its resting {1, 0}; bstride in elements of es bytes
+void set_batch(int k, int64_t bstride, int64_t es = 8) {
+  tl_batch.k = k;
+  tl_batch.stride = (long)(bstride * es);
+}
+// k parameter blocks / k rows of NACC packed for the device: candidate c at c * stride bytes (stride 0 with k == 1)
+std::vector<char> pack_strided(const void *h, size_t item, int k, size_t stride) {
+  std::vector<char> buf((size_t)(k - 1) * stride + item, 0);
+  for (int c = 0; c < k; ++c) memcpy(buf.data() + (size_t)c * stride, (const char *)h + (size_t)c * item, item);
+  return buf;
+}
+void unpack_strided(const std::vector<char> &buf, void *h, size_t item, int k, size_t stride) {
+  for (int c = 0; c < k; ++c) memcpy((char *)h + (size_t)c * item, buf.data() + (size_t)c * stride, item);
+}
+
+// a device buffer, freed on every path.  up() allocates max(n, room) bytes, presets them to the byte `fill` (>= 0) and
+// uploads the n bytes at h (h == nullptr: none); nothing to hold: nothing is allocated.  down() copies the n bytes back.
+struct DevCopy {
+  char *d = nullptr;
+  size_t bytes = 0;
+  hipError_t up(const void *h, size_t n, size_t room = 0, int fill = -1) {
+    if (!h) n = 0;
+    const size_t cap = n > room ? n : room;
+    if (!cap) return hipSuccess;
+    bytes = n;
+    hipError_t e = hipMalloc(&d, cap);
+    if (e == hipSuccess && fill >= 0) e = hipMemset(d, fill, cap);
+    if (e == hipSuccess && n) e = hipMemcpy(d, h, n, hipMemcpyHostToDevice);
+    return e;
+  }
+  hipError_t down(void *h) const { return d && bytes ? hipMemcpy(h, d, bytes, hipMemcpyDeviceToHost) : hipSuccess; }
+  template <class T>
+  T *as() const {
+    return reinterpret_cast<T *>(d);
+  }
+  ~DevCopy() { (void)hipFree(d); }
+};
+// one array of a hook's table: len elements of es bytes at h
+struct Arr {
+  const void *h;
+  int64_t len;
+  int es;
+  bool out;     // comes back after the launch
+  bool opt;     // may be NULL, with length 0
+  size_t room;  // bytes of the device copy where it is larger than the host array; all of a scratch array
+  int fill;     // >= 0: the byte the device copy starts from
+};
+Arr rd(const void *h, int64_t len, int es = 8) { return {h, len, es, false, false, 0, -1}; }  // read by the launch
+Arr io(void *h, int64_t len, int es = 8) { return {h, len, es, true, false, 0, -1}; }          // in / out
+Arr opt(Arr a, bool may_be_null = true) {
+  a.opt = may_be_null;
+  return a;
+}
+Arr padded(Arr a, size_t bytes, int fill) {  // `bytes` on the device, of the byte `fill` behind the host array's
+  a.room = bytes;
+  a.fill = fill;
+  return a;
+}
+Arr scratch(size_t bytes, int fill = -1) { return padded(opt(rd(nullptr, 0, 1)), bytes, fill); }  // device-only
+bool have(const std::vector<Arr> &arrs) {
+  for (const Arr &a : arrs) {
+    if (a.opt && !a.h) {
+      if (a.len != 0) return false;
+      continue;
+    }
+    if (!a.h || a.len <= 0) return false;
+  }
+  return true;
+}
+// the device copies a launch works on, in the order of the table: d[i] as double *, d.f32(i), d.as<T>(i); nullptr for an
+// array that is not there
+struct Dev {
+  std::vector<DevCopy> c;
+  template <class T>
+  T *as(size_t i) const {
+    return c[i].as<T>();
+  }
+  double *operator[](size_t i) const { return as<double>(i); }
+  float *f32(size_t i) const { return as<float>(i); }
+};
+// uploads the arrays in the order given, runs `launch` on their device copies, puts tl_batch back, synchronises and, if
+// all of that succeeded, brings the in / out arrays back
+template <class F>
+int run(int device, const std::vector<Arr> &arrs, F &&launch) {
+  if (!device_ok(device)) return GOGP_EHIP;
+  Dev d;
+  d.c = std::vector<DevCopy>(arrs.size());
+  hipError_t e = hipSuccess;
+  size_t i = 0;
+  for (const Arr &a : arrs) {
+    if (e == hipSuccess) e = d.c[i].up(a.h, a.h && a.len > 0 ? (size_t)a.len * (size_t)a.es : 0, a.room, a.fill);
+    ++i;
+  }
+  if (e == hipSuccess) {
+    launch(d);
+    set_batch(1, 0);
+    e = launched();
+  }
+  i = 0;
+  for (const Arr &a : arrs) {
+    if (e == hipSuccess && a.out) e = d.c[i].down(const_cast<void *>(a.h));
+    ++i;
+  }
+  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+}
+}  // namespace
+
+extern "C" int gogp_mfma_f64_peak(int device, int iters, double *tflops, double *cyc_per_mfma,
+                                  double *clock_mhz) {
+  if (!tflops || iters <= 0) return GOGP_EARG;
+  if (!device_ok(device)) return GOGP_EHIP;
+  return mfma_f64_peak(iters, tflops, cyc_per_mfma, clock_mhz);
+}
+
+extern "C" int gogp_mfma_f32_peak(int device, int iters, double *tflops, double *cyc_per_mfma,
+                                  double *clock_mhz) {
+  if (!tflops || iters <= 0) return GOGP_EARG;
+  if (!device_ok(device)) return GOGP_EHIP;
+  return mfma_f32_peak(iters, tflops, cyc_per_mfma, clock_mhz);
+}
+
+extern "C" int gogp_test_dgemm_nt(int device, int64_t M, int64_t N, int64_t K, double alpha,
+                                  const double *A, const double *B, double beta, double *C) {
+  if (!A || !B || !C || M <= 0 || N <= 0 || K <= 0) return GOGP_EARG;
+  if (M % TILE || N % TILE || K % GEMM_BK) return GOGP_EARG;
+  return run(device, {rd(A, M * K), rd(B, N * K), io(C, M * N)}, [&](const Dev &d) {
+    launch_dgemm_nt(0, GEMM_RECT, (int)(M / TILE), (int)(N / TILE), K, alpha, d[0], K, d[1], K, beta, d[2], N, nullptr);
+  });
+}
+
+// ---- the product launchers of the tile kernel, the fp64 diagonal-block update and the diagonal-block kernel on host
+// buffers (tests/test_tile_kernels.py)
+namespace {
 // the launcher's arguments proper (no buffers): false for what the kernels cannot honour
 bool gemm_launch_args_ok(int precision, int mode, int mt, int nt, int64_t K, const gogp_test_gemm_opts &o) {
   if (precision != 64 && precision != 32) return false;
@@ -312,35 +475,16 @@ extern "C" int gogp_test_gemm_nt(int device, int precision, int mode, int mt, in
   if (!covers(a_len, a_off, lda, M, K, o.k, o.bstride) || !covers(b_len, b_off, ldb, N, K, o.k, o.bstride) ||
       !covers(c_len, c_off, ldc, M, N, o.k, o.bstride))
     return GOGP_EARG;
-  if (!device_ok(device)) return GOGP_EHIP;
-
-  char *dA = nullptr, *dB = nullptr, *dC = nullptr;
-  hipError_t e = hipMalloc(&dA, (size_t)(a_len * es));
-  if (e == hipSuccess) e = hipMalloc(&dB, (size_t)(b_len * es));
-  if (e == hipSuccess) e = hipMalloc(&dC, (size_t)(c_len * es));
-  if (e == hipSuccess) e = hipMemcpy(dA, A, (size_t)(a_len * es), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(dB, B, (size_t)(b_len * es), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(dC, C, (size_t)(c_len * es), hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
+  return run(device, {rd(A, a_len, (int)es), rd(B, b_len, (int)es), io(C, c_len, (int)es)}, [&](const Dev &d) {
     const GemmGrid g = gemm_grid_of(o);
-    tl_batch.k = o.k;
-    tl_batch.stride = (long)(o.bstride * es);
+    set_batch(o.k, o.bstride, es);
     if (precision == 64)
-      launch_gemm_nt(0, (GemmMode)mode, mt, nt, K, alpha, (const double *)dA + a_off, lda, (const double *)dB + b_off, ldb,
-                     beta, (double *)dC + c_off, ldc, nullptr, &g);
+      launch_gemm_nt(0, (GemmMode)mode, mt, nt, K, alpha, (const double *)d[0] + a_off, lda, (const double *)d[1] + b_off,
+                     ldb, beta, d[2] + c_off, ldc, nullptr, &g);
     else
-      launch_gemm_nt(0, (GemmMode)mode, mt, nt, K, alpha, (const float *)dA + a_off, lda, (const float *)dB + b_off, ldb,
-                     beta, (float *)dC + c_off, ldc, nullptr, &g);
-    tl_batch.k = 1;
-    tl_batch.stride = 0;
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-  }
-  if (e == hipSuccess) e = hipMemcpy(C, dC, (size_t)(c_len * es), hipMemcpyDeviceToHost);
-  (void)hipFree(dA);
-  (void)hipFree(dB);
-  (void)hipFree(dC);
-  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+      launch_gemm_nt(0, (GemmMode)mode, mt, nt, K, alpha, (const float *)d.f32(0) + a_off, lda,
+                     (const float *)d.f32(1) + b_off, ldb, beta, d.f32(2) + c_off, ldc, nullptr, &g);
+  });
 }
 
 extern "C" int gogp_test_diag_syrk(int device, int bs, const float *L, int64_t l_len, int64_t l_off, int64_t ld,
@@ -349,25 +493,12 @@ extern "C" int gogp_test_diag_syrk(int device, int bs, const float *L, int64_t l
   if (K < 16 || K % 16 || ld % 4 || l_off % 4 || row_stride % 4) return GOGP_EARG;  // float4 loads, k-chunks of 16
   if (bs == PANEL && row_stride != PANEL * ld) return GOGP_EARG;  // launch_diag_syrk_f64: blocks 256 rows apart
   if (!covers(l_len, l_off, ld, bs, K, nblocks, row_stride) || d_len < (int64_t)nblocks * bs * bs) return GOGP_EARG;
-  if (!device_ok(device)) return GOGP_EHIP;
-  float *dL = nullptr;
-  double *dD = nullptr;
-  hipError_t e = hipMalloc(&dL, (size_t)l_len * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc(&dD, (size_t)d_len * sizeof(double));
-  if (e == hipSuccess) e = hipMemcpy(dL, L, (size_t)l_len * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(dD, D64, (size_t)d_len * sizeof(double), hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
+  return run(device, {rd(L, l_len, 4), io(D64, d_len)}, [&](const Dev &d) {
     if (bs == PANEL)
-      launch_diag_syrk_f64(0, dL + l_off, ld, K, dD, nblocks);
+      launch_diag_syrk_f64(0, d.f32(0) + l_off, ld, K, d[1], nblocks);
     else
-      launch_diag_syrk_f64_tiles(0, dL + l_off, ld, K, dD, nblocks, row_stride, bs);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-  }
-  if (e == hipSuccess) e = hipMemcpy(D64, dD, (size_t)d_len * sizeof(double), hipMemcpyDeviceToHost);
-  (void)hipFree(dL);
-  (void)hipFree(dD);
-  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+      launch_diag_syrk_f64_tiles(0, d.f32(0) + l_off, ld, K, d[1], nblocks, row_stride, bs);
+  });
 }
 
 extern "C" int gogp_test_diag256_product(int device, int variant, const double *A, int64_t ld, double *L, int64_t ldl,
@@ -375,33 +506,15 @@ extern "C" int gogp_test_diag256_product(int device, int variant, const double *
   if (!A || !L || !Dinv || !info || variant < 0 || variant > 3) return GOGP_EARG;
   if (ld < PANEL || ldl < PANEL || ld % 2 || ldl % 2 || row0 < 0 || nvalid < 0) return GOGP_EARG;  // 16-B loads
   const int64_t ldd = (variant & 1) ? 2 * PANEL : PANEL;  // variants 1, 3: Dinv a block of a leading dimension 512
-  if (!device_ok(device)) return GOGP_EHIP;
-  double *dA = nullptr, *dL = nullptr, *dD = nullptr;
-  long long *dinfo = nullptr;
-  const size_t na = (size_t)PANEL * ld * 8, nl = (size_t)PANEL * ldl * 8, nd = (size_t)PANEL * ldd * 8;
-  hipError_t e = hipMalloc(&dA, na);
-  if (e == hipSuccess) e = hipMalloc(&dL, nl);
-  if (e == hipSuccess) e = hipMalloc(&dD, nd);
-  if (e == hipSuccess) e = hipMalloc(&dinfo, 8);
-  if (e == hipSuccess) e = hipMemcpy(dA, A, na, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(dL, L, nl, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(dD, Dinv, nd, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(dinfo, info, 8, hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
+  return run(device, {rd(A, PANEL * ld), io(L, PANEL * ldl), io(Dinv, PANEL * ldd), io(info, 1)}, [&](const Dev &d) {
+    long long *dinfo = d.as<long long>(3);
     switch (variant) {
-      case 0: launch_diag256(0, dA, ld, dL, ldl, dD, row0, nvalid, dinfo); break;
-      case 1: launch_diag256_ld512(0, dA, ld, dL, ldl, dD, row0, nvalid, dinfo); break;
-      case 2: launch_diag256_inv_only(0, dA, ld, dD); break;
-      default: launch_diag256_inv_only_ld512(0, dA, ld, dD); break;
+      case 0: launch_diag256(0, d[0], ld, d[1], ldl, d[2], row0, nvalid, dinfo); break;
+      case 1: launch_diag256_ld512(0, d[0], ld, d[1], ldl, d[2], row0, nvalid, dinfo); break;
+      case 2: launch_diag256_inv_only(0, d[0], ld, d[2]); break;
+      default: launch_diag256_inv_only_ld512(0, d[0], ld, d[2]); break;
     }
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-  }
-  if (e == hipSuccess) e = hipMemcpy(L, dL, nl, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(Dinv, dD, nd, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(info, dinfo, 8, hipMemcpyDeviceToHost);
-  (void)hipFree(dA); (void)hipFree(dL); (void)hipFree(dD); (void)hipFree(dinfo);
-  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+  });
 }
 
 // Diagnostic: factor+invert one 256x256 SPD block (host buffers) with the stamped
@@ -409,9 +522,7 @@ extern "C" int gogp_test_diag256_product(int device, int variant, const double *
 extern "C" int gogp_test_diag256(int device, const double *A, double *Lout, double *Dinv,
                                  unsigned long long *stamps, double *elapsed_us) {
   if (!A || !Lout || !Dinv || !stamps) return GOGP_EARG;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return GOGP_EHIP;
-  if (device >= 0 && hipSetDevice(device) != hipSuccess) return GOGP_EHIP;
+  if (!device_ok(device)) return GOGP_EHIP;
   double *dA = nullptr, *dL = nullptr, *dD = nullptr;
   long long *dinfo = nullptr;
   unsigned long long *dst = nullptr;
@@ -498,9 +609,7 @@ __global__ __launch_bounds__(64) void valu_cost_kernel(double *out, double seed)
 }
 extern "C" int gogp_test_valu_cost(int device, double *out8) {
   if (!out8) return GOGP_EARG;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return GOGP_EHIP;
-  if (device >= 0 && hipSetDevice(device) != hipSuccess) return GOGP_EHIP;
+  if (!device_ok(device)) return GOGP_EHIP;
   double *d = nullptr;
   if (hipMalloc(&d, (8 + 64) * sizeof(double)) != hipSuccess) return GOGP_ENOMEM;
   for (int rep = 0; rep < 3; ++rep) hipLaunchKernelGGL(valu_cost_kernel, dim3(1), dim3(64), 0, 0, d, 1.5);
@@ -516,9 +625,7 @@ extern "C" int gogp_test_valu_cost(int device, double *out8) {
 extern "C" int gogp_test_panel128(int device, const double *A, double *Lout, int64_t rows_below, int reps,
                                   unsigned long long *stamps, double *elapsed_us) {
   if (!A || !Lout || !stamps || rows_below < 0 || rows_below % 64 || reps <= 0) return GOGP_EARG;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return GOGP_EHIP;
-  if (device >= 0 && hipSetDevice(device) != hipSuccess) return GOGP_EHIP;
+  if (!device_ok(device)) return GOGP_EHIP;
   double *dA = nullptr, *dL = nullptr;
   long long *dinfo = nullptr;
   unsigned long long *dst = nullptr;
@@ -565,9 +672,7 @@ extern "C" int gogp_test_panel128(int device, const double *A, double *Lout, int
 extern "C" int gogp_test_panel128_slabs(int device, const double *A, double *Lout, int64_t rows_below, int slabs, int reps,
                                         double *elapsed_us) {
   if (!A || !Lout || rows_below < 0 || rows_below % 64 || slabs < 0 || slabs > 8 || reps <= 0) return GOGP_EARG;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return GOGP_EHIP;
-  if (device >= 0 && hipSetDevice(device) != hipSuccess) return GOGP_EHIP;
+  if (!device_ok(device)) return GOGP_EHIP;
   const size_t rows = 128 + (size_t)rows_below, nb2 = rows * 256 * sizeof(double);
   double *dA = nullptr, *dL = nullptr;
   long long *dinfo = nullptr;
@@ -604,9 +709,7 @@ extern "C" int gogp_bench_gemm(int device, int mode, int mt, int nt, int64_t K, 
                                double *ms_per_launch, double *tflops) {
   if (mt <= 0 || nt <= 0 || K <= 0 || K % GEMM_BK || reps <= 0 || mode < 0 || mode > 2)
     return GOGP_EARG;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return GOGP_EHIP;
-  if (device >= 0 && hipSetDevice(device) != hipSuccess) return GOGP_EHIP;
+  if (!device_ok(device)) return GOGP_EHIP;
   const int64_t M = (int64_t)mt * TILE, N = (int64_t)nt * TILE;
   const int64_t Kld = (mode == GEMM_LAUUM) ? M : K;  // LAUUM: K range = matrix size
   double *dA = nullptr, *dB = nullptr, *dC = nullptr;
@@ -683,35 +786,7 @@ extern "C" int gogp_bench_gemm(int device, int mode, int mt, int nt, int64_t K, 
 
 // ---- the kernels that consume the factor, through their product launchers on host buffers
 // (tests/test_substitution_kernels.py): the one-pass substitution of trsm_small.hip, and of solve.hip the substitution
-// steps, alpha_from_y, rownorm_dot, tinv_init and the batched 256-block product.  Same rules as gogp_test_gemm_nt: every
-// argument is checked before the device is touched, every array goes to the device whole and every output comes back whole.
-namespace {
-// a host array's copy on the device: up() allocates and uploads (n == 0 or h == nullptr: nothing), down() copies back
-struct DevCopy {
-  char *d = nullptr;
-  size_t bytes = 0;
-  hipError_t up(const void *h, size_t n) {
-    if (!h || !n) return hipSuccess;
-    bytes = n;
-    hipError_t e = hipMalloc(&d, n);
-    if (e == hipSuccess) e = hipMemcpy(d, h, n, hipMemcpyHostToDevice);
-    return e;
-  }
-  hipError_t down(void *h) const { return d ? hipMemcpy(h, d, bytes, hipMemcpyDeviceToHost) : hipSuccess; }
-  template <class T>
-  T *as() const {
-    return reinterpret_cast<T *>(d);
-  }
-  ~DevCopy() { (void)hipFree(d); }
-};
-hipError_t launched() {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? hipDeviceSynchronize() : e;
-}
-bool prec_ok(int precision) { return precision == 64 || precision == 32; }
-constexpr int64_t TH_NPAD_MAX = 1 << 17;
-}  // namespace
-
+// steps, alpha_from_y, rownorm_dot, tinv_init and the batched 256-block product.
 extern "C" int64_t gogp_test_trsm_small_workspace(int64_t npad) {
   if (npad <= 0 || npad % PANEL || npad > TH_NPAD_MAX) return -1;
   return (int64_t)trsm_small_workspace_bytes(npad);
@@ -729,33 +804,27 @@ extern "C" int gogp_test_trsm_small(int device, int precision, int64_t npad, con
     return GOGP_EARG;
   const size_t wsb = trsm_small_workspace_bytes(npad);
   if (sol_len < 0 || (size_t)sol_len != wsb) return GOGP_EARG;
-  if (!device_ok(device)) return GOGP_EHIP;
-  const size_t es = precision / 8;
-  DevCopy dL, dD, dK, dQ, dW;
-  hipError_t e = dL.up(L, (size_t)l_len * es);
-  if (e == hipSuccess) e = dD.up(Dinv, (size_t)npad * PANEL * es);
-  if (e == hipSuccess) e = dK.up(KsT, (size_t)k_len * es);
-  if (e == hipSuccess) e = dQ.up(dq, (size_t)dq_len * sizeof(double));
-  if (e == hipSuccess) e = dW.up(sol, wsb);
-  unsigned *dtmo = nullptr;
-  if (e == hipSuccess) {
+  const int es = precision / 8;
+  int64_t tmo_off = -1;  // the time-out word lies in the work area, which comes back whole as `sol`
+  const std::vector<Arr> arrs = {rd(L, l_len, es), rd(Dinv, npad * PANEL, es), rd(KsT, k_len, es), io(dq, dq_len),
+                                 io(sol, sol_len, 1)};
+  const int rc = run(device, arrs, [&](const Dev &d) {
+    char *ws = d.as<char>(4);
+    unsigned *dtmo = nullptr;
     if (precision == 64)
-      launch_trsm_small(0, dL.as<double>(), ld, dD.as<double>(), dK.as<double>(), ldk, npad, j0, cnt, dW.d, dQ.as<double>(),
-                        &dtmo);
+      launch_trsm_small(0, d[0], ld, d[1], d[2], ldk, npad, j0, cnt, ws, d[3], &dtmo);
     else
-      launch_trsm_small(0, dL.as<float>(), ld, dD.as<float>(), dK.as<float>(), ldk, npad, j0, cnt, dW.d, dQ.as<double>(),
-                        &dtmo);
-    e = launched();
-  }
-  if (e == hipSuccess && !dtmo) e = hipErrorUnknown;
-  if (e == hipSuccess) e = hipMemcpy(tmo, dtmo, sizeof(unsigned), hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = dQ.down(dq);
-  if (e == hipSuccess) e = dW.down(sol);
-  const TsSolution r = trsm_small_solution(npad, j0, cnt, dW.d, precision == 32);
-  *kind = r.kind;
-  *width = r.width;
-  *sol_off = dW.d ? (int64_t)((const char *)r.p - dW.d) : -1;
-  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+      launch_trsm_small(0, d.f32(0), ld, d.f32(1), d.f32(2), ldk, npad, j0, cnt, ws, d[3], &dtmo);
+    if (dtmo) tmo_off = (const char *)dtmo - ws;
+    const TsSolution r = trsm_small_solution(npad, j0, cnt, ws, precision == 32);
+    *kind = r.kind;
+    *width = r.width;
+    *sol_off = (int64_t)((const char *)r.p - ws);
+  });
+  if (rc != GOGP_OK) return rc;
+  if (tmo_off < 0 || tmo_off + (int64_t)sizeof(unsigned) > sol_len) return GOGP_EHIP;
+  memcpy(tmo, (const char *)sol + tmo_off, sizeof(unsigned));
+  return GOGP_OK;
 }
 
 extern "C" int gogp_test_trsv_steps(int device, int precision, int dir, int64_t npad, const void *L, int64_t l_len,
@@ -771,34 +840,22 @@ extern "C" int gogp_test_trsv_steps(int device, int precision, int dir, int64_t 
   if (!covers(l_len, 0, ld, npad, npad, k, bstride) || !covers(w_len, 0, npad, 1, npad, k, bstride) ||
       !covers(out_len, 0, npad, 1, npad, k, bstride))
     return GOGP_EARG;
-  if (!device_ok(device)) return GOGP_EHIP;
-  const size_t es = precision / 8;
-  DevCopy dL, dD, dw, dout;
-  hipError_t e = dL.up(L, (size_t)l_len * es);
-  if (e == hipSuccess) e = dD.up(Dinv, (size_t)((k - 1) * bstride + npad * PANEL) * es);
-  if (e == hipSuccess) e = dw.up(w, (size_t)w_len * sizeof(double));
-  if (e == hipSuccess) e = dout.up(out, (size_t)out_len * sizeof(double));
-  if (e == hipSuccess) {
-    tl_batch.k = k;
-    tl_batch.stride = (long)(bstride * 8);
-    for (int i = 0; i <= b1 - b0; ++i) {
-      const int b = dir == 0 ? b0 + i : b1 - i;
-      if (precision == 64 && dir == 0)
-        launch_trsv_fwd_step(0, dL.as<double>(), ld, dD.as<double>(), b, nb, dw.as<double>(), dout.as<double>());
-      else if (precision == 64)
-        launch_trsv_bwd_step(0, dL.as<double>(), ld, dD.as<double>(), b, nb, dw.as<double>(), dout.as<double>());
-      else if (dir == 0)
-        launch_trsv_fwd_step(0, dL.as<float>(), ld, dD.as<float>(), b, nb, dw.as<double>(), dout.as<double>());
-      else
-        launch_trsv_bwd_step(0, dL.as<float>(), ld, dD.as<float>(), b, nb, dw.as<double>(), dout.as<double>());
-    }
-    tl_batch.k = 1;
-    tl_batch.stride = 0;
-    e = launched();
-  }
-  if (e == hipSuccess) e = dw.down(w);
-  if (e == hipSuccess) e = dout.down(out);
-  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+  const int es = precision / 8;
+  return run(device, {rd(L, l_len, es), rd(Dinv, (k - 1) * bstride + npad * PANEL, es), io(w, w_len), io(out, out_len)},
+             [&](const Dev &d) {
+               set_batch(k, bstride);
+               for (int i = 0; i <= b1 - b0; ++i) {
+                 const int b = dir == 0 ? b0 + i : b1 - i;
+                 if (precision == 64 && dir == 0)
+                   launch_trsv_fwd_step(0, d[0], ld, d[1], b, nb, d[2], d[3]);
+                 else if (precision == 64)
+                   launch_trsv_bwd_step(0, d[0], ld, d[1], b, nb, d[2], d[3]);
+                 else if (dir == 0)
+                   launch_trsv_fwd_step(0, d.f32(0), ld, d.f32(1), b, nb, d[2], d[3]);
+                 else
+                   launch_trsv_bwd_step(0, d.f32(0), ld, d.f32(1), b, nb, d[2], d[3]);
+               }
+             });
 }
 
 extern "C" int gogp_test_alpha_from_y(int device, int precision, int64_t npad, const void *Y, int64_t y_len, int64_t ld,
@@ -806,20 +863,12 @@ extern "C" int gogp_test_alpha_from_y(int device, int precision, int64_t npad, c
   if (!Y || !z || !alpha || !prec_ok(precision)) return GOGP_EARG;
   if (npad <= 0 || npad % 2 || npad > TH_NPAD_MAX || ld % 2) return GOGP_EARG;  // pairs of columns
   if (!covers(y_len, 0, ld, npad, npad, 1, 0) || z_len < npad || alpha_len < npad) return GOGP_EARG;
-  if (!device_ok(device)) return GOGP_EHIP;
-  DevCopy dY, dz, da;
-  hipError_t e = dY.up(Y, (size_t)y_len * (precision / 8));
-  if (e == hipSuccess) e = dz.up(z, (size_t)z_len * sizeof(double));
-  if (e == hipSuccess) e = da.up(alpha, (size_t)alpha_len * sizeof(double));
-  if (e == hipSuccess) {
+  return run(device, {rd(Y, y_len, precision / 8), rd(z, z_len), io(alpha, alpha_len)}, [&](const Dev &d) {
     if (precision == 64)
-      launch_alpha_from_y(0, dY.as<double>(), ld, dz.as<double>(), npad, da.as<double>());
+      launch_alpha_from_y(0, (const double *)d[0], ld, d[1], npad, d[2]);
     else
-      launch_alpha_from_y(0, dY.as<float>(), ld, dz.as<double>(), npad, da.as<double>());
-    e = launched();
-  }
-  if (e == hipSuccess) e = da.down(alpha);
-  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+      launch_alpha_from_y(0, (const float *)d.f32(0), ld, d[1], npad, d[2]);
+  });
 }
 
 extern "C" int gogp_test_rownorm_dot(int device, int precision, const void *V, int64_t v_len, int64_t ld, int64_t ncols,
@@ -828,22 +877,13 @@ extern "C" int gogp_test_rownorm_dot(int device, int precision, const void *V, i
   if (!V || !prec_ok(precision) || m <= 0 || m > 65535 || ncols <= 0) return GOGP_EARG;
   if (!covers(v_len, 0, ld, m, ncols, 1, 0) || (vec && vec_len < ncols) || (dot && dot_len < m) || (sq && sq_len < m))
     return GOGP_EARG;
-  if (!device_ok(device)) return GOGP_EHIP;
-  DevCopy dV, dvec, ddot, dsq;
-  hipError_t e = dV.up(V, (size_t)v_len * (precision / 8));
-  if (e == hipSuccess) e = dvec.up(vec, vec ? (size_t)vec_len * sizeof(double) : 0);
-  if (e == hipSuccess) e = ddot.up(dot, dot ? (size_t)dot_len * sizeof(double) : 0);
-  if (e == hipSuccess) e = dsq.up(sq, sq ? (size_t)sq_len * sizeof(double) : 0);
-  if (e == hipSuccess) {
+  // vec, dot and sq may each be NULL: run() copies nothing for those and the launcher gets nullptr
+  return run(device, {rd(V, v_len, precision / 8), rd(vec, vec_len), io(dot, dot_len), io(sq, sq_len)}, [&](const Dev &d) {
     if (precision == 64)
-      launch_rownorm_dot(0, dV.as<double>(), ld, dvec.as<double>(), ncols, m, ddot.as<double>(), dsq.as<double>());
+      launch_rownorm_dot(0, d[0], ld, d[1], ncols, m, d[2], d[3]);
     else
-      launch_rownorm_dot(0, dV.as<float>(), ld, dvec.as<double>(), ncols, m, ddot.as<double>(), dsq.as<double>());
-    e = launched();
-  }
-  if (e == hipSuccess && dot) e = ddot.down(dot);
-  if (e == hipSuccess && sq) e = dsq.down(sq);
-  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+      launch_rownorm_dot(0, d.f32(0), ld, d[1], ncols, m, d[2], d[3]);
+  });
 }
 
 extern "C" int gogp_test_tinv(int device, int precision, int nsub, const void *Dinv, void *X, int64_t x_len, int64_t tld,
@@ -851,22 +891,13 @@ extern "C" int gogp_test_tinv(int device, int precision, int nsub, const void *D
   if (!Dinv || !X || !prec_ok(precision) || nsub < 1 || nsub > 16 || (with_xt && !XT)) return GOGP_EARG;
   const int64_t n = (int64_t)nsub * PANEL;
   if (!covers(x_len, 0, tld, n, n, 1, 0)) return GOGP_EARG;
-  if (!device_ok(device)) return GOGP_EHIP;
-  const size_t es = precision / 8;
-  DevCopy dD, dX, dXT;
-  hipError_t e = dD.up(Dinv, (size_t)n * PANEL * es);
-  if (e == hipSuccess) e = dX.up(X, (size_t)x_len * es);
-  if (e == hipSuccess && with_xt) e = dXT.up(XT, (size_t)x_len * es);
-  if (e == hipSuccess) {
+  const int es = precision / 8;
+  return run(device, {rd(Dinv, n * PANEL, es), io(X, x_len, es), io(with_xt ? XT : nullptr, x_len, es)}, [&](const Dev &d) {
     if (precision == 64)
-      launch_tinv_init(0, dD.as<double>(), dX.as<double>(), dXT.as<double>(), nsub, tld);
+      launch_tinv_init(0, d[0], d[1], d[2], nsub, tld);
     else
-      launch_tinv_init(0, dD.as<float>(), dX.as<float>(), dXT.as<float>(), nsub, tld);
-    e = launched();
-  }
-  if (e == hipSuccess) e = dX.down(X);
-  if (e == hipSuccess && with_xt) e = dXT.down(XT);
-  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+      launch_tinv_init(0, d.f32(0), d.f32(1), d.f32(2), nsub, tld);
+  });
 }
 
 extern "C" int gogp_test_blockmm(int device, int precision, int nprod, void *arena, int64_t arena_len, const int64_t *a_off,
@@ -882,100 +913,33 @@ extern "C" int gogp_test_blockmm(int device, int precision, int nprod, void *are
         !covers(arena_len, c_off[b], ldc[b], PANEL, PANEL, k, bstride))
       return GOGP_EARG;
   }
-  if (!device_ok(device)) return GOGP_EHIP;
-  const size_t es = precision / 8;
-  DevCopy dA;
-  hipError_t e = dA.up(arena, (size_t)arena_len * es);
-  if (e == hipSuccess) {
-    tl_batch.k = k;
-    tl_batch.stride = (long)(bstride * (int64_t)es);
+  const int es = precision / 8;
+  return run(device, {io(arena, arena_len, es)}, [&](const Dev &d) {
+    set_batch(k, bstride, es);
     if (precision == 64) {
       const double *A[6], *B[6];
       double *C[6];
       for (int b = 0; b < nprod; ++b) {
-        A[b] = dA.as<double>() + a_off[b];
-        B[b] = dA.as<double>() + b_off[b];
-        C[b] = dA.as<double>() + c_off[b];
+        A[b] = d[0] + a_off[b];
+        B[b] = d[0] + b_off[b];
+        C[b] = d[0] + c_off[b];
       }
       launch_blockmm(0, nprod, A, lda, B, ldb, C, ldc, K, alpha);
     } else {
       const float *A[6], *B[6];
       float *C[6];
       for (int b = 0; b < nprod; ++b) {
-        A[b] = dA.as<float>() + a_off[b];
-        B[b] = dA.as<float>() + b_off[b];
-        C[b] = dA.as<float>() + c_off[b];
+        A[b] = d.f32(0) + a_off[b];
+        B[b] = d.f32(0) + b_off[b];
+        C[b] = d.f32(0) + c_off[b];
       }
       launch_blockmm(0, nprod, A, lda, B, ldb, C, ldc, K, alpha);
     }
-    tl_batch.k = 1;
-    tl_batch.stride = 0;
-    e = launched();
-  }
-  if (e == hipSuccess) e = dA.down(arena);
-  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+  });
 }
 
 // ---- the kernels that turn K^-1 into the gradient, through their product launchers (tests/test_grad_kernels.py) ----------
 namespace {
-static_assert(GOGP_TEST_NACC == NACC, "GOGP_TEST_NACC mirrors NACC");
-constexpr int64_t GR_NPAD_MAX = 1 << 15;
-// the launchers' selection arguments and the parameters they go with
-bool kparams_ok(const gogp_test_kparams *kp, int k, int ard_dims, int radial1, int mfma_min, int ev) {
-  if (!kp || k < 1) return false;
-  for (int c = 0; c < k; ++c) {
-    const gogp_test_kparams &q = kp[c];
-    if (q.ndim < 1 || q.ndim > GOGP_MAX_NDIM || q.nterms < 1 || q.nterms > GOGP_MAX_TERMS) return false;
-    if (q.ndim != kp[0].ndim || q.nterms != kp[0].nterms) return false;  // one launch sequence: one kernel shape
-    int nard = 0;
-    for (int t = 0; t < q.nterms; ++t) {
-      if (q.kind[t] < GOGP_K_NORMAL || q.kind[t] > GOGP_K_PERIODIC || q.kind[t] != kp[0].kind[t]) return false;
-      nard += q.ard[t] != 0;
-      for (int d = q.ndim; d < GOGP_MAX_NDIM; ++d)
-        if (q.inv_len[t][d] != 0.0) return false;  // the ARD pass relies on it (common.h: launch_grad_reduce)
-    }
-    if (nard > 1 || ard_dims != (nard ? q.ndim : 0)) return false;  // one ARD term at most; ard_dims is 0 or ndim
-    if (radial1 && (q.nterms != 1 || q.kind[0] == GOGP_K_PERIODIC)) return false;
-    if (q.nevents < 0 || q.nevents > GOGP_MAX_EVENTS || q.ev_axis < 0 || q.ev_axis >= q.ndim) return false;
-  }
-  if (ev && ard_dims > 0) return false;  // no instance has both (gogp_set_events refuses ARD)
-  return mfma_min >= 1;
-}
-DevParams to_dev(const gogp_test_kparams &q) {
-  DevParams p;
-  memset(&p, 0, sizeof p);
-  p.ndim = q.ndim;
-  p.nterms = q.nterms;
-  for (int t = 0; t < GOGP_MAX_TERMS; ++t) {
-    p.kind[t] = q.kind[t];
-    p.ard[t] = q.ard[t];
-    p.c[t] = q.c[t];
-    p.w[t] = q.w[t];
-    for (int d = 0; d < GOGP_MAX_NDIM; ++d) p.inv_len[t][d] = q.inv_len[t][d];
-  }
-  p.noise_var = q.noise_var;
-  p.dnoise = q.dnoise;
-  p.nevents = q.nevents;
-  p.ev_axis = q.ev_axis;
-  for (int e = 0; e < GOGP_MAX_EVENTS; ++e) {
-    p.ev_from[e] = q.ev_from[e];
-    p.ev_to[e] = q.ev_to[e];
-    p.ev_disc[e] = q.ev_disc[e];
-  }
-  return p;
-}
-// k parameter blocks / k rows of NACC, candidate c at c * stride bytes (stride 0 with k == 1)
-hipError_t up_strided(DevCopy &d, const void *h, size_t item, int k, size_t stride) {
-  std::vector<char> buf((size_t)(k - 1) * stride + item, 0);
-  for (int c = 0; c < k; ++c) memcpy(buf.data() + (size_t)c * stride, (const char *)h + (size_t)c * item, item);
-  return d.up(buf.data(), buf.size());
-}
-hipError_t down_strided(const DevCopy &d, void *h, size_t item, int k, size_t stride) {
-  std::vector<char> buf(d.bytes);
-  const hipError_t e = d.down(buf.data());
-  for (int c = 0; c < k && e == hipSuccess; ++c) memcpy((char *)h + (size_t)c * item, buf.data() + (size_t)c * stride, item);
-  return e;
-}
 int blocks_of(int64_t npad, int64_t mrows, int64_t ncols, int max_blocks) {
   if (max_blocks < 0) return -1;
   int b;
@@ -1012,33 +976,24 @@ extern "C" int gogp_test_grad_reduce(int device, int precision, const gogp_test_
   if (x_len < npad * ndim + GOGP_MAX_NDIM || !covers(alpha_len, 0, npad, 1, npad, k, bstride) ||
       !covers(kinv_len, 0, ld, npad, npad, k, bstride) || !covers(partials_len, 0, prow, 1, prow, k, bstride))
     return GOGP_EARG;
-  if (!device_ok(device)) return GOGP_EHIP;
   std::vector<DevParams> hp;
   for (int c = 0; c < k; ++c) hp.push_back(to_dev(kparams[c]));
   const size_t sb = (size_t)bstride * 8;
-  DevCopy dP, dX, da, dK, dpart, dout;
-  hipError_t e = up_strided(dP, hp.data(), sizeof(DevParams), k, sb);
-  if (e == hipSuccess) e = dX.up(X, (size_t)x_len * sizeof(double));
-  if (e == hipSuccess) e = da.up(alpha, (size_t)alpha_len * sizeof(double));
-  if (e == hipSuccess) e = dK.up(Kinv, (size_t)kinv_len * (precision / 8));
-  if (e == hipSuccess) e = dpart.up(partials, (size_t)partials_len * sizeof(double));
-  if (e == hipSuccess) e = up_strided(dout, out, NACC * sizeof(double), k, sb);
-  if (e == hipSuccess) {
-    tl_batch.k = k;
-    tl_batch.stride = (long)sb;
+  const std::vector<char> P = pack_strided(hp.data(), sizeof(DevParams), k, sb);
+  std::vector<char> O = pack_strided(out, NACC * sizeof(double), k, sb);
+  const std::vector<Arr> arrs = {rd(P.data(), P.size(), 1),      rd(X, x_len), rd(alpha, alpha_len), rd(Kinv, kinv_len, precision / 8),
+                                 io(partials, partials_len), io(O.data(), O.size(), 1)};
+  const int rc = run(device, arrs, [&](const Dev &d) {
+    set_batch(k, bstride);
     if (precision == 64)
-      launch_grad_reduce(0, dP.as<DevParams>(), ndim, ard_dims, dX.as<double>(), da.as<double>(), dK.as<double>(), ld, n,
-                         npad, dpart.as<double>(), dout.as<double>(), radial1 != 0, mfma_min, ev != 0, max_blocks);
+      launch_grad_reduce(0, d.as<DevParams>(0), ndim, ard_dims, d[1], d[2], d[3], ld, n, npad, d[4], d[5], radial1 != 0,
+                         mfma_min, ev != 0, max_blocks);
     else
-      launch_grad_reduce(0, dP.as<DevParams>(), ndim, ard_dims, dX.as<double>(), da.as<double>(), dK.as<float>(), ld, n,
-                         npad, dpart.as<double>(), dout.as<double>(), radial1 != 0, mfma_min, ev != 0, max_blocks);
-    tl_batch.k = 1;
-    tl_batch.stride = 0;
-    e = launched();
-  }
-  if (e == hipSuccess) e = dpart.down(partials);
-  if (e == hipSuccess) e = down_strided(dout, out, NACC * sizeof(double), k, sb);
-  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+      launch_grad_reduce(0, d.as<DevParams>(0), ndim, ard_dims, d[1], d[2], d.f32(3), ld, n, npad, d[4], d[5], radial1 != 0,
+                         mfma_min, ev != 0, max_blocks);
+  });
+  if (rc == GOGP_OK) unpack_strided(O, out, NACC * sizeof(double), k, sb);
+  return rc;
 }
 
 extern "C" int gogp_test_grad_reduce_local(int device, int precision, const gogp_test_kparams *kparams, int ard_dims,
@@ -1068,29 +1023,17 @@ extern "C" int gogp_test_grad_reduce_local(int device, int precision, const gogp
   if (x_len < npad * ndim + GOGP_MAX_NDIM || alpha_len < npad || !covers(kinv_len, 0, ld, mrows, ncols, 1, 0) ||
       partials_len < prow)
     return GOGP_EARG;
-  if (!device_ok(device)) return GOGP_EHIP;
   const DevParams hp = to_dev(kparams[0]);
-  DevCopy dP, dX, da, dK, dpart, dout;
-  hipError_t e = dP.up(&hp, sizeof hp);
-  if (e == hipSuccess) e = dX.up(X, (size_t)x_len * sizeof(double));
-  if (e == hipSuccess) e = da.up(alpha, (size_t)alpha_len * sizeof(double));
-  if (e == hipSuccess) e = dK.up(Kinv, (size_t)kinv_len * (precision / 8));
-  if (e == hipSuccess) e = dpart.up(partials, (size_t)partials_len * sizeof(double));
-  if (e == hipSuccess) e = dout.up(out, NACC * sizeof(double));
-  if (e == hipSuccess) {
-    if (precision == 64)
-      launch_grad_reduce_local(0, dP.as<DevParams>(), ndim, ard_dims, dX.as<double>(), da.as<double>(), dK.as<double>(), ld,
-                               n, mrows, ncols, map, dpart.as<double>(), dout.as<double>(), radial1 != 0, mfma_min, ev != 0,
-                               max_blocks);
-    else
-      launch_grad_reduce_local(0, dP.as<DevParams>(), ndim, ard_dims, dX.as<double>(), da.as<double>(), dK.as<float>(), ld,
-                               n, mrows, ncols, map, dpart.as<double>(), dout.as<double>(), radial1 != 0, mfma_min, ev != 0,
-                               max_blocks);
-    e = launched();
-  }
-  if (e == hipSuccess) e = dpart.down(partials);
-  if (e == hipSuccess) e = dout.down(out);
-  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+  return run(device, {rd(&hp, 1, sizeof hp), rd(X, x_len), rd(alpha, alpha_len), rd(Kinv, kinv_len, precision / 8),
+                      io(partials, partials_len), io(out, NACC)},
+             [&](const Dev &d) {
+               if (precision == 64)
+                 launch_grad_reduce_local(0, d.as<DevParams>(0), ndim, ard_dims, d[1], d[2], d[3], ld, n, mrows, ncols, map,
+                                          d[4], d[5], radial1 != 0, mfma_min, ev != 0, max_blocks);
+               else
+                 launch_grad_reduce_local(0, d.as<DevParams>(0), ndim, ard_dims, d[1], d[2], d.f32(3), ld, n, mrows, ncols,
+                                          map, d[4], d[5], radial1 != 0, mfma_min, ev != 0, max_blocks);
+             });
 }
 
 extern "C" int gogp_test_xgrad(int device, const gogp_test_kparams *kparams, int ev, const double *X, int64_t x_len,
@@ -1104,28 +1047,16 @@ extern "C" int gogp_test_xgrad(int device, const gogp_test_kparams *kparams, int
   const int ndim = kparams->ndim;
   if (x_len < npad * ndim || alpha_len < npad || !covers(kinv_len, 0, ld, npad, npad, 1, 0) || gx_len < npad * ndim)
     return GOGP_EARG;
-  if (!device_ok(device)) return GOGP_EHIP;
   const DevParams hp = to_dev(*kparams);
-  DevCopy dP, dX, da, dK, dg;
-  hipError_t e = dP.up(&hp, sizeof hp);
-  if (e == hipSuccess) e = dX.up(X, (size_t)x_len * sizeof(double));
-  if (e == hipSuccess) e = da.up(alpha, (size_t)alpha_len * sizeof(double));
-  if (e == hipSuccess) e = dK.up(Kinv, (size_t)kinv_len * sizeof(double));
-  if (e == hipSuccess) e = dg.up(gx, (size_t)gx_len * sizeof(double));
-  if (e == hipSuccess) {
-    launch_xgrad(0, dP.as<DevParams>(), ndim, dX.as<double>(), da.as<double>(), dK.as<double>(), ld, n, npad, dg.as<double>(),
-                 ev != 0);
-    e = launched();
-  }
-  if (e == hipSuccess) e = dK.down(Kinv);
-  if (e == hipSuccess) e = dg.down(gx);
-  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+  return run(device, {rd(&hp, 1, sizeof hp), rd(X, x_len), rd(alpha, alpha_len), io(Kinv, kinv_len), io(gx, gx_len)},
+             [&](const Dev &d) {
+               launch_xgrad(0, d.as<DevParams>(0), ndim, d[1], d[2], d[3], ld, n, npad, d[4], ev != 0);
+             });
 }
 
 // ---- the kernels that update a factor or consume Produce's V^T, through their product launchers
 // (tests/test_update_kernels.py): append_gram_kernel and append_commit_kernel (append.hip), the gather, W, snapshot and
-// block kernels of remove.hip, bwd_panel_kernel (pgrad.hip) and the two kernels of launch_pcov (pcov.hip).  The rules of the
-// hooks above.
+// block kernels of remove.hip, bwd_panel_kernel (pgrad.hip) and the two kernels of launch_pcov (pcov.hip).
 namespace {
 // bytes a solution of `cols` right-hand sides over npc rows occupies from its first byte on; -1: not a layout
 int64_t sol_bytes(int kind, int width, int cols, int64_t npc) {
@@ -1144,20 +1075,12 @@ bool sol_ok(const void *p, int64_t len, int kind, int width, int64_t off, int co
   if (cols == 0) return true;  // never read
   return p && off >= 0 && off % (kind == TS_SOL_GRANULE ? 16 : 8) == 0 && off + need <= len;
 }
-// the one-term-at-most ARD count kparams_ok wants stated
-int ard_dims_of(const gogp_test_kparams *kp) {
-  if (!kp || kp->nterms < 1 || kp->nterms > GOGP_MAX_TERMS) return 0;
-  int nard = 0;
-  for (int t = 0; t < kp->nterms; ++t) nard += kp->ard[t] != 0;
-  return nard == 1 ? kp->ndim : 0;
-}
 // every entry of an index list names a row of a matrix of leading dimension ld0 that src (src_len elements) holds whole
 bool rows_ok(const int *idx, int64_t cnt, int64_t ld0, int64_t src_len) {
   for (int64_t i = 0; i < cnt; ++i)
     if (idx[i] < 0 || idx[i] >= ld0 || ((int64_t)idx[i] + 1) * ld0 > src_len) return false;
   return true;
 }
-constexpr int64_t UP_NPAD_MAX = 1 << 15;
 }  // namespace
 
 extern "C" int gogp_test_append_gram(int device, const void *sol0, int64_t sol0_len, int kind0, int width0, int64_t off0,
@@ -1170,34 +1093,26 @@ extern "C" int gogp_test_append_gram(int device, const void *sol0, int64_t sol0_
     return GOGP_EARG;
   if (z_len < npc || part_len < npc / PANEL * APPEND_PART || lnew_len <= 0) return GOGP_EARG;
   if (n > 0 && !covers(lnew_len, 0, ld, m, n, 1, 0)) return GOGP_EARG;
-  if (!device_ok(device)) return GOGP_EHIP;
-  DevCopy d0, d1, dz, dpart, dL;
-  hipError_t e = d0.up(m0 ? sol0 : nullptr, (size_t)sol0_len);
-  if (e == hipSuccess) e = d1.up(m - m0 ? sol1 : nullptr, (size_t)sol1_len);
-  if (e == hipSuccess) e = dz.up(z, (size_t)z_len * sizeof(double));
-  if (e == hipSuccess) e = dpart.up(part, (size_t)part_len * sizeof(double));
-  if (e == hipSuccess) e = dL.up(Lnew, (size_t)lnew_len * sizeof(double));
-  if (e == hipSuccess) {
-    TsSolution v0, v1;
-    v0.p = d0.d ? d0.d + off0 : nullptr;
-    v0.kind = kind0;
-    v0.width = width0;
-    v1.p = d1.d ? d1.d + off1 : nullptr;
-    v1.kind = kind1;
-    v1.width = width1;
-    launch_append_gram(0, v0, v1, m0, m, npc, n, dz.as<double>(), dpart.as<double>(), dL.as<double>(), ld);
-    e = launched();
-  }
-  if (e == hipSuccess) e = dpart.down(part);
-  if (e == hipSuccess) e = dL.down(Lnew);
-  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+  // a source that gives no column is not uploaded: its solution pointer is nullptr
+  return run(device, {rd(m0 ? sol0 : nullptr, sol0_len, 1), rd(m - m0 ? sol1 : nullptr, sol1_len, 1), rd(z, z_len),
+                      io(part, part_len), io(Lnew, lnew_len)},
+             [&](const Dev &d) {
+               TsSolution v0, v1;
+               v0.p = d.as<char>(0) ? d.as<char>(0) + off0 : nullptr;
+               v0.kind = kind0;
+               v0.width = width0;
+               v1.p = d.as<char>(1) ? d.as<char>(1) + off1 : nullptr;
+               v1.kind = kind1;
+               v1.width = width1;
+               launch_append_gram(0, v0, v1, m0, m, npc, n, d[2], d[3], d[4], ld);
+             });
 }
 
-// v2 != nullptr: launch_nv_append_fold (noisevar.hip) on the parts first, as gogp_append_noisy does; part_out != nullptr:
-// the parts come back whole
+// v2 != nullptr: launch_nv_append_fold (noisevar.hip) on the parts first, as gogp_append_noisy does; parts_back: the
+// parts come back whole
 static int test_append_commit(int device, const gogp_test_kparams *kparams, int ev, const double *X2, int64_t x2_len,
                               const double *y2, int64_t y2_len, const double *v2, int64_t v2_len, int m, int64_t n,
-                              const double *part, double *part_out, int64_t part_len, int nslab, double *Lnew,
+                              const double *part, bool parts_back, int64_t part_len, int nslab, double *Lnew,
                               int64_t lnew_len, int64_t ld, double *z2, int64_t z2_len, long long *info) {
   if (!kparams || !X2 || !y2 || !part || !Lnew || !z2 || !info) return GOGP_EARG;
   if (v2 && v2_len < m) return GOGP_EARG;
@@ -1206,35 +1121,23 @@ static int test_append_commit(int device, const gogp_test_kparams *kparams, int 
   if (x2_len < (int64_t)m * kparams->ndim || y2_len < m || z2_len < m || part_len < (int64_t)nslab * APPEND_PART)
     return GOGP_EARG;
   if (!covers(lnew_len, 0, ld, m, n + m, 1, 0)) return GOGP_EARG;
-  if (!device_ok(device)) return GOGP_EHIP;
   const DevParams hp = to_dev(*kparams);
-  DevCopy dP, dX, dy, dv, dpart, dL, dz, di;
-  hipError_t e = dP.up(&hp, sizeof hp);
-  if (e == hipSuccess) e = dX.up(X2, (size_t)x2_len * sizeof(double));
-  if (e == hipSuccess) e = dy.up(y2, (size_t)y2_len * sizeof(double));
-  if (e == hipSuccess && v2) e = dv.up(v2, (size_t)v2_len * sizeof(double));
-  if (e == hipSuccess) e = dpart.up(part, (size_t)part_len * sizeof(double));
-  if (e == hipSuccess) e = dL.up(Lnew, (size_t)lnew_len * sizeof(double));
-  if (e == hipSuccess) e = dz.up(z2, (size_t)z2_len * sizeof(double));
-  if (e == hipSuccess) e = di.up(info, sizeof(long long));
-  if (e == hipSuccess) {
-    if (v2) launch_nv_append_fold(0, dpart.as<double>(), dv.as<double>(), m);
-    launch_append_commit(0, dP.as<DevParams>(), dX.as<double>(), dy.as<double>(), m, n, dpart.as<double>(), nslab,
-                         dL.as<double>(), ld, dz.as<double>(), di.as<long long>(), ev != 0);
-    e = launched();
-  }
-  if (e == hipSuccess) e = dL.down(Lnew);
-  if (e == hipSuccess) e = dz.down(z2);
-  if (e == hipSuccess) e = di.down(info);
-  if (e == hipSuccess && part_out) e = dpart.down(part_out);
-  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+  Arr parts = rd(part, part_len);
+  parts.out = parts_back;
+  return run(device, {rd(&hp, 1, sizeof hp), rd(X2, x2_len), rd(y2, y2_len), rd(v2, v2_len), parts, io(Lnew, lnew_len),
+                      io(z2, z2_len), io(info, 1)},
+             [&](const Dev &d) {
+               if (v2) launch_nv_append_fold(0, d[4], d[3], m);
+               launch_append_commit(0, d.as<DevParams>(0), d[1], d[2], m, n, d[4], nslab, d[5], ld, d[6],
+                                    d.as<long long>(7), ev != 0);
+             });
 }
 
 extern "C" int gogp_test_append_commit(int device, const gogp_test_kparams *kparams, int ev, const double *X2, int64_t x2_len,
                                        const double *y2, int64_t y2_len, int m, int64_t n, const double *part,
                                        int64_t part_len, int nslab, double *Lnew, int64_t lnew_len, int64_t ld, double *z2,
                                        int64_t z2_len, long long *info) {
-  return test_append_commit(device, kparams, ev, X2, x2_len, y2, y2_len, nullptr, 0, m, n, part, nullptr, part_len, nslab,
+  return test_append_commit(device, kparams, ev, X2, x2_len, y2, y2_len, nullptr, 0, m, n, part, false, part_len, nslab,
                             Lnew, lnew_len, ld, z2, z2_len, info);
 }
 
@@ -1243,7 +1146,7 @@ extern "C" int gogp_test_nv_append_commit(int device, const gogp_test_kparams *k
                                           int m, int64_t n, double *part, int64_t part_len, int nslab, double *Lnew,
                                           int64_t lnew_len, int64_t ld, double *z2, int64_t z2_len, long long *info) {
   if ((v2 == nullptr) != (v2_len == 0)) return GOGP_EARG;
-  return test_append_commit(device, kparams, ev, X2, x2_len, y2, y2_len, v2, v2_len, m, n, part, part, part_len, nslab,
+  return test_append_commit(device, kparams, ev, X2, x2_len, y2, y2_len, v2, v2_len, m, n, part, true, part_len, nslab,
                             Lnew, lnew_len, ld, z2, z2_len, info);
 }
 
@@ -1251,17 +1154,8 @@ extern "C" int gogp_test_remove_gather(int device, const double *src, int64_t sr
                                        int64_t map_len, int64_t n1, double *dst, int64_t dst_len, int64_t npad1) {
   if (!src || !map || !dst || npad1 <= 0 || npad1 % PANEL || npad1 > UP_NPAD_MAX || n1 < 1 || n1 > npad1) return GOGP_EARG;
   if (ld0 < 1 || map_len < n1 || dst_len < npad1 * npad1 || !rows_ok(map, n1, ld0, src_len)) return GOGP_EARG;
-  if (!device_ok(device)) return GOGP_EHIP;
-  DevCopy ds, dm, dd;
-  hipError_t e = ds.up(src, (size_t)src_len * sizeof(double));
-  if (e == hipSuccess) e = dm.up(map, (size_t)map_len * sizeof(int));
-  if (e == hipSuccess) e = dd.up(dst, (size_t)dst_len * sizeof(double));
-  if (e == hipSuccess) {
-    launch_remove_gather(0, ds.as<double>(), ld0, dm.as<int>(), n1, dd.as<double>(), npad1);
-    e = launched();
-  }
-  if (e == hipSuccess) e = dd.down(dst);
-  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+  return run(device, {rd(src, src_len), rd(map, map_len, 4), io(dst, dst_len)},
+             [&](const Dev &d) { launch_remove_gather(0, d[0], ld0, d.as<int>(1), n1, d[2], npad1); });
 }
 
 extern "C" int gogp_test_remove_w(int device, const double *src, int64_t src_len, int64_t ld0, const int *map,
@@ -1272,18 +1166,9 @@ extern "C" int gogp_test_remove_w(int device, const double *src, int64_t src_len
   if (mw < 1 || mw > REMOVE_W || mc < 1 || mc > mw || r0 < 0 || r0 >= npad1) return GOGP_EARG;
   if (ld0 < 1 || map_len < n1 || rem_len < mc || w_len < (int64_t)mw * npad1) return GOGP_EARG;
   if (!rows_ok(map, n1, ld0, src_len) || !rows_ok(rem, mc, ld0, src_len)) return GOGP_EARG;
-  if (!device_ok(device)) return GOGP_EHIP;
-  DevCopy ds, dm, dr, dW;
-  hipError_t e = ds.up(src, (size_t)src_len * sizeof(double));
-  if (e == hipSuccess) e = dm.up(map, (size_t)map_len * sizeof(int));
-  if (e == hipSuccess) e = dr.up(rem, (size_t)rem_len * sizeof(int));
-  if (e == hipSuccess) e = dW.up(W, (size_t)w_len * sizeof(double));
-  if (e == hipSuccess) {
-    launch_remove_w(0, ds.as<double>(), ld0, dm.as<int>(), dr.as<int>(), mc, mw, r0, n1, npad1, dW.as<double>());
-    e = launched();
-  }
-  if (e == hipSuccess) e = dW.down(W);
-  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+  return run(device, {rd(src, src_len), rd(map, map_len, 4), rd(rem, rem_len, 4), io(W, w_len)}, [&](const Dev &d) {
+    launch_remove_w(0, d[0], ld0, d.as<int>(1), d.as<int>(2), mc, mw, r0, n1, npad1, d[3]);
+  });
 }
 
 extern "C" int gogp_test_remove_block(int device, double *L, int64_t l_len, int64_t ld, int snap_b0, int snap_nb,
@@ -1296,21 +1181,10 @@ extern "C" int gogp_test_remove_block(int device, double *L, int64_t l_len, int6
   if (l_len < ld * ld || w_len < (int64_t)mw * ld || snap_len < (kb1 / TILE + 1) * (int64_t)(TILE * TILE) ||
       snap_len < (int64_t)(snap_b0 + snap_nb) * (TILE * TILE))
     return GOGP_EARG;
-  if (!device_ok(device)) return GOGP_EHIP;
-  DevCopy dL, ds, dW;
-  hipError_t e = dL.up(L, (size_t)l_len * sizeof(double));
-  if (e == hipSuccess) e = ds.up(snap, (size_t)snap_len * sizeof(double));
-  if (e == hipSuccess) e = dW.up(W, (size_t)w_len * sizeof(double));
-  if (e == hipSuccess) {
-    launch_remove_snap(0, dL.as<double>(), ld, snap_b0, snap_nb, ds.as<double>());
-    for (int64_t kb = kb0; kb <= kb1; kb += TILE)
-      launch_remove_block(0, dL.as<double>(), ld, ds.as<double>(), dW.as<double>(), mw, kb, n1);
-    e = launched();
-  }
-  if (e == hipSuccess) e = dL.down(L);
-  if (e == hipSuccess) e = ds.down(snap);
-  if (e == hipSuccess) e = dW.down(W);
-  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+  return run(device, {io(L, l_len), io(snap, snap_len), io(W, w_len)}, [&](const Dev &d) {
+    launch_remove_snap(0, d[0], ld, snap_b0, snap_nb, d[1]);
+    for (int64_t kb = kb0; kb <= kb1; kb += TILE) launch_remove_block(0, d[0], ld, d[1], d[2], mw, kb, n1);
+  });
 }
 
 extern "C" int gogp_test_bwd_panel(int device, int64_t rows16, const double *A, int64_t a_len, int64_t a_off, int64_t lda,
@@ -1323,18 +1197,9 @@ extern "C" int gogp_test_bwd_panel(int device, int64_t rows16, const double *A, 
   if (!covers(a_len, a_off, lda, rows, K, 1, 0) || !covers(b_len, b_off, ldb, K, ncols, 1, 0) ||
       !covers(c_len, c_off, ldc, rows, ncols, 1, 0))
     return GOGP_EARG;
-  if (!device_ok(device)) return GOGP_EHIP;
-  DevCopy dA, dB, dC;
-  hipError_t e = dA.up(A, (size_t)a_len * sizeof(double));
-  if (e == hipSuccess) e = dB.up(B, (size_t)b_len * sizeof(double));
-  if (e == hipSuccess) e = dC.up(C, (size_t)c_len * sizeof(double));
-  if (e == hipSuccess) {
-    launch_bwd_panel(0, rows16, dA.as<double>() + a_off, lda, dB.as<double>() + b_off, ldb, dC.as<double>() + c_off, ldc,
-                     ncols, (int)K, tri != 0, sub != 0);
-    e = launched();
-  }
-  if (e == hipSuccess) e = dC.down(C);
-  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+  return run(device, {rd(A, a_len), rd(B, b_len), io(C, c_len)}, [&](const Dev &d) {
+    launch_bwd_panel(0, rows16, d[0] + a_off, lda, d[1] + b_off, ldb, d[2] + c_off, ldc, ncols, (int)K, tri != 0, sub != 0);
+  });
 }
 
 extern "C" int gogp_test_pcov_slabs(int64_t npad, int64_t m, int ncu, int *cols_per_slab) {
@@ -1355,26 +1220,16 @@ extern "C" int gogp_test_pcov(int device, const gogp_test_kparams *kparams, int 
     if (nslab < 1 || npad > UP_NPAD_MAX || ld % 2 || !covers(vt_len, 0, ld, m, npad, 1, 0)) return GOGP_EARG;  // 16-B loads
     if (!part || part_len < nslab * pairs * 4096) return GOGP_EARG;
   }
-  if (!device_ok(device)) return GOGP_EHIP;
   const DevParams hp = to_dev(*kparams);
-  DevCopy dP, dZ, dV, dpart, dout;
-  hipError_t e = dP.up(&hp, sizeof hp);
-  if (e == hipSuccess) e = dZ.up(Z, (size_t)z_len * sizeof(double));
-  if (e == hipSuccess && Vt) e = dV.up(Vt, (size_t)vt_len * sizeof(double));
-  if (e == hipSuccess && part && part_len > 0) e = dpart.up(part, (size_t)part_len * sizeof(double));
-  if (e == hipSuccess) e = dout.up(out, (size_t)out_len * sizeof(double));
-  if (e == hipSuccess) {
-    launch_pcov(0, dP.as<DevParams>(), dZ.as<double>(), m, dV.as<double>(), ld, npad, ncu, dpart.as<double>(), diag_add,
-                dout.as<double>(), mo, ldo, ev != 0);
-    e = launched();
-  }
-  if (e == hipSuccess && part) e = dpart.down(part);
-  if (e == hipSuccess) e = dout.down(out);
-  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+  // Vt and part may be NULL (the prior covariance alone): nothing is copied for them and the launcher gets nullptr
+  return run(device, {rd(&hp, 1, sizeof hp), rd(Z, z_len), rd(Vt, vt_len), io(part, part_len), io(out, out_len)},
+             [&](const Dev &d) {
+               launch_pcov(0, d.as<DevParams>(0), d[1], m, d[2], ld, npad, ncu, d[3], diag_add, d[4], mo, ldo, ev != 0);
+             });
 }
 
-// ---- multi_weight_kernel (multi.hip) through its product launcher (tests/test_multi_output_gpu.py).  The rules of the
-// hooks above; the product keeps A^T with zero rows up to a multiple of 4, so the hook appends them to its device copy.
+// ---- multi_weight_kernel (multi.hip) through its product launcher (tests/test_multi_output_gpu.py).  The product keeps
+// A^T with zero rows up to a multiple of 4, so the hook appends them to its device copy.
 extern "C" int gogp_test_multi_weight(int device, const double *At, int64_t at_len, int64_t ld, int T, const double *Kinv,
                                       int64_t kinv_len, int64_t ldk, int64_t n, int64_t npad, double *G, int64_t g_len) {
   if (!At || !Kinv || !G || T < 1 || T > GOGP_MULTI_MAX_T) return GOGP_EARG;
@@ -1382,29 +1237,17 @@ extern "C" int gogp_test_multi_weight(int device, const double *At, int64_t at_l
   if (!covers(at_len, 0, ld, T, npad, 1, 0) || !covers(kinv_len, 0, ldk, npad, npad, 1, 0) ||
       !covers(g_len, 0, ldk, npad, npad, 1, 0))
     return GOGP_EARG;
-  if (!device_ok(device)) return GOGP_EHIP;
   const int T4 = (T + 3) / 4 * 4;
   const size_t at_bytes = (size_t)std::max<int64_t>(at_len, (int64_t)T4 * ld) * sizeof(double);
-  DevCopy dK, dG;
-  double *dA = nullptr;
-  hipError_t e = hipMalloc(&dA, at_bytes);
-  if (e == hipSuccess) e = hipMemset(dA, 0, at_bytes);
-  // (the rows of the caller's array: T of them, the last one possibly shorter than ld)
-  if (e == hipSuccess)
-    e = hipMemcpy(dA, At, (size_t)std::min<int64_t>(at_len, (int64_t)T * ld) * sizeof(double), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = dK.up(Kinv, (size_t)kinv_len * sizeof(double));
-  if (e == hipSuccess) e = dG.up(G, (size_t)g_len * sizeof(double));
-  if (e == hipSuccess) {
-    launch_multi_weight(0, dA, ld, T, dK.as<double>(), ldk, n, npad, (double)T, dG.as<double>());
-    e = launched();
-  }
-  if (e == hipSuccess) e = dG.down(G);
-  (void)hipFree(dA);
-  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+  // (the rows of the caller's array: T of them, the last one possibly shorter than ld; zeros behind them)
+  const Arr A = padded(rd(At, std::min<int64_t>(at_len, (int64_t)T * ld)), at_bytes, 0);
+  return run(device, {A, rd(Kinv, kinv_len), io(G, g_len)}, [&](const Dev &d) {
+    launch_multi_weight(0, d[0], ld, T, d[1], ldk, n, npad, (double)T, d[2]);
+  });
 }
 
 // ---- sparse_syrk_kernel and sparse_grad_kernel (sparse.hip) through their product launchers
-// (tests/test_sparse_gpu.py).  The rules of the hooks above.
+// (tests/test_sparse_gpu.py).
 extern "C" int gogp_test_sparse_syrk(int device, const double *Vt, int64_t vt_len, int64_t ld, int64_t rows, int64_t M,
                                      int64_t Mp, const double *y, int64_t y_len, double *Bacc, int64_t b_len, int64_t ldb,
                                      double *r, int64_t r_len) {
@@ -1412,19 +1255,8 @@ extern "C" int gogp_test_sparse_syrk(int device, const double *Vt, int64_t vt_le
   if (Mp <= 0 || Mp % 64 || Mp > GOGP_SPARSE_MAX_M || M < 1 || M > Mp || rows < 1 || rows > (1 << 16)) return GOGP_EARG;
   if (!covers(vt_len, 0, ld, rows, Mp, 1, 0) || !covers(b_len, 0, ldb, Mp, Mp, 1, 0) || y_len < rows || r_len < Mp)
     return GOGP_EARG;
-  if (!device_ok(device)) return GOGP_EHIP;
-  DevCopy dV, dy, dB, dr;
-  hipError_t e = dV.up(Vt, (size_t)vt_len * sizeof(double));
-  if (e == hipSuccess) e = dy.up(y, (size_t)y_len * sizeof(double));
-  if (e == hipSuccess) e = dB.up(Bacc, (size_t)b_len * sizeof(double));
-  if (e == hipSuccess) e = dr.up(r, (size_t)r_len * sizeof(double));
-  if (e == hipSuccess) {
-    launch_sparse_syrk(0, dV.as<double>(), ld, rows, M, Mp, dy.as<double>(), dB.as<double>(), ldb, dr.as<double>());
-    e = launched();
-  }
-  if (e == hipSuccess) e = dB.down(Bacc);
-  if (e == hipSuccess) e = dr.down(r);
-  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+  return run(device, {rd(Vt, vt_len), rd(y, y_len), io(Bacc, b_len), io(r, r_len)},
+             [&](const Dev &d) { launch_sparse_syrk(0, d[0], ld, rows, M, Mp, d[1], d[2], ldb, d[3]); });
 }
 
 extern "C" int gogp_test_sparse_grad(int device, const gogp_test_kparams *kparams, const double *X, int64_t x_len, int64_t rows,
@@ -1436,26 +1268,13 @@ extern "C" int gogp_test_sparse_grad(int device, const gogp_test_kparams *kparam
   if (rows < 1 || rows > (1 << 16) || M < 1 || M > GOGP_SPARSE_MAX_M || !std::isfinite(s4)) return GOGP_EARG;
   if (x_len < rows * kparams->ndim || u_len < M * kparams->ndim || y_len < rows || m_len < M) return GOGP_EARG;
   if (!covers(wt_len, 0, ldw, rows, M, 1, 0)) return GOGP_EARG;
-  if (!device_ok(device)) return GOGP_EHIP;
   const DevParams hp = to_dev(*kparams);
-  DevCopy dP, dX, dU, dW, dy, dm, dout;
-  double *part = nullptr;
-  hipError_t e = dP.up(&hp, sizeof hp);
-  if (e == hipSuccess) e = dX.up(X, (size_t)x_len * sizeof(double));
-  if (e == hipSuccess) e = dU.up(U, (size_t)u_len * sizeof(double));
-  if (e == hipSuccess) e = dW.up(Wt, (size_t)wt_len * sizeof(double));
-  if (e == hipSuccess) e = dy.up(y, (size_t)y_len * sizeof(double));
-  if (e == hipSuccess) e = dm.up(mvec, (size_t)m_len * sizeof(double));
-  if (e == hipSuccess) e = dout.up(out, (size_t)NACC * sizeof(double));
-  if (e == hipSuccess) e = hipMalloc(&part, (size_t)sparse_grad_blocks(rows, M) * NACC * sizeof(double));
-  if (e == hipSuccess) {
-    launch_sparse_grad(0, dP.as<DevParams>(), kparams->ndim, ard_dims_of(kparams), dX.as<double>(), rows, dU.as<double>(), M,
-                       dW.as<double>(), ldw, dy.as<double>(), dm.as<double>(), s4, part, dout.as<double>(), accumulate != 0);
-    e = launched();
-  }
-  if (e == hipSuccess) e = dout.down(out);
-  (void)hipFree(part);
-  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+  return run(device, {rd(&hp, 1, sizeof hp), rd(X, x_len), rd(U, u_len), rd(Wt, wt_len), rd(y, y_len), rd(mvec, m_len),
+                      io(out, NACC), scratch((size_t)sparse_grad_blocks(rows, M) * NACC * sizeof(double))},
+             [&](const Dev &d) {
+               launch_sparse_grad(0, d.as<DevParams>(0), kparams->ndim, ard_dims_of(kparams), d[1], rows, d[2], M, d[3], ldw,
+                                  d[4], d[5], s4, d[7], d[6], accumulate != 0);
+             });
 }
 
 extern "C" int gogp_test_sparse_ugrad_slabs(int64_t rows, int64_t M, int *tiles_per_slab) {
@@ -1478,27 +1297,14 @@ extern "C" int gogp_test_sparse_ugrad(int device, const gogp_test_kparams *kpara
   if (x_len < rows * kparams->ndim || u_len < M * kparams->ndim || y_len < rows || m_len < M || du_len < M * kparams->ndim)
     return GOGP_EARG;
   if (!covers(wt_len, 0, ldw, rows, M, 1, 0)) return GOGP_EARG;
-  if (!device_ok(device)) return GOGP_EHIP;
   const DevParams hp = to_dev(*kparams);
-  DevCopy dP, dX, dUp, dW, dy, dm, dout;
-  double *part = nullptr;
-  hipError_t e = dP.up(&hp, sizeof hp);
-  if (e == hipSuccess) e = dX.up(X, (size_t)x_len * sizeof(double));
-  if (e == hipSuccess) e = dUp.up(U, (size_t)u_len * sizeof(double));
-  if (e == hipSuccess) e = dW.up(Wt, (size_t)wt_len * sizeof(double));
-  if (e == hipSuccess) e = dy.up(y, (size_t)y_len * sizeof(double));
-  if (e == hipSuccess) e = dm.up(mvec, (size_t)m_len * sizeof(double));
-  if (e == hipSuccess) e = dout.up(dU, (size_t)du_len * sizeof(double));
-  if (e == hipSuccess)
-    e = hipMalloc(&part, (size_t)sparse_ugrad_slabs(rows, M, nullptr) * (size_t)M * kparams->ndim * sizeof(double));
-  if (e == hipSuccess) {
-    launch_sparse_ugrad(0, dP.as<DevParams>(), kparams->ndim, dX.as<double>(), rows, dUp.as<double>(), M, dW.as<double>(), ldw,
-                        dy.as<double>(), dm.as<double>(), s4, part, dout.as<double>(), accumulate != 0);
-    e = launched();
-  }
-  if (e == hipSuccess) e = dout.down(dU);
-  (void)hipFree(part);
-  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+  const size_t part_bytes = (size_t)sparse_ugrad_slabs(rows, M, nullptr) * (size_t)M * kparams->ndim * sizeof(double);
+  return run(device, {rd(&hp, 1, sizeof hp), rd(X, x_len), rd(U, u_len), rd(Wt, wt_len), rd(y, y_len), rd(mvec, m_len),
+                      io(dU, du_len), scratch(part_bytes)},
+             [&](const Dev &d) {
+               launch_sparse_ugrad(0, d.as<DevParams>(0), kparams->ndim, d[1], rows, d[2], M, d[3], ldw, d[4], d[5], s4, d[7],
+                                   d[6], accumulate != 0);
+             });
 }
 
 // launch_sparse_xty on host arrays: R (in / out) += Y^T Vt.  The partials are sized as the product sizes them.
@@ -1511,20 +1317,9 @@ extern "C" int gogp_test_sparse_xty(int device, const double *Vt, int64_t vt_len
   const int64_t tt = (T + 63) / 64 * 64, mc = (M + 63) / 64 * 64;
   if (!covers(vt_len, 0, ld, rows, M, 1, 0) || !covers(y_len, 0, ldy, rows, T, 1, 0) || !covers(r_len, 0, ldr, tt, mc, 1, 0))
     return GOGP_EARG;
-  if (!device_ok(device)) return GOGP_EHIP;
-  DevCopy dV, dY, dR;
-  double *part = nullptr;
-  hipError_t e = dV.up(Vt, (size_t)vt_len * sizeof(double));
-  if (e == hipSuccess) e = dY.up(Y, (size_t)y_len * sizeof(double));
-  if (e == hipSuccess) e = dR.up(R, (size_t)r_len * sizeof(double));
-  if (e == hipSuccess) e = hipMalloc(&part, sparse_xty_part_doubles(rows, M, T) * sizeof(double));
-  if (e == hipSuccess) {
-    launch_sparse_xty(0, dV.as<double>(), ld, rows, M, dY.as<double>(), ldy, T, part, dR.as<double>(), ldr);
-    e = launched();
-  }
-  if (e == hipSuccess) e = dR.down(R);
-  (void)hipFree(part);
-  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+  const size_t part_bytes = sparse_xty_part_doubles(rows, M, T) * sizeof(double);
+  return run(device, {rd(Vt, vt_len), rd(Y, y_len), io(R, r_len), scratch(part_bytes)},
+             [&](const Dev &d) { launch_sparse_xty(0, d[0], ld, rows, M, d[1], ldy, T, d[3], d[2], ldr); });
 }
 
 extern "C" int gogp_test_sparse_xty_slabs(int64_t rows, int64_t M, int64_t T, int64_t *rows_per_slab) {
@@ -1538,8 +1333,6 @@ extern "C" int gogp_test_sparse_xty_slabs_bound(int64_t rows, int64_t M, int64_t
 }
 
 // ---- greedy selection of inducing points (select.hip; tests/test_select_inducing_kernels.py) ----------------------------
-// The rules of the hooks above: every argument is checked before the device is touched, every array goes to the device
-// whole and every in / out array comes back whole.
 namespace {
 constexpr int64_t SEL_N_MAX = 1 << 22;
 bool select_args_ok(const gogp_test_kparams *kp, int64_t x_len, int64_t N, double tol, int max_blocks) {
@@ -1562,12 +1355,11 @@ extern "C" int gogp_test_select_step(int device, const gogp_test_kparams *kparam
   if (part_len != blocks || out_len < blocks) return GOGP_EARG;
   for (int q = 0; q < blocks; ++q)
     if (part_i[q] < 0 || part_i[q] >= N) return GOGP_EARG;  // the kernel reads row part_i of X and of the factor
-  if (!device_ok(device)) return GOGP_EHIP;
   const DevParams hp = to_dev(*kparams);
   const int D = kparams->ndim;
+  // the select_layout work area is packed on the host, travels as one in / out array and is unpacked afterwards
   SelectBufs b;
   const size_t small = select_layout(nullptr, N, j + 1, D, &b);
-  DevCopy dP, dX, dL, dW;
   std::vector<char> work(small, 0);
   select_layout(work.data(), N, j + 1, D, &b);
   memcpy(b.d, d, (size_t)N * sizeof(double));
@@ -1575,21 +1367,15 @@ extern "C" int gogp_test_select_step(int device, const gogp_test_kparams *kparam
   SelPair *pin = b.part + (size_t)(j & 1) * SELECT_BLOCKS_MAX;
   for (int q = 0; q < blocks; ++q) pin[q].v = part_v[q], pin[q].i = part_i[q];
   for (int64_t t = 0; t <= j; ++t) b.piv[t] = t < j ? 0 : -1;  // the earlier steps recorded pivots
-  hipError_t e = dP.up(&hp, sizeof hp);
-  if (e == hipSuccess) e = dX.up(X, (size_t)x_len * sizeof(double));
-  if (e == hipSuccess) e = dL.up(Lt, (size_t)lt_len * sizeof(double));
-  if (e == hipSuccess) e = dW.up(work.data(), small);
-  if (e == hipSuccess) {
-    SelectBufs db;
-    select_layout(dW.d, N, j + 1, D, &db);
-    db.Lt = dL.as<double>();
-    db.ldn = ldn;
-    launch_select_step(0, dP.as<DevParams>(), D, dX.as<double>(), N, blocks, (int)j, tol, db);
-    e = launched();
-  }
-  if (e == hipSuccess) e = dL.down(Lt);
-  if (e == hipSuccess) e = dW.down(work.data());
-  if (e != hipSuccess) return GOGP_EHIP;
+  const int rc = run(device, {rd(&hp, 1, sizeof hp), rd(X, x_len), io(Lt, lt_len), io(work.data(), (int64_t)small, 1)},
+                     [&](const Dev &dv) {
+                       SelectBufs db;
+                       select_layout(dv.as<char>(3), N, j + 1, D, &db);
+                       db.Lt = dv[2];
+                       db.ldn = ldn;
+                       launch_select_step(0, dv.as<DevParams>(0), D, dv[1], N, blocks, (int)j, tol, db);
+                     });
+  if (rc != GOGP_OK) return rc;
   memcpy(d, b.d, (size_t)N * sizeof(double));
   memcpy(sel, b.sel, (size_t)N);
   const SelPair *pout = b.part + (size_t)((j + 1) & 1) * SELECT_BLOCKS_MAX;
@@ -1612,33 +1398,30 @@ extern "C" int gogp_test_select_run(int device, const gogp_test_kparams *kparams
   const int64_t cols = std::min(M, N);
   if ((d0 && d0_len < N) || (U && u_len < M * D) || (Lt && lt_len < cols * b.ldn) || (d && d_len < N)) return GOGP_EARG;
   if (!device_ok(device)) return GOGP_EHIP;
+  // not on run(): select_run is the product's whole loop, which returns its own error and the count m, and the results
+  // are the first m entries of pieces of its device work area, not copies of host arrays
   const DevParams hp = to_dev(*kparams);
-  DevCopy dP, dX, d0c;
-  char *work = nullptr;
-  double *dL = nullptr;
+  DevCopy dP, dX, d0c, work, dL;
   const size_t lbytes = (size_t)cols * (size_t)b.ldn * sizeof(double);
   hipError_t e = dP.up(&hp, sizeof hp);
   if (e == hipSuccess) e = dX.up(X, (size_t)x_len * sizeof(double));
   if (e == hipSuccess && d0) e = d0c.up(d0, (size_t)d0_len * sizeof(double));
-  if (e == hipSuccess) e = hipMalloc(&work, small);
-  if (e == hipSuccess) e = hipMalloc(&dL, lbytes);
-  if (e == hipSuccess) e = hipMemset(dL, 0xff, lbytes);  // NaN: what no step wrote shows
+  if (e == hipSuccess) e = work.up(nullptr, 0, small);
+  if (e == hipSuccess) e = dL.up(nullptr, 0, lbytes, 0xff);  // NaN: what no step wrote shows
   int64_t m = 0;
   if (e == hipSuccess) {
-    select_layout(work, N, M, D, &b);
-    b.Lt = dL;
-    e = select_run(0, dP.as<DevParams>(), D, dX.as<double>(), N, M, tol, max_blocks, d0 ? d0c.as<double>() : nullptr, b, &m);
+    select_layout(work.d, N, M, D, &b);
+    b.Lt = dL.as<double>();
+    e = select_run(0, dP.as<DevParams>(), D, dX.as<double>(), N, M, tol, max_blocks, d0c.as<double>(), b, &m);
   }
   if (e == hipSuccess) e = hipDeviceSynchronize();
   std::vector<long long> hpiv((size_t)M);
   if (e == hipSuccess) e = hipMemcpy(hpiv.data(), b.piv, (size_t)M * sizeof(long long), hipMemcpyDeviceToHost);
   if (e == hipSuccess && m > 0) e = hipMemcpy(pivots, b.pv, (size_t)m * sizeof(double), hipMemcpyDeviceToHost);
   if (e == hipSuccess && U && m > 0) e = hipMemcpy(U, b.U, (size_t)m * D * sizeof(double), hipMemcpyDeviceToHost);
-  if (e == hipSuccess && Lt) e = hipMemcpy(Lt, dL, lbytes, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && Lt) e = hipMemcpy(Lt, dL.d, lbytes, hipMemcpyDeviceToHost);
   if (e == hipSuccess && d) e = hipMemcpy(d, b.d, (size_t)N * sizeof(double), hipMemcpyDeviceToHost);
   if (e == hipSuccess) e = hipMemcpy(trace, b.trace, sizeof(double), hipMemcpyDeviceToHost);
-  (void)hipFree(work);
-  (void)hipFree(dL);
   if (e != hipSuccess) return GOGP_EHIP;
   for (int64_t t = 0; t < m; ++t) idx[t] = (int64_t)hpiv[(size_t)t];
   *m_out = m;
@@ -1647,42 +1430,8 @@ extern "C" int gogp_test_select_run(int device, const gogp_test_kparams *kparams
 
 // ---- the small kernels that finish leave-one-out, multi-output and sparse evaluations, through their product launchers
 // (tests/test_finish_kernels.py): the kernels of loo.hip, multi_dots_kernel (multi.hip) and the element-wise, scalar and
-// Produce kernels of sparse.hip.  The rules of the hooks above: every argument is checked before the device is touched,
-// every array goes to the device whole and every in / out array comes back whole.
+// Produce kernels of sparse.hip.
 namespace {
-struct FinArr {
-  const double *h;
-  int64_t len;
-  bool out;
-};
-bool fin_have(std::initializer_list<FinArr> arrs) {
-  for (const FinArr &a : arrs)
-    if (!a.h || a.len <= 0) return false;
-  return true;
-}
-// uploads the arrays, runs `launch` on their device copies (in the order given) and brings the in / out ones back
-template <class F>
-int fin_run(int device, std::initializer_list<FinArr> arrs, F &&launch) {
-  if (!device_ok(device)) return GOGP_EHIP;
-  std::vector<DevCopy> dc(arrs.size());
-  std::vector<double *> d;
-  hipError_t e = hipSuccess;
-  size_t i = 0;
-  for (const FinArr &a : arrs) {
-    if (e == hipSuccess) e = dc[i].up(a.h, (size_t)a.len * sizeof(double));
-    d.push_back(dc[i++].as<double>());
-  }
-  if (e == hipSuccess) {
-    launch(d.data());
-    e = launched();
-  }
-  i = 0;
-  for (const FinArr &a : arrs) {
-    if (e == hipSuccess && a.out) e = dc[i].down(const_cast<double *>(a.h));
-    ++i;
-  }
-  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
-}
 bool fin_npad_ok(int64_t n, int64_t npad) {
   return npad > 0 && npad % PANEL == 0 && npad <= UP_NPAD_MAX && n >= 1 && n <= npad;
 }
@@ -1696,13 +1445,13 @@ extern "C" int gogp_test_loo_stats(int device, const double *Kinv, int64_t kinv_
                                    int64_t alpha_len, const double *y, int64_t y_len, int64_t n, int64_t npad, double *mu,
                                    int64_t mu_len, double *sigma, int64_t sigma_len, double *logp, int64_t logp_len, double *v,
                                    int64_t v_len, double *sc, int64_t sc_len, double *part, int64_t part_len) {
-  const std::initializer_list<FinArr> arrs = {{Kinv, kinv_len, false}, {alpha, alpha_len, false}, {y, y_len, false},
-                                              {mu, mu_len, true},      {sigma, sigma_len, true},  {logp, logp_len, true},
-                                              {v, v_len, true},        {sc, sc_len, true},        {part, part_len, true}};
-  if (!fin_have(arrs) || !fin_npad_ok(n, npad) || !covers(kinv_len, 0, ld, npad, npad, 1, 0)) return GOGP_EARG;
+  const std::vector<Arr> arrs = {rd(Kinv, kinv_len), rd(alpha, alpha_len), rd(y, y_len),
+                                           io(mu, mu_len),     io(sigma, sigma_len), io(logp, logp_len),
+                                           io(v, v_len),       io(sc, sc_len),       io(part, part_len)};
+  if (!have(arrs) || !fin_npad_ok(n, npad) || !covers(kinv_len, 0, ld, npad, npad, 1, 0)) return GOGP_EARG;
   if (alpha_len < n || y_len < n || mu_len < n || sigma_len < n || logp_len < n) return GOGP_EARG;
   if (v_len < npad || sc_len < npad || part_len < npad / PANEL) return GOGP_EARG;
-  return fin_run(device, arrs, [&](double **d) {
+  return run(device, arrs, [&](const Dev &d) {
     launch_loo_stats(0, d[0], ld, d[1], d[2], n, npad, d[3], d[4], d[5], d[6], d[7], d[8]);
   });
 }
@@ -1711,41 +1460,35 @@ extern "C" int gogp_test_loo_scale_symv(int device, const double *Kinv, int64_t 
                                         const double *sc, int64_t sc_len, const double *v, int64_t v_len, double *B,
                                         int64_t b_len, int64_t ldb, double *upart, int64_t upart_len, double *u,
                                         int64_t u_len) {
-  const std::initializer_list<FinArr> arrs = {{Kinv, kinv_len, false}, {sc, sc_len, false},      {v, v_len, false},
-                                              {B, b_len, true},        {upart, upart_len, true}, {u, u_len, true}};
-  if (!fin_have(arrs) || !fin_npad_ok(n, npad)) return GOGP_EARG;
+  const std::vector<Arr> arrs = {rd(Kinv, kinv_len), rd(sc, sc_len),       rd(v, v_len),
+                                           io(B, b_len),       io(upart, upart_len), io(u, u_len)};
+  if (!have(arrs) || !fin_npad_ok(n, npad)) return GOGP_EARG;
   if (!covers(kinv_len, 0, ld, npad, npad, 1, 0) || !covers(b_len, 0, ldb, npad, npad, 1, 0)) return GOGP_EARG;
   if (sc_len < npad || v_len < npad || u_len < npad || upart_len < npad / 64 * npad) return GOGP_EARG;
-  return fin_run(device, arrs, [&](double **d) {
+  return run(device, arrs, [&](const Dev &d) {
     launch_loo_scale_symv(0, d[0], ld, n, npad, d[1], d[2], d[3], ldb, d[4], d[5]);
   });
 }
 
 extern "C" int gogp_test_loo_rank2(int device, double *G, int64_t g_len, int64_t ld, int64_t n, int64_t npad, const double *u,
                                    int64_t u_len, const double *alpha, int64_t alpha_len) {
-  const std::initializer_list<FinArr> arrs = {{G, g_len, true}, {u, u_len, false}, {alpha, alpha_len, false}};
-  if (!fin_have(arrs) || !fin_npad_ok(n, npad) || !covers(g_len, 0, ld, npad, npad, 1, 0)) return GOGP_EARG;
+  const std::vector<Arr> arrs = {io(G, g_len), rd(u, u_len), rd(alpha, alpha_len)};
+  if (!have(arrs) || !fin_npad_ok(n, npad) || !covers(g_len, 0, ld, npad, npad, 1, 0)) return GOGP_EARG;
   if (u_len < npad || alpha_len < n) return GOGP_EARG;
-  return fin_run(device, arrs, [&](double **d) { launch_loo_rank2(0, d[0], ld, n, npad, d[1], d[2]); });
+  return run(device, arrs, [&](const Dev &d) { launch_loo_rank2(0, d[0], ld, n, npad, d[1], d[2]); });
 }
 
 // ---- the two kernels of leave-block-out cross-validation (blockcv.hip; tests/test_blockcv_kernels.py) ------------------
 namespace {
-// the block and group tables of `start` on the device, as api.hip lays them out: [F + 1 starts | ngroups + 1 firsts]
-struct BcvTables {
-  DevCopy d;
-  int ngroups = 0;
-  int64_t F = 0;
-  hipError_t up(const int64_t *start, int64_t F_) {
-    F = F_;
-    std::vector<int64_t> tab((size_t)(2 * F + 3));
-    for (int64_t f = 0; f <= F; ++f) tab[(size_t)f] = start[f];
-    ngroups = blockcv_pack(start, F, tab.data() + F + 1);
-    return d.up(tab.data(), (size_t)(F + 1 + ngroups + 1) * sizeof(int64_t));
-  }
-  const int64_t *bstart() const { return d.as<int64_t>(); }
-  const int64_t *gfirst() const { return d.as<int64_t>() + F + 1; }
-};
+// the block and group tables of `start` (checked), packed as api.hip lays them out on the device: [F + 1 starts | ngroups
+// + 1 firsts]; they travel as one read-only array
+std::vector<int64_t> bcv_tables(const int64_t *start, int64_t F, int *ngroups) {
+  std::vector<int64_t> tab((size_t)(2 * F + 3));
+  for (int64_t f = 0; f <= F; ++f) tab[(size_t)f] = start[f];
+  *ngroups = blockcv_pack(start, F, tab.data() + F + 1);
+  tab.resize((size_t)(F + 1 + *ngroups + 1));
+  return tab;
+}
 }  // namespace
 
 extern "C" int gogp_test_blockcv_groups(int device, const double *Kinv, int64_t kinv_len, int64_t ld, const double *alpha,
@@ -1753,154 +1496,143 @@ extern "C" int gogp_test_blockcv_groups(int device, const double *Kinv, int64_t 
                                         int64_t F, double *mu, int64_t mu_len, double *sigma, int64_t sigma_len, double *v,
                                         int64_t v_len, double *ones, int64_t ones_len, double *logp, int64_t logp_len,
                                         double *Sg, int64_t sg_len, int64_t *info, int64_t info_len) {
-  const std::initializer_list<FinArr> arrs = {{Kinv, kinv_len, false}, {alpha, alpha_len, false}, {y, y_len, false},
-                                              {mu, mu_len, true},      {sigma, sigma_len, true},  {v, v_len, true},
-                                              {ones, ones_len, true},  {logp, logp_len, true},    {Sg, sg_len, true}};
-  if (!fin_have(arrs) || !info || n < 1 || n > UP_NPAD_MAX || F < 1 || gogp_blockcv_check(start, F, n) != GOGP_OK)
+  std::vector<Arr> arrs = {rd(Kinv, kinv_len), rd(alpha, alpha_len), rd(y, y_len),       io(mu, mu_len), io(sigma, sigma_len),
+                           io(v, v_len),       io(ones, ones_len),   io(logp, logp_len), io(Sg, sg_len)};
+  if (!have(arrs) || !info || n < 1 || n > UP_NPAD_MAX || F < 1 || gogp_blockcv_check(start, F, n) != GOGP_OK)
     return GOGP_EARG;
   if (!covers(kinv_len, 0, ld, n, n, 1, 0) || alpha_len < n || y_len < n) return GOGP_EARG;
   if (mu_len < n || sigma_len < n || v_len < n || ones_len < n || logp_len < F) return GOGP_EARG;
-  std::vector<int64_t> first((size_t)F + 1);
-  const int64_t ng = blockcv_pack(start, F, first.data());
-  if (sg_len < ng * 128 * 128 || info_len < ng) return GOGP_EARG;
-  if (!device_ok(device)) return GOGP_EHIP;
-  BcvTables tab;
-  DevCopy dinfo;
-  hipError_t e = tab.up(start, F);
-  if (e == hipSuccess) e = dinfo.up(info, (size_t)info_len * sizeof(int64_t));
-  if (e != hipSuccess) return GOGP_EHIP;
-  return fin_run(device, arrs, [&](double **d) {
-    launch_blockcv_groups(0, d[0], ld, d[1], d[2], tab.bstart(), tab.gfirst(), tab.ngroups, d[3], d[4], d[5], d[6], d[7], d[8],
-                          dinfo.as<long long>());
-    if (launched() == hipSuccess) (void)dinfo.down(info);
+  int ng = 0;
+  const std::vector<int64_t> tab = bcv_tables(start, F, &ng);
+  if (sg_len < (int64_t)ng * 128 * 128 || info_len < ng) return GOGP_EARG;
+  arrs.push_back(rd(tab.data(), (int64_t)tab.size()));
+  arrs.push_back(io(info, info_len));
+  return run(device, arrs, [&](const Dev &d) {
+    const int64_t *dt = d.as<int64_t>(9);
+    launch_blockcv_groups(0, d[0], ld, d[1], d[2], dt, dt + F + 1, ng, d[3], d[4], d[5], d[6], d[7], d[8], d.as<long long>(10));
   });
 }
 
 extern "C" int gogp_test_blockcv_apply(int device, double *Q, int64_t q_len, int64_t q_off, int64_t ld, int64_t rows, int64_t n,
                                        const int64_t *start, int64_t F, const double *Sg, int64_t sg_len) {
-  const std::initializer_list<FinArr> arrs = {{Q, q_len, true}, {Sg, sg_len, false}};
-  if (!fin_have(arrs) || n < 1 || n > UP_NPAD_MAX || F < 1 || gogp_blockcv_check(start, F, n) != GOGP_OK) return GOGP_EARG;
+  std::vector<Arr> arrs = {io(Q, q_len), rd(Sg, sg_len)};
+  if (!have(arrs) || n < 1 || n > UP_NPAD_MAX || F < 1 || gogp_blockcv_check(start, F, n) != GOGP_OK) return GOGP_EARG;
   if (rows % 64 || rows < n || !covers(q_len, q_off, ld, rows, n, 1, 0)) return GOGP_EARG;
-  std::vector<int64_t> first((size_t)F + 1);
-  if (sg_len < (int64_t)blockcv_pack(start, F, first.data()) * 128 * 128) return GOGP_EARG;
-  if (!device_ok(device)) return GOGP_EHIP;
-  BcvTables tab;
-  if (tab.up(start, F) != hipSuccess) return GOGP_EHIP;
-  return fin_run(device, arrs, [&](double **d) {
-    launch_blockcv_apply(0, d[0] + q_off, ld, n, tab.bstart(), tab.gfirst(), tab.ngroups, d[1]);
+  int ng = 0;
+  const std::vector<int64_t> tab = bcv_tables(start, F, &ng);
+  if (sg_len < (int64_t)ng * 128 * 128) return GOGP_EARG;
+  arrs.push_back(rd(tab.data(), (int64_t)tab.size()));
+  return run(device, arrs, [&](const Dev &d) {
+    const int64_t *dt = d.as<int64_t>(2);
+    launch_blockcv_apply(0, d[0] + q_off, ld, n, dt, dt + F + 1, ng, d[1]);
   });
 }
 
 extern "C" int gogp_test_multi_dots(int device, const double *Yt, int64_t yt_len, const double *At, int64_t at_len, int64_t ld,
                                     int64_t n, int T, double *dots, int64_t dots_len) {
-  const std::initializer_list<FinArr> arrs = {{Yt, yt_len, false}, {At, at_len, false}, {dots, dots_len, true}};
-  if (!fin_have(arrs) || T < 1 || T > GOGP_MULTI_MAX_T || n < 1 || n > UP_NPAD_MAX || dots_len < T) return GOGP_EARG;
+  const std::vector<Arr> arrs = {rd(Yt, yt_len), rd(At, at_len), io(dots, dots_len)};
+  if (!have(arrs) || T < 1 || T > GOGP_MULTI_MAX_T || n < 1 || n > UP_NPAD_MAX || dots_len < T) return GOGP_EARG;
   if (!covers(yt_len, 0, ld, T, n, 1, 0) || !covers(at_len, 0, ld, T, n, 1, 0)) return GOGP_EARG;
-  return fin_run(device, arrs, [&](double **d) { launch_multi_dots(0, d[0], d[1], ld, n, T, d[2]); });
+  return run(device, arrs, [&](const Dev &d) { launch_multi_dots(0, d[0], d[1], ld, n, T, d[2]); });
 }
 
 extern "C" int gogp_test_sparse_finish_b(int device, const double *Bacc, int64_t bacc_len, int64_t Mp, double inv_s2, double *B,
                                          int64_t b_len) {
-  const std::initializer_list<FinArr> arrs = {{Bacc, bacc_len, false}, {B, b_len, true}};
-  if (!fin_have(arrs) || !fin_mp_ok(Mp) || !std::isfinite(inv_s2) || bacc_len < Mp * Mp || b_len < Mp * Mp) return GOGP_EARG;
-  return fin_run(device, arrs, [&](double **d) { launch_sparse_finish_b(0, d[0], Mp, inv_s2, d[1]); });
+  const std::vector<Arr> arrs = {rd(Bacc, bacc_len), io(B, b_len)};
+  if (!have(arrs) || !fin_mp_ok(Mp) || !std::isfinite(inv_s2) || bacc_len < Mp * Mp || b_len < Mp * Mp) return GOGP_EARG;
+  return run(device, arrs, [&](const Dev &d) { launch_sparse_finish_b(0, d[0], Mp, inv_s2, d[1]); });
 }
 
 extern "C" int gogp_test_sparse_copy_upper(int device, const double *src, int64_t src_len, int64_t Mp, double *dst,
                                            int64_t dst_len) {
-  const std::initializer_list<FinArr> arrs = {{src, src_len, false}, {dst, dst_len, true}};
-  if (!fin_have(arrs) || !fin_mp_ok(Mp) || src_len < Mp * Mp || dst_len < Mp * Mp) return GOGP_EARG;
-  return fin_run(device, arrs, [&](double **d) { launch_sparse_copy_upper(0, d[0], Mp, d[1]); });
+  const std::vector<Arr> arrs = {rd(src, src_len), io(dst, dst_len)};
+  if (!have(arrs) || !fin_mp_ok(Mp) || src_len < Mp * Mp || dst_len < Mp * Mp) return GOGP_EARG;
+  return run(device, arrs, [&](const Dev &d) { launch_sparse_copy_upper(0, d[0], Mp, d[1]); });
 }
 
 extern "C" int gogp_test_sparse_weights(int device, const double *B, int64_t b_len, const double *Binv, int64_t binv_len,
                                         const double *g, int64_t g_len, int64_t Mp, double s4, double *T, int64_t t_len,
                                         double *S, int64_t s_len) {
-  const std::initializer_list<FinArr> arrs = {
-      {B, b_len, false}, {Binv, binv_len, false}, {g, g_len, false}, {T, t_len, true}, {S, s_len, true}};
-  if (!fin_have(arrs) || !fin_mp_ok(Mp) || !std::isfinite(s4) || g_len < Mp) return GOGP_EARG;
+  const std::vector<Arr> arrs = {rd(B, b_len), rd(Binv, binv_len), rd(g, g_len), io(T, t_len), io(S, s_len)};
+  if (!have(arrs) || !fin_mp_ok(Mp) || !std::isfinite(s4) || g_len < Mp) return GOGP_EARG;
   if (b_len < Mp * Mp || binv_len < Mp * Mp || t_len < Mp * Mp || s_len < Mp * Mp) return GOGP_EARG;
-  return fin_run(device, arrs, [&](double **d) { launch_sparse_weights(0, d[0], d[1], d[2], Mp, s4, d[3], d[4]); });
+  return run(device, arrs, [&](const Dev &d) { launch_sparse_weights(0, d[0], d[1], d[2], Mp, s4, d[3], d[4]); });
 }
 
 extern "C" int gogp_test_sparse_multi_weights(int device, const double *B, int64_t b_len, const double *Binv, int64_t binv_len,
                                               const double *GG, int64_t gg_len, int64_t Mp, int T, double s4, double *Tm,
                                               int64_t tm_len, double *S, int64_t s_len) {
-  const std::initializer_list<FinArr> arrs = {
-      {B, b_len, false}, {Binv, binv_len, false}, {GG, gg_len, false}, {Tm, tm_len, true}, {S, s_len, true}};
-  if (!fin_have(arrs) || !fin_mp_ok(Mp) || !std::isfinite(s4) || T < 1 || T > GOGP_SPARSE_MULTI_MAX_T) return GOGP_EARG;
+  const std::vector<Arr> arrs = {rd(B, b_len), rd(Binv, binv_len), rd(GG, gg_len), io(Tm, tm_len), io(S, s_len)};
+  if (!have(arrs) || !fin_mp_ok(Mp) || !std::isfinite(s4) || T < 1 || T > GOGP_SPARSE_MULTI_MAX_T) return GOGP_EARG;
   if (b_len < Mp * Mp || binv_len < Mp * Mp || gg_len < Mp * Mp || tm_len < Mp * Mp || s_len < Mp * Mp) return GOGP_EARG;
-  return fin_run(device, arrs, [&](double **d) { launch_sparse_multi_weights(0, d[0], d[1], d[2], Mp, T, s4, d[3], d[4]); });
+  return run(device, arrs, [&](const Dev &d) { launch_sparse_multi_weights(0, d[0], d[1], d[2], Mp, T, s4, d[3], d[4]); });
 }
 
 extern "C" int gogp_test_sparse_scalars(int device, const double *C, int64_t c_len, const double *B, int64_t b_len,
                                         const double *Binv, int64_t binv_len, const double *r, int64_t r_len, const double *g,
                                         int64_t g_len, int64_t M, int64_t Mp, double *out, int64_t out_len) {
-  const std::initializer_list<FinArr> arrs = {{C, c_len, false}, {B, b_len, false}, {Binv, binv_len, false},
-                                              {r, r_len, false}, {g, g_len, false}, {out, out_len, true}};
-  if (!fin_have(arrs) || M < 1 || M > Mp || Mp > GOGP_SPARSE_MAX_M || r_len < M || g_len < M || out_len < 5) return GOGP_EARG;
+  const std::vector<Arr> arrs = {rd(C, c_len), rd(B, b_len), rd(Binv, binv_len), rd(r, r_len), rd(g, g_len), io(out, out_len)};
+  if (!have(arrs) || M < 1 || M > Mp || Mp > GOGP_SPARSE_MAX_M || r_len < M || g_len < M || out_len < 5) return GOGP_EARG;
   if (!covers(c_len, 0, Mp, M, M, 1, 0) || !covers(b_len, 0, Mp, M, M, 1, 0) || !covers(binv_len, 0, Mp, M, M, 1, 0))
     return GOGP_EARG;
-  return fin_run(device, arrs, [&](double **d) { launch_sparse_scalars(0, d[0], d[1], d[2], d[3], d[4], M, Mp, d[5]); });
+  return run(device, arrs, [&](const Dev &d) { launch_sparse_scalars(0, d[0], d[1], d[2], d[3], d[4], M, Mp, d[5]); });
 }
 
 extern "C" int gogp_test_sparse_sumsq(int device, const double *y, int64_t y_len, int64_t n, double *out, int64_t out_len) {
-  const std::initializer_list<FinArr> arrs = {{y, y_len, false}, {out, out_len, true}};
-  if (!fin_have(arrs) || n < 1 || n > FIN_ROWS_MAX || y_len < n) return GOGP_EARG;
-  return fin_run(device, arrs, [&](double **d) { launch_sparse_sumsq(0, d[0], n, d[1]); });
+  const std::vector<Arr> arrs = {rd(y, y_len), io(out, out_len)};
+  if (!have(arrs) || n < 1 || n > FIN_ROWS_MAX || y_len < n) return GOGP_EARG;
+  return run(device, arrs, [&](const Dev &d) { launch_sparse_sumsq(0, d[0], n, d[1]); });
 }
 
 extern "C" int gogp_test_sparse_predict(int device, const double *A, int64_t a_len, const double *V, int64_t v_len, int64_t ld,
                                         int64_t ncols, int64_t m, const double *prior, int64_t prior_len, const double *q,
                                         int64_t q_len, const double *dot, int64_t dot_len, double inv_s2, double *mu,
                                         int64_t mu_len, double *sigma, int64_t sigma_len) {
-  const std::initializer_list<FinArr> arrs = {{A, a_len, false},     {V, v_len, false},     {prior, prior_len, false},
-                                              {q, q_len, false},     {dot, dot_len, false}, {mu, mu_len, true},
-                                              {sigma, sigma_len, true}};
-  if (!fin_have(arrs) || m < 1 || m > FIN_M_MAX || !std::isfinite(inv_s2)) return GOGP_EARG;
+  const std::vector<Arr> arrs = {rd(A, a_len),     rd(V, v_len),   rd(prior, prior_len),   rd(q, q_len),
+                                 rd(dot, dot_len), io(mu, mu_len), io(sigma, sigma_len)};
+  if (!have(arrs) || m < 1 || m > FIN_M_MAX || !std::isfinite(inv_s2)) return GOGP_EARG;
   if (!covers(a_len, 0, ld, m, ncols, 1, 0) || !covers(v_len, 0, ld, m, ncols, 1, 0)) return GOGP_EARG;
   if (prior_len < m || q_len < m || dot_len < m || mu_len < m || sigma_len < m) return GOGP_EARG;
-  return fin_run(device, arrs, [&](double **d) {
+  return run(device, arrs, [&](const Dev &d) {
     launch_sparse_predict(0, d[0], d[1], ld, ncols, m, d[2], d[3], d[4], inv_s2, d[5], d[6]);
   });
 }
 
 extern "C" int gogp_test_sparse_multi_dots(int device, const double *Rt, int64_t rt_len, const double *Gt, int64_t gt_len,
                                            int64_t ld, int64_t M, int T, int tstride, double *out, int64_t out_len) {
-  const std::initializer_list<FinArr> arrs = {{Rt, rt_len, false}, {Gt, gt_len, false}, {out, out_len, true}};
-  if (!fin_have(arrs) || M < 1 || M > GOGP_SPARSE_MAX_M || T < 1 || T > GOGP_SPARSE_MULTI_MAX_T) return GOGP_EARG;
+  const std::vector<Arr> arrs = {rd(Rt, rt_len), rd(Gt, gt_len), io(out, out_len)};
+  if (!have(arrs) || M < 1 || M > GOGP_SPARSE_MAX_M || T < 1 || T > GOGP_SPARSE_MULTI_MAX_T) return GOGP_EARG;
   if (tstride < T || out_len < (int64_t)tstride + T) return GOGP_EARG;
   if (!covers(rt_len, 0, ld, T, M, 1, 0) || !covers(gt_len, 0, ld, T, M, 1, 0)) return GOGP_EARG;
-  return fin_run(device, arrs, [&](double **d) { launch_sparse_multi_dots(0, d[0], d[1], ld, M, T, tstride, d[2]); });
+  return run(device, arrs, [&](const Dev &d) { launch_sparse_multi_dots(0, d[0], d[1], ld, M, T, tstride, d[2]); });
 }
 
 extern "C" int gogp_test_sparse_multi_sumsq(int device, const double *Y, int64_t y_len, int64_t ldy, int64_t n, int T,
                                             double *out, int64_t out_len) {
-  const std::initializer_list<FinArr> arrs = {{Y, y_len, false}, {out, out_len, true}};
-  if (!fin_have(arrs) || n < 1 || n > FIN_ROWS_MAX || T < 1 || T > GOGP_SPARSE_MULTI_MAX_T || out_len < T) return GOGP_EARG;
+  const std::vector<Arr> arrs = {rd(Y, y_len), io(out, out_len)};
+  if (!have(arrs) || n < 1 || n > FIN_ROWS_MAX || T < 1 || T > GOGP_SPARSE_MULTI_MAX_T || out_len < T) return GOGP_EARG;
   if (!covers(y_len, 0, ldy, n, T, 1, 0)) return GOGP_EARG;  // (ldy < T is refused here)
-  return fin_run(device, arrs, [&](double **d) { launch_sparse_multi_sumsq(0, d[0], ldy, n, T, d[1]); });
+  return run(device, arrs, [&](const Dev &d) { launch_sparse_multi_sumsq(0, d[0], ldy, n, T, d[1]); });
 }
 
 extern "C" int gogp_test_sparse_multi_pad(int device, const double *Y, int64_t y_len, int64_t ldy, int64_t rows, int64_t T,
                                           int64_t kp, int64_t rpad, double *Yp, int64_t yp_len, int64_t ldp) {
-  const std::initializer_list<FinArr> arrs = {{Y, y_len, false}, {Yp, yp_len, true}};
-  if (!fin_have(arrs) || rpad < 1 || rpad > (1 << 16) || kp < 1 || kp > (1 << 12) || rows < 1 || rows > rpad || T < 1 || T > kp)
+  const std::vector<Arr> arrs = {rd(Y, y_len), io(Yp, yp_len)};
+  if (!have(arrs) || rpad < 1 || rpad > (1 << 16) || kp < 1 || kp > (1 << 12) || rows < 1 || rows > rpad || T < 1 || T > kp)
     return GOGP_EARG;
   if ((rpad * kp) % 256) return GOGP_EARG;  // the launcher starts whole workgroups of 256 elements or none at all
   if (!covers(y_len, 0, ldy, rows, T, 1, 0) || !covers(yp_len, 0, ldp, rpad, kp, 1, 0)) return GOGP_EARG;  // ldy < T, ldp < kp
-  return fin_run(device, arrs, [&](double **d) { launch_sparse_multi_pad(0, d[0], ldy, rows, T, kp, rpad, d[1], ldp); });
+  return run(device, arrs, [&](const Dev &d) { launch_sparse_multi_pad(0, d[0], ldy, rows, T, kp, rpad, d[1], ldp); });
 }
 
 extern "C" int gogp_test_sparse_multi_sigma(int device, const double *A, int64_t a_len, const double *V, int64_t v_len,
                                             int64_t ld, int64_t ncols, int64_t m, const double *prior, int64_t prior_len,
                                             const double *q, int64_t q_len, double *sigma, int64_t sigma_len) {
-  const std::initializer_list<FinArr> arrs = {
-      {A, a_len, false}, {V, v_len, false}, {prior, prior_len, false}, {q, q_len, false}, {sigma, sigma_len, true}};
-  if (!fin_have(arrs) || m < 1 || m > FIN_M_MAX) return GOGP_EARG;
+  const std::vector<Arr> arrs = {rd(A, a_len), rd(V, v_len), rd(prior, prior_len), rd(q, q_len), io(sigma, sigma_len)};
+  if (!have(arrs) || m < 1 || m > FIN_M_MAX) return GOGP_EARG;
   if (!covers(a_len, 0, ld, m, ncols, 1, 0) || !covers(v_len, 0, ld, m, ncols, 1, 0)) return GOGP_EARG;
   if (prior_len < m || q_len < m || sigma_len < m) return GOGP_EARG;
-  return fin_run(device, arrs, [&](double **d) {
+  return run(device, arrs, [&](const Dev &d) {
     launch_sparse_multi_sigma(0, d[0], d[1], ld, ncols, m, d[2], d[3], d[4]);
   });
 }
@@ -1989,8 +1721,6 @@ extern "C" int gogp_bench_sparse_syrk(int device, int64_t rows, int64_t M, int r
 }
 
 // ---- the kernels of the Laplace approximation (laplace.hip; tests/test_laplace_kernels.py) --------------------------------
-// The rules of the finishing hooks above: every argument is checked before the device is touched, every array goes to
-// the device whole and every in / out array comes back whole.
 namespace {
 bool lap_lik_known(int lik) { return lik == GOGP_LIK_BERNOULLI_LOGIT || lik == GOGP_LIK_POISSON_LOG; }
 }  // namespace
@@ -1999,34 +1729,32 @@ extern "C" int gogp_test_lap_site(int device, int lik, const double *f, int64_t 
                                   const double *a, int64_t a_len, int64_t n, int64_t npad, double *g, int64_t g_len,
                                   double *W, int64_t w_len, double *sw, int64_t sw_len, double *b, int64_t b_len, double *rho,
                                   int64_t rho_len, double *part, int64_t part_len, double *out, int64_t out_len) {
-  const std::initializer_list<FinArr> arrs = {{f, f_len, false},  {y, y_len, false}, {a, a_len, false},  {g, g_len, true},
-                                              {W, w_len, true},   {sw, sw_len, true}, {b, b_len, true},  {rho, rho_len, true},
-                                              {part, part_len, true}, {out, out_len, true}};
-  if (!fin_have(arrs) || !fin_npad_ok(n, npad) || !lap_lik_known(lik)) return GOGP_EARG;
+  const std::vector<Arr> arrs = {rd(f, f_len),   rd(y, y_len), rd(a, a_len),     io(g, g_len),       io(W, w_len),
+                                 io(sw, sw_len), io(b, b_len), io(rho, rho_len), io(part, part_len), io(out, out_len)};
+  if (!have(arrs) || !fin_npad_ok(n, npad) || !lap_lik_known(lik)) return GOGP_EARG;
   if (f_len < n || y_len < n || a_len < n) return GOGP_EARG;
   if (g_len < npad || w_len < npad || sw_len < npad || b_len < npad || rho_len < npad) return GOGP_EARG;
   if (part_len < 5 * (npad / PANEL) || out_len < 5) return GOGP_EARG;
-  return fin_run(device, arrs, [&](double **d) {
+  return run(device, arrs, [&](const Dev &d) {
     launch_lap_site(0, lik, d[0], d[1], d[2], n, npad, d[3], d[4], d[5], d[6], d[7], d[8], d[9]);
   });
 }
 
 extern "C" int gogp_test_lap_scale_gram(int device, double *A, int64_t a_len, int64_t ld, int64_t n, int64_t npad,
                                         const double *sw, int64_t sw_len, int64_t wcols) {
-  const std::initializer_list<FinArr> arrs = {{A, a_len, true}, {sw, sw_len, false}};
-  if (!fin_have(arrs) || !fin_npad_ok(n, npad) || !covers(a_len, 0, ld, npad, npad, 1, 0)) return GOGP_EARG;
+  const std::vector<Arr> arrs = {io(A, a_len), rd(sw, sw_len)};
+  if (!have(arrs) || !fin_npad_ok(n, npad) || !covers(a_len, 0, ld, npad, npad, 1, 0)) return GOGP_EARG;
   if (sw_len < n || wcols < 0 || wcols % 64) return GOGP_EARG;
-  return fin_run(device, arrs, [&](double **d) { launch_lap_scale_gram(0, 0, d[0], ld, n, npad, d[1], wcols); });
+  return run(device, arrs, [&](const Dev &d) { launch_lap_scale_gram(0, 0, d[0], ld, n, npad, d[1], wcols); });
 }
 
 extern "C" int gogp_test_lap_step(int device, const double *b, int64_t b_len, const double *sw, int64_t sw_len,
                                   const double *beta, int64_t beta_len, int64_t n, int64_t npad, double *rhs, int64_t rhs_len,
                                   double *a1, int64_t a1_len) {
-  const std::initializer_list<FinArr> arrs = {{b, b_len, false}, {sw, sw_len, false}, {beta, beta_len, false},
-                                              {rhs, rhs_len, true}, {a1, a1_len, true}};
-  if (!fin_have(arrs) || !fin_npad_ok(n, npad)) return GOGP_EARG;
+  const std::vector<Arr> arrs = {rd(b, b_len), rd(sw, sw_len), rd(beta, beta_len), io(rhs, rhs_len), io(a1, a1_len)};
+  if (!have(arrs) || !fin_npad_ok(n, npad)) return GOGP_EARG;
   if (b_len < n || sw_len < n || beta_len < n || rhs_len < npad || a1_len < npad) return GOGP_EARG;
-  return fin_run(device, arrs, [&](double **d) {
+  return run(device, arrs, [&](const Dev &d) {
     launch_lap_vec(0, nullptr, d[1], d[2], n, npad, d[3]);  // rhs = sw o beta
     launch_lap_vec(0, d[0], d[1], d[2], n, npad, d[4]);     // a1 = b - sw o beta
   });
@@ -2035,58 +1763,56 @@ extern "C" int gogp_test_lap_step(int device, const double *b, int64_t b_len, co
 extern "C" int gogp_test_lap_interp(int device, const double *a, int64_t a_len, const double *a1, int64_t a1_len,
                                     const double *f, int64_t f_len, const double *f1, int64_t f1_len, double t, int64_t n,
                                     int64_t npad, double *at, int64_t at_len, double *ft, int64_t ft_len) {
-  const std::initializer_list<FinArr> arrs = {{a, a_len, false}, {a1, a1_len, false}, {f, f_len, false},
-                                              {f1, f1_len, false}, {at, at_len, true}, {ft, ft_len, true}};
-  if (!fin_have(arrs) || !fin_npad_ok(n, npad) || !std::isfinite(t)) return GOGP_EARG;
+  const std::vector<Arr> arrs = {rd(a, a_len), rd(a1, a1_len), rd(f, f_len), rd(f1, f1_len), io(at, at_len), io(ft, ft_len)};
+  if (!have(arrs) || !fin_npad_ok(n, npad) || !std::isfinite(t)) return GOGP_EARG;
   if (a_len < n || a1_len < n || f_len < n || f1_len < n || at_len < npad || ft_len < npad) return GOGP_EARG;
-  return fin_run(device, arrs, [&](double **d) { launch_lap_interp(0, d[0], d[1], d[2], d[3], t, n, npad, d[4], d[5]); });
+  return run(device, arrs, [&](const Dev &d) { launch_lap_interp(0, d[0], d[1], d[2], d[3], t, n, npad, d[4], d[5]); });
 }
 
 extern "C" int gogp_test_lap_weight_vectors(int device, const double *Binv, int64_t binv_len, int64_t ld, const double *rho,
                                             int64_t rho_len, int64_t n, int64_t npad, double *sv, int64_t sv_len) {
-  const std::initializer_list<FinArr> arrs = {{Binv, binv_len, false}, {rho, rho_len, false}, {sv, sv_len, true}};
-  if (!fin_have(arrs) || !fin_npad_ok(n, npad) || !covers(binv_len, 0, ld, npad, npad, 1, 0)) return GOGP_EARG;
+  const std::vector<Arr> arrs = {rd(Binv, binv_len), rd(rho, rho_len), io(sv, sv_len)};
+  if (!have(arrs) || !fin_npad_ok(n, npad) || !covers(binv_len, 0, ld, npad, npad, 1, 0)) return GOGP_EARG;
   if (rho_len < n || sv_len < npad) return GOGP_EARG;
-  return fin_run(device, arrs, [&](double **d) { launch_lap_weight_vectors(0, d[0], ld, d[1], n, npad, d[2]); });
+  return run(device, arrs, [&](const Dev &d) { launch_lap_weight_vectors(0, d[0], ld, d[1], n, npad, d[2]); });
 }
 
 extern "C" int gogp_test_lap_symv_u(int device, const double *Binv, int64_t binv_len, int64_t ld, int64_t n, int64_t npad,
                                     const double *v, int64_t v_len, const double *sv, int64_t sv_len, const double *sw,
                                     int64_t sw_len, double *upart, int64_t upart_len, double *u, int64_t u_len) {
-  const std::initializer_list<FinArr> arrs = {{Binv, binv_len, false}, {v, v_len, false},       {sv, sv_len, false},
-                                              {sw, sw_len, false},     {upart, upart_len, true}, {u, u_len, true}};
-  if (!fin_have(arrs) || !fin_npad_ok(n, npad) || !covers(binv_len, 0, ld, npad, npad, 1, 0)) return GOGP_EARG;
+  const std::vector<Arr> arrs = {rd(Binv, binv_len), rd(v, v_len),         rd(sv, sv_len),
+                                 rd(sw, sw_len),     io(upart, upart_len), io(u, u_len)};
+  if (!have(arrs) || !fin_npad_ok(n, npad) || !covers(binv_len, 0, ld, npad, npad, 1, 0)) return GOGP_EARG;
   if (v_len < npad || sv_len < n || sw_len < n || u_len < npad || upart_len < npad / 64 * npad) return GOGP_EARG;
-  return fin_run(device, arrs, [&](double **d) { launch_lap_symv_u(0, d[0], ld, n, npad, d[1], d[2], d[3], d[4], d[5]); });
+  return run(device, arrs, [&](const Dev &d) { launch_lap_symv_u(0, d[0], ld, n, npad, d[1], d[2], d[3], d[4], d[5]); });
 }
 
 extern "C" int gogp_test_lap_weight(int device, double *G, int64_t g_len, int64_t ld, int64_t n, int64_t npad,
                                     const double *sw, int64_t sw_len, const double *u, int64_t u_len, const double *a,
                                     int64_t a_len) {
-  const std::initializer_list<FinArr> arrs = {{G, g_len, true}, {sw, sw_len, false}, {u, u_len, false}, {a, a_len, false}};
-  if (!fin_have(arrs) || !fin_npad_ok(n, npad) || !covers(g_len, 0, ld, npad, npad, 1, 0)) return GOGP_EARG;
+  const std::vector<Arr> arrs = {io(G, g_len), rd(sw, sw_len), rd(u, u_len), rd(a, a_len)};
+  if (!have(arrs) || !fin_npad_ok(n, npad) || !covers(g_len, 0, ld, npad, npad, 1, 0)) return GOGP_EARG;
   if (sw_len < n || u_len < n || a_len < n) return GOGP_EARG;
-  return fin_run(device, arrs, [&](double **d) { launch_lap_weight(0, d[0], ld, n, npad, d[1], d[2], d[3]); });
+  return run(device, arrs, [&](const Dev &d) { launch_lap_weight(0, d[0], ld, n, npad, d[1], d[2], d[3]); });
 }
 
 extern "C" int gogp_test_lap_colscale(int device, double *KsT, int64_t k_len, int64_t ld, int64_t rows, int64_t npad,
                                       const double *sw, int64_t sw_len) {
-  const std::initializer_list<FinArr> arrs = {{KsT, k_len, true}, {sw, sw_len, false}};
-  if (!fin_have(arrs) || npad <= 0 || npad % PANEL || npad > UP_NPAD_MAX || rows < 1 || rows > FIN_M_MAX) return GOGP_EARG;
+  const std::vector<Arr> arrs = {io(KsT, k_len), rd(sw, sw_len)};
+  if (!have(arrs) || npad <= 0 || npad % PANEL || npad > UP_NPAD_MAX || rows < 1 || rows > FIN_M_MAX) return GOGP_EARG;
   if (!covers(k_len, 0, ld, rows, npad, 1, 0) || sw_len < npad) return GOGP_EARG;
-  return fin_run(device, arrs, [&](double **d) { launch_lap_colscale(0, d[0], ld, rows, npad, d[1]); });
+  return run(device, arrs, [&](const Dev &d) { launch_lap_colscale(0, d[0], ld, rows, npad, d[1]); });
 }
 
 extern "C" int gogp_test_lap_mean(int device, int lik, const double *mu, int64_t mu_len, const double *sigma,
                                   int64_t sigma_len, int64_t m, double *mean, int64_t mean_len) {
-  const std::initializer_list<FinArr> arrs = {{mu, mu_len, false}, {sigma, sigma_len, false}, {mean, mean_len, true}};
-  if (!fin_have(arrs) || !lap_lik_known(lik) || m < 1 || m > FIN_M_MAX) return GOGP_EARG;
+  const std::vector<Arr> arrs = {rd(mu, mu_len), rd(sigma, sigma_len), io(mean, mean_len)};
+  if (!have(arrs) || !lap_lik_known(lik) || m < 1 || m > FIN_M_MAX) return GOGP_EARG;
   if (mu_len < m || sigma_len < m || mean_len < m) return GOGP_EARG;
-  return fin_run(device, arrs, [&](double **d) { launch_lap_mean(0, lik, d[0], d[1], m, d[2]); });
+  return run(device, arrs, [&](const Dev &d) { launch_lap_mean(0, lik, d[0], d[1], m, d[2]); });
 }
 
-// ---- the kernels of basis.hip through their product launchers (tests/test_basis_kernels.py).  The rules of the hooks
-// above.
+// ---- the kernels of basis.hip through their product launchers (tests/test_basis_kernels.py)
 namespace {
 bool basis_p_ok(int p) { return p >= 1 && p <= GOGP_BASIS_MAX_P; }
 }  // namespace
@@ -2096,42 +1822,38 @@ extern "C" int gogp_test_basis_gram_slabs(int64_t n) { return n >= 1 && n <= UP_
 extern "C" int gogp_test_basis_symm(int device, const double *Kinv, int64_t kinv_len, int64_t ldk, int64_t n, int64_t npad,
                                     const double *Ht, int64_t ht_len, int64_t ld, int p, double *part, int64_t part_len,
                                     double *Wt, int64_t wt_len) {
-  const std::initializer_list<FinArr> arrs = {{Kinv, kinv_len, false}, {Ht, ht_len, false}, {part, part_len, true},
-                                              {Wt, wt_len, true}};
-  if (!fin_have(arrs) || !fin_npad_ok(n, npad) || !basis_p_ok(p) || ld < npad || ldk < npad) return GOGP_EARG;
+  const std::vector<Arr> arrs = {rd(Kinv, kinv_len), rd(Ht, ht_len), io(part, part_len), io(Wt, wt_len)};
+  if (!have(arrs) || !fin_npad_ok(n, npad) || !basis_p_ok(p) || ld < npad || ldk < npad) return GOGP_EARG;
   const int64_t p4 = (p + 3) / 4 * 4;
   if (!covers(kinv_len, 0, ldk, npad, npad, 1, 0) || ht_len < (int64_t)p * ld || wt_len < p4 * ld ||
       part_len < (int64_t)basis_symm_slabs(n) * p4 * ld)
     return GOGP_EARG;
-  return fin_run(device, arrs, [&](double **d) { launch_basis_symm(0, d[0], ldk, n, npad, d[1], ld, p, d[2], d[3]); });
+  return run(device, arrs, [&](const Dev &d) { launch_basis_symm(0, d[0], ldk, n, npad, d[1], ld, p, d[2], d[3]); });
 }
 
 extern "C" int gogp_test_basis_gram(int device, const double *Ht, int64_t ht_len, const double *Wt, int64_t wt_len, int64_t ld,
                                     const double *alpha, int64_t alpha_len, int64_t n, int p, double *part, int64_t part_len,
                                     double *Ag, int64_t ag_len) {
-  const std::initializer_list<FinArr> arrs = {{Ht, ht_len, false}, {Wt, wt_len, false}, {alpha, alpha_len, false},
-                                              {part, part_len, true}, {Ag, ag_len, true}};
-  if (!fin_have(arrs) || !basis_p_ok(p) || n < 1 || n > UP_NPAD_MAX || ld < n) return GOGP_EARG;
+  const std::vector<Arr> arrs = {rd(Ht, ht_len), rd(Wt, wt_len), rd(alpha, alpha_len), io(part, part_len), io(Ag, ag_len)};
+  if (!have(arrs) || !basis_p_ok(p) || n < 1 || n > UP_NPAD_MAX || ld < n) return GOGP_EARG;
   const int64_t total = (int64_t)p * (p + 1);
   if (ht_len < (int64_t)p * ld || wt_len < (int64_t)p * ld || alpha_len < n || ag_len < total ||
       part_len < (int64_t)basis_gram_slabs(n) * total)
     return GOGP_EARG;
-  return fin_run(device, arrs, [&](double **d) { launch_basis_gram(0, d[0], d[1], ld, d[2], n, p, d[3], d[4]); });
+  return run(device, arrs, [&](const Dev &d) { launch_basis_gram(0, d[0], d[1], ld, d[2], n, p, d[3], d[4]); });
 }
 
 extern "C" int gogp_test_basis_finish(int device, const double *Ag, int64_t ag_len, int p, double *LA, int64_t la_len,
                                       double *Ainv, int64_t ainv_len, double *beta, int64_t beta_len, double *scal,
                                       int64_t scal_len, double *info, int64_t info_len) {
-  const std::initializer_list<FinArr> arrs = {{Ag, ag_len, false}, {LA, la_len, true}, {Ainv, ainv_len, true},
-                                              {beta, beta_len, true}, {scal, scal_len, true}};
-  if (!fin_have(arrs) || !info || info_len < 1 || !basis_p_ok(p)) return GOGP_EARG;
+  // the info word is a long long on the device: it travels in the caller's double and is converted on the way back
+  const std::vector<Arr> arrs = {rd(Ag, ag_len),     io(LA, la_len),     io(Ainv, ainv_len),
+                                 io(beta, beta_len), io(scal, scal_len), io(info, info_len)};
+  if (!have(arrs) || !basis_p_ok(p)) return GOGP_EARG;
   const int64_t pp = (int64_t)p * p;
   if (ag_len < pp + p || la_len < pp || ainv_len < pp || beta_len < p || scal_len < 2) return GOGP_EARG;
-  // the info word is a long long on the device: it travels in the caller's double and is converted on the way back
-  const std::initializer_list<FinArr> all = {{Ag, ag_len, false}, {LA, la_len, true}, {Ainv, ainv_len, true},
-                                             {beta, beta_len, true}, {scal, scal_len, true}, {info, info_len, true}};
-  const int rc = fin_run(device, all, [&](double **d) {
-    launch_basis_finish(0, d[0], p, d[1], d[2], d[3], d[4], reinterpret_cast<long long *>(d[5]));
+  const int rc = run(device, arrs, [&](const Dev &d) {
+    launch_basis_finish(0, d[0], p, d[1], d[2], d[3], d[4], d.as<long long>(5));
   });
   if (rc != GOGP_OK) return rc;
   long long word;
@@ -2143,13 +1865,12 @@ extern "C" int gogp_test_basis_finish(int device, const double *Ag, int64_t ag_l
 extern "C" int gogp_test_basis_cols(int device, const double *Wt, int64_t wt_len, int64_t ld, int64_t n, int p,
                                     const double *LA, int64_t la_len, const double *beta, int64_t beta_len,
                                     const double *alpha, int64_t alpha_len, double *Ct, int64_t ct_len) {
-  const std::initializer_list<FinArr> arrs = {{Wt, wt_len, false}, {LA, la_len, false}, {beta, beta_len, false},
-                                              {alpha, alpha_len, false}, {Ct, ct_len, true}};
-  if (!fin_have(arrs) || !basis_p_ok(p) || n < 1 || ld < n || ld > UP_NPAD_MAX) return GOGP_EARG;
+  const std::vector<Arr> arrs = {rd(Wt, wt_len), rd(LA, la_len), rd(beta, beta_len), rd(alpha, alpha_len), io(Ct, ct_len)};
+  if (!have(arrs) || !basis_p_ok(p) || n < 1 || ld < n || ld > UP_NPAD_MAX) return GOGP_EARG;
   const int64_t rows = (p + 1 + 3) / 4 * 4;
   if (wt_len < (int64_t)p * ld || la_len < (int64_t)p * p || beta_len < p || alpha_len < n || ct_len < rows * ld)
     return GOGP_EARG;
-  return fin_run(device, arrs, [&](double **d) { launch_basis_cols(0, d[0], ld, n, p, d[1], d[2], d[3], d[4]); });
+  return run(device, arrs, [&](const Dev &d) { launch_basis_cols(0, d[0], ld, n, p, d[1], d[2], d[3], d[4]); });
 }
 
 extern "C" int gogp_test_basis_predict(int device, const double *Hz, int64_t hz_len, const double *KW, int64_t kw_len,
@@ -2162,92 +1883,37 @@ extern "C" int gogp_test_basis_predict(int device, const double *Hz, int64_t hz_
   if (hz_len < m * p || kw_len < (m - 1) * ldkw + p || beta_len < p || ainv_len < (int64_t)p * p || mu0_len < m ||
       prior_len < m || q_len < m || mu_len < m || (ws && sigma_len < m))
     return GOGP_EARG;
-  if (ws) {
-    const std::initializer_list<FinArr> arrs = {{Hz, hz_len, false}, {KW, kw_len, false}, {beta, beta_len, false},
-                                                {Ainv, ainv_len, false}, {mu0, mu0_len, false}, {prior, prior_len, false},
-                                                {q, q_len, false}, {mu, mu_len, true}, {sigma, sigma_len, true}};
-    if (!fin_have(arrs)) return GOGP_EARG;
-    return fin_run(device, arrs, [&](double **d) {
-      launch_basis_predict(0, d[0], d[1], ldkw, m, p, d[2], d[3], d[4], d[5], d[6], d[7], d[8]);
-    });
-  }
-  const std::initializer_list<FinArr> arrs = {{Hz, hz_len, false}, {KW, kw_len, false}, {beta, beta_len, false},
-                                              {Ainv, ainv_len, false}, {mu0, mu0_len, false}, {prior, prior_len, false},
-                                              {q, q_len, false}, {mu, mu_len, true}};
-  if (!fin_have(arrs)) return GOGP_EARG;
-  return fin_run(device, arrs, [&](double **d) {
-    launch_basis_predict(0, d[0], d[1], ldkw, m, p, d[2], d[3], d[4], d[5], d[6], d[7], nullptr);
+  const std::vector<Arr> arrs = {rd(Hz, hz_len),   rd(KW, kw_len),       rd(beta, beta_len), rd(Ainv, ainv_len),
+                                 rd(mu0, mu0_len), rd(prior, prior_len), rd(q, q_len),       io(mu, mu_len),
+                                 opt(io(sigma, sigma_len))};  // no sigma: the launcher gets nullptr
+  if (!have(arrs)) return GOGP_EARG;
+  return run(device, arrs, [&](const Dev &d) {
+    launch_basis_predict(0, d[0], d[1], ldkw, m, p, d[2], d[3], d[4], d[5], d[6], d[7], d[8]);
   });
 }
 
-// ---- the kernels of the per-observation noise variances (noisevar.hip; tests/test_noise_variances_kernels.py), under the
-// rules of the finishing hooks above ------------------------------------------------------------------------------------
+// ---- the kernels of the per-observation noise variances (noisevar.hip; tests/test_noise_variances_kernels.py) ----
 extern "C" int gogp_test_nv_diag_add(int device, double *A, int64_t a_len, int64_t ld, int64_t n, int64_t npad,
                                      const double *v, int64_t v_len, int64_t wcols) {
-  const std::initializer_list<FinArr> arrs = {{A, a_len, true}, {v, v_len, false}};
-  if (!fin_have(arrs) || !fin_npad_ok(n, npad) || !covers(a_len, 0, ld, npad, npad, 1, 0)) return GOGP_EARG;
+  const std::vector<Arr> arrs = {io(A, a_len), rd(v, v_len)};
+  if (!have(arrs) || !fin_npad_ok(n, npad) || !covers(a_len, 0, ld, npad, npad, 1, 0)) return GOGP_EARG;
   if (v_len < n || wcols < 0 || wcols % 64) return GOGP_EARG;
-  return fin_run(device, arrs, [&](double **d) { launch_nv_diag_add(0, 0, d[0], ld, n, d[1], wcols); });
+  return run(device, arrs, [&](const Dev &d) { launch_nv_diag_add(0, 0, d[0], ld, n, d[1], wcols); });
 }
 
 extern "C" int gogp_test_nv_gradient(int device, const double *Kinv, int64_t kinv_len, int64_t ld, const double *alpha,
                                      int64_t alpha_len, int64_t n, int64_t npad, double *dv, int64_t dv_len) {
-  const std::initializer_list<FinArr> arrs = {{Kinv, kinv_len, false}, {alpha, alpha_len, false}, {dv, dv_len, true}};
-  if (!fin_have(arrs) || !fin_npad_ok(n, npad) || !covers(kinv_len, 0, ld, npad, npad, 1, 0)) return GOGP_EARG;
+  const std::vector<Arr> arrs = {rd(Kinv, kinv_len), rd(alpha, alpha_len), io(dv, dv_len)};
+  if (!have(arrs) || !fin_npad_ok(n, npad) || !covers(kinv_len, 0, ld, npad, npad, 1, 0)) return GOGP_EARG;
   if (alpha_len < n || dv_len < n) return GOGP_EARG;
-  return fin_run(device, arrs, [&](double **d) { launch_nv_gradient(0, d[0], ld, d[1], n, d[2]); });
+  return run(device, arrs, [&](const Dev &d) { launch_nv_gradient(0, d[0], ld, d[1], n, d[2]); });
 }
 
 // ---- the kernels of the sharded path (dist2d.hip and the "helpers of the sharded evaluation" of solve.hip) and the rest of
 // solve.hip -- the LML scalars, the fp64 trace, the layout kernels around the factor, the one-line vector kernels --
-// through their product launchers (tests/test_shard_kernels.py).  The rules of the hooks above: every argument is checked
-// before the device is touched, every array goes to the device whole and every in / out array comes back whole.  Arrays
-// typed `void *` hold doubles (precision 64) or floats (32); lengths count elements.
+// through their product launchers (tests/test_shard_kernels.py).  Arrays typed `void *` hold doubles (precision 64) or
+// floats (32); lengths count elements.
 namespace {
-struct ShArr {
-  const void *h;
-  int64_t len;
-  int es;  // bytes per element
-  bool out;
-  bool opt = false;  // may be NULL (with length 0)
-};
-bool sh_have(std::initializer_list<ShArr> arrs) {
-  for (const ShArr &a : arrs) {
-    if (a.opt && !a.h) {
-      if (a.len != 0) return false;
-      continue;
-    }
-    if (!a.h || a.len <= 0) return false;
-  }
-  return true;
-}
-template <class F>
-int sh_run(int device, std::initializer_list<ShArr> arrs, F &&launch) {
-  if (!device_ok(device)) return GOGP_EHIP;
-  std::vector<DevCopy> dc(arrs.size());
-  std::vector<char *> d;
-  hipError_t e = hipSuccess;
-  size_t i = 0;
-  for (const ShArr &a : arrs) {
-    if (e == hipSuccess) e = dc[i].up(a.h, a.h ? (size_t)a.len * (size_t)a.es : 0);
-    d.push_back(dc[i++].d);
-  }
-  if (e == hipSuccess) {
-    launch(d.data());
-    tl_batch.k = 1;
-    tl_batch.stride = 0;
-    e = launched();
-  }
-  i = 0;
-  for (const ShArr &a : arrs) {
-    if (e == hipSuccess && a.out && a.h) e = dc[i].down(const_cast<void *>(a.h));
-    ++i;
-  }
-  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
-}
-#define SH_D(i) reinterpret_cast<double *>(d[i])
-#define SH_F(i) reinterpret_cast<float *>(d[i])
-constexpr int64_t SH_COUNT_MAX = 1 << 26;
 // the block map of rank (pr, pc) of a Pr x Pc grid with tiles of 2^nb_shift; false for what no rank can be
 bool sh_map(int nb_shift, int Pr, int Pc, int pr, int pc, BlockMap *m) {
   if (nb_shift < 5 || nb_shift > 10 || Pr < 1 || Pr > 8 || Pc < 1 || Pc > 8 || pr < 0 || pr >= Pr || pc < 0 || pc >= Pc)
@@ -2263,19 +1929,6 @@ bool sh_map(int nb_shift, int Pr, int Pc, int pr, int pc, BlockMap *m) {
 bool sh_tiles(int mloc, int nloc, const BlockMap &m) {
   return mloc >= 1 && nloc >= 1 && mloc <= 64 && nloc <= 64 && (int64_t)mloc * m.Pr == (int64_t)nloc * m.Pc;
 }
-// candidate batch of a launcher that reads tl_batch: k == 1 (stride ignored) or 2 .. 16 candidates `bstride` elements apart
-bool sh_batch(int precision, int k, int64_t *bstride) {
-  if (k < 1 || k > GOGP_MAX_CANDIDATES) return false;
-  if (k == 1) {
-    *bstride = 0;
-    return true;
-  }
-  return precision == 64 && *bstride > 0 && *bstride % 2 == 0;  // the float launchers do not batch
-}
-void sh_set_batch(int k, int64_t bstride) {
-  tl_batch.k = k;
-  tl_batch.stride = (long)(bstride * 8);
-}
 }  // namespace
 
 extern "C" int64_t gogp_test_chunk_tdot_scratch(int64_t rows, int nb) {
@@ -2285,39 +1938,38 @@ extern "C" int64_t gogp_test_chunk_tdot_scratch(int64_t rows, int nb) {
 
 extern "C" int gogp_test_gather_rows(int device, const double *y, int64_t y_len, int64_t rows, int nb_shift, int Pr, int Pc,
                                      int pr, int pc, double *yloc, int64_t yloc_len) {
-  const std::initializer_list<ShArr> arrs = {{y, y_len, 8, false}, {yloc, yloc_len, 8, true}};
+  const std::vector<Arr> arrs = {rd(y, y_len), io(yloc, yloc_len)};
   BlockMap m;
-  if (!sh_have(arrs) || !sh_map(nb_shift, Pr, Pc, pr, pc, &m)) return GOGP_EARG;
+  if (!have(arrs) || !sh_map(nb_shift, Pr, Pc, pr, pc, &m)) return GOGP_EARG;
   if (rows < 1 || rows > SH_COUNT_MAX || rows % (1 << nb_shift) || yloc_len < rows || y_len < m.grow(rows - 1) + 1)
     return GOGP_EARG;
-  return sh_run(device, arrs, [&](char **d) { launch_gather_rows(0, SH_D(0), SH_D(1), rows, m); });
+  return run(device, arrs, [&](const Dev &d) { launch_gather_rows(0, d[0], d[1], rows, m); });
 }
 
 extern "C" int gogp_test_gather_x(int device, const double *X, int64_t x_len, const double *a, int64_t a_len, int D, int64_t n,
                                   int64_t rows, int nb_shift, int Pr, int Pc, int pr, int pc, double *Xloc, int64_t xloc_len,
                                   double *aloc, int64_t aloc_len) {
-  const std::initializer_list<ShArr> arrs = {{X, x_len, 8, false}, {a, a_len, 8, false}, {Xloc, xloc_len, 8, true},
-                                             {aloc, aloc_len, 8, true}};
+  const std::vector<Arr> arrs = {rd(X, x_len), rd(a, a_len), io(Xloc, xloc_len), io(aloc, aloc_len)};
   BlockMap m;
-  if (!sh_have(arrs) || !sh_map(nb_shift, Pr, Pc, pr, pc, &m) || D < 1 || D > GOGP_MAX_NDIM) return GOGP_EARG;
+  if (!have(arrs) || !sh_map(nb_shift, Pr, Pc, pr, pc, &m) || D < 1 || D > GOGP_MAX_NDIM) return GOGP_EARG;
   if (rows < 1 || rows > SH_COUNT_MAX || rows % (1 << nb_shift) || n < 1 || n > SH_COUNT_MAX) return GOGP_EARG;
   if (x_len < n * D || a_len < n || xloc_len < rows * D || aloc_len < rows) return GOGP_EARG;
-  return sh_run(device, arrs, [&](char **d) { launch_gather_x(0, SH_D(0), SH_D(1), D, n, rows, m, SH_D(2), SH_D(3)); });
+  return run(device, arrs, [&](const Dev &d) { launch_gather_x(0, d[0], d[1], D, n, rows, m, d[2], d[3]); });
 }
 
 extern "C" int gogp_test_scatter_tile(int device, int precision, const void *src, int64_t src_len, int nb, int64_t n,
                                       int64_t row0, int64_t col0, int diag, int64_t r0, double *dst, int64_t dst_len) {
   if (!prec_ok(precision)) return GOGP_EARG;
-  const std::initializer_list<ShArr> arrs = {{src, src_len, precision / 8, false}, {dst, dst_len, 8, true}};
-  if (!sh_have(arrs) || nb < 1 || nb > 1024 || n < 1 || n > TH_NPAD_MAX || (diag != 0 && diag != 1)) return GOGP_EARG;
+  const std::vector<Arr> arrs = {rd(src, src_len, precision / 8), io(dst, dst_len)};
+  if (!have(arrs) || nb < 1 || nb > 1024 || n < 1 || n > TH_NPAD_MAX || (diag != 0 && diag != 1)) return GOGP_EARG;
   if (r0 < 0 || row0 < r0 || row0 >= n || col0 < 0 || col0 >= n || src_len < (int64_t)nb * nb) return GOGP_EARG;
   const int64_t rend = row0 + nb < n ? row0 + nb : n;  // dst is the band of the rows from r0 on
   if (dst_len < (rend - r0) * n) return GOGP_EARG;
-  return sh_run(device, arrs, [&](char **d) {
+  return run(device, arrs, [&](const Dev &d) {
     if (precision == 64)
-      launch_scatter_tile(0, SH_D(0), nb, SH_D(1) - r0 * n, n, row0, col0, diag);
+      launch_scatter_tile(0, d[0], nb, d[1] - r0 * n, n, row0, col0, diag);
     else
-      launch_scatter_tile(0, SH_F(0), nb, SH_D(1) - r0 * n, n, row0, col0, diag);
+      launch_scatter_tile(0, d.f32(0), nb, d[1] - r0 * n, n, row0, col0, diag);
   });
 }
 
@@ -2325,118 +1977,117 @@ extern "C" int gogp_test_gather_rows_of_l(int device, int precision, const void 
                                           int nb_shift, int Pr, int Pc, int pr, int pc, const int64_t *rows, int64_t rows_len,
                                           int64_t n, int diag_only, double *out, int64_t out_len) {
   if (!prec_ok(precision) || (diag_only != 0 && diag_only != 1)) return GOGP_EARG;
-  const std::initializer_list<ShArr> arrs = {{Lch, lch_len, precision / 8, false}, {rows, rows_len, 8, false, diag_only == 1},
-                                             {out, out_len, 8, true}};
+  const std::vector<Arr> arrs = {rd(Lch, lch_len, precision / 8), opt(rd(rows, rows_len), diag_only == 1), io(out, out_len)};
   BlockMap m;
-  if (!sh_have(arrs) || !sh_map(nb_shift, Pr, Pc, pr, pc, &m) || !sh_tiles(mloc, nloc, m)) return GOGP_EARG;
+  if (!have(arrs) || !sh_map(nb_shift, Pr, Pc, pr, pc, &m) || !sh_tiles(mloc, nloc, m)) return GOGP_EARG;
   const int64_t nb = 1 << nb_shift;
   if (diag_only && rows) return GOGP_EARG;
   if (n < 1 || n > (int64_t)mloc * Pr * nb || lch_len < (int64_t)nloc * mloc * nb * nb) return GOGP_EARG;
   if (rows_len > 65535 || out_len < (diag_only ? n : rows_len * n)) return GOGP_EARG;
   for (int64_t k = 0; k < rows_len; ++k)
     if (rows[k] < 0 || rows[k] >= n) return GOGP_EARG;  // the kernel indexes the chunks with them
-  return sh_run(device, arrs, [&](char **d) {
-    const int64_t *dr = reinterpret_cast<const int64_t *>(d[1]);
+  return run(device, arrs, [&](const Dev &d) {
+    const int64_t *dr = d.as<int64_t>(1);
     if (precision == 64)
-      launch_gather_rows_of_l(0, SH_D(0), mloc, nloc, (int)nb, m, dr, rows_len, n, diag_only, SH_D(2));
+      launch_gather_rows_of_l(0, d[0], mloc, nloc, (int)nb, m, dr, rows_len, n, diag_only, d[2]);
     else
-      launch_gather_rows_of_l(0, SH_F(0), mloc, nloc, (int)nb, m, dr, rows_len, n, diag_only, SH_D(2));
+      launch_gather_rows_of_l(0, d.f32(0), mloc, nloc, (int)nb, m, dr, rows_len, n, diag_only, d[2]);
   });
 }
 
 extern "C" int gogp_test_scatter_stage(int device, int precision, const double *stage, int64_t stage_len, int64_t lds_,
                                        void *Lch, int64_t lch_len, int nloc, int mloc, int bi, int nb) {
   if (!prec_ok(precision)) return GOGP_EARG;
-  const std::initializer_list<ShArr> arrs = {{stage, stage_len, 8, false}, {Lch, lch_len, precision / 8, true}};
-  if (!sh_have(arrs) || nloc < 1 || nloc > 64 || mloc < 1 || mloc > 64 || bi < 0 || bi >= mloc || nb < 1 || nb > 1024)
+  const std::vector<Arr> arrs = {rd(stage, stage_len), io(Lch, lch_len, precision / 8)};
+  if (!have(arrs) || nloc < 1 || nloc > 64 || mloc < 1 || mloc > 64 || bi < 0 || bi >= mloc || nb < 1 || nb > 1024)
     return GOGP_EARG;
   if (!covers(stage_len, 0, lds_, nb, (int64_t)nloc * nb, 1, 0) || lch_len < (int64_t)nloc * mloc * nb * nb) return GOGP_EARG;
-  return sh_run(device, arrs, [&](char **d) {
+  return run(device, arrs, [&](const Dev &d) {
     if (precision == 64)
-      launch_scatter_stage(0, SH_D(0), lds_, SH_D(1), nloc, mloc, bi, nb);
+      launch_scatter_stage(0, d[0], lds_, d[1], nloc, mloc, bi, nb);
     else
-      launch_scatter_stage(0, SH_D(0), lds_, SH_F(1), nloc, mloc, bi, nb);
+      launch_scatter_stage(0, d[0], lds_, d.f32(1), nloc, mloc, bi, nb);
   });
 }
 
 extern "C" int gogp_test_transpose_rect(int device, int precision, const void *src, int64_t src_len, int64_t lds_, void *dst,
                                         int64_t dst_len, int64_t ldd, int64_t rows, int cols) {
   if (!prec_ok(precision)) return GOGP_EARG;
-  const std::initializer_list<ShArr> arrs = {{src, src_len, precision / 8, false}, {dst, dst_len, precision / 8, true}};
-  if (!sh_have(arrs) || rows < 32 || cols < 32 || rows % 32 || cols % 32 || rows > (1 << 16) || cols > (1 << 16))
+  const std::vector<Arr> arrs = {rd(src, src_len, precision / 8), io(dst, dst_len, precision / 8)};
+  if (!have(arrs) || rows < 32 || cols < 32 || rows % 32 || cols % 32 || rows > (1 << 16) || cols > (1 << 16))
     return GOGP_EARG;
   if (!covers(src_len, 0, lds_, rows, cols, 1, 0) || !covers(dst_len, 0, ldd, cols, rows, 1, 0)) return GOGP_EARG;
-  return sh_run(device, arrs, [&](char **d) {
+  return run(device, arrs, [&](const Dev &d) {
     if (precision == 64)
-      launch_transpose_rect(0, SH_D(0), lds_, SH_D(1), ldd, rows, cols);
+      launch_transpose_rect(0, d[0], lds_, d[1], ldd, rows, cols);
     else
-      launch_transpose_rect(0, SH_F(0), lds_, SH_F(1), ldd, rows, cols);
+      launch_transpose_rect(0, d.f32(0), lds_, d.f32(1), ldd, rows, cols);
   });
 }
 
 extern "C" int gogp_test_transpose_sq(int device, int precision, const void *src, int64_t src_len, int64_t lds_, void *dst,
                                       int64_t dst_len, int64_t ldd, int n) {
   if (!prec_ok(precision)) return GOGP_EARG;
-  const std::initializer_list<ShArr> arrs = {{src, src_len, precision / 8, false}, {dst, dst_len, precision / 8, true}};
-  if (!sh_have(arrs) || n < 32 || n % 32 || n > (1 << 13)) return GOGP_EARG;
+  const std::vector<Arr> arrs = {rd(src, src_len, precision / 8), io(dst, dst_len, precision / 8)};
+  if (!have(arrs) || n < 32 || n % 32 || n > (1 << 13)) return GOGP_EARG;
   if (!covers(src_len, 0, lds_, n, n, 1, 0) || !covers(dst_len, 0, ldd, n, n, 1, 0)) return GOGP_EARG;
-  return sh_run(device, arrs, [&](char **d) {
+  return run(device, arrs, [&](const Dev &d) {
     if (precision == 64)
-      launch_transpose_sq(0, SH_D(0), lds_, SH_D(1), ldd, n);
+      launch_transpose_sq(0, d[0], lds_, d[1], ldd, n);
     else
-      launch_transpose_sq(0, SH_F(0), lds_, SH_F(1), ldd, n);
+      launch_transpose_sq(0, d.f32(0), lds_, d.f32(1), ldd, n);
   });
 }
 
 extern "C" int gogp_test_copy_block(int device, double *dst, int64_t dst_len, const double *src, int64_t src_len, int64_t ld,
                                     int nb, int64_t rows) {
-  const std::initializer_list<ShArr> arrs = {{dst, dst_len, 8, true}, {src, src_len, 8, false}};
-  if (!sh_have(arrs) || nb < 1 || nb > 1024 || rows < 1 || rows > (1 << 16)) return GOGP_EARG;
+  const std::vector<Arr> arrs = {io(dst, dst_len), rd(src, src_len)};
+  if (!have(arrs) || nb < 1 || nb > 1024 || rows < 1 || rows > (1 << 16)) return GOGP_EARG;
   if (dst_len < rows * nb || !covers(src_len, 0, ld, rows, nb, 1, 0)) return GOGP_EARG;
-  return sh_run(device, arrs, [&](char **d) { launch_copy_block(0, SH_D(0), SH_D(1), ld, nb, rows); });
+  return run(device, arrs, [&](const Dev &d) { launch_copy_block(0, d[0], d[1], ld, nb, rows); });
 }
 
 extern "C" int gogp_test_residual_block(int device, int precision, void *W, int64_t w_len, const void *Ks, int64_t ks_len,
                                         const double *U, int64_t u_len, int64_t ld, const double *recv, int64_t recv_len,
                                         int nrecv, int nb, int64_t rows) {
   if (!prec_ok(precision) || nrecv < 0 || nrecv > 64) return GOGP_EARG;
-  const std::initializer_list<ShArr> arrs = {{W, w_len, precision / 8, true}, {Ks, ks_len, precision / 8, false},
-                                             {U, u_len, 8, false}, {recv, recv_len, 8, false, nrecv == 0}};
-  if (!sh_have(arrs) || nb < 1 || nb > 1024 || rows < 1 || rows > (1 << 16) || (nrecv == 0 && recv)) return GOGP_EARG;
+  const std::vector<Arr> arrs = {io(W, w_len, precision / 8), rd(Ks, ks_len, precision / 8), rd(U, u_len),
+                                 opt(rd(recv, recv_len), nrecv == 0)};
+  if (!have(arrs) || nb < 1 || nb > 1024 || rows < 1 || rows > (1 << 16) || (nrecv == 0 && recv)) return GOGP_EARG;
   if (w_len < rows * nb || !covers(ks_len, 0, ld, rows, nb, 1, 0) || !covers(u_len, 0, ld, rows, nb, 1, 0) ||
       recv_len < (int64_t)nrecv * rows * nb)
     return GOGP_EARG;
-  return sh_run(device, arrs, [&](char **d) {
+  return run(device, arrs, [&](const Dev &d) {
     if (precision == 64)
-      launch_residual_block(0, SH_D(0), SH_D(1), SH_D(2), ld, SH_D(3), nrecv, nb, rows);
+      launch_residual_block(0, d[0], d[1], d[2], ld, d[3], nrecv, nb, rows);
     else
-      launch_residual_block(0, SH_F(0), SH_F(1), SH_D(2), ld, SH_D(3), nrecv, nb, rows);
+      launch_residual_block(0, d.f32(0), d.f32(1), d[2], ld, d[3], nrecv, nb, rows);
   });
 }
 
 extern "C" int gogp_test_pack_blocks(int device, double *dst, int64_t dst_len, const double *src, int64_t src_len, int nblk,
                                      int64_t blk, int first, int stride) {
-  const std::initializer_list<ShArr> arrs = {{dst, dst_len, 8, true}, {src, src_len, 8, false}};
-  if (!sh_have(arrs) || nblk < 1 || nblk > 65535 || blk < 2 || blk % 2 || blk > SH_COUNT_MAX || first < 0 || stride < 1 ||
+  const std::vector<Arr> arrs = {io(dst, dst_len), rd(src, src_len)};
+  if (!have(arrs) || nblk < 1 || nblk > 65535 || blk < 2 || blk % 2 || blk > SH_COUNT_MAX || first < 0 || stride < 1 ||
       first > 4096 || stride > 4096)
     return GOGP_EARG;
   if (dst_len < (int64_t)nblk * blk || src_len < ((int64_t)first + (int64_t)(nblk - 1) * stride + 1) * blk) return GOGP_EARG;
-  return sh_run(device, arrs, [&](char **d) { launch_pack_blocks(0, SH_D(0), SH_D(1), nblk, blk, first, stride); });
+  return run(device, arrs, [&](const Dev &d) { launch_pack_blocks(0, d[0], d[1], nblk, blk, first, stride); });
 }
 
 extern "C" int gogp_test_convert_block(int device, int precision, int precision2, const void *src, int64_t src_len,
                                        int64_t lds_, void *dst, int64_t dst_len, int64_t ldd, int rows, int cols) {
   if (!prec_ok(precision) || !prec_ok(precision2) || (precision == 32 && precision2 == 32)) return GOGP_EARG;
-  const std::initializer_list<ShArr> arrs = {{src, src_len, precision / 8, false}, {dst, dst_len, precision2 / 8, true}};
-  if (!sh_have(arrs) || rows < 1 || rows > (1 << 16) || cols < 1 || cols > (1 << 16)) return GOGP_EARG;
+  const std::vector<Arr> arrs = {rd(src, src_len, precision / 8), io(dst, dst_len, precision2 / 8)};
+  if (!have(arrs) || rows < 1 || rows > (1 << 16) || cols < 1 || cols > (1 << 16)) return GOGP_EARG;
   if (!covers(src_len, 0, lds_, rows, cols, 1, 0) || !covers(dst_len, 0, ldd, rows, cols, 1, 0)) return GOGP_EARG;
-  return sh_run(device, arrs, [&](char **d) {
+  return run(device, arrs, [&](const Dev &d) {
     if (precision == 32)
-      launch_convert_block(0, SH_F(0), lds_, SH_D(1), ldd, rows, cols);
+      launch_convert_block(0, d.f32(0), lds_, d[1], ldd, rows, cols);
     else if (precision2 == 32)
-      launch_convert_block(0, SH_D(0), lds_, SH_F(1), ldd, rows, cols);
+      launch_convert_block(0, d[0], lds_, d.f32(1), ldd, rows, cols);
     else
-      launch_convert_block(0, (const double *)SH_D(0), lds_, SH_D(1), ldd, rows, cols);
+      launch_convert_block(0, (const double *)d[0], lds_, d[1], ldd, rows, cols);
   });
 }
 
@@ -2444,16 +2095,15 @@ extern "C" int gogp_test_chunk_tdot(int device, int precision, const void *chunk
                                     const double *v, int64_t v_len, double *part, int64_t part_len, double *out,
                                     int64_t out_len) {
   if (!prec_ok(precision)) return GOGP_EARG;
-  const std::initializer_list<ShArr> arrs = {{chunk, chunk_len, precision / 8, false}, {v, v_len, 8, false},
-                                             {part, part_len, 8, true}, {out, out_len, 8, true}};
+  const std::vector<Arr> arrs = {rd(chunk, chunk_len, precision / 8), rd(v, v_len), io(part, part_len), io(out, out_len)};
   // the grid is nb / 64 column groups: any other nb would leave columns unwritten
-  if (!sh_have(arrs) || rows < 1 || rows > (1 << 20) || nb < 64 || nb > 1024 || nb % 64) return GOGP_EARG;
+  if (!have(arrs) || rows < 1 || rows > (1 << 20) || nb < 64 || nb > 1024 || nb % 64) return GOGP_EARG;
   if (chunk_len < rows * nb || v_len < rows || part_len < chunk_tdot_scratch(rows, nb) || out_len < nb) return GOGP_EARG;
-  return sh_run(device, arrs, [&](char **d) {
+  return run(device, arrs, [&](const Dev &d) {
     if (precision == 64)
-      launch_chunk_tdot(0, SH_D(0), rows, nb, SH_D(1), SH_D(2), SH_D(3));
+      launch_chunk_tdot(0, d[0], rows, nb, d[1], d[2], d[3]);
     else
-      launch_chunk_tdot(0, SH_F(0), rows, nb, SH_D(1), SH_D(2), SH_D(3));
+      launch_chunk_tdot(0, d.f32(0), rows, nb, d[1], d[2], d[3]);
   });
 }
 
@@ -2461,16 +2111,16 @@ extern "C" int gogp_test_chunk_alpha(int device, int precision, const void *Ych,
                                      int nb_shift, int Pr, int Pc, int pr, int pc, const double *z, int64_t z_len, double *out,
                                      int64_t out_len) {
   if (!prec_ok(precision)) return GOGP_EARG;
-  const std::initializer_list<ShArr> arrs = {{Ych, ych_len, precision / 8, false}, {z, z_len, 8, false}, {out, out_len, 8, true}};
+  const std::vector<Arr> arrs = {rd(Ych, ych_len, precision / 8), rd(z, z_len), io(out, out_len)};
   BlockMap m;
-  if (!sh_have(arrs) || !sh_map(nb_shift, Pr, Pc, pr, pc, &m) || !sh_tiles(mloc, nloc, m)) return GOGP_EARG;
+  if (!have(arrs) || !sh_map(nb_shift, Pr, Pc, pr, pc, &m) || !sh_tiles(mloc, nloc, m)) return GOGP_EARG;
   const int64_t nb = 1 << nb_shift, npad = (int64_t)mloc * Pr * nb;
   if (ych_len < (int64_t)nloc * mloc * nb * nb || z_len < npad || out_len < npad) return GOGP_EARG;
-  return sh_run(device, arrs, [&](char **d) {
+  return run(device, arrs, [&](const Dev &d) {
     if (precision == 64)
-      launch_chunk_alpha(0, SH_D(0), mloc, nloc, (int)nb, m, SH_D(1), SH_D(2));
+      launch_chunk_alpha(0, d[0], mloc, nloc, (int)nb, m, d[1], d[2]);
     else
-      launch_chunk_alpha(0, SH_F(0), mloc, nloc, (int)nb, m, SH_D(1), SH_D(2));
+      launch_chunk_alpha(0, d.f32(0), mloc, nloc, (int)nb, m, d[1], d[2]);
   });
 }
 
@@ -2478,17 +2128,16 @@ extern "C" int gogp_test_chunk_sumsq(int device, int precision, const void *Ych,
                                      int nb_shift, int Pr, int Pc, int pr, int pc, int64_t n, double *part, int64_t part_len,
                                      double *out, int64_t out_len) {
   if (!prec_ok(precision)) return GOGP_EARG;
-  const std::initializer_list<ShArr> arrs = {{Ych, ych_len, precision / 8, false}, {part, part_len, 8, true},
-                                             {out, out_len, 8, true}};
+  const std::vector<Arr> arrs = {rd(Ych, ych_len, precision / 8), io(part, part_len), io(out, out_len)};
   BlockMap m;
-  if (!sh_have(arrs) || !sh_map(nb_shift, Pr, Pc, pr, pc, &m) || !sh_tiles(mloc, nloc, m)) return GOGP_EARG;
+  if (!have(arrs) || !sh_map(nb_shift, Pr, Pc, pr, pc, &m) || !sh_tiles(mloc, nloc, m)) return GOGP_EARG;
   const int64_t nb = 1 << nb_shift, npad = (int64_t)mloc * Pr * nb;
   if (n < 1 || n > npad || ych_len < (int64_t)nloc * mloc * nb * nb || part_len < mloc * nb || out_len < 1) return GOGP_EARG;
-  return sh_run(device, arrs, [&](char **d) {
+  return run(device, arrs, [&](const Dev &d) {
     if (precision == 64)
-      launch_chunk_sumsq(0, SH_D(0), mloc, nloc, (int)nb, m, n, SH_D(1), SH_D(2));
+      launch_chunk_sumsq(0, d[0], mloc, nloc, (int)nb, m, n, d[1], d[2]);
     else
-      launch_chunk_sumsq(0, SH_F(0), mloc, nloc, (int)nb, m, n, SH_D(1), SH_D(2));
+      launch_chunk_sumsq(0, d.f32(0), mloc, nloc, (int)nb, m, n, d[1], d[2]);
   });
 }
 
@@ -2496,151 +2145,148 @@ extern "C" int gogp_test_lml_scalars(int device, int precision, const void *L, i
                                      int64_t z_len, const double *y, int64_t y_len, const double *alpha, int64_t alpha_len,
                                      int64_t n, int k, int64_t bstride, double *scalars, int64_t scalars_len) {
   if (!prec_ok(precision)) return GOGP_EARG;
-  const std::initializer_list<ShArr> arrs = {{L, l_len, precision / 8, false}, {z, z_len, 8, false}, {y, y_len, 8, false},
-                                             {alpha, alpha_len, 8, false, true}, {scalars, scalars_len, 8, true}};
-  if (!sh_have(arrs) || !sh_batch(precision, k, &bstride) || n < 1 || n > TH_NPAD_MAX) return GOGP_EARG;
+  const std::vector<Arr> arrs = {rd(L, l_len, precision / 8), rd(z, z_len), rd(y, y_len), opt(rd(alpha, alpha_len)),
+                                 io(scalars, scalars_len)};
+  if (!have(arrs) || !batch_ok(precision, k, &bstride) || n < 1 || n > TH_NPAD_MAX) return GOGP_EARG;
   if (!covers(l_len, 0, ld, n, n, k, bstride) || !covers(z_len, 0, n, 1, n, k, bstride) || y_len < n ||
       (alpha && !covers(alpha_len, 0, n, 1, n, k, bstride)) || !covers(scalars_len, 0, 5, 1, 5, k, bstride))
     return GOGP_EARG;
-  return sh_run(device, arrs, [&](char **d) {
-    sh_set_batch(k, bstride);
+  return run(device, arrs, [&](const Dev &d) {
+    set_batch(k, bstride);
     if (precision == 64)
-      launch_lml_scalars(0, SH_D(0), ld, SH_D(1), SH_D(2), SH_D(3), n, SH_D(4));
+      launch_lml_scalars(0, d[0], ld, d[1], d[2], d[3], n, d[4]);
     else
-      launch_lml_scalars(0, SH_F(0), ld, SH_D(1), SH_D(2), SH_D(3), n, SH_D(4));
+      launch_lml_scalars(0, d.f32(0), ld, d[1], d[2], d[3], n, d[4]);
   });
 }
 
 extern "C" int gogp_test_alpha_from_y_batched(int device, const double *Y, int64_t y_len, int64_t ld, const double *z,
                                               int64_t z_len, int64_t npad, int k, int64_t bstride, double *alpha,
                                               int64_t alpha_len) {
-  const std::initializer_list<ShArr> arrs = {{Y, y_len, 8, false}, {z, z_len, 8, false}, {alpha, alpha_len, 8, true}};
-  if (!sh_have(arrs) || !sh_batch(64, k, &bstride) || npad <= 0 || npad % 2 || npad > TH_NPAD_MAX || ld % 2) return GOGP_EARG;
+  const std::vector<Arr> arrs = {rd(Y, y_len), rd(z, z_len), io(alpha, alpha_len)};
+  if (!have(arrs) || !batch_ok(64, k, &bstride) || npad <= 0 || npad % 2 || npad > TH_NPAD_MAX || ld % 2) return GOGP_EARG;
   if (!covers(y_len, 0, ld, npad, npad, k, bstride) || !covers(z_len, 0, npad, 1, npad, k, bstride) ||
       !covers(alpha_len, 0, npad, 1, npad, k, bstride))
     return GOGP_EARG;
-  return sh_run(device, arrs, [&](char **d) {
-    sh_set_batch(k, bstride);
-    launch_alpha_from_y(0, (const double *)SH_D(0), ld, SH_D(1), npad, SH_D(2));
+  return run(device, arrs, [&](const Dev &d) {
+    set_batch(k, bstride);
+    launch_alpha_from_y(0, (const double *)d[0], ld, d[1], npad, d[2]);
   });
 }
 
 extern "C" int gogp_test_trace_from_y(int device, const float *Y, int64_t y_len, int64_t ld, int64_t n, int64_t npad,
                                       const double *alpha, int64_t alpha_len, double *part, int64_t part_len, double *out,
                                       int64_t out_len) {
-  const std::initializer_list<ShArr> arrs = {{Y, y_len, 4, false}, {alpha, alpha_len, 8, false}, {part, part_len, 8, true},
-                                             {out, out_len, 8, true}};
-  if (!sh_have(arrs) || npad <= 0 || npad % PANEL || npad > TH_NPAD_MAX || n < 1 || n > npad) return GOGP_EARG;
+  const std::vector<Arr> arrs = {rd(Y, y_len, 4), rd(alpha, alpha_len), io(part, part_len), io(out, out_len)};
+  if (!have(arrs) || npad <= 0 || npad % PANEL || npad > TH_NPAD_MAX || n < 1 || n > npad) return GOGP_EARG;
   if (!covers(y_len, 0, ld, n, npad, 1, 0) || alpha_len < n || part_len < n || out_len < 1) return GOGP_EARG;
-  return sh_run(device, arrs, [&](char **d) { launch_trace_from_y(0, SH_F(0), ld, n, npad, SH_D(1), SH_D(2), SH_D(3)); });
+  return run(device, arrs, [&](const Dev &d) { launch_trace_from_y(0, d.f32(0), ld, n, npad, d[1], d[2], d[3]); });
 }
 
 extern "C" int gogp_test_zero_upper_blocks(int device, int precision, void *R, int64_t r_len, int64_t ld, int64_t npad, int k,
                                            int64_t bstride) {
   if (!prec_ok(precision)) return GOGP_EARG;
-  const std::initializer_list<ShArr> arrs = {{R, r_len, precision / 8, true}};
-  if (!sh_have(arrs) || !sh_batch(precision, k, &bstride) || npad <= 0 || npad % PANEL || npad > (1 << 15) || ld % 2)
+  const std::vector<Arr> arrs = {io(R, r_len, precision / 8)};
+  if (!have(arrs) || !batch_ok(precision, k, &bstride) || npad <= 0 || npad % PANEL || npad > (1 << 15) || ld % 2)
     return GOGP_EARG;
   if (!covers(r_len, 0, ld, npad, npad, k, bstride)) return GOGP_EARG;
-  return sh_run(device, arrs, [&](char **d) {
-    sh_set_batch(k, bstride);
+  return run(device, arrs, [&](const Dev &d) {
+    set_batch(k, bstride);
     if (precision == 64)
-      launch_zero_upper_blocks(0, SH_D(0), ld, npad);
+      launch_zero_upper_blocks(0, d[0], ld, npad);
     else
-      launch_zero_upper_blocks(0, SH_F(0), ld, npad);
+      launch_zero_upper_blocks(0, d.f32(0), ld, npad);
   });
 }
 
 extern "C" int gogp_test_ydiag(int device, int precision, const void *Dinv, int64_t dinv_len, void *Y, int64_t y_len,
                                int64_t ld, int k, int64_t bstride) {
   if (!prec_ok(precision)) return GOGP_EARG;
-  const std::initializer_list<ShArr> arrs = {{Dinv, dinv_len, precision / 8, false}, {Y, y_len, precision / 8, true}};
-  if (!sh_have(arrs) || !sh_batch(precision, k, &bstride)) return GOGP_EARG;
+  const std::vector<Arr> arrs = {rd(Dinv, dinv_len, precision / 8), io(Y, y_len, precision / 8)};
+  if (!have(arrs) || !batch_ok(precision, k, &bstride)) return GOGP_EARG;
   if (!covers(dinv_len, 0, PANEL, PANEL, PANEL, k, bstride) || !covers(y_len, 0, ld, PANEL, PANEL, k, bstride))
     return GOGP_EARG;
-  return sh_run(device, arrs, [&](char **d) {
-    sh_set_batch(k, bstride);
+  return run(device, arrs, [&](const Dev &d) {
+    set_batch(k, bstride);
     if (precision == 64)
-      launch_ydiag(0, SH_D(0), SH_D(1), ld);
+      launch_ydiag(0, d[0], d[1], ld);
     else
-      launch_ydiag(0, SH_F(0), SH_F(1), ld);
+      launch_ydiag(0, d.f32(0), d.f32(1), ld);
   });
 }
 
 extern "C" int gogp_test_zero_block(int device, int precision, void *B, int64_t b_len, int64_t ld, int64_t rows, int64_t cols,
                                     int k, int64_t bstride) {
   if (!prec_ok(precision)) return GOGP_EARG;
-  const std::initializer_list<ShArr> arrs = {{B, b_len, precision / 8, true}};
+  const std::vector<Arr> arrs = {io(B, b_len, precision / 8)};
   // pairs of columns are stored: an odd cols would write one column more, an odd ld misalign the pairs
-  if (!sh_have(arrs) || !sh_batch(precision, k, &bstride) || rows < 1 || rows > 65535 || cols < 2 || cols % 2 || ld % 2 ||
+  if (!have(arrs) || !batch_ok(precision, k, &bstride) || rows < 1 || rows > 65535 || cols < 2 || cols % 2 || ld % 2 ||
       cols > (1 << 20))
     return GOGP_EARG;
   if (!covers(b_len, 0, ld, rows, cols, k, bstride)) return GOGP_EARG;
-  return sh_run(device, arrs, [&](char **d) {
-    sh_set_batch(k, bstride);
+  return run(device, arrs, [&](const Dev &d) {
+    set_batch(k, bstride);
     if (precision == 64)
-      launch_zero_block(0, SH_D(0), ld, rows, cols);
+      launch_zero_block(0, d[0], ld, rows, cols);
     else
-      launch_zero_block(0, SH_F(0), ld, rows, cols);
+      launch_zero_block(0, d.f32(0), ld, rows, cols);
   });
 }
 
 extern "C" int gogp_test_extract_lower(int device, int precision, const void *L, int64_t l_len, int64_t ld, int64_t n,
                                        double *out, int64_t out_len) {
   if (!prec_ok(precision)) return GOGP_EARG;
-  const std::initializer_list<ShArr> arrs = {{L, l_len, precision / 8, false}, {out, out_len, 8, true}};
-  if (!sh_have(arrs) || n < 1 || n > 65535 || !covers(l_len, 0, ld, n, n, 1, 0) || out_len < n * n) return GOGP_EARG;
-  return sh_run(device, arrs, [&](char **d) {
+  const std::vector<Arr> arrs = {rd(L, l_len, precision / 8), io(out, out_len)};
+  if (!have(arrs) || n < 1 || n > 65535 || !covers(l_len, 0, ld, n, n, 1, 0) || out_len < n * n) return GOGP_EARG;
+  return run(device, arrs, [&](const Dev &d) {
     if (precision == 64)
-      launch_extract_lower(0, SH_D(0), ld, n, SH_D(1));
+      launch_extract_lower(0, d[0], ld, n, d[1]);
     else
-      launch_extract_lower(0, SH_F(0), ld, n, SH_D(1));
+      launch_extract_lower(0, d.f32(0), ld, n, d[1]);
   });
 }
 
 extern "C" int gogp_test_pack_lower(int device, int precision, const double *src, int64_t src_len, int64_t n, int64_t npad,
                                     void *L, int64_t l_len, int64_t ld) {
   if (!prec_ok(precision)) return GOGP_EARG;
-  const std::initializer_list<ShArr> arrs = {{src, src_len, 8, false}, {L, l_len, precision / 8, true}};
-  if (!sh_have(arrs) || n < 1 || n > npad || npad > 65535 || src_len < n * n || !covers(l_len, 0, ld, npad, npad, 1, 0))
+  const std::vector<Arr> arrs = {rd(src, src_len), io(L, l_len, precision / 8)};
+  if (!have(arrs) || n < 1 || n > npad || npad > 65535 || src_len < n * n || !covers(l_len, 0, ld, npad, npad, 1, 0))
     return GOGP_EARG;
-  return sh_run(device, arrs, [&](char **d) {
+  return run(device, arrs, [&](const Dev &d) {
     if (precision == 64)
-      launch_pack_lower(0, SH_D(0), n, npad, SH_D(1), ld);
+      launch_pack_lower(0, d[0], n, npad, d[1], ld);
     else
-      launch_pack_lower(0, SH_D(0), n, npad, SH_F(1), ld);
+      launch_pack_lower(0, d[0], n, npad, d.f32(1), ld);
   });
 }
 
 extern "C" int gogp_test_sigma(int device, const double *prior, int64_t prior_len, const double *q, int64_t q_len, int64_t m,
                                double *sigma, int64_t sigma_len) {
-  const std::initializer_list<ShArr> arrs = {{prior, prior_len, 8, false}, {q, q_len, 8, false, true}, {sigma, sigma_len, 8, true}};
-  if (!sh_have(arrs) || m < 1 || m > SH_COUNT_MAX || prior_len < m || (q && q_len < m) || sigma_len < m) return GOGP_EARG;
-  return sh_run(device, arrs, [&](char **d) { launch_sigma(0, SH_D(0), SH_D(1), m, SH_D(2)); });
+  const std::vector<Arr> arrs = {rd(prior, prior_len), opt(rd(q, q_len)), io(sigma, sigma_len)};
+  if (!have(arrs) || m < 1 || m > SH_COUNT_MAX || prior_len < m || (q && q_len < m) || sigma_len < m) return GOGP_EARG;
+  return run(device, arrs, [&](const Dev &d) { launch_sigma(0, d[0], d[1], m, d[2]); });
 }
 
 extern "C" int gogp_test_logdet_block(int device, const double *L, int64_t l_len, int64_t ld, int64_t row0, int64_t n, int nb,
                                       double *acc, int64_t acc_len) {
-  const std::initializer_list<ShArr> arrs = {{L, l_len, 8, false}, {acc, acc_len, 8, true}};
-  if (!sh_have(arrs) || nb < 1 || nb > 1024 || row0 < 0 || n < 0 || n > TH_NPAD_MAX || row0 > TH_NPAD_MAX) return GOGP_EARG;
+  const std::vector<Arr> arrs = {rd(L, l_len), io(acc, acc_len)};
+  if (!have(arrs) || nb < 1 || nb > 1024 || row0 < 0 || n < 0 || n > TH_NPAD_MAX || row0 > TH_NPAD_MAX) return GOGP_EARG;
   if (!covers(l_len, 0, ld, nb, nb, 1, 0) || acc_len < 1) return GOGP_EARG;
-  return sh_run(device, arrs, [&](char **d) { launch_logdet_block(0, SH_D(0), ld, row0, n, nb, SH_D(1)); });
+  return run(device, arrs, [&](const Dev &d) { launch_logdet_block(0, d[0], ld, row0, n, nb, d[1]); });
 }
 
 extern "C" int gogp_test_dot(int device, const double *a, int64_t a_len, const double *b, int64_t b_len, int64_t n, double *out,
                              int64_t out_len) {
-  const std::initializer_list<ShArr> arrs = {{a, a_len, 8, false}, {b, b_len, 8, false}, {out, out_len, 8, true}};
-  if (!sh_have(arrs) || n < 1 || n > SH_COUNT_MAX || a_len < n || b_len < n || out_len < 1) return GOGP_EARG;
-  return sh_run(device, arrs, [&](char **d) { launch_dot(0, SH_D(0), SH_D(1), n, SH_D(2)); });
+  const std::vector<Arr> arrs = {rd(a, a_len), rd(b, b_len), io(out, out_len)};
+  if (!have(arrs) || n < 1 || n > SH_COUNT_MAX || a_len < n || b_len < n || out_len < 1) return GOGP_EARG;
+  return run(device, arrs, [&](const Dev &d) { launch_dot(0, d[0], d[1], n, d[2]); });
 }
 
 extern "C" int gogp_test_sumsq_info(int device, const double *z, int64_t z_len, int64_t n, const int64_t *info,
                                     int64_t info_len, double *out, int64_t out_len) {
-  const std::initializer_list<ShArr> arrs = {{z, z_len, 8, false}, {info, info_len, 8, false, true}, {out, out_len, 8, true}};
-  if (!sh_have(arrs) || n < 1 || n > SH_COUNT_MAX || z_len < n || out_len < (info ? 2 : 1)) return GOGP_EARG;
-  return sh_run(device, arrs, [&](char **d) {
-    launch_sumsq_info(0, SH_D(0), n, reinterpret_cast<const long long *>(d[1]), SH_D(2));
-  });
+  const std::vector<Arr> arrs = {rd(z, z_len), opt(rd(info, info_len)), io(out, out_len)};
+  if (!have(arrs) || n < 1 || n > SH_COUNT_MAX || z_len < n || out_len < (info ? 2 : 1)) return GOGP_EARG;
+  return run(device, arrs, [&](const Dev &d) { launch_sumsq_info(0, d[0], n, d.as<long long>(1), d[2]); });
 }
 
 // the one-line vector kernels: op 0 fill (a := f), 1 axpy (a += b), 2 add_vec (a += b), 3 scale (a *= f), 4 residual_from
@@ -2650,29 +2296,29 @@ extern "C" int gogp_test_vector_op(int device, int op, int precision, void *a, i
                                    int64_t count, double f) {
   if (!prec_ok(precision) || op < 0 || op > 6 || (precision == 32 && op != 5)) return GOGP_EARG;
   const bool no_b = op == 0 || op == 3;
-  const std::initializer_list<ShArr> arrs = {{a, a_len, precision / 8, true}, {b, b_len, precision / 8, false, no_b}};
-  if (!sh_have(arrs) || count < 1 || count > SH_COUNT_MAX || a_len < count || (op == 6 && count != 1)) return GOGP_EARG;
+  const std::vector<Arr> arrs = {io(a, a_len, precision / 8), opt(rd(b, b_len, precision / 8), no_b)};
+  if (!have(arrs) || count < 1 || count > SH_COUNT_MAX || a_len < count || (op == 6 && count != 1)) return GOGP_EARG;
   if (no_b ? b != nullptr : b_len < count) return GOGP_EARG;
-  return sh_run(device, arrs, [&](char **d) {
+  return run(device, arrs, [&](const Dev &d) {
     switch (op) {
-      case 0: launch_fill(0, SH_D(0), count, f); break;
-      case 1: launch_axpy(0, SH_D(0), SH_D(1), count); break;
-      case 2: launch_add_vec(0, SH_D(0), SH_D(1), count); break;
-      case 3: launch_scale(0, SH_D(0), f, count); break;
-      case 4: launch_residual_from(0, SH_D(0), SH_D(1), count); break;
+      case 0: launch_fill(0, d[0], count, f); break;
+      case 1: launch_axpy(0, d[0], d[1], count); break;
+      case 2: launch_add_vec(0, d[0], d[1], count); break;
+      case 3: launch_scale(0, d[0], f, count); break;
+      case 4: launch_residual_from(0, d[0], d[1], count); break;
       case 5:
         if (precision == 64)
-          launch_add_inplace(0, SH_D(0), SH_D(1), count);
+          launch_add_inplace(0, d[0], d[1], count);
         else
-          launch_add_inplace(0, SH_F(0), SH_F(1), count);
+          launch_add_inplace(0, d.f32(0), d.f32(1), count);
         break;
-      default: launch_info_to_double(0, reinterpret_cast<const long long *>(d[1]), SH_D(0)); break;
+      default: launch_info_to_double(0, d.as<long long>(1), d[0]); break;
     }
   });
 }
 
 // ---- the kernels of gram.hip and the forecast-derivative kernels of pgrad.hip, through their product launchers
-// (tests/test_gram_kernels.py).  The rules of the hooks above.  What they refuse beyond the arrays' lengths follows from
+// (tests/test_gram_kernels.py).  What they refuse beyond the arrays' lengths follows from
 // the kernels (common.h states it at the launchers): whole 64 x 64 tiles are written, so npad / mpad / mrows / ncols are
 // positive multiples of 64 and the output holds all of their rows; the one-radial-term paths read rows n .. npad - 1 of X
 // unguarded, so X holds npad rows (and GOGP_MAX_NDIM doubles of slack, the convention of gogp_test_grad_reduce); wcols == 0
@@ -2688,31 +2334,23 @@ bool pad_ok(int64_t npad) { return npad > 0 && npad % 64 == 0 && npad <= GR_NPAD
 extern "C" int gogp_test_gram_split(int device, int precision, const gogp_test_kparams *kparams, int ev, const double *X,
                                     int64_t x_len, int64_t n, int64_t npad, int64_t wcols, int k, int64_t bstride, void *K,
                                     int64_t k_len, int64_t ld) {
-  if (!kparams || !X || !K || !prec_ok(precision) || !sh_batch(precision, k, &bstride)) return GOGP_EARG;
+  if (!kparams || !X || !K || !prec_ok(precision) || !batch_ok(precision, k, &bstride)) return GOGP_EARG;
   if (!gram_args_ok(kparams, k, 0, ev) || !pad_ok(npad) || n < 1 || n > npad || ld < npad) return GOGP_EARG;
   if (wcols < 64 || wcols % 64 || wcols > GR_NPAD_MAX) return GOGP_EARG;
   // every per-candidate buffer shares the stride: it must hold the matrix and the parameters
   if (k > 1 && (bstride < (npad - 1) * ld + npad || bstride * 8 < (int64_t)sizeof(DevParams))) return GOGP_EARG;
   const int ndim = kparams[0].ndim;
   if (x_len < npad * ndim + GOGP_MAX_NDIM || !covers(k_len, 0, ld, npad, npad, k, bstride)) return GOGP_EARG;
-  if (!device_ok(device)) return GOGP_EHIP;
   std::vector<DevParams> hp;
   for (int c = 0; c < k; ++c) hp.push_back(to_dev(kparams[c]));
-  DevCopy dP, dX, dK;
-  hipError_t e = up_strided(dP, hp.data(), sizeof(DevParams), k, (size_t)bstride * 8);
-  if (e == hipSuccess) e = dX.up(X, (size_t)x_len * sizeof(double));
-  if (e == hipSuccess) e = dK.up(K, (size_t)k_len * (precision / 8));
-  if (e == hipSuccess) {
-    sh_set_batch(k, bstride);
+  const std::vector<char> P = pack_strided(hp.data(), sizeof(DevParams), k, (size_t)bstride * 8);
+  return run(device, {rd(P.data(), (int64_t)P.size(), 1), rd(X, x_len), io(K, k_len, precision / 8)}, [&](const Dev &d) {
+    set_batch(k, bstride);
     if (precision == 64)
-      launch_gram_lower_split(0, 0, dP.as<DevParams>(), ndim, dX.as<double>(), n, npad, dK.as<double>(), ld, wcols, ev != 0);
+      launch_gram_lower_split(0, 0, d.as<DevParams>(0), ndim, d[1], n, npad, d[2], ld, wcols, ev != 0);
     else
-      launch_gram_lower_split(0, 0, dP.as<DevParams>(), ndim, dX.as<double>(), n, npad, dK.as<float>(), ld, wcols, ev != 0);
-    sh_set_batch(1, 0);
-    e = launched();
-  }
-  if (e == hipSuccess) e = dK.down(K);
-  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+      launch_gram_lower_split(0, 0, d.as<DevParams>(0), ndim, d[1], n, npad, d.f32(2), ld, wcols, ev != 0);
+  });
 }
 
 extern "C" int gogp_test_gram_local(int device, int precision, const gogp_test_kparams *kparams, int ev, const double *X,
@@ -2732,21 +2370,13 @@ extern "C" int gogp_test_gram_local(int device, int precision, const gogp_test_k
   if (map.grow(mrows - 1) >= npad || map.gcol(ncols - 1) >= npad) return GOGP_EARG;
   const int ndim = kparams->ndim;
   if (x_len < npad * ndim + GOGP_MAX_NDIM || !covers(k_len, 0, ld, mrows, ncols, 1, 0)) return GOGP_EARG;
-  if (!device_ok(device)) return GOGP_EHIP;
   const DevParams hp = to_dev(*kparams);
-  DevCopy dP, dX, dK;
-  hipError_t e = dP.up(&hp, sizeof hp);
-  if (e == hipSuccess) e = dX.up(X, (size_t)x_len * sizeof(double));
-  if (e == hipSuccess) e = dK.up(K, (size_t)k_len * (precision / 8));
-  if (e == hipSuccess) {
+  return run(device, {rd(&hp, 1, sizeof hp), rd(X, x_len), io(K, k_len, precision / 8)}, [&](const Dev &d) {
     if (precision == 64)
-      launch_gram_local(0, dP.as<DevParams>(), ndim, dX.as<double>(), n, mrows, ncols, map, dK.as<double>(), ld, ev != 0);
+      launch_gram_local(0, d.as<DevParams>(0), ndim, d[1], n, mrows, ncols, map, d[2], ld, ev != 0);
     else
-      launch_gram_local(0, dP.as<DevParams>(), ndim, dX.as<double>(), n, mrows, ncols, map, dK.as<float>(), ld, ev != 0);
-    e = launched();
-  }
-  if (e == hipSuccess) e = dK.down(K);
-  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+      launch_gram_local(0, d.as<DevParams>(0), ndim, d[1], n, mrows, ncols, map, d.f32(2), ld, ev != 0);
+  });
 }
 
 extern "C" int gogp_test_cross(int device, int precision, const gogp_test_kparams *kparams, int ev, const double *X,
@@ -2757,40 +2387,22 @@ extern "C" int gogp_test_cross(int device, int precision, const gogp_test_kparam
     return GOGP_EARG;
   const int ndim = kparams->ndim;
   if (x_len < npad * ndim + GOGP_MAX_NDIM || z_len < mpad * ndim || !covers(k_len, 0, ld, mpad, npad, 1, 0)) return GOGP_EARG;
-  if (!device_ok(device)) return GOGP_EHIP;
   const DevParams hp = to_dev(*kparams);
-  DevCopy dP, dX, dZ, dK;
-  hipError_t e = dP.up(&hp, sizeof hp);
-  if (e == hipSuccess) e = dX.up(X, (size_t)x_len * sizeof(double));
-  if (e == hipSuccess) e = dZ.up(Z, (size_t)z_len * sizeof(double));
-  if (e == hipSuccess) e = dK.up(KsT, (size_t)k_len * (precision / 8));
-  if (e == hipSuccess) {
+  return run(device, {rd(&hp, 1, sizeof hp), rd(X, x_len), rd(Z, z_len), io(KsT, k_len, precision / 8)}, [&](const Dev &d) {
     if (precision == 64)
-      launch_cross(0, dP.as<DevParams>(), ndim, dX.as<double>(), n, npad, dZ.as<double>(), m, mpad, dK.as<double>(), ld, ev != 0);
+      launch_cross(0, d.as<DevParams>(0), ndim, d[1], n, npad, d[2], m, mpad, d[3], ld, ev != 0);
     else
-      launch_cross(0, dP.as<DevParams>(), ndim, dX.as<double>(), n, npad, dZ.as<double>(), m, mpad, dK.as<float>(), ld, ev != 0);
-    e = launched();
-  }
-  if (e == hipSuccess) e = dK.down(KsT);
-  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+      launch_cross(0, d.as<DevParams>(0), ndim, d[1], n, npad, d[2], m, mpad, d.f32(3), ld, ev != 0);
+  });
 }
 
 extern "C" int gogp_test_prior(int device, const gogp_test_kparams *kparams, const double *Z, int64_t z_len, int64_t m,
                                double *prior, int64_t prior_len) {
   if (!kparams || !Z || !prior || !gram_args_ok(kparams, 1, 0, 0)) return GOGP_EARG;
   if (m < 1 || m > SH_COUNT_MAX || z_len < m * kparams->ndim || prior_len < m) return GOGP_EARG;
-  if (!device_ok(device)) return GOGP_EHIP;
   const DevParams hp = to_dev(*kparams);
-  DevCopy dP, dZ, dp;
-  hipError_t e = dP.up(&hp, sizeof hp);
-  if (e == hipSuccess) e = dZ.up(Z, (size_t)z_len * sizeof(double));
-  if (e == hipSuccess) e = dp.up(prior, (size_t)prior_len * sizeof(double));
-  if (e == hipSuccess) {
-    launch_prior(0, dP.as<DevParams>(), dZ.as<double>(), m, dp.as<double>());
-    e = launched();
-  }
-  if (e == hipSuccess) e = dp.down(prior);
-  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+  return run(device, {rd(&hp, 1, sizeof hp), rd(Z, z_len), io(prior, prior_len)},
+             [&](const Dev &d) { launch_prior(0, d.as<DevParams>(0), d[1], m, d[2]); });
 }
 
 extern "C" int gogp_test_kmatvec(int device, const gogp_test_kparams *kparams, int radial1, int ev, const double *X,
@@ -2804,27 +2416,16 @@ extern "C" int gogp_test_kmatvec(int device, const gogp_test_kparams *kparams, i
   if (y ? (nparts != 1 || y_len < n) : y_len != 0) return GOGP_EARG;  // launch_residual takes every column
   const int ndim = kparams->ndim;
   if (x_len < npad * ndim + GOGP_MAX_NDIM || v_len < npad || part_len < (int64_t)nslab * npad || out_len < npad) return GOGP_EARG;
-  if (!device_ok(device)) return GOGP_EHIP;
   const DevParams hp = to_dev(*kparams);
-  DevCopy dP, dX, dv, dy, dpart, dout;
-  hipError_t e = dP.up(&hp, sizeof hp);
-  if (e == hipSuccess) e = dX.up(X, (size_t)x_len * sizeof(double));
-  if (e == hipSuccess) e = dv.up(v, (size_t)v_len * sizeof(double));
-  if (e == hipSuccess) e = dy.up(y, (size_t)y_len * sizeof(double));
-  if (e == hipSuccess) e = dpart.up(part, (size_t)part_len * sizeof(double));
-  if (e == hipSuccess) e = dout.up(out, (size_t)out_len * sizeof(double));
-  if (e == hipSuccess) {
-    if (y)
-      launch_residual(0, dP.as<DevParams>(), ndim, dX.as<double>(), n, npad, dv.as<double>(), dy.as<double>(),
-                      dpart.as<double>(), nslab, dout.as<double>(), radial1 != 0, ev != 0);
-    else
-      launch_kmatvec_share(0, dP.as<DevParams>(), ndim, dX.as<double>(), n, npad, dv.as<double>(), part_idx, nparts,
-                           dpart.as<double>(), nslab, dout.as<double>(), radial1 != 0, ev != 0);
-    e = launched();
-  }
-  if (e == hipSuccess) e = dpart.down(part);
-  if (e == hipSuccess) e = dout.down(out);
-  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+  return run(device, {rd(&hp, 1, sizeof hp), rd(X, x_len), rd(v, v_len), rd(y, y_len), io(part, part_len), io(out, out_len)},
+             [&](const Dev &d) {
+               if (y)
+                 launch_residual(0, d.as<DevParams>(0), ndim, d[1], n, npad, d[2], d[3], d[4], nslab, d[5], radial1 != 0,
+                                 ev != 0);
+               else
+                 launch_kmatvec_share(0, d.as<DevParams>(0), ndim, d[1], n, npad, d[2], part_idx, nparts, d[4], nslab, d[5],
+                                      radial1 != 0, ev != 0);
+             });
 }
 
 extern "C" int gogp_test_pgrad_slabs(int64_t npad, int64_t m, int *tiles_per_slab) {
@@ -2845,25 +2446,11 @@ extern "C" int gogp_test_pgrad(int device, const gogp_test_kparams *kparams, int
   if (x_len < npad * ndim || z_len < md || alpha_len < npad || !covers(wt_len, 0, ld, m, npad, 1, 0) || sigma_len < m ||
       part_len < 2 * nslab * md || dmu_len < md || dsigma_len < md)
     return GOGP_EARG;
-  if (!device_ok(device)) return GOGP_EHIP;
   const DevParams hp = to_dev(*kparams);
-  DevCopy dP, dX, dZ, da, dW, ds, dpart, dm, dsg;
-  hipError_t e = dP.up(&hp, sizeof hp);
-  if (e == hipSuccess) e = dX.up(X, (size_t)x_len * sizeof(double));
-  if (e == hipSuccess) e = dZ.up(Z, (size_t)z_len * sizeof(double));
-  if (e == hipSuccess) e = da.up(alpha, (size_t)alpha_len * sizeof(double));
-  if (e == hipSuccess) e = dW.up(Wt, (size_t)wt_len * sizeof(double));
-  if (e == hipSuccess) e = ds.up(sigma, (size_t)sigma_len * sizeof(double));
-  if (e == hipSuccess) e = dpart.up(part, (size_t)part_len * sizeof(double));
-  if (e == hipSuccess) e = dm.up(dmu, (size_t)dmu_len * sizeof(double));
-  if (e == hipSuccess) e = dsg.up(dsigma, (size_t)dsigma_len * sizeof(double));
-  if (e == hipSuccess) {
-    launch_pgrad(0, dP.as<DevParams>(), ndim, dX.as<double>(), n, npad, dZ.as<double>(), m, da.as<double>(), dW.as<double>(),
-                 ld, ds.as<double>(), dpart.as<double>(), dm.as<double>(), dsg.as<double>(), ev != 0);
-    e = launched();
-  }
-  if (e == hipSuccess) e = dpart.down(part);
-  if (e == hipSuccess) e = dm.down(dmu);
-  if (e == hipSuccess) e = dsg.down(dsigma);
-  return e == hipSuccess ? GOGP_OK : GOGP_EHIP;
+  return run(device, {rd(&hp, 1, sizeof hp), rd(X, x_len), rd(Z, z_len), rd(alpha, alpha_len), rd(Wt, wt_len),
+                      rd(sigma, sigma_len), io(part, part_len), io(dmu, dmu_len), io(dsigma, dsigma_len)},
+             [&](const Dev &d) {
+               launch_pgrad(0, d.as<DevParams>(0), ndim, d[1], n, npad, d[2], m, d[3], d[4], ld, d[5], d[6], d[7], d[8],
+                            ev != 0);
+             });
 }
