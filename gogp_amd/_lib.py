@@ -72,6 +72,21 @@ class CGemmPlan(ctypes.Structure):
                 ("grid_z", ctypes.c_int64), ("flops", ctypes.c_double), ("tag", ctypes.c_int64)]
 
 
+GOGP_CG_MAX_RANK, GOGP_CG_MAX_RHS = 1024, 64
+
+
+class CCgCol(ctypes.Structure):
+    """gogp_cg_col (include/gogp_hip.h): one column of a lock-step block of the iterative solver."""
+    _fields_ = [("iterations", ctypes.c_int32), ("converged", ctypes.c_int32), ("rel_residual", ctypes.c_double),
+                ("rel_residual_recurrence", ctypes.c_double)]
+
+
+class CCgInfo(ctypes.Structure):
+    """gogp_cg_info (include/gogp_hip.h)."""
+    _fields_ = [("rank_used", ctypes.c_int32), ("products", ctypes.c_int32), ("blocks", ctypes.c_int32),
+                ("yt_alpha", ctypes.c_double)]
+
+
 SYMBOLS = [
     ("gogp_desc_check", ctypes.c_int, [_descp]),
     ("gogp_desc_ntheta_noise", ctypes.c_int, [_descp]),
@@ -126,6 +141,16 @@ SYMBOLS = [
      [_h, _dp, _i64, _dp, _i64, _i64, ctypes.c_double, ctypes.POINTER(_i64), _dp, _dp, ctypes.POINTER(_i64), _dp]),
     ("gogp_sparse_select_inducing_resident", ctypes.c_int,
      [_h, _dp, _i64, _i64, ctypes.c_double, ctypes.POINTER(_i64), _dp, _dp, ctypes.POINTER(_i64), _dp]),
+    ("gogp_cg_set_data", ctypes.c_int, [_h, _dp, _dp, _dp, _i64]),
+    ("gogp_cg_solve", ctypes.c_int,
+     [_h, _dp, _i64, ctypes.c_int32, ctypes.c_double, ctypes.c_double, ctypes.c_int32, ctypes.POINTER(CCgInfo),
+      ctypes.POINTER(CCgCol)]),
+    ("gogp_cg_get_alpha", ctypes.c_int, [_h, _dp, _i64]),
+    ("gogp_cg_solve_columns", ctypes.c_int,
+     [_h, _dp, _i64, ctypes.c_double, ctypes.c_int32, _dp, ctypes.POINTER(CCgCol)]),
+    ("gogp_cg_produce", ctypes.c_int,
+     [_h, _dp, _i64, _dp, _dp, ctypes.c_double, ctypes.c_int32, ctypes.POINTER(CCgCol)]),
+    ("gogp_cg_last_info", ctypes.c_int, [_h, ctypes.POINTER(CCgInfo)]),
     ("gogp_observe_gradient_batch", ctypes.c_int,
      [ctypes.POINTER(_h), ctypes.c_int, _dp, _i64, _dp, _dp, ctypes.POINTER(ctypes.c_int)]),
     ("gogp_observe_gradient_candidates", ctypes.c_int,
@@ -419,6 +444,23 @@ HOOK_SYMBOLS += [
     ("gogp_test_pgrad_slabs", _ci, [_i64, _i64, ctypes.POINTER(ctypes.c_int)]),
     ("gogp_test_pgrad", _ci, [_ci, _kpp, _ci, _dp, _i64, _i64, _i64, _dp, _i64, _i64, _dp, _i64, _dp, _i64, _i64, _dp, _i64]
      + [_dp, _i64] * 3),
+]
+
+#: the hooks of the kernels of cg.hip (tests/test_cg_kernels.py; gp.kmm_check, gp.cg_*_check)
+_i32p = ctypes.POINTER(ctypes.c_int32)
+HOOK_SYMBOLS += [
+    ("gogp_test_kmm_slabs", _ci, [_i64, _i64]),
+    ("gogp_test_cg_dot_blocks", _ci, [_i64]),
+    ("gogp_test_kmm", _ci, [_ci, _kpp, _dp, _i64, _i64, _dp, _i64, _i64, _dp, _i64, _i64, _ci, _dp, _i64, _ci, _ci, _dp, _i64,
+                            _dp, _i64, _i64]),
+    ("gogp_test_cg_dots", _ci, [_ci, _dp, _i64, _dp, _i64, _i64, _i64, _ci, _ci, _ci, ctypes.c_double, _dp, _i64, _dp, _i64,
+                                _dp, _i64, _i32p, _i64]),
+    ("gogp_test_cg_update_xr", _ci, [_ci] + [_dp, _i64] * 4 + [_i64, _i64, _ci, _dp, _i64, _i32p, _i64]),
+    ("gogp_test_cg_update_p", _ci, [_ci] + [_dp, _i64] * 2 + [_i64, _i64, _ci, _dp, _i64, _i32p, _i64]),
+    ("gogp_test_cg_scale", _ci, [_ci] + [_dp, _i64] * 3 + [_i64, _i64, _ci, _dp, _i64]),
+    ("gogp_test_cg_status", _ci, [_ci, _ci, _i32p, _i64]),
+    ("gogp_test_cg_precond", _ci, [_ci, _dp, _i64, _i64, _i64, _ci, _dp, _i64, _dp, _i64, _dp, _i64, _i64, _ci, _dp, _i64,
+                                   _dp, _i64]),
 ]
 
 

@@ -254,6 +254,7 @@ static hipError_t graph_stream(gogp_handle *h) {
 }
 
 static void sparse_free(gogp_handle *h);  // the inducing-point state (gogp_sparse_*), below
+static void cg_free(gogp_handle *h);      // the data and state of the iterative exact GP (gogp_cg_*), below
 
 static void release_streams(gogp_handle *h) {
   std::lock_guard<std::mutex> lock(g_pool_mutex);
@@ -269,6 +270,7 @@ extern "C" void gogp_destroy(gogp_handle *h) {
   if (h->s) (void)hipStreamSynchronize(h->s);
   gogp_dist_destroy(h);
   sparse_free(h);
+  cg_free(h);
   free_n_buffers(h);
   free_m_buffers(h);
   free_cand_buffers(h);
@@ -4193,6 +4195,480 @@ extern "C" int gogp_sparse_select_inducing_resident(gogp_handle *h, const double
                             trace);
 }
 
+// ---- the iterative exact GP (cg.hip) ---------------------------------------------------------------------------------------
+// include/gogp_hip.h states the iteration and the preconditioner; DESIGN.md section 4, "Iterative (CG)".  Everything runs
+// on the handle's main stream with buffers of the family's own.  Reused launchers: select_run (the factor), launch_cross
+// (the right-hand sides k* of Produce, whose KsT layout is one row of N per test point), launch_prior.  The Woodbury
+// products are cg.hip's own: the factor lies column-major and a block's vectors as T rows of N, which neither
+// launch_sparse_xty / launch_sparse_syrk (row-major chunks of Vt) nor the tile GEMM (multiples of 128) take without
+// transposed copies of N x rank and N x T doubles per application.  C = I + Ls^T Ls (rank <= 1024) is factored and inverted on
+// the host, once per solve.
+static int cg_refuse_handle(gogp_handle *h, const char *who);
+static void cg_free(gogp_handle *h) {
+  for (double *q : {h->cg_X, h->cg_y, h->cg_v, h->cg_d, h->cg_dis, h->cg_alpha}) (void)hipFree(q);
+  (void)hipFree(h->cg_P);
+  h->cg_X = h->cg_y = h->cg_v = h->cg_d = h->cg_dis = h->cg_alpha = nullptr;
+  h->cg_P = nullptr;
+  h->cg_L.release();
+  h->cg_small.release();
+  h->cg_vec.release();
+  h->cg_part.release();
+  h->cg_ks.release();
+  h->cg_N = h->cg_npad = 0;
+  h->cg_have = h->cg_solved = false;
+  h->cg_rank = h->cg_rp = 0;
+}
+
+extern "C" int gogp_cg_set_data(gogp_handle *h, const double *X, const double *y, const double *v, int64_t N) {
+  if (!h) return GOGP_EARG;
+  if (N == 0 && !X && !y && !v) {  // clear
+    HIPCHK(h, hipSetDevice(h->device));
+    cg_free(h);
+    return GOGP_OK;
+  }
+  if (sparse_refusal(h)) return cg_refuse_handle(h, "cg_set_data");
+  if (N < 1 || !X || !y) return fail(h, GOGP_EARG, "cg_set_data: need X, y and N >= 1 (N == 0 with NULLs clears)");
+  const int D = h->D;
+  for (int64_t i = 0; i < N * D; ++i)
+    if (!std::isfinite(X[i])) return fail(h, GOGP_EARG, "cg_set_data: non-finite input");
+  for (int64_t i = 0; i < N; ++i)
+    if (!std::isfinite(y[i])) return fail(h, GOGP_EARG, "cg_set_data: non-finite output");
+  double vmin = 0.0;
+  if (v) {
+    vmin = INFINITY;
+    for (int64_t i = 0; i < N; ++i) {
+      if (!std::isfinite(v[i]) || v[i] < 0.0) return fail(h, GOGP_EARG, "cg_set_data: noise variances must be finite and >= 0");
+      vmin = std::min(vmin, v[i]);
+    }
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  if (h->s) HIPCHK(h, hipStreamSynchronize(h->s));
+  cg_free(h);
+  const int64_t npad = (N + 255) / 256 * 256;
+  const size_t xb = ((size_t)npad * D + GOGP_MAX_NDIM) * sizeof(double), vb = (size_t)npad * sizeof(double);
+  hipStream_t s = h->s;
+  hipError_t e = hipMalloc(&h->cg_X, xb);
+  if (e == hipSuccess) e = hipMalloc(&h->cg_y, vb);
+  if (e == hipSuccess && v) e = hipMalloc(&h->cg_v, vb);
+  if (e == hipSuccess) e = hipMalloc(&h->cg_d, vb);
+  if (e == hipSuccess) e = hipMalloc(&h->cg_dis, vb);
+  if (e == hipSuccess) e = hipMalloc(&h->cg_alpha, vb);
+  if (e == hipSuccess) e = hipMalloc(&h->cg_P, sizeof(DevParams));
+  if (e == hipSuccess) e = hipMemsetAsync(h->cg_X, 0, xb, s);
+  if (e == hipSuccess) e = hipMemsetAsync(h->cg_y, 0, vb, s);
+  if (e == hipSuccess && v) e = hipMemsetAsync(h->cg_v, 0, vb, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(h->cg_X, X, (size_t)N * D * sizeof(double), hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(h->cg_y, y, (size_t)N * sizeof(double), hipMemcpyHostToDevice, s);
+  if (e == hipSuccess && v) e = hipMemcpyAsync(h->cg_v, v, (size_t)N * sizeof(double), hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e != hipSuccess) {
+    cg_free(h);
+    HIPCHK(h, e);
+  }
+  h->cg_N = N;
+  h->cg_npad = npad;
+  h->cg_vmin = vmin;
+  h->cg_have = true;
+  return GOGP_OK;
+}
+
+// The small device buffers of the family behind C^-1: W, Y, the state, the dots' results
+struct CgSmall {
+  double *Cinv, *W, *Y, *sc, *dots;
+  int *st;
+};
+static size_t cg_small_layout(char *base, int rp, CgSmall *b) {
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    char *q = base ? base + off : nullptr;
+    off += (bytes + 255) / 256 * 256;
+    return q;
+  };
+  const size_t rr = (size_t)std::max(rp, 16);
+  b->Cinv = reinterpret_cast<double *>(take(rr * rr * sizeof(double)));
+  b->W = reinterpret_cast<double *>(take((size_t)CG_MAX_T * rr * sizeof(double)));
+  b->Y = reinterpret_cast<double *>(take((size_t)CG_MAX_T * rr * sizeof(double)));
+  b->sc = reinterpret_cast<double *>(take((size_t)CG_SC_ROWS * CG_MAX_T * sizeof(double)));
+  b->dots = reinterpret_cast<double *>(take((size_t)CG_MAX_T * sizeof(double)));
+  b->st = reinterpret_cast<int *>(take((size_t)CG_ST_ROWS * CG_MAX_T * sizeof(int)));
+  return off;
+}
+
+// z = P^-1 r for a block (T rows of ld = npad doubles)
+static void cg_apply_precond(gogp_handle *h, const CgSmall &sm, const double *R, int T, double *Z) {
+  hipStream_t s = h->s;
+  const int r = h->cg_rank, rp = h->cg_rp;
+  const double *Ls = h->cg_L.as<double>();
+  if (r > 0) {
+    launch_cg_lst(s, Ls, h->cg_ldn, h->cg_N, r, rp, h->cg_dis, R, h->cg_npad, T, h->cg_part.as<double>(), sm.W);
+    launch_cg_small_mm(s, sm.Cinv, r, rp, sm.W, T, sm.Y);
+  }
+  launch_cg_precond(s, Ls, h->cg_ldn, h->cg_N, r, rp, h->cg_dis, R, sm.Y, h->cg_npad, T, Z);
+}
+
+// the scratch the product and the skinny transposed product share: sized for CG_MAX_T columns once
+static int cg_reserve_part(gogp_handle *h, int T) {
+  const int64_t n = h->cg_N;
+  const size_t kmm = (size_t)kmm_slabs(n, n) * (size_t)T * (size_t)((n + 63) / 64 * 64);
+  const size_t lst = (size_t)cg_lst_slabs(n) * (size_t)((T + 15) / 16 * 16) * (size_t)std::max(h->cg_rp, 16);
+  return h->cg_part.reserve(h, std::max(kmm, lst) * sizeof(double));
+}
+
+// One lock-step block: K^ x_t = b_t for the T <= CG_MAX_T rows of dB (device, ld = npad, zero from column n on); the
+// solutions are left in the first T rows of the workspace's x (returned through *xout).  GOGP_OK, GOGP_ENOCONV (every
+// output written) or an error.
+static int cg_block_solve(gogp_handle *h, const char *who, const double *dB, int T, double tol, int max_iter, double **xout,
+                          gogp_cg_col *cols, int col0) {
+  const int64_t n = h->cg_N, ld = h->cg_npad;
+  hipStream_t s = h->s;
+  const int nb = cg_dot_blocks(n);
+  const size_t vec = (size_t)T * (size_t)ld;
+  int rc = h->cg_vec.reserve(h, (5 * vec + (size_t)CG_MAX_T * nb) * sizeof(double));
+  if (rc == GOGP_OK) rc = cg_reserve_part(h, T);
+  if (rc != GOGP_OK) return rc;
+  CgSmall sm;
+  cg_small_layout(h->cg_small.as<char>(), h->cg_rp, &sm);
+  double *x = h->cg_vec.as<double>(), *r = x + vec, *p = r + vec, *z = p + vec, *q = z + vec, *dpart = q + vec;
+  double *kpart = h->cg_part.as<double>();
+  const CgState cs{sm.sc, sm.st};
+  const int nslab = kmm_slabs(n, n);
+  const DevParams *P = h->cg_P;
+  const int D = h->D;
+  HIPCHK(h, hipMemsetAsync(x, 0, 5 * vec * sizeof(double), s));
+  HIPCHK(h, hipMemcpyAsync(r, dB, vec * sizeof(double), hipMemcpyDeviceToDevice, s));
+  launch_cg_dots(s, r, r, ld, n, T, CG_DOT_BNORM, 0, tol, dpart, nullptr, cs);
+  cg_apply_precond(h, sm, r, T, z);
+  HIPCHK(h, hipMemcpyAsync(p, z, vec * sizeof(double), hipMemcpyDeviceToDevice, s));
+  launch_cg_dots(s, r, z, ld, n, T, CG_DOT_RHO0, 0, tol, dpart, nullptr, cs);
+  int status[2] = {T, 0};
+  const int check = std::max(1, h->cg_check);
+  for (int it = 1; it <= max_iter; ++it) {
+    launch_kmm(s, P, D, h->cg_X, n, h->cg_X, n, p, ld, T, h->cg_d, nslab, 0, kpart, q, ld);
+    ++h->cg_products;
+    launch_cg_dots(s, p, q, ld, n, T, CG_DOT_PQ, it, tol, dpart, nullptr, cs);
+    launch_cg_update_xr(s, x, r, p, q, ld, n, T, cs);
+    launch_cg_dots(s, r, r, ld, n, T, CG_DOT_RR, it, tol, dpart, nullptr, cs);
+    cg_apply_precond(h, sm, r, T, z);
+    launch_cg_dots(s, r, z, ld, n, T, CG_DOT_BETA, it, tol, dpart, nullptr, cs);
+    launch_cg_update_p(s, p, z, ld, n, T, cs);
+    if (it % check == 0 || it == max_iter) {
+      launch_cg_status(s, T, cs);
+      HIPCHK(h, hipMemcpyAsync(status, sm.st + CG_ST_STATUS * CG_MAX_T, sizeof status, hipMemcpyDeviceToHost, s));
+      HIPCHK(h, hipStreamSynchronize(s));
+      if (status[0] == 0 || status[1] != 0) break;
+    }
+  }
+  // the true residual: one more product; b - K^ x into z, its squared norms through the plain dots
+  launch_kmm(s, P, D, h->cg_X, n, h->cg_X, n, x, ld, T, h->cg_d, nslab, 0, kpart, q, ld);
+  ++h->cg_products;
+  launch_cg_scale(s, dB, nullptr, q, ld, n, T, z);
+  launch_cg_dots(s, z, z, ld, n, T, CG_DOT_PLAIN, 0, tol, dpart, sm.dots, cs);
+  double hsc[CG_SC_ROWS * CG_MAX_T], hdots[CG_MAX_T];
+  int hst[CG_ST_ROWS * CG_MAX_T];
+  // (the three copies land in locals: the stream is drained before any return, whatever failed)
+  hipError_t ce = hipMemcpyAsync(hsc, sm.sc, sizeof hsc, hipMemcpyDeviceToHost, s);
+  if (ce == hipSuccess) ce = hipMemcpyAsync(hdots, sm.dots, sizeof hdots, hipMemcpyDeviceToHost, s);
+  if (ce == hipSuccess) ce = hipMemcpyAsync(hst, sm.st, sizeof hst, hipMemcpyDeviceToHost, s);
+  const hipError_t se = hipStreamSynchronize(s);
+  HIPCHK(h, ce);
+  HIPCHK(h, se);
+  HIPCHK(h, hipGetLastError());
+  ++h->cg_blocks;
+  *xout = x;
+  int bad = -1;
+  bool all = true;
+  for (int t = 0; t < T; ++t) {
+    const bool isbad = hst[CG_ST_BAD * CG_MAX_T + t] != 0;
+    if (isbad && bad < 0) bad = t;
+    const bool conv = hst[CG_ST_FROZEN * CG_MAX_T + t] != 0 && !isbad;
+    all = all && conv;
+    if (cols) {
+      gogp_cg_col &c = cols[t];
+      const double bn = sqrt(hsc[CG_SC_BNORM2 * CG_MAX_T + t]);
+      c.iterations = hst[CG_ST_ITERS * CG_MAX_T + t];
+      c.converged = conv ? 1 : 0;
+      c.rel_residual = bn > 0.0 ? sqrt(hdots[t]) / bn : 0.0;
+      c.rel_residual_recurrence = bn > 0.0 ? sqrt(hsc[CG_SC_RR * CG_MAX_T + t]) / bn : 0.0;
+    }
+  }
+  char buf[200];
+  if (bad >= 0) {
+    snprintf(buf, sizeof buf, "%s: p^T K p of column %d is not positive and finite (%g): the matrix is not positive definite",
+             who, col0 + bad, hsc[CG_SC_PQ * CG_MAX_T + bad]);
+    return fail(h, GOGP_ENOTPD, buf);
+  }
+  if (!all) {
+    snprintf(buf, sizeof buf, "%s: a column did not reach the tolerance within %d iterations", who, max_iter);
+    return fail(h, GOGP_ENOCONV, buf);
+  }
+  return GOGP_OK;
+}
+
+// the kinds of handle the sparse calls refuse, in the iterative calls' own words
+static int cg_refuse_handle(gogp_handle *h, const char *who) {
+  const char *why = h->prec == 32 ? "precision = 32 handles are not supported"
+                    : h->dist     ? "sharded handles are not supported"
+                                  : "event discounts are out of scope of the iterative solver (clear them with gogp_set_events)";
+  return fail(h, GOGP_EARG, (std::string(who) + ": " + why).c_str());
+}
+static const char *cg_tol_refusal(double tol, int32_t max_iter) {
+  if (!(tol > 0.0) || !std::isfinite(tol)) return "tol must be positive and finite";
+  if (max_iter < 1) return "max_iter must be at least 1";
+  return nullptr;
+}
+static int cg_refuse(gogp_handle *h, const char *who, int code, const char *what) {
+  return fail(h, code, (std::string(who) + ": " + what).c_str());
+}
+
+extern "C" int gogp_cg_solve(gogp_handle *h, const double *x, int64_t len, int32_t rank, double piv_tol, double tol,
+                             int32_t max_iter, gogp_cg_info *info, gogp_cg_col *col) {
+  const char *who = "cg_solve";
+  if (!h) return GOGP_EARG;
+  if (!x || !info) return cg_refuse(h, who, GOGP_EARG, "NULL");
+  if (sparse_refusal(h)) return cg_refuse_handle(h, who);
+  if (len != h->P) return cg_refuse(h, who, GOGP_EARG, "len(x)");
+  for (int64_t i = 0; i < len; ++i)
+    if (!std::isfinite(x[i])) return cg_refuse(h, who, GOGP_EARG, "non-finite parameter");
+  if (rank < 0 || rank > GOGP_CG_MAX_RANK) return cg_refuse(h, who, GOGP_EARG, "need 0 <= rank <= GOGP_CG_MAX_RANK");
+  if (std::isnan(piv_tol) || piv_tol == INFINITY) return cg_refuse(h, who, GOGP_EARG, "piv_tol must be finite or negative");
+  if (const char *why = cg_tol_refusal(tol, max_iter)) return cg_refuse(h, who, GOGP_EARG, why);
+  if (!h->cg_have) return cg_refuse(h, who, GOGP_ESTATE, "no data (gogp_cg_set_data)");
+  std::vector<double> th(h->P > 0 ? h->P : 1);
+  for (int i = 0; i < h->P; ++i) th[i] = exp(x[i]);
+  if (const char *why = theta_refusal(h, th.data(), th.data() + h->ns)) return cg_refuse(h, who, GOGP_EARG, why);
+  DevParams hp;
+  fill_params_theta(h, th.data(), th.data() + h->ns, hp);
+  // D = diag(noise_var + v_i) is inverted: its smallest entry must be positive
+  if (!(hp.noise_var + h->cg_vmin > 0.0)) return cg_refuse(h, who, GOGP_EARG, "noise_var + min v_i must be positive");
+  if (piv_tol < 0.0) piv_tol = pow(10.0, (double)h->sp_jitter_log10);
+  HIPCHK(h, hipSetDevice(h->device));
+  hipStream_t s = h->s;
+  const int64_t N = h->cg_N, npad = h->cg_npad;
+  const int D = h->D;
+  h->cg_solved = false;
+  h->cg_products = h->cg_blocks = 0;
+  h->cg_rank = h->cg_rp = 0;
+  *info = gogp_cg_info();
+  HIPCHK(h, hipMemcpyAsync(h->cg_P, &hp, sizeof hp, hipMemcpyHostToDevice, s));
+  HIPCHK(h, hipStreamSynchronize(s));  // hp is a local
+  launch_cg_diag(s, h->cg_P, h->cg_v, N, npad, h->cg_d, h->cg_dis);
+  // ---- the preconditioner: pivoted Cholesky of k(X, X), scaled, and the inverse of its capacitance matrix -----------------
+  int64_t m = 0;
+  const int64_t cap = std::min<int64_t>(rank, N);
+  if (cap > 0) {
+    SelectBufs b;
+    const size_t small = select_layout(nullptr, N, cap, D, &b);
+    const size_t lbytes = (size_t)cap * (size_t)b.ldn * sizeof(double);
+    if (const int rl = h->cg_L.reserve(h, lbytes)) {
+      if (rl != GOGP_ENOMEM) return rl;
+      char buf[240];
+      snprintf(buf, sizeof buf, "cg_solve: the factor (%lld columns of %lld doubles, %.3f GB) could not be allocated: %s",
+               (long long)cap, (long long)b.ldn, (double)lbytes * 1e-9, h->err.c_str());
+      h->err = buf;
+      return GOGP_ENOMEM;
+    }
+    char *work = nullptr;
+    HIPCHK(h, hipMalloc(&work, small));
+    select_layout(work, N, cap, D, &b);
+    b.Lt = h->cg_L.as<double>();
+    const hipError_t e = select_run(s, h->cg_P, D, h->cg_X, N, cap, piv_tol, 0, nullptr, b, &m);
+    (void)hipFree(work);
+    HIPCHK(h, e);
+    h->cg_ldn = b.ldn;
+  }
+  const int r = (int)m, rp = (r + 15) / 16 * 16;
+  CgSmall sm;
+  int rc = h->cg_small.reserve(h, cg_small_layout(nullptr, rp, &sm));
+  if (rc != GOGP_OK) return rc;
+  cg_small_layout(h->cg_small.as<char>(), rp, &sm);
+  if (r > 0) {
+    launch_cg_scale_factor(s, h->cg_L.as<double>(), h->cg_ldn, N, r, h->cg_dis);
+    launch_cg_capacitance(s, h->cg_L.as<double>(), h->cg_ldn, N, r, rp, sm.Cinv);
+    std::vector<double> C((size_t)rp * rp), G((size_t)rp * rp, 0.0);
+    HIPCHK(h, hipMemcpyAsync(C.data(), sm.Cinv, C.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    HIPCHK(h, hipGetLastError());
+    // C = G G^T (C >= I: every pivot is at least 1 up to rounding), Ginv = G^-1, C^-1 = Ginv^T Ginv -- on the host
+    for (int j = 0; j < rp; ++j) {
+      double dj = C[(size_t)j * rp + j];
+      for (int k = 0; k < j; ++k) dj -= G[(size_t)j * rp + k] * G[(size_t)j * rp + k];
+      if (!(dj > 0.0) || !std::isfinite(dj)) return cg_refuse(h, who, GOGP_ENOTPD, "the capacitance matrix of the preconditioner is not positive definite");
+      dj = sqrt(dj);
+      G[(size_t)j * rp + j] = dj;
+      for (int i = j + 1; i < rp; ++i) {
+        double v = C[(size_t)i * rp + j];
+        const double *gi = &G[(size_t)i * rp], *gj = &G[(size_t)j * rp];
+        for (int k = 0; k < j; ++k) v -= gi[k] * gj[k];
+        G[(size_t)i * rp + j] = v / dj;
+      }
+    }
+    // G^-1 kept TRANSPOSED (Gt[c][k] = (G^-1)[k][c], upper): every inner loop below runs along rows of G and of Gt
+    std::vector<double> Gt((size_t)rp * rp, 0.0);
+    for (int c = 0; c < rp; ++c) {
+      double *gt = &Gt[(size_t)c * rp];
+      gt[c] = 1.0 / G[(size_t)c * rp + c];
+      for (int i = c + 1; i < rp; ++i) {
+        double v = 0.0;
+        const double *gi = &G[(size_t)i * rp];
+        for (int k = c; k < i; ++k) v -= gi[k] * gt[k];
+        gt[i] = v / gi[i];
+      }
+    }
+    for (int i = 0; i < rp; ++i)
+      for (int j = 0; j <= i; ++j) {  // C^-1[i][j] = sum_{k >= i} (G^-1)[k][i] (G^-1)[k][j]
+        double v = 0.0;
+        const double *ti = &Gt[(size_t)i * rp], *tj = &Gt[(size_t)j * rp];
+        for (int k = i; k < rp; ++k) v += ti[k] * tj[k];
+        C[(size_t)i * rp + j] = C[(size_t)j * rp + i] = v;
+      }
+    HIPCHK(h, hipMemcpyAsync(sm.Cinv, C.data(), C.size() * sizeof(double), hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipStreamSynchronize(s));  // C is a local
+  }
+  h->cg_rank = r;
+  h->cg_rp = rp;
+  // ---- K^ alpha = y ------------------------------------------------------------------------------------------------------------
+  double *xs = nullptr;
+  gogp_cg_col c1{};
+  rc = cg_block_solve(h, who, h->cg_y, 1, tol, max_iter, &xs, &c1, 0);
+  if (col) *col = c1;
+  info->rank_used = r;
+  info->products = h->cg_products;
+  info->blocks = h->cg_blocks;
+  if (rc != GOGP_OK && rc != GOGP_ENOCONV) return rc;
+  const std::string keep = h->err;
+  HIPCHK(h, hipMemsetAsync(h->cg_alpha, 0, (size_t)npad * sizeof(double), s));
+  HIPCHK(h, hipMemcpyAsync(h->cg_alpha, xs, (size_t)N * sizeof(double), hipMemcpyDeviceToDevice, s));
+  CgState cs{sm.sc, sm.st};
+  launch_cg_dots(s, h->cg_y, h->cg_alpha, npad, N, 1, CG_DOT_PLAIN, 0, tol, xs + 5 * (size_t)npad, sm.dots, cs);
+  HIPCHK(h, hipMemcpyAsync(&h->cg_yta, sm.dots, sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipStreamSynchronize(s));
+  HIPCHK(h, hipGetLastError());
+  info->yt_alpha = h->cg_yta;
+  h->cg_solved = true;
+  if (rc != GOGP_OK) h->err = keep;
+  return rc;
+}
+
+extern "C" int gogp_cg_last_info(gogp_handle *h, gogp_cg_info *info) {
+  if (!h) return GOGP_EARG;
+  if (!info) return fail(h, GOGP_EARG, "cg_last_info: NULL");
+  info->rank_used = h->cg_rank;
+  info->products = h->cg_products;
+  info->blocks = h->cg_blocks;
+  info->yt_alpha = h->cg_yta;
+  return GOGP_OK;
+}
+
+extern "C" int gogp_cg_get_alpha(gogp_handle *h, double *alpha, int64_t n) {
+  const char *who = "cg_get_alpha";
+  if (!h) return GOGP_EARG;
+  if (!alpha) return cg_refuse(h, who, GOGP_EARG, "NULL");
+  if (sparse_refusal(h)) return cg_refuse_handle(h, who);
+  if (!h->cg_have || !h->cg_solved) return cg_refuse(h, who, GOGP_ESTATE, "no solution (gogp_cg_solve)");
+  if (n != h->cg_N) return cg_refuse(h, who, GOGP_EARG, "n is not the number of observations");
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipMemcpyAsync(alpha, h->cg_alpha, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->s));
+  HIPCHK(h, hipStreamSynchronize(h->s));
+  return GOGP_OK;
+}
+
+extern "C" int gogp_cg_solve_columns(gogp_handle *h, const double *B, int64_t T, double tol, int32_t max_iter, double *S,
+                                     gogp_cg_col *cols) {
+  const char *who = "cg_solve_columns";
+  if (!h) return GOGP_EARG;
+  if (sparse_refusal(h)) return cg_refuse_handle(h, who);
+  if (T < 0 || (T > 0 && (!B || !S))) return cg_refuse(h, who, GOGP_EARG, "need B and S for T > 0, T >= 0");
+  if (const char *why = cg_tol_refusal(tol, max_iter)) return cg_refuse(h, who, GOGP_EARG, why);
+  if (!h->cg_have || !h->cg_solved) return cg_refuse(h, who, GOGP_ESTATE, "no preconditioner (gogp_cg_solve)");
+  const int64_t N = h->cg_N, npad = h->cg_npad;
+  for (int64_t i = 0; i < T * N; ++i)
+    if (!std::isfinite(B[i])) return cg_refuse(h, who, GOGP_EARG, "non-finite right-hand side");
+  HIPCHK(h, hipSetDevice(h->device));
+  hipStream_t s = h->s;
+  h->cg_products = h->cg_blocks = 0;
+  int rc = GOGP_OK;
+  std::string first_err;
+  for (int64_t t0 = 0; t0 < T; t0 += CG_MAX_T) {
+    const int cnt = (int)std::min<int64_t>(CG_MAX_T, T - t0);
+    int r1 = h->cg_ks.reserve(h, (size_t)CG_MAX_T * (size_t)npad * sizeof(double));
+    if (r1 != GOGP_OK) return r1;
+    double *dB = h->cg_ks.as<double>();
+    HIPCHK(h, hipMemsetAsync(dB, 0, (size_t)cnt * npad * sizeof(double), s));
+    HIPCHK(h, hipMemcpy2DAsync(dB, (size_t)npad * sizeof(double), B + t0 * N, (size_t)N * sizeof(double),
+                               (size_t)N * sizeof(double), (size_t)cnt, hipMemcpyHostToDevice, s));
+    double *xs = nullptr;
+    r1 = cg_block_solve(h, who, dB, cnt, tol, max_iter, &xs, cols ? cols + t0 : nullptr, (int)t0);
+    if (r1 != GOGP_OK && r1 != GOGP_ENOCONV) return r1;
+    if (r1 != GOGP_OK && rc == GOGP_OK) rc = r1, first_err = h->err;
+    HIPCHK(h, hipMemcpy2DAsync(S + t0 * N, (size_t)N * sizeof(double), xs, (size_t)npad * sizeof(double),
+                               (size_t)N * sizeof(double), (size_t)cnt, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+  }
+  if (rc != GOGP_OK) h->err = first_err;
+  return rc;
+}
+
+extern "C" int gogp_cg_produce(gogp_handle *h, const double *Z, int64_t m, double *mu, double *sigma, double tol,
+                               int32_t max_iter, gogp_cg_col *cols) {
+  const char *who = "cg_produce";
+  if (!h) return GOGP_EARG;
+  if (sparse_refusal(h)) return cg_refuse_handle(h, who);
+  if (m < 0 || (m > 0 && (!Z || !mu))) return cg_refuse(h, who, GOGP_EARG, "need Z and mu for m > 0, m >= 0");
+  if (sigma)
+    if (const char *why = cg_tol_refusal(tol, max_iter)) return cg_refuse(h, who, GOGP_EARG, why);
+  if (!h->cg_have || !h->cg_solved) return cg_refuse(h, who, GOGP_ESTATE, "no solution (gogp_cg_solve)");
+  const int D = h->D;
+  for (int64_t i = 0; i < m * D; ++i)
+    if (!std::isfinite(Z[i])) return cg_refuse(h, who, GOGP_EARG, "non-finite test point");
+  HIPCHK(h, hipSetDevice(h->device));
+  hipStream_t s = h->s;
+  h->cg_products = h->cg_blocks = 0;
+  if (m == 0) return GOGP_OK;
+  const int64_t N = h->cg_N, npad = h->cg_npad;
+  // layout of cg_ks: 64 rows of k* (npad each), 64 test points, prior, q, mu, sigma (64 each)
+  int rc = h->cg_ks.reserve(h, ((size_t)CG_MAX_T * npad + (size_t)CG_MAX_T * (D + 4)) * sizeof(double));
+  if (rc == GOGP_OK) rc = cg_reserve_part(h, CG_MAX_T);
+  if (rc == GOGP_OK) rc = h->cg_part.reserve(h, (size_t)kmm_slabs(CG_MAX_T, N) * 64 * sizeof(double));
+  if (rc != GOGP_OK) return rc;
+  double *Ks = h->cg_ks.as<double>(), *dZ = Ks + (size_t)CG_MAX_T * npad, *prior = dZ + (size_t)CG_MAX_T * D;
+  double *dq = prior + CG_MAX_T, *dmu = dq + CG_MAX_T, *dsg = dmu + CG_MAX_T;
+  CgSmall sm;
+  cg_small_layout(h->cg_small.as<char>(), h->cg_rp, &sm);
+  const CgState cs{sm.sc, sm.st};
+  std::string first_err;
+  int ret = GOGP_OK;
+  for (int64_t j0 = 0; j0 < m; j0 += CG_MAX_T) {
+    const int cnt = (int)std::min<int64_t>(CG_MAX_T, m - j0);
+    HIPCHK(h, hipMemsetAsync(dZ, 0, (size_t)CG_MAX_T * D * sizeof(double), s));
+    HIPCHK(h, hipMemcpyAsync(dZ, Z + j0 * D, (size_t)cnt * D * sizeof(double), hipMemcpyHostToDevice, s));
+    // the mean: rows = the test points, columns = X, one right-hand side alpha
+    launch_kmm(s, h->cg_P, D, dZ, cnt, h->cg_X, N, h->cg_alpha, npad, 1, nullptr, kmm_slabs(cnt, N), 0,
+               h->cg_part.as<double>(), dmu, CG_MAX_T);
+    ++h->cg_products;
+    HIPCHK(h, hipMemcpyAsync(mu + j0, dmu, (size_t)cnt * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (sigma) {
+      launch_cross(s, h->cg_P, D, h->cg_X, N, npad, dZ, cnt, CG_MAX_T, Ks, npad, false);
+      launch_prior(s, h->cg_P, dZ, cnt, prior);
+      double *xs = nullptr;
+      rc = cg_block_solve(h, who, Ks, cnt, tol, max_iter, &xs, cols ? cols + j0 : nullptr, (int)j0);
+      if (rc != GOGP_OK && rc != GOGP_ENOCONV) {
+        (void)hipStreamSynchronize(s);  // the copy of mu into the caller's array must not outlive the call
+        return rc;
+      }
+      if (rc != GOGP_OK && ret == GOGP_OK) ret = rc, first_err = h->err;
+      launch_cg_dots(s, Ks, xs, npad, N, cnt, CG_DOT_PLAIN, 0, tol, xs + 5 * (size_t)cnt * npad, dq, cs);
+      launch_sigma(s, prior, dq, cnt, dsg);
+      HIPCHK(h, hipMemcpyAsync(sigma + j0, dsg, (size_t)cnt * sizeof(double), hipMemcpyDeviceToHost, s));
+    } else if (cols) {
+      for (int t = 0; t < cnt; ++t) cols[j0 + t] = gogp_cg_col();
+    }
+    HIPCHK(h, hipStreamSynchronize(s));
+    HIPCHK(h, hipGetLastError());
+  }
+  if (ret != GOGP_OK) h->err = first_err;
+  return ret;
+}
+
 // ---- non-Gaussian likelihoods by the Laplace approximation (laplace.hip) -----------------------------------------------
 // No reference counterpart.  The formulas are in laplace.hip and DESIGN.md section 4 "Laplace".  Every Newton step is
 // one non-eager factorize_t<double> of B = I + diag(sw) K diag(sw) -- the Gram stage scales K (Sweep::build_gram), the
@@ -5344,6 +5820,11 @@ extern "C" int gogp_set_option(gogp_handle *h, const char *name, int64_t value) 
   if (strcmp(name, "sparse_chunk") == 0) {  // gogp_sparse_*: rows of X per pass
     if (value < 256 || value > 65536 || value % 256) return fail(h, GOGP_EARG, "sparse_chunk must be a multiple of 256 in 256..65536");
     h->sp_chunk = value;
+    return GOGP_OK;
+  }
+  if (strcmp(name, "cg_check") == 0) {  // gogp_cg_*: iterations between two looks at the status word; no result depends on it
+    if (value < 1 || value > 1024) return fail(h, GOGP_EARG, "cg_check must be 1..1024");
+    h->cg_check = (int)value;
     return GOGP_OK;
   }
   if (strcmp(name, "laplace_max_iter") == 0) {  // gogp_laplace_observe: Newton steps at the most

@@ -593,6 +593,59 @@ void launch_select_step(hipStream_t s, const DevParams *p, int ndim, const doubl
 void launch_select_final(hipStream_t s, const double *X, int64_t N, int ndim, const SelectBufs &b, bool gather);
 hipError_t select_run(hipStream_t s, const DevParams *p, int ndim, const double *X, int64_t N, int64_t M, double tol,
                       int max_blocks, const double *d0, const SelectBufs &b, int64_t *m_out);
+// cg.hip (gogp_cg_*): matrix-free preconditioned conjugate gradients on up to CG_MAX_T systems in lock-step.  A block of
+// T vectors lies as T rows of ld doubles (ld >= n); the launchers read and write the elements i < n of the rows t < T and
+// nothing else, unless stated.
+// launch_kmm: Out[t][i] = sum_{j < cols} k(a_i, b_j) V[t][j] (+ diag[i] V[t][i]: diag != nullptr, which needs A == B and
+// rows == cols) for i < rows, t < T <= CG_MAX_T, on v_mfma_f64_16x16x4_f64; Out[t][i] = 0 for rows <= i < ldo.  A: rows x
+// ndim, B: cols x ndim, read on their first rows / cols rows only; V is read on t < T, j < cols only; noise_var of *p is
+// NOT added.  The column tiles (64 columns each) are split into nslab slabs (1 <= nslab <= KMM_SLABS_MAX; kmm_slabs gives
+// the product's choice, which depends on rows and cols alone); part: nslab * T * rpad doubles, rpad = rows rounded up
+// to 64, every one of which is written: part[(slab * T + t) * rpad + i]; the finish kernel adds them in slab order.
+// max_blocks > 0 caps the grid (tests: a workgroup that walks several row tiles and slabs).
+// launch_cg_dots: out-of-place partial sums (part: T * cg_dot_blocks(n) doubles) and a final kernel per column that adds
+// them in a fixed order and, by `mode`, updates the per-column state of the iteration (CgState; cg.hip states the modes).
+// launch_cg_update_xr: x += a p, r -= a q; launch_cg_update_p: p = z + beta p; both leave a frozen column untouched.
+// launch_cg_scale: out = in o w - sub (w == nullptr: in; sub == nullptr: nothing subtracted); w has n entries.
+// launch_cg_status: st.status[0] = columns t < T not frozen, st.status[1] = first column + 1 with a bad p^T q, or 0.
+constexpr int CG_MAX_T = GOGP_CG_MAX_RHS;
+constexpr int KMM_SLABS_MAX = 64;
+enum CgDotMode { CG_DOT_PLAIN = 0, CG_DOT_BNORM = 1, CG_DOT_RHO0 = 2, CG_DOT_PQ = 3, CG_DOT_RR = 4, CG_DOT_BETA = 5 };
+// per-column state on the device: CG_SC_* rows of CG_MAX_T doubles in sc, CG_ST_* rows of CG_MAX_T ints in st
+enum { CG_SC_RHO = 0, CG_SC_A = 1, CG_SC_BETA = 2, CG_SC_BNORM2 = 3, CG_SC_RR = 4, CG_SC_PQ = 5, CG_SC_ROWS = 6 };
+enum { CG_ST_FROZEN = 0, CG_ST_ITERS = 1, CG_ST_BAD = 2, CG_ST_STATUS = 3, CG_ST_ROWS = 4 };
+struct CgState {
+  double *sc = nullptr;  // CG_SC_ROWS * CG_MAX_T
+  int *st = nullptr;     // CG_ST_ROWS * CG_MAX_T
+};
+int kmm_slabs(int64_t rows, int64_t cols);
+void launch_kmm(hipStream_t s, const DevParams *p, int ndim, const double *A, int64_t rows, const double *B, int64_t cols,
+                const double *V, int64_t ldv, int T, const double *diag, int nslab, int max_blocks, double *part,
+                double *Out, int64_t ldo);
+int cg_dot_blocks(int64_t n);
+void launch_cg_dots(hipStream_t s, const double *A, const double *B, int64_t ld, int64_t n, int T, int mode, int it,
+                    double tol, double *part, double *out, CgState cs);
+void launch_cg_update_xr(hipStream_t s, double *x, double *r, const double *p, const double *q, int64_t ld, int64_t n, int T,
+                         CgState cs);
+void launch_cg_update_p(hipStream_t s, double *p, const double *z, int64_t ld, int64_t n, int T, CgState cs);
+void launch_cg_scale(hipStream_t s, const double *in, const double *w, const double *sub, int64_t ld, int64_t n, int T,
+                     double *out);
+void launch_cg_status(hipStream_t s, int T, CgState cs);
+// The preconditioner P = L L^T + D (cg.hip).  launch_cg_diag: d_i = noise_var + v_i (v == nullptr: 0), dis_i = d_i^-1/2
+// for i < n and 0 for n <= i < npad.  launch_cg_scale_factor: Ls = D^-1/2 L in place on the r columns of the column-major
+// factor (column k at Lt + k * ldn; rows >= n are neither read nor written).  launch_cg_capacitance: C (rp x rp, rp = r
+// rounded up to 16) = I + Ls^T Ls, both triangles.  launch_cg_lst: W[t][k] = sum_i Ls[i][k] dis_i R[t][i] (W: T rows of rp
+// doubles; part: cg_lst_slabs(n) * T16 * rp doubles, T16 = T rounded up to 16).  launch_cg_small_mm: Y[t][k] = sum_k'
+// Cinv[k][k'] W[t][k'].  launch_cg_precond: Z[t][i] = dis_i (dis_i R[t][i] - sum_k Ls[i][k] Y[t][k]); r == 0: Jacobi.
+int cg_lst_slabs(int64_t n);
+void launch_cg_diag(hipStream_t s, const DevParams *p, const double *v, int64_t n, int64_t npad, double *d, double *dis);
+void launch_cg_scale_factor(hipStream_t s, double *Lt, int64_t ldn, int64_t n, int r, const double *dis);
+void launch_cg_capacitance(hipStream_t s, const double *Ls, int64_t ldn, int64_t n, int r, int rp, double *C);
+void launch_cg_lst(hipStream_t s, const double *Ls, int64_t ldn, int64_t n, int r, int rp, const double *dis,
+                   const double *R, int64_t ld, int T, double *part, double *W);
+void launch_cg_small_mm(hipStream_t s, const double *Cinv, int r, int rp, const double *W, int T, double *Y);
+void launch_cg_precond(hipStream_t s, const double *Ls, int64_t ldn, int64_t n, int r, int rp, const double *dis,
+                       const double *R, const double *Y, int64_t ld, int T, double *Z);
 // laplace.hip (gogp_laplace_*): the passes around the factorisation of B = I + diag(sw) K diag(sw).  Vectors hold npad
 // doubles (npad a multiple of 256) and leave every launcher zero from row n on.
 // launch_lap_site: g, W, sw = sqrt(W), b = W f + g, rho of the rows i < n; part: 5 * npad / 256 doubles of block results;

@@ -260,6 +260,24 @@ struct gogp_handle : EvalBufs, EvalState {
   Workspace sp_mws;                // state of the multi observe, sized by gogp_sparse_multi_set_outputs (api.hip: SparseMultiBufs)
   Workspace sp_mscr;               // scratch sized by the chunk: the partials of launch_sparse_xty, the padded chunk of Y
   Workspace sp_mmu;                // gogp_sparse_multi_produce: mpad x 128 means
+  // the iterative exact GP (gogp_cg_*, cg.hip): a data set of its own, resident; nothing of the handle's other state is
+  // touched (the parameters too are a copy of its own, so that devP keeps what the last evaluation uploaded)
+  double *cg_X = nullptr, *cg_y = nullptr, *cg_v = nullptr;  // N x D (+ slack, npad rows), npad, npad (nullptr: no variances)
+  double *cg_d = nullptr, *cg_dis = nullptr, *cg_alpha = nullptr;  // D, D^-1/2, alpha: npad doubles each
+  DevParams *cg_P = nullptr;
+  int64_t cg_N = 0, cg_npad = 0;
+  bool cg_have = false, cg_solved = false;
+  int cg_rank = 0, cg_rp = 0;      // columns of the factor in use and their count rounded up to 16
+  int64_t cg_ldn = 0;
+  int cg_check = 8;                // option "cg_check": iterations between two looks at the status word
+  int cg_products = 0, cg_blocks = 0;  // counters of the call in progress (gogp_cg_last_info)
+  double cg_yta = 0.0;
+  double cg_vmin = 0.0;            // the smallest noise variance given (0 without variances)
+  Workspace cg_L;                  // Ls = D^-1/2 L, column-major, `rank` columns of cg_ldn doubles
+  Workspace cg_small;              // C^-1 (rp x rp), W and Y (CG_MAX_T x rp each), the per-column state
+  Workspace cg_vec;                // a block's six vectors, the dots' partials and results
+  Workspace cg_part;               // the slab partials of the product and of the skinny transposed product
+  Workspace cg_ks;                 // gogp_cg_produce: 64 rows of k*, the test points, prior, q, mu
   // the Laplace approximation (gogp_laplace_*, laplace.hip; api.hip: LapVecs).  B's factor lies in bufL / Dinv, B^-1 and
   // then the gradient's weight matrix in bufA; only vectors are its own (released with the N buffers).
   Workspace lap_ws;

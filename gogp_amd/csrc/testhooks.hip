@@ -2454,3 +2454,125 @@ extern "C" int gogp_test_pgrad(int device, const gogp_test_kparams *kparams, int
                             ev != 0);
              });
 }
+
+// ---- the kernels of cg.hip (the iterative exact GP), through their product launchers (tests/test_cg_kernels.py).  The
+// kernels guard every access by the sizes given, so the hooks hold the arrays to exactly those: a block of T vectors
+// needs (T - 1) * ld + n elements, the per-column state CG_SC_ROWS / CG_ST_ROWS rows of GOGP_CG_MAX_RHS.
+namespace {
+bool cg_block_ok(int64_t len, int64_t ld, int64_t n, int T) { return covers(len, 0, ld, T, n, 1, 0); }
+bool cg_dims_ok(int64_t ld, int64_t n, int T) { return n >= 1 && n <= SH_COUNT_MAX && ld >= n && T >= 1 && T <= CG_MAX_T; }
+bool cg_state_ok(int64_t sc_len, int64_t st_len) { return sc_len >= CG_SC_ROWS * CG_MAX_T && st_len >= CG_ST_ROWS * CG_MAX_T; }
+}  // namespace
+
+extern "C" int gogp_test_kmm_slabs(int64_t rows, int64_t cols) {
+  if (rows < 1 || cols < 1) return -1;
+  return kmm_slabs(rows, cols);
+}
+
+extern "C" int gogp_test_cg_dot_blocks(int64_t n) { return n < 1 ? -1 : cg_dot_blocks(n); }
+
+// B == NULL (b_len 0): the square product, columns = rows = the rows of A; diag only then
+extern "C" int gogp_test_kmm(int device, const gogp_test_kparams *kparams, const double *A, int64_t a_len, int64_t rows,
+                             const double *B, int64_t b_len, int64_t cols, const double *V, int64_t v_len, int64_t ldv, int T,
+                             const double *diag, int64_t diag_len, int nslab, int max_blocks, double *part, int64_t part_len,
+                             double *Out, int64_t out_len, int64_t ldo) {
+  if (!kparams || !A || !V || !part || !Out || !gram_args_ok(kparams, 1, 0, 0)) return GOGP_EARG;
+  if (kparams->nevents != 0) return GOGP_EARG;  // the product has no instance with event discounts
+  if (rows < 1 || rows > GR_NPAD_MAX || cols < 1 || cols > GR_NPAD_MAX || T < 1 || T > CG_MAX_T) return GOGP_EARG;
+  if (nslab < 1 || nslab > KMM_SLABS_MAX || max_blocks < 0) return GOGP_EARG;
+  const int ndim = kparams->ndim;
+  if (B ? b_len < cols * ndim : (b_len != 0 || cols != rows)) return GOGP_EARG;
+  if (diag ? (B != nullptr || diag_len < rows) : diag_len != 0) return GOGP_EARG;
+  const int64_t rpad = (rows + 63) / 64 * 64;
+  if (a_len < rows * ndim || !cg_block_ok(v_len, ldv, cols, T) || part_len < (int64_t)nslab * T * rpad || ldo < rows ||
+      out_len < (int64_t)T * ldo)
+    return GOGP_EARG;
+  const DevParams hp = to_dev(*kparams);
+  return run(device, {rd(&hp, 1, sizeof hp), rd(A, a_len), opt(rd(B, b_len)), rd(V, v_len), opt(rd(diag, diag_len)),
+                      io(part, part_len), io(Out, out_len)},
+             [&](const Dev &d) {
+               launch_kmm(0, d.as<DevParams>(0), ndim, d[1], rows, B ? d[2] : d[1], cols, d[3], ldv, T, d[4], nslab,
+                          max_blocks, d[5], d[6], ldo);
+             });
+}
+
+// out may be NULL (length 0) except in mode CG_DOT_PLAIN; st holds 32-bit integers
+extern "C" int gogp_test_cg_dots(int device, const double *A, int64_t a_len, const double *B, int64_t b_len, int64_t ld,
+                                 int64_t n, int T, int mode, int it, double tol, double *part, int64_t part_len, double *out,
+                                 int64_t out_len, double *sc, int64_t sc_len, int32_t *st, int64_t st_len) {
+  if (!A || !B || !part || !sc || !st || !cg_dims_ok(ld, n, T) || mode < CG_DOT_PLAIN || mode > CG_DOT_BETA) return GOGP_EARG;
+  if (!cg_block_ok(a_len, ld, n, T) || !cg_block_ok(b_len, ld, n, T) || part_len < (int64_t)T * cg_dot_blocks(n) ||
+      !cg_state_ok(sc_len, st_len))
+    return GOGP_EARG;
+  if (out ? out_len < T : (out_len != 0 || mode == CG_DOT_PLAIN)) return GOGP_EARG;
+  return run(device, {rd(A, a_len), rd(B, b_len), io(part, part_len), opt(io(out, out_len)), io(sc, sc_len), io(st, st_len, 4)},
+             [&](const Dev &d) {
+               launch_cg_dots(0, d[0], d[1], ld, n, T, mode, it, tol, d[2], d[3], CgState{d[4], d.as<int>(5)});
+             });
+}
+
+extern "C" int gogp_test_cg_update_xr(int device, double *x, int64_t x_len, double *r, int64_t r_len, const double *p,
+                                      int64_t p_len, const double *q, int64_t q_len, int64_t ld, int64_t n, int T,
+                                      const double *sc, int64_t sc_len, const int32_t *st, int64_t st_len) {
+  if (!x || !r || !p || !q || !sc || !st || !cg_dims_ok(ld, n, T) || !cg_state_ok(sc_len, st_len)) return GOGP_EARG;
+  if (!cg_block_ok(x_len, ld, n, T) || !cg_block_ok(r_len, ld, n, T) || !cg_block_ok(p_len, ld, n, T) ||
+      !cg_block_ok(q_len, ld, n, T))
+    return GOGP_EARG;
+  return run(device, {io(x, x_len), io(r, r_len), rd(p, p_len), rd(q, q_len), rd(sc, sc_len), rd(st, st_len, 4)},
+             [&](const Dev &d) {
+               launch_cg_update_xr(0, d[0], d[1], d[2], d[3], ld, n, T, CgState{d[4], d.as<int>(5)});
+             });
+}
+
+extern "C" int gogp_test_cg_update_p(int device, double *p, int64_t p_len, const double *z, int64_t z_len, int64_t ld,
+                                     int64_t n, int T, const double *sc, int64_t sc_len, const int32_t *st, int64_t st_len) {
+  if (!p || !z || !sc || !st || !cg_dims_ok(ld, n, T) || !cg_state_ok(sc_len, st_len)) return GOGP_EARG;
+  if (!cg_block_ok(p_len, ld, n, T) || !cg_block_ok(z_len, ld, n, T)) return GOGP_EARG;
+  return run(device, {io(p, p_len), rd(z, z_len), rd(sc, sc_len), rd(st, st_len, 4)},
+             [&](const Dev &d) { launch_cg_update_p(0, d[0], d[1], ld, n, T, CgState{d[2], d.as<int>(3)}); });
+}
+
+// w (n entries) and sub (a block) may be NULL with length 0
+extern "C" int gogp_test_cg_scale(int device, const double *in, int64_t in_len, const double *w, int64_t w_len,
+                                  const double *sub, int64_t sub_len, int64_t ld, int64_t n, int T, double *out,
+                                  int64_t out_len) {
+  if (!in || !out || !cg_dims_ok(ld, n, T) || !cg_block_ok(in_len, ld, n, T) || !cg_block_ok(out_len, ld, n, T))
+    return GOGP_EARG;
+  if (w ? w_len < n : w_len != 0) return GOGP_EARG;
+  if (sub ? !cg_block_ok(sub_len, ld, n, T) : sub_len != 0) return GOGP_EARG;
+  return run(device, {rd(in, in_len), opt(rd(w, w_len)), opt(rd(sub, sub_len)), io(out, out_len)},
+             [&](const Dev &d) { launch_cg_scale(0, d[0], d[1], d[2], ld, n, T, d[3]); });
+}
+
+extern "C" int gogp_test_cg_status(int device, int T, int32_t *st, int64_t st_len) {
+  if (!st || T < 1 || T > CG_MAX_T || st_len < CG_ST_ROWS * CG_MAX_T) return GOGP_EARG;
+  return run(device, {io(st, st_len, 4)}, [&](const Dev &d) { launch_cg_status(0, T, CgState{nullptr, d.as<int>(0)}); });
+}
+
+// The preconditioner's application on a given scaled factor: Z = P^-1 R with Ls (r columns of ldn doubles, column-major),
+// dis (n) and Cinv (rp x rp, rp = r rounded up to 16; r == 0: Jacobi, Ls and Cinv NULL).  Runs launch_cg_lst,
+// launch_cg_small_mm and launch_cg_precond; C (rp x rp, may be NULL) receives launch_cg_capacitance's I + Ls^T Ls.
+extern "C" int gogp_test_cg_precond(int device, const double *Ls, int64_t ls_len, int64_t ldn, int64_t n, int r,
+                                    const double *dis, int64_t dis_len, const double *Cinv, int64_t cinv_len, const double *R,
+                                    int64_t r_len, int64_t ld, int T, double *Z, int64_t z_len, double *C, int64_t c_len) {
+  if (!dis || !R || !Z || !cg_dims_ok(ld, n, T) || r < 0 || r > GOGP_CG_MAX_RANK || dis_len < n) return GOGP_EARG;
+  if (!cg_block_ok(r_len, ld, n, T) || !cg_block_ok(z_len, ld, n, T)) return GOGP_EARG;
+  const int rp = (r + 15) / 16 * 16;
+  if (r > 0 ? (!Ls || !Cinv || ldn < n || !covers(ls_len, 0, ldn, r, n, 1, 0) || cinv_len < (int64_t)rp * rp)
+            : (Ls || Cinv || ls_len != 0 || cinv_len != 0))
+    return GOGP_EARG;
+  if (C ? (r < 1 || c_len < (int64_t)rp * rp) : c_len != 0) return GOGP_EARG;
+  const int rr = rp > 16 ? rp : 16;
+  const size_t wy = (size_t)CG_MAX_T * rr * sizeof(double);
+  const size_t pb = (size_t)cg_lst_slabs(n) * (size_t)((T + 15) / 16 * 16) * rr * sizeof(double);
+  return run(device, {opt(rd(Ls, ls_len)), rd(dis, dis_len), opt(rd(Cinv, cinv_len)), rd(R, r_len), io(Z, z_len),
+                      opt(io(C, c_len)), scratch(wy), scratch(wy), scratch(pb)},
+             [&](const Dev &d) {
+               if (C) launch_cg_capacitance(0, d[0], ldn, n, r, rp, d[5]);
+               if (r > 0) {
+                 launch_cg_lst(0, d[0], ldn, n, r, rp, d[1], d[3], ld, T, d[8], d[6]);
+                 launch_cg_small_mm(0, d[2], r, rp, d[6], T, d[7]);
+               }
+               launch_cg_precond(0, d[0], ldn, n, r, rp, d[1], d[3], d[7], ld, T, d[4]);
+             });
+}

@@ -735,6 +735,105 @@ class GP:
         self.SetSparse(X, Y, U)
         return idx
 
+    # ---- the iterative exact GP: matrix-free preconditioned conjugate gradients (gogp_cg_*) ----
+    def SetCG(self, X, Y, v=None) -> None:
+        """The data of the iterative calls, a set of their own that stays on the device (gogp_cg_set_data): X (N x
+        NDim), Y (N) and, optionally, per-observation noise variances v (N, finite and >= 0).  ``SetCG(None, None)``
+        clears them.  Nothing else of the process changes."""
+        if X is None and Y is None and v is None:
+            self._cg_n = 0
+            self._check(_lib.lib().gogp_cg_set_data(self._h, None, None, None, 0))
+            return
+        xs = np.ascontiguousarray(_arr(X).reshape(-1, self.NDim))
+        ys = np.ascontiguousarray(_arr(Y).reshape(-1))
+        if len(xs) != len(ys):
+            raise ValueError("SetCG: len(X) != len(Y)")
+        va = None
+        if v is not None:
+            va = np.ascontiguousarray(_arr(v).reshape(-1))
+            if va.size != len(ys):
+                raise ValueError("SetCG: one variance per observation")
+        self._check(_lib.lib().gogp_cg_set_data(self._h, _dp(xs) if len(xs) else None, _dp(ys) if len(ys) else None,
+                                                _dp(va), len(ys)))
+        self._cg_n = len(ys)
+
+    @staticmethod
+    def _cg_cols(cols, k):
+        return {"iterations": np.array([cols[i].iterations for i in range(k)], dtype=np.int64),
+                "converged": np.array([bool(cols[i].converged) for i in range(k)]),
+                "rel_residual": np.array([cols[i].rel_residual for i in range(k)]),
+                "rel_residual_recurrence": np.array([cols[i].rel_residual_recurrence for i in range(k)])}
+
+    def _cg_info(self) -> dict:
+        info = _lib.CCgInfo()
+        self._check(_lib.lib().gogp_cg_last_info(self._h, ctypes.byref(info)))
+        return {"rank_used": int(info.rank_used), "products": int(info.products), "blocks": int(info.blocks),
+                "yt_alpha": float(info.yt_alpha)}
+
+    def _cg_finish(self, rc: int, result):
+        """GOGP_ENOCONV raises ConvergenceError carrying the results that were written; other errors as usual."""
+        if rc == _lib.GOGP_ENOCONV:
+            e = ConvergenceError(_lib.lib().gogp_last_error(self._h).decode())
+            e.result = result
+            raise e
+        self._check(rc)
+        return result
+
+    def CGSolve(self, x, rank: int = 64, tol: float = 1e-8, max_iter: int = 1000, piv_tol=None) -> dict:
+        """Solve K^ alpha = Y at x = log theta by preconditioned conjugate gradients, K^ = k(X, X) + sigma^2 I + diag(v)
+        never stored (gogp_cg_solve).  The preconditioner is a pivoted-Cholesky factor of k(X, X) of at most ``rank``
+        columns (0: Jacobi) that stops once no residual variance exceeds ``piv_tol`` (None: the sparse calls' jitter).
+        Returns the info fields (rank_used, products, blocks, yt_alpha) and the column's iterations, converged,
+        rel_residual (true, from one more product) and rel_residual_recurrence.  alpha, theta and the preconditioner
+        stay for CGAlpha, CGSolveColumns and CGProduce.  Not converged within max_iter: ConvergenceError whose
+        ``result`` is this dict; alpha is stored all the same."""
+        xa = np.ascontiguousarray(_arr(x).reshape(-1))
+        info, col = _lib.CCgInfo(), (_lib.CCgCol * 1)()
+        rc = _lib.lib().gogp_cg_solve(self._h, _dp(xa if xa.size else np.zeros(1)), xa.size, int(rank),
+                                      -1.0 if piv_tol is None else float(piv_tol), float(tol), int(max_iter),
+                                      ctypes.byref(info), col)
+        out = {"rank_used": int(info.rank_used), "products": int(info.products), "blocks": int(info.blocks),
+               "yt_alpha": float(info.yt_alpha)}
+        out.update({k: v[0] for k, v in self._cg_cols(col, 1).items()})
+        self.cg_info = out
+        return self._cg_finish(rc, out)
+
+    def CGAlpha(self) -> np.ndarray:
+        """alpha of the last CGSolve (gogp_cg_get_alpha)."""
+        a = np.zeros(max(int(getattr(self, "_cg_n", 0)), 1))
+        self._check(_lib.lib().gogp_cg_get_alpha(self._h, _dp(a), int(getattr(self, "_cg_n", 0))))
+        return a[:int(getattr(self, "_cg_n", 0))]
+
+    def CGSolveColumns(self, B, tol: float = 1e-8, max_iter: int = 1000):
+        """(S, cols): K^ S[t] = B[t] for the T rows of B (T x N), in lock-step blocks of 64, with the parameters and
+        preconditioner of the last CGSolve (gogp_cg_solve_columns).  cols: the per-column arrays of CGSolve.  A column
+        has the same bits alone as inside a block."""
+        n = int(getattr(self, "_cg_n", 0))
+        b = np.ascontiguousarray(_arr(B).reshape(-1, n) if n else _arr(B).reshape(0, 0))
+        T = len(b)
+        S = np.zeros((T, n))
+        cols = (_lib.CCgCol * max(T, 1))()
+        rc = _lib.lib().gogp_cg_solve_columns(self._h, _dp(b) if T else None, T, float(tol), int(max_iter),
+                                              _dp(S) if T else None, cols)
+        self.cg_info = self._cg_info()
+        return self._cg_finish(rc, (S, self._cg_cols(cols, T)))
+
+    def CGProduce(self, z, sigma: bool = True, tol: float = 1e-8, max_iter: int = 1000):
+        """(mu, sigma) of the exact posterior at the test points z (m x NDim), latent and unclamped as Produce
+        (gogp_cg_produce): the mean is one rectangular matrix-free product with alpha; the deviations take one solve
+        per test point, 64 at a time.  ``sigma=False`` returns (mu, None) without any solve.  ``cg_info`` and
+        ``cg_cols`` keep the counters and the per-column results of the call."""
+        zs = np.ascontiguousarray(_arr(z).reshape(-1, self.NDim))
+        m = len(zs)
+        mu = np.zeros(m)
+        sg = np.zeros(m) if sigma else None
+        cols = (_lib.CCgCol * max(m, 1))()
+        rc = _lib.lib().gogp_cg_produce(self._h, _dp(zs) if m else None, m, _dp(mu) if m else None,
+                                        _dp(sg) if (sigma and m) else None, float(tol), int(max_iter), cols)
+        self.cg_info = self._cg_info()
+        self.cg_cols = self._cg_cols(cols, m)
+        return self._cg_finish(rc, (mu, sg))
+
     def SparseObserve(self, x) -> float:
         """The collapsed variational bound of Titsias (2009) at x = log theta (gogp_sparse_observe): a lower bound of
         the LML of the sparse data that costs O(N M^2)."""
@@ -2103,3 +2202,128 @@ def pgrad_check(kp, X: np.ndarray, n: int, npad: int, Z: np.ndarray, m: int, alp
     if rc != _lib.GOGP_OK:
         raise GogpError(rc, "test_pgrad")
     return part, dmu, dsigma
+
+
+# ---- the kernels of cg.hip (include/gogp_testhooks.h; tests/test_cg_kernels.py).  Flat host arrays in, copies of the in /
+# out arrays back; a refusal or a device error raises GogpError.  The per-column state: sc, float64 of 6 x 64 (rho, a,
+# beta, |b|^2, |r|^2, p^T q); st, int32 of 4 x 64 (frozen, iterations, bad, status).
+CG_DOT_MODES = {"plain": 0, "bnorm": 1, "rho0": 2, "pq": 3, "rr": 4, "beta": 5}
+
+
+def _i32(a, what):
+    if not isinstance(a, np.ndarray) or a.dtype != np.int32 or not a.flags.c_contiguous:
+        raise TypeError("%s: a C-contiguous int32 array" % what)
+    return a
+
+
+def _i32p(a):
+    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+
+
+def _opt(a, what):
+    return (None, 0) if a is None else (_dp(_vec(a, what)), a.size)
+
+
+def kmm_slabs(rows: int, cols: int) -> int:
+    """The slabs of column tiles the product splits rows x cols pairs into.  No device."""
+    r = int(_lib.hooks().gogp_test_kmm_slabs(rows, cols))
+    if r < 0:
+        raise GogpError(_lib.GOGP_EARG, "test_kmm_slabs")
+    return r
+
+
+def cg_dot_blocks(n: int) -> int:
+    """The partial sums per column of launch_cg_dots for vectors of n elements.  No device."""
+    r = int(_lib.hooks().gogp_test_cg_dot_blocks(n))
+    if r < 0:
+        raise GogpError(_lib.GOGP_EARG, "test_cg_dot_blocks")
+    return r
+
+
+def kmm_check(kp, A: np.ndarray, rows: int, B, cols: int, V: np.ndarray, ldv: int, T: int, diag, nslab: int,
+              part: np.ndarray, Out: np.ndarray, ldo: int, max_blocks: int = 0, device: int = -1):
+    """launch_kmm (test hook gogp_test_kmm): B None is the square product on the rows of A, the only form that takes
+    diag.  Returns copies of (part, Out)."""
+    A, V = _vec(A, "A"), _vec(V, "V")
+    part, Out = _vec(part, "part").copy(), _vec(Out, "Out").copy()
+    bp, bl = _opt(B, "B")
+    dg, dl = _opt(diag, "diag")
+    rc = _lib.hooks().gogp_test_kmm(device, ctypes.byref(kp), _dp(A), A.size, rows, bp, bl, cols, _dp(V), V.size, ldv, T,
+                                    dg, dl, nslab, max_blocks, _dp(part), part.size, _dp(Out), Out.size, ldo)
+    if rc != _lib.GOGP_OK:
+        raise GogpError(rc, "test_kmm")
+    return part, Out
+
+
+def cg_dots_check(A: np.ndarray, B: np.ndarray, ld: int, n: int, T: int, mode, it: int, tol: float, part: np.ndarray, out,
+                  sc: np.ndarray, st: np.ndarray, device: int = -1):
+    """launch_cg_dots (test hook gogp_test_cg_dots); mode: a key of CG_DOT_MODES or its number.  Returns copies of
+    (part, out, sc, st); out may be None except in mode "plain"."""
+    A, B = _vec(A, "A"), _vec(B, "B")
+    part, sc, st = _vec(part, "part").copy(), _vec(sc, "sc").copy(), _i32(st, "st").copy()
+    out = None if out is None else _vec(out, "out").copy()
+    rc = _lib.hooks().gogp_test_cg_dots(device, _dp(A), A.size, _dp(B), B.size, ld, n, T,
+                                        CG_DOT_MODES.get(mode, mode), it, float(tol), _dp(part), part.size, _dp(out),
+                                        0 if out is None else out.size, _dp(sc), sc.size, _i32p(st), st.size)
+    if rc != _lib.GOGP_OK:
+        raise GogpError(rc, "test_cg_dots")
+    return part, out, sc, st
+
+
+def cg_update_xr_check(x: np.ndarray, r: np.ndarray, p: np.ndarray, q: np.ndarray, ld: int, n: int, T: int, sc: np.ndarray,
+                       st: np.ndarray, device: int = -1):
+    """launch_cg_update_xr (test hook gogp_test_cg_update_xr); returns copies of (x, r)."""
+    x, r = _vec(x, "x").copy(), _vec(r, "r").copy()
+    p, q, sc, st = _vec(p, "p"), _vec(q, "q"), _vec(sc, "sc"), _i32(st, "st")
+    rc = _lib.hooks().gogp_test_cg_update_xr(device, _dp(x), x.size, _dp(r), r.size, _dp(p), p.size, _dp(q), q.size, ld, n, T,
+                                             _dp(sc), sc.size, _i32p(st), st.size)
+    if rc != _lib.GOGP_OK:
+        raise GogpError(rc, "test_cg_update_xr")
+    return x, r
+
+
+def cg_update_p_check(p: np.ndarray, z: np.ndarray, ld: int, n: int, T: int, sc: np.ndarray, st: np.ndarray,
+                      device: int = -1):
+    """launch_cg_update_p (test hook gogp_test_cg_update_p); returns a copy of p."""
+    p = _vec(p, "p").copy()
+    z, sc, st = _vec(z, "z"), _vec(sc, "sc"), _i32(st, "st")
+    rc = _lib.hooks().gogp_test_cg_update_p(device, _dp(p), p.size, _dp(z), z.size, ld, n, T, _dp(sc), sc.size, _i32p(st),
+                                            st.size)
+    if rc != _lib.GOGP_OK:
+        raise GogpError(rc, "test_cg_update_p")
+    return p
+
+
+def cg_scale_check(src: np.ndarray, w, sub, ld: int, n: int, T: int, out: np.ndarray, device: int = -1):
+    """launch_cg_scale (test hook gogp_test_cg_scale): out = src o w - sub, w and sub optional; returns a copy of out."""
+    src, out = _vec(src, "src"), _vec(out, "out").copy()
+    wp, wl = _opt(w, "w")
+    sp, sl = _opt(sub, "sub")
+    rc = _lib.hooks().gogp_test_cg_scale(device, _dp(src), src.size, wp, wl, sp, sl, ld, n, T, _dp(out), out.size)
+    if rc != _lib.GOGP_OK:
+        raise GogpError(rc, "test_cg_scale")
+    return out
+
+
+def cg_status_check(T: int, st: np.ndarray, device: int = -1):
+    """launch_cg_status (test hook gogp_test_cg_status); returns a copy of st."""
+    st = _i32(st, "st").copy()
+    rc = _lib.hooks().gogp_test_cg_status(device, T, _i32p(st), st.size)
+    if rc != _lib.GOGP_OK:
+        raise GogpError(rc, "test_cg_status")
+    return st
+
+
+def cg_precond_check(Ls, ldn: int, n: int, r: int, dis: np.ndarray, Cinv, R: np.ndarray, ld: int, T: int, Z: np.ndarray,
+                     C=None, device: int = -1):
+    """The preconditioner's application Z = P^-1 R on a given scaled factor (test hook gogp_test_cg_precond); r == 0:
+    Jacobi (Ls and Cinv None).  Returns a copy of Z, or of (Z, C) where C is given (it receives I + Ls^T Ls)."""
+    dis, R, Z = _vec(dis, "dis"), _vec(R, "R"), _vec(Z, "Z").copy()
+    lp, ll = _opt(Ls, "Ls")
+    cp, cl = _opt(Cinv, "Cinv")
+    C = None if C is None else _vec(C, "C").copy()
+    rc = _lib.hooks().gogp_test_cg_precond(device, lp, ll, ldn, n, r, _dp(dis), dis.size, cp, cl, _dp(R), R.size, ld, T,
+                                           _dp(Z), Z.size, _dp(C), 0 if C is None else C.size)
+    if rc != _lib.GOGP_OK:
+        raise GogpError(rc, "test_cg_precond")
+    return Z if C is None else (Z, C)

@@ -383,6 +383,63 @@ class GP {
                                 std::vector<double> &u, std::vector<double> &pivots) {
     return select(logtheta, nullptr, M, tol, idx, u, pivots);
   }
+  // ---- the iterative exact GP: matrix-free preconditioned conjugate gradients (gogp_cg_*) ----
+  // The data of the iterative calls (x: row-major N x NDim; v: per-observation noise variances, empty = none); all
+  // empty clears them.  Nothing else of the process changes.
+  void SetCG(const std::vector<double> &x, const std::vector<double> &y, const std::vector<double> &v = {}) {
+    if (x.empty() && y.empty() && v.empty()) {
+      cg_n_ = 0;
+      check(gogp_cg_set_data(h_, nullptr, nullptr, nullptr, 0));
+      return;
+    }
+    if (x.size() != y.size() * (size_t)NDim || (!v.empty() && v.size() != y.size())) throw Error(GOGP_EARG, "SetCG: sizes");
+    check(gogp_cg_set_data(h_, x.data(), y.data(), v.empty() ? nullptr : v.data(), (int64_t)y.size()));
+    cg_n_ = y.size();
+  }
+  // K^ alpha = y at logtheta with a pivoted-Cholesky preconditioner of at most `rank` columns (0: Jacobi; piv_tol < 0: the
+  // sparse calls' jitter).  Returns the status, as LaplaceObserve does: GOGP_OK or GOGP_ENOCONV (max_iter reached; every
+  // output written, alpha stored); anything else throws.
+  int CGSolve(const std::vector<double> &logtheta, int32_t rank, double tol, int32_t max_iter, gogp_cg_info *info,
+              gogp_cg_col *col = nullptr, double piv_tol = -1.0) {
+    const int rc = gogp_cg_solve(h_, logtheta.data(), (int64_t)logtheta.size(), rank, piv_tol, tol, max_iter, info, col);
+    if (rc != GOGP_ENOCONV) check(rc);
+    return rc;
+  }
+  std::vector<double> CGAlpha() {
+    std::vector<double> a(cg_n_ ? cg_n_ : 1, 0.0);
+    check(gogp_cg_get_alpha(h_, a.data(), (int64_t)cg_n_));
+    a.resize(cg_n_);
+    return a;
+  }
+  // K^ S[t] = B[t] for the T rows (of N) of b, in lock-step blocks of GOGP_CG_MAX_RHS; cols: one entry per row
+  int CGSolveColumns(const std::vector<double> &b, double tol, int32_t max_iter, std::vector<double> &s,
+                     std::vector<gogp_cg_col> *cols = nullptr) {
+    const int64_t T = cg_n_ ? (int64_t)(b.size() / cg_n_) : 0;
+    s.assign(b.size(), 0.0);
+    if (cols) cols->assign((size_t)T, gogp_cg_col());
+    const int rc = gogp_cg_solve_columns(h_, T ? b.data() : nullptr, T, tol, max_iter, T ? s.data() : nullptr,
+                                         cols && T ? cols->data() : nullptr);
+    if (rc != GOGP_ENOCONV) check(rc);
+    return rc;
+  }
+  // mu and (with_sigma) sigma of the exact posterior at the test points z (row-major m x NDim); sigma stays empty without
+  // it, and no system is solved then
+  int CGProduce(const std::vector<double> &z, bool with_sigma, double tol, int32_t max_iter, std::vector<double> &mu,
+                std::vector<double> &sigma, std::vector<gogp_cg_col> *cols = nullptr) {
+    const int64_t m = (int64_t)(z.size() / (size_t)NDim);
+    mu.assign((size_t)m, 0.0);
+    sigma.assign(with_sigma ? (size_t)m : 0, 0.0);
+    if (cols) cols->assign((size_t)m, gogp_cg_col());
+    const int rc = gogp_cg_produce(h_, m ? z.data() : nullptr, m, m ? mu.data() : nullptr,
+                                   with_sigma && m ? sigma.data() : nullptr, tol, max_iter, cols && m ? cols->data() : nullptr);
+    if (rc != GOGP_ENOCONV) check(rc);
+    return rc;
+  }
+  gogp_cg_info CGLastInfo() {
+    gogp_cg_info info;
+    check(gogp_cg_last_info(h_, &info));
+    return info;
+  }
   // SparseGradient and, from the same pass over the data, d bound / d U of the inducing points of SetSparse (dU:
   // row-major M x NDim)
   std::vector<double> SparseGradientInducing(std::vector<double> &dU) {
@@ -603,6 +660,7 @@ class GP {
   int p_ = 0;  // basis columns of SetBasis
   size_t sparse_m_ = 0;  // inducing points of SetSparse
   int sparse_t_ = 0;     // output columns of SetSparseOutputs
+  size_t cg_n_ = 0;      // observations of SetCG
 
   std::vector<double> pack(const std::vector<std::vector<double>> &x) const {
     std::vector<double> flat(x.size() * (size_t)NDim);

@@ -570,6 +570,74 @@ int gogp_sparse_select_inducing(gogp_handle *h, const double *x /* log theta */,
 int gogp_sparse_select_inducing_resident(gogp_handle *h, const double *x, int64_t len, int64_t M, double tol,
                                          int64_t *idx, double *pivots, double *U, int64_t *m_out, double *trace);
 
+/* Iterative exact GP: matrix-free preconditioned conjugate gradients (cg.hip; Gardner et al. 2018, Wang et al. 2019).
+ * The exact posterior at a size where no N x N matrix fits: K^ = k(X, X) + sigma^2 I + diag(v) is never stored, every
+ * product recomputes it from X on the matrix cores (v_mfma_f64_16x16x4_f64: a lane evaluates one k(x_i, x_j) and feeds it
+ * in as its A operand), for up to GOGP_CG_MAX_RHS right-hand sides at once.  The data are a set of their own, like the
+ * sparse calls': gogp_cg_set_data copies X (N x ndim), y (N) and v (N per-observation noise variances, finite and >= 0;
+ * NULL: none) to the device, where they stay; N == 0 with NULLs clears them.  Nothing else of the handle changes, and no
+ * dense, sparse, batch, multi-output, basis or Laplace call sees the CG state.
+ * gogp_cg_solve: theta = exp(x); the preconditioner P = L L^T + D at that theta, D = diag(sigma^2 + v_i) and L the
+ * N x rank_used pivoted-Cholesky factor of k(X, X) that gogp_sparse_select_inducing describes (cap `rank`, tolerance
+ * piv_tol; piv_tol < 0: 10^"sparse_jitter_log10"; rank == 0: plain Jacobi, P = D), applied by Woodbury's identity:
+ * Ls = D^-1/2 L, C = I + Ls^T Ls, P^-1 R = D^-1/2 (R' - Ls C^-1 Ls^T R'), R' = D^-1/2 R; then K^ alpha = y.  alpha, theta and
+ * the preconditioner stay for gogp_cg_get_alpha, gogp_cg_solve_columns and gogp_cg_produce; info->yt_alpha = y^T alpha is
+ * the data-fit term (the log-determinant is not computed).  Every column c of a block runs
+ *     x = 0, r = b, z = P^-1 r, p = z, rho = r^T z
+ *     q = K^ p; a = rho / p^T q; x += a p; r -= a q; |r| <= tol |b|: the column FREEZES (its count is recorded, a = beta = 0
+ *     from then on); z = P^-1 r; rho' = r^T z; beta = rho' / rho; p = z + beta p; rho = rho'
+ * with the columns of a block advancing together.  The freeze decision is taken on the device in the iteration where it
+ * happens; the host reads a status word every "cg_check" iterations (option, default 8) to stop launching, so no bit and no
+ * count depends on it.  b = 0 gives zeros after 0 iterations.  After the block stops ONE more product gives the true
+ * |b - K^ x| / |b| (rel_residual) beside the recurrence's value.  A column that did not freeze within max_iter: the call
+ * returns GOGP_ENOCONV, every output is written, converged = 0 for it.  p^T q not positive and finite: GOGP_ENOTPD, and
+ * gogp_last_error names the column.  Every sum has a fixed order (slab partials, two-stage dot products, no atomics, no
+ * spin-waits): two identical calls return identical bits, and a column's solution has the same bits alone as in a block.
+ * gogp_cg_solve_columns: K^ s_t = b_t for T >= 0 right-hand sides (rows of N), in blocks of GOGP_CG_MAX_RHS, at the theta
+ * and preconditioner of the last gogp_cg_solve.  gogp_cg_produce: mu_j = sum_i k(z_j, x_i) alpha_i (one rectangular
+ * product) and, unless sigma == NULL, sigma_j = sqrt(k(z_j, z_j) - k*_j^T K^^-1 k*_j) -- latent and unclamped as gogp_produce
+ * defines it -- from one solve per 64 test points; sigma == NULL runs no solve.  gogp_cg_last_info: the counters of the
+ * last of these three calls (blocks: lock-step blocks; products: matrix-free products LAUNCHED -- the one figure that
+ * depends on "cg_check", because the launches run on until the host's next look at the status word: between iterations
+ * + 1 and iterations + cg_check per block).
+ * GOGP_ESTATE: no CG data, or columns / produce / get_alpha before a solve.  GOGP_EARG: NULLs, len != P, a non-finite
+ * value in X, y, x, B or Z, a negative or non-finite v, rank outside 0 .. GOGP_CG_MAX_RANK, tol <= 0 or non-finite,
+ * max_iter < 1, a size mismatch (n, T < 0, m < 0), sigma^2 + min v_i not positive (D is inverted), and the kinds of
+ * handle the sparse calls refuse (precision = 32, sharded, event discounts).  GOGP_ENOMEM: the factor (8 N_pad rank bytes, N_pad = N rounded up to 256) could not be
+ * allocated; gogp_last_error carries the size.
+ * Device memory: X, y, v, D and alpha (N (ndim + 5) doubles), the factor, C^-1 (rank^2), and per block of T columns six
+ * vectors each (x, r, p, z, q, b: 48 N T bytes) plus the product's slab partials (8 N T kmm slabs; one slab from
+ * N = 131072 on).  C is factored and inverted on the host (rank^3 flops, once per solve); everything per iteration runs
+ * on the device.
+ * Measured on one MI355X (tools/cg_probe.py, profiles/cg.txt; D = 8, medians of three): one CG iteration at rank 0 for
+ * T = 1 / 16 / 64 columns: Normal 22.8 / 23.3 / 31.8 ms at N = 65536, 352 / 369 / 524 ms at N = 262144 and 5.4 / - / 8.1 s at
+ * N = 1048576 (one measurement), Matern-5/2 26.6 / 27.0 / 35.3 and 409 / 431 / 576 ms: 1.6 - 2.05e11 kernel evaluations per
+ * second, and 64 right-hand sides cost 1.33 - 1.52 of one.  gogp_cg_solve at N = 16384, tol = 1e-8, rank 0 / 64 / 256 / 1024:
+ * Normal 437 / 140 / 38 / 7 iterations in 641 / 228 / 74 / 270 ms, Matern-5/2 778 / 356 / 166 / 62 in 1329 / 648 / 328 / 362 ms,
+ * beside 30 ms for the dense gogp_absorb, which is the call at that size; the two alpha differ by 6e-9 - 1e-8 of their
+ * norm.  gogp_cg_produce at rank 256: the means of 1024 points 2 ms, with sigma 1.2 s (Normal) and 4.8 s (Matern-5/2).
+ * Out of scope: the log-determinant and the gradient's trace term (stochastic Lanczos quadrature / probe
+ * vectors), the symmetry of K in the product, event discounts, several GPUs.  DESIGN.md section 4, "Iterative (CG)". */
+#define GOGP_CG_MAX_RANK 1024
+#define GOGP_CG_MAX_RHS 64 /* systems per lock-step block */
+typedef struct {
+  int32_t iterations, converged;
+  double rel_residual, rel_residual_recurrence;
+} gogp_cg_col;
+typedef struct {
+  int32_t rank_used, products, blocks;
+  double yt_alpha;
+} gogp_cg_info;
+int gogp_cg_set_data(gogp_handle *h, const double *X, const double *y, const double *v /* may be NULL */, int64_t N);
+int gogp_cg_solve(gogp_handle *h, const double *x /* log theta */, int64_t len, int32_t rank, double piv_tol, double tol,
+                  int32_t max_iter, gogp_cg_info *info, gogp_cg_col *col /* 1, may be NULL */);
+int gogp_cg_get_alpha(gogp_handle *h, double *alpha, int64_t n);
+int gogp_cg_solve_columns(gogp_handle *h, const double *B /* T rows of N */, int64_t T, double tol, int32_t max_iter,
+                          double *S /* T rows of N */, gogp_cg_col *cols /* T, may be NULL */);
+int gogp_cg_produce(gogp_handle *h, const double *Z, int64_t m, double *mu, double *sigma /* may be NULL */, double tol,
+                    int32_t max_iter, gogp_cg_col *cols /* m, may be NULL */);
+int gogp_cg_last_info(gogp_handle *h, gogp_cg_info *info);
+
 /* k independent Observe + Gradient evaluations at once: handle hs[i] (each created and given
  * its data separately; they may hold the same data) evaluates x[i*len .. (i+1)*len) from its own
  * host thread, so the dependent launch chains of the k evaluations overlap on the GPU.

@@ -644,6 +644,47 @@ int gogp_test_pgrad(int device, const gogp_test_kparams *kparams, int ev, const 
                     const double *Wt, int64_t wt_len, int64_t ld, const double *sigma, int64_t sigma_len, double *part,
                     int64_t part_len, double *dmu, int64_t dmu_len, double *dsigma, int64_t dsigma_len);
 
+/* ---- the kernels of cg.hip (the iterative exact GP; tests/test_cg_kernels.py), through their product launchers
+ * (common.h states what each reads and writes).  A block of T <= 64 vectors: T rows of ld >= n doubles, (T - 1) * ld + n
+ * elements at least.  The per-column state: sc, 6 rows of 64 doubles (rho, a, beta, |b|^2, |r|^2, p^T q); st, 4 rows of 64
+ * 32-bit integers (frozen, iterations, bad, status).  Every argument is refused before the device is touched. */
+/* kmm_slabs / cg_dot_blocks themselves; -1: bad arguments.  No device. */
+int gogp_test_kmm_slabs(int64_t rows, int64_t cols);
+int gogp_test_cg_dot_blocks(int64_t n);
+/* launch_kmm: Out (in / out; T rows of ldo >= rows) [t][i] = sum_j k(a_i, b_j) V[t][j] (+ diag[i] V[t][i]), zero for
+ * rows <= i < ldo; part (in / out): nslab x T x rpad, rpad = rows rounded up to 64.  B NULL (length 0): the square
+ * product on the rows of A, the only form that takes diag (rows entries; NULL with length 0: none).  1 <= nslab <= 64;
+ * max_blocks 0: no cap on the grid. */
+int gogp_test_kmm(int device, const gogp_test_kparams *kparams, const double *A, int64_t a_len, int64_t rows,
+                  const double *B, int64_t b_len, int64_t cols, const double *V, int64_t v_len, int64_t ldv, int T,
+                  const double *diag, int64_t diag_len, int nslab, int max_blocks, double *part, int64_t part_len,
+                  double *Out, int64_t out_len, int64_t ldo);
+/* launch_cg_dots: the T dot products A[t] . B[t] and, by mode (0 plain, 1 |b|^2, 2 rho0, 3 p^T q, 4 |r|^2 and the freeze
+ * test, 5 beta), the update of sc / st (in / out).  part (in / out): T x gogp_test_cg_dot_blocks(n); out (in / out, T;
+ * NULL with length 0 except in mode 0) receives the dot products. */
+int gogp_test_cg_dots(int device, const double *A, int64_t a_len, const double *B, int64_t b_len, int64_t ld, int64_t n,
+                      int T, int mode, int it, double tol, double *part, int64_t part_len, double *out, int64_t out_len,
+                      double *sc, int64_t sc_len, int32_t *st, int64_t st_len);
+/* launch_cg_update_xr: x += a p, r -= a q (x, r in / out); launch_cg_update_p: p = z + beta p (p in / out); a frozen
+ * column keeps its bits. */
+int gogp_test_cg_update_xr(int device, double *x, int64_t x_len, double *r, int64_t r_len, const double *p, int64_t p_len,
+                           const double *q, int64_t q_len, int64_t ld, int64_t n, int T, const double *sc, int64_t sc_len,
+                           const int32_t *st, int64_t st_len);
+int gogp_test_cg_update_p(int device, double *p, int64_t p_len, const double *z, int64_t z_len, int64_t ld, int64_t n, int T,
+                          const double *sc, int64_t sc_len, const int32_t *st, int64_t st_len);
+/* launch_cg_scale: out (in / out) = in o w - sub; w (n entries) and sub (a block) may be NULL with length 0. */
+int gogp_test_cg_scale(int device, const double *in, int64_t in_len, const double *w, int64_t w_len, const double *sub,
+                       int64_t sub_len, int64_t ld, int64_t n, int T, double *out, int64_t out_len);
+/* launch_cg_status: st (in / out) row 3: [0] = columns t < T not frozen, [1] = first bad column + 1 or 0. */
+int gogp_test_cg_status(int device, int T, int32_t *st, int64_t st_len);
+/* The preconditioner on a given scaled factor: Z (in / out) = D^-1/2 (R' - Ls Cinv Ls^T R'), R' = D^-1/2 R, through
+ * launch_cg_lst, launch_cg_small_mm and launch_cg_precond.  Ls: r columns of ldn >= n doubles, column-major; dis: n;
+ * Cinv: rp x rp, rp = r rounded up to 16; r == 0: Jacobi, Ls and Cinv NULL with length 0.  C (in / out, rp x rp; NULL
+ * with length 0: not asked for) receives launch_cg_capacitance's I + Ls^T Ls. */
+int gogp_test_cg_precond(int device, const double *Ls, int64_t ls_len, int64_t ldn, int64_t n, int r, const double *dis,
+                         int64_t dis_len, const double *Cinv, int64_t cinv_len, const double *R, int64_t r_len, int64_t ld,
+                         int T, double *Z, int64_t z_len, double *C, int64_t c_len);
+
 #ifdef __cplusplus
 }
 #endif
