@@ -10,5 +10,13 @@ constructing a ``GP`` raises if the library or a HIP device is missing.
 """
 from . import kernel  # noqa: F401
 
-__all__ = ["kernel", "gp"]
+__all__ = ["kernel", "gp", "CGModel"]
 __version__ = "0.1.0"
+
+
+def __getattr__(name):
+    # gogp_amd.CGModel: the iterative exact GP's objective (gp.CGModel), resolved on first use like the gp module itself
+    if name == "CGModel":
+        from .gp import CGModel
+        return CGModel
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

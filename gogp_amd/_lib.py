@@ -87,6 +87,13 @@ class CCgInfo(ctypes.Structure):
                 ("yt_alpha", ctypes.c_double)]
 
 
+class CCgLmlInfo(ctypes.Structure):
+    """gogp_cg_lml_info (include/gogp_hip.h)."""
+    _fields_ = [("lml", ctypes.c_double), ("yt_alpha", ctypes.c_double), ("logdet", ctypes.c_double),
+                ("logdet_precond", ctypes.c_double), ("logdet_stderr", ctypes.c_double), ("probes", ctypes.c_int32),
+                ("blocks", ctypes.c_int32), ("products", ctypes.c_int32), ("lanczos_max", ctypes.c_int32)]
+
+
 SYMBOLS = [
     ("gogp_desc_check", ctypes.c_int, [_descp]),
     ("gogp_desc_ntheta_noise", ctypes.c_int, [_descp]),
@@ -151,6 +158,9 @@ SYMBOLS = [
     ("gogp_cg_produce", ctypes.c_int,
      [_h, _dp, _i64, _dp, _dp, ctypes.c_double, ctypes.c_int32, ctypes.POINTER(CCgCol)]),
     ("gogp_cg_last_info", ctypes.c_int, [_h, ctypes.POINTER(CCgInfo)]),
+    ("gogp_cg_lml_gradient", ctypes.c_int,
+     [_h, _dp, _i64, _i64, ctypes.c_double, ctypes.c_int32, _dp, _i64, _dp, ctypes.POINTER(CCgLmlInfo),
+      ctypes.POINTER(CCgCol)]),
     ("gogp_observe_gradient_batch", ctypes.c_int,
      [ctypes.POINTER(_h), ctypes.c_int, _dp, _i64, _dp, _dp, ctypes.POINTER(ctypes.c_int)]),
     ("gogp_observe_gradient_candidates", ctypes.c_int,
@@ -459,6 +469,9 @@ HOOK_SYMBOLS += [
     ("gogp_test_cg_update_p", _ci, [_ci] + [_dp, _i64] * 2 + [_i64, _i64, _ci, _dp, _i64, _i32p, _i64]),
     ("gogp_test_cg_scale", _ci, [_ci] + [_dp, _i64] * 3 + [_i64, _i64, _ci, _dp, _i64]),
     ("gogp_test_cg_status", _ci, [_ci, _ci, _i32p, _i64]),
+    ("gogp_test_cg_grad", _ci, [_ci, _kpp, _dp, _i64, _i64, _dp, _i64, _dp, _i64, _i64, _ci, ctypes.c_double, _ci, _dp]),
+    ("gogp_test_cg_probes", _ci, [_ci, _dp, _i64, _i64, _i64, _ci, _dp, _i64, _dp, _i64, _i64, _i64, _ci, _dp, _i64]),
+    ("gogp_test_cg_quadrature", _ci, [_dp, _dp, _i64, ctypes.c_double, _dp]),
     ("gogp_test_cg_precond", _ci, [_ci, _dp, _i64, _i64, _i64, _ci, _dp, _i64, _dp, _i64, _dp, _i64, _i64, _ci, _dp, _i64,
                                    _dp, _i64]),
 ]

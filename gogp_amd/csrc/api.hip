@@ -4214,6 +4214,7 @@ static void cg_free(gogp_handle *h) {
   h->cg_vec.release();
   h->cg_part.release();
   h->cg_ks.release();
+  h->cg_lml.release();
   h->cg_N = h->cg_npad = 0;
   h->cg_have = h->cg_solved = false;
   h->cg_rank = h->cg_rp = 0;
@@ -4316,14 +4317,20 @@ static int cg_reserve_part(gogp_handle *h, int T) {
 
 // One lock-step block: K^ x_t = b_t for the T <= CG_MAX_T rows of dB (device, ld = npad, zero from column n on); the
 // solutions are left in the first T rows of the workspace's x (returned through *xout).  GOGP_OK, GOGP_ENOCONV (every
-// output written) or an error.
+// output written) or an error.  With `keep` (gogp_cg_lml_gradient) the block also holds on to w = P^-1 b (a seventh
+// vector behind the dots' partials, returned through keep->w), records every iteration's a and beta (keep->hist, device:
+// 2 max_iter rows of CG_MAX_T) and leaves rho0 = b^T w per column in keep->rho0 (device, CG_MAX_T); no bit of x depends on it.
+struct CgKeep {
+  double *hist = nullptr, *rho0 = nullptr;  // in: device buffers
+  double *w = nullptr;                      // out
+};
 static int cg_block_solve(gogp_handle *h, const char *who, const double *dB, int T, double tol, int max_iter, double **xout,
-                          gogp_cg_col *cols, int col0) {
+                          gogp_cg_col *cols, int col0, CgKeep *keep = nullptr) {
   const int64_t n = h->cg_N, ld = h->cg_npad;
   hipStream_t s = h->s;
   const int nb = cg_dot_blocks(n);
   const size_t vec = (size_t)T * (size_t)ld;
-  int rc = h->cg_vec.reserve(h, (5 * vec + (size_t)CG_MAX_T * nb) * sizeof(double));
+  int rc = h->cg_vec.reserve(h, ((keep ? 6 : 5) * vec + (size_t)CG_MAX_T * nb) * sizeof(double));
   if (rc == GOGP_OK) rc = cg_reserve_part(h, T);
   if (rc != GOGP_OK) return rc;
   CgSmall sm;
@@ -4339,17 +4346,23 @@ static int cg_block_solve(gogp_handle *h, const char *who, const double *dB, int
   launch_cg_dots(s, r, r, ld, n, T, CG_DOT_BNORM, 0, tol, dpart, nullptr, cs);
   cg_apply_precond(h, sm, r, T, z);
   HIPCHK(h, hipMemcpyAsync(p, z, vec * sizeof(double), hipMemcpyDeviceToDevice, s));
-  launch_cg_dots(s, r, z, ld, n, T, CG_DOT_RHO0, 0, tol, dpart, nullptr, cs);
+  double *hist = nullptr;
+  if (keep) {
+    keep->w = dpart + (size_t)CG_MAX_T * nb;
+    hist = keep->hist;
+    HIPCHK(h, hipMemcpyAsync(keep->w, z, vec * sizeof(double), hipMemcpyDeviceToDevice, s));
+  }
+  launch_cg_dots(s, r, z, ld, n, T, CG_DOT_RHO0, 0, tol, dpart, keep ? keep->rho0 : nullptr, cs);
   int status[2] = {T, 0};
   const int check = std::max(1, h->cg_check);
   for (int it = 1; it <= max_iter; ++it) {
     launch_kmm(s, P, D, h->cg_X, n, h->cg_X, n, p, ld, T, h->cg_d, nslab, 0, kpart, q, ld);
     ++h->cg_products;
-    launch_cg_dots(s, p, q, ld, n, T, CG_DOT_PQ, it, tol, dpart, nullptr, cs);
+    launch_cg_dots(s, p, q, ld, n, T, CG_DOT_PQ, it, tol, dpart, nullptr, cs, hist);
     launch_cg_update_xr(s, x, r, p, q, ld, n, T, cs);
     launch_cg_dots(s, r, r, ld, n, T, CG_DOT_RR, it, tol, dpart, nullptr, cs);
     cg_apply_precond(h, sm, r, T, z);
-    launch_cg_dots(s, r, z, ld, n, T, CG_DOT_BETA, it, tol, dpart, nullptr, cs);
+    launch_cg_dots(s, r, z, ld, n, T, CG_DOT_BETA, it, tol, dpart, nullptr, cs, hist);
     launch_cg_update_p(s, p, z, ld, n, T, cs);
     if (it % check == 0 || it == max_iter) {
       launch_cg_status(s, T, cs);
@@ -4448,6 +4461,8 @@ extern "C" int gogp_cg_solve(gogp_handle *h, const double *x, int64_t len, int32
   h->cg_solved = false;
   h->cg_products = h->cg_blocks = 0;
   h->cg_rank = h->cg_rp = 0;
+  h->cg_logdet_c = 0.0;
+  h->cg_dnoise = hp.dnoise;
   *info = gogp_cg_info();
   HIPCHK(h, hipMemcpyAsync(h->cg_P, &hp, sizeof hp, hipMemcpyHostToDevice, s));
   HIPCHK(h, hipStreamSynchronize(s));  // hp is a local
@@ -4523,6 +4538,9 @@ extern "C" int gogp_cg_solve(gogp_handle *h, const double *x, int64_t len, int32
       }
     HIPCHK(h, hipMemcpyAsync(sm.Cinv, C.data(), C.size() * sizeof(double), hipMemcpyHostToDevice, s));
     HIPCHK(h, hipStreamSynchronize(s));  // C is a local
+    double ldc = 0.0;  // log |C| = 2 sum_j log G_jj (gogp_cg_lml_gradient; the padded pivots are 1)
+    for (int j = 0; j < r; ++j) ldc += log(G[(size_t)j * rp + j]);
+    h->cg_logdet_c = 2.0 * ldc;
   }
   h->cg_rank = r;
   h->cg_rp = rp;
@@ -4664,6 +4682,119 @@ extern "C" int gogp_cg_produce(gogp_handle *h, const double *Z, int64_t m, doubl
     }
     HIPCHK(h, hipStreamSynchronize(s));
     HIPCHK(h, hipGetLastError());
+  }
+  if (ret != GOGP_OK) h->err = first_err;
+  return ret;
+}
+
+// The LML and its gradient at the theta, preconditioner and alpha of the last gogp_cg_solve (include/gogp_hip.h states
+// the estimator).  Per block of CG_MAX_T probes: the rows of Xi go up, cg_probe_kernel forms z = D^1/2 (Ls xi1 + xi2), one
+// lock-step block solves K^ u = z and keeps w = P^-1 z, rho0 and the a / beta history; the host turns each column's history
+// into its quadrature value, and the pair reduction adds the block's (-u_s / t, w_s) to the (alpha, alpha) pass that went
+// first -- the order of the passes depends on t alone.
+extern "C" int gogp_cg_lml_gradient(gogp_handle *h, const double *Xi, int64_t t, int64_t ldxi, double tol, int32_t max_iter,
+                                    double *grad, int64_t len, double *quad, gogp_cg_lml_info *info, gogp_cg_col *cols) {
+  const char *who = "cg_lml_gradient";
+  if (!h) return GOGP_EARG;
+  if (sparse_refusal(h)) return cg_refuse_handle(h, who);
+  if (!Xi || !info) return cg_refuse(h, who, GOGP_EARG, "NULL");
+  if (t < 1 || t > (1 << 20)) return cg_refuse(h, who, GOGP_EARG, "need 1 <= t <= 2^20 probes");
+  if (const char *why = cg_tol_refusal(tol, max_iter)) return cg_refuse(h, who, GOGP_EARG, why);
+  if (grad && len != h->P) return cg_refuse(h, who, GOGP_EARG, "len(grad)");
+  if (!h->cg_have || !h->cg_solved) return cg_refuse(h, who, GOGP_ESTATE, "no solution (gogp_cg_solve)");
+  const int64_t N = h->cg_N, npad = h->cg_npad;
+  const int r = h->cg_rank, D = h->D;
+  const int64_t nx = N + r;
+  if (ldxi < nx) return cg_refuse(h, who, GOGP_EARG, "ldxi is less than N + rank_used");
+  if (grad && N >= (1 << 21)) return cg_refuse(h, who, GOGP_EARG, "the gradient's pair reduction counts its tiles in 32 bits: N < 2^21 (grad == NULL computes the LML alone)");
+  for (int64_t sI = 0; sI < t; ++sI)
+    for (int64_t i = 0; i < nx; ++i)
+      if (!std::isfinite(Xi[sI * ldxi + i])) return cg_refuse(h, who, GOGP_EARG, "non-finite normal");
+  HIPCHK(h, hipSetDevice(h->device));
+  hipStream_t s = h->s;
+  *info = gogp_cg_lml_info();
+  // the counters of the last solve / columns / produce call stay what gogp_cg_last_info reports
+  const int keep_products = h->cg_products, keep_blocks = h->cg_blocks;
+  struct Restore {
+    gogp_handle *h;
+    int p, b;
+    ~Restore() { h->cg_products = p, h->cg_blocks = b; }
+  } restore{h, keep_products, keep_blocks};
+  h->cg_products = h->cg_blocks = 0;
+  const int gblocks = cg_grad_blocks(N);
+  const size_t n_xi = (size_t)CG_MAX_T * (size_t)nx, n_hist = (size_t)2 * (size_t)max_iter * CG_MAX_T;
+  int rc = h->cg_lml.reserve(h, (n_xi + n_hist + CG_MAX_T + NACC + (size_t)gblocks * NACC) * sizeof(double));
+  if (rc == GOGP_OK) rc = h->cg_ks.reserve(h, (size_t)CG_MAX_T * (size_t)npad * sizeof(double));
+  if (rc != GOGP_OK) return rc;
+  double *dXi = h->cg_lml.as<double>(), *dhist = dXi + n_xi, *drho0 = dhist + n_hist, *gout = drho0 + CG_MAX_T;
+  double *gpart = gout + NACC;
+  double *dZ = h->cg_ks.as<double>();
+  // log |P| = sum_i log D_i + log |C|: the diagonal comes down once and is summed in index order
+  std::vector<double> hd((size_t)N);
+  HIPCHK(h, hipMemcpyAsync(hd.data(), h->cg_d, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipStreamSynchronize(s));
+  double ldp = 0.0;
+  for (int64_t i = 0; i < N; ++i) ldp += log(hd[(size_t)i]);
+  ldp += h->cg_logdet_c;
+  if (grad)
+    launch_cg_grad(s, h->cg_P, D, h->ard_dims, h->cg_X, N, h->cg_alpha, h->cg_alpha, npad, 1, 1.0, gpart, gout, false);
+  std::vector<double> hhist, q((size_t)t);
+  double hrho0[CG_MAX_T];
+  std::vector<gogp_cg_col> lcols((size_t)CG_MAX_T);
+  int ret = GOGP_OK, lmax = 0;
+  std::string first_err;
+  const double *Ls = h->cg_L.as<double>();
+  for (int64_t t0 = 0; t0 < t; t0 += CG_MAX_T) {
+    const int cnt = (int)std::min<int64_t>(CG_MAX_T, t - t0);
+    HIPCHK(h, hipMemcpy2DAsync(dXi, (size_t)nx * sizeof(double), Xi + t0 * ldxi, (size_t)ldxi * sizeof(double),
+                               (size_t)nx * sizeof(double), (size_t)cnt, hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemsetAsync(dZ, 0, (size_t)cnt * npad * sizeof(double), s));
+    launch_cg_probes(s, Ls, h->cg_ldn, N, r, h->cg_d, dXi, nx, npad, cnt, dZ);
+    CgKeep keep;
+    keep.hist = dhist, keep.rho0 = drho0;
+    double *xs = nullptr;
+    rc = cg_block_solve(h, who, dZ, cnt, tol, max_iter, &xs, lcols.data(), (int)t0, &keep);
+    if (rc != GOGP_OK && rc != GOGP_ENOCONV) return rc;
+    if (rc != GOGP_OK && ret == GOGP_OK) ret = rc, first_err = h->err;
+    int mmax = 0;
+    for (int c = 0; c < cnt; ++c) mmax = std::max(mmax, (int)lcols[(size_t)c].iterations);
+    lmax = std::max(lmax, mmax);
+    hhist.resize((size_t)2 * (size_t)std::max(mmax, 1) * CG_MAX_T);
+    if (mmax > 0)
+      HIPCHK(h, hipMemcpyAsync(hhist.data(), dhist, (size_t)2 * mmax * CG_MAX_T * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(hrho0, drho0, sizeof hrho0, hipMemcpyDeviceToHost, s));
+    if (grad)
+      launch_cg_grad(s, h->cg_P, D, h->ard_dims, h->cg_X, N, xs, keep.w, npad, cnt, -1.0 / (double)t, gpart, gout, true);
+    HIPCHK(h, hipStreamSynchronize(s));
+    HIPCHK(h, hipGetLastError());
+    for (int c = 0; c < cnt; ++c) {
+      const int m = lcols[(size_t)c].iterations;
+      q[(size_t)(t0 + c)] = cg_lanczos_quadrature(hhist.data() + c, hhist.data() + CG_MAX_T + c, 2 * CG_MAX_T, m, hrho0[c]);
+      if (cols) cols[t0 + c] = lcols[(size_t)c];
+    }
+  }
+  double qsum = 0.0;
+  for (int64_t c = 0; c < t; ++c) qsum += q[(size_t)c];
+  const double qmean = qsum / (double)t;
+  double var = 0.0;
+  for (int64_t c = 0; c < t; ++c) var += (q[(size_t)c] - qmean) * (q[(size_t)c] - qmean);
+  info->logdet_precond = ldp;
+  info->logdet = ldp + qmean;
+  info->logdet_stderr = t > 1 ? sqrt(var / (double)(t - 1)) / sqrt((double)t) : 0.0;
+  info->yt_alpha = h->cg_yta;
+  info->lml = -0.5 * h->cg_yta - 0.5 * info->logdet - 0.5 * (double)N * log(2.0 * M_PI);
+  info->probes = (int32_t)t;
+  info->blocks = h->cg_blocks;
+  info->products = h->cg_products;
+  info->lanczos_max = lmax;
+  if (quad)
+    for (int64_t c = 0; c < t; ++c) quad[c] = q[(size_t)c];
+  if (grad) {
+    double acc[NACC];
+    HIPCHK(h, hipMemcpyAsync(acc, gout, sizeof acc, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    for (int64_t i = 0; i < len; ++i) grad[i] = 0.0;
+    assemble_gradient(h, acc, h->cg_dnoise, grad);
   }
   if (ret != GOGP_OK) h->err = first_err;
   return ret;

@@ -13,11 +13,17 @@
 //                         |r| <= tol |b|, beta = rho' / rho.
 //   cg_update_xr_kernel, cg_update_p_kernel, cg_scale_kernel   the fused vector updates; a frozen column is not touched.
 //   cg_diag_kernel .. cg_precond_kernel   the preconditioner P = L L^T + D by Woodbury's identity (common.h).
+//   cg_probe_kernel, cg_grad_kernel       the LML's gradient (gogp_cg_lml_gradient): the probes z = D^1/2 (Ls xi1 + xi2), and
+//                         the pair reduction of W = alpha alpha^T - (1/t) sum u_s w_s^T against theta dk/dtheta -- the
+//                         product's mirror image: the matrix cores form the weights, the lanes evaluate the derivative.
+//   cg_lanczos_quadrature (host)          e_1^T log(T) e_1 of a column's Lanczos tridiagonal, from its a and beta.
 //
 // Kernel boundaries are the only synchronisation: no atomics, no spin-waits, vector stores only; the order of every
 // sum depends on the sizes alone -- never on T --, so two identical calls return identical bits and a column has the
 // same bits alone as inside a block of 64.
 #include <algorithm>
+#include <cmath>
+#include <vector>
 
 #include "kern_eval.h"
 
@@ -143,10 +149,12 @@ __global__ __launch_bounds__(256) void cg_dots_kernel(const double *__restrict__
 //                 with a = 0; a frozen column: a = 0
 //   CG_DOT_RR     a live column: rr = dot, iterations = it, frozen iff sqrt(dot) <= tol sqrt(|b|^2)
 //   CG_DOT_BETA   a live column: beta = dot / rho, rho = dot; a frozen one: beta = 0
-// out (may be nullptr in the other modes) receives the dot product in every mode.
+// out (may be nullptr in the other modes) receives the dot product in every mode.  hist (may be nullptr): the column's a
+// (mode CG_DOT_PQ) and beta (mode CG_DOT_BETA) of iteration `it` as just decided, rows 2 (it - 1) and 2 (it - 1) + 1 of
+// CG_MAX_T doubles.
 __global__ __launch_bounds__(256) void cg_dots_final_kernel(const double *__restrict__ part, int nb, int mode, int it,
                                                             double tol, double *__restrict__ out, double *__restrict__ sc,
-                                                            int *__restrict__ st) {
+                                                            int *__restrict__ st, double *__restrict__ hist) {
   __shared__ double red[4];
   const int t = blockIdx.x;
   double s = 0.0;
@@ -177,6 +185,7 @@ __global__ __launch_bounds__(256) void cg_dots_final_kernel(const double *__rest
     } else {
       a[t] = 0.0, bad[t] = 1, frozen[t] = 1;
     }
+    if (hist) hist[(long)(2 * (it - 1)) * CG_MAX_T + t] = a[t];
   } else if (mode == CG_DOT_RR) {
     if (live) {
       rr[t] = s, iters[t] = it;
@@ -189,6 +198,7 @@ __global__ __launch_bounds__(256) void cg_dots_final_kernel(const double *__rest
     } else {
       beta[t] = 0.0;
     }
+    if (hist) hist[(long)(2 * (it - 1) + 1) * CG_MAX_T + t] = beta[t];
   }
 }
 
@@ -370,6 +380,148 @@ __global__ __launch_bounds__(256) void cg_precond_kernel(const double *__restric
     }
 }
 
+// ---- the LML's gradient: probes and the pair reduction ---------------------------------------------------------------------------
+// Z[t][i] = sqrt(d_i) (sum_{k < r} Ls[i][k] Xi[t][n + k] + Xi[t][i]) ~ N(0, L L^T + D) for standard normal Xi: the four
+// right-hand sides 4 blockIdx.y .. per pass over the row of Ls, as cg_precond_kernel takes them
+__global__ __launch_bounds__(256) void cg_probe_kernel(const double *__restrict__ Ls, long ldn, long n, int r,
+                                                       const double *__restrict__ d, const double *__restrict__ Xi, long ldxi,
+                                                       long ld, int T, double *__restrict__ Z) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int t0 = 4 * blockIdx.y;
+  // rows of Xi beyond T are never read: their index is clamped and their sum dropped
+  const double *x0 = Xi + (long)t0 * ldxi, *x1 = Xi + (long)std::min(t0 + 1, T - 1) * ldxi;
+  const double *x2 = Xi + (long)std::min(t0 + 2, T - 1) * ldxi, *x3 = Xi + (long)std::min(t0 + 3, T - 1) * ldxi;
+  double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+  const double *col = Ls + i;
+  for (int k = 0; k < r; ++k, col += ldn) {
+    const double l = col[0];
+    s0 += l * x0[n + k], s1 += l * x1[n + k], s2 += l * x2[n + k], s3 += l * x3[n + k];
+  }
+  const double sd = sqrt(d[i]);
+  const double sv[4] = {s0 + x0[i], s1 + x1[i], s2 + x2[i], s3 + x3[i]};
+#pragma unroll
+  for (int u = 0; u < 4; ++u)
+    if (t0 + u < T) Z[(long)(t0 + u) * ld + i] = sd * sv[u];
+}
+
+// partials[b][slot] = sum over the 64 x 64 tiles (row tile ti, column tile tj; t = ti ntc + tj) b * per .. of workgroup b of
+//     (scale sum_{s < S} A[s][i] B[s][j]) theta_p dk(x_i, x_j)/dtheta_p,        i, j < n,
+// in the slot layout of grad.hip (common.h: ACC_*; the trace slot takes the weights of the pairs i == j).  The mirror image
+// of kmm_kernel: there a lane evaluates the kernel and the matrix cores multiply, here the matrix cores form the weights
+// and the lanes evaluate the derivative.  Wave w takes the rows 16 w .. 16 w + 15 of the tile and its four 16 x 16
+// sub-tiles c in turn: ceil(S / 4) v_mfma_f64_16x16x4_f64 (A operand scale A[4 k + fk][i_fr], B operand B[4 k + fk][j_fr],
+// both from LDS, the A tile staged once per row tile; rows s >= S and elements >= n are exact zeros and never read)
+// leave the weights of the pairs (row fk + 4 v, column fr), v < 4, in the lane's C fragment, which go through
+// simil_grad_accum in the order c, v.  A lane's order of pairs and the block's tree depend on n alone, never on S.
+// Dynamic LDS: Xa[64][DS], Xb[64][DS] (DS = ndim | 1), As[S4][64], Bs[S4][64] (S4 = S rounded up to 4; element (s, j) at
+// column j ^ 16 (s & 1): the rows fk, fk + 1 that half a wave reads lie in different banks), red[4][NACC].
+// ARD dimensions ard0 .. ard0 + ARD_D - 1 per pass, the pass with ard0 == 0 writing every slot and a later one only its own
+// (sparse_grad_kernel).  Tiles are counted in 32 bits: n < 2^21.
+constexpr int CG_GRAD_BLOCKS_MAX = 2048;
+
+template <int ARD_D>
+__global__ __launch_bounds__(256, 2) void cg_grad_kernel(const DevParams *__restrict__ Pp, const double *__restrict__ X,
+                                                         int n, const double *__restrict__ A,
+                                                         const double *__restrict__ B, long ld, int S, double scale,
+                                                         int ntc, int ntiles, int per, double *__restrict__ partials,
+                                                         int ard0) {
+  extern __shared__ double sm[];
+  const DevParams &P = *Pp;
+  const int D = P.ndim;
+  const int DS = D | 1;
+  const int nsteps = (S + 3) >> 2;
+  double *Xa = sm, *Xb = sm + 64 * DS, *As = Xb + 64 * DS;
+  double *Bs = As + 4 * nsteps * 64;
+  double *red = Bs + 4 * nsteps * 64;  // [4][NACC]
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int fr = lane & 15, fk = lane >> 4;
+
+  double acc[ACC_TRACE + 1];
+#pragma unroll
+  for (int q = 0; q <= ACC_TRACE; ++q) acc[q] = 0.0;
+  double ard[ARD_D > 0 ? ARD_D : 1];
+#pragma unroll
+  for (int q = 0; q < (ARD_D > 0 ? ARD_D : 1); ++q) ard[q] = 0.0;
+
+  const int tb = blockIdx.x * per, te = min(ntiles, tb + per);
+  int have_ti = -1;
+  for (int t = tb; t < te; ++t) {
+    const int ti = t / ntc, tj = t - ti * ntc;
+    const int r0 = ti * 64, c0 = tj * 64;
+    __syncthreads();  // the previous tile's readers are done
+    if (ti != have_ti) {  // (uniform)
+      have_ti = ti;
+      for (int idx = tid; idx < 64 * D; idx += 256) {
+        const int r = idx / D, d = idx - r * D;
+        Xa[r * DS + d] = (r0 + r < n) ? X[(long)(r0 + r) * D + d] : 0.0;
+      }
+      for (int idx = tid; idx < 4 * nsteps * 64; idx += 256) {
+        const int s = idx >> 6, j = idx & 63;
+        As[s * 64 + (j ^ ((s & 1) << 4))] = (s < S && r0 + j < n) ? scale * A[(long)s * ld + r0 + j] : 0.0;
+      }
+    }
+    for (int idx = tid; idx < 64 * D; idx += 256) {
+      const int r = idx / D, d = idx - r * D;
+      Xb[r * DS + d] = (c0 + r < n) ? X[(long)(c0 + r) * D + d] : 0.0;
+    }
+    for (int idx = tid; idx < 4 * nsteps * 64; idx += 256) {
+      const int s = idx >> 6, j = idx & 63;
+      Bs[s * 64 + (j ^ ((s & 1) << 4))] = (s < S && c0 + j < n) ? B[(long)s * ld + c0 + j] : 0.0;
+    }
+    __syncthreads();
+    const double *ap = As + fk * 64 + ((16 * w + fr) ^ ((fk & 1) << 4));
+    for (int c = 0; c < 4; ++c) {
+      cg_f64x4 wt = {0.0, 0.0, 0.0, 0.0};
+      const double *bp = Bs + fk * 64 + ((16 * c + fr) ^ ((fk & 1) << 4));
+      for (int k = 0; k < nsteps; ++k) wt = __builtin_amdgcn_mfma_f64_16x16x4f64(ap[k * 256], bp[k * 256], wt, 0, 0, 0);
+      // C fragment: column = lane & 15, row = (lane >> 4) + 4 v
+      const int gj = c0 + 16 * c + fr;
+      const double *xb = Xb + (16 * c + fr) * DS;
+      // (one copy of the derivative's code: four inlined ones are over the audit's limit of SGPR spills)
+#pragma nounroll
+      for (int v = 0; v < 4; ++v) {
+        const int r = 16 * w + fk + 4 * v;
+        const int gi = r0 + r;
+        if (gi < n && gj < n) {
+          const double wgt = v == 0 ? wt[0] : v == 1 ? wt[1] : v == 2 ? wt[2] : wt[3];
+          const double *xa = Xa + r * DS;
+          simil_grad_accum<ARD_D>(
+              P, [&](int d) { return xa[d]; }, [&](int d) { return xb[d]; }, wgt, acc, ard, ard0);
+          if (gi == gj) acc[ACC_TRACE] += wgt;
+        }
+      }
+    }
+  }
+
+  // ---- block reduction: wave shuffles, then 4 waves through LDS (sparse_grad_kernel) -------------
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q <= ACC_TRACE; ++q) {
+    double v = acc[q];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    if (lane == 0) red[w * NACC + q] = v;
+  }
+  if (ARD_D > 0) {
+#pragma unroll
+    for (int q = 0; q < (ARD_D > 0 ? ARD_D : 1); ++q) {
+      double v = ard[q];
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+      if (lane == 0) red[w * NACC + ACC_ARD0 + q] = v;
+    }
+  }
+  __syncthreads();
+  if (tid < NACC) {
+    const bool base = tid <= ACC_TRACE, mine = tid >= ACC_ARD0 && tid < ACC_ARD0 + ARD_D;
+    double v = 0.0;
+    if (base || mine) v = red[tid] + red[NACC + tid] + red[2 * NACC + tid] + red[3 * NACC + tid];
+    if (ard0 == 0) partials[(long)blockIdx.x * NACC + tid] = v;
+    else if (mine && tid + ard0 < NACC) partials[(long)blockIdx.x * NACC + tid + ard0] = v;
+  }
+}
+
 // ---- launchers -----------------------------------------------------------------------------------------------------------------
 // Slabs of column tiles: about 2048 work items where the row tiles alone do not give them; a function of the sizes only
 int kmm_slabs(int64_t rows, int64_t cols) {
@@ -404,11 +556,11 @@ void launch_kmm(hipStream_t s, const DevParams *p, int ndim, const double *A, in
 int cg_dot_blocks(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + 2047) / 2048, 512)); }
 
 void launch_cg_dots(hipStream_t s, const double *A, const double *B, int64_t ld, int64_t n, int T, int mode, int it,
-                    double tol, double *part, double *out, CgState cs) {
+                    double tol, double *part, double *out, CgState cs, double *hist) {
   const int nb = cg_dot_blocks(n);
   GOGP_KLAUNCH(cg_dots_kernel, dim3((unsigned)nb, (unsigned)T), dim3(256), 0, s, A, B, (long)ld, (long)n, part);
   GOGP_KLAUNCH(cg_dots_final_kernel, dim3((unsigned)T), dim3(256), 0, s, (const double *)part, nb, mode, it, tol, out, cs.sc,
-               cs.st);
+               cs.st, hist);
 }
 
 void launch_cg_update_xr(hipStream_t s, double *x, double *r, const double *p, const double *q, int64_t ld, int64_t n, int T,
@@ -470,6 +622,113 @@ void launch_cg_precond(hipStream_t s, const double *Ls, int64_t ldn, int64_t n, 
                        const double *R, const double *Y, int64_t ld, int T, double *Z) {
   GOGP_KLAUNCH(cg_precond_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)((T + 3) / 4)), dim3(256), 0, s, Ls,
                (long)ldn, (long)n, r, rp, dis, R, Y, (long)ld, T, Z);
+}
+
+void launch_cg_probes(hipStream_t s, const double *Ls, int64_t ldn, int64_t n, int r, const double *d, const double *Xi,
+                      int64_t ldxi, int64_t ld, int T, double *Z) {
+  GOGP_KLAUNCH(cg_probe_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)((T + 3) / 4)), dim3(256), 0, s, Ls, (long)ldn,
+               (long)n, r, d, Xi, (long)ldxi, (long)ld, T, Z);
+}
+
+// workgroups of the pair reduction: one per 64 x 64 tile up to CG_GRAD_BLOCKS_MAX, then runs of consecutive tiles; a function
+// of n only
+int cg_grad_blocks(int64_t n) {
+  const int64_t rt = std::max<int64_t>(1, (n + 63) / 64);
+  return (int)std::min<int64_t>(rt * rt, CG_GRAD_BLOCKS_MAX);
+}
+
+template <int AD>
+static void cgg_launch(int blocks, hipStream_t s, int ndim, const DevParams *p, const double *X, int n, const double *A,
+                       const double *B, long ld, int S, double scale, int ntc, int ntiles, int per, double *partials,
+                       int ard0) {
+  const int ds = ndim | 1;
+  const size_t lds = (size_t)(128 * ds + (S + 3) / 4 * 4 * 128 + 4 * NACC) * sizeof(double);
+  if (lds > 64 * 1024)  // raised explicitly, per launch (the attribute belongs to the function on the current device)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&cg_grad_kernel<AD>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)((128 * (GOGP_MAX_NDIM | 1) + CG_MAX_T * 128 + 4 * NACC) * sizeof(double)));
+  GOGP_KLAUNCH(cg_grad_kernel<AD>, dim3((unsigned)blocks), dim3(256), lds, s, p, X, n, A, B, ld, S, scale, ntc, ntiles, per,
+               partials, ard0);
+}
+
+void launch_cg_grad(hipStream_t s, const DevParams *p, int ndim, int ard_dims, const double *X, int64_t n, const double *A,
+                    const double *B, int64_t ld, int S, double scale, double *partials, double *out, bool accumulate) {
+  if (n <= 0 || n >= (1 << 21) || S <= 0) return;  // (tiles are counted in 32 bits; the callers refuse such an n)
+  const int ntc = (int)((n + 63) / 64), ntiles = ntc * ntc;
+  const int blocks = cg_grad_blocks(n);
+  const int per = (ntiles + blocks - 1) / blocks;
+  // the rows in passes of CG_MAX_T, each summed behind the one before it; ARD dimensions in passes of 8 accumulators
+  // (launch_sparse_grad: the 16-accumulator instance is over the audit's limit of SGPR spills)
+  for (int s0 = 0; s0 < S; s0 += CG_MAX_T) {
+    const int cnt = std::min(CG_MAX_T, S - s0);
+    const double *a = A + (long)s0 * ld, *b = B + (long)s0 * ld;
+    if (ard_dims <= 0)
+      cgg_launch<0>(blocks, s, ndim, p, X, (int)n, a, b, (long)ld, cnt, scale, ntc, ntiles, per, partials, 0);
+    else
+      for (int a0 = 0; a0 < ard_dims; a0 += 8)
+        cgg_launch<8>(blocks, s, ndim, p, X, (int)n, a, b, (long)ld, cnt, scale, ntc, ntiles, per, partials, a0);
+    launch_sparse_grad_final(s, partials, blocks, out, accumulate || s0 > 0);
+  }
+}
+
+// rho0 e_1^T log(T) e_1 = rho0 sum_j tau_j^2 log lambda_j of the symmetric tridiagonal T_kk = 1 / a_k + beta_{k-1} / a_{k-1},
+// T_{k,k+1} = sqrt(beta_k) / a_k (k < m): the implicit QL sweep (EISPACK tql2), its rotations applied to the first row of
+// the eigenvector matrix alone -- O(m^2).  m < 1: 0.  NaN where T is not positive definite or the sweep does not settle.
+double cg_lanczos_quadrature(const double *a, const double *beta, int64_t stride, int m, double rho0) {
+  if (m < 1) return 0.0;
+  std::vector<double> d((size_t)m), e((size_t)m, 0.0), z((size_t)m, 0.0);
+  for (int k = 0; k < m; ++k) {
+    const double ak = a[(int64_t)k * stride];
+    d[k] = 1.0 / ak + (k > 0 ? beta[(int64_t)(k - 1) * stride] / a[(int64_t)(k - 1) * stride] : 0.0);
+    if (k + 1 < m) e[k] = sqrt(beta[(int64_t)k * stride]) / ak;  // couples k and k + 1
+  }
+  z[0] = 1.0;
+  for (int l = 0; l < m; ++l) {
+    for (int iter = 0;; ++iter) {
+      int mm = l;
+      for (; mm < m - 1; ++mm) {
+        const double dd = fabs(d[mm]) + fabs(d[mm + 1]);
+        if (fabs(e[mm]) + dd == dd) break;
+      }
+      if (mm == l) break;
+      if (iter == 120) return NAN;
+      double g = (d[l + 1] - d[l]) / (2.0 * e[l]);
+      double r = hypot(g, 1.0);
+      g = d[mm] - d[l] + e[l] / (g + copysign(r, g));
+      double sn = 1.0, cs = 1.0, p = 0.0;
+      int i = mm - 1;
+      for (; i >= l; --i) {
+        double f = sn * e[i];
+        const double b = cs * e[i];
+        r = hypot(f, g);
+        e[i + 1] = r;
+        if (r == 0.0) {
+          d[i + 1] -= p;
+          e[mm] = 0.0;
+          break;
+        }
+        sn = f / r, cs = g / r;
+        g = d[i + 1] - p;
+        r = (d[i] - g) * sn + 2.0 * cs * b;
+        p = sn * r;
+        d[i + 1] = g + p;
+        g = cs * r - b;
+        f = z[i + 1];
+        z[i + 1] = sn * z[i] + cs * f;
+        z[i] = cs * z[i] - sn * f;
+      }
+      if (r == 0.0 && i >= l) continue;
+      d[l] -= p;
+      e[l] = g;
+      e[mm] = 0.0;
+    }
+  }
+  // (the sum runs in index order of the sweep's output: a function of the coefficients alone)
+  double sum = 0.0;
+  for (int k = 0; k < m; ++k) {
+    if (!(d[k] > 0.0)) return NAN;
+    sum += z[k] * z[k] * log(d[k]);
+  }
+  return rho0 * sum;
 }
 
 }  // namespace gogp

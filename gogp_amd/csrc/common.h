@@ -515,6 +515,8 @@ void launch_sparse_syrk(hipStream_t s, const double *Vt, int64_t ld, int64_t row
                         double *Bacc, int64_t ldb, double *r);
 constexpr int SPARSE_GRAD_BLOCKS_MAX = 2048;  // workgroups (rows of `partials`) of launch_sparse_grad at most
 int sparse_grad_blocks(int64_t rows, int64_t M);
+// out[q] (+)= sum_b partials[b][q] for the NACC slots, in block order per thread and then a fixed tree
+void launch_sparse_grad_final(hipStream_t s, const double *partials, int blocks, double *out, bool accumulate);
 void launch_sparse_grad(hipStream_t s, const DevParams *p, int ndim, int ard_dims, const double *X, int64_t rows,
                         const double *U, int64_t M, const double *Wt, int64_t ldw, const double *y, const double *mvec,
                         double s4, double *partials, double *out, bool accumulate);
@@ -624,7 +626,7 @@ void launch_kmm(hipStream_t s, const DevParams *p, int ndim, const double *A, in
                 double *Out, int64_t ldo);
 int cg_dot_blocks(int64_t n);
 void launch_cg_dots(hipStream_t s, const double *A, const double *B, int64_t ld, int64_t n, int T, int mode, int it,
-                    double tol, double *part, double *out, CgState cs);
+                    double tol, double *part, double *out, CgState cs, double *hist = nullptr);
 void launch_cg_update_xr(hipStream_t s, double *x, double *r, const double *p, const double *q, int64_t ld, int64_t n, int T,
                          CgState cs);
 void launch_cg_update_p(hipStream_t s, double *p, const double *z, int64_t ld, int64_t n, int T, CgState cs);
@@ -646,6 +648,22 @@ void launch_cg_lst(hipStream_t s, const double *Ls, int64_t ldn, int64_t n, int 
 void launch_cg_small_mm(hipStream_t s, const double *Cinv, int r, int rp, const double *W, int T, double *Y);
 void launch_cg_precond(hipStream_t s, const double *Ls, int64_t ldn, int64_t n, int r, int rp, const double *dis,
                        const double *R, const double *Y, int64_t ld, int T, double *Z);
+// The LML and its gradient (gogp_cg_lml_gradient).  launch_cg_dots with hist != nullptr records the iteration's
+// coefficients of every column t < T: a at hist[(2 (it - 1)) CG_MAX_T + t] in mode CG_DOT_PQ, beta at
+// hist[(2 (it - 1) + 1) CG_MAX_T + t] in mode CG_DOT_BETA (0 for a frozen column); other modes leave it alone.
+// launch_cg_probes: Z[t][i] = sqrt(d_i) (sum_{k < r} Ls[i][k] Xi[t][n + k] + Xi[t][i]) for i < n, t < T; Xi: T rows of ldxi
+// >= n + r doubles.  launch_cg_grad: out[slot] (+)= sum_{i, j < n} (scale sum_{s < S} A[s][i] B[s][j]) theta_p
+// dk(x_i, x_j)/dtheta_p in the slot layout of grad.hip (ACC_*), the trace slot taking the weights of the pairs i == j;
+// A, B: S >= 1 rows of ld >= n doubles, taken in passes of CG_MAX_T rows, read on s < S, i < n only; noise_var of *p is
+// not used; n < 2^21 (tiles are counted in 32 bits; a larger n launches nothing).  partials: cg_grad_blocks(n) * NACC
+// doubles of scratch.  cg_lanczos_quadrature (host): rho0 e_1^T log(T) e_1
+// of the m x m Lanczos tridiagonal T that the coefficients a[k stride], beta[k stride] (k < m) of one column define.
+int cg_grad_blocks(int64_t n);
+void launch_cg_probes(hipStream_t s, const double *Ls, int64_t ldn, int64_t n, int r, const double *d, const double *Xi,
+                      int64_t ldxi, int64_t ld, int T, double *Z);
+void launch_cg_grad(hipStream_t s, const DevParams *p, int ndim, int ard_dims, const double *X, int64_t n, const double *A,
+                    const double *B, int64_t ld, int S, double scale, double *partials, double *out, bool accumulate);
+double cg_lanczos_quadrature(const double *a, const double *beta, int64_t stride, int m, double rho0);
 // laplace.hip (gogp_laplace_*): the passes around the factorisation of B = I + diag(sw) K diag(sw).  Vectors hold npad
 // doubles (npad a multiple of 256) and leave every launcher zero from row n on.
 // launch_lap_site: g, W, sw = sqrt(W), b = W f + g, rho of the rows i < n; part: 5 * npad / 256 doubles of block results;

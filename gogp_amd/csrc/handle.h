@@ -278,6 +278,9 @@ struct gogp_handle : EvalBufs, EvalState {
   Workspace cg_vec;                // a block's six vectors, the dots' partials and results
   Workspace cg_part;               // the slab partials of the product and of the skinny transposed product
   Workspace cg_ks;                 // gogp_cg_produce: 64 rows of k*, the test points, prior, q, mu
+  double cg_logdet_c = 0.0;        // log |C| of the last solve's capacitance matrix (0 at rank 0)
+  double cg_dnoise = 0.0;          // d noise_var / d log(noise parameter) at the last solve's theta
+  Workspace cg_lml;                // gogp_cg_lml_gradient: a block's rows of Xi, the a / beta history, rho0, slot sums and partials
   // the Laplace approximation (gogp_laplace_*, laplace.hip; api.hip: LapVecs).  B's factor lies in bufL / Dinv, B^-1 and
   // then the gradient's weight matrix in bufA; only vectors are its own (released with the N buffers).
   Workspace lap_ws;

@@ -312,6 +312,10 @@ int sparse_grad_blocks(int64_t rows, int64_t M) {
   return (int)(ntiles < SPARSE_GRAD_BLOCKS_MAX ? (ntiles > 0 ? ntiles : 1) : SPARSE_GRAD_BLOCKS_MAX);
 }
 
+void launch_sparse_grad_final(hipStream_t s, const double *partials, int blocks, double *out, bool accumulate) {
+  GOGP_KLAUNCH(sparse_grad_final_kernel, dim3(NACC), dim3(256), 0, s, partials, blocks, out, accumulate ? 1 : 0);
+}
+
 template <int AD>
 static void sg_launch(int blocks, hipStream_t s, int ndim, const DevParams *p, const double *X, long rows, const double *U,
                       long M, const double *Wt, long ldw, const double *y, const double *mvec, double s4, int ntc,
@@ -338,7 +342,7 @@ void launch_sparse_grad(hipStream_t s, const DevParams *p, int ndim, int ard_dim
   else
     for (int a0 = 0; a0 < ard_dims; a0 += 8)
       sg_launch<8>(blocks, s, ndim, p, X, (long)rows, U, (long)M, Wt, (long)ldw, y, mvec, s4, ntc, ntiles, partials, a0);
-  GOGP_KLAUNCH(sparse_grad_final_kernel, dim3(NACC), dim3(256), 0, s, partials, blocks, out, accumulate ? 1 : 0);
+  launch_sparse_grad_final(s, partials, blocks, out, accumulate);
 }
 
 // ---- the derivative in the inducing points: the (U, X) pairs ---------------------------------------------------------

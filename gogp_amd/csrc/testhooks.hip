@@ -2576,3 +2576,36 @@ extern "C" int gogp_test_cg_precond(int device, const double *Ls, int64_t ls_len
                launch_cg_precond(0, d[0], ldn, n, r, rp, d[1], d[3], d[7], ld, T, d[4]);
              });
 }
+
+// ---- the kernels of gogp_cg_lml_gradient: the pair reduction, the probes, the host's quadrature
+extern "C" int gogp_test_cg_grad(int device, const gogp_test_kparams *kparams, const double *X, int64_t x_len, int64_t n,
+                                 const double *A, int64_t a_len, const double *B, int64_t b_len, int64_t ld, int S,
+                                 double scale, int accumulate, double *out /* GOGP_TEST_NACC */) {
+  if (!kparams || !X || !A || !B || !out) return GOGP_EARG;
+  if (!kparams_ok(kparams, 1, ard_dims_of(kparams), 0, 1, 0) || kparams->nevents != 0) return GOGP_EARG;
+  if (n < 1 || n > (1 << 16) || ld < n || S < 1 || S > 4 * CG_MAX_T || !std::isfinite(scale)) return GOGP_EARG;
+  if (x_len < n * kparams->ndim || !covers(a_len, 0, ld, S, n, 1, 0) || !covers(b_len, 0, ld, S, n, 1, 0)) return GOGP_EARG;
+  const DevParams hp = to_dev(*kparams);
+  return run(device, {rd(&hp, 1, sizeof hp), rd(X, x_len), rd(A, a_len), rd(B, b_len), io(out, NACC),
+                      scratch((size_t)cg_grad_blocks(n) * NACC * sizeof(double))},
+             [&](const Dev &d) {
+               launch_cg_grad(0, d.as<DevParams>(0), kparams->ndim, ard_dims_of(kparams), d[1], n, d[2], d[3], ld, S, scale,
+                              d[5], d[4], accumulate != 0);
+             });
+}
+
+extern "C" int gogp_test_cg_probes(int device, const double *Ls, int64_t ls_len, int64_t ldn, int64_t n, int r,
+                                   const double *dd, int64_t d_len, const double *Xi, int64_t xi_len, int64_t ldxi,
+                                   int64_t ld, int T, double *Z, int64_t z_len) {
+  if (!dd || !Xi || !Z || !cg_dims_ok(ld, n, T) || r < 0 || r > GOGP_CG_MAX_RANK || d_len < n) return GOGP_EARG;
+  if (ldxi < n + r || !covers(xi_len, 0, ldxi, T, n + r, 1, 0) || !cg_block_ok(z_len, ld, n, T)) return GOGP_EARG;
+  if (r > 0 ? (!Ls || ldn < n || !covers(ls_len, 0, ldn, r, n, 1, 0)) : (Ls || ls_len != 0)) return GOGP_EARG;
+  return run(device, {opt(rd(Ls, ls_len)), rd(dd, d_len), rd(Xi, xi_len), io(Z, z_len)},
+             [&](const Dev &d) { launch_cg_probes(0, d[0], ldn, n, r, d[1], d[2], ldxi, ld, T, d[3]); });
+}
+
+extern "C" int gogp_test_cg_quadrature(const double *a, const double *beta, int64_t m, double rho0, double *out) {
+  if (!out || m < 0 || m > (1 << 20) || (m > 0 && (!a || !beta))) return GOGP_EARG;
+  *out = cg_lanczos_quadrature(a, beta, 1, (int)m, rho0);
+  return GOGP_OK;
+}

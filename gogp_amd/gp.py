@@ -834,6 +834,71 @@ class GP:
         self.cg_cols = self._cg_cols(cols, m)
         return self._cg_finish(rc, (mu, sg))
 
+    _cg_normals_cache: dict = {}
+
+    @classmethod
+    def _cg_normals(cls, seed: int, n: int, rank: int, probes: int) -> np.ndarray:
+        """The probes' standard normals, probes x (n + rank), drawn once per (seed, n, rank, probes) and read only: the
+        same probes serve every theta (common random numbers)."""
+        key = (int(seed), int(n), int(rank), int(probes))
+        xi = cls._cg_normals_cache.get(key)
+        if xi is None:
+            if len(cls._cg_normals_cache) >= 4:
+                cls._cg_normals_cache.clear()
+            xi = np.random.default_rng(key[0]).standard_normal((key[3], key[1] + key[2]))
+            xi.setflags(write=False)
+            cls._cg_normals_cache[key] = xi
+        return xi
+
+    def CGObserve(self, x, probes: int = 16, seed: int = 0, rank: int = 64, tol: float = 1e-8, max_iter: int = 1000,
+                  piv_tol=None, xi=None) -> float:
+        """The log marginal likelihood of the CG data at x = log theta by stochastic Lanczos quadrature (CGSolve, then
+        gogp_cg_lml_gradient): ``probes`` probe vectors z = D^1/2 (Ls xi1 + xi2) ~ N(0, P), one preconditioned solve
+        each, the log-determinant from the solves' own CG coefficients and the gradient's trace term from the same
+        solves.  The normals come from numpy.random.default_rng(seed), drawn once per (seed, N, rank, probes), or from
+        ``xi`` (probes x (N + rank); the first N + rank_used columns of a row are used: [xi2 | xi1]).  The gradient is
+        kept for CGGradient; ``cg_lml_info`` holds lml, yt_alpha, logdet, logdet_precond, logdet_stderr, probes, blocks,
+        products, lanczos_max, quad (per probe) and the per-column arrays of CGSolve.  Not converged within max_iter:
+        ConvergenceError whose ``result`` is the estimate from the columns as they stand."""
+        n = int(getattr(self, "_cg_n", 0))
+        if int(probes) < 1:
+            raise ValueError("CGObserve: probes >= 1")
+        if int(rank) < 0:
+            raise ValueError("CGObserve: rank >= 0")
+        if xi is None:
+            xs = self._cg_normals(seed, n, int(rank), int(probes))
+        else:
+            xs = np.ascontiguousarray(_arr(xi))
+            if xs.ndim != 2 or xs.shape[0] != int(probes) or xs.shape[1] < n + int(rank):
+                raise ValueError("CGObserve: xi is probes x (N + rank)")
+        try:
+            self.CGSolve(x, rank=rank, tol=tol, max_iter=max_iter, piv_tol=piv_tol)
+            noconv = None
+        except ConvergenceError as e:
+            noconv = e
+        t, p = xs.shape[0], self._ns + self._nn
+        g, quad = np.zeros(max(p, 1)), np.zeros(t)
+        info, cols = _lib.CCgLmlInfo(), (_lib.CCgCol * t)()
+        rc = _lib.lib().gogp_cg_lml_gradient(self._h, _dp(xs), t, xs.shape[1], float(tol), int(max_iter), _dp(g), p,
+                                             _dp(quad), ctypes.byref(info), cols)
+        out = {k: float(getattr(info, k)) for k in ("lml", "yt_alpha", "logdet", "logdet_precond", "logdet_stderr")}
+        out.update({k: int(getattr(info, k)) for k in ("probes", "blocks", "products", "lanczos_max")})
+        out["quad"] = quad
+        out.update(self._cg_cols(cols, t))
+        self.cg_lml_info = out
+        self._cg_grad = g[:p] if rc in (_lib.GOGP_OK, _lib.GOGP_ENOCONV) else None
+        if rc == _lib.GOGP_OK and noconv is not None:
+            noconv.result = out["lml"]
+            raise noconv
+        return self._cg_finish(rc, out["lml"])
+
+    def CGGradient(self) -> np.ndarray:
+        """d LML / d log theta of the last CGObserve (the estimate of gogp_cg_lml_gradient)."""
+        g = getattr(self, "_cg_grad", None)
+        if g is None:
+            raise GogpError(_lib.GOGP_ESTATE, "CGGradient before CGObserve")
+        return g.copy()
+
     def SparseObserve(self, x) -> float:
         """The collapsed variational bound of Titsias (2009) at x = log theta (gogp_sparse_observe): a lower bound of
         the LML of the sparse data that costs O(N M^2)."""
@@ -1423,6 +1488,41 @@ class SparseMultiModel:
             g = self.gp.SparseMultiGradient()
         if self.Priors is not None:
             self.Priors.Observe(self._x[:self.gp._ns + self.gp._nn])
+            pg = np.asarray(self.Priors.Gradient(), dtype=float)
+            g[:len(pg)] += pg
+        return g
+
+
+class CGModel:
+    """Model with the iterative exact GP's estimate of the LML in the place of the LML: Observe(x) returns
+    GP.CGObserve(x, probes, seed, rank, tol) on the data of GP.SetCG (+ the log prior), Gradient() returns GP.CGGradient()
+    (+ the prior's), for optimize.lbfgs and optimize.Adam.  The probes are fixed by ``seed``: every x sees the same
+    normals (common random numbers), so the objective is a deterministic function of x.
+
+    With fixed probes the value and the gradient are each unbiased, but the gradient is NOT the exact derivative of the
+    quadrature value: the value estimates log|K^| by Lanczos quadrature, the gradient estimates tr(K^^-1 dK^) from the
+    solves.  A line search sees an inconsistency of order 1 / sqrt(probes) between the two, so optimize.Adam, which
+    uses the gradient alone, is the recommended driver; lbfgs may stop early in its line search."""
+
+    def __init__(self, gp: GP, probes: int = 16, seed: int = 0, rank: int = 64, tol: float = 1e-8, Priors=None,
+                 max_iter: int = 1000):
+        self.gp = gp
+        self.probes, self.seed, self.rank, self.tol, self.max_iter = int(probes), int(seed), int(rank), float(tol), int(max_iter)
+        self.Priors = Priors
+        self._x = None
+
+    def Observe(self, x) -> float:
+        self._x = _arr(x).reshape(-1).copy()
+        if self._x.size != self.gp._ns + self.gp._nn:
+            raise ValueError("len(x): the iterative objective takes the hyperparameters only")
+        v = self.gp.CGObserve(self._x, probes=self.probes, seed=self.seed, rank=self.rank, tol=self.tol,
+                              max_iter=self.max_iter)
+        return v + self.Priors.Observe(self._x) if self.Priors is not None else v
+
+    def Gradient(self) -> np.ndarray:
+        g = self.gp.CGGradient()
+        if self.Priors is not None:
+            self.Priors.Observe(self._x)
             pg = np.asarray(self.Priors.Gradient(), dtype=float)
             g[:len(pg)] += pg
         return g
@@ -2327,3 +2427,44 @@ def cg_precond_check(Ls, ldn: int, n: int, r: int, dis: np.ndarray, Cinv, R: np.
     if rc != _lib.GOGP_OK:
         raise GogpError(rc, "test_cg_precond")
     return Z if C is None else (Z, C)
+
+
+def cg_grad_check(kp, X: np.ndarray, n: int, A: np.ndarray, B: np.ndarray, ld: int, S: int, out: np.ndarray,
+                  scale: float = 1.0, accumulate: bool = False, device: int = -1):
+    """launch_cg_grad (test hook gogp_test_cg_grad): the slot sums of (scale sum_s A[s][i] B[s][j]) theta dk/dtheta over
+    the pairs i, j < n.  Returns a copy of out (NACC slots, extra elements untouched)."""
+    X, A, B, out = _vec(X, "X"), _vec(A, "A"), _vec(B, "B"), _vec(out, "out").copy()
+    if out.size < NACC:
+        raise ValueError("out: NACC slots")
+    rc = _lib.hooks().gogp_test_cg_grad(device, ctypes.byref(kp), _dp(X), X.size, n, _dp(A), A.size, _dp(B), B.size, ld, S,
+                                        float(scale), int(bool(accumulate)), _dp(out))
+    if rc != _lib.GOGP_OK:
+        raise GogpError(rc, "test_cg_grad")
+    return out
+
+
+def cg_probes_check(Ls, ldn: int, n: int, r: int, d: np.ndarray, Xi: np.ndarray, ldxi: int, ld: int, T: int, Z: np.ndarray,
+                    device: int = -1):
+    """launch_cg_probes (test hook gogp_test_cg_probes): Z[t][i] = sqrt(d_i) (sum_k Ls[i][k] Xi[t][n + k] + Xi[t][i]);
+    returns a copy of Z."""
+    d, Xi, Z = _vec(d, "d"), _vec(Xi, "Xi"), _vec(Z, "Z").copy()
+    lp, ll = _opt(Ls, "Ls")
+    rc = _lib.hooks().gogp_test_cg_probes(device, lp, ll, ldn, n, r, _dp(d), d.size, _dp(Xi), Xi.size, ldxi, ld, T, _dp(Z),
+                                          Z.size)
+    if rc != _lib.GOGP_OK:
+        raise GogpError(rc, "test_cg_probes")
+    return Z
+
+
+def cg_quadrature(a: np.ndarray, beta: np.ndarray, rho0: float) -> float:
+    """rho0 e_1^T log(T) e_1 of the Lanczos tridiagonal of the CG coefficients a, beta (test hook
+    gogp_test_cg_quadrature: the host routine of gogp_cg_lml_gradient).  No device."""
+    a, beta = np.ascontiguousarray(a, dtype=np.float64).reshape(-1), np.ascontiguousarray(beta, dtype=np.float64).reshape(-1)
+    if a.size != beta.size:
+        raise ValueError("a and beta: one entry per iteration each")
+    out = np.zeros(1)
+    rc = _lib.hooks().gogp_test_cg_quadrature(_dp(a) if a.size else None, _dp(beta) if a.size else None, a.size,
+                                              float(rho0), _dp(out))
+    if rc != _lib.GOGP_OK:
+        raise GogpError(rc, "test_cg_quadrature")
+    return float(out[0])

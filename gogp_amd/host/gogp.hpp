@@ -440,6 +440,23 @@ class GP {
     check(gogp_cg_last_info(h_, &info));
     return info;
   }
+  // The LML and d LML / d log theta at the parameters of the last CGSolve, from t probes: xi holds t rows of ldxi >= N +
+  // rank_used standard normals [xi2 (N) | xi1 (rank_used)] (gogp_cg_lml_gradient; nothing random happens in the library).
+  // grad receives the gradient (nullptr: the pair reduction is skipped), quad the per-probe quadrature values.  Returns
+  // the status as CGSolve does: GOGP_OK or GOGP_ENOCONV (every output written from the columns as they stand).
+  int CGLmlGradient(const std::vector<double> &xi, int64_t t, int64_t ldxi, double tol, int32_t max_iter,
+                    gogp_cg_lml_info *info, std::vector<double> *grad = nullptr, std::vector<double> *quad = nullptr,
+                    std::vector<gogp_cg_col> *cols = nullptr) {
+    if (t < 1 || ldxi < 1 || xi.size() < (size_t)((t - 1) * ldxi) + cg_n_) throw Error(GOGP_EARG, "CGLmlGradient: sizes");
+    if (grad) grad->assign(ThetaSimil.size() + ThetaNoise.size(), 0.0);
+    if (quad) quad->assign((size_t)t, 0.0);
+    if (cols) cols->assign((size_t)t, gogp_cg_col());
+    const int rc = gogp_cg_lml_gradient(h_, xi.data(), t, ldxi, tol, max_iter, grad ? grad->data() : nullptr,
+                                        grad ? (int64_t)grad->size() : 0, quad ? quad->data() : nullptr, info,
+                                        cols ? cols->data() : nullptr);
+    if (rc != GOGP_ENOCONV) check(rc);
+    return rc;
+  }
   // SparseGradient and, from the same pass over the data, d bound / d U of the inducing points of SetSparse (dU:
   // row-major M x NDim)
   std::vector<double> SparseGradientInducing(std::vector<double> &dU) {

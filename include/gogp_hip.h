@@ -582,7 +582,7 @@ int gogp_sparse_select_inducing_resident(gogp_handle *h, const double *x, int64_
  * piv_tol; piv_tol < 0: 10^"sparse_jitter_log10"; rank == 0: plain Jacobi, P = D), applied by Woodbury's identity:
  * Ls = D^-1/2 L, C = I + Ls^T Ls, P^-1 R = D^-1/2 (R' - Ls C^-1 Ls^T R'), R' = D^-1/2 R; then K^ alpha = y.  alpha, theta and
  * the preconditioner stay for gogp_cg_get_alpha, gogp_cg_solve_columns and gogp_cg_produce; info->yt_alpha = y^T alpha is
- * the data-fit term (the log-determinant is not computed).  Every column c of a block runs
+ * the data-fit term (the log-determinant: gogp_cg_lml_gradient, below).  Every column c of a block runs
  *     x = 0, r = b, z = P^-1 r, p = z, rho = r^T z
  *     q = K^ p; a = rho / p^T q; x += a p; r -= a q; |r| <= tol |b|: the column FREEZES (its count is recorded, a = beta = 0
  *     from then on); z = P^-1 r; rho' = r^T z; beta = rho' / rho; p = z + beta p; rho = rho'
@@ -606,8 +606,8 @@ int gogp_sparse_select_inducing_resident(gogp_handle *h, const double *x, int64_
  * handle the sparse calls refuse (precision = 32, sharded, event discounts).  GOGP_ENOMEM: the factor (8 N_pad rank bytes, N_pad = N rounded up to 256) could not be
  * allocated; gogp_last_error carries the size.
  * Device memory: X, y, v, D and alpha (N (ndim + 5) doubles), the factor, C^-1 (rank^2), and per block of T columns six
- * vectors each (x, r, p, z, q, b: 48 N T bytes) plus the product's slab partials (8 N T kmm slabs; one slab from
- * N = 131072 on).  C is factored and inverted on the host (rank^3 flops, once per solve); everything per iteration runs
+ * vectors each (x, r, p, z, q, b: 48 N T bytes; gogp_cg_lml_gradient keeps a seventh, w = P^-1 b: 56 N T bytes) plus the
+ * product's slab partials (8 N T kmm slabs; one slab from N = 131072 on).  C is factored and inverted on the host (rank^3 flops, once per solve); everything per iteration runs
  * on the device.
  * Measured on one MI355X (tools/cg_probe.py, profiles/cg.txt; D = 8, medians of three): one CG iteration at rank 0 for
  * T = 1 / 16 / 64 columns: Normal 22.8 / 23.3 / 31.8 ms at N = 65536, 352 / 369 / 524 ms at N = 262144 and 5.4 / - / 8.1 s at
@@ -616,8 +616,41 @@ int gogp_sparse_select_inducing_resident(gogp_handle *h, const double *x, int64_
  * Normal 437 / 140 / 38 / 7 iterations in 641 / 228 / 74 / 270 ms, Matern-5/2 778 / 356 / 166 / 62 in 1329 / 648 / 328 / 362 ms,
  * beside 30 ms for the dense gogp_absorb, which is the call at that size; the two alpha differ by 6e-9 - 1e-8 of their
  * norm.  gogp_cg_produce at rank 256: the means of 1024 points 2 ms, with sigma 1.2 s (Normal) and 4.8 s (Matern-5/2).
- * Out of scope: the log-determinant and the gradient's trace term (stochastic Lanczos quadrature / probe
- * vectors), the symmetry of K in the product, event discounts, several GPUs.  DESIGN.md section 4, "Iterative (CG)". */
+ * gogp_cg_lml_gradient (after gogp_cg_solve; its theta, preconditioner and alpha): the log marginal likelihood and
+ * d LML / d log theta by stochastic Lanczos quadrature and probe vectors (Gardner et al. 2018).  Nothing random happens
+ * in the library: row s of Xi holds standard normals [xi2 (N) | xi1 (rank_used)], ldxi >= N + rank_used, and probe s is
+ * z_s = D^1/2 (Ls xi1 + xi2) ~ N(0, P).  One lock-step solve K^ u_s = z_s per probe (blocks of GOGP_CG_MAX_RHS, the freeze
+ * rule above); w_s = P^-1 z_s, the block's first preconditioned residual, is kept, rho0_s = z_s^T w_s, and the device
+ * records a and beta of every iteration and column (2 max_iter GOGP_CG_MAX_RHS doubles).  From a column's own coefficients
+ * the host recovers the Lanczos tridiagonal of P^-1/2 K^ P^-1/2 -- T_kk = 1 / a_k + beta_{k-1} / a_{k-1}, T_{k,k+1} =
+ * sqrt(beta_k) / a_k, k up to the column's iteration count -- and e_1^T log(T_s) e_1 by an implicit QL sweep that carries
+ * the first components of the eigenvectors only (O(m^2) per probe; nothing per iteration moves to the host):
+ *     quad_s = rho0_s e_1^T log(T_s) e_1,   log|K^| = log|P| + (1/t) sum_s quad_s,   log|P| = sum_i log D_i + log|C|
+ *     LML = -1/2 y^T alpha - 1/2 log|K^| - N/2 log 2 pi
+ *     d LML / d log theta_p = 1/2 sum_ij W_ij dK^_ij / d log theta_p,   W = alpha alpha^T - (1/t) sum_s u_s w_s^T
+ * (E[u w^T] = K^^-1 P P^-1 = K^^-1; W has rank t + 1 and is never stored).  The gradient is one matrix-free pair reduction
+ * (cg.hip: cg_grad_kernel): a wave forms each 16 x 16 tile of weights from the rows (alpha, alpha) and (-u_s / t, w_s) on
+ * v_mfma_f64_16x16x4_f64 and its lanes evaluate theta_p dk(x_i, x_j) / d theta_p for the four pairs in their C fragment;
+ * the noise parameter takes tr W.  grad == NULL skips the reduction; quad (t, may be NULL) receives quad_s;
+ * logdet_stderr is the sample standard deviation of the quad_s over sqrt(t) (0 for t = 1); lanczos_max the largest
+ * iteration count of a probe; products and blocks count this call's own (gogp_cg_last_info keeps the figures of the
+ * call before).  With orthogonal probes (t = N + rank_used, Xi = sqrt(t) Q) the estimator is exact.  Cost: ceil(t / 64)
+ * lock-step blocks -- each iteration one product, as in gogp_cg_solve_columns -- and 1 + ceil(t / 64) passes of the pair
+ * reduction (per ARD pass of 8 dimensions) over all N^2 pairs.  Every sum has a fixed order; the order of the passes
+ * depends on t alone: identical calls return identical bits, and a probe's quad_s has the same bits alone as in a block.
+ * The handle is left as found (alpha, preconditioner, gogp_cg_last_info).  GOGP_ESTATE before a solve; GOGP_EARG: NULL Xi
+ * or info, t < 1, ldxi < N + rank_used, a non-finite value in Xi, len != P (with grad), N >= 2^21 with grad (the pair
+ * reduction counts its 64 x 64 tiles in 32 bits), a bad tol or max_iter;
+ * GOGP_ENOCONV with every output written from the columns as they stand; GOGP_ENOTPD naming the column.
+ * Measured on one MI355X (tools/cg_lml_probe.py, profiles/cg_lml.txt; D = 8, medians of three): one pass of the pair
+ * reduction over N^2 pairs for S = 1 / 16 / 64 rows of weights: Normal 24.5 / 26.4 / 44.6 ms at N = 65536 and 388 / 434 / 719 ms
+ * at N = 262144, Matern-5/2 28.4 / 30.4 / 49.9 and 453 / 493 / 834 ms: 1.4 - 1.8e11 pairs per second at S = 1, and 64 rows cost
+ * 1.76 - 1.85 of one.  The whole evaluation (gogp_cg_solve at rank 256 + this call with 16 probes, tol = 1e-8) at N = 16384:
+ * 149 ms (Normal) and 668 ms (Matern-5/2) beside 71 ms for the dense gogp_observe + gogp_gradient, which is the call at
+ * that size; the estimate lies 1.55 and 0.35 standard errors (5.4 and 34.5) from the dense LML, the gradient within 6.9e-4
+ * and 1.4e-2 of the dense one's norm.  At N = 65536: 3.46 s and 19.3 s.
+ * Out of scope: the symmetry of K in the product and in the pair reduction, event discounts, several GPUs.  DESIGN.md
+ * section 4, "Iterative (CG)" and "Iterative (CG): LML and gradient". */
 #define GOGP_CG_MAX_RANK 1024
 #define GOGP_CG_MAX_RHS 64 /* systems per lock-step block */
 typedef struct {
@@ -637,6 +670,14 @@ int gogp_cg_solve_columns(gogp_handle *h, const double *B /* T rows of N */, int
 int gogp_cg_produce(gogp_handle *h, const double *Z, int64_t m, double *mu, double *sigma /* may be NULL */, double tol,
                     int32_t max_iter, gogp_cg_col *cols /* m, may be NULL */);
 int gogp_cg_last_info(gogp_handle *h, gogp_cg_info *info);
+typedef struct {
+  double lml, yt_alpha, logdet, logdet_precond, logdet_stderr;
+  int32_t probes, blocks, products, lanczos_max;
+} gogp_cg_lml_info;
+int gogp_cg_lml_gradient(gogp_handle *h, const double *Xi /* t rows of ldxi */, int64_t t, int64_t ldxi, double tol,
+                         int32_t max_iter, double *grad /* len, may be NULL */, int64_t len,
+                         double *quad /* t, may be NULL: rho0_s e1^T log(T_s) e1 */, gogp_cg_lml_info *info,
+                         gogp_cg_col *cols /* t, may be NULL */);
 
 /* k independent Observe + Gradient evaluations at once: handle hs[i] (each created and given
  * its data separately; they may hold the same data) evaluates x[i*len .. (i+1)*len) from its own

@@ -684,6 +684,21 @@ int gogp_test_cg_status(int device, int T, int32_t *st, int64_t st_len);
 int gogp_test_cg_precond(int device, const double *Ls, int64_t ls_len, int64_t ldn, int64_t n, int r, const double *dis,
                          int64_t dis_len, const double *Cinv, int64_t cinv_len, const double *R, int64_t r_len, int64_t ld,
                          int T, double *Z, int64_t z_len, double *C, int64_t c_len);
+/* The kernels of gogp_cg_lml_gradient (tests/test_cg_grad_kernel.py, test_cg_lml_cpu.py).
+ * launch_cg_grad: out (in / out; GOGP_TEST_NACC slot sums; `accumulate`: added to what it holds) [slot] = sum over i, j < n
+ * of (scale sum_{s < S} A[s][i] B[s][j]) theta_p dk(x_i, x_j)/dtheta_p, the trace slot taking the weights of i == j.  A, B:
+ * S >= 1 rows of ld >= n doubles ((S - 1) * ld + n elements at least), rows in passes of 64; X: n x ndim. */
+int gogp_test_cg_grad(int device, const gogp_test_kparams *kparams, const double *X, int64_t x_len, int64_t n,
+                      const double *A, int64_t a_len, const double *B, int64_t b_len, int64_t ld, int S, double scale,
+                      int accumulate, double *out /* GOGP_TEST_NACC */);
+/* launch_cg_probes: Z (in / out; T <= 64 rows of ld >= n) [t][i] = sqrt(d_i) (sum_{k < r} Ls[i][k] Xi[t][n + k] + Xi[t][i]).
+ * Ls: r columns of ldn >= n doubles, column-major (r == 0: NULL with length 0); d: n; Xi: T rows of ldxi >= n + r. */
+int gogp_test_cg_probes(int device, const double *Ls, int64_t ls_len, int64_t ldn, int64_t n, int r, const double *d,
+                        int64_t d_len, const double *Xi, int64_t xi_len, int64_t ldxi, int64_t ld, int T, double *Z,
+                        int64_t z_len);
+/* The host's quadrature: *out = rho0 e_1^T log(T) e_1 of the m x m Lanczos tridiagonal of the coefficients a[0 .. m),
+ * beta[0 .. m) (beta[m - 1] is not used); m == 0: 0.  No device. */
+int gogp_test_cg_quadrature(const double *a, const double *beta, int64_t m, double rho0, double *out);
 
 #ifdef __cplusplus
 }
