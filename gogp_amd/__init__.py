@@ -10,7 +10,7 @@ constructing a ``GP`` raises if the library or a HIP device is missing.
 """
 from . import kernel  # noqa: F401
 
-__all__ = ["kernel", "gp", "CGModel"]
+__all__ = ["kernel", "gp", "vecchia", "CGModel", "VecchiaModel"]
 __version__ = "0.1.0"
 
 
@@ -19,4 +19,10 @@ def __getattr__(name):
     if name == "CGModel":
         from .gp import CGModel
         return CGModel
+    if name == "VecchiaModel":  # Vecchia's approximation as an objective (gp.VecchiaModel)
+        from .gp import VecchiaModel
+        return VecchiaModel
+    if name == "vecchia":  # the host helpers that build neighbour tables (numpy only)
+        import importlib
+        return importlib.import_module(".vecchia", __name__)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

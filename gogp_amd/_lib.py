@@ -73,6 +73,7 @@ class CGemmPlan(ctypes.Structure):
 
 
 GOGP_CG_MAX_RANK, GOGP_CG_MAX_RHS = 1024, 64
+GOGP_VECCHIA_MAX_M = 63
 
 
 class CCgCol(ctypes.Structure):
@@ -161,6 +162,11 @@ SYMBOLS = [
     ("gogp_cg_lml_gradient", ctypes.c_int,
      [_h, _dp, _i64, _i64, ctypes.c_double, ctypes.c_int32, _dp, _i64, _dp, ctypes.POINTER(CCgLmlInfo),
       ctypes.POINTER(CCgCol)]),
+    ("gogp_vecchia_check", ctypes.c_int, [ctypes.POINTER(ctypes.c_int32), _i64, ctypes.c_int32, _i64, ctypes.c_int]),
+    ("gogp_vecchia_set_data", ctypes.c_int, [_h, _dp, _dp, _dp, _i64, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32]),
+    ("gogp_vecchia_observe", ctypes.c_int, [_h, _dp, _i64, _dp, _dp]),
+    ("gogp_vecchia_gradient", ctypes.c_int, [_h, _dp, _i64]),
+    ("gogp_vecchia_produce", ctypes.c_int, [_h, _dp, _i64, ctypes.POINTER(ctypes.c_int32), _dp, _dp]),
     ("gogp_observe_gradient_batch", ctypes.c_int,
      [ctypes.POINTER(_h), ctypes.c_int, _dp, _i64, _dp, _dp, ctypes.POINTER(ctypes.c_int)]),
     ("gogp_observe_gradient_candidates", ctypes.c_int,
@@ -474,6 +480,13 @@ HOOK_SYMBOLS += [
     ("gogp_test_cg_quadrature", _ci, [_dp, _dp, _i64, ctypes.c_double, _dp]),
     ("gogp_test_cg_precond", _ci, [_ci, _dp, _i64, _i64, _i64, _ci, _dp, _i64, _dp, _i64, _dp, _i64, _i64, _ci, _dp, _i64,
                                    _dp, _i64]),
+]
+
+#: the hook of the kernel of vecchia.hip (tests/test_vecchia_kernel.py; gp.vecchia_check)
+HOOK_SYMBOLS += [
+    ("gogp_test_vecchia_blocks", _ci, [_i64, _ci]),
+    ("gogp_test_vecchia", _ci, [_ci, _kpp, _ci, _ci, _dp, _i64, _dp, _i64, _dp, _i64, _i64, _dp, _i64, _i64, _i32p, _i64, _ci,
+                                _dp, _i64, _dp, _i64, _dp, _i64, _dp, ctypes.POINTER(_i64), _ci]),
 ]
 
 

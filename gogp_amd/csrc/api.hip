@@ -255,6 +255,7 @@ static hipError_t graph_stream(gogp_handle *h) {
 
 static void sparse_free(gogp_handle *h);  // the inducing-point state (gogp_sparse_*), below
 static void cg_free(gogp_handle *h);      // the data and state of the iterative exact GP (gogp_cg_*), below
+static void vecchia_free(gogp_handle *h); // the data and state of Vecchia's approximation (gogp_vecchia_*), below
 
 static void release_streams(gogp_handle *h) {
   std::lock_guard<std::mutex> lock(g_pool_mutex);
@@ -271,6 +272,7 @@ extern "C" void gogp_destroy(gogp_handle *h) {
   gogp_dist_destroy(h);
   sparse_free(h);
   cg_free(h);
+  vecchia_free(h);
   free_n_buffers(h);
   free_m_buffers(h);
   free_cand_buffers(h);
@@ -4798,6 +4800,257 @@ extern "C" int gogp_cg_lml_gradient(gogp_handle *h, const double *Xi, int64_t t,
   }
   if (ret != GOGP_OK) h->err = first_err;
   return ret;
+}
+
+// ---- Vecchia's approximation (vecchia.hip) -----------------------------------------------------------------------------
+// include/gogp_hip.h states the approximation and the table; DESIGN.md section 4, "Vecchia".  One kernel does all the
+// work; everything runs on the handle's main stream with buffers of the family's own, and the parameters are a copy of
+// the family's own, so that devP keeps what the last dense evaluation uploaded.
+static void vecchia_free(gogp_handle *h) {
+  VecchiaState &vc = h->vc;
+  for (double *q : {vc.X, vc.y, vc.v}) (void)hipFree(q);
+  (void)hipFree(vc.nbr);
+  (void)hipFree(vc.P);
+  vc.small.release();
+  vc.terms.release();
+  vc.prod.release();
+  vc = VecchiaState();
+}
+
+// the first row of the table that breaks the format of include/gogp_hip.h, or -1
+static int64_t vecchia_bad_row(const int32_t *nbr, int64_t rows, int32_t m, int64_t n, int causal) {
+  for (int64_t i = 0; i < rows; ++i) {
+    const int32_t *r = nbr + i * m;
+    const int64_t lim = causal ? i : n;
+    bool pad = false;
+    for (int32_t a = 0; a < m; ++a) {
+      if (r[a] == -1) {
+        pad = true;
+        continue;
+      }
+      if (pad || r[a] < 0 || (int64_t)r[a] >= lim) return i;
+      for (int32_t b = 0; b < a; ++b)
+        if (r[b] == r[a]) return i;
+    }
+  }
+  return -1;
+}
+
+extern "C" int gogp_vecchia_check(const int32_t *nbr, int64_t rows, int32_t m, int64_t n, int causal) {
+  if (m < 0 || m > GOGP_VECCHIA_MAX_M || rows < 0 || n < 0 || (causal && rows > n)) return GOGP_EARG;
+  if (rows > 0 && m > 0 && !nbr) return GOGP_EARG;
+  return vecchia_bad_row(nbr, rows, m, n, causal) < 0 ? GOGP_OK : GOGP_EARG;
+}
+
+// gogp_vecchia_check with the first offending row named in the handle's error text
+static int vecchia_check_named(gogp_handle *h, const char *who, const int32_t *nbr, int64_t rows, int32_t m, int64_t n,
+                               int causal) {
+  if (gogp_vecchia_check(nbr, rows, m, n, causal) == GOGP_OK) return GOGP_OK;
+  char buf[320];
+  const int64_t bad = (nbr && m >= 0 && m <= GOGP_VECCHIA_MAX_M && rows >= 0) ? vecchia_bad_row(nbr, rows, m, n, causal) : -1;
+  if (bad >= 0)
+    snprintf(buf, sizeof buf,
+             "%s: row %lld of the table is not %s: distinct indices %s, then -1 padding (gogp_vecchia_check)", who,
+             (long long)bad, causal ? "causal" : "valid", causal ? "below the row's own" : "in [0, N)");
+  else
+    snprintf(buf, sizeof buf, "%s: need a table of rows x m int32 with 0 <= m <= %d (gogp_vecchia_check)", who,
+             GOGP_VECCHIA_MAX_M);
+  return fail(h, GOGP_EARG, buf);
+}
+
+// the small device buffers behind an observe: the value, the info word, the slot sums, then per workgroup the value, the
+// failure word and the partial row
+struct VecchiaSmall {
+  double *value, *gout, *vpart, *partials;
+  long long *info, *fpart;
+};
+static size_t vecchia_small_layout(char *base, int blocks, VecchiaSmall *b) {
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    char *q = base ? base + off : nullptr;
+    off += (bytes + 255) / 256 * 256;
+    return q;
+  };
+  b->value = reinterpret_cast<double *>(take(sizeof(double)));
+  b->info = reinterpret_cast<long long *>(take(sizeof(long long)));
+  b->gout = reinterpret_cast<double *>(take(NACC * sizeof(double)));
+  b->vpart = reinterpret_cast<double *>(take((size_t)blocks * sizeof(double)));
+  b->fpart = reinterpret_cast<long long *>(take((size_t)blocks * sizeof(long long)));
+  b->partials = reinterpret_cast<double *>(take((size_t)blocks * NACC * sizeof(double)));
+  return off;
+}
+
+extern "C" int gogp_vecchia_set_data(gogp_handle *h, const double *X, const double *y, const double *v, int64_t N,
+                                     const int32_t *nbr, int32_t m) {
+  const char *who = "vecchia_set_data";
+  if (!h) return GOGP_EARG;
+  if (N == 0 && !X && !y && !v && !nbr) {  // clear
+    HIPCHK(h, hipSetDevice(h->device));
+    vecchia_free(h);
+    return GOGP_OK;
+  }
+  if (sparse_refusal(h)) return cg_refuse_handle(h, who);
+  if (N < 1 || !X || !y) return cg_refuse(h, who, GOGP_EARG, "need X, y and N >= 1 (N == 0 with NULLs clears)");
+  if (N > INT32_MAX) return cg_refuse(h, who, GOGP_EARG, "the table's indices are int32: N <= 2^31 - 1");
+  if (const int rc = vecchia_check_named(h, who, nbr, N, m, N, 1)) return rc;
+  const int D = h->D;
+  for (int64_t i = 0; i < N * D; ++i)
+    if (!std::isfinite(X[i])) return cg_refuse(h, who, GOGP_EARG, "non-finite input");
+  for (int64_t i = 0; i < N; ++i)
+    if (!std::isfinite(y[i])) return cg_refuse(h, who, GOGP_EARG, "non-finite output");
+  if (v)
+    for (int64_t i = 0; i < N; ++i)
+      if (!std::isfinite(v[i]) || v[i] < 0.0) return cg_refuse(h, who, GOGP_EARG, "noise variances must be finite and >= 0");
+  HIPCHK(h, hipSetDevice(h->device));
+  if (h->s) HIPCHK(h, hipStreamSynchronize(h->s));
+  vecchia_free(h);
+  VecchiaState &vc = h->vc;
+  const size_t xb = (size_t)N * D * sizeof(double), vb = (size_t)N * sizeof(double);
+  const size_t tb = std::max<size_t>((size_t)N * (size_t)m * sizeof(int32_t), 256);
+  hipStream_t s = h->s;
+  hipError_t e = hipMalloc(&vc.X, xb);
+  if (e == hipSuccess) e = hipMalloc(&vc.y, vb);
+  if (e == hipSuccess && v) e = hipMalloc(&vc.v, vb);
+  if (e == hipSuccess) e = hipMalloc(&vc.nbr, tb);
+  if (e == hipSuccess) e = hipMalloc(&vc.P, sizeof(DevParams));
+  if (e == hipSuccess) e = hipMemcpyAsync(vc.X, X, xb, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(vc.y, y, vb, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess && v) e = hipMemcpyAsync(vc.v, v, vb, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess && m > 0)
+    e = hipMemcpyAsync(vc.nbr, nbr, (size_t)N * (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e != hipSuccess) {
+    vecchia_free(h);
+    HIPCHK(h, e);
+  }
+  vc.N = N;
+  vc.m = m;
+  vc.have = true;
+  return GOGP_OK;
+}
+
+// One pass of the kernel over the stored data: the value's (grad false: terms, *value, *info) or the gradient's (the
+// slot sums into acc; nothing else is written).  The stream is idle on return.
+static int vecchia_run(gogp_handle *h, bool grad, double *dterms, double *value, long long *info, double *acc) {
+  VecchiaState &vc = h->vc;
+  hipStream_t s = h->s;
+  const int blocks = vecchia_blocks(vc.N);
+  VecchiaSmall sm;
+  const size_t bytes = vecchia_small_layout(nullptr, blocks, &sm);
+  if (const int rc = vc.small.reserve(h, bytes)) return rc;
+  vecchia_small_layout(vc.small.as<char>(), blocks, &sm);
+  launch_vecchia_observe(s, vc.P, h->D, h->ard_dims, vc.X, vc.y, vc.v, vc.N, vc.nbr, vc.m, dterms,
+                         grad ? sm.partials : nullptr, sm.vpart, sm.fpart, sm.gout, grad ? nullptr : sm.value,
+                         grad ? nullptr : sm.info);
+  if (grad) {
+    HIPCHK(h, hipMemcpyAsync(acc, sm.gout, NACC * sizeof(double), hipMemcpyDeviceToHost, s));
+  } else {
+    HIPCHK(h, hipMemcpyAsync(value, sm.value, sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(info, sm.info, sizeof(long long), hipMemcpyDeviceToHost, s));
+  }
+  HIPCHK(h, hipStreamSynchronize(s));
+  HIPCHK(h, hipGetLastError());
+  return GOGP_OK;
+}
+
+static int vecchia_notpd(gogp_handle *h, const char *who, long long info, const char *what) {
+  char buf[240];
+  snprintf(buf, sizeof buf, "%s: the block of %s %lld has a pivot that is not positive and finite", who, what, info - 1);
+  h->notpd = (int64_t)(info - 1);
+  return fail(h, GOGP_ENOTPD, buf);
+}
+
+extern "C" int gogp_vecchia_observe(gogp_handle *h, const double *x, int64_t len, double *lml, double *terms) {
+  const char *who = "vecchia_observe";
+  if (!h) return GOGP_EARG;
+  if (!x || !lml) return cg_refuse(h, who, GOGP_EARG, "NULL");
+  if (sparse_refusal(h)) return cg_refuse_handle(h, who);
+  if (len != h->P) return cg_refuse(h, who, GOGP_EARG, "len(x)");
+  for (int64_t i = 0; i < len; ++i)
+    if (!std::isfinite(x[i])) return cg_refuse(h, who, GOGP_EARG, "non-finite parameter");
+  VecchiaState &vc = h->vc;
+  if (!vc.have) return cg_refuse(h, who, GOGP_ESTATE, "no data (gogp_vecchia_set_data)");
+  std::vector<double> th(h->P > 0 ? h->P : 1);
+  for (int i = 0; i < h->P; ++i) th[i] = exp(x[i]);
+  if (const char *why = theta_refusal(h, th.data(), th.data() + h->ns)) return cg_refuse(h, who, GOGP_EARG, why);
+  DevParams hp;
+  fill_params_theta(h, th.data(), th.data() + h->ns, hp);
+  HIPCHK(h, hipSetDevice(h->device));
+  hipStream_t s = h->s;
+  vc.observed = false;
+  vc.dnoise = hp.dnoise;
+  HIPCHK(h, hipMemcpyAsync(vc.P, &hp, sizeof hp, hipMemcpyHostToDevice, s));
+  HIPCHK(h, hipStreamSynchronize(s));  // hp is a local
+  double *dterms = nullptr;
+  if (terms) {
+    if (const int rc = vc.terms.reserve(h, (size_t)vc.N * 3 * sizeof(double))) return rc;
+    dterms = vc.terms.as<double>();
+  }
+  double value = 0.0;
+  long long info = 0;
+  if (const int rc = vecchia_run(h, false, dterms, &value, &info, nullptr)) return rc;
+  if (terms) HIPCHK(h, hipMemcpy(terms, dterms, (size_t)vc.N * 3 * sizeof(double), hipMemcpyDeviceToHost));
+  if (info != 0) {
+    *lml = NAN;
+    return vecchia_notpd(h, who, info, "row");
+  }
+  *lml = value;
+  vc.observed = true;
+  return GOGP_OK;
+}
+
+extern "C" int gogp_vecchia_gradient(gogp_handle *h, double *grad, int64_t len) {
+  const char *who = "vecchia_gradient";
+  if (!h) return GOGP_EARG;
+  if (!grad) return cg_refuse(h, who, GOGP_EARG, "NULL");
+  if (sparse_refusal(h)) return cg_refuse_handle(h, who);
+  if (len != h->P) return cg_refuse(h, who, GOGP_EARG, "len(grad)");
+  VecchiaState &vc = h->vc;
+  if (!vc.have || !vc.observed) return cg_refuse(h, who, GOGP_ESTATE, "nothing observed (gogp_vecchia_observe)");
+  HIPCHK(h, hipSetDevice(h->device));
+  double acc[NACC];
+  if (const int rc = vecchia_run(h, true, nullptr, nullptr, nullptr, acc)) return rc;
+  for (int64_t i = 0; i < len; ++i) grad[i] = 0.0;
+  assemble_gradient(h, acc, vc.dnoise, grad);
+  return GOGP_OK;
+}
+
+extern "C" int gogp_vecchia_produce(gogp_handle *h, const double *Z, int64_t mz, const int32_t *nbrz, double *mu,
+                                    double *sigma) {
+  const char *who = "vecchia_produce";
+  if (!h) return GOGP_EARG;
+  if (sparse_refusal(h)) return cg_refuse_handle(h, who);
+  if (mz < 0 || (mz > 0 && (!Z || !mu))) return cg_refuse(h, who, GOGP_EARG, "need Z and mu for mz > 0, mz >= 0");
+  VecchiaState &vc = h->vc;
+  if (!vc.have || !vc.observed) return cg_refuse(h, who, GOGP_ESTATE, "nothing observed (gogp_vecchia_observe)");
+  if (const int rc = vecchia_check_named(h, who, nbrz, mz, vc.m, vc.N, 0)) return rc;
+  const int D = h->D, m = vc.m;
+  for (int64_t i = 0; i < mz * D; ++i)
+    if (!std::isfinite(Z[i])) return cg_refuse(h, who, GOGP_EARG, "non-finite test point");
+  if (mz == 0) return GOGP_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  hipStream_t s = h->s;
+  const int blocks = vecchia_blocks(mz);
+  auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+  const size_t zb = up((size_t)mz * D * sizeof(double)), vb = up((size_t)mz * sizeof(double));
+  const size_t tb = up(std::max<size_t>((size_t)mz * (size_t)m * sizeof(int32_t), 4)), fb = up((size_t)blocks * sizeof(long long));
+  if (const int rc = vc.prod.reserve(h, zb + 2 * vb + tb + fb + 256)) return rc;
+  char *base = vc.prod.as<char>();
+  double *dZ = reinterpret_cast<double *>(base), *dmu = reinterpret_cast<double *>(base + zb);
+  double *dsig = reinterpret_cast<double *>(base + zb + vb);
+  int *dnb = reinterpret_cast<int *>(base + zb + 2 * vb);
+  long long *dfp = reinterpret_cast<long long *>(base + zb + 2 * vb + tb), *dinfo = dfp + blocks;
+  HIPCHK(h, hipMemcpyAsync(dZ, Z, (size_t)mz * D * sizeof(double), hipMemcpyHostToDevice, s));
+  if (m > 0) HIPCHK(h, hipMemcpyAsync(dnb, nbrz, (size_t)mz * (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  launch_vecchia_produce(s, vc.P, D, vc.X, vc.y, vc.v, dZ, mz, dnb, m, dmu, sigma ? dsig : nullptr, dfp, dinfo);
+  long long info = 0;
+  HIPCHK(h, hipMemcpyAsync(mu, dmu, (size_t)mz * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (sigma) HIPCHK(h, hipMemcpyAsync(sigma, dsig, (size_t)mz * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipMemcpyAsync(&info, dinfo, sizeof info, hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipStreamSynchronize(s));
+  HIPCHK(h, hipGetLastError());
+  if (info != 0) return vecchia_notpd(h, who, info, "test point");
+  return GOGP_OK;
 }
 
 // ---- non-Gaussian likelihoods by the Laplace approximation (laplace.hip) -----------------------------------------------

@@ -664,6 +664,24 @@ void launch_cg_probes(hipStream_t s, const double *Ls, int64_t ldn, int64_t n, i
 void launch_cg_grad(hipStream_t s, const DevParams *p, int ndim, int ard_dims, const double *X, int64_t n, const double *A,
                     const double *B, int64_t ld, int S, double scale, double *partials, double *out, bool accumulate);
 double cg_lanczos_quadrature(const double *a, const double *beta, int64_t stride, int m, double rho0);
+// vecchia.hip (gogp_vecchia_*): Vecchia's approximation, one wave per target (the head of vecchia.hip states the kernel).
+// nbr: `targets` rows of m <= 63 int32 indices into X's rows, -1 padding trailing, as gogp_vecchia_check accepts them --
+// the kernel indexes X, y and v with them unchecked.  launch_vecchia_observe, value != nullptr: the value's pass -- terms (N
+// x 3: mu, s, log p; nullptr: not written), value[0] = sum_i log p_i, info[0] = the lowest target with a bad pivot + 1, or
+// 0; partials != nullptr (vecchia_blocks(N) * NACC doubles): the gradient's pass(es), which leave the NACC slot sums in
+// gout and skip a target with a bad pivot.  vpart / fpart: vecchia_blocks(targets) entries each.  launch_vecchia_produce: mu, sigma (nullptr: not written) of the mz rows
+// of Z, each conditioned on the rows nbrz names; info as above.  Both instances (blocks of at most 32 / 64 rows) give a
+// target the same bits.  max_blocks > 0 caps the grid below VECCHIA_BLOCKS_MAX (tests: waves that walk several targets at
+// a small size).
+constexpr int VECCHIA_BLOCKS_MAX = 2048;  // workgroups (one wave each; rows of `partials`) at most
+int vecchia_blocks(int64_t targets, int max_blocks = 0);
+void launch_vecchia_observe(hipStream_t s, const DevParams *p, int ndim, int ard_dims, const double *X, const double *y,
+                            const double *v, int64_t N, const int *nbr, int m, double *terms, double *partials,
+                            double *vpart, long long *fpart, double *gout, double *value, long long *info,
+                            int max_blocks = 0);
+void launch_vecchia_produce(hipStream_t s, const DevParams *p, int ndim, const double *X, const double *y, const double *v,
+                            const double *Z, int64_t mz, const int *nbrz, int m, double *mu, double *sigma,
+                            long long *fpart, long long *info, int max_blocks = 0);
 // laplace.hip (gogp_laplace_*): the passes around the factorisation of B = I + diag(sw) K diag(sw).  Vectors hold npad
 // doubles (npad a multiple of 256) and leave every launcher zero from row n on.
 // launch_lap_site: g, W, sw = sqrt(W), b = W f + g, rho of the rows i < n; part: 5 * npad / 256 doubles of block results;

@@ -61,6 +61,22 @@ struct Workspace {
   T *as() const { return static_cast<T *>(p); }
 };
 
+// The state of the Vecchia calls (api.hip: gogp_vecchia_*).  Device memory: X, y and v (N (D + 2) doubles), 4 N m bytes of
+// table, the terms (3 N doubles, from the first observe that asks for them) and at most VECCHIA_BLOCKS_MAX partial rows
+// with the workgroups' values and failure words.
+struct VecchiaState {
+  double *X = nullptr, *y = nullptr, *v = nullptr;  // N x D, N, N (nullptr: no variances)
+  int *nbr = nullptr;                               // N x m, row-major
+  DevParams *P = nullptr;                           // the parameters of the last observe
+  int64_t N = 0;
+  int m = 0;
+  bool have = false, observed = false;
+  double dnoise = 0.0;  // d noise_var / d log(noise parameter) at the last observe's theta
+  Workspace small;      // value, info word, NACC slot sums, the workgroups' values, failure words and partial rows
+  Workspace terms;      // N x 3
+  Workspace prod;       // gogp_vecchia_produce: Z, the table, mu, sigma, the failure words
+};
+
 // What an evaluation leaves in the handle; a candidates call saves it and puts it back
 struct EvalState {
   bool factored = false, have_alpha = false, have_kinv = false;
@@ -281,6 +297,9 @@ struct gogp_handle : EvalBufs, EvalState {
   double cg_logdet_c = 0.0;        // log |C| of the last solve's capacitance matrix (0 at rank 0)
   double cg_dnoise = 0.0;          // d noise_var / d log(noise parameter) at the last solve's theta
   Workspace cg_lml;                // gogp_cg_lml_gradient: a block's rows of Xi, the a / beta history, rho0, slot sums and partials
+  // Vecchia's approximation (gogp_vecchia_*, vecchia.hip): a data set and a table of its own, resident; nothing of the
+  // handle's other state is touched
+  VecchiaState vc;
   // the Laplace approximation (gogp_laplace_*, laplace.hip; api.hip: LapVecs).  B's factor lies in bufL / Dinv, B^-1 and
   // then the gradient's weight matrix in bufA; only vectors are its own (released with the N buffers).
   Workspace lap_ws;

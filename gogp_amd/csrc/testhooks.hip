@@ -2609,3 +2609,43 @@ extern "C" int gogp_test_cg_quadrature(const double *a, const double *beta, int6
   *out = cg_lanczos_quadrature(a, beta, 1, (int)m, rho0);
   return GOGP_OK;
 }
+
+// ---- vecchia.hip ---------------------------------------------------------------------------------------------------------
+extern "C" int gogp_test_vecchia_blocks(int64_t targets, int max_blocks) {
+  return targets < 1 || max_blocks < 0 ? -1 : vecchia_blocks(targets, max_blocks);
+}
+
+extern "C" int gogp_test_vecchia(int device, const gogp_test_kparams *kparams, int produce, int grad, const double *X,
+                                 int64_t x_len, const double *y, int64_t y_len, const double *v, int64_t v_len, int64_t n,
+                                 const double *Z, int64_t z_len, int64_t targets, const int32_t *nbr, int64_t nbr_len, int m,
+                                 double *terms, int64_t terms_len, double *partials, int64_t partials_len, double *vpart,
+                                 int64_t vpart_len, double *value, int64_t *info, int max_blocks) {
+  if (!kparams || !value || !info || max_blocks < 0) return GOGP_EARG;
+  if (!kparams_ok(kparams, 1, ard_dims_of(kparams), 0, 1, 0) || kparams->nevents != 0) return GOGP_EARG;
+  const int D = kparams->ndim;
+  if (n < 1 || n > (1 << 20) || targets < 1 || targets > (1 << 20) || m < 0 || m > GOGP_VECCHIA_MAX_M) return GOGP_EARG;
+  if (!produce && targets != n) return GOGP_EARG;
+  if (x_len < n * D || y_len < n || (v ? v_len < n : v_len != 0)) return GOGP_EARG;
+  if (m > 0 ? (!nbr || nbr_len < targets * m) : (nbr || nbr_len != 0)) return GOGP_EARG;
+  if (gogp_vecchia_check(nbr, targets, m, n, produce ? 0 : 1) != GOGP_OK) return GOGP_EARG;
+  const int blocks = vecchia_blocks(targets, max_blocks);
+  const bool want_grad = !produce && grad != 0;
+  if (produce ? (!Z || z_len < targets * D || !terms || terms_len < 2 * targets || partials || vpart)
+              : (Z || z_len != 0 || (terms ? terms_len < 3 * n : terms_len != 0) || !vpart || vpart_len < blocks))
+    return GOGP_EARG;
+  if (want_grad ? (!partials || partials_len < (int64_t)blocks * NACC) : (partials || partials_len != 0)) return GOGP_EARG;
+  const DevParams hp = to_dev(*kparams);
+  const std::vector<Arr> arrs = {rd(&hp, 1, sizeof hp), rd(X, x_len), rd(y, y_len), opt(rd(v, v_len)), opt(rd(Z, z_len)),
+                                 opt(rd(nbr, nbr_len, 4)), opt(io(terms, terms_len)), opt(io(partials, partials_len)),
+                                 opt(io(vpart, vpart_len)), io(value, 1), io(info, 1),
+                                 scratch((size_t)blocks * sizeof(long long)), scratch(NACC * sizeof(double))};
+  if (!have(arrs)) return GOGP_EARG;
+  return run(device, arrs, [&](const Dev &d) {
+    if (produce)
+      launch_vecchia_produce(0, d.as<DevParams>(0), D, d[1], d[2], d[3], d[4], targets, d.as<int>(5), m, d[6],
+                             d[6] + targets, d.as<long long>(11), d.as<long long>(10), max_blocks);
+    else
+      launch_vecchia_observe(0, d.as<DevParams>(0), D, ard_dims_of(kparams), d[1], d[2], d[3], n, d.as<int>(5), m, d[6], d[7],
+                             d[8], d.as<long long>(11), d[12], d[9], d.as<long long>(10), max_blocks);
+  });
+}

@@ -899,6 +899,84 @@ class GP:
             raise GogpError(_lib.GOGP_ESTATE, "CGGradient before CGObserve")
         return g.copy()
 
+    # ---- Vecchia's approximation: nearest-neighbour conditionals (gogp_vecchia_*) ----
+    @staticmethod
+    def _vecchia_table(neighbours, rows: int, what: str) -> np.ndarray:
+        t = np.ascontiguousarray(np.asarray(neighbours, dtype=np.int32))
+        if t.ndim != 2 or t.shape[0] != rows:
+            raise ValueError("%s: the table has one row per target (%d x m int32)" % (what, rows))
+        return t
+
+    def SetVecchia(self, x, y, neighbours, v=None) -> None:
+        """The data of the Vecchia calls, a set of their own that stays on the device (gogp_vecchia_set_data): x (N x
+        NDim), y (N), the table ``neighbours`` (N x m int32, m <= 63: row i holds distinct indices below i, then -1
+        padding; gogp_amd.vecchia.previous / nearest build one) and, optionally, per-observation noise variances v.
+        ``SetVecchia(None, None, None)`` clears them.  Nothing else of the process changes."""
+        if x is None and y is None and neighbours is None and v is None:
+            self._vc_n, self._vc_m = 0, 0
+            self._check(_lib.lib().gogp_vecchia_set_data(self._h, None, None, None, 0, None, 0))
+            return
+        xs = np.ascontiguousarray(_arr(x).reshape(-1, self.NDim))
+        ys = np.ascontiguousarray(_arr(y).reshape(-1))
+        if len(xs) != len(ys):
+            raise ValueError("SetVecchia: len(x) != len(y)")
+        t = self._vecchia_table(neighbours, len(ys), "SetVecchia")
+        va = None
+        if v is not None:
+            va = np.ascontiguousarray(_arr(v).reshape(-1))
+            if va.size != len(ys):
+                raise ValueError("SetVecchia: one variance per observation")
+        self._vc_terms = None
+        self._check(_lib.lib().gogp_vecchia_set_data(self._h, _dp(xs) if len(xs) else None, _dp(ys) if len(ys) else None,
+                                                     _dp(va), len(ys), _i32p(t) if t.size else None, t.shape[1]))
+        self._vc_n, self._vc_m = len(ys), t.shape[1]
+
+    def VecchiaObserve(self, theta) -> float:
+        """Vecchia's approximation of the LML at theta = log of the hyperparameters (gogp_vecchia_observe): the sum of the
+        N conditionals' log densities.  A valid joint density, not a bound; exact when every row conditions on all earlier
+        ones.  The terms are kept for VecchiaTerms()."""
+        xa = np.ascontiguousarray(_arr(theta).reshape(-1))
+        n = getattr(self, "_vc_n", 0)
+        terms = np.zeros((max(n, 1), 3))
+        val = ctypes.c_double(0.0)
+        self._vc_terms = None
+        rc = _lib.lib().gogp_vecchia_observe(self._h, _dp(xa if xa.size else np.zeros(1)), xa.size, ctypes.byref(val),
+                                             _dp(terms))
+        if rc in (_lib.GOGP_OK, _lib.GOGP_ENOTPD):
+            self._vc_terms = terms[:n]
+        self._check(rc)
+        return val.value
+
+    def VecchiaTerms(self):
+        """(mu, s, logp) of the last VecchiaObserve, N each: the one-step-ahead forecast of y_i from its conditioning rows
+        (s includes the noise) and its log density.  After a FactorizeError the failing rows hold NaN."""
+        t = getattr(self, "_vc_terms", None)
+        if t is None:
+            raise GogpError(_lib.GOGP_ESTATE, "VecchiaTerms before VecchiaObserve")
+        return t[:, 0].copy(), t[:, 1].copy(), t[:, 2].copy()
+
+    def VecchiaGradient(self) -> np.ndarray:
+        """d value / d log theta at the parameters of the last VecchiaObserve (gogp_vecchia_gradient): the exact derivative
+        of VecchiaObserve's value, the noise parameter's component included."""
+        g = np.zeros(self._ns + self._nn)
+        self._check(_lib.lib().gogp_vecchia_gradient(self._h, _dp(g if g.size else np.zeros(1)), g.size))
+        return g
+
+    def VecchiaProduce(self, z, neighbours, sigma: bool = True):
+        """(mu, sigma) at the test points z, each conditioned on the rows of the Vecchia data its row of ``neighbours``
+        (len(z) x m, the m of SetVecchia; gogp_amd.vecchia.nearest_to builds one) names, at the parameters of the last
+        VecchiaObserve; latent and unclamped as Produce (gogp_vecchia_produce).  ``sigma=False`` returns (mu, None)."""
+        zz = np.ascontiguousarray(_arr(z).reshape(-1, self.NDim))
+        mz = len(zz)
+        t = self._vecchia_table(neighbours, mz, "VecchiaProduce")
+        if t.shape[1] != getattr(self, "_vc_m", 0):  # the library reads mz x m entries, the m of SetVecchia
+            raise ValueError("VecchiaProduce: the table has %d columns, SetVecchia's has %d" % (t.shape[1], getattr(self, "_vc_m", 0)))
+        mu = np.zeros(mz)
+        sg = np.zeros(mz) if sigma else None
+        self._check(_lib.lib().gogp_vecchia_produce(self._h, _dp(zz) if mz else None, mz, _i32p(t) if t.size else None,
+                                                    _dp(mu) if mz else None, _dp(sg) if mz and sigma else None))
+        return mu, sg
+
     def SparseObserve(self, x) -> float:
         """The collapsed variational bound of Titsias (2009) at x = log theta (gogp_sparse_observe): a lower bound of
         the LML of the sparse data that costs O(N M^2)."""
@@ -1521,6 +1599,33 @@ class CGModel:
 
     def Gradient(self) -> np.ndarray:
         g = self.gp.CGGradient()
+        if self.Priors is not None:
+            self.Priors.Observe(self._x)
+            pg = np.asarray(self.Priors.Gradient(), dtype=float)
+            g[:len(pg)] += pg
+        return g
+
+
+class VecchiaModel:
+    """Model with Vecchia's approximation of GP.SetVecchia in the place of the LML: Observe(x) returns
+    GP.VecchiaObserve(x) (+ the log prior), Gradient() returns GP.VecchiaGradient() (+ the prior's), for optimize.lbfgs and
+    optimize.Adam.  The gradient is the exact derivative of the value, so a line search is consistent.  The neighbour
+    table is fixed by GP.SetVecchia: a table built with length scales (vecchia.nearest) is not rebuilt as they move."""
+
+    def __init__(self, gp: GP, Priors=None):
+        self.gp = gp
+        self.Priors = Priors
+        self._x = None
+
+    def Observe(self, x) -> float:
+        self._x = _arr(x).reshape(-1).copy()
+        if self._x.size != self.gp._ns + self.gp._nn:
+            raise ValueError("len(x): the Vecchia objective takes the hyperparameters only")
+        v = self.gp.VecchiaObserve(self._x)
+        return v + self.Priors.Observe(self._x) if self.Priors is not None else v
+
+    def Gradient(self) -> np.ndarray:
+        g = self.gp.VecchiaGradient()
         if self.Priors is not None:
             self.Priors.Observe(self._x)
             pg = np.asarray(self.Priors.Gradient(), dtype=float)
@@ -2468,3 +2573,37 @@ def cg_quadrature(a: np.ndarray, beta: np.ndarray, rho0: float) -> float:
     if rc != _lib.GOGP_OK:
         raise GogpError(rc, "test_cg_quadrature")
     return float(out[0])
+
+
+def vecchia_blocks(targets: int, max_blocks: int = 0) -> int:
+    """The workgroups (rows of partial sums) of a Vecchia launch over ``targets`` targets.  No device."""
+    r = int(_lib.hooks().gogp_test_vecchia_blocks(targets, max_blocks))
+    if r < 0:
+        raise GogpError(_lib.GOGP_EARG, "test_vecchia_blocks")
+    return r
+
+
+def vecchia_check(kp, X: np.ndarray, y: np.ndarray, v, n: int, nbr, m: int, terms, partials=None, vpart=None, Z=None,
+                  targets=None, max_blocks: int = 0, device: int = -1):
+    """The kernel of vecchia.hip on caller-supplied parameters, rows, table and y (test hook gogp_test_vecchia).  Observe
+    (Z None): terms (n x 3 or None), vpart (one value per workgroup) and, where ``partials`` is given, the workgroups' rows
+    of NACC slot sums.  Produce (Z given, ``targets`` rows): terms is targets x 2 (mu, sigma).  nbr: int32, targets x m
+    (None with m == 0).  Returns copies: (terms, partials, vpart, value, info) with info = the lowest failing target + 1."""
+    X, y = _vec(X, "X"), _vec(y, "y")
+    produce = Z is not None
+    targets = n if targets is None else targets
+    vp, vl = _opt(v, "v")
+    zp, zl = _opt(Z, "Z")
+    terms = None if terms is None else _vec(terms, "terms").copy()
+    partials = None if partials is None else _vec(partials, "partials").copy()
+    vpart = None if vpart is None else _vec(vpart, "vpart").copy()
+    nb = None if nbr is None else _i32(nbr, "nbr")
+    value, info = np.zeros(1), np.zeros(1, dtype=np.int64)
+    rc = _lib.hooks().gogp_test_vecchia(
+        device, ctypes.byref(kp), int(produce), int(partials is not None), _dp(X), X.size, _dp(y), y.size, vp, vl, n, zp, zl,
+        targets, None if nb is None else _i32p(nb), 0 if nb is None else nb.size, m, _dp(terms),
+        0 if terms is None else terms.size, _dp(partials), 0 if partials is None else partials.size, _dp(vpart),
+        0 if vpart is None else vpart.size, _dp(value), _ip(info), max_blocks)
+    if rc != _lib.GOGP_OK:
+        raise GogpError(rc, "test_vecchia")
+    return terms, partials, vpart, float(value[0]), int(info[0])

@@ -457,6 +457,49 @@ class GP {
     if (rc != GOGP_ENOCONV) check(rc);
     return rc;
   }
+  // Vecchia's approximation (gogp_vecchia_*): log p(y) ~ sum_i log p(y_i | y_c(i)) on the conditioning rows the table
+  // names -- nbr: N x m int32 row-major, m <= GOGP_VECCHIA_MAX_M, row i distinct indices below i and then -1 padding
+  // (gogp_vecchia_check).  A data set of its own that stays on the device; empty x, y and nbr clear it.
+  static bool VecchiaCheck(const std::vector<int32_t> &nbr, int64_t rows, int32_t m, int64_t n, bool causal) {
+    return (int64_t)nbr.size() >= rows * m && gogp_vecchia_check(nbr.data(), rows, m, n, causal ? 1 : 0) == GOGP_OK;
+  }
+  void SetVecchia(const std::vector<double> &x, const std::vector<double> &y, const std::vector<int32_t> &nbr, int32_t m,
+                  const std::vector<double> &v = {}) {
+    if (x.empty() && y.empty() && nbr.empty() && v.empty()) {
+      vecchia_n_ = 0;
+      check(gogp_vecchia_set_data(h_, nullptr, nullptr, nullptr, 0, nullptr, 0));
+      return;
+    }
+    if (m < 0 || x.size() != y.size() * (size_t)NDim || nbr.size() != y.size() * (size_t)m || (!v.empty() && v.size() != y.size()))
+      throw Error(GOGP_EARG, "SetVecchia: sizes");
+    check(gogp_vecchia_set_data(h_, x.data(), y.data(), v.empty() ? nullptr : v.data(), (int64_t)y.size(),
+                                nbr.empty() ? nullptr : nbr.data(), m));
+    vecchia_n_ = y.size();
+    vecchia_m_ = m;
+  }
+  // The value at x = log theta; terms (unless nullptr) receives N x 3: mu_i, s_i, log p_i
+  double VecchiaObserve(const std::vector<double> &x, std::vector<double> *terms = nullptr) {
+    double v = 0.0;
+    if (terms) terms->assign(3 * vecchia_n_, 0.0);
+    check(gogp_vecchia_observe(h_, x.data(), (int64_t)x.size(), &v, terms ? terms->data() : nullptr));
+    return v;
+  }
+  // d value / d log theta at the parameters of the last VecchiaObserve: the exact derivative of its value
+  std::vector<double> VecchiaGradient() {
+    std::vector<double> g(ThetaSimil.size() + ThetaNoise.size(), 0.0);
+    check(gogp_vecchia_gradient(h_, g.data(), (int64_t)g.size()));
+    return g;
+  }
+  // mu and (unless nullptr) sigma of the test points, each conditioned on the rows its row of nbrz (x.size() x m) names
+  void VecchiaProduce(const std::vector<std::vector<double>> &x, const std::vector<int32_t> &nbrz, std::vector<double> &mu,
+                      std::vector<double> *sigma = nullptr) {
+    if (nbrz.size() != x.size() * (size_t)vecchia_m_) throw Error(GOGP_EARG, "VecchiaProduce: the table is x.size() x m");
+    std::vector<double> flat = pack(x);
+    mu.assign(x.size(), 0.0);
+    if (sigma) sigma->assign(x.size(), 0.0);
+    check(gogp_vecchia_produce(h_, flat.data(), (int64_t)x.size(), nbrz.empty() ? nullptr : nbrz.data(), mu.data(),
+                               sigma ? sigma->data() : nullptr));
+  }
   // SparseGradient and, from the same pass over the data, d bound / d U of the inducing points of SetSparse (dU:
   // row-major M x NDim)
   std::vector<double> SparseGradientInducing(std::vector<double> &dU) {
@@ -678,6 +721,8 @@ class GP {
   size_t sparse_m_ = 0;  // inducing points of SetSparse
   int sparse_t_ = 0;     // output columns of SetSparseOutputs
   size_t cg_n_ = 0;      // observations of SetCG
+  size_t vecchia_n_ = 0; // observations of SetVecchia
+  int32_t vecchia_m_ = 0; // ... and the columns of its table
 
   std::vector<double> pack(const std::vector<std::vector<double>> &x) const {
     std::vector<double> flat(x.size() * (size_t)NDim);

@@ -679,6 +679,46 @@ int gogp_cg_lml_gradient(gogp_handle *h, const double *Xi /* t rows of ldxi */, 
                          double *quad /* t, may be NULL: rho0_s e1^T log(T_s) e1 */, gogp_cg_lml_info *info,
                          gogp_cg_col *cols /* t, may be NULL */);
 
+/* Vecchia's approximation, also known as the nearest-neighbour GP (vecchia.hip; Vecchia 1988, Datta et al. 2016, Katzfuss &
+ * Guinness 2021):
+ *     log p(y) ~ sum_i log p(y_i | y_c(i)),    c(i) a set of at most m earlier rows,
+ * a product of N exact Gaussian conditionals on blocks of at most m + 1 <= 64 rows.  It is a valid joint density, not a
+ * bound; it equals the exact LML when c(i) holds every earlier row; its gradient is the exact derivative of its value.
+ * Cost: O(N m^3) flops and N (m + 1)^2 / 2 similarity evaluations, one wave per target.  Per target i with block b =
+ * [c(i) in the table's order, i]:  K_b = k(X_b, X_b) + sigma^2 I + diag(v_b), L = chol(K_b), z = L^-1 y_b, and the terms
+ *     mu_i = y_i - L_qq z_q,   s_i = L_qq,   log p_i = -1/2 log 2 pi - log L_qq - 1/2 z_q^2         (q = |c(i)|):
+ * the one-step-ahead forecast of y_i from its conditioning rows (noisy: s_i includes the noise) and its log density.
+ * The table: `rows` rows of m int32, 0 <= m <= GOGP_VECCHIA_MAX_M; a row holds distinct indices, then -1 padding (trailing
+ * only); causal: every index of row i is < i (row 0 is empty); otherwise every index is in [0, n).  The order within a
+ * row is kept: it fixes the bits, not the value beyond rounding.  gogp_vecchia_check (host only) returns GOGP_EARG for a
+ * table that breaks this; gogp_vecchia_set_data and gogp_vecchia_produce call it and name the first offending row in
+ * gogp_last_error.  The data are a set of their own, like the iterative calls': gogp_vecchia_set_data copies X (N x
+ * ndim), y (N), v (N per-observation noise variances, finite and >= 0; NULL: none) and the table to the device, where
+ * they stay (N (ndim + 2) doubles, 4 N m bytes, the 3 N terms, at most 2048 partial rows); N == 0 with NULLs clears them.
+ * Nothing else of the handle changes: a dense, sparse or iterative call made afterwards returns the bits it would have
+ * returned without these calls.
+ * gogp_vecchia_observe: the value at x = log theta into *lml and, unless NULL, the terms (N x 3: mu, s, log p).
+ * gogp_vecchia_gradient: d value / d log theta at the last observe's theta, the noise parameter's component included
+ * (d / dv and d / dX are out of scope); it runs the kernel again with the gradient's stages.
+ * gogp_vecchia_produce: mu_j and, unless NULL, sigma_j of the test points Z (mz x ndim), each conditioned on the rows of the
+ * data its row of nbrz (mz x m, same m) names: the target row is z_j with k(z_j, z_j) on its diagonal, no noise and no y --
+ * the latent sigma, unclamped, as gogp_produce defines it.  It uses the last observe's theta.
+ * Identical calls give identical bits (fixed-order sums, no atomics), and a target's terms have the same bits whatever
+ * else is in the call.  GOGP_EARG: NULL pointers, non-finite values, a bad table, len != P, a precision = 32 handle, a
+ * sharded handle, a handle with event discounts.  GOGP_ESTATE: observe before set_data; gradient or produce before
+ * observe.  GOGP_ENOTPD: a block has a pivot that is not positive and finite; gogp_notpd_index is the LOWEST such target
+ * (row of the data; test point for produce), that target's outputs are NaN, every other target's are written, *lml is NaN.
+ * DESIGN.md section 4, "Vecchia". */
+#define GOGP_VECCHIA_MAX_M 63
+int gogp_vecchia_check(const int32_t *nbr, int64_t rows, int32_t m, int64_t n, int causal);
+int gogp_vecchia_set_data(gogp_handle *h, const double *X, const double *y, const double *v /* may be NULL */, int64_t N,
+                          const int32_t *nbr /* N x m, row-major */, int32_t m);
+int gogp_vecchia_observe(gogp_handle *h, const double *x /* log theta */, int64_t len, double *lml,
+                         double *terms /* N x 3: mu, s, logp; may be NULL */);
+int gogp_vecchia_gradient(gogp_handle *h, double *grad, int64_t len);
+int gogp_vecchia_produce(gogp_handle *h, const double *Z, int64_t mz, const int32_t *nbrz /* mz x m */, double *mu,
+                         double *sigma /* may be NULL */);
+
 /* k independent Observe + Gradient evaluations at once: handle hs[i] (each created and given
  * its data separately; they may hold the same data) evaluates x[i*len .. (i+1)*len) from its own
  * host thread, so the dependent launch chains of the k evaluations overlap on the GPU.

@@ -700,6 +700,22 @@ int gogp_test_cg_probes(int device, const double *Ls, int64_t ls_len, int64_t ld
  * beta[0 .. m) (beta[m - 1] is not used); m == 0: 0.  No device. */
 int gogp_test_cg_quadrature(const double *a, const double *beta, int64_t m, double rho0, double *out);
 
+/* ---- the kernel of vecchia.hip (Vecchia's approximation; tests/test_vecchia_kernel.py), through its product launchers.
+ * The table nbr (`targets` rows of m int32; NULL with length 0 when m == 0) must pass gogp_vecchia_check -- causal for
+ * observe (targets == n), indices in [0, n) for produce -- and every length is checked before the device is touched.
+ * Observe (produce == 0, Z NULL with length 0): terms (in / out; n x 3: mu, s, log p; NULL with length 0: not asked for),
+ * value[0] = sum log p, info[0] = the lowest target with a bad pivot + 1 or 0, vpart (in / out) the workgroups' values;
+ * grad != 0 also fills partials (in / out; gogp_test_vecchia_blocks(n) rows of GOGP_TEST_NACC slot sums).  Produce: terms is
+ * targets x 2 (mu, sigma), partials and vpart NULL with length 0.  X: n x ndim, y: n, v: n or NULL with length 0.
+ * max_blocks > 0 caps the grid (a wave then walks several targets at a small size); gogp_test_vecchia_blocks: the rows
+ * of partials and vpart (-1: bad arguments; no device). */
+int gogp_test_vecchia_blocks(int64_t targets, int max_blocks);
+int gogp_test_vecchia(int device, const gogp_test_kparams *kparams, int produce, int grad, const double *X, int64_t x_len,
+                      const double *y, int64_t y_len, const double *v, int64_t v_len, int64_t n, const double *Z,
+                      int64_t z_len, int64_t targets, const int32_t *nbr, int64_t nbr_len, int m, double *terms,
+                      int64_t terms_len, double *partials, int64_t partials_len, double *vpart, int64_t vpart_len,
+                      double *value /* 1 */, int64_t *info /* 1 */, int max_blocks);
+
 #ifdef __cplusplus
 }
 #endif
