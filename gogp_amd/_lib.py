@@ -167,6 +167,12 @@ SYMBOLS = [
     ("gogp_vecchia_observe", ctypes.c_int, [_h, _dp, _i64, _dp, _dp]),
     ("gogp_vecchia_gradient", ctypes.c_int, [_h, _dp, _i64]),
     ("gogp_vecchia_produce", ctypes.c_int, [_h, _dp, _i64, ctypes.POINTER(ctypes.c_int32), _dp, _dp]),
+    ("gogp_vecchia_neighbours", ctypes.c_int,
+     [_h, _dp, _i64, _dp, _i64, _dp, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32)]),
+    ("gogp_vecchia_set_data_nearest", ctypes.c_int, [_h, _dp, _dp, _dp, _i64, _dp, ctypes.c_int32]),
+    ("gogp_vecchia_reneighbour", ctypes.c_int, [_h, _dp]),
+    ("gogp_vecchia_get_neighbours", ctypes.c_int, [_h, ctypes.POINTER(ctypes.c_int32)]),
+    ("gogp_vecchia_produce_nearest", ctypes.c_int, [_h, _dp, _i64, _dp, _dp, _dp, ctypes.POINTER(ctypes.c_int32)]),
     ("gogp_observe_gradient_batch", ctypes.c_int,
      [ctypes.POINTER(_h), ctypes.c_int, _dp, _i64, _dp, _dp, ctypes.POINTER(ctypes.c_int)]),
     ("gogp_observe_gradient_candidates", ctypes.c_int,
@@ -487,6 +493,13 @@ HOOK_SYMBOLS += [
     ("gogp_test_vecchia_blocks", _ci, [_i64, _ci]),
     ("gogp_test_vecchia", _ci, [_ci, _kpp, _ci, _ci, _dp, _i64, _dp, _i64, _dp, _i64, _i64, _dp, _i64, _i64, _i32p, _i64, _ci,
                                 _dp, _i64, _dp, _i64, _dp, _i64, _dp, ctypes.POINTER(_i64), _ci]),
+]
+
+#: the hooks of the search of vecchia_knn.hip (tests/test_vecchia_knn_kernel.py; gp.vecchia_knn_check, gp.vecchia_knn_plan)
+HOOK_SYMBOLS += [
+    ("gogp_test_vecchia_knn", _ci, [_ci, _dp, _i64, _i64, _ci, _dp, _i64, _i64, _dp, _ci, _ci, _ci, _i32p, _i64, _dp, _i64,
+                                    _dp, _i64]),
+    ("gogp_test_vecchia_knn_plan", _ci, [_i64, _i64, _ci, ctypes.POINTER(_i64)]),
 ]
 
 

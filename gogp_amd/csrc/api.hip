@@ -4814,6 +4814,7 @@ static void vecchia_free(gogp_handle *h) {
   vc.small.release();
   vc.terms.release();
   vc.prod.release();
+  vc.knn.release();
   vc = VecchiaState();
 }
 
@@ -5046,6 +5047,208 @@ extern "C" int gogp_vecchia_produce(gogp_handle *h, const double *Z, int64_t mz,
   long long info = 0;
   HIPCHK(h, hipMemcpyAsync(mu, dmu, (size_t)mz * sizeof(double), hipMemcpyDeviceToHost, s));
   if (sigma) HIPCHK(h, hipMemcpyAsync(sigma, dsig, (size_t)mz * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipMemcpyAsync(&info, dinfo, sizeof info, hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipStreamSynchronize(s));
+  HIPCHK(h, hipGetLastError());
+  if (info != 0) return vecchia_notpd(h, who, info, "test point");
+  return GOGP_OK;
+}
+
+// ---- Vecchia: neighbour tables built on the device (vecchia_knn.hip) ------------------------------------------------------
+// The exact search of gogp_amd/vecchia.py (nearest / nearest_to) on the handle's main stream; DESIGN.md section 4,
+// "Vecchia: neighbour tables on the device".  The resident forms keep the table, the scaled copy of X and the partial
+// lists on the device: nothing but the length scales crosses the bus.
+static int vecchia_knn_args(gogp_handle *h, const char *who, const double *lengths, int32_t m) {
+  if (m < 0 || m > GOGP_VECCHIA_MAX_M) return cg_refuse(h, who, GOGP_EARG, "m: need 0 <= m <= 63 conditioning rows");
+  if (lengths)
+    for (int d = 0; d < h->D; ++d)
+      if (!(lengths[d] > 0.0) || !std::isfinite(lengths[d]))
+        return cg_refuse(h, who, GOGP_EARG, "lengths: every length scale must be positive and finite");
+  return GOGP_OK;
+}
+
+// the scratch of one search: the lengths, the scaled copies of X and Z, the partial lists of a split search
+struct VecchiaKnnBufs {
+  double *len, *Xs, *Zs;
+  void *ws;
+};
+static size_t vecchia_knn_layout(char *base, int D, int64_t N, int64_t mz, size_t ws_bytes, VecchiaKnnBufs *b) {
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    char *q = base ? base + off : nullptr;
+    off += (bytes + 255) / 256 * 256;
+    return q;
+  };
+  b->len = reinterpret_cast<double *>(take(GOGP_MAX_NDIM * sizeof(double)));
+  b->Xs = reinterpret_cast<double *>(take((size_t)N * D * sizeof(double)));
+  b->Zs = reinterpret_cast<double *>(take((size_t)mz * D * sizeof(double)));
+  b->ws = take(ws_bytes);
+  return off;
+}
+static size_t vecchia_knn_bytes(int D, int64_t N, int64_t mz, int m) {
+  VecchiaKnnBufs b;
+  return vecchia_knn_layout(nullptr, D, N, mz, vknn_plan(mz > 0 ? mz : N, N, m).ws_bytes, &b);
+}
+
+// The launches of one search on device rows: dX (N x D) and dZ (mz x D; nullptr: the causal table of dX) into dnbr, with
+// vecchia_knn_bytes of scratch at base.  lengths: the host's, or nullptr.  The caller synchronises before it returns.
+static int vecchia_knn_launch(gogp_handle *h, char *base, const double *dX, int64_t N, const double *dZ, int64_t mz,
+                              const double *lengths, int m, int *dnbr) {
+  hipStream_t s = h->s;
+  const int D = h->D;
+  const int64_t targets = dZ ? mz : N;
+  VecchiaKnnBufs b;
+  vecchia_knn_layout(base, D, N, dZ ? mz : 0, vknn_plan(targets, N, m).ws_bytes, &b);
+  if (lengths) HIPCHK(h, hipMemcpyAsync(b.len, lengths, (size_t)D * sizeof(double), hipMemcpyHostToDevice, s));
+  launch_vknn_scale(s, dX, N, D, lengths ? b.len : nullptr, b.Xs);
+  if (dZ) launch_vknn_scale(s, dZ, mz, D, lengths ? b.len : nullptr, b.Zs);
+  launch_vknn(s, b.Xs, N, dZ ? b.Zs : nullptr, targets, D, m, 0, 0, b.ws, dnbr, nullptr);
+  return GOGP_OK;
+}
+
+extern "C" int gogp_vecchia_neighbours(gogp_handle *h, const double *X, int64_t N, const double *Z, int64_t mz,
+                                       const double *lengths, int32_t m, int32_t *nbr) {
+  const char *who = "vecchia_neighbours";
+  if (!h) return GOGP_EARG;
+  if (sparse_refusal(h)) return cg_refuse_handle(h, who);
+  if (N < 1 || !X) return cg_refuse(h, who, GOGP_EARG, "need X and N >= 1");
+  if (N > INT32_MAX) return cg_refuse(h, who, GOGP_EARG, "N: the table's indices are int32: N <= 2^31 - 1");
+  if (Z ? mz < 0 : mz != 0) return cg_refuse(h, who, GOGP_EARG, "mz: the rows of Z, 0 without Z");
+  if (const int rc = vecchia_knn_args(h, who, lengths, m)) return rc;
+  const int64_t targets = Z ? mz : N;
+  if (targets == 0 || m == 0) return GOGP_OK;
+  if (!nbr) return cg_refuse(h, who, GOGP_EARG, "nbr: NULL");
+  const int D = h->D;
+  HIPCHK(h, hipSetDevice(h->device));
+  hipStream_t s = h->s;
+  // buffers of the call's own: nothing of the handle changes
+  auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+  const size_t xb = up((size_t)N * D * sizeof(double)), zb = up((size_t)(Z ? mz : 0) * D * sizeof(double));
+  const size_t tb = up((size_t)targets * (size_t)m * sizeof(int32_t));
+  Workspace w;
+  struct Release {
+    Workspace &w;
+    ~Release() { w.release(); }
+  } release{w};
+  if (const int rc = w.reserve(h, xb + zb + tb + vecchia_knn_bytes(D, N, Z ? mz : 0, m))) return rc;
+  char *base = w.as<char>();
+  double *dX = reinterpret_cast<double *>(base), *dZ = Z ? reinterpret_cast<double *>(base + xb) : nullptr;
+  int *dnb = reinterpret_cast<int *>(base + xb + zb);
+  HIPCHK(h, hipMemcpyAsync(dX, X, (size_t)N * D * sizeof(double), hipMemcpyHostToDevice, s));
+  if (Z) HIPCHK(h, hipMemcpyAsync(dZ, Z, (size_t)mz * D * sizeof(double), hipMemcpyHostToDevice, s));
+  if (const int rc = vecchia_knn_launch(h, base + xb + zb + tb, dX, N, dZ, mz, lengths, m, dnb)) return rc;
+  HIPCHK(h, hipMemcpyAsync(nbr, dnb, (size_t)targets * (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipStreamSynchronize(s));
+  HIPCHK(h, hipGetLastError());
+  return GOGP_OK;
+}
+
+// the resident table from the resident X under `lengths` (nullptr: unscaled); the last observe is dropped
+static int vecchia_rebuild(gogp_handle *h, const double *lengths) {
+  VecchiaState &vc = h->vc;
+  if (const int rc = vc.knn.reserve(h, vecchia_knn_bytes(h->D, vc.N, 0, vc.m))) return rc;
+  vc.observed = false;
+  if (const int rc = vecchia_knn_launch(h, vc.knn.as<char>(), vc.X, vc.N, nullptr, 0, lengths, vc.m, vc.nbr)) return rc;
+  HIPCHK(h, hipStreamSynchronize(h->s));
+  HIPCHK(h, hipGetLastError());
+  vc.built_here = true;
+  vc.scaled = lengths != nullptr;
+  for (int d = 0; d < h->D; ++d) vc.lengths[d] = lengths ? lengths[d] : 1.0;
+  return GOGP_OK;
+}
+
+extern "C" int gogp_vecchia_set_data_nearest(gogp_handle *h, const double *X, const double *y, const double *v, int64_t N,
+                                             const double *lengths, int32_t m) {
+  const char *who = "vecchia_set_data_nearest";
+  if (!h) return GOGP_EARG;
+  if (sparse_refusal(h)) return cg_refuse_handle(h, who);
+  if (N < 1 || !X || !y) return cg_refuse(h, who, GOGP_EARG, "need X, y and N >= 1");
+  if (N > INT32_MAX) return cg_refuse(h, who, GOGP_EARG, "N: the table's indices are int32: N <= 2^31 - 1");
+  if (const int rc = vecchia_knn_args(h, who, lengths, m)) return rc;
+  // the upload and its checks are gogp_vecchia_set_data's, with an empty table; the table proper is then built in place
+  if (const int rc = gogp_vecchia_set_data(h, X, y, v, N, nullptr, 0)) return rc;
+  VecchiaState &vc = h->vc;
+  if (m > 0) {
+    (void)hipFree(vc.nbr);
+    vc.nbr = nullptr;
+    const hipError_t e = hipMalloc(&vc.nbr, (size_t)N * (size_t)m * sizeof(int32_t));
+    if (e != hipSuccess) {
+      vecchia_free(h);
+      HIPCHK(h, e);
+    }
+  }
+  vc.m = m;
+  if (const int rc = vecchia_rebuild(h, lengths)) {
+    const auto keep = h->err;
+    vecchia_free(h);
+    h->err = keep;
+    return rc;
+  }
+  return GOGP_OK;
+}
+
+extern "C" int gogp_vecchia_reneighbour(gogp_handle *h, const double *lengths) {
+  const char *who = "vecchia_reneighbour";
+  if (!h) return GOGP_EARG;
+  if (sparse_refusal(h)) return cg_refuse_handle(h, who);
+  VecchiaState &vc = h->vc;
+  if (!vc.have) return cg_refuse(h, who, GOGP_ESTATE, "no data (gogp_vecchia_set_data, gogp_vecchia_set_data_nearest)");
+  if (const int rc = vecchia_knn_args(h, who, lengths, vc.m)) return rc;
+  HIPCHK(h, hipSetDevice(h->device));
+  return vecchia_rebuild(h, lengths);
+}
+
+extern "C" int gogp_vecchia_get_neighbours(gogp_handle *h, int32_t *nbr) {
+  const char *who = "vecchia_get_neighbours";
+  if (!h) return GOGP_EARG;
+  if (sparse_refusal(h)) return cg_refuse_handle(h, who);
+  VecchiaState &vc = h->vc;
+  if (!vc.have) return cg_refuse(h, who, GOGP_ESTATE, "no data (gogp_vecchia_set_data, gogp_vecchia_set_data_nearest)");
+  if (vc.m == 0) return GOGP_OK;
+  if (!nbr) return cg_refuse(h, who, GOGP_EARG, "nbr: NULL");
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipMemcpyAsync(nbr, vc.nbr, (size_t)vc.N * (size_t)vc.m * sizeof(int32_t), hipMemcpyDeviceToHost, h->s));
+  HIPCHK(h, hipStreamSynchronize(h->s));
+  return GOGP_OK;
+}
+
+extern "C" int gogp_vecchia_produce_nearest(gogp_handle *h, const double *Z, int64_t mz, const double *lengths, double *mu,
+                                            double *sigma, int32_t *nbrz) {
+  const char *who = "vecchia_produce_nearest";
+  if (!h) return GOGP_EARG;
+  if (sparse_refusal(h)) return cg_refuse_handle(h, who);
+  if (mz < 0 || (mz > 0 && (!Z || !mu))) return cg_refuse(h, who, GOGP_EARG, "need Z and mu for mz > 0, mz >= 0");
+  VecchiaState &vc = h->vc;
+  if (!vc.have || !vc.observed) return cg_refuse(h, who, GOGP_ESTATE, "nothing observed (gogp_vecchia_observe)");
+  if (!lengths && !vc.built_here)
+    return cg_refuse(h, who, GOGP_ESTATE, "lengths: the resident table is the caller's, so it has none to take");
+  if (const int rc = vecchia_knn_args(h, who, lengths, vc.m)) return rc;
+  const double *len = lengths ? lengths : vc.scaled ? vc.lengths : nullptr;
+  const int D = h->D, m = vc.m;
+  for (int64_t i = 0; i < mz * D; ++i)
+    if (!std::isfinite(Z[i])) return cg_refuse(h, who, GOGP_EARG, "non-finite test point");
+  if (mz == 0) return GOGP_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  hipStream_t s = h->s;
+  // gogp_vecchia_produce's buffers, with the table found on the device in the place of the caller's
+  const int blocks = vecchia_blocks(mz);
+  auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+  const size_t zb = up((size_t)mz * D * sizeof(double)), vb = up((size_t)mz * sizeof(double));
+  const size_t tb = up(std::max<size_t>((size_t)mz * (size_t)m * sizeof(int32_t), 4)), fb = up((size_t)blocks * sizeof(long long));
+  if (const int rc = vc.prod.reserve(h, zb + 2 * vb + tb + fb + 256)) return rc;
+  if (const int rc = vc.knn.reserve(h, vecchia_knn_bytes(D, vc.N, mz, m))) return rc;
+  char *base = vc.prod.as<char>();
+  double *dZ = reinterpret_cast<double *>(base), *dmu = reinterpret_cast<double *>(base + zb);
+  double *dsig = reinterpret_cast<double *>(base + zb + vb);
+  int *dnb = reinterpret_cast<int *>(base + zb + 2 * vb);
+  long long *dfp = reinterpret_cast<long long *>(base + zb + 2 * vb + tb), *dinfo = dfp + blocks;
+  HIPCHK(h, hipMemcpyAsync(dZ, Z, (size_t)mz * D * sizeof(double), hipMemcpyHostToDevice, s));
+  if (const int rc = vecchia_knn_launch(h, vc.knn.as<char>(), vc.X, vc.N, dZ, mz, len, m, dnb)) return rc;
+  launch_vecchia_produce(s, vc.P, D, vc.X, vc.y, vc.v, dZ, mz, dnb, m, dmu, sigma ? dsig : nullptr, dfp, dinfo);
+  long long info = 0;
+  HIPCHK(h, hipMemcpyAsync(mu, dmu, (size_t)mz * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (sigma) HIPCHK(h, hipMemcpyAsync(sigma, dsig, (size_t)mz * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (nbrz && m > 0) HIPCHK(h, hipMemcpyAsync(nbrz, dnb, (size_t)mz * (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost, s));
   HIPCHK(h, hipMemcpyAsync(&info, dinfo, sizeof info, hipMemcpyDeviceToHost, s));
   HIPCHK(h, hipStreamSynchronize(s));
   HIPCHK(h, hipGetLastError());

@@ -682,6 +682,25 @@ void launch_vecchia_observe(hipStream_t s, const DevParams *p, int ndim, int ard
 void launch_vecchia_produce(hipStream_t s, const DevParams *p, int ndim, const double *X, const double *y, const double *v,
                             const double *Z, int64_t mz, const int *nbrz, int m, double *mu, double *sigma,
                             long long *fpart, long long *info, int max_blocks = 0);
+// vecchia_knn.hip (gogp_vecchia_neighbours, ..._set_data_nearest, ..._reneighbour, ..._produce_nearest): the exact
+// nearest-neighbour tables of gogp_amd/vecchia.py, integer for integer (the head of vecchia_knn.hip states the definition
+// and the kernel).  launch_vknn_scale: xs = x / lengths per dimension (lengths: ndim doubles on the device, or nullptr: a
+// copy).  launch_vknn: Xs the n scaled rows; Zs == nullptr: the causal table of Xs (targets == n), else row z of the table
+// holds the m nearest rows of Xs to row z of Zs; nbr: targets x m, d2out (nullptr: not written): the squared distance of
+// every entry, 0.0 under the padding; ws: vknn_plan(targets, n, m, slabs).ws_bytes bytes of scratch.  slabs > 0 forces the
+// candidate split, tile_cap > 0 caps the grid (tests); the table does not depend on either.  n < 2^31, 0 <= m <= 63.
+constexpr int VKNN_TILE = 64;  // targets of a work unit: one lane each
+// the workspace at most: 12 bytes per (target, slab, entry), and tiles * slabs < 768 wherever a search is split
+constexpr size_t VKNN_WS_MAX = (size_t)768 * VKNN_TILE * 12 * 63;
+struct VknnPlan {
+  int tile, slabs;
+  int64_t slab_len;  // slab s holds the candidates [s * slab_len, min(n, (s + 1) * slab_len))
+  size_t ws_bytes;
+};
+VknnPlan vknn_plan(int64_t targets, int64_t n, int m, int slabs = 0);
+void launch_vknn_scale(hipStream_t s, const double *x, int64_t rows, int ndim, const double *lengths, double *xs);
+void launch_vknn(hipStream_t s, const double *Xs, int64_t n, const double *Zs, int64_t targets, int ndim, int m, int slabs,
+                 int tile_cap, void *ws, int *nbr, double *d2out);
 // laplace.hip (gogp_laplace_*): the passes around the factorisation of B = I + diag(sw) K diag(sw).  Vectors hold npad
 // doubles (npad a multiple of 256) and leave every launcher zero from row n on.
 // launch_lap_site: g, W, sw = sqrt(W), b = W f + g, rho of the rows i < n; part: 5 * npad / 256 doubles of block results;

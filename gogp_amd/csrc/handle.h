@@ -75,6 +75,11 @@ struct VecchiaState {
   Workspace small;      // value, info word, NACC slot sums, the workgroups' values, failure words and partial rows
   Workspace terms;      // N x 3
   Workspace prod;       // gogp_vecchia_produce: Z, the table, mu, sigma, the failure words
+  // the table's origin (gogp_vecchia_set_data_nearest, gogp_vecchia_reneighbour): built on the device from the resident X
+  // under these length scales (scaled false: the unscaled distance); false for a caller's table
+  bool built_here = false, scaled = false;
+  double lengths[GOGP_MAX_NDIM] = {};
+  Workspace knn;        // a search's scratch: the lengths, the scaled copies of X and Z, the partial lists (vknn_plan)
 };
 
 // What an evaluation leaves in the handle; a candidates call saves it and puts it back

@@ -2649,3 +2649,36 @@ extern "C" int gogp_test_vecchia(int device, const gogp_test_kparams *kparams, i
                              d[8], d.as<long long>(11), d[12], d[9], d.as<long long>(10), max_blocks);
   });
 }
+
+// ---- vecchia_knn.hip ------------------------------------------------------------------------------------------------------
+extern "C" int gogp_test_vecchia_knn_plan(int64_t targets, int64_t n, int m, int64_t out[3]) {
+  if (!out || targets < 1 || n < 1 || m < 0 || m > GOGP_VECCHIA_MAX_M) return GOGP_EARG;
+  const VknnPlan p = vknn_plan(targets, n, m);
+  out[0] = p.tile, out[1] = p.slabs, out[2] = (int64_t)p.ws_bytes;
+  return GOGP_OK;
+}
+
+extern "C" int gogp_test_vecchia_knn(int device, const double *X, int64_t x_len, int64_t n, int ndim, const double *Z,
+                                     int64_t z_len, int64_t targets, const double *lengths, int m, int slabs, int tile_cap,
+                                     int32_t *nbr, int64_t nbr_len, double *d2, int64_t d2_len, double *xs, int64_t xs_len) {
+  if (!X || !xs || ndim < 1 || ndim > GOGP_MAX_NDIM || m < 0 || m > GOGP_VECCHIA_MAX_M) return GOGP_EARG;
+  if (slabs < 0 || slabs > 256 || tile_cap < 0) return GOGP_EARG;
+  if (n < 1 || n > (1 << 20) || targets < 1 || targets > (1 << 20)) return GOGP_EARG;
+  if (Z ? z_len < targets * ndim : (z_len != 0 || targets != n)) return GOGP_EARG;
+  if (x_len < n * ndim || xs_len < n * ndim) return GOGP_EARG;
+  if (m > 0 && (!nbr || !d2 || nbr_len < targets * m || d2_len < targets * m)) return GOGP_EARG;
+  if (lengths)
+    for (int d = 0; d < ndim; ++d)
+      if (!(lengths[d] > 0.0) || !std::isfinite(lengths[d])) return GOGP_EARG;
+  const VknnPlan p = vknn_plan(targets, n, m, slabs);
+  if (p.ws_bytes > ((size_t)1 << 28)) return GOGP_EARG;
+  const std::vector<Arr> arrs = {rd(X, x_len), opt(rd(Z, z_len)), opt(rd(lengths, lengths ? ndim : 0)),
+                                 opt(io(nbr, nbr_len, 4)), opt(io(d2, d2_len)), io(xs, xs_len), scratch(p.ws_bytes),
+                                 scratch(Z ? (size_t)targets * ndim * sizeof(double) : 0)};
+  if (!have(arrs)) return GOGP_EARG;
+  return run(device, arrs, [&](const Dev &d) {
+    launch_vknn_scale(0, d[0], n, ndim, d[2], d[5]);
+    if (Z) launch_vknn_scale(0, d[1], targets, ndim, d[2], d[7]);
+    launch_vknn(0, d[5], n, Z ? d[7] : nullptr, targets, ndim, m, slabs, tile_cap, d.as<void>(6), d.as<int>(3), d[4]);
+  });
+}

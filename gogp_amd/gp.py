@@ -977,6 +977,100 @@ class GP:
                                                     _dp(mu) if mz else None, _dp(sg) if mz and sigma else None))
         return mu, sg
 
+    # ---- ... with the table built on the device (vecchia_knn.hip): the search of vecchia.nearest / nearest_to ----
+    def _vecchia_lengths(self, lengths, what: str):
+        """``lengths`` as the host helpers take it -- a scalar or one value per dimension -- as NDim doubles; None stays."""
+        if lengths is None:
+            return None
+        la = np.asarray(lengths, dtype=np.float64)
+        if la.ndim > 1 or (la.ndim == 1 and la.size != self.NDim):
+            raise ValueError("%s: lengths is a scalar or one value per dimension (%d)" % (what, self.NDim))
+        la = np.ascontiguousarray(np.broadcast_to(la, (self.NDim,)))
+        if not np.all(np.isfinite(la) & (la > 0.0)):
+            raise ValueError("%s: lengths must be positive and finite" % what)
+        return la
+
+    @staticmethod
+    def _vecchia_m(m, what: str) -> int:
+        m = int(m)
+        if not 0 <= m <= 63:
+            raise ValueError("%s: m: 0 .. 63 conditioning rows" % what)
+        return m
+
+    def _vecchia_rows(self, a, what: str) -> np.ndarray:
+        a = _arr(a)
+        if a.ndim == 2 and a.shape[1] != self.NDim:
+            raise ValueError("%s: rows of %d values, not %d" % (what, self.NDim, a.shape[1]))
+        if a.size % self.NDim:
+            raise ValueError("%s: rows of %d values" % (what, self.NDim))
+        return np.ascontiguousarray(a.reshape(-1, self.NDim))
+
+    def VecchiaNeighbours(self, x, m: int, lengths=None, z=None) -> np.ndarray:
+        """The table of vecchia.nearest(x, m, lengths) -- or, with test points ``z``, of vecchia.nearest_to(x, z, m,
+        lengths) -- found on the device, integer for integer (gogp_vecchia_neighbours).  One-shot: nothing of the process
+        changes."""
+        what = "VecchiaNeighbours"
+        m = self._vecchia_m(m, what)
+        xs = self._vecchia_rows(x, what + ": x")
+        la = self._vecchia_lengths(lengths, what)
+        zz = None if z is None else self._vecchia_rows(z, what + ": z")
+        rows = len(xs) if zz is None else len(zz)
+        t = np.full((rows, m), -1, dtype=np.int32)
+        if len(xs) == 0 or rows == 0 or m == 0:
+            return t
+        self._check(_lib.lib().gogp_vecchia_neighbours(self._h, _dp(xs), len(xs), None if zz is None else _dp(zz),
+                                                       0 if zz is None else len(zz), _dp(la), m, _i32p(t)))
+        return t
+
+    def SetVecchiaNearest(self, x, y, m: int, lengths=None, v=None) -> None:
+        """SetVecchia(x, y, vecchia.nearest(x, m, lengths), v) with the table built on the device from the uploaded x, where
+        it stays (gogp_vecchia_set_data_nearest).  VecchiaNeighbourTable() returns it, VecchiaReneighbour rebuilds it."""
+        what = "SetVecchiaNearest"
+        m = self._vecchia_m(m, what)
+        xs = self._vecchia_rows(x, what + ": x")
+        ys = np.ascontiguousarray(_arr(y).reshape(-1))
+        if len(xs) != len(ys):
+            raise ValueError("SetVecchiaNearest: len(x) != len(y)")
+        la = self._vecchia_lengths(lengths, what)
+        va = None
+        if v is not None:
+            va = np.ascontiguousarray(_arr(v).reshape(-1))
+            if va.size != len(ys):
+                raise ValueError("SetVecchiaNearest: one variance per observation")
+        self._vc_terms = None
+        self._check(_lib.lib().gogp_vecchia_set_data_nearest(self._h, _dp(xs) if len(xs) else None,
+                                                             _dp(ys) if len(ys) else None, _dp(va), len(ys), _dp(la), m))
+        self._vc_n, self._vc_m = len(ys), m
+
+    def VecchiaReneighbour(self, lengths) -> None:
+        """Rebuild the resident table from the resident x under new length scales, same m (gogp_vecchia_reneighbour); also
+        on data that SetVecchia brought with a table, which it replaces.  The last VecchiaObserve is dropped."""
+        la = self._vecchia_lengths(lengths, "VecchiaReneighbour")
+        self._vc_terms = None
+        self._check(_lib.lib().gogp_vecchia_reneighbour(self._h, _dp(la)))
+
+    def VecchiaNeighbourTable(self) -> np.ndarray:
+        """The resident table, N x m int32 (gogp_vecchia_get_neighbours)."""
+        t = np.full((getattr(self, "_vc_n", 0), getattr(self, "_vc_m", 0)), -1, dtype=np.int32)
+        self._check(_lib.lib().gogp_vecchia_get_neighbours(self._h, _i32p(t) if t.size else None))
+        return t
+
+    def VecchiaProduceNearest(self, z, lengths=None, sigma: bool = True, table: bool = False):
+        """VecchiaProduce(z, vecchia.nearest_to(x, z, m, lengths)) with the table found on the device
+        (gogp_vecchia_produce_nearest); ``lengths=None``: those the resident table was built with.  Returns (mu, sigma), or
+        (mu, sigma, table) with ``table=True``."""
+        what = "VecchiaProduceNearest"
+        zz = self._vecchia_rows(z, what + ": z")
+        la = self._vecchia_lengths(lengths, what)
+        mz, m = len(zz), getattr(self, "_vc_m", 0)
+        mu = np.zeros(mz)
+        sg = np.zeros(mz) if sigma else None
+        t = np.full((mz, m), -1, dtype=np.int32) if table else None
+        self._check(_lib.lib().gogp_vecchia_produce_nearest(
+            self._h, _dp(zz) if mz else None, mz, _dp(la), _dp(mu) if mz else None, _dp(sg) if mz and sigma else None,
+            _i32p(t) if table and t.size else None))
+        return (mu, sg, t) if table else (mu, sg)
+
     def SparseObserve(self, x) -> float:
         """The collapsed variational bound of Titsias (2009) at x = log theta (gogp_sparse_observe): a lower bound of
         the LML of the sparse data that costs O(N M^2)."""
@@ -1610,12 +1704,22 @@ class VecchiaModel:
     """Model with Vecchia's approximation of GP.SetVecchia in the place of the LML: Observe(x) returns
     GP.VecchiaObserve(x) (+ the log prior), Gradient() returns GP.VecchiaGradient() (+ the prior's), for optimize.lbfgs and
     optimize.Adam.  The gradient is the exact derivative of the value, so a line search is consistent.  The neighbour
-    table is fixed by GP.SetVecchia: a table built with length scales (vecchia.nearest) is not rebuilt as they move."""
+    table is fixed by GP.SetVecchia: a table built with length scales (vecchia.nearest) is not rebuilt as they move.
 
-    def __init__(self, gp: GP, Priors=None):
+    ``lengths_of``, a callable from x = log theta to the length scales (a scalar or one per dimension), offers
+    ``reneighbour(x)``: the resident table rebuilt on the device under lengths_of(x) (GP.VecchiaReneighbour), between two
+    runs of an optimiser -- never inside one, where it would change the objective under the line search."""
+
+    def __init__(self, gp: GP, Priors=None, lengths_of=None):
         self.gp = gp
         self.Priors = Priors
+        self.lengths_of = lengths_of
         self._x = None
+
+    def reneighbour(self, x) -> None:
+        if self.lengths_of is None:
+            raise ValueError("reneighbour: the model was built without lengths_of")
+        self.gp.VecchiaReneighbour(self.lengths_of(_arr(x).reshape(-1)))
 
     def Observe(self, x) -> float:
         self._x = _arr(x).reshape(-1).copy()
@@ -2607,3 +2711,36 @@ def vecchia_check(kp, X: np.ndarray, y: np.ndarray, v, n: int, nbr, m: int, term
     if rc != _lib.GOGP_OK:
         raise GogpError(rc, "test_vecchia")
     return terms, partials, vpart, float(value[0]), int(info[0])
+
+
+def vecchia_knn_plan(targets: int, n: int, m: int):
+    """(targets of a tile, slabs, bytes of workspace) of a search of ``targets`` targets over n candidates (test hook
+    gogp_test_vecchia_knn_plan): tile t holds the targets [t tile, (t + 1) tile), slab s the candidates [s L, (s + 1) L)
+    with L = ceil(n / slabs).  No device."""
+    out = np.zeros(3, dtype=np.int64)
+    rc = _lib.hooks().gogp_test_vecchia_knn_plan(targets, n, m, _ip(out))
+    if rc != _lib.GOGP_OK:
+        raise GogpError(rc, "test_vecchia_knn_plan")
+    return int(out[0]), int(out[1]), int(out[2])
+
+
+def vecchia_knn_check(X: np.ndarray, n: int, ndim: int, m: int, nbr, d2, xs: np.ndarray, Z=None, targets=None, lengths=None,
+                      slabs: int = 0, tile_cap: int = 0, device: int = -1):
+    """The search of vecchia_knn.hip on caller-supplied rows (test hook gogp_test_vecchia_knn): the causal table of the n
+    rows of X, or (Z given) of ``targets`` rows of Z against them.  nbr (int32) and d2: targets x m at least, xs: n x ndim
+    at least; what lies behind comes back as it went in.  Returns copies: (nbr, d2, xs)."""
+    X = _vec(X, "X")
+    targets = n if targets is None else targets
+    zp, zl = _opt(Z, "Z")
+    lp = None if lengths is None else _dp(_vec(lengths, "lengths"))
+    if lengths is not None and lengths.size != ndim:
+        raise GogpError(_lib.GOGP_EARG, "test_vecchia_knn: lengths")
+    nb = None if nbr is None else _i32(nbr, "nbr").copy()
+    dd = None if d2 is None else _vec(d2, "d2").copy()
+    xs = _vec(xs, "xs").copy()
+    rc = _lib.hooks().gogp_test_vecchia_knn(device, _dp(X), X.size, n, ndim, zp, zl, targets, lp, m, slabs, tile_cap,
+                                            None if nb is None else _i32p(nb), 0 if nb is None else nb.size, _dp(dd),
+                                            0 if dd is None else dd.size, _dp(xs), xs.size)
+    if rc != _lib.GOGP_OK:
+        raise GogpError(rc, "test_vecchia_knn")
+    return nb, dd, xs

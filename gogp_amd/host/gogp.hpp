@@ -500,6 +500,55 @@ class GP {
     check(gogp_vecchia_produce(h_, flat.data(), (int64_t)x.size(), nbrz.empty() ? nullptr : nbrz.data(), mu.data(),
                                sigma ? sigma->data() : nullptr));
   }
+  // ... with the table built on the device (gogp_vecchia_neighbours etc.): the m nearest earlier rows under the distance
+  // of x / lengths (lengths: empty = unscaled, else NDim values > 0), ties to the lower index, nearest first.
+  // VecchiaNeighbours: one-shot; z empty: the causal table of x (rows x m), else z.size() rows over all of x.
+  std::vector<int32_t> VecchiaNeighbours(const std::vector<double> &x, int32_t m, const std::vector<double> &lengths = {},
+                                         const std::vector<std::vector<double>> &z = {}) {
+    if (m < 0 || x.size() % (size_t)NDim || (!lengths.empty() && lengths.size() != (size_t)NDim))
+      throw Error(GOGP_EARG, "VecchiaNeighbours: sizes");
+    const size_t n = x.size() / (size_t)NDim, rows = z.empty() ? n : z.size();
+    std::vector<int32_t> t(rows * (size_t)m, -1);
+    if (n == 0 || t.empty()) return t;
+    std::vector<double> flat = pack(z);
+    check(gogp_vecchia_neighbours(h_, x.data(), (int64_t)n, z.empty() ? nullptr : flat.data(), (int64_t)z.size(),
+                                  lengths.empty() ? nullptr : lengths.data(), m, t.data()));
+    return t;
+  }
+  void SetVecchiaNearest(const std::vector<double> &x, const std::vector<double> &y, int32_t m,
+                         const std::vector<double> &lengths = {}, const std::vector<double> &v = {}) {
+    if (m < 0 || x.size() != y.size() * (size_t)NDim || (!lengths.empty() && lengths.size() != (size_t)NDim) ||
+        (!v.empty() && v.size() != y.size()))
+      throw Error(GOGP_EARG, "SetVecchiaNearest: sizes");
+    check(gogp_vecchia_set_data_nearest(h_, x.data(), y.data(), v.empty() ? nullptr : v.data(), (int64_t)y.size(),
+                                        lengths.empty() ? nullptr : lengths.data(), m));
+    vecchia_n_ = y.size();
+    vecchia_m_ = m;
+  }
+  // the resident table rebuilt under new lengths (same m); the last VecchiaObserve is dropped
+  void VecchiaReneighbour(const std::vector<double> &lengths) {
+    if (!lengths.empty() && lengths.size() != (size_t)NDim) throw Error(GOGP_EARG, "VecchiaReneighbour: sizes");
+    check(gogp_vecchia_reneighbour(h_, lengths.empty() ? nullptr : lengths.data()));
+  }
+  std::vector<int32_t> VecchiaNeighbourTable() {
+    std::vector<int32_t> t(vecchia_n_ * (size_t)vecchia_m_, -1);
+    check(gogp_vecchia_get_neighbours(h_, t.empty() ? nullptr : t.data()));
+    return t;
+  }
+  // VecchiaProduce on each test point's m nearest resident rows, found on the device; lengths empty: the resident
+  // table's; nbrz (unless nullptr) receives the table
+  void VecchiaProduceNearest(const std::vector<std::vector<double>> &x, std::vector<double> &mu,
+                             std::vector<double> *sigma = nullptr, const std::vector<double> &lengths = {},
+                             std::vector<int32_t> *nbrz = nullptr) {
+    if (!lengths.empty() && lengths.size() != (size_t)NDim) throw Error(GOGP_EARG, "VecchiaProduceNearest: sizes");
+    std::vector<double> flat = pack(x);
+    mu.assign(x.size(), 0.0);
+    if (sigma) sigma->assign(x.size(), 0.0);
+    if (nbrz) nbrz->assign(x.size() * (size_t)vecchia_m_, -1);
+    check(gogp_vecchia_produce_nearest(h_, flat.data(), (int64_t)x.size(), lengths.empty() ? nullptr : lengths.data(),
+                                       mu.data(), sigma ? sigma->data() : nullptr,
+                                       nbrz && !nbrz->empty() ? nbrz->data() : nullptr));
+  }
   // SparseGradient and, from the same pass over the data, d bound / d U of the inducing points of SetSparse (dU:
   // row-major M x NDim)
   std::vector<double> SparseGradientInducing(std::vector<double> &dU) {

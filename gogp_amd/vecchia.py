@@ -57,7 +57,9 @@ def _smallest(d2: np.ndarray, k: int) -> np.ndarray:
 def nearest(x, m: int, lengths=None, chunk: int = 1024) -> np.ndarray:
     """For every row its m nearest EARLIER rows under the Euclidean distance of x / lengths (``lengths``: one scale per
     dimension or one for all; None: unscaled), nearest first, ties to the lower index.  Brute force in chunks of rows:
-    O(N^2 D) time and O(chunk N) memory, meant for N up to about 1e5 -- beyond that bring a table from a spatial index."""
+    O(N^2 D) time and O(chunk N) memory, meant for N up to about 1e5 -- beyond that bring a table from a spatial index.
+    GP.VecchiaNeighbours and GP.SetVecchiaNearest run the same search on the device and return this table integer for
+    integer."""
     m = _m_ok(m)
     xs = _scaled(x, lengths)
     n = len(xs)

@@ -719,6 +719,39 @@ int gogp_vecchia_gradient(gogp_handle *h, double *grad, int64_t len);
 int gogp_vecchia_produce(gogp_handle *h, const double *Z, int64_t mz, const int32_t *nbrz /* mz x m */, double *mu,
                          double *sigma /* may be NULL */);
 
+/* Neighbour tables built on the device (vecchia_knn.hip): the exact brute-force search of gogp_amd/vecchia.py, nearest
+ * and nearest_to, and the same table integer for integer.  xs = x / lengths per dimension (lengths: ndim values, > 0 and
+ * finite; NULL: unscaled); d2(a, b) = sum_d (a_d - b_d)^2 from the differences, in index order of d, every product
+ * rounded before it is added; row i of the causal table holds the m smallest keys (d2(xs_i, xs_j), j) over j < i, a row
+ * of the query form the m smallest over all j < N; keys are ordered by value, then by index; nearest first, then -1; a
+ * distance that is not finite is never taken.  0 <= m <= GOGP_VECCHIA_MAX_M; m == 0 writes nothing.  The key is a strict
+ * total order: identical calls give identical tables, whatever the launch.  Cost: N^2 / 2 (causal) or mz N pairs of
+ * 3 ndim fp64 operations; the search of a few targets is cut over the candidates; the scratch beside the scaled copies
+ * stays under 36 MiB.
+ * gogp_vecchia_neighbours: one-shot, nothing of the handle changes; Z == NULL (mz == 0): the causal table of X (N x m),
+ * else mz rows over all of X.
+ * gogp_vecchia_set_data_nearest: gogp_vecchia_set_data, with the table built on the device from the uploaded X; it stays
+ * there beside the scaled copy of X (N ndim doubles more).
+ * gogp_vecchia_reneighbour: rebuilds the resident table from the resident X under new lengths (same m; also a table that
+ * gogp_vecchia_set_data brought, which it replaces); the last observe is dropped, so gogp_vecchia_gradient and the produce
+ * calls want a new one.
+ * gogp_vecchia_get_neighbours: the resident table (N x m).
+ * gogp_vecchia_produce_nearest: finds each test point's m nearest resident rows on the device, then gogp_vecchia_produce's
+ * launch on that table; lengths NULL: those the resident table was built with (GOGP_ESTATE if a caller brought it); nbrz,
+ * unless NULL, receives the table (mz x m).
+ * GOGP_EARG (gogp_last_error names the argument): m outside 0 .. 63, a length that is not positive and finite, N >= 2^31,
+ * NULL pointers, and the handles the other Vecchia calls refuse.  GOGP_ESTATE: reneighbour, get_neighbours and
+ * produce_nearest without resident data; produce_nearest before an observe.
+ * DESIGN.md section 4, "Vecchia: neighbour tables on the device". */
+int gogp_vecchia_neighbours(gogp_handle *h, const double *X, int64_t N, const double *Z /* may be NULL */, int64_t mz,
+                            const double *lengths /* ndim; may be NULL */, int32_t m, int32_t *nbr);
+int gogp_vecchia_set_data_nearest(gogp_handle *h, const double *X, const double *y, const double *v /* may be NULL */,
+                                  int64_t N, const double *lengths /* may be NULL */, int32_t m);
+int gogp_vecchia_reneighbour(gogp_handle *h, const double *lengths /* may be NULL */);
+int gogp_vecchia_get_neighbours(gogp_handle *h, int32_t *nbr /* N x m */);
+int gogp_vecchia_produce_nearest(gogp_handle *h, const double *Z, int64_t mz, const double *lengths /* may be NULL */,
+                                 double *mu, double *sigma /* may be NULL */, int32_t *nbrz /* mz x m, may be NULL */);
+
 /* k independent Observe + Gradient evaluations at once: handle hs[i] (each created and given
  * its data separately; they may hold the same data) evaluates x[i*len .. (i+1)*len) from its own
  * host thread, so the dependent launch chains of the k evaluations overlap on the GPU.

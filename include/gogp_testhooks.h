@@ -716,6 +716,21 @@ int gogp_test_vecchia(int device, const gogp_test_kparams *kparams, int produce,
                       int64_t terms_len, double *partials, int64_t partials_len, double *vpart, int64_t vpart_len,
                       double *value /* 1 */, int64_t *info /* 1 */, int max_blocks);
 
+/* ---- the search of vecchia_knn.hip (tests/test_vecchia_knn_kernel.py), through its product launchers on caller-supplied
+ * rows.  X: n x ndim (x_len >= n ndim; what lies behind row n - 1 travels to the device too).  Z NULL with length 0: the
+ * causal table of X (targets == n); else `targets` rows of Z against all of X.  lengths: ndim values > 0 or NULL.
+ * 0 <= m <= 63, n and targets in 1 .. 2^20, 0 <= slabs <= 256 (> 0 forces the candidate split), tile_cap >= 0 (> 0 caps
+ * the grid).  In / out: nbr (nbr_len >= targets m) the table, d2 (same length) the squared distance of every entry taken
+ * (0.0 under the padding), xs (xs_len >= n ndim) the scaled copy of X; with m == 0 nbr and d2 may be NULL with length 0.
+ * Every length is checked before the device is touched.
+ * gogp_test_vecchia_knn_plan: out = {targets of a tile, slabs, bytes of workspace} of a search of `targets` targets over n
+ * candidates: tile t holds the targets [t tile, min(targets, (t + 1) tile)), slab s the candidates [s L, min(n, (s + 1) L))
+ * with L = ceil(n / slabs); the workspace stays under 768 * 64 * 12 * m bytes.  No device. */
+int gogp_test_vecchia_knn(int device, const double *X, int64_t x_len, int64_t n, int ndim, const double *Z, int64_t z_len,
+                          int64_t targets, const double *lengths, int m, int slabs, int tile_cap, int32_t *nbr,
+                          int64_t nbr_len, double *d2, int64_t d2_len, double *xs, int64_t xs_len);
+int gogp_test_vecchia_knn_plan(int64_t targets, int64_t n, int m, int64_t out[3]);
+
 #ifdef __cplusplus
 }
 #endif
