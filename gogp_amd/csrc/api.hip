@@ -977,13 +977,16 @@ static void begin_evaluation(gogp_handle *h, std::initializer_list<hipStream_t> 
   if (h->kinv_c1 > 0 && !h->have_kinv) wait(EV_KINV);
   h->trtri_pending = h->kinv_pending = false;
   h->factored = h->have_alpha = h->have_kinv = h->grad_valid = false;
-  h->multi_solved = false;
-  h->basis_solved = false;
-  h->lap_observed = h->lap_grad_valid = false;  // a new factor replaces a Laplace fit's (gogp_laplace_observe sets them behind its own)
   h->alpha_pending = h->trtri_done = h->ydone_valid = h->d64_active = false;
   h->notpd = -1;
   h->kinv_c1 = 0;
-  if (!h->batch_mode) h->tinv_valid = false;  // Produce assembles T^-1 of the new factor on its first call
+  // A batched evaluation factors in its arena and gets EvalState back afterwards: what was solved on the handle's own
+  // factor, a Laplace fit in the handle's own buffers and Produce's T^-1 stay as they are (none is part of EvalState).
+  if (h->batch_mode) return;
+  h->multi_solved = false;
+  h->basis_solved = false;
+  h->lap_observed = h->lap_grad_valid = false;  // a new factor replaces a Laplace fit's (gogp_laplace_observe sets them behind its own)
+  h->tinv_valid = false;  // Produce assembles T^-1 of the new factor on its first call
 }
 // the factorisation's scalars and its pivot word on their way to the pinned row(s) that judge_scalars reads
 static hipError_t enqueue_result_scalars(gogp_handle *h, hipStream_t s) {
@@ -5827,6 +5830,16 @@ extern "C" int gogp_append_noisy(gogp_handle *h, const double *X2, const double 
     }
     return rc;
   }
+  // (begin_factor_update drops the outputs and the basis, which belong to the rows as they were: the rollback puts them
+  // back with the rows; their solutions lie in workspaces of their own, which the update does not write)
+  const int multi_T0 = h->multi_T, basis_p0 = h->basis_p;
+  const bool multi_solved0 = h->multi_solved, basis_solved0 = h->basis_solved;
+  auto keep_outputs = [&]() {  // on every return that leaves the old rows and their factor in place
+    h->multi_T = multi_T0;
+    h->multi_solved = multi_solved0;
+    h->basis_p = basis_p0;
+    h->basis_solved = basis_solved0;
+  };
   int rc = begin_factor_update(h);
   if (rc != GOGP_OK) return rc;
   hipStream_t s = h->s;
@@ -5834,10 +5847,10 @@ extern "C" int gogp_append_noisy(gogp_handle *h, const double *X2, const double 
   const int64_t n0 = h->n, npad0 = h->npad, n1 = n0 + m, npad1 = ((n1 + PANEL - 1) / PANEL) * PANEL;
   const bool restride = npad1 != npad0, grow = npad1 > h->cap_npad;
   rc = gogp_upload_params(h);
-  if (rc != GOGP_OK) return rc;
+  if (rc != GOGP_OK) return keep_outputs(), rc;
   const size_t blk = (size_t)PANEL * PANEL;
   rc = h->app_ws.reserve(h, (blk + (size_t)(std::max(npad1, h->cap_npad) / PANEL) * gogp::APPEND_PART) * sizeof(double));
-  if (rc != GOGP_OK) return rc;
+  if (rc != GOGP_OK) return keep_outputs(), rc;
   double *dsave = h->app_ws.as<double>(), *part = dsave + blk;
   const size_t vb0 = (size_t)npad0 * sizeof(double);
   if (!h->z_valid) {  // a restored factor: z = L^-1 y by the substitution steps
@@ -5858,6 +5871,7 @@ extern "C" int gogp_append_noisy(gogp_handle *h, const double *X2, const double 
     NBufs nb;
     if (nbufs_alloc(h, cap, &nb) != hipSuccess) {
       (void)hipGetLastError();
+      keep_outputs();
       return fail(h, GOGP_ENOMEM, "append: out of device memory");
     }
     HIPCHK(h, hipMemsetAsync(nb.dX, 0, ((size_t)cap * D + xslack) * sizeof(double), s));
@@ -5923,6 +5937,7 @@ extern "C" int gogp_append_noisy(gogp_handle *h, const double *X2, const double 
     h->nblk = saved.nblk;
     static_cast<EvalState &>(*h) = saved.es;
     if (restride && !grow) h->have_kinv = false;  // bufA held the restrided copy
+    keep_outputs();
     (void)hipStreamSynchronize(s);
     free_m_buffers(h);  // sized for the npad that did not come to be
   };

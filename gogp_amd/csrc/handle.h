@@ -243,13 +243,14 @@ struct gogp_handle : EvalBufs, EvalState {
   Workspace bcv_s;          // ... and the groups' 128 x 128 S_g; the gradient's two matrices are loo_mat
   // T output columns on the handle's factorisation (gogp_multi_*, multi.hip); all released with the N buffers
   int multi_T = 0;             // outputs set (gogp_multi_set_outputs) for the current data; 0: none
-  bool multi_solved = false;   // A = K^-1 Y of the current factor is in multi_vec: cleared wherever have_alpha is
+  bool multi_solved = false;   // A = K^-1 Y of the current factor is in multi_vec: cleared with every new factor of the handle's own
+                               // (not by a batched evaluation in the candidates arena: begin_evaluation) and restored by Append's rollback
   Workspace multi_vec;      // Y^T, then A^T: GOGP_MULTI_MAX_T rows of npad doubles each, zero from column n and from row T on
   Workspace multi_mean;     // gogp_multi_produce: Kstar^T A, mpad x GOGP_MULTI_MAX_T; gogp_multi_lml: the T dots
   Workspace multi_mat;      // gogp_multi_gradient: G = T K^-1 - A A^T and a zero vector, (npad + 1) x npad
   // explicit basis functions on the handle's factorisation (gogp_basis_*, basis.hip); all released with the N buffers
   int basis_p = 0;             // basis columns set (gogp_basis_set) for the current data; 0: none
-  bool basis_solved = false;   // W, A's factor, beta and [Q | alpha~] of the current factor are in basis_vec: cleared wherever multi_solved is
+  bool basis_solved = false;   // W, A's factor, beta and [Q | alpha~] of the current factor are in basis_vec: cleared and kept exactly where multi_solved is
   int basis_symm = -1;         // option "basis_symm": W from the explicit K^-1 (1), from the factor (0), -1: from K^-1 where it is there
   Workspace basis_vec;      // H^T, W^T, [Q | alpha~]^T and the p x p results (api.hip: BasisBufs)
   Workspace basis_part;     // the slabs' partial sums of basis_symm_kernel

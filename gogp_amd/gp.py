@@ -262,8 +262,8 @@ class GP:
         (gogp_append_noisy): the state Absorb on all observations would leave, without a new factorisation.  An empty
         process absorbs them at ThetaSimil / ThetaNoise.  ``v``: the new observations' noise variances
         (SetNoiseVariances); None: zeros.  With ``v`` on a process without variances the old rows get zeros.  Raises
-        FactorizeError (``pivot``: the global index) and leaves the process, its variances included, as it was when
-        the enlarged matrix is not positive definite."""
+        FactorizeError (``pivot``: the global index) and leaves the process -- its variances, outputs and basis included
+        -- as it was when the enlarged matrix is not positive definite."""
         xa = _arr(x).reshape(-1, self.NDim)
         ya = _arr(y).reshape(-1)
         if len(xa) != len(ya):
@@ -442,6 +442,8 @@ class GP:
 
     # ---- gp.GP.Gradient (gp/gp.go:418-499) ---------------------------------------------
     def Gradient(self) -> np.ndarray:
+        """d LML / d log theta (and, after the full form of Observe, d / dX and d / dY) at the last Observe.  It belongs
+        to Observe alone: after Absorb, Append, Remove, restore or LaplaceObserve it is refused (GOGP_ESTATE)."""
         g = np.zeros(self._last_len)
         self._check(_lib.lib().gogp_gradient(self._h, _dp(g), g.size))
         return g
@@ -665,11 +667,14 @@ class GP:
         the mean's contribution, and the standard deviation widened by the uncertainty of beta (gogp_basis_produce)."""
         z = _arr(x).reshape(-1, self.NDim)
         m = len(z)
-        hz = np.ascontiguousarray(_arr(Hz).reshape(m, -1)) if m else np.zeros((0, 0))
+        hz = _arr(Hz)
+        # (an m x 0 array: no basis is set, and the library says so as BasisLML does, with GOGP_ESTATE)
+        hz = np.ascontiguousarray(hz.reshape(m, -1)) if m and hz.size else np.zeros((m, 0))
         if m and hz.shape[1] != getattr(self, "_p", 0):
             raise ValueError("BasisProduce: Hz must be m x p")
         mu, sigma = np.zeros(m), np.zeros(m)
-        self._check(_lib.lib().gogp_basis_produce(self._h, _dp(z) if m else None, _dp(hz) if m else None, m,
+        buf = hz if hz.size else np.zeros(1)  # (no basis: a pointer the library may look at)
+        self._check(_lib.lib().gogp_basis_produce(self._h, _dp(z) if m else None, _dp(buf) if m else None, m,
                                                   _dp(mu) if m else None, _dp(sigma) if m else None))
         return mu, sigma
 
@@ -1057,7 +1062,8 @@ class GP:
 
     def VecchiaProduceNearest(self, z, lengths=None, sigma: bool = True, table: bool = False):
         """VecchiaProduce(z, vecchia.nearest_to(x, z, m, lengths)) with the table found on the device
-        (gogp_vecchia_produce_nearest); ``lengths=None``: those the resident table was built with.  Returns (mu, sigma), or
+        (gogp_vecchia_produce_nearest); ``lengths=None``: those the resident table was built with (refused with GOGP_ESTATE
+        where the caller brought the table: SetVecchia).  Returns (mu, sigma), or
         (mu, sigma, table) with ``table=True``."""
         what = "VecchiaProduceNearest"
         zz = self._vecchia_rows(z, what + ": z")
@@ -1073,7 +1079,9 @@ class GP:
 
     def SparseObserve(self, x) -> float:
         """The collapsed variational bound of Titsias (2009) at x = log theta (gogp_sparse_observe): a lower bound of
-        the LML of the sparse data that costs O(N M^2)."""
+        the LML of the sparse data that costs O(N M^2).  SparseObserve and SparseMultiObserve share one workspace: the
+        last one of either flavour owns it, and the other flavour's gradient and forecast are refused (GOGP_ESTATE)
+        until it observes again."""
         xa = np.ascontiguousarray(_arr(x).reshape(-1))
         v = ctypes.c_double(0.0)
         self._check(_lib.lib().gogp_sparse_observe(self._h, _dp(xa if xa.size else np.zeros(1)), xa.size, ctypes.byref(v)))
@@ -1129,7 +1137,8 @@ class GP:
 
     def SparseMultiObserve(self, x):
         """(total, bounds): the collapsed bound of every output column at x = log theta and their sum in column order
-        (gogp_sparse_multi_observe): one pass over the data for all of them."""
+        (gogp_sparse_multi_observe): one pass over the data for all of them.  It takes the workspace it shares with
+        SparseObserve: SparseGradient and SparseProduce are refused (GOGP_ESTATE) until the next SparseObserve."""
         xa = np.ascontiguousarray(_arr(x).reshape(-1))
         T = getattr(self, "_sparse_t", 0)
         total, per = ctypes.c_double(0.0), np.zeros(max(T, 1))
@@ -1218,6 +1227,12 @@ class GP:
         return int(nodes.value), bool(refused.value)
 
     def set_option(self, name: str, value: int):
+        """gogp_set_option; include/gogp_hip.h lists the options.  "gradient_precision" = 32 (K^-1 in float for Gradient
+        alone) is refused while noise variances are set (GOGP_EARG); while it holds, SetNoiseVariances and the calls that
+        read an fp64 K^-1 -- LOO, BlockCV, NoiseVariancesGradient, the Multi* and Basis* calls -- and LaplaceObserve,
+        LaplaceGradient and LaplaceProduce are refused with GOGP_EARG (LaplaceMode still copies out a stored mode); LML,
+        Alpha, Produce and the candidates are unchanged.  Setting it (to either value)
+        drops a stored K^-1 and gradient, nothing else."""
         self._check(_lib.lib().gogp_set_option(self._h, name.encode(), int(value)))
 
     def profile_enable(self, on: bool = True):
@@ -1233,7 +1248,8 @@ class GP:
     def observe_gradient_candidates(self, xs, strict=True):
         """LML and gradient of k candidate parameter vectors (rows of xs, log theta) on this GP's
         data in ONE launch sequence (gogp_observe_gradient_candidates): what Observe(xs[c]) +
-        Gradient() would return for each c, without touching the GP's own state (a ShardedGP evaluates
+        Gradient() would return for each c, without touching the GP's own state -- its factor and what was solved on it, a
+        Laplace fit, its outputs and basis -- (a ShardedGP evaluates
         them one after the other in its own tiles and afterwards holds the last one's factorisation).  Counterpart:
         candidates evaluated concurrently by the reference's optimiser (optimize.Settings.
         Concurrent, tutorial/tutorial.go:30,141).  Returns (lmls[k], grads[k x P], status[k]):
