@@ -31,7 +31,7 @@
 #include <type_traits>
 #include <utility>
 
-#include "handle.h"
+#include "api_internal.h"
 
 using namespace gogp;
 
@@ -254,8 +254,6 @@ static hipError_t graph_stream(gogp_handle *h) {
 }
 
 static void sparse_free(gogp_handle *h);  // the inducing-point state (gogp_sparse_*), below
-static void cg_free(gogp_handle *h);      // the data and state of the iterative exact GP (gogp_cg_*), below
-static void vecchia_free(gogp_handle *h); // the data and state of Vecchia's approximation (gogp_vecchia_*), below
 
 static void release_streams(gogp_handle *h) {
   std::lock_guard<std::mutex> lock(g_pool_mutex);
@@ -271,8 +269,8 @@ extern "C" void gogp_destroy(gogp_handle *h) {
   if (h->s) (void)hipStreamSynchronize(h->s);
   gogp_dist_destroy(h);
   sparse_free(h);
-  cg_free(h);
-  vecchia_free(h);
+  h->cg.release();
+  h->vc.release();
   free_n_buffers(h);
   free_m_buffers(h);
   free_cand_buffers(h);
@@ -453,7 +451,7 @@ extern "C" int gogp_set_events(gogp_handle *h, const double *events, int nevents
 
 // ---- parameters ---------------------------------------------------------------------------
 // DevParams of the natural parameters ts (similarity), tn (noise)
-static void fill_params_theta(const gogp_handle *h, const double *ts, const double *tn, DevParams &p) {
+void gogp::fill_params_theta(const gogp_handle *h, const double *ts, const double *tn, DevParams &p) {
   const gogp_desc &d = h->desc;
   memset(&p, 0, sizeof p);
   p.ndim = d.ndim;
@@ -1324,7 +1322,7 @@ static int ensure_alpha(gogp_handle *h) {
 }
 
 // NULL, or what is wrong with the natural parameters ts / tn
-static const char *theta_refusal(const gogp_handle *h, const double *ts, const double *tn) {
+const char *gogp::theta_refusal(const gogp_handle *h, const double *ts, const double *tn) {
   for (int i = 0; i < h->ns; ++i)
     if (!(ts[i] > 0.0) || !std::isfinite(ts[i])) return "similarity parameters must be positive and finite";
   for (int i = 0; i < h->nn; ++i)
@@ -1480,7 +1478,7 @@ static int64_t grad_len(const gogp_handle *h) {
 }
 
 // d LML / d log theta from the slot sums of the fused reduction (common.h: ACC_*); out: P zeros
-static void assemble_gradient(const gogp_handle *h, const double *a, double dnoise, double *out) {
+void gogp::assemble_gradient(const gogp_handle *h, const double *a, double dnoise, double *out) {
   const gogp_desc &d = h->desc;
   for (int t = 0; t < d.nterms; ++t) {
     const gogp_term &T = d.terms[t];
@@ -3535,12 +3533,19 @@ static void sparse_free(gogp_handle *h) {
   h->sp_have = h->sp_observed = false;
 }
 
-// NULL, or the kind of handle the sparse calls refuse
-static const char *sparse_refusal(const gogp_handle *h) {
+// NULL, or the kind of handle the sparse calls refuse (events: another text for a handle with event discounts)
+static const char *sparse_refusal(const gogp_handle *h, const char *events = nullptr) {
   return h->prec == 32 ? "precision = 32 handles are not supported"
          : h->dist     ? "sharded handles are not supported"
-         : h->ev()     ? "event discounts are out of scope of the inducing-point approximation (clear them with gogp_set_events)"
-                       : nullptr;
+         : !h->ev()    ? nullptr
+         : events      ? events
+                       : "event discounts are out of scope of the inducing-point approximation (clear them with gogp_set_events)";
+}
+// ... which the iterative and the Vecchia calls refuse too, the event discounts in words of their own
+int gogp::refuse_handle(gogp_handle *h, const char *who) {
+  if (!h) return GOGP_EARG;
+  const char *why = sparse_refusal(h, "event discounts are out of scope of the iterative solver (clear them with gogp_set_events)");
+  return why ? refuse(h, who, GOGP_EARG, why) : GOGP_OK;
 }
 static int sparse_refuse(gogp_handle *h, const char *who) {
   char buf[200];
@@ -4198,1065 +4203,6 @@ extern "C" int gogp_sparse_select_inducing_resident(gogp_handle *h, const double
                                                     int64_t *idx, double *pivots, double *U, int64_t *m_out, double *trace) {
   return sparse_select_impl(h, "sparse_select_inducing_resident", true, x, len, nullptr, 0, M, tol, idx, pivots, U, m_out,
                             trace);
-}
-
-// ---- the iterative exact GP (cg.hip) ---------------------------------------------------------------------------------------
-// include/gogp_hip.h states the iteration and the preconditioner; DESIGN.md section 4, "Iterative (CG)".  Everything runs
-// on the handle's main stream with buffers of the family's own.  Reused launchers: select_run (the factor), launch_cross
-// (the right-hand sides k* of Produce, whose KsT layout is one row of N per test point), launch_prior.  The Woodbury
-// products are cg.hip's own: the factor lies column-major and a block's vectors as T rows of N, which neither
-// launch_sparse_xty / launch_sparse_syrk (row-major chunks of Vt) nor the tile GEMM (multiples of 128) take without
-// transposed copies of N x rank and N x T doubles per application.  C = I + Ls^T Ls (rank <= 1024) is factored and inverted on
-// the host, once per solve.
-static int cg_refuse_handle(gogp_handle *h, const char *who);
-static void cg_free(gogp_handle *h) {
-  for (double *q : {h->cg_X, h->cg_y, h->cg_v, h->cg_d, h->cg_dis, h->cg_alpha}) (void)hipFree(q);
-  (void)hipFree(h->cg_P);
-  h->cg_X = h->cg_y = h->cg_v = h->cg_d = h->cg_dis = h->cg_alpha = nullptr;
-  h->cg_P = nullptr;
-  h->cg_L.release();
-  h->cg_small.release();
-  h->cg_vec.release();
-  h->cg_part.release();
-  h->cg_ks.release();
-  h->cg_lml.release();
-  h->cg_N = h->cg_npad = 0;
-  h->cg_have = h->cg_solved = false;
-  h->cg_rank = h->cg_rp = 0;
-}
-
-extern "C" int gogp_cg_set_data(gogp_handle *h, const double *X, const double *y, const double *v, int64_t N) {
-  if (!h) return GOGP_EARG;
-  if (N == 0 && !X && !y && !v) {  // clear
-    HIPCHK(h, hipSetDevice(h->device));
-    cg_free(h);
-    return GOGP_OK;
-  }
-  if (sparse_refusal(h)) return cg_refuse_handle(h, "cg_set_data");
-  if (N < 1 || !X || !y) return fail(h, GOGP_EARG, "cg_set_data: need X, y and N >= 1 (N == 0 with NULLs clears)");
-  const int D = h->D;
-  for (int64_t i = 0; i < N * D; ++i)
-    if (!std::isfinite(X[i])) return fail(h, GOGP_EARG, "cg_set_data: non-finite input");
-  for (int64_t i = 0; i < N; ++i)
-    if (!std::isfinite(y[i])) return fail(h, GOGP_EARG, "cg_set_data: non-finite output");
-  double vmin = 0.0;
-  if (v) {
-    vmin = INFINITY;
-    for (int64_t i = 0; i < N; ++i) {
-      if (!std::isfinite(v[i]) || v[i] < 0.0) return fail(h, GOGP_EARG, "cg_set_data: noise variances must be finite and >= 0");
-      vmin = std::min(vmin, v[i]);
-    }
-  }
-  HIPCHK(h, hipSetDevice(h->device));
-  if (h->s) HIPCHK(h, hipStreamSynchronize(h->s));
-  cg_free(h);
-  const int64_t npad = (N + 255) / 256 * 256;
-  const size_t xb = ((size_t)npad * D + GOGP_MAX_NDIM) * sizeof(double), vb = (size_t)npad * sizeof(double);
-  hipStream_t s = h->s;
-  hipError_t e = hipMalloc(&h->cg_X, xb);
-  if (e == hipSuccess) e = hipMalloc(&h->cg_y, vb);
-  if (e == hipSuccess && v) e = hipMalloc(&h->cg_v, vb);
-  if (e == hipSuccess) e = hipMalloc(&h->cg_d, vb);
-  if (e == hipSuccess) e = hipMalloc(&h->cg_dis, vb);
-  if (e == hipSuccess) e = hipMalloc(&h->cg_alpha, vb);
-  if (e == hipSuccess) e = hipMalloc(&h->cg_P, sizeof(DevParams));
-  if (e == hipSuccess) e = hipMemsetAsync(h->cg_X, 0, xb, s);
-  if (e == hipSuccess) e = hipMemsetAsync(h->cg_y, 0, vb, s);
-  if (e == hipSuccess && v) e = hipMemsetAsync(h->cg_v, 0, vb, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(h->cg_X, X, (size_t)N * D * sizeof(double), hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(h->cg_y, y, (size_t)N * sizeof(double), hipMemcpyHostToDevice, s);
-  if (e == hipSuccess && v) e = hipMemcpyAsync(h->cg_v, v, (size_t)N * sizeof(double), hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (e != hipSuccess) {
-    cg_free(h);
-    HIPCHK(h, e);
-  }
-  h->cg_N = N;
-  h->cg_npad = npad;
-  h->cg_vmin = vmin;
-  h->cg_have = true;
-  return GOGP_OK;
-}
-
-// The small device buffers of the family behind C^-1: W, Y, the state, the dots' results
-struct CgSmall {
-  double *Cinv, *W, *Y, *sc, *dots;
-  int *st;
-};
-static size_t cg_small_layout(char *base, int rp, CgSmall *b) {
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char *q = base ? base + off : nullptr;
-    off += (bytes + 255) / 256 * 256;
-    return q;
-  };
-  const size_t rr = (size_t)std::max(rp, 16);
-  b->Cinv = reinterpret_cast<double *>(take(rr * rr * sizeof(double)));
-  b->W = reinterpret_cast<double *>(take((size_t)CG_MAX_T * rr * sizeof(double)));
-  b->Y = reinterpret_cast<double *>(take((size_t)CG_MAX_T * rr * sizeof(double)));
-  b->sc = reinterpret_cast<double *>(take((size_t)CG_SC_ROWS * CG_MAX_T * sizeof(double)));
-  b->dots = reinterpret_cast<double *>(take((size_t)CG_MAX_T * sizeof(double)));
-  b->st = reinterpret_cast<int *>(take((size_t)CG_ST_ROWS * CG_MAX_T * sizeof(int)));
-  return off;
-}
-
-// z = P^-1 r for a block (T rows of ld = npad doubles)
-static void cg_apply_precond(gogp_handle *h, const CgSmall &sm, const double *R, int T, double *Z) {
-  hipStream_t s = h->s;
-  const int r = h->cg_rank, rp = h->cg_rp;
-  const double *Ls = h->cg_L.as<double>();
-  if (r > 0) {
-    launch_cg_lst(s, Ls, h->cg_ldn, h->cg_N, r, rp, h->cg_dis, R, h->cg_npad, T, h->cg_part.as<double>(), sm.W);
-    launch_cg_small_mm(s, sm.Cinv, r, rp, sm.W, T, sm.Y);
-  }
-  launch_cg_precond(s, Ls, h->cg_ldn, h->cg_N, r, rp, h->cg_dis, R, sm.Y, h->cg_npad, T, Z);
-}
-
-// the scratch the product and the skinny transposed product share: sized for CG_MAX_T columns once
-static int cg_reserve_part(gogp_handle *h, int T) {
-  const int64_t n = h->cg_N;
-  const size_t kmm = (size_t)kmm_slabs(n, n) * (size_t)T * (size_t)((n + 63) / 64 * 64);
-  const size_t lst = (size_t)cg_lst_slabs(n) * (size_t)((T + 15) / 16 * 16) * (size_t)std::max(h->cg_rp, 16);
-  return h->cg_part.reserve(h, std::max(kmm, lst) * sizeof(double));
-}
-
-// One lock-step block: K^ x_t = b_t for the T <= CG_MAX_T rows of dB (device, ld = npad, zero from column n on); the
-// solutions are left in the first T rows of the workspace's x (returned through *xout).  GOGP_OK, GOGP_ENOCONV (every
-// output written) or an error.  With `keep` (gogp_cg_lml_gradient) the block also holds on to w = P^-1 b (a seventh
-// vector behind the dots' partials, returned through keep->w), records every iteration's a and beta (keep->hist, device:
-// 2 max_iter rows of CG_MAX_T) and leaves rho0 = b^T w per column in keep->rho0 (device, CG_MAX_T); no bit of x depends on it.
-struct CgKeep {
-  double *hist = nullptr, *rho0 = nullptr;  // in: device buffers
-  double *w = nullptr;                      // out
-};
-static int cg_block_solve(gogp_handle *h, const char *who, const double *dB, int T, double tol, int max_iter, double **xout,
-                          gogp_cg_col *cols, int col0, CgKeep *keep = nullptr) {
-  const int64_t n = h->cg_N, ld = h->cg_npad;
-  hipStream_t s = h->s;
-  const int nb = cg_dot_blocks(n);
-  const size_t vec = (size_t)T * (size_t)ld;
-  int rc = h->cg_vec.reserve(h, ((keep ? 6 : 5) * vec + (size_t)CG_MAX_T * nb) * sizeof(double));
-  if (rc == GOGP_OK) rc = cg_reserve_part(h, T);
-  if (rc != GOGP_OK) return rc;
-  CgSmall sm;
-  cg_small_layout(h->cg_small.as<char>(), h->cg_rp, &sm);
-  double *x = h->cg_vec.as<double>(), *r = x + vec, *p = r + vec, *z = p + vec, *q = z + vec, *dpart = q + vec;
-  double *kpart = h->cg_part.as<double>();
-  const CgState cs{sm.sc, sm.st};
-  const int nslab = kmm_slabs(n, n);
-  const DevParams *P = h->cg_P;
-  const int D = h->D;
-  HIPCHK(h, hipMemsetAsync(x, 0, 5 * vec * sizeof(double), s));
-  HIPCHK(h, hipMemcpyAsync(r, dB, vec * sizeof(double), hipMemcpyDeviceToDevice, s));
-  launch_cg_dots(s, r, r, ld, n, T, CG_DOT_BNORM, 0, tol, dpart, nullptr, cs);
-  cg_apply_precond(h, sm, r, T, z);
-  HIPCHK(h, hipMemcpyAsync(p, z, vec * sizeof(double), hipMemcpyDeviceToDevice, s));
-  double *hist = nullptr;
-  if (keep) {
-    keep->w = dpart + (size_t)CG_MAX_T * nb;
-    hist = keep->hist;
-    HIPCHK(h, hipMemcpyAsync(keep->w, z, vec * sizeof(double), hipMemcpyDeviceToDevice, s));
-  }
-  launch_cg_dots(s, r, z, ld, n, T, CG_DOT_RHO0, 0, tol, dpart, keep ? keep->rho0 : nullptr, cs);
-  int status[2] = {T, 0};
-  const int check = std::max(1, h->cg_check);
-  for (int it = 1; it <= max_iter; ++it) {
-    launch_kmm(s, P, D, h->cg_X, n, h->cg_X, n, p, ld, T, h->cg_d, nslab, 0, kpart, q, ld);
-    ++h->cg_products;
-    launch_cg_dots(s, p, q, ld, n, T, CG_DOT_PQ, it, tol, dpart, nullptr, cs, hist);
-    launch_cg_update_xr(s, x, r, p, q, ld, n, T, cs);
-    launch_cg_dots(s, r, r, ld, n, T, CG_DOT_RR, it, tol, dpart, nullptr, cs);
-    cg_apply_precond(h, sm, r, T, z);
-    launch_cg_dots(s, r, z, ld, n, T, CG_DOT_BETA, it, tol, dpart, nullptr, cs, hist);
-    launch_cg_update_p(s, p, z, ld, n, T, cs);
-    if (it % check == 0 || it == max_iter) {
-      launch_cg_status(s, T, cs);
-      HIPCHK(h, hipMemcpyAsync(status, sm.st + CG_ST_STATUS * CG_MAX_T, sizeof status, hipMemcpyDeviceToHost, s));
-      HIPCHK(h, hipStreamSynchronize(s));
-      if (status[0] == 0 || status[1] != 0) break;
-    }
-  }
-  // the true residual: one more product; b - K^ x into z, its squared norms through the plain dots
-  launch_kmm(s, P, D, h->cg_X, n, h->cg_X, n, x, ld, T, h->cg_d, nslab, 0, kpart, q, ld);
-  ++h->cg_products;
-  launch_cg_scale(s, dB, nullptr, q, ld, n, T, z);
-  launch_cg_dots(s, z, z, ld, n, T, CG_DOT_PLAIN, 0, tol, dpart, sm.dots, cs);
-  double hsc[CG_SC_ROWS * CG_MAX_T], hdots[CG_MAX_T];
-  int hst[CG_ST_ROWS * CG_MAX_T];
-  // (the three copies land in locals: the stream is drained before any return, whatever failed)
-  hipError_t ce = hipMemcpyAsync(hsc, sm.sc, sizeof hsc, hipMemcpyDeviceToHost, s);
-  if (ce == hipSuccess) ce = hipMemcpyAsync(hdots, sm.dots, sizeof hdots, hipMemcpyDeviceToHost, s);
-  if (ce == hipSuccess) ce = hipMemcpyAsync(hst, sm.st, sizeof hst, hipMemcpyDeviceToHost, s);
-  const hipError_t se = hipStreamSynchronize(s);
-  HIPCHK(h, ce);
-  HIPCHK(h, se);
-  HIPCHK(h, hipGetLastError());
-  ++h->cg_blocks;
-  *xout = x;
-  int bad = -1;
-  bool all = true;
-  for (int t = 0; t < T; ++t) {
-    const bool isbad = hst[CG_ST_BAD * CG_MAX_T + t] != 0;
-    if (isbad && bad < 0) bad = t;
-    const bool conv = hst[CG_ST_FROZEN * CG_MAX_T + t] != 0 && !isbad;
-    all = all && conv;
-    if (cols) {
-      gogp_cg_col &c = cols[t];
-      const double bn = sqrt(hsc[CG_SC_BNORM2 * CG_MAX_T + t]);
-      c.iterations = hst[CG_ST_ITERS * CG_MAX_T + t];
-      c.converged = conv ? 1 : 0;
-      c.rel_residual = bn > 0.0 ? sqrt(hdots[t]) / bn : 0.0;
-      c.rel_residual_recurrence = bn > 0.0 ? sqrt(hsc[CG_SC_RR * CG_MAX_T + t]) / bn : 0.0;
-    }
-  }
-  char buf[200];
-  if (bad >= 0) {
-    snprintf(buf, sizeof buf, "%s: p^T K p of column %d is not positive and finite (%g): the matrix is not positive definite",
-             who, col0 + bad, hsc[CG_SC_PQ * CG_MAX_T + bad]);
-    return fail(h, GOGP_ENOTPD, buf);
-  }
-  if (!all) {
-    snprintf(buf, sizeof buf, "%s: a column did not reach the tolerance within %d iterations", who, max_iter);
-    return fail(h, GOGP_ENOCONV, buf);
-  }
-  return GOGP_OK;
-}
-
-// the kinds of handle the sparse calls refuse, in the iterative calls' own words
-static int cg_refuse_handle(gogp_handle *h, const char *who) {
-  const char *why = h->prec == 32 ? "precision = 32 handles are not supported"
-                    : h->dist     ? "sharded handles are not supported"
-                                  : "event discounts are out of scope of the iterative solver (clear them with gogp_set_events)";
-  return fail(h, GOGP_EARG, (std::string(who) + ": " + why).c_str());
-}
-static const char *cg_tol_refusal(double tol, int32_t max_iter) {
-  if (!(tol > 0.0) || !std::isfinite(tol)) return "tol must be positive and finite";
-  if (max_iter < 1) return "max_iter must be at least 1";
-  return nullptr;
-}
-static int cg_refuse(gogp_handle *h, const char *who, int code, const char *what) {
-  return fail(h, code, (std::string(who) + ": " + what).c_str());
-}
-
-extern "C" int gogp_cg_solve(gogp_handle *h, const double *x, int64_t len, int32_t rank, double piv_tol, double tol,
-                             int32_t max_iter, gogp_cg_info *info, gogp_cg_col *col) {
-  const char *who = "cg_solve";
-  if (!h) return GOGP_EARG;
-  if (!x || !info) return cg_refuse(h, who, GOGP_EARG, "NULL");
-  if (sparse_refusal(h)) return cg_refuse_handle(h, who);
-  if (len != h->P) return cg_refuse(h, who, GOGP_EARG, "len(x)");
-  for (int64_t i = 0; i < len; ++i)
-    if (!std::isfinite(x[i])) return cg_refuse(h, who, GOGP_EARG, "non-finite parameter");
-  if (rank < 0 || rank > GOGP_CG_MAX_RANK) return cg_refuse(h, who, GOGP_EARG, "need 0 <= rank <= GOGP_CG_MAX_RANK");
-  if (std::isnan(piv_tol) || piv_tol == INFINITY) return cg_refuse(h, who, GOGP_EARG, "piv_tol must be finite or negative");
-  if (const char *why = cg_tol_refusal(tol, max_iter)) return cg_refuse(h, who, GOGP_EARG, why);
-  if (!h->cg_have) return cg_refuse(h, who, GOGP_ESTATE, "no data (gogp_cg_set_data)");
-  std::vector<double> th(h->P > 0 ? h->P : 1);
-  for (int i = 0; i < h->P; ++i) th[i] = exp(x[i]);
-  if (const char *why = theta_refusal(h, th.data(), th.data() + h->ns)) return cg_refuse(h, who, GOGP_EARG, why);
-  DevParams hp;
-  fill_params_theta(h, th.data(), th.data() + h->ns, hp);
-  // D = diag(noise_var + v_i) is inverted: its smallest entry must be positive
-  if (!(hp.noise_var + h->cg_vmin > 0.0)) return cg_refuse(h, who, GOGP_EARG, "noise_var + min v_i must be positive");
-  if (piv_tol < 0.0) piv_tol = pow(10.0, (double)h->sp_jitter_log10);
-  HIPCHK(h, hipSetDevice(h->device));
-  hipStream_t s = h->s;
-  const int64_t N = h->cg_N, npad = h->cg_npad;
-  const int D = h->D;
-  h->cg_solved = false;
-  h->cg_products = h->cg_blocks = 0;
-  h->cg_rank = h->cg_rp = 0;
-  h->cg_logdet_c = 0.0;
-  h->cg_dnoise = hp.dnoise;
-  *info = gogp_cg_info();
-  HIPCHK(h, hipMemcpyAsync(h->cg_P, &hp, sizeof hp, hipMemcpyHostToDevice, s));
-  HIPCHK(h, hipStreamSynchronize(s));  // hp is a local
-  launch_cg_diag(s, h->cg_P, h->cg_v, N, npad, h->cg_d, h->cg_dis);
-  // ---- the preconditioner: pivoted Cholesky of k(X, X), scaled, and the inverse of its capacitance matrix -----------------
-  int64_t m = 0;
-  const int64_t cap = std::min<int64_t>(rank, N);
-  if (cap > 0) {
-    SelectBufs b;
-    const size_t small = select_layout(nullptr, N, cap, D, &b);
-    const size_t lbytes = (size_t)cap * (size_t)b.ldn * sizeof(double);
-    if (const int rl = h->cg_L.reserve(h, lbytes)) {
-      if (rl != GOGP_ENOMEM) return rl;
-      char buf[240];
-      snprintf(buf, sizeof buf, "cg_solve: the factor (%lld columns of %lld doubles, %.3f GB) could not be allocated: %s",
-               (long long)cap, (long long)b.ldn, (double)lbytes * 1e-9, h->err.c_str());
-      h->err = buf;
-      return GOGP_ENOMEM;
-    }
-    char *work = nullptr;
-    HIPCHK(h, hipMalloc(&work, small));
-    select_layout(work, N, cap, D, &b);
-    b.Lt = h->cg_L.as<double>();
-    const hipError_t e = select_run(s, h->cg_P, D, h->cg_X, N, cap, piv_tol, 0, nullptr, b, &m);
-    (void)hipFree(work);
-    HIPCHK(h, e);
-    h->cg_ldn = b.ldn;
-  }
-  const int r = (int)m, rp = (r + 15) / 16 * 16;
-  CgSmall sm;
-  int rc = h->cg_small.reserve(h, cg_small_layout(nullptr, rp, &sm));
-  if (rc != GOGP_OK) return rc;
-  cg_small_layout(h->cg_small.as<char>(), rp, &sm);
-  if (r > 0) {
-    launch_cg_scale_factor(s, h->cg_L.as<double>(), h->cg_ldn, N, r, h->cg_dis);
-    launch_cg_capacitance(s, h->cg_L.as<double>(), h->cg_ldn, N, r, rp, sm.Cinv);
-    std::vector<double> C((size_t)rp * rp), G((size_t)rp * rp, 0.0);
-    HIPCHK(h, hipMemcpyAsync(C.data(), sm.Cinv, C.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipStreamSynchronize(s));
-    HIPCHK(h, hipGetLastError());
-    // C = G G^T (C >= I: every pivot is at least 1 up to rounding), Ginv = G^-1, C^-1 = Ginv^T Ginv -- on the host
-    for (int j = 0; j < rp; ++j) {
-      double dj = C[(size_t)j * rp + j];
-      for (int k = 0; k < j; ++k) dj -= G[(size_t)j * rp + k] * G[(size_t)j * rp + k];
-      if (!(dj > 0.0) || !std::isfinite(dj)) return cg_refuse(h, who, GOGP_ENOTPD, "the capacitance matrix of the preconditioner is not positive definite");
-      dj = sqrt(dj);
-      G[(size_t)j * rp + j] = dj;
-      for (int i = j + 1; i < rp; ++i) {
-        double v = C[(size_t)i * rp + j];
-        const double *gi = &G[(size_t)i * rp], *gj = &G[(size_t)j * rp];
-        for (int k = 0; k < j; ++k) v -= gi[k] * gj[k];
-        G[(size_t)i * rp + j] = v / dj;
-      }
-    }
-    // G^-1 kept TRANSPOSED (Gt[c][k] = (G^-1)[k][c], upper): every inner loop below runs along rows of G and of Gt
-    std::vector<double> Gt((size_t)rp * rp, 0.0);
-    for (int c = 0; c < rp; ++c) {
-      double *gt = &Gt[(size_t)c * rp];
-      gt[c] = 1.0 / G[(size_t)c * rp + c];
-      for (int i = c + 1; i < rp; ++i) {
-        double v = 0.0;
-        const double *gi = &G[(size_t)i * rp];
-        for (int k = c; k < i; ++k) v -= gi[k] * gt[k];
-        gt[i] = v / gi[i];
-      }
-    }
-    for (int i = 0; i < rp; ++i)
-      for (int j = 0; j <= i; ++j) {  // C^-1[i][j] = sum_{k >= i} (G^-1)[k][i] (G^-1)[k][j]
-        double v = 0.0;
-        const double *ti = &Gt[(size_t)i * rp], *tj = &Gt[(size_t)j * rp];
-        for (int k = i; k < rp; ++k) v += ti[k] * tj[k];
-        C[(size_t)i * rp + j] = C[(size_t)j * rp + i] = v;
-      }
-    HIPCHK(h, hipMemcpyAsync(sm.Cinv, C.data(), C.size() * sizeof(double), hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipStreamSynchronize(s));  // C is a local
-    double ldc = 0.0;  // log |C| = 2 sum_j log G_jj (gogp_cg_lml_gradient; the padded pivots are 1)
-    for (int j = 0; j < r; ++j) ldc += log(G[(size_t)j * rp + j]);
-    h->cg_logdet_c = 2.0 * ldc;
-  }
-  h->cg_rank = r;
-  h->cg_rp = rp;
-  // ---- K^ alpha = y ------------------------------------------------------------------------------------------------------------
-  double *xs = nullptr;
-  gogp_cg_col c1{};
-  rc = cg_block_solve(h, who, h->cg_y, 1, tol, max_iter, &xs, &c1, 0);
-  if (col) *col = c1;
-  info->rank_used = r;
-  info->products = h->cg_products;
-  info->blocks = h->cg_blocks;
-  if (rc != GOGP_OK && rc != GOGP_ENOCONV) return rc;
-  const std::string keep = h->err;
-  HIPCHK(h, hipMemsetAsync(h->cg_alpha, 0, (size_t)npad * sizeof(double), s));
-  HIPCHK(h, hipMemcpyAsync(h->cg_alpha, xs, (size_t)N * sizeof(double), hipMemcpyDeviceToDevice, s));
-  CgState cs{sm.sc, sm.st};
-  launch_cg_dots(s, h->cg_y, h->cg_alpha, npad, N, 1, CG_DOT_PLAIN, 0, tol, xs + 5 * (size_t)npad, sm.dots, cs);
-  HIPCHK(h, hipMemcpyAsync(&h->cg_yta, sm.dots, sizeof(double), hipMemcpyDeviceToHost, s));
-  HIPCHK(h, hipStreamSynchronize(s));
-  HIPCHK(h, hipGetLastError());
-  info->yt_alpha = h->cg_yta;
-  h->cg_solved = true;
-  if (rc != GOGP_OK) h->err = keep;
-  return rc;
-}
-
-extern "C" int gogp_cg_last_info(gogp_handle *h, gogp_cg_info *info) {
-  if (!h) return GOGP_EARG;
-  if (!info) return fail(h, GOGP_EARG, "cg_last_info: NULL");
-  info->rank_used = h->cg_rank;
-  info->products = h->cg_products;
-  info->blocks = h->cg_blocks;
-  info->yt_alpha = h->cg_yta;
-  return GOGP_OK;
-}
-
-extern "C" int gogp_cg_get_alpha(gogp_handle *h, double *alpha, int64_t n) {
-  const char *who = "cg_get_alpha";
-  if (!h) return GOGP_EARG;
-  if (!alpha) return cg_refuse(h, who, GOGP_EARG, "NULL");
-  if (sparse_refusal(h)) return cg_refuse_handle(h, who);
-  if (!h->cg_have || !h->cg_solved) return cg_refuse(h, who, GOGP_ESTATE, "no solution (gogp_cg_solve)");
-  if (n != h->cg_N) return cg_refuse(h, who, GOGP_EARG, "n is not the number of observations");
-  HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, hipMemcpyAsync(alpha, h->cg_alpha, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->s));
-  HIPCHK(h, hipStreamSynchronize(h->s));
-  return GOGP_OK;
-}
-
-extern "C" int gogp_cg_solve_columns(gogp_handle *h, const double *B, int64_t T, double tol, int32_t max_iter, double *S,
-                                     gogp_cg_col *cols) {
-  const char *who = "cg_solve_columns";
-  if (!h) return GOGP_EARG;
-  if (sparse_refusal(h)) return cg_refuse_handle(h, who);
-  if (T < 0 || (T > 0 && (!B || !S))) return cg_refuse(h, who, GOGP_EARG, "need B and S for T > 0, T >= 0");
-  if (const char *why = cg_tol_refusal(tol, max_iter)) return cg_refuse(h, who, GOGP_EARG, why);
-  if (!h->cg_have || !h->cg_solved) return cg_refuse(h, who, GOGP_ESTATE, "no preconditioner (gogp_cg_solve)");
-  const int64_t N = h->cg_N, npad = h->cg_npad;
-  for (int64_t i = 0; i < T * N; ++i)
-    if (!std::isfinite(B[i])) return cg_refuse(h, who, GOGP_EARG, "non-finite right-hand side");
-  HIPCHK(h, hipSetDevice(h->device));
-  hipStream_t s = h->s;
-  h->cg_products = h->cg_blocks = 0;
-  int rc = GOGP_OK;
-  std::string first_err;
-  for (int64_t t0 = 0; t0 < T; t0 += CG_MAX_T) {
-    const int cnt = (int)std::min<int64_t>(CG_MAX_T, T - t0);
-    int r1 = h->cg_ks.reserve(h, (size_t)CG_MAX_T * (size_t)npad * sizeof(double));
-    if (r1 != GOGP_OK) return r1;
-    double *dB = h->cg_ks.as<double>();
-    HIPCHK(h, hipMemsetAsync(dB, 0, (size_t)cnt * npad * sizeof(double), s));
-    HIPCHK(h, hipMemcpy2DAsync(dB, (size_t)npad * sizeof(double), B + t0 * N, (size_t)N * sizeof(double),
-                               (size_t)N * sizeof(double), (size_t)cnt, hipMemcpyHostToDevice, s));
-    double *xs = nullptr;
-    r1 = cg_block_solve(h, who, dB, cnt, tol, max_iter, &xs, cols ? cols + t0 : nullptr, (int)t0);
-    if (r1 != GOGP_OK && r1 != GOGP_ENOCONV) return r1;
-    if (r1 != GOGP_OK && rc == GOGP_OK) rc = r1, first_err = h->err;
-    HIPCHK(h, hipMemcpy2DAsync(S + t0 * N, (size_t)N * sizeof(double), xs, (size_t)npad * sizeof(double),
-                               (size_t)N * sizeof(double), (size_t)cnt, hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipStreamSynchronize(s));
-  }
-  if (rc != GOGP_OK) h->err = first_err;
-  return rc;
-}
-
-extern "C" int gogp_cg_produce(gogp_handle *h, const double *Z, int64_t m, double *mu, double *sigma, double tol,
-                               int32_t max_iter, gogp_cg_col *cols) {
-  const char *who = "cg_produce";
-  if (!h) return GOGP_EARG;
-  if (sparse_refusal(h)) return cg_refuse_handle(h, who);
-  if (m < 0 || (m > 0 && (!Z || !mu))) return cg_refuse(h, who, GOGP_EARG, "need Z and mu for m > 0, m >= 0");
-  if (sigma)
-    if (const char *why = cg_tol_refusal(tol, max_iter)) return cg_refuse(h, who, GOGP_EARG, why);
-  if (!h->cg_have || !h->cg_solved) return cg_refuse(h, who, GOGP_ESTATE, "no solution (gogp_cg_solve)");
-  const int D = h->D;
-  for (int64_t i = 0; i < m * D; ++i)
-    if (!std::isfinite(Z[i])) return cg_refuse(h, who, GOGP_EARG, "non-finite test point");
-  HIPCHK(h, hipSetDevice(h->device));
-  hipStream_t s = h->s;
-  h->cg_products = h->cg_blocks = 0;
-  if (m == 0) return GOGP_OK;
-  const int64_t N = h->cg_N, npad = h->cg_npad;
-  // layout of cg_ks: 64 rows of k* (npad each), 64 test points, prior, q, mu, sigma (64 each)
-  int rc = h->cg_ks.reserve(h, ((size_t)CG_MAX_T * npad + (size_t)CG_MAX_T * (D + 4)) * sizeof(double));
-  if (rc == GOGP_OK) rc = cg_reserve_part(h, CG_MAX_T);
-  if (rc == GOGP_OK) rc = h->cg_part.reserve(h, (size_t)kmm_slabs(CG_MAX_T, N) * 64 * sizeof(double));
-  if (rc != GOGP_OK) return rc;
-  double *Ks = h->cg_ks.as<double>(), *dZ = Ks + (size_t)CG_MAX_T * npad, *prior = dZ + (size_t)CG_MAX_T * D;
-  double *dq = prior + CG_MAX_T, *dmu = dq + CG_MAX_T, *dsg = dmu + CG_MAX_T;
-  CgSmall sm;
-  cg_small_layout(h->cg_small.as<char>(), h->cg_rp, &sm);
-  const CgState cs{sm.sc, sm.st};
-  std::string first_err;
-  int ret = GOGP_OK;
-  for (int64_t j0 = 0; j0 < m; j0 += CG_MAX_T) {
-    const int cnt = (int)std::min<int64_t>(CG_MAX_T, m - j0);
-    HIPCHK(h, hipMemsetAsync(dZ, 0, (size_t)CG_MAX_T * D * sizeof(double), s));
-    HIPCHK(h, hipMemcpyAsync(dZ, Z + j0 * D, (size_t)cnt * D * sizeof(double), hipMemcpyHostToDevice, s));
-    // the mean: rows = the test points, columns = X, one right-hand side alpha
-    launch_kmm(s, h->cg_P, D, dZ, cnt, h->cg_X, N, h->cg_alpha, npad, 1, nullptr, kmm_slabs(cnt, N), 0,
-               h->cg_part.as<double>(), dmu, CG_MAX_T);
-    ++h->cg_products;
-    HIPCHK(h, hipMemcpyAsync(mu + j0, dmu, (size_t)cnt * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (sigma) {
-      launch_cross(s, h->cg_P, D, h->cg_X, N, npad, dZ, cnt, CG_MAX_T, Ks, npad, false);
-      launch_prior(s, h->cg_P, dZ, cnt, prior);
-      double *xs = nullptr;
-      rc = cg_block_solve(h, who, Ks, cnt, tol, max_iter, &xs, cols ? cols + j0 : nullptr, (int)j0);
-      if (rc != GOGP_OK && rc != GOGP_ENOCONV) {
-        (void)hipStreamSynchronize(s);  // the copy of mu into the caller's array must not outlive the call
-        return rc;
-      }
-      if (rc != GOGP_OK && ret == GOGP_OK) ret = rc, first_err = h->err;
-      launch_cg_dots(s, Ks, xs, npad, N, cnt, CG_DOT_PLAIN, 0, tol, xs + 5 * (size_t)cnt * npad, dq, cs);
-      launch_sigma(s, prior, dq, cnt, dsg);
-      HIPCHK(h, hipMemcpyAsync(sigma + j0, dsg, (size_t)cnt * sizeof(double), hipMemcpyDeviceToHost, s));
-    } else if (cols) {
-      for (int t = 0; t < cnt; ++t) cols[j0 + t] = gogp_cg_col();
-    }
-    HIPCHK(h, hipStreamSynchronize(s));
-    HIPCHK(h, hipGetLastError());
-  }
-  if (ret != GOGP_OK) h->err = first_err;
-  return ret;
-}
-
-// The LML and its gradient at the theta, preconditioner and alpha of the last gogp_cg_solve (include/gogp_hip.h states
-// the estimator).  Per block of CG_MAX_T probes: the rows of Xi go up, cg_probe_kernel forms z = D^1/2 (Ls xi1 + xi2), one
-// lock-step block solves K^ u = z and keeps w = P^-1 z, rho0 and the a / beta history; the host turns each column's history
-// into its quadrature value, and the pair reduction adds the block's (-u_s / t, w_s) to the (alpha, alpha) pass that went
-// first -- the order of the passes depends on t alone.
-extern "C" int gogp_cg_lml_gradient(gogp_handle *h, const double *Xi, int64_t t, int64_t ldxi, double tol, int32_t max_iter,
-                                    double *grad, int64_t len, double *quad, gogp_cg_lml_info *info, gogp_cg_col *cols) {
-  const char *who = "cg_lml_gradient";
-  if (!h) return GOGP_EARG;
-  if (sparse_refusal(h)) return cg_refuse_handle(h, who);
-  if (!Xi || !info) return cg_refuse(h, who, GOGP_EARG, "NULL");
-  if (t < 1 || t > (1 << 20)) return cg_refuse(h, who, GOGP_EARG, "need 1 <= t <= 2^20 probes");
-  if (const char *why = cg_tol_refusal(tol, max_iter)) return cg_refuse(h, who, GOGP_EARG, why);
-  if (grad && len != h->P) return cg_refuse(h, who, GOGP_EARG, "len(grad)");
-  if (!h->cg_have || !h->cg_solved) return cg_refuse(h, who, GOGP_ESTATE, "no solution (gogp_cg_solve)");
-  const int64_t N = h->cg_N, npad = h->cg_npad;
-  const int r = h->cg_rank, D = h->D;
-  const int64_t nx = N + r;
-  if (ldxi < nx) return cg_refuse(h, who, GOGP_EARG, "ldxi is less than N + rank_used");
-  if (grad && N >= (1 << 21)) return cg_refuse(h, who, GOGP_EARG, "the gradient's pair reduction counts its tiles in 32 bits: N < 2^21 (grad == NULL computes the LML alone)");
-  for (int64_t sI = 0; sI < t; ++sI)
-    for (int64_t i = 0; i < nx; ++i)
-      if (!std::isfinite(Xi[sI * ldxi + i])) return cg_refuse(h, who, GOGP_EARG, "non-finite normal");
-  HIPCHK(h, hipSetDevice(h->device));
-  hipStream_t s = h->s;
-  *info = gogp_cg_lml_info();
-  // the counters of the last solve / columns / produce call stay what gogp_cg_last_info reports
-  const int keep_products = h->cg_products, keep_blocks = h->cg_blocks;
-  struct Restore {
-    gogp_handle *h;
-    int p, b;
-    ~Restore() { h->cg_products = p, h->cg_blocks = b; }
-  } restore{h, keep_products, keep_blocks};
-  h->cg_products = h->cg_blocks = 0;
-  const int gblocks = cg_grad_blocks(N);
-  const size_t n_xi = (size_t)CG_MAX_T * (size_t)nx, n_hist = (size_t)2 * (size_t)max_iter * CG_MAX_T;
-  int rc = h->cg_lml.reserve(h, (n_xi + n_hist + CG_MAX_T + NACC + (size_t)gblocks * NACC) * sizeof(double));
-  if (rc == GOGP_OK) rc = h->cg_ks.reserve(h, (size_t)CG_MAX_T * (size_t)npad * sizeof(double));
-  if (rc != GOGP_OK) return rc;
-  double *dXi = h->cg_lml.as<double>(), *dhist = dXi + n_xi, *drho0 = dhist + n_hist, *gout = drho0 + CG_MAX_T;
-  double *gpart = gout + NACC;
-  double *dZ = h->cg_ks.as<double>();
-  // log |P| = sum_i log D_i + log |C|: the diagonal comes down once and is summed in index order
-  std::vector<double> hd((size_t)N);
-  HIPCHK(h, hipMemcpyAsync(hd.data(), h->cg_d, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, s));
-  HIPCHK(h, hipStreamSynchronize(s));
-  double ldp = 0.0;
-  for (int64_t i = 0; i < N; ++i) ldp += log(hd[(size_t)i]);
-  ldp += h->cg_logdet_c;
-  if (grad)
-    launch_cg_grad(s, h->cg_P, D, h->ard_dims, h->cg_X, N, h->cg_alpha, h->cg_alpha, npad, 1, 1.0, gpart, gout, false);
-  std::vector<double> hhist, q((size_t)t);
-  double hrho0[CG_MAX_T];
-  std::vector<gogp_cg_col> lcols((size_t)CG_MAX_T);
-  int ret = GOGP_OK, lmax = 0;
-  std::string first_err;
-  const double *Ls = h->cg_L.as<double>();
-  for (int64_t t0 = 0; t0 < t; t0 += CG_MAX_T) {
-    const int cnt = (int)std::min<int64_t>(CG_MAX_T, t - t0);
-    HIPCHK(h, hipMemcpy2DAsync(dXi, (size_t)nx * sizeof(double), Xi + t0 * ldxi, (size_t)ldxi * sizeof(double),
-                               (size_t)nx * sizeof(double), (size_t)cnt, hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemsetAsync(dZ, 0, (size_t)cnt * npad * sizeof(double), s));
-    launch_cg_probes(s, Ls, h->cg_ldn, N, r, h->cg_d, dXi, nx, npad, cnt, dZ);
-    CgKeep keep;
-    keep.hist = dhist, keep.rho0 = drho0;
-    double *xs = nullptr;
-    rc = cg_block_solve(h, who, dZ, cnt, tol, max_iter, &xs, lcols.data(), (int)t0, &keep);
-    if (rc != GOGP_OK && rc != GOGP_ENOCONV) return rc;
-    if (rc != GOGP_OK && ret == GOGP_OK) ret = rc, first_err = h->err;
-    int mmax = 0;
-    for (int c = 0; c < cnt; ++c) mmax = std::max(mmax, (int)lcols[(size_t)c].iterations);
-    lmax = std::max(lmax, mmax);
-    hhist.resize((size_t)2 * (size_t)std::max(mmax, 1) * CG_MAX_T);
-    if (mmax > 0)
-      HIPCHK(h, hipMemcpyAsync(hhist.data(), dhist, (size_t)2 * mmax * CG_MAX_T * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipMemcpyAsync(hrho0, drho0, sizeof hrho0, hipMemcpyDeviceToHost, s));
-    if (grad)
-      launch_cg_grad(s, h->cg_P, D, h->ard_dims, h->cg_X, N, xs, keep.w, npad, cnt, -1.0 / (double)t, gpart, gout, true);
-    HIPCHK(h, hipStreamSynchronize(s));
-    HIPCHK(h, hipGetLastError());
-    for (int c = 0; c < cnt; ++c) {
-      const int m = lcols[(size_t)c].iterations;
-      q[(size_t)(t0 + c)] = cg_lanczos_quadrature(hhist.data() + c, hhist.data() + CG_MAX_T + c, 2 * CG_MAX_T, m, hrho0[c]);
-      if (cols) cols[t0 + c] = lcols[(size_t)c];
-    }
-  }
-  double qsum = 0.0;
-  for (int64_t c = 0; c < t; ++c) qsum += q[(size_t)c];
-  const double qmean = qsum / (double)t;
-  double var = 0.0;
-  for (int64_t c = 0; c < t; ++c) var += (q[(size_t)c] - qmean) * (q[(size_t)c] - qmean);
-  info->logdet_precond = ldp;
-  info->logdet = ldp + qmean;
-  info->logdet_stderr = t > 1 ? sqrt(var / (double)(t - 1)) / sqrt((double)t) : 0.0;
-  info->yt_alpha = h->cg_yta;
-  info->lml = -0.5 * h->cg_yta - 0.5 * info->logdet - 0.5 * (double)N * log(2.0 * M_PI);
-  info->probes = (int32_t)t;
-  info->blocks = h->cg_blocks;
-  info->products = h->cg_products;
-  info->lanczos_max = lmax;
-  if (quad)
-    for (int64_t c = 0; c < t; ++c) quad[c] = q[(size_t)c];
-  if (grad) {
-    double acc[NACC];
-    HIPCHK(h, hipMemcpyAsync(acc, gout, sizeof acc, hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipStreamSynchronize(s));
-    for (int64_t i = 0; i < len; ++i) grad[i] = 0.0;
-    assemble_gradient(h, acc, h->cg_dnoise, grad);
-  }
-  if (ret != GOGP_OK) h->err = first_err;
-  return ret;
-}
-
-// ---- Vecchia's approximation (vecchia.hip) -----------------------------------------------------------------------------
-// include/gogp_hip.h states the approximation and the table; DESIGN.md section 4, "Vecchia".  One kernel does all the
-// work; everything runs on the handle's main stream with buffers of the family's own, and the parameters are a copy of
-// the family's own, so that devP keeps what the last dense evaluation uploaded.
-static void vecchia_free(gogp_handle *h) {
-  VecchiaState &vc = h->vc;
-  for (double *q : {vc.X, vc.y, vc.v}) (void)hipFree(q);
-  (void)hipFree(vc.nbr);
-  (void)hipFree(vc.P);
-  vc.small.release();
-  vc.terms.release();
-  vc.prod.release();
-  vc.knn.release();
-  vc = VecchiaState();
-}
-
-// the first row of the table that breaks the format of include/gogp_hip.h, or -1
-static int64_t vecchia_bad_row(const int32_t *nbr, int64_t rows, int32_t m, int64_t n, int causal) {
-  for (int64_t i = 0; i < rows; ++i) {
-    const int32_t *r = nbr + i * m;
-    const int64_t lim = causal ? i : n;
-    bool pad = false;
-    for (int32_t a = 0; a < m; ++a) {
-      if (r[a] == -1) {
-        pad = true;
-        continue;
-      }
-      if (pad || r[a] < 0 || (int64_t)r[a] >= lim) return i;
-      for (int32_t b = 0; b < a; ++b)
-        if (r[b] == r[a]) return i;
-    }
-  }
-  return -1;
-}
-
-extern "C" int gogp_vecchia_check(const int32_t *nbr, int64_t rows, int32_t m, int64_t n, int causal) {
-  if (m < 0 || m > GOGP_VECCHIA_MAX_M || rows < 0 || n < 0 || (causal && rows > n)) return GOGP_EARG;
-  if (rows > 0 && m > 0 && !nbr) return GOGP_EARG;
-  return vecchia_bad_row(nbr, rows, m, n, causal) < 0 ? GOGP_OK : GOGP_EARG;
-}
-
-// gogp_vecchia_check with the first offending row named in the handle's error text
-static int vecchia_check_named(gogp_handle *h, const char *who, const int32_t *nbr, int64_t rows, int32_t m, int64_t n,
-                               int causal) {
-  if (gogp_vecchia_check(nbr, rows, m, n, causal) == GOGP_OK) return GOGP_OK;
-  char buf[320];
-  const int64_t bad = (nbr && m >= 0 && m <= GOGP_VECCHIA_MAX_M && rows >= 0) ? vecchia_bad_row(nbr, rows, m, n, causal) : -1;
-  if (bad >= 0)
-    snprintf(buf, sizeof buf,
-             "%s: row %lld of the table is not %s: distinct indices %s, then -1 padding (gogp_vecchia_check)", who,
-             (long long)bad, causal ? "causal" : "valid", causal ? "below the row's own" : "in [0, N)");
-  else
-    snprintf(buf, sizeof buf, "%s: need a table of rows x m int32 with 0 <= m <= %d (gogp_vecchia_check)", who,
-             GOGP_VECCHIA_MAX_M);
-  return fail(h, GOGP_EARG, buf);
-}
-
-// the small device buffers behind an observe: the value, the info word, the slot sums, then per workgroup the value, the
-// failure word and the partial row
-struct VecchiaSmall {
-  double *value, *gout, *vpart, *partials;
-  long long *info, *fpart;
-};
-static size_t vecchia_small_layout(char *base, int blocks, VecchiaSmall *b) {
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char *q = base ? base + off : nullptr;
-    off += (bytes + 255) / 256 * 256;
-    return q;
-  };
-  b->value = reinterpret_cast<double *>(take(sizeof(double)));
-  b->info = reinterpret_cast<long long *>(take(sizeof(long long)));
-  b->gout = reinterpret_cast<double *>(take(NACC * sizeof(double)));
-  b->vpart = reinterpret_cast<double *>(take((size_t)blocks * sizeof(double)));
-  b->fpart = reinterpret_cast<long long *>(take((size_t)blocks * sizeof(long long)));
-  b->partials = reinterpret_cast<double *>(take((size_t)blocks * NACC * sizeof(double)));
-  return off;
-}
-
-extern "C" int gogp_vecchia_set_data(gogp_handle *h, const double *X, const double *y, const double *v, int64_t N,
-                                     const int32_t *nbr, int32_t m) {
-  const char *who = "vecchia_set_data";
-  if (!h) return GOGP_EARG;
-  if (N == 0 && !X && !y && !v && !nbr) {  // clear
-    HIPCHK(h, hipSetDevice(h->device));
-    vecchia_free(h);
-    return GOGP_OK;
-  }
-  if (sparse_refusal(h)) return cg_refuse_handle(h, who);
-  if (N < 1 || !X || !y) return cg_refuse(h, who, GOGP_EARG, "need X, y and N >= 1 (N == 0 with NULLs clears)");
-  if (N > INT32_MAX) return cg_refuse(h, who, GOGP_EARG, "the table's indices are int32: N <= 2^31 - 1");
-  if (const int rc = vecchia_check_named(h, who, nbr, N, m, N, 1)) return rc;
-  const int D = h->D;
-  for (int64_t i = 0; i < N * D; ++i)
-    if (!std::isfinite(X[i])) return cg_refuse(h, who, GOGP_EARG, "non-finite input");
-  for (int64_t i = 0; i < N; ++i)
-    if (!std::isfinite(y[i])) return cg_refuse(h, who, GOGP_EARG, "non-finite output");
-  if (v)
-    for (int64_t i = 0; i < N; ++i)
-      if (!std::isfinite(v[i]) || v[i] < 0.0) return cg_refuse(h, who, GOGP_EARG, "noise variances must be finite and >= 0");
-  HIPCHK(h, hipSetDevice(h->device));
-  if (h->s) HIPCHK(h, hipStreamSynchronize(h->s));
-  vecchia_free(h);
-  VecchiaState &vc = h->vc;
-  const size_t xb = (size_t)N * D * sizeof(double), vb = (size_t)N * sizeof(double);
-  const size_t tb = std::max<size_t>((size_t)N * (size_t)m * sizeof(int32_t), 256);
-  hipStream_t s = h->s;
-  hipError_t e = hipMalloc(&vc.X, xb);
-  if (e == hipSuccess) e = hipMalloc(&vc.y, vb);
-  if (e == hipSuccess && v) e = hipMalloc(&vc.v, vb);
-  if (e == hipSuccess) e = hipMalloc(&vc.nbr, tb);
-  if (e == hipSuccess) e = hipMalloc(&vc.P, sizeof(DevParams));
-  if (e == hipSuccess) e = hipMemcpyAsync(vc.X, X, xb, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(vc.y, y, vb, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess && v) e = hipMemcpyAsync(vc.v, v, vb, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess && m > 0)
-    e = hipMemcpyAsync(vc.nbr, nbr, (size_t)N * (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (e != hipSuccess) {
-    vecchia_free(h);
-    HIPCHK(h, e);
-  }
-  vc.N = N;
-  vc.m = m;
-  vc.have = true;
-  return GOGP_OK;
-}
-
-// One pass of the kernel over the stored data: the value's (grad false: terms, *value, *info) or the gradient's (the
-// slot sums into acc; nothing else is written).  The stream is idle on return.
-static int vecchia_run(gogp_handle *h, bool grad, double *dterms, double *value, long long *info, double *acc) {
-  VecchiaState &vc = h->vc;
-  hipStream_t s = h->s;
-  const int blocks = vecchia_blocks(vc.N);
-  VecchiaSmall sm;
-  const size_t bytes = vecchia_small_layout(nullptr, blocks, &sm);
-  if (const int rc = vc.small.reserve(h, bytes)) return rc;
-  vecchia_small_layout(vc.small.as<char>(), blocks, &sm);
-  launch_vecchia_observe(s, vc.P, h->D, h->ard_dims, vc.X, vc.y, vc.v, vc.N, vc.nbr, vc.m, dterms,
-                         grad ? sm.partials : nullptr, sm.vpart, sm.fpart, sm.gout, grad ? nullptr : sm.value,
-                         grad ? nullptr : sm.info);
-  if (grad) {
-    HIPCHK(h, hipMemcpyAsync(acc, sm.gout, NACC * sizeof(double), hipMemcpyDeviceToHost, s));
-  } else {
-    HIPCHK(h, hipMemcpyAsync(value, sm.value, sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipMemcpyAsync(info, sm.info, sizeof(long long), hipMemcpyDeviceToHost, s));
-  }
-  HIPCHK(h, hipStreamSynchronize(s));
-  HIPCHK(h, hipGetLastError());
-  return GOGP_OK;
-}
-
-static int vecchia_notpd(gogp_handle *h, const char *who, long long info, const char *what) {
-  char buf[240];
-  snprintf(buf, sizeof buf, "%s: the block of %s %lld has a pivot that is not positive and finite", who, what, info - 1);
-  h->notpd = (int64_t)(info - 1);
-  return fail(h, GOGP_ENOTPD, buf);
-}
-
-extern "C" int gogp_vecchia_observe(gogp_handle *h, const double *x, int64_t len, double *lml, double *terms) {
-  const char *who = "vecchia_observe";
-  if (!h) return GOGP_EARG;
-  if (!x || !lml) return cg_refuse(h, who, GOGP_EARG, "NULL");
-  if (sparse_refusal(h)) return cg_refuse_handle(h, who);
-  if (len != h->P) return cg_refuse(h, who, GOGP_EARG, "len(x)");
-  for (int64_t i = 0; i < len; ++i)
-    if (!std::isfinite(x[i])) return cg_refuse(h, who, GOGP_EARG, "non-finite parameter");
-  VecchiaState &vc = h->vc;
-  if (!vc.have) return cg_refuse(h, who, GOGP_ESTATE, "no data (gogp_vecchia_set_data)");
-  std::vector<double> th(h->P > 0 ? h->P : 1);
-  for (int i = 0; i < h->P; ++i) th[i] = exp(x[i]);
-  if (const char *why = theta_refusal(h, th.data(), th.data() + h->ns)) return cg_refuse(h, who, GOGP_EARG, why);
-  DevParams hp;
-  fill_params_theta(h, th.data(), th.data() + h->ns, hp);
-  HIPCHK(h, hipSetDevice(h->device));
-  hipStream_t s = h->s;
-  vc.observed = false;
-  vc.dnoise = hp.dnoise;
-  HIPCHK(h, hipMemcpyAsync(vc.P, &hp, sizeof hp, hipMemcpyHostToDevice, s));
-  HIPCHK(h, hipStreamSynchronize(s));  // hp is a local
-  double *dterms = nullptr;
-  if (terms) {
-    if (const int rc = vc.terms.reserve(h, (size_t)vc.N * 3 * sizeof(double))) return rc;
-    dterms = vc.terms.as<double>();
-  }
-  double value = 0.0;
-  long long info = 0;
-  if (const int rc = vecchia_run(h, false, dterms, &value, &info, nullptr)) return rc;
-  if (terms) HIPCHK(h, hipMemcpy(terms, dterms, (size_t)vc.N * 3 * sizeof(double), hipMemcpyDeviceToHost));
-  if (info != 0) {
-    *lml = NAN;
-    return vecchia_notpd(h, who, info, "row");
-  }
-  *lml = value;
-  vc.observed = true;
-  return GOGP_OK;
-}
-
-extern "C" int gogp_vecchia_gradient(gogp_handle *h, double *grad, int64_t len) {
-  const char *who = "vecchia_gradient";
-  if (!h) return GOGP_EARG;
-  if (!grad) return cg_refuse(h, who, GOGP_EARG, "NULL");
-  if (sparse_refusal(h)) return cg_refuse_handle(h, who);
-  if (len != h->P) return cg_refuse(h, who, GOGP_EARG, "len(grad)");
-  VecchiaState &vc = h->vc;
-  if (!vc.have || !vc.observed) return cg_refuse(h, who, GOGP_ESTATE, "nothing observed (gogp_vecchia_observe)");
-  HIPCHK(h, hipSetDevice(h->device));
-  double acc[NACC];
-  if (const int rc = vecchia_run(h, true, nullptr, nullptr, nullptr, acc)) return rc;
-  for (int64_t i = 0; i < len; ++i) grad[i] = 0.0;
-  assemble_gradient(h, acc, vc.dnoise, grad);
-  return GOGP_OK;
-}
-
-extern "C" int gogp_vecchia_produce(gogp_handle *h, const double *Z, int64_t mz, const int32_t *nbrz, double *mu,
-                                    double *sigma) {
-  const char *who = "vecchia_produce";
-  if (!h) return GOGP_EARG;
-  if (sparse_refusal(h)) return cg_refuse_handle(h, who);
-  if (mz < 0 || (mz > 0 && (!Z || !mu))) return cg_refuse(h, who, GOGP_EARG, "need Z and mu for mz > 0, mz >= 0");
-  VecchiaState &vc = h->vc;
-  if (!vc.have || !vc.observed) return cg_refuse(h, who, GOGP_ESTATE, "nothing observed (gogp_vecchia_observe)");
-  if (const int rc = vecchia_check_named(h, who, nbrz, mz, vc.m, vc.N, 0)) return rc;
-  const int D = h->D, m = vc.m;
-  for (int64_t i = 0; i < mz * D; ++i)
-    if (!std::isfinite(Z[i])) return cg_refuse(h, who, GOGP_EARG, "non-finite test point");
-  if (mz == 0) return GOGP_OK;
-  HIPCHK(h, hipSetDevice(h->device));
-  hipStream_t s = h->s;
-  const int blocks = vecchia_blocks(mz);
-  auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-  const size_t zb = up((size_t)mz * D * sizeof(double)), vb = up((size_t)mz * sizeof(double));
-  const size_t tb = up(std::max<size_t>((size_t)mz * (size_t)m * sizeof(int32_t), 4)), fb = up((size_t)blocks * sizeof(long long));
-  if (const int rc = vc.prod.reserve(h, zb + 2 * vb + tb + fb + 256)) return rc;
-  char *base = vc.prod.as<char>();
-  double *dZ = reinterpret_cast<double *>(base), *dmu = reinterpret_cast<double *>(base + zb);
-  double *dsig = reinterpret_cast<double *>(base + zb + vb);
-  int *dnb = reinterpret_cast<int *>(base + zb + 2 * vb);
-  long long *dfp = reinterpret_cast<long long *>(base + zb + 2 * vb + tb), *dinfo = dfp + blocks;
-  HIPCHK(h, hipMemcpyAsync(dZ, Z, (size_t)mz * D * sizeof(double), hipMemcpyHostToDevice, s));
-  if (m > 0) HIPCHK(h, hipMemcpyAsync(dnb, nbrz, (size_t)mz * (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, s));
-  launch_vecchia_produce(s, vc.P, D, vc.X, vc.y, vc.v, dZ, mz, dnb, m, dmu, sigma ? dsig : nullptr, dfp, dinfo);
-  long long info = 0;
-  HIPCHK(h, hipMemcpyAsync(mu, dmu, (size_t)mz * sizeof(double), hipMemcpyDeviceToHost, s));
-  if (sigma) HIPCHK(h, hipMemcpyAsync(sigma, dsig, (size_t)mz * sizeof(double), hipMemcpyDeviceToHost, s));
-  HIPCHK(h, hipMemcpyAsync(&info, dinfo, sizeof info, hipMemcpyDeviceToHost, s));
-  HIPCHK(h, hipStreamSynchronize(s));
-  HIPCHK(h, hipGetLastError());
-  if (info != 0) return vecchia_notpd(h, who, info, "test point");
-  return GOGP_OK;
-}
-
-// ---- Vecchia: neighbour tables built on the device (vecchia_knn.hip) ------------------------------------------------------
-// The exact search of gogp_amd/vecchia.py (nearest / nearest_to) on the handle's main stream; DESIGN.md section 4,
-// "Vecchia: neighbour tables on the device".  The resident forms keep the table, the scaled copy of X and the partial
-// lists on the device: nothing but the length scales crosses the bus.
-static int vecchia_knn_args(gogp_handle *h, const char *who, const double *lengths, int32_t m) {
-  if (m < 0 || m > GOGP_VECCHIA_MAX_M) return cg_refuse(h, who, GOGP_EARG, "m: need 0 <= m <= 63 conditioning rows");
-  if (lengths)
-    for (int d = 0; d < h->D; ++d)
-      if (!(lengths[d] > 0.0) || !std::isfinite(lengths[d]))
-        return cg_refuse(h, who, GOGP_EARG, "lengths: every length scale must be positive and finite");
-  return GOGP_OK;
-}
-
-// the scratch of one search: the lengths, the scaled copies of X and Z, the partial lists of a split search
-struct VecchiaKnnBufs {
-  double *len, *Xs, *Zs;
-  void *ws;
-};
-static size_t vecchia_knn_layout(char *base, int D, int64_t N, int64_t mz, size_t ws_bytes, VecchiaKnnBufs *b) {
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char *q = base ? base + off : nullptr;
-    off += (bytes + 255) / 256 * 256;
-    return q;
-  };
-  b->len = reinterpret_cast<double *>(take(GOGP_MAX_NDIM * sizeof(double)));
-  b->Xs = reinterpret_cast<double *>(take((size_t)N * D * sizeof(double)));
-  b->Zs = reinterpret_cast<double *>(take((size_t)mz * D * sizeof(double)));
-  b->ws = take(ws_bytes);
-  return off;
-}
-static size_t vecchia_knn_bytes(int D, int64_t N, int64_t mz, int m) {
-  VecchiaKnnBufs b;
-  return vecchia_knn_layout(nullptr, D, N, mz, vknn_plan(mz > 0 ? mz : N, N, m).ws_bytes, &b);
-}
-
-// The launches of one search on device rows: dX (N x D) and dZ (mz x D; nullptr: the causal table of dX) into dnbr, with
-// vecchia_knn_bytes of scratch at base.  lengths: the host's, or nullptr.  The caller synchronises before it returns.
-static int vecchia_knn_launch(gogp_handle *h, char *base, const double *dX, int64_t N, const double *dZ, int64_t mz,
-                              const double *lengths, int m, int *dnbr) {
-  hipStream_t s = h->s;
-  const int D = h->D;
-  const int64_t targets = dZ ? mz : N;
-  VecchiaKnnBufs b;
-  vecchia_knn_layout(base, D, N, dZ ? mz : 0, vknn_plan(targets, N, m).ws_bytes, &b);
-  if (lengths) HIPCHK(h, hipMemcpyAsync(b.len, lengths, (size_t)D * sizeof(double), hipMemcpyHostToDevice, s));
-  launch_vknn_scale(s, dX, N, D, lengths ? b.len : nullptr, b.Xs);
-  if (dZ) launch_vknn_scale(s, dZ, mz, D, lengths ? b.len : nullptr, b.Zs);
-  launch_vknn(s, b.Xs, N, dZ ? b.Zs : nullptr, targets, D, m, 0, 0, b.ws, dnbr, nullptr);
-  return GOGP_OK;
-}
-
-extern "C" int gogp_vecchia_neighbours(gogp_handle *h, const double *X, int64_t N, const double *Z, int64_t mz,
-                                       const double *lengths, int32_t m, int32_t *nbr) {
-  const char *who = "vecchia_neighbours";
-  if (!h) return GOGP_EARG;
-  if (sparse_refusal(h)) return cg_refuse_handle(h, who);
-  if (N < 1 || !X) return cg_refuse(h, who, GOGP_EARG, "need X and N >= 1");
-  if (N > INT32_MAX) return cg_refuse(h, who, GOGP_EARG, "N: the table's indices are int32: N <= 2^31 - 1");
-  if (Z ? mz < 0 : mz != 0) return cg_refuse(h, who, GOGP_EARG, "mz: the rows of Z, 0 without Z");
-  if (const int rc = vecchia_knn_args(h, who, lengths, m)) return rc;
-  const int64_t targets = Z ? mz : N;
-  if (targets == 0 || m == 0) return GOGP_OK;
-  if (!nbr) return cg_refuse(h, who, GOGP_EARG, "nbr: NULL");
-  const int D = h->D;
-  HIPCHK(h, hipSetDevice(h->device));
-  hipStream_t s = h->s;
-  // buffers of the call's own: nothing of the handle changes
-  auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-  const size_t xb = up((size_t)N * D * sizeof(double)), zb = up((size_t)(Z ? mz : 0) * D * sizeof(double));
-  const size_t tb = up((size_t)targets * (size_t)m * sizeof(int32_t));
-  Workspace w;
-  struct Release {
-    Workspace &w;
-    ~Release() { w.release(); }
-  } release{w};
-  if (const int rc = w.reserve(h, xb + zb + tb + vecchia_knn_bytes(D, N, Z ? mz : 0, m))) return rc;
-  char *base = w.as<char>();
-  double *dX = reinterpret_cast<double *>(base), *dZ = Z ? reinterpret_cast<double *>(base + xb) : nullptr;
-  int *dnb = reinterpret_cast<int *>(base + xb + zb);
-  HIPCHK(h, hipMemcpyAsync(dX, X, (size_t)N * D * sizeof(double), hipMemcpyHostToDevice, s));
-  if (Z) HIPCHK(h, hipMemcpyAsync(dZ, Z, (size_t)mz * D * sizeof(double), hipMemcpyHostToDevice, s));
-  if (const int rc = vecchia_knn_launch(h, base + xb + zb + tb, dX, N, dZ, mz, lengths, m, dnb)) return rc;
-  HIPCHK(h, hipMemcpyAsync(nbr, dnb, (size_t)targets * (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  HIPCHK(h, hipStreamSynchronize(s));
-  HIPCHK(h, hipGetLastError());
-  return GOGP_OK;
-}
-
-// the resident table from the resident X under `lengths` (nullptr: unscaled); the last observe is dropped
-static int vecchia_rebuild(gogp_handle *h, const double *lengths) {
-  VecchiaState &vc = h->vc;
-  if (const int rc = vc.knn.reserve(h, vecchia_knn_bytes(h->D, vc.N, 0, vc.m))) return rc;
-  vc.observed = false;
-  if (const int rc = vecchia_knn_launch(h, vc.knn.as<char>(), vc.X, vc.N, nullptr, 0, lengths, vc.m, vc.nbr)) return rc;
-  HIPCHK(h, hipStreamSynchronize(h->s));
-  HIPCHK(h, hipGetLastError());
-  vc.built_here = true;
-  vc.scaled = lengths != nullptr;
-  for (int d = 0; d < h->D; ++d) vc.lengths[d] = lengths ? lengths[d] : 1.0;
-  return GOGP_OK;
-}
-
-extern "C" int gogp_vecchia_set_data_nearest(gogp_handle *h, const double *X, const double *y, const double *v, int64_t N,
-                                             const double *lengths, int32_t m) {
-  const char *who = "vecchia_set_data_nearest";
-  if (!h) return GOGP_EARG;
-  if (sparse_refusal(h)) return cg_refuse_handle(h, who);
-  if (N < 1 || !X || !y) return cg_refuse(h, who, GOGP_EARG, "need X, y and N >= 1");
-  if (N > INT32_MAX) return cg_refuse(h, who, GOGP_EARG, "N: the table's indices are int32: N <= 2^31 - 1");
-  if (const int rc = vecchia_knn_args(h, who, lengths, m)) return rc;
-  // the upload and its checks are gogp_vecchia_set_data's, with an empty table; the table proper is then built in place
-  if (const int rc = gogp_vecchia_set_data(h, X, y, v, N, nullptr, 0)) return rc;
-  VecchiaState &vc = h->vc;
-  if (m > 0) {
-    (void)hipFree(vc.nbr);
-    vc.nbr = nullptr;
-    const hipError_t e = hipMalloc(&vc.nbr, (size_t)N * (size_t)m * sizeof(int32_t));
-    if (e != hipSuccess) {
-      vecchia_free(h);
-      HIPCHK(h, e);
-    }
-  }
-  vc.m = m;
-  if (const int rc = vecchia_rebuild(h, lengths)) {
-    const auto keep = h->err;
-    vecchia_free(h);
-    h->err = keep;
-    return rc;
-  }
-  return GOGP_OK;
-}
-
-extern "C" int gogp_vecchia_reneighbour(gogp_handle *h, const double *lengths) {
-  const char *who = "vecchia_reneighbour";
-  if (!h) return GOGP_EARG;
-  if (sparse_refusal(h)) return cg_refuse_handle(h, who);
-  VecchiaState &vc = h->vc;
-  if (!vc.have) return cg_refuse(h, who, GOGP_ESTATE, "no data (gogp_vecchia_set_data, gogp_vecchia_set_data_nearest)");
-  if (const int rc = vecchia_knn_args(h, who, lengths, vc.m)) return rc;
-  HIPCHK(h, hipSetDevice(h->device));
-  return vecchia_rebuild(h, lengths);
-}
-
-extern "C" int gogp_vecchia_get_neighbours(gogp_handle *h, int32_t *nbr) {
-  const char *who = "vecchia_get_neighbours";
-  if (!h) return GOGP_EARG;
-  if (sparse_refusal(h)) return cg_refuse_handle(h, who);
-  VecchiaState &vc = h->vc;
-  if (!vc.have) return cg_refuse(h, who, GOGP_ESTATE, "no data (gogp_vecchia_set_data, gogp_vecchia_set_data_nearest)");
-  if (vc.m == 0) return GOGP_OK;
-  if (!nbr) return cg_refuse(h, who, GOGP_EARG, "nbr: NULL");
-  HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, hipMemcpyAsync(nbr, vc.nbr, (size_t)vc.N * (size_t)vc.m * sizeof(int32_t), hipMemcpyDeviceToHost, h->s));
-  HIPCHK(h, hipStreamSynchronize(h->s));
-  return GOGP_OK;
-}
-
-extern "C" int gogp_vecchia_produce_nearest(gogp_handle *h, const double *Z, int64_t mz, const double *lengths, double *mu,
-                                            double *sigma, int32_t *nbrz) {
-  const char *who = "vecchia_produce_nearest";
-  if (!h) return GOGP_EARG;
-  if (sparse_refusal(h)) return cg_refuse_handle(h, who);
-  if (mz < 0 || (mz > 0 && (!Z || !mu))) return cg_refuse(h, who, GOGP_EARG, "need Z and mu for mz > 0, mz >= 0");
-  VecchiaState &vc = h->vc;
-  if (!vc.have || !vc.observed) return cg_refuse(h, who, GOGP_ESTATE, "nothing observed (gogp_vecchia_observe)");
-  if (!lengths && !vc.built_here)
-    return cg_refuse(h, who, GOGP_ESTATE, "lengths: the resident table is the caller's, so it has none to take");
-  if (const int rc = vecchia_knn_args(h, who, lengths, vc.m)) return rc;
-  const double *len = lengths ? lengths : vc.scaled ? vc.lengths : nullptr;
-  const int D = h->D, m = vc.m;
-  for (int64_t i = 0; i < mz * D; ++i)
-    if (!std::isfinite(Z[i])) return cg_refuse(h, who, GOGP_EARG, "non-finite test point");
-  if (mz == 0) return GOGP_OK;
-  HIPCHK(h, hipSetDevice(h->device));
-  hipStream_t s = h->s;
-  // gogp_vecchia_produce's buffers, with the table found on the device in the place of the caller's
-  const int blocks = vecchia_blocks(mz);
-  auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-  const size_t zb = up((size_t)mz * D * sizeof(double)), vb = up((size_t)mz * sizeof(double));
-  const size_t tb = up(std::max<size_t>((size_t)mz * (size_t)m * sizeof(int32_t), 4)), fb = up((size_t)blocks * sizeof(long long));
-  if (const int rc = vc.prod.reserve(h, zb + 2 * vb + tb + fb + 256)) return rc;
-  if (const int rc = vc.knn.reserve(h, vecchia_knn_bytes(D, vc.N, mz, m))) return rc;
-  char *base = vc.prod.as<char>();
-  double *dZ = reinterpret_cast<double *>(base), *dmu = reinterpret_cast<double *>(base + zb);
-  double *dsig = reinterpret_cast<double *>(base + zb + vb);
-  int *dnb = reinterpret_cast<int *>(base + zb + 2 * vb);
-  long long *dfp = reinterpret_cast<long long *>(base + zb + 2 * vb + tb), *dinfo = dfp + blocks;
-  HIPCHK(h, hipMemcpyAsync(dZ, Z, (size_t)mz * D * sizeof(double), hipMemcpyHostToDevice, s));
-  if (const int rc = vecchia_knn_launch(h, vc.knn.as<char>(), vc.X, vc.N, dZ, mz, len, m, dnb)) return rc;
-  launch_vecchia_produce(s, vc.P, D, vc.X, vc.y, vc.v, dZ, mz, dnb, m, dmu, sigma ? dsig : nullptr, dfp, dinfo);
-  long long info = 0;
-  HIPCHK(h, hipMemcpyAsync(mu, dmu, (size_t)mz * sizeof(double), hipMemcpyDeviceToHost, s));
-  if (sigma) HIPCHK(h, hipMemcpyAsync(sigma, dsig, (size_t)mz * sizeof(double), hipMemcpyDeviceToHost, s));
-  if (nbrz && m > 0) HIPCHK(h, hipMemcpyAsync(nbrz, dnb, (size_t)mz * (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  HIPCHK(h, hipMemcpyAsync(&info, dinfo, sizeof info, hipMemcpyDeviceToHost, s));
-  HIPCHK(h, hipStreamSynchronize(s));
-  HIPCHK(h, hipGetLastError());
-  if (info != 0) return vecchia_notpd(h, who, info, "test point");
-  return GOGP_OK;
 }
 
 // ---- non-Gaussian likelihoods by the Laplace approximation (laplace.hip) -----------------------------------------------
@@ -6426,7 +5372,7 @@ extern "C" int gogp_set_option(gogp_handle *h, const char *name, int64_t value) 
   }
   if (strcmp(name, "cg_check") == 0) {  // gogp_cg_*: iterations between two looks at the status word; no result depends on it
     if (value < 1 || value > 1024) return fail(h, GOGP_EARG, "cg_check must be 1..1024");
-    h->cg_check = (int)value;
+    h->cg.check = (int)value;
     return GOGP_OK;
   }
   if (strcmp(name, "laplace_max_iter") == 0) {  // gogp_laplace_observe: Newton steps at the most

@@ -1,4 +1,4 @@
-// cg.hip -- the kernels of the iterative exact GP (gogp_cg_*; api.hip orchestrates; include/gogp_hip.h states the
+// cg.hip -- the kernels of the iterative exact GP (gogp_cg_*; cg_api.hip orchestrates; include/gogp_hip.h states the
 // iteration; DESIGN.md section 4, "Iterative (CG)"): matrix-free preconditioned conjugate gradients on
 // K^ = k(X, X) + sigma^2 I + diag(v), up to CG_MAX_T = 64 systems in lock-step.
 //

@@ -1,5 +1,5 @@
-// handle.h -- the handle behind the C ABI, shared by api.hip (single-GPU orchestration)
-// and dist2d.hip (2-D block-cyclic sharded evaluation).  Private to libgogp_hip.so.
+// handle.h -- the handle behind the C ABI, shared by api.hip (single-GPU orchestration), cg_api.hip and vecchia_api.hip
+// (two call families of their own) and dist2d.hip (2-D block-cyclic sharded evaluation).  Private to libgogp_hip.so.
 #pragma once
 #include <algorithm>
 #include <array>
@@ -61,9 +61,43 @@ struct Workspace {
   T *as() const { return static_cast<T *>(p); }
 };
 
-// The state of the Vecchia calls (api.hip: gogp_vecchia_*).  Device memory: X, y and v (N (D + 2) doubles), 4 N m bytes of
-// table, the terms (3 N doubles, from the first observe that asks for them) and at most VECCHIA_BLOCKS_MAX partial rows
-// with the workgroups' values and failure words.
+// The state of the iterative calls (cg_api.hip: gogp_cg_*): a data set and a copy of the parameters of its own, resident, so
+// that devP keeps what the last evaluation uploaded.  (common.h's CgState is a lock-step block's per-column state.)
+struct CgHandleState {
+  double *X = nullptr, *y = nullptr, *v = nullptr;  // N x D (+ slack, npad rows), npad, npad (nullptr: no variances)
+  double *d = nullptr, *dis = nullptr, *alpha = nullptr;  // D, D^-1/2, alpha: npad doubles each
+  DevParams *P = nullptr;
+  int64_t N = 0, npad = 0;
+  bool have = false, solved = false;
+  int rank = 0, rp = 0;         // columns of the factor in use and their count rounded up to 16
+  int64_t ldn = 0;
+  int check = 8;                // option "cg_check": iterations between two looks at the status word
+  int products = 0, blocks = 0;  // counters of the call in progress (gogp_cg_last_info)
+  double yta = 0.0;
+  double vmin = 0.0;            // the smallest noise variance given (0 without variances)
+  Workspace L;                  // Ls = D^-1/2 L, column-major, `rank` columns of ldn doubles
+  Workspace small;              // C^-1 (rp x rp), W and Y (CG_MAX_T x rp each), the per-column state
+  Workspace vec;                // a block's six vectors, the dots' partials and results
+  Workspace part;               // the slab partials of the product and of the skinny transposed product
+  Workspace ks;                 // gogp_cg_produce: 64 rows of k*, the test points, prior, q, mu
+  double logdet_c = 0.0;        // log |C| of the last solve's capacitance matrix (0 at rank 0)
+  double dnoise = 0.0;          // d noise_var / d log(noise parameter) at the last solve's theta
+  Workspace lml;                // gogp_cg_lml_gradient: a block's rows of Xi, the a / beta history, rho0, slot sums and partials
+  void release() {  // the option stays, and so do the last solve's counters and scalars (gogp_cg_last_info reports them)
+    for (double *q : {X, y, v, d, dis, alpha}) (void)hipFree(q);
+    (void)hipFree(P);
+    X = y = v = d = dis = alpha = nullptr;
+    P = nullptr;
+    for (Workspace *w : {&L, &small, &vec, &part, &ks, &lml}) w->release();
+    N = npad = 0;
+    have = solved = false;
+    rank = rp = 0;
+  }
+};
+
+// The state of the Vecchia calls (vecchia_api.hip: gogp_vecchia_*).  Device memory: X, y and v (N (D + 2) doubles), 4 N m
+// bytes of table, the terms (3 N doubles, from the first observe that asks for them) and at most VECCHIA_BLOCKS_MAX partial
+// rows with the workgroups' values and failure words.
 struct VecchiaState {
   double *X = nullptr, *y = nullptr, *v = nullptr;  // N x D, N, N (nullptr: no variances)
   int *nbr = nullptr;                               // N x m, row-major
@@ -80,6 +114,13 @@ struct VecchiaState {
   bool built_here = false, scaled = false;
   double lengths[GOGP_MAX_NDIM] = {};
   Workspace knn;        // a search's scratch: the lengths, the scaled copies of X and Z, the partial lists (vknn_plan)
+  void release() {  // leaves the state of a new handle
+    for (double *q : {X, y, v}) (void)hipFree(q);
+    (void)hipFree(nbr);
+    (void)hipFree(P);
+    for (Workspace *w : {&small, &terms, &prod, &knn}) w->release();
+    *this = VecchiaState();
+  }
 };
 
 // What an evaluation leaves in the handle; a candidates call saves it and puts it back
@@ -282,29 +323,9 @@ struct gogp_handle : EvalBufs, EvalState {
   Workspace sp_mws;                // state of the multi observe, sized by gogp_sparse_multi_set_outputs (api.hip: SparseMultiBufs)
   Workspace sp_mscr;               // scratch sized by the chunk: the partials of launch_sparse_xty, the padded chunk of Y
   Workspace sp_mmu;                // gogp_sparse_multi_produce: mpad x 128 means
-  // the iterative exact GP (gogp_cg_*, cg.hip): a data set of its own, resident; nothing of the handle's other state is
-  // touched (the parameters too are a copy of its own, so that devP keeps what the last evaluation uploaded)
-  double *cg_X = nullptr, *cg_y = nullptr, *cg_v = nullptr;  // N x D (+ slack, npad rows), npad, npad (nullptr: no variances)
-  double *cg_d = nullptr, *cg_dis = nullptr, *cg_alpha = nullptr;  // D, D^-1/2, alpha: npad doubles each
-  DevParams *cg_P = nullptr;
-  int64_t cg_N = 0, cg_npad = 0;
-  bool cg_have = false, cg_solved = false;
-  int cg_rank = 0, cg_rp = 0;      // columns of the factor in use and their count rounded up to 16
-  int64_t cg_ldn = 0;
-  int cg_check = 8;                // option "cg_check": iterations between two looks at the status word
-  int cg_products = 0, cg_blocks = 0;  // counters of the call in progress (gogp_cg_last_info)
-  double cg_yta = 0.0;
-  double cg_vmin = 0.0;            // the smallest noise variance given (0 without variances)
-  Workspace cg_L;                  // Ls = D^-1/2 L, column-major, `rank` columns of cg_ldn doubles
-  Workspace cg_small;              // C^-1 (rp x rp), W and Y (CG_MAX_T x rp each), the per-column state
-  Workspace cg_vec;                // a block's six vectors, the dots' partials and results
-  Workspace cg_part;               // the slab partials of the product and of the skinny transposed product
-  Workspace cg_ks;                 // gogp_cg_produce: 64 rows of k*, the test points, prior, q, mu
-  double cg_logdet_c = 0.0;        // log |C| of the last solve's capacitance matrix (0 at rank 0)
-  double cg_dnoise = 0.0;          // d noise_var / d log(noise parameter) at the last solve's theta
-  Workspace cg_lml;                // gogp_cg_lml_gradient: a block's rows of Xi, the a / beta history, rho0, slot sums and partials
-  // Vecchia's approximation (gogp_vecchia_*, vecchia.hip): a data set and a table of its own, resident; nothing of the
-  // handle's other state is touched
+  // the iterative exact GP (cg_api.hip: gogp_cg_*) and Vecchia's approximation (vecchia_api.hip: gogp_vecchia_*): each a
+  // data set of its own, resident; nothing of the handle's other state is touched
+  CgHandleState cg;
   VecchiaState vc;
   // the Laplace approximation (gogp_laplace_*, laplace.hip; api.hip: LapVecs).  B's factor lies in bufL / Dinv, B^-1 and
   // then the gradient's weight matrix in bufA; only vectors are its own (released with the N buffers).

@@ -1,4 +1,4 @@
-// vecchia.hip -- the kernel of Vecchia's approximation (gogp_vecchia_*; api.hip orchestrates).
+// vecchia.hip -- the kernel of Vecchia's approximation (gogp_vecchia_*; vecchia_api.hip orchestrates).
 //
 //     log p(y) ~ sum_i log p(y_i | y_c(i)),     c(i) a set of at most m <= 63 EARLIER rows (Vecchia 1988; Datta et al. 2016).
 // Target i with conditioning rows c = c(i) in the table's order, q = |c|, block b = [c..., i] (the target LAST):

@@ -1,5 +1,5 @@
 // vecchia_knn.hip -- neighbour tables of Vecchia's approximation built on the device (gogp_vecchia_neighbours,
-// gogp_vecchia_set_data_nearest, gogp_vecchia_reneighbour, gogp_vecchia_produce_nearest; api.hip orchestrates).
+// gogp_vecchia_set_data_nearest, gogp_vecchia_reneighbour, gogp_vecchia_produce_nearest; vecchia_api.hip orchestrates).
 //
 // The definition is that of gogp_amd/vecchia.py (nearest / nearest_to), and the table is the host's integer for integer:
 //     xs = x / lengths per dimension (a plain IEEE fp64 division; lengths == nullptr: xs = x),
