@@ -159,6 +159,7 @@ SYMBOLS = [
     ("gogp_cg_produce", ctypes.c_int,
      [_h, _dp, _i64, _dp, _dp, ctypes.c_double, ctypes.c_int32, ctypes.POINTER(CCgCol)]),
     ("gogp_cg_last_info", ctypes.c_int, [_h, ctypes.POINTER(CCgInfo)]),
+    ("gogp_cg_last_rounds", ctypes.c_int, [_h] + [ctypes.POINTER(ctypes.c_int32)] * 4),
     ("gogp_cg_lml_gradient", ctypes.c_int,
      [_h, _dp, _i64, _i64, ctypes.c_double, ctypes.c_int32, _dp, _i64, _dp, ctypes.POINTER(CCgLmlInfo),
       ctypes.POINTER(CCgCol)]),
@@ -475,6 +476,8 @@ HOOK_SYMBOLS += [
     ("gogp_test_cg_dot_blocks", _ci, [_i64]),
     ("gogp_test_kmm", _ci, [_ci, _kpp, _dp, _i64, _i64, _dp, _i64, _i64, _dp, _i64, _i64, _ci, _dp, _i64, _ci, _ci, _dp, _i64,
                             _dp, _i64, _i64]),
+    ("gogp_test_kmm32", _ci, [_ci, _kpp, _dp, _i64, _i64, _dp, _i64, _i64, _dp, _i64, _dp, _i64, _i64, _ci, _dp, _i64, _ci,
+                              _ci, _dp, _i64, _dp, _i64, _i64]),
     ("gogp_test_cg_dots", _ci, [_ci, _dp, _i64, _dp, _i64, _i64, _i64, _ci, _ci, _ci, ctypes.c_double, _dp, _i64, _dp, _i64,
                                 _dp, _i64, _i32p, _i64]),
     ("gogp_test_cg_update_xr", _ci, [_ci] + [_dp, _i64] * 4 + [_i64, _i64, _ci, _dp, _i64, _i32p, _i64]),

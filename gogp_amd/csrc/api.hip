@@ -5375,6 +5375,12 @@ extern "C" int gogp_set_option(gogp_handle *h, const char *name, int64_t value) 
     h->cg.check = (int)value;
     return GOGP_OK;
   }
+  if (strcmp(name, "cg_precision") == 0) {  // gogp_cg_*: 32 evaluates the similarity of a block's iterations in float (cg_mixed.hip)
+    if (h->prec == 32 || h->dist) return fail(h, GOGP_EARG, (std::string("cg_precision: ") + sparse_refusal(h)).c_str());
+    if (value != 32 && value != 64) return fail(h, GOGP_EARG, "cg_precision must be 32 or 64");
+    h->cg.precision = (int)value;
+    return GOGP_OK;
+  }
   if (strcmp(name, "laplace_max_iter") == 0) {  // gogp_laplace_observe: Newton steps at the most
     if (value < 1 || value > 200) return fail(h, GOGP_EARG, "laplace_max_iter must be 1..200");
     h->lap_max_iter = (int)value;

@@ -553,6 +553,13 @@ void launch_kmm(hipStream_t s, const DevParams *p, int ndim, const double *A, in
                (const double *)part, nslab, T, rpad, (long)rows, Out, (long)ldo);
 }
 
+// the second half of a product on its own: launch_kmm32 (cg_mixed.hip) adds its partials with the same kernel
+void launch_kmm_finish(hipStream_t s, const double *part, int nslab, int T, int64_t rpad, int64_t rows, double *Out,
+                       int64_t ldo) {
+  GOGP_KLAUNCH(kmm_finish_kernel, dim3((unsigned)((ldo + 255) / 256), (unsigned)T), dim3(256), 0, s, part, nslab, T,
+               (long)rpad, (long)rows, Out, (long)ldo);
+}
+
 int cg_dot_blocks(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + 2047) / 2048, 512)); }
 
 void launch_cg_dots(hipStream_t s, const double *A, const double *B, int64_t ld, int64_t n, int T, int mode, int it,

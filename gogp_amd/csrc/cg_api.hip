@@ -37,12 +37,23 @@ extern "C" int gogp_cg_set_data(gogp_handle *h, const double *X, const double *y
   if (e == hipSuccess) e = hipMalloc(&cg.dis, vb);
   if (e == hipSuccess) e = hipMalloc(&cg.alpha, vb);
   if (e == hipSuccess) e = hipMalloc(&cg.P, sizeof(DevParams));
+  if (e == hipSuccess) e = hipMalloc(&cg.centre, GOGP_MAX_NDIM * sizeof(double));
   if (e == hipSuccess) e = hipMemsetAsync(cg.X, 0, xb, s);
   if (e == hipSuccess) e = hipMemsetAsync(cg.y, 0, vb, s);
   if (e == hipSuccess && v) e = hipMemsetAsync(cg.v, 0, vb, s);
   if (e == hipSuccess) e = hipMemcpyAsync(cg.X, X, (size_t)N * D * sizeof(double), hipMemcpyHostToDevice, s);
   if (e == hipSuccess) e = hipMemcpyAsync(cg.y, y, (size_t)N * sizeof(double), hipMemcpyHostToDevice, s);
   if (e == hipSuccess && v) e = hipMemcpyAsync(cg.v, v, (size_t)N * sizeof(double), hipMemcpyHostToDevice, s);
+  // the midpoint of every column's range: what the float-evaluated product (cg_mixed.hip) centres by, test points included
+  double centre[GOGP_MAX_NDIM] = {};
+  if (e == hipSuccess) {
+    double lo[GOGP_MAX_NDIM], hi[GOGP_MAX_NDIM];
+    for (int d = 0; d < D; ++d) lo[d] = hi[d] = X[d];
+    for (int64_t i = 1; i < N; ++i)
+      for (int d = 0; d < D; ++d) lo[d] = std::min(lo[d], X[i * D + d]), hi[d] = std::max(hi[d], X[i * D + d]);
+    for (int d = 0; d < D; ++d) centre[d] = lo[d] + 0.5 * (hi[d] - lo[d]);
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(cg.centre, centre, sizeof centre, hipMemcpyHostToDevice, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
   if (e != hipSuccess) {
     cg.release();
@@ -135,50 +146,119 @@ static int cg_block_solve(gogp_handle *h, const char *who, const double *dB, int
   launch_cg_dots(s, r, z, ld, n, T, CG_DOT_RHO0, 0, tol, dpart, keep ? keep->rho0 : nullptr, cs);
   int status[2] = {T, 0};
   const int check = std::max(1, cg.check);
-  for (int it = 1; it <= max_iter; ++it) {
-    launch_kmm(s, P, D, cg.X, n, cg.X, n, p, ld, T, cg.d, nslab, 0, kpart, q, ld);
-    ++cg.products;
-    launch_cg_dots(s, p, q, ld, n, T, CG_DOT_PQ, it, tol, dpart, nullptr, cs, hist);
-    launch_cg_update_xr(s, x, r, p, q, ld, n, T, cs);
-    launch_cg_dots(s, r, r, ld, n, T, CG_DOT_RR, it, tol, dpart, nullptr, cs);
-    cg_apply_precond(h, sm, r, T, z);
-    launch_cg_dots(s, r, z, ld, n, T, CG_DOT_BETA, it, tol, dpart, nullptr, cs, hist);
-    launch_cg_update_p(s, p, z, ld, n, T, cs);
-    if (it % check == 0 || it == max_iter) {
-      launch_cg_status(s, T, cs);
-      HIPCHK(h, hipMemcpyAsync(status, sm.st + CG_ST_STATUS * CG_MAX_T, sizeof status, hipMemcpyDeviceToHost, s));
-      HIPCHK(h, hipStreamSynchronize(s));
-      if (status[0] == 0 || status[1] != 0) break;
+  // q = K^ v on the fp64 product or, in a round of "cg_precision" = 32, on the float-evaluated one (cg_mixed.hip)
+  auto product = [&](bool f32, const double *v) {
+    if (f32) {
+      launch_kmm32(s, P, D, cg.nterms, cg.kind0, cg.X, n, cg.X, n, cg.centre, v, ld, T, cg.d, nslab, 0, kpart, q, ld);
+      ++cg.products32;
+    } else {
+      launch_kmm(s, P, D, cg.X, n, cg.X, n, v, ld, T, cg.d, nslab, 0, kpart, q, ld);
     }
-  }
-  // the true residual: one more product; b - K^ x into z, its squared norms through the plain dots
-  launch_kmm(s, P, D, cg.X, n, cg.X, n, x, ld, T, cg.d, nslab, 0, kpart, q, ld);
-  ++cg.products;
-  launch_cg_scale(s, dB, nullptr, q, ld, n, T, z);
-  launch_cg_dots(s, z, z, ld, n, T, CG_DOT_PLAIN, 0, tol, dpart, sm.dots, cs);
+    ++cg.products;
+  };
+  // the iterations first .. last at the most, columns freezing at ftol |b|; the host looks every `check` of them
+  auto iterate = [&](int first, int last, bool f32, double ftol) -> int {
+    for (int it = first; it <= last; ++it) {
+      product(f32, p);
+      launch_cg_dots(s, p, q, ld, n, T, CG_DOT_PQ, it, ftol, dpart, nullptr, cs, hist);
+      launch_cg_update_xr(s, x, r, p, q, ld, n, T, cs);
+      launch_cg_dots(s, r, r, ld, n, T, CG_DOT_RR, it, ftol, dpart, nullptr, cs);
+      cg_apply_precond(h, sm, r, T, z);
+      launch_cg_dots(s, r, z, ld, n, T, CG_DOT_BETA, it, ftol, dpart, nullptr, cs, hist);
+      launch_cg_update_p(s, p, z, ld, n, T, cs);
+      if ((it - first + 1) % check == 0 || it == last) {
+        launch_cg_status(s, T, cs);
+        HIPCHK(h, hipMemcpyAsync(status, sm.st + CG_ST_STATUS * CG_MAX_T, sizeof status, hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipStreamSynchronize(s));
+        if (status[0] == 0 || status[1] != 0) break;
+      }
+    }
+    return GOGP_OK;
+  };
+  // the true residual: one more fp64 product; b - K^ x into z, its squared norms through the plain dots, and the state
   double hsc[CG_SC_ROWS * CG_MAX_T], hdots[CG_MAX_T];
   int hst[CG_ST_ROWS * CG_MAX_T];
-  // (the three copies land in locals: the stream is drained before any return, whatever failed)
-  hipError_t ce = hipMemcpyAsync(hsc, sm.sc, sizeof hsc, hipMemcpyDeviceToHost, s);
-  if (ce == hipSuccess) ce = hipMemcpyAsync(hdots, sm.dots, sizeof hdots, hipMemcpyDeviceToHost, s);
-  if (ce == hipSuccess) ce = hipMemcpyAsync(hst, sm.st, sizeof hst, hipMemcpyDeviceToHost, s);
-  const hipError_t se = hipStreamSynchronize(s);
-  HIPCHK(h, ce);
-  HIPCHK(h, se);
-  HIPCHK(h, hipGetLastError());
+  auto residual = [&]() -> int {
+    product(false, x);
+    launch_cg_scale(s, dB, nullptr, q, ld, n, T, z);
+    launch_cg_dots(s, z, z, ld, n, T, CG_DOT_PLAIN, 0, tol, dpart, sm.dots, cs);
+    // (the three copies land in locals: the stream is drained before any return, whatever failed)
+    hipError_t ce = hipMemcpyAsync(hsc, sm.sc, sizeof hsc, hipMemcpyDeviceToHost, s);
+    if (ce == hipSuccess) ce = hipMemcpyAsync(hdots, sm.dots, sizeof hdots, hipMemcpyDeviceToHost, s);
+    if (ce == hipSuccess) ce = hipMemcpyAsync(hst, sm.st, sizeof hst, hipMemcpyDeviceToHost, s);
+    const hipError_t se = hipStreamSynchronize(s);
+    HIPCHK(h, ce);
+    HIPCHK(h, se);
+    HIPCHK(h, hipGetLastError());
+    return GOGP_OK;
+  };
+  // "cg_precision" = 32 (include/gogp_hip.h states the rounds); the LML's blocks (keep) stay on the fp64 product
+  const bool mixed = cg.precision == 32 && !keep;
+  int tot[CG_MAX_T] = {};       // mixed: a column's iterations, summed over the rounds
+  bool done[CG_MAX_T] = {};     // mixed: its true residual is within tol
+  bool last64 = !mixed;         // the block finished on the fp64 product: today's meaning of converged and bad
+  if (!mixed) {
+    if (const int e1 = iterate(1, max_iter, false, tol)) return e1;
+    if (const int e2 = residual()) return e2;
+    ++cg.rounds;
+  } else {
+    bool f32 = true;
+    double prev = 1.0;  // the worst live column's true relative residual before the round (x = 0: 1)
+    int first = 1, frounds = 0;
+    for (;;) {
+      int used = 0;
+      for (int t = 0; t < T; ++t)
+        if (!done[t]) used = std::max(used, tot[t]);
+      if (const int e1 = iterate(first, first + (max_iter - used) - 1, f32, 0.5 * tol)) return e1;
+      if (const int e2 = residual()) return e2;
+      ++cg.rounds;
+      int it_max = first - 1;
+      for (int t = 0; t < T; ++t) {
+        const int it = hst[CG_ST_ITERS * CG_MAX_T + t];
+        if (it >= first) tot[t] += it - first + 1, it_max = std::max(it_max, it);
+      }
+      first = it_max + 1;
+      if (!f32) {
+        last64 = true;
+        break;
+      }
+      bool all = true, anybad = false, spent = false;
+      double worst = 0.0;
+      for (int t = 0; t < T; ++t) {
+        const double bn2 = hsc[CG_SC_BNORM2 * CG_MAX_T + t];
+        done[t] = bn2 == 0.0 || sqrt(hdots[t]) <= tol * sqrt(bn2);
+        anybad = anybad || hst[CG_ST_BAD * CG_MAX_T + t] != 0;
+        if (done[t]) continue;
+        all = false;
+        spent = spent || tot[t] >= max_iter;
+        const double rel = sqrt(hdots[t]) / sqrt(bn2);
+        worst = rel > worst || std::isnan(rel) ? rel : worst;
+      }
+      if (all || spent) break;
+      // the safeguards: p^T K~ p <= 0, a round that did not halve the worst live residual, the cap on the rounds
+      ++frounds;
+      if (anybad || frounds >= GOGP_CG_MAX_ROUNDS || !(worst <= 0.5 * prev)) f32 = false, ++cg.fallbacks;
+      prev = worst;
+      launch_cg_restart(s, T, tol, sm.dots, cs);
+      HIPCHK(h, hipMemcpyAsync(r, z, vec * sizeof(double), hipMemcpyDeviceToDevice, s));
+      cg_apply_precond(h, sm, r, T, z);
+      HIPCHK(h, hipMemcpyAsync(p, z, vec * sizeof(double), hipMemcpyDeviceToDevice, s));
+      launch_cg_dots(s, r, z, ld, n, T, CG_DOT_RHO0, 0, tol, dpart, nullptr, cs);
+    }
+  }
   ++cg.blocks;
   *xout = x;
   int bad = -1;
   bool all = true;
   for (int t = 0; t < T; ++t) {
-    const bool isbad = hst[CG_ST_BAD * CG_MAX_T + t] != 0;
+    const bool isbad = last64 && hst[CG_ST_BAD * CG_MAX_T + t] != 0;
     if (isbad && bad < 0) bad = t;
-    const bool conv = hst[CG_ST_FROZEN * CG_MAX_T + t] != 0 && !isbad;
+    const bool conv = last64 ? hst[CG_ST_FROZEN * CG_MAX_T + t] != 0 && !isbad : done[t];
     all = all && conv;
     if (cols) {
       gogp_cg_col &c = cols[t];
       const double bn = sqrt(hsc[CG_SC_BNORM2 * CG_MAX_T + t]);
-      c.iterations = hst[CG_ST_ITERS * CG_MAX_T + t];
+      c.iterations = mixed ? tot[t] : hst[CG_ST_ITERS * CG_MAX_T + t];
       c.converged = conv ? 1 : 0;
       c.rel_residual = bn > 0.0 ? sqrt(hdots[t]) / bn : 0.0;
       c.rel_residual_recurrence = bn > 0.0 ? sqrt(hsc[CG_SC_RR * CG_MAX_T + t]) / bn : 0.0;
@@ -234,6 +314,8 @@ extern "C" int gogp_cg_solve(gogp_handle *h, const double *x, int64_t len, int32
   cg.rank = cg.rp = 0;
   cg.logdet_c = 0.0;
   cg.dnoise = hp.dnoise;
+  cg.nterms = hp.nterms, cg.kind0 = hp.kind[0];
+  cg.rounds = cg.products32 = cg.fallbacks = 0;
   *info = gogp_cg_info();
   HIPCHK(h, hipMemcpyAsync(cg.P, &hp, sizeof hp, hipMemcpyHostToDevice, s));
   HIPCHK(h, hipStreamSynchronize(s));  // hp is a local
@@ -347,6 +429,18 @@ extern "C" int gogp_cg_last_info(gogp_handle *h, gogp_cg_info *info) {
   return GOGP_OK;
 }
 
+extern "C" int gogp_cg_last_rounds(gogp_handle *h, int32_t *rounds, int32_t *products32, int32_t *products64,
+                                   int32_t *fallbacks) {
+  if (!h) return GOGP_EARG;
+  const CgHandleState &cg = h->cg;
+  if (!rounds || !products32 || !products64 || !fallbacks) return fail(h, GOGP_EARG, "cg_last_rounds: NULL");
+  *rounds = cg.rounds;
+  *products32 = cg.products32;
+  *products64 = cg.products - cg.products32;
+  *fallbacks = cg.fallbacks;
+  return GOGP_OK;
+}
+
 extern "C" int gogp_cg_get_alpha(gogp_handle *h, double *alpha, int64_t n) {
   const char *who = "cg_get_alpha";
   if (!h) return GOGP_EARG;
@@ -375,6 +469,7 @@ extern "C" int gogp_cg_solve_columns(gogp_handle *h, const double *B, int64_t T,
   HIPCHK(h, hipSetDevice(h->device));
   hipStream_t s = h->s;
   cg.products = cg.blocks = 0;
+  cg.rounds = cg.products32 = cg.fallbacks = 0;
   int rc = GOGP_OK;
   std::string first_err;
   for (int64_t t0 = 0; t0 < T; t0 += CG_MAX_T) {
@@ -412,6 +507,7 @@ extern "C" int gogp_cg_produce(gogp_handle *h, const double *Z, int64_t m, doubl
   HIPCHK(h, hipSetDevice(h->device));
   hipStream_t s = h->s;
   cg.products = cg.blocks = 0;
+  cg.rounds = cg.products32 = cg.fallbacks = 0;
   if (m == 0) return GOGP_OK;
   const int64_t N = cg.N, npad = cg.npad;
   // layout of cg_ks: 64 rows of k* (npad each), 64 test points, prior, q, mu, sigma (64 each)
@@ -487,8 +583,8 @@ extern "C" int gogp_cg_lml_gradient(gogp_handle *h, const double *Xi, int64_t t,
   // the counters of the last solve / columns / produce call stay what gogp_cg_last_info reports
   struct Restore {
     CgHandleState &cg;
-    const int p = cg.products, b = cg.blocks;
-    ~Restore() { cg.products = p, cg.blocks = b; }
+    const int p = cg.products, b = cg.blocks, r = cg.rounds, p32 = cg.products32, f = cg.fallbacks;
+    ~Restore() { cg.products = p, cg.blocks = b, cg.rounds = r, cg.products32 = p32, cg.fallbacks = f; }
   } restore{cg};
   cg.products = cg.blocks = 0;
   const int gblocks = cg_grad_blocks(N);

@@ -624,6 +624,20 @@ int kmm_slabs(int64_t rows, int64_t cols);
 void launch_kmm(hipStream_t s, const DevParams *p, int ndim, const double *A, int64_t rows, const double *B, int64_t cols,
                 const double *V, int64_t ldv, int T, const double *diag, int nslab, int max_blocks, double *part,
                 double *Out, int64_t ldo);
+// cg_mixed.hip: launch_kmm with the similarity evaluated in single precision ("cg_precision" = 32) -- the same arguments,
+// sizes, partials and finish kernel (launch_kmm_finish), plus what the host knows of the descriptor (nterms, the first
+// term's kind: they pick the instance with ndim, kmm32_fast_dims: the padded dimension count of the one-radial-term
+// instance or 0 for the generic one) and centre (device, ndim doubles): every coordinate is centred in fp64 before it is
+// rounded.  The scales, diag, V, the sums and the partials are fp64.
+void launch_kmm_finish(hipStream_t s, const double *part, int nslab, int T, int64_t rpad, int64_t rows, double *Out,
+                       int64_t ldo);
+int kmm32_fast_dims(int ndim, int nterms, int kind0);
+void launch_kmm32(hipStream_t s, const DevParams *p, int ndim, int nterms, int kind0, const double *A, int64_t rows,
+                  const double *B, int64_t cols, const double *centre, const double *V, int64_t ldv, int T,
+                  const double *diag, int nslab, int max_blocks, double *part, double *Out, int64_t ldo);
+// launch_cg_restart (mode 32): the columns whose true residual dots[t] = |b - K^ x|^2 is within tol^2 |b|^2 (or whose b is
+// zero) are frozen, the others live again, nothing is bad; |r|^2 of the state becomes dots[t].
+void launch_cg_restart(hipStream_t s, int T, double tol, const double *dots, CgState cs);
 int cg_dot_blocks(int64_t n);
 void launch_cg_dots(hipStream_t s, const double *A, const double *B, int64_t ld, int64_t n, int T, int mode, int it,
                     double tol, double *part, double *out, CgState cs, double *hist = nullptr);

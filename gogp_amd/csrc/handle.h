@@ -73,6 +73,10 @@ struct CgHandleState {
   int64_t ldn = 0;
   int check = 8;                // option "cg_check": iterations between two looks at the status word
   int products = 0, blocks = 0;  // counters of the call in progress (gogp_cg_last_info)
+  int precision = 64;           // option "cg_precision": 32 runs a block's iterations on the float-evaluated product
+  int rounds = 0, products32 = 0, fallbacks = 0;  // ... and how that call spent its products (gogp_cg_last_rounds)
+  double *centre = nullptr;     // GOGP_MAX_NDIM doubles: the midpoint of every column of X (cg_mixed.hip centres by it)
+  int nterms = 0, kind0 = 0;    // of the last solve's descriptor: what picks launch_kmm32's instance
   double yta = 0.0;
   double vmin = 0.0;            // the smallest noise variance given (0 without variances)
   Workspace L;                  // Ls = D^-1/2 L, column-major, `rank` columns of ldn doubles
@@ -83,10 +87,10 @@ struct CgHandleState {
   double logdet_c = 0.0;        // log |C| of the last solve's capacitance matrix (0 at rank 0)
   double dnoise = 0.0;          // d noise_var / d log(noise parameter) at the last solve's theta
   Workspace lml;                // gogp_cg_lml_gradient: a block's rows of Xi, the a / beta history, rho0, slot sums and partials
-  void release() {  // the option stays, and so do the last solve's counters and scalars (gogp_cg_last_info reports them)
-    for (double *q : {X, y, v, d, dis, alpha}) (void)hipFree(q);
+  void release() {  // the options stay, and so do the last solve's counters and scalars (gogp_cg_last_info reports them)
+    for (double *q : {X, y, v, d, dis, alpha, centre}) (void)hipFree(q);
     (void)hipFree(P);
-    X = y = v = d = dis = alpha = nullptr;
+    X = y = v = d = dis = alpha = centre = nullptr;
     P = nullptr;
     for (Workspace *w : {&L, &small, &vec, &part, &ks, &lml}) w->release();
     N = npad = 0;

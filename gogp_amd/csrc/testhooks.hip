@@ -2496,6 +2496,35 @@ extern "C" int gogp_test_kmm(int device, const gogp_test_kparams *kparams, const
              });
 }
 
+// launch_kmm32 (cg_mixed.hip): gogp_test_kmm's arguments and refusals, plus the centres (ndim doubles)
+extern "C" int gogp_test_kmm32(int device, const gogp_test_kparams *kparams, const double *A, int64_t a_len, int64_t rows,
+                               const double *B, int64_t b_len, int64_t cols, const double *centre, int64_t centre_len,
+                               const double *V, int64_t v_len, int64_t ldv, int T, const double *diag, int64_t diag_len,
+                               int nslab, int max_blocks, double *part, int64_t part_len, double *Out, int64_t out_len,
+                               int64_t ldo) {
+  if (!kparams || !A || !V || !centre || !part || !Out || !gram_args_ok(kparams, 1, 0, 0)) return GOGP_EARG;
+  if (kparams->nevents != 0) return GOGP_EARG;
+  if (rows < 1 || rows > GR_NPAD_MAX || cols < 1 || cols > GR_NPAD_MAX || T < 1 || T > CG_MAX_T) return GOGP_EARG;
+  if (nslab < 1 || nslab > KMM_SLABS_MAX || max_blocks < 0) return GOGP_EARG;
+  const int ndim = kparams->ndim;
+  if (centre_len < ndim) return GOGP_EARG;
+  for (int d = 0; d < ndim; ++d)
+    if (!std::isfinite(centre[d])) return GOGP_EARG;
+  if (B ? b_len < cols * ndim : (b_len != 0 || cols != rows)) return GOGP_EARG;
+  if (diag ? (B != nullptr || diag_len < rows) : diag_len != 0) return GOGP_EARG;
+  const int64_t rpad = (rows + 63) / 64 * 64;
+  if (a_len < rows * ndim || !cg_block_ok(v_len, ldv, cols, T) || part_len < (int64_t)nslab * T * rpad || ldo < rows ||
+      out_len < (int64_t)T * ldo)
+    return GOGP_EARG;
+  const DevParams hp = to_dev(*kparams);
+  return run(device, {rd(&hp, 1, sizeof hp), rd(A, a_len), opt(rd(B, b_len)), rd(V, v_len), opt(rd(diag, diag_len)),
+                      io(part, part_len), io(Out, out_len), rd(centre, centre_len)},
+             [&](const Dev &d) {
+               launch_kmm32(0, d.as<DevParams>(0), ndim, hp.nterms, hp.kind[0], d[1], rows, B ? d[2] : d[1], cols, d[7],
+                            d[3], ldv, T, d[4], nslab, max_blocks, d[5], d[6], ldo);
+             });
+}
+
 // out may be NULL (length 0) except in mode CG_DOT_PLAIN; st holds 32-bit integers
 extern "C" int gogp_test_cg_dots(int device, const double *A, int64_t a_len, const double *B, int64_t b_len, int64_t ld,
                                  int64_t n, int T, int mode, int it, double tol, double *part, int64_t part_len, double *out,

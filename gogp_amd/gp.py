@@ -775,6 +775,15 @@ class GP:
         return {"rank_used": int(info.rank_used), "products": int(info.products), "blocks": int(info.blocks),
                 "yt_alpha": float(info.yt_alpha)}
 
+    def _cg_rounds(self) -> dict:
+        """How the call just made spent its products (gogp_cg_last_rounds): ``rounds`` (summed over its lock-step blocks:
+        1 per block with "cg_precision" = 64, the restarts on the true residual with 32), ``products32`` and
+        ``products64`` (float-evaluated and fp64 products; their sum is ``products`` of cg_info) and ``fallbacks``
+        (blocks that finished on the fp64 product)."""
+        v = [ctypes.c_int32() for _ in range(4)]
+        self._check(_lib.lib().gogp_cg_last_rounds(self._h, *[ctypes.byref(q) for q in v]))
+        return dict(zip(("rounds", "products32", "products64", "fallbacks"), (int(q.value) for q in v)))
+
     def _cg_finish(self, rc: int, result):
         """GOGP_ENOCONV raises ConvergenceError carrying the results that were written; other errors as usual."""
         if rc == _lib.GOGP_ENOCONV:
@@ -801,6 +810,7 @@ class GP:
                "yt_alpha": float(info.yt_alpha)}
         out.update({k: v[0] for k, v in self._cg_cols(col, 1).items()})
         self.cg_info = out
+        self.cg_rounds = self._cg_rounds()
         return self._cg_finish(rc, out)
 
     def CGAlpha(self) -> np.ndarray:
@@ -821,6 +831,7 @@ class GP:
         rc = _lib.lib().gogp_cg_solve_columns(self._h, _dp(b) if T else None, T, float(tol), int(max_iter),
                                               _dp(S) if T else None, cols)
         self.cg_info = self._cg_info()
+        self.cg_rounds = self._cg_rounds()
         return self._cg_finish(rc, (S, self._cg_cols(cols, T)))
 
     def CGProduce(self, z, sigma: bool = True, tol: float = 1e-8, max_iter: int = 1000):
@@ -836,6 +847,7 @@ class GP:
         rc = _lib.lib().gogp_cg_produce(self._h, _dp(zs) if m else None, m, _dp(mu) if m else None,
                                         _dp(sg) if (sigma and m) else None, float(tol), int(max_iter), cols)
         self.cg_info = self._cg_info()
+        self.cg_rounds = self._cg_rounds()
         self.cg_cols = self._cg_cols(cols, m)
         return self._cg_finish(rc, (mu, sg))
 
@@ -2577,6 +2589,22 @@ def kmm_check(kp, A: np.ndarray, rows: int, B, cols: int, V: np.ndarray, ldv: in
                                     dg, dl, nslab, max_blocks, _dp(part), part.size, _dp(Out), Out.size, ldo)
     if rc != _lib.GOGP_OK:
         raise GogpError(rc, "test_kmm")
+    return part, Out
+
+
+def kmm32_check(kp, A: np.ndarray, rows: int, B, cols: int, centre: np.ndarray, V: np.ndarray, ldv: int, T: int, diag,
+                nslab: int, part: np.ndarray, Out: np.ndarray, ldo: int, max_blocks: int = 0, device: int = -1):
+    """launch_kmm32 (test hook gogp_test_kmm32): kmm_check with the similarity evaluated in single precision; centre
+    (NDim) is subtracted from every coordinate in fp64 before it is rounded.  Returns copies of (part, Out)."""
+    A, V, centre = _vec(A, "A"), _vec(V, "V"), _vec(centre, "centre")
+    part, Out = _vec(part, "part").copy(), _vec(Out, "Out").copy()
+    bp, bl = _opt(B, "B")
+    dg, dl = _opt(diag, "diag")
+    rc = _lib.hooks().gogp_test_kmm32(device, ctypes.byref(kp), _dp(A), A.size, rows, bp, bl, cols, _dp(centre), centre.size,
+                                      _dp(V), V.size, ldv, T, dg, dl, nslab, max_blocks, _dp(part), part.size, _dp(Out),
+                                      Out.size, ldo)
+    if rc != _lib.GOGP_OK:
+        raise GogpError(rc, "test_kmm32")
     return part, Out
 
 

@@ -440,6 +440,10 @@ class GP {
     check(gogp_cg_last_info(h_, &info));
     return info;
   }
+  // how the last CGSolve / CGSolveColumns / CGProduce spent its products (option "cg_precision"; gogp_cg_last_rounds)
+  void CGRounds(int32_t *rounds, int32_t *products32, int32_t *products64, int32_t *fallbacks) {
+    check(gogp_cg_last_rounds(h_, rounds, products32, products64, fallbacks));
+  }
   // The LML and d LML / d log theta at the parameters of the last CGSolve, from t probes: xi holds t rows of ldxi >= N +
   // rank_used standard normals [xi2 (N) | xi1 (rank_used)] (gogp_cg_lml_gradient; nothing random happens in the library).
   // grad receives the gradient (nullptr: the pair reduction is skipped), quad the per-probe quadrature values.  Returns

@@ -649,10 +649,37 @@ int gogp_sparse_select_inducing_resident(gogp_handle *h, const double *x, int64_
  * 149 ms (Normal) and 668 ms (Matern-5/2) beside 71 ms for the dense gogp_observe + gogp_gradient, which is the call at
  * that size; the estimate lies 1.55 and 0.35 standard errors (5.4 and 34.5) from the dense LML, the gradient within 6.9e-4
  * and 1.4e-2 of the dense one's norm.  At N = 65536: 3.46 s and 19.3 s.
- * Out of scope: the symmetry of K in the product and in the pair reduction, event discounts, several GPUs.  DESIGN.md
- * section 4, "Iterative (CG)" and "Iterative (CG): LML and gradient". */
+ * Option "cg_precision" (gogp_set_option; 64, the default, or 32; GOGP_EARG for another value and on precision = 32 and
+ * sharded handles; kept across gogp_cg_set_data like "cg_check"): 32 runs the iterations of a lock-step block -- of
+ * gogp_cg_solve, gogp_cg_solve_columns and the sigma of gogp_cg_produce -- on a product whose similarity f is evaluated
+ * in SINGLE precision (cg_mixed.hip: kmm32_kernel; hardware exp2, sqrt and sine, a fully unrolled one-radial-term instance
+ * for D <= 16 and a generic one), while the scales c_t, D, every vector, every sum and every decision stay fp64, and
+ * corrects the result against the fp64 operator in ROUNDS:
+ *   1  today's iteration on the float product K~, a column freezing at |r| <= (tol / 2) |b| with |b| of the ORIGINAL
+ *      right-hand side, taken once;
+ *   2  one fp64 product: z = b - K^ x.  A column with |z| <= tol |b| is done: converged, its rel_residual this figure;
+ *   3  the others restart -- r = z, z = P^-1 r, p = z -- and go to 1: x keeps accumulating, done columns stay frozen and
+ *      keep their bits.
+ * max_iter bounds a column's iterations summed over its rounds; after GOGP_CG_MAX_ROUNDS float rounds, after a round
+ * that did not halve the worst live column's true residual, or when p^T K~ p is not positive, the block FALLS BACK: it
+ * restarts once more from its current x and finishes on the fp64 product (freezing at tol / 2, converged and GOGP_ENOTPD
+ * meaning what they mean with 64).  A float operator too coarse for a badly conditioned problem costs time, never
+ * correctness.  Error of the float operator: an entry of K~ is off by c_t times the float evaluation error of f (a few
+ * 2^-24: tests/golden/cg_mixed.json has the measured factors per family), the coordinates are centred on the midpoint of
+ * each column of X in fp64 before they are rounded (gogp_cg_set_data computes the centres; an error of 2^-24 range_d / l_d
+ * per coordinate, whatever common offset the inputs carry), and K~ is symmetric bit for bit.  With a fallback a column's
+ * bits may depend on the columns beside it (the decision is the block's); without one they do not.  The mean of
+ * gogp_cg_produce stays on the fp64 product, and so does gogp_cg_lml_gradient whatever the option says (the alpha it
+ * starts from may come from a mixed solve).  gogp_cg_last_rounds: of the last solve / columns / produce call, the rounds
+ * summed over its blocks (1 per block with 64), the products by kind (their sum is gogp_cg_info.products) and the blocks
+ * that fell back.  With the option at 64 every call returns the bits it returned before the option existed.  Measured:
+ * profiles/cg_mixed.txt (tools/cg_mixed_probe.py); DESIGN.md section 4, "Iterative (CG): float-evaluated product".
+ * Out of scope: the symmetry of K in the product and in the pair reduction, event discounts, several GPUs, the probes'
+ * solves and the Lanczos log-determinant on the float product.  DESIGN.md section 4, "Iterative (CG)" and "Iterative
+ * (CG): LML and gradient". */
 #define GOGP_CG_MAX_RANK 1024
 #define GOGP_CG_MAX_RHS 64 /* systems per lock-step block */
+#define GOGP_CG_MAX_ROUNDS 8 /* "cg_precision" = 32: float rounds of a block before it finishes on the fp64 product */
 typedef struct {
   int32_t iterations, converged;
   double rel_residual, rel_residual_recurrence;
@@ -670,6 +697,7 @@ int gogp_cg_solve_columns(gogp_handle *h, const double *B /* T rows of N */, int
 int gogp_cg_produce(gogp_handle *h, const double *Z, int64_t m, double *mu, double *sigma /* may be NULL */, double tol,
                     int32_t max_iter, gogp_cg_col *cols /* m, may be NULL */);
 int gogp_cg_last_info(gogp_handle *h, gogp_cg_info *info);
+int gogp_cg_last_rounds(gogp_handle *h, int32_t *rounds, int32_t *products32, int32_t *products64, int32_t *fallbacks);
 typedef struct {
   double lml, yt_alpha, logdet, logdet_precond, logdet_stderr;
   int32_t probes, blocks, products, lanczos_max;

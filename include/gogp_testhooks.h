@@ -659,6 +659,12 @@ int gogp_test_kmm(int device, const gogp_test_kparams *kparams, const double *A,
                   const double *B, int64_t b_len, int64_t cols, const double *V, int64_t v_len, int64_t ldv, int T,
                   const double *diag, int64_t diag_len, int nslab, int max_blocks, double *part, int64_t part_len,
                   double *Out, int64_t out_len, int64_t ldo);
+/* launch_kmm32 (cg_mixed.hip: the product with the similarity evaluated in single precision): gogp_test_kmm's arguments and
+ * refusals, plus centre (ndim finite doubles): every coordinate is centred in fp64 before it is rounded to float. */
+int gogp_test_kmm32(int device, const gogp_test_kparams *kparams, const double *A, int64_t a_len, int64_t rows,
+                    const double *B, int64_t b_len, int64_t cols, const double *centre, int64_t centre_len, const double *V,
+                    int64_t v_len, int64_t ldv, int T, const double *diag, int64_t diag_len, int nslab, int max_blocks,
+                    double *part, int64_t part_len, double *Out, int64_t out_len, int64_t ldo);
 /* launch_cg_dots: the T dot products A[t] . B[t] and, by mode (0 plain, 1 |b|^2, 2 rho0, 3 p^T q, 4 |r|^2 and the freeze
  * test, 5 beta), the update of sc / st (in / out).  part (in / out): T x gogp_test_cg_dot_blocks(n); out (in / out, T;
  * NULL with length 0 except in mode 0) receives the dot products. */
