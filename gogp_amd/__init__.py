@@ -10,7 +10,7 @@ constructing a ``GP`` raises if the library or a HIP device is missing.
 """
 from . import kernel  # noqa: F401
 
-__all__ = ["kernel", "gp", "vecchia", "CGModel", "VecchiaModel"]
+__all__ = ["kernel", "gp", "vecchia", "CGModel", "VecchiaModel", "VecchiaBlockModel"]
 __version__ = "0.1.0"
 
 
@@ -22,6 +22,9 @@ def __getattr__(name):
     if name == "VecchiaModel":  # Vecchia's approximation as an objective (gp.VecchiaModel)
         from .gp import VecchiaModel
         return VecchiaModel
+    if name == "VecchiaBlockModel":  # ... on blocks of targets (gp.VecchiaBlockModel)
+        from .gp import VecchiaBlockModel
+        return VecchiaBlockModel
     if name == "vecchia":  # the host helpers that build neighbour tables (numpy only)
         import importlib
         return importlib.import_module(".vecchia", __name__)

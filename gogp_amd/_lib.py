@@ -174,6 +174,16 @@ SYMBOLS = [
     ("gogp_vecchia_reneighbour", ctypes.c_int, [_h, _dp]),
     ("gogp_vecchia_get_neighbours", ctypes.c_int, [_h, ctypes.POINTER(ctypes.c_int32)]),
     ("gogp_vecchia_produce_nearest", ctypes.c_int, [_h, _dp, _i64, _dp, _dp, _dp, ctypes.POINTER(ctypes.c_int32)]),
+    ("gogp_vecchia_blocks_check", ctypes.c_int,
+     [ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), _i64, ctypes.c_int32, _i64]),
+    ("gogp_vecchia_blocks_set_data", ctypes.c_int,
+     [_h, _dp, _dp, _dp, _i64, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+      _i64, ctypes.c_int32]),
+    ("gogp_vecchia_blocks_observe", ctypes.c_int, [_h, _dp, _i64, _dp, _dp]),
+    ("gogp_vecchia_blocks_gradient", ctypes.c_int, [_h, _dp, _i64]),
+    ("gogp_vecchia_blocks_produce", ctypes.c_int,
+     [_h, _dp, _i64, ctypes.POINTER(_i64), _i64, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
+      _dp, _dp]),
     ("gogp_observe_gradient_batch", ctypes.c_int,
      [ctypes.POINTER(_h), ctypes.c_int, _dp, _i64, _dp, _dp, ctypes.POINTER(ctypes.c_int)]),
     ("gogp_observe_gradient_candidates", ctypes.c_int,

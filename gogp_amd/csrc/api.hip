@@ -271,6 +271,7 @@ extern "C" void gogp_destroy(gogp_handle *h) {
   sparse_free(h);
   h->cg.release();
   h->vc.release();
+  h->vb.release();
   free_n_buffers(h);
   free_m_buffers(h);
   free_cand_buffers(h);
@@ -5379,6 +5380,12 @@ extern "C" int gogp_set_option(gogp_handle *h, const char *name, int64_t value) 
     if (h->prec == 32 || h->dist) return fail(h, GOGP_EARG, (std::string("cg_precision: ") + sparse_refusal(h)).c_str());
     if (value != 32 && value != 64) return fail(h, GOGP_EARG, "cg_precision must be 32 or 64");
     h->cg.precision = (int)value;
+    return GOGP_OK;
+  }
+  if (strcmp(name, "vecchia_blocks_grid") == 0) {  // gogp_vecchia_blocks_*: workgroups at most (0: the default); no block's bits depend on it
+    if (value < 0 || value > VBLOCKS_GRID_MAX) return fail(h, GOGP_EARG, "vecchia_blocks_grid must be 0..1024");
+    h->vb.grid = (int)value;
+    h->vb.observed = false;  // (the sums over the workgroups are regrouped)
     return GOGP_OK;
   }
   if (strcmp(name, "laplace_max_iter") == 0) {  // gogp_laplace_observe: Newton steps at the most

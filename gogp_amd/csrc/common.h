@@ -696,6 +696,25 @@ void launch_vecchia_observe(hipStream_t s, const DevParams *p, int ndim, int ard
 void launch_vecchia_produce(hipStream_t s, const DevParams *p, int ndim, const double *X, const double *y, const double *v,
                             const double *Z, int64_t mz, const int *nbrz, int m, double *mu, double *sigma,
                             long long *fpart, long long *info, int max_blocks = 0);
+// vecchia_blocks.hip (gogp_vecchia_blocks_*): blocks of targets on a shared conditioning set, one workgroup per block (the
+// head of vecchia_blocks.hip states the model and the kernel).  tbl: nb rows of w <= 128 int32, row k holding nc[k]
+// conditioning rows, then nt[k] targets, as gogp_vecchia_blocks_check accepts them -- the kernel indexes X, y and v with
+// them unchecked.  launch_vblocks_observe: value != nullptr: the value's pass -- terms (N x 3, through the targets' rows;
+// nullptr: not written), value[0], info[0] = the lowest BLOCK with a bad pivot + 1, or 0; partials != nullptr
+// (vblocks_grid(nb) * NACC doubles): the gradient's pass(es) into gout.  vpart / fpart: vblocks_grid(nb) entries each; the
+// launchers zero them and run one launch per round of vblocks_grid(nb) blocks.
+// launch_vblocks_produce: group g's test points are the rows goff[g] .. goff[g + 1] - 1 of Z, its conditioning rows the
+// first ncz[g] entries of row g of tblz (ng x wz).  max_grid > 0 caps the grid below VBLOCKS_GRID_MAX (tests, and the
+// option "vecchia_blocks_grid": workgroups that walk several blocks at a small size); no block's bits depend on it.
+constexpr int GOGP_VBLOCK_ROWS = 128;   // rows of a block at most
+constexpr int VBLOCKS_GRID_MAX = 1024;  // workgroups (rows of `partials`) of a round at most; a CU holds one at a time
+int vblocks_grid(int64_t nb, int max_grid = 0);
+void launch_vblocks_observe(hipStream_t s, const DevParams *p, int ard_dims, const double *X, const double *y, const double *v,
+                            const int *tbl, const int *nc, const int *nt, int nb, int w, double *terms, double *partials,
+                            double *vpart, long long *fpart, double *gout, double *value, long long *info, int max_grid = 0);
+void launch_vblocks_produce(hipStream_t s, const DevParams *p, const double *X, const double *y, const double *v,
+                            const double *Z, const long long *goff, int ng, const int *tblz, int wz, const int *ncz, double *mu,
+                            double *sigma, long long *fpart, long long *info, int max_grid = 0);
 // vecchia_knn.hip (gogp_vecchia_neighbours, ..._set_data_nearest, ..._reneighbour, ..._produce_nearest): the exact
 // nearest-neighbour tables of gogp_amd/vecchia.py, integer for integer (the head of vecchia_knn.hip states the definition
 // and the kernel).  launch_vknn_scale: xs = x / lengths per dimension (lengths: ndim doubles on the device, or nullptr: a

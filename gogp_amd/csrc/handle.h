@@ -127,6 +127,32 @@ struct VecchiaState {
   }
 };
 
+// The state of the Vecchia block calls (vecchia_api.hip: gogp_vecchia_blocks_*), a data set of this family's own.  Device
+// memory: X, y and v (N (D + 2) doubles), the table (4 nb (w + 2) bytes), the terms (3 N doubles, from the first observe
+// that asks for them) and at most VBLOCKS_GRID_MAX partial rows with the workgroups' values and failure words.
+struct VecchiaBlocksState {
+  double *X = nullptr, *y = nullptr, *v = nullptr;  // N x D, N, N (nullptr: no variances)
+  int *tbl = nullptr, *nc = nullptr, *nt = nullptr;  // nb x w row-major, nb, nb
+  DevParams *P = nullptr;                            // the parameters of the last observe
+  int64_t N = 0;
+  int nb = 0, w = 0;
+  int grid = 0;         // option "vecchia_blocks_grid": workgroups at most (0: vblocks_grid's own cap); kept across set_data
+  bool have = false, observed = false;
+  double dnoise = 0.0;  // d noise_var / d log(noise parameter) at the last observe's theta
+  Workspace small;      // value, info word, NACC slot sums, the workgroups' values, failure words and partial rows
+  Workspace terms;      // N x 3
+  Workspace prod;       // gogp_vecchia_blocks_produce: Z, the offsets, the table, mu, sigma, the failure words
+  void release() {  // leaves the state of a new handle, the option apart
+    for (double *q : {X, y, v}) (void)hipFree(q);
+    for (int *q : {tbl, nc, nt}) (void)hipFree(q);
+    (void)hipFree(P);
+    for (Workspace *ws : {&small, &terms, &prod}) ws->release();
+    const int keep = grid;
+    *this = VecchiaBlocksState();
+    grid = keep;
+  }
+};
+
 // What an evaluation leaves in the handle; a candidates call saves it and puts it back
 struct EvalState {
   bool factored = false, have_alpha = false, have_kinv = false;
@@ -331,6 +357,7 @@ struct gogp_handle : EvalBufs, EvalState {
   // data set of its own, resident; nothing of the handle's other state is touched
   CgHandleState cg;
   VecchiaState vc;
+  VecchiaBlocksState vb;  // ... and its blocks of targets (gogp_vecchia_blocks_*)
   // the Laplace approximation (gogp_laplace_*, laplace.hip; api.hip: LapVecs).  B's factor lies in bufL / Dinv, B^-1 and
   // then the gradient's weight matrix in bufA; only vectors are its own (released with the N buffers).
   Workspace lap_ws;

@@ -1,4 +1,5 @@
-// vecchia_api.hip -- C ABI of Vecchia's approximation (gogp_vecchia_*): host code; kernels in vecchia.hip and vecchia_knn.hip.
+// vecchia_api.hip -- C ABI of Vecchia's approximation (gogp_vecchia_*): host code; kernels in vecchia.hip, vecchia_blocks.hip and
+// vecchia_knn.hip.
 // include/gogp_hip.h states the approximation and the table; DESIGN.md section 4, "Vecchia".  One kernel does all the
 // work; everything runs on the handle's main stream with buffers of the family's own, and the parameters are a copy of
 // the family's own, so that devP keeps what the last dense evaluation uploaded.
@@ -402,4 +403,247 @@ extern "C" int gogp_vecchia_produce_nearest(gogp_handle *h, const double *Z, int
     return refuse(h, who, GOGP_ESTATE, "lengths: the resident table is the caller's, so it has none to take");
   if (const int rc = vecchia_knn_args(h, who, lengths, vc.m)) return rc;
   return vecchia_produce_run(h, who, Z, mz, nullptr, true, lengths ? lengths : vc.scaled ? vc.lengths : nullptr, mu, sigma, nbrz);
+}
+
+// ---- Vecchia on blocks of targets (vecchia_blocks.hip): gogp_vecchia_blocks_* ----------------------------------------------
+// A call family beside the one above, with a state of its own (handle.h: VecchiaBlocksState); DESIGN.md section 4,
+// "Vecchia: blocks of targets".
+// NULL, or what is wrong with the shape of a block table (w, the counts, the entries' range and the -1 padding)
+static const char *vblocks_shape_refusal(const int32_t *tbl, const int32_t *nc, const int32_t *nt, int64_t nb, int32_t w,
+                                         int64_t n, bool produce, int64_t *bad) {
+  *bad = -1;
+  if (w < (produce ? 0 : 1) || w > GOGP_VECCHIA_BLOCK_MAX || nb < 0 || nb > INT32_MAX || n < 0) return "need 1 <= w <= 128, nb >= 0";
+  if (nb > 0 && (!nc || (!produce && !nt) || (w > 0 && !tbl))) return "NULL";
+  for (int64_t k = 0; k < nb; ++k) {
+    *bad = k;
+    const int32_t c = nc[k], t = produce ? 0 : nt[k];
+    if (c < 0 || t < (produce ? 0 : 1) || (int64_t)c + t > w) return "needs nc >= 0, nt >= 1, nc + nt <= w";
+    const int32_t *r = tbl + k * w;
+    for (int32_t a = 0; a < w; ++a) {
+      if (a >= c + t) {
+        if (r[a] != -1) return "holds something other than -1 behind its entries";
+        continue;
+      }
+      if (r[a] < 0 || (int64_t)r[a] >= n) return "holds an index outside [0, N)";
+      for (int32_t b = 0; b < a; ++b)
+        if (r[b] == r[a]) return "holds a row twice";
+    }
+  }
+  *bad = -1;
+  return nullptr;
+}
+
+// NULL, or why the table is no valid joint density; *bad: the offending block, or -1
+static const char *vblocks_refusal(const int32_t *tbl, const int32_t *nc, const int32_t *nt, int64_t nb, int32_t w, int64_t n,
+                                   int64_t *bad) {
+  if (const char *why = vblocks_shape_refusal(tbl, nc, nt, nb, w, n, false, bad)) return why;
+  std::vector<int32_t> owner((size_t)n, -1);  // the block a row is a target of
+  for (int64_t k = 0; k < nb; ++k) {
+    *bad = k;
+    const int32_t *r = tbl + k * w;
+    for (int32_t a = 0; a < nc[k]; ++a)
+      if (owner[r[a]] < 0) return "conditions on a row that is no target of an earlier block";
+    for (int32_t a = nc[k]; a < nc[k] + nt[k]; ++a) {
+      if (owner[r[a]] >= 0) return "targets a row another block targets";
+      owner[r[a]] = (int32_t)k;
+    }
+  }
+  *bad = -1;
+  for (int64_t i = 0; i < n; ++i)
+    if (owner[i] < 0) return "a row of the data is the target of no block";
+  return nullptr;
+}
+
+extern "C" int gogp_vecchia_blocks_check(const int32_t *tbl, const int32_t *nc, const int32_t *nt, int64_t nb, int32_t w,
+                                         int64_t n) {
+  int64_t bad;
+  return vblocks_refusal(tbl, nc, nt, nb, w, n, &bad) ? GOGP_EARG : GOGP_OK;
+}
+
+static int vblocks_refuse_table(gogp_handle *h, const char *who, const char *why, int64_t bad) {
+  char buf[320];
+  if (bad >= 0) snprintf(buf, sizeof buf, "%s: block %lld of the table %s (gogp_vecchia_blocks_check)", who, (long long)bad, why);
+  else snprintf(buf, sizeof buf, "%s: the table: %s (gogp_vecchia_blocks_check)", who, why);
+  return fail(h, GOGP_EARG, buf);
+}
+
+extern "C" int gogp_vecchia_blocks_set_data(gogp_handle *h, const double *X, const double *y, const double *v, int64_t N,
+                                            const int32_t *tbl, const int32_t *nc, const int32_t *nt, int64_t nb, int32_t w) {
+  const char *who = "vecchia_blocks_set_data";
+  if (!h) return GOGP_EARG;
+  VecchiaBlocksState &vb = h->vb;
+  if (N == 0 && !X && !y && !v && !tbl && !nc && !nt) {  // clear
+    HIPCHK(h, hipSetDevice(h->device));
+    vb.release();
+    return GOGP_OK;
+  }
+  if (const int rc = refuse_handle(h, who)) return rc;
+  if (N < 1 || !X || !y) return refuse(h, who, GOGP_EARG, "need X, y and N >= 1 (N == 0 with NULLs clears)");
+  if (N > INT32_MAX) return refuse(h, who, GOGP_EARG, "the table's indices are int32: N <= 2^31 - 1");
+  int64_t bad;
+  if (const char *why = vblocks_refusal(tbl, nc, nt, nb, w, N, &bad)) return vblocks_refuse_table(h, who, why, bad);
+  const int D = h->D;
+  if (const char *why = resident_data_refusal(X, y, v, N, D)) return refuse(h, who, GOGP_EARG, why);
+  HIPCHK(h, hipSetDevice(h->device));
+  if (h->s) HIPCHK(h, hipStreamSynchronize(h->s));
+  vb.release();
+  const size_t xb = (size_t)N * D * sizeof(double), yb = (size_t)N * sizeof(double);
+  const size_t tb = (size_t)nb * (size_t)w * sizeof(int32_t), cb = (size_t)nb * sizeof(int32_t);
+  hipStream_t s = h->s;
+  hipError_t e = hipMalloc(&vb.X, xb);
+  if (e == hipSuccess) e = hipMalloc(&vb.y, yb);
+  if (e == hipSuccess && v) e = hipMalloc(&vb.v, yb);
+  if (e == hipSuccess) e = hipMalloc(&vb.tbl, tb);
+  if (e == hipSuccess) e = hipMalloc(&vb.nc, cb);
+  if (e == hipSuccess) e = hipMalloc(&vb.nt, cb);
+  if (e == hipSuccess) e = hipMalloc(&vb.P, sizeof(DevParams));
+  if (e == hipSuccess) e = hipMemcpyAsync(vb.X, X, xb, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(vb.y, y, yb, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess && v) e = hipMemcpyAsync(vb.v, v, yb, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(vb.tbl, tbl, tb, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(vb.nc, nc, cb, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(vb.nt, nt, cb, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e != hipSuccess) {
+    vb.release();
+    HIPCHK(h, e);
+  }
+  vb.N = N;
+  vb.nb = (int)nb;
+  vb.w = w;
+  vb.have = true;
+  return GOGP_OK;
+}
+
+// One pass of the kernel over the stored blocks: the value's (grad false) or the gradient's.  The stream is idle on return.
+static int vblocks_run(gogp_handle *h, bool grad, double *dterms, double *value, long long *info, double *acc) {
+  VecchiaBlocksState &vb = h->vb;
+  hipStream_t s = h->s;
+  const int grid = vblocks_grid(vb.nb, vb.grid);
+  VecchiaSmall sm;
+  const size_t bytes = vecchia_small_layout(nullptr, grid, &sm);
+  if (const int rc = vb.small.reserve(h, bytes)) return rc;
+  vecchia_small_layout(vb.small.as<char>(), grid, &sm);
+  launch_vblocks_observe(s, vb.P, h->ard_dims, vb.X, vb.y, vb.v, vb.tbl, vb.nc, vb.nt, vb.nb, vb.w, dterms,
+                         grad ? sm.partials : nullptr, sm.vpart, sm.fpart, sm.gout, grad ? nullptr : sm.value,
+                         grad ? nullptr : sm.info, vb.grid);
+  if (grad) {
+    HIPCHK(h, hipMemcpyAsync(acc, sm.gout, NACC * sizeof(double), hipMemcpyDeviceToHost, s));
+  } else {
+    HIPCHK(h, hipMemcpyAsync(value, sm.value, sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(info, sm.info, sizeof(long long), hipMemcpyDeviceToHost, s));
+  }
+  HIPCHK(h, hipStreamSynchronize(s));
+  HIPCHK(h, hipGetLastError());
+  return GOGP_OK;
+}
+
+extern "C" int gogp_vecchia_blocks_observe(gogp_handle *h, const double *x, int64_t len, double *lml, double *terms) {
+  const char *who = "vecchia_blocks_observe";
+  if (!h) return GOGP_EARG;
+  if (!x || !lml) return refuse(h, who, GOGP_EARG, "NULL");
+  if (const int rc = refuse_handle(h, who)) return rc;
+  if (len != h->P) return refuse(h, who, GOGP_EARG, "len(x)");
+  for (int64_t i = 0; i < len; ++i)
+    if (!std::isfinite(x[i])) return refuse(h, who, GOGP_EARG, "non-finite parameter");
+  VecchiaBlocksState &vb = h->vb;
+  if (!vb.have) return refuse(h, who, GOGP_ESTATE, "no data (gogp_vecchia_blocks_set_data)");
+  std::vector<double> th(h->P > 0 ? h->P : 1);
+  for (int i = 0; i < h->P; ++i) th[i] = exp(x[i]);
+  if (const char *why = theta_refusal(h, th.data(), th.data() + h->ns)) return refuse(h, who, GOGP_EARG, why);
+  DevParams hp;
+  fill_params_theta(h, th.data(), th.data() + h->ns, hp);
+  HIPCHK(h, hipSetDevice(h->device));
+  hipStream_t s = h->s;
+  vb.observed = false;
+  vb.dnoise = hp.dnoise;
+  HIPCHK(h, hipMemcpyAsync(vb.P, &hp, sizeof hp, hipMemcpyHostToDevice, s));
+  HIPCHK(h, hipStreamSynchronize(s));  // hp is a local
+  double *dterms = nullptr;
+  if (terms) {
+    if (const int rc = vb.terms.reserve(h, (size_t)vb.N * 3 * sizeof(double))) return rc;
+    dterms = vb.terms.as<double>();
+  }
+  double value = 0.0;
+  long long info = 0;
+  if (const int rc = vblocks_run(h, false, dterms, &value, &info, nullptr)) return rc;
+  if (terms) HIPCHK(h, hipMemcpy(terms, dterms, (size_t)vb.N * 3 * sizeof(double), hipMemcpyDeviceToHost));
+  if (info != 0) {
+    *lml = NAN;
+    return vecchia_notpd(h, who, info, "block");
+  }
+  *lml = value;
+  vb.observed = true;
+  return GOGP_OK;
+}
+
+extern "C" int gogp_vecchia_blocks_gradient(gogp_handle *h, double *grad, int64_t len) {
+  const char *who = "vecchia_blocks_gradient";
+  if (!h) return GOGP_EARG;
+  if (!grad) return refuse(h, who, GOGP_EARG, "NULL");
+  if (const int rc = refuse_handle(h, who)) return rc;
+  if (len != h->P) return refuse(h, who, GOGP_EARG, "len(grad)");
+  VecchiaBlocksState &vb = h->vb;
+  if (!vb.have || !vb.observed) return refuse(h, who, GOGP_ESTATE, "nothing observed (gogp_vecchia_blocks_observe)");
+  HIPCHK(h, hipSetDevice(h->device));
+  double acc[NACC];
+  if (const int rc = vblocks_run(h, true, nullptr, nullptr, nullptr, acc)) return rc;
+  for (int64_t i = 0; i < len; ++i) grad[i] = 0.0;
+  assemble_gradient(h, acc, vb.dnoise, grad);
+  return GOGP_OK;
+}
+
+extern "C" int gogp_vecchia_blocks_produce(gogp_handle *h, const double *Z, int64_t mz, const int64_t *goff, int64_t ng,
+                                           const int32_t *tblz, int32_t wz, const int32_t *ncz, double *mu, double *sigma) {
+  const char *who = "vecchia_blocks_produce";
+  if (const int rc = refuse_handle(h, who)) return rc;
+  if (mz < 0 || ng < 0 || (mz > 0 && (!Z || !mu)) || (ng > 0 && !goff))
+    return refuse(h, who, GOGP_EARG, "need Z and mu for mz > 0, goff for ng > 0, mz >= 0, ng >= 0");
+  VecchiaBlocksState &vb = h->vb;
+  if (!vb.have || !vb.observed) return refuse(h, who, GOGP_ESTATE, "nothing observed (gogp_vecchia_blocks_observe)");
+  if (ng == 0 ? mz != 0 : (goff[0] != 0 || goff[ng] != mz)) return refuse(h, who, GOGP_EARG, "goff: need goff[0] = 0 and goff[ng] = mz");
+  for (int64_t g = 0; g < ng; ++g)
+    if (goff[g + 1] < goff[g]) return refuse(h, who, GOGP_EARG, "goff: the offsets must not decrease");
+  int64_t bad;
+  if (const char *why = vblocks_shape_refusal(tblz, ncz, nullptr, ng, wz, vb.N, true, &bad)) return vblocks_refuse_table(h, who, why, bad);
+  const int D = h->D;
+  for (int64_t i = 0; i < mz * D; ++i)
+    if (!std::isfinite(Z[i])) return refuse(h, who, GOGP_EARG, "non-finite test point");
+  if (mz == 0) return GOGP_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  hipStream_t s = h->s;
+  const int grid = vblocks_grid(ng, vb.grid);
+  Carve c{nullptr};
+  auto layout = [&](Carve &cv, double *&dZ, double *&dmu, double *&dsig, long long *&doff, int *&dtb, int *&dnc, long long *&dfp,
+                    long long *&dinfo) {
+    dZ = cv.take<double>((size_t)mz * D);
+    dmu = cv.take<double>((size_t)mz);
+    dsig = cv.take<double>((size_t)mz);
+    doff = cv.take<long long>((size_t)ng + 1);
+    dtb = cv.take<int>(std::max<size_t>((size_t)ng * (size_t)wz, 1));
+    dnc = cv.take<int>((size_t)ng);
+    dfp = cv.take<long long>((size_t)grid);
+    dinfo = cv.take<long long>(1);
+  };
+  double *dZ, *dmu, *dsig;
+  long long *doff, *dfp, *dinfo;
+  int *dtb, *dnc;
+  layout(c, dZ, dmu, dsig, doff, dtb, dnc, dfp, dinfo);
+  if (const int rc = vb.prod.reserve(h, c.off)) return rc;
+  Carve c2{vb.prod.as<char>()};
+  layout(c2, dZ, dmu, dsig, doff, dtb, dnc, dfp, dinfo);
+  static_assert(sizeof(long long) == sizeof(int64_t), "the offsets go up as they are");
+  HIPCHK(h, hipMemcpyAsync(dZ, Z, (size_t)mz * D * sizeof(double), hipMemcpyHostToDevice, s));
+  HIPCHK(h, hipMemcpyAsync(doff, goff, ((size_t)ng + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
+  if (wz > 0) HIPCHK(h, hipMemcpyAsync(dtb, tblz, (size_t)ng * (size_t)wz * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  HIPCHK(h, hipMemcpyAsync(dnc, ncz, (size_t)ng * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  launch_vblocks_produce(s, vb.P, vb.X, vb.y, vb.v, dZ, doff, (int)ng, dtb, wz, dnc, dmu, sigma ? dsig : nullptr, dfp, dinfo, vb.grid);
+  long long info = 0;
+  HIPCHK(h, hipMemcpyAsync(mu, dmu, (size_t)mz * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (sigma) HIPCHK(h, hipMemcpyAsync(sigma, dsig, (size_t)mz * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipMemcpyAsync(&info, dinfo, sizeof info, hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipStreamSynchronize(s));
+  HIPCHK(h, hipGetLastError());
+  if (info != 0) return vecchia_notpd(h, who, info, "group");
+  return GOGP_OK;
 }

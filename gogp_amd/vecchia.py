@@ -92,3 +92,73 @@ def nearest_to(x, z, m: int, lengths=None, chunk: int = 1024) -> np.ndarray:
         r1 = min(mz, r0 + max(int(chunk), 1))
         out[r0:r1, :k] = _smallest(_d2(zs[r0:r1], xs), k)
     return out
+
+
+# ---- blocks of targets on a shared conditioning set (GP.SetVecchiaBlocks, GP.VecchiaBlockProduce) ---------------------------
+MAX_BLOCK = 128
+
+
+def _block_ok(t: int, c: int):
+    t, c = int(t), int(c)
+    if t < 1 or c < 0 or t + c > MAX_BLOCK:
+        raise ValueError("blocks: t >= 1 targets, c >= 0 conditioning rows, t + c <= %d" % MAX_BLOCK)
+    return t, c
+
+
+def _pack(cond, targ, w):
+    tbl = np.full((len(cond), w), -1, dtype=np.int32)
+    for k, (a, b) in enumerate(zip(cond, targ)):
+        tbl[k, :len(a)] = a
+        tbl[k, len(a):len(a) + len(b)] = b
+    return (tbl, np.array([len(a) for a in cond], dtype=np.int32), np.array([len(b) for b in targ], dtype=np.int32))
+
+
+def block_previous(n: int, t: int, c: int):
+    """(tbl, nc, nt) of consecutive blocks of t targets (the last one shorter), each conditioned on the c rows before its
+    first target, the latest first.  block_previous(n, 1, m) names the rows of previous(n, m)."""
+    t, c = _block_ok(t, c)
+    n = int(n)
+    starts = range(0, n, t)
+    cond = [np.arange(s - 1, max(s - c, 0) - 1, -1) for s in starts]
+    targ = [np.arange(s, min(s + t, n)) for s in starts]
+    return _pack(cond, targ, t + c)
+
+
+def block_nearest(x, t: int, c: int, lengths=None):
+    """(tbl, nc, nt) of consecutive blocks of t targets in the given order, each conditioned on the c EARLIER rows (rows
+    before its first target) nearest to the block's centroid under the Euclidean distance of x / lengths, nearest first,
+    ties to the lower index.  O(N^2 D / t) on the host.  block_nearest(x, 1, m) names the rows of nearest(x, m)."""
+    t, c = _block_ok(t, c)
+    xs = _scaled(x, lengths)
+    n = len(xs)
+    cond, targ = [], []
+    for s in range(0, n, t):
+        e = min(s + t, n)
+        k = min(c, s)
+        if k:
+            cen = xs[s:e].mean(axis=0, keepdims=True) if e - s > 1 else xs[s:e]
+            cond.append(_smallest(_d2(cen, xs[:s]), k)[0])
+        else:
+            cond.append(np.zeros(0, dtype=np.int64))
+        targ.append(np.arange(s, e))
+    return _pack(cond, targ, t + c)
+
+
+def group_nearest_to(x, z, g: int, c: int, lengths=None):
+    """For GP.VecchiaBlockProduce: consecutive groups of g test points (rows of z), each conditioned on the c rows of x
+    nearest to the group's centroid.  Returns (offsets, (tbl, nc)): ng + 1 offsets into z, the ng x c table and counts."""
+    g, c = int(g), int(c)
+    if g < 1 or not 0 <= c <= MAX_BLOCK:
+        raise ValueError("group_nearest_to: g >= 1 test points, 0 <= c <= %d conditioning rows" % MAX_BLOCK)
+    xs = _scaled(x, lengths)
+    zs = _scaled(z, lengths, xs.shape[1])
+    if zs.shape[1] != xs.shape[1]:
+        raise ValueError("group_nearest_to: x and z differ in dimension")
+    mz, k = len(zs), min(c, len(xs))
+    offsets = np.append(np.arange(0, mz, g, dtype=np.int64), mz) if mz else np.zeros(1, dtype=np.int64)
+    cond = []
+    for a, b in zip(offsets[:-1], offsets[1:]):
+        cen = zs[a:b].mean(axis=0, keepdims=True) if b - a > 1 else zs[a:b]
+        cond.append(_smallest(_d2(cen, xs), k)[0] if k else np.zeros(0, dtype=np.int64))
+    tbl, nc, _ = _pack(cond, [()] * len(cond), c)
+    return offsets, (tbl, nc)

@@ -780,6 +780,51 @@ int gogp_vecchia_get_neighbours(gogp_handle *h, int32_t *nbr /* N x m */);
 int gogp_vecchia_produce_nearest(gogp_handle *h, const double *Z, int64_t mz, const double *lengths /* may be NULL */,
                                  double *mu, double *sigma /* may be NULL */, int32_t *nbrz /* mz x m, may be NULL */);
 
+/* Vecchia's approximation on blocks of targets that share a conditioning set (vecchia_blocks.hip; block NNGP, Quiroz et
+ * al. 2019; Guinness 2018, "grouping"):
+ *     log p(y) ~ sum_k log p(y_T(k) | y_C(k)),
+ * block k predicting its nt_k targets T(k) jointly from its nc_k conditioning rows C(k), nc_k + nt_k <= 128.  The density
+ * is exact inside a block, target q of a block conditions on nc_k + q rows, and one factorisation of nc_k + nt_k rows
+ * serves nt_k targets (one workgroup per block, on the matrix cores).  With nt = 1 everywhere it is the model of
+ * gogp_vecchia_*; with one block and nc = 0 it is the exact LML.  Per block b = [C..., T...], K_b = k(X_b, X_b) + sigma^2 I +
+ * diag(v_b), L = chol(K_b), z = L^-1 y_b, the terms of target row q >= nc_k are
+ *     mu_q = y_q - L_qq z_q,   s_q = L_qq,   log p_q = -1/2 log 2 pi - log L_qq - 1/2 z_q^2:
+ * the conditional on C(k) and on the block's EARLIER targets; their sum over the block is its joint log density.
+ * The table: nb rows of w int32 (1 <= w <= 128), row-major, with nc[nb] and nt[nb]: entries [0, nc_k) of row k are the
+ * conditioning rows, [nc_k, nc_k + nt_k) the targets in the order in which they are predicted, the rest -1; nt_k >= 1,
+ * nc_k + nt_k <= w.  gogp_vecchia_blocks_check (host only) returns GOGP_OK iff every row 0 .. n - 1 is a target of exactly
+ * one block, no row appears twice in a block, and every conditioning row of block k is a target of a block before k --
+ * which makes the sum a valid joint density.  The order within a row is kept: it fixes the bits.
+ * The data are a set of this family's own (gogp_vecchia_blocks_set_data copies X, y, v -- NULL: none -- and the table to
+ * the device; N == 0 with NULLs clears them); nothing else of the handle changes.  New data or a new theta drop what was
+ * stored: gradient and produce want an observe after them.
+ * gogp_vecchia_blocks_observe: the value at x = log theta into *lml and, unless NULL, the terms (N x 3, row i those of
+ * data row i).  gogp_vecchia_blocks_gradient: d value / d log theta at the last observe's theta, the exact derivative of
+ * the value, the noise parameter's component included.
+ * gogp_vecchia_blocks_produce: ng groups of test points; group g is the rows goff[g] .. goff[g + 1] - 1 of Z (goff[0] = 0,
+ * goff[ng] = mz, non-decreasing) and shares the ncz[g] <= wz <= 128 conditioning rows in row g of tblz (ng x wz: distinct
+ * indices in [0, N), then -1): K_C is factored once per group; mu_j and, unless NULL, sigma_j are the latent, unclamped
+ * predictive mean and deviation of gogp_produce on those rows.
+ * Option "vecchia_blocks_grid" (gogp_set_option; 0, the default, or 1 .. 1024): the workgroups of a launch at most; a
+ * block's terms have the same bits whatever it is, the sums over blocks are grouped by it.
+ * Identical calls give identical bits (fixed-order sums, no atomics), and a block's terms have the same bits whatever
+ * else is in the call.  Errors as gogp_vecchia_*: GOGP_EARG for NULL pointers, non-finite values, a bad table, len != P,
+ * precision = 32, sharded and event-discount handles; GOGP_ESTATE for observe before set_data, gradient or produce before
+ * observe; GOGP_ENOTPD: a block has a pivot that is not positive and finite -- gogp_notpd_index is the LOWEST such block
+ * (group for produce), its targets' outputs are NaN, every other block's are written, *lml is NaN.
+ * DESIGN.md section 4, "Vecchia: blocks of targets". */
+#define GOGP_VECCHIA_BLOCK_MAX 128
+int gogp_vecchia_blocks_check(const int32_t *tbl, const int32_t *nc, const int32_t *nt, int64_t nb, int32_t w, int64_t n);
+int gogp_vecchia_blocks_set_data(gogp_handle *h, const double *X, const double *y, const double *v /* may be NULL */,
+                                 int64_t N, const int32_t *tbl /* nb x w, row-major */, const int32_t *nc, const int32_t *nt,
+                                 int64_t nb, int32_t w);
+int gogp_vecchia_blocks_observe(gogp_handle *h, const double *x /* log theta */, int64_t len, double *lml,
+                                double *terms /* N x 3: mu, s, logp; may be NULL */);
+int gogp_vecchia_blocks_gradient(gogp_handle *h, double *grad, int64_t len);
+int gogp_vecchia_blocks_produce(gogp_handle *h, const double *Z, int64_t mz, const int64_t *goff /* ng + 1 */, int64_t ng,
+                                const int32_t *tblz /* ng x wz */, int32_t wz, const int32_t *ncz, double *mu,
+                                double *sigma /* may be NULL */);
+
 /* k independent Observe + Gradient evaluations at once: handle hs[i] (each created and given
  * its data separately; they may hold the same data) evaluates x[i*len .. (i+1)*len) from its own
  * host thread, so the dependent launch chains of the k evaluations overlap on the GPU.
