@@ -85,6 +85,7 @@ type GP struct {
 	nbasis     int // basis columns of SetBasis
 	sparseM    int // inducing points of SetSparse
 	sparseT    int // output columns of SetSparseOutputs
+	vbNb, vbW  int // the table of SetVecchiaBlocksNearest: vbNb x vbW
 	upX        *[]float64 // &gp.X[0] at the time of the last upload
 	upY        *float64   // &gp.Y[0] at the time of the last upload
 	upN        int
@@ -919,6 +920,97 @@ func (gp *GP) SparseProduce(x [][]float64) (mu, sigma []float64, err error) {
 		return nil, nil, err
 	}
 	return mu, sigma, nil
+}
+
+func i32ptr(s []int32) *C.int32_t {
+	if len(s) == 0 {
+		return nil
+	}
+	return (*C.int32_t)(unsafe.Pointer(&s[0]))
+}
+
+func flatRows(x [][]float64, ndim int) []float64 {
+	flat := make([]float64, len(x)*ndim)
+	for i, row := range x {
+		copy(flat[i*ndim:], row)
+	}
+	return flat
+}
+
+// VecchiaBlockTables builds on the device the table of Vecchia's block
+// approximation (no reference counterpart): consecutive blocks of t rows of x
+// (row-major N x NDim), each conditioned on the c earlier rows nearest to its
+// centroid under the distance of x / lengths (nil: unscaled).  z nil: tbl is
+// nb x (t + c) with counts nc and nt; else the groups of t rows of z over all
+// of x: tbl is ng x c with nc, and nt is nil.  Nothing of the GP changes.
+func (gp *GP) VecchiaBlockTables(x []float64, t, c int, lengths []float64, z [][]float64) (tbl, nc, nt []int32, err error) {
+	gp.defaults()
+	n, rows, w := len(x)/gp.NDim, len(x)/gp.NDim, t+c
+	if z != nil {
+		rows, w = len(z), c
+	}
+	if t < 1 || c < 0 || n < 1 {
+		return nil, nil, nil, fmt.Errorf("gogp: VecchiaBlockTables: need t >= 1, c >= 0 and rows")
+	}
+	nq := (rows + t - 1) / t
+	tbl, nc = make([]int32, nq*w), make([]int32, nq)
+	var zp *C.double
+	if z != nil {
+		zp = dptr(flatRows(z, gp.NDim))
+	} else {
+		nt = make([]int32, nq)
+	}
+	rc := C.gogp_vecchia_blocks_nearest(gp.handle(), dptr(x), C.int64_t(n), zp, C.int64_t(len(z)), C.int32_t(t), C.int32_t(c),
+		dptr(lengths), i32ptr(tbl), i32ptr(nc), i32ptr(nt))
+	if err = gp.err(rc); err != nil {
+		return nil, nil, nil, err
+	}
+	return tbl, nc, nt, nil
+}
+
+// SetVecchiaBlocksNearest uploads x, y and (unless nil) the noise variances v
+// as the data of the block calls, with the table of VecchiaBlockTables built
+// on the device, where it stays.
+func (gp *GP) SetVecchiaBlocksNearest(x, y, v []float64, t, c int, lengths []float64) error {
+	gp.defaults()
+	if t < 1 || c < 0 {
+		return fmt.Errorf("gogp: SetVecchiaBlocksNearest: need t >= 1 and c >= 0")
+	}
+	gp.vbNb, gp.vbW = (len(y)+t-1)/t, t+c
+	return gp.err(C.gogp_vecchia_blocks_set_data_nearest(gp.handle(), dptr(x), dptr(y), dptr(v), C.int64_t(len(y)),
+		C.int32_t(t), C.int32_t(c), dptr(lengths)))
+}
+
+// VecchiaBlockReneighbour rebuilds the resident block table under new length
+// scales (nil: unscaled), same t and c; the last block observe is dropped.
+func (gp *GP) VecchiaBlockReneighbour(lengths []float64) error {
+	return gp.err(C.gogp_vecchia_blocks_reneighbour(gp.handle(), dptr(lengths)))
+}
+
+// VecchiaBlockTable returns the table SetVecchiaBlocksNearest built.
+func (gp *GP) VecchiaBlockTable() (tbl, nc, nt []int32, err error) {
+	tbl, nc, nt = make([]int32, gp.vbNb*gp.vbW), make([]int32, gp.vbNb), make([]int32, gp.vbNb)
+	if err = gp.err(C.gogp_vecchia_blocks_get_table(gp.handle(), i32ptr(tbl), i32ptr(nc), i32ptr(nt))); err != nil {
+		return nil, nil, nil, err
+	}
+	return tbl, nc, nt, nil
+}
+
+// VecchiaBlockProduceNearest predicts the test points in groups of g, each
+// group conditioned on the c resident rows nearest to its centroid, found on
+// the device (lengths nil: those of the resident table); tbl is ng x c.
+func (gp *GP) VecchiaBlockProduceNearest(x [][]float64, g, c int, lengths []float64) (mu, sigma []float64, tbl []int32, err error) {
+	m := len(x)
+	if g < 1 || c < 0 {
+		return nil, nil, nil, fmt.Errorf("gogp: VecchiaBlockProduceNearest: need g >= 1 and c >= 0")
+	}
+	mu, sigma, tbl = make([]float64, m), make([]float64, m), make([]int32, (m+g-1)/g*c)
+	rc := C.gogp_vecchia_blocks_produce_nearest(gp.handle(), dptr(flatRows(x, gp.NDim)), C.int64_t(m), C.int32_t(g), C.int32_t(c),
+		dptr(lengths), dptr(mu), dptr(sigma), i32ptr(tbl))
+	if err = gp.err(rc); err != nil {
+		return nil, nil, nil, err
+	}
+	return mu, sigma, tbl, nil
 }
 
 // SetSparseOutputs gives the sparse data nout <= 128 output columns observed

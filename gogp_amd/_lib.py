@@ -184,6 +184,14 @@ SYMBOLS = [
     ("gogp_vecchia_blocks_produce", ctypes.c_int,
      [_h, _dp, _i64, ctypes.POINTER(_i64), _i64, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
       _dp, _dp]),
+    ("gogp_vecchia_blocks_nearest", ctypes.c_int,
+     [_h, _dp, _i64, _dp, _i64, ctypes.c_int32, ctypes.c_int32, _dp, ctypes.POINTER(ctypes.c_int32),
+      ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
+    ("gogp_vecchia_blocks_set_data_nearest", ctypes.c_int, [_h, _dp, _dp, _dp, _i64, ctypes.c_int32, ctypes.c_int32, _dp]),
+    ("gogp_vecchia_blocks_reneighbour", ctypes.c_int, [_h, _dp]),
+    ("gogp_vecchia_blocks_get_table", ctypes.c_int, [_h] + [ctypes.POINTER(ctypes.c_int32)] * 3),
+    ("gogp_vecchia_blocks_produce_nearest", ctypes.c_int,
+     [_h, _dp, _i64, ctypes.c_int32, ctypes.c_int32, _dp, _dp, _dp, ctypes.POINTER(ctypes.c_int32)]),
     ("gogp_observe_gradient_batch", ctypes.c_int,
      [ctypes.POINTER(_h), ctypes.c_int, _dp, _i64, _dp, _dp, ctypes.POINTER(ctypes.c_int)]),
     ("gogp_observe_gradient_candidates", ctypes.c_int,
@@ -513,6 +521,13 @@ HOOK_SYMBOLS += [
     ("gogp_test_vecchia_knn", _ci, [_ci, _dp, _i64, _i64, _ci, _dp, _i64, _i64, _dp, _ci, _ci, _ci, _i32p, _i64, _dp, _i64,
                                     _dp, _i64]),
     ("gogp_test_vecchia_knn_plan", _ci, [_i64, _i64, _ci, ctypes.POINTER(_i64)]),
+]
+
+#: the hooks of the selection of vecchia_bknn.hip (tests/test_vecchia_bknn_kernel.py; gp.vecchia_bknn_check, gp.vecchia_bknn_plan)
+HOOK_SYMBOLS += [
+    ("gogp_test_vecchia_bknn", _ci, [_ci, _dp, _i64, _i64, _ci, _dp, _i64, _i64, _dp, _ci, _ci, _ci, _ci, _i32p, _i64, _dp, _i64,
+                                     _i32p, _i64, _dp, _i64]),
+    ("gogp_test_vecchia_bknn_plan", _ci, [_i64, _i64, _ci, ctypes.POINTER(_i64)]),
 ]
 
 

@@ -734,6 +734,27 @@ VknnPlan vknn_plan(int64_t targets, int64_t n, int m, int slabs = 0);
 void launch_vknn_scale(hipStream_t s, const double *x, int64_t rows, int ndim, const double *lengths, double *xs);
 void launch_vknn(hipStream_t s, const double *Xs, int64_t n, const double *Zs, int64_t targets, int ndim, int m, int slabs,
                  int tile_cap, void *ws, int *nbr, double *d2out);
+// vecchia_bknn.hip (gogp_vecchia_blocks_nearest, ..._set_data_nearest, ..._reneighbour, ..._produce_nearest): the tables of
+// gogp_amd/vecchia.py's block_nearest / group_nearest_to, integer for integer (the head of vecchia_bknn.hip states the
+// definition and the kernels).  launch_bknn_centroids: cen (ceil(rows / t) x ndim) of the blocks of t consecutive rows of xs.
+// launch_bknn: Xs the n scaled rows, Cen the nq centroids; t > 0: query k takes the candidates j < min(k t, n) (the causal
+// form), t == 0: all j < n; nbr: nq x c, the keys nearest first, then -1; cnt: nq, the entries taken; d2out (nullptr: not
+// written): their squared distances, 0.0 under the padding; ws: bknn_plan(nq, n, c, qt, slabs).ws_bytes bytes of scratch.
+// qt > 0 forces the queries of a tile (at most 8), slabs > 0 the candidate split (tests); the lists depend on neither.
+// c == 0 launches nothing.  launch_bknn_pack: the table of launch_vblocks_observe -- row k of nb x (t + c): the cnt[k] entries
+// of row k of sel (nb x c), then the targets k t .. min(k t + t, n) - 1, then -1 -- with nc and nt.  n < 2^31, 0 <= c <= 128.
+constexpr size_t BKNN_WS_MAX = (size_t)768 * 8 * 12 * 128;  // tiles * slabs < 768 wherever a search is split
+struct BknnPlan {
+  int qt, slabs;     // tile k holds the queries [k qt, min(queries, (k + 1) qt))
+  int64_t slab_len;  // slab s holds the candidates [s * slab_len, min(n, (s + 1) * slab_len))
+  size_t ws_bytes;
+};
+BknnPlan bknn_plan(int64_t queries, int64_t n, int c, int qt = 0, int slabs = 0);
+void launch_bknn_centroids(hipStream_t s, const double *xs, int64_t rows, int ndim, int64_t t, double *cen);
+void launch_bknn(hipStream_t s, const double *Xs, int64_t n, const double *Cen, int64_t nq, int64_t t, int ndim, int c, int qt,
+                 int slabs, void *ws, int *nbr, int *cnt, double *d2out);
+void launch_bknn_pack(hipStream_t s, const int *sel, const int *cnt, int64_t nb, int64_t n, int t, int c, int *tbl, int *nc,
+                      int *nt);
 // laplace.hip (gogp_laplace_*): the passes around the factorisation of B = I + diag(sw) K diag(sw).  Vectors hold npad
 // doubles (npad a multiple of 256) and leave every launcher zero from row n on.
 // launch_lap_site: g, W, sw = sqrt(W), b = W f + g, rho of the rows i < n; part: 5 * npad / 256 doubles of block results;

@@ -142,11 +142,19 @@ struct VecchiaBlocksState {
   Workspace small;      // value, info word, NACC slot sums, the workgroups' values, failure words and partial rows
   Workspace terms;      // N x 3
   Workspace prod;       // gogp_vecchia_blocks_produce: Z, the offsets, the table, mu, sigma, the failure words
+  // The table's shape and origin (gogp_vecchia_blocks_set_data_nearest, gogp_vecchia_blocks_reneighbour).  t > 0: block k's
+  // targets are the rows k t .. min(k t + t, N) - 1 and w = t + c, which is what the device can rebuild; t == 0: a caller's
+  // table of another shape.  built_here: built on the device from the resident X under these length scales (scaled false:
+  // the unscaled distance); false for a caller's table.
+  int t = 0, c = 0;
+  bool built_here = false, scaled = false;
+  double lengths[GOGP_MAX_NDIM] = {};
+  Workspace knn;        // a search's scratch: the lengths, the scaled copies of X and Z, centroids, lists, partial lists
   void release() {  // leaves the state of a new handle, the option apart
     for (double *q : {X, y, v}) (void)hipFree(q);
     for (int *q : {tbl, nc, nt}) (void)hipFree(q);
     (void)hipFree(P);
-    for (Workspace *ws : {&small, &terms, &prod}) ws->release();
+    for (Workspace *ws : {&small, &terms, &prod, &knn}) ws->release();
     const int keep = grid;
     *this = VecchiaBlocksState();
     grid = keep;

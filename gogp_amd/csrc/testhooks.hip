@@ -2711,3 +2711,40 @@ extern "C" int gogp_test_vecchia_knn(int device, const double *X, int64_t x_len,
     launch_vknn(0, d[5], n, Z ? d[7] : nullptr, targets, ndim, m, slabs, tile_cap, d.as<void>(6), d.as<int>(3), d[4]);
   });
 }
+
+// ---- vecchia_bknn.hip -----------------------------------------------------------------------------------------------------
+extern "C" int gogp_test_vecchia_bknn_plan(int64_t queries, int64_t n, int c, int64_t out[3]) {
+  if (!out || queries < 1 || n < 1 || c < 0 || c > GOGP_VECCHIA_BLOCK_MAX) return GOGP_EARG;
+  const BknnPlan p = bknn_plan(queries, n, c);
+  out[0] = p.qt, out[1] = p.slabs, out[2] = (int64_t)p.ws_bytes;
+  return GOGP_OK;
+}
+
+extern "C" int gogp_test_vecchia_bknn(int device, const double *X, int64_t x_len, int64_t n, int ndim, const double *Z,
+                                      int64_t z_len, int64_t mz, const double *lengths, int t, int c, int qt, int slabs,
+                                      int32_t *nbr, int64_t nbr_len, double *d2, int64_t d2_len, int32_t *cnt, int64_t cnt_len,
+                                      double *cen, int64_t cen_len) {
+  if (!X || !cen || ndim < 1 || ndim > GOGP_MAX_NDIM || t < 1 || c < 0 || c > GOGP_VECCHIA_BLOCK_MAX) return GOGP_EARG;
+  if (qt < 0 || qt > 8 || slabs < 0 || slabs > 256) return GOGP_EARG;
+  if (n < 1 || n > (1 << 20) || x_len < n * ndim) return GOGP_EARG;
+  if (Z ? (mz < 1 || mz > (1 << 20) || z_len < mz * ndim) : (z_len != 0 || mz != 0)) return GOGP_EARG;
+  const int64_t rows = Z ? mz : n, nq = (rows + t - 1) / t;
+  if (cen_len < nq * ndim) return GOGP_EARG;
+  if (c > 0 && (!nbr || !d2 || !cnt || nbr_len < nq * c || d2_len < nq * c || cnt_len < nq)) return GOGP_EARG;
+  if (lengths)
+    for (int d = 0; d < ndim; ++d)
+      if (!(lengths[d] > 0.0) || !std::isfinite(lengths[d])) return GOGP_EARG;
+  const BknnPlan p = bknn_plan(nq, n, c, qt, slabs);
+  if (p.ws_bytes > ((size_t)1 << 28)) return GOGP_EARG;
+  const std::vector<Arr> arrs = {rd(X, x_len), opt(rd(Z, z_len)), opt(rd(lengths, lengths ? ndim : 0)),
+                                 opt(io(nbr, nbr_len, 4)), opt(io(d2, d2_len)), opt(io(cnt, cnt_len, 4)), io(cen, cen_len),
+                                 scratch(p.ws_bytes), scratch((size_t)n * ndim * sizeof(double)),
+                                 scratch(Z ? (size_t)mz * ndim * sizeof(double) : 0)};
+  if (!have(arrs)) return GOGP_EARG;
+  return run(device, arrs, [&](const Dev &d) {
+    launch_vknn_scale(0, d[0], n, ndim, d[2], d[8]);
+    if (Z) launch_vknn_scale(0, d[1], mz, ndim, d[2], d[9]);
+    launch_bknn_centroids(0, Z ? d[9] : d[8], rows, ndim, t, d[6]);
+    launch_bknn(0, d[8], n, d[6], nq, Z ? 0 : t, ndim, c, qt, slabs, d.as<void>(7), d.as<int>(3), d.as<int>(5), d[4]);
+  });
+}

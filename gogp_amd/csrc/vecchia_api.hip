@@ -1,5 +1,5 @@
-// vecchia_api.hip -- C ABI of Vecchia's approximation (gogp_vecchia_*): host code; kernels in vecchia.hip, vecchia_blocks.hip and
-// vecchia_knn.hip.
+// vecchia_api.hip -- C ABI of Vecchia's approximation (gogp_vecchia_*): host code; kernels in vecchia.hip, vecchia_blocks.hip,
+// vecchia_knn.hip and vecchia_bknn.hip.
 // include/gogp_hip.h states the approximation and the table; DESIGN.md section 4, "Vecchia".  One kernel does all the
 // work; everything runs on the handle's main stream with buffers of the family's own, and the parameters are a copy of
 // the family's own, so that devP keeps what the last dense evaluation uploaded.
@@ -467,6 +467,57 @@ static int vblocks_refuse_table(gogp_handle *h, const char *who, const char *why
   return fail(h, GOGP_EARG, buf);
 }
 
+// The upload behind gogp_vecchia_blocks_set_data and gogp_vecchia_blocks_set_data_nearest, after their checks: X, y, v and the
+// table (tbl == nullptr: its buffers alone, nb x w, nb and nb, for the device to fill)
+static int vblocks_upload(gogp_handle *h, const double *X, const double *y, const double *v, int64_t N, const int32_t *tbl,
+                          const int32_t *nc, const int32_t *nt, int64_t nb, int32_t w) {
+  VecchiaBlocksState &vb = h->vb;
+  const int D = h->D;
+  HIPCHK(h, hipSetDevice(h->device));
+  if (h->s) HIPCHK(h, hipStreamSynchronize(h->s));
+  vb.release();
+  const size_t xb = (size_t)N * D * sizeof(double), yb = (size_t)N * sizeof(double);
+  const size_t tb = (size_t)nb * (size_t)w * sizeof(int32_t), cb = (size_t)nb * sizeof(int32_t);
+  hipStream_t s = h->s;
+  hipError_t e = hipMalloc(&vb.X, xb);
+  if (e == hipSuccess) e = hipMalloc(&vb.y, yb);
+  if (e == hipSuccess && v) e = hipMalloc(&vb.v, yb);
+  if (e == hipSuccess) e = hipMalloc(&vb.tbl, tb);
+  if (e == hipSuccess) e = hipMalloc(&vb.nc, cb);
+  if (e == hipSuccess) e = hipMalloc(&vb.nt, cb);
+  if (e == hipSuccess) e = hipMalloc(&vb.P, sizeof(DevParams));
+  if (e == hipSuccess) e = hipMemcpyAsync(vb.X, X, xb, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(vb.y, y, yb, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess && v) e = hipMemcpyAsync(vb.v, v, yb, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess && tbl) e = hipMemcpyAsync(vb.tbl, tbl, tb, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess && tbl) e = hipMemcpyAsync(vb.nc, nc, cb, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess && tbl) e = hipMemcpyAsync(vb.nt, nt, cb, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e != hipSuccess) {
+    vb.release();
+    HIPCHK(h, e);
+  }
+  vb.N = N;
+  vb.nb = (int)nb;
+  vb.w = w;
+  vb.have = true;
+  return GOGP_OK;
+}
+
+// t = nt[0] if block k's targets are the rows k t .. min(k t + t, n) - 1 -- the shape gogp_vecchia_blocks_reneighbour can
+// rebuild -- else 0; the table has passed vblocks_refusal
+static int32_t vblocks_consecutive_t(const int32_t *tbl, const int32_t *nc, const int32_t *nt, int64_t nb, int32_t w, int64_t n) {
+  const int32_t t = nt[0];
+  if (nb != (n + t - 1) / t) return 0;
+  for (int64_t k = 0; k < nb; ++k) {
+    const int64_t s = k * t;
+    if (nt[k] != std::min<int64_t>(t, n - s)) return 0;
+    for (int32_t a = 0; a < nt[k]; ++a)
+      if (tbl[k * w + nc[k] + a] != s + a) return 0;
+  }
+  return t;
+}
+
 extern "C" int gogp_vecchia_blocks_set_data(gogp_handle *h, const double *X, const double *y, const double *v, int64_t N,
                                             const int32_t *tbl, const int32_t *nc, const int32_t *nt, int64_t nb, int32_t w) {
   const char *who = "vecchia_blocks_set_data";
@@ -484,34 +535,9 @@ extern "C" int gogp_vecchia_blocks_set_data(gogp_handle *h, const double *X, con
   if (const char *why = vblocks_refusal(tbl, nc, nt, nb, w, N, &bad)) return vblocks_refuse_table(h, who, why, bad);
   const int D = h->D;
   if (const char *why = resident_data_refusal(X, y, v, N, D)) return refuse(h, who, GOGP_EARG, why);
-  HIPCHK(h, hipSetDevice(h->device));
-  if (h->s) HIPCHK(h, hipStreamSynchronize(h->s));
-  vb.release();
-  const size_t xb = (size_t)N * D * sizeof(double), yb = (size_t)N * sizeof(double);
-  const size_t tb = (size_t)nb * (size_t)w * sizeof(int32_t), cb = (size_t)nb * sizeof(int32_t);
-  hipStream_t s = h->s;
-  hipError_t e = hipMalloc(&vb.X, xb);
-  if (e == hipSuccess) e = hipMalloc(&vb.y, yb);
-  if (e == hipSuccess && v) e = hipMalloc(&vb.v, yb);
-  if (e == hipSuccess) e = hipMalloc(&vb.tbl, tb);
-  if (e == hipSuccess) e = hipMalloc(&vb.nc, cb);
-  if (e == hipSuccess) e = hipMalloc(&vb.nt, cb);
-  if (e == hipSuccess) e = hipMalloc(&vb.P, sizeof(DevParams));
-  if (e == hipSuccess) e = hipMemcpyAsync(vb.X, X, xb, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(vb.y, y, yb, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess && v) e = hipMemcpyAsync(vb.v, v, yb, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(vb.tbl, tbl, tb, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(vb.nc, nc, cb, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(vb.nt, nt, cb, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (e != hipSuccess) {
-    vb.release();
-    HIPCHK(h, e);
-  }
-  vb.N = N;
-  vb.nb = (int)nb;
-  vb.w = w;
-  vb.have = true;
+  if (const int rc = vblocks_upload(h, X, y, v, N, tbl, nc, nt, nb, w)) return rc;
+  vb.t = vblocks_consecutive_t(tbl, nc, nt, nb, w, N);
+  vb.c = vb.t > 0 ? w - vb.t : 0;
   return GOGP_OK;
 }
 
@@ -593,19 +619,78 @@ extern "C" int gogp_vecchia_blocks_gradient(gogp_handle *h, double *grad, int64_
   return GOGP_OK;
 }
 
-extern "C" int gogp_vecchia_blocks_produce(gogp_handle *h, const double *Z, int64_t mz, const int64_t *goff, int64_t ng,
-                                           const int32_t *tblz, int32_t wz, const int32_t *ncz, double *mu, double *sigma) {
-  const char *who = "vecchia_blocks_produce";
-  if (const int rc = refuse_handle(h, who)) return rc;
-  if (mz < 0 || ng < 0 || (mz > 0 && (!Z || !mu)) || (ng > 0 && !goff))
-    return refuse(h, who, GOGP_EARG, "need Z and mu for mz > 0, goff for ng > 0, mz >= 0, ng >= 0");
+// ---- block tables built on the device (vecchia_bknn.hip) --------------------------------------------------------------------
+// The searches of gogp_amd/vecchia.py's block_nearest / group_nearest_to on the handle's main stream; DESIGN.md section 4,
+// "Vecchia: block tables on the device".
+static int vblocks_knn_args(gogp_handle *h, const char *who, int32_t t, int32_t c, bool block, const double *lengths) {
+  if (t < 1) return refuse(h, who, GOGP_EARG, block ? "t: need t >= 1 targets per block" : "g: need g >= 1 test points per group");
+  if (c < 0 || c > GOGP_VECCHIA_BLOCK_MAX) return refuse(h, who, GOGP_EARG, "c: need 0 <= c <= 128 conditioning rows");
+  if (block && t + c > GOGP_VECCHIA_BLOCK_MAX) return refuse(h, who, GOGP_EARG, "t + c: a block holds at most 128 rows");
+  if (lengths)
+    for (int d = 0; d < h->D; ++d)
+      if (!(lengths[d] > 0.0) || !std::isfinite(lengths[d]))
+        return refuse(h, who, GOGP_EARG, "lengths: every length scale must be positive and finite");
+  return GOGP_OK;
+}
+
+// the scratch of one search: the lengths, the scaled copies of X and Z, the centroids, the lists and their counts, the
+// partial lists of a split search
+struct VblocksKnnBufs {
+  double *len, *Xs, *Zs, *cen;
+  int *sel, *cnt;
+  void *ws;
+};
+static size_t vblocks_knn_layout(char *base, int D, int64_t N, int64_t mz, int64_t nq, int c, VblocksKnnBufs *b) {
+  Carve cv{base};
+  b->len = cv.take<double>(GOGP_MAX_NDIM);
+  b->Xs = cv.take<double>((size_t)N * D);
+  b->Zs = cv.take<double>((size_t)mz * D);
+  b->cen = cv.take<double>((size_t)nq * D);
+  b->sel = cv.take<int>((size_t)nq * c);
+  b->cnt = cv.take<int>((size_t)nq);
+  b->ws = cv.take<char>(bknn_plan(nq, N, c).ws_bytes);
+  return cv.off;
+}
+static int64_t vblocks_queries(int64_t N, int64_t mz, bool query, int t) { return ((query ? mz : N) + t - 1) / t; }
+static size_t vblocks_knn_bytes(int D, int64_t N, int64_t mz, bool query, int t, int c) {
+  VblocksKnnBufs b;
+  return vblocks_knn_layout(nullptr, D, N, query ? mz : 0, vblocks_queries(N, mz, query, t), c, &b);
+}
+
+// The launches of one search on device rows, with vblocks_knn_bytes of scratch at base.  dZ == nullptr: the causal block
+// table of dX (N x D) into dtbl (nb x (t + c)), dnc and dnt; else the table of the groups of t rows of dZ (mz x D) over all
+// of dX into dtbl (ng x c) and dnc.  lengths: the host's, or nullptr.  The caller synchronises before it returns.
+static int vblocks_knn_launch(gogp_handle *h, char *base, const double *dX, int64_t N, const double *dZ, int64_t mz, int t,
+                              int c, const double *lengths, int *dtbl, int *dnc, int *dnt) {
+  hipStream_t s = h->s;
+  const int D = h->D;
+  const int64_t nq = vblocks_queries(N, mz, dZ != nullptr, t);
+  if (nq == 0) return GOGP_OK;
+  VblocksKnnBufs b;
+  vblocks_knn_layout(base, D, N, dZ ? mz : 0, nq, c, &b);
+  if (c > 0) {
+    if (lengths) HIPCHK(h, hipMemcpyAsync(b.len, lengths, (size_t)D * sizeof(double), hipMemcpyHostToDevice, s));
+    launch_vknn_scale(s, dX, N, D, lengths ? b.len : nullptr, b.Xs);
+    if (dZ) launch_vknn_scale(s, dZ, mz, D, lengths ? b.len : nullptr, b.Zs);
+    launch_bknn_centroids(s, dZ ? b.Zs : b.Xs, dZ ? mz : N, D, t, b.cen);
+  }
+  if (dZ) {
+    if (c > 0) launch_bknn(s, b.Xs, N, b.cen, nq, 0, D, c, 0, 0, b.ws, dtbl, dnc, nullptr);
+    else HIPCHK(h, hipMemsetAsync(dnc, 0, (size_t)nq * sizeof(int), s));
+  } else {
+    launch_bknn(s, b.Xs, N, b.cen, nq, t, D, c, 0, 0, b.ws, b.sel, b.cnt, nullptr);
+    launch_bknn_pack(s, b.sel, b.cnt, nq, N, t, c, dtbl, dnc, dnt);
+  }
+  return GOGP_OK;
+}
+
+// What the two block Produce calls do behind their own checks, for a resident and observed data set: the test points and
+// the groups' offsets go up, the table is the caller's (tblz, ncz) or, with `search`, found on the device in its place for
+// groups of g rows under `lengths` (nullptr: unscaled) and handed back through tblz_out (nullptr: not wanted); then one launch
+static int vblocks_produce_run(gogp_handle *h, const char *who, const double *Z, int64_t mz, const int64_t *goff, int64_t ng,
+                               const int32_t *tblz, int32_t wz, const int32_t *ncz, bool search, int32_t g,
+                               const double *lengths, double *mu, double *sigma, int32_t *tblz_out) {
   VecchiaBlocksState &vb = h->vb;
-  if (!vb.have || !vb.observed) return refuse(h, who, GOGP_ESTATE, "nothing observed (gogp_vecchia_blocks_observe)");
-  if (ng == 0 ? mz != 0 : (goff[0] != 0 || goff[ng] != mz)) return refuse(h, who, GOGP_EARG, "goff: need goff[0] = 0 and goff[ng] = mz");
-  for (int64_t g = 0; g < ng; ++g)
-    if (goff[g + 1] < goff[g]) return refuse(h, who, GOGP_EARG, "goff: the offsets must not decrease");
-  int64_t bad;
-  if (const char *why = vblocks_shape_refusal(tblz, ncz, nullptr, ng, wz, vb.N, true, &bad)) return vblocks_refuse_table(h, who, why, bad);
   const int D = h->D;
   for (int64_t i = 0; i < mz * D; ++i)
     if (!std::isfinite(Z[i])) return refuse(h, who, GOGP_EARG, "non-finite test point");
@@ -630,20 +715,170 @@ extern "C" int gogp_vecchia_blocks_produce(gogp_handle *h, const double *Z, int6
   int *dtb, *dnc;
   layout(c, dZ, dmu, dsig, doff, dtb, dnc, dfp, dinfo);
   if (const int rc = vb.prod.reserve(h, c.off)) return rc;
+  if (const int rc = search ? vb.knn.reserve(h, vblocks_knn_bytes(D, vb.N, mz, true, g, wz)) : GOGP_OK) return rc;
   Carve c2{vb.prod.as<char>()};
   layout(c2, dZ, dmu, dsig, doff, dtb, dnc, dfp, dinfo);
   static_assert(sizeof(long long) == sizeof(int64_t), "the offsets go up as they are");
   HIPCHK(h, hipMemcpyAsync(dZ, Z, (size_t)mz * D * sizeof(double), hipMemcpyHostToDevice, s));
   HIPCHK(h, hipMemcpyAsync(doff, goff, ((size_t)ng + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
-  if (wz > 0) HIPCHK(h, hipMemcpyAsync(dtb, tblz, (size_t)ng * (size_t)wz * sizeof(int32_t), hipMemcpyHostToDevice, s));
-  HIPCHK(h, hipMemcpyAsync(dnc, ncz, (size_t)ng * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  if (search) {
+    if (const int rc = vblocks_knn_launch(h, vb.knn.as<char>(), vb.X, vb.N, dZ, mz, g, wz, lengths, dtb, dnc, nullptr)) return rc;
+  } else {
+    if (wz > 0) HIPCHK(h, hipMemcpyAsync(dtb, tblz, (size_t)ng * (size_t)wz * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(dnc, ncz, (size_t)ng * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  }
   launch_vblocks_produce(s, vb.P, vb.X, vb.y, vb.v, dZ, doff, (int)ng, dtb, wz, dnc, dmu, sigma ? dsig : nullptr, dfp, dinfo, vb.grid);
   long long info = 0;
   HIPCHK(h, hipMemcpyAsync(mu, dmu, (size_t)mz * sizeof(double), hipMemcpyDeviceToHost, s));
   if (sigma) HIPCHK(h, hipMemcpyAsync(sigma, dsig, (size_t)mz * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (tblz_out && wz > 0) HIPCHK(h, hipMemcpyAsync(tblz_out, dtb, (size_t)ng * (size_t)wz * sizeof(int32_t), hipMemcpyDeviceToHost, s));
   HIPCHK(h, hipMemcpyAsync(&info, dinfo, sizeof info, hipMemcpyDeviceToHost, s));
   HIPCHK(h, hipStreamSynchronize(s));
   HIPCHK(h, hipGetLastError());
   if (info != 0) return vecchia_notpd(h, who, info, "group");
   return GOGP_OK;
+}
+
+extern "C" int gogp_vecchia_blocks_produce(gogp_handle *h, const double *Z, int64_t mz, const int64_t *goff, int64_t ng,
+                                           const int32_t *tblz, int32_t wz, const int32_t *ncz, double *mu, double *sigma) {
+  const char *who = "vecchia_blocks_produce";
+  if (const int rc = refuse_handle(h, who)) return rc;
+  if (mz < 0 || ng < 0 || (mz > 0 && (!Z || !mu)) || (ng > 0 && !goff))
+    return refuse(h, who, GOGP_EARG, "need Z and mu for mz > 0, goff for ng > 0, mz >= 0, ng >= 0");
+  VecchiaBlocksState &vb = h->vb;
+  if (!vb.have || !vb.observed) return refuse(h, who, GOGP_ESTATE, "nothing observed (gogp_vecchia_blocks_observe)");
+  if (ng == 0 ? mz != 0 : (goff[0] != 0 || goff[ng] != mz)) return refuse(h, who, GOGP_EARG, "goff: need goff[0] = 0 and goff[ng] = mz");
+  for (int64_t g = 0; g < ng; ++g)
+    if (goff[g + 1] < goff[g]) return refuse(h, who, GOGP_EARG, "goff: the offsets must not decrease");
+  int64_t bad;
+  if (const char *why = vblocks_shape_refusal(tblz, ncz, nullptr, ng, wz, vb.N, true, &bad)) return vblocks_refuse_table(h, who, why, bad);
+  return vblocks_produce_run(h, who, Z, mz, goff, ng, tblz, wz, ncz, false, 0, nullptr, mu, sigma, nullptr);
+}
+
+extern "C" int gogp_vecchia_blocks_nearest(gogp_handle *h, const double *X, int64_t N, const double *Z, int64_t mz, int32_t t,
+                                           int32_t c, const double *lengths, int32_t *tbl, int32_t *nc, int32_t *nt) {
+  const char *who = "vecchia_blocks_nearest";
+  if (const int rc = refuse_handle(h, who)) return rc;
+  if (N < 1 || !X) return refuse(h, who, GOGP_EARG, "need X and N >= 1");
+  if (N > INT32_MAX) return refuse(h, who, GOGP_EARG, "N: the table's indices are int32: N <= 2^31 - 1");
+  if (Z ? mz < 0 : mz != 0) return refuse(h, who, GOGP_EARG, "mz: the rows of Z, 0 without Z");
+  if (const int rc = vblocks_knn_args(h, who, t, c, Z == nullptr, lengths)) return rc;
+  const int64_t nq = vblocks_queries(N, mz, Z != nullptr, t);
+  if (nq == 0) return GOGP_OK;
+  const int w = Z ? c : t + c;
+  if (!nc || (w > 0 && !tbl) || (!Z && !nt)) return refuse(h, who, GOGP_EARG, "tbl, nc, nt: NULL");
+  const int D = h->D;
+  HIPCHK(h, hipSetDevice(h->device));
+  hipStream_t s = h->s;
+  // buffers of the call's own: nothing of the handle changes
+  Workspace ws;
+  struct Release {
+    Workspace &w;
+    ~Release() { w.release(); }
+  } release{ws};
+  auto layout = [&](Carve &cv, double *&dX, double *&dZ, int *&dtb, int *&dnc, int *&dnt, char *&scratch) {
+    dX = cv.take<double>((size_t)N * D);
+    dZ = cv.take<double>((size_t)mz * D);
+    dtb = cv.take<int>(std::max<size_t>((size_t)nq * w, 1));
+    dnc = cv.take<int>((size_t)nq);
+    dnt = cv.take<int>((size_t)nq);
+    scratch = cv.take<char>(vblocks_knn_bytes(D, N, mz, Z != nullptr, t, c));
+  };
+  double *dX, *dZ;
+  int *dtb, *dnc, *dnt;
+  char *scratch;
+  Carve c0{nullptr};
+  layout(c0, dX, dZ, dtb, dnc, dnt, scratch);
+  if (const int rc = ws.reserve(h, c0.off)) return rc;
+  Carve c1{ws.as<char>()};
+  layout(c1, dX, dZ, dtb, dnc, dnt, scratch);
+  HIPCHK(h, hipMemcpyAsync(dX, X, (size_t)N * D * sizeof(double), hipMemcpyHostToDevice, s));
+  if (Z) HIPCHK(h, hipMemcpyAsync(dZ, Z, (size_t)mz * D * sizeof(double), hipMemcpyHostToDevice, s));
+  if (const int rc = vblocks_knn_launch(h, scratch, dX, N, Z ? dZ : nullptr, mz, t, c, lengths, dtb, dnc, dnt)) return rc;
+  if (w > 0) HIPCHK(h, hipMemcpyAsync(tbl, dtb, (size_t)nq * w * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipMemcpyAsync(nc, dnc, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  if (!Z) HIPCHK(h, hipMemcpyAsync(nt, dnt, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipStreamSynchronize(s));
+  HIPCHK(h, hipGetLastError());
+  return GOGP_OK;
+}
+
+// the resident table from the resident X under `lengths` (nullptr: unscaled), t and c as stored; the last observe is dropped
+static int vblocks_rebuild(gogp_handle *h, const double *lengths) {
+  VecchiaBlocksState &vb = h->vb;
+  if (const int rc = vb.knn.reserve(h, vblocks_knn_bytes(h->D, vb.N, 0, false, vb.t, vb.c))) return rc;
+  vb.observed = false;
+  if (const int rc = vblocks_knn_launch(h, vb.knn.as<char>(), vb.X, vb.N, nullptr, 0, vb.t, vb.c, lengths, vb.tbl, vb.nc, vb.nt))
+    return rc;
+  HIPCHK(h, hipStreamSynchronize(h->s));
+  HIPCHK(h, hipGetLastError());
+  vb.built_here = true;
+  vb.scaled = lengths != nullptr;
+  for (int d = 0; d < h->D; ++d) vb.lengths[d] = lengths ? lengths[d] : 1.0;
+  return GOGP_OK;
+}
+
+extern "C" int gogp_vecchia_blocks_set_data_nearest(gogp_handle *h, const double *X, const double *y, const double *v, int64_t N,
+                                                    int32_t t, int32_t c, const double *lengths) {
+  const char *who = "vecchia_blocks_set_data_nearest";
+  if (const int rc = refuse_handle(h, who)) return rc;
+  if (N < 1 || !X || !y) return refuse(h, who, GOGP_EARG, "need X, y and N >= 1");
+  if (N > INT32_MAX) return refuse(h, who, GOGP_EARG, "N: the table's indices are int32: N <= 2^31 - 1");
+  if (const int rc = vblocks_knn_args(h, who, t, c, true, lengths)) return rc;
+  if (const char *why = resident_data_refusal(X, y, v, N, h->D)) return refuse(h, who, GOGP_EARG, why);
+  if (const int rc = vblocks_upload(h, X, y, v, N, nullptr, nullptr, nullptr, (N + t - 1) / t, t + c)) return rc;
+  VecchiaBlocksState &vb = h->vb;
+  vb.t = t;
+  vb.c = c;
+  if (const int rc = vblocks_rebuild(h, lengths)) {
+    vb.release();  // (the error text stays)
+    return rc;
+  }
+  return GOGP_OK;
+}
+
+extern "C" int gogp_vecchia_blocks_reneighbour(gogp_handle *h, const double *lengths) {
+  const char *who = "vecchia_blocks_reneighbour";
+  if (const int rc = refuse_handle(h, who)) return rc;
+  VecchiaBlocksState &vb = h->vb;
+  if (!vb.have)
+    return refuse(h, who, GOGP_ESTATE, "no data (gogp_vecchia_blocks_set_data, gogp_vecchia_blocks_set_data_nearest)");
+  if (vb.t < 1)
+    return refuse(h, who, GOGP_ESTATE, "the resident table is not one of consecutive blocks (block k's targets: the rows k t ...)");
+  if (const int rc = vblocks_knn_args(h, who, vb.t, vb.c, true, lengths)) return rc;
+  HIPCHK(h, hipSetDevice(h->device));
+  return vblocks_rebuild(h, lengths);
+}
+
+extern "C" int gogp_vecchia_blocks_get_table(gogp_handle *h, int32_t *tbl, int32_t *nc, int32_t *nt) {
+  const char *who = "vecchia_blocks_get_table";
+  if (const int rc = refuse_handle(h, who)) return rc;
+  VecchiaBlocksState &vb = h->vb;
+  if (!vb.have)
+    return refuse(h, who, GOGP_ESTATE, "no data (gogp_vecchia_blocks_set_data, gogp_vecchia_blocks_set_data_nearest)");
+  if (!tbl || !nc || !nt) return refuse(h, who, GOGP_EARG, "tbl, nc, nt: NULL");
+  HIPCHK(h, hipSetDevice(h->device));
+  hipStream_t s = h->s;
+  HIPCHK(h, hipMemcpyAsync(tbl, vb.tbl, (size_t)vb.nb * (size_t)vb.w * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipMemcpyAsync(nc, vb.nc, (size_t)vb.nb * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipMemcpyAsync(nt, vb.nt, (size_t)vb.nb * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipStreamSynchronize(s));
+  return GOGP_OK;
+}
+
+extern "C" int gogp_vecchia_blocks_produce_nearest(gogp_handle *h, const double *Z, int64_t mz, int32_t g, int32_t c,
+                                                   const double *lengths, double *mu, double *sigma, int32_t *tblz) {
+  const char *who = "vecchia_blocks_produce_nearest";
+  if (const int rc = refuse_handle(h, who)) return rc;
+  if (mz < 0 || (mz > 0 && (!Z || !mu))) return refuse(h, who, GOGP_EARG, "need Z and mu for mz > 0, mz >= 0");
+  if (const int rc = vblocks_knn_args(h, who, g, c, false, lengths)) return rc;
+  VecchiaBlocksState &vb = h->vb;
+  if (!vb.have || !vb.observed) return refuse(h, who, GOGP_ESTATE, "nothing observed (gogp_vecchia_blocks_observe)");
+  if (!lengths && !vb.built_here)
+    return refuse(h, who, GOGP_ESTATE, "lengths: the resident table is the caller's, so it has none to take");
+  const int64_t ng = (mz + g - 1) / g;
+  std::vector<int64_t> goff((size_t)ng + 1);
+  for (int64_t k = 0; k <= ng; ++k) goff[k] = std::min<int64_t>(k * g, mz);
+  return vblocks_produce_run(h, who, Z, mz, goff.data(), ng, nullptr, c, nullptr, true, g,
+                             lengths ? lengths : vb.scaled ? vb.lengths : nullptr, mu, sigma, tblz);
 }

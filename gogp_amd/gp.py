@@ -145,7 +145,7 @@ class _VecchiaBlockCalls:
         self._check(L.gogp_vecchia_blocks_set_data(self._h, _dp(xs) if len(xs) else None, _dp(ys) if len(ys) else None, _dp(va),
                                                    len(ys), _i32p(t) if t.size else None, _i32p(c) if c.size else None,
                                                    _i32p(n) if n.size else None, len(c), t.shape[1]))
-        self._vb_n = len(ys)
+        self._vb_n, self._vb_shape, self._vb_c = len(ys), (len(c), t.shape[1]), max(t.shape[1] - int(n[0]), 0) if n.size else 0
 
     def VecchiaBlockObserve(self, theta) -> float:
         """The block approximation of the LML at theta = log of the hyperparameters (gogp_vecchia_blocks_observe): the sum
@@ -197,6 +197,89 @@ class _VecchiaBlockCalls:
             _i32p(t) if t.size else None, t.shape[1], _i32p(c) if c.size else None, _dp(mu) if mz else None,
             _dp(sg) if mz and sigma else None))
         return mu, sg
+
+    # ---- ... with the tables built on the device (vecchia_bknn.hip): the searches of vecchia.block_nearest / group_nearest_to ----
+    @staticmethod
+    def _vecchia_tc(t, c, what: str, block: bool = True):
+        t, c = int(t), int(c)
+        if t < 1 or not 0 <= c <= 128 or (block and t + c > 128):
+            raise ValueError("%s: t >= 1 rows per block, 0 <= c <= 128 conditioning rows%s" %
+                             (what, ", t + c <= 128" if block else ""))
+        return t, c
+
+    def VecchiaBlockTables(self, x, t: int, c: int, lengths=None, z=None):
+        """(tbl, nc, nt) of vecchia.block_nearest(x, t, c, lengths) -- or, with test points ``z``, (tbl, nc) of
+        vecchia.group_nearest_to(x, z, t, c, lengths) for groups of t test points -- found on the device, integer for
+        integer (gogp_vecchia_blocks_nearest).  One-shot: nothing of the process changes."""
+        what = "VecchiaBlockTables"
+        t, c = self._vecchia_tc(t, c, what, block=z is None)
+        xs = self._vecchia_rows(x, what + ": x")
+        la = self._vecchia_lengths(lengths, what)
+        zz = None if z is None else self._vecchia_rows(z, what + ": z")
+        rows = len(xs) if zz is None else len(zz)
+        nq = -(-rows // t)
+        tbl = np.full((nq, c if zz is not None else t + c), -1, dtype=np.int32)
+        nc, nt = np.zeros(nq, dtype=np.int32), np.zeros(nq, dtype=np.int32)
+        if len(xs) and nq:
+            self._check(_lib.lib().gogp_vecchia_blocks_nearest(
+                self._h, _dp(xs), len(xs), None if zz is None else _dp(zz), 0 if zz is None else len(zz), t, c, _dp(la),
+                _i32p(tbl) if tbl.size else None, _i32p(nc), None if zz is not None else _i32p(nt)))
+        return (tbl, nc, nt) if zz is None else (tbl, nc)
+
+    def SetVecchiaBlocksNearest(self, x, y, t: int, c: int, lengths=None, v=None) -> None:
+        """SetVecchiaBlocks(x, y, vecchia.block_nearest(x, t, c, lengths), v) with the table built on the device from the
+        uploaded x, where it stays (gogp_vecchia_blocks_set_data_nearest).  VecchiaBlockTable() returns it,
+        VecchiaBlockReneighbour rebuilds it."""
+        what = "SetVecchiaBlocksNearest"
+        t, c = self._vecchia_tc(t, c, what)
+        xs = self._vecchia_rows(x, what + ": x")
+        ys = np.ascontiguousarray(_arr(y).reshape(-1))
+        if len(xs) != len(ys):
+            raise ValueError("SetVecchiaBlocksNearest: len(x) != len(y)")
+        la = self._vecchia_lengths(lengths, what)
+        va = None
+        if v is not None:
+            va = np.ascontiguousarray(_arr(v).reshape(-1))
+            if va.size != len(ys):
+                raise ValueError("SetVecchiaBlocksNearest: one variance per observation")
+        self._vb_terms = None
+        self._check(_lib.lib().gogp_vecchia_blocks_set_data_nearest(
+            self._h, _dp(xs) if len(xs) else None, _dp(ys) if len(ys) else None, _dp(va), len(ys), t, c, _dp(la)))
+        self._vb_n, self._vb_shape, self._vb_c = len(ys), (-(-len(ys) // t), t + c), c
+
+    def VecchiaBlockReneighbour(self, lengths) -> None:
+        """Rebuild the resident block table from the resident x under new length scales, same t and c
+        (gogp_vecchia_blocks_reneighbour); also on data that SetVecchiaBlocks brought, if its blocks are consecutive runs of
+        t rows (else GOGP_ESTATE).  The last VecchiaBlockObserve is dropped."""
+        la = self._vecchia_lengths(lengths, "VecchiaBlockReneighbour")
+        self._vb_terms = None
+        self._check(_lib.lib().gogp_vecchia_blocks_reneighbour(self._h, _dp(la)))
+
+    def VecchiaBlockTable(self):
+        """The resident block table (tbl, nc, nt): nb x w, nb and nb int32 (gogp_vecchia_blocks_get_table)."""
+        nb, w = getattr(self, "_vb_shape", (0, 0)) if getattr(self, "_vb_n", 0) else (0, 0)
+        tbl = np.full((max(nb, 1), max(w, 1)), -1, dtype=np.int32)
+        nc, nt = np.zeros(max(nb, 1), dtype=np.int32), np.zeros(max(nb, 1), dtype=np.int32)
+        self._check(_lib.lib().gogp_vecchia_blocks_get_table(self._h, _i32p(tbl), _i32p(nc), _i32p(nt)))
+        return tbl[:nb, :w], nc[:nb], nt[:nb]
+
+    def VecchiaBlockProduceNearest(self, z, g: int, c=None, lengths=None, sigma: bool = True, table: bool = False):
+        """VecchiaBlockProduce(z, *vecchia.group_nearest_to(x, z, g, c, lengths)) with the groups' conditioning rows found on
+        the device (gogp_vecchia_blocks_produce_nearest).  ``c=None``: as many as the resident table's blocks have;
+        ``lengths=None``: those the resident table was built with (refused with GOGP_ESTATE where the caller brought the
+        table: SetVecchiaBlocks).  Returns (mu, sigma), or (mu, sigma, (tbl, nc)) with ``table=True``."""
+        what = "VecchiaBlockProduceNearest"
+        g, c = self._vecchia_tc(g, getattr(self, "_vb_c", 0) if c is None else c, what, block=False)
+        zz = self._vecchia_rows(z, what + ": z")
+        la = self._vecchia_lengths(lengths, what)
+        mz = len(zz)
+        mu = np.zeros(mz)
+        sg = np.zeros(mz) if sigma else None
+        t = np.full((-(-mz // g), c), -1, dtype=np.int32)
+        self._check(_lib.lib().gogp_vecchia_blocks_produce_nearest(
+            self._h, _dp(zz) if mz else None, mz, g, c, _dp(la), _dp(mu) if mz else None, _dp(sg) if mz and sigma else None,
+            _i32p(t) if table and t.size else None))
+        return (mu, sg, (t, (t >= 0).sum(axis=1).astype(np.int32))) if table else (mu, sg)
 
 
 class GP(_VecchiaBlockCalls):
@@ -1868,12 +1951,22 @@ class VecchiaBlockModel:
     """Model with the block approximation of GP.SetVecchiaBlocks in the place of the LML: Observe(x) returns
     GP.VecchiaBlockObserve(x) (+ the log prior), Gradient() returns GP.VecchiaBlockGradient() (+ the prior's), for
     optimize.lbfgs and optimize.Adam.  The gradient is the exact derivative of the value; the blocks are fixed by
-    GP.SetVecchiaBlocks."""
+    GP.SetVecchiaBlocks.
 
-    def __init__(self, gp: GP, Priors=None):
+    ``lengths_of``, a callable from x = log theta to the length scales (a scalar or one per dimension), offers
+    ``reneighbour(x)`` as VecchiaModel does: the resident block table rebuilt on the device under lengths_of(x)
+    (GP.VecchiaBlockReneighbour), between two runs of an optimiser -- never inside one."""
+
+    def __init__(self, gp: GP, Priors=None, lengths_of=None):
         self.gp = gp
         self.Priors = Priors
+        self.lengths_of = lengths_of
         self._x = None
+
+    def reneighbour(self, x) -> None:
+        if self.lengths_of is None:
+            raise ValueError("reneighbour: the model was built without lengths_of")
+        self.gp.VecchiaBlockReneighbour(self.lengths_of(_arr(x).reshape(-1)))
 
     def Observe(self, x) -> float:
         self._x = _arr(x).reshape(-1).copy()
@@ -2914,3 +3007,35 @@ def vecchia_knn_check(X: np.ndarray, n: int, ndim: int, m: int, nbr, d2, xs: np.
     if rc != _lib.GOGP_OK:
         raise GogpError(rc, "test_vecchia_knn")
     return nb, dd, xs
+
+
+def vecchia_bknn_plan(queries: int, n: int, c: int):
+    """(queries of a tile, slabs, bytes of workspace) of a search of ``queries`` centroids over n candidates (test hook
+    gogp_test_vecchia_bknn_plan): tile k holds the queries [k qt, (k + 1) qt), slab s the candidates [s L, (s + 1) L) with
+    L = ceil(n / slabs).  No device."""
+    out = np.zeros(3, dtype=np.int64)
+    rc = _lib.hooks().gogp_test_vecchia_bknn_plan(queries, n, c, _ip(out))
+    if rc != _lib.GOGP_OK:
+        raise GogpError(rc, "test_vecchia_bknn_plan")
+    return int(out[0]), int(out[1]), int(out[2])
+
+
+def vecchia_bknn_check(X: np.ndarray, n: int, ndim: int, t: int, c: int, Z=None, mz: int = 0, lengths=None, qt: int = 0,
+                       slabs: int = 0, device: int = -1):
+    """The selection of vecchia_bknn.hip on caller-supplied rows (test hook gogp_test_vecchia_bknn): the lists of the
+    centroids of the blocks of t rows of X over the earlier rows, or (Z given, mz rows) of the groups of t rows of Z over
+    all of X, with a forced tile (qt) and candidate split (slabs) where > 0.  Returns (nbr, d2, cnt, cen): queries x c
+    indices (-1 padded) and squared distances, the entries taken, queries x ndim centroids."""
+    X = _vec(X, "X")
+    zp, zl = _opt(Z, "Z")
+    lp = None if lengths is None else _dp(_vec(lengths, "lengths"))
+    if lengths is not None and lengths.size != ndim:
+        raise GogpError(_lib.GOGP_EARG, "test_vecchia_bknn: lengths")
+    nq = max(-(-(mz if Z is not None else n) // max(t, 1)), 0)
+    nb, dd = np.full(max(nq * max(c, 0), 1), -1, dtype=np.int32), np.zeros(max(nq * max(c, 0), 1))
+    cn, ce = np.zeros(max(nq, 1), dtype=np.int32), np.zeros(max(nq * ndim, 1))
+    rc = _lib.hooks().gogp_test_vecchia_bknn(device, _dp(X), X.size, n, ndim, zp, zl, mz, lp, t, c, qt, slabs, _i32p(nb), nb.size,
+                                             _dp(dd), dd.size, _i32p(cn), cn.size, _dp(ce), ce.size)
+    if rc != _lib.GOGP_OK:
+        raise GogpError(rc, "test_vecchia_bknn")
+    return nb[:nq * c].reshape(nq, c), dd[:nq * c].reshape(nq, c), cn[:nq], ce[:nq * ndim].reshape(nq, ndim)

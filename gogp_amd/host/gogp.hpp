@@ -553,6 +553,65 @@ class GP {
                                        mu.data(), sigma ? sigma->data() : nullptr,
                                        nbrz && !nbrz->empty() ? nbrz->data() : nullptr));
   }
+  // Block tables built on the device (gogp_vecchia_blocks_nearest etc.): consecutive blocks of t rows, each conditioned on
+  // the c earlier rows nearest to its centroid under the distance of x / lengths (lengths: empty = unscaled).
+  // VecchiaBlockTables: one-shot; z empty: the causal table of x (tbl: nb x (t + c), nc, nt), else the groups of t rows of z
+  // over all of x (tbl: ng x c, nc; nt stays empty).
+  void VecchiaBlockTables(const std::vector<double> &x, int32_t t, int32_t c, std::vector<int32_t> &tbl, std::vector<int32_t> &nc,
+                          std::vector<int32_t> &nt, const std::vector<double> &lengths = {},
+                          const std::vector<std::vector<double>> &z = {}) {
+    if (t < 1 || c < 0 || x.size() % (size_t)NDim || (!lengths.empty() && lengths.size() != (size_t)NDim))
+      throw Error(GOGP_EARG, "VecchiaBlockTables: sizes");
+    const size_t n = x.size() / (size_t)NDim, nq = ((z.empty() ? n : z.size()) + (size_t)t - 1) / (size_t)t;
+    tbl.assign(nq * (size_t)(z.empty() ? t + c : c), -1);
+    nc.assign(nq, 0);
+    nt.assign(z.empty() ? nq : 0, 0);
+    if (n == 0 || nq == 0) return;
+    std::vector<double> flat = pack(z);
+    check(gogp_vecchia_blocks_nearest(h_, x.data(), (int64_t)n, z.empty() ? nullptr : flat.data(), (int64_t)z.size(), t, c,
+                                      lengths.empty() ? nullptr : lengths.data(), tbl.empty() ? nullptr : tbl.data(), nc.data(),
+                                      z.empty() ? nt.data() : nullptr));
+  }
+  void SetVecchiaBlocksNearest(const std::vector<double> &x, const std::vector<double> &y, int32_t t, int32_t c,
+                               const std::vector<double> &lengths = {}, const std::vector<double> &v = {}) {
+    if (t < 1 || c < 0 || x.size() != y.size() * (size_t)NDim || (!lengths.empty() && lengths.size() != (size_t)NDim) ||
+        (!v.empty() && v.size() != y.size()))
+      throw Error(GOGP_EARG, "SetVecchiaBlocksNearest: sizes");
+    check(gogp_vecchia_blocks_set_data_nearest(h_, x.data(), y.data(), v.empty() ? nullptr : v.data(), (int64_t)y.size(), t, c,
+                                               lengths.empty() ? nullptr : lengths.data()));
+    vblocks_nb_ = (y.size() + (size_t)t - 1) / (size_t)t;
+    vblocks_w_ = (size_t)(t + c);
+  }
+  // the resident block table rebuilt under new lengths (same t and c); the last block observe is dropped
+  void VecchiaBlockReneighbour(const std::vector<double> &lengths) {
+    if (!lengths.empty() && lengths.size() != (size_t)NDim) throw Error(GOGP_EARG, "VecchiaBlockReneighbour: sizes");
+    check(gogp_vecchia_blocks_reneighbour(h_, lengths.empty() ? nullptr : lengths.data()));
+  }
+  // the table SetVecchiaBlocksNearest built: tbl (nb x (t + c)), nc, nt
+  void VecchiaBlockTable(std::vector<int32_t> &tbl, std::vector<int32_t> &nc, std::vector<int32_t> &nt) {
+    tbl.assign(std::max<size_t>(vblocks_nb_ * vblocks_w_, 1), -1);
+    nc.assign(std::max<size_t>(vblocks_nb_, 1), 0);
+    nt.assign(std::max<size_t>(vblocks_nb_, 1), 0);
+    check(gogp_vecchia_blocks_get_table(h_, tbl.data(), nc.data(), nt.data()));
+    tbl.resize(vblocks_nb_ * vblocks_w_);
+    nc.resize(vblocks_nb_);
+    nt.resize(vblocks_nb_);
+  }
+  // mu and (unless nullptr) sigma of the test points in groups of g, each group conditioned on the c resident rows nearest
+  // to its centroid, found on the device; lengths empty: the resident table's; tblz (unless nullptr) receives the table
+  void VecchiaBlockProduceNearest(const std::vector<std::vector<double>> &x, int32_t g, int32_t c, std::vector<double> &mu,
+                                  std::vector<double> *sigma = nullptr, const std::vector<double> &lengths = {},
+                                  std::vector<int32_t> *tblz = nullptr) {
+    if (g < 1 || c < 0 || (!lengths.empty() && lengths.size() != (size_t)NDim))
+      throw Error(GOGP_EARG, "VecchiaBlockProduceNearest: sizes");
+    std::vector<double> flat = pack(x);
+    mu.assign(x.size(), 0.0);
+    if (sigma) sigma->assign(x.size(), 0.0);
+    if (tblz) tblz->assign((x.size() + (size_t)g - 1) / (size_t)g * (size_t)c, -1);
+    check(gogp_vecchia_blocks_produce_nearest(h_, flat.data(), (int64_t)x.size(), g, c, lengths.empty() ? nullptr : lengths.data(),
+                                              mu.data(), sigma ? sigma->data() : nullptr,
+                                              tblz && !tblz->empty() ? tblz->data() : nullptr));
+  }
   // SparseGradient and, from the same pass over the data, d bound / d U of the inducing points of SetSparse (dU:
   // row-major M x NDim)
   std::vector<double> SparseGradientInducing(std::vector<double> &dU) {
@@ -775,6 +834,7 @@ class GP {
   int sparse_t_ = 0;     // output columns of SetSparseOutputs
   size_t cg_n_ = 0;      // observations of SetCG
   size_t vecchia_n_ = 0; // observations of SetVecchia
+  size_t vblocks_nb_ = 0, vblocks_w_ = 0; // the table of SetVecchiaBlocksNearest: nb x w
   int32_t vecchia_m_ = 0; // ... and the columns of its table
 
   std::vector<double> pack(const std::vector<std::vector<double>> &x) const {

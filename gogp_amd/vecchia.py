@@ -124,19 +124,41 @@ def block_previous(n: int, t: int, c: int):
     return _pack(cond, targ, t + c)
 
 
+def _centroid(xs: np.ndarray, t: int) -> np.ndarray:
+    """The centroids of the consecutive blocks of t rows of xs (the last one shorter), one row per block, in a stated
+    order of operations: the rows are summed in index order, one IEEE add per row, and the sum is divided once by the row
+    count; a block of one row is the row itself, undivided.  The device (GP.VecchiaBlockTables) does the same, so both
+    name the same rows.  For two or more dimensions this is ndarray.mean(axis=0) bit for bit; for one dimension and eight
+    or more rows numpy's mean adds eight interleaved partial sums, so this centroid may differ from it in the last bit,
+    which changes a table only where two keys lie within that bit."""
+    n = len(xs)
+    starts = np.arange(0, n, t)
+    cnt = np.minimum(t, n - starts)
+    acc = xs[starts].copy()
+    for p in range(1, min(t, n)):  # vectorised over the blocks: a loop over the positions within a block
+        live = cnt > p
+        acc[live] += xs[starts[live] + p]
+    many = cnt > 1
+    acc[many] /= cnt[many, None].astype(np.float64)
+    return acc
+
+
 def block_nearest(x, t: int, c: int, lengths=None):
     """(tbl, nc, nt) of consecutive blocks of t targets in the given order, each conditioned on the c EARLIER rows (rows
-    before its first target) nearest to the block's centroid under the Euclidean distance of x / lengths, nearest first,
-    ties to the lower index.  O(N^2 D / t) on the host.  block_nearest(x, 1, m) names the rows of nearest(x, m)."""
+    before its first target) nearest to the block's centroid (_centroid) under the Euclidean distance of x / lengths,
+    nearest first, ties to the lower index.  O(N^2 D / t) on the host; GP.VecchiaBlockTables and GP.SetVecchiaBlocksNearest
+    run the same search on the device and return this table integer for integer.  block_nearest(x, 1, m) names the rows
+    of nearest(x, m)."""
     t, c = _block_ok(t, c)
     xs = _scaled(x, lengths)
     n = len(xs)
+    cens = _centroid(xs, t)
     cond, targ = [], []
     for s in range(0, n, t):
         e = min(s + t, n)
         k = min(c, s)
         if k:
-            cen = xs[s:e].mean(axis=0, keepdims=True) if e - s > 1 else xs[s:e]
+            cen = cens[s // t:s // t + 1]
             cond.append(_smallest(_d2(cen, xs[:s]), k)[0])
         else:
             cond.append(np.zeros(0, dtype=np.int64))
@@ -146,7 +168,9 @@ def block_nearest(x, t: int, c: int, lengths=None):
 
 def group_nearest_to(x, z, g: int, c: int, lengths=None):
     """For GP.VecchiaBlockProduce: consecutive groups of g test points (rows of z), each conditioned on the c rows of x
-    nearest to the group's centroid.  Returns (offsets, (tbl, nc)): ng + 1 offsets into z, the ng x c table and counts."""
+    nearest to the group's centroid (_centroid).  Returns (offsets, (tbl, nc)): ng + 1 offsets into z, the ng x c table and
+    counts.  GP.VecchiaBlockTables(x, g, c, lengths, z) and GP.VecchiaBlockProduceNearest find the same table on the
+    device."""
     g, c = int(g), int(c)
     if g < 1 or not 0 <= c <= MAX_BLOCK:
         raise ValueError("group_nearest_to: g >= 1 test points, 0 <= c <= %d conditioning rows" % MAX_BLOCK)
@@ -156,9 +180,10 @@ def group_nearest_to(x, z, g: int, c: int, lengths=None):
         raise ValueError("group_nearest_to: x and z differ in dimension")
     mz, k = len(zs), min(c, len(xs))
     offsets = np.append(np.arange(0, mz, g, dtype=np.int64), mz) if mz else np.zeros(1, dtype=np.int64)
+    cens = _centroid(zs, g) if mz else zs
     cond = []
-    for a, b in zip(offsets[:-1], offsets[1:]):
-        cen = zs[a:b].mean(axis=0, keepdims=True) if b - a > 1 else zs[a:b]
+    for i in range(len(offsets) - 1):
+        cen = cens[i:i + 1]
         cond.append(_smallest(_d2(cen, xs), k)[0] if k else np.zeros(0, dtype=np.int64))
     tbl, nc, _ = _pack(cond, [()] * len(cond), c)
     return offsets, (tbl, nc)

@@ -825,6 +825,44 @@ int gogp_vecchia_blocks_produce(gogp_handle *h, const double *Z, int64_t mz, con
                                 const int32_t *tblz /* ng x wz */, int32_t wz, const int32_t *ncz, double *mu,
                                 double *sigma /* may be NULL */);
 
+/* Block tables built on the device (vecchia_bknn.hip): gogp_amd/vecchia.py's block_nearest and group_nearest_to, and the
+ * same tables integer for integer.  xs, d2 and the order of the keys are those of "Neighbour tables built on the device"
+ * above.  A query is the centroid of a block of t consecutive scaled rows: their sum in index order, one IEEE add per row,
+ * and one IEEE division by the row count (a block of one row is the row itself).  Block k of the causal form has s_k = k t,
+ * searches the rows j < s_k for min(c, s_k) entries, and row k of its table (nb x w, nb = ceil(N / t), w = t + c) holds the
+ * nc_k conditioning rows nearest first, then the targets s_k .. min(s_k + t, N) - 1, then -1.  A group of the query form --
+ * t consecutive rows of Z -- searches all j < N for min(c, N) entries; its table is ceil(mz / t) x c.  t >= 1, c >= 0,
+ * t + c <= 128 for a block, c <= 128 for a group; c == 0 searches nothing.  The key is a strict total order: identical
+ * calls give identical tables, whatever the launch.  Cost: N^2 / (2 t) (causal) or ceil(mz / t) N pairs of 3 ndim fp64
+ * operations; the search of a few queries is cut over the candidates; the scratch beside the scaled copy, the centroids and
+ * the lists stays under 10 MiB.
+ * gogp_vecchia_blocks_nearest: one-shot, nothing of the handle changes; Z == NULL (mz == 0): the causal block table of X
+ * into tbl (nb x w), nc and nt (nb each); else the groups' table into tbl (ceil(mz / t) x c) and nc, with nt NULL.
+ * gogp_vecchia_blocks_set_data_nearest: gogp_vecchia_blocks_set_data, with the table built on the device from the uploaded
+ * X; it stays there, with the search's scratch (the scaled copy of X, the centroids, the lists).
+ * gogp_vecchia_blocks_reneighbour: rebuilds the resident table from the resident X under new lengths (NULL: unscaled), same
+ * t and c; also a table that gogp_vecchia_blocks_set_data brought, if block k's targets are the rows k t .. min(k t + t, N)
+ * - 1 for t = nt_0 (then c = w - t), else GOGP_ESTATE.  The last observe is dropped: gradient and the produce calls want
+ * a new one.
+ * gogp_vecchia_blocks_get_table: the resident table (nb x w), nc and nt.
+ * gogp_vecchia_blocks_produce_nearest: groups of g consecutive test points, each conditioned on the c resident rows nearest
+ * to its centroid, found on the device; then gogp_vecchia_blocks_produce's launch on that table.  lengths NULL: those the
+ * resident table was built with (GOGP_ESTATE if a caller brought it); tblz, unless NULL, receives the table (ceil(mz / g) x c).
+ * GOGP_EARG (gogp_last_error names the argument): t < 1, c < 0, t + c > 128 for a block, c > 128 for a group, a length that
+ * is not positive and finite, N >= 2^31, NULL pointers, and the handles the block calls refuse.  GOGP_ESTATE: reneighbour,
+ * get_table and produce_nearest without resident data; reneighbour on a table of another shape; produce_nearest before an
+ * observe.  DESIGN.md section 4, "Vecchia: block tables on the device". */
+int gogp_vecchia_blocks_nearest(gogp_handle *h, const double *X, int64_t N, const double *Z /* may be NULL */, int64_t mz,
+                                int32_t t, int32_t c, const double *lengths /* ndim; may be NULL */, int32_t *tbl,
+                                int32_t *nc, int32_t *nt /* NULL with Z */);
+int gogp_vecchia_blocks_set_data_nearest(gogp_handle *h, const double *X, const double *y, const double *v /* may be NULL */,
+                                         int64_t N, int32_t t, int32_t c, const double *lengths /* may be NULL */);
+int gogp_vecchia_blocks_reneighbour(gogp_handle *h, const double *lengths /* may be NULL */);
+int gogp_vecchia_blocks_get_table(gogp_handle *h, int32_t *tbl /* nb x w */, int32_t *nc, int32_t *nt);
+int gogp_vecchia_blocks_produce_nearest(gogp_handle *h, const double *Z, int64_t mz, int32_t g, int32_t c,
+                                        const double *lengths /* may be NULL */, double *mu, double *sigma /* may be NULL */,
+                                        int32_t *tblz /* ceil(mz / g) x c, may be NULL */);
+
 /* k independent Observe + Gradient evaluations at once: handle hs[i] (each created and given
  * its data separately; they may hold the same data) evaluates x[i*len .. (i+1)*len) from its own
  * host thread, so the dependent launch chains of the k evaluations overlap on the GPU.

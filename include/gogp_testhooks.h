@@ -737,6 +737,22 @@ int gogp_test_vecchia_knn(int device, const double *X, int64_t x_len, int64_t n,
                           int64_t nbr_len, double *d2, int64_t d2_len, double *xs, int64_t xs_len);
 int gogp_test_vecchia_knn_plan(int64_t targets, int64_t n, int m, int64_t out[3]);
 
+/* ---- the selection of vecchia_bknn.hip (tests/test_vecchia_bknn_kernel.py), through its product launchers on
+ * caller-supplied rows.  X: n x ndim (x_len >= n ndim).  Z NULL with length 0: the causal form -- the queries are the
+ * centroids of the ceil(n / t) blocks of t rows of X, query k over the rows j < k t; else the centroids of the ceil(mz / t)
+ * groups of t rows of Z (z_len >= mz ndim) over all of X.  lengths: ndim values > 0 or NULL.  t >= 1, 0 <= c <= 128, n and mz
+ * in 1 .. 2^20, 0 <= qt <= 8 and 0 <= slabs <= 256 (> 0 forces the queries of a tile / the candidate split).  In / out: nbr
+ * (nbr_len >= queries c) the lists, d2 (same length) the squared distance of every entry taken (0.0 under the padding), cnt
+ * (cnt_len >= queries) the entries taken, cen (cen_len >= queries ndim) the centroids; with c == 0 nothing but cen is
+ * written.  Every length is checked before the device is touched.
+ * gogp_test_vecchia_bknn_plan: out = {queries of a tile, slabs, bytes of workspace} of a search of `queries` centroids over
+ * n candidates: tile k holds the queries [k qt, min(queries, (k + 1) qt)), slab s the candidates [s L, min(n, (s + 1) L))
+ * with L = ceil(n / slabs); the workspace stays under 768 * 8 * 12 * c bytes.  No device. */
+int gogp_test_vecchia_bknn(int device, const double *X, int64_t x_len, int64_t n, int ndim, const double *Z, int64_t z_len,
+                           int64_t mz, const double *lengths, int t, int c, int qt, int slabs, int32_t *nbr, int64_t nbr_len,
+                           double *d2, int64_t d2_len, int32_t *cnt, int64_t cnt_len, double *cen, int64_t cen_len);
+int gogp_test_vecchia_bknn_plan(int64_t queries, int64_t n, int c, int64_t out[3]);
+
 #ifdef __cplusplus
 }
 #endif
