@@ -580,6 +580,19 @@ func (gp *GP) LOOGradient() ([]float64, error) {
 	return g, nil
 }
 
+// LMLHessian computes the Hessian of the log marginal likelihood with respect
+// to the log-transformed hyperparameters, P x P row-major (no reference
+// counterpart).
+func (gp *GP) LMLHessian() ([]float64, error) {
+	gp.defaults()
+	p := len(gp.ThetaSimil) + len(gp.ThetaNoise)
+	h := make([]float64, p*p)
+	if err := gp.err(C.gogp_lml_hessian(gp.handle(), dptr(h))); err != nil {
+		return nil, err
+	}
+	return h, nil
+}
+
 // Blocks returns start for BlockCV: n rows in consecutive blocks of length
 // rows, the last one shorter where length does not divide n.
 func Blocks(n, length int) []int64 {

@@ -114,6 +114,7 @@ SYMBOLS = [
     ("gogp_gradient", ctypes.c_int, [_h, _dp, _i64]),
     ("gogp_loo", ctypes.c_int, [_h, _dp, _dp, _dp, _dp]),
     ("gogp_loo_gradient", ctypes.c_int, [_h, _dp, _i64]),
+    ("gogp_lml_hessian", ctypes.c_int, [_h, _dp]),
     ("gogp_blockcv_check", ctypes.c_int, [ctypes.POINTER(_i64), _i64, _i64]),
     ("gogp_blockcv_groups", ctypes.c_int, [ctypes.POINTER(_i64), _i64, ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
     ("gogp_blockcv", ctypes.c_int, [_h, ctypes.POINTER(_i64), _i64, _dp, _dp, _dp, _dp]),
@@ -507,6 +508,11 @@ HOOK_SYMBOLS += [
     ("gogp_test_cg_quadrature", _ci, [_dp, _dp, _i64, ctypes.c_double, _dp]),
     ("gogp_test_cg_precond", _ci, [_ci, _dp, _i64, _i64, _i64, _ci, _dp, _i64, _dp, _i64, _dp, _i64, _i64, _ci, _dp, _i64,
                                    _dp, _i64]),
+]
+
+#: the hook of the tile product of hessian.hip (tests/test_hessian_kernel.py; hessian.kmm_check)
+HOOK_SYMBOLS += [
+    ("gogp_test_hess_kmm", _ci, [_ci, _kpp, _ci, _ci, _i32p, _i32p, _dp, _i64, _i64, _i64, _dp, _i64, _i64, _dp, _i64]),
 ]
 
 #: the hook of the kernel of vecchia.hip (tests/test_vecchia_kernel.py; gp.vecchia_check)

@@ -106,6 +106,7 @@ static void free_n_buffers(gogp_handle *h) {
   h->rm_ws.release();
   h->loo_vec.release();
   h->loo_mat.release();
+  h->hess_ws.release();
   h->lap_ws.release();
   h->lap_observed = h->lap_grad_valid = h->lap_warm_valid = false;
   (void)hipFree(h->nv);
@@ -1472,6 +1473,11 @@ static int compute_kinv_t(gogp_handle *h) {
 }
 static int compute_kinv(gogp_handle *h) {
   return h->prec == 32 ? compute_kinv_t<float>(h) : compute_kinv_t<double>(h);
+}
+
+int gogp::regression_kinv_alpha(gogp_handle *h) {
+  const int rc = compute_kinv(h);
+  return rc == GOGP_OK ? ensure_alpha(h) : rc;
 }
 
 static int64_t grad_len(const gogp_handle *h) {

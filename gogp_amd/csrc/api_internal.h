@@ -17,6 +17,9 @@ void assemble_gradient(const gogp_handle *h, const double *a, double dnoise, dou
 // GOGP_OK, or GOGP_EARG for no handle (h == NULL) and, with "<who>: <why>" as the error text, for the kinds of handle both
 // families refuse: precision = 32, sharded, event discounts
 int refuse_handle(gogp_handle *h, const char *who);
+// K^-1 (lower tiles of bufA) and alpha of the current factor ordered on the main stream, as gogp_loo_gradient obtains them
+// (hessian.hip); the handle's state afterwards is what a gogp_gradient at this point would have left
+int regression_kinv_alpha(gogp_handle *h);
 
 // ---- shared host code ------------------------------------------------------------------------------------------------------
 // `code`, with "<who>: <what>" as the handle's error text

@@ -875,5 +875,22 @@ void launch_add_inplace(hipStream_t s, double *a, const double *b, int64_t count
 void launch_add_inplace(hipStream_t s, float *a, const float *b, int64_t count);
 void launch_scale(hipStream_t s, double *a, double f, int64_t count);                 // a *= f
 void launch_add_vec(hipStream_t s, double *a, const double *b, int64_t count);        // a += b
+// hessian.hip (gogp_lml_hessian).  A group: nslot <= 3 (a periodic term: 2) parameters ("slots") of term `term` that share one radial
+// evaluation -- type[q] (hess_eval.h: 0 the term's value, 1 its length, 2 the ARD length of dimension dim[q], 3 the period).
+// launch_hess_kmm: M_q (npad x npad at M + q * mstride, leading dimension ldm >= npad) = K^-1 K_q, K_q = dK / dlog of slot
+// q, on the matrix cores; whole 64-tiles are written, exact zeros from row / column n on; npad a multiple of 64.  Of Kinv
+// (ld) only the elements j <= i < n are read, of X n rows of ndim doubles.
+// launch_hess_pair: out (HESS_NMOM doubles, hess_eval.h: hess_moments) = the sums over i, j < n, weighted with alpha_i alpha_j
+// - Kinv_ij, from which the host forms sum_ij W_ij K_ab,ij for the second derivatives of two groups of one term; part:
+// npad / 64 * (npad / 64 + 1) / 2 * HESS_NMOM doubles of scratch.  periodic: the term's kind is GOGP_K_PERIODIC.
+// launch_hess_kvec: b_q (row q of b, ldb >= npad doubles) = K_q alpha, zero from row n on.
+void launch_hess_kmm(hipStream_t s, const DevParams *p, int ndim, bool periodic, int term, int nslot, const int *type, const int *dim,
+                     const double *X, const double *Kinv, int64_t ld, int64_t n, int64_t npad, double *M, int64_t ldm,
+                     int64_t mstride);
+void launch_hess_pair(hipStream_t s, const DevParams *p, int ndim, bool periodic, int term, int na, const int *type_a, const int *dim_a,
+                      int nb, const int *type_b, const int *dim_b, const double *X, const double *alpha, const double *Kinv,
+                      int64_t ld, int64_t n, int64_t npad, double *part, double *out);
+void launch_hess_kvec(hipStream_t s, const DevParams *p, int ndim, bool periodic, int term, int nslot, const int *type, const int *dim,
+                      const double *X, const double *alpha, int64_t n, int64_t npad, double *b, int64_t ldb);
 
 }  // namespace gogp

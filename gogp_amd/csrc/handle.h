@@ -318,6 +318,7 @@ struct gogp_handle : EvalBufs, EvalState {
   Workspace rm_ws;          // gogp_remove: index maps, a pass's columns of W, the diagonal-block snapshot, compacted X / y (remove.hip)
   Workspace loo_vec;        // gogp_loo / gogp_loo_gradient: mu, sigma, log p, v, s, u, a zero vector and the block sums (loo.hip)
   Workspace loo_mat;        // gogp_loo_gradient: B = K^-1 diag(s) and G = B B^T - u alpha^T - alpha u^T, npad x npad each
+  Workspace hess_ws;        // gogp_lml_hessian: the M_s = K^-1 K_s (npad x npad per slot), b_s, c_s, partial sums (hessian.hip)
   Workspace bcv_vec;        // gogp_blockcv / gogp_blockcv_gradient: the vectors, the block and group tables, the pivots (blockcv.hip)
   Workspace bcv_s;          // ... and the groups' 128 x 128 S_g; the gradient's two matrices are loo_mat
   // T output columns on the handle's factorisation (gogp_multi_*, multi.hip); all released with the N buffers

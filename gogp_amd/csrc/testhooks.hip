@@ -2525,6 +2525,26 @@ extern "C" int gogp_test_kmm32(int device, const gogp_test_kparams *kparams, con
              });
 }
 
+// launch_hess_kmm (hessian.hip): the tile product M_q = K^-1 K_q alone, for one group of slots of one term
+extern "C" int gogp_test_hess_kmm(int device, const gogp_test_kparams *kparams, int term, int nslot, const int *type,
+                                  const int *dim, const double *X, int64_t x_len, int64_t n, int64_t npad, const double *Kinv,
+                                  int64_t k_len, int64_t ld, double *M, int64_t m_len) {
+  if (!kparams || !type || !dim || !X || !Kinv || !M || !gram_args_ok(kparams, 1, 0, 0)) return GOGP_EARG;
+  if (kparams->nevents != 0 || term < 0 || term >= kparams->nterms || nslot < 1 ||
+      nslot > (kparams->kind[term] == GOGP_K_PERIODIC ? 2 : 3))
+    return GOGP_EARG;
+  const int ndim = kparams->ndim;
+  for (int q = 0; q < nslot; ++q)
+    if (type[q] < 0 || type[q] > 3 || dim[q] < 0 || dim[q] >= ndim) return GOGP_EARG;
+  if (!pad_ok(npad) || n < 1 || n > npad || ld < n || x_len < n * ndim || !covers(k_len, 0, ld, n, n, 1, 0) ||
+      m_len < (int64_t)nslot * npad * npad)
+    return GOGP_EARG;
+  const DevParams hp = to_dev(*kparams);
+  return run(device, {rd(&hp, 1, sizeof hp), rd(X, x_len), rd(Kinv, k_len), io(M, m_len)}, [&](const Dev &d) {
+    launch_hess_kmm(0, d.as<DevParams>(0), ndim, hp.kind[term] == GOGP_K_PERIODIC, term, nslot, type, dim, d[1], d[2], ld, n, npad, d[3], npad, npad * npad);
+  });
+}
+
 // out may be NULL (length 0) except in mode CG_DOT_PLAIN; st holds 32-bit integers
 extern "C" int gogp_test_cg_dots(int device, const double *A, int64_t a_len, const double *B, int64_t b_len, int64_t ld,
                                  int64_t n, int T, int mode, int it, double tol, double *part, int64_t part_len, double *out,

@@ -217,6 +217,14 @@ class GP {
     return g;
   }
 
+  // The Hessian of the LML in the log hyperparameters, P x P row-major (gogp_lml_hessian)
+  std::vector<double> LMLHessian() {
+    const size_t P = ThetaSimil.size() + ThetaNoise.size();
+    std::vector<double> H(P * P, 0.0);
+    check(gogp_lml_hessian(h_, H.data()));
+    return H;
+  }
+
   // Non-Gaussian likelihoods by the Laplace approximation (gogp_laplace_*; no reference counterpart).  LaplaceObserve:
   // the approximate log marginal likelihood of Y under `lik` (GOGP_LIK_BERNOULLI_LOGIT: Y in {0, 1};
   // GOGP_LIK_POISSON_LOG: counts) at x = log theta, the mode found by a damped Newton iteration; drops the regression

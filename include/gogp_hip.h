@@ -227,6 +227,27 @@ int gogp_gradient(gogp_handle *h, double *grad, int64_t len);
 int gogp_loo(gogp_handle *h, double *mu, double *sigma, double *logp, double *total);
 int gogp_loo_gradient(gogp_handle *h, double *grad, int64_t len);
 
+/* The Hessian of the LML in the log hyperparameters at the parameters of the last gogp_absorb / gogp_observe[_full] /
+ * gogp_set_factor; no reference counterpart.  H is P x P row-major, P = ntheta_simil + ntheta_noise, symmetric bit for bit.
+ * With K_i = dK / dlog theta_i, K_ij the second derivative, alpha = K^-1 y and W = alpha alpha^T - K^-1:
+ *     H_ij = 1/2 tr(W K_ij) - (K_i alpha)^T K^-1 (K_j alpha) + 1/2 tr(K^-1 K_i K^-1 K_j)
+ * -- what the Laplace approximation over the hyperparameters (Rasmussen & Williams 5.2), a Newton step or a mass matrix
+ * needs, exact instead of 2 P central differences of the gradient.  Every kernel family, ARD, sums and the parametrised
+ * noise kinds are covered (closed-form second derivatives, csrc/hess_eval.h); the products M_i = K^-1 K_i run on the
+ * matrix cores with K_i evaluated on the fly from X (csrc/hessian.hip), the noise parameter's from K^-1 directly.
+ * Works wherever gogp_loo_gradient works, obtains alpha and K^-1 as it does and leaves the handle as it found it: stored
+ * results of other calls stay valid, and two identical calls return identical bits (fixed-order sums, no atomics).
+ * n == 0: zeros.  A parameter the Gram matrix does not depend on (GOGP_NOISE_CONSTANT_PARAM) has a zero row and column.
+ * GOGP_EARG: NULL, a precision = 32 handle, "gradient_precision" = 32, event discounts, a sharded handle.  GOGP_ESTATE
+ * before anything is factored.  GOGP_ENOMEM: one npad x npad fp64 matrix per occurrence of a similarity parameter in a
+ * term (8 npad^2 bytes each, kept until the data's buffers are released) does not fit; the message names the bytes
+ * needed, and nothing is allocated.
+ * Cost, measured on one MI355X (profiles/hessian.txt; D = 8, beside the 2 P evaluations of Observe + Gradient that central
+ * differences take): n = 1024 / 4096 / 16384, P = 3: 0.61 / 11.8 / 673 ms against 4.4 / 16.2 / 430 ms; P = 10 (ARD, D = 8):
+ * 2.08 / 46.6 / 2574 ms against 14.3 / 55.7 / 1437 ms.  At n = 16384 differences are 1.6 - 1.8 times FASTER (a parameter
+ * costs 2 n^3 flops at >= 26 - 31 TFLOP/s, an evaluation n^3 at 71); they keep half the digits. */
+int gogp_lml_hessian(gogp_handle *h, double *H /* P * P, row-major */);
+
 /* Leave-block-out ("h-block", leave-out-k; Rasmussen & Williams 5.4.2) cross-validation at the parameters of the last
  * gogp_absorb / gogp_observe[_full] / gogp_set_factor; no reference counterpart.  The rows are cut into F consecutive
  * blocks B_f = [start[f], start[f + 1]), start[0] = 0, start[F] = n, of 1 .. GOGP_BLOCKCV_MAX rows each, and every block

@@ -665,6 +665,14 @@ int gogp_test_kmm32(int device, const gogp_test_kparams *kparams, const double *
                     const double *B, int64_t b_len, int64_t cols, const double *centre, int64_t centre_len, const double *V,
                     int64_t v_len, int64_t ldv, int T, const double *diag, int64_t diag_len, int nslab, int max_blocks,
                     double *part, int64_t part_len, double *Out, int64_t out_len, int64_t ldo);
+/* launch_hess_kmm (hessian.hip: the tile product of gogp_lml_hessian alone): M (in / out; nslot matrices of npad x npad,
+ * one behind the other) [q] = Kinv K_q with K_q = dK / dlog of slot q of term `term`, evaluated on the fly from X (n rows
+ * of ndim doubles): type[q] 0 the term's value, 1 its length, 2 the ARD length of dimension dim[q], 3 the period; 1 <=
+ * nslot <= 3 (2 for a periodic term).  Of Kinv (n rows of ld >= n) only the elements j <= i < n are read; whole 64-tiles of M are written, exact
+ * zeros from row / column n on; npad a multiple of 64.  No event discounts. */
+int gogp_test_hess_kmm(int device, const gogp_test_kparams *kparams, int term, int nslot, const int *type, const int *dim,
+                       const double *X, int64_t x_len, int64_t n, int64_t npad, const double *Kinv, int64_t k_len, int64_t ld,
+                       double *M, int64_t m_len);
 /* launch_cg_dots: the T dot products A[t] . B[t] and, by mode (0 plain, 1 |b|^2, 2 rho0, 3 p^T q, 4 |r|^2 and the freeze
  * test, 5 beta), the update of sc / st (in / out).  part (in / out): T x gogp_test_cg_dot_blocks(n); out (in / out, T;
  * NULL with length 0 except in mode 0) receives the dot products. */
