@@ -1134,6 +1134,53 @@ func (gp *GP) Sample(x [][]float64, xi []float64, diagAdd float64) (samples []fl
 	return samples, nil
 }
 
+// Paths holds S pathwise posterior function draws (gogp_pathwise_*; no
+// reference counterpart): f_s(z) = phi(z)^T w_s + k(z, X) v_s with the caller's
+// random Fourier features and normals.  It owns copies of everything it reads
+// and stays valid whatever happens to the GP afterwards.  Close frees it.
+type Paths struct {
+	p       *C.gogp_paths
+	S, NDim int
+}
+
+// DrawPaths fixes S draws at the current parameters and data: omega is R x
+// NDim, phase and amp have R entries, w is R x S and xi S x n, all row-major.
+func (gp *GP) DrawPaths(omega, phase, amp []float64, S int, w, xi []float64) (*Paths, error) {
+	gp.defaults()
+	R := len(amp)
+	n := int(C.gogp_n(gp.handle()))
+	if len(omega) != R*gp.NDim || len(phase) != R || len(w) != R*S || len(xi) != S*n {
+		return nil, fmt.Errorf("gogp: DrawPaths: array sizes")
+	}
+	ps := &Paths{S: S, NDim: gp.NDim}
+	if err := gp.err(C.gogp_pathwise_create(gp.handle(), C.int32_t(R), dptr(omega), dptr(phase), dptr(amp), C.int32_t(S), dptr(w), dptr(xi), &ps.p)); err != nil {
+		return nil, err
+	}
+	return ps, nil
+}
+
+// Eval returns f (S x m) and, with grad, df (S x m x NDim) at the m points z
+// (m x NDim, row-major).
+func (ps *Paths) Eval(z []float64, grad bool) (f, df []float64, err error) {
+	m := len(z) / ps.NDim
+	f = make([]float64, ps.S*m)
+	var dp *C.double
+	if grad {
+		df = make([]float64, ps.S*m*ps.NDim)
+		dp = dptr(df)
+	}
+	if rc := C.gogp_pathwise_eval(ps.p, dptr(z), C.int64_t(m), dptr(f), dp); rc != C.GOGP_OK {
+		return nil, nil, fmt.Errorf("gogp: gogp_pathwise_eval: error %d", int(rc))
+	}
+	return f, df, nil
+}
+
+// Close frees the draws.
+func (ps *Paths) Close() {
+	C.gogp_pathwise_destroy(ps.p)
+	ps.p = nil
+}
+
 // Observe computes the log marginal likelihood of log-transformed
 // hyperparameters [, inputs, outputs] (gp/gp.go:374-413).  Panics where the
 // reference panics.

@@ -10,7 +10,7 @@ constructing a ``GP`` raises if the library or a HIP device is missing.
 """
 from . import kernel  # noqa: F401
 
-__all__ = ["kernel", "gp", "vecchia", "CGModel", "VecchiaModel", "VecchiaBlockModel", "lml_hessian", "laplace_evidence"]
+__all__ = ["kernel", "gp", "vecchia", "CGModel", "VecchiaModel", "VecchiaBlockModel", "lml_hessian", "laplace_evidence", "pathwise"]
 __version__ = "0.1.0"
 
 
@@ -28,6 +28,9 @@ def __getattr__(name):
     if name in ("lml_hessian", "laplace_evidence"):  # the LML Hessian and the Laplace evidence built on it (hessian.py)
         from . import hessian
         return getattr(hessian, name)
+    if name == "pathwise":  # pathwise posterior samples: function draws (pathwise.py)
+        import importlib
+        return importlib.import_module(".pathwise", __name__)
     if name == "vecchia":  # the host helpers that build neighbour tables (numpy only)
         import importlib
         return importlib.import_module(".vecchia", __name__)

@@ -213,6 +213,11 @@ SYMBOLS = [
     ("gogp_produce_gradient", ctypes.c_int, [_h, _dp, _i64, _dp, _dp, _dp, _dp]),
     ("gogp_produce_covariance", ctypes.c_int, [_h, _dp, _i64, _dp, _dp]),
     ("gogp_produce_samples", ctypes.c_int, [_h, _dp, _i64, _dp, _i64, ctypes.c_double, _dp, _dp]),
+    ("gogp_pathwise_create", ctypes.c_int, [_h, ctypes.c_int32, _dp, _dp, _dp, ctypes.c_int32, _dp, _dp,
+                                            ctypes.POINTER(ctypes.c_void_p)]),
+    ("gogp_pathwise_eval", ctypes.c_int, [ctypes.c_void_p, _dp, _i64, _dp, _dp]),
+    ("gogp_pathwise_get_v", ctypes.c_int, [ctypes.c_void_p, _dp]),
+    ("gogp_pathwise_destroy", ctypes.c_int, [ctypes.c_void_p]),
     ("gogp_n", _i64, [_h]),
     ("gogp_get_alpha", ctypes.c_int, [_h, _dp]),
     ("gogp_get_factor", ctypes.c_int, [_h, _dp]),
@@ -513,6 +518,12 @@ HOOK_SYMBOLS += [
 #: the hook of the tile product of hessian.hip (tests/test_hessian_kernel.py; hessian.kmm_check)
 HOOK_SYMBOLS += [
     ("gogp_test_hess_kmm", _ci, [_ci, _kpp, _ci, _ci, _i32p, _i32p, _dp, _i64, _i64, _i64, _dp, _i64, _i64, _dp, _i64]),
+]
+
+#: the hooks of the kernels of pathwise.hip (tests/test_pathwise_kernels.py; pathwise.features_check, pathwise.crossgrad_check)
+HOOK_SYMBOLS += [
+    ("gogp_test_pw_features", _ci, [_ci, _ci, _ci, _dp, _i64, _dp, _dp, _dp, _i64, _i64, _dp, _i64, _ci, _ci, _dp, _i64]),
+    ("gogp_test_pw_crossgrad", _ci, [_ci, _kpp, _dp, _i64, _i64, _dp, _i64, _i64, _dp, _i64, _i64, _ci, _dp, _i64]),
 ]
 
 #: the hook of the kernel of vecchia.hip (tests/test_vecchia_kernel.py; gp.vecchia_check)

@@ -2932,21 +2932,31 @@ extern "C" int gogp_multi_set_outputs(gogp_handle *h, const double *Y, int64_t n
   return GOGP_OK;
 }
 
-// A^T = (K^-1 Y)^T of the current factor into its buffer, on the main stream
-static int multi_solve(gogp_handle *h) {
-  if (h->multi_solved) return GOGP_OK;
-  const int T = h->multi_T;
+// out (T rows of npad doubles) = the rows of rhs (one tile row: TILE rows of npad doubles, zero from row T and column n on)
+// solved through the current factor, on the main stream: Produce's forward and ProduceGradient's backward substitution.
+// Writes Produce's workspaces, whose contents no call expects to find again.
+int gogp::factor_solve_rows(gogp_handle *h, const double *rhs, int T, double *out) {
   int rc = ensure_alpha(h);  // the main stream behind the factorisation
   if (rc == GOGP_OK) rc = ensure_m(h, T, TILE);
   if (rc != GOGP_OK) return rc;
   hipStream_t s = h->s;
   const size_t row = (size_t)h->npad * sizeof(double);
-  static_assert(GOGP_MULTI_MAX_T == TILE, "the outputs are one tile row of right-hand sides");
-  HIPCHK(h, hipMemcpyAsync(h->KsT, multi_yt(h), TILE * row, hipMemcpyDeviceToDevice, s));
-  produce_substitute_t<double>(h, s, T, TILE, nullptr);  // V^T = Y^T L^-T into Vt
+  HIPCHK(h, hipMemcpyAsync(h->KsT, rhs, TILE * row, hipMemcpyDeviceToDevice, s));
+  produce_substitute_t<double>(h, s, T, TILE, nullptr);  // V^T = R L^-T into Vt
   produce_backward(h, s, T);                             // A^T = V^T L^-1 into KsT
-  HIPCHK(h, hipMemcpyAsync(multi_at(h), h->KsT, (size_t)T * row, hipMemcpyDeviceToDevice, s));
-  if (T < TILE) HIPCHK(h, hipMemsetAsync(multi_at(h) + (size_t)T * h->npad, 0, (size_t)(TILE - T) * row, s));
+  HIPCHK(h, hipMemcpyAsync(out, h->KsT, (size_t)T * row, hipMemcpyDeviceToDevice, s));
+  return GOGP_OK;
+}
+
+// A^T = (K^-1 Y)^T of the current factor into its buffer, on the main stream
+static int multi_solve(gogp_handle *h) {
+  if (h->multi_solved) return GOGP_OK;
+  const int T = h->multi_T;
+  static_assert(GOGP_MULTI_MAX_T == TILE, "the outputs are one tile row of right-hand sides");
+  const int rc = factor_solve_rows(h, multi_yt(h), T, multi_at(h));
+  if (rc != GOGP_OK) return rc;
+  if (T < TILE)
+    HIPCHK(h, hipMemsetAsync(multi_at(h) + (size_t)T * h->npad, 0, (size_t)(TILE - T) * h->npad * sizeof(double), h->s));
   h->multi_solved = true;
   return GOGP_OK;
 }

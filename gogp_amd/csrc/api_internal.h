@@ -1,4 +1,4 @@
-// api_internal.h -- what cg_api.hip (gogp_cg_*) and vecchia_api.hip (gogp_vecchia_*) take from api.hip, and the few lines
+// api_internal.h -- what cg_api.hip (gogp_cg_*), vecchia_api.hip (gogp_vecchia_*), hessian.hip and pathwise.hip take from api.hip, and the few lines
 // of host code the two families share.  Private to libgogp_hip.so.
 #pragma once
 #include <math.h>
@@ -20,6 +20,10 @@ int refuse_handle(gogp_handle *h, const char *who);
 // K^-1 (lower tiles of bufA) and alpha of the current factor ordered on the main stream, as gogp_loo_gradient obtains them
 // (hessian.hip); the handle's state afterwards is what a gogp_gradient at this point would have left
 int regression_kinv_alpha(gogp_handle *h);
+// out (T <= TILE rows of npad doubles, device) = K^^-1 applied to the rows of rhs (device; TILE rows of npad doubles, zero from
+// row T and from column n on), through the current factor by Produce's forward and ProduceGradient's backward substitution
+// on the main stream (gogp_multi_*, pathwise.hip); writes Produce's workspaces only
+int factor_solve_rows(gogp_handle *h, const double *rhs, int T, double *out);
 
 // ---- shared host code ------------------------------------------------------------------------------------------------------
 // `code`, with "<who>: <what>" as the handle's error text

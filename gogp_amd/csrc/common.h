@@ -893,4 +893,21 @@ void launch_hess_pair(hipStream_t s, const DevParams *p, int ndim, bool periodic
 void launch_hess_kvec(hipStream_t s, const DevParams *p, int ndim, bool periodic, int term, int nslot, const int *type, const int *dim,
                       const double *X, const double *alpha, int64_t n, int64_t npad, double *b, int64_t ldb);
 
+// pathwise.hip (gogp_pathwise_*): pathwise posterior samples.  Features phi_r(z) = am[r] cos(Om[r] . z + ph[r]), r < R (Om: R x
+// ndim), W: R x S row-major, 1 <= S <= CG_MAX_T.
+// launch_pw_features: part[(slab * S + s) * rpad + i] (grad: ... * ndim + d) = the slab's share of sum_r phi_r(z_i) W[r][s]
+// (grad: of its derivative in z_d) for i < m, s < S on v_mfma_f64_16x16x4_f64; rpad = m rounded up to 64; nslab slabs of
+// 64-feature tiles (1 <= nslab <= KMM_SLABS_MAX; pw_feature_slabs gives the call's choice, a function of m and R alone).
+// Elements of part with i >= m are not written.
+// launch_pw_crossgrad: part[((slab * S + s) * rpad + i) * ndim + d] = the slab's share of sum_j dk(z_i, x_j)/dz_d V[s][j],
+// launch_kmm's arguments, tiling and slabs (kmm_slabs(m, n)); no event discounts.
+// launch_pw_finish: Out[t][i] (ldo) = the na slabs of pa, then the nb slabs of pb (nullptr: none), added in that order, i < rows.
+int pw_feature_slabs(int64_t m, int R);
+void launch_pw_features(hipStream_t s, int ndim, const double *Om, const double *ph, const double *am, int R, const double *Z,
+                        int64_t m, const double *W, int S, bool grad, int nslab, double *part);
+void launch_pw_crossgrad(hipStream_t s, const DevParams *p, int ndim, const double *Z, int64_t m, const double *X, int64_t n,
+                         const double *V, int64_t ldv, int S, int nslab, double *part);
+void launch_pw_finish(hipStream_t s, const double *pa, int na, const double *pb, int nb, int T, int64_t rpad, int64_t rows,
+                      double *Out, int64_t ldo);
+
 }  // namespace gogp

@@ -2545,6 +2545,48 @@ extern "C" int gogp_test_hess_kmm(int device, const gogp_test_kparams *kparams, 
   });
 }
 
+// launch_pw_features + launch_pw_finish (pathwise.hip): the feature product alone, value (grad == 0: Out S x m) or gradient
+// (Out S x m x ndim), with the slabs the call itself would choose
+extern "C" int gogp_test_pw_features(int device, int ndim, int R, const double *Omega, int64_t om_len, const double *phase,
+                                     const double *amp, const double *Z, int64_t z_len, int64_t m, const double *W,
+                                     int64_t w_len, int S, int grad, double *Out, int64_t out_len) {
+  if (!Omega || !phase || !amp || !Z || !W || !Out || (grad != 0 && grad != 1)) return GOGP_EARG;
+  if (ndim < 1 || ndim > GOGP_MAX_NDIM || R < 1 || R > GOGP_PATHWISE_MAX_R || S < 1 || S > CG_MAX_T || m < 1 || m > GR_NPAD_MAX)
+    return GOGP_EARG;
+  const int64_t gd = grad ? ndim : 1;
+  if (om_len < (int64_t)R * ndim || z_len < m * ndim || w_len < (int64_t)R * S || out_len < S * m * gd) return GOGP_EARG;
+  const int nslab = pw_feature_slabs(m, R);
+  const int64_t rpad = (m + 63) / 64 * 64;
+  return run(device,
+             {rd(Omega, om_len), rd(phase, R), rd(amp, R), rd(Z, z_len), rd(W, w_len), io(Out, out_len),
+              scratch((size_t)nslab * S * rpad * gd * sizeof(double))},
+             [&](const Dev &d) {
+               launch_pw_features(0, ndim, d[0], d[1], d[2], R, d[3], m, d[4], S, grad != 0, nslab, d[6]);
+               launch_pw_finish(0, d[6], nslab, nullptr, 0, S, rpad * gd, m * gd, d[5], m * gd);
+             });
+}
+
+// launch_pw_crossgrad + launch_pw_finish (pathwise.hip): G[s][i][d] = sum_j dk(z_i, x_j)/dz_d V[s][j] alone (Out S x m x ndim),
+// with the slabs the call itself would choose
+extern "C" int gogp_test_pw_crossgrad(int device, const gogp_test_kparams *kparams, const double *Z, int64_t z_len, int64_t m,
+                                      const double *X, int64_t x_len, int64_t n, const double *V, int64_t v_len, int64_t ldv,
+                                      int S, double *Out, int64_t out_len) {
+  if (!kparams || !Z || !X || !V || !Out || !gram_args_ok(kparams, 1, 0, 0) || kparams->nevents != 0) return GOGP_EARG;
+  if (m < 1 || m > GR_NPAD_MAX || n < 1 || n > GR_NPAD_MAX || S < 1 || S > CG_MAX_T) return GOGP_EARG;
+  const int ndim = kparams->ndim;
+  if (z_len < m * ndim || x_len < n * ndim || !cg_block_ok(v_len, ldv, n, S) || out_len < S * m * ndim) return GOGP_EARG;
+  const int nslab = kmm_slabs(m, n);
+  const int64_t rpad = (m + 63) / 64 * 64;
+  const DevParams hp = to_dev(*kparams);
+  return run(device,
+             {rd(&hp, 1, sizeof hp), rd(Z, z_len), rd(X, x_len), rd(V, v_len), io(Out, out_len),
+              scratch((size_t)nslab * S * rpad * ndim * sizeof(double))},
+             [&](const Dev &d) {
+               launch_pw_crossgrad(0, d.as<DevParams>(0), ndim, d[1], m, d[2], n, d[3], ldv, S, nslab, d[5]);
+               launch_pw_finish(0, d[5], nslab, nullptr, 0, S, rpad * ndim, (int64_t)m * ndim, d[4], (int64_t)m * ndim);
+             });
+}
+
 // out may be NULL (length 0) except in mode CG_DOT_PLAIN; st holds 32-bit integers
 extern "C" int gogp_test_cg_dots(int device, const double *A, int64_t a_len, const double *B, int64_t b_len, int64_t ld,
                                  int64_t n, int T, int mode, int it, double tol, double *part, int64_t part_len, double *out,

@@ -889,4 +889,44 @@ class GP {
   }
 };
 
+// S pathwise posterior function draws (gogp_pathwise_*; no reference counterpart): f_s(z) = phi(z)^T w_s + k(z, X) v_s with
+// the caller's random Fourier features phi_r(z) = amp[r] cos(Omega[r] . z + phase[r]) and normals W (R x S), Xi (S x n).
+// Owns copies of everything it reads: it outlives the GP it was drawn from and never goes stale.
+class Paths {
+ public:
+  Paths(GP &gp, const std::vector<double> &Omega, const std::vector<double> &phase, const std::vector<double> &amp, int S,
+        const std::vector<double> &W, const std::vector<double> &Xi)
+      : S_(S), ndim_(gp.NDim), n_((size_t)gogp_n(gp.handle())) {
+    const size_t R = amp.size();
+    if (Omega.size() != R * (size_t)ndim_ || phase.size() != R || W.size() != R * (size_t)S || Xi.size() != (size_t)S * n_)
+      throw Error(GOGP_EARG, "Paths: array sizes");
+    const int rc = gogp_pathwise_create(gp.handle(), (int32_t)R, Omega.data(), phase.data(), amp.data(), S, W.data(),
+                                        Xi.data(), &p_);
+    if (rc != GOGP_OK) throw Error(rc, gogp_last_error(gp.handle()));
+  }
+  Paths(const Paths &) = delete;
+  Paths &operator=(const Paths &) = delete;
+  ~Paths() { gogp_pathwise_destroy(p_); }
+  // F (S x m, row-major) and, dF != nullptr, dF (S x m x NDim) at the m points z (m x NDim, row-major)
+  std::vector<double> Eval(const std::vector<double> &z, std::vector<double> *dF = nullptr) {
+    const size_t m = z.size() / (size_t)ndim_;
+    std::vector<double> F((size_t)S_ * m, 0.0);
+    if (dF) dF->assign((size_t)S_ * m * (size_t)ndim_, 0.0);
+    const int rc = gogp_pathwise_eval(p_, z.data(), (int64_t)m, F.data(), dF ? dF->data() : nullptr);
+    if (rc != GOGP_OK) throw Error(rc, "gogp_pathwise_eval");
+    return F;
+  }
+  std::vector<double> V() {  // S x n
+    std::vector<double> v((size_t)S_ * n_, 0.0);
+    const int rc = gogp_pathwise_get_v(p_, v.data());
+    if (rc != GOGP_OK) throw Error(rc, "gogp_pathwise_get_v");
+    return v;
+  }
+
+ private:
+  gogp_paths *p_ = nullptr;
+  int S_, ndim_;
+  size_t n_;
+};
+
 }  // namespace gogp

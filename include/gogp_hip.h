@@ -1019,6 +1019,42 @@ int gogp_produce_covariance(gogp_handle *h, const double *Z, int64_t m, double *
 int gogp_produce_samples(gogp_handle *h, const double *Z, int64_t m, const double *xi, int64_t ns, double diag_add,
                          double *mu /* m */, double *samples /* ns x m */);
 
+/* ---- pathwise posterior samples (csrc/pathwise.hip; DESIGN.md section 4, "Pathwise samples"); no reference counterpart ----
+ * gogp_produce_samples draws jointly at up to GOGP_COV_MAX_M points and the draw exists at those points only.  By Matheron's
+ * rule (Wilson et al. 2020, "Efficiently sampling functions from Gaussian process posteriors") a draw is a FUNCTION,
+ *     f_s(z) = phi(z)^T w_s + k(z, X) v_s,     v_s = K^^-1 (y - Phi(X) w_s - eps_s),     K^ = k(X, X) + sigma^2 I + diag(v),
+ * with R random Fourier features phi_r(z) = amp[r] cos(Omega[r] . z + phase[r]) of the prior, w_s ~ N(0, I) and eps_s,i =
+ * sqrt(sigma^2 + v_i) Xi[s][i]: fixed once, then evaluated and differentiated in z at any number of points for O(n) each.  The
+ * second term is exact; only the prior draw is approximated by the features.  Nothing random happens in the library: the
+ * features (gogp_amd.pathwise.spectral_features draws them from the kernel's spectral measure; any are accepted) and the
+ * normals W (R x S, row-major) and Xi (S x n) are the caller's.
+ *
+ * gogp_pathwise_create: on a factored fp64 handle, wherever gogp_produce works (after Absorb, Observe, Append, Remove or a
+ * restore; with or without per-observation variances): F_X = Phi(X) W on the feature kernel, the S residual columns, the
+ * handle's forward and backward substitutions.  The new object holds V and its OWN copies of X, the kernel parameters and the
+ * features: it does not depend on what happens to h afterwards (another Observe, new data, gogp_destroy) and is not part of
+ * the handle's state; the handle's stored results are left bit for bit as found (Produce's workspaces are written).
+ * 1 <= S <= GOGP_CG_MAX_RHS, 1 <= R <= GOGP_PATHWISE_MAX_R.  GOGP_EARG with a text in gogp_last_error(h): NULL, S or R out of
+ * range, non-finite input, a precision = 32 handle, "gradient_precision" = 32, event discounts, a sharded handle.
+ * GOGP_ESTATE: nothing factored (or no observations).  GOGP_ENOMEM: the bytes needed (named in the text) exceed what
+ * hipMemGetInfo reports free; nothing is allocated.
+ *
+ * gogp_pathwise_eval: F[s][j] = f_s(z_j) (S x m, row-major) and, dF != NULL, dF[s][j][d] = d f_s / d z_d at z_j (S x m x
+ * ndim) for any m >= 1, in passes of at most 16384 points: the feature kernel plus the matrix-free product k(Z, X) V, the
+ * feature kernel's gradient instances plus the cross-gradient kernel, all on v_mfma_f64_16x16x4_f64.  Every sum has a fixed
+ * order that depends on m, n and R alone: identical calls return identical bits, and a draw has the same bits alone as
+ * among 64.  GOGP_EARG: NULL, m < 1, a non-finite coordinate.  GOGP_ENOMEM: the pass's partial sums do not fit.
+ * gogp_pathwise_get_v: V (S x n).  gogp_pathwise_destroy: NULL is OK. */
+#define GOGP_PATHWISE_MAX_R 4096
+typedef struct gogp_paths gogp_paths;
+int gogp_pathwise_create(gogp_handle *h, int32_t R, const double *Omega /* R x ndim */, const double *phase /* R */,
+                         const double *amp /* R */, int32_t S, const double *W /* R x S */, const double *Xi /* S x n */,
+                         gogp_paths **paths);
+int gogp_pathwise_eval(gogp_paths *paths, const double *Z /* m x ndim */, int64_t m, double *F /* S x m */,
+                       double *dF /* S x m x ndim, or NULL */);
+int gogp_pathwise_get_v(gogp_paths *paths, double *V /* S x n */);
+int gogp_pathwise_destroy(gogp_paths *paths);
+
 /* ---- cached state (gp.GP.L, gp.GP.Alpha: gp/gp.go:35-36,255-257) ---------- */
 int64_t gogp_n(const gogp_handle *h);
 int gogp_get_alpha(gogp_handle *h, double *alpha /* n */);

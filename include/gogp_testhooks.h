@@ -673,6 +673,17 @@ int gogp_test_kmm32(int device, const gogp_test_kparams *kparams, const double *
 int gogp_test_hess_kmm(int device, const gogp_test_kparams *kparams, int term, int nslot, const int *type, const int *dim,
                        const double *X, int64_t x_len, int64_t n, int64_t npad, const double *Kinv, int64_t k_len, int64_t ld,
                        double *M, int64_t m_len);
+/* The feature product of the pathwise samples alone (pathwise.hip: launch_pw_features, launch_pw_finish), with the slabs
+ * gogp_pathwise_eval would choose: Out[s][i] = sum_r amp[r] cos(Omega[r] . z_i + phase[r]) W[r][s] (grad == 0; S x m) or its
+ * derivative in z_d (grad == 1; S x m x ndim).  Omega: R x ndim, W: R x S, Z: m x ndim; Out in / out. */
+int gogp_test_pw_features(int device, int ndim, int R, const double *Omega, int64_t om_len, const double *phase,
+                          const double *amp, const double *Z, int64_t z_len, int64_t m, const double *W, int64_t w_len, int S,
+                          int grad, double *Out, int64_t out_len);
+/* The cross-gradient kernel of the pathwise samples alone (launch_pw_crossgrad, launch_pw_finish): Out[s][i][d] = sum_j
+ * dk(z_i, x_j)/dz_d V[s][j] (S x m x ndim; in / out); V: S rows of ldv >= n.  No event discounts. */
+int gogp_test_pw_crossgrad(int device, const gogp_test_kparams *kparams, const double *Z, int64_t z_len, int64_t m,
+                           const double *X, int64_t x_len, int64_t n, const double *V, int64_t v_len, int64_t ldv, int S,
+                           double *Out, int64_t out_len);
 /* launch_cg_dots: the T dot products A[t] . B[t] and, by mode (0 plain, 1 |b|^2, 2 rho0, 3 p^T q, 4 |r|^2 and the freeze
  * test, 5 beta), the update of sc / st (in / out).  part (in / out): T x gogp_test_cg_dot_blocks(n); out (in / out, T;
  * NULL with length 0 except in mode 0) receives the dot products. */
