@@ -515,9 +515,16 @@ HOOK_SYMBOLS += [
                                    _dp, _i64]),
 ]
 
-#: the hook of the tile product of hessian.hip (tests/test_hessian_kernel.py; hessian.kmm_check)
+#: the hooks of the kernels of hessian.hip (tests/test_hessian_kernel.py, tests/test_hessian_kernels.py; hessian.*_check)
 HOOK_SYMBOLS += [
     ("gogp_test_hess_kmm", _ci, [_ci, _kpp, _ci, _ci, _i32p, _i32p, _dp, _i64, _i64, _i64, _dp, _i64, _i64, _dp, _i64]),
+    ("gogp_test_hess_pair", _ci, [_ci, _kpp, _ci, _ci, _i32p, _i32p, _ci, _i32p, _i32p, _dp, _i64, _dp, _i64, _i64, _i64,
+                                  _dp, _i64, _i64, _dp, _i64, _dp, _i64]),
+    ("gogp_test_hess_kvec", _ci, [_ci, _kpp, _ci, _ci, _i32p, _i32p, _dp, _i64, _dp, _i64, _i64, _i64, _dp, _i64, _i64]),
+    ("gogp_test_hess_matvec", _ci, [_ci, _dp, _i64, _dp, _i64, _i64, _i64, _ci, _dp, _i64]),
+    ("gogp_test_hess_dots", _ci, [_ci, _dp, _i64, _dp, _i64, _dp, _i64, _i64, _i64, _ci, _dp, _i64]),
+    ("gogp_test_hess_traces", _ci, [_ci, _dp, _i64, _ci, _dp, _i64, _i64, _i64, _i64, _i32p, _i64, _dp, _i64, _dp, _i64]),
+    ("gogp_test_hess_quad", _ci, [_ci, _dp, _i64, _i64, _dp, _i64, _i64, _i64, _dp, _i64, _dp, _i64]),
 ]
 
 #: the hooks of the kernels of pathwise.hip (tests/test_pathwise_kernels.py; pathwise.features_check, pathwise.crossgrad_check)

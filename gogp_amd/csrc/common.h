@@ -884,6 +884,16 @@ void launch_add_vec(hipStream_t s, double *a, const double *b, int64_t count);  
 // - Kinv_ij, from which the host forms sum_ij W_ij K_ab,ij for the second derivatives of two groups of one term; part:
 // npad / 64 * (npad / 64 + 1) / 2 * HESS_NMOM doubles of scratch.  periodic: the term's kind is GOGP_K_PERIODIC.
 // launch_hess_kvec: b_q (row q of b, ldb >= npad doubles) = K_q alpha, zero from row n on.
+// launch_hess_matvec: c_s (row s of c, ldc >= npad) [a] = sum_{b < n} M_s[a][b] alpha_b for a < npad (zero from row n on),
+// s < S, M_s at M + s * mstride (ldm).
+// launch_hess_dots: dots[s * (S + 1) + t] = b_s . c_t for s <= t < S (zero for t < s), dots[s * (S + 1) + S] = alpha . c_s
+// over the first n elements; b, c: S rows of ldv.
+// launch_hess_quad: out[0 .. 3] = alpha^T K^-1 alpha, |K^-1|_F^2, |alpha|^2, tr K^-1 from the stored half (j <= i < n) of
+// Kinv; part: npad / 64 * (npad / 64 + 1) / 2 * 4 doubles of scratch.
+// launch_hess_traces: out[p] = tr(A B) over the leading n x n for the npairs pairs p, B = slot pairs[2 p + 1] of M and A =
+// slot pairs[2 p] of M or, pairs[2 p] < 0, the symmetric K^-1 from its stored half; pairs on the device; HESS_TCHUNK pairs
+// per launch; part: min(npairs, HESS_TCHUNK) * (npad / 64)^2 doubles of scratch, reused by every launch.
+constexpr int HESS_TCHUNK = 64;
 void launch_hess_kmm(hipStream_t s, const DevParams *p, int ndim, bool periodic, int term, int nslot, const int *type, const int *dim,
                      const double *X, const double *Kinv, int64_t ld, int64_t n, int64_t npad, double *M, int64_t ldm,
                      int64_t mstride);
@@ -892,6 +902,14 @@ void launch_hess_pair(hipStream_t s, const DevParams *p, int ndim, bool periodic
                       int64_t ld, int64_t n, int64_t npad, double *part, double *out);
 void launch_hess_kvec(hipStream_t s, const DevParams *p, int ndim, bool periodic, int term, int nslot, const int *type, const int *dim,
                       const double *X, const double *alpha, int64_t n, int64_t npad, double *b, int64_t ldb);
+void launch_hess_matvec(hipStream_t s, const double *M, int64_t ldm, int64_t mstride, const double *alpha, int64_t n,
+                        int64_t npad, int S, double *c, int64_t ldc);
+void launch_hess_dots(hipStream_t s, const double *b, const double *c, int64_t ldv, const double *alpha, int64_t n, int S,
+                      double *dots);
+void launch_hess_quad(hipStream_t s, const double *Kinv, int64_t ld, const double *alpha, int64_t n, int64_t npad,
+                      double *part, double *out);
+void launch_hess_traces(hipStream_t s, const double *M, int64_t ldm, int64_t mstride, const double *Kinv, int64_t ld,
+                        int64_t n, int64_t npad, const int *pairs, int npairs, double *part, double *out);
 
 // pathwise.hip (gogp_pathwise_*): pathwise posterior samples.  Features phi_r(z) = am[r] cos(Om[r] . z + ph[r]), r < R (Om: R x
 // ndim), W: R x S row-major, 1 <= S <= CG_MAX_T.

@@ -406,6 +406,37 @@ void launch_hess_kvec(hipStream_t s, const DevParams *p, int ndim, bool periodic
                hess_x_lds(ndim), s, p, g, X, alpha, (long)n, b, (long)ldb);
 }
 
+void launch_hess_matvec(hipStream_t s, const double *M, int64_t ldm, int64_t mstride, const double *alpha, int64_t n,
+                        int64_t npad, int S, double *c, int64_t ldc) {
+  GOGP_KLAUNCH(hess_matvec_kernel, dim3((unsigned)(npad / 4), (unsigned)S), dim3(256), 0, s, M, (long)ldm, (long)mstride, alpha,
+               (long)n, c, (long)ldc);
+}
+
+void launch_hess_dots(hipStream_t s, const double *b, const double *c, int64_t ldv, const double *alpha, int64_t n, int S,
+                      double *dots) {
+  GOGP_KLAUNCH(hess_dots_kernel, dim3((unsigned)S, (unsigned)(S + 1)), dim3(256), 0, s, b, c, (long)ldv, alpha, (long)n, S,
+               dots);
+}
+
+void launch_hess_quad(hipStream_t s, const double *Kinv, int64_t ld, const double *alpha, int64_t n, int64_t npad,
+                      double *part, double *out) {
+  const int64_t nt = npad / 64, ntl = nt * (nt + 1) / 2;
+  GOGP_KLAUNCH(hess_quad_kernel, dim3((unsigned)ntl), dim3(256), 0, s, Kinv, (long)ld, alpha, (long)n, part);
+  GOGP_KLAUNCH(hess_sum_kernel, dim3(4), dim3(256), 0, s, (const double *)part, (long)ntl, 4L, 1L, out);
+}
+
+void launch_hess_traces(hipStream_t s, const double *M, int64_t ldm, int64_t mstride, const double *Kinv, int64_t ld,
+                        int64_t n, int64_t npad, const int *pairs, int npairs, double *part, double *out) {
+  const int64_t nt = npad / 64;
+  for (int p0 = 0; p0 < npairs; p0 += HESS_TCHUNK) {
+    const int np = std::min(HESS_TCHUNK, npairs - p0);
+    GOGP_KLAUNCH(hess_trdot_kernel, dim3((unsigned)(nt * nt), (unsigned)np), dim3(256), 0, s, M, (long)ldm, (long)mstride, Kinv,
+                 (long)ld, (long)n, (int)nt, pairs + 2 * p0, part);
+    GOGP_KLAUNCH(hess_sum_kernel, dim3((unsigned)np), dim3(256), 0, s, (const double *)part, (long)(nt * nt), 1L,
+                 (long)(nt * nt), out + p0);
+  }
+}
+
 }  // namespace gogp
 
 // ---- gogp_lml_hessian ------------------------------------------------------------------------------------------------------
@@ -462,7 +493,7 @@ extern "C" int gogp_lml_hessian(gogp_handle *h, double *H) {
   for (int a = 0; a < S; ++a)
     for (int b = a; b < S; ++b) tpairs.push_back(a), tpairs.push_back(b);
   for (int b = 0; b < S; ++b) tpairs.push_back(-1), tpairs.push_back(b);
-  const int NT = (int)tpairs.size() / 2, TCHUNK = 64;  // trace pairs per launch
+  const int NT = (int)tpairs.size() / 2;
 
   int rc = regression_kinv_alpha(h);
   if (rc != GOGP_OK) return rc;
@@ -475,7 +506,7 @@ extern "C" int gogp_lml_hessian(gogp_handle *h, double *H) {
     M = c.take<double>((size_t)S * mat);
     bv = c.take<double>((size_t)S * npad);
     cvv = c.take<double>((size_t)S * npad);
-    part = c.take<double>(std::max<size_t>((size_t)ntl * HESS_NMOM, (size_t)std::min(NT, TCHUNK) * nt * nt));
+    part = c.take<double>(std::max<size_t>((size_t)ntl * HESS_NMOM, (size_t)std::min(NT, HESS_TCHUNK) * nt * nt));
     res = c.take<double>((size_t)gpairs.size() * HESS_NMOM + 4 + (size_t)S * (S + 1) + NT);
     tp = c.take<int>(tpairs.size());
   };
@@ -516,20 +547,10 @@ extern "C" int gogp_lml_hessian(gogp_handle *h, double *H) {
                      dim.data() + a.first, b.n, type.data() + b.first, dim.data() + b.first, h->dX, h->alpha, h->bufA, ld, n,
                      npad, part, r_pair + k * HESS_NMOM);
   }
-  GOGP_KLAUNCH(hess_quad_kernel, dim3((unsigned)ntl), dim3(256), 0, s, (const double *)h->bufA, (long)ld,
-               (const double *)h->alpha, (long)n, part);
-  GOGP_KLAUNCH(hess_sum_kernel, dim3(4), dim3(256), 0, s, (const double *)part, (long)ntl, 4L, 1L, r_quad);
-  GOGP_KLAUNCH(hess_matvec_kernel, dim3((unsigned)(npad / 4), (unsigned)S), dim3(256), 0, s, (const double *)M, (long)npad,
-               (long)mat, (const double *)h->alpha, (long)n, cvv, (long)npad);
-  GOGP_KLAUNCH(hess_dots_kernel, dim3((unsigned)S, (unsigned)(S + 1)), dim3(256), 0, s, (const double *)bv,
-               (const double *)cvv, (long)npad, (const double *)h->alpha, (long)n, S, r_dots);
-  for (int p0 = 0; p0 < NT; p0 += TCHUNK) {
-    const int np = std::min(TCHUNK, NT - p0);
-    GOGP_KLAUNCH(hess_trdot_kernel, dim3((unsigned)(nt * nt), (unsigned)np), dim3(256), 0, s, (const double *)M, (long)npad,
-                 (long)mat, (const double *)h->bufA, (long)ld, (long)n, (int)nt, (const int *)(tp + 2 * p0), part);
-    GOGP_KLAUNCH(hess_sum_kernel, dim3((unsigned)np), dim3(256), 0, s, (const double *)part, (long)(nt * nt), 1L,
-                 (long)(nt * nt), r_tr + p0);
-  }
+  launch_hess_quad(s, h->bufA, ld, h->alpha, n, npad, part, r_quad);
+  launch_hess_matvec(s, M, npad, (int64_t)mat, h->alpha, n, npad, S, cvv, npad);
+  launch_hess_dots(s, bv, cvv, npad, h->alpha, n, S, r_dots);
+  launch_hess_traces(s, M, npad, (int64_t)mat, h->bufA, ld, n, npad, tp, NT, part, r_tr);
   std::vector<double> hres(nres);
   HIPCHK(h, hipMemcpyAsync(hres.data(), res, nres * sizeof(double), hipMemcpyDeviceToHost, s));
   HIPCHK(h, hipStreamSynchronize(s));

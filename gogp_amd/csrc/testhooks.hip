@@ -4,10 +4,12 @@
 #include <cstdlib>
 #include <cstring>
 #include <stdio.h>
+#include <algorithm>
 #include <vector>
 
 #include "common.h"
 #include "gemm_plan.h"  // for gogp_test_gemm_plan
+#include "hess_eval.h"  // HESS_NMOM, hess_group_max and the slot types of the hooks of hessian.hip
 #include "../../include/gogp_testhooks.h"
 
 struct gogp_handle;
@@ -2525,24 +2527,132 @@ extern "C" int gogp_test_kmm32(int device, const gogp_test_kparams *kparams, con
              });
 }
 
-// launch_hess_kmm (hessian.hip): the tile product M_q = K^-1 K_q alone, for one group of slots of one term
+// ---- the kernels of hessian.hip, through their product launchers (tests/test_hessian_kernel.py, test_hessian_kernels.py).
+// The kernels guard every read by n and write whole 64-row tiles up to npad, so the hooks hold the arrays to exactly that.
+namespace {
+// the parameter block and the term: no event discounts (gogp_lml_hessian refuses them)
+bool hess_term_ok(const gogp_test_kparams *kp, int term) {
+  return kp && gram_args_ok(kp, 1, 0, 0) && kp->nevents == 0 && term >= 0 && term < kp->nterms;
+}
+// a group of the term: 1 .. hess_group_max slots, known types, the period on a periodic term only, dimensions below ndim
+bool hess_group_ok(const gogp_test_kparams *kp, int term, int nslot, const int *type, const int *dim) {
+  const bool per = kp->kind[term] == GOGP_K_PERIODIC;
+  if (!type || !dim || nslot < 1 || nslot > hess_group_max(per)) return false;
+  for (int q = 0; q < nslot; ++q)
+    if (type[q] < HESS_VALUE || type[q] > HESS_PERIOD || (type[q] == HESS_PERIOD && !per) || dim[q] < 0 || dim[q] >= kp->ndim)
+      return false;
+  return true;
+}
+// n rows below npad, X, and where they are read alpha and the stored half of K^-1 (n rows of ld)
+bool hess_sizes_ok(int64_t n, int64_t npad) { return pad_ok(npad) && n >= 1 && n <= npad; }
+constexpr int HESS_HOOK_MAX_S = 1024;  // slots a hook takes: the grids' second dimension
+}  // namespace
+
+// launch_hess_kmm: the tile product M_q = K^-1 K_q alone, for one group of slots of one term
 extern "C" int gogp_test_hess_kmm(int device, const gogp_test_kparams *kparams, int term, int nslot, const int *type,
                                   const int *dim, const double *X, int64_t x_len, int64_t n, int64_t npad, const double *Kinv,
                                   int64_t k_len, int64_t ld, double *M, int64_t m_len) {
-  if (!kparams || !type || !dim || !X || !Kinv || !M || !gram_args_ok(kparams, 1, 0, 0)) return GOGP_EARG;
-  if (kparams->nevents != 0 || term < 0 || term >= kparams->nterms || nslot < 1 ||
-      nslot > (kparams->kind[term] == GOGP_K_PERIODIC ? 2 : 3))
-    return GOGP_EARG;
+  if (!X || !Kinv || !M || !hess_term_ok(kparams, term) || !hess_group_ok(kparams, term, nslot, type, dim)) return GOGP_EARG;
   const int ndim = kparams->ndim;
-  for (int q = 0; q < nslot; ++q)
-    if (type[q] < 0 || type[q] > 3 || dim[q] < 0 || dim[q] >= ndim) return GOGP_EARG;
-  if (!pad_ok(npad) || n < 1 || n > npad || ld < n || x_len < n * ndim || !covers(k_len, 0, ld, n, n, 1, 0) ||
+  if (!hess_sizes_ok(n, npad) || ld < n || x_len < n * ndim || !covers(k_len, 0, ld, n, n, 1, 0) ||
       m_len < (int64_t)nslot * npad * npad)
     return GOGP_EARG;
   const DevParams hp = to_dev(*kparams);
   return run(device, {rd(&hp, 1, sizeof hp), rd(X, x_len), rd(Kinv, k_len), io(M, m_len)}, [&](const Dev &d) {
     launch_hess_kmm(0, d.as<DevParams>(0), ndim, hp.kind[term] == GOGP_K_PERIODIC, term, nslot, type, dim, d[1], d[2], ld, n, npad, d[3], npad, npad * npad);
   });
+}
+
+// launch_hess_pair: the second-derivative sums of two groups of one term (hess_pair_kernel and its hess_sum_kernel)
+extern "C" int gogp_test_hess_pair(int device, const gogp_test_kparams *kparams, int term, int na, const int *type_a,
+                                   const int *dim_a, int nb, const int *type_b, const int *dim_b, const double *X,
+                                   int64_t x_len, const double *alpha, int64_t alpha_len, int64_t n, int64_t npad,
+                                   const double *Kinv, int64_t k_len, int64_t ld, double *part, int64_t part_len, double *out,
+                                   int64_t out_len) {
+  if (!X || !alpha || !Kinv || !part || !out || !hess_term_ok(kparams, term) ||
+      !hess_group_ok(kparams, term, na, type_a, dim_a) || !hess_group_ok(kparams, term, nb, type_b, dim_b))
+    return GOGP_EARG;
+  const int ndim = kparams->ndim;
+  if (!hess_sizes_ok(n, npad)) return GOGP_EARG;
+  const int64_t nt = npad / 64, ntl = nt * (nt + 1) / 2;
+  if (ld < n || x_len < n * ndim || alpha_len < n || !covers(k_len, 0, ld, n, n, 1, 0) || part_len < ntl * HESS_NMOM ||
+      out_len < HESS_NMOM)
+    return GOGP_EARG;
+  const DevParams hp = to_dev(*kparams);
+  return run(device, {rd(&hp, 1, sizeof hp), rd(X, x_len), rd(alpha, alpha_len), rd(Kinv, k_len), io(part, part_len),
+                      io(out, out_len)},
+             [&](const Dev &d) {
+               launch_hess_pair(0, d.as<DevParams>(0), ndim, hp.kind[term] == GOGP_K_PERIODIC, term, na, type_a, dim_a, nb,
+                                type_b, dim_b, d[1], d[2], d[3], ld, n, npad, d[4], d[5]);
+             });
+}
+
+// launch_hess_kvec: b_q = K_q alpha for one group
+extern "C" int gogp_test_hess_kvec(int device, const gogp_test_kparams *kparams, int term, int nslot, const int *type,
+                                   const int *dim, const double *X, int64_t x_len, const double *alpha, int64_t alpha_len,
+                                   int64_t n, int64_t npad, double *b, int64_t b_len, int64_t ldb) {
+  if (!X || !alpha || !b || !hess_term_ok(kparams, term) || !hess_group_ok(kparams, term, nslot, type, dim)) return GOGP_EARG;
+  const int ndim = kparams->ndim;
+  if (!hess_sizes_ok(n, npad) || x_len < n * ndim || alpha_len < n || !covers(b_len, 0, ldb, nslot, npad, 1, 0))
+    return GOGP_EARG;
+  const DevParams hp = to_dev(*kparams);
+  return run(device, {rd(&hp, 1, sizeof hp), rd(X, x_len), rd(alpha, alpha_len), io(b, b_len)}, [&](const Dev &d) {
+    launch_hess_kvec(0, d.as<DevParams>(0), ndim, hp.kind[term] == GOGP_K_PERIODIC, term, nslot, type, dim, d[1], d[2], n, npad,
+                     d[3], ldb);
+  });
+}
+
+// launch_hess_matvec: c_s = M_s alpha
+extern "C" int gogp_test_hess_matvec(int device, const double *M, int64_t m_len, const double *alpha, int64_t alpha_len,
+                                     int64_t n, int64_t npad, int S, double *c, int64_t c_len) {
+  if (!M || !alpha || !c || !hess_sizes_ok(n, npad) || S < 1 || S > HESS_HOOK_MAX_S) return GOGP_EARG;
+  if (m_len < (int64_t)S * npad * npad || alpha_len < n || c_len < (int64_t)S * npad) return GOGP_EARG;
+  return run(device, {rd(M, m_len), rd(alpha, alpha_len), io(c, c_len)}, [&](const Dev &d) {
+    launch_hess_matvec(0, d[0], npad, npad * npad, d[1], n, npad, S, d[2], npad);
+  });
+}
+
+// launch_hess_dots: b_s . c_t (s <= t) and alpha . c_s
+extern "C" int gogp_test_hess_dots(int device, const double *b, int64_t b_len, const double *c, int64_t c_len,
+                                   const double *alpha, int64_t alpha_len, int64_t ldv, int64_t n, int S, double *dots,
+                                   int64_t dots_len) {
+  if (!b || !c || !alpha || !dots || n < 1 || n > GR_NPAD_MAX || S < 1 || S > HESS_HOOK_MAX_S) return GOGP_EARG;
+  if (!covers(b_len, 0, ldv, S, n, 1, 0) || !covers(c_len, 0, ldv, S, n, 1, 0) || alpha_len < n ||
+      dots_len < (int64_t)S * (S + 1))
+    return GOGP_EARG;
+  return run(device, {rd(b, b_len), rd(c, c_len), rd(alpha, alpha_len), io(dots, dots_len)},
+             [&](const Dev &d) { launch_hess_dots(0, d[0], d[1], ldv, d[2], n, S, d[3]); });
+}
+
+// launch_hess_traces: tr(A B) for a list of pairs of slots (hess_trdot_kernel and its hess_sum_kernel, HESS_TCHUNK pairs a
+// launch)
+extern "C" int gogp_test_hess_traces(int device, const double *M, int64_t m_len, int S, const double *Kinv, int64_t k_len,
+                                     int64_t ld, int64_t n, int64_t npad, const int *pairs, int64_t pairs_len, double *part,
+                                     int64_t part_len, double *out, int64_t out_len) {
+  if (!M || !Kinv || !pairs || !part || !out || !hess_sizes_ok(n, npad) || S < 1 || S > HESS_HOOK_MAX_S) return GOGP_EARG;
+  if (pairs_len < 2 || pairs_len % 2 || pairs_len / 2 > (int64_t)HESS_HOOK_MAX_S * HESS_HOOK_MAX_S) return GOGP_EARG;
+  const int npairs = (int)(pairs_len / 2);
+  for (int p = 0; p < npairs; ++p)
+    if (pairs[2 * p] < -1 || pairs[2 * p] >= S || pairs[2 * p + 1] < 0 || pairs[2 * p + 1] >= S) return GOGP_EARG;
+  const int64_t nt = npad / 64;
+  if (ld < n || m_len < (int64_t)S * npad * npad || !covers(k_len, 0, ld, n, n, 1, 0) ||
+      part_len < (int64_t)std::min(npairs, HESS_TCHUNK) * nt * nt || out_len < npairs)
+    return GOGP_EARG;
+  return run(device, {rd(M, m_len), rd(Kinv, k_len), rd(pairs, pairs_len, sizeof(int)), io(part, part_len), io(out, out_len)},
+             [&](const Dev &d) {
+               launch_hess_traces(0, d[0], npad, npad * npad, d[1], ld, n, npad, d.as<int>(2), npairs, d[3], d[4]);
+             });
+}
+
+// launch_hess_quad: alpha^T K^-1 alpha, |K^-1|_F^2, |alpha|^2, tr K^-1 (hess_quad_kernel and its hess_sum_kernel)
+extern "C" int gogp_test_hess_quad(int device, const double *Kinv, int64_t k_len, int64_t ld, const double *alpha,
+                                   int64_t alpha_len, int64_t n, int64_t npad, double *part, int64_t part_len, double *out,
+                                   int64_t out_len) {
+  if (!Kinv || !alpha || !part || !out || !hess_sizes_ok(n, npad)) return GOGP_EARG;
+  const int64_t nt = npad / 64, ntl = nt * (nt + 1) / 2;
+  if (ld < n || !covers(k_len, 0, ld, n, n, 1, 0) || alpha_len < n || part_len < ntl * 4 || out_len < 4) return GOGP_EARG;
+  return run(device, {rd(Kinv, k_len), rd(alpha, alpha_len), io(part, part_len), io(out, out_len)},
+             [&](const Dev &d) { launch_hess_quad(0, d[0], ld, d[1], n, npad, d[2], d[3]); });
 }
 
 // launch_pw_features + launch_pw_finish (pathwise.hip): the feature product alone, value (grad == 0: Out S x m) or gradient

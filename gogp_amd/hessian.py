@@ -5,6 +5,8 @@ Laplace approximation over the hyperparameters (Rasmussen & Williams section 5.2
     laplace_evidence(gp, x)      covariance and standard errors of log theta^ and the evidence corrected for the width
                                  of the optimum -- host arithmetic on the Hessian
     kmm_check(...)               the tile product K^-1 dK alone (test hook gogp_test_hess_kmm)
+    pair_check, kvec_check, matvec_check, dots_check, traces_check, quad_check
+                                 the other kernels alone (test hooks gogp_test_hess_*)
 
 Functions of a module, not methods of GP: the handle is the same, the class keeps the reference's surface.
 """
@@ -79,3 +81,80 @@ def kmm_check(kp, term: int, types, dims, X: np.ndarray, n: int, npad: int, Kinv
     if rc != _lib.GOGP_OK:
         raise RuntimeError("gogp_test_hess_kmm: error %d" % rc)
     return M
+
+
+# ---- the other kernels of csrc/hessian.hip alone (tests/test_hessian_kernels.py).  Every wrapper copies its in / out arrays,
+# hands every array over whole with its length in elements and returns the copies as the launch left them.
+_I32P, _DP = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double)
+
+
+def _f(a, copy=False):
+    a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1)
+    return a.copy() if copy else a
+
+
+def _group(types, dims):
+    ty, dm = np.ascontiguousarray(types, dtype=np.int32), np.ascontiguousarray(dims, dtype=np.int32)
+    return ty, dm, (ty.size, ty.ctypes.data_as(_I32P), dm.ctypes.data_as(_I32P))
+
+
+def _hook(name, *args):
+    rc = getattr(_lib.hooks(), name)(*args)
+    if rc != _lib.GOGP_OK:
+        raise RuntimeError("%s: error %d" % (name, rc))
+
+
+def _a(a):
+    return (a.ctypes.data_as(_DP), a.size)
+
+
+def pair_check(kp, term: int, types_a, dims_a, types_b, dims_b, X, alpha, n: int, npad: int, Kinv, ld: int, part, out,
+               device: int = -1):
+    """launch_hess_pair (gogp_test_hess_pair): the HESS_NMOM second-derivative sums of the groups a and b of term ``term``
+    (csrc/hess_eval.h: hess_moments).  Returns (part, out): the lower 64-tiles' sums, rows of 25, and their totals."""
+    X, alpha, Kinv, part, out = _f(X), _f(alpha), _f(Kinv), _f(part, True), _f(out, True)
+    ka, kb = _group(types_a, dims_a), _group(types_b, dims_b)
+    _hook("gogp_test_hess_pair", device, ctypes.byref(kp), term, *ka[2], *kb[2], *_a(X), *_a(alpha), n, npad, *_a(Kinv), ld,
+          *_a(part), *_a(out))
+    return part, out
+
+
+def kvec_check(kp, term: int, types, dims, X, alpha, n: int, npad: int, b, ldb: int, device: int = -1) -> np.ndarray:
+    """launch_hess_kvec (gogp_test_hess_kvec): b[q] = dK / dlog(slot q) @ alpha; b: len(types) rows of ldb, returned flat."""
+    X, alpha, b = _f(X), _f(alpha), _f(b, True)
+    g = _group(types, dims)
+    _hook("gogp_test_hess_kvec", device, ctypes.byref(kp), term, *g[2], *_a(X), *_a(alpha), n, npad, *_a(b), ldb)
+    return b
+
+
+def matvec_check(M, alpha, n: int, npad: int, S: int, c, device: int = -1) -> np.ndarray:
+    """launch_hess_matvec (gogp_test_hess_matvec): c[s] = M[s] @ alpha on the leading n x n; M: S matrices of npad x npad,
+    c: S rows of npad, returned flat."""
+    M, alpha, c = _f(M), _f(alpha), _f(c, True)
+    _hook("gogp_test_hess_matvec", device, *_a(M), *_a(alpha), n, npad, S, *_a(c))
+    return c
+
+
+def dots_check(b, c, alpha, ldv: int, n: int, S: int, dots, device: int = -1) -> np.ndarray:
+    """launch_hess_dots (gogp_test_hess_dots): dots[s][t] = b_s . c_t (s <= t < S, zero below), dots[s][S] = alpha . c_s;
+    S rows of S + 1, returned flat."""
+    b, c, alpha, dots = _f(b), _f(c), _f(alpha), _f(dots, True)
+    _hook("gogp_test_hess_dots", device, *_a(b), *_a(c), *_a(alpha), ldv, n, S, *_a(dots))
+    return dots
+
+
+def traces_check(M, S: int, Kinv, ld: int, n: int, npad: int, pairs, part, out, device: int = -1):
+    """launch_hess_traces (gogp_test_hess_traces): out[p] = tr(A B), B = M[pairs[p][1]], A = M[pairs[p][0]] or (-1) the
+    symmetric Kinv from its stored half.  Returns (part, out)."""
+    M, Kinv, part, out = _f(M), _f(Kinv), _f(part, True), _f(out, True)
+    pr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1)
+    _hook("gogp_test_hess_traces", device, *_a(M), S, *_a(Kinv), ld, n, npad, pr.ctypes.data_as(_I32P), pr.size, *_a(part),
+          *_a(out))
+    return part, out
+
+
+def quad_check(Kinv, ld: int, alpha, n: int, npad: int, part, out, device: int = -1):
+    """launch_hess_quad (gogp_test_hess_quad): out = alpha^T Kinv alpha, |Kinv|_F^2, |alpha|^2, tr Kinv.  Returns (part, out)."""
+    Kinv, alpha, part, out = _f(Kinv), _f(alpha), _f(part, True), _f(out, True)
+    _hook("gogp_test_hess_quad", device, *_a(Kinv), ld, *_a(alpha), n, npad, *_a(part), *_a(out))
+    return part, out

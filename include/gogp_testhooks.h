@@ -673,6 +673,40 @@ int gogp_test_kmm32(int device, const gogp_test_kparams *kparams, const double *
 int gogp_test_hess_kmm(int device, const gogp_test_kparams *kparams, int term, int nslot, const int *type, const int *dim,
                        const double *X, int64_t x_len, int64_t n, int64_t npad, const double *Kinv, int64_t k_len, int64_t ld,
                        double *M, int64_t m_len);
+/* The other kernels of hessian.hip through their launchers (tests/test_hessian_kernels.py).  Groups, X, Kinv, n and npad
+ * as gogp_test_hess_kmm; a type 3 (the period) slot is refused on a term that is not periodic; alpha: n doubles at least.
+ * launch_hess_pair (hess_pair_kernel, hess_sum_kernel): out (in / out; 25 = HESS_NMOM doubles, csrc/hess_eval.h:
+ * hess_moments) = the second-derivative sums of the groups a and b of one term over the pairs j <= i < n, weighted with
+ * alpha_i alpha_j - Kinv_ij, pairs off the diagonal twice; part (in / out): npad / 64 * (npad / 64 + 1) / 2 rows of 25, one
+ * per lower 64-tile. */
+int gogp_test_hess_pair(int device, const gogp_test_kparams *kparams, int term, int na, const int *type_a, const int *dim_a,
+                        int nb, const int *type_b, const int *dim_b, const double *X, int64_t x_len, const double *alpha,
+                        int64_t alpha_len, int64_t n, int64_t npad, const double *Kinv, int64_t k_len, int64_t ld,
+                        double *part, int64_t part_len, double *out, int64_t out_len);
+/* launch_hess_kvec: b (in / out; nslot rows of ldb >= npad) [q][i] = sum_{j < n} K_q(x_i, x_j) alpha_j, zero for n <= i <
+ * npad. */
+int gogp_test_hess_kvec(int device, const gogp_test_kparams *kparams, int term, int nslot, const int *type, const int *dim,
+                        const double *X, int64_t x_len, const double *alpha, int64_t alpha_len, int64_t n, int64_t npad,
+                        double *b, int64_t b_len, int64_t ldb);
+/* launch_hess_matvec: c (in / out; S rows of npad) [s][a] = sum_{b < n} M_s[a][b] alpha_b, zero for n <= a < npad; M: S
+ * matrices of npad x npad, read on the leading n x n only.  1 <= S <= 1024. */
+int gogp_test_hess_matvec(int device, const double *M, int64_t m_len, const double *alpha, int64_t alpha_len, int64_t n,
+                          int64_t npad, int S, double *c, int64_t c_len);
+/* launch_hess_dots: dots (in / out; S rows of S + 1) [s][t] = b_s . c_t for s <= t < S, zero for t < s, [s][S] = alpha .
+ * c_s, over n elements; b, c: S rows of ldv >= n. */
+int gogp_test_hess_dots(int device, const double *b, int64_t b_len, const double *c, int64_t c_len, const double *alpha,
+                        int64_t alpha_len, int64_t ldv, int64_t n, int S, double *dots, int64_t dots_len);
+/* launch_hess_traces (hess_trdot_kernel, hess_sum_kernel; 64 pairs a launch): out (in / out; one per pair) [p] = tr(A B)
+ * over the leading n x n with B = matrix pairs[2 p + 1] of M (S of npad x npad) and A = matrix pairs[2 p] of M or, pairs[2 p]
+ * == -1, the symmetric Kinv from its stored half.  pairs_len = 2 x the number of pairs; an index outside [-1, S) / [0, S)
+ * is refused.  part (in / out): min(pairs, 64) x (npad / 64)^2, the tiles' sums of the LAST launch. */
+int gogp_test_hess_traces(int device, const double *M, int64_t m_len, int S, const double *Kinv, int64_t k_len, int64_t ld,
+                          int64_t n, int64_t npad, const int *pairs, int64_t pairs_len, double *part, int64_t part_len,
+                          double *out, int64_t out_len);
+/* launch_hess_quad (hess_quad_kernel, hess_sum_kernel): out (in / out; 4) = alpha^T Kinv alpha, |Kinv|_F^2, |alpha|^2, tr
+ * Kinv from the stored half; part (in / out): npad / 64 * (npad / 64 + 1) / 2 rows of 4. */
+int gogp_test_hess_quad(int device, const double *Kinv, int64_t k_len, int64_t ld, const double *alpha, int64_t alpha_len,
+                        int64_t n, int64_t npad, double *part, int64_t part_len, double *out, int64_t out_len);
 /* The feature product of the pathwise samples alone (pathwise.hip: launch_pw_features, launch_pw_finish), with the slabs
  * gogp_pathwise_eval would choose: Out[s][i] = sum_r amp[r] cos(Omega[r] . z_i + phase[r]) W[r][s] (grad == 0; S x m) or its
  * derivative in z_d (grad == 1; S x m x ndim).  Omega: R x ndim, W: R x S, Z: m x ndim; Out in / out. */
